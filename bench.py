@@ -5,11 +5,14 @@ A *step* is one full ``HessianQuantCalibrator(net, wrapped, loader, sequential=F
 .batching_quant_calib()`` -- the region the reference times (example/test_all.py:31-34) -- on a ViT-B/224 with
 seeded random weights and 32 seeded synthetic images that are resident in HBM before the clock starts.
 value = wrapped modules calibrated per second, whole job (74 modules per step, sharded over the ranks for N > 1).
+A plain run sets up, warms up, times the K steps and prints one JSON line; `--full` adds every other measurement
+(roofline, CPU baseline, untimed extras, ...); `--dump-outputs DIR` writes the intervals of the last timed step.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N
 """
 import argparse
+import copy
 import json
 import os
 import sys
@@ -68,6 +71,16 @@ def probe_shapes(net, wrapped, image):
     for h in hooks:
         h.remove()
     return shapes
+
+
+def dump_outputs(wrapped, out_dir):
+    """What a caller of batching_quant_calib() receives: the intervals installed on every wrapped module, as
+    out_dir/<module>.<attribute>.npy in float32."""
+    from ptq4vit_amd.utils.intervals import module_intervals
+    os.makedirs(out_dir, exist_ok=True)
+    for name, m in wrapped.items():
+        for attr, t in module_intervals(m).items():
+            np.save(os.path.join(out_dir, f"{name}.{attr}.npy"), t.numpy().astype(np.float32))
 
 
 def production_profile():
@@ -273,7 +286,7 @@ def cpu_baseline(calib=32, rounds=3, sample_images=4, backend="torch"):
 def cpu_full_deit_tiny(calib=4):
     """BASELINE.json config 0 on the CPU path, in full: DeiT-tiny/224, BasePTQ (cosine, 1 round), 4 calibration images --
     every wrapped module's step 2 through the numpy oracle on tensors captured by a CPU forward/backward of the same
-    network (capture time reported separately).  ~1 min of host time: run with `bench.py --cpu-full`, not by default."""
+    network (capture time reported separately).  ~1 min of host time: run with `bench.py --full --cpu-full`, not by default."""
     import contextlib
     import io
     from oracle.ptq4vit_oracle import ConvOracle, LinearOracle, MatMulOracle
@@ -343,7 +356,17 @@ def main():
                     help="images per capture pass of the timed steps (0 = batch_size = 4, the reference's passes)")
     ap.add_argument("--tune", default="", help="key=value,... engine tuning overrides (p4v_debug_set_tuning), experiments only")
     ap.add_argument("--variant", type=int, default=0, help="engine A/B switch word (p4v_debug_set_variant), experiments only: use with --no-roofline")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline (steady-state re-calibration, single-pass capture, roofline, "
+                         "untimed extras, both capture plans at N > 1, CPU baseline, top-1); a plain run only sets up, warms up and "
+                         "times the steps")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the intervals the last timed step calibrated, one DIR/<module>.<attribute>.npy (float32) each")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full and (args.cpu_full or args.dump_launches):
+        ap.error("--cpu-full and --dump-launches belong to measurements that only run with --full")
 
     if args.profile:
         args.search_streams, args.no_extras, args.no_cpu_baseline = 1, True, True
@@ -380,11 +403,14 @@ def main():
     import contextlib as _ctx, io as _io
     with _ctx.redirect_stdout(_io.StringIO()):       # (stdout carries the ONE JSON line and nothing else)
         wrapped = net_wrap.wrap_modules_in_net(net, PTQ4ViT)
+    # every fresh network is a copy of this wrapped, uncalibrated one: get_net(seed=0) + wrapping build the same values each
+    # time, and a device copy takes milliseconds where their host-side initialisation takes about a second per ViT-B
+    template = copy.deepcopy((net, wrapped))
     img = models.input_size(args.model)
     g = torch.Generator(device="cpu").manual_seed(0)
     images = torch.randn(args.calib, 3, img, img, generator=g).to(dev)
     loader = SyntheticLoader(images)
-    shapes = probe_shapes(net, wrapped, images[:1])
+    shapes = probe_shapes(net, wrapped, images[:1]) if args.full else None
 
     def calibrate(net_, wrapped_, search_streams=None, capture_batch=None):
         for m in wrapped_.values():
@@ -400,8 +426,7 @@ def main():
         return calibrate(net, wrapped, search_streams, capture_batch)
 
     def fresh_pair():
-        net_ = models.get_net(args.model, seed=0, device=dev)
-        return net_, net_wrap.wrap_modules_in_net(net_, PTQ4ViT)
+        return copy.deepcopy(template)
 
     def sync():
         torch.cuda.synchronize()
@@ -433,10 +458,12 @@ def main():
         sync()
         elapsed = time.time() - t0
         launches = engine.launch_counters(reset=True)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(pairs[-1][1], args.dump_outputs)
         del pairs
         # the same network object calibrated again and again (rounds 1-5 timed this): its capture graph needs no parameter copy
         steady_s = None
-        if not args.profile:
+        if args.full and not args.profile:
             one_step(); one_step()
             sync()
             t_s = time.time()
@@ -450,7 +477,7 @@ def main():
         elapsed = float(tt.item())
     # the same calibration with ONE capture pass over all images (opt-in `capture_batch_size`: not part of `value`)
     cal_big, big_s = None, None
-    if not args.profile:
+    if args.full and not args.profile:
         with quiet:
             one_step(capture_batch=args.calib)
             sync()
@@ -462,7 +489,7 @@ def main():
     value = n_mod * args.steps / elapsed
 
     roof = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # live HIP-event timing of the dominant kernels (the int8 sweeps) on their launch stream, over one more
         # step that is not part of `value` (every rank runs it: the step ends with a collective)
         engine.stats_reset()
@@ -535,7 +562,7 @@ def main():
 
     # ---- untimed extras (not part of `value`) ---------------------------------------------------------------------------
     eager_s = qf = None
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         # (a) a fresh network with the architecture's capture graph switched off (P4V_ARCH_GRAPHS=0): eight eager sub-batch passes,
         # what every fresh network cost until round 5 and what the first one of a process still costs
         with quiet:
@@ -579,7 +606,7 @@ def main():
     # rate the automatic choice was made on, and what tools/predict_scale.py predicted for this world size from one-GPU
     # measurements -- a first SCALE run needs no re-run to be interpreted
     capture_modes = predicted = None
-    if world > 1 and not args.profile:
+    if args.full and world > 1 and not args.profile:
         from ptq4vit_amd.utils import shard as _shard
         capture_modes = {"automatic_choice": getattr(cals[-1], "capture_mode", None), "a2a_gbps_per_peer_measured": _shard.a2a_rate_gbps()}
         for mode_name, flag in (("replicated", False), ("sharded", True)):
@@ -641,7 +668,7 @@ def main():
         roof["full_sweeps_without_pruning"] = {k: {q: v[q] for q in keep} for k, v in full.items()}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_model, threads, logical = _cpu_info()
         backend = "numpy" if args.cpu_numpy else "torch"
         if backend == "torch":
@@ -668,8 +695,9 @@ def main():
     # reference's seed-3 rule).  Untimed, after everything else.
     top1, top1_reason = None, ("no ImageNet and no pretrained weights in this environment (no network): set P4V_IMAGENET and P4V_WEIGHTS "
                                "to fill this through tools/eval_top1.py; parity evidence without them is interval parity on identical "
-                               "tensors + the reference's own quantised logits (tests/golden: mini ViT, DeiT-tiny/224)")
-    if rank == 0 and world == 1 and os.environ.get("P4V_IMAGENET") and os.environ.get("P4V_WEIGHTS"):
+                               "tensors + the reference's own quantised logits (tests/golden: mini ViT, DeiT-tiny/224)") if args.full \
+        else "not measured: runs with --full"
+    if args.full and rank == 0 and world == 1 and os.environ.get("P4V_IMAGENET") and os.environ.get("P4V_WEIGHTS"):
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import eval_top1
         del net, wrapped

@@ -7,7 +7,7 @@ tunes=$1; shift
 for kv in "$@"; do export "$kv"; done
 for t in $tunes; do
   arg=""; [ "$t" != "-" ] && arg="--tune $t"
-  python bench.py $arg --steps 6 --warmup 3 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > /tmp/ab6.json
+  python bench.py $arg --full --steps 6 --warmup 3 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > /tmp/ab6.json
   python - "$t" <<'PY'
 import sys, json
 d = json.loads(open("/tmp/ab6.json").read())

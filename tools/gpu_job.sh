@@ -11,7 +11,7 @@ for step in "$@"; do
   case $name in
     tests)   if [ -n "$arg" ]; then timeout 1500 python -m pytest tests -m gpu -x -q -k "$arg" 2>&1 | tail -15 | tee $O/tests_k.log
              else timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | tail -15 | tee $O/tests.log; fi ;;
-    bench)   timeout 900 python bench.py --steps ${arg:-10} --warmup 3 > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err
+    bench)   timeout 900 python bench.py --full --steps ${arg:-10} --warmup 3 > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err
              tail -1 $O/bench.json | python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['value'], d['ms_per_step'], d.get('breakdown'), d.get('first_calibration_s')); print({k:(v['launches'], round(v['ms'],1), round(v['frac'],3), {s:(q['launches'], round(q['avg_launch_ms']*1e3,1), round(q['frac'],3)) for s,q in v['by_stage'].items()}) for k,v in r.get('by_kernel',{}).items() if v}, r.get('all_int8_sweeps',{}).get('frac'), r.get('whole_search'), (d.get('cpu_baseline') or {}).get('value'))" ;;
     kstats1|kstats3|kstats4)
              n=${name#kstats}
@@ -27,7 +27,7 @@ for step in "$@"; do
              head -52 $O/bench_group${n}_kernel_stats.txt | cut -c1-170; tail -8 $O/bench_group${n}_kernel_stats.txt | cut -c1-200; rm -rf $O/profg$n ;;
     prodprof) # profile of the production step, joined with the engine's launch records (tools/prof_join.py); arg = output stem
              stem=${arg:-r6_production_by_stage}; T=/tmp/pp_$TAG; rm -rf $T; mkdir -p $T
-             ( cd /tmp && timeout 900 rocprofv3 --kernel-trace -d $T/trace -o t -- python $R/bench.py --profile --steps 3 --warmup 2 --dump-launches $T/launches.json > $O/prodprof_bench.json 2> $O/prodprof_bench.err )
+             ( cd /tmp && timeout 900 rocprofv3 --kernel-trace -d $T/trace -o t -- python $R/bench.py --profile --full --steps 3 --warmup 2 --dump-launches $T/launches.json > $O/prodprof_bench.json 2> $O/prodprof_bench.err )
              for pass in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY"; do
                tag=$(echo $pass | cut -d' ' -f1)
                ( cd /tmp && timeout 900 rocprofv3 --pmc $pass --kernel-trace --output-format csv -d $T/pmc_$tag -o p -- python $R/bench.py --profile --steps 1 --warmup 1 --no-roofline > $T/pmc_$tag.log 2>&1 )
