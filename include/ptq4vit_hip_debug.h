@@ -15,13 +15,16 @@ extern "C" {
 #endif
 
 /* A/B switches for measurements and kernel-vs-kernel agreement tests; never needed in production (default 0).
- * `variant` disables individual kernel paths (bit list in csrc/p4v_api.hip), `force_generic` routes every int8 sweep
- * through the generic kernel.  Process-wide, relaxed atomics: set them while no call is in flight. */
+ * `variant` selects reference kernel paths (bits 1, 2, 4, 2048, 32768, 65536, 131072, 524288, 1048576, 2097152, 4194304,
+ * 8388608, 134217728; list in csrc/p4v_api.hip), `force_generic` routes every int8 sweep through the generic kernel.  Any
+ * other bit selected a path that was measured and removed: P4V_ERR_INVALID.  Process-wide, relaxed atomics: set them while
+ * no call is in flight. */
 int p4v_debug_set_variant(int variant, int force_generic);
 /* Overrides of launch heuristics: key 0 / 1 / 2 / 3 = candidate groups of k_sweep6 / k_sweep2 / k_sweep2g / k_sweep7
  * (0 = cost model), key 4 = print the launch plans to stderr, key 5 = workgroup order of k_sweep7 + 1, key 6 = k_sweep6 prologue
- * of the cost model (0.1 us), keys 9-15 = slice sizes / tiers / thresholds of the pruned passes, key 12 = path switches for A/B runs (list in
- * csrc/p4v_api.hip: e.g. 8 read-backs by copy, 9 no per-score-block ranges, 11 the round-4 quantiser). */
+ * of the cost model (0.1 us), keys 9-15 = slice sizes / tiers / thresholds of the pruned passes, key 12 = reference path switches (7 cosine
+ * on the generic kernel, 9 no per-score-block ranges, 11 the round-4 quantiser, >= 16 k_bound timing ablations; 1, 2, 3, 5, 6, 8, 10
+ * and 12 selected removed paths: P4V_ERR_INVALID). */
 int p4v_debug_set_tuning(int key, int value);
 /* The row selection of the exact pruning alone (k_topk_rows; csrc/p4v_api.hip::slice_fill runs it on the per-sample metric
  * weight): for each of `segs` segments of `n` fp32 masses, d_mass [segs][n], the segment-local indices of the k heaviest

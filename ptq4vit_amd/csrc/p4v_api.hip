@@ -102,25 +102,18 @@ thread_local long g_memo_hits = 0, g_memo_misses = 0;
 //   [3] passes not eligible at all (score tables requested, cosine, fp32 planes, pruning switched off)
 std::atomic<long long> g_prune_cnt[4];
 // Kernel-variant switches for A/B measurements and kernel-vs-kernel agreement tests (p4v_debug_set_variant; 0 in
-// production).  One relaxed atomic word, read once per pass:
-//   4   no stationary-operand sweeps (everything on k_sweep2)      8   k_sweep4 instead of k_sweep5 (one candidate per pass)
-//   16  no k_sweep6 (stationary operand in LDS instead of registers)  32  k_sweep6 with 8 waves (two per SIMD)
-//   64  no folding of the twin's negative plane in the activation search   128  old candidate-group heuristic
-//   256 no k_sweep2g (one candidate per pass at large K)            512  no pass memoisation
-//   1024 no candidate-plane cache (every pass re-packs its candidate-expanded operand)
+// production).  One relaxed atomic word, read once per pass; every bit is a reference path a test or bench.py uses
+// (paths that lost their measurement were removed together with their bits -- p4v_debug_set_variant rejects those):
+//   1, 2: kernel debug flags (SweepParams::dbg)
+//   4   no stationary-operand sweeps (everything on k_sweep2)
 //   2048 cosine Linear searches on k_sweep2 (swapped operands, one GEMM per V block) instead of k_sweep6
-//   4096 quant_forward / folded-target GEMMs on the generic k_sweep instead of k_sweep2
-//   8192 no candidate groups for the generic k_sweep
-//   16384 k_sweep6 without the separate launch of the last, partial wave of workgroups
 //   32768 no k_sweep7 (K >= 1024 sweeps on k_sweep2 / k_sweep2g)      65536 no k_sweep8 (single-k-tile sweeps on k_sweep2)
+//   131072 no k_sos_split      524288 no k_sweep9      1048576 k_sweep9 wherever it applies (not only on padded tiles)
 //   2097152 post-GELU twin of k_sweep7 on two streamed planes (not the merged one)
 //   4194304 no exact candidate pruning (every candidate over every sample)   8388608 prune even where the slice's bounds are loose
-//   16777216 pruned passes with several score blocks: stage B1 on the hull of the winners (no synthetic candidate)
-//   33554432 the two fixed planes of a twin row operand from two k_pack launches (not k_pack_dual)
-//   67108864 pruned Linear passes never try the half-size slice first
 //   134217728 cross-check: every pruned pass is followed by the full sweep of the same pass, a differing selection is an error
-//   1, 2: kernel debug flags (SweepParams::dbg)
 //   bit 30: route every int8 sweep through the generic k_sweep
+constexpr int VARIANT_KEPT = 1 | 2 | 4 | 2048 | 32768 | 65536 | 131072 | 524288 | 1048576 | 2097152 | 4194304 | 8388608 | 134217728;
 std::atomic<int> g_variant_word{0};
 #define g_variant (g_variant_word.load(std::memory_order_relaxed) & 0x3fffffff)
 #define g_force_v1 ((g_variant_word.load(std::memory_order_relaxed) >> 30) & 1)
@@ -128,10 +121,10 @@ std::atomic<int> g_variant_word{0};
 std::atomic<int> g_tune[16];
 enum { TUNE_CG6 = 0, TUNE_CG2 = 1, TUNE_CG2G = 2, TUNE_CG7 = 3, TUNE_PRINT = 4, TUNE_ORDER7 = 5, TUNE_P6 = 6, TUNE_PLANE_GIB = 7, TUNE_EPI6W = 8,
        TUNE_LOOSE_PCT = 9, TUNE_SLICE_DIV = 10, TUNE_SLICE_SMALL = 11, TUNE_B1_PATH = 12, TUNE_TIER2 = 13, TUNE_TIER2_DIV = 14, TUNE_LOOSE_ROWS = 15 };   // LOOSE_ROWS: sample rows from which a module prunes on a 5 % slice share   // TIER2: 1 = no second slice tier; >= 2: minimum survivor count that triggers it   // SLICE_SMALL: rows of the slice a Linear tries first   // pruning: weight share below which a module keeps full sweeps (%); Linear slice = M / div   // EPI6W: 1 = fragment-order epilogue image also in the weight search   // P6: k_sweep6 prologue, 0.1 us; PLANE_GIB: plane budget per chunk (cache limit = half)
-// TUNE_B1_PATH (key 12) doubles as the A/B switch of the round-4 / round-5 paths: 1 / 2 the bound pass on k_sweep2 / k_sweep4,
-// 3 the bound pass on the sweep kernels, 5 padded 64-column planes, 6 no slice kernels, 7 cosine on the generic kernel,
-// 8 read-backs by copy (no mapped host memory), 9 no per-score-block candidate ranges, 10 k_slice_b instead of k_slice_b2,
-// 11 quant_fast1 instead of quant16_sat8, 12 launch geometry not planned for the host-known candidate range, >= 16 k_bound timing ablations
+// TUNE_B1_PATH (key 12) doubles as the switch of the reference paths the tests use: 7 cosine on the generic kernel, 9 no
+// per-score-block candidate ranges, 11 quant_fast1 instead of quant16_sat8, >= 16 k_bound timing ablations.  Values 1, 2, 3,
+// 5, 6, 8, 10 and 12 selected paths that were measured and removed; p4v_debug_set_tuning rejects them.
+inline bool tune_b1_removed(int v) { return v == 1 || v == 2 || v == 3 || v == 5 || v == 6 || v == 8 || v == 10 || v == 12; }
 inline int tune(int k) { return g_tune[k].load(std::memory_order_relaxed); }
 
 struct Group;
@@ -473,7 +466,7 @@ int q_sync(Ctx& c) {
 // and ~270 interval read-backs per ViT-B calibration).  One block per (device, stream) -- per MEMBER inside a group --, allocated
 // at first use (the calibrator's streams are persistent), never freed: 32 ints ([0,1] / [2,3] survivor ranges of the two tiers,
 // [4] weight share, [8..15] / [16..23] their per-score-block ranges) + MIR_SLOTS interval vectors of MIR_SLOT floats.  The null
-// stream has no block (calls from different threads would share it): it takes the copy path, as p4v_debug_set_tuning(12, 8) does.
+// stream has no block (calls from different threads would share it): it takes the copy path, as does a stream whose allocation failed.
 int* host_mirror(Ctx& c) {
     if (c.grp) return c.grp->mirrors[c.slot];
     if (!c.st) return nullptr;
@@ -628,8 +621,7 @@ template <typename T, bool TWIN> int launch_sweep_epi(Ctx& c, const SweepParams&
 
 // k_sweep2g: large K, column operand expanded, row operand invariant (weight search): two candidates per pass
 bool sweep2g_ok(const SweepParams& p) {
-    return p.b_cs != 0 && p.a_cs == 0 && p.ktiles >= 16 && (p.c1 - p.c0) >= 2 && p.o_bs == 0 && p.o_nbs == 0 &&
-           !(g_variant & 256);
+    return p.b_cs != 0 && p.a_cs == 0 && p.ktiles >= 16 && (p.c1 - p.c0) >= 2 && p.o_bs == 0 && p.o_nbs == 0;
 }
 
 template <bool TWIN> int launch_sweep2g_epi(Ctx& c, const SweepParams& p, int epi, int cgroups, const StatInfo* si) {
@@ -683,10 +675,10 @@ inline StatInfo stat_info(int kind, double macs, double alg, int gx, int gz, dou
     return StatInfo{kind, macs * g_exec_frac, alg * g_exec_frac, g_stage, gx, gz, bytes};
 }
 
-int launch_sweep4(Ctx& c, const Sweep3Params& p, int epi, int cgroups, bool pair) {
+int launch_sweep5(Ctx& c, const Sweep3Params& p, int epi, int cgroups) {
     if (c.dry) return 0;
-    const int per = pair ? 2 * cdiv(p.c1 - p.c0, 2 * cgroups) : cdiv(p.c1 - p.c0, cgroups);
-    const size_t lds = (size_t)p.ktiles * SW2_TILE + (size_t)(pair ? SW5_NP * 2 : SW4_NS) * SW2_TILE + (size_t)per * 8 * sizeof(float) * 2 + 256;
+    const int per = 2 * cdiv(p.c1 - p.c0, 2 * cgroups);
+    const size_t lds = (size_t)p.ktiles * SW2_TILE + (size_t)SW5_NP * 2 * SW2_TILE + (size_t)per * 8 * sizeof(float) * 2 + 256;
     dim3 grid(p.stiles * p.ttiles, 1, cgroups), block(512);
 #ifdef P4V_TRACE
     CHK(trace_attach(const_cast<Sweep3Params&>(p)));
@@ -694,22 +686,19 @@ int launch_sweep4(Ctx& c, const Sweep3Params& p, int epi, int cgroups, bool pair
     const StatInfo si = stat_info(5, (double)p.stiles * 128 * (double)p.ttiles * 128 * (double)p.ldk * (p.c1 - p.c0), g_alg_macs_cand * (p.c1 - p.c0),
                                   (int)grid.x, (int)grid.z, g_alg_bytes);
     const StatInfo* sp = &si;
-    if (pair) { P4V_EPI4(epi, CHK(enqueue(c, KERN_T(Sweep3Params, k_sweep5, E), grid, block, lds, p, sp)); break) }
-    else { P4V_EPI4(epi, CHK(enqueue(c, KERN_T(Sweep3Params, k_sweep4, E), grid, block, lds, p, sp)); break) }
+    P4V_EPI4(epi, CHK(enqueue(c, KERN_T(Sweep3Params, k_sweep5, E), grid, block, lds, p, sp)); break)
 #ifdef P4V_TRACE
     CHK(trace_dump(c, grid, p.ktiles));
 #endif
     return 0;
 }
 
-template <int KT, int RB>
+template <int KT>
 int launch_sweep6_kt(Ctx& c, const Sweep3Params& p, int epi, dim3 grid, size_t lds, const StatInfo* si) {
-    if constexpr (RB == 2) {       // cosine (plain = activation search, transposed = weight search): one wave per SIMD only
-        if (epi == EPI_COS) return enqueue(c, KERN_T(Sweep3Params, k_sweep6, EPI_COS, KT, 2), grid, dim3(256), lds, p, si);
-        if (epi == EPI_COS_T) return enqueue(c, KERN_T(Sweep3Params, k_sweep6, EPI_COS_T, KT, 2), grid, dim3(256), lds, p, si);
-    }
-    if (epi == EPI_COS || epi == EPI_COS_T) return fail(P4V_ERR_UNSUPPORTED, "k_sweep6: the cosine epilogue has no 8-wave instance");
-    P4V_EPI4(epi, return enqueue(c, KERN_T(Sweep3Params, k_sweep6, E, KT, RB), grid, dim3(512 / RB), lds, p, si))
+    // (cosine: plain = activation search, transposed = weight search)
+    if (epi == EPI_COS) return enqueue(c, KERN_T(Sweep3Params, k_sweep6, EPI_COS, KT, 2), grid, dim3(256), lds, p, si);
+    if (epi == EPI_COS_T) return enqueue(c, KERN_T(Sweep3Params, k_sweep6, EPI_COS_T, KT, 2), grid, dim3(256), lds, p, si);
+    P4V_EPI4(epi, return enqueue(c, KERN_T(Sweep3Params, k_sweep6, E, KT, 2), grid, dim3(256), lds, p, si))
 }
 
 // k_sweep6 (stationary operand in registers): K = 192 / 256 / 384 / 512 / 768 bytes -- the Linear layers of
@@ -733,7 +722,7 @@ int launch_sweep6(Ctx& c, const Sweep3Params& p, int epi, int cgroups, int nc_mo
     const double P = tune(TUNE_P6) > 0 ? 0.1 * tune(TUNE_P6) : 20.0, t_c = 0.196 * p.ktiles;        // prologue, one candidate of one tile
     auto waves = [](long wgs) { return (double)((wgs + 255) / 256); };
     int q_best = 0;
-    if (rem > 0 && full > 0 && !(g_variant & 16384) && lockstep(c, 2) <= 1) {
+    if (rem > 0 && full > 0 && lockstep(c, 2) <= 1) {
         double best = waves((long)tiles * cgroups) * (P + cdiv(nc, cgroups) * t_c) * 0.97;   // the uniform plan
         for (int q = 1; q <= std::min(nc, 12); ++q) {
             const double t = waves(full) * (P + nc * t_c) + waves((long)rem * q) * (P + cdiv(nc, q) * t_c);
@@ -757,11 +746,7 @@ int launch_sweep6(Ctx& c, const Sweep3Params& p, int epi, int cgroups, int nc_mo
 
 int launch_sweep6_part(Ctx& c, const Sweep3Params& p, int epi, int cgroups) {
     const int per = cdiv(p.c1 - p.c0, cgroups);
-    // 32-row blocks per wave: 2 = 4 waves, one per SIMD (default: bound by its own VALU + MFMA issue, LDS-light);
-    // 1 = 8 waves, two per SIMD (A/B variant 32: hides the VALU work but doubles the fragment reads -> LDS-bound;
-    // both measure 3.33 ms per fc1 search round on MI355X)
-    const int rb = ((g_variant & 32) && epi != EPI_COS && epi != EPI_COS_T) ? 1 : 2;
-    const int nw = 8 / rb;
+    const int nw = 4;       // waves per workgroup, one per SIMD
     const size_t lds = (size_t)3 * p.ktiles * 4096 + (size_t)(per + 1) * 2 * nw * sizeof(float) + (size_t)per * nw * sizeof(float) + 64 * sizeof(float) + 256;
     dim3 grid(p.ntile > 0 ? p.ntile : p.stiles * p.ttiles, 1, cgroups);
 #ifdef P4V_TRACE
@@ -773,15 +758,13 @@ int launch_sweep6_part(Ctx& c, const Sweep3Params& p, int epi, int cgroups) {
                                   share * g_alg_macs_cand * (p.c1 - p.c0), (int)grid.x, (int)grid.z, share * g_alg_bytes);
     const StatInfo* sp = &si;
     int r;
-#define P4V_KT(K) (rb == 2 ? launch_sweep6_kt<K, 2>(c, p, epi, grid, lds, sp) : launch_sweep6_kt<K, 1>(c, p, epi, grid, lds, sp))
     switch (p.ktiles) {
-        case 12: r = P4V_KT(12); break;
-        case 8: r = P4V_KT(8); break;
-        case 6: r = P4V_KT(6); break;
-        case 4: r = P4V_KT(4); break;
-        default: r = P4V_KT(3); break;
+        case 12: r = launch_sweep6_kt<12>(c, p, epi, grid, lds, sp); break;
+        case 8: r = launch_sweep6_kt<8>(c, p, epi, grid, lds, sp); break;
+        case 6: r = launch_sweep6_kt<6>(c, p, epi, grid, lds, sp); break;
+        case 4: r = launch_sweep6_kt<4>(c, p, epi, grid, lds, sp); break;
+        default: r = launch_sweep6_kt<3>(c, p, epi, grid, lds, sp); break;
     }
-#undef P4V_KT
     if (r) return r;
 #ifdef P4V_TRACE
     CHK(trace_dump(c, grid, p.ktiles));
@@ -818,19 +801,15 @@ bool sweep8_ok(const SweepParams& p, bool twin, int epi) {
            !(g_variant & 65536);
 }
 
-template <bool ROWS_FIXED, bool SKIP> int launch_sweep8_epi_s(Ctx& c, const SweepParams& p, int epi, int cgroups, const StatInfo* si) {
+// (no padding skip as in k_sweep2 -- wave parts without a valid element doing no MFMA / epilogue work: measured slower at 197
+// tokens, 4 of 32 parts padding: 459 vs 428 us, AND at the 144 tokens of a Swin window, 17 of 32 parts: 10.0 vs 9.3 ms per
+// module -- a single-k-tile candidate is paced by its ring step (DMA landing + barrier), not by the MFMAs and the epilogue it
+// would skip.  k_sweep8's SKIP parameter is always false.)
+template <bool ROWS_FIXED> int launch_sweep8_epi(Ctx& c, const SweepParams& p, int epi, int cgroups, const StatInfo* si) {
     const int per = cdiv(p.c1 - p.c0, cgroups);
     const size_t lds = (size_t)SW8_NS * SW2_TILE + (size_t)per * 8 * sizeof(float) * 2;
     dim3 grid(p.mtiles * p.ntiles, p.Z, cgroups), block(512);
-    P4V_EPI4(epi, return enqueue(c, KERN_T(SweepParams, k_sweep8, ROWS_FIXED, E, SKIP), grid, block, lds, p, si))
-}
-// The padding skip of k_sweep2 (wave parts without a valid element do no MFMA / epilogue work) is available here only as an A/B
-// switch (variant 262144): measured slower at 197 tokens (4 of 32 parts padding: 459 vs 428 us) AND at the 144 tokens of a Swin
-// window (17 of 32 parts: 10.0 vs 9.3 ms per module) -- a single-k-tile candidate is paced by its ring step (DMA landing +
-// barrier), not by the MFMAs and the epilogue it would skip.
-template <bool ROWS_FIXED> int launch_sweep8_epi(Ctx& c, const SweepParams& p, int epi, int cgroups, const StatInfo* si) {
-    const bool skip = (g_variant & 262144) != 0;
-    return skip ? launch_sweep8_epi_s<ROWS_FIXED, true>(c, p, epi, cgroups, si) : launch_sweep8_epi_s<ROWS_FIXED, false>(c, p, epi, cgroups, si);
+    P4V_EPI4(epi, return enqueue(c, KERN_T(SweepParams, k_sweep8, ROWS_FIXED, E, false), grid, block, lds, p, si))
 }
 
 // k_sweep7: large-K int8 sweep (both operands streaming, 256 x 256 workgroup tile)
@@ -1024,7 +1003,7 @@ int run_pass(Ctx& c, Pass& ps) {
     g_alg_bytes = 4.0 * ((double)ps.Mrows * ps.K * (ps.row_zs_shared ? 1 : ps.Z) + (double)ps.Ncols * ps.K * (ps.col_zs_shared ? 1 : ps.Z)) +
                   (ps.G ? 8.0 : 4.0) * (double)ps.Mrows * ps.Ncols * ps.Z;
     const int Kp = (int)rup(ps.K, 64 / esz);          // 64-byte k-tiles
-    // stationary-operand sweep (k_sweep4): Linear layers whose invariant operand tile (128 x K int8) fits in LDS
+    // stationary-operand sweeps (k_sweep6 / k_sweep5): Linear layers whose invariant operand tile (128 x K int8) fits in LDS
     const bool blocks64 = (ps.s_cs == 1 || ps.sb_div % 64 == 0) &&
                           (ps.j_mode == 0 || (ps.j_mode == 1 && (ps.nj == 1 || ps.j_div % 64 == 0)));
     // stage B1 (one candidate over all samples): k_bound -- rows = samples, columns = features of a plain [M][N] layer, whole
@@ -1033,14 +1012,12 @@ int run_pass(Ctx& c, Pass& ps) {
                        ps.o_bs == 0 && ps.o_nbs == 0 && ps.bias_axis == 0 && (ps.sb_mode == 0 || ps.sb_mode == 1) &&
                        (ps.j_mode == 0 || (ps.j_mode == 1 && (ps.nj == 1 || ps.j_div % 32 == 0))) &&
                        (ps.sb_mode != 1 || ps.s_cs == 1 || ps.sb_div % 32 == 0) && (ps.eq_n == 1 || ps.crange);
-    const bool b1_generic = bound || (g_stage == 2 && tune(TUNE_B1_PATH) == 1);    // (tuning 12=1: experiment, the bound pass on k_sweep2)
-    const bool stat_ok = !b1_generic && !ps.store_out && ps.i8 && !ps.twin && (ps.epi != EPI_COS || ps.cos6) && !g_force_v1 && !(g_variant & 4) && ps.Z == 1 &&
+    const bool stat_ok = !bound && !ps.store_out && ps.i8 && !ps.twin && (ps.epi != EPI_COS || ps.cos6) && !g_force_v1 && !(g_variant & 4) && ps.Z == 1 &&
                          ps.sb_mode == 1 && blocks64 && (ps.row.expanded != ps.col.expanded) &&
                          rup(ps.K, 64) <= 768 && ps.o_bs == 0 && ps.o_nbs == 0;
-    const bool b1_lds = g_stage == 2 && tune(TUNE_B1_PATH) == 2;        // experiment: the bound pass on k_sweep4 (stationary operand in LDS)
-    const bool regs6 = stat_ok && sweep6_supported(Kp / SW_BKB) && !(g_variant & 16) && !b1_lds;   // k_sweep6: stationary operand in registers
+    const bool regs6 = stat_ok && sweep6_supported(Kp / SW_BKB);   // k_sweep6: stationary operand in registers
     if (ps.cos6 && !regs6) return fail(P4V_ERR_UNSUPPORTED, "cosine pass planned for k_sweep6 does not qualify for it");
-    const bool pairs = stat_ok && !regs6 && !(g_variant & 8) && !b1_lds;                // k_sweep5: two candidates per pass
+    const bool pairs = stat_ok && !regs6;                // k_sweep5: two candidates per pass
     // per-score-block candidate ranges: the weight search on k_sweep6 (a streaming 64-row tile lies in one scale block = one score
     // block: blocks64); tuning 12 = 9 switches them off (A/B)
     const int* rblk = (ps.crange && ps.crange_blk && regs6 && !ps.row.expanded && ps.j_mode == 1 && ps.nj == ps.s_cs &&
@@ -1053,7 +1030,7 @@ int run_pass(Ctx& c, Pass& ps) {
     // k_sweep7 (large K): rows = samples, columns = output features of a plain [M][N] layer; features contiguous in
     // raw_out / raw_grad and a multiple of 32 (dwordx4 epilogue loads, whole 32-feature blocks), every 32-feature block
     // inside one scale / score block, exactly one operand candidate-expanded, the twin's second plane not expanded
-    const bool big7 = !b1_generic && !stat_ok && !ps.store_out && ps.i8 && (ps.epi != EPI_COS || ps.cos7) && !g_force_v1 && !(g_variant & 32768) && ps.Z == 1 &&
+    const bool big7 = !bound && !stat_ok && !ps.store_out && ps.i8 && (ps.epi != EPI_COS || ps.cos7) && !g_force_v1 && !(g_variant & 32768) && ps.Z == 1 &&
                       rup(ps.K, 64) >= 1024 && rup(ps.K, 64) % 256 == 0 && (long)ps.Mrows * ps.o_ms * 4 < (1L << 32) && ps.sb_mode == 1 && (ps.s_cs == 1 || ps.sb_div % 32 == 0) &&
                       (ps.j_mode == 0 || (ps.j_mode == 1 && (ps.nj == 1 || ps.j_div % 32 == 0))) &&
                       ps.row.expanded != ps.col.expanded && !(ps.twin && (ps.row.expanded || ps.row2.expanded)) &&
@@ -1069,11 +1046,11 @@ int run_pass(Ctx& c, Pass& ps) {
     // rows of the column operand's plane: the tile-padded count, except for the 64-column operands of the batched k_sweep2 passes
     // (attn.v: B = V, N = head_dim = 64 -- 100 candidate planes of 384 x 128 x 256 B = 1.26 GB per ViT-B module half of which was
     // padding: 630 us of k_pack and the stream of k_sweep2's stage A): k_sweep2 re-reads rows 0..63 for the tile's upper half
-    const bool fast_pre = !stat_ok && !(ps.store_out && (g_variant & 4096)) && ps.i8 && ps.epi != EPI_COS && !(g_force_v1) &&
+    const bool fast_pre = !stat_ok && ps.i8 && ps.epi != EPI_COS && !(g_force_v1) &&
                           (ps.sb_mode != 1 || ps.s_cs == 1 || ps.sb_div % 32 == 0) &&
                           (ps.j_mode == 0 || ps.j_mode == 2 || (ps.j_mode == 1 && (ps.nj == 1 || ps.j_div % 32 == 0)));
     const bool b64 = fast_pre && !big7 && !bound && ps.Z > 1 && !ps.col_zs_shared && ps.Ncols <= 64 && Kp / SW_BKB >= 2 && Kp / SW_BKB <= 15 &&
-                     !ps.store_out && tune(TUNE_B1_PATH) != 5;
+                     !ps.store_out;
     const int NpB = b64 ? 64 : Np;
     const long row_plane = (long)ps.Z * Mp * Kp * esz, col_plane = (long)ps.Z * NpB * Kp * esz;
     const long row_plane1 = ps.row_zs_shared ? (long)Mp * Kp * esz : row_plane;
@@ -1082,14 +1059,13 @@ int run_pass(Ctx& c, Pass& ps) {
     int chunk = (int)std::max<long>(1, std::min<long>(ps.eq_n, PLANE_BUDGET / std::max<long>(1, exp_plane)));
 
     const size_t mark = c.ws.off;
-    const size_t slack = stat_ok ? 4096 : 0;   // k_sweep4's ring keeps issuing a few tiles past the last candidate
+    const size_t slack = stat_ok ? 4096 : 0;   // the stationary sweeps' rings keep issuing a few tiles past the last candidate
     if (pairs && chunk > 1) chunk &= ~1;                  // chunks start on a candidate pair
     const int chunk_al = pairs ? ((chunk + 1) & ~1) : chunk;   // an odd count is padded to a whole pair
     // (planes above PLANE_CACHE_MAX are re-packed every pass: with three search streams and two searched operands per
     // module the cache would otherwise add up to 6 x PLANE_BUDGET of workspace on the 128-image configurations)
     PlaneCache* pc = (ps.cache && chunk >= ps.eq_n && !ps.store_out && ps.row.expanded != ps.col.expanded &&
-                      !(ps.twin && ps.row2.expanded) && exp_plane * (long)ps.eq_n <= PLANE_CACHE_MAX &&
-                      !(g_variant & 1024)) ? ps.cache : nullptr;
+                      !(ps.twin && ps.row2.expanded) && exp_plane * (long)ps.eq_n <= PLANE_CACHE_MAX) ? ps.cache : nullptr;
     if (pc && !pc->assigned) {
         pc->buf = c.ws.get_top((size_t)exp_plane * chunk_al + slack);
         pc->done = reinterpret_cast<unsigned char*>(c.ws.get_top((size_t)rup(ps.eq_n, 256)));
@@ -1102,13 +1078,13 @@ int run_pass(Ctx& c, Pass& ps) {
     const int MT = Mp / 64;
     const bool cosm = ps.epi == EPI_COS;
     // fast int8 sweep (k_sweep2): needs every 32-column group inside one scale block and one score block
-    const bool fast = !stat_ok && !(ps.store_out && (g_variant & 4096)) && ps.i8 && !cosm && !(g_force_v1) &&
+    const bool fast = !stat_ok && ps.i8 && !cosm && !(g_force_v1) &&
                       (ps.sb_mode != 1 || ps.s_cs == 1 || ps.sb_div % 32 == 0) &&
                       (ps.j_mode == 0 || ps.j_mode == 2 || (ps.j_mode == 1 && (ps.nj == 1 || ps.j_div % 32 == 0)));
     // cosine on k_sweep2 (same stream and ring; three sums per sample and wave in k_sweep's table layout, k_finish_cos unchanged)
     const bool fast_cos = cosm && !stat_ok && !big7 && ps.i8 && !ps.store_out && !g_force_v1 && tune(TUNE_B1_PATH) != 7 &&
                           (ps.sb_mode != 1 || ps.s_cs == 1 || ps.sb_div % 32 == 0);
-    // k_sweep4 table: [slabs of 64 stationary rows][groups of 32 streaming rows]
+    // k_sweep5 / k_sweep6 table: [slabs of 64 stationary rows][groups of 32 streaming rows]
     const bool a_search = ps.row.expanded;          // stationary = weights (col operand), streaming = activations
     const int s3_gw = 32;                           // streaming rows per wave (column group width of the table)
     const int s3_slabs = (a_search ? Np : Mp) / 64, s3_groups = (a_search ? Mp : Np) / s3_gw;
@@ -1134,7 +1110,7 @@ int run_pass(Ctx& c, Pass& ps) {
     // lanes of a load already read consecutive features)
     const bool epi6_on = regs6 && (a_search || ps.cos6 || tune(TUNE_EPI6W) == 1);
     const size_t epi6_bytes = epi6_on ? (size_t)s6_stiles * s6_ttiles * (256 * 64 * 8) : 0;
-    EpiCache* ec = (epi6_on && ps.ecache && (long)epi6_bytes <= PLANE_CACHE_MAX && !(g_variant & 1024)) ? ps.ecache : nullptr;
+    EpiCache* ec = (epi6_on && ps.ecache && (long)epi6_bytes <= PLANE_CACHE_MAX) ? ps.ecache : nullptr;
     if (ec && !ec->assigned) {
         ec->buf = c.ws.get_top(epi6_bytes);
         ec->assigned = true; ec->valid = false;
@@ -1146,7 +1122,7 @@ int run_pass(Ctx& c, Pass& ps) {
         pk.Rp = Rp; pk.Kp = Kp; pk.dst = buf;
         pk.Z = shared ? 1 : ps.Z;
         pk.C = op.expanded ? nc : 1;
-        pk.c_inner = (stat_ok && op.expanded) ? (pairs ? 2 : 1) : 0;   // k_sweep4 / k_sweep5 stream [row][candidate][K]
+        pk.c_inner = (stat_ok && op.expanded) ? (pairs ? 2 : 1) : 0;   // k_sweep6 / k_sweep5 stream [row][candidate][K] / [row][pair][K]
         if (regs6 && !op.expanded) pk.c_inner = 3;                     // k_sweep6: stationary operand in MFMA-fragment order
         if (bound) pk.c_inner = 3;                                     // k_bound: both operands (one candidate each) in fragment order
         if (op.expanded && pk.scales) pk.scales += (long)c0 * pk.sc_cs;
@@ -1200,7 +1176,7 @@ int run_pass(Ctx& c, Pass& ps) {
         both.pk.mode = PACK_TWIN_I8;
         both.pk.lo = ps.row2.pk.lo; both.pk.neg_scale = ps.row2.pk.neg_scale;
         CHK(pack(both, rowbuf, Mp, ps.row_zs_shared, 0, 1));
-    } else if (ps.twin && ps.i8 && !ps.row.expanded && !ps.row2.expanded && dual_pack_ok(ps.row.pk, ps.row2.pk) && !(g_variant & 33554432)) {
+    } else if (ps.twin && ps.i8 && !ps.row.expanded && !ps.row2.expanded && dual_pack_ok(ps.row.pk, ps.row2.pk)) {
         // both planes of the twin row operand from one read of the source (k_pack_dual)
         PackParams p1 = ps.row.pk, p2 = ps.row2.pk;
         p1.Rp = p2.Rp = Mp; p1.Kp = p2.Kp = Kp; p1.Z = p2.Z = ps.row_zs_shared ? 1 : ps.Z; p1.C = p2.C = 1;
@@ -1271,7 +1247,7 @@ int run_pass(Ctx& c, Pass& ps) {
                 const int epi6k = ps.cos6 ? (a_search ? EPI_COS : EPI_COS_T) : ps.epi;
                 if (ps.cos6) q.NG = cos6_Sp;
                 // what the host knows of the device-side range: the launch geometry is planned for the candidates that will run
-                const bool known = ps.crange && ps.host_hi > ps.host_lo && tune(TUNE_B1_PATH) != 12;
+                const bool known = ps.crange && ps.host_hi > ps.host_lo;
                 const int nc_known = known ? std::max(1, std::min(ps.host_hi, c0 + nc) - std::max(ps.host_lo, c0)) : nc;
                 const double P6 = tune(TUNE_P6) > 0 ? 0.125 * tune(TUNE_P6) : 25.0;
                 if (rblk && known && ps.host_rblk && ps.nj <= 4) {
@@ -1309,7 +1285,7 @@ int run_pass(Ctx& c, Pass& ps) {
             }
             const long wgs = (long)q.stiles * q.ttiles;
             const int cgroups = choose_cgroups(wgs, nc, q.ktiles, cu_slots(c, 256, 5), 30.0, 0.15);
-            CHK(launch_sweep4(c, q, ps.epi, cgroups, pairs));
+            CHK(launch_sweep5(c, q, ps.epi, cgroups));
             continue;
         }
         if (big7) {
@@ -1364,7 +1340,7 @@ int run_pass(Ctx& c, Pass& ps) {
         sp.dbg = g_variant & 3;
         sp.store = ps.store_out;
         int cgroups = 1;
-        if (!fast && !fast_cos && !(g_variant & 8192)) {
+        if (!fast && !fast_cos) {
             // generic sweep: 2 workgroups per CU; per k-tile step ~2.6 us with fp32 operands (8 x mfma_f32_32x32x2 per
             // 32x32 block), ~1.6 us on the int8 grid (measured on the patch-embedding search)
             const long wgs = (long)sp.mtiles * sp.ntiles * ps.Z;
@@ -1372,8 +1348,7 @@ int run_pass(Ctx& c, Pass& ps) {
         }
         if (fast || fast_cos) {
             const long wgs = (long)sp.mtiles * sp.ntiles * ps.Z;
-            cgroups = (g_variant & 128) ? (int)std::max<long>(1, std::min<long>(std::min(nc, 10), (2048 + wgs - 1) / wgs))
-                                        : choose_cgroups(wgs, nc, sp.ktiles, cu_slots(c, ps.twin ? 256 : 512, 9), ps.twin ? 40.0 : 25.0, ps.twin ? 0.45 : 0.40);
+            cgroups = choose_cgroups(wgs, nc, sp.ktiles, cu_slots(c, ps.twin ? 256 : 512, 9), ps.twin ? 40.0 : 25.0, ps.twin ? 0.45 : 0.40);
         }
         sp.bound = bound ? 1 : 0;
         if (bound) sp.dbg = tune(TUNE_B1_PATH) >= 16 ? (tune(TUNE_B1_PATH) >> 4) : 0;   // (tuning 12 = 16 / 32: k_bound timing ablations)
@@ -1407,7 +1382,7 @@ int run_pass(Ctx& c, Pass& ps) {
         CHK(launch_finish(c, fp));
     } else if (!cosm) {
         const int gdiv = stat_ok ? s3_gw : 32;
-        // k_sweep4 activation search (j_mode 0) sums the whole table; its columns are sample groups
+        // k_sweep5 / k_sweep6 activation search (j_mode 0) sums the whole table; its columns are sample groups
         // (k_sweep6 skips streaming tiles that are pure padding: their table entries are never written)
         const int fin_cols = stat_ok ? (a_search ? (regs6 ? 2 * cdiv(ps.Mrows, 64) : s3_groups) : cdiv(ps.Ncols, s3_gw))
                                      : fast ? cdiv(ps.Ncols, 32) : ps.Ncols;
@@ -1498,7 +1473,7 @@ int slice_fill(Ctx& c, SliceCache* sc, const SliceGeo& g, bool host_sync_ok) {
             // sample rows on a module prunes when its slice holds 5 % (Swin-B/384 x 128: search 4.75 -> 3.83 s; 25 %: no change,
             // 1 %: 3.81 s).  What survives is re-evaluated exactly as before: the selection does not depend on the threshold.
             float f = 1.0f;
-            int* hm = tune(TUNE_B1_PATH) == 8 ? nullptr : host_mirror(c);
+            int* hm = host_mirror(c);
             CHK(enqueue(c, KERN(MassFracParams, k_mass_fraction), dim3(1), dim3(1024), 0,
                         MassFracParams{sc->mass, zrows, sc->idx, g.segs, g.seg_rows, g.k, sc->frac, hm ? reinterpret_cast<float*>(hm + 4) : nullptr}));
             if (!hm) CHK(q_d2h(c, &f, sc->frac, sizeof f));
@@ -1578,7 +1553,7 @@ int prune_crosscheck_end(Ctx& c, const float* interval, int n, const std::vector
             return fail(P4V_ERR_INVALID, "exact candidate pruning selected another candidate than the full sweep (%s, output %d: %.9g vs %.9g)", what, i, (double)pruned[i], (double)full[i]);
     return 0;
 }
-// ---- stage A of a pruned MatMul B search in one kernel (k_slice_b: B quantised in the kernel, no candidate planes) ---------------
+// ---- stage A of a pruned MatMul B search in one kernel (k_slice_b2: B quantised in the kernel, no candidate planes) --------------
 // `a` is the stage-A pass run_pass_pruned built (row operand = the 16-row slices, dense [Z][16][K]; column operand = the whole B,
 // candidate-expanded); `SA` receives the scores [eq_n][nj].  Conditions: int8, head-wise scales (block = z % H on both the
 // quantiser and the output scales), K <= 256, N <= 208, no bias, a difference metric.
@@ -1589,15 +1564,14 @@ bool slice_b_ok(const Pass& a) {
            a.sb_div == a.j_div && a.s_cs == a.sb_div && !a.crange && a.scores_keep && a.no_select &&
            !b.conv && b.mode == PACK_SYM && b.blk_mode == 2 && b.blk_div == a.sb_div && b.scales && !a.col_zs_shared && !a.row_zs_shared &&
            rup(a.K, 64) <= 256 && a.Ncols <= 208 && (rup(a.K, 64) == 64 || a.Ncols <= 64) && a.o_ms == a.Ncols && a.o_ns == 1 &&
-           a.o_zs == (long)a.Mrows * a.Ncols && !a.o_bs && !a.o_nbs && !g_force_v1 && tune(TUNE_B1_PATH) != 6;
+           a.o_zs == (long)a.Mrows * a.Ncols && !a.o_bs && !a.o_nbs && !g_force_v1;
 }
 int run_slice_b(Ctx& c, Pass& a, float* SA) {
     const int Kp = (int)rup(a.K, 64), Z = a.Z;
     const size_t mark = c.ws.off;
     int8_t* A1 = c.ws.get<int8_t>((size_t)Z * 16 * Kp);
     int8_t* A2 = a.twin ? c.ws.get<int8_t>((size_t)Z * 16 * Kp) : nullptr;
-    const bool v2 = tune(TUNE_B1_PATH) != 10;           // k_slice_b2 (B in registers, waves deal the column blocks); 12 = 10: k_slice_b (A/B)
-    float* part = c.ws.get<float>((size_t)a.eq_n * Z * (v2 ? 4 : 1));
+    float* part = c.ws.get<float>((size_t)a.eq_n * Z * 4);      // one float per (candidate, batch entry, wave)
     float* S1 = a.S1_pre ? a.S1_pre : c.ws.get<float>((size_t)a.eq_n * a.s_cs);
     float* S2 = !a.twin ? nullptr : a.S2_pre ? a.S2_pre : c.ws.get<float>((size_t)a.eq_n * a.s_cs);
     if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", c.ws.off);
@@ -1623,41 +1597,30 @@ int run_slice_b(Ctx& c, Pass& a, float* SA) {
         kp.O = a.O; kp.Wt = a.G ? a.G : a.O; kp.wt_mode = a.wt_mode;
         kp.Z = Z; kp.M = a.Mrows; kp.K = a.K; kp.Kp = Kp; kp.N = a.Ncols; kp.C = a.eq_n; kp.part = part;
         const int nb = cdiv(a.Ncols, 16);
-        const size_t lds = (size_t)nb * 16 * (Kp + 4) * sizeof(float);
-        // k_slice_b: >= 1024 workgroups, >= 4 candidates each (one per wave); k_slice_b2: every wave runs every candidate of its
-        // workgroup, the prologue (B -> registers) is paid per workgroup: >= 512 workgroups of >= 10 candidates
-        // (k_slice_b2 keeps 3 workgroups per CU -- 2 with the twin's second accumulator set, 250 registers: whole rounds of 256 x that)
+        // every wave runs every candidate of its workgroup, the prologue (B -> registers) is paid per workgroup: >= 512 workgroups
+        // of >= 10 candidates (3 workgroups per CU -- 2 with the twin's second accumulator set, 250 registers: whole rounds of 256 x that)
         const int slots = std::max(8, 256 * (a.twin ? 2 : 3) / lockstep(c, 13));
-        int g2 = std::max(1, std::min(a.eq_n / 10, cdiv(std::max(1, 512 / lockstep(c, 13)), Z)));
+        int groups = std::max(1, std::min(a.eq_n / 10, cdiv(std::max(1, 512 / lockstep(c, 13)), Z)));
         // no mostly-empty last round -- where the rounds are few (ViT: 384 batch entries; with tens of thousands of them, Swin's
         // windows, the tail does not matter and more groups only repeat the prologue)
-        while ((long)Z * g2 < 4L * slots && g2 < a.eq_n / 10 && ((long)Z * g2) % slots != 0 && ((long)Z * g2) % slots < slots * 3 / 4) ++g2;
-        if (tune(TUNE_CG2) > 0) g2 = std::max(1, std::min(a.eq_n, tune(TUNE_CG2)));
-        const int groups = v2 ? g2 : std::max(1, std::min(a.eq_n / 4, cdiv(std::max(1, 1024 / lockstep(c, 13)), Z)));
+        while ((long)Z * groups < 4L * slots && groups < a.eq_n / 10 && ((long)Z * groups) % slots != 0 && ((long)Z * groups) % slots < slots * 3 / 4) ++groups;
+        if (tune(TUNE_CG2) > 0) groups = std::max(1, std::min(a.eq_n, tune(TUNE_CG2)));
         const dim3 grid(Z, groups), block(256);
-        const float qbias = (v2 && b.lo == -128 && b.hi == 127 && tune(TUNE_B1_PATH) != 11) ? cvt_bias(c) : 0.0f;   // 12 = 11: quant_fast1 in k_slice_b2 (A/B)
+        const float qbias = (b.lo == -128 && b.hi == 127 && tune(TUNE_B1_PATH) != 11) ? cvt_bias(c) : 0.0f;   // 12 = 11: quant_fast1 (A/B)
         const StatInfo si{13, 16.0 * nb * 16 * Kp * Z * a.eq_n * (a.twin ? 2 : 1), (double)a.Mrows * a.Ncols * a.K * Z * a.eq_n, g_stage, Z, groups,
                           4.0 * ((double)a.Mrows * a.K * Z + (double)a.Ncols * a.K * Z) + (a.G ? 8.0 : 4.0) * (double)a.Mrows * a.Ncols * Z};
         const StatInfo* sp = &si;
         int r_ = 0;
-        if (v2) {
-            SliceB2Params kp2{kp, qbias};
+        SliceB2Params kp2{kp, qbias};
 #define P4V_LAUNCH_SB2(TW, KTM, NBW)                                                                                                  \
-            P4V_EPI4(a.epi, r_ = (qbias != 0.0f) ? enqueue(c, KERN_T(SliceB2Params, k_slice_b2, TW, KTM, NBW, E, true), grid, block, 0, kp2, sp)   \
-                                                 : enqueue(c, KERN_T(SliceB2Params, k_slice_b2, TW, KTM, NBW, E, false), grid, block, 0, kp2, sp); break)
-            if (Kp == 64) { if (a.twin) { P4V_LAUNCH_SB2(true, 1, 4) } else { P4V_LAUNCH_SB2(false, 1, 4) } }
-            else { if (a.twin) { P4V_LAUNCH_SB2(true, 4, 1) } else { P4V_LAUNCH_SB2(false, 4, 1) } }
+        P4V_EPI4(a.epi, r_ = (qbias != 0.0f) ? enqueue(c, KERN_T(SliceB2Params, k_slice_b2, TW, KTM, NBW, E, true), grid, block, 0, kp2, sp)   \
+                                             : enqueue(c, KERN_T(SliceB2Params, k_slice_b2, TW, KTM, NBW, E, false), grid, block, 0, kp2, sp); break)
+        if (Kp == 64) { if (a.twin) { P4V_LAUNCH_SB2(true, 1, 4) } else { P4V_LAUNCH_SB2(false, 1, 4) } }
+        else { if (a.twin) { P4V_LAUNCH_SB2(true, 4, 1) } else { P4V_LAUNCH_SB2(false, 4, 1) } }
 #undef P4V_LAUNCH_SB2
-        } else {
-#define P4V_LAUNCH_SB(TW, KTM, NBM) P4V_EPI4(a.epi, r_ = enqueue(c, KERN_T(SliceBParams, k_slice_b, TW, KTM, NBM, E), grid, block, lds, kp, sp); break)
-            if (Kp == 64) { if (a.twin) { P4V_LAUNCH_SB(true, 1, 13) } else { P4V_LAUNCH_SB(false, 1, 13) } }
-            else { if (a.twin) { P4V_LAUNCH_SB(true, 4, 4) } else { P4V_LAUNCH_SB(false, 4, 4) } }
-#undef P4V_LAUNCH_SB
-        }
         if (r_) return r_;
     }
-    const int pw = v2 ? 4 : 1;                          // floats per (candidate, batch entry): one per wave of k_slice_b2
-    FinishParams fp{part, (long)Z * pw, (long)pw, pw, 1, Z, pw, a.eq_n, a.j_mode, std::max(1, a.j_div), a.nj, a.norm, SA, nullptr};
+    FinishParams fp{part, (long)Z * 4, 4L, 4, 1, Z, 4, a.eq_n, a.j_mode, std::max(1, a.j_div), a.nj, a.norm, SA, nullptr};
     CHK(launch_finish(c, fp));
     c.ws.off = mark;
     return 0;
@@ -1672,7 +1635,7 @@ bool slice_a_ok(const Pass& a) {
            !r.conv && r.mode == PACK_SYM && r.blk_mode == 2 && r.blk_div == a.sb_div && r.scales && r.s_k == 1 && r.s_r == a.K &&
            r.zdiv > 0 && r.s_z == (long)a.Mrows * a.K && r.s_z2 == (long)r.zdiv * a.Mrows * a.K && a.Mrows == 16 &&
            !a.col_zs_shared && !a.row_zs_shared && a.K <= 64 && a.Ncols <= 208 && a.o_ms == a.Ncols && a.o_ns == 1 &&
-           a.o_zs == (long)a.Mrows * a.Ncols && !a.o_bs && !a.o_nbs && !g_force_v1 && tune(TUNE_B1_PATH) != 6;
+           a.o_zs == (long)a.Mrows * a.Ncols && !a.o_bs && !a.o_nbs && !g_force_v1;
 }
 int run_slice_a(Ctx& c, Pass& a, float* SA) {
     const int Z = a.Z, nb = cdiv(a.Ncols, 16);
@@ -1754,10 +1717,10 @@ int run_pass_pruned_impl(Ctx& c, Pass& ps) {
     // A Linear first tries a QUARTER of the slice: the M/64 (at least 128) heaviest samples -- in a ViT the class-token rows, one
     // per image of 197+ tokens, are among them -- hold > 97 % of the weight in every layer but qkv, and stage A costs in proportion
     // to the slice.  Measured (ViT-B/224 x 32, one box): full slice 155.4 ms per calibration, 256 rows 151.2, 128 rows 148.8,
-    // 64 rows 148.6 (variant 67108864: always the full slice; p4v_debug_set_tuning(11, rows) overrides the size)
+    // 64 rows 148.6 (p4v_debug_set_tuning(11, rows) overrides the size)
     const int k_cap = k;
     if (sc->k_eff > 0) k = sc->k_eff;
-    else if (lin && ps.scache && ps.host_sync_ok && !c.dry && k_cap >= 512 && !(g_variant & (8388608 | 67108864)))
+    else if (lin && ps.scache && ps.host_sync_ok && !c.dry && k_cap >= 512 && !(g_variant & 8388608))
         k = tune(TUNE_SLICE_SMALL) > 0 ? std::min(tune(TUNE_SLICE_SMALL), k_cap)
                                        : (int)std::min<long>(std::max<long>(128, rup(ps.Mrows / 64, 64)), k_cap / 2);
     SliceGeo geo{lin, segs, seg_rows, k, ps.Ncols, ps.K, ps.O, ps.G, ps.wt_mode, ps.o_ms, ps.row.pk.src, ps.row.pk.s_r, ps.row.pk.s_k,
@@ -1819,7 +1782,7 @@ int run_pass_pruned_impl(Ctx& c, Pass& ps) {
     a.ecache = nullptr; a.scores_keep = SA; a.no_select = true;
     a.S1_pre = S1s; a.S2_pre = S2s; a.s_ready = false;
     // several score blocks whose entries of the candidate table are exactly one row: stage B1 on ONE synthetic candidate
-    const bool virt = ps.nj > 1 && ps.cand_off == 0 && ps.cand_js * ps.nj == ps.cand_cs && ps.cand_cs <= 4096 && !(g_variant & 16777216);
+    const bool virt = ps.nj > 1 && ps.cand_off == 0 && ps.cand_js * ps.nj == ps.cand_cs && ps.cand_cs <= 4096;
     PruneParams pp{SA, SB, ps.eq_n, ps.nj, prune_margin(), r1, r1, virt ? 1 : 0, best_idx, ps.cands, ps.cand_cs, ps.cand_js, ps.cand_off, vrow};
     g_stage = 1;
     { const int r_ = slice_b_ok(a) ? run_slice_b(c, a, SA) : slice_a_ok(a) ? run_slice_a(c, a, SA) : run_pass(c, a); g_stage = 0; if (r_) return r_; }
@@ -1835,17 +1798,17 @@ int run_pass_pruned_impl(Ctx& c, Pass& ps) {
         swap(b1.s1.x); swap(b1.s1.y); swap(b1.s2.x); swap(b1.s2.y);
         b1.cands = vrow;
     } else b1.crange = r1;
-    // ONE candidate per score block over all samples: the kernel built for that (k_bound; tuning 12=3 keeps the sweep kernels).
+    // ONE candidate per score block over all samples: the kernel built for that (k_bound).
     // Its totals are summed in another order than the sweeps', so from here on nothing may depend on stage B1's numbers but the
     // bound: the selections below are either "the only survivor of every block" (no totals involved) or come from stage B2,
     // which always re-evaluates stage B1's candidates together with the other survivors.  The candidate's plane is packed for
     // this pass (one candidate: ~12 us) instead of being read from the module's plane, whose layout belongs to its sweep kernel.
-    if (lin && ps.i8 && !ps.twin && (virt || ps.nj == 1) && tune(TUNE_B1_PATH) != 3) { b1.bound_kernel = true; b1.cache = nullptr; b1.ecache = nullptr; }
+    if (lin && ps.i8 && !ps.twin && (virt || ps.nj == 1)) { b1.bound_kernel = true; b1.cache = nullptr; b1.ecache = nullptr; }
     g_stage = 2;
     { const int r_ = run_pass(c, b1); g_stage = 0; if (r_) return r_; }
     // the survivors, and -- when there are none besides stage B1's candidates -- the pass's selection from its totals
     pp.r_out = r2; pp.rblk = rblk2;
-    int* hm = (ps.host_sync_ok && !c.dry && tune(TUNE_B1_PATH) != 8) ? host_mirror(c) : nullptr;
+    int* hm = (ps.host_sync_ok && !c.dry) ? host_mirror(c) : nullptr;
     pp.r_host = hm; pp.rblk_host = hm ? hm + MIR_RB1 : nullptr;
     int hblk[2 * MIR_BLK] = {};                             // host copy of the per-block ranges stage A2 / B2 run on (nj <= MIR_BLK)
     int hlo = 0, hhi = 0;
@@ -2064,7 +2027,7 @@ int run_sos_split_pruned_impl(Ctx& c, SosSplitJob& j) {
 // is a deterministic function of the counterpart's CURRENT interval only.  Rounds 2-3 often see an interval that
 // was already evaluated (the alternation has converged): the pass would recompute, bit for bit, the selection it
 // produced before.  Such a pass is skipped and its recorded output restored.  Exact by construction (the kernels
-// are deterministic); disabled when the caller asks for score tables, with desc.reserved bit 1, or P4V variant 512.
+// are deterministic); disabled when the caller asks for score tables, or with desc.reserved bit 1.
 struct PassMemo {
     struct Entry { std::vector<float> in, out; };
     std::vector<Entry> entries;
@@ -2097,7 +2060,7 @@ int write_dev(Ctx& c, float* d, const std::vector<float>& h) {
 // binds the interval vectors of one *_impl call (the ones its pass memo reads back) to the stream's mapped block
 struct MirrorScope {
     MirrorScope(Ctx& c, bool on, const float* a, const float* b = nullptr, const float* d3 = nullptr) {
-        float* base = (on && !c.dry && tune(TUNE_B1_PATH) != 8) ? reinterpret_cast<float*>(host_mirror(c)) : nullptr;
+        float* base = (on && !c.dry) ? reinterpret_cast<float*>(host_mirror(c)) : nullptr;
         const float* devs[MIR_SLOTS] = {a, b, d3};
         for (int i = 0; i < MIR_SLOTS; ++i)
             g_mir[i] = IvMirror{(base && devs[i]) ? devs[i] : nullptr, base ? base + MIR_HDR + i * MIR_SLOT : nullptr, false, 0};
@@ -2243,7 +2206,7 @@ int linear_impl(const p4v_linear_desc* d, const float* W, const float* bias, con
         fp.nj = 1; fp.store_out = fwd_out;
         return run_pass(c, fp);
     }
-    const bool memo_on = sg.full() && !c.dry && !scores_out && !best_out && !(d->reserved & 2) && !(g_variant & 512);
+    const bool memo_on = sg.full() && !c.dry && !scores_out && !best_out && !(d->reserved & 2);
     PassMemo memo_w, memo_a;
     MirrorScope mirrors(c, memo_on, w_iv, a_iv);
     PlaneCache plane_w, plane_a;
@@ -2259,7 +2222,7 @@ int linear_impl(const p4v_linear_desc* d, const float* W, const float* bias, con
     // slabs of k_finish_cos's table.  Otherwise (K > 768, blocks that are not whole slabs, variant 2048): k_sweep2 on the swapped
     // operands, one GEMM per V block.
     const bool cos6 = cosm && i8 && !twin && !general && nH == 1 && nA == 1 && (nV == 1 || crb_rows % 64 == 0) &&
-                      sweep6_supported((int)(rup(K, 64) / 64)) && !(g_variant & (4 | 16 | 2048)) && !g_force_v1;
+                      sweep6_supported((int)(rup(K, 64) / 64)) && !(g_variant & (4 | 2048)) && !g_force_v1;
     // ... and on k_sweep7 for K >= 1024 (fc2): 128-feature slabs; the conditions are run_pass's for that kernel
     const bool cos7 = cosm && i8 && !twin && !general && nH == 1 && nA == 1 && (nV == 1 || crb_rows % 128 == 0) && !cos6 &&
                       rup(K, 64) >= 1024 && rup(K, 64) % 256 == 0 && N % 32 == 0 && (long)M * N * 4 < (1L << 32) &&
@@ -2391,7 +2354,7 @@ int linear_impl(const p4v_linear_desc* d, const float* W, const float* bias, con
                 ps.j_mode = 0;
                 ps.norm = 1.0 / ((double)d->tokens * N);
                 ps.prunable = !(d->reserved & 8); ps.scache = &slice; ps.scache2 = &slice2; ps.host_sync_ok = memo_a_on;
-                if (twin && wt_mode <= 1 && !(g_variant & 64)) {
+                if (twin && wt_mode <= 1) {
                     // Twin activation search: the negative-range plane and the weights are candidate-invariant, so
                     // their product is folded into the target once (U = raw_out - bias - s_neg*s_w*(x_neg . W_q))
                     // and the sweep runs on the positive-range plane alone: half the MFMA work of this pass.
@@ -2535,7 +2498,7 @@ int matmul_impl(const p4v_matmul_desc* d, const float* A, const float* B, const 
         fp.nj = 1; fp.store_out = fwd_out;
         return run_pass(c, fp);
     }
-    const bool memo_on = sg.full() && !c.dry && !scores_out && !best_out && !(d->reserved & 2) && !(g_variant & 512);
+    const bool memo_on = sg.full() && !c.dry && !scores_out && !best_out && !(d->reserved & 2);
     PassMemo memo_A, memo_B;
     MirrorScope mirrors(c, memo_on, A_iv, B_iv, d->sos ? split : nullptr);
     PlaneCache plane_A, plane_B;
@@ -2760,7 +2723,7 @@ int conv_impl(const p4v_conv_desc* d, const float* W, const float* bias, const f
         }
     };
 
-    const bool memo_on = sg.full() && !c.dry && !scores_out && !best_out && !(d->reserved & 2) && !(g_variant & 512);
+    const bool memo_on = sg.full() && !c.dry && !scores_out && !best_out && !(d->reserved & 2);
     PassMemo memo_w, memo_a;
     MirrorScope mirrors(c, memo_on, w_iv, a_iv);
     PlaneCache plane_w, plane_a;
@@ -2982,7 +2945,7 @@ int p4v_calibrate_group(p4v_group_job* jobs, int32_t n_jobs, void* stream, void*
     Group g;
     g.st = (hipStream_t)stream; g.n = n_jobs;
     g.q.resize(n_jobs); g.state.assign(n_jobs, 0); g.mirrors.resize(n_jobs);
-    for (int i = 0; i < n_jobs; ++i) g.mirrors[i] = tune(TUNE_B1_PATH) == 8 ? nullptr : group_mirror(g.st, dev, i);
+    for (int i = 0; i < n_jobs; ++i) g.mirrors[i] = group_mirror(g.st, dev, i);
     g.stat_on = g_stat_on;
     g.stat_recs = g_stat_on ? &g_stat_recs : nullptr;
     g.inputs_ready = (hipEvent_t)inputs_ready_event;
@@ -3281,12 +3244,14 @@ int p4v_prune_counters(int64_t* out4, int reset) {
 
 int p4v_debug_set_variant(int variant, int force_generic) {
     if (variant < 0 || variant >= (1 << 30)) return fail(P4V_ERR_INVALID, "p4v_debug_set_variant: bad variant word");
+    if (variant & ~VARIANT_KEPT) return fail(P4V_ERR_INVALID, "p4v_debug_set_variant: bits 0x%x select removed paths", variant & ~VARIANT_KEPT);
     g_variant_word.store(variant | (force_generic ? (1 << 30) : 0), std::memory_order_relaxed);
     return 0;
 }
 
 int p4v_debug_set_tuning(int key, int value) {
     if (key < 0 || key >= 16) return fail(P4V_ERR_INVALID, "p4v_debug_set_tuning: unknown key %d", key);
+    if (key == TUNE_B1_PATH && tune_b1_removed(value)) return fail(P4V_ERR_INVALID, "p4v_debug_set_tuning: 12 = %d selects a removed path", value);
     g_tune[key].store(value, std::memory_order_relaxed);
     return 0;
 }

@@ -1534,26 +1534,11 @@ __device__ __forceinline__ void k_sweep8_body(const SweepParams& p, const uint3 
     if (c_lo >= c_hi) return;
     const int ncand = c_hi - c_lo;
 
-    // the 64 x 32 part of this wave; the padding skip of k_sweep2 (parts of pure padding do no work, parts with work are dealt
-    // to wave ids 0, 1, ... first):
-    int pos = wid;
-    // SKIP: A/B switch only (launch_sweep8_epi) -- slower at 197 and at 144 tokens: the candidate step of this kernel is
-    // paced by the ring (DMA landing + barrier), not by the work the padding parts would skip
-    if constexpr (SKIP) {
-        auto useful = [&](int q) { return (n0 + (q & 3) * 32 < p.N) && (m0 + (q >> 2) * 64 < p.M); };
-        int cnt = 0, found = -1;
-        for (int q = 0; q < 8; ++q)
-            if (useful(q)) { if (cnt == wid) found = q; ++cnt; }
-        if (found < 0) {
-            int k = wid - cnt;
-            for (int q = 0; q < 8; ++q)
-                if (!useful(q)) { if (k == 0) found = q; --k; }
-        }
-        pos = __builtin_amdgcn_readfirstlane(found);
-    }
-    const int wr = pos >> 2, wc = pos & 3;
-    const bool act = !SKIP || ((n0 + wc * 32 < p.N) && (m0 + wr * 64 < p.M));
-    const bool act1 = !SKIP || (act && (m0 + wr * 64 + 32 < p.M));   // second 32-row block of the part
+    // the 64 x 32 part of this wave.  Parts of pure padding run the candidate loop like the others: a candidate step of this
+    // kernel is paced by the ring (DMA landing + barrier), not by the MFMAs and the epilogue such a part could skip (a padding
+    // skip as in k_sweep2 measured slower at 197 and at 144 tokens, and was removed)
+    static_assert(!SKIP, "k_sweep8: the padding skip was removed");
+    const int wr = wid >> 2, wc = wid & 3;
 
     // ---- candidate-invariant epilogue operands (as k_sweep2) --------------------------------------------------------------
     float u[2][16], w[2][16];
@@ -1590,7 +1575,7 @@ __device__ __forceinline__ void k_sweep8_body(const SweepParams& p, const uint3 
     const int nw0 = n0 + wc * 32;
     const int sb = __builtin_amdgcn_readfirstlane(p.sb_mode == 1 ? min(nw0 / p.sb_div, p.s_cs - 1) : p.sb_mode == 2 ? z % p.sb_div : 0);
     float* s1tab = res + per * 8;
-    for (int i = lane; i < ncand; i += 64) s1tab[i * 8 + pos] = p.S1 ? p.S1[(c_lo + i) * p.s_cs + sb] : 1.0f;
+    for (int i = lane; i < ncand; i += 64) s1tab[i * 8 + wid] = p.S1 ? p.S1[(c_lo + i) * p.s_cs + sb] : 1.0f;
 
     // ---- the fixed operand's fragments: registers for the whole sweep (ldk = 64: one k-tile) ----------------------------------
     v4i fx[2][2];                                        // [32-row block (row side only)][k-half]
@@ -1654,11 +1639,6 @@ __device__ __forceinline__ void k_sweep8_body(const SweepParams& p, const uint3 
         if (it + SW8_NS - 1 < ncand) wait_vmcnt<SW8_NS - 3>(); else wait_vmcnt<0>();   // (tail: no younger pieces are counted on)
         __builtin_amdgcn_s_barrier();
         if constexpr (!(P4V_SW8_DBG & 1)) if (it + SW8_NS - 1 < ncand) issue((ST + SW8_NS - 1) % SW8_NS);
-        if (!act) {                                    // a part of pure padding: stream and barriers only
-            if (lane == 63) res[(c - c_lo) * 8 + pos] = 0.0f;
-            ++c;
-            return;
-        }
         if (it + 1 < ncand) {
             read_fr(nxt, std::integral_constant<int, (ST + 1) % SW8_NS>{});
             __builtin_amdgcn_s_waitcnt(0xC07F | (NRD << 8));
@@ -1670,23 +1650,22 @@ __device__ __forceinline__ void k_sweep8_body(const SweepParams& p, const uint3 
         if constexpr ((P4V_SW8_DBG & 2) != 0) { acc[0] = zero16; acc[1] = zero16; acc[0][0] = curf.t00[0] + curf.t01[1]; }
         else if (ROWS_FIXED) {      // A (rows) in registers, B (columns) streamed
             acc[0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fx[0][0], curf.t00, zero16, 0, 0, 0);
-            if (act1) acc[1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fx[1][0], curf.t00, zero16, 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fx[1][0], curf.t00, zero16, 0, 0, 0);
             acc[0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fx[0][1], curf.t01, acc[0], 0, 0, 0);
-            if (act1) acc[1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fx[1][1], curf.t01, acc[1], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fx[1][1], curf.t01, acc[1], 0, 0, 0);
         } else {               // A (rows) streamed, B (columns) in registers
             acc[0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(curf.t00, fx[0][0], zero16, 0, 0, 0);
-            if (act1) acc[1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(curf.t10, fx[0][0], zero16, 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(curf.t10, fx[0][0], zero16, 0, 0, 0);
             acc[0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(curf.t01, fx[0][1], acc[0], 0, 0, 0);
-            if (act1) acc[1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(curf.t11, fx[0][1], acc[1], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(curf.t11, fx[0][1], acc[1], 0, 0, 0);
         }
         // ---- fused similarity epilogue of candidate c: one float per wave -----------------------------------------------
-        const float s1 = s1tab[(c - c_lo) * 8 + pos];
+        const float s1 = s1tab[(c - c_lo) * 8 + wid];
         v2f sum2 = {0.0f, 0.0f};
         if constexpr ((P4V_SW8_DBG & 4) != 0) sum2.x = (float)(acc[0][0] + acc[1][5]) * s1;
         else
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            if (i == 1 && !act1) break;                  // a block of pure padding rows
 #pragma unroll
             for (int r = 0; r < 16; r += 2) {
                 const v2f a = {(float)acc[i][r], (float)acc[i][r + 1]};
@@ -1700,7 +1679,7 @@ __device__ __forceinline__ void k_sweep8_body(const SweepParams& p, const uint3 
             }
         }
         const float sum = wave_sum_dpp(sum2.x + sum2.y);           // fixed order: deterministic
-        if (lane == 63) res[(c - c_lo) * 8 + pos] = sum;
+        if (lane == 63) res[(c - c_lo) * 8 + wid] = sum;
         ++c;
     };
     if (ncand >= SW8_NS) wait_vmcnt<SW8_NS - 2>(); else wait_vmcnt<0>();
@@ -1916,18 +1895,22 @@ template <bool ROWS_FIXED, int EPI>
 __global__ __launch_bounds__(SW9_NW * 64, 2) void k_sweep9_g(GroupArgs<SweepParams> a) { P4V_GROUP_ENTER(a); k_sweep9_body<ROWS_FIXED, EPI>(a.p[m_], vb_, vg_); }
 
 // ------------------------------------------------------------------------------------------
-// k_slice_b: stage A of a pruned MatMul B search -- all candidates of B on the 16-row sample slice, B quantised IN the kernel
+// k_slice_b2: stage A of a pruned MatMul B search -- all candidates of B on the 16-row sample slice, B quantised IN the kernel
 // ------------------------------------------------------------------------------------------
 // Stage A of the B search of an attention matmul (p4v_api.hip::run_pass_pruned) scores the 100 candidate scales of the WHOLE
 // column operand (the keys of q.k^T, the values of attn.v) against the 16 heaviest query rows of every (image, head).  On the sweep
 // kernels that meant materialising 100 int8 planes of B (629 MB per ViT-B module for the keys, 630 MB for the values: k_pack at
 // 4.6 TB/s) only to stream them once through a GEMM with 16 useful rows (k_sweep9 / k_sweep2 at the HBM rate, or below it: the
 // fixed twin planes of attn.v were re-streamed per candidate) -- both memory-bound on bytes that exist for this one read.
-// Here a workgroup owns one (image, head): B (fp32, 50 KB) is read ONCE into the LDS (transposed to [n][k], padded rows), every
-// wave takes every fourth candidate and quantises B's 16 x 64 fragments in registers with k_pack's own arithmetic
-// (quant_fast1 + the exactness check + the IEEE division for flagged elements: the same integers), feeds them to
-// mfma_i32_16x16x64_i8 against the slice's fragments, which stay in registers with raw_out / the metric weight, and writes one
-// float per (candidate, batch entry).  No candidate plane is written or read; what is left is the VALU work of the quantisation.
+// Here a workgroup owns one (image, head) and its four waves deal the 16-COLUMN BLOCKS of B (q.k^T: 13 blocks of one k-tile
+// -> 4 / 3 / 3 / 3; attn.v: 4 blocks of 4 k-tiles -> one each): a lane keeps its 16 fp32 values of each of its (at most 4)
+// fragments in REGISTERS for the whole kernel, every wave works on EVERY candidate and quantises only its own fragments with
+// k_pack's arithmetic (quant16_sat8 on the symmetric 8-bit grid, 4.5 operations per element, else quant_fast1: the same
+// integers), feeds them to mfma_i32_16x16x64_i8 against the slice's fragments, which stay in registers with raw_out / the
+// metric weight, and writes one float per (candidate, batch entry, wave); k_finish adds the four.  No LDS, no candidate plane
+// is written or read; what is left is the VALU work of the quantisation.  (Measured and removed: B in the LDS with the
+// candidates dealt over the waves -- every wave re-read all of B per candidate, ~200 instructions per 1 KB fragment,
+// VALU-bound at 0.015 of the matrix peak.)
 // The planes stage B2 needs (the few surviving candidates, all rows) are packed on demand as before.
 struct SliceBParams {
     const int8_t* A; const int8_t* A2;     // int8 planes [Z][16][Kp] of the fixed row operand (its slice); A2: twin second plane
@@ -1937,133 +1920,8 @@ struct SliceBParams {
     const float* S1; const float* S2; int s_cs, s_div;      // combined output scales [C][s_cs] of plane 1 / 2, block z % s_div
     const float* O; const float* Wt; int wt_mode;           // slice tiles [Z][16][N] fp32 (dense): raw_out, metric weight source
     int Z, M, K, Kp, N, C;                                  // M <= 16 valid slice rows
-    float* part;                                            // [C][Z]
+    float* part;                                            // [C][Z][4]: one float per wave
 };
-template <bool TWIN, int KTM, int NBM, int EPI>
-__device__ __forceinline__ void k_slice_b_body(const SliceBParams& p, const uint3 blockIdx, const uint3 gridDim) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* Bt = reinterpret_cast<float*>(smem);                         // [NB * 16][Kp + 4] fp32, zero padded
-    typedef int v4i_ __attribute__((ext_vector_type(4)));
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l15 = lane & 15, l4 = lane >> 4;
-    const int z = blockIdx.x;
-    const int ktn = p.Kp / 64, nb = (p.N + 15) / 16, ldb = p.Kp + 4;
-    const int per = (p.C + gridDim.y - 1) / gridDim.y;
-    const int c_lo = blockIdx.y * per, c_hi = min(p.C, c_lo + per);
-    // ---- B of this batch entry -> LDS as [n][k]; the faster-varying index of the copy follows the contiguous source stride --------
-    const float* Bz = p.B + (p.zdiv > 0 ? (long)(z / p.zdiv) * p.b_z2 + (long)(z % p.zdiv) * p.b_z : (long)z * p.b_z);
-    const int rows = nb * 16;
-    if (p.b_k == 1) {
-        for (int i = tid; i < rows * p.Kp; i += 256) {
-            const int n = i / p.Kp, k = i - n * p.Kp;
-            Bt[n * ldb + k] = (n < p.N && k < p.K) ? Bz[(long)n * p.b_n + k] : 0.0f;
-        }
-    } else {
-        for (int i = tid; i < rows * p.Kp; i += 256) {
-            const int k = i / rows, n = i - k * rows;
-            Bt[n * ldb + k] = (n < p.N && k < p.K) ? Bz[(long)n * p.b_n + (long)k * p.b_k] : 0.0f;
-        }
-    }
-    // ---- fixed fragments of the slice (16 rows x 64 B per k-tile: lane (l4, l15) holds bytes [16 l4, +16) of row l15) -----------
-    v4i_ fa[KTM], fa2[KTM];
-#pragma unroll
-    for (int kt = 0; kt < KTM; ++kt) {
-        const long off = ((long)z * 16 + l15) * p.Kp + (long)min(kt, ktn - 1) * 64 + l4 * 16;
-        fa[kt] = *reinterpret_cast<const v4i_*>(p.A + off);
-        if (TWIN) fa2[kt] = *reinterpret_cast<const v4i_*>(p.A2 + off);
-    }
-    // ---- raw_out / metric weight of the 16 x N tile in accumulator layout: lane -> column l15 of a block, rows 4 l4 + e ---------
-    float u[NBM][4], w[NBM][4];
-    const int wm = p.wt_mode;
-#pragma unroll
-    for (int j = 0; j < NBM; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int n = j * 16 + l15, m = 4 * l4 + e;
-            const bool ok = j < nb && n < p.N && m < p.M;
-            const long idx = ((long)z * 16 + min(m, 15)) * p.N + min(n, p.N - 1);
-            const float o = p.O[idx], gw = p.Wt[idx];
-            float wv;
-            if (wm == 1) wv = gw; else if (wm == 2) wv = o; else if (wm == 3) wv = fabsf(o); else wv = 1.0f;
-            u[j][e] = ok ? o : 0.0f;
-            w[j][e] = ok ? wv : 0.0f;
-        }
-    __syncthreads();
-    const int sbz = p.bs_div > 0 ? z % p.bs_div : 0, ssz = p.s_div > 0 ? z % p.s_div : 0;
-    const float flo = (float)p.lo, fhi = (float)p.hi;
-    const bool wide = !(fmaxf(-flo, fhi) < 129.0f);
-    const float* brow = Bt + l15 * ldb + l4 * 16;                        // + (block * 16) * ldb + k-tile * 64
-    for (int c = c_lo + wid; c < c_hi; c += 4) {
-        const float s = p.bscale[(long)c * p.bs_cs + sbz];
-        const float rcp = 1.0f / s;
-        const float s1 = p.S1 ? p.S1[(long)c * p.s_cs + ssz] : 1.0f;
-        const float s2 = (TWIN && p.S2) ? p.S2[(long)c * p.s_cs + ssz] : 1.0f;
-        float sum = 0.0f;
-#pragma unroll
-        for (int j = 0; j < NBM; ++j) {
-            if (j < nb) {                                            // (uniform guard, no break: the loop must unroll -- u / w are registers)
-            v4i_ acc = {0, 0, 0, 0}, acc2 = {0, 0, 0, 0};
-#pragma unroll
-            for (int kt = 0; kt < KTM; ++kt) {
-                if (kt < ktn) {
-                const v4f* src = reinterpret_cast<const v4f*>(brow + (j * 16) * ldb + kt * 64);
-                float x[16];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) { const v4f t = src[q]; x[q * 4] = t[0]; x[q * 4 + 1] = t[1]; x[q * 4 + 2] = t[2]; x[q * 4 + 3] = t[3]; }
-                // k_pack's hot path (symmetric grid): x * (1 / s) where provably equal to the division, the division otherwise
-                unsigned qb[16];
-                float maxdev = 0.0f, magic = PACK_MAGIC;
-                asm volatile("" : "+v"(magic));
-#pragma unroll
-                for (int e = 0; e < 16; ++e) qb[e] = quant_fast1(x[e], rcp, flo - 0.49f, fhi + 0.49f, magic, maxdev);
-                const bool bad = !(maxdev <= 0.49996f) || !(rcp < 3.0e38f) || wide;
-                if (__any(bad)) {
-                    float sd = s;
-                    asm volatile("" : "+v"(sd));
-                    if (bad) {
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) qb[e] = __builtin_bit_cast(unsigned, fminf(fmaxf(rintf(x[e] / sd), flo), fhi) + PACK_MAGIC);
-                    }
-                }
-                v4i_ fb;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const unsigned lo16 = __builtin_amdgcn_perm(qb[q * 4 + 1], qb[q * 4], 0x0c0c0400u);
-                    const unsigned hi16 = __builtin_amdgcn_perm(qb[q * 4 + 3], qb[q * 4 + 2], 0x0c0c0400u);
-                    fb[q] = (int)(lo16 | (hi16 << 16));
-                }
-                acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[kt], fb, acc, 0, 0, 0);
-                if (TWIN) acc2 = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa2[kt], fb, acc2, 0, 0, 0);
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float d = u[j][e] - (float)acc[e] * s1;
-                if (TWIN) d -= (float)acc2[e] * s2;
-                const float ww = w[j][e];
-                if (EPI == EPI_SQ_W) { const float t2 = ww * d; sum = fmaf(t2, t2, sum); }
-                else if (EPI == EPI_ABS) sum = fmaf(ww, fabsf(d), sum);
-                else sum = fmaf(ww * d, d, sum);                        // EPI_SQ (w = validity mask) and EPI_W_SQ
-            }
-            }
-        }
-        sum = wave_sum_dpp(sum);
-        if (lane == 63) p.part[(long)c * p.Z + z] = sum;
-    }
-}
-template <bool TWIN, int KTM, int NBM, int EPI>
-__global__ __launch_bounds__(256, 2) void k_slice_b(SliceBParams p) { k_slice_b_body<TWIN, KTM, NBM, EPI>(p, P4V_BIDX, P4V_GDIM); }
-template <bool TWIN, int KTM, int NBM, int EPI>
-__global__ __launch_bounds__(256, 2) void k_slice_b_g(GroupArgs<SliceBParams> a) { P4V_GROUP_ENTER(a); k_slice_b_body<TWIN, KTM, NBM, EPI>(a.p[m_], vb_, vg_); }
-
-// k_slice_b2 (round 5): k_slice_b with B in REGISTERS.  k_slice_b dealt the candidates over the four waves: every wave
-// re-read all of B (fp32) from the LDS for each of its candidates -- 4 KB of ds_read_b128 and the address arithmetic per 1 KB
-// fragment, ~200 instructions per fragment, VALU-bound at 0.015 of the matrix peak.  Here the waves deal the 16-COLUMN BLOCKS
-// of B instead (q.k^T: 13 blocks of one k-tile -> 4 / 3 / 3 / 3; attn.v: 4 blocks of 4 k-tiles -> one each): a lane keeps its
-// 16 fp32 values of each of its (at most 4) fragments for the whole kernel, every wave works on EVERY candidate and quantises
-// only its own fragments (quant16_sat8 on the symmetric 8-bit grid: 4.5 operations per element), and writes one float per
-// (candidate, batch entry, wave); k_finish adds the four.  No LDS, no candidate planes.
 struct SliceB2Params {
     SliceBParams b;
     float qbias;            // bias of quant16_sat8's conversion (k_probe_cvt); 0: the conversion is not usable -> SAT8 must be false
@@ -2459,7 +2317,7 @@ template <bool TWIN, int EPI>
 __global__ __launch_bounds__(512, 2) void k_sweep2g_g(GroupArgs<SweepParams> a) { P4V_GROUP_ENTER(a); k_sweep2g_body<TWIN, EPI>(a.p[m_], vb_, vg_); }
 
 // ------------------------------------------------------------------------------------------
-// Stationary-operand int8 sweep (k_sweep4 below): parameter block
+// Stationary-operand int8 sweeps (k_sweep5, k_sweep6 below): parameter block
 // ------------------------------------------------------------------------------------------
 // The candidate-invariant operand (activations in the weight search, weights in the activation search) is
 // re-used by all ~100 candidates.  k_sweep2 re-streams its 128 x K tile from L2 for every candidate; here the
@@ -2494,204 +2352,25 @@ struct Sweep3Params {
 };
 
 // ------------------------------------------------------------------------------------------
-// k_sweep4: int8 sweep with the candidate-INVARIANT operand stationary in LDS (Linear layers, K <= 768)
+// k_sweep5: int8 sweep with the candidate-INVARIANT operand stationary in LDS, TWO candidates per pass (Linear layers, K <= 768)
 // ------------------------------------------------------------------------------------------
 // The candidate-invariant operand (activations in the weight search, weights in the activation search) is
 // re-used by all ~100 candidates: its whole 128 x K tile (K/64 k-tiles of 8 KB, <= 96 KB) is loaded into LDS
-// ONCE per workgroup and only the candidate-expanded operand streams, through a 6-deep LDS-DMA ring.
-// Tile 128 (stationary rows) x 128 (streaming rows), 8 waves as 2 x 4, 64 x 32 per wave.  What profiling the
-// earlier variants taught (profiles/):
-//   * every wave keeps TWO fragment sets: the ds_reads of k-tile t+1 are in flight while the MFMAs of k-tile t
-//     run, and the barrier only has to prove that tile t+1 has landed;
-//   * the loop is scalar-instruction bound if it does any bookkeeping: the expanded plane is therefore laid out
-//     [row][candidate][K] so the stream cursor advances by a constant 64 B per tile (no candidate wrap), the
-//     ring always issues (the plane has slack behind it; stale tiles are never consumed) so the vmcnt wait is a
-//     constant, and ring / k-tile offsets wrap with one s_cselect each.
-// The MFMA rows are the stationary rows: in the activation search the output tile is transposed (rows = output
-// features, columns = samples); the raw_out / raw_grad tile is gathered through strides.
-static constexpr int SW4_NS = 6;
-
-template <int EPI>
-__device__ __forceinline__ void k_sweep4_body(const Sweep3Params& p, const uint3 blockIdx, const uint3 gridDim) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int ktiles = p.ktiles;
-    const int ring0 = ktiles * SW2_TILE;                 // LDS byte offset of the ring
-    float* res = reinterpret_cast<float*>(smem + ring0 + SW4_NS * SW2_TILE);
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wid >> 2, wc = wid & 3;
-    const int g = lane >> 5, l31 = lane & 31;
-
-    const int nwg = p.stiles * p.ttiles;
-    const int t = xcd_remap(blockIdx.x, nwg);
-    const int st = t % p.stiles, tt = t / p.stiles;    // neighbours share the streaming tile
-    const int s0 = st * 128, t0 = tt * 128;
-    const int per = (p.c1 - p.c0 + gridDim.z - 1) / gridDim.z;
-    int c_lo_ = p.c0 + blockIdx.z * per, c_hi_ = min(p.c1, c_lo_ + per);
-    clip_crange(p.crange, c_lo_, c_hi_);
-    const int c_lo = c_lo_, c_hi = c_hi_;
-    if (c_lo >= c_hi) return;
-
-    // ---- stationary operand: all k-tiles of this workgroup's 128 rows, once ------------------------------
-    const int ld_row = wid * 16 + (lane >> 2);
-    const int ld_chunk = (lane & 3) ^ ((ld_row >> 2) & 3);
-    {
-        const char* gS = (const char*)p.S + (long)(s0 + ld_row) * p.ldk + ld_chunk * 16;
-        for (int kt = 0; kt < ktiles; ++kt) glds16(gS + kt * SW_BKB, smem + kt * SW2_TILE + wid * 1024);
-    }
-    // ---- streaming operand [row][candidate][K]: one 16-row piece per wave per tile, cursor += 64 B per tile --------
-    const char* curT = (const char*)p.T + (long)(t0 + ld_row) * p.t_rs + (long)(c_lo - p.c0) * p.ldk + ld_chunk * 16;
-    const int total = (c_hi - c_lo) * ktiles;
-#pragma unroll
-    for (int i = 0; i < SW4_NS - 1; ++i) { glds16(curT, smem + ring0 + i * SW2_TILE + wid * 1024); curT += SW_BKB; }
-
-    // ---- candidate-invariant epilogue operands: 2 MFMA tiles of 32 x 32 (rows = stationary, cols = streaming) --
-    float u[2][16], w[2][16];
-    {
-        const int tr = t0 + wc * 32 + l31;
-        const long toff = (long)min(tr, p.TR - 1) * p.o_ts;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const long idx = toff + (long)min(s0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g, p.SR - 1) * p.o_ss;
-                u[i][r] = p.O[idx];
-                w[i][r] = p.Wt[idx];
-            }
-        float bias_s[2][16];
-        const float bias_t = p.bias[p.bias_on_t ? min(tr, p.TR - 1) : 0];
-        if (!p.bias_on_t) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) bias_s[i][r] = p.bias[min(s0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g, p.SR - 1)];
-        }
-        const bool t_ok = tr < p.TR;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const bool ok = t_ok && (s0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g) < p.SR;
-                const float o = u[i][r], gw = w[i][r];
-                const float b = p.bias_on_t ? bias_t : bias_s[i][r];
-                float wv;
-                if (p.wt_mode == 1) wv = gw; else if (p.wt_mode == 2) wv = o; else if (p.wt_mode == 3) wv = fabsf(o); else wv = 1.0f;
-                u[i][r] = ok ? o - b : 0.0f;
-                w[i][r] = ok ? wv : 0.0f;
-            }
-    }
-    const int blk_row = p.sb_on_t ? (t0 + wc * 32) : (s0 + wr * 64);
-    const int sb = __builtin_amdgcn_readfirstlane(min(blk_row / p.sb_div, p.s_cs - 1));
-    float* s1tab = res + per * 8;
-    for (int i = lane; i < c_hi - c_lo; i += 64) s1tab[i * 8 + wid] = p.S1 ? p.S1[(c_lo + i) * p.s_cs + sb] : 1.0f;
-
-    v16i acc[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][r] = 0;
-
-    // fragment addresses (LDS byte offsets): stationary rows + k-tile offset, streaming rows + stage offset
-    const int rs0 = wr * 64 + l31, rs1 = rs0 + 32, rt = wc * 32 + l31;
-    const int ss0 = (rs0 >> 2) & 3, ss1 = (rs1 >> 2) & 3, stz = (rt >> 2) & 3;
-    const int aS00 = rs0 * 64 + ((g ^ ss0) << 4), aS01 = rs0 * 64 + (((2 + g) ^ ss0) << 4);
-    const int aS10 = rs1 * 64 + ((g ^ ss1) << 4), aS11 = rs1 * 64 + (((2 + g) ^ ss1) << 4);
-    const int aT0 = ring0 + rt * 64 + ((g ^ stz) << 4), aT1 = ring0 + rt * 64 + (((2 + g) ^ stz) << 4);
-    const int issue_base = ring0 + wid * 1024;
-
-    struct Frag { v4i s00, s10, s01, s11, t0, t1; };
-    Frag fa, fb;
-    // wave-uniform loop state (SGPRs): byte offsets of the stage / stationary k-tile of the tile to READ next, the
-    // stage to ISSUE into next, and the k-tile counter of the tile to COMPUTE next
-    int rd_stage = 0, is_stage = (SW4_NS - 1) * SW2_TILE, rd_koff = 0;
-    const int koff_end = ktiles * SW2_TILE;
-    int kt = 0, cidx = 0;
-    auto read_frags = [&](Frag& f) __attribute__((always_inline)) {
-        f.s00 = *reinterpret_cast<const v4i*>(smem + rd_koff + aS00);
-        f.s10 = *reinterpret_cast<const v4i*>(smem + rd_koff + aS10);
-        f.t0 = *reinterpret_cast<const v4i*>(smem + rd_stage + aT0);
-        f.s01 = *reinterpret_cast<const v4i*>(smem + rd_koff + aS01);
-        f.s11 = *reinterpret_cast<const v4i*>(smem + rd_koff + aS11);
-        f.t1 = *reinterpret_cast<const v4i*>(smem + rd_stage + aT1);
-        rd_stage = (rd_stage + SW2_TILE == SW4_NS * SW2_TILE) ? 0 : rd_stage + SW2_TILE;
-        rd_koff = (rd_koff + SW2_TILE == koff_end) ? 0 : rd_koff + SW2_TILE;
-    };
-    auto mma = [&](const Frag& f) __attribute__((always_inline)) {
-        acc[0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(f.s00, f.t0, acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(f.s10, f.t0, acc[1], 0, 0, 0);
-        acc[0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(f.s01, f.t1, acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(f.s11, f.t1, acc[1], 0, 0, 0);
-        if (++kt == ktiles) {
-            const float s1 = s1tab[cidx * 8 + wid];
-            v2f sum2 = {0.0f, 0.0f};
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    const v2f a = {(float)acc[i][r], (float)acc[i][r + 1]};
-                    const v2f uu = {u[i][r], u[i][r + 1]};
-                    const v2f ww = {w[i][r], w[i][r + 1]};
-                    const v2f d = uu - a * s1;
-                    if (EPI == EPI_SQ_W) { const v2f t2 = ww * d; sum2 = t2 * t2 + sum2; }
-                    else if (EPI == EPI_SQ) sum2 = d * d + sum2;
-                    else if (EPI == EPI_ABS) sum2 += v2f{fabsf(d.x), fabsf(d.y)};
-                    else sum2 = (ww * d) * d + sum2;
-                    acc[i][r] = 0;
-                    acc[i][r + 1] = 0;
-                }
-            float sum = sum2.x + sum2.y;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-            if (lane == 0) res[cidx * 8 + wid] = sum;
-            kt = 0;
-            ++cidx;
-        }
-    };
-    // step: tile `it` is in `cur`.  Prove tile it+1 landed (own piece waited for, then the barrier), issue tile
-    // it+NS-1 into the stage of tile it-1 (everybody finished reading it one step ago), start the ds_reads of tile
-    // it+1 into the idle fragment set and run the MFMAs of tile it.  No tail conditionals: the ring keeps issuing
-    // (slack behind the plane) so exactly NS-3 younger pieces are outstanding at every wait.
-    auto step = [&](Frag& cur, Frag& nxt) __attribute__((always_inline)) {
-        wait_vmcnt<SW4_NS - 3>();
-        __builtin_amdgcn_s_barrier();
-        glds16(curT, smem + issue_base + is_stage);
-        curT += SW_BKB;
-        is_stage = (is_stage + SW2_TILE == SW4_NS * SW2_TILE) ? 0 : is_stage + SW2_TILE;
-        read_frags(nxt);
-        mma(cur);
-    };
-    // tile 0 (older loads -- the stationary operand -- complete first: vmcnt is in order)
-    wait_vmcnt<SW4_NS - 2>();
-    __builtin_amdgcn_s_barrier();
-    read_frags(fa);
-    int it = 0;
-    for (; it + 1 < total; it += 2) { step(fa, fb); step(fb, fa); }
-    if (it < total) step(fa, fb);
-    __syncthreads();   // also drains the over-issued (never consumed) ring pieces before the LDS is released
-    for (int i = tid; i < (c_hi - c_lo) * 8; i += 512) {
-        const int cc = c_lo + i / 8, wv = i % 8;
-        p.part[(long)cc * p.p_cs + (long)(st * 2 + (wv >> 2)) * p.NG + tt * 4 + (wv & 3)] = res[i];
-    }
-}
-template <int EPI>
-__global__ __launch_bounds__(512, 2) void k_sweep4(Sweep3Params p) { k_sweep4_body<EPI>(p, P4V_BIDX, P4V_GDIM); }
-template <int EPI>
-__global__ __launch_bounds__(512, 2) void k_sweep4_g(GroupArgs<Sweep3Params> a) { P4V_GROUP_ENTER(a); k_sweep4_body<EPI>(a.p[m_], vb_, vg_); }
-
-// ------------------------------------------------------------------------------------------
-// k_sweep5: k_sweep4 with TWO candidates per pass (candidate pair = one "pair-step" per k-tile)
-// ------------------------------------------------------------------------------------------
-// k_sweep4's inner loop is bound by LDS bandwidth, not by the matrix pipe: per k-tile every wave reads 4 KB of
-// stationary and 2 KB of streaming fragments for 4 MFMAs (1.5 KB / MFMA; 8 waves -> 48 KB + 8 KB of LDS-DMA
-// writes = 448 clk of the 128 B/clk LDS against 256 clk of MFMA; measured 458, tools/ubench_mfma.hip).  The
+// ONCE per workgroup and only the candidate-expanded operand streams, through an LDS-DMA ring.  Tile 128
+// (stationary rows) x 128 (streaming rows), 8 waves as 2 x 4, 64 x 32 per wave.  The MFMA rows are the stationary
+// rows: in the activation search the output tile is transposed (rows = output features, columns = samples); the
+// raw_out / raw_grad tile is gathered through strides.
+// With ONE candidate per pass such a loop is bound by LDS bandwidth, not by the matrix pipe: per k-tile every wave
+// reads 4 KB of stationary and 2 KB of streaming fragments for 4 MFMAs (1.5 KB / MFMA; 8 waves -> 48 KB + 8 KB of
+// LDS-DMA writes = 448 clk of the 128 B/clk LDS against 256 clk of MFMA; measured 458, tools/ubench_mfma.hip).  The
 // candidate-invariant state -- stationary fragments and the raw_out / raw_grad registers -- can be shared by
 // several candidates: here each wave keeps two accumulator sets and feeds both candidates of a pair from ONE read
-// of the stationary fragments (1 KB / MFMA -> 320 clk per candidate-step).  The expanded plane is laid out
-// [row][pair][k-tile][2][64 B] (k_pack c_inner = 2) so that the stream cursor still advances by a constant
-// (128 B per pair-step).  Ring = 3 pair-stages of 2 x 8 KB; every step ends with lgkmcnt(0), so the stage whose
-// fragments were read during step t-1 can be refilled right after the barrier of step t (two steps of L2 latency
-// covered with three stages).  An odd candidate count runs one padding candidate whose score is dropped.
+// of the stationary fragments (1 KB / MFMA -> 320 clk per candidate-step).  The loop is scalar-instruction bound if
+// it does any bookkeeping: the expanded plane is laid out [row][pair][k-tile][2][64 B] (k_pack c_inner = 2) so that
+// the stream cursor advances by a constant (128 B per pair-step).  Ring = 3 pair-stages of 2 x 8 KB; every step ends
+// with lgkmcnt(0), so the stage whose fragments were read during step t-1 can be refilled right after the barrier of
+// step t (two steps of L2 latency covered with three stages).  An odd candidate count runs one padding candidate
+// whose score is dropped.
 static constexpr int SW5_NP = 3;
 
 template <int EPI>
@@ -2902,7 +2581,7 @@ __global__ __launch_bounds__(512, 2) void k_sweep5_g(GroupArgs<Sweep3Params> a) 
 // ------------------------------------------------------------------------------------------
 // k_sweep6: stationary operand in REGISTERS, one wave per SIMD (K = KT * 64 bytes, KT <= 12)
 // ------------------------------------------------------------------------------------------
-// What bounds k_sweep4/5 (tools/ubench_mfma.hip, profiles/r1_ubench.txt): not the matrix pipe but the LDS --
+// What bounds k_sweep5 (tools/ubench_mfma.hip, profiles/r1_ubench.txt): not the matrix pipe but the LDS --
 // 6 (4) ds_read_b128 per 4 MFMAs plus the LDS-DMA writes of the streamed tile, which interfere badly with the
 // reads (MFMA only 133 ns per k-tile step, + reads 162 ns, + LDS-DMA 231 ns, + epilogue 261 ns = the kernel).
 // The cure is fewer LDS bytes per MFMA on BOTH paths:
@@ -2914,11 +2593,11 @@ __global__ __launch_bounds__(512, 2) void k_sweep5_g(GroupArgs<Sweep3Params> a) 
 //   * the ring holds whole candidates (KT x 4 KB per stage, 3 stages): ONE barrier and one counted vmcnt wait per
 //     candidate instead of per k-tile; the epilogue of candidate c-1 runs after the barrier of candidate c, under
 //     the latency of its first fragment reads.
-// Output tile orientation, scales, bias, partial-sum table and plane layout ([row][candidate][K], c_inner = 1)
-// are those of k_sweep4, so k_pack / k_finish are unchanged.
-// RB = 32-row blocks of the stationary operand per wave: RB = 2 -> 4 waves (one per SIMD, 512 registers each);
-// RB = 1 -> 8 waves (two per SIMD, 256 registers each): half the rows per wave, so one wave's epilogue VALU work and
-// LDS waits hide under the other wave's MFMAs, at twice the fragment reads per MFMA.
+// Output tile orientation, scales, bias and partial-sum table are those of k_sweep5, and the streamed plane is laid out
+// [row][candidate][K] (c_inner = 1), so k_pack / k_finish are unchanged.
+// RB = 32-row blocks of the stationary operand per wave, always 2: 4 waves, one per SIMD, 512 registers each.  (Measured
+// and removed: RB = 1, 8 waves of 256 registers, hid one wave's epilogue VALU work under the other's MFMAs but doubled the
+// fragment reads per MFMA and became LDS-bound -- the same 3.33 ms per fc1 search round.)
 // Epilogue operands of k_sweep6 in fragment order, written once per (module, search orientation) and read by every pass
 // of that orientation (raw_out, raw_grad and the bias do not change during calibration_step2).  For tile t = tt * stiles + st,
 // 32-row block b (of the tile's 256 stationary rows), column block cb, quarter q and lane (g, l31): the four values of
@@ -2980,7 +2659,7 @@ __device__ __forceinline__ void k_sweep6_body(const Sweep3Params& p, const uint3
     // sample) straight to k_finish_cos's table [slab][sample][3] (p.NG = padded samples): there is no LDS left for 100
     // candidates x 256 samples, and the stores ride behind the ring barrier, a whole candidate before the next counted wait.
     constexpr bool COS = EPI == EPI_COS || EPI == EPI_COS_T, TR = EPI == EPI_COS_T;
-    static_assert(!COS || RB == 2, "cosine epilogue: one wave per SIMD only");
+    static_assert(RB == 2, "k_sweep6: one wave per SIMD (RB = 2) only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
 #ifdef P4V_TRACE
     unsigned long long* trc = p.trace + ((size_t)blockIdx.z * gridDim.x + blockIdx.x) * 16;
@@ -3039,7 +2718,6 @@ __device__ __forceinline__ void k_sweep6_body(const Sweep3Params& p, const uint3
     {
         // fragment order (k_pack c_inner == 3): every load of a wave is 1 KB contiguous
         const v4i* gS = reinterpret_cast<const v4i*>(p.S) + (long)(s0 >> 6) * (KT * 4 * 64) + lane;
-        const int ib = (s0 >> 5) & 1;                        // RB == 1: the wave's single 32-row block within its 64-row slab
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
@@ -3047,7 +2725,7 @@ __device__ __forceinline__ void k_sweep6_body(const Sweep3Params& p, const uint3
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     if constexpr ((P4V_SW6_DBG & 32) != 0) sfr[kt][i][h] = v4i{lane, kt, i, h};     // ablation: no stationary loads
-                    else sfr[kt][i][h] = gS[((kt * 2 + (RB == 2 ? i : ib)) * 2 + h) * 64];
+                    else sfr[kt][i][h] = gS[((kt * 2 + i) * 2 + h) * 64];
                 }
         // cosine instances: the fragments are pinned to the ACCUMULATION file (the MFMAs read them there).  Left alone the
         // allocator spreads them over both files and shuffles them inside the candidate loop (112 v_accvgpr_mov + 3 scratch
@@ -3393,12 +3071,11 @@ __device__ __forceinline__ void k_sweep6_body(const Sweep3Params& p, const uint3
     }
     __syncthreads();   // also drains the over-issued (never consumed) ring pieces before the LDS is released
     if constexpr (COS) return;
-    // part[c][64-row slab][32-column group]; with RB = 1 two waves share a slab: fixed-order sum of their results
+    // part[c][64-row slab][32-column group]
     for (int i = tid; i < ncand * 8; i += 64 * NW) {
         const int ci = i / 8, wv = (i % 8) >> 1, cb = i & 1;
         const float* r = res + (ci + 1) * (2 * NW);
-        const float v = (RB == 2) ? r[wv * 2 + cb] : r[(2 * wv) * 2 + cb] + r[(2 * wv + 1) * 2 + cb];
-        p.part[(long)(c_lo + ci) * p.p_cs + (long)(st * 4 + wv) * p.NG + tt * 2 + cb] = v;
+        p.part[(long)(c_lo + ci) * p.p_cs + (long)(st * 4 + wv) * p.NG + tt * 2 + cb] = r[wv * 2 + cb];
     }
 #undef P4V_DSR
 #ifdef P4V_TRACE
@@ -3406,9 +3083,9 @@ __device__ __forceinline__ void k_sweep6_body(const Sweep3Params& p, const uint3
 #endif
 }
 template <int EPI, int KT, int RB>
-__global__ __launch_bounds__(512 / RB, RB == 2 ? 1 : 2) void k_sweep6(Sweep3Params p) { k_sweep6_body<EPI, KT, RB>(p, P4V_BIDX, P4V_GDIM); }
+__global__ __launch_bounds__(256, 1) void k_sweep6(Sweep3Params p) { k_sweep6_body<EPI, KT, RB>(p, P4V_BIDX, P4V_GDIM); }
 template <int EPI, int KT, int RB>
-__global__ __launch_bounds__(512 / RB, RB == 2 ? 1 : 2) void k_sweep6_g(GroupArgs<Sweep3Params> a) { P4V_GROUP_ENTER(a); k_sweep6_body<EPI, KT, RB>(a.p[m_], vb_, vg_); }
+__global__ __launch_bounds__(256, 1) void k_sweep6_g(GroupArgs<Sweep3Params> a) { P4V_GROUP_ENTER(a); k_sweep6_body<EPI, KT, RB>(a.p[m_], vb_, vg_); }
 
 // ------------------------------------------------------------------------------------------
 // k_sweep7: int8 candidate sweep for LARGE K (K >= 1024: fc2 of every ViT, every Linear of ViT-L / Swin stage 4)

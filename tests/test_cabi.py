@@ -94,6 +94,9 @@ def test_granular_entry_points_validate_arguments(lib):
     ed.mode = 9
     assert lib.p4v_export_quantize(C.byref(ed), one, one, null, one, null) == -1 and b"unknown mode" in lib.p4v_last_error()
     assert lib.p4v_debug_set_variant(-1, 0) == -1 and lib.p4v_debug_set_tuning(99, 0) == -1
+    # switches of removed paths (variant bit 8, key 12 = 8) fail instead of timing production under a stale label
+    assert lib.p4v_debug_set_variant(8, 0) == -1 and b"removed" in lib.p4v_last_error()
+    assert lib.p4v_debug_set_tuning(12, 8) == -1 and b"removed" in lib.p4v_last_error()
     assert lib.p4v_debug_set_variant(0, 0) == 0 and lib.p4v_stats_enable(0) == 0
 
 

@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of p4v_debug_set_tuning switches on the default bench: tools/ab_tune.sh "<tune or -> ..."   e.g.  tools/ab_tune.sh "- 12=8 -"
+# A/B of p4v_debug_set_tuning switches on the default bench: tools/ab_tune.sh "<tune or -> ..."   e.g.  tools/ab_tune.sh "- 12=9 -"
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 i=0
 for t in $1; do

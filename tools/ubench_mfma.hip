@@ -25,7 +25,7 @@ __global__ __launch_bounds__(512, 2) void k(int iters, int* out, const char* src
     v16i acc0 = {0}, acc1 = {0};
     v4i a0 = {lane, 1, 2, 3}, a1 = {4, lane, 6, 7}, b0 = {1, 1, lane, 1}, b1 = {2, 2, 2, lane};
     v4i n_a0 = a0, n_a1 = a1, n_b0 = b0, n_b1 = b1, n_t0 = a0, n_t1 = a1;
-    // swizzled like k_sweep4: row R = lane&31, logical chunk c = lane>>5 (+2 for the second K half) -> physical c ^ ((R>>2)&3)
+    // swizzled like k_sweep5: row R = lane&31, logical chunk c = lane>>5 (+2 for the second K half) -> physical c ^ ((R>>2)&3)
     const int R = lane & 31, sw = (R >> 2) & 3, g = lane >> 5;
     const char* base = smem + R * 64 + (wid & 3) * 2048;
     const int o0 = (g ^ sw) << 4, o1 = ((2 + g) ^ sw) << 4;
@@ -67,7 +67,7 @@ __global__ __launch_bounds__(512, 2) void k(int iters, int* out, const char* src
             r0 = r1; r1 = r2; r2 = *(const v4i*)cur;
             cur += CSTEP; stg = (stg + 8192 == 6 * 8192) ? 0 : stg + 8192; if ((it & 1023) == 1023) cur -= 1024 * CSTEP;
         }
-        if (MODE & 2) {   // 6 fragment reads per 4 MFMAs, like k_sweep4
+        if (MODE & 2) {   // 6 fragment reads per 4 MFMAs, like a one-candidate k_sweep5 step
             const char* st = base + ((it & 3) * 8192);
             if (MODE & 16) {   // software pipelined: fragments read now are used in the NEXT step
                 n_a0 = *reinterpret_cast<const v4i*>(st + o0);
