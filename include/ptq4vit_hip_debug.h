@@ -32,6 +32,17 @@ int p4v_debug_set_tuning(int key, int value);
  * count as the lightest.  Exposed for the tests: a repeated or missing row would make the slice's partial sums an
  * invalid bound.  1 <= k <= n. */
 int p4v_debug_topk_rows(const float* d_mass, int segs, int n, int k, int32_t* d_idx, void* stream);
+/* The two fixed int8 planes of a twin row operand from one read of the source (k_pack_dual, the search's kernel for them):
+ * d_x [rows][cols] fp32 -> d_q1, d_q2 [rows][cols_padded] (cols_padded % 64 == 0, zero padded).  sos = 0: the post-GELU
+ * pair clamp(rint(x / *d_scale), 0, hi) and clamp(rint(x / const_scale), lo, 0); sos = 1: the split-of-softmax pair
+ * PACK_SOS_HI / PACK_SOS_LO of the split *d_scale with q - 1 = qmax - 1.  Exposed for the bit-exactness tests. */
+int p4v_debug_pack_dual(const float* d_x, long rows, long cols, long cols_padded, int sos, int lo, int hi, int qmax,
+                        const float* d_scale, float const_scale, int8_t* d_q1, int8_t* d_q2, void* stream);
+/* k_sweep6's epilogue operands in fragment order (k_prep_epi6): raw_out d_o (element (s, t) at s * o_ss + t * o_ts, s < sr
+ * stationary rows, t < tr streaming rows), the metric weight d_wt (wt_mode 1), the bias (indexed by t if bias_on_t, else
+ * by s) -> d_e, ceil(sr / 256) * ceil(tr / 64) tiles of 256 * 64 * 2 floats.  Exposed for the layout tests. */
+int p4v_debug_prep_epi6(const float* d_o, const float* d_wt, const float* d_bias, long o_ss, long o_ts, int sr, int tr,
+                        int bias_on_t, int wt_mode, int transposed, float* d_e, void* stream);
 
 #ifdef __cplusplus
 }

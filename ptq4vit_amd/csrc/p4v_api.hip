@@ -1153,8 +1153,7 @@ int run_pass(Ctx& c, Pass& ps) {
         pe.bias_on_t = a_search ? 0 : 1; pe.wt_mode = ps.cos6 ? 4 : ps.wt_mode;
         pe.stiles = s6_stiles; pe.ttiles = s6_ttiles; pe.E = epi6; pe.transposed = (ps.cos6 && !a_search) ? 1 : 0;
         if (zero_bias) CHK(q_fill(c, zero_bias, 0, sizeof(float) * (size_t)std::max(Mp, Np)));
-        const long chunks = (long)(epi6_bytes / 16);
-        CHK(enqueue(c, KERN(PrepEpi6Params, k_prep_epi6), dim3((unsigned)std::min<long>(cdiv(chunks, 256), 256L * 32)), dim3(256), 0, pe));
+        CHK(enqueue(c, KERN(PrepEpi6Params, k_prep_epi6), dim3((unsigned)std::min<long>((long)s6_stiles * s6_ttiles, 256L * 32)), dim3(256), 0, pe));
     }
     if (ec) ec->valid = true;
     if (big7 && !c.dry) {
@@ -3261,6 +3260,40 @@ int p4v_debug_topk_rows(const float* d_mass, int segs, int n, int k, int32_t* d_
     hipLaunchKernelGGL(k_topk_rows, dim3(segs), dim3(1024), 0, (hipStream_t)stream, TopkParams{d_mass, n, k, d_idx});
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+int p4v_debug_pack_dual(const float* d_x, long rows, long cols, long cols_padded, int sos, int lo, int hi, int qmax,
+                        const float* d_scale, float const_scale, int8_t* d_q1, int8_t* d_q2, void* stream) {
+    if (!d_x || !d_scale || !d_q1 || !d_q2 || rows <= 0 || cols <= 0 || cols_padded % 64 || cols_padded < cols ||
+        lo > 0 || hi < 0 || lo < -128 || hi > 127 || qmax < 2 || qmax > 128 || (!sos && !(const_scale > 0.0f)))
+        return fail(P4V_ERR_INVALID, "p4v_debug_pack_dual: bad argument");
+    PackParams p1 = pack2d(d_x, rows, cols, cols);
+    p1.Rp = (int)rows; p1.Kp = (int)cols_padded; p1.C = 1; p1.scales = d_scale; p1.qm1 = (float)(qmax - 1);
+    PackParams p2 = p1;
+    p1.dst = d_q1; p2.dst = d_q2;
+    if (sos) {
+        p1.mode = PACK_SOS_HI; p2.mode = PACK_SOS_LO;
+    } else {              // the post-GELU pair: [0, hi] on *d_scale, [lo, 0] on const_scale
+        p1.lo = 0; p1.hi = hi; p2.lo = lo; p2.hi = 0; p2.scales = nullptr; p2.neg_scale = const_scale;
+    }
+    if (!dual_pack_ok(p1, p2)) return fail(P4V_ERR_INVALID, "p4v_debug_pack_dual: not a dual pair");
+    Ctx c{(hipStream_t)stream, Arena(nullptr, 0), false};
+    const long total = rows * (cols_padded / 16);
+    if (total >= (1L << 31)) return fail(P4V_ERR_UNSUPPORTED, "p4v_debug_pack_dual: plane too large");
+    return enqueue(c, KERN(PackDualParams, k_pack_dual), dim3((unsigned)std::min<long>(cdiv(total, 256), 256L * 64)), dim3(256), 0,
+                   PackDualParams{p1, p2});
+}
+
+int p4v_debug_prep_epi6(const float* d_o, const float* d_wt, const float* d_bias, long o_ss, long o_ts, int sr, int tr,
+                        int bias_on_t, int wt_mode, int transposed, float* d_e, void* stream) {
+    if (!d_o || !d_bias || !d_e || (wt_mode == 1 && !d_wt) || sr <= 0 || tr <= 0 || wt_mode < 0 || wt_mode > 4)
+        return fail(P4V_ERR_INVALID, "p4v_debug_prep_epi6: bad argument");
+    PrepEpi6Params pe{};
+    pe.O = d_o; pe.Wt = d_wt ? d_wt : d_o; pe.bias = d_bias; pe.o_ss = o_ss; pe.o_ts = o_ts; pe.SR = sr; pe.TR = tr;
+    pe.bias_on_t = bias_on_t ? 1 : 0; pe.wt_mode = wt_mode; pe.transposed = transposed ? 1 : 0;
+    pe.stiles = cdiv(sr, 256); pe.ttiles = cdiv(tr, 64); pe.E = d_e;
+    Ctx c{(hipStream_t)stream, Arena(nullptr, 0), false};
+    return enqueue(c, KERN(PrepEpi6Params, k_prep_epi6), dim3((unsigned)std::min<long>((long)pe.stiles * pe.ttiles, 256L * 32)), dim3(256), 0, pe);
 }
 
 int p4v_pack_plane_i8(const p4v_plane_desc* d, const float* d_x, const float* d_scales, int8_t* d_q, void* stream) {

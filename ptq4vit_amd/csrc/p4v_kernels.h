@@ -507,35 +507,54 @@ __global__ __launch_bounds__(256) void k_pack(PackParams p) { k_pack_body<T>(p, 
 template <typename T>
 __global__ __launch_bounds__(256) void k_pack_g(GroupArgs<PackParams> a) { P4V_GROUP_ENTER(a); k_pack_body<T>(a.p[m_], vb_, vg_); }
 
+// The 16-element run [kc * 16, + 16) of row r: four dwordx4 loads where the view is plain (no im2col gather) and the run is
+// whole, in range and 16-byte aligned, else pack_load per element (0 outside the valid rows / columns).
+__device__ __forceinline__ void pack_load16(const PackParams& p, const float* zbase, int r, int kc, float (&x)[16]) {
+    const bool vec = !p.conv && p.s_k == 1 && r < p.R && kc * 16 + 16 <= p.K && (p.s_r & 3) == 0 &&
+                     ((((unsigned long long)zbase) & 15) == 0);
+    if (vec) {
+        const v4f* src4 = reinterpret_cast<const v4f*>(zbase + (long)r * p.s_r + kc * 16);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const v4f t = src4[q];
+            x[q * 4 + 0] = t[0]; x[q * 4 + 1] = t[1]; x[q * 4 + 2] = t[2]; x[q * 4 + 3] = t[3];
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) x[e] = pack_load(p, zbase, r, kc * 16 + e);
+    }
+}
+
 // PACK_TWIN_I8: both grid indices of the post-GELU twin (linear.py:605-606) in ONE int8 plane, row-major [Z][Rp][Kp], zero
 // padded.  A kernel of its own: the plane is small and fixed (one per weight-search pass) and k_pack's hot path is register
-// sensitive (the extra branch there cost it an occupancy step: 112 -> 155 VGPRs).  IEEE divisions, as the reference divides;
-// the supports are disjoint (x > 0 clamps the negative range to 0, x < 0 the positive one), so the sum is the index that is
-// not zero and fits the int8 range.
+// sensitive (the extra branch there cost it an occupancy step: 112 -> 155 VGPRs).  Each range is quant16_any with its own
+// fl(1/s), which equals the reference's IEEE division clamp(rint(x / s), lo, hi) byte for byte (its fallback IS that division,
+// padding included: x = 0 there).  The plane holds the byte of the float sum of the two indices; both are integers in
+// [-128, 127], so that byte is the sum mod 256, added bytewise without carries between the bytes.  (With positive scales
+// the supports are disjoint -- x > 0 clamps the negative range to 0, x < 0 the positive one -- and one of the two is 0.)
 __device__ __forceinline__ void k_pack_twin_body(const PackParams& p, const uint3 blockIdx, const uint3 gridDim) {
     const unsigned kchunks = p.Kp / 16;
     const unsigned total = (unsigned)p.Z * p.Rp * kchunks;
     const float s = p.scales[0], sn = p.neg_scale, flo = (float)p.lo, fhi = (float)p.hi;
+    const float rs = 1.0f / s, rn = 1.0f / sn;
+    const bool wide = !(fmaxf(-flo, fhi) < 129.0f);
     for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
         const unsigned row = i / kchunks;
         const int kc = (int)(i - row * kchunks);
         const int z = (int)(row / (unsigned)p.Rp);
         const int r = (int)(row - (unsigned)z * p.Rp);
-        const float* zbase = p.src + (long)z * p.s_z;
-        int w[4];
+        float x[16];
+        pack_load16(p, p.src + (long)z * p.s_z, r, kc, x);
+        v4i a, b;
+        quant16_any(x, s, rs, 0.0f, fhi, wide, a);
+        quant16_any(x, sn, rn, flo, 0.0f, wide, b);
+        v4i w;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            int acc = 0;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int k = kc * 16 + q * 4 + e;
-                const float x = pack_load(p, zbase, r, k);           // 0 outside the valid rows / columns
-                const float v = fminf(fmaxf(rintf(x / s), 0.0f), fhi) + fminf(fmaxf(rintf(x / sn), flo), 0.0f);
-                acc |= ((int)v & 0xff) << (8 * e);
-            }
-            w[q] = acc;
+            const unsigned ua = (unsigned)a[q], ub = (unsigned)b[q];
+            w[q] = (int)(((ua & 0x7f7f7f7fu) + (ub & 0x7f7f7f7fu)) ^ ((ua ^ ub) & 0x80808080u));
         }
-        *reinterpret_cast<v4i*>(reinterpret_cast<int8_t*>(p.dst) + (((long)z * p.Rp + r) * p.Kp + (long)kc * 16)) = v4i{w[0], w[1], w[2], w[3]};
+        __builtin_nontemporal_store(w, reinterpret_cast<v4i*>(reinterpret_cast<int8_t*>(p.dst) + (((long)z * p.Rp + r) * p.Kp + (long)kc * 16)));
     }
 }
 __global__ __launch_bounds__(256) void k_pack_twin(PackParams p) { k_pack_twin_body(p, P4V_BIDX, P4V_GDIM); }
@@ -546,7 +565,9 @@ __global__ __launch_bounds__(256) void k_pack_twin_g(GroupArgs<PackParams> a) { 
 // (linear.py:605-606: two PACK_SYM planes with clamps [0, hi] / [lo, 0]) or the split-of-softmax pair (matmul.py:595-598:
 // PACK_SOS_HI / PACK_SOS_LO).  Same arithmetic as k_pack's per-element path (pack_value: IEEE division), two fixed planes
 // (C = 1), one scale each (no blocks), row-major [Z][Rp][Kp].  Memory-bound: the source is read once instead of twice
-// (quant_forward at batch 128: 310 MB per fc2, 238 MB per attention-probability operand).
+// (quant_forward at batch 128: 310 MB per fc2, 238 MB per attention-probability operand).  (quant16_any in place of the
+// divisions was measured and not kept: 109 VGPRs instead of 56 halve the occupancy this latency-bound kernel lives on --
+// the attention-probability rows, 197 floats apart, take the per-element loads -- 300 -> 349 us per grouped launch.)
 struct PackDualParams { PackParams p; PackParams p2; };
 __device__ __forceinline__ void k_pack_dual_body(const PackDualParams& a_, const uint3 blockIdx, const uint3 gridDim) {
     const auto& [p, p2] = a_;
@@ -561,18 +582,7 @@ __device__ __forceinline__ void k_pack_dual_body(const PackDualParams& a_, const
         const float* zbase = p.zdiv > 0 ? p.src + (long)(z / p.zdiv) * p.s_z2 + (long)(z % p.zdiv) * p.s_z
                                         : p.src + (long)z * p.s_z;
         float x[16];
-        const bool vec = p.s_k == 1 && r < p.R && kc * 16 + 16 <= p.K && (p.s_r & 3) == 0 && ((((unsigned long long)zbase) & 15) == 0);
-        if (vec) {
-            const v4f* src4 = reinterpret_cast<const v4f*>(zbase + (long)r * p.s_r + kc * 16);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const v4f t = src4[q];
-                x[q * 4 + 0] = t[0]; x[q * 4 + 1] = t[1]; x[q * 4 + 2] = t[2]; x[q * 4 + 3] = t[3];
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) x[e] = pack_load(p, zbase, r, kc * 16 + e);
-        }
+        pack_load16(p, zbase, r, kc, x);
         const bool live = r < p.R;
         int w1[4], w2[4];
 #pragma unroll
@@ -2613,30 +2623,70 @@ struct PrepEpi6Params {
     float* E;
     int transposed;     // cosine weight search (EPI_COS_T): a lane's four values are four STREAMING rows of one stationary row
 };
+// One workgroup per 256 x 64 tile.  In the source, a chunk's four values are one row and four consecutive columns of a 32 x 32
+// block, rows = the streaming rows (plain) or the stationary rows (transposed).  Both production orientations have the columns
+// contiguous (the activation search: features; the cosine weight search: features again), so every lane makes one dwordx4 load
+// per operand for both halves, k = 0 and k = 1, and the bias (indexed by the column there) is one dwordx4 too.  Wave w takes
+// quarter q = w of a 32 x 32 block, so the four waves read whole 128-byte lines of 32 rows together, and each wave stores its
+// two 1 KB chunk runs (k = 0, 1) contiguously.  Other strides (the weight search with TUNE_EPI6W) load element by element.
 __device__ __forceinline__ void k_prep_epi6_body(const PrepEpi6Params& p, const uint3 blockIdx, const uint3 gridDim) {
-    const long total = (long)p.stiles * p.ttiles * 8 * 2 * 4 * 2 * 64;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const int lane = (int)(i & 63), k = (int)((i >> 6) & 1), q = (int)((i >> 7) & 3), cb = (int)((i >> 9) & 1), b = (int)((i >> 10) & 7);
-        const long t = i >> 13;
-        const int st = (int)(t % p.stiles), tt = (int)(t / p.stiles);
-        const int g = lane >> 5, l31 = lane & 31;
-        // plain: stationary rows st*256 + b*32 + 8q + 4g + e at streaming row tt*64 + cb*32 + l31;
-        // transposed: streaming rows tt*64 + cb*32 + 8q + 4g + e at stationary row st*256 + b*32 + l31
-        const int tr0 = tt * 64 + cb * 32 + (p.transposed ? 8 * q + 4 * g : l31);
-        const int sr0 = st * 256 + b * 32 + (p.transposed ? l31 : 8 * q + 4 * g);
-        v4f v = {0.f, 0.f, 0.f, 0.f};
+    const bool tr_cols = p.transposed != 0;                  // columns = streaming rows
+    const long rs = tr_cols ? p.o_ss : p.o_ts, cs = tr_cols ? p.o_ts : p.o_ss;
+    const int nrow = tr_cols ? p.SR : p.TR, ncol = tr_cols ? p.TR : p.SR;
+    const bool bias_col = (p.bias_on_t != 0) == tr_cols;     // the bias follows the column index
+    const bool wt = p.wt_mode == 1;
+    const bool vec = cs == 1 && (rs & 3) == 0 && bias_col &&
+                     ((((unsigned long long)p.O) | (wt ? (unsigned long long)p.Wt : 0ull) | ((unsigned long long)p.bias)) & 15) == 0;
+    const int lane = threadIdx.x & 63, q = threadIdx.x >> 6, g = lane >> 5, l31 = lane & 31;
+    const int ntiles = p.stiles * p.ttiles;
+    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const int st = t % p.stiles, tt = t / p.stiles;
+#pragma unroll 1
+        for (int u0 = 0; u0 < 16; u0 += 4) {
+            // four 32 x 32 blocks (b, cb) = (u / 2, u % 2) in flight: the loads of all four before the first store
+            v4f o[4], w[4], bs[4];
+            int row[4], col0[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int sr = sr0 + (p.transposed ? 0 : e), tr = tr0 + (p.transposed ? e : 0);
-            if (sr < p.SR && tr < p.TR) {
-                const long idx = (long)sr * p.o_ss + (long)tr * p.o_ts;
-                const float o = p.O[idx];
-                const float bs = p.bias[p.bias_on_t ? tr : sr];
-                if (k == 0) v[e] = p.wt_mode == 4 ? o : o - bs;
-                else v[e] = p.wt_mode == 1 ? p.Wt[idx] : p.wt_mode == 2 ? o : p.wt_mode == 3 ? fabsf(o) : p.wt_mode == 4 ? bs : 1.0f;
+            for (int j = 0; j < 4; ++j) {
+                const int b = (u0 + j) >> 1, cb = (u0 + j) & 1;
+                const int sb = st * 256 + b * 32, tb = tt * 64 + cb * 32;
+                row[j] = (tr_cols ? sb : tb) + l31;
+                col0[j] = (tr_cols ? tb : sb) + 8 * q + 4 * g;
+                o[j] = v4f{0.f, 0.f, 0.f, 0.f}; w[j] = o[j]; bs[j] = o[j];
+                if (row[j] >= nrow) continue;
+                if (vec && col0[j] + 4 <= ncol) {
+                    const long idx = (long)row[j] * rs + col0[j];
+                    o[j] = *reinterpret_cast<const v4f*>(p.O + idx);
+                    if (wt) w[j] = *reinterpret_cast<const v4f*>(p.Wt + idx);
+                    bs[j] = *reinterpret_cast<const v4f*>(p.bias + col0[j]);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int col = col0[j] + e;
+                        if (col >= ncol) continue;
+                        const long idx = (long)row[j] * rs + (long)col * cs;
+                        o[j][e] = p.O[idx];
+                        if (wt) w[j][e] = p.Wt[idx];
+                        bs[j][e] = p.bias[bias_col ? col : row[j]];
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int b = (u0 + j) >> 1, cb = (u0 + j) & 1;
+                v4f v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (row[j] >= nrow || col0[j] + e >= ncol) continue;      // zero where either row is padding
+                    const float x = o[j][e], bx = bs[j][e];
+                    v0[e] = p.wt_mode == 4 ? x : x - bx;
+                    v1[e] = wt ? w[j][e] : p.wt_mode == 2 ? x : p.wt_mode == 3 ? fabsf(x) : p.wt_mode == 4 ? bx : 1.0f;
+                }
+                v4f* E = reinterpret_cast<v4f*>(p.E) + ((((long)(t * 8 + b) * 2 + cb) * 4 + q) * 2) * 64 + lane;
+                E[0] = v0;
+                E[64] = v1;
             }
         }
-        reinterpret_cast<v4f*>(p.E)[i] = v;
     }
 }
 __global__ __launch_bounds__(256) void k_prep_epi6(PrepEpi6Params p) { k_prep_epi6_body(p, P4V_BIDX, P4V_GDIM); }

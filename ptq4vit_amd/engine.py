@@ -626,6 +626,35 @@ def debug_topk_rows(mass, k):
     return out
 
 
+def debug_pack_dual(x2d, *, sos, scale, lo, hi, qmax, const_scale=0.0):
+    """Both int8 planes of a twin row operand from one launch (k_pack_dual): `sos` False the post-GELU pair ([0, hi] on
+    `scale`, [lo, 0] on `const_scale`), True the split-of-softmax pair (split `scale`).  Returns the two [rows][cols] planes
+    (padding stripped) and the padded ones.  For the tests."""
+    x2d = x2d.contiguous().float()
+    rows, cols = x2d.shape
+    colsp = (cols + 63) // 64 * 64
+    q1 = torch.empty(rows, colsp, dtype=torch.int8, device=x2d.device)
+    q2 = torch.empty_like(q1)
+    sc = torch.tensor([float(scale)], dtype=torch.float32, device=x2d.device)
+    with torch.cuda.device(x2d.device):
+        rc = _lib.load().p4v_debug_pack_dual(ptr(x2d), rows, cols, colsp, int(bool(sos)), int(lo), int(hi), int(qmax), ptr(sc),
+                                             float(const_scale), ptr(q1), ptr(q2), stream_ptr(x2d.device))
+    _lib.check(rc, "p4v_debug_pack_dual")
+    return q1[:, :cols], q2[:, :cols], q1, q2
+
+
+def debug_prep_epi6(o, wt, bias, *, o_ss, o_ts, sr, tr, bias_on_t, wt_mode, transposed):
+    """k_sweep6's epilogue operands in fragment order (k_prep_epi6) from the flat fp32 tensors `o`, `wt` (or None), `bias`:
+    a flat fp32 tensor of ceil(sr / 256) * ceil(tr / 64) * 256 * 64 * 2 values.  For the tests."""
+    n = -(-sr // 256) * -(-tr // 64) * 256 * 64 * 2
+    e = torch.full((n,), float("nan"), dtype=torch.float32, device=o.device)
+    with torch.cuda.device(o.device):
+        rc = _lib.load().p4v_debug_prep_epi6(ptr(o), ptr(wt) if wt is not None else None, ptr(bias), int(o_ss), int(o_ts),
+                                             int(sr), int(tr), int(bias_on_t), int(wt_mode), int(transposed), ptr(e),
+                                             stream_ptr(o.device))
+    _lib.check(rc, "p4v_debug_prep_epi6")
+    return e
+
 def stats_reset():
     _lib.load().p4v_stats_reset()
 
