@@ -38,6 +38,18 @@ int p4v_debug_topk_rows(const float* d_mass, int segs, int n, int k, int32_t* d_
  * PACK_SOS_HI / PACK_SOS_LO of the split *d_scale with q - 1 = qmax - 1.  Exposed for the bit-exactness tests. */
 int p4v_debug_pack_dual(const float* d_x, long rows, long cols, long cols_padded, int sos, int lo, int hi, int qmax,
                         const float* d_scale, float const_scale, int8_t* d_q1, int8_t* d_q2, void* stream);
+/* The candidate planes of one operand as the search packs them (k_pack; k_pack1 for a single plane and for the one
+ * candidate of a range with live_max == 1): d_x [rows][cols] fp32 ->
+ * clamp(rint(x / d_scales[c]), lo, hi) for the candidates c < n_cands, zero padded to [rows_padded][cols_padded]
+ * (cols_padded % 64 == 0).  layout 0: [c][row][k]; 1: [row][c][k]; 2: [row][c / 2][k / 64][c % 2][64] (an odd n_cands padded
+ * to a pair); 3: MFMA-fragment order of ONE plane (rows_padded % 64 == 0; every packed candidate lands in it).  d_crange
+ * (optional, two ints on the device): only the candidates in [d_crange[0], d_crange[1]) are packed, and of those only the
+ * ones whose d_done flag (optional, one byte per candidate) is 0; live_max >= 0: what the host knows of that range -- an upper
+ * bound of its length (0: empty, nothing is launched) --, < 0: nothing.  general != 0: k_pack also where k_pack1 would
+ * take the launch.  Bytes of candidates that are not packed are left as they were.  Exposed for the bit-exactness tests. */
+int p4v_debug_pack_cands(const float* d_x, long rows, long cols, long rows_padded, long cols_padded, int layout, int lo, int hi,
+                         const float* d_scales, int n_cands, const int* d_crange, const unsigned char* d_done, int live_max,
+                         int general, int8_t* d_q, void* stream);
 /* k_sweep6's epilogue operands in fragment order (k_prep_epi6): raw_out d_o (element (s, t) at s * o_ss + t * o_ts, s < sr
  * stationary rows, t < tr streaming rows), the metric weight d_wt (wt_mode 1), the bias (indexed by t if bias_on_t, else
  * by s) -> d_e, ceil(sr / 256) * ceil(tr / 64) tiles of 256 * 64 * 2 floats.  Exposed for the layout tests. */

@@ -98,6 +98,7 @@ EXPORTS = [
     "p4v_quantize_i8", "p4v_pack_plane_i8", "p4v_fake_quant", "p4v_export_quantize", "p4v_multi_copy",
     "p4v_stats_enable", "p4v_stats_reset", "p4v_stats_get", "p4v_stats_launches", "p4v_prune_counters",
     "p4v_debug_set_variant", "p4v_debug_set_tuning", "p4v_debug_topk_rows", "p4v_debug_pack_dual", "p4v_debug_prep_epi6",
+    "p4v_debug_pack_cands",
 ]
 
 _lib = None
@@ -170,6 +171,9 @@ def load():
     lib.p4v_debug_topk_rows.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp]
     lib.p4v_debug_pack_dual.restype = C.c_int
     lib.p4v_debug_pack_dual.argtypes = [fp, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, fp, C.c_float, vp, vp, vp]
+    lib.p4v_debug_pack_cands.restype = C.c_int
+    lib.p4v_debug_pack_cands.argtypes = [fp, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, fp, C.c_int, vp, vp,
+                                         C.c_int, C.c_int, vp, vp]
     lib.p4v_debug_prep_epi6.restype = C.c_int
     lib.p4v_debug_prep_epi6.argtypes = [fp, fp, fp, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, vp]
     lib.p4v_debug_set_variant.restype = C.c_int

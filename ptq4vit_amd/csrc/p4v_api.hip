@@ -568,23 +568,40 @@ float cvt_bias(Ctx& c) {
     const int st = g_cvt_state.load(std::memory_order_acquire);
     return st == 1 ? 128.5f : st == 2 ? 128.0f : 0.0f;
 }
-template <typename T> int launch_pack(Ctx& c, const PackParams& p_) {
+// what k_pack1 covers: one int8 PACK_SYM plane in any layout, scales per plane / row block / batch block -- a single plane, or
+// the one candidate of a device-side range that the host knows to hold at most one
+inline bool pack1_ok(const PackParams& p, int live_max) {
+    return p.mode == PACK_SYM && !p.conv && !(p.blk_mode == 1 && p.blk_div2) && p.lo >= -128 && p.hi <= 127 && p.lo <= p.hi &&
+           (p.crange ? live_max == 1 : p.C == 1) && (p.c_inner != 3 || (p.Rp % 64 == 0 && p.Kp % 64 == 0));
+}
+std::atomic<int> g_pack_general{0};   // p4v_debug_pack_cands: single planes through k_pack as well (kernel-vs-kernel test)
+// `live_max`: what the host knows of a pruned launch -- an upper bound of the number of candidates in p.crange - p.c_base that
+// fall inside [0, p.C) (< 0: nothing; 0: none, no launch).  The candidate groups of k_pack are counted from the first candidate
+// of the range, so ceil(live_max / PACK_CG) of them cover it wherever it lies.
+template <typename T> int launch_pack(Ctx& c, const PackParams& p_, int live_max = -1) {
     if (c.dry) return 0;
     PackParams p = p_;
+    if (p.crange && live_max == 0) return 0;
     // the full symmetric 8-bit grid: quant16_sat8 once the conversion has been probed (the *_impl entry points do that first);
     // tuning 12 = 11 keeps quant_fast1 (A/B)
     p.qbias = (sizeof(T) == 1 && p.mode == PACK_SYM && p.lo == -128 && p.hi == 127 && tune(TUNE_B1_PATH) != 11) ? cvt_bias(c) : 0.0f;
     const long total = (long)p.Z * p.Rp * (p.Kp / 16);
     if (total >= (1L << 31)) return fail(P4V_ERR_UNSUPPORTED, "operand plane too large for k_pack (%ld 16-element runs)", total);
-    // (a pruned launch lets most candidate groups exit at once: fewer, longer-running workgroups)
-    const int blocks = (int)std::min<long>(cdiv(total, 256), p.crange ? 256L * 12 : 256L * 64);
+    // candidate groups: all of C, or -- a pruned launch whose length the host knows -- the ones that can be live
+    const int groups = cdiv((p.crange && live_max > 0) ? std::min(p.C, live_max) : p.C, PACK_CG);
+    // A pruned launch of unknown length lets most of its groups exit at once: fewer, longer-running workgroups.  One whose
+    // groups are all live is an unpruned launch of that many groups: the same 256 * 64 workgroups over all of them.
+    const long cap = !p.crange ? 256L * 64 : live_max > 0 ? std::max(256L * 12, 256L * 64 / groups) : 256L * 12;
+    const int blocks = (int)std::min<long>(cdiv(total, 256), cap);
     if (p.mode == PACK_TWIN_I8) {
         if (sizeof(T) != 1 || p.C != 1 || p.c_inner != 0 || !p.scales || p.conv || p.zdiv > 0)
             return fail(P4V_ERR_UNSUPPORTED, "merged twin plane: one fixed row-major int8 plane only");
         return enqueue(c, KERN(PackParams, k_pack_twin), dim3(blocks), dim3(256), 0, p);
     }
-    if (tune(TUNE_PRINT) > 1) fprintf(stderr, "[p4v] k_pack stage %d: Z %d Rp %d Kp %d C %d crange %d done %d layout %d blocks %d\n", g_stage, p.Z, p.Rp, p.Kp, p.C, p.crange != nullptr, p.done != nullptr, p.c_inner, blocks);
-    return enqueue(c, KERN_T(PackParams, k_pack, T), dim3(blocks, cdiv(p.C, PACK_CG)), dim3(256), 0, p);
+    const bool single = sizeof(T) == 1 && pack1_ok(p, live_max) && !g_pack_general.load(std::memory_order_relaxed);
+    if (tune(TUNE_PRINT) > 1) fprintf(stderr, "[p4v] %s stage %d: Z %d Rp %d Kp %d C %d crange %d done %d live_max %d layout %d grid %d x %d\n", single ? "k_pack1" : "k_pack", g_stage, p.Z, p.Rp, p.Kp, p.C, p.crange != nullptr, p.done != nullptr, live_max, p.c_inner, blocks, single ? 1 : groups);
+    if (single) return enqueue(c, KERN(PackParams, k_pack1), dim3(blocks), dim3(256), 0, p);
+    return enqueue(c, KERN_T(PackParams, k_pack, T), dim3(blocks, groups), dim3(256), 0, p);
 }
 
 // (inside a group the lock-step members share the chip: each plans for its share of the workgroup slots)
@@ -952,6 +969,8 @@ struct Pass {
                               // one score block (run_pass decides; otherwise every block sweeps `crange`, a superset)
     int host_lo, host_hi;     // what the host read of `crange` (host_hi > host_lo: known) -- the launch geometry is planned for the
     const int* host_rblk;     // candidates that will run -- and of `crange_blk` (nj <= MIR_BLK; nullptr: unknown): closed blocks are not launched
+    int host_len;             // > 0: the host does not know where `crange` lies but knows it holds at most this many candidates
+                              // (stage B1 of a single score block: the slice winner) -- k_pack launches that many, counted from crange[0]
     float* scores_keep;
     bool no_select;
     bool prunable;            // set by the *_impl callers for passes whose score is minus a sum of non-negative terms
@@ -1130,7 +1149,11 @@ int run_pass(Ctx& c, Pass& ps) {
             pk.crange = ps.crange; pk.c_base = c0;
             pk.done = (pc && pc->done) ? pc->done : nullptr;
         }
-        CHK(ps.i8 ? launch_pack<int8_t>(c, pk) : launch_pack<float>(c, pk));
+        // what the host knows of the range (stages A2 / B2: the survivor range it read back; stage B1: its length)
+        int live_max = -1;
+        if (pk.crange && ps.host_hi > ps.host_lo) live_max = std::max(0, std::min(ps.host_hi, c0 + nc) - std::max(ps.host_lo, c0));
+        else if (pk.crange && ps.host_len > 0) live_max = std::min(ps.host_len, nc);
+        CHK(ps.i8 ? launch_pack<int8_t>(c, pk, live_max) : launch_pack<float>(c, pk, live_max));
         return 0;      // (the finish of this pass flags the groups as packed: FinishParams.mark_done)
     };
     if (ps.pack_only) {
@@ -1796,7 +1819,7 @@ int run_pass_pruned_impl(Ctx& c, Pass& ps) {
         swap(b1.row.pk.scales); swap(b1.row2.pk.scales); swap(b1.col.pk.scales);
         swap(b1.s1.x); swap(b1.s1.y); swap(b1.s2.x); swap(b1.s2.y);
         b1.cands = vrow;
-    } else b1.crange = r1;
+    } else { b1.crange = r1; if (ps.nj == 1) b1.host_len = 1; }     // (one score block: r1 = [winner, winner + 1), k_prune_pick)
     // ONE candidate per score block over all samples: the kernel built for that (k_bound).
     // Its totals are summed in another order than the sweeps', so from here on nothing may depend on stage B1's numbers but the
     // bound: the selections below are either "the only survivor of every block" (no totals involved) or come from stage B2,
@@ -3282,6 +3305,25 @@ int p4v_debug_pack_dual(const float* d_x, long rows, long cols, long cols_padded
     if (total >= (1L << 31)) return fail(P4V_ERR_UNSUPPORTED, "p4v_debug_pack_dual: plane too large");
     return enqueue(c, KERN(PackDualParams, k_pack_dual), dim3((unsigned)std::min<long>(cdiv(total, 256), 256L * 64)), dim3(256), 0,
                    PackDualParams{p1, p2});
+}
+
+int p4v_debug_pack_cands(const float* d_x, long rows, long cols, long rows_padded, long cols_padded, int layout, int lo, int hi,
+                         const float* d_scales, int n_cands, const int* d_crange, const unsigned char* d_done, int live_max,
+                         int general, int8_t* d_q, void* stream) {
+    if (!d_x || !d_scales || !d_q || rows <= 0 || cols <= 0 || rows_padded < rows || cols_padded % 64 || cols_padded < cols ||
+        layout < 0 || layout > 3 || (layout == 3 && rows_padded % 64) || lo > hi || lo < -128 || hi > 127 || n_cands <= 0 ||
+        (d_done && !d_crange) || (live_max >= 0 && !d_crange))
+        return fail(P4V_ERR_INVALID, "p4v_debug_pack_cands: bad argument");
+    Ctx c{(hipStream_t)stream, Arena(nullptr, 0), false};
+    cvt_bias(c);
+    PackParams p = pack2d(d_x, rows, cols, cols);
+    p.Rp = (int)rows_padded; p.Kp = (int)cols_padded; p.dst = d_q; p.C = n_cands; p.c_inner = layout;
+    p.scales = d_scales; p.sc_cs = 1; p.lo = lo; p.hi = hi;
+    p.crange = d_crange; p.c_base = 0; p.done = d_done;
+    g_pack_general.store(general ? 1 : 0, std::memory_order_relaxed);
+    const int r = launch_pack<int8_t>(c, p, live_max);
+    g_pack_general.store(0, std::memory_order_relaxed);
+    return r;
 }
 
 int p4v_debug_prep_epi6(const float* d_o, const float* d_wt, const float* d_bias, long o_ss, long o_ts, int sr, int tr,

@@ -383,13 +383,18 @@ template <typename T>
 __device__ __forceinline__ void k_pack_body(const PackParams& p, const uint3 blockIdx, const uint3 gridDim) {
     const unsigned kchunks = p.Kp / 16;
     const unsigned total = (unsigned)p.Z * p.Rp * kchunks;      // < 2^31: checked by the launcher
-    const int cbeg = blockIdx.y * PACK_CG, cend = min(p.C, cbeg + PACK_CG);
-    unsigned need = (1u << (cend - cbeg)) - 1u;            // the candidates of this group to pack (bit j: candidate cbeg + j)
+    int cbeg = blockIdx.y * PACK_CG, cend = min(p.C, cbeg + PACK_CG);
     if (p.crange) {
-        const int a = p.crange[0] - p.c_base, b = p.crange[1] - p.c_base;
-        if (cend <= a || cbeg >= b) return;
+        // a pruned pass: the groups are counted from the first candidate of the device-side range, so a launch needs only
+        // ceil(length / PACK_CG) of them -- the launcher sizes gridDim.y by what the host knows of the length (all of C if nothing)
+        const int a = max(p.crange[0] - p.c_base, 0), b = min(p.crange[1] - p.c_base, p.C);
+        cbeg = a + (int)blockIdx.y * PACK_CG; cend = min(b, cbeg + PACK_CG);
+        if (cbeg >= cend) return;
+    }
+    unsigned need = (1u << (cend - cbeg)) - 1u;            // the candidates of this group to pack (bit j: candidate cbeg + j)
+    if (p.crange && p.done) {
         for (int j = 0; j < PACK_CG; ++j)
-            if (cbeg + j < a || cbeg + j >= b || (p.done && cbeg + j < cend && p.done[cbeg + j])) need &= ~(1u << j);
+            if (cbeg + j < cend && p.done[cbeg + j]) need &= ~(1u << j);
         if (!need) return;
     }
     for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
@@ -559,6 +564,73 @@ __device__ __forceinline__ void k_pack_twin_body(const PackParams& p, const uint
 }
 __global__ __launch_bounds__(256) void k_pack_twin(PackParams p) { k_pack_twin_body(p, P4V_BIDX, P4V_GDIM); }
 __global__ __launch_bounds__(256) void k_pack_twin_g(GroupArgs<PackParams> a) { P4V_GROUP_ENTER(a); k_pack_twin_body(a.p[m_], vb_, vg_); }
+
+// ONE int8 PACK_SYM plane: the fixed operand of a pass, the fragment-order operands of k_sweep6 / k_bound, the slice planes,
+// p4v_quantize_i8 (C == 1, no candidate range) -- and the one candidate of a pruned launch whose range the host knows to hold
+// at most one (stage B1 of a single score block: the slice winner; C candidates, p.crange says which).  Any plane layout
+// (c_inner 0..3), one scale per plane or per row / batch block (blk_mode 1 without a k split, blk_mode 2).  k_pack carries
+// ten scale slots, the candidate loop and its mask, a division per candidate and the layout switch through this case; here it
+// is k_pack_twin's pattern: pack_load16, one reciprocal, quant16_sat8 on the full symmetric 8-bit grid and quant16_any
+// otherwise (each equals the reference's IEEE division byte for byte: their fallback IS that division), one 16-byte streaming
+// store.  In fragment order (c_inner 3) the threads are numbered by DESTINATION chunk: a wave stores 1 KB contiguous and reads
+// 32 rows x 128 B (whole lines); numbered by source run, as in k_pack, its 64 stores are 16-byte pieces 512 B apart.  Bytes of
+// padding (rows >= R, columns >= K) are zero whatever the scale is.  Everything else (im2col views, per-k scale blocks, the
+// SoS modes, fp32 planes, ranges of unknown length) stays on k_pack: launch_pack decides (pack1_ok).
+__device__ __forceinline__ void k_pack1_body(const PackParams& p, const uint3 blockIdx, const uint3 gridDim) {
+    const unsigned kchunks = p.Kp / 16;
+    const unsigned total = (unsigned)p.Z * p.Rp * kchunks;      // < 2^31: checked by the launcher
+    int c = 0;
+    if (p.crange) {
+        c = max(p.crange[0] - p.c_base, 0);
+        if (c >= min(p.crange[1] - p.c_base, p.C) || (p.done && p.done[c])) return;
+    }
+    const long sc_off = (long)c * p.sc_cs;       // (an offset, not a pointer derived from p: that one sent the grouped entry's argument block to scratch)
+    const float flo = (float)p.lo, fhi = (float)p.hi;
+    const bool one_scale = p.blk_mode == 0 || !p.scales;
+    float s = p.scales ? p.scales[sc_off] : p.neg_scale;
+    float rcp = 1.0f / s;
+    const unsigned plane = (unsigned)p.Rp * kchunks, ktiles = (unsigned)p.Kp >> 6;
+    const long cbase = p.c_inner == 0 ? (long)c * p.Z * p.Rp * p.Kp : p.c_inner == 1 ? (long)c * p.Kp
+                     : p.c_inner == 2 ? (long)(c & ~1) * p.Kp + (c & 1) * 64 : 0;
+    const long rstride = p.c_inner == 1 ? (long)p.C * p.Kp : p.c_inner == 2 ? (long)((p.C + 1) & ~1) * p.Kp : (long)p.Kp;
+    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+        int z, r, kc;
+        if (p.c_inner == 3) {          // i = destination chunk: bits [0,5) r % 32, 5 kc % 2, 6 (kc / 2) % 2, 7 (r / 32) % 2, then (r / 64, kc / 4)
+            z = (int)(i / plane);
+            const unsigned d = i - (unsigned)z * plane, t = d >> 8;
+            const unsigned r64 = t / ktiles, kt = t - r64 * ktiles;
+            r = (int)(r64 * 64 + ((d >> 7) & 1) * 32 + (d & 31));
+            kc = (int)(kt * 4 + ((d >> 6) & 1) * 2 + ((d >> 5) & 1));
+        } else {
+            const unsigned row = i / kchunks;
+            kc = (int)(i - row * kchunks);
+            z = (int)(row / (unsigned)p.Rp);
+            r = (int)(row - (unsigned)z * p.Rp);
+        }
+        const float* zbase = p.zdiv > 0 ? p.src + (long)(z / p.zdiv) * p.s_z2 + (long)(z % p.zdiv) * p.s_z
+                                        : p.src + (long)z * p.s_z;
+        float x[16];
+        pack_load16(p, zbase, r, kc, x);
+        if (!one_scale) { s = p.scales[sc_off + pack_blk(p, z, r, 0)]; rcp = 1.0f / s; }
+        v4i w;
+        if (p.qbias != 0.0f) quant16_sat8(x, s, rcp, p.qbias, w);
+        else quant16_any(x, s, rcp, flo, fhi, false, w);
+        const int nvalid = r < p.R ? p.K - kc * 16 : 0;        // bytes of this run that are not padding
+        if (nvalid < 16) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int rem = nvalid - 4 * q;
+                w[q] = rem >= 4 ? w[q] : rem <= 0 ? 0 : (int)((unsigned)w[q] & ((1u << (8 * rem)) - 1u));
+            }
+        }
+        const long o = p.c_inner == 3 ? (long)i * 16
+                     : p.c_inner == 2 ? cbase + ((long)z * p.Rp + r) * rstride + (long)(kc >> 2) * 128 + (kc & 3) * 16
+                                      : cbase + ((long)z * p.Rp + r) * rstride + (long)kc * 16;
+        __builtin_nontemporal_store(w, reinterpret_cast<v4i*>(reinterpret_cast<int8_t*>(p.dst) + o));
+    }
+}
+__global__ __launch_bounds__(256) void k_pack1(PackParams p) { k_pack1_body(p, P4V_BIDX, P4V_GDIM); }
+__global__ __launch_bounds__(256) void k_pack1_g(GroupArgs<PackParams> a) { P4V_GROUP_ENTER(a); k_pack1_body(a.p[m_], vb_, vg_); }
 
 
 // Both int8 planes of a twin operand from ONE read of the source: the post-GELU twin's positive / negative range

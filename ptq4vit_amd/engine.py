@@ -643,6 +643,32 @@ def debug_pack_dual(x2d, *, sos, scale, lo, hi, qmax, const_scale=0.0):
     return q1[:, :cols], q2[:, :cols], q1, q2
 
 
+def debug_pack_cands(x2d, scales, *, layout, lo, hi, rows_padded=None, crange=None, done=None, live_max=-1, general=False,
+                     out=None):
+    """The candidate planes of `x2d` [rows][cols] on the scales `scales` [C] as the search packs them (k_pack, k_pack1 for a
+    single plane; p4v_debug_pack_cands): layout 0 [C][rows_padded][cols_padded], 1 [rows_padded][C][cols_padded], 2 candidate
+    pairs interleaved per 64-byte k-tile, 3 one plane in MFMA-fragment order.  `crange` (int32 [2] on the device) / `done`
+    (uint8 [C]) / `live_max` as in the header; `out`: the destination (flat int8, left as it is where nothing is packed).  Returns
+    the flat int8 buffer.  For the tests."""
+    x2d = x2d.contiguous().float()
+    scales = scales.contiguous().float()
+    rows, cols = x2d.shape
+    n = scales.numel()
+    colsp = (cols + 63) // 64 * 64
+    rowsp = rows if rows_padded is None else int(rows_padded)
+    size = rowsp * colsp * (1 if layout == 3 else (n + 1) // 2 * 2 if layout == 2 else n)
+    if out is None:
+        out = torch.zeros(size, dtype=torch.int8, device=x2d.device)
+    assert out.dtype == torch.int8 and out.is_contiguous() and out.numel() >= size
+    with torch.cuda.device(x2d.device):
+        rc = _lib.load().p4v_debug_pack_cands(ptr(x2d), rows, cols, rowsp, colsp, int(layout), int(lo), int(hi), ptr(scales), n,
+                                              ptr(crange) if crange is not None else None,
+                                              ptr(done) if done is not None else None, int(live_max), int(bool(general)),
+                                              ptr(out), stream_ptr(x2d.device))
+    _lib.check(rc, "p4v_debug_pack_cands")
+    return out
+
+
 def debug_prep_epi6(o, wt, bias, *, o_ss, o_ts, sr, tr, bias_on_t, wt_mode, transposed):
     """k_sweep6's epilogue operands in fragment order (k_prep_epi6) from the flat fp32 tensors `o`, `wt` (or None), `bias`:
     a flat fp32 tensor of ceil(sr / 256) * ceil(tr / 64) * 256 * 64 * 2 values.  For the tests."""
