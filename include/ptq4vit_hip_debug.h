@@ -50,6 +50,15 @@ int p4v_debug_pack_dual(const float* d_x, long rows, long cols, long cols_padded
 int p4v_debug_pack_cands(const float* d_x, long rows, long cols, long rows_padded, long cols_padded, int layout, int lo, int hi,
                          const float* d_scales, int n_cands, const int* d_crange, const unsigned char* d_done, int live_max,
                          int general, int8_t* d_q, void* stream);
+/* Rows of the im2col matrix of a conv input as the pruned passes gather them (k_gather_im2col, the search's kernel for the
+ * slice rows of a Conv2d weight search): d_x [batch][in_channels][height][width] fp32, zero padded, groups = 1; row
+ * r = (image, oy, ox) of the [batch * fh * fw][in_channels * kernel_h * kernel_w] matrix, column (ci, ki, kj) -- the element
+ * F.unfold(x, ...).transpose(1, 2) holds there.  d_idx [k]: the rows to gather, 0 <= d_idx[i] < batch * fh * fw; d_dst
+ * [k][in_channels * kernel_h * kernel_w].  A copy: every element is bit-identical to its source or 0 (padding).  A geometry
+ * whose dilated kernel exceeds the padded input is P4V_ERR_INVALID.  Exposed for the geometry tests. */
+int p4v_debug_gather_im2col(int batch, int in_channels, int height, int width, int kernel_h, int kernel_w, int stride_h, int stride_w,
+                            int pad_h, int pad_w, int dil_h, int dil_w, const float* d_x, const int32_t* d_idx, int k, float* d_dst,
+                            void* stream);
 /* k_sweep6's epilogue operands in fragment order (k_prep_epi6): raw_out d_o (element (s, t) at s * o_ss + t * o_ts, s < sr
  * stationary rows, t < tr streaming rows), the metric weight d_wt (wt_mode 1), the bias (indexed by t if bias_on_t, else
  * by s) -> d_e, ceil(sr / 256) * ceil(tr / 64) tiles of 256 * 64 * 2 floats.  Exposed for the layout tests. */

@@ -8,6 +8,7 @@ intervals, expected score tables).  The reference does not exist on the GPU
 box, so this script is never run there; the committed ``.npz`` files travel.
 
     python oracle/gen_golden.py            # rewrites tests/golden/*.npz
+    python oracle/gen_golden.py convgeo    # only the convgeo_* files (likewise ptqslconv, minivit, ...)
 """
 import json
 import os
@@ -154,17 +155,32 @@ def gen_matmul(name, *, b, H, d1, d2, d3, sos=False, grad_scale=1e-3, seed=0, cl
     _save(name, dict(kind="matmul", sos=sos, **kw), arrays, rec.tables)
 
 
-def gen_conv(name, *, b, ic, hw, oc, k, stride, channelwise=True, grad_scale=1e-3, seed=0, **kw):
+def _pair(v):
+    return [int(v), int(v)] if isinstance(v, int) else [int(t) for t in v]
+
+
+def gen_conv(name, *, b, ic, hw, oc, k, stride, channelwise=True, grad_scale=1e-3, seed=0, padding=None, dilation=None,
+             zero_filters=None, **kw):
+    """`hw`, `k`, `stride` are an int (square, as the patch embeddings) or an (h, w) pair; `padding` / `dilation` likewise.
+    With a pair anywhere, or `padding` / `dilation` given, the geometry goes into `params` as two-element lists
+    (stride, padding, dilation); otherwise `params` is what it always was.  `zero_filters`: output channels whose filter is
+    set to zero (a pruned channel: interval 0, NaN score column -- SURVEY.md App. A-10)."""
     from quant_layers.conv import BatchingEasyQuantConv2d, ChannelwiseBatchingQuantConv2d
 
+    general = padding is not None or dilation is not None or not all(isinstance(v, int) for v in (hw, k, stride))
+    (H, W), (kh, kw_) = _pair(hw), _pair(k)
+    pad, dil = (0 if padding is None else padding), (1 if dilation is None else dilation)
+    conv_args = (tuple(_pair(stride)), tuple(_pair(pad)), tuple(_pair(dil))) if general else (stride,)
     g = torch.Generator().manual_seed(seed)
-    w = torch.randn(oc, ic, k, k, generator=g) * 0.05 * torch.linspace(0.5, 2.0, oc).view(-1, 1, 1, 1)
+    w = torch.randn(oc, ic, kh, kw_, generator=g) * 0.05 * torch.linspace(0.5, 2.0, oc).view(-1, 1, 1, 1)
+    for c in zero_filters or ():
+        w[c] = 0.0
     bias = torch.randn(oc, generator=g) * 0.1
-    x = torch.randn(b, ic, hw, hw, generator=g)
-    out = F.conv2d(x, w, bias, stride)
+    x = torch.randn(b, ic, H, W, generator=g)
+    out = F.conv2d(x, w, bias, *conv_args)
     grad = torch.randn(out.shape, generator=g) * grad_scale
     cls = ChannelwiseBatchingQuantConv2d if channelwise else BatchingEasyQuantConv2d
-    m = cls(ic, oc, k, stride, **kw)
+    m = cls(ic, oc, (kh, kw_) if general else k, *conv_args, **kw)
     m.weight.data = w.clone()
     m.bias.data = bias.clone()
     m.raw_input, m.raw_out, m.raw_grad = x.clone(), out.clone(), grad.clone()
@@ -176,7 +192,34 @@ def gen_conv(name, *, b, ic, hw, oc, k, stride, channelwise=True, grad_scale=1e-
     arrays = dict(weight=w.numpy(), bias=bias.numpy(), x=x.numpy(), out=out.numpy(), grad=grad.numpy(),
                   w_interval=np.asarray(m.w_interval), a_interval=np.asarray(m.a_interval),
                   quant_forward=qf.numpy())
-    _save(name, dict(kind="conv", channelwise=channelwise, stride=stride, **kw), arrays, rec.tables)
+    if zero_filters:
+        arrays["zero_filters"] = np.asarray(zero_filters, dtype=np.int64)
+    geo = dict(stride=_pair(stride), padding=_pair(pad), dilation=_pair(dil)) if general else dict(stride=stride)
+    _save(name, dict(kind="conv", channelwise=channelwise, **geo, **kw), arrays, rec.tables)
+
+
+def gen_conv_geometries():
+    """Conv2d searches that are NOT unpadded square patch embeddings (prefix `convgeo_`: the `conv_` parametrisations, which
+    hard-code zero padding, do not load them): rectangular images / kernels / strides, asymmetric padding, dilation on one
+    axis, a ResNet-style 7x7 stride-2 stem, a patchify conv whose image is not a multiple of the patch (floor: the last
+    pixels are dropped), and a channel whose filter is all zero (interval 0, NaN score column)."""
+    cos = dict(BASEPTQ)
+    gen_conv("convgeo_a_cw_hessian_a8_rect_dil", b=3, ic=5, hw=(17, 23), oc=10, k=(3, 5), stride=(2, 1), padding=(1, 2),
+             dilation=(2, 1), w_bit=8, a_bit=8, seed=80, **PTQ4VIT)
+    gen_conv("convgeo_b_cw_hessian_stem7", b=2, ic=3, hw=32, oc=12, k=7, stride=2, padding=3, dilation=1, w_bit=8, a_bit=32,
+             seed=81, **PTQ4VIT)
+    gen_conv("convgeo_c_lw_cosine_rect_stride", b=3, ic=4, hw=(15, 19), oc=9, k=3, stride=(1, 2), padding=1, dilation=1,
+             channelwise=False, w_bit=8, a_bit=32, seed=82, **cos)
+    gen_conv("convgeo_d_cw_cosine_w6_rect_dil", b=3, ic=4, hw=(15, 19), oc=9, k=(3, 2), stride=2, padding=(2, 0),
+             dilation=(1, 3), w_bit=6, a_bit=32, seed=83, **cos)
+    gen_conv("convgeo_e_lw_hessian_w6_rect", b=2, ic=3, hw=(21, 13), oc=7, k=(5, 3), stride=(3, 2), padding=(2, 1),
+             dilation=1, channelwise=False, w_bit=6, a_bit=32, seed=84, **PTQ4VIT)
+    gen_conv("convgeo_f_cw_hessian_patch_floor", b=3, ic=3, hw=30, oc=12, k=8, stride=8, padding=0, dilation=1, w_bit=8,
+             a_bit=32, seed=85, **PTQ4VIT)
+    gen_conv("convgeo_g_cw_hessian_zero_filter", b=3, ic=4, hw=(12, 14), oc=10, k=3, stride=1, padding=1, dilation=1,
+             zero_filters=[3], w_bit=8, a_bit=32, seed=86, **PTQ4VIT)
+    gen_conv("convgeo_h_cw_hessian_a8_zero_filter", b=3, ic=4, hw=(12, 14), oc=10, k=3, stride=1, padding=1, dilation=1,
+             zero_filters=[3], w_bit=8, a_bit=8, seed=86, **PTQ4VIT)
 
 
 def gen_ptqsl_conv(name, *, b, ic, hw, oc, k, stride, grad_scale=1e-3, seed=0, **kw):
@@ -222,6 +265,8 @@ def main(only=None):
         return gen_mini_vit()
     if only == "ptqslconv":
         return gen_ptqsl_convs()
+    if only == "convgeo":
+        return gen_conv_geometries()
     # ---- Linear (quant_layers/linear.py:349-642) ---------------------------------
     gen_linear("linear_qkv_hessian_w8a8", shape_x=(4, 13, 48), oc=36, n_V=3, w_bit=8, a_bit=8, **PTQ4VIT)
     gen_linear("linear_hessian_w6a6_tinygrad", shape_x=(4, 13, 48), oc=24, n_V=1, w_bit=6, a_bit=6,
@@ -259,6 +304,7 @@ def main(only=None):
     gen_ptqsl_convs()
     gen_conv("conv_channelwise_hessian_a8_overlap", b=3, ic=3, hw=20, oc=8, k=5, stride=3, w_bit=8, a_bit=8, seed=34,
              metric="hessian", eq_alpha=0.3, eq_beta=1.2, eq_n=30, search_round=2)
+    gen_conv_geometries()
 
 
 

@@ -256,12 +256,14 @@ class TorchMatMul:
 class TorchConv:
     """ChannelwiseBatchingQuantConv2d (conv.py:444-614) / BatchingEasyQuantConv2d (conv.py:279-441), a_bit = 32."""
 
-    def __init__(self, weight, bias, *, stride=1, w_bit=8, a_bit=32, metric="hessian", search_round=1, eq_alpha=0.1,
-                 eq_beta=2.0, eq_n=100, channelwise=True, init_layerwise=False, chunk=10, **unused):
+    def __init__(self, weight, bias, *, stride=1, padding=0, dilation=1, w_bit=8, a_bit=32, metric="hessian", search_round=1,
+                 eq_alpha=0.1, eq_beta=2.0, eq_n=100, channelwise=True, init_layerwise=False, chunk=10, **unused):
         assert a_bit >= 32, "the shipped configurations keep the patch embedding's input in fp32 (PTQ4ViT.py:54)"
         self.w = torch.as_tensor(weight, dtype=torch.float32)
         self.b = None if bias is None else torch.as_tensor(bias, dtype=torch.float32)
-        self.stride, self.wq, self.metric, self.R, self.eq_n = stride, 2 ** (w_bit - 1), metric, search_round, eq_n
+        pair = lambda v: (v, v) if isinstance(v, int) else tuple(v)
+        self.stride, self.padding, self.dilation = pair(stride), pair(padding), pair(dilation)
+        self.wq, self.metric, self.R, self.eq_n = 2 ** (w_bit - 1), metric, search_round, eq_n
         self.mult, self.channelwise, self.init_layerwise, self.chunk = _mult(eq_alpha, eq_beta, eq_n), channelwise, init_layerwise, chunk
         self.trace = []
 
@@ -286,7 +288,7 @@ class TorchConv:
             p = p1 - p0
             cur = w_c[p0:p1]
             ws = (torch.clamp(torch.round(self.w[None] / cur), -self.wq, self.wq - 1) * cur).reshape(p * oc, *self.w.shape[1:])
-            o = F.conv2d(x, ws, None if self.b is None else self.b.repeat(p), self.stride)
+            o = F.conv2d(x, ws, None if self.b is None else self.b.repeat(p), self.stride, self.padding, self.dilation)
             o = o.view(b, p, oc, *o.shape[2:])
             if self.channelwise:                                                # conv.py:498-524, mean over the pixels
                 if self.metric == "cosine":

@@ -2645,9 +2645,13 @@ int conv_impl(const p4v_conv_desc* d, const float* W, const float* bias, const f
               const Stage& sg = Stage{}) {
     const int b = d->batch, ic = d->in_channels, H = d->height, Wd = d->width, oc = d->out_channels;
     const int kh = d->kernel_h, kw = d->kernel_w;
-    const int fh = (H + 2 * d->pad_h - d->dil_h * (kh - 1) - 1) / d->stride_h + 1;
-    const int fw = (Wd + 2 * d->pad_w - d->dil_w * (kw - 1) - 1) / d->stride_w + 1;
-    if (b <= 0 || ic <= 0 || oc <= 0 || fh <= 0 || fw <= 0 || d->eq_n <= 0) return fail(P4V_ERR_INVALID, "conv: bad geometry");
+    if (kh <= 0 || kw <= 0 || d->stride_h <= 0 || d->stride_w <= 0 || d->pad_h < 0 || d->pad_w < 0 || d->dil_h <= 0 || d->dil_w <= 0)
+        return fail(P4V_ERR_INVALID, "conv: bad geometry");
+    // output size floor((size + 2 pad - dil (k - 1) - 1) / stride) + 1: the numerators are tested for their sign -- C division
+    // truncates toward zero, so a dilated kernel one larger than the padded image (numerator -1) would give 1 with stride >= 2
+    const int num_h = H + 2 * d->pad_h - d->dil_h * (kh - 1) - 1, num_w = Wd + 2 * d->pad_w - d->dil_w * (kw - 1) - 1;
+    if (b <= 0 || ic <= 0 || oc <= 0 || H <= 0 || Wd <= 0 || num_h < 0 || num_w < 0 || d->eq_n <= 0) return fail(P4V_ERR_INVALID, "conv: bad geometry");
+    const int fh = num_h / d->stride_h + 1, fw = num_w / d->stride_w + 1;
     if (d->w_bit > 8) return fail(P4V_ERR_UNSUPPORTED, "conv: w_bit <= 8 supported");
     const int L = fh * fw, K = ic * kh * kw, M = b * L;
     const int wq = 1 << (d->w_bit - 1);
@@ -3324,6 +3328,27 @@ int p4v_debug_pack_cands(const float* d_x, long rows, long cols, long rows_padde
     const int r = launch_pack<int8_t>(c, p, live_max);
     g_pack_general.store(0, std::memory_order_relaxed);
     return r;
+}
+
+int p4v_debug_gather_im2col(int batch, int in_channels, int height, int width, int kernel_h, int kernel_w, int stride_h, int stride_w,
+                            int pad_h, int pad_w, int dil_h, int dil_w, const float* d_x, const int32_t* d_idx, int k, float* d_dst,
+                            void* stream) {
+    if (!d_x || !d_idx || !d_dst || k <= 0 || batch <= 0 || in_channels <= 0 || height <= 0 || width <= 0 || kernel_h <= 0 ||
+        kernel_w <= 0 || stride_h <= 0 || stride_w <= 0 || pad_h < 0 || pad_w < 0 || dil_h <= 0 || dil_w <= 0)
+        return fail(P4V_ERR_INVALID, "p4v_debug_gather_im2col: bad argument");
+    const int num_h = height + 2 * pad_h - dil_h * (kernel_h - 1) - 1, num_w = width + 2 * pad_w - dil_w * (kernel_w - 1) - 1;
+    if (num_h < 0 || num_w < 0) return fail(P4V_ERR_INVALID, "p4v_debug_gather_im2col: bad geometry");
+    const int fh = num_h / stride_h + 1, fw = num_w / stride_w + 1;
+    PackParams p{};         // the conv view exactly as conv_impl's x_operand builds it for the flat layout (Z = 1, rows = b * L)
+    p.src = d_x; p.conv = 1; p.ic = in_channels; p.H = height; p.W = width; p.kh = kernel_h; p.kw = kernel_w;
+    p.sh = stride_h; p.sw = stride_w; p.ph = pad_h; p.pw = pad_w; p.dh = dil_h; p.dw = dil_w;
+    p.fw = fw; p.L = fh * fw;
+    p.Z = 1; p.s_z = 0; p.R = batch * fh * fw; p.K = in_channels * kernel_h * kernel_w; p.nblk_r = 1; p.nblk_k = 1;
+    p.mode = PACK_RAW;
+    Ctx c{(hipStream_t)stream, Arena(nullptr, 0), false};
+    const long total = (long)k * p.K;
+    return enqueue(c, KERN(GatherIm2colParams, k_gather_im2col), dim3((unsigned)std::min<long>(cdiv(total, 256), 256L * 16)), dim3(256), 0,
+                   GatherIm2colParams{p, d_idx, k, d_dst});
 }
 
 int p4v_debug_prep_epi6(const float* d_o, const float* d_wt, const float* d_bias, long o_ss, long o_ts, int sr, int tr,

@@ -236,7 +236,12 @@ __device__ __forceinline__ float pack_value(const PackParams& p, float x, float 
 __device__ __forceinline__ float pack_value_f32(const PackParams& p, float x, float s) {
     switch (p.mode) {
         case PACK_RAW: return x;
-        case PACK_SYM: return fminf(fmaxf(rintf(x / s), (float)p.lo), (float)p.hi) * s;
+        case PACK_SYM: {
+            // torch.clamp keeps a NaN, fmaxf / fminf drop it: a block that is all zero has interval 0, its fake quantisation is
+            // 0 / 0 and its score NaN for every candidate -- the fp32 plane must carry that NaN
+            const float q = rintf(x / s);
+            return (q != q ? q : fminf(fmaxf(q, (float)p.lo), (float)p.hi)) * s;
+        }
         case PACK_SOS_SIM: {
             const float a_int = s / p.qm1;
             const float hi = fminf(fmaxf(rintf(fminf(fmaxf(x, s), 1.0f) * p.qm1), 0.0f), p.qm1) / p.qm1;

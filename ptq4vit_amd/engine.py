@@ -669,6 +669,24 @@ def debug_pack_cands(x2d, scales, *, layout, lo, hi, rows_padded=None, crange=No
     return out
 
 
+def debug_gather_im2col(x, idx, *, kernel_size, stride, padding, dilation):
+    """Rows `idx` (int32 [k], each in [0, b * fh * fw)) of the im2col matrix of the conv input `x` [b][ic][H][W] as the pruned
+    passes gather them (k_gather_im2col; p4v_debug_gather_im2col): fp32 [k][ic * kh * kw].  For the tests."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and idx.is_cuda and idx.dtype == torch.int32 and idx.dim() == 1
+    x, idx = x.contiguous(), idx.contiguous()
+    b, ic, H, W = x.shape
+    (kh, kw), (sh, sw), (ph, pw), (dh, dw) = kernel_size, stride, padding, dilation
+    fh, fw = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    if fh > 0 and fw > 0:
+        assert idx.numel() > 0 and int(idx.min()) >= 0 and int(idx.max()) < b * fh * fw, "row index outside the im2col matrix"
+    out = torch.full((idx.numel(), ic * kh * kw), float("nan"), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = _lib.load().p4v_debug_gather_im2col(b, ic, H, W, kh, kw, sh, sw, ph, pw, dh, dw, ptr(x), ptr(idx), idx.numel(), ptr(out),
+                                                 stream_ptr(x.device))
+    _lib.check(rc, "p4v_debug_gather_im2col")
+    return out
+
+
 def debug_prep_epi6(o, wt, bias, *, o_ss, o_ts, sr, tr, bias_on_t, wt_mode, transposed):
     """k_sweep6's epilogue operands in fragment order (k_prep_epi6) from the flat fp32 tensors `o`, `wt` (or None), `bias`:
     a flat fp32 tensor of ceil(sr / 256) * ceil(tr / 64) * 256 * 64 * 2 values.  For the tests."""

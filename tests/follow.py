@@ -124,19 +124,22 @@ def follow_matmul(eng, *, A, B, out, grad, hp, sos, rounds=3, what="matmul", exp
     return (flips,) + traj[-1]
 
 
-def follow_conv(eng, *, weight, bias, x, out, grad, stride, hp, channelwise=True, what="conv", expect_pruned=True, tie_rtol=TIE_RTOL):
-    """Patch embedding (a_bit = 32: no activation search, every round repeats the weight search, conv.py:600)."""
+def follow_conv(eng, *, weight, bias, x, out, grad, stride, hp, channelwise=True, what="conv", expect_pruned=True, tie_rtol=TIE_RTOL,
+                padding=0, dilation=1):
+    """a_bit = 32: no activation search, every round repeats the weight search, conv.py:600.  `stride`, `padding`, `dilation`:
+    an int or an (h, w) pair."""
     from oracle.torch_port import TorchConv
+    pair = lambda v: (v, v) if isinstance(v, int) else tuple(v)
     dev = torch.device("cuda")
     eng.prune_counters(reset=True)
     w_iv, a_iv, sc, best = eng.conv_calibrate(weight=weight.to(dev), bias=bias.to(dev), x=x.to(dev), out=out.to(dev),
-                                              grad=None if grad is None else grad.to(dev), stride=(stride, stride),
-                                              padding=(0, 0), dilation=(1, 1), channelwise=channelwise, search_round=3, **hp)
+                                              grad=None if grad is None else grad.to(dev), stride=pair(stride),
+                                              padding=pair(padding), dilation=pair(dilation), channelwise=channelwise, search_round=3, **hp)
     torch.cuda.synchronize()
     assert sc is None and best is None
     if expect_pruned:
         _expect_staged(eng, what)
-    port = TorchConv(weight, bias, stride=stride, channelwise=channelwise, **hp)
+    port = TorchConv(weight, bias, stride=stride, padding=padding, dilation=dilation, channelwise=channelwise, **hp)
     w0, w_c = port.initial()
     tab = port.score_w(x, out, grad, w_c).numpy()
     table = w_c.numpy().reshape(w_c.shape[0], -1)

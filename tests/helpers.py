@@ -78,10 +78,13 @@ def golden_names(prefix=""):
 def assert_scores_close(got, ref, rtol=SCORE_RTOL, what=""):
     got = np.asarray(got, dtype=np.float64).reshape(np.asarray(ref).shape)
     ref = np.asarray(ref, dtype=np.float64)
-    scale = np.maximum(np.abs(ref), np.abs(ref).max() * 1e-6 + 1e-300)
-    err = np.abs(got - ref) / scale
-    assert np.all(np.isfinite(got) == np.isfinite(ref)), f"{what}: finiteness differs"
     m = np.isfinite(ref)
+    # (the floor of the scale comes from the FINITE entries: a NaN column -- a zero interval, SURVEY.md App. A-10 -- must not
+    # turn every error of the table into NaN)
+    scale = np.maximum(np.abs(ref), np.abs(ref[m]).max(initial=0.0) * 1e-6 + 1e-300)
+    with np.errstate(invalid="ignore"):
+        err = np.abs(got - ref) / scale
+    assert np.all(np.isfinite(got) == np.isfinite(ref)), f"{what}: finiteness differs"
     record_margin("score_rel_err", err[m].max(initial=0.0))
     assert err[m].max(initial=0.0) <= rtol, f"{what}: score rel err {err[m].max():.3e} > {rtol}"
 
