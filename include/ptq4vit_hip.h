@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define P4V_VERSION 140 /* 0.1.4: + p4v_calibrate_group (grouped launches over the modules of a network), p4v_launch_counters */
+#define P4V_VERSION 141 /* 0.1.4.1: + p4v_matmul_blocks_* (MatMul row / column sub-blocks, n_V / n_H > 1) */
 
 /* similarity metrics: reference quant_layers/linear.py:399-424 */
 enum p4v_metric {
@@ -102,7 +102,8 @@ int p4v_linear_calibrate(const p4v_linear_desc* desc, const float* d_weight, con
 /* ------------------------------------------------------------------------------------------
  * MatMul: replaces PTQSLBatchingQuantMatMul.calibration_step2 (quant_layers/matmul.py:565-576)
  * and SoSPTQSLBatchingQuantMatMul (matmul.py:633-644, `sos` = 1: split-of-softmax on A).
- * Head-wise intervals (n_G = heads, matmul.py:411-417); n_V = n_H = 1 (all shipped configs).
+ * Head-wise intervals (n_G = heads, matmul.py:411-417) with n_V = n_H = 1 (all shipped configs); row / column
+ * sub-blocks: p4v_matmul_blocks_* below.
  * ---------------------------------------------------------------------------------------- */
 typedef struct p4v_matmul_desc {
     int32_t batch, heads;
@@ -130,6 +131,57 @@ int p4v_matmul_calibrate(const p4v_matmul_desc* desc, const float* d_A, const fl
                          const float* d_grad, const float* d_mult, float* d_A_interval, float* d_B_interval,
                          float* d_split, float* d_scores, int32_t* d_best, void* d_workspace,
                          size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * MatMul with row / column sub-blocks: the (n_G = heads, n_V, n_H) padding view of the reference
+ * (quant_layers/matmul.py:109-138) with n_V / n_H > 1 on either operand.  Blocks are ceil(dim / n) wide, the last one
+ * ragged or empty; an empty block keeps the interval 0.  Interval tensors are [heads][n_V][n_H] (the reference's
+ * (1, n_G, 1, n_V, 1, n_H, 1), flattened).  1 <= n_V, n_H <= 8; with `sos` n_V_A = n_H_A = 1 (matmul.py:586-588) and
+ * d_A_interval is the scalar split/(qmax-1).  The cosine metric is not offered with sub-blocks (P4V_ERR_UNSUPPORTED).
+ * With all four counts 1 every entry point below is its head-wise counterpart: same launches, same results.
+ * `p4v_matmul_desc` keeps its layout; this descriptor wraps it.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct p4v_matmul_blocks_desc {
+    p4v_matmul_desc mm;
+    int32_t n_V_A, n_H_A, n_V_B, n_H_B;
+} p4v_matmul_blocks_desc;
+
+size_t p4v_matmul_blocks_workspace_bytes(const p4v_matmul_blocks_desc* desc);
+
+/*
+ * The fused search (matmul.py:565-576 / 633-644): min-max initialisation, then search_round x {A blocks, B blocks}, greedy
+ * per block in product(range(n_V), range(n_H)) order (matmul.py:489-521 / 530-562): the candidates mult * INITIAL interval
+ * replace that block's scale only, every other block keeps the interval entering the step, the score is the full-output
+ * score per head.
+ * d_A_interval [heads][n_V_A][n_H_A] out (sos: [1]);  d_B_interval [heads][n_V_B][n_H_B] out;  d_split [1] out (sos only)
+ * d_scores     optional: [search_round][steps][eq_n][heads], steps = n_V_A*n_H_A + n_V_B*n_H_B in the reference's order
+ *              (sos: the split table first -- rows 0..19, column 0 -- then the B blocks: steps = 1 + n_V_B*n_H_B)
+ * d_best       optional: [search_round][steps][heads]
+ */
+int p4v_matmul_blocks_calibrate(const p4v_matmul_blocks_desc* desc, const float* d_A, const float* d_B, const float* d_out,
+                                const float* d_grad, const float* d_mult, float* d_A_interval, float* d_B_interval,
+                                float* d_split, float* d_scores, int32_t* d_best, void* d_workspace,
+                                size_t workspace_bytes, void* stream);
+
+/* Granular: _initialize_intervals (matmul.py:419-440) with blocks.  With `sos` d_A_interval is left untouched. */
+int p4v_amax_init_matmul_blocks(const p4v_matmul_blocks_desc* desc, const float* d_A, const float* d_B,
+                                float* d_A_interval, float* d_B_interval, void* d_workspace, size_t workspace_bytes,
+                                void* stream);
+
+/* Granular: ONE block step of _search_best_A_interval / _search_best_B_interval.  `operand` 0 = A, 1 = B; (v, h) the block;
+ * d_cands [eq_n+1][heads] that block's candidates per head; both interval tensors in, the searched one is updated in
+ * place at block (v, h) of every head.  d_scores [eq_n][heads] / d_best [heads] optional.  The split-of-softmax split search
+ * knows no blocks: p4v_sos_search_split with `desc->mm`. */
+int p4v_matmul_blocks_search(const p4v_matmul_blocks_desc* desc, int32_t operand, int32_t v, int32_t h, const float* d_A,
+                             const float* d_B, const float* d_out, const float* d_grad, const float* d_cands,
+                             float* d_A_interval, float* d_B_interval, const float* d_split, float* d_scores,
+                             int32_t* d_best, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* quant_forward (matmul.py:140-145; sos: 595-598) as an int8 MFMA GEMM over K segments with one fp32 rescale per segment.
+ * Workspace: p4v_matmul_blocks_workspace_bytes with bit 2 of `mm.reserved` set (or of the full descriptor). */
+int p4v_matmul_blocks_quant_forward(const p4v_matmul_blocks_desc* desc, const float* d_A, const float* d_B,
+                                    const float* d_A_interval, const float* d_B_interval, const float* d_split,
+                                    float* d_out, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Conv2d: replaces ChannelwiseBatchingQuantConv2d.calibration_step2 (quant_layers/conv.py:591-603,
@@ -165,7 +217,7 @@ int p4v_conv_calibrate(const p4v_conv_desc* desc, const float* d_weight, const f
  *
  * Replaces the loop `for name, module in ...: module.calibration_step2()` of the reference's calibrator
  * (utils/quant_calib.py:371-372; with sequential=False the modules are independent, quant_calib.py:316-372).  Each member is
- * exactly one p4v_linear_calibrate / p4v_matmul_calibrate / p4v_conv_calibrate call (same descriptor, same pointers, its own
+ * exactly one p4v_linear_calibrate / p4v_matmul_calibrate / p4v_matmul_blocks_calibrate / p4v_conv_calibrate call (same descriptor, same pointers, its own
  * workspace of p4v_*_workspace_bytes(desc), no score tables); the members search in lock step and every kernel launch of the
  * same kind is issued ONCE for all members that are at that point (one k_finish / k_pack / k_sweep6 ... over the concatenated
  * grids instead of one per module).  The results are bit-identical to the members' single calls: a grouped kernel runs each
@@ -176,9 +228,10 @@ int p4v_conv_calibrate(const p4v_conv_desc* desc, const float* d_weight, const f
  *   P4V_JOB_LINEAR  desc = p4v_linear_desc   in = {weight, bias, x, raw_out, raw_grad}   out = {w_interval, a_interval, NULL}
  *   P4V_JOB_MATMUL  desc = p4v_matmul_desc   in = {A, B, raw_out, raw_grad, NULL}        out = {A_interval, B_interval, split}
  *   P4V_JOB_CONV    desc = p4v_conv_desc     in = {weight, bias, x, raw_out, raw_grad}   out = {w_interval, a_interval, NULL}
+ *   P4V_JOB_MATMUL_BLOCKS  desc = p4v_matmul_blocks_desc, pointers as P4V_JOB_MATMUL (one p4v_matmul_blocks_calibrate call)
  * `status` receives the member's own status; the call returns the first non-zero one (p4v_last_error() has its message).
  * ---------------------------------------------------------------------------------------- */
-enum p4v_job_kind { P4V_JOB_LINEAR = 0, P4V_JOB_MATMUL = 1, P4V_JOB_CONV = 2 };
+enum p4v_job_kind { P4V_JOB_LINEAR = 0, P4V_JOB_MATMUL = 1, P4V_JOB_CONV = 2, P4V_JOB_MATMUL_BLOCKS = 3 };
 typedef struct p4v_group_job {
     int32_t kind;
     int32_t status;

@@ -31,6 +31,11 @@ class MatMulDesc(C.Structure):
                                           "init_layerwise", "reserved")])
 
 
+class MatMulBlocksDesc(C.Structure):
+    """p4v_matmul_blocks_desc: the MatMul descriptor plus the row / column block counts of both operands."""
+    _fields_ = [("mm", MatMulDesc)] + [(n, C.c_int32) for n in ("n_V_A", "n_H_A", "n_V_B", "n_H_B")]
+
+
 class ConvDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "batch", "in_channels", "height", "width", "out_channels", "kernel_h", "kernel_w", "stride_h", "stride_w",
@@ -54,7 +59,7 @@ class LaunchRecord(C.Structure):
 
 
 LAUNCH_KINDS = {0: "k_sweep<int8>", 1: "k_sweep<float>", 2: "k_sweep6", 3: "k_sweep7", 4: "k_sweep7 (twin)", 5: "k_sweep4/5", 6: "k_sweep9",
-                7: "k_sweep8", 8: "k_sweep2g", 9: "k_sweep2", 11: "k_sos_split", 12: "k_bound", 13: "k_slice_b", 14: "k_slice_a"}
+                7: "k_sweep8", 8: "k_sweep2g", 9: "k_sweep2", 11: "k_sos_split", 12: "k_bound", 13: "k_slice_b", 14: "k_slice_a", 15: "k_sweep_seg"}
 LAUNCH_STAGES = {0: "full", 1: "A", 2: "B1", 3: "B2", 4: "A2"}
 
 
@@ -79,7 +84,7 @@ class GroupJob(C.Structure):
                 ("out", C.c_void_p * 3), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
-JOB_LINEAR, JOB_MATMUL, JOB_CONV = 0, 1, 2
+JOB_LINEAR, JOB_MATMUL, JOB_CONV, JOB_MATMUL_BLOCKS = 0, 1, 2, 3
 PLANE_SYM, PLANE_SOS_HI, PLANE_SOS_LO, PLANE_TWIN = 1, 2, 3, 4
 EXPORT_SYM_I8, EXPORT_SYM_F32, EXPORT_GELU_U8, EXPORT_SOS_U8 = 0, 1, 2, 3
 
@@ -88,6 +93,8 @@ EXPORTS = [
     "p4v_version", "p4v_last_error",
     "p4v_linear_workspace_bytes", "p4v_linear_calibrate",
     "p4v_matmul_workspace_bytes", "p4v_matmul_calibrate",
+    "p4v_matmul_blocks_workspace_bytes", "p4v_matmul_blocks_calibrate", "p4v_amax_init_matmul_blocks",
+    "p4v_matmul_blocks_search", "p4v_matmul_blocks_quant_forward",
     "p4v_conv_workspace_bytes", "p4v_conv_calibrate",
     "p4v_calibrate_group", "p4v_launch_counters",
     "p4v_linear_quant_forward", "p4v_matmul_quant_forward",
@@ -129,6 +136,17 @@ def load():
     lib.p4v_matmul_workspace_bytes.argtypes = [C.POINTER(MatMulDesc)]
     lib.p4v_matmul_calibrate.restype = C.c_int
     lib.p4v_matmul_calibrate.argtypes = [C.POINTER(MatMulDesc), fp, fp, fp, fp, fp, fp, fp, fp, fp, ip, vp, C.c_size_t, vp]
+    MBD = C.POINTER(MatMulBlocksDesc)
+    lib.p4v_matmul_blocks_workspace_bytes.restype = C.c_size_t
+    lib.p4v_matmul_blocks_workspace_bytes.argtypes = [MBD]
+    lib.p4v_matmul_blocks_calibrate.restype = C.c_int
+    lib.p4v_matmul_blocks_calibrate.argtypes = [MBD, fp, fp, fp, fp, fp, fp, fp, fp, fp, ip, vp, C.c_size_t, vp]
+    lib.p4v_amax_init_matmul_blocks.restype = C.c_int
+    lib.p4v_amax_init_matmul_blocks.argtypes = [MBD, fp, fp, fp, fp, vp, C.c_size_t, vp]
+    lib.p4v_matmul_blocks_search.restype = C.c_int
+    lib.p4v_matmul_blocks_search.argtypes = [MBD, C.c_int32, C.c_int32, C.c_int32] + [fp] * 9 + [ip, vp, C.c_size_t, vp]
+    lib.p4v_matmul_blocks_quant_forward.restype = C.c_int
+    lib.p4v_matmul_blocks_quant_forward.argtypes = [MBD, fp, fp, fp, fp, fp, fp, vp, C.c_size_t, vp]
     lib.p4v_conv_workspace_bytes.restype = C.c_size_t
     lib.p4v_conv_workspace_bytes.argtypes = [C.POINTER(ConvDesc)]
     lib.p4v_conv_calibrate.restype = C.c_int

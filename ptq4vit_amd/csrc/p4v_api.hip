@@ -934,6 +934,21 @@ struct Operand {
     bool present;
 };
 
+// A MatMul pass with row / column sub-blocks (n_V, n_H > 1; matmul_impl): the K axis cut where either operand's scale changes
+// (p4v_kernels.h, "MatMul sub-block scales"), both interval tensors, and -- for a search step -- the ONE block whose candidates
+// are swept (reference matmul.py:489-521 / 530-562: every other block keeps the interval entering the step).
+struct SegPlan {
+    SegTable seg; unsigned char ablk[SEG_MAX], bblk[SEG_MAX]; int Kseg;
+    int batch, H, M, K, N;
+    int nVA, nHA, nVB, nHB, crA, ccA, crB, ccB;     // block counts; rows / columns per block (ceil, matmul.py:109-122)
+    const float* A; long a_st[4]; const float* B; long b_st[4];
+    int Aq, Bq; bool sos;
+    const float* ivA; const float* ivB;             // [H][nVA][nHA] / [H][nVB][nHB]; sos: ivA = the scalar A_interval
+    const float* split;                             // sos
+    int side, ov_v, ov_h;                           // 0: forward; 1 / 2: the searched block of A / B
+    const float* cands; int cand_cs, cand_hs;       // its candidates: cands[c * cand_cs + head * cand_hs]
+};
+
 struct Pass {
     bool i8, twin;
     int epi, wt_mode;
@@ -985,6 +1000,8 @@ struct Pass {
     EpiCache* ecache;         // optional: keeps k_sweep6's fragment-order epilogue operands across the rounds of one call
     bool pack_only;           // plan the pass and pack its candidate-expanded operand into `cache`, nothing else (linear_impl: the
                               // candidate planes of the WEIGHTS depend on no captured tensor -- packed while the capture still runs)
+    const SegPlan* seg;       // MatMul sub-block scales: the K-segment table and the two block-scale tables -> k_pack_seg / k_sweep_seg
+                              // (run_pass_seg); the operands, scales and candidates of such a pass are described there
 };
 
 static const long PLANE_BUDGET_DEFAULT = 6L << 30;  // bytes of candidate-expanded plane kept resident per chunk
@@ -1015,7 +1032,111 @@ bool dual_pack_ok(const PackParams& a, const PackParams& b) {
            a.s_z == b.s_z && a.s_z2 == b.s_z2 && a.zdiv == b.zdiv;
 }
 
+// ---- the sub-block MatMul pass: k_pack_seg planes, k_sweep_seg, then the common finish / selection ---------------------------
+int launch_pack_seg(Ctx& c, PackSegParams p) {
+    if (c.dry) return 0;
+    p.qbias = (p.mode == PACK_SYM && p.lo == -128 && p.hi == 127) ? cvt_bias(c) : 0.0f;
+    const long total = (long)p.Z * p.Rp * (p.Kseg / 16);
+    if (total >= (1L << 31)) return fail(P4V_ERR_UNSUPPORTED, "operand plane too large for k_pack_seg (%ld 16-element runs)", total);
+    const int groups = cdiv(p.C, PACK_CG);
+    return enqueue(c, KERN(PackSegParams, k_pack_seg), dim3((unsigned)std::min<long>(cdiv(total, 256), 256L * 64), groups), dim3(256), 0, p);
+}
+template <bool TWIN> int launch_sweep_seg_epi(Ctx& c, const SweepSegParams& p, int epi, int cgroups, const StatInfo* si) {
+    const size_t lds = 2 * (TWIN ? 3 : 2) * SW_TILE_BYTES + 2 * SEG_MAX * 128 * sizeof(float) + SEG_KT_MAX * sizeof(short) + 2 * SEG_MAX;
+    dim3 grid(p.mtiles * p.ntiles, p.Z, cgroups), block(512);
+    if (epi == EPI_FWD) return enqueue(c, KERN_T(SweepSegParams, k_sweep_seg, TWIN, EPI_FWD), grid, block, lds, p, si);
+    P4V_EPI4(epi, return enqueue(c, KERN_T(SweepSegParams, k_sweep_seg, TWIN, E), grid, block, lds, p, si))
+}
+int run_pass_seg(Ctx& c, Pass& ps) {
+    const SegPlan& g = *ps.seg;
+    const int Z = ps.Z, M = g.M, N = g.N, H = g.H, Kseg = g.Kseg;
+    const bool fwd = ps.epi == EPI_FWD;
+    g_alg_macs_cand = (double)M * N * g.K * Z;
+    g_alg_bytes = 4.0 * ((double)M * g.K * Z + (double)N * g.K * Z) + (ps.G ? 8.0 : 4.0) * (double)M * N * Z;
+    const int Mp = (int)rup(M, SW_BM), Np = (int)rup(N, SW_BN), MT = Mp / 64;
+    const long a_plane = (long)Z * Mp * Kseg, b_plane = (long)Z * Np * Kseg;
+    const bool a_exp = g.side == 1, b_exp = g.side == 2;
+    const long exp_plane = a_exp ? a_plane : b_plane;
+    const int chunk = (int)std::max<long>(1, std::min<long>(ps.eq_n, PLANE_BUDGET / std::max<long>(1, exp_plane)));
+    const size_t mark = c.ws.off;
+    char* abuf = c.ws.get<char>((size_t)a_plane * (a_exp ? chunk : 1));
+    char* a2buf = g.sos ? c.ws.get<char>((size_t)a_plane) : nullptr;
+    char* bbuf = c.ws.get<char>((size_t)b_plane * (b_exp ? chunk : 1));
+    const long p_zs = (long)MT * Np, p_cs = p_zs * Z;
+    float* part = fwd ? nullptr : c.ws.get<float>((size_t)p_cs * ps.eq_n);
+    float* scores = fwd ? nullptr : c.ws.get<float>((size_t)ps.eq_n * H);
+    if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", c.ws.off);
+    if (c.dry) { c.ws.off = mark; return 0; }
+
+    auto a_pack = [&](int mode, char* dst, const float* cands, int C) {
+        PackSegParams p{};
+        p.src = g.A; p.s_z2 = g.a_st[0]; p.s_z = g.a_st[1]; p.s_r = g.a_st[2]; p.s_k = g.a_st[3]; p.zdiv = H;
+        p.Z = Z; p.R = M; p.K = g.K; p.Rp = Mp; p.Kseg = Kseg; p.dst = dst; p.C = C;
+        p.H = H; p.mode = mode; p.seg = g.seg;
+        std::memcpy(p.kblk, g.ablk, sizeof p.kblk);
+        if (mode == PACK_SYM) {
+            p.iv = g.ivA; p.iv_hs = g.nVA * g.nHA; p.iv_rs = g.nHA; p.iv_ks = 1; p.r_div = g.crA; p.nblk_r = g.nVA;
+            p.cands = cands; p.cand_cs = g.cand_cs; p.cand_hs = g.cand_hs; p.ov_r = g.ov_v; p.ov_k = g.ov_h;
+            p.lo = -g.Aq; p.hi = g.Aq - 1;
+        } else {                    // the split-of-softmax ranges: one scalar, the split (no blocks on A, matmul.py:586-588)
+            p.iv = g.split; p.iv_hs = p.iv_rs = p.iv_ks = 0; p.r_div = std::max(1, M); p.nblk_r = 1;
+            p.qm1 = (float)(g.Aq - 1);
+        }
+        return launch_pack_seg(c, p);
+    };
+    auto b_pack = [&](char* dst, const float* cands, int C) {
+        PackSegParams p{};           // logical [Z][rows = n][K]: the row block is B's column block, the k block its row block
+        p.src = g.B; p.s_z2 = g.b_st[0]; p.s_z = g.b_st[1]; p.s_r = g.b_st[3]; p.s_k = g.b_st[2]; p.zdiv = H;
+        p.Z = Z; p.R = N; p.K = g.K; p.Rp = Np; p.Kseg = Kseg; p.dst = dst; p.C = C;
+        p.H = H; p.mode = PACK_SYM; p.seg = g.seg;
+        std::memcpy(p.kblk, g.bblk, sizeof p.kblk);
+        p.iv = g.ivB; p.iv_hs = g.nVB * g.nHB; p.iv_rs = 1; p.iv_ks = g.nHB; p.r_div = g.ccB; p.nblk_r = g.nHB;
+        p.cands = cands; p.cand_cs = g.cand_cs; p.cand_hs = g.cand_hs; p.ov_r = g.ov_h; p.ov_k = g.ov_v;
+        p.lo = -g.Bq; p.hi = g.Bq - 1;
+        return launch_pack_seg(c, p);
+    };
+    // fixed planes once
+    if (g.sos) { CHK(a_pack(PACK_SOS_HI, abuf, nullptr, 1)); CHK(a_pack(PACK_SOS_LO, a2buf, nullptr, 1)); }
+    else if (!a_exp) CHK(a_pack(PACK_SYM, abuf, nullptr, 1));
+    if (!b_exp) CHK(b_pack(bbuf, nullptr, 1));
+    for (int c0 = 0; c0 < ps.eq_n; c0 += chunk) {
+        const int nc = std::min(chunk, ps.eq_n - c0);
+        if (a_exp) CHK(a_pack(PACK_SYM, abuf, g.cands + (long)c0 * g.cand_cs, nc));
+        if (b_exp) CHK(b_pack(bbuf, g.cands + (long)c0 * g.cand_cs, nc));
+        SweepSegParams sp{};
+        sp.a_cs = a_exp ? a_plane : 0; sp.A = abuf - (long)c0 * sp.a_cs; sp.a_zs = (long)Mp * Kseg;
+        sp.A2 = a2buf; sp.a2_zs = sp.a_zs;
+        sp.b_cs = b_exp ? b_plane : 0; sp.B = bbuf - (long)c0 * sp.b_cs; sp.b_zs = (long)Np * Kseg;
+        sp.ldk = Kseg; sp.ktiles = Kseg / SW_BKB;
+        sp.ivA = g.sos ? nullptr : g.ivA; sp.ivB = g.ivB;
+        sp.H = H; sp.nVA = g.nVA; sp.nHA = g.nHA; sp.nVB = g.nVB; sp.nHB = g.nHB; sp.m_div = g.crA; sp.n_div = g.ccB;
+        sp.cands = g.cands; sp.cand_cs = g.cand_cs; sp.cand_hs = g.cand_hs; sp.side = g.side; sp.ov_v = g.ov_v; sp.ov_h = g.ov_h;
+        sp.rs_const = 1.0f / (float)(g.Aq - 1); sp.rs2 = g.sos ? g.ivA : nullptr;
+        sp.O = ps.O; sp.Wt = ps.G ? ps.G : ps.O; sp.wt_mode = ps.wt_mode; sp.o_zs = (long)M * N; sp.o_ms = N;
+        sp.M = M; sp.N = N; sp.Z = Z; sp.c0 = c0; sp.c1 = c0 + nc; sp.crange = nullptr;
+        sp.part = part; sp.p_cs = p_cs; sp.p_zs = p_zs; sp.Np = Np; sp.mtiles = Mp / SW_BM; sp.ntiles = Np / SW_BN;
+        sp.store = ps.store_out;
+        sp.seg = g.seg;
+        std::memcpy(sp.ablk, g.ablk, sizeof sp.ablk); std::memcpy(sp.bblk, g.bblk, sizeof sp.bblk);
+        // one workgroup per CU (512 threads, three or four register tiles per lane); per k-tile step as the generic int8 sweep
+        const long wgs = (long)sp.mtiles * sp.ntiles * Z;
+        const int cgroups = choose_cgroups(wgs, nc, sp.ktiles, cu_slots(c, 256, 15), 20.0, 1.6);
+        const StatInfo si = stat_info(15, (double)Mp * Np * (double)Kseg * Z * nc * (g.sos ? 2 : 1), g_alg_macs_cand * nc,
+                                      sp.mtiles * sp.ntiles, cgroups, g_alg_bytes);
+        CHK(g.sos ? launch_sweep_seg_epi<true>(c, sp, ps.epi, cgroups, &si) : launch_sweep_seg_epi<false>(c, sp, ps.epi, cgroups, &si));
+    }
+    if (fwd) { c.ws.off = mark; return 0; }
+    FinishParams fp{part, p_cs, p_zs, Np, MT, Z, N, ps.eq_n, ps.j_mode, std::max(1, ps.j_div), ps.nj, ps.norm, scores, nullptr};
+    CHK(launch_finish(c, fp));
+    SelectParams sl{scores, ps.eq_n, ps.nj, ps.cands, ps.cand_cs, ps.cand_js, ps.cand_off, ps.interval, ps.out_js,
+                    ps.out_off, ps.aux_out, ps.aux_div, ps.scores_out, ps.scores_out_ld, ps.best_out};
+    CHK(launch_select(c, sl));
+    c.ws.off = mark;
+    return 0;
+}
+
 int run_pass(Ctx& c, Pass& ps) {
+    if (ps.seg) return run_pass_seg(c, ps);
     const int esz = ps.i8 ? 1 : 4;
     g_alg_macs_cand = (double)ps.Mrows * ps.Ncols * ps.K * ps.Z;
     // every cached tensor read once per search pass -- both operands in fp32 as captured, raw_out and the metric weight
@@ -2420,9 +2541,18 @@ int linear_impl(const p4v_linear_desc* d, const float* W, const float* bias, con
 // ------------------------------------------------------------------------------------------------
 // MatMul
 // ------------------------------------------------------------------------------------------------
+// Row / column sub-blocks of the (n_G, n_V, n_H) view (reference matmul.py:109-138); (v, h): the block of a granular step
+struct MatMulBlocks {
+    int nVA = 1, nHA = 1, nVB = 1, nHB = 1, v = 0, h = 0;
+    bool any() const { return nVA != 1 || nHA != 1 || nVB != 1 || nHB != 1; }
+};
+int matmul_blocks_impl(const p4v_matmul_desc* d, const MatMulBlocks& mb, const float* A, const float* B, const float* O, const float* G,
+                       const float* mult, float* A_iv, float* B_iv, float* split, float* scores_out, int32_t* best_out, Ctx& c,
+                       float* fwd_out, const Stage& sg);
+
 int matmul_impl(const p4v_matmul_desc* d, const float* A, const float* B, const float* O, const float* G,
                 const float* mult, float* A_iv, float* B_iv, float* split, float* scores_out, int32_t* best_out, Ctx& c,
-                float* fwd_out = nullptr, const Stage& sg = Stage{}) {
+                float* fwd_out = nullptr, const Stage& sg = Stage{}, const MatMulBlocks* mb = nullptr) {
     // fwd_out != nullptr: quant_forward (matmul.py:140-145; sos: matmul.py:595-598) -- intervals / split are INPUTS
     const int H = d->heads, Z = d->batch * d->heads, M = d->M, K = d->K, N = d->N;
     if (Z <= 0 || M <= 0 || K <= 0 || N <= 0 || d->eq_n <= 0) return fail(P4V_ERR_INVALID, "matmul: non-positive dimension");
@@ -2435,6 +2565,8 @@ int matmul_impl(const p4v_matmul_desc* d, const float* A, const float* B, const 
     if (d->sos && !split) return fail(P4V_ERR_INVALID, "matmul: sos needs d_split");
     cvt_bias(c);     // (first call of the process: probe the conversion quant16_sat8 relies on)
     CHK(q_wait_inputs(c));     // (inside a group with a "capture done" event: everything below reads captured tensors)
+    // row / column sub-blocks: the K-segmented kernel family; with all four block counts 1 nothing below changes
+    if (mb && mb->any()) return matmul_blocks_impl(d, *mb, A, B, O, G, mult, A_iv, B_iv, split, scores_out, best_out, c, fwd_out, sg);
     const int ncand = d->eq_n + 1;
     const int NSPLIT = 20;  // matmul.py:636
 
@@ -2633,6 +2765,130 @@ int matmul_impl(const p4v_matmul_desc* d, const float* A, const float* B, const 
             CHK(run_pass_pruned(c, ps));
             if (memo_on) { CHK(read_dev(c, B_iv, H, val)); memo_B.entries.push_back({key, val}); g_memo_misses++; }
         }
+    }
+    return 0;
+}
+
+// ---- MatMul with row / column sub-blocks (n_V, n_H > 1; reference matmul.py:109-138, 419-440, 483-563) -------------------------
+// Intervals are [heads][n_V][n_H] (the reference's (1, n_G = heads, 1, n_V, 1, n_H, 1)).  The search is the reference's greedy
+// coordinate descent: block (v, h) in product(range(n_V), range(n_H)) order, its candidates mult * INITIAL interval replacing
+// that block's scale only, every other block on the interval entering the step, the score the full-output score per head; each
+// step is one sweep of the whole operand (no pruning, no pass memo: first version).  Score tables [round][step][eq_n][heads],
+// steps = A blocks then B blocks (split-of-softmax: the 20-row split table, then B blocks).
+int matmul_blocks_impl(const p4v_matmul_desc* d, const MatMulBlocks& mb, const float* A, const float* B, const float* O, const float* G,
+                       const float* mult, float* A_iv, float* B_iv, float* split, float* scores_out, int32_t* best_out, Ctx& c,
+                       float* fwd_out, const Stage& sg) {
+    const int H = d->heads, Z = d->batch * d->heads, M = d->M, K = d->K, N = d->N;
+    const int nVA = mb.nVA, nHA = mb.nHA, nVB = mb.nVB, nHB = mb.nHB;
+    if (nVA < 1 || nHA < 1 || nVB < 1 || nHB < 1) return fail(P4V_ERR_INVALID, "matmul: non-positive block count");
+    if (nVA > 8 || nHA > 8 || nVB > 8 || nHB > 8) return fail(P4V_ERR_UNSUPPORTED, "matmul: sub-blocks up to n_V, n_H = 8 are implemented on the GPU");
+    if (d->sos && (nVA != 1 || nHA != 1)) return fail(P4V_ERR_INVALID, "matmul: the split-of-softmax operand has no sub-blocks (matmul.py:586-588)");
+    if (d->A_bit < 2 || d->B_bit < 2) return fail(P4V_ERR_UNSUPPORTED, "matmul: bit widths 2..8 supported");
+    int epi, wt_mode;
+    metric_epi(d->metric, &epi, &wt_mode);
+    if (epi == EPI_COS && !fwd_out && sg.searches())
+        return fail(P4V_ERR_UNSUPPORTED, "matmul: the cosine metric with row/column sub-blocks (n_V, n_H > 1) is not implemented on the GPU");
+    SegPlan g{};
+    g.batch = d->batch; g.H = H; g.M = M; g.K = K; g.N = N;
+    g.nVA = nVA; g.nHA = nHA; g.nVB = nVB; g.nHB = nHB;
+    g.crA = cdiv(M, nVA); g.ccA = cdiv(K, nHA); g.crB = cdiv(K, nVB); g.ccB = cdiv(N, nHB);
+    g.A = A; g.B = B;
+    for (int i = 0; i < 4; ++i) { g.a_st[i] = d->a_stride[i]; g.b_st[i] = d->b_stride[i]; }
+    g.Aq = 1 << (d->A_bit - 1); g.Bq = 1 << (d->B_bit - 1); g.sos = d->sos != 0;
+    {   // K cut at every multiple of A's column-block width and of B's row-block width: S <= n_H_A + n_V_B - 1 segments
+        if (K >= 16384) return fail(P4V_ERR_UNSUPPORTED, "matmul: K < 16384 with sub-blocks");
+        std::vector<int> cuts{0};
+        for (int i = 1; i < nHA; ++i) if (i * g.ccA < K) cuts.push_back(i * g.ccA);
+        for (int i = 1; i < nVB; ++i) if (i * g.crB < K) cuts.push_back(i * g.crB);
+        std::sort(cuts.begin(), cuts.end());
+        cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
+        g.seg.S = (int)cuts.size();
+        int dpos = 0;
+        for (int s = 0; s < g.seg.S; ++s) {
+            const int k1 = s + 1 < g.seg.S ? cuts[s + 1] : K;
+            g.seg.k0[s] = (short)cuts[s]; g.seg.d0[s] = (short)dpos;
+            g.ablk[s] = (unsigned char)(cuts[s] / g.ccA); g.bblk[s] = (unsigned char)(cuts[s] / g.crB);
+            dpos += (int)rup(k1 - cuts[s], 64);
+        }
+        for (int s = g.seg.S; s <= SEG_MAX; ++s) { g.seg.k0[s] = (short)K; g.seg.d0[s] = (short)dpos; }
+        g.Kseg = dpos;
+        if (g.Kseg / SW_BKB > SEG_KT_MAX) return fail(P4V_ERR_UNSUPPORTED, "matmul: K too large for the segment table");
+    }
+    const int nA = d->sos ? 1 : H * nVA * nHA, nB = H * nVB * nHB, ncand = d->eq_n + 1;
+    unsigned* enc_A = c.ws.get<unsigned>((size_t)H * nVA * nHA);
+    unsigned* enc_B = c.ws.get<unsigned>((size_t)nB);
+    float* A_cands_ws = c.ws.get<float>((size_t)ncand * H * nVA * nHA);
+    float* B_cands_ws = c.ws.get<float>((size_t)ncand * nB);
+    if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small");
+    g.ivA = A_iv; g.ivB = B_iv; g.split = split;
+
+    if (fwd_out) {       // quant_forward (matmul.py:140-145; sos: 595-598): intervals / split are inputs
+        Pass fp{};
+        fp.seg = &g; fp.Z = Z; fp.K = K; fp.Mrows = M; fp.Ncols = N; fp.i8 = true; fp.twin = g.sos;
+        fp.epi = EPI_FWD; fp.eq_n = 1; fp.store_out = fwd_out;
+        return run_pass(c, fp);
+    }
+    if (sg.mask & ST_INIT) {
+        // min-max per block; a block of nothing but padding gets 0 (the reference pads with zeros): the running maxima start at
+        // enc(+0.0f) -- the bit pattern of -0.0f --, not at k_absmax's "nothing seen" (which decodes to NaN)
+        auto absmax = [&](const float* src, const int64_t* st, int R, int C, int nV, int nH, int crb_r, int crb_c, unsigned* out) -> int {
+            if (c.dry) return 0;
+            const int n = H * nV * nH;
+            CHK(enqueue(c, KERN(FillParams, k_fill_f32), dim3(cdiv(n, 256)), dim3(256), 0, FillParams{reinterpret_cast<float*>(out), -0.0f, n}));
+            AbsMaxParams p{src, (long)st[0], (long)st[1], (long)st[2], (long)st[3], d->batch, H, R, C, nV, nH, crb_r, crb_c, 0, 0, out};
+            p.row_tile = std::max(1, std::min(crb_r, std::max(1, 8192 / std::max(1, std::min(crb_c, C)))));
+            return enqueue(c, KERN(AbsMaxParams, k_absmax), dim3(cdiv(crb_r, p.row_tile) * nV * nH, H, d->batch), dim3(256), 0, p);
+        };
+        if (!d->sos) {
+            CHK(absmax(A, d->a_stride, M, K, nVA, nHA, g.crA, g.ccA, enc_A));
+            CHK(launch_interval(c, enc_A, nA, (float)(g.Aq - 0.5), d->init_layerwise, A_iv));
+        }
+        CHK(absmax(B, d->b_stride, K, N, nVB, nHB, g.crB, g.ccB, enc_B));
+        CHK(launch_interval(c, enc_B, nB, (float)(g.Bq - 0.5), d->init_layerwise, B_iv));
+        if (sg.searches()) {
+            if (!d->sos) CHK(launch_cands(c, mult, A_iv, ncand, nA, A_cands_ws));
+            CHK(launch_cands(c, mult, B_iv, ncand, nB, B_cands_ws));
+        }
+    }
+    if (!sg.searches()) return 0;
+    // one block step: `side` 1 / 2 = A / B, candidates cands[c * cs + head * hs] of block (v, h)
+    auto step = [&](int side, int v, int h, const float* cands, int cs, int hs, float* so, int32_t* bo) -> int {
+        const int nV = side == 1 ? nVA : nVB, nH = side == 1 ? nHA : nHB;
+        if (v < 0 || v >= nV || h < 0 || h >= nH) return fail(P4V_ERR_INVALID, "matmul: block (%d, %d) outside the %d x %d blocks", v, h, nV, nH);
+        g.side = side; g.ov_v = v; g.ov_h = h; g.cands = cands; g.cand_cs = cs; g.cand_hs = hs;
+        Pass ps{};
+        ps.seg = &g; ps.Z = Z; ps.K = K; ps.Mrows = M; ps.Ncols = N; ps.i8 = true; ps.twin = g.sos;
+        ps.epi = epi; ps.wt_mode = wt_mode; ps.O = O; ps.G = G; ps.eq_n = d->eq_n;
+        ps.j_mode = 2; ps.j_div = H; ps.nj = H; ps.norm = 1.0 / ((double)M * N);
+        ps.cands = cands; ps.cand_cs = cs; ps.cand_js = hs; ps.cand_off = 0;
+        ps.interval = (side == 1 ? A_iv : B_iv) + v * nH + h; ps.out_js = nV * nH; ps.out_off = 0;
+        ps.scores_out = so; ps.scores_out_ld = H; ps.best_out = bo;
+        return run_pass(c, ps);
+    };
+    if (!sg.full()) {    // granular: ONE block step on the caller's candidate table [eq_n + 1][heads]
+        if (sg.mask & ST_S1) CHK(step(1, mb.v, mb.h, sg.cands1, H, 1, scores_out, best_out));
+        if (sg.mask & ST_S2) CHK(step(2, mb.v, mb.h, sg.cands2, H, 1, scores_out, best_out));
+        return 0;
+    }
+    const int stepsA = d->sos ? 1 : nVA * nHA, steps = stepsA + nVB * nHB;
+    for (int round = 0; round < d->search_round; ++round) {
+        int st = 0;
+        auto so = [&](int s) { return scores_out ? scores_out + ((long)(round * steps + s) * d->eq_n) * H : nullptr; };
+        auto bo = [&](int s) { return best_out ? best_out + (long)(round * steps + s) * H : nullptr; };
+        if (d->sos) {
+            // the split search against the UNQUANTISED B (matmul.py:600-631) knows no blocks: the head-wise engine's pass
+            const size_t mark = c.ws.off;
+            CHK(matmul_impl(d, A, B, O, G, nullptr, A_iv, nullptr, split, so(0), bo(0), c, nullptr, Stage{ST_S1, nullptr, nullptr}));
+            c.ws.off = mark;
+            st = 1;
+        } else {
+            for (int v = 0; v < nVA; ++v)
+                for (int h = 0; h < nHA; ++h, ++st)
+                    CHK(step(1, v, h, A_cands_ws + v * nHA + h, H * nVA * nHA, nVA * nHA, so(st), bo(st)));
+        }
+        for (int v = 0; v < nVB; ++v)
+            for (int h = 0; h < nHB; ++h, ++st)
+                CHK(step(2, v, h, B_cands_ws + v * nHB + h, nB, nVB * nHB, so(st), bo(st)));
     }
     return 0;
 }
@@ -2858,6 +3114,14 @@ int run_group_member(const p4v_group_job& j, Ctx& c) {
             if (!j.in[0] || !j.in[1] || !j.in[2] || !j.mult || !j.out[0] || !j.out[1] || !j.workspace) return fail(P4V_ERR_INVALID, "group: matmul member with a null pointer");
             return matmul_impl(d, j.in[0], j.in[1], j.in[2], j.in[3], j.mult, j.out[0], j.out[1], j.out[2], nullptr, nullptr, c);
         }
+        case P4V_JOB_MATMUL_BLOCKS: {
+            const p4v_matmul_blocks_desc* d = (const p4v_matmul_blocks_desc*)j.desc;
+            if (!j.in[0] || !j.in[1] || !j.in[2] || !j.mult || !j.out[0] || !j.out[1] || !j.workspace) return fail(P4V_ERR_INVALID, "group: matmul member with a null pointer");
+            if (d->n_V_A < 1 || d->n_H_A < 1 || d->n_V_B < 1 || d->n_H_B < 1) return fail(P4V_ERR_INVALID, "group: matmul member with a non-positive block count");
+            MatMulBlocks mb;
+            mb.nVA = d->n_V_A; mb.nHA = d->n_H_A; mb.nVB = d->n_V_B; mb.nHB = d->n_H_B;
+            return matmul_impl(&d->mm, j.in[0], j.in[1], j.in[2], j.in[3], j.mult, j.out[0], j.out[1], j.out[2], nullptr, nullptr, c, nullptr, Stage{}, &mb);
+        }
         case P4V_JOB_CONV: {
             const p4v_conv_desc* d = (const p4v_conv_desc*)j.desc;
             if (!j.in[0] || !j.in[2] || !j.in[3] || !j.mult || !j.out[0] || !j.out[1] || !j.workspace) return fail(P4V_ERR_INVALID, "group: conv member with a null pointer");
@@ -2868,7 +3132,8 @@ int run_group_member(const p4v_group_job& j, Ctx& c) {
     }
 }
 size_t group_desc_bytes(int kind) {
-    return kind == P4V_JOB_LINEAR ? sizeof(p4v_linear_desc) : kind == P4V_JOB_MATMUL ? sizeof(p4v_matmul_desc) : kind == P4V_JOB_CONV ? sizeof(p4v_conv_desc) : 0;
+    return kind == P4V_JOB_LINEAR ? sizeof(p4v_linear_desc) : kind == P4V_JOB_MATMUL ? sizeof(p4v_matmul_desc) : kind == P4V_JOB_CONV ? sizeof(p4v_conv_desc) :
+           kind == P4V_JOB_MATMUL_BLOCKS ? sizeof(p4v_matmul_blocks_desc) : 0;
 }
 
 }  // namespace
@@ -2937,6 +3202,84 @@ int p4v_matmul_calibrate(const p4v_matmul_desc* desc, const float* d_A, const fl
         return fail(P4V_ERR_INVALID, "matmul: null pointer");
     Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
     return matmul_impl(desc, d_A, d_B, d_out, d_grad, d_mult, d_A_interval, d_B_interval, d_split, d_scores, d_best, c);
+}
+
+// ---- MatMul with row / column sub-blocks: matmul_impl with the block counts (all 1: the head-wise path, launch for launch) ----
+static MatMulBlocks blocks_of(const p4v_matmul_blocks_desc* d, int v = 0, int h = 0) {
+    MatMulBlocks mb;
+    mb.nVA = d->n_V_A; mb.nHA = d->n_H_A; mb.nVB = d->n_V_B; mb.nHB = d->n_H_B; mb.v = v; mb.h = h;
+    return mb;
+}
+static int blocks_check(const p4v_matmul_blocks_desc* d, const char* who) {
+    if (d->n_V_A < 1 || d->n_H_A < 1 || d->n_V_B < 1 || d->n_H_B < 1) return fail(P4V_ERR_INVALID, "%s: non-positive block count", who);
+    return 0;
+}
+
+size_t p4v_matmul_blocks_workspace_bytes(const p4v_matmul_blocks_desc* desc) {
+    if (!desc || blocks_check(desc, "p4v_matmul_blocks_workspace_bytes")) return 0;
+    Ctx c{nullptr, Arena(nullptr, 0), true};
+    float dummy = 0;
+    float* fwd = (desc->mm.reserved & 4) ? (float*)16 : nullptr;
+    const MatMulBlocks mb = blocks_of(desc);
+    if (matmul_impl(&desc->mm, nullptr, nullptr, nullptr, (const float*)1, nullptr, nullptr, nullptr, &dummy, nullptr, nullptr, c, fwd,
+                    Stage{}, &mb) != 0) return 0;
+    return c.ws.peak + 4096;
+}
+
+int p4v_matmul_blocks_calibrate(const p4v_matmul_blocks_desc* desc, const float* d_A, const float* d_B, const float* d_out,
+                                const float* d_grad, const float* d_mult, float* d_A_interval, float* d_B_interval,
+                                float* d_split, float* d_scores, int32_t* d_best, void* d_workspace, size_t workspace_bytes,
+                                void* stream) {
+    if (!desc || !d_A || !d_B || !d_out || !d_mult || !d_A_interval || !d_B_interval || !d_workspace)
+        return fail(P4V_ERR_INVALID, "p4v_matmul_blocks_calibrate: null pointer");
+    CHK(blocks_check(desc, "p4v_matmul_blocks_calibrate"));
+    Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
+    const MatMulBlocks mb = blocks_of(desc);
+    return matmul_impl(&desc->mm, d_A, d_B, d_out, d_grad, d_mult, d_A_interval, d_B_interval, d_split, d_scores, d_best, c, nullptr,
+                       Stage{}, &mb);
+}
+
+int p4v_amax_init_matmul_blocks(const p4v_matmul_blocks_desc* desc, const float* d_A, const float* d_B, float* d_A_interval,
+                                float* d_B_interval, void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (!desc || !d_A || !d_B || !d_A_interval || !d_B_interval || !d_workspace)
+        return fail(P4V_ERR_INVALID, "p4v_amax_init_matmul_blocks: null pointer");
+    CHK(blocks_check(desc, "p4v_amax_init_matmul_blocks"));
+    Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
+    float dummy_split = 0;   // only checked for presence
+    const MatMulBlocks mb = blocks_of(desc);
+    return matmul_impl(&desc->mm, d_A, d_B, nullptr, nullptr, nullptr, d_A_interval, d_B_interval, &dummy_split, nullptr, nullptr, c,
+                       nullptr, Stage{ST_INIT, nullptr, nullptr}, &mb);
+}
+
+int p4v_matmul_blocks_search(const p4v_matmul_blocks_desc* desc, int32_t operand, int32_t v, int32_t h, const float* d_A,
+                             const float* d_B, const float* d_out, const float* d_grad, const float* d_cands,
+                             float* d_A_interval, float* d_B_interval, const float* d_split, float* d_scores, int32_t* d_best,
+                             void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (!desc || !d_A || !d_B || !d_out || !d_cands || !d_A_interval || !d_B_interval || !d_workspace)
+        return fail(P4V_ERR_INVALID, "p4v_matmul_blocks_search: null pointer");
+    CHK(blocks_check(desc, "p4v_matmul_blocks_search"));
+    if (operand != 0 && operand != 1) return fail(P4V_ERR_INVALID, "p4v_matmul_blocks_search: operand is 0 (A) or 1 (B)");
+    if (operand == 0 && desc->mm.sos) return fail(P4V_ERR_INVALID, "p4v_matmul_blocks_search: the split-of-softmax class searches its split (p4v_sos_search_split)");
+    if (desc->mm.sos && !d_split) return fail(P4V_ERR_INVALID, "p4v_matmul_blocks_search: sos needs d_split");
+    const int nV = operand == 0 ? desc->n_V_A : desc->n_V_B, nH = operand == 0 ? desc->n_H_A : desc->n_H_B;
+    if (v < 0 || v >= nV || h < 0 || h >= nH) return fail(P4V_ERR_INVALID, "p4v_matmul_blocks_search: block (%d, %d) outside the %d x %d blocks", v, h, nV, nH);
+    Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
+    const MatMulBlocks mb = blocks_of(desc, v, h);
+    return matmul_impl(&desc->mm, d_A, d_B, d_out, d_grad, nullptr, d_A_interval, d_B_interval, const_cast<float*>(d_split), d_scores,
+                       d_best, c, nullptr, operand == 0 ? Stage{ST_S1, d_cands, nullptr} : Stage{ST_S2, nullptr, d_cands}, &mb);
+}
+
+int p4v_matmul_blocks_quant_forward(const p4v_matmul_blocks_desc* desc, const float* d_A, const float* d_B,
+                                    const float* d_A_interval, const float* d_B_interval, const float* d_split, float* d_out,
+                                    void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (!desc || !d_A || !d_B || !d_A_interval || !d_B_interval || !d_out || !d_workspace)
+        return fail(P4V_ERR_INVALID, "p4v_matmul_blocks_quant_forward: null pointer");
+    CHK(blocks_check(desc, "p4v_matmul_blocks_quant_forward"));
+    if (desc->mm.sos && !d_split) return fail(P4V_ERR_INVALID, "p4v_matmul_blocks_quant_forward: sos needs d_split");
+    Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
+    const MatMulBlocks mb = blocks_of(desc);
+    return matmul_impl(&desc->mm, d_A, d_B, nullptr, nullptr, nullptr, const_cast<float*>(d_A_interval),
+                       const_cast<float*>(d_B_interval), const_cast<float*>(d_split), nullptr, nullptr, c, d_out, Stage{}, &mb);
 }
 
 size_t p4v_conv_workspace_bytes(const p4v_conv_desc* desc) {
@@ -3219,7 +3562,7 @@ static int stats_drain() {
         float ms = 0;
         HIPCHK(hipEventElapsedTime(&ms, r.a, r.b));
         ms = (float)std::max(0.0, (double)ms - g_evt_overhead_ms);
-        if (r.kind == 0 || (r.kind >= 2 && r.kind <= 9) || (r.kind >= 12 && r.kind <= 14)) { g_stats.sweep_i8_ms += ms; g_stats.sweep_i8_launches++; g_stats.sweep_i8_macs += r.macs; g_stats.sweep_i8_alg_macs += r.alg; }
+        if (r.kind == 0 || (r.kind >= 2 && r.kind <= 9) || (r.kind >= 12 && r.kind <= 15)) { g_stats.sweep_i8_ms += ms; g_stats.sweep_i8_launches++; g_stats.sweep_i8_macs += r.macs; g_stats.sweep_i8_alg_macs += r.alg; }
         if (r.kind == 2) { g_stats.sweep6_ms += ms; g_stats.sweep6_launches++; g_stats.sweep6_macs += r.macs; g_stats.sweep6_alg_macs += r.alg; }
         if (r.kind == 3 || r.kind == 4) { g_stats.sweep7_ms += ms; g_stats.sweep7_launches++; g_stats.sweep7_macs += r.macs; g_stats.sweep7_alg_macs += r.alg; }
         if (r.kind == 4) { g_stats.sweep7_twin_ms += ms; g_stats.sweep7_twin_launches++; }

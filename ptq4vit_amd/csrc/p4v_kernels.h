@@ -4467,4 +4467,333 @@ __device__ __forceinline__ void k_merge_scores_body(const MergeParams& a_, const
 __global__ void k_merge_scores(MergeParams p) { k_merge_scores_body(p, P4V_BIDX, P4V_GDIM); }
 __global__ void k_merge_scores_g(GroupArgs<MergeParams> a) { P4V_GROUP_ENTER(a); k_merge_scores_body(a.p[m_], vb_, vg_); }
 
+// ------------------------------------------------------------------------------------------
+// MatMul sub-block scales (n_V, n_H > 1; reference matmul.py:109-138, 483-563): k_pack_seg + k_sweep_seg
+// ------------------------------------------------------------------------------------------
+// A is (b, H, M, K) with intervals sA[head][vA(m)][hA(k)], B is (b, H, K, N) with sB[head][vB(k)][hB(n)]; the blocks are
+// ceil(dim / n) wide, the last one ragged or empty (matmul.py:109-122).  Cut K at every multiple of A's column-block width and of
+// B's row-block width: S <= n_H_A + n_V_B - 1 segments, and inside segment s both scales are constant along k, so
+//   out_sim[m][n] = sum_s sA[h][vA(m)][hA(s)] * sB[h][vB(s)][hB(n)] * I_s[m][n],   I_s = sum_{k in s} kA * kB
+// with I_s an exact int32 dot product of grid indices and the sum a handful of fp32 terms in fixed segment order: the same
+// O(1e-7) distance to the reference's fp32 GEMM as the head-wise int8 path.  The planes are laid out so that every segment starts
+// on a 64-byte k-tile (Kseg = sum_s roundup64(len_s), zeros between): a k-tile never straddles a cut, and the sweep flushes its
+// int32 accumulators into fp32 sums at the last k-tile of each segment.  A zero-length block has no segment and no element:
+// its interval (0: the min-max of nothing but padding) is never read.
+constexpr int SEG_MAX = 16;
+struct SegTable {
+    int S;                       // segments (1 .. SEG_MAX - 1)
+    short k0[SEG_MAX + 1];       // first source k of segment s; k0[S] = K
+    short d0[SEG_MAX + 1];       // first plane k of segment s (multiple of 64); d0[S] = Kseg
+};
+
+// The segment-aligned producer: int8 planes [C][Z][Rp][Kseg] of one operand's logical [Z][R][K] view.  The scale of an element is
+// iv[head][row block][k block] (head = z % H; strides iv_hs / iv_rs / iv_ks), except that candidate c replaces block (ov_r, ov_k)
+// by cands[c][head] -- the table scales[c][head][row block][k block] of a block step, without materialising it.  A kernel of
+// its own rather than a branch of k_pack (which lives on its register budget, tests/test_isa_budget.py).  Quantisers: k_pack1's
+// (quant16_sat8 on the full symmetric 8-bit grid, quant16_any otherwise: both fall back to the IEEE division the reference
+// performs), pack_value's formulas for the split-of-softmax ranges.  Padding bytes are zero whatever the scale.
+struct PackSegParams {
+    const float* src; long s_z, s_r, s_k, s_z2; int zdiv;
+    int Z, R, K, Rp, Kseg;
+    void* dst; int C;
+    const float* iv; int iv_hs, iv_rs, iv_ks; int H, r_div, nblk_r;
+    const float* cands; int cand_cs, cand_hs, ov_r, ov_k;
+    int mode, lo, hi; float qm1, qbias;
+    SegTable seg;
+    unsigned char kblk[SEG_MAX];      // k block of segment s in THIS operand's interval tensor
+};
+__device__ __forceinline__ void k_pack_seg_body(const PackSegParams& p, const uint3 blockIdx, const uint3 gridDim) {
+    const unsigned kchunks = p.Kseg / 16;
+    const unsigned total = (unsigned)p.Z * p.Rp * kchunks;      // < 2^31: checked by the launcher
+    const int cbeg = blockIdx.y * PACK_CG, cend = min(p.C, cbeg + PACK_CG);
+    const float flo = (float)p.lo, fhi = (float)p.hi;
+    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+        const unsigned row = i / kchunks;
+        const int kd = (int)(i - row * kchunks) * 16;
+        const int z = (int)(row / (unsigned)p.Rp);
+        const int r = (int)(row - (unsigned)z * p.Rp);
+        // the segment of this 16-byte run (segments start on multiples of 64: a run lies in one); constant indices only
+        int ks0 = p.seg.k0[0], kd0 = 0, kend = p.seg.k0[1], kb = p.kblk[0];
+#pragma unroll
+        for (int t = 1; t < SEG_MAX; ++t)
+            if (t < p.seg.S && kd >= p.seg.d0[t]) { ks0 = p.seg.k0[t]; kd0 = p.seg.d0[t]; kend = p.seg.k0[t + 1]; kb = p.kblk[t]; }
+        const int ks = ks0 + (kd - kd0);
+        const int nvalid = r < p.R ? max(0, min(16, kend - ks)) : 0;      // bytes of this run that are not padding
+        const float* zbase = p.zdiv > 0 ? p.src + (long)(z / p.zdiv) * p.s_z2 + (long)(z % p.zdiv) * p.s_z
+                                        : p.src + (long)z * p.s_z;
+        float x[16];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) x[e] = e < nvalid ? zbase[(long)r * p.s_r + (long)(ks + e) * p.s_k] : 0.0f;
+        const int head = z % p.H, rb = min(r / p.r_div, p.nblk_r - 1);
+        const float s_base = p.iv[head * p.iv_hs + rb * p.iv_rs + kb * p.iv_ks];
+        const bool ov = p.cands && rb == p.ov_r && kb == p.ov_k;
+        for (int c = cbeg; c < cend; ++c) {
+            const float s = ov ? p.cands[(long)c * p.cand_cs + head * p.cand_hs] : s_base;
+            v4i w;
+            if (p.mode == PACK_SYM) {
+                if (p.qbias != 0.0f) quant16_sat8(x, s, 1.0f / s, p.qbias, w);
+                else quant16_any(x, s, 1.0f / s, flo, fhi, false, w);
+            } else {
+                const float a_int = s / p.qm1;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    int acc = 0;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float xe = x[q * 4 + e];
+                        const float v = p.mode == PACK_SOS_HI ? fminf(fmaxf(rintf(fminf(fmaxf(xe, s), 1.0f) * p.qm1), 0.0f), p.qm1)
+                                                              : fminf(fmaxf(rintf(fminf(fmaxf(xe, 0.0f), s) / a_int), 0.0f), p.qm1);
+                        acc |= ((int)v & 0xff) << (8 * e);
+                    }
+                    w[q] = acc;
+                }
+            }
+            if (nvalid < 16) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int rem = nvalid - 4 * q;
+                    w[q] = rem >= 4 ? w[q] : rem <= 0 ? 0 : (int)((unsigned)w[q] & ((1u << (8 * rem)) - 1u));
+                }
+            }
+            __builtin_nontemporal_store(w, reinterpret_cast<v4i*>(reinterpret_cast<int8_t*>(p.dst) + ((((long)c * p.Z + z) * p.Rp + r) * p.Kseg + kd)));
+        }
+    }
+}
+__global__ __launch_bounds__(256) void k_pack_seg(PackSegParams p) { k_pack_seg_body(p, P4V_BIDX, P4V_GDIM); }
+__global__ __launch_bounds__(256) void k_pack_seg_g(GroupArgs<PackSegParams> a) { P4V_GROUP_ENTER(a); k_pack_seg_body(a.p[m_], vb_, vg_); }
+
+// The int8 sweep over segment-aligned planes: k_sweep<int8_t>'s 128 x 128 LDS-staged tile (2 x 4 waves of 64 x 32, the same
+// fragment and C/D maps, `part` layout and candidate-range handling), plus per workgroup
+//   tile_seg[kt]   the segment that ENDS with k-tile kt (-1: none),
+//   rs[s][128]     the row-side scale of segment s for the tile's rows:    sA[head][vA(m)][hA(s)]   (TWIN: the constant 1/(q-1))
+//   cs[s][128]     the column-side scale for the tile's columns:           sB[head][vB(s)][hB(n)]
+// in LDS.  Both tables are filled once with the current intervals; the searched side is refilled per candidate with the block
+// (ov_v, ov_h) on cands[c][head].  At a segment's last k-tile every wave flushes sum = fma((float)acc, rs * cs, sum), acc = 0.
+// TWIN: the split-of-softmax low-range plane accumulates beside the high-range one and flushes with the scalar A_interval (the
+// class has no blocks on A, matmul.py:586-588).  Epilogues: the difference metrics and EPI_FWD (cosine is not offered).
+struct SweepSegParams {
+    const int* crange;
+    const void* A; long a_cs, a_zs;
+    const void* A2; long a2_zs;
+    const void* B; long b_cs, b_zs;
+    int ldk, ktiles;
+    const float* ivA; const float* ivB;        // [H][nVA][nHA] / [H][nVB][nHB] current intervals
+    int H, nVA, nHA, nHB, nVB, m_div, n_div;   // rows per A row block, columns per B column block
+    const float* cands; int cand_cs, cand_hs;  // searched block's candidates: cands[c * cand_cs + head * cand_hs]
+    int side, ov_v, ov_h;                      // 0: nothing searched (forward), 1: A block (ov_v, ov_h), 2: B block
+    float rs_const; const float* rs2;          // TWIN: high-range row scale 1/(q-1); low-range row scale *rs2 (A_interval)
+    const float* O; const float* Wt; int wt_mode;
+    long o_zs, o_ms;
+    int M, N, Z, c0, c1;
+    float* part; long p_cs, p_zs; int Np, mtiles, ntiles;
+    float* store;                              // EPI_FWD output [Z][M][N]
+    SegTable seg;
+    unsigned char ablk[SEG_MAX], bblk[SEG_MAX];   // hA(s), vB(s)
+};
+static constexpr int SEG_KT_MAX = 256;            // k-tiles of a plane row the tile table holds
+
+template <bool TWIN, int EPI>
+__device__ __forceinline__ void k_sweep_seg_body(const SweepSegParams& p, const uint3 blockIdx, const uint3 gridDim) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int NPL = TWIN ? 3 : 2;
+    constexpr int STAGE = NPL * SW_TILE_BYTES;
+    float* rs = reinterpret_cast<float*>(smem + 2 * STAGE);          // [SEG_MAX][128]
+    float* cs = rs + SEG_MAX * 128;                                  // [SEG_MAX][128]
+    short* tile_seg = reinterpret_cast<short*>(cs + SEG_MAX * 128);  // [SEG_KT_MAX]
+    unsigned char* sblk = reinterpret_cast<unsigned char*>(tile_seg + SEG_KT_MAX);   // [2][SEG_MAX]: hA(s), vB(s)
+
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int wr = wid >> 2, wc = wid & 3;
+    const int g = lane >> 5, l31 = lane & 31;
+    const int nwg = p.mtiles * p.ntiles;
+    const int t = xcd_remap(blockIdx.x, nwg);
+    const int mt = t % p.mtiles, nt = t / p.mtiles;
+    const int z = blockIdx.y, head = z % p.H;
+    const int m0 = mt * SW_BM, n0 = nt * SW_BN;
+    const int per = (p.c1 - p.c0 + gridDim.z - 1) / gridDim.z;
+    int c_lo_ = p.c0 + blockIdx.z * per, c_hi_ = min(p.c1, c_lo_ + per);
+    clip_crange(p.crange, c_lo_, c_hi_);
+    const int c_lo = c_lo_, c_hi = c_hi_;
+    if (c_lo >= c_hi) return;
+    const int S = p.seg.S;
+
+    // ---- per-workgroup tables ----------------------------------------------------------------------
+    for (int kt = tid; kt < p.ktiles; kt += 512) tile_seg[kt] = -1;
+    if (tid == 0) {
+#pragma unroll
+        for (int s = 0; s < SEG_MAX; ++s) { sblk[s] = p.ablk[s]; sblk[SEG_MAX + s] = p.bblk[s]; }
+    }
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int s = 0; s < SEG_MAX - 1; ++s)
+            if (s < S) tile_seg[p.seg.d0[s + 1] / SW_BKB - 1] = (short)s;
+    }
+    auto fill_rows = [&](int c) {
+        for (int i = tid; i < S * 128; i += 512) {
+            const int s = i >> 7, v = min(min(m0 + (i & 127), p.M - 1) / p.m_div, p.nVA - 1), h = sblk[s];
+            float val = TWIN ? p.rs_const : p.ivA[(head * p.nVA + v) * p.nHA + h];
+            if (!TWIN && c >= 0 && p.side == 1 && v == p.ov_v && h == p.ov_h) val = p.cands[(long)c * p.cand_cs + head * p.cand_hs];
+            rs[i] = val;
+        }
+    };
+    auto fill_cols = [&](int c) {
+        for (int i = tid; i < S * 128; i += 512) {
+            const int s = i >> 7, h = min(min(n0 + (i & 127), p.N - 1) / p.n_div, p.nHB - 1), v = sblk[SEG_MAX + s];
+            float val = p.ivB[(head * p.nVB + v) * p.nHB + h];
+            if (c >= 0 && p.side == 2 && v == p.ov_v && h == p.ov_h) val = p.cands[(long)c * p.cand_cs + head * p.cand_hs];
+            cs[i] = val;
+        }
+    };
+    fill_rows(-1);
+    fill_cols(-1);
+    const float rs2 = TWIN ? p.rs2[0] : 0.0f;
+
+    // ---- candidate-invariant epilogue operands (k_sweep's phases 1 and 2) ---------------------------
+    float u[2][16], w[2][16];
+    const int n = n0 + wc * 32 + l31;
+    const bool ncol_ok = n < p.N;
+    if constexpr (EPI != EPI_FWD) {
+        const long ncol_off = (long)z * p.o_zs + min(n, p.N - 1);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int mc = min(m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g, p.M - 1);
+                const long idx = ncol_off + (long)mc * p.o_ms;
+                u[i][r] = p.O[idx];
+                w[i][r] = p.Wt[idx];   // host passes Wt = O when the metric has no weight tensor
+            }
+        const int wm = p.wt_mode;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
+                const bool ok = ncol_ok && m < p.M;
+                const float o = u[i][r], gw = w[i][r];
+                float wv;
+                if (wm == 1) wv = gw; else if (wm == 2) wv = o; else if (wm == 3) wv = fabsf(o); else wv = 1.0f;
+                u[i][r] = ok ? o : 0.0f;
+                w[i][r] = ok ? wv : 0.0f;
+            }
+    }
+
+    // ---- global -> LDS staging: one 16-byte piece per thread per plane per k-tile ---------------------
+    const int ld_row = tid >> 2, ld_col = (tid & 3) * 16;
+    const char* gA = (const char*)p.A + (long)z * p.a_zs + (long)(m0 + ld_row) * p.ldk + ld_col;
+    const char* gA2 = TWIN ? (const char*)p.A2 + (long)z * p.a2_zs + (long)(m0 + ld_row) * p.ldk + ld_col : nullptr;
+    const char* gB = (const char*)p.B + (long)z * p.b_zs + (long)(n0 + ld_row) * p.ldk + ld_col;
+    const int lds_st = ld_row * SW_ROW + ld_col;
+    const int total = (c_hi - c_lo) * p.ktiles;
+    v4i ra, ra2, rb;
+    auto gload = [&](int it) {
+        const int c = c_lo + it / p.ktiles, kt = it % p.ktiles;
+        ra = *reinterpret_cast<const v4i*>(gA + (long)c * p.a_cs + kt * SW_BKB);
+        if (TWIN) ra2 = *reinterpret_cast<const v4i*>(gA2 + kt * SW_BKB);
+        rb = *reinterpret_cast<const v4i*>(gB + (long)c * p.b_cs + kt * SW_BKB);
+    };
+    auto lstore = [&](int stage) {
+        char* s = smem + stage * STAGE + lds_st;
+        *reinterpret_cast<v4i*>(s) = ra;
+        if (TWIN) *reinterpret_cast<v4i*>(s + SW_TILE_BYTES) = ra2;
+        *reinterpret_cast<v4i*>(s + (NPL - 1) * SW_TILE_BYTES) = rb;
+    };
+
+    v16i acc[2], acc2[2];
+    float sum[2][16];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { acc[i][r] = 0; if (TWIN) acc2[i][r] = 0; sum[i][r] = 0.0f; }
+
+    const int fa = (wr * 64 + l31) * SW_ROW;
+    const int fb = (NPL - 1) * SW_TILE_BYTES + (wc * 32 + l31) * SW_ROW;
+    const int row_l = wr * 64 + 4 * g, col_l = wc * 32 + l31;     // + i * 32 + (r & 3) + 8 * (r >> 2)
+
+    gload(0);
+    lstore(0);
+    __syncthreads();
+
+    for (int it = 0; it < total; ++it) {
+        const int stage = it & 1, kt = it % p.ktiles;
+        if (kt == 0 && it > 0 && p.side != 0) {
+            // the searched block's scales of the next candidate (every wave has left the previous candidate's epilogue: the
+            // barrier behind it; the first flush of this one lies behind this iteration's barrier)
+            const int c = c_lo + it / p.ktiles;
+            if (p.side == 1) fill_rows(c); else fill_cols(c);
+        }
+        if (it == 0 && p.side != 0) { if (p.side == 1) fill_rows(c_lo); else fill_cols(c_lo); }
+        if (it + 1 < total) gload(it + 1);
+        const char* s = smem + stage * STAGE;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {          // two 32-deep K steps per 64-byte row
+            const int off = h * 32 + g * 16;
+            const v4i b = *reinterpret_cast<const v4i*>(s + fb + off);
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const v4i a = *reinterpret_cast<const v4i*>(s + fa + i * 32 * SW_ROW + off);
+                acc[i] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, acc[i], 0, 0, 0);
+                if (TWIN) {
+                    const v4i a2 = *reinterpret_cast<const v4i*>(s + SW_TILE_BYTES + fa + i * 32 * SW_ROW + off);
+                    acc2[i] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a2, b, acc2[i], 0, 0, 0);
+                }
+            }
+        }
+        if (it + 1 < total) lstore(stage ^ 1);
+        __syncthreads();
+
+        const int sg = tile_seg[kt];
+        if (sg >= 0) {
+            // ---- last k-tile of segment sg: int32 partial products -> fp32 sums on the segment's scales ----
+            const float cscale = cs[sg * 128 + col_l];
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float rscale = rs[sg * 128 + row_l + i * 32 + (r & 3) + 8 * (r >> 2)];
+                    sum[i][r] = fmaf((float)acc[i][r], rscale * cscale, sum[i][r]);
+                    acc[i][r] = 0;
+                    if (TWIN) { sum[i][r] = fmaf((float)acc2[i][r], rs2 * cscale, sum[i][r]); acc2[i][r] = 0; }
+                }
+        }
+        if (kt == p.ktiles - 1) {
+            const int c = c_lo + it / p.ktiles;
+            if constexpr (EPI == EPI_FWD) {
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int m = m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
+                        if (ncol_ok && m < p.M) p.store[(long)z * p.M * p.N + (long)m * p.N + n] = sum[i][r];
+                    }
+            } else {
+                float colsum = 0.0f;
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float d = u[i][r] - sum[i][r];
+                        if (EPI == EPI_SQ_W) { const float tt = w[i][r] * d; colsum = fmaf(tt, tt, colsum); }
+                        else if (EPI == EPI_SQ) colsum = fmaf(d, d, colsum);
+                        else if (EPI == EPI_ABS) colsum += fabsf(d);
+                        else colsum = fmaf(w[i][r] * d, d, colsum);
+                    }
+                colsum += __shfl_xor(colsum, 32);
+                if (g == 0)
+                    p.part[(long)c * p.p_cs + (long)z * p.p_zs + (long)(mt * 2 + wr) * p.Np + n0 + wc * 32 + l31] = colsum;
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) sum[i][r] = 0.0f;
+            __syncthreads();      // the scale tables are rewritten for the next candidate
+        }
+    }
+}
+template <bool TWIN, int EPI>
+__global__ __launch_bounds__(512) void k_sweep_seg(SweepSegParams p) { k_sweep_seg_body<TWIN, EPI>(p, P4V_BIDX, P4V_GDIM); }
+template <bool TWIN, int EPI>
+__global__ __launch_bounds__(512) void k_sweep_seg_g(GroupArgs<SweepSegParams> a) { P4V_GROUP_ENTER(a); k_sweep_seg_body<TWIN, EPI>(a.p[m_], vb_, vg_); }
+
 }  // namespace p4v

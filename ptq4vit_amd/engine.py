@@ -264,8 +264,54 @@ def matmul_quant_forward(*, A, B, A_interval, B_interval, split, A_bit, B_bit, s
     return out
 
 
+def has_blocks(blocks):
+    """`blocks` = (n_V_A, n_H_A, n_V_B, n_H_B) of a MatMul: does any operand have row / column sub-blocks?"""
+    return blocks is not None and tuple(int(n) for n in blocks) != (1, 1, 1, 1)
+
+
+def _matmul_desc(A, B, A_bit, B_bit, metric, eq_n, search_round, sos, init_layerwise, reserved, blocks=None, wrap=False):
+    """p4v_matmul_desc of the operands -- wrapped in a p4v_matmul_blocks_desc when `blocks` has a count above 1 or `wrap` is
+    set (returns the descriptor to pass and its p4v_matmul_desc part)."""
+    bd = _lib.MatMulBlocksDesc() if (wrap or has_blocks(blocks)) else None
+    d = bd.mm if bd is not None else _lib.MatMulDesc()
+    b, H, M, K = A.shape
+    d.batch, d.heads, d.M, d.K, d.N = b, H, M, K, B.shape[3]
+    for i in range(4):
+        d.a_stride[i] = A.stride(i)
+        d.b_stride[i] = B.stride(i)
+    d.A_bit, d.B_bit, d.metric, d.eq_n, d.search_round = A_bit, B_bit, metric_id(metric), eq_n, search_round
+    d.sos, d.init_layerwise, d.reserved = int(sos), int(init_layerwise), int(reserved)
+    if bd is not None:
+        bd.n_V_A, bd.n_H_A, bd.n_V_B, bd.n_H_B = (int(n) for n in blocks)
+    return (bd if bd is not None else d), d
+
+
+def matmul_blocks_quant_forward(*, A, B, A_interval, B_interval, split, A_bit, B_bit, blocks, sos=False):
+    """quant_forward of a calibrated MatMul with row / column sub-blocks (p4v_matmul_blocks_quant_forward): intervals
+    [heads][n_V][n_H] per operand (the split-of-softmax A: its scalar interval and the split), `blocks` = (n_V_A, n_H_A, n_V_B,
+    n_H_B).  An int8 MFMA GEMM per K segment, one fp32 rescale per segment."""
+    lib = _lib.load()
+    dev = device_of(A, B)
+    A, B = to_dev(A, dev), to_dev(B, dev)
+    bd, d = _matmul_desc(A, B, A_bit, B_bit, "L2_norm", 1, 1, sos, 0, 4, blocks, wrap=True)
+    b, H, M, _ = A.shape
+    need = _need(lib.p4v_matmul_blocks_workspace_bytes, bd, "p4v_matmul_blocks_workspace_bytes")
+    ws = workspace(dev, need)
+    A_iv = to_dev(A_interval, dev).reshape(-1).contiguous()
+    B_iv = to_dev(B_interval, dev).reshape(-1).contiguous()
+    if A_iv.numel() != (1 if sos else H * bd.n_V_A * bd.n_H_A) or B_iv.numel() != H * bd.n_V_B * bd.n_H_B:
+        raise ValueError("matmul_blocks_quant_forward: interval tensors must hold [heads][n_V][n_H] values")
+    sp = to_dev(split, dev).reshape(-1).contiguous() if sos else None
+    out = torch.empty(b, H, M, d.N, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.p4v_matmul_blocks_quant_forward(C.byref(bd), ptr(A), ptr(B), ptr(A_iv), ptr(B_iv), ptr(sp), ptr(out),
+                                                 ptr(ws), ws.numel(), stream_ptr(dev))
+    _lib.check(rc, "p4v_matmul_blocks_quant_forward")
+    return out
+
+
 def matmul_job(*, A, B, out, grad, A_bit, B_bit, metric, eq_alpha, eq_beta, eq_n, search_round,
-               sos=False, init_layerwise=False, want_scores=False, prune=True):
+               sos=False, init_layerwise=False, want_scores=False, prune=True, blocks=None):
     lib = _lib.load()
     dev = device_of(A, B)
     A, B, out, grad = (to_dev(t, dev) for t in (A, B, out, grad))
@@ -273,6 +319,20 @@ def matmul_job(*, A, B, out, grad, A_bit, B_bit, metric, eq_alpha, eq_beta, eq_n
     grad = grad.contiguous() if grad is not None else None
     b, H, M, K = A.shape
     N = B.shape[3]
+    if has_blocks(blocks):
+        # row / column sub-blocks: p4v_matmul_blocks_calibrate; intervals [heads][n_V][n_H], one score table per block step
+        bd, _ = _matmul_desc(A, B, A_bit, B_bit, metric, eq_n, search_round, sos, init_layerwise, 0, blocks)
+        need = _need(lib.p4v_matmul_blocks_workspace_bytes, bd, "p4v_matmul_blocks_workspace_bytes")
+        mult = candidate_multipliers(eq_alpha, eq_beta, eq_n, dev)
+        nA, nB = (1 if sos else H * bd.n_V_A * bd.n_H_A), H * bd.n_V_B * bd.n_H_B
+        steps = (1 if sos else bd.n_V_A * bd.n_H_A) + bd.n_V_B * bd.n_H_B
+        A_iv = torch.empty(nA, dtype=torch.float32, device=dev)
+        B_iv = torch.empty(nB, dtype=torch.float32, device=dev)
+        split = torch.empty(1, dtype=torch.float32, device=dev) if sos else None
+        scores = torch.zeros(search_round, steps, eq_n, H, dtype=torch.float32, device=dev) if want_scores else None
+        best = torch.zeros(search_round, steps, H, dtype=torch.int32, device=dev) if want_scores else None
+        return Job(_lib.JOB_MATMUL_BLOCKS, "p4v_matmul_blocks_calibrate", bd, (A, B, out, grad), mult, (A_iv, B_iv, split), need,
+                   dev, scores, best)
     d = _lib.MatMulDesc()
     d.batch, d.heads, d.M, d.K, d.N = b, H, M, K, N
     for i in range(4):
@@ -390,32 +450,53 @@ class LinearStepper(_Stepper):
 
 
 class MatMulStepper(_Stepper):
-    def __init__(self, *, A, B, out, grad, A_bit, B_bit, metric, eq_n, sos=False, init_layerwise=False):
+    def __init__(self, *, A, B, out, grad, A_bit, B_bit, metric, eq_n, sos=False, init_layerwise=False, blocks=None):
         self.lib = _lib.load()
         self.dev = dev = device_of(A, B)
         self.A, self.B = to_dev(A, dev), to_dev(B, dev)
         self.out = to_dev(out, dev).contiguous() if out is not None else None
         self.grad = to_dev(grad, dev).contiguous() if grad is not None else None
-        b, H, M, K = self.A.shape
-        self.H, self.sos = H, bool(sos)
-        d = self.d = _lib.MatMulDesc()
-        d.batch, d.heads, d.M, d.K, d.N = b, H, M, K, self.B.shape[3]
-        for i in range(4):
-            d.a_stride[i] = self.A.stride(i)
-            d.b_stride[i] = self.B.stride(i)
-        d.A_bit, d.B_bit, d.metric, d.eq_n, d.search_round = A_bit, B_bit, metric_id(metric), eq_n, 1
-        d.sos, d.init_layerwise, d.reserved = int(sos), int(init_layerwise), 0
-        need = self.lib.p4v_matmul_workspace_bytes(C.byref(d))
-        if need == 0:
-            _lib.check(-2, "p4v_matmul_workspace_bytes")
+        self.H, self.sos = self.A.shape[1], bool(sos)
+        # `d`: the p4v_matmul_desc of the head-wise entry points; `bd`: with row / column sub-blocks, the descriptor around it
+        self.blocks = tuple(int(n) for n in blocks) if has_blocks(blocks) else None
+        desc, self.d = _matmul_desc(self.A, self.B, A_bit, B_bit, metric, eq_n, 1, sos, init_layerwise, 0, self.blocks)
+        self.bd = desc if self.blocks else None
+        if self.blocks:
+            need = _need(self.lib.p4v_matmul_blocks_workspace_bytes, desc, "p4v_matmul_blocks_workspace_bytes")
+        else:
+            need = self.lib.p4v_matmul_workspace_bytes(C.byref(self.d))
+            if need == 0:
+                _lib.check(-2, "p4v_matmul_workspace_bytes")
         self.ws = workspace(dev, need)
 
+    def _call_blocks(self, name, lead, *args):
+        with torch.cuda.device(self.dev):
+            rc = getattr(self.lib, name)(C.byref(self.bd), *lead, *[ptr(a) for a in args], ptr(self.ws), self.ws.numel(),
+                                         stream_ptr(self.dev))
+        _lib.check(rc, name)
+
     def init_intervals(self):
-        """(A_interval [heads] -- None for the split-of-softmax class, whose split search sets it -- , B_interval [heads])"""
-        A_iv = torch.empty(self.H, dtype=torch.float32, device=self.dev)
-        B_iv = torch.empty(self.H, dtype=torch.float32, device=self.dev)
-        self._call("p4v_amax_init_matmul", self.A, self.B, A_iv, B_iv)
+        """(A_interval [heads] -- None for the split-of-softmax class, whose split search sets it -- , B_interval [heads]);
+        with row / column sub-blocks [heads * n_V * n_H] each."""
+        nA, nB = (self.H * self.blocks[0] * self.blocks[1], self.H * self.blocks[2] * self.blocks[3]) if self.blocks else (self.H, self.H)
+        A_iv = torch.empty(nA, dtype=torch.float32, device=self.dev)
+        B_iv = torch.empty(nB, dtype=torch.float32, device=self.dev)
+        if self.blocks:
+            self._call_blocks("p4v_amax_init_matmul_blocks", (), self.A, self.B, A_iv, B_iv)
+        else:
+            self._call("p4v_amax_init_matmul", self.A, self.B, A_iv, B_iv)
         return (None if self.sos else A_iv), B_iv
+
+    def search_block(self, operand, v, h, cands, A_interval, B_interval, split=None, want_scores=False):
+        """ONE block step (p4v_matmul_blocks_search): `operand` "A" / "B", block (v, h), `cands` [eq_n+1][heads] that block's
+        candidates per head, both interval tensors [heads * n_V * n_H] as they enter the step.  Returns (the searched tensor
+        with block (v, h) of every head replaced, scores [eq_n][heads] | None, best [heads] | None)."""
+        A_iv, B_iv = _flat(A_interval, self.dev).clone(), _flat(B_interval, self.dev).clone()
+        scores, best = self._tables(want_scores, self.H)
+        self._call_blocks("p4v_matmul_blocks_search", (0 if operand == "A" else 1, int(v), int(h)), self.A, self.B, self.out,
+                          self.grad, _flat(cands, self.dev, self.d.eq_n + 1), A_iv, B_iv,
+                          (_flat(split, self.dev) if self.sos else None), scores, best)
+        return (A_iv if operand == "A" else B_iv), scores, best
 
     def search_A(self, A_cands, A_interval, B_interval, want_scores=False):
         A_iv = _flat(A_interval, self.dev).clone()

@@ -2,7 +2,8 @@
 
 Hot classes (reference matmul.py:390-644): PTQSLBatchingQuantMatMul (head-wise intervals) and
 SoSPTQSLBatchingQuantMatMul (split-of-softmax twin on A).  ``calibration_step2()`` calls
-``p4v_matmul_calibrate`` (include/ptq4vit_hip.h).
+``p4v_matmul_calibrate`` (include/ptq4vit_hip.h), with row / column sub-blocks (n_V, n_H > 1)
+``p4v_matmul_blocks_calibrate``.
 """
 import torch
 import torch.nn.functional as F
@@ -100,22 +101,33 @@ class PTQSLQuantMatMul(MinMaxQuantMatMul):
 
     int8_forward = True   # GPU tensors, no autograd: quant_forward runs as ONE int8 MFMA GEMM (p4v_matmul_quant_forward)
 
+    @property
+    def _blocks(self):
+        """(n_V_A, n_H_A, n_V_B, n_H_B): the row / column sub-blocks of the two operands."""
+        return (self.n_V_A, self.n_H_A, self.n_V_B, self.n_H_B)
+
     def quant_forward(self, A, B):
         """Reference matmul.py:140-145 (SoS operand: matmul.py:595-598).  On the GPU the product is taken on the grid
-        indices (head-wise intervals; the split-of-softmax operand as its two range planes) and rescaled in the
-        epilogue; the fake-quant fp32 formulation is kept for CPU tensors, autograd and block layouts other than
-        head-wise."""
+        indices and rescaled in fp32 -- once for head-wise intervals (the split-of-softmax operand as its two range planes),
+        once per K segment with row / column sub-blocks (p4v_matmul_blocks_quant_forward); the fake-quant fp32 formulation is
+        kept for CPU tensors and autograd."""
         assert self.calibrated is not None, f"You should run calibrate_forward before run quant_forward for {self}"
         if self.crb_rows_A is None or self.crb_rows_B is None:
             # intervals loaded from elsewhere (shard.exchange_intervals on a rank that did not search this module, or a
             # checkpoint): the block geometry is a function of the operand shapes only (matmul.py:109-122)
             self._get_padding_parameters(A, B)
-        # whole heads share a scale (row / column sub-blocks do not): group intervals are handed over head by head
-        by_head = (self.n_V_A, self.n_H_A, self.n_V_B, self.n_H_B) == (1, 1, 1, 1) and A.dim() == 4
-        if (self.int8_forward and A.is_cuda and by_head and 2 <= self.A_bit <= 8 and 2 <= self.B_bit <= 8
+        if (self.int8_forward and A.is_cuda and A.dim() == 4 and 2 <= self.A_bit <= 8 and 2 <= self.B_bit <= 8
                 and not (torch.is_grad_enabled() and (A.requires_grad or B.requires_grad))):
-            # inside the envelope of p4v_matmul_quant_forward the engine's errors propagate (no silent fallback)
+            # inside the envelope of the int8 entry points the engine's errors propagate (no silent fallback); group
+            # intervals are handed over head by head
             H = A.shape[1]
+            if engine.has_blocks(self._blocks):
+                A_iv = self.A_interval if self._sos else self._per_head(self.A_interval, H, self.crb_groups_A, self.n_V_A * self.n_H_A)
+                return engine.matmul_blocks_quant_forward(
+                    A=A, B=B, A_interval=A_iv,
+                    B_interval=self._per_head(self.B_interval, H, self.crb_groups_B, self.n_V_B * self.n_H_B),
+                    split=self.split if self._sos else None, A_bit=self.A_bit, B_bit=self.B_bit, sos=self._sos,
+                    blocks=self._blocks)
             A_iv = self.A_interval if self._sos else self._per_head(self.A_interval, H, self.crb_groups_A)
             return engine.matmul_quant_forward(A=A, B=B, A_interval=A_iv,
                                                B_interval=self._per_head(self.B_interval, H, self.crb_groups_B),
@@ -126,40 +138,40 @@ class PTQSLQuantMatMul(MinMaxQuantMatMul):
     # ---- the GPU search --------------------------------------------------------------------------
     def _search_job(self, A, B, raw_out, raw_grad):
         """The prepared p4v_matmul_calibrate call (engine.Job): replaces matmul.py:565-576 / :633-644.  The engine searches
-        one interval per head (the Batching classes force n_G = heads, matmul.py:411-417) with n_V = n_H = 1."""
+        one interval per head (the Batching classes force n_G = heads, matmul.py:411-417) and row / column block
+        (p4v_matmul_blocks_calibrate when some n_V / n_H > 1)."""
         if self.metric == "hessian":
             assert raw_grad is not None, "No raw_grad in PTQSLBatchingQuantMatMul!"
-        if (self.n_V_A, self.n_H_A, self.n_V_B, self.n_H_B) != (1, 1, 1, 1):
-            raise NotImplementedError("ptq4vit_amd: MatMul row/column sub-blocks (n_V, n_H > 1) are not implemented on the GPU")
         H = A.shape[1]
         self.n_G_A, self.n_G_B = H, H   # head-wise (matmul.py:415-416; also overrides the SoS constructor's n_G_A = 1)
         self._get_padding_parameters(A, B)
         return engine.matmul_job(
             A=A, B=B, out=raw_out, grad=raw_grad if self.metric == "hessian" else None, A_bit=self.A_bit,
             B_bit=self.B_bit, metric=self.metric, eq_alpha=self.eq_alpha, eq_beta=self.eq_beta, eq_n=self.eq_n,
-            search_round=self.search_round, sos=self._sos, init_layerwise=self.init_layerwise)
+            search_round=self.search_round, sos=self._sos, init_layerwise=self.init_layerwise, blocks=self._blocks)
 
     def _search_install(self, job):
         A_iv, B_iv, split = job.outputs
-        H = B_iv.numel()
-        self.B_interval = B_iv.view(1, H, 1, 1, 1, 1, 1)
+        H = B_iv.numel() // (self.n_V_B * self.n_H_B)
+        self.B_interval = B_iv.view(1, H, 1, self.n_V_B, 1, self.n_H_B, 1)
         if self._sos:
             self.split = split.reshape(())
             self.A_interval = A_iv.reshape(())
         else:
-            self.A_interval = A_iv.view(1, H, 1, 1, 1, 1, 1)
+            self.A_interval = A_iv.view(1, H, 1, self.n_V_A, 1, self.n_H_A, 1)
 
     def _search_on_gpu(self, A, B, raw_out, raw_grad):
         self._search_install(engine.run_job(self._search_job(A, B, raw_out, raw_grad)))
 
     @staticmethod
-    def _per_head(interval, H, crb_groups):
-        """(1, n_G, 1, 1, 1, 1, 1) group intervals -> one value per head (head h belongs to group h // crb_groups)."""
-        iv = torch.as_tensor(interval).reshape(-1)
-        if iv.numel() == H:
-            return iv
+    def _per_head(interval, H, crb_groups, blocks=1):
+        """(1, n_G, 1, n_V, 1, n_H, 1) group intervals -> the `blocks` = n_V * n_H values of every head, flat [H * blocks]
+        (head h belongs to group h // crb_groups)."""
+        iv = torch.as_tensor(interval).reshape(-1, blocks)
+        if iv.shape[0] == H:
+            return iv.reshape(-1)
         idx = torch.arange(H, device=iv.device) // int(crb_groups)
-        return iv[idx]
+        return iv[idx].reshape(-1)
 
     def _search_grouped(self, A, B, raw_out, raw_grad):
         """Reference matmul.py:165-282 (SoS: :305-388) with the CONFIGURED group counts (the batching classes force
@@ -167,12 +179,12 @@ class PTQSLQuantMatMul(MinMaxQuantMatMul):
         scores (matmul.py:199 / 234; zero padding heads only rescale the last group).  Every pass is one GPU sweep with
         per-head candidate tables (p4v_matmul_search_A / _B / p4v_sos_search_split); the per-head score table is folded
         to groups and the first-maximum / NaN-is-maximum selection taken on the device."""
-        if (self.n_V_A, self.n_H_A, self.n_V_B, self.n_H_B) != (1, 1, 1, 1):
-            raise NotImplementedError("ptq4vit_amd: MatMul row/column sub-blocks (n_V, n_H > 1) are not implemented on the GPU")
         self._get_padding_parameters(A, B)
         st = engine.MatMulStepper(A=A, B=B, out=raw_out, grad=raw_grad if self.metric == "hessian" else None,
                                   A_bit=self.A_bit, B_bit=self.B_bit, metric=self.metric, eq_n=self.eq_n, sos=self._sos,
-                                  init_layerwise=self.init_layerwise)
+                                  init_layerwise=self.init_layerwise, blocks=self._blocks)
+        if st.blocks:
+            return self._search_grouped_blocks(st)
         H, dev = st.H, st.dev
         mult = torch.tensor([self.eq_alpha + i * (self.eq_beta - self.eq_alpha) / self.eq_n for i in range(self.eq_n + 1)],
                             dtype=torch.float32, device=dev)
@@ -211,6 +223,56 @@ class PTQSLQuantMatMul(MinMaxQuantMatMul):
             self.A_interval = A_cur.reshape(())
         else:
             self.A_interval = side["A"]["iv"].view(1, self.n_G_A, 1, 1, 1, 1, 1)
+
+    def _search_grouped_blocks(self, st):
+        """_search_grouped with row / column sub-blocks (matmul.py:187-208 / 220-241): the greedy pass over the blocks
+        (v, h) in product order, ONE GPU sweep per block step (p4v_matmul_blocks_search) on per-head candidates; the
+        per-head score table of the step is folded to groups on the device and the group's block interval written back
+        for all its heads."""
+        H, dev = st.H, st.dev
+        mult = torch.tensor([self.eq_alpha + i * (self.eq_beta - self.eq_alpha) / self.eq_n for i in range(self.eq_n + 1)],
+                            dtype=torch.float32, device=dev)
+        A_h, B_h = st.init_intervals()                      # amax / (qmax - 0.5) per head and block (or layer-wise)
+        side = {}
+        for s, iv_h, nG, crb in (("A", A_h, self.n_G_A, self.crb_groups_A), ("B", B_h, self.n_G_B, self.crb_groups_B)):
+            nV, nH = getattr(self, f"n_V_{s}"), getattr(self, f"n_H_{s}")
+            idx = torch.arange(H, device=dev) // int(crb)
+            if iv_h is None:        # split-of-softmax A: no interval tensor of its own
+                continue
+            # the division by (qmax - 0.5) is monotone: the group's min-max interval is the largest of its heads'
+            iv_g = torch.zeros(nG, nV * nH, dtype=torch.float32, device=dev).index_reduce_(
+                0, idx, iv_h.view(H, nV * nH), "amax", include_self=False)
+            side[s] = dict(idx=idx, iv=iv_g, cands=mult[:, None, None] * iv_g[None], nG=nG, nV=nV, nH=nH)
+
+        def per_head(s):
+            d = side[s]
+            return d["iv"][d["idx"]].reshape(-1)
+
+        def search(s, other_iv, split=None):
+            d = side[s]
+            for v in range(d["nV"]):
+                for h in range(d["nH"]):
+                    k = v * d["nH"] + h
+                    A_cur, B_cur = (per_head("A"), other_iv) if s == "A" else (other_iv, per_head("B"))
+                    _, scores, _ = st.search_block(s, v, h, d["cands"][:, d["idx"], k], A_cur, B_cur, split=split, want_scores=True)
+                    grp = torch.zeros(self.eq_n, d["nG"], dtype=torch.float32, device=dev).index_add_(1, d["idx"], scores[: self.eq_n])
+                    best = torch.argmax(grp, dim=0)
+                    d["iv"][:, k] = torch.gather(d["cands"][:, :, k], 0, best[None, :]).reshape(-1)
+
+        split = A_cur = None
+        for _ in range(self.search_round):
+            if self._sos:
+                split, A_cur, _, _ = st.search_split()
+            else:
+                search("A", per_head("B"))
+                A_cur = per_head("A")
+            search("B", A_cur, split=split)
+        self.B_interval = side["B"]["iv"].view(1, self.n_G_B, 1, self.n_V_B, 1, self.n_H_B, 1)
+        if self._sos:
+            self.split = split.reshape(())
+            self.A_interval = A_cur.reshape(())
+        else:
+            self.A_interval = side["A"]["iv"].view(1, self.n_G_A, 1, self.n_V_A, 1, self.n_H_A, 1)
 
     def calibration_step2(self, A, B):
         H = A.shape[1]
@@ -276,30 +338,44 @@ class PTQSLBatchingQuantMatMul(PTQSLQuantMatMul):
     # p4v_matmul_search_A / _B, p4v_sos_search_split).  calibration_step2 runs the same kernels fused in one call. ----
     def _stepper(self):
         A, B = self.raw_input
-        if (self.n_V_A, self.n_H_A, self.n_V_B, self.n_H_B) != (1, 1, 1, 1):
-            raise NotImplementedError("ptq4vit_amd: MatMul row/column sub-blocks (n_V, n_H > 1) are not implemented on the GPU")
         self._get_padding_parameters(A, B)
         return engine.MatMulStepper(A=A, B=B, out=self.raw_out, grad=self.raw_grad if self.metric == "hessian" else None,
                                     A_bit=self.A_bit, B_bit=self.B_bit, metric=self.metric, eq_n=self.eq_n,
-                                    sos=self._sos, init_layerwise=self.init_layerwise)
+                                    sos=self._sos, init_layerwise=self.init_layerwise, blocks=self._blocks)
 
     def _initialize_intervals(self):
-        """Reference matmul.py:419-440: head-wise min-max intervals (1, heads, 1, 1, 1, 1, 1)."""
+        """Reference matmul.py:419-440: min-max intervals per head and row / column block (1, heads, 1, n_V, 1, n_H, 1)."""
         st = self._stepper()
         A_iv, B_iv = st.init_intervals()
-        self.B_interval = B_iv.view(1, st.H, 1, 1, 1, 1, 1)
+        self.B_interval = B_iv.view(1, st.H, 1, self.n_V_B, 1, self.n_H_B, 1)
         if A_iv is not None:
-            self.A_interval = A_iv.view(1, st.H, 1, 1, 1, 1, 1)
+            self.A_interval = A_iv.view(1, st.H, 1, self.n_V_A, 1, self.n_H_A, 1)
+
+    def _search_blocks(self, st, s, candidates):
+        """The greedy pass over the blocks of operand `s` (matmul.py:489-521 / 530-562), one GPU sweep per block step."""
+        nV, nH = getattr(self, f"n_V_{s}"), getattr(self, f"n_H_{s}")
+        cands = engine.to_dev(candidates, st.dev).reshape(self.eq_n + 1, st.H, nV, nH)
+        iv = {"A": self.A_interval, "B": self.B_interval}
+        for v in range(nV):
+            for h in range(nH):
+                iv[s], _, _ = st.search_block(s, v, h, cands[:, :, v, h], iv["A"], iv["B"], split=self.split if self._sos else None)
+        return iv[s].view(1, st.H, 1, nV, 1, nH, 1)
 
     def _search_best_A_interval(self, A_interval_candidates):
-        """Reference matmul.py:483-522; candidates (eq_n+1, 1, heads, 1, 1, 1, 1, 1)."""
+        """Reference matmul.py:483-522; candidates (eq_n+1, 1, heads, 1, n_V, 1, n_H, 1)."""
         st = self._stepper()
+        if st.blocks:
+            self.A_interval = self._search_blocks(st, "A", A_interval_candidates)
+            return
         A_iv, _, _ = st.search_A(A_interval_candidates, self.A_interval, self.B_interval)
         self.A_interval = A_iv.view(1, st.H, 1, 1, 1, 1, 1)
 
     def _search_best_B_interval(self, B_interval_candidates):
         """Reference matmul.py:524-563 (the split-of-softmax class inherits it with its own quant_input_A)."""
         st = self._stepper()
+        if st.blocks:
+            self.B_interval = self._search_blocks(st, "B", B_interval_candidates)
+            return
         B_iv, _, _ = st.search_B(B_interval_candidates, self.A_interval, self.B_interval,
                                  split=self.split if self._sos else None)
         self.B_interval = B_iv.view(1, st.H, 1, 1, 1, 1, 1)

@@ -102,10 +102,13 @@ _HDR = 9 * len(INTERVAL_ATTRS)        # per module: for each attribute (1 + ndim
 def _slot_capacity(module):
     """Interval scalars a module can produce at most -- from attributes EVERY rank knows before any search (no communication):
     Linear n_V * n_H + n_a, Conv2d one per output channel + 1, MatMul one per head and operand + the split (the head count is
-    only known to the owner, after its capture: 128 heads unless the module carries `_p4v_interval_slots`; exceeding a slot raises)."""
+    only known to the owner, after its capture: 128 heads unless the module carries `_p4v_interval_slots`; exceeding a slot raises).
+    A MatMul with row / column sub-blocks holds n_V * n_H intervals per head and operand (the four counts are constructor
+    arguments, known to every rank)."""
     w = getattr(module, "weight", None)
     if w is None:
-        return int(getattr(module, "_p4v_interval_slots", 2 * 128 + 2))
+        blocks = lambda s: int(getattr(module, f"n_V_{s}", 1)) * int(getattr(module, f"n_H_{s}", 1))   # noqa: E731
+        return int(getattr(module, "_p4v_interval_slots", 128 * blocks("A") + 128 * blocks("B") + 2))
     if w.dim() == 4:
         return int(w.shape[0]) + 2
     return int(getattr(module, "n_V", 1)) * int(getattr(module, "n_H", 1)) + int(getattr(module, "n_a", 1)) + 2
