@@ -72,7 +72,7 @@ typedef struct p4v_linear_desc {
     int32_t in_features;  /* K */
     int32_t out_features; /* N */
     int32_t n_V, n_H, n_a;
-    int32_t w_bit, a_bit;
+    int32_t w_bit, a_bit; /* 2..8 each, independently; anything else: P4V_ERR_UNSUPPORTED before any launch */
     int32_t metric;       /* enum p4v_metric */
     int32_t eq_n;         /* searched candidates 0..eq_n-1 of an (eq_n+1)-entry table */
     int32_t search_round;
@@ -110,7 +110,7 @@ typedef struct p4v_matmul_desc {
     int32_t M, K, N;            /* A: (batch,heads,M,K)  B: (batch,heads,K,N) */
     int64_t a_stride[4];        /* element strides of A for (batch, head, m, k) */
     int64_t b_stride[4];        /* element strides of B for (batch, head, k, n) */
-    int32_t A_bit, B_bit;
+    int32_t A_bit, B_bit;       /* 2..8 each, independently; anything else: P4V_ERR_UNSUPPORTED before any launch */
     int32_t metric;
     int32_t eq_n;
     int32_t search_round;
@@ -142,7 +142,7 @@ int p4v_matmul_calibrate(const p4v_matmul_desc* desc, const float* d_A, const fl
  * `p4v_matmul_desc` keeps its layout; this descriptor wraps it.
  * ---------------------------------------------------------------------------------------- */
 typedef struct p4v_matmul_blocks_desc {
-    p4v_matmul_desc mm;
+    p4v_matmul_desc mm;         /* A_bit, B_bit 2..8 as above */
     int32_t n_V_A, n_H_A, n_V_B, n_H_B;
 } p4v_matmul_blocks_desc;
 
@@ -191,7 +191,8 @@ typedef struct p4v_conv_desc {
     int32_t batch, in_channels, height, width;
     int32_t out_channels, kernel_h, kernel_w;
     int32_t stride_h, stride_w, pad_h, pad_w, dil_h, dil_w;
-    int32_t w_bit, a_bit;       /* a_bit >= 32 disables input quantisation (conv.py:544,600) */
+    int32_t w_bit, a_bit;       /* w_bit 2..8; a_bit >= 2, and a_bit >= 32 disables input quantisation (conv.py:544,600);
+                                   anything else: P4V_ERR_UNSUPPORTED before any launch */
     int32_t metric;
     int32_t eq_n;
     int32_t search_round;

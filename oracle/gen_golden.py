@@ -8,7 +8,7 @@ intervals, expected score tables).  The reference does not exist on the GPU
 box, so this script is never run there; the committed ``.npz`` files travel.
 
     python oracle/gen_golden.py            # rewrites tests/golden/*.npz
-    python oracle/gen_golden.py convgeo    # only the convgeo_* files (likewise ptqslconv, minivit, ...)
+    python oracle/gen_golden.py convgeo    # only the convgeo_* files (likewise ptqslconv, minivit, mixbit, ...)
 """
 import json
 import os
@@ -258,6 +258,66 @@ def gen_ptqsl_convs():
                    metric="cosine", eq_alpha=0.5, eq_beta=1.2, eq_n=100, search_round=1)
 
 
+# --------------------------------------------------------------------------- #
+# mixed and low bit widths (prefix `mixbit_`: none of the `linear_` / `matmul_` / `conv_` / `mmblk_` parametrisations loads them)
+# --------------------------------------------------------------------------- #
+MIXBIT_GAP = 2.5e-4      # > helpers.SCORE_RTOL: a right kernel cannot flip a selection of these fixtures
+
+
+def min_table_gap(tables):
+    """Smallest relative gap between the maximum and the runner-up over every column of every score table."""
+    worst = np.inf
+    for t in tables:
+        t = np.asarray(t, dtype=np.float64)
+        t = t.reshape(t.shape[0], -1)
+        top = np.sort(t, axis=0)[-2:]
+        worst = min(worst, float(((top[1] - top[0]) / np.maximum(np.abs(top[1]), 1e-300)).min()))
+    return worst
+
+
+_MIX_HS = dict(metric="hessian", eq_alpha=0.01, eq_beta=1.2, eq_n=100, search_round=2)
+_MIX_L2 = dict(_MIX_HS, metric="L2_norm")
+_MIX_LIN = dict(shape_x=(3, 17, 96), oc=48)
+_MIX_MM = dict(b=2, H=3, d1=19, d2=32, d3=19)
+_MIX_SOS = dict(b=2, H=3, d1=19, d2=19, d3=32, sos=True)
+_MIX_CONV = dict(b=3, ic=3, hw=24, oc=16, k=4, stride=4)
+# (generator, name, arguments).  The seeds are the first from 100 upwards whose reference run has every column of every score
+# table decided by at least MIXBIT_GAP (gen_mixed_bits asserts it, tests/test_oracle_mixbit.py again).  No cosine case: a cosine
+# score is 1 - O(1e-5), so neighbouring candidates are within 1e-6 relative of each other on every seed (40 tried for a W8A6
+# n_V = 3 Linear and for an A4B8 q.k^T); cosine at mixed widths -- Linear, q.k^T and split-of-softmax MatMul -- is tested against
+# the numpy oracle on the GPU instead (tests/test_hip_mixbit.py, routes cos-*).
+MIXBIT_CASES = [
+    ("gen_linear", "mixbit_linear_w4a8_hessian_v3", dict(_MIX_LIN, n_V=3, w_bit=4, a_bit=8, seed=100, **_MIX_HS)),
+    ("gen_linear", "mixbit_linear_w8a4_l2_v3", dict(_MIX_LIN, n_V=3, w_bit=8, a_bit=4, seed=103, **_MIX_L2)),
+    ("gen_linear", "mixbit_linear_w2a8_hessian", dict(_MIX_LIN, n_V=1, w_bit=2, a_bit=8, seed=100, **_MIX_HS)),
+    ("gen_linear", "mixbit_postgelu_w8a4_hessian", dict(_MIX_LIN, postgelu=True, n_V=1, w_bit=8, a_bit=4, seed=100, **_MIX_HS)),
+    ("gen_linear", "mixbit_postgelu_w4a8_hessian", dict(_MIX_LIN, postgelu=True, n_V=1, w_bit=4, a_bit=8, seed=100, **_MIX_HS)),
+    ("gen_matmul", "mixbit_matmul_qk_a8b4_hessian", dict(_MIX_MM, A_bit=8, B_bit=4, seed=100, **_MIX_HS)),
+    ("gen_matmul", "mixbit_matmul_sos_a4b8_hessian", dict(_MIX_SOS, A_bit=4, B_bit=8, seed=100, **_MIX_HS)),
+    ("gen_matmul", "mixbit_matmul_sos_a2b8_l2", dict(_MIX_SOS, A_bit=2, B_bit=8, seed=103, **_MIX_L2)),
+    ("gen_conv", "mixbit_conv_cw_w4a8_hessian", dict(_MIX_CONV, w_bit=4, a_bit=8, seed=101, **_MIX_HS)),
+    ("gen_conv", "mixbit_conv_cw_w8a4_hessian", dict(_MIX_CONV, w_bit=8, a_bit=4, seed=102, **_MIX_HS)),
+]
+# the sub-block MatMul cases (tools/gen_golden_mmblk.py writes them)
+MIXBIT_MMBLK_CASES = [
+    ("gen_matmul", "mixbit_mmblk_qk_a8b4_vA2hA2_vB2hB2",
+     dict(_MIX_MM, A_bit=8, B_bit=4, seed=118, n_V_A=2, n_H_A=2, n_V_B=2, n_H_B=2, **_MIX_HS)),
+    ("gen_matmul", "mixbit_mmblk_sos_a4b8_vB2hB2", dict(_MIX_SOS, A_bit=4, B_bit=8, seed=125, n_V_B=2, n_H_B=2, **_MIX_HS)),
+]
+
+
+def gen_mixed_bits(cases=None):
+    """Layers whose two operands have DIFFERENT widths, or widths below 4: Linear and post-GELU Linear (w_bit != a_bit), q.k^T and
+    split-of-softmax MatMul (A_bit != B_bit), channel-wise Conv2d with a quantised input.  Every fixture must leave no selection
+    to rounding: each column of each table the reference fed to argmax has its runner-up at least MIXBIT_GAP below the maximum."""
+    for gen, name, kw in (MIXBIT_CASES if cases is None else cases):
+        globals()[gen](name, **kw)
+        z = np.load(os.path.join(OUT, name + ".npz"), allow_pickle=False)
+        gap = min_table_gap([z[f"scores_{i:02d}"] for i in range(int(z["n_scores"]))])
+        assert gap >= MIXBIT_GAP, f"{name}: a score column is decided by {gap:.2e} < {MIXBIT_GAP}: pick another seed"
+        print(f"  {name}: smallest decision gap {gap:.2e}, {os.path.getsize(os.path.join(OUT, name + '.npz'))} bytes")
+
+
 def main(only=None):
     _install_shims()
     os.chdir(REF)
@@ -267,6 +327,8 @@ def main(only=None):
         return gen_ptqsl_convs()
     if only == "convgeo":
         return gen_conv_geometries()
+    if only == "mixbit":
+        return gen_mixed_bits()
     # ---- Linear (quant_layers/linear.py:349-642) ---------------------------------
     gen_linear("linear_qkv_hessian_w8a8", shape_x=(4, 13, 48), oc=36, n_V=3, w_bit=8, a_bit=8, **PTQ4VIT)
     gen_linear("linear_hessian_w6a6_tinygrad", shape_x=(4, 13, 48), oc=24, n_V=1, w_bit=6, a_bit=6,
@@ -305,7 +367,7 @@ def main(only=None):
     gen_conv("conv_channelwise_hessian_a8_overlap", b=3, ic=3, hw=20, oc=8, k=5, stride=3, w_bit=8, a_bit=8, seed=34,
              metric="hessian", eq_alpha=0.3, eq_beta=1.2, eq_n=30, search_round=2)
     gen_conv_geometries()
-
+    gen_mixed_bits()
 
 
 

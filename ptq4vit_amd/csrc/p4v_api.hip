@@ -2556,7 +2556,7 @@ int matmul_impl(const p4v_matmul_desc* d, const float* A, const float* B, const 
     // fwd_out != nullptr: quant_forward (matmul.py:140-145; sos: matmul.py:595-598) -- intervals / split are INPUTS
     const int H = d->heads, Z = d->batch * d->heads, M = d->M, K = d->K, N = d->N;
     if (Z <= 0 || M <= 0 || K <= 0 || N <= 0 || d->eq_n <= 0) return fail(P4V_ERR_INVALID, "matmul: non-positive dimension");
-    if (d->A_bit > 8 || d->B_bit > 8) return fail(P4V_ERR_UNSUPPORTED, "matmul: bit widths <= 8 supported");
+    if (d->A_bit > 8 || d->B_bit > 8 || d->A_bit < 2 || d->B_bit < 2) return fail(P4V_ERR_UNSUPPORTED, "matmul: bit widths 2..8 supported");
     const int Aq = 1 << (d->A_bit - 1), Bq = 1 << (d->B_bit - 1);
     int epi, wt_mode;
     metric_epi(d->metric, &epi, &wt_mode);
@@ -2908,7 +2908,8 @@ int conv_impl(const p4v_conv_desc* d, const float* W, const float* bias, const f
     const int num_h = H + 2 * d->pad_h - d->dil_h * (kh - 1) - 1, num_w = Wd + 2 * d->pad_w - d->dil_w * (kw - 1) - 1;
     if (b <= 0 || ic <= 0 || oc <= 0 || H <= 0 || Wd <= 0 || num_h < 0 || num_w < 0 || d->eq_n <= 0) return fail(P4V_ERR_INVALID, "conv: bad geometry");
     const int fh = num_h / d->stride_h + 1, fw = num_w / d->stride_w + 1;
-    if (d->w_bit > 8) return fail(P4V_ERR_UNSUPPORTED, "conv: w_bit <= 8 supported");
+    if (d->w_bit > 8 || d->w_bit < 2) return fail(P4V_ERR_UNSUPPORTED, "conv: w_bit 2..8 supported");
+    if (d->a_bit < 2) return fail(P4V_ERR_UNSUPPORTED, "conv: a_bit >= 2 supported (>= 32: unquantised input)");
     const int L = fh * fw, K = ic * kh * kw, M = b * L;
     const int wq = 1 << (d->w_bit - 1);
     const bool aquant = d->a_bit < 32;

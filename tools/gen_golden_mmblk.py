@@ -15,6 +15,9 @@ What the cases cover (b, H, d1, d2, d3 = batch, heads, M, K, N):
   mmblk_sv_hessian_m133_k133_vA2hA2_vB2hB2       rows cross a 128 tile, segments of 67 / 66 = two k-tiles each (1 round)
   mmblk_ptqsl_qk_hessian_g2of3_vA2hA2_vB2hB2     non-batching class, 2 groups of 3 heads (a padding head) + sub-blocks
   mmblk_ptqsl_sos_l2_g1_vB2hB2                   non-batching split-of-softmax class, one group
+and, with `mixbit` (or their names) on the command line, the mixed-width cases of oracle.gen_golden.MIXBIT_MMBLK_CASES:
+  mixbit_mmblk_qk_a8b4_vA2hA2_vB2hB2             A 8 bit, B 4 bit, 2 x 2 blocks on both operands
+  mixbit_mmblk_sos_a4b8_vB2hB2                   split-of-softmax A on 4 bits, B on 8 bits in 2 x 2 blocks
 """
 import argparse
 import os
@@ -65,6 +68,11 @@ def main(argv=None):
             continue
         getattr(gg, gen)(name, **kw)
         print(f"[gen] {name}: {os.path.getsize(os.path.join(gg.OUT, name + '.npz'))} bytes", flush=True)
+    # the mixed-width sub-block cases (prefix mixbit_: tests/test_oracle_mixbit.py, tests/test_hip_mixbit.py), on request only
+    mix = [c for c in gg.MIXBIT_MMBLK_CASES if "mixbit" in args.names or c[1] in args.names]
+    if mix:
+        os.chdir(gg.REF)
+        gg.gen_mixed_bits(mix)
 
 
 if __name__ == "__main__":
