@@ -23,9 +23,16 @@ int p4v_debug_set_variant(int variant, int force_generic);
 /* Overrides of launch heuristics: key 0 / 1 / 2 / 3 = candidate groups of k_sweep6 / k_sweep2 / k_sweep2g / k_sweep7
  * (0 = cost model), key 4 = print the launch plans to stderr, key 5 = workgroup order of k_sweep7 + 1, key 6 = k_sweep6 prologue
  * of the cost model (0.1 us), keys 9-15 = slice sizes / tiers / thresholds of the pruned passes, key 12 = reference path switches (7 cosine
- * on the generic kernel, 9 no per-score-block ranges, 11 the round-4 quantiser, >= 16 k_bound timing ablations; 1, 2, 3, 5, 6, 8, 10
- * and 12 selected removed paths: P4V_ERR_INVALID). */
+ * on the generic kernel, 9 no per-score-block ranges, 11 the round-4 quantiser, >= 16 k_bound timing ablations, 4 the previous
+ * stage-B1 kernel of Linear passes (k_bound, 64 x 32 wave tile); 1, 2, 3, 5, 6, 8, 10 and 12 selected removed paths:
+ * P4V_ERR_INVALID). */
 int p4v_debug_set_tuning(int key, int value);
+/* The stage-B1 totals (the bound) of the pruned search passes of the calling thread.  out == NULL and count == NULL: start
+ * keeping them (costs one small copy and a stream synchronise per pruned pass; not inside p4v_calibrate_group).  Otherwise:
+ * stop, *count = how many were kept, out receives min(capacity, *count) of them -- per pass, the evaluated entries of its
+ * [candidate][score block] table in table order.  Nothing but the bound may depend on these numbers (csrc/p4v_api.hip::
+ * run_pass_pruned); exposed so that a test can hold two stage-B1 kernels against each other within prune_margin. */
+int p4v_debug_bound_totals(float* out, int64_t capacity, int64_t* count);
 /* The row selection of the exact pruning alone (k_topk_rows; csrc/p4v_api.hip::slice_fill runs it on the per-sample metric
  * weight): for each of `segs` segments of `n` fp32 masses, d_mass [segs][n], the segment-local indices of the k heaviest
  * entries in ASCENDING index order, d_idx [segs][k]; among equal masses the lowest indices are taken; negative masses

@@ -104,7 +104,7 @@ EXPORTS = [
     "p4v_score_argmax_gather",
     "p4v_quantize_i8", "p4v_pack_plane_i8", "p4v_fake_quant", "p4v_export_quantize", "p4v_multi_copy",
     "p4v_stats_enable", "p4v_stats_reset", "p4v_stats_get", "p4v_stats_launches", "p4v_prune_counters",
-    "p4v_debug_set_variant", "p4v_debug_set_tuning", "p4v_debug_topk_rows", "p4v_debug_pack_dual", "p4v_debug_prep_epi6",
+    "p4v_debug_set_variant", "p4v_debug_set_tuning", "p4v_debug_bound_totals", "p4v_debug_topk_rows", "p4v_debug_pack_dual", "p4v_debug_prep_epi6",
     "p4v_debug_pack_cands", "p4v_debug_gather_im2col",
 ]
 
@@ -200,6 +200,8 @@ def load():
     lib.p4v_debug_set_variant.argtypes = [C.c_int, C.c_int]
     lib.p4v_debug_set_tuning.restype = C.c_int
     lib.p4v_debug_set_tuning.argtypes = [C.c_int, C.c_int]
+    lib.p4v_debug_bound_totals.restype = C.c_int
+    lib.p4v_debug_bound_totals.argtypes = [fp, C.c_int64, C.POINTER(C.c_int64)]
     lib.p4v_stats_enable.restype = C.c_int
     lib.p4v_stats_enable.argtypes = [C.c_int]
     lib.p4v_stats_reset.restype = C.c_int

@@ -92,6 +92,8 @@ thread_local double g_exec_frac = 1.0;     // share of a launch's candidates tha
 thread_local bool g_stat_on = false;
 thread_local std::vector<StatRec> g_stat_recs;
 thread_local std::vector<StatRec> g_stat_done;   // drained records, kept until p4v_stats_reset (p4v_stats_launches)
+thread_local bool g_b1_keep = false;            // p4v_debug_bound_totals: keep the stage-B1 totals of this thread's pruned passes
+thread_local std::vector<float> g_b1_totals;
 thread_local int g_stage = 0;                   // which stage of a pruned pass is being launched: 0 full sweep, 1 A, 2 B1, 3 B2
 thread_local p4v_kernel_stats g_stats = {};
 thread_local long g_memo_hits = 0, g_memo_misses = 0;
@@ -122,10 +124,12 @@ std::atomic<int> g_tune[16];
 enum { TUNE_CG6 = 0, TUNE_CG2 = 1, TUNE_CG2G = 2, TUNE_CG7 = 3, TUNE_PRINT = 4, TUNE_ORDER7 = 5, TUNE_P6 = 6, TUNE_PLANE_GIB = 7, TUNE_EPI6W = 8,
        TUNE_LOOSE_PCT = 9, TUNE_SLICE_DIV = 10, TUNE_SLICE_SMALL = 11, TUNE_B1_PATH = 12, TUNE_TIER2 = 13, TUNE_TIER2_DIV = 14, TUNE_LOOSE_ROWS = 15 };   // LOOSE_ROWS: sample rows from which a module prunes on a 5 % slice share   // TIER2: 1 = no second slice tier; >= 2: minimum survivor count that triggers it   // SLICE_SMALL: rows of the slice a Linear tries first   // pruning: weight share below which a module keeps full sweeps (%); Linear slice = M / div   // EPI6W: 1 = fragment-order epilogue image also in the weight search   // P6: k_sweep6 prologue, 0.1 us; PLANE_GIB: plane budget per chunk (cache limit = half)
 // TUNE_B1_PATH (key 12) doubles as the switch of the reference paths the tests use: 7 cosine on the generic kernel, 9 no
-// per-score-block candidate ranges, 11 quant_fast1 instead of quant16_sat8, >= 16 k_bound timing ablations.  Values 1, 2, 3,
-// 5, 6, 8, 10 and 12 selected paths that were measured and removed; p4v_debug_set_tuning rejects them.
+// per-score-block candidate ranges, 11 quant_fast1 instead of quant16_sat8, >= 16 k_bound timing ablations, 4 the previous
+// stage-B1 kernel of Linear passes (k_bound with a 64 x 32 wave tile: the before / after handle of the tests and of the timing).
+// Values 1, 2, 3, 5, 6, 8, 10 and 12 selected paths that were measured and removed; p4v_debug_set_tuning rejects them.
 inline bool tune_b1_removed(int v) { return v == 1 || v == 2 || v == 3 || v == 5 || v == 6 || v == 8 || v == 10 || v == 12; }
 inline int tune(int k) { return g_tune[k].load(std::memory_order_relaxed); }
+inline bool b1_previous() { return tune(TUNE_B1_PATH) == 4; }
 
 struct Group;
 struct Ctx {
@@ -862,11 +866,16 @@ int launch_sweep(Ctx& c, const SweepParams& p, bool i8, bool twin, int epi, bool
     const double kelems = (double)p.ldk / (i8 ? 1 : 4);
     const StatInfo si = stat_info(kind, (double)p.mtiles * SW_BM * (double)p.ntiles * SW_BN * kelems * p.Z * (p.c1 - p.c0) * (twin ? 2 : 1),
                                   g_alg_macs_cand * (p.c1 - p.c0),
-                                  (fast && p.bound) ? p.mtiles * p.ntiles * 2 : (fast && p.halves > 0) ? p.halves : p.mtiles * p.ntiles, cgroups, g_alg_bytes);
+                                  (fast && p.bound) ? p.mtiles * p.ntiles * (b1_previous() ? 2 : 1) : (fast && p.halves > 0) ? p.halves : p.mtiles * p.ntiles, cgroups, g_alg_bytes);
     const StatInfo* sp = &si;
     if (fast && p.bound) {
-        const dim3 grid(p.mtiles * p.ntiles * 2), block(256);      // 128 x 64 workgroup tiles
-        P4V_EPI4(epi, return enqueue(c, KERN_T(SweepParams, k_bound, E), grid, block, 0, p, sp))
+        const dim3 block(256);
+        if (b1_previous()) {                                       // 128 x 64 workgroup tiles, 64 x 32 per wave (the comparison path)
+            const dim3 grid(p.mtiles * p.ntiles * 2);
+            P4V_EPI4(epi, return enqueue(c, KERN_T(SweepParams, k_bound, E, 1), grid, block, 0, p, sp))
+        }
+        const dim3 grid(p.mtiles * p.ntiles);                      // 128 x 128 workgroup tiles, 64 x 64 per wave
+        P4V_EPI4(epi, return enqueue(c, KERN_T(SweepParams, k_bound, E, 2), grid, block, 0, p, sp))
     }
     if (fast && p.halves > 0) return p.a_cs == 0 ? launch_sweep9_epi<true>(c, p, epi, cgroups, sp) : launch_sweep9_epi<false>(c, p, epi, cgroups, sp);
     if (fast && sweep8_ok(p, twin, epi)) return p.a_cs == 0 ? launch_sweep8_epi<true>(c, p, epi, cgroups, sp) : launch_sweep8_epi<false>(c, p, epi, cgroups, sp);
@@ -1949,6 +1958,12 @@ int run_pass_pruned_impl(Ctx& c, Pass& ps) {
     if (lin && ps.i8 && !ps.twin && (virt || ps.nj == 1)) { b1.bound_kernel = true; b1.cache = nullptr; b1.ecache = nullptr; }
     g_stage = 2;
     { const int r_ = run_pass(c, b1); g_stage = 0; if (r_) return r_; }
+    if (g_b1_keep && !c.dry && !c.grp) {                   // (tests: the bound's totals, the evaluated entries of SB in table order)
+        std::vector<float> h((size_t)b1.eq_n * std::max(1, ps.nj));
+        CHK(q_d2h(c, h.data(), SB, sizeof(float) * h.size()));
+        CHK(q_sync(c));
+        for (float v : h) if (v != -INFINITY) g_b1_totals.push_back(v);
+    }
     // the survivors, and -- when there are none besides stage B1's candidates -- the pass's selection from its totals
     pp.r_out = r2; pp.rblk = rblk2;
     int* hm = (ps.host_sync_ok && !c.dry) ? host_mirror(c) : nullptr;
@@ -3623,6 +3638,14 @@ int p4v_debug_set_tuning(int key, int value) {
     if (key < 0 || key >= 16) return fail(P4V_ERR_INVALID, "p4v_debug_set_tuning: unknown key %d", key);
     if (key == TUNE_B1_PATH && tune_b1_removed(value)) return fail(P4V_ERR_INVALID, "p4v_debug_set_tuning: 12 = %d selects a removed path", value);
     g_tune[key].store(value, std::memory_order_relaxed);
+    return 0;
+}
+
+int p4v_debug_bound_totals(float* out, int64_t capacity, int64_t* count) {
+    if (!out && !count) { g_b1_keep = true; g_b1_totals.clear(); return 0; }
+    g_b1_keep = false;
+    if (count) *count = (int64_t)g_b1_totals.size();
+    if (out) std::copy(g_b1_totals.begin(), g_b1_totals.begin() + std::min<int64_t>(capacity, (int64_t)g_b1_totals.size()), out);
     return 0;
 }
 

@@ -1462,13 +1462,21 @@ __global__ __launch_bounds__(512, 2) void k_sweep2_g(GroupArgs<SweepParams> a) {
 // Its totals are summed in another order than the sweeps' -- so run_pass_pruned never lets a selection depend on them: they
 // only set the bound (margin: prune_margin), and whenever more than the bound's own candidate survives, stage B2 re-evaluates
 // ALL survivors with the unpruned kernels.
-template <int EPI>
+// Wave tile (NB = 32-column blocks per wave).  With NB = 1 a wave reloads (64 + 32) rows x K of fragments for its 64 x 32 outputs:
+// 36 B per output through L1 / L2 against the 8 B of raw_out / raw_grad from HBM -- the fragment stream, not HBM, bounded the
+// kernel.  NB = 2 (the default path) gives the wave the whole 64-column slab: (64 + 64) rows for 64 x 64 outputs,
+// 24 B per output, eight 1 KB loads and eight MFMAs per k-tile, three fragment sets + 64 accumulators = three waves per SIMD.
+// The workgroup tile becomes 128 x 128.  Every (64-row slab, 32-column group) is still summed by one wave, over the same lanes
+// and in the same order, into the same slot of the table: the totals are bit-identical to NB = 1 (integer MFMAs are exact).
+// NB = 1 stays as the comparison path (tuning 12 = 4).
+template <int EPI, int NB>
 __device__ __forceinline__ void k_bound_body(const SweepParams& p, const uint3 blockIdx, const uint3 gridDim) {
+    static_assert(NB == 1 || NB == 2, "k_bound: one or two 32-column blocks per wave");
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 5, l31 = lane & 31;
-    // workgroup tile 128 rows x 64 columns (2 x 2 waves of 64 x 32): p.ntiles counts 128-column tiles
-    const int ntiles = p.ntiles * 2;
+    // workgroup tile 128 rows x 64 NB columns (2 x 2 waves of 64 x 32 NB): p.ntiles counts 128-column tiles
+    const int ntiles = p.ntiles * (2 / NB);
     const int nwg = p.mtiles * ntiles;
     const int t = xcd_remap(blockIdx.x, nwg);
     constexpr int GM = 4;                                  // tile order as k_sweep2: GM row tiles x all column tiles per group
@@ -1486,10 +1494,13 @@ __device__ __forceinline__ void k_bound_body(const SweepParams& p, const uint3 b
     }
     if (c >= p.c1) return;                                 // (a chunked plane: the candidate lives in another chunk's launch)
     const int wr = wid >> 1, wc = wid & 1;
-    const int m0 = mt * 128 + wr * 64, n0 = nt * 64 + wc * 32;
-    float* slot = p.part + (long)c * p.p_cs + (long)(mt * 2 + wr) * p.Np + nt * 2 + wc;
+    const int m0 = mt * 128 + wr * 64, n0 = nt * (64 * NB) + wc * (32 * NB);
+    float* slot = p.part + (long)c * p.p_cs + (long)(mt * 2 + wr) * p.Np + (n0 >> 5);   // one slot per 32-column group
     if (m0 >= p.M || n0 >= p.N) {                          // a tile of pure padding
-        if (lane == 63) slot[0] = 0.0f;
+        if (lane == 63) {
+#pragma unroll
+            for (int j = 0; j < NB; ++j) slot[j] = 0.0f;
+        }
         return;
     }
     // Both planes are packed FOR this pass in MFMA-fragment order (k_pack layout c_inner = 3, the one k_sweep6's stationary
@@ -1497,34 +1508,40 @@ __device__ __forceinline__ void k_bound_body(const SweepParams& p, const uint3 b
     // a wave's load touches 8 cache lines instead of 32 rows.  Wave-uniform 64-bit bases (SGPR pairs, advanced per k-tile) +
     // the lane's 32-bit offset: no vector address arithmetic.
     const char* sA = (const char*)p.A + (long)(m0 >> 6) * p.ktiles * 4096;
-    const char* sB = (const char*)p.B + (long)(n0 >> 6) * p.ktiles * 4096 + ((n0 >> 5) & 1) * 2048;
+    const char* sB = (const char*)p.B + (long)(n0 >> 6) * p.ktiles * 4096 + (NB == 1 ? ((n0 >> 5) & 1) * 2048 : 0);
     const unsigned vo = (unsigned)lane * 16u;
-    v16i acc[2];
+    v16i acc[2][NB];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][r] = 0;
-    struct Fr { v4i a[2][2], b[2]; };                      // [32-row block][first / second 16 bytes of the lane's 32]
+        for (int j = 0; j < NB; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0;
+    struct Fr { v4i a[2][2], b[NB][2]; };                  // [32-row block][first / second 16 bytes of the lane's 32]
     // Inline-asm loads with counted waits: left to itself hipcc waits vmcnt(0) before the MFMAs of k-tile t, i.e. also for the
     // fragments of k-tile t + 1 it has just requested -- no overlap at all (seen in the ISA of the first version).
 #define P4V_BLD(dst, voff, sbase, off) asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(dst) : "v"(voff), "s"(sbase), "n"(off) : "memory")
-    auto load = [&](Fr& f) __attribute__((always_inline)) {            // 6 loads of 1 KB: the next k-tile of both operands
+    auto load = [&](Fr& f) __attribute__((always_inline)) {            // 4 + 2 NB loads of 1 KB: the next k-tile of both operands
         P4V_BLD(f.a[0][0], vo, sA, 0); P4V_BLD(f.a[0][1], vo, sA, 1024);
-        P4V_BLD(f.b[0], vo, sB, 0); P4V_BLD(f.b[1], vo, sB, 1024);
+        P4V_BLD(f.b[0][0], vo, sB, 0); P4V_BLD(f.b[0][1], vo, sB, 1024);
         P4V_BLD(f.a[1][0], vo, sA, 2048); P4V_BLD(f.a[1][1], vo, sA, 3072);
+        if constexpr (NB == 2) { P4V_BLD(f.b[1][0], vo, sB, 2048); P4V_BLD(f.b[1][1], vo, sB, 3072); }
         sA += 4096; sB += 4096;
     };
     auto mma = [&](Fr& f) __attribute__((always_inline)) {
-        asm volatile("" : "+v"(f.a[0][0]), "+v"(f.a[0][1]), "+v"(f.a[1][0]), "+v"(f.a[1][1]), "+v"(f.b[0]), "+v"(f.b[1]) :: "memory");   // after the wait
+        asm volatile("" : "+v"(f.a[0][0]), "+v"(f.a[0][1]), "+v"(f.a[1][0]), "+v"(f.a[1][1]), "+v"(f.b[0][0]), "+v"(f.b[0][1]) :: "memory");   // after the wait
+        if constexpr (NB == 2) asm volatile("" : "+v"(f.b[1][0]), "+v"(f.b[1][1]) :: "memory");
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
-            for (int i = 0; i < 2; ++i) acc[i] = __builtin_amdgcn_mfma_i32_32x32x32_i8(f.a[i][h], f.b[h], acc[i], 0, 0, 0);
+            for (int j = 0; j < NB; ++j)
+#pragma unroll
+                for (int i = 0; i < 2; ++i) acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(f.a[i][h], f.b[j][h], acc[i][j], 0, 0, 0);
     };
     Fr f0, f1, f2;
     const int ktiles = p.ktiles;
-    // three fragment sets, two k-tiles in flight (tile t + 2 is requested before the MFMAs of tile t), four waves per SIMD
-    constexpr int LD = 6;
+    // three fragment sets, two k-tiles in flight (tile t + 2 is requested before the MFMAs of tile t), four (NB = 2: three) waves per SIMD
+    constexpr int LD = 4 + 2 * NB;
     load(f0);
     if (ktiles > 1) load(f1);
     auto step = [&](int kt, Fr& cur, Fr& refill) __attribute__((always_inline)) {
@@ -1542,48 +1559,55 @@ __device__ __forceinline__ void k_bound_body(const SweepParams& p, const uint3 b
     // ---- metric epilogue: raw_out / weight read in place, one sum per (64-row slab, 32-column group) ----
     // The weight tensor is raw_grad (hessian) or raw_out itself (the host passes Wt = O for the raw_out-weighted metrics:
     // square-weighted (w d)^2 with w = raw_out, linear-weighted |w| d^2) -- no run-time switch in the element loop.
-    const int n = n0 + l31;
-    const bool ncol_ok = n < p.N;
-    const int nc = min(n, p.N - 1);
-    const float bias_n = (p.bias && ncol_ok) ? p.bias[nc] : 0.0f;
-    const int sb = p.sb_mode == 1 ? min(nc / p.sb_div, p.s_cs - 1) : 0;
-    const float s1 = p.S1 ? p.S1[(long)c * p.s_cs + sb] : 1.0f;
-    const float* On = p.O + (long)nc * p.o_ns;
-    const float* Wn = p.Wt + (long)nc * p.o_ns;
-    float sum = 0.0f;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {                          // one 32 x 32 block: 16 + 16 loads in flight per lane (the fragment registers are dead)
-        float u[16], w[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {                     // every load at a clamped (valid) address, back to back
-            const int mc = (p.dbg & 2) ? 0 : min(m0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g, p.M - 1);   // (dbg 2: ablation, one row)
-            u[r] = On[(long)mc * p.o_ms];
-            if (EPI == EPI_SQ_W || EPI == EPI_W_SQ) w[r] = Wn[(long)mc * p.o_ms];
+    for (int j = 0; j < NB; ++j) {
+        if (NB > 1 && n0 + j * 32 >= p.N) {                // (a 32-column group of pure padding: its own wave wrote this zero before)
+            if (lane == 63) slot[j] = 0.0f;
+            continue;
         }
+        const int n = n0 + j * 32 + l31;
+        const bool ncol_ok = n < p.N;
+        const int nc = min(n, p.N - 1);
+        const float bias_n = (p.bias && ncol_ok) ? p.bias[nc] : 0.0f;
+        const int sb = p.sb_mode == 1 ? min(nc / p.sb_div, p.s_cs - 1) : 0;
+        const float s1 = p.S1 ? p.S1[(long)c * p.s_cs + sb] : 1.0f;
+        const float* On = p.O + (long)nc * p.o_ns;
+        const float* Wn = p.Wt + (long)nc * p.o_ns;
+        float sum = 0.0f;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int m = m0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-            const bool ok = ncol_ok && m < p.M;
-            const float o = u[r];
-            float wv = 1.0f;
-            if (EPI == EPI_SQ_W) wv = w[r]; else if (EPI == EPI_W_SQ) wv = fabsf(w[r]);
-            const float d = (o - bias_n) - (float)acc[i][r] * s1;
-            float term;
-            if (EPI == EPI_SQ_W) { const float t2 = wv * d; term = t2 * t2; }
-            else if (EPI == EPI_SQ) term = d * d;
-            else if (EPI == EPI_ABS) term = fabsf(d);
-            else term = (wv * d) * d;
-            sum += ok ? term : 0.0f;
+        for (int i = 0; i < 2; ++i) {                      // one 32 x 32 block: 16 + 16 loads in flight per lane (the fragment registers are dead)
+            float u[16], w[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {                 // every load at a clamped (valid) address, back to back
+                const int mc = (p.dbg & 2) ? 0 : min(m0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g, p.M - 1);   // (dbg 2: ablation, one row)
+                u[r] = On[(long)mc * p.o_ms];
+                if (EPI == EPI_SQ_W || EPI == EPI_W_SQ) w[r] = Wn[(long)mc * p.o_ms];
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = m0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
+                const bool ok = ncol_ok && m < p.M;
+                const float o = u[r];
+                float wv = 1.0f;
+                if (EPI == EPI_SQ_W) wv = w[r]; else if (EPI == EPI_W_SQ) wv = fabsf(w[r]);
+                const float d = (o - bias_n) - (float)acc[i][j][r] * s1;
+                float term;
+                if (EPI == EPI_SQ_W) { const float t2 = wv * d; term = t2 * t2; }
+                else if (EPI == EPI_SQ) term = d * d;
+                else if (EPI == EPI_ABS) term = fabsf(d);
+                else term = (wv * d) * d;
+                sum += ok ? term : 0.0f;
+            }
+            asm volatile("" ::: "memory");
         }
-        asm volatile("" ::: "memory");
+        sum = wave_sum_dpp(sum);
+        if (lane == 63) slot[j] = sum;
     }
-    sum = wave_sum_dpp(sum);
-    if (lane == 63) slot[0] = sum;
 }
-template <int EPI>
-__global__ __launch_bounds__(256, 4) void k_bound(SweepParams p) { k_bound_body<EPI>(p, P4V_BIDX, P4V_GDIM); }
-template <int EPI>
-__global__ __launch_bounds__(256, 4) void k_bound_g(GroupArgs<SweepParams> a) { P4V_GROUP_ENTER(a); k_bound_body<EPI>(a.p[m_], vb_, vg_); }
+template <int EPI, int NB>
+__global__ __launch_bounds__(256, NB == 2 ? 3 : 4) void k_bound(SweepParams p) { k_bound_body<EPI, NB>(p, P4V_BIDX, P4V_GDIM); }
+template <int EPI, int NB>
+__global__ __launch_bounds__(256, NB == 2 ? 3 : 4) void k_bound_g(GroupArgs<SweepParams> a) { P4V_GROUP_ENTER(a); k_bound_body<EPI, NB>(a.p[m_], vb_, vg_); }
 
 // ------------------------------------------------------------------------------------------
 // k_sweep8: k_sweep2 for K <= 64 (ONE k-tile: the q.k^T matmuls of every ViT / DeiT / Swin, head_dim <= 64)

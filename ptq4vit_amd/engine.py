@@ -695,6 +695,20 @@ def debug_tuning(key, value):
     _lib.check(_lib.load().p4v_debug_set_tuning(int(key), int(value)), "p4v_debug_set_tuning")
 
 
+def debug_bound_totals(start=False):
+    """start=True: keep the stage-B1 totals (the bound) of this thread's pruned passes from now on.  Otherwise stop and return
+    the ones kept, in pass order (p4v_debug_bound_totals) -- for tests that compare two stage-B1 kernels."""
+    lib = _lib.load()
+    if start:
+        _lib.check(lib.p4v_debug_bound_totals(None, 0, None), "p4v_debug_bound_totals")
+        return None
+    n = C.c_int64(0)
+    _lib.check(lib.p4v_debug_bound_totals(None, 0, C.byref(n)), "p4v_debug_bound_totals")
+    buf = (C.c_float * max(1, n.value))()
+    _lib.check(lib.p4v_debug_bound_totals(buf, n.value, C.byref(n)), "p4v_debug_bound_totals")
+    return [float(v) for v in buf[:n.value]]
+
+
 def debug_topk_rows(mass, k):
     """Row selection of the exact pruning (k_topk_rows) on `mass` [segs, n] fp32: int32 [segs, k], the segment-local indices
     of the k heaviest entries in ascending order (ties: lowest indices).  For the tests."""

@@ -1,4 +1,4 @@
-"""Timing probe of k_bound (stage B1) on ViT-B layer shapes: python tools/bound_probe.py [tuning value of key 12, e.g. 16 / 32: timing ablations]"""
+"""Timing probe of k_bound (stage B1) on ViT-B layer shapes: python tools/bound_probe.py [tuning value of key 12, e.g. 4: the previous kernel (64 x 32 wave tile), 16 / 32: timing ablations]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
