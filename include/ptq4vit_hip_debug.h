@@ -33,6 +33,14 @@ int p4v_debug_set_tuning(int key, int value);
  * [candidate][score block] table in table order.  Nothing but the bound may depend on these numbers (csrc/p4v_api.hip::
  * run_pass_pruned); exposed so that a test can hold two stage-B1 kernels against each other within prune_margin. */
 int p4v_debug_bound_totals(float* out, int64_t capacity, int64_t* count);
+/* ONE sweep of the split-of-softmax split search (k_sos_split + k_finish) on the operands of `desc`, over the first n_cands of
+ * the 20 splits: d_scores [n_cands] receives the score table, entries outside [c_lo, c_hi) as k_finish leaves them (-inf).
+ * c_lo < 0: no candidate range.  known_cands: what the caller tells the sweep about the number of candidates in the range
+ * (< 0: unknown) -- it selects the kernel instance, never the result.  Synchronises the stream.  For tests that hold the
+ * instances of the kernel against each other on ranges the search itself does not produce. */
+int p4v_debug_sos_sweep(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_out, const float* d_grad,
+                        int n_cands, int c_lo, int c_hi, int known_cands, float* d_scores, void* d_workspace, size_t workspace_bytes,
+                        void* stream);
 /* The row selection of the exact pruning alone (k_topk_rows; csrc/p4v_api.hip::slice_fill runs it on the per-sample metric
  * weight): for each of `segs` segments of `n` fp32 masses, d_mass [segs][n], the segment-local indices of the k heaviest
  * entries in ASCENDING index order, d_idx [segs][k]; among equal masses the lowest indices are taken; negative masses

@@ -105,7 +105,7 @@ EXPORTS = [
     "p4v_quantize_i8", "p4v_pack_plane_i8", "p4v_fake_quant", "p4v_export_quantize", "p4v_multi_copy",
     "p4v_stats_enable", "p4v_stats_reset", "p4v_stats_get", "p4v_stats_launches", "p4v_prune_counters",
     "p4v_debug_set_variant", "p4v_debug_set_tuning", "p4v_debug_bound_totals", "p4v_debug_topk_rows", "p4v_debug_pack_dual", "p4v_debug_prep_epi6",
-    "p4v_debug_pack_cands", "p4v_debug_gather_im2col",
+    "p4v_debug_pack_cands", "p4v_debug_gather_im2col", "p4v_debug_sos_sweep",
 ]
 
 _lib = None
@@ -194,6 +194,8 @@ def load():
                                          C.c_int, C.c_int, vp, vp]
     lib.p4v_debug_gather_im2col.restype = C.c_int
     lib.p4v_debug_gather_im2col.argtypes = [C.c_int] * 12 + [fp, ip, C.c_int, fp, vp]
+    lib.p4v_debug_sos_sweep.restype = C.c_int
+    lib.p4v_debug_sos_sweep.argtypes = [C.POINTER(MatMulDesc), fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, fp, vp, C.c_size_t, vp]
     lib.p4v_debug_prep_epi6.restype = C.c_int
     lib.p4v_debug_prep_epi6.argtypes = [fp, fp, fp, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, vp]
     lib.p4v_debug_set_variant.restype = C.c_int

@@ -2066,10 +2066,37 @@ struct SosSplitJob {
 bool sos_split_ok(int M, int K, int N, bool cosm) {
     return !cosm && K <= 200 && M <= 256 && N <= 64 && !(g_variant & 131072);
 }
-template <int KS> int launch_sos_split_ks(Ctx& c, const SosSplitParams& kp, int epi, const StatInfo* si) {
+template <int KS, int VAR> int launch_sos_split_var(Ctx& c, const SosSplitParams& kp, int epi, const StatInfo* si) {
     const dim3 grid(kp.halves, kp.Z), block(256);
     const size_t lds = (size_t)2 * KS * 64 * sizeof(float);
-    P4V_EPI4(epi, return enqueue(c, KERN_T(SosSplitParams, k_sos_split, KS, E), grid, block, lds, kp, si))
+    P4V_EPI4(epi, return enqueue(c, KERN_T(SosSplitParams, k_sos_split, KS, E, VAR), grid, block, lds, kp, si))
+}
+template <int KS> int launch_sos_split_ks(Ctx& c, const SosSplitParams& kp, int var, int epi, const StatInfo* si) {
+    switch (var) {
+        case SOS_PREV: return launch_sos_split_var<KS, SOS_PREV>(c, kp, epi, si);
+        case SOS_PAIR: return launch_sos_split_var<KS, SOS_PAIR>(c, kp, epi, si);
+        case SOS_LIGHT: return launch_sos_split_var<KS, SOS_LIGHT>(c, kp, epi, si);
+        default: return launch_sos_split_var<KS, SOS_RES>(c, kp, epi, si);
+    }
+}
+// The instance of k_sos_split for one sweep (see the kernel).  `known_cands`: the host's count of the candidates in `crange`, < 0
+// when it does not know.  SOS_LIGHT recomputes the two images of every element per candidate, so it pays while the candidates
+// are few: up to SOS_LIGHT_MAX of them (timed at ViT-B shapes with tools/sos_probe.py, docs/DESIGN_LOG.md round 13).
+// Tuning 12 = 13: the previous kernel everywhere; 14: never the light instance; 15: the light instance for every known count.
+constexpr int SOS_LIGHT_MAX = 2;
+int sos_variant(const SosSplitParams& kp, int known_cands) {
+    const int path = tune(TUNE_B1_PATH);
+    if (path == 13) return SOS_PREV;
+    if (kp.halves == 1 && kp.M <= 16) return SOS_PAIR;
+    if (kp.halves == 1 && kp.M <= 32) return SOS_RES;           // (the unpaired share path)
+    // (the light instance addresses A by 32-bit offsets from the (image, head)'s base)
+    const bool a_compact = kp.a_r >= 0 && kp.a_k >= 0 && ((long)(kp.M - 1) * kp.a_r + (long)(kp.K - 1) * kp.a_k) * 4 < (1L << 31);
+    if (path != 14 && a_compact && known_cands >= 1 && (known_cands <= SOS_LIGHT_MAX || path == 15)) return SOS_LIGHT;
+    return SOS_RES;
+}
+bool sos_b_vector_ok(const SosSplitParams& kp) {
+    return kp.b_n == 1 && kp.N % 4 == 0 && reinterpret_cast<uintptr_t>(kp.B) % 16 == 0 && kp.b_k % 4 == 0 && kp.b_z % 4 == 0 &&
+           (kp.zdiv <= 0 || kp.b_z2 % 4 == 0);
 }
 // one launch of the split-search kernel on `kp` (+ k_finish into `scores`, [C] floats); `crange`: device-side candidate range
 SelectParams sos_select_params(const SosSplitJob& j, const float* scores) {
@@ -2080,6 +2107,7 @@ int sos_sweep(Ctx& c, SosSplitJob& j, SosSplitParams kp, const int* crange, floa
     float* part = c.ws.get<float>((size_t)kp.C * kp.Z * slots);
     if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", c.ws.off);
     kp.part = part; kp.crange = crange;
+    kp.bvec = sos_b_vector_ok(kp) ? 1 : 0;
     if (!c.dry) {
         CHK(q_fill(c, part, 0, sizeof(float) * (size_t)kp.C * kp.Z * slots));   // slots of all-padding waves
         const int KS = kp.K <= 64 ? 32 : kp.K <= 144 ? 72 : 100;
@@ -2094,12 +2122,33 @@ int sos_sweep(Ctx& c, SosSplitJob& j, SosSplitParams kp, const int* crange, floa
         const StatInfo si{11, frac * (double)kp.Z * kp.halves * 128 * (2.0 * KS) * 64 * kp.C, frac * (double)kp.Z * kp.M * kp.K * kp.N * kp.C, g_stage, kp.halves, kp.Z,
                           4.0 * ((double)kp.Z * kp.M * kp.K + (double)kp.Z * kp.K * kp.N) + 8.0 * (double)kp.Z * kp.M * kp.N};
         const StatInfo* sp = &si;
-        if (KS == 32) CHK(launch_sos_split_ks<32>(c, kp, j.epi, sp));
-        else if (KS == 72) CHK(launch_sos_split_ks<72>(c, kp, j.epi, sp));
-        else CHK(launch_sos_split_ks<100>(c, kp, j.epi, sp));
+        const int var = sos_variant(kp, crange ? known_cands : -1);
+        if (KS == 32) CHK(launch_sos_split_ks<32>(c, kp, var, j.epi, sp));
+        else if (KS == 72) CHK(launch_sos_split_ks<72>(c, kp, var, j.epi, sp));
+        else CHK(launch_sos_split_ks<100>(c, kp, var, j.epi, sp));
     }
     FinishParams fp{part, (long)kp.Z * slots, (long)slots, slots, 1, kp.Z, slots, kp.C, 0, 1, 1, j.norm, scores, crange};
     return launch_finish(c, fp);
+}
+// p4v_debug_sos_sweep: the calling thread's next split search runs ONE sos_sweep on the first n_cands splits with the given
+// candidate range and known count, and copies its [n_cands] scores out (no selection)
+struct SosDebugSweep { int n_cands, c_lo, c_hi, known_cands; float* d_scores; };
+thread_local const SosDebugSweep* g_sos_debug = nullptr;
+int run_sos_debug_sweep(Ctx& c, SosSplitJob& j, const SosDebugSweep& dbg) {
+    const size_t mark = c.ws.off;
+    SosSplitParams kp = j.kp;
+    kp.C = dbg.n_cands;
+    float* scores = c.ws.get<float>((size_t)kp.C);
+    int* r = c.ws.get<int>(2);
+    if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", c.ws.off);
+    const int h[2] = {dbg.c_lo, dbg.c_hi};
+    const bool ranged = dbg.c_lo >= 0;
+    if (ranged) { CHK(q_h2d(c, r, h, sizeof h)); CHK(q_sync(c)); }
+    CHK(sos_sweep(c, j, kp, ranged ? r : nullptr, scores, dbg.known_cands));
+    HIPCHK(hipMemcpyAsync(dbg.d_scores, scores, sizeof(float) * (size_t)kp.C, hipMemcpyDeviceToDevice, c.st));
+    CHK(q_sync(c));
+    c.ws.off = mark;
+    return 0;
 }
 int sos_select(Ctx& c, SosSplitJob& j, const float* scores) {
     return launch_select(c, sos_select_params(j, scores));
@@ -2725,6 +2774,7 @@ int matmul_impl(const p4v_matmul_desc* d, const float* A, const float* B, const 
             j.cands = split_cands; j.split = split; j.A_iv = A_iv; j.aux_div = (float)(Aq - 1);   // A_interval = split/(qmax-1) (matmul.py:629)
             j.scores_out = (d->eq_n >= NSPLIT) ? so : nullptr; j.scores_out_ld = H; j.best_out = bo;
             j.scache = &slice; j.host_sync_ok = memo_on; j.prunable = !(d->reserved & 8);
+            if (g_sos_debug) return c.grp || c.dry ? fail(P4V_ERR_INVALID, "p4v_debug_sos_sweep: not inside a group") : run_sos_debug_sweep(c, j, *g_sos_debug);
             CHK(run_sos_split_pruned(c, j));
         } else {
             // ---- split search against the UNQUANTISED B (matmul.py:600-631): fp32 operands ----
@@ -3639,6 +3689,24 @@ int p4v_debug_set_tuning(int key, int value) {
     if (key == TUNE_B1_PATH && tune_b1_removed(value)) return fail(P4V_ERR_INVALID, "p4v_debug_set_tuning: 12 = %d selects a removed path", value);
     g_tune[key].store(value, std::memory_order_relaxed);
     return 0;
+}
+
+int p4v_debug_sos_sweep(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_out, const float* d_grad,
+                        int n_cands, int c_lo, int c_hi, int known_cands, float* d_scores, void* d_workspace, size_t workspace_bytes,
+                        void* stream) {
+    if (!desc || !d_A || !d_B || !d_out || !d_scores || !d_workspace) return fail(P4V_ERR_INVALID, "p4v_debug_sos_sweep: null pointer");
+    if (!desc->sos || n_cands < 1 || n_cands > 20 || !sos_split_ok(desc->M, desc->K, desc->N, false))
+        return fail(P4V_ERR_INVALID, "p4v_debug_sos_sweep: a split-of-softmax matmul of the one-kernel split search, 1..20 candidates");
+    const SosDebugSweep dbg{n_cands, c_lo, c_hi, known_cands, d_scores};
+    float* d_split = nullptr;                       // (the sweep selects nothing: split and interval go to scratch)
+    HIPCHK(hipMalloc(&d_split, 2 * sizeof(float)));
+    Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
+    g_sos_debug = &dbg;
+    const int rc = matmul_impl(desc, d_A, d_B, d_out, d_grad, nullptr, d_split + 1, nullptr, d_split, nullptr, nullptr, c, nullptr,
+                               Stage{ST_S1, nullptr, nullptr});
+    g_sos_debug = nullptr;
+    (void)hipFree(d_split);
+    return rc;
 }
 
 int p4v_debug_bound_totals(float* out, int64_t capacity, int64_t* count) {

@@ -3767,58 +3767,176 @@ struct SosSplitParams {
     float* part;                           // [C][Z][halves * 4]
     int halves;
     const int* crange;                     // optional device-side candidate range (clip_crange)
+    int bvec;                              // B tile by 16-byte loads: b_n == 1, N % 4 == 0, base and every stride 16-byte aligned
 };
 
 #ifndef P4V_SOS_DBG
 #define P4V_SOS_DBG 0          // timing-only ablations: 1 no quantisation arithmetic, 2 no B fragment reads, 4 no MFMAs
 #endif
-template <int KS, int EPI>
+// Instances of the one body (VAR), chosen per launch by sos_sweep:
+//   SOS_PREV   the kernel as it was (tuning 12 = 13 runs it in every stage: the before / after handle of tests and timing)
+//   SOS_RES    hv / yv resident for all candidates (the full search, stage B2 with many survivors, 16 < M <= 32 slices)
+//   SOS_PAIR   slices of at most 16 rows (stage A): lanes 16-31 of the 32-row MFMA tile take the SAME 16 rows as lanes 0-15 and
+//              quantise them with the NEXT candidate's constants, so one pair of MFMAs per k-step scores two candidates --
+//              accumulator registers 0-7 are candidate c, 8-15 candidate c + 1.  The previous kernel's registers 8-15 were the
+//              w = 0 padding rows, whose terms are +0: summing 0-7 only, in the same order, gives the same bits.  The ten pairs
+//              go 3 / 3 / 2 / 2 over the four waves (pair i to wave i % 4), pairs counted from the range's start; candidate c
+//              keeps the `part` slot (c - c_lo) % 4 it had, so k_finish adds the same numbers in the same places.
+//   SOS_LIGHT  few candidates over all rows (stage B1, B2 with few survivors): only the raw A values stay resident and the two
+//              images are computed where they are used -- the same two IEEE divisions, the same floats -- which halves the
+//              register count, so two workgroups share a CU and one's prologue runs under the other's MFMAs.
+// Every instance but SOS_PREV issues its whole prologue -- B tile, A rows, O / G -- as ONE burst of loads before the first wait
+// (the previous fill loop was one load, one wait, one LDS write per iteration: 50 serial memory round trips per workgroup with
+// nothing else resident on the CU).  p.bvec (decided on the host from the strides): the B tile in 16-byte loads.
+enum { SOS_PREV = 0, SOS_RES = 1, SOS_PAIR = 2, SOS_LIGHT = 3 };
+template <int KS, int EPI, int VAR>
 __device__ __forceinline__ void k_sos_split_body(const SosSplitParams& p, const uint3 blockIdx, const uint3 gridDim) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* Bt = reinterpret_cast<float*>(smem);                    // [2 KS][64]
+    constexpr bool PAIR = VAR == SOS_PAIR, LIGHT = VAR == SOS_LIGHT;
+    constexpr int NR = PAIR ? 8 : 16;                              // accumulator registers of one candidate
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 5, l31 = lane & 31;
     const int half = blockIdx.x, z = blockIdx.y;
     const long zoffA = p.zdiv > 0 ? (long)(z / p.zdiv) * p.a_z2 + (long)(z % p.zdiv) * p.a_z : (long)z * p.a_z;
     const long zoffB = p.zdiv > 0 ? (long)(z / p.zdiv) * p.b_z2 + (long)(z % p.zdiv) * p.b_z : (long)z * p.b_z;
-
-    // ---- B tile -> LDS, zero padded -------------------------------------------------------------------------------
-    for (int i = tid; i < 2 * KS * 64; i += 256) {
-        const int k = i >> 6, n = i & 63;
-        Bt[i] = (k < p.K && n < p.N) ? p.B[zoffB + (long)k * p.b_k + (long)n * p.b_n] : 0.0f;
-    }
-    // ---- this wave's 32 rows: the two candidate-invariant images of every element ----------------------------------
     // (a problem of at most 32 rows -- the 16-row sample slice of a pruned pass -- would leave three of the four waves without
-    // rows: there all four take the SAME rows and every fourth candidate each)
-    const bool share = p.M <= 32 && p.halves == 1;
+    // rows: there all four take the SAME rows and every fourth candidate -- or candidate pair -- each)
+    const bool share = PAIR || (p.M <= 32 && p.halves == 1);
     const int row0 = share ? 0 : half * 128 + wid * 32;
-    const int row = row0 + l31;
-    float hv[KS], yv[KS];
-    {
-        const float* ap = p.A + zoffA + (long)min(row, p.M - 1) * p.a_r;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const int k = 2 * ks + g;
-            const float x = (row < p.M && k < p.K) ? ap[(long)k * p.a_k] : 0.0f;
-            hv[ks] = rintf(x * p.qm1) / p.qm1;
-            yv[ks] = x / p.c_inv;
+    const int row = row0 + (PAIR ? (l31 & 15) : l31);
+    // hv / yv: the two candidate-invariant images of every element of this wave's rows (LIGHT: xr, the raw element)
+    float hv[LIGHT ? 1 : KS], yv[LIGHT ? 1 : KS], xr[KS];
+    // raw_out / metric weight of the wave's 32 x 64 outputs, accumulator layout
+    float u[2][NR], w[2][NR];
+    auto images = [&](auto ks_c) __attribute__((always_inline)) {
+        constexpr int ks = decltype(ks_c)::value;
+        hv[ks] = rintf(xr[ks] * p.qm1) / p.qm1;
+        yv[ks] = xr[ks] / p.c_inv;
+    };
+    if constexpr (VAR == SOS_PREV) {
+        // ---- B tile -> LDS, zero padded ---------------------------------------------------------------------------
+        for (int i = tid; i < 2 * KS * 64; i += 256) {
+            const int k = i >> 6, n = i & 63;
+            Bt[i] = (k < p.K && n < p.N) ? p.B[zoffB + (long)k * p.b_k + (long)n * p.b_n] : 0.0f;
         }
+        {
+            const float* ap = p.A + zoffA + (long)min(row, p.M - 1) * p.a_r;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const int k = 2 * ks + g;
+                const float x = (row < p.M && k < p.K) ? ap[(long)k * p.a_k] : 0.0f;
+                hv[ks] = rintf(x * p.qm1) / p.qm1;
+                yv[ks] = x / p.c_inv;
+            }
+        }
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = row0 + (r & 3) + 8 * (r >> 2) + 4 * g, n = cb * 32 + l31;
+                const bool ok = m < p.M && n < p.N;
+                const long idx = ((long)z * p.M + min(m, p.M - 1)) * p.N + min(n, p.N - 1);
+                const float o = p.O[idx];
+                const float gw = p.wt_mode == 1 ? p.G[idx] : p.wt_mode == 2 ? o : p.wt_mode == 3 ? fabsf(o) : 1.0f;
+                u[cb][r] = ok ? o : 0.0f;
+                w[cb][r] = ok ? gw : 0.0f;         // also the validity mask of the unweighted metrics (padding rows quantise to != 0)
+            }
+    } else {
+        // ---- the prologue's loads, all in flight before the first wait: B tile, A rows, O (and G) -------------------
+        // (every load is unconditional, from an address clamped into the operand, and the padding is a select on the value where
+        // it is used: a conditional load is a branch around it, and a wait wherever the register allocator copies its result)
+        const float* bp = p.B + zoffB;
+        auto load_a = [&]() __attribute__((always_inline)) {
+            if constexpr (LIGHT) {
+                // (256 registers: one 32-bit offset per load from the (image, head)'s uniform base, not a 64-bit address each --
+                // sos_sweep takes this instance only where the operand's extent allows it)
+                const char* ab = reinterpret_cast<const char*>(p.A + zoffA);
+                const unsigned ro = (unsigned)min(row, p.M - 1) * (unsigned)p.a_r, ak = (unsigned)p.a_k;
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks)
+                    xr[ks] = *reinterpret_cast<const float*>(ab + (size_t)((ro + (unsigned)min(2 * ks + g, p.K - 1) * ak) * 4u));
+            } else {
+                const float* ap = p.A + zoffA + (long)min(row, p.M - 1) * p.a_r;
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks)
+                    xr[ks] = ap[(long)min(2 * ks + g, p.K - 1) * p.a_k];
+            }
+        };
+        auto load_og = [&]() __attribute__((always_inline)) {       // (the wt_mode decision is taken once, not per load)
+            const char* ob = reinterpret_cast<const char*>(p.O + (long)z * p.M * p.N);      // M N <= 256 * 64: 32-bit offsets
+            const char* gb = reinterpret_cast<const char*>(p.G + (long)z * p.M * p.N);
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+                for (int r = 0; r < NR; ++r) {
+                    const int m = row0 + (r & 3) + 8 * (r >> 2) + 4 * g, n = cb * 32 + l31;
+                    u[cb][r] = *reinterpret_cast<const float*>(ob + (size_t)((unsigned)(min(m, p.M - 1) * p.N + min(n, p.N - 1)) * 4u));
+                }
+            if (p.wt_mode == 1) {
+#pragma unroll
+                for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+                    for (int r = 0; r < NR; ++r) {
+                        const int m = row0 + (r & 3) + 8 * (r >> 2) + 4 * g, n = cb * 32 + l31;
+                        w[cb][r] = *reinterpret_cast<const float*>(gb + (size_t)((unsigned)(min(m, p.M - 1) * p.N + min(n, p.N - 1)) * 4u));
+                    }
+            }
+        };
+        // The thread's pieces of the B tile go through registers: VEC 16-byte pieces, else single elements.  (LIGHT has 256
+        // registers and a second workgroup on the CU to hide behind: the A rows and O / G are its second burst, issued when
+        // the B tile has left its registers.)
+        auto loads = [&](auto vec_c) __attribute__((always_inline)) {
+            constexpr bool VEC = decltype(vec_c)::value;
+            constexpr int W = VEC ? 4 : 1;
+            constexpr int NB = (2 * KS * 64 / W + 255) / 256;          // pieces per thread
+            typedef float piece __attribute__((ext_vector_type(W)));
+            piece bb[NB];
+#pragma unroll
+            for (int t = 0; t < NB; ++t) {
+                const int i = (tid + t * 256) * W, k = i >> 6, n = i & 63;
+                bb[t] = *reinterpret_cast<const piece*>(bp + (long)min(k, p.K - 1) * p.b_k + (VEC ? (long)min(n, p.N - 4) : (long)min(n, p.N - 1) * p.b_n));
+            }
+            if constexpr (!LIGHT) { load_a(); load_og(); }
+            __builtin_amdgcn_sched_barrier(0);
+            // ---- ... and their uses, in the order the loads were issued ----
+#pragma unroll
+            for (int t = 0; t < NB; ++t) {
+                const int i = (tid + t * 256) * W, k = i >> 6, n = i & 63;
+                const piece v = (k < p.K && n < p.N) ? bb[t] : piece(0.0f);
+                if (NB * 256 * W == 2 * KS * 64 || i < 2 * KS * 64) *reinterpret_cast<piece*>(Bt + i) = v;
+            }
+            if constexpr (LIGHT) { __builtin_amdgcn_sched_barrier(0); load_a(); load_og(); __builtin_amdgcn_sched_barrier(0); }
+        };
+        if (p.bvec) loads(std::true_type{}); else loads(std::false_type{});
+        const int kg = row < p.M ? p.K - g : 0;                  // k = 2 ks + g < K  <=>  2 ks < kg (no per-element index register)
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) xr[ks] = 2 * ks < kg ? xr[ks] : 0.0f;
+        if constexpr (!LIGHT) {
+            [&]<int... S>(std::integer_sequence<int, S...>) __attribute__((always_inline)) {
+                (images(std::integral_constant<int, S>{}), ...);
+            }(std::make_integer_sequence<int, KS>{});
+        }
+        auto weights = [&](auto wsel_c) __attribute__((always_inline)) {
+            constexpr int wsel = decltype(wsel_c)::value;
+#pragma unroll
+          for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+                const int m = row0 + (r & 3) + 8 * (r >> 2) + 4 * g, n = cb * 32 + l31;
+                const bool ok = m < p.M && n < p.N;
+                const float o = u[cb][r];
+                const float gw = wsel == 0 ? w[cb][r] : wsel == 1 ? o : wsel == 2 ? fabsf(o) : 1.0f;
+                u[cb][r] = ok ? o : 0.0f;
+                w[cb][r] = ok ? gw : 0.0f;
+            }
+        };
+        if (p.wt_mode == 1) weights(std::integral_constant<int, 0>{});
+        else if (p.wt_mode == 2) weights(std::integral_constant<int, 1>{});
+        else if (p.wt_mode == 3) weights(std::integral_constant<int, 2>{});
+        else weights(std::integral_constant<int, 3>{});
     }
-    // ---- raw_out / metric weight of the wave's 32 x 64 outputs, accumulator layout -----------------------------------
-    float u[2][16], w[2][16];
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int m = row0 + (r & 3) + 8 * (r >> 2) + 4 * g, n = cb * 32 + l31;
-            const bool ok = m < p.M && n < p.N;
-            const long idx = ((long)z * p.M + min(m, p.M - 1)) * p.N + min(n, p.N - 1);
-            const float o = p.O[idx];
-            const float gw = p.wt_mode == 1 ? p.G[idx] : p.wt_mode == 2 ? o : p.wt_mode == 3 ? fabsf(o) : 1.0f;
-            u[cb][r] = ok ? o : 0.0f;
-            w[cb][r] = ok ? gw : 0.0f;         // also the validity mask of the unweighted metrics (padding rows quantise to != 0)
-        }
     __syncthreads();
     if (row0 >= p.M) return;                  // a wave of pure padding (no barrier below)
 
@@ -3826,8 +3944,11 @@ __device__ __forceinline__ void k_sos_split_body(const SosSplitParams& p, const 
     const float* b0 = Bt + g * 64 + l31;      // B fragment of k-step ks, column block cb: b0[ks * 128 + cb * 32]
     int c_lo_ = 0, c_hi_ = p.C;
     clip_crange(p.crange, c_lo_, c_hi_);
-    for (int c = c_lo_ + (share ? wid : 0); c < c_hi_; c += share ? 4 : 1) {
-        const float s = p.splits[c];
+    constexpr int CW = PAIR ? 2 : 1;          // candidates of one pass over k
+    for (int c = c_lo_ + (share ? wid * CW : 0); c < c_hi_; c += share ? 4 * CW : CW) {
+        // PAIR: lanes 16-31 of each half-wave carry candidate c + 1 (the last pair of an odd range: c again, not written)
+        const bool two = PAIR && c + 1 < c_hi_;
+        const float s = (PAIR && two && (l31 & 16)) ? p.splits[c + 1] : p.splits[c];
         const float inv_s = 1.0f / s;                           // 2^i, exact
         const float a_int = s / p.qm1;                          // matmul.py:609
         const float cl = rintf(s * p.qm1) / p.qm1;
@@ -3840,9 +3961,16 @@ __device__ __forceinline__ void k_sos_split_body(const SosSplitParams& p, const 
             if constexpr (ks < KS) {
                 if constexpr ((P4V_SOS_DBG & 2) != 0) { bq0[ks % 3] = cl; bq1[ks % 3] = inv_s; }
                 else { bq0[ks % 3] = b0[ks * 128]; bq1[ks % 3] = b0[ks * 128 + 32]; }
-                if constexpr ((P4V_SOS_DBG & 1) != 0) { aq[ks % 3] = hv[ks] + yv[ks]; return; }
-                const float hi = __builtin_amdgcn_fmed3f(hv[ks], cl, 1.0f);
-                const float li = __builtin_amdgcn_fmed3f(rintf(yv[ks] * inv_s), 0.0f, p.lo_top);
+                float hvk, yvk;
+                if constexpr (LIGHT) {
+                    float x = xr[ks];
+                    asm volatile("" : "+v"(x));                   // (the images are NOT to be hoisted out of the candidate loop)
+                    hvk = rintf(x * p.qm1) / p.qm1;
+                    yvk = x / p.c_inv;
+                } else { hvk = hv[ks]; yvk = yv[ks]; }
+                if constexpr ((P4V_SOS_DBG & 1) != 0) { aq[ks % 3] = hvk + yvk; return; }
+                const float hi = __builtin_amdgcn_fmed3f(hvk, cl, 1.0f);
+                const float li = __builtin_amdgcn_fmed3f(rintf(yvk * inv_s), 0.0f, p.lo_top);
                 float lo = li * a_int;
                 asm volatile("" : "+v"(lo));                      // the product is rounded before the sum (no fma contraction)
                 aq[ks % 3] = hi + lo;
@@ -3861,26 +3989,30 @@ __device__ __forceinline__ void k_sos_split_body(const SosSplitParams& p, const 
                 __builtin_amdgcn_sched_barrier(0);
             }(), ...);
         }(std::make_integer_sequence<int, KS>{});
-        float sum = 0.0f;
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
+        for (int h = 0; h < CW; ++h) {
+            float sum = 0.0f;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float d = u[cb][r] - (cb ? acc1[r] : acc0[r]);
-                const float ww = w[cb][r];
-                if (EPI == EPI_SQ_W) { const float t2 = ww * d; sum = fmaf(t2, t2, sum); }
-                else if (EPI == EPI_SQ) sum = fmaf(ww * d, d, sum);
-                else if (EPI == EPI_ABS) sum = fmaf(ww, fabsf(d), sum);
-                else sum = fmaf(ww * d, d, sum);
-            }
-        sum = wave_sum_dpp(sum);
-        if (lane == 63) p.part[((long)c * p.Z + z) * (p.halves * 4) + half * 4 + wid] = sum;
+            for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+                for (int r = 0; r < NR; ++r) {
+                    const float d = u[cb][r] - (cb ? acc1[h * NR + r] : acc0[h * NR + r]);
+                    const float ww = w[cb][r];
+                    if (EPI == EPI_SQ_W) { const float t2 = ww * d; sum = fmaf(t2, t2, sum); }
+                    else if (EPI == EPI_SQ) sum = fmaf(ww * d, d, sum);
+                    else if (EPI == EPI_ABS) sum = fmaf(ww, fabsf(d), sum);
+                    else sum = fmaf(ww * d, d, sum);
+                }
+            sum = wave_sum_dpp(sum);
+            const int slot = PAIR ? ((c + h - c_lo_) & 3) : wid;
+            if (lane == 63 && (h == 0 || two)) p.part[((long)(c + h) * p.Z + z) * (p.halves * 4) + half * 4 + slot] = sum;
+        }
     }
 }
-template <int KS, int EPI>
-__global__ __launch_bounds__(256, 1) void k_sos_split(SosSplitParams p) { k_sos_split_body<KS, EPI>(p, P4V_BIDX, P4V_GDIM); }
-template <int KS, int EPI>
-__global__ __launch_bounds__(256, 1) void k_sos_split_g(GroupArgs<SosSplitParams> a) { P4V_GROUP_ENTER(a); k_sos_split_body<KS, EPI>(a.p[m_], vb_, vg_); }
+template <int KS, int EPI, int VAR>
+__global__ __launch_bounds__(256, VAR == SOS_LIGHT ? 2 : 1) void k_sos_split(SosSplitParams p) { k_sos_split_body<KS, EPI, VAR>(p, P4V_BIDX, P4V_GDIM); }
+template <int KS, int EPI, int VAR>
+__global__ __launch_bounds__(256, VAR == SOS_LIGHT ? 2 : 1) void k_sos_split_g(GroupArgs<SosSplitParams> a) { P4V_GROUP_ENTER(a); k_sos_split_body<KS, EPI, VAR>(a.p[m_], vb_, vg_); }
 
 // ------------------------------------------------------------------------------------------
 // k_finish / k_select

@@ -794,6 +794,27 @@ def debug_prep_epi6(o, wt, bias, *, o_ss, o_ts, sr, tr, bias_on_t, wt_mode, tran
     _lib.check(rc, "p4v_debug_prep_epi6")
     return e
 
+def debug_sos_sweep(*, A, B, out, grad, A_bit, metric, crange=None, known_cands=-1, n_cands=20):
+    """ONE sweep of the split-of-softmax split search (k_sos_split + k_finish; p4v_debug_sos_sweep) over the first `n_cands`
+    splits of A [b][H][M][K] against the raw B [b][H][K][N] (any strides): the [n_cands] score table, -inf outside `crange`
+    = (lo, hi) (None: no range).  `known_cands`: what the sweep is told about the number of candidates in the range; it
+    selects the kernel instance, never the result.  For the tests and tools/sos_probe.py."""
+    lib = _lib.load()
+    dev = device_of(A, B)
+    A, B = to_dev(A, dev), to_dev(B, dev)
+    out = to_dev(out, dev).contiguous()
+    grad = to_dev(grad, dev).contiguous() if grad is not None else None
+    d = _matmul_desc(A, B, A_bit, 8, metric, 100, 1, True, 0, 0)[1]
+    ws = workspace(dev, _need(lib.p4v_matmul_workspace_bytes, d, "p4v_matmul_workspace_bytes"))
+    scores = torch.full((int(n_cands),), float("nan"), dtype=torch.float32, device=dev)
+    lo, hi = (-1, -1) if crange is None else (int(crange[0]), int(crange[1]))
+    with torch.cuda.device(dev):
+        rc = lib.p4v_debug_sos_sweep(C.byref(d), ptr(A), ptr(B), ptr(out), ptr(grad), int(n_cands), lo, hi, int(known_cands),
+                                     ptr(scores), ptr(ws), ws.numel(), stream_ptr(dev))
+    _lib.check(rc, "p4v_debug_sos_sweep")
+    return scores
+
+
 def stats_reset():
     _lib.load().p4v_stats_reset()
 
