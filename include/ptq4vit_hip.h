@@ -65,6 +65,8 @@ const char* p4v_last_error(void);
 /* ------------------------------------------------------------------------------------------
  * Linear: replaces PTQSLBatchingQuantLinear.calibration_step2 (quant_layers/linear.py:536-555)
  * and PostGeluPTQSLBatchingQuantLinear (linear.py:557-642, `twin_postgelu` = 1).
+ * Blocks: n_H = n_a = 1 searches on int8 planes.  n_H > 1 or n_a > 1: the difference metrics on fp32 candidate planes; the
+ * cosine metric on K-segmented int8 planes (K < 16384, n_H, n_a <= 8; not with `twin_postgelu`: P4V_ERR_UNSUPPORTED).
  * ---------------------------------------------------------------------------------------- */
 typedef struct p4v_linear_desc {
     int32_t batch;        /* raw_input.shape[0]                                   */
@@ -81,7 +83,9 @@ typedef struct p4v_linear_desc {
     int32_t has_bias;
     int32_t reserved;     /* bit 0: force the generic fp32-operand path; bit 1: disable pass memoisation;
                              bit 2: p4v_linear_workspace_bytes sizes the workspace for p4v_linear_quant_forward only;
-                             bit 3: disable exact candidate pruning (every candidate is swept over every sample) */
+                             bit 3: disable exact candidate pruning (every candidate is swept over every sample);
+                             bits 8..11 (p4v_linear_search_w / _a only): 1 + b runs the step of column / activation block b
+                             alone and returns ITS score table and selections (0: every block in turn, tables of block 0) */
 } p4v_linear_desc;
 
 size_t p4v_linear_workspace_bytes(const p4v_linear_desc* desc);
@@ -272,7 +276,8 @@ int p4v_launch_counters(int64_t* out4, int reset);
 int p4v_amax_init_linear(const p4v_linear_desc* desc, const float* d_weight, const float* d_x, float* d_w_interval,
                          float* d_a_interval, void* d_workspace, size_t workspace_bytes, void* stream);
 
-/* PTQSLBatchingQuantLinear._search_best_w_interval (linear.py:455-495): all n_H column blocks, argmax per V block.
+/* PTQSLBatchingQuantLinear._search_best_w_interval (linear.py:455-495): all n_H column blocks, argmax per V block
+ * (desc.reserved bits 8..11 = 1 + b: column block b alone, d_scores / d_best of that block; likewise p4v_linear_search_a).
  * d_w_cands [eq_n+1][n_V*n_H]; d_w_interval in/out; d_a_interval in (the current counterpart, linear.py:476). */
 int p4v_linear_search_w(const p4v_linear_desc* desc, const float* d_weight, const float* d_bias, const float* d_x,
                         const float* d_out, const float* d_grad, const float* d_w_cands, float* d_w_interval,

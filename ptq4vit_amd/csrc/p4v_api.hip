@@ -956,6 +956,8 @@ struct SegPlan {
     const float* split;                             // sos
     int side, ov_v, ov_h;                           // 0: forward; 1 / 2: the searched block of A / B
     const float* cands; int cand_cs, cand_hs;       // its candidates: cands[c * cand_cs + head * cand_hs]
+    bool b_shared;                                  // B and its intervals [nVB][nHB] are the same for every head (b_st[0] = b_st[1] = 0):
+                                                    // ONE plane of B -- the activations of a Linear layer (linear_impl)
 };
 
 struct Pass {
@@ -1041,7 +1043,8 @@ bool dual_pack_ok(const PackParams& a, const PackParams& b) {
            a.s_z == b.s_z && a.s_z2 == b.s_z2 && a.zdiv == b.zdiv;
 }
 
-// ---- the sub-block MatMul pass: k_pack_seg planes, k_sweep_seg, then the common finish / selection ---------------------------
+// ---- the sub-block pass (MatMul; cosine Linear with column / activation blocks): k_pack_seg planes, k_sweep_seg, then the
+// common finish (k_finish; EPI_COS: k_finish_cos) and selection -----------------------------------------------------------------
 int launch_pack_seg(Ctx& c, PackSegParams p) {
     if (c.dry) return 0;
     p.qbias = (p.mode == PACK_SYM && p.lo == -128 && p.hi == 127) ? cvt_bias(c) : 0.0f;
@@ -1054,16 +1057,20 @@ template <bool TWIN> int launch_sweep_seg_epi(Ctx& c, const SweepSegParams& p, i
     const size_t lds = 2 * (TWIN ? 3 : 2) * SW_TILE_BYTES + 2 * SEG_MAX * 128 * sizeof(float) + SEG_KT_MAX * sizeof(short) + 2 * SEG_MAX;
     dim3 grid(p.mtiles * p.ntiles, p.Z, cgroups), block(512);
     if (epi == EPI_FWD) return enqueue(c, KERN_T(SweepSegParams, k_sweep_seg, TWIN, EPI_FWD), grid, block, lds, p, si);
+    if constexpr (!TWIN) { if (epi == EPI_COS) return enqueue(c, KERN_T(SweepSegParams, k_sweep_seg, false, EPI_COS), grid, block, lds, p, si); }
+    if (epi == EPI_COS) return fail(P4V_ERR_UNSUPPORTED, "k_sweep_seg: the cosine epilogue has no twin instance");
     P4V_EPI4(epi, return enqueue(c, KERN_T(SweepSegParams, k_sweep_seg, TWIN, E), grid, block, lds, p, si))
 }
 int run_pass_seg(Ctx& c, Pass& ps) {
     const SegPlan& g = *ps.seg;
     const int Z = ps.Z, M = g.M, N = g.N, H = g.H, Kseg = g.Kseg;
-    const bool fwd = ps.epi == EPI_FWD;
+    const bool fwd = ps.epi == EPI_FWD, cosm = ps.epi == EPI_COS;
+    const int ZB = g.b_shared ? 1 : Z;                           // planes of B
     g_alg_macs_cand = (double)M * N * g.K * Z;
-    g_alg_bytes = 4.0 * ((double)M * g.K * Z + (double)N * g.K * Z) + (ps.G ? 8.0 : 4.0) * (double)M * N * Z;
-    const int Mp = (int)rup(M, SW_BM), Np = (int)rup(N, SW_BN), MT = Mp / 64;
-    const long a_plane = (long)Z * Mp * Kseg, b_plane = (long)Z * Np * Kseg;
+    g_alg_bytes = 4.0 * ((double)M * g.K * Z + (double)N * g.K * ZB) + (ps.G ? 8.0 : 4.0) * (double)M * N * Z;
+    // (cosine: k_finish_cos's table, ceil(M / 64) slabs of (dot, |sim|^2, |raw|^2) per padded sample)
+    const int Mp = (int)rup(M, SW_BM), Np = (int)rup(N, SW_BN), MT = cosm ? cdiv(M, 64) : Mp / 64;
+    const long a_plane = (long)Z * Mp * Kseg, b_plane = (long)ZB * Np * Kseg;
     const bool a_exp = g.side == 1, b_exp = g.side == 2;
     const long exp_plane = a_exp ? a_plane : b_plane;
     const int chunk = (int)std::max<long>(1, std::min<long>(ps.eq_n, PLANE_BUDGET / std::max<long>(1, exp_plane)));
@@ -1071,7 +1078,7 @@ int run_pass_seg(Ctx& c, Pass& ps) {
     char* abuf = c.ws.get<char>((size_t)a_plane * (a_exp ? chunk : 1));
     char* a2buf = g.sos ? c.ws.get<char>((size_t)a_plane) : nullptr;
     char* bbuf = c.ws.get<char>((size_t)b_plane * (b_exp ? chunk : 1));
-    const long p_zs = (long)MT * Np, p_cs = p_zs * Z;
+    const long p_zs = (long)MT * Np * (cosm ? 3 : 1), p_cs = p_zs * Z;
     float* part = fwd ? nullptr : c.ws.get<float>((size_t)p_cs * ps.eq_n);
     float* scores = fwd ? nullptr : c.ws.get<float>((size_t)ps.eq_n * H);
     if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", c.ws.off);
@@ -1096,7 +1103,7 @@ int run_pass_seg(Ctx& c, Pass& ps) {
     auto b_pack = [&](char* dst, const float* cands, int C) {
         PackSegParams p{};           // logical [Z][rows = n][K]: the row block is B's column block, the k block its row block
         p.src = g.B; p.s_z2 = g.b_st[0]; p.s_z = g.b_st[1]; p.s_r = g.b_st[3]; p.s_k = g.b_st[2]; p.zdiv = H;
-        p.Z = Z; p.R = N; p.K = g.K; p.Rp = Np; p.Kseg = Kseg; p.dst = dst; p.C = C;
+        p.Z = ZB; p.R = N; p.K = g.K; p.Rp = Np; p.Kseg = Kseg; p.dst = dst; p.C = C;     // (b_shared: z = head = 0)
         p.H = H; p.mode = PACK_SYM; p.seg = g.seg;
         std::memcpy(p.kblk, g.bblk, sizeof p.kblk);
         p.iv = g.ivB; p.iv_hs = g.nVB * g.nHB; p.iv_rs = 1; p.iv_ks = g.nHB; p.r_div = g.ccB; p.nblk_r = g.nHB;
@@ -1115,7 +1122,8 @@ int run_pass_seg(Ctx& c, Pass& ps) {
         SweepSegParams sp{};
         sp.a_cs = a_exp ? a_plane : 0; sp.A = abuf - (long)c0 * sp.a_cs; sp.a_zs = (long)Mp * Kseg;
         sp.A2 = a2buf; sp.a2_zs = sp.a_zs;
-        sp.b_cs = b_exp ? b_plane : 0; sp.B = bbuf - (long)c0 * sp.b_cs; sp.b_zs = (long)Np * Kseg;
+        sp.b_cs = b_exp ? b_plane : 0; sp.B = bbuf - (long)c0 * sp.b_cs; sp.b_zs = g.b_shared ? 0 : (long)Np * Kseg;
+        sp.b_shared = g.b_shared; sp.bias = ps.bias; sp.bias_zs = ps.bias_zs;
         sp.ldk = Kseg; sp.ktiles = Kseg / SW_BKB;
         sp.ivA = g.sos ? nullptr : g.ivA; sp.ivB = g.ivB;
         sp.H = H; sp.nVA = g.nVA; sp.nHA = g.nHA; sp.nVB = g.nVB; sp.nHB = g.nHB; sp.m_div = g.crA; sp.n_div = g.ccB;
@@ -1135,8 +1143,13 @@ int run_pass_seg(Ctx& c, Pass& ps) {
         CHK(g.sos ? launch_sweep_seg_epi<true>(c, sp, ps.epi, cgroups, &si) : launch_sweep_seg_epi<false>(c, sp, ps.epi, cgroups, &si));
     }
     if (fwd) { c.ws.off = mark; return 0; }
-    FinishParams fp{part, p_cs, p_zs, Np, MT, Z, N, ps.eq_n, ps.j_mode, std::max(1, ps.j_div), ps.nj, ps.norm, scores, nullptr};
-    CHK(launch_finish(c, fp));
+    if (cosm) {
+        FinishCosParams fp{part, p_cs, p_zs, Np, MT, ps.cos_ZB, ps.cos_ZV, N, ps.eq_n, ps.cos_j_mode, std::max(1, ps.cos_j_div), ps.nj, ps.norm, scores};
+        CHK(launch_finish_cos(c, fp));
+    } else {
+        FinishParams fp{part, p_cs, p_zs, Np, MT, Z, N, ps.eq_n, ps.j_mode, std::max(1, ps.j_div), ps.nj, ps.norm, scores, nullptr};
+        CHK(launch_finish(c, fp));
+    }
     SelectParams sl{scores, ps.eq_n, ps.nj, ps.cands, ps.cand_cs, ps.cand_js, ps.cand_off, ps.interval, ps.out_js,
                     ps.out_off, ps.aux_out, ps.aux_div, ps.scores_out, ps.scores_out_ld, ps.best_out};
     CHK(launch_select(c, sl));
@@ -2297,6 +2310,31 @@ PackParams pack2d(const float* src, long rows, long cols, long ld) {
     return p;
 }
 
+// The K-segment table of a SegPlan whose sizes and block counts are set: K cut at every multiple of A's column-block width and
+// of B's row-block width, S <= n_H_A + n_V_B - 1 segments
+int seg_cut_k(SegPlan& g, const char* who) {
+    const int K = g.K;
+    if (K >= 16384) return fail(P4V_ERR_UNSUPPORTED, "%s: K < 16384 with sub-blocks", who);
+    std::vector<int> cuts{0};
+    for (int i = 1; i < g.nHA; ++i) if (i * g.ccA < K) cuts.push_back(i * g.ccA);
+    for (int i = 1; i < g.nVB; ++i) if (i * g.crB < K) cuts.push_back(i * g.crB);
+    std::sort(cuts.begin(), cuts.end());
+    cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
+    if ((int)cuts.size() > SEG_MAX - 1) return fail(P4V_ERR_UNSUPPORTED, "%s: more than %d K segments", who, SEG_MAX - 1);
+    g.seg.S = (int)cuts.size();
+    int dpos = 0;
+    for (int s = 0; s < g.seg.S; ++s) {
+        const int k1 = s + 1 < g.seg.S ? cuts[s + 1] : K;
+        g.seg.k0[s] = (short)cuts[s]; g.seg.d0[s] = (short)dpos;
+        g.ablk[s] = (unsigned char)(cuts[s] / g.ccA); g.bblk[s] = (unsigned char)(cuts[s] / g.crB);
+        dpos += (int)rup(k1 - cuts[s], 64);
+    }
+    for (int s = g.seg.S; s <= SEG_MAX; ++s) { g.seg.k0[s] = (short)K; g.seg.d0[s] = (short)dpos; }
+    g.Kseg = dpos;
+    if (g.Kseg / SW_BKB > SEG_KT_MAX) return fail(P4V_ERR_UNSUPPORTED, "%s: K too large for the segment table", who);
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Linear
 // ------------------------------------------------------------------------------------------------
@@ -2320,7 +2358,24 @@ int linear_impl(const p4v_linear_desc* d, const float* W, const float* bias, con
     const bool general = (nH > 1 || nA > 1 || (d->reserved & 1) || (cosm && d->twin_postgelu && !fwd_out));
     const bool i8 = !general;
     const bool twin = d->twin_postgelu && i8;
-    if (cosm && !fwd_out && (nH > 1 || nA > 1)) return fail(P4V_ERR_UNSUPPORTED, "linear: cosine with n_H>1 / n_a>1 is not implemented on the GPU");
+    // Cosine with column / activation blocks (linear.py:455-533): the K-segmented int8 sweep, transposed -- A := W as n_V heads of
+    // crb_rows x K with intervals w_iv[v][h], B := x as K x samples shared by the heads with intervals a_iv[a]; K cut at the
+    // multiples of crb_cols and crb_acts.  One block step per pass (run_pass_seg), every other block on the interval entering it.
+    const bool segcos = cosm && !fwd_out && (nH > 1 || nA > 1);
+    if (segcos && d->twin_postgelu)
+        return fail(P4V_ERR_UNSUPPORTED, "linear: cosine with n_H>1 / n_a>1 on the post-GELU twin is not implemented on the GPU "
+                                         "(the twin's second plane lies on the column side, k_sweep_seg has no instance for that)");
+    SegPlan sgp{};
+    if (segcos) {
+        if (nH > 8 || nA > 8) return fail(P4V_ERR_UNSUPPORTED, "linear: cosine with up to n_H, n_a = 8 blocks is implemented on the GPU");
+        sgp.batch = 1; sgp.H = nV; sgp.M = crb_rows; sgp.K = K; sgp.N = M;
+        sgp.nVA = 1; sgp.nHA = nH; sgp.nVB = nA; sgp.nHB = 1;
+        sgp.crA = crb_rows; sgp.ccA = crb_cols; sgp.crB = crb_acts; sgp.ccB = M;
+        sgp.A = W; sgp.a_st[0] = 0; sgp.a_st[1] = (long)crb_rows * K; sgp.a_st[2] = K; sgp.a_st[3] = 1;
+        sgp.B = X; sgp.b_st[0] = 0; sgp.b_st[1] = 0; sgp.b_st[2] = 1; sgp.b_st[3] = K; sgp.b_shared = true;
+        sgp.Aq = wq; sgp.Bq = aq; sgp.ivA = w_iv; sgp.ivB = a_iv;
+        CHK(seg_cut_k(sgp, "linear"));
+    }
     const int ncand = d->eq_n + 1;
 
     cvt_bias(c);     // (first call of the process: probe the conversion quant16_sat8 relies on)
@@ -2334,6 +2389,7 @@ int linear_impl(const p4v_linear_desc* d, const float* W, const float* bias, con
     float* Ufold = twin ? c.ws.get<float>((size_t)M * N) : nullptr;   // twin activation search: folded target
     float* w_mix = c.ws.get<float>((size_t)ncand * nV * nH);   // general path: candidates of block column h only
     float* a_mix = c.ws.get<float>((size_t)ncand * nA);
+    float* Ot = segcos ? c.ws.get<float>((size_t)M * N) : nullptr;   // raw_out as [feature][sample]: the seg sweep's rows are features
     if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small");
     // (the weight side first: it depends on no captured tensor -- inside a group that was handed a "capture done" event it runs,
     // with the candidate planes of the weights further down, while the capture passes are still on the GPU)
@@ -2424,6 +2480,10 @@ int linear_impl(const p4v_linear_desc* d, const float* W, const float* bias, con
     bool host_w_ok = false, host_a_ok = false;
     const int n_rounds = sg.full() ? d->search_round : 1;
     auto slot = [&](int round, int which) { return sg.full() ? round * 2 + which : 0; };   // granular call: one table
+    // granular call, desc.reserved bits 8..11 = 1 + b: the step of column / activation block b alone, and ITS tables
+    const int only_blk = sg.full() ? -1 : ((d->reserved >> 8) & 15) - 1;
+    if (only_blk >= ((sg.mask & ST_S1) ? nH : nA)) return fail(P4V_ERR_INVALID, "linear: block %d outside the layer's blocks", only_blk);
+    const int tab_blk = std::max(0, only_blk);       // the block whose score table and selections the call returns
     // Cosine on k_sweep6 (round 6): the layer as ONE GEMM in the orientation of the difference metrics (rows = samples, columns =
     // features), the register-stationary sweep with the cosine epilogues EPI_COS / EPI_COS_T; the V blocks are runs of 64-feature
     // slabs of k_finish_cos's table.  Otherwise (K > 768, blocks that are not whole slabs, variant 2048): k_sweep2 on the swapped
@@ -2450,7 +2510,7 @@ int linear_impl(const p4v_linear_desc* d, const float* W, const float* bias, con
         ps.scores_out = scores_out ? scores_out + ((long)slot(round, 0) * d->eq_n) * nV : nullptr;
         ps.scores_out_ld = nV;
         ps.best_out = best_out ? best_out + (long)slot(round, 0) * nV : nullptr;
-        if (h > 0) { ps.scores_out = nullptr; ps.best_out = nullptr; }  // tables of the first column block only
+        if (h != tab_blk) { ps.scores_out = nullptr; ps.best_out = nullptr; }  // tables of the first column block only (granular: of the one asked for)
         if (!cosm || cos6 || cos7) {
             ps.Z = 1; ps.Mrows = M; ps.Ncols = N;
             ps.row = x_operand(false, a_iv, 0);
@@ -2480,6 +2540,29 @@ int linear_impl(const p4v_linear_desc* d, const float* W, const float* bias, con
         }
         return ps;
     };
+    // the block step of the cosine seg sweep: side 1 = column block h of every V block (one score per V block), side 2 =
+    // activation block a (ONE score over all features); tables of block 0 only, as for the difference metrics
+    auto seg_cos_pass = [&](int round, int side, int blk) -> Pass {
+        const bool ws_ = side == 1;
+        sgp.side = side; sgp.ov_v = ws_ ? 0 : blk; sgp.ov_h = ws_ ? blk : 0;
+        sgp.cands = (ws_ ? w_cands : a_cands) + blk; sgp.cand_cs = ws_ ? nV * nH : nA; sgp.cand_hs = ws_ ? nH : 0;
+        Pass ps{};
+        ps.seg = &sgp; ps.i8 = true; ps.epi = EPI_COS; ps.eq_n = d->eq_n; ps.K = K;
+        ps.Z = nV; ps.Mrows = crb_rows; ps.Ncols = M;
+        ps.bias = bias; ps.bias_axis = 1; ps.bias_zs = crb_rows;
+        ps.O = Ot;
+        ps.cos_ZB = 1; ps.cos_ZV = nV; ps.cos_j_mode = ws_ ? 1 : 0;
+        ps.norm = 1.0 / (double)d->tokens;
+        ps.nj = ws_ ? nV : 1;
+        ps.cands = ws_ ? w_cands : a_cands; ps.cand_cs = sgp.cand_cs; ps.cand_js = sgp.cand_hs; ps.cand_off = blk;
+        ps.interval = ws_ ? w_iv : a_iv; ps.out_js = ws_ ? nH : 0; ps.out_off = blk;
+        if (blk == tab_blk) {
+            ps.scores_out = scores_out ? scores_out + ((long)slot(round, ws_ ? 0 : 1) * d->eq_n) * nV : nullptr;
+            ps.best_out = best_out ? best_out + (long)slot(round, ws_ ? 0 : 1) * nV : nullptr;
+        }
+        ps.scores_out_ld = nV;
+        return ps;
+    };
     if (sg.full()) {
         // The 100 candidate planes of the weights (8.5 GB per ViT-B calibration over its 48 Linear layers) need the weights and
         // their candidate table, nothing captured: packed here, before the call waits for its captured tensors.
@@ -2491,6 +2574,7 @@ int linear_impl(const p4v_linear_desc* d, const float* W, const float* bias, con
         CHK(q_wait_inputs(c));
         CHK(init_activation_side());
     }
+    if (segcos) CHK(enqueue(c, KERN(NchwRowsParams, k_nchw_to_rows), dim3(cdiv(N, 32), cdiv(M, 32), 1), dim3(256), 0, NchwRowsParams{O, M, N, Ot}));
     for (int round = 0; round < n_rounds; ++round) {
         // ================= weight search (linear.py:455-495) =================
         // With n_H > 1 the weight search is a coordinate descent over the column blocks: block h is swept with the other
@@ -2506,6 +2590,8 @@ int linear_impl(const p4v_linear_desc* d, const float* W, const float* bias, con
         for (int h = 0; h < nH && !skip_w && (sg.mask & ST_S1); ++h) {
             const float* wc = w_cands;
             int wc_cs = nV * nH;
+            if (only_blk >= 0 && h != only_blk) continue;
+            if (segcos) { Pass ps = seg_cos_pass(round, 1, h); CHK(run_pass(c, ps)); continue; }
             if (general && nH > 1) {
                 // candidates replace column block h only, the others keep the current interval (linear.py:468-469)
                 if (!c.dry) {
@@ -2529,6 +2615,8 @@ int linear_impl(const p4v_linear_desc* d, const float* W, const float* bias, con
             if (const auto* hit = memo_a.find(key)) { CHK(write_dev(c, a_iv, *hit)); skip_a = true; g_memo_hits++; host_a = *hit; host_a_ok = true; }
         }
         for (int a = 0; a < nA && !skip_a && (sg.mask & ST_S2); ++a) {
+            if (only_blk >= 0 && a != only_blk) continue;
+            if (segcos) { Pass sp = seg_cos_pass(round, 2, a); CHK(run_pass(c, sp)); continue; }
             Pass ps{};
             ps.i8 = i8; ps.twin = twin; ps.epi = epi; ps.wt_mode = wt_mode; ps.eq_n = d->eq_n; ps.K = K;
             const float* ac = a_cands;
@@ -2545,9 +2633,9 @@ int linear_impl(const p4v_linear_desc* d, const float* W, const float* bias, con
             ps.ecache = keep_planes ? &epi_a : nullptr;
             ps.nj = 1; ps.cands = a_cands; ps.cand_cs = nA; ps.cand_js = 0; ps.cand_off = a;
             ps.interval = a_iv; ps.out_js = 0; ps.out_off = a;
-            ps.scores_out = (scores_out && a == 0) ? scores_out + ((long)slot(round, 1) * d->eq_n) * nV : nullptr;
+            ps.scores_out = (scores_out && a == tab_blk) ? scores_out + ((long)slot(round, 1) * d->eq_n) * nV : nullptr;
             ps.scores_out_ld = nV;
-            ps.best_out = (best_out && a == 0) ? best_out + (long)slot(round, 1) * nV : nullptr;
+            ps.best_out = (best_out && a == tab_blk) ? best_out + (long)slot(round, 1) * nV : nullptr;
             if (!cosm || cos6 || cos7) {
                 ps.Z = 1; ps.Mrows = M; ps.Ncols = N;
                 ps.row = x_operand(true, ac, nA);
@@ -2860,25 +2948,7 @@ int matmul_blocks_impl(const p4v_matmul_desc* d, const MatMulBlocks& mb, const f
     g.A = A; g.B = B;
     for (int i = 0; i < 4; ++i) { g.a_st[i] = d->a_stride[i]; g.b_st[i] = d->b_stride[i]; }
     g.Aq = 1 << (d->A_bit - 1); g.Bq = 1 << (d->B_bit - 1); g.sos = d->sos != 0;
-    {   // K cut at every multiple of A's column-block width and of B's row-block width: S <= n_H_A + n_V_B - 1 segments
-        if (K >= 16384) return fail(P4V_ERR_UNSUPPORTED, "matmul: K < 16384 with sub-blocks");
-        std::vector<int> cuts{0};
-        for (int i = 1; i < nHA; ++i) if (i * g.ccA < K) cuts.push_back(i * g.ccA);
-        for (int i = 1; i < nVB; ++i) if (i * g.crB < K) cuts.push_back(i * g.crB);
-        std::sort(cuts.begin(), cuts.end());
-        cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
-        g.seg.S = (int)cuts.size();
-        int dpos = 0;
-        for (int s = 0; s < g.seg.S; ++s) {
-            const int k1 = s + 1 < g.seg.S ? cuts[s + 1] : K;
-            g.seg.k0[s] = (short)cuts[s]; g.seg.d0[s] = (short)dpos;
-            g.ablk[s] = (unsigned char)(cuts[s] / g.ccA); g.bblk[s] = (unsigned char)(cuts[s] / g.crB);
-            dpos += (int)rup(k1 - cuts[s], 64);
-        }
-        for (int s = g.seg.S; s <= SEG_MAX; ++s) { g.seg.k0[s] = (short)K; g.seg.d0[s] = (short)dpos; }
-        g.Kseg = dpos;
-        if (g.Kseg / SW_BKB > SEG_KT_MAX) return fail(P4V_ERR_UNSUPPORTED, "matmul: K too large for the segment table");
-    }
+    CHK(seg_cut_k(g, "matmul"));
     const int nA = d->sos ? 1 : H * nVA * nHA, nB = H * nVB * nHB, ncand = d->eq_n + 1;
     unsigned* enc_A = c.ws.get<unsigned>((size_t)H * nVA * nHA);
     unsigned* enc_B = c.ws.get<unsigned>((size_t)nB);

@@ -4726,7 +4726,12 @@ __global__ __launch_bounds__(256) void k_pack_seg_g(GroupArgs<PackSegParams> a) 
 // in LDS.  Both tables are filled once with the current intervals; the searched side is refilled per candidate with the block
 // (ov_v, ov_h) on cands[c][head].  At a segment's last k-tile every wave flushes sum = fma((float)acc, rs * cs, sum), acc = 0.
 // TWIN: the split-of-softmax low-range plane accumulates beside the high-range one and flushes with the scalar A_interval (the
-// class has no blocks on A, matmul.py:586-588).  Epilogues: the difference metrics and EPI_FWD (cosine is not offered).
+// class has no blocks on A, matmul.py:586-588).  Epilogues: the difference metrics and EPI_FWD, and (not TWIN) EPI_COS.
+// EPI_COS is the Linear layer with column / activation blocks, swapped as the head-wise cosine sweeps are: rows = the features of
+// V block z (A = W, head = z), columns = samples (B = x, `b_shared`: one plane and one scale table [nVB][nHB] for every head),
+// O = raw_out TRANSPOSED to [feature][sample] (the host does that once per call), bias[z * bias_zs + m] added to row m.  A lane
+// owns one sample and 32 features: per candidate it leaves (dot(raw, sim), |sim|^2, |raw|^2) over the wave's 64 features in
+// k_finish_cos's table [C][Z][ceil(M / 64)][Np][3] (p_cs / p_zs); padding rows carry raw = bias = 0 and add nothing.
 struct SweepSegParams {
     const int* crange;
     const void* A; long a_cs, a_zs;
@@ -4739,10 +4744,12 @@ struct SweepSegParams {
     int side, ov_v, ov_h;                      // 0: nothing searched (forward), 1: A block (ov_v, ov_h), 2: B block
     float rs_const; const float* rs2;          // TWIN: high-range row scale 1/(q-1); low-range row scale *rs2 (A_interval)
     const float* O; const float* Wt; int wt_mode;
+    int b_shared;                              // B's intervals carry no head index (ivB[vB][hB]); the host also passes b_zs = 0
     long o_zs, o_ms;
     int M, N, Z, c0, c1;
     float* part; long p_cs, p_zs; int Np, mtiles, ntiles;
     float* store;                              // EPI_FWD output [Z][M][N]
+    const float* bias; long bias_zs;           // EPI_COS: bias of row m (nullptr: none)
     SegTable seg;
     unsigned char ablk[SEG_MAX], bblk[SEG_MAX];   // hA(s), vB(s)
 };
@@ -4796,7 +4803,7 @@ __device__ __forceinline__ void k_sweep_seg_body(const SweepSegParams& p, const 
     auto fill_cols = [&](int c) {
         for (int i = tid; i < S * 128; i += 512) {
             const int s = i >> 7, h = min(min(n0 + (i & 127), p.N - 1) / p.n_div, p.nHB - 1), v = sblk[SEG_MAX + s];
-            float val = p.ivB[(head * p.nVB + v) * p.nHB + h];
+            float val = p.ivB[((p.b_shared ? 0 : head) * p.nVB + v) * p.nHB + h];
             if (c >= 0 && p.side == 2 && v == p.ov_v && h == p.ov_h) val = p.cands[(long)c * p.cand_cs + head * p.cand_hs];
             cs[i] = val;
         }
@@ -4809,7 +4816,31 @@ __device__ __forceinline__ void k_sweep_seg_body(const SweepSegParams& p, const 
     float u[2][16], w[2][16];
     const int n = n0 + wc * 32 + l31;
     const bool ncol_ok = n < p.N;
-    if constexpr (EPI != EPI_FWD) {
+    float oo = 0.0f;        // EPI_COS: |raw|^2 over the wave's 64 features of this lane's sample
+    if constexpr (EPI == EPI_COS) {
+        // u = raw_out, w = the bias of the row; both 0 on padding rows and columns (k_sweep's cosine prologue)
+        const long ncol_off = (long)z * p.o_zs + min(n, p.N - 1);
+        const float* biasz = p.bias ? p.bias + (long)z * p.bias_zs : nullptr;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int mc = min(m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g, p.M - 1);
+                u[i][r] = p.O[ncol_off + (long)mc * p.o_ms];
+                w[i][r] = biasz ? biasz[mc] : 0.0f;
+            }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
+                const bool ok = ncol_ok && m < p.M;
+                u[i][r] = ok ? u[i][r] : 0.0f;
+                w[i][r] = ok ? w[i][r] : 0.0f;
+                oo = fmaf(u[i][r], u[i][r], oo);
+            }
+        oo += __shfl_xor(oo, 32);
+    } else if constexpr (EPI != EPI_FWD) {
         const long ncol_off = (long)z * p.o_zs + min(n, p.N - 1);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -4923,6 +4954,23 @@ __device__ __forceinline__ void k_sweep_seg_body(const SweepSegParams& p, const 
                         const int m = m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
                         if (ncol_ok && m < p.M) p.store[(long)z * p.M * p.N + (long)m * p.N + n] = sum[i][r];
                     }
+            } else if constexpr (EPI == EPI_COS) {
+                float dot = 0.0f, nn = 0.0f;
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float o_sim = sum[i][r] + w[i][r];
+                        dot = fmaf(u[i][r], o_sim, dot);
+                        nn = fmaf(o_sim, o_sim, nn);
+                    }
+                dot += __shfl_xor(dot, 32);
+                nn += __shfl_xor(nn, 32);
+                const int slab = mt * 2 + wr;          // the table has ceil(M / 64) slabs: a wave of padding rows only has none
+                if (g == 0 && slab * 64 < p.M) {
+                    float* q = p.part + (long)c * p.p_cs + (long)z * p.p_zs + ((long)slab * p.Np + n0 + wc * 32 + l31) * 3;
+                    q[0] = dot; q[1] = nn; q[2] = oo;
+                }
             } else {
                 float colsum = 0.0f;
 #pragma unroll

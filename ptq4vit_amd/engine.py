@@ -433,19 +433,29 @@ class LinearStepper(_Stepper):
         self._call("p4v_amax_init_linear", self.weight, self.x, w_iv, a_iv)
         return w_iv, a_iv
 
-    def search_w(self, w_cands, w_interval, a_interval, want_scores=False):
+    def _call_block(self, block, name, *args):
+        """One granular search call; `block`: the step of that column / activation block alone (desc.reserved bits 8..11), whose
+        score table the call then returns -- None: every block in turn, the tables of block 0."""
+        base = self.d.reserved
+        self.d.reserved = base | (0 if block is None else (int(block) + 1) << 8)
+        try:
+            self._call(name, *args)
+        finally:
+            self.d.reserved = base
+
+    def search_w(self, w_cands, w_interval, a_interval, want_scores=False, block=None):
         """Returns (new w_interval [n_V*n_H], scores [eq_n][n_V] | None, best [n_V] | None)."""
         w_iv = _flat(w_interval, self.dev).clone()
         scores, best = self._tables(want_scores, self.n_V)
-        self._call("p4v_linear_search_w", self.weight, self.bias, self.x, self.out, self.grad,
-                   _flat(w_cands, self.dev, self.d.eq_n + 1), w_iv, _flat(a_interval, self.dev), scores, best)
+        self._call_block(block, "p4v_linear_search_w", self.weight, self.bias, self.x, self.out, self.grad,
+                         _flat(w_cands, self.dev, self.d.eq_n + 1), w_iv, _flat(a_interval, self.dev), scores, best)
         return w_iv, scores, best
 
-    def search_a(self, a_cands, w_interval, a_interval, want_scores=False):
+    def search_a(self, a_cands, w_interval, a_interval, want_scores=False, block=None):
         a_iv = _flat(a_interval, self.dev).clone()
         scores, best = self._tables(want_scores, self.n_V)
-        self._call("p4v_linear_search_a", self.weight, self.bias, self.x, self.out, self.grad,
-                   _flat(a_cands, self.dev, self.d.eq_n + 1), _flat(w_interval, self.dev), a_iv, scores, best)
+        self._call_block(block, "p4v_linear_search_a", self.weight, self.bias, self.x, self.out, self.grad,
+                         _flat(a_cands, self.dev, self.d.eq_n + 1), _flat(w_interval, self.dev), a_iv, scores, best)
         return a_iv, scores, best
 
 

@@ -4,6 +4,8 @@ Hot classes (reference linear.py:349-642): PTQSLBatchingQuantLinear, PostGeluPTQ
 Their ``calibration_step2()`` hands weight / bias / raw_input / raw_out / raw_grad to
 ``p4v_linear_calibrate`` (include/ptq4vit_hip.h): min-max init, candidate grid, the alternating
 weight / activation search with the MFMA candidate sweep, argmax + gather all run on the GPU.
+Weight column blocks / activation blocks (n_H, n_a > 1) search on fp32 candidate planes with the difference metrics and on
+K-segmented int8 planes with the cosine metric; the post-GELU twin with cosine and blocks is refused by the engine.
 """
 import torch
 import torch.nn as nn
