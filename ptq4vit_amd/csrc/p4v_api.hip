@@ -641,10 +641,6 @@ template <typename T, bool TWIN> int launch_sweep_epi(Ctx& c, const SweepParams&
 }
 
 // k_sweep2g: large K, column operand expanded, row operand invariant (weight search): two candidates per pass
-bool sweep2g_ok(const SweepParams& p) {
-    return p.b_cs != 0 && p.a_cs == 0 && p.ktiles >= 16 && (p.c1 - p.c0) >= 2 && p.o_bs == 0 && p.o_nbs == 0;
-}
-
 template <bool TWIN> int launch_sweep2g_epi(Ctx& c, const SweepParams& p, int epi, int cgroups, const StatInfo* si) {
     const int per = 2 * cdiv(p.c1 - p.c0, 2 * cgroups);
     const size_t lds = (size_t)SW2_NS * (TWIN ? 4 : 3) * SW2_TILE + (size_t)per * 8 * sizeof(float) * (TWIN ? 3 : 2);
@@ -696,6 +692,14 @@ inline StatInfo stat_info(int kind, double macs, double alg, int gx, int gz, dou
     return StatInfo{kind, macs * g_exec_frac, alg * g_exec_frac, g_stage, gx, gz, bytes};
 }
 
+// The sweep kernel family of a pass, decided once by plan_sweep ("pass -> kernel": the same order), and the
+// family number of its launch records (p4v_launch_record.kind)
+enum SweepKind { SK_BOUND, SK_SWEEP6, SK_SWEEP5, SK_SWEEP7, SK_SWEEP7_TWIN, SK_SWEEP7_MERGED, SK_SWEEP9, SK_SWEEP8, SK_SWEEP2G, SK_SWEEP2,
+                 SK_GENERIC_I8, SK_GENERIC_F32, SK_COUNT };
+constexpr int SWEEP_RECORD_KIND[SK_COUNT] = {12, 2, 5, 3, 4, 4, 6, 7, 8, 9, 0, 1};
+inline bool sweep_stationary(SweepKind k) { return k == SK_SWEEP6 || k == SK_SWEEP5; }
+inline bool sweep_large_k(SweepKind k) { return k == SK_SWEEP7 || k == SK_SWEEP7_TWIN || k == SK_SWEEP7_MERGED; }
+
 int launch_sweep5(Ctx& c, const Sweep3Params& p, int epi, int cgroups) {
     if (c.dry) return 0;
     const int per = 2 * cdiv(p.c1 - p.c0, 2 * cgroups);
@@ -704,7 +708,7 @@ int launch_sweep5(Ctx& c, const Sweep3Params& p, int epi, int cgroups) {
 #ifdef P4V_TRACE
     CHK(trace_attach(const_cast<Sweep3Params&>(p)));
 #endif
-    const StatInfo si = stat_info(5, (double)p.stiles * 128 * (double)p.ttiles * 128 * (double)p.ldk * (p.c1 - p.c0), g_alg_macs_cand * (p.c1 - p.c0),
+    const StatInfo si = stat_info(SWEEP_RECORD_KIND[SK_SWEEP5], (double)p.stiles * 128 * (double)p.ttiles * 128 * (double)p.ldk * (p.c1 - p.c0), g_alg_macs_cand * (p.c1 - p.c0),
                                   (int)grid.x, (int)grid.z, g_alg_bytes);
     const StatInfo* sp = &si;
     P4V_EPI4(epi, CHK(enqueue(c, KERN_T(Sweep3Params, k_sweep5, E), grid, block, lds, p, sp)); break)
@@ -775,7 +779,7 @@ int launch_sweep6_part(Ctx& c, const Sweep3Params& p, int epi, int cgroups) {
 #endif
     // one record per kernel launch; a split sweep books its work (and the pass's bytes) in proportion to the tiles of each part
     const double share = (double)grid.x / ((double)p.stiles * p.ttiles);
-    const StatInfo si = stat_info(2, share * (double)p.stiles * 256 * (double)p.ttiles * 64 * (double)p.ldk * (p.c1 - p.c0),
+    const StatInfo si = stat_info(SWEEP_RECORD_KIND[SK_SWEEP6], share * (double)p.stiles * 256 * (double)p.ttiles * 64 * (double)p.ldk * (p.c1 - p.c0),
                                   share * g_alg_macs_cand * (p.c1 - p.c0), (int)grid.x, (int)grid.z, share * g_alg_bytes);
     const StatInfo* sp = &si;
     int r;
@@ -793,22 +797,7 @@ int launch_sweep6_part(Ctx& c, const Sweep3Params& p, int epi, int cgroups) {
     return 0;
 }
 
-// k_sweep9: single-k-tile sweeps on 16 x 16 blocks (part layout [C][Z][halves * 8], set up by run_pass)
-int sweep9_halves(const SweepParams& p, bool twin, int epi) {
-    if (p.ktiles != 1 || twin || (p.a_cs == 0) == (p.b_cs == 0) || epi == EPI_STORE || epi == EPI_FWD || epi == EPI_COS) return 0;
-    if (p.sb_mode == 1 && p.s_cs > 1) return 0;
-    if (p.bias_axis != 0 || (g_variant & 524288)) return 0;
-    // one ring stage holds the whole streamed operand of a candidate: 256 rows x 64 B (SW9_STAGE); beyond that k_sweep8
-    if ((p.a_cs == 0 ? p.N : p.M) > 256) return 0;
-    const long nb = (long)cdiv(p.M, 16) * cdiv(p.N, 16);
-    const int halves = (int)cdiv(nb, (long)SW9_NW * SW9_NB);
-    if (halves > 32 / SW9_NW) return 0;
-    // worth it where the 128 x 128 tiles of k_sweep8 carry padding: Swin windows (144 tokens: 3.2 x the 16-granular area, q.k^T
-    // search 9.2 -> 6.0 ms per module; 49 tokens: 4 x) and, by 5 %, the 197 tokens of ViT / DeiT (1.5 x: 433 -> 410 us per pass).
-    // Variant 1048576 forces it for A/B runs, 524288 disables it.
-    const double waste = (double)rup(p.M, 128) * rup(p.N, 128) / ((double)rup(p.M, 16) * rup(p.N, 16));
-    return (waste >= 1.4 || (g_variant & 1048576)) ? halves : 0;
-}
+// k_sweep9: single-k-tile sweeps on 16 x 16 blocks (part layout [C][Z][halves * 8], set up by plan_sweep)
 template <bool ROWS_FIXED> int launch_sweep9_epi(Ctx& c, const SweepParams& p, int epi, int cgroups, const StatInfo* si) {
     const int per = cdiv(p.c1 - p.c0, cgroups);
     const size_t lds = (size_t)SW9_NS * SW9_STAGE + (size_t)per * SW9_NW * sizeof(float) * 2;
@@ -817,11 +806,6 @@ template <bool ROWS_FIXED> int launch_sweep9_epi(Ctx& c, const SweepParams& p, i
 }
 
 // k_sweep8: single k-tile (K <= 64) int8 sweep with the fixed operand's fragments in registers: q.k^T of every ViT / Swin
-bool sweep8_ok(const SweepParams& p, bool twin, int epi) {
-    return p.ktiles == 1 && !twin && (p.a_cs == 0) != (p.b_cs == 0) && epi != EPI_STORE && epi != EPI_FWD && epi != EPI_COS &&
-           !(g_variant & 65536);
-}
-
 // (no padding skip as in k_sweep2 -- wave parts without a valid element doing no MFMA / epilogue work: measured slower at 197
 // tokens, 4 of 32 parts padding: 459 vs 428 us, AND at the 144 tokens of a Swin window, 17 of 32 parts: 10.0 vs 9.3 ms per
 // module -- a single-k-tile candidate is paced by its ring step (DMA landing + barrier), not by the MFMAs and the epilogue it
@@ -852,37 +836,56 @@ int launch_sweep7(Ctx& c, const Sweep7Params& p, int twin, int epi, int cgroups)
     q.cgroups = cgroups;
     dim3 grid(p.rtiles * p.ctiles * cgroups, 1, 1);
     // (twin: 128 samples x 2 planes)
-    const StatInfo si = stat_info(twin ? 4 : 3, (double)p.rtiles * 256 * (double)p.ctiles * 256 * (double)p.ldk * nc, g_alg_macs_cand * nc,
+    const StatInfo si = stat_info(SWEEP_RECORD_KIND[twin ? SK_SWEEP7_TWIN : SK_SWEEP7], (double)p.rtiles * 256 * (double)p.ctiles * 256 * (double)p.ldk * nc, g_alg_macs_cand * nc,
                                   (int)grid.x, (int)grid.z, g_alg_bytes);
     const StatInfo* sp = &si;
     return twin == 2 ? launch_sweep7_epi<2>(c, q, epi, grid, lds, sp) : twin ? launch_sweep7_epi<1>(c, q, epi, grid, lds, sp) : launch_sweep7_epi<0>(c, q, epi, grid, lds, sp);
 }
 
-int launch_sweep(Ctx& c, const SweepParams& p, bool i8, bool twin, int epi, bool fast = false, int cgroups = 1) {
+// the tiled sweeps (one SweepParams): the launch of `kind` and its record, whose grid_x is the arm's own grid
+int launch_sweep(Ctx& c, const SweepParams& p, SweepKind kind, bool twin, int epi, int cgroups) {
     if (c.dry) return 0;
-    // kernel family of the record (p4v_launch_record.kind): 12 k_bound, 6 k_sweep9, 7 k_sweep8, 8 k_sweep2g, 9 k_sweep2, 0 / 1 generic int8 / fp32
-    const int kind = (fast && p.bound) ? 12 : (fast && p.halves > 0) ? 6 : (fast && sweep8_ok(p, twin, epi)) ? 7 :
-                     (fast && epi != EPI_COS && sweep2g_ok(p)) ? 8 : fast ? 9 : i8 ? 0 : 1;
-    const double kelems = (double)p.ldk / (i8 ? 1 : 4);
-    const StatInfo si = stat_info(kind, (double)p.mtiles * SW_BM * (double)p.ntiles * SW_BN * kelems * p.Z * (p.c1 - p.c0) * (twin ? 2 : 1),
-                                  g_alg_macs_cand * (p.c1 - p.c0),
-                                  (fast && p.bound) ? p.mtiles * p.ntiles * (b1_previous() ? 2 : 1) : (fast && p.halves > 0) ? p.halves : p.mtiles * p.ntiles, cgroups, g_alg_bytes);
-    const StatInfo* sp = &si;
-    if (fast && p.bound) {
-        const dim3 block(256);
-        if (b1_previous()) {                                       // 128 x 64 workgroup tiles, 64 x 32 per wave (the comparison path)
-            const dim3 grid(p.mtiles * p.ntiles * 2);
-            P4V_EPI4(epi, return enqueue(c, KERN_T(SweepParams, k_bound, E, 1), grid, block, 0, p, sp))
+    const double kelems = (double)p.ldk / (kind == SK_GENERIC_F32 ? 4 : 1);
+    const int tiles = p.mtiles * p.ntiles;
+    auto record = [&](int gx) {
+        return stat_info(SWEEP_RECORD_KIND[kind], (double)p.mtiles * SW_BM * (double)p.ntiles * SW_BN * kelems * p.Z * (p.c1 - p.c0) * (twin ? 2 : 1),
+                         g_alg_macs_cand * (p.c1 - p.c0), gx, cgroups, g_alg_bytes);
+    };
+    switch (kind) {
+        case SK_BOUND: {
+            // 128 x 128 workgroup tiles, 64 x 64 per wave; the comparison path (tuning 12 = 4): 128 x 64 tiles, 64 x 32 per wave
+            const bool prev = b1_previous();
+            const StatInfo si = record(tiles * (prev ? 2 : 1));
+            const dim3 grid(tiles * (prev ? 2 : 1)), block(256);
+            if (prev) P4V_EPI4(epi, return enqueue(c, KERN_T(SweepParams, k_bound, E, 1), grid, block, 0, p, &si))
+            P4V_EPI4(epi, return enqueue(c, KERN_T(SweepParams, k_bound, E, 2), grid, block, 0, p, &si))
         }
-        const dim3 grid(p.mtiles * p.ntiles);                      // 128 x 128 workgroup tiles, 64 x 64 per wave
-        P4V_EPI4(epi, return enqueue(c, KERN_T(SweepParams, k_bound, E, 2), grid, block, 0, p, sp))
+        case SK_SWEEP9: {
+            const StatInfo si = record(p.halves);
+            return p.a_cs == 0 ? launch_sweep9_epi<true>(c, p, epi, cgroups, &si) : launch_sweep9_epi<false>(c, p, epi, cgroups, &si);
+        }
+        case SK_SWEEP8: {
+            const StatInfo si = record(tiles);
+            return p.a_cs == 0 ? launch_sweep8_epi<true>(c, p, epi, cgroups, &si) : launch_sweep8_epi<false>(c, p, epi, cgroups, &si);
+        }
+        case SK_SWEEP2G: {
+            const StatInfo si = record(tiles);
+            return twin ? launch_sweep2g_epi<true>(c, p, epi, cgroups, &si) : launch_sweep2g_epi<false>(c, p, epi, cgroups, &si);
+        }
+        case SK_SWEEP2: {
+            const StatInfo si = record(tiles);
+            return twin ? launch_sweep2_epi<true>(c, p, epi, cgroups, &si) : launch_sweep2_epi<false>(c, p, epi, cgroups, &si);
+        }
+        case SK_GENERIC_I8: {
+            const StatInfo si = record(tiles);
+            return twin ? launch_sweep_epi<int8_t, true>(c, p, epi, cgroups, &si) : launch_sweep_epi<int8_t, false>(c, p, epi, cgroups, &si);
+        }
+        case SK_GENERIC_F32: {
+            const StatInfo si = record(tiles);
+            return twin ? launch_sweep_epi<float, true>(c, p, epi, cgroups, &si) : launch_sweep_epi<float, false>(c, p, epi, cgroups, &si);
+        }
+        default: return fail(P4V_ERR_INVALID, "launch_sweep: family %d has a launcher of its own", (int)kind);
     }
-    if (fast && p.halves > 0) return p.a_cs == 0 ? launch_sweep9_epi<true>(c, p, epi, cgroups, sp) : launch_sweep9_epi<false>(c, p, epi, cgroups, sp);
-    if (fast && sweep8_ok(p, twin, epi)) return p.a_cs == 0 ? launch_sweep8_epi<true>(c, p, epi, cgroups, sp) : launch_sweep8_epi<false>(c, p, epi, cgroups, sp);
-    if (fast && epi != EPI_COS && sweep2g_ok(p)) return twin ? launch_sweep2g_epi<true>(c, p, epi, cgroups, sp) : launch_sweep2g_epi<false>(c, p, epi, cgroups, sp);
-    if (fast) return twin ? launch_sweep2_epi<true>(c, p, epi, cgroups, sp) : launch_sweep2_epi<false>(c, p, epi, cgroups, sp);
-    if (i8) return twin ? launch_sweep_epi<int8_t, true>(c, p, epi, cgroups, sp) : launch_sweep_epi<int8_t, false>(c, p, epi, cgroups, sp);
-    return twin ? launch_sweep_epi<float, true>(c, p, epi, cgroups, sp) : launch_sweep_epi<float, false>(c, p, epi, cgroups, sp);
 }
 
 int launch_finish(Ctx& c, const FinishParams& p) {
@@ -1043,6 +1046,12 @@ bool dual_pack_ok(const PackParams& a, const PackParams& b) {
            a.s_z == b.s_z && a.s_z2 == b.s_z2 && a.zdiv == b.zdiv;
 }
 
+int launch_pass_select(Ctx& c, const Pass& ps, const float* scores) {
+    SelectParams sl{scores, ps.eq_n, ps.nj, ps.cands, ps.cand_cs, ps.cand_js, ps.cand_off, ps.interval, ps.out_js,
+                    ps.out_off, ps.aux_out, ps.aux_div, ps.scores_out, ps.scores_out_ld, ps.best_out};
+    return launch_select(c, sl);
+}
+
 // ---- the sub-block pass (MatMul; cosine Linear with column / activation blocks): k_pack_seg planes, k_sweep_seg, then the
 // common finish (k_finish; EPI_COS: k_finish_cos) and selection -----------------------------------------------------------------
 int launch_pack_seg(Ctx& c, PackSegParams p) {
@@ -1150,426 +1159,533 @@ int run_pass_seg(Ctx& c, Pass& ps) {
         FinishParams fp{part, p_cs, p_zs, Np, MT, Z, N, ps.eq_n, ps.j_mode, std::max(1, ps.j_div), ps.nj, ps.norm, scores, nullptr};
         CHK(launch_finish(c, fp));
     }
-    SelectParams sl{scores, ps.eq_n, ps.nj, ps.cands, ps.cand_cs, ps.cand_js, ps.cand_off, ps.interval, ps.out_js,
-                    ps.out_off, ps.aux_out, ps.aux_div, ps.scores_out, ps.scores_out_ld, ps.best_out};
-    CHK(launch_select(c, sl));
+    CHK(launch_pass_select(c, ps, scores));
     c.ws.off = mark;
     return 0;
 }
 
-int run_pass(Ctx& c, Pass& ps) {
-    if (ps.seg) return run_pass_seg(c, ps);
-    const int esz = ps.i8 ? 1 : 4;
-    g_alg_macs_cand = (double)ps.Mrows * ps.Ncols * ps.K * ps.Z;
-    // SURVEY.md s8-d3: every cached tensor read once per search pass -- both operands in fp32 as captured, raw_out and the metric weight
-    g_alg_bytes = 4.0 * ((double)ps.Mrows * ps.K * (ps.row_zs_shared ? 1 : ps.Z) + (double)ps.Ncols * ps.K * (ps.col_zs_shared ? 1 : ps.Z)) +
-                  (ps.G ? 8.0 : 4.0) * (double)ps.Mrows * ps.Ncols * ps.Z;
-    const int Kp = (int)rup(ps.K, 64 / esz);          // 64-byte k-tiles
-    // stationary-operand sweeps (k_sweep6 / k_sweep5): Linear layers whose invariant operand tile (128 x K int8) fits in LDS
-    const bool blocks64 = (ps.s_cs == 1 || ps.sb_div % 64 == 0) &&
-                          (ps.j_mode == 0 || (ps.j_mode == 1 && (ps.nj == 1 || ps.j_div % 64 == 0)));
-    // stage B1 (one candidate over all samples): k_bound -- rows = samples, columns = features of a plain [M][N] layer, whole
-    // 32-column groups inside one score block (the partial-sum table of the fast sweeps)
-    const bool bound = ps.bound_kernel && ps.i8 && !ps.twin && ps.Z == 1 && !ps.store_out && ps.epi != EPI_COS && !g_force_v1 &&
-                       ps.o_bs == 0 && ps.o_nbs == 0 && ps.bias_axis == 0 && (ps.sb_mode == 0 || ps.sb_mode == 1) &&
-                       (ps.j_mode == 0 || (ps.j_mode == 1 && (ps.nj == 1 || ps.j_div % 32 == 0))) &&
-                       (ps.sb_mode != 1 || ps.s_cs == 1 || ps.sb_div % 32 == 0) && (ps.eq_n == 1 || ps.crange);
-    const bool stat_ok = !bound && !ps.store_out && ps.i8 && !ps.twin && (ps.epi != EPI_COS || ps.cos6) && !g_force_v1 && !(g_variant & 4) && ps.Z == 1 &&
-                         ps.sb_mode == 1 && blocks64 && (ps.row.expanded != ps.col.expanded) &&
-                         rup(ps.K, 64) <= 768 && ps.o_bs == 0 && ps.o_nbs == 0;
-    const bool regs6 = stat_ok && sweep6_supported(Kp / SW_BKB);   // k_sweep6: stationary operand in registers
+// ---- the plan of a pass: which sweep kernel, and every size that follows from it ("pass -> kernel") -------------
+struct SweepPlan {
+    SweepKind kind;               // of a chunk of two or more candidates (chunk_kind)
+    bool pairs;                   // k_sweep5: two candidates per pass, chunks start on a candidate pair
+    bool merged7;                 // k_sweep7, post-GELU twin: ONE merged int8 plane k_pos + k_neg, split in registers
+    bool b64;                     // k_sweep2, batched, N <= 64: the column operand's planes hold 64 rows
+    bool fast_cos;                // cosine on k_sweep2 (three sums per sample and wave in k_sweep's table layout)
+    bool epi6_on;                 // k_sweep6 reads its epilogue operands from the fragment-order image (k_prep_epi6)
+    const int* rblk;              // Pass.crange_blk where the sweep honours it: k_sweep6's streaming tiles ...
+    const int* rblk_z;            // ... / the z planes of the tiled sweeps (score block = z % heads)
+    int esz, Kp, Mp, Np, NpB;     // operand element size; padded K / rows / columns; rows of the column operand's plane
+    long row_plane1, col_plane1, exp_plane;      // bytes of one (candidate's) plane
+    int chunk, chunk_al; size_t slack;           // candidates per chunk, padded to a pair; bytes the stationary rings read past the end
+    int cin_exp, cin_fix;         // PackParams.c_inner of the expanded / the fixed operand
+    size_t zero_bias_n, epi7_n;   // floats: the stationary sweeps' stand-in bias, k_sweep7's fragment-order epilogue operands
+    int s6_stiles, s6_ttiles; size_t epi6_bytes; // k_sweep6: 256-row stationary slabs, 64-row streaming tiles, their epilogue image
+    bool a_search;                // the row operand is expanded: stationary = weights (columns), streaming = activations
+    long part_cs;                 // floats of partial-sum table per candidate (the allocation)
+    long p_zs, p_cs; int NpP;     // the table the sweep writes: per z, per candidate, columns
+    int s3_groups, cos6_Sp;       // its column count on the stationary sweeps / the padded samples of a cos6 / cos7 table
+    int h9;                       // k_sweep9: halves per z
+    long fin_zs; int fin_ld, fin_rows, fin_cols, fin_jdiv;   // k_finish / k_finish_cos: the same table as they read it
+};
+
+// k_sweep9: where the 128 x 128 tiles of k_sweep8 carry padding (>= 1.4 x the 16-granular area; DESIGN_LOG round 15 has the
+// measurements).  Variant 1048576 forces it for A/B runs, 524288 disables it.  Returns the halves per z, 0: not this kernel.
+int sweep9_halves(const Pass& ps, int ktiles) {
+    const int epi = ps.epi;
+    if (ktiles != 1 || ps.twin || ps.row.expanded == ps.col.expanded || epi == EPI_STORE || epi == EPI_FWD || epi == EPI_COS) return 0;
+    if (ps.sb_mode == 1 && ps.s_cs > 1) return 0;
+    if (ps.bias_axis != 0 || (g_variant & 524288)) return 0;
+    // one ring stage holds the whole streamed operand of a candidate: 256 rows x 64 B (SW9_STAGE); beyond that k_sweep8
+    if ((ps.row.expanded ? ps.Mrows : ps.Ncols) > 256) return 0;
+    const long nb = (long)cdiv(ps.Mrows, 16) * cdiv(ps.Ncols, 16);
+    const int halves = (int)cdiv(nb, (long)SW9_NW * SW9_NB);
+    if (halves > 32 / SW9_NW) return 0;
+    const double waste = (double)rup(ps.Mrows, 128) * rup(ps.Ncols, 128) / ((double)rup(ps.Mrows, 16) * rup(ps.Ncols, 16));
+    return (waste >= 1.4 || (g_variant & 1048576)) ? halves : 0;
+}
+bool sweep8_ok(const Pass& ps, int ktiles) {
+    return ktiles == 1 && !ps.twin && ps.row.expanded != ps.col.expanded && ps.epi != EPI_STORE && ps.epi != EPI_FWD && ps.epi != EPI_COS &&
+           !(g_variant & 65536);
+}
+// (k_sweep2g also needs two candidates in the chunk: chunk_kind)
+bool sweep2g_ok(const Pass& ps, int ktiles) {
+    return ps.col.expanded && !ps.row.expanded && ktiles >= 16 && ps.o_bs == 0 && ps.o_nbs == 0 && ps.epi != EPI_COS;
+}
+
+int plan_sweep(const Ctx& c, const Pass& ps, SweepPlan& pl) {
+    pl = SweepPlan{};
+    const int esz = pl.esz = ps.i8 ? 1 : 4;
+    const int Kp = pl.Kp = (int)rup(ps.K, 64 / esz);          // 64-byte k-tiles
+    const int ktiles = Kp * esz / SW_BKB;
+    const long K64 = rup(ps.K, 64);
+    const bool cosm = ps.epi == EPI_COS, i8v2 = ps.i8 && !g_force_v1;
+    const bool one_expanded = ps.row.expanded != ps.col.expanded, plain_out = ps.o_bs == 0 && ps.o_nbs == 0;
+    // whole 32-column groups inside one scale block / one score block (the partial-sum table of the fast sweeps), whole 64-row
+    // tiles inside both (the stationary sweeps)
+    const bool scale32 = ps.sb_mode != 1 || ps.s_cs == 1 || ps.sb_div % 32 == 0;
+    const bool score32 = ps.j_mode == 0 || (ps.j_mode == 1 && (ps.nj == 1 || ps.j_div % 32 == 0));
+    const bool blocks64 = (ps.s_cs == 1 || ps.sb_div % 64 == 0) && (ps.j_mode == 0 || (ps.j_mode == 1 && (ps.nj == 1 || ps.j_div % 64 == 0)));
+    // -- the family, in the order of the table in DESIGN.md s5 --
+    // k_bound, stage B1 (one candidate over all samples): rows = samples, columns = features of a plain [M][N] layer
+    const bool bound = ps.bound_kernel && i8v2 && !ps.twin && ps.Z == 1 && !ps.store_out && !cosm && plain_out && ps.bias_axis == 0 &&
+                       (ps.sb_mode == 0 || ps.sb_mode == 1) && score32 && scale32 && (ps.eq_n == 1 || ps.crange);
+    // k_sweep6 / k_sweep5, stationary operand: Linear layers whose invariant operand tile (128 x K int8) fits in LDS; in registers
+    // (k_sweep6) for the K that sweep6_supported lists
+    const bool stat_ok = !bound && !ps.store_out && i8v2 && !ps.twin && (!cosm || ps.cos6) && !(g_variant & 4) && ps.Z == 1 &&
+                         ps.sb_mode == 1 && blocks64 && one_expanded && K64 <= 768 && plain_out;
+    const bool regs6 = stat_ok && sweep6_supported(ktiles);
     if (ps.cos6 && !regs6) return fail(P4V_ERR_UNSUPPORTED, "cosine pass planned for k_sweep6 does not qualify for it");
-    const bool pairs = stat_ok && !regs6;                // k_sweep5: two candidates per pass
-    // per-score-block candidate ranges: the weight search on k_sweep6 (a streaming 64-row tile lies in one scale block = one score
-    // block: blocks64); tuning 12 = 9 switches them off (A/B)
-    const int* rblk = (ps.crange && ps.crange_blk && regs6 && !ps.row.expanded && ps.j_mode == 1 && ps.nj == ps.s_cs &&
-                       ps.j_div == ps.sb_div && tune(TUNE_B1_PATH) != 9) ? ps.crange_blk : nullptr;
-    // ... and the head-wise searches of the attention matmuls (score block = z % heads: a workgroup works on one z)
-    const bool rblk_z_ok = ps.crange && ps.crange_blk && !stat_ok && ps.j_mode == 2 && ps.nj == ps.j_div && ps.Z > 1 && ps.epi != EPI_COS &&
-                           !ps.store_out && !bound && rup(ps.K, 64) < 1024 && tune(TUNE_B1_PATH) != 9;
-    const int* rblk_z = rblk_z_ok ? ps.crange_blk : nullptr;
-    const int PADR = SW_BM;
     // k_sweep7 (large K): rows = samples, columns = output features of a plain [M][N] layer; features contiguous in
     // raw_out / raw_grad and a multiple of 32 (dwordx4 epilogue loads, whole 32-feature blocks), every 32-feature block
     // inside one scale / score block, exactly one operand candidate-expanded, the twin's second plane not expanded
-    const bool big7 = !bound && !stat_ok && !ps.store_out && ps.i8 && (ps.epi != EPI_COS || ps.cos7) && !g_force_v1 && !(g_variant & 32768) && ps.Z == 1 &&
-                      rup(ps.K, 64) >= 1024 && rup(ps.K, 64) % 256 == 0 && (long)ps.Mrows * ps.o_ms * 4 < (1L << 32) && ps.sb_mode == 1 && (ps.s_cs == 1 || ps.sb_div % 32 == 0) &&
-                      (ps.j_mode == 0 || (ps.j_mode == 1 && (ps.nj == 1 || ps.j_div % 32 == 0))) &&
-                      ps.row.expanded != ps.col.expanded && !(ps.twin && (ps.row.expanded || ps.row2.expanded)) &&
-                      ps.o_bs == 0 && ps.o_nbs == 0 && ps.o_ns == 1 && ps.Ncols % 32 == 0 && ps.o_ms % 4 == 0 &&
+    const bool big7 = !bound && !stat_ok && !ps.store_out && i8v2 && (!cosm || ps.cos7) && !(g_variant & 32768) && ps.Z == 1 &&
+                      K64 >= 1024 && K64 % 256 == 0 && (long)ps.Mrows * ps.o_ms * 4 < (1L << 32) && ps.sb_mode == 1 && scale32 && score32 &&
+                      one_expanded && !(ps.twin && (ps.row.expanded || ps.row2.expanded)) &&
+                      plain_out && ps.o_ns == 1 && ps.Ncols % 32 == 0 && ps.o_ms % 4 == 0 &&
                       (c.dry || ((((unsigned long long)ps.O) | ((unsigned long long)(ps.G ? ps.G : ps.O))) & 15) == 0) && ps.bias_axis == 0;
-    // post-GELU twin on k_sweep7: ONE merged int8 plane k_pos + k_neg (disjoint supports), split in registers (variant
-    // 2097152 keeps the two-plane kernel for A/B runs)
-    const bool merged7 = big7 && ps.twin && ps.twin_disjoint && !(g_variant & 2097152);
     if (ps.cos7 && (!big7 || ps.twin)) return fail(P4V_ERR_UNSUPPORTED, "cosine pass planned for k_sweep7 does not qualify for it");
+    // the fast tiled sweeps (k_sweep2 and its kin); tuning 12 = 7 keeps the cosine on the generic kernel
+    const bool fast = !stat_ok && i8v2 && !cosm && scale32 && (score32 || ps.j_mode == 2);
+    pl.fast_cos = cosm && !stat_ok && !big7 && i8v2 && !ps.store_out && tune(TUNE_B1_PATH) != 7 && scale32;
+    pl.pairs = stat_ok && !regs6;
+    pl.merged7 = big7 && ps.twin && ps.twin_disjoint && !(g_variant & 2097152);   // (variant 2097152 keeps the two-plane kernel)
+    pl.kind = bound ? SK_BOUND : regs6 ? SK_SWEEP6 : stat_ok ? SK_SWEEP5 :
+              big7 ? (pl.merged7 ? SK_SWEEP7_MERGED : ps.twin ? SK_SWEEP7_TWIN : SK_SWEEP7) :
+              !(fast || pl.fast_cos) ? (ps.i8 ? SK_GENERIC_I8 : SK_GENERIC_F32) :
+              (fast && sweep8_ok(ps, ktiles)) ? SK_SWEEP8 : (fast && sweep2g_ok(ps, ktiles)) ? SK_SWEEP2G : SK_SWEEP2;
+    // per-score-block candidate ranges: the weight search on k_sweep6 (a streaming 64-row tile lies in one scale block = one score
+    // block: blocks64), and the head-wise searches of the attention matmuls (score block = z % heads: a workgroup works on one z);
+    // tuning 12 = 9 switches them off (A/B)
+    const bool blk_ranges = ps.crange && ps.crange_blk && tune(TUNE_B1_PATH) != 9;
+    pl.rblk = (blk_ranges && regs6 && !ps.row.expanded && ps.j_mode == 1 && ps.nj == ps.s_cs && ps.j_div == ps.sb_div) ? ps.crange_blk : nullptr;
+    pl.rblk_z = (blk_ranges && !stat_ok && ps.j_mode == 2 && ps.nj == ps.j_div && ps.Z > 1 && !cosm && !ps.store_out && !bound && K64 < 1024)
+                    ? ps.crange_blk : nullptr;
+    // -- operands and planes --
     // k_sweep6 tiles the stationary operand (the one that is NOT candidate-expanded) in 256-row slabs
-    const int Mp = (int)rup(ps.Mrows, big7 ? (ps.twin ? 128 : 256) : (regs6 && !ps.row.expanded) ? 256 : PADR);
-    const int Np = (int)rup(ps.Ncols, big7 ? 256 : (regs6 && !ps.col.expanded) ? 256 : PADR);
+    const int Mp = pl.Mp = (int)rup(ps.Mrows, big7 ? (ps.twin ? 128 : 256) : (regs6 && !ps.row.expanded) ? 256 : SW_BM);
+    const int Np = pl.Np = (int)rup(ps.Ncols, big7 ? 256 : (regs6 && !ps.col.expanded) ? 256 : SW_BM);
     // rows of the column operand's plane: the tile-padded count, except for the 64-column operands of the batched k_sweep2 passes
-    // (attn.v: B = V, N = head_dim = 64 -- 100 candidate planes of 384 x 128 x 256 B = 1.26 GB per ViT-B module half of which was
-    // padding: 630 us of k_pack and the stream of k_sweep2's stage A): k_sweep2 re-reads rows 0..63 for the tile's upper half
-    const bool fast_pre = !stat_ok && ps.i8 && ps.epi != EPI_COS && !(g_force_v1) &&
-                          (ps.sb_mode != 1 || ps.s_cs == 1 || ps.sb_div % 32 == 0) &&
-                          (ps.j_mode == 0 || ps.j_mode == 2 || (ps.j_mode == 1 && (ps.nj == 1 || ps.j_div % 32 == 0)));
-    const bool b64 = fast_pre && !big7 && !bound && ps.Z > 1 && !ps.col_zs_shared && ps.Ncols <= 64 && Kp / SW_BKB >= 2 && Kp / SW_BKB <= 15 &&
-                     !ps.store_out;
-    const int NpB = b64 ? 64 : Np;
-    const long row_plane = (long)ps.Z * Mp * Kp * esz, col_plane = (long)ps.Z * NpB * Kp * esz;
-    const long row_plane1 = ps.row_zs_shared ? (long)Mp * Kp * esz : row_plane;
-    const long col_plane1 = ps.col_zs_shared ? (long)NpB * Kp * esz : col_plane;
-    const long exp_plane = ps.row.expanded ? row_plane1 : col_plane1;
-    int chunk = (int)std::max<long>(1, std::min<long>(ps.eq_n, PLANE_BUDGET / std::max<long>(1, exp_plane)));
+    // (attn.v: B = V, N = head_dim = 64): k_sweep2 re-reads rows 0..63 for the tile's upper half
+    pl.b64 = fast && !big7 && !bound && ps.Z > 1 && !ps.col_zs_shared && ps.Ncols <= 64 && ktiles >= 2 && ktiles <= 15 && !ps.store_out;
+    pl.NpB = pl.b64 ? 64 : Np;
+    pl.row_plane1 = (long)(ps.row_zs_shared ? 1 : ps.Z) * Mp * Kp * esz;
+    pl.col_plane1 = (long)(ps.col_zs_shared ? 1 : ps.Z) * pl.NpB * Kp * esz;
+    pl.exp_plane = ps.row.expanded ? pl.row_plane1 : pl.col_plane1;
+    pl.chunk = (int)std::max<long>(1, std::min<long>(ps.eq_n, PLANE_BUDGET / std::max<long>(1, pl.exp_plane)));
+    if (pl.pairs && pl.chunk > 1) pl.chunk &= ~1;                          // chunks start on a candidate pair
+    pl.chunk_al = pl.pairs ? ((pl.chunk + 1) & ~1) : pl.chunk;             // an odd count is padded to a whole pair
+    pl.slack = stat_ok ? 4096 : 0;   // the stationary sweeps' rings keep issuing a few tiles past the last candidate
+    // k_sweep6 / k_sweep5 stream [row][candidate][K] / [row][pair][K]; k_sweep6's stationary operand and both operands of k_bound
+    // (one candidate each) are in MFMA-fragment order
+    pl.cin_exp = bound ? 3 : stat_ok ? (pl.pairs ? 2 : 1) : 0;
+    pl.cin_fix = (bound || regs6) ? 3 : 0;
+    pl.zero_bias_n = stat_ok ? (size_t)std::max(Mp, Np) : 0;
+    pl.epi7_n = big7 ? (size_t)Mp * Np * 2 : 0;
+    // k_sweep6: epilogue operands in fragment order, one image per 256 x 64 tile (8 bytes per output element) -- only where the
+    // in-place gather is uncoalesced: the activation search, whose tile is transposed; in the weight search the lanes of a load
+    // already read consecutive features
+    const bool a_search = pl.a_search = ps.row.expanded;
+    pl.s6_stiles = (a_search ? Np : Mp) / 256; pl.s6_ttiles = (int)cdiv(a_search ? ps.Mrows : ps.Ncols, 64);
+    pl.epi6_on = regs6 && (a_search || ps.cos6 || tune(TUNE_EPI6W) == 1);
+    pl.epi6_bytes = pl.epi6_on ? (size_t)pl.s6_stiles * pl.s6_ttiles * (256 * 64 * 8) : 0;
+    // -- the partial-sum table --
+    // k_sweep5 / k_sweep6: [slabs of 64 stationary rows][groups of 32 streaming rows]; k_sweep7: one row per (sample tile, wave
+    // column); the tiled sweeps: [64-row slab][column], columns in groups of 32 on the fast ones
+    const int MT = Mp / 64, s3_slabs = (a_search ? Np : Mp) / 64, s3_groups = pl.s3_groups = (a_search ? Mp : Np) / 32;
+    const int NpP = pl.NpP = stat_ok ? s3_groups : fast ? Np / 32 : Np;
+    const int MT7 = big7 ? (Mp / (ps.twin ? 128 : 256)) * 4 : 0;
+    // cosine on k_sweep6: k_finish_cos's table [64-feature slab][padded sample][3]; the samples are the streaming rows of the
+    // activation search (tiles of 64) and the stationary rows of the weight search (slabs of 256)
+    // ... on k_sweep7: slabs of 128 features (a wave's rows), the samples are the tile-padded rows
+    const bool cosp = ps.cos6 || ps.cos7;
+    const int cos_slab = ps.cos7 ? 128 : 64;
+    const int cos6_Sp = pl.cos6_Sp = ps.cos7 ? Mp : ps.cos6 ? (a_search ? (int)cdiv(ps.Mrows, 64) * 64 : Mp) : 0;
+    const int cos6_slabs = ps.cos7 ? Np / 128 : ps.cos6 ? (a_search ? Np / 64 : (int)cdiv(ps.Ncols, 64)) : 0;
+    pl.p_zs = cosp ? (long)cos6_slabs * cos6_Sp * 3 : stat_ok ? (long)s3_slabs * s3_groups : big7 ? (long)MT7 * NpP : (long)MT * NpP * (cosm ? 3 : 1);
+    pl.p_cs = pl.part_cs = pl.p_zs * ps.Z;
+    // k_sweep9 (before k_sweep8 in the order of the families) writes [C][Z][halves * SW9_NW] into the table allocated for the
+    // 128-tile layout, where that holds it
+    if (fast && !bound && !big7 && !ps.store_out && (ps.j_mode == 0 || ps.j_mode == 2)) {
+        const int h9 = sweep9_halves(ps, ktiles);
+        if (h9 > 0 && (long)h9 * SW9_NW <= pl.p_zs) { pl.kind = SK_SWEEP9; pl.h9 = h9; pl.p_zs = (long)h9 * SW9_NW; pl.p_cs = pl.p_zs * ps.Z; }
+    }
+    // -- the finish --
+    pl.fin_zs = pl.p_zs;
+    if (pl.kind == SK_SWEEP9) {
+        pl.fin_ld = pl.fin_cols = (int)pl.p_zs; pl.fin_rows = 1; pl.fin_jdiv = std::max(1, ps.j_div);
+    } else if (!cosm) {
+        // k_sweep5 / k_sweep6 activation search (j_mode 0) sums the whole table; its columns are sample groups
+        // (k_sweep6 skips streaming tiles that are pure padding: their table entries are never written)
+        pl.fin_ld = NpP; pl.fin_rows = stat_ok ? s3_slabs : big7 ? MT7 : MT;
+        pl.fin_cols = stat_ok ? (a_search ? (regs6 ? 2 * cdiv(ps.Mrows, 64) : s3_groups) : cdiv(ps.Ncols, 32)) : fast ? cdiv(ps.Ncols, 32) : ps.Ncols;
+        pl.fin_jdiv = std::max(1, (fast || stat_ok) && ps.j_mode == 1 ? cdiv(ps.j_div, 32) : ps.j_div);
+    } else {
+        // part layout [C][ZB][ZV][FS][Sp][3] with z = zb*ZV + zv
+        // (k_sweep6 / k_sweep7: Z = 1, the V blocks are consecutive runs of feature slabs of the one table; samples = the rows;
+        // a V block = sb_div features = sb_div / slab whole slabs, whatever the padding behind the last block)
+        const int FS = !cosp ? 0 : ps.cos_ZV == 1 ? cos6_slabs : ps.sb_div / cos_slab;
+        if (cosp) pl.fin_zs = (long)FS * cos6_Sp * 3;
+        pl.fin_ld = cosp ? cos6_Sp : Np; pl.fin_rows = cosp ? FS : MT; pl.fin_cols = cosp ? ps.Mrows : ps.Ncols;
+        pl.fin_jdiv = std::max(1, ps.cos_j_div);
+    }
+    return 0;
+}
+// what waits for the chunk: k_sweep2g works on candidate pairs, a single candidate goes to k_sweep2
+inline SweepKind chunk_kind(const SweepPlan& pl, int nc) { return (pl.kind == SK_SWEEP2G && nc < 2) ? SK_SWEEP2 : pl.kind; }
 
-    const size_t mark = c.ws.off;
-    const size_t slack = stat_ok ? 4096 : 0;   // the stationary sweeps' rings keep issuing a few tiles past the last candidate
-    if (pairs && chunk > 1) chunk &= ~1;                  // chunks start on a candidate pair
-    const int chunk_al = pairs ? ((chunk + 1) & ~1) : chunk;   // an odd count is padded to a whole pair
+// ---- the steps of a pass ------------------------------------------------------------------------------------------------------
+struct PassBufs {
+    char* row; char* row2; char* col;
+    float* part; float* S1; float* S2; float* scores; float* zero_bias; float* epi7; float* epi6;
+    PlaneCache* pc; EpiCache* ec;
+};
+int pass_workspace(Ctx& c, const Pass& ps, const SweepPlan& pl, PassBufs& b) {
     // (planes above PLANE_CACHE_MAX are re-packed every pass: with three search streams and two searched operands per
     // module the cache would otherwise add up to 6 x PLANE_BUDGET of workspace on the 128-image configurations)
-    PlaneCache* pc = (ps.cache && chunk >= ps.eq_n && !ps.store_out && ps.row.expanded != ps.col.expanded &&
-                      !(ps.twin && ps.row2.expanded) && exp_plane * (long)ps.eq_n <= PLANE_CACHE_MAX) ? ps.cache : nullptr;
+    PlaneCache* pc = b.pc = (ps.cache && pl.chunk >= ps.eq_n && !ps.store_out && ps.row.expanded != ps.col.expanded &&
+                             !(ps.twin && ps.row2.expanded) && pl.exp_plane * (long)ps.eq_n <= PLANE_CACHE_MAX) ? ps.cache : nullptr;
     if (pc && !pc->assigned) {
-        pc->buf = c.ws.get_top((size_t)exp_plane * chunk_al + slack);
+        pc->buf = c.ws.get_top((size_t)pl.exp_plane * pl.chunk_al + pl.slack);
         pc->done = reinterpret_cast<unsigned char*>(c.ws.get_top((size_t)rup(ps.eq_n, 256)));
         pc->assigned = true; pc->valid = false;
         if (!c.dry && pc->done) CHK(q_fill(c, pc->done, 0, (size_t)ps.eq_n));
     }
-    char* rowbuf = (pc && ps.row.expanded) ? pc->buf : c.ws.get<char>((size_t)row_plane1 * (ps.row.expanded ? chunk_al : 1) + slack);
-    char* row2buf = ps.twin ? c.ws.get<char>((size_t)row_plane1 * (ps.row2.expanded ? chunk : 1)) : nullptr;
-    char* colbuf = (pc && ps.col.expanded) ? pc->buf : c.ws.get<char>((size_t)col_plane1 * (ps.col.expanded ? chunk_al : 1) + slack);
-    const int MT = Mp / 64;
-    const bool cosm = ps.epi == EPI_COS;
-    // fast int8 sweep (k_sweep2): needs every 32-column group inside one scale block and one score block
-    const bool fast = !stat_ok && ps.i8 && !cosm && !(g_force_v1) &&
-                      (ps.sb_mode != 1 || ps.s_cs == 1 || ps.sb_div % 32 == 0) &&
-                      (ps.j_mode == 0 || ps.j_mode == 2 || (ps.j_mode == 1 && (ps.nj == 1 || ps.j_div % 32 == 0)));
-    // cosine on k_sweep2 (same stream and ring; three sums per sample and wave in k_sweep's table layout, k_finish_cos unchanged)
-    const bool fast_cos = cosm && !stat_ok && !big7 && ps.i8 && !ps.store_out && !g_force_v1 && tune(TUNE_B1_PATH) != 7 &&
-                          (ps.sb_mode != 1 || ps.s_cs == 1 || ps.sb_div % 32 == 0);
-    // k_sweep5 / k_sweep6 table: [slabs of 64 stationary rows][groups of 32 streaming rows]
-    const bool a_search = ps.row.expanded;          // stationary = weights (col operand), streaming = activations
-    const int s3_gw = 32;                           // streaming rows per wave (column group width of the table)
-    const int s3_slabs = (a_search ? Np : Mp) / 64, s3_groups = (a_search ? Mp : Np) / s3_gw;
-    const int NpP = stat_ok ? s3_groups : fast ? Np / 32 : Np;          // columns of the partial-sum table
-    const int MT7 = big7 ? (Mp / (ps.twin ? 128 : 256)) * 4 : 0;        // k_sweep7: one row per (sample tile, wave column)
-    // cosine on k_sweep6: k_finish_cos's table [64-feature slab][padded sample][3]; the samples are the streaming rows of the
-    // activation search (tiles of 64) and the stationary rows of the weight search (slabs of 256)
-    // ... on k_sweep7: slabs of 128 features (a wave's rows), the samples are the tile-padded rows
-    const int cos_slab = ps.cos7 ? 128 : 64;
-    const int cos6_Sp = ps.cos7 ? Mp : ps.cos6 ? (a_search ? (int)cdiv(ps.Mrows, 64) * 64 : Mp) : 0;
-    const int cos6_slabs = ps.cos7 ? Np / 128 : ps.cos6 ? (a_search ? Np / 64 : (int)cdiv(ps.Ncols, 64)) : 0;
-    const long p_zs = (ps.cos6 || ps.cos7) ? (long)cos6_slabs * cos6_Sp * 3 : stat_ok ? (long)s3_slabs * s3_groups : big7 ? (long)MT7 * NpP : (long)MT * NpP * (cosm ? 3 : 1);
-    const long p_cs = p_zs * ps.Z;
-    float* part = c.ws.get<float>((size_t)p_cs * ps.eq_n);
-    float* S1 = !ps.use_s1 ? nullptr : ps.S1_pre ? ps.S1_pre : c.ws.get<float>((size_t)ps.eq_n * ps.s_cs);
-    float* S2 = !(ps.use_s1 && ps.twin) ? nullptr : ps.S2_pre ? ps.S2_pre : c.ws.get<float>((size_t)ps.eq_n * ps.s_cs);
-    float* scores = ps.scores_keep ? ps.scores_keep : c.ws.get<float>((size_t)ps.eq_n * std::max(1, ps.nj));
-    float* zero_bias = (stat_ok && !ps.bias) ? c.ws.get<float>((size_t)std::max(Mp, Np)) : nullptr;
-    float* epi7 = big7 ? c.ws.get<float>((size_t)Mp * Np * 2) : nullptr;   // k_sweep7: epilogue operands in fragment order
-    // k_sweep6: epilogue operands in fragment order, one image per 256 x 64 tile (8 bytes per output element)
-    const int s6_stiles = (a_search ? Np : Mp) / 256, s6_ttiles = (int)cdiv(a_search ? ps.Mrows : ps.Ncols, 64);
-    // (only where the in-place gather is uncoalesced: the activation search, whose tile is transposed; in the weight search the
-    // lanes of a load already read consecutive features)
-    const bool epi6_on = regs6 && (a_search || ps.cos6 || tune(TUNE_EPI6W) == 1);
-    const size_t epi6_bytes = epi6_on ? (size_t)s6_stiles * s6_ttiles * (256 * 64 * 8) : 0;
-    EpiCache* ec = (epi6_on && ps.ecache && (long)epi6_bytes <= PLANE_CACHE_MAX) ? ps.ecache : nullptr;
+    b.row = (pc && ps.row.expanded) ? pc->buf : c.ws.get<char>((size_t)pl.row_plane1 * (ps.row.expanded ? pl.chunk_al : 1) + pl.slack);
+    b.row2 = ps.twin ? c.ws.get<char>((size_t)pl.row_plane1 * (ps.row2.expanded ? pl.chunk : 1)) : nullptr;
+    b.col = (pc && ps.col.expanded) ? pc->buf : c.ws.get<char>((size_t)pl.col_plane1 * (ps.col.expanded ? pl.chunk_al : 1) + pl.slack);
+    b.part = c.ws.get<float>((size_t)pl.part_cs * ps.eq_n);
+    b.S1 = !ps.use_s1 ? nullptr : ps.S1_pre ? ps.S1_pre : c.ws.get<float>((size_t)ps.eq_n * ps.s_cs);
+    b.S2 = !(ps.use_s1 && ps.twin) ? nullptr : ps.S2_pre ? ps.S2_pre : c.ws.get<float>((size_t)ps.eq_n * ps.s_cs);
+    b.scores = ps.scores_keep ? ps.scores_keep : c.ws.get<float>((size_t)ps.eq_n * std::max(1, ps.nj));
+    b.zero_bias = (pl.zero_bias_n && !ps.bias) ? c.ws.get<float>(pl.zero_bias_n) : nullptr;
+    b.epi7 = pl.epi7_n ? c.ws.get<float>(pl.epi7_n) : nullptr;
+    EpiCache* ec = b.ec = (pl.epi6_on && ps.ecache && (long)pl.epi6_bytes <= PLANE_CACHE_MAX) ? ps.ecache : nullptr;
     if (ec && !ec->assigned) {
-        ec->buf = c.ws.get_top(epi6_bytes);
+        ec->buf = c.ws.get_top(pl.epi6_bytes);
         ec->assigned = true; ec->valid = false;
     }
-    float* epi6 = !epi6_on ? nullptr : ec ? reinterpret_cast<float*>(ec->buf) : c.ws.get<float>(epi6_bytes / 4);
+    b.epi6 = !pl.epi6_on ? nullptr : ec ? reinterpret_cast<float*>(ec->buf) : c.ws.get<float>(pl.epi6_bytes / 4);
     if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", c.ws.off);
-    auto pack = [&](Operand& op, char* buf, int Rp, bool shared, int c0, int nc) -> int {
-        PackParams pk = op.pk;
-        pk.Rp = Rp; pk.Kp = Kp; pk.dst = buf;
-        pk.Z = shared ? 1 : ps.Z;
-        pk.C = op.expanded ? nc : 1;
-        pk.c_inner = (stat_ok && op.expanded) ? (pairs ? 2 : 1) : 0;   // k_sweep6 / k_sweep5 stream [row][candidate][K] / [row][pair][K]
-        if (regs6 && !op.expanded) pk.c_inner = 3;                     // k_sweep6: stationary operand in MFMA-fragment order
-        if (bound) pk.c_inner = 3;                                     // k_bound: both operands (one candidate each) in fragment order
-        if (op.expanded && pk.scales) pk.scales += (long)c0 * pk.sc_cs;
-        if (op.expanded && ps.crange) {       // pruned pass: only the candidate groups in range, and not the ones already kept
-            pk.crange = ps.crange; pk.c_base = c0;
-            pk.done = (pc && pc->done) ? pc->done : nullptr;
-        }
-        // what the host knows of the range (stages A2 / B2: the survivor range it read back; stage B1: its length)
-        int live_max = -1;
-        if (pk.crange && ps.host_hi > ps.host_lo) live_max = std::max(0, std::min(ps.host_hi, c0 + nc) - std::max(ps.host_lo, c0));
-        else if (pk.crange && ps.host_len > 0) live_max = std::min(ps.host_len, nc);
-        CHK(ps.i8 ? launch_pack<int8_t>(c, pk, live_max) : launch_pack<float>(c, pk, live_max));
-        return 0;      // (the finish of this pass flags the groups as packed: FinishParams.mark_done)
-    };
-    if (ps.pack_only) {
-        // every candidate of the expanded operand into the module's plane cache, in the layout this pass's sweep streams; the
-        // pass itself (and every later one of the module) then finds the plane packed
-        if (pc && !pc->valid && ps.row.expanded != ps.col.expanded && !ps.crange) {
-            if (ps.row.expanded) CHK(pack(ps.row, rowbuf, Mp, ps.row_zs_shared, 0, ps.eq_n));
-            else CHK(pack(ps.col, colbuf, NpB, ps.col_zs_shared, 0, ps.eq_n));
-            pc->valid = true;
-            if (!c.dry && pc->done) CHK(q_fill(c, pc->done, 1, (size_t)ps.eq_n));
-        }
-        c.ws.off = mark;
-        return 0;
+    return 0;
+}
+
+// one operand of the pass (the row side: ps.row / ps.row2 / the merged twin plane; `col`: ps.col) into `buf`: its fixed plane, or the
+// candidates [c0, c0 + nc) of an expanded one
+int pack_operand(Ctx& c, const Pass& ps, const SweepPlan& pl, const PassBufs& b, const Operand& op, char* buf, bool col, int c0, int nc) {
+    PackParams pk = op.pk;
+    pk.Rp = col ? pl.NpB : pl.Mp; pk.Kp = pl.Kp; pk.dst = buf;
+    pk.Z = (col ? ps.col_zs_shared : ps.row_zs_shared) ? 1 : ps.Z;
+    pk.C = op.expanded ? nc : 1;
+    pk.c_inner = op.expanded ? pl.cin_exp : pl.cin_fix;
+    if (op.expanded && pk.scales) pk.scales += (long)c0 * pk.sc_cs;
+    if (op.expanded && ps.crange) {       // pruned pass: only the candidate groups in range, and not the ones already kept
+        pk.crange = ps.crange; pk.c_base = c0;
+        pk.done = (b.pc && b.pc->done) ? b.pc->done : nullptr;
     }
-    if (epi6_on && !c.dry && !(ec && ec->valid)) {
+    // what the host knows of the range (stages A2 / B2: the survivor range it read back; stage B1: its length)
+    int live_max = -1;
+    if (pk.crange && ps.host_hi > ps.host_lo) live_max = std::max(0, std::min(ps.host_hi, c0 + nc) - std::max(ps.host_lo, c0));
+    else if (pk.crange && ps.host_len > 0) live_max = std::min(ps.host_len, nc);
+    // (the finish of this pass flags the groups as packed: FinishParams.mark_done)
+    return ps.i8 ? launch_pack<int8_t>(c, pk, live_max) : launch_pack<float>(c, pk, live_max);
+}
+// the expanded operand's candidates [c0, c0 + nc), unless the module's plane cache holds them
+int pack_expanded(Ctx& c, const Pass& ps, const SweepPlan& pl, const PassBufs& b, int c0, int nc) {
+    PlaneCache* pc = b.pc;
+    const bool packed = pc && pc->valid;   // (a cached plane is never chunked: one iteration)
+    if (ps.row.expanded && !packed) CHK(pack_operand(c, ps, pl, b, ps.row, b.row, false, c0, nc));
+    if (ps.twin && ps.row2.expanded) CHK(pack_operand(c, ps, pl, b, ps.row2, b.row2, false, c0, nc));
+    if (ps.col.expanded && !packed) CHK(pack_operand(c, ps, pl, b, ps.col, b.col, true, c0, nc));
+    if (pc && !ps.crange && !packed) {   // every candidate is in the buffer now (a pruned pass packs a range and keeps flags)
+        pc->valid = true;
+        if (!c.dry && pc->done) CHK(q_fill(c, pc->done, 1, (size_t)ps.eq_n));
+    }
+    return 0;
+}
+
+// the epilogue operands of k_sweep6 / k_sweep7 in fragment order, and the stationary sweeps' stand-in for a missing bias
+int prep_epilogue(Ctx& c, const Pass& ps, const SweepPlan& pl, const PassBufs& b) {
+    const bool a_search = pl.a_search;
+    const size_t zero_bytes = sizeof(float) * pl.zero_bias_n;
+    if (pl.epi6_on && !c.dry && !(b.ec && b.ec->valid)) {
         PrepEpi6Params pe{};
-        pe.O = ps.O; pe.Wt = ps.G ? ps.G : ps.O; pe.bias = ps.bias ? ps.bias : zero_bias;
+        pe.O = ps.O; pe.Wt = ps.G ? ps.G : ps.O; pe.bias = ps.bias ? ps.bias : b.zero_bias;
         pe.o_ss = a_search ? ps.o_ns : ps.o_ms; pe.o_ts = a_search ? ps.o_ms : ps.o_ns;
         pe.SR = a_search ? ps.Ncols : ps.Mrows; pe.TR = a_search ? ps.Mrows : ps.Ncols;
         pe.bias_on_t = a_search ? 0 : 1; pe.wt_mode = ps.cos6 ? 4 : ps.wt_mode;
-        pe.stiles = s6_stiles; pe.ttiles = s6_ttiles; pe.E = epi6; pe.transposed = (ps.cos6 && !a_search) ? 1 : 0;
-        if (zero_bias) CHK(q_fill(c, zero_bias, 0, sizeof(float) * (size_t)std::max(Mp, Np)));
-        CHK(enqueue(c, KERN(PrepEpi6Params, k_prep_epi6), dim3((unsigned)std::min<long>((long)s6_stiles * s6_ttiles, 256L * 32)), dim3(256), 0, pe));
+        pe.stiles = pl.s6_stiles; pe.ttiles = pl.s6_ttiles; pe.E = b.epi6; pe.transposed = (ps.cos6 && !a_search) ? 1 : 0;
+        if (b.zero_bias) CHK(q_fill(c, b.zero_bias, 0, zero_bytes));
+        CHK(enqueue(c, KERN(PrepEpi6Params, k_prep_epi6), dim3((unsigned)std::min<long>((long)pl.s6_stiles * pl.s6_ttiles, 256L * 32)), dim3(256), 0, pe));
     }
-    if (ec) ec->valid = true;
-    if (big7 && !c.dry) {
+    if (b.ec) b.ec->valid = true;
+    if (pl.epi7_n && !c.dry) {
         PrepEpiParams pe{ps.O, ps.G ? ps.G : ps.O, ps.bias, ps.o_ms, ps.Mrows, ps.Ncols, ps.cos7 ? 4 : ps.wt_mode,
-                         Np / 256, Mp / (ps.twin ? 128 : 256), ps.twin ? 1 : 0, epi7};
-        const long chunks = (long)Mp * Np * 2 / 4;
+                         pl.Np / 256, pl.Mp / (ps.twin ? 128 : 256), ps.twin ? 1 : 0, b.epi7};
+        const long chunks = (long)pl.Mp * pl.Np * 2 / 4;
         CHK(enqueue(c, KERN(PrepEpiParams, k_prep_epi), dim3((unsigned)std::min<long>(cdiv(chunks, 256), 256L * 16)), dim3(256), 0, pe));
     }
+    // (with the image built above this is the second fill of the same buffer: DESIGN.md s10-7)
+    if (b.zero_bias && !c.dry) CHK(q_fill(c, b.zero_bias, 0, zero_bytes));
+    return 0;
+}
 
-    if (zero_bias && !c.dry) CHK(q_fill(c, zero_bias, 0, sizeof(float) * (size_t)std::max(Mp, Np)));
-    if (ps.use_s1 && !ps.s_ready) {
-        ps.s1.S = S1; ps.s1.C = ps.eq_n; ps.s1.nblk = ps.s_cs;
-        CHK(launch_scale(c, ps.s1));
-        if (ps.twin) { ps.s2.S = S2; ps.s2.C = ps.eq_n; ps.s2.nblk = ps.s_cs; CHK(launch_scale(c, ps.s2)); }
-    }
-    // fixed planes once
-    if (merged7) {
+// the planes that do not depend on the candidate, once
+int pack_fixed_planes(Ctx& c, const Pass& ps, const SweepPlan& pl, const PassBufs& b) {
+    if (pl.merged7) {
         Operand both = ps.row;              // positive range: scale + upper clamp; negative range: fixed scale + lower clamp
         both.pk.mode = PACK_TWIN_I8;
         both.pk.lo = ps.row2.pk.lo; both.pk.neg_scale = ps.row2.pk.neg_scale;
-        CHK(pack(both, rowbuf, Mp, ps.row_zs_shared, 0, 1));
+        CHK(pack_operand(c, ps, pl, b, both, b.row, false, 0, 1));
     } else if (ps.twin && ps.i8 && !ps.row.expanded && !ps.row2.expanded && dual_pack_ok(ps.row.pk, ps.row2.pk)) {
         // both planes of the twin row operand from one read of the source (k_pack_dual)
         PackParams p1 = ps.row.pk, p2 = ps.row2.pk;
-        p1.Rp = p2.Rp = Mp; p1.Kp = p2.Kp = Kp; p1.Z = p2.Z = ps.row_zs_shared ? 1 : ps.Z; p1.C = p2.C = 1;
-        p1.dst = rowbuf; p2.dst = row2buf;
+        p1.Rp = p2.Rp = pl.Mp; p1.Kp = p2.Kp = pl.Kp; p1.Z = p2.Z = ps.row_zs_shared ? 1 : ps.Z; p1.C = p2.C = 1;
+        p1.dst = b.row; p2.dst = b.row2;
         if (!c.dry) {
-            const long total = (long)p1.Z * Mp * (Kp / 16);
+            const long total = (long)p1.Z * pl.Mp * (pl.Kp / 16);
             if (total >= (1L << 31)) return fail(P4V_ERR_UNSUPPORTED, "operand plane too large for k_pack_dual (%ld 16-element runs)", total);
             CHK(enqueue(c, KERN(PackDualParams, k_pack_dual), dim3((unsigned)std::min<long>(cdiv(total, 256), 256L * 64)), dim3(256), 0, PackDualParams{p1, p2}));
         }
     } else {
-        if (!ps.row.expanded) CHK(pack(ps.row, rowbuf, Mp, ps.row_zs_shared, 0, 1));
-        if (ps.twin && !ps.row2.expanded) CHK(pack(ps.row2, row2buf, Mp, ps.row_zs_shared, 0, 1));
+        if (!ps.row.expanded) CHK(pack_operand(c, ps, pl, b, ps.row, b.row, false, 0, 1));
+        if (ps.twin && !ps.row2.expanded) CHK(pack_operand(c, ps, pl, b, ps.row2, b.row2, false, 0, 1));
     }
-    if (!ps.col.expanded) CHK(pack(ps.col, colbuf, NpB, ps.col_zs_shared, 0, 1));
+    if (!ps.col.expanded) CHK(pack_operand(c, ps, pl, b, ps.col, b.col, true, 0, 1));
+    return 0;
+}
 
-    int nine_halves = 0;
-    for (int c0 = 0; c0 < ps.eq_n; c0 += chunk) {
-        const int nc = std::min(chunk, ps.eq_n - c0);
-        const bool packed = pc && pc->valid;   // (a cached plane is never chunked: one iteration)
-        if (ps.row.expanded && !packed) CHK(pack(ps.row, rowbuf, Mp, ps.row_zs_shared, c0, nc));
-        if (ps.twin && ps.row2.expanded) CHK(pack(ps.row2, row2buf, Mp, ps.row_zs_shared, c0, nc));
-        if (ps.col.expanded && !packed) CHK(pack(ps.col, colbuf, NpB, ps.col_zs_shared, c0, nc));
-        if (pc && !ps.crange && !packed) {   // every candidate is in the buffer now (a pruned pass packs a range and keeps flags)
-            pc->valid = true;
-            if (!c.dry && pc->done) CHK(q_fill(c, pc->done, 1, (size_t)ps.eq_n));
-        }
-        if (g_stat_on && ps.crange && !c.dry) {     // roofline step only: how many of this launch's candidates run
-            // From what the host knows WITHOUT another round trip wherever it does -- the timed calibration must make the same
-            // launches, in the same issue rounds, as an untimed one (inside a group an extra synchronisation regroups the members):
-            // the survivor range the pruned pass read back anyway (stages A2 / B2 under the pass memo), or "one candidate" (stage B1
-            // of a single score block: the range holds the slice winner).  Only a caller without either reads the range back here.
-            int h[2] = {0, 0};
-            const bool host_knows = ps.host_hi > ps.host_lo;
-            const bool one_cand = !host_knows && g_stage == 2 && ps.nj == 1;
-            if (host_knows) { h[0] = ps.host_lo; h[1] = ps.host_hi; }
-            else if (one_cand) { h[0] = c0; h[1] = c0 + 1; }
-            else { CHK(q_d2h(c, h, ps.crange, sizeof h)); CHK(q_sync(c)); }
-            const int lo = std::max(h[0], c0), hi = std::min(h[1], c0 + nc);
-            g_exec_frac = (double)std::max(0, hi - lo) / (double)nc;
-            if ((rblk || rblk_z) && ps.nj <= 64 && !one_cand) {               // equal-sized score blocks, each on its own range
-                int hb[128];
-                if (host_knows && ps.host_rblk && ps.nj <= MIR_BLK) std::copy(ps.host_rblk, ps.host_rblk + 2 * ps.nj, hb);
-                else { CHK(q_d2h(c, hb, rblk ? rblk : rblk_z, sizeof(int) * 2 * ps.nj)); CHK(q_sync(c)); }
-                double sum = 0;
-                for (int j = 0; j < ps.nj; ++j) sum += std::max(0, std::min(std::min(hb[2 * j + 1], h[1]), c0 + nc) - std::max(std::max(hb[2 * j], h[0]), c0));
-                g_exec_frac = sum / ((double)nc * ps.nj);
+// roofline step only: g_exec_frac = how many of the chunk's candidates [c0, c0 + nc) a pruned pass runs.
+// From what the host knows WITHOUT another round trip wherever it does -- the timed calibration must make the same launches, in
+// the same issue rounds, as an untimed one (inside a group an extra synchronisation regroups the members): the survivor range the
+// pruned pass read back anyway (stages A2 / B2 under the pass memo), or "one candidate" (stage B1 of a single score block: the
+// range holds the slice winner).  Only a caller without either reads the range back here.
+int chunk_exec_frac(Ctx& c, const Pass& ps, const SweepPlan& pl, int c0, int nc) {
+    g_exec_frac = 1.0;
+    if (!(g_stat_on && ps.crange && !c.dry)) return 0;
+    int h[2] = {0, 0};
+    const bool host_knows = ps.host_hi > ps.host_lo;
+    const bool one_cand = !host_knows && g_stage == 2 && ps.nj == 1;
+    if (host_knows) { h[0] = ps.host_lo; h[1] = ps.host_hi; }
+    else if (one_cand) { h[0] = c0; h[1] = c0 + 1; }
+    else { CHK(q_d2h(c, h, ps.crange, sizeof h)); CHK(q_sync(c)); }
+    const int lo = std::max(h[0], c0), hi = std::min(h[1], c0 + nc);
+    g_exec_frac = (double)std::max(0, hi - lo) / (double)nc;
+    const int* blk = pl.rblk ? pl.rblk : pl.rblk_z;
+    if (blk && ps.nj <= 64 && !one_cand) {               // equal-sized score blocks, each on its own range
+        int hb[128];
+        if (host_knows && ps.host_rblk && ps.nj <= MIR_BLK) std::copy(ps.host_rblk, ps.host_rblk + 2 * ps.nj, hb);
+        else { CHK(q_d2h(c, hb, blk, sizeof(int) * 2 * ps.nj)); CHK(q_sync(c)); }
+        double sum = 0;
+        for (int j = 0; j < ps.nj; ++j) sum += std::max(0, std::min(std::min(hb[2 * j + 1], h[1]), c0 + nc) - std::max(std::max(hb[2 * j], h[0]), c0));
+        g_exec_frac = sum / ((double)nc * ps.nj);
+    }
+    if (tune(TUNE_PRINT) > 0) fprintf(stderr, "[p4v] pruned stage: candidates [%d, %d) of %d  (M %d N %d K %d Z %d nj %d)\n", h[0], h[1], ps.eq_n, ps.Mrows, ps.Ncols, ps.K, ps.Z, ps.nj);
+    return 0;
+}
+
+// k_sweep6 / k_sweep5 over the candidates [c0, c0 + nc)
+int sweep_chunk_stationary(Ctx& c, const Pass& ps, const SweepPlan& pl, const PassBufs& b, int c0, int nc) {
+    const bool a_search = pl.a_search;
+    const int Kp = pl.Kp;
+    Sweep3Params q{};
+    q.S = a_search ? b.col : b.row; q.s_zs = 0;
+    q.T = a_search ? b.row : b.col; q.t_cs = 0; q.t_zs = 0;
+    q.t_rs = (long)(pl.pairs ? ((nc + 1) & ~1) : nc) * Kp;   // [row][candidate][K] layout written by k_pack (c_inner)
+    q.ldk = Kp; q.ktiles = Kp / SW_BKB;
+    q.S1 = b.S1; q.s_cs = ps.s_cs; q.sb_on_t = a_search ? 0 : 1; q.sb_div = std::max(1, ps.sb_div);
+    q.bias = ps.bias ? ps.bias : b.zero_bias; q.bias_on_t = a_search ? 0 : 1;
+    q.O = ps.O; q.Wt = ps.G ? ps.G : ps.O; q.wt_mode = ps.wt_mode;
+    q.o_ss = a_search ? ps.o_ns : ps.o_ms; q.o_ts = a_search ? ps.o_ms : ps.o_ns;
+    q.SR = a_search ? ps.Ncols : ps.Mrows; q.TR = a_search ? ps.Mrows : ps.Ncols;
+    q.c0 = c0; q.c1 = c0 + nc; q.crange = ps.crange;
+    q.part = b.part; q.p_cs = pl.p_cs; q.NG = pl.s3_groups;
+    q.stiles = (a_search ? pl.Np : pl.Mp) / 128; q.ttiles = (a_search ? pl.Mp : pl.Np) / 128;
+    q.dbg = g_variant & 3;
+    if (pl.kind == SK_SWEEP5) {
+        const int cgroups = choose_cgroups((long)q.stiles * q.ttiles, nc, q.ktiles, cu_slots(c, 256, SWEEP_RECORD_KIND[SK_SWEEP5]), 30.0, 0.15);
+        return launch_sweep5(c, q, ps.epi, cgroups);
+    }
+    // streaming tiles of 64 rows: only those holding valid rows (the plane is padded to 128)
+    q.stiles = pl.s6_stiles; q.ttiles = pl.s6_ttiles; q.E = b.epi6; q.crange_blk = pl.rblk;
+    const int epi6k = ps.cos6 ? (a_search ? EPI_COS : EPI_COS_T) : ps.epi;
+    if (ps.cos6) q.NG = pl.cos6_Sp;
+    // what the host knows of the device-side range: the launch geometry is planned for the candidates that will run
+    const bool known = ps.crange && ps.host_hi > ps.host_lo;
+    const int nc_known = known ? std::max(1, std::min(ps.host_hi, c0 + nc) - std::max(ps.host_lo, c0)) : nc;
+    const double P6 = tune(TUNE_P6) > 0 ? 0.125 * tune(TUNE_P6) : 25.0;
+    const int slots6 = cu_slots(c, 256, SWEEP_RECORD_KIND[SK_SWEEP6]);
+    if (pl.rblk && known && ps.host_rblk && ps.nj <= 4) {
+        // per-score-block ranges known to the host: one launch per run of OPEN blocks (a closed block -- its only survivor
+        // is its stage-A winner -- has nothing to sweep: the q block of a ViT qkv layer); score block j = streaming
+        // tiles [j, j + 1) * sb_div / 64
+        const int tpb = ps.sb_div / 64;
+        for (int j = 0; j < ps.nj;) {
+            if (ps.host_rblk[2 * j + 1] <= ps.host_rblk[2 * j]) { ++j; continue; }
+            int j1 = j, lo = INT_MAX, hi = 0;
+            double fsum = 0;
+            for (; j1 < ps.nj && ps.host_rblk[2 * j1 + 1] > ps.host_rblk[2 * j1]; ++j1) {
+                const int l = std::max(ps.host_rblk[2 * j1], c0), h = std::min(ps.host_rblk[2 * j1 + 1], c0 + nc);
+                lo = std::min(lo, l); hi = std::max(hi, h);
+                fsum += std::max(0, h - l);
             }
-            if (tune(TUNE_PRINT) > 0) fprintf(stderr, "[p4v] pruned stage: candidates [%d, %d) of %d  (M %d N %d K %d Z %d nj %d)\n", h[0], h[1], ps.eq_n, ps.Mrows, ps.Ncols, ps.K, ps.Z, ps.nj);
-        } else g_exec_frac = 1.0;
-        if (stat_ok) {
-            Sweep3Params q{};
-            q.S = a_search ? colbuf : rowbuf; q.s_zs = 0;
-            q.T = a_search ? rowbuf : colbuf; q.t_cs = 0; q.t_zs = 0;
-            q.t_rs = (long)(pairs ? ((nc + 1) & ~1) : nc) * Kp;   // [row][candidate][K] layout written by k_pack (c_inner)
-            q.ldk = Kp; q.ktiles = Kp / SW_BKB;
-            q.S1 = S1; q.s_cs = ps.s_cs; q.sb_on_t = a_search ? 0 : 1; q.sb_div = std::max(1, ps.sb_div);
-            q.bias = ps.bias ? ps.bias : zero_bias; q.bias_on_t = a_search ? 0 : 1;
-            q.O = ps.O; q.Wt = ps.G ? ps.G : ps.O; q.wt_mode = ps.wt_mode;
-            q.o_ss = a_search ? ps.o_ns : ps.o_ms; q.o_ts = a_search ? ps.o_ms : ps.o_ns;
-            q.SR = a_search ? ps.Ncols : ps.Mrows; q.TR = a_search ? ps.Mrows : ps.Ncols;
-            q.c0 = c0; q.c1 = c0 + nc; q.crange = ps.crange;
-            q.part = part; q.p_cs = p_cs; q.NG = s3_groups;
-            q.stiles = (a_search ? Np : Mp) / 128; q.ttiles = (a_search ? Mp : Np) / 128;
-            q.dbg = g_variant & 3;
-            if (regs6) {
-                // streaming tiles of 64 rows: only those holding valid rows (the plane is padded to 128)
-                q.stiles = s6_stiles; q.ttiles = s6_ttiles; q.E = epi6; q.crange_blk = rblk;
-                const int epi6k = ps.cos6 ? (a_search ? EPI_COS : EPI_COS_T) : ps.epi;
-                if (ps.cos6) q.NG = cos6_Sp;
-                // what the host knows of the device-side range: the launch geometry is planned for the candidates that will run
-                const bool known = ps.crange && ps.host_hi > ps.host_lo;
-                const int nc_known = known ? std::max(1, std::min(ps.host_hi, c0 + nc) - std::max(ps.host_lo, c0)) : nc;
-                const double P6 = tune(TUNE_P6) > 0 ? 0.125 * tune(TUNE_P6) : 25.0;
-                if (rblk && known && ps.host_rblk && ps.nj <= 4) {
-                    // per-score-block ranges known to the host: one launch per run of OPEN blocks (a closed block -- its only survivor
-                    // is its stage-A winner -- has nothing to sweep: the q block of a ViT qkv layer); score block j = streaming
-                    // tiles [j, j + 1) * sb_div / 64
-                    const int tpb = ps.sb_div / 64;
-                    for (int j = 0; j < ps.nj;) {
-                        if (ps.host_rblk[2 * j + 1] <= ps.host_rblk[2 * j]) { ++j; continue; }
-                        int j1 = j, lo = INT_MAX, hi = 0;
-                        double fsum = 0;
-                        for (; j1 < ps.nj && ps.host_rblk[2 * j1 + 1] > ps.host_rblk[2 * j1]; ++j1) {
-                            const int l = std::max(ps.host_rblk[2 * j1], c0), h = std::min(ps.host_rblk[2 * j1 + 1], c0 + nc);
-                            lo = std::min(lo, l); hi = std::max(hi, h);
-                            fsum += std::max(0, h - l);
-                        }
-                        Sweep3Params qq = q;
-                        const int tt0 = j * tpb, tt1 = std::min(q.ttiles, j1 * tpb);
-                        qq.tile0 = tt0 * q.stiles; qq.ntile = (tt1 - tt0) * q.stiles;
-                        const int ncr = std::max(1, hi - lo);
-                        g_exec_frac = fsum / ((double)(j1 - j) * nc);
-                        int cg6 = choose_cgroups((long)qq.ntile, ncr, q.ktiles, cu_slots(c, 256, 2), P6, 0.14);
-                        if (tune(TUNE_CG6) > 0) cg6 = std::max(1, std::min(ncr, tune(TUNE_CG6)));
-                        if (tune(TUNE_PRINT) > 0) fprintf(stderr, "[p4v] sweep6 open blocks [%d, %d): tiles %d x %d ktiles %d cand %d -> cgroups %d\n", j, j1, q.stiles, tt1 - tt0, q.ktiles, ncr, cg6);
-                        if (hi > lo && qq.ntile > 0) CHK(launch_sweep6(c, qq, epi6k, cg6, ncr));
-                        j = j1;
-                    }
-                    continue;
-                }
-                int cg6 = choose_cgroups((long)q.stiles * q.ttiles, nc_known, q.ktiles, cu_slots(c, 256, 2), P6, 0.14);
-                if (tune(TUNE_CG6) > 0) cg6 = std::max(1, std::min(nc, tune(TUNE_CG6)));
-                if (tune(TUNE_PRINT) > 0) fprintf(stderr, "[p4v] sweep6 tiles %d x %d ktiles %d cand %d (%d known) -> cgroups %d\n", q.stiles, q.ttiles, q.ktiles, nc, nc_known, cg6);
-                CHK(launch_sweep6(c, q, epi6k, cg6, known ? nc_known : 0));
-                continue;
-            }
-            const long wgs = (long)q.stiles * q.ttiles;
-            const int cgroups = choose_cgroups(wgs, nc, q.ktiles, cu_slots(c, 256, 5), 30.0, 0.15);
-            CHK(launch_sweep5(c, q, ps.epi, cgroups));
-            continue;
+            Sweep3Params qq = q;
+            const int tt0 = j * tpb, tt1 = std::min(q.ttiles, j1 * tpb);
+            qq.tile0 = tt0 * q.stiles; qq.ntile = (tt1 - tt0) * q.stiles;
+            const int ncr = std::max(1, hi - lo);
+            g_exec_frac = fsum / ((double)(j1 - j) * nc);
+            int cg6 = choose_cgroups((long)qq.ntile, ncr, q.ktiles, slots6, P6, 0.14);
+            if (tune(TUNE_CG6) > 0) cg6 = std::max(1, std::min(ncr, tune(TUNE_CG6)));
+            if (tune(TUNE_PRINT) > 0) fprintf(stderr, "[p4v] sweep6 open blocks [%d, %d): tiles %d x %d ktiles %d cand %d -> cgroups %d\n", j, j1, q.stiles, tt1 - tt0, q.ktiles, ncr, cg6);
+            if (hi > lo && qq.ntile > 0) CHK(launch_sweep6(c, qq, epi6k, cg6, ncr));
+            j = j1;
         }
-        if (big7) {
-            Sweep7Params q{};
-            q.r_cs = ps.col.expanded ? col_plane1 : 0;
-            q.R = colbuf - (long)c0 * q.r_cs;
-            q.c_cs = ps.row.expanded ? row_plane1 : 0;
-            q.Cp = rowbuf - (long)c0 * q.c_cs;
-            q.C2 = (ps.twin && !merged7) ? row2buf : nullptr;
-            q.ldk = Kp; q.ktiles = Kp / SW_BKB;
-            q.S1 = S1; q.S2 = S2; q.s_cs = ps.s_cs; q.sb_div = ps.s_cs > 1 ? std::max(1, ps.sb_div) : (1 << 30);
-            q.E = epi7;
-            q.c0 = c0; q.c1 = c0 + nc; q.crange = ps.crange;
-            q.part = part; q.p_cs = p_cs; q.NG = ps.cos7 ? cos6_Sp : NpP;
-            q.rtiles = Np / 256; q.ctiles = Mp / (ps.twin ? 128 : 256);
-            // one workgroup per CU; per k-tile ~0.62 us (16 MFMAs per wave, two waves per SIMD), ~3 k-tiles' worth of
-            // epilogue per candidate, a prologue of a few us (scale tables, first tiles)
-            // (up to one candidate per workgroup: stage A of a pruned pass is 3 tiles x 100 candidates -- with the 25 groups of the
-            // other sweeps 75 workgroups on 256 CUs, 140-160 us per launch)
-            int cg7 = choose_cgroups((long)q.rtiles * q.ctiles, nc, q.ktiles + 3, cu_slots(c, 256, ps.twin ? 4 : 3), 6.0, 0.62, 100);
-            if (tune(TUNE_CG7) > 0) cg7 = std::max(1, std::min(nc, tune(TUNE_CG7)));
-            q.order = tune(TUNE_ORDER7) > 0 ? tune(TUNE_ORDER7) - 1 : 1;
-            if (tune(TUNE_PRINT) > 0) fprintf(stderr, "[p4v] sweep7 tiles %d x %d ktiles %d cand %d twin %d -> cgroups %d\n", q.rtiles, q.ctiles, q.ktiles, nc, (int)ps.twin, cg7);
-            CHK(launch_sweep7(c, q, merged7 ? 2 : ps.twin ? 1 : 0, ps.epi, cg7));
-            continue;
-        }
-        SweepParams sp{};
-        // plane pointers are biased so that the kernel can index them with the absolute candidate id
-        sp.a_cs = ps.row.expanded ? row_plane1 : 0;
-        sp.A = rowbuf - (long)c0 * sp.a_cs;
-        sp.a_zs = ps.row_zs_shared ? 0 : (long)Mp * Kp * esz;
-        if (ps.twin) {
-            sp.a2_cs = ps.row2.expanded ? row_plane1 : 0;
-            sp.A2 = row2buf - (long)c0 * sp.a2_cs;
-            sp.a2_zs = sp.a_zs;
-        }
-        sp.b_cs = ps.col.expanded ? col_plane1 : 0;
-        sp.B = colbuf - (long)c0 * sp.b_cs;
-        sp.b_zs = ps.col_zs_shared ? 0 : (long)NpB * Kp * esz;
-        sp.b_rows = b64 ? 64 : 0;
-        sp.ldk = Kp * esz; sp.ktiles = sp.ldk / SW_BKB;
-        sp.S1 = S1; sp.S2 = S2; sp.s_cs = ps.s_cs; sp.sb_mode = ps.sb_mode; sp.sb_div = std::max(1, ps.sb_div);
-        sp.bias = ps.bias; sp.bias_axis = ps.bias_axis; sp.bias_zs = ps.bias_zs;
-        sp.O = ps.O; sp.Wt = ps.G ? ps.G : ps.O; sp.wt_mode = ps.wt_mode;
-        sp.o_zs = ps.o_zs; sp.o_bs = ps.o_bs; sp.o_ms = ps.o_ms; sp.o_nbs = ps.o_nbs; sp.o_ns = ps.o_ns;
-        sp.o_inner = ps.o_inner > 0 ? ps.o_inner : INT_MAX;
-        sp.o_ninner = ps.o_ninner > 0 ? ps.o_ninner : INT_MAX;
-        sp.M = ps.Mrows; sp.N = ps.Ncols; sp.Z = ps.Z; sp.c0 = c0; sp.c1 = c0 + nc; sp.crange = ps.crange;
-        sp.crange_blk = rblk_z; sp.cb_div = std::max(1, ps.j_div);
-        sp.part = part; sp.p_cs = p_cs; sp.p_zs = p_zs; sp.Np = NpP;
-        sp.mtiles = Mp / SW_BM; sp.ntiles = Np / SW_BN;
-        sp.dbg = g_variant & 3;
-        sp.store = ps.store_out;
-        int cgroups = 1;
-        if (!fast && !fast_cos) {
-            // generic sweep: 2 workgroups per CU; per k-tile step ~2.6 us with fp32 operands (8 x mfma_f32_32x32x2 per
-            // 32x32 block), ~1.6 us on the int8 grid (measured on the patch-embedding search)
-            const long wgs = (long)sp.mtiles * sp.ntiles * ps.Z;
-            cgroups = choose_cgroups(wgs, nc, sp.ktiles, cu_slots(c, 512, ps.i8 ? 0 : 1), 20.0, ps.i8 ? 1.6 : 2.6);
-        }
-        if (fast || fast_cos) {
-            const long wgs = (long)sp.mtiles * sp.ntiles * ps.Z;
-            cgroups = choose_cgroups(wgs, nc, sp.ktiles, cu_slots(c, ps.twin ? 256 : 512, 9), ps.twin ? 40.0 : 25.0, ps.twin ? 0.45 : 0.40);
-        }
-        sp.bound = bound ? 1 : 0;
-        if (bound) sp.dbg = tune(TUNE_B1_PATH) >= 16 ? (tune(TUNE_B1_PATH) >> 4) : 0;   // (tuning 12 = 16 / 32: k_bound timing ablations)
-        if (bound) { sp.A = rowbuf; sp.B = colbuf; sp.a_cs = sp.b_cs = 0; }   // (the fragment-order image holds the ONE candidate in range)
-        if (fast && !bound && !ps.store_out && (ps.j_mode == 0 || ps.j_mode == 2)) {
-            const int h9 = sweep9_halves(sp, ps.twin, ps.epi);
-            if (h9 > 0 && (long)h9 * SW9_NW <= p_zs) {       // the table allocated for the 128-tile layout holds this one
-                sp.halves = h9;
-                sp.rows_p_stream = sp.a_cs == 0 ? Np : Mp;
-                sp.p_zs = (long)h9 * SW9_NW; sp.p_cs = sp.p_zs * ps.Z;
-                nine_halves = h9;
-                cgroups = choose_cgroups((long)h9 * ps.Z, nc, 1, cu_slots(c, SW9_NW == 4 ? 512 : 256, 6), 12.0, 0.9);
-            }
-        }
-        if (fast && !ps.store_out) {
-            if (const int t_ = tune(sweep2g_ok(sp) ? TUNE_CG2G : TUNE_CG2); t_ > 0) cgroups = std::max(1, std::min(nc, t_));
-            if (tune(TUNE_PRINT) > 0) fprintf(stderr, "[p4v] sweep2%s tiles %d x %d z %d ktiles %d cand %d twin %d -> cgroups %d\n", sweep2g_ok(sp) ? "g" : "", sp.mtiles, sp.ntiles, ps.Z, sp.ktiles, nc, (int)ps.twin, cgroups);
-        }
-        CHK(launch_sweep(c, sp, ps.i8, ps.twin, ps.epi, fast || fast_cos, cgroups));
+        return 0;
+    }
+    int cg6 = choose_cgroups((long)q.stiles * q.ttiles, nc_known, q.ktiles, slots6, P6, 0.14);
+    if (tune(TUNE_CG6) > 0) cg6 = std::max(1, std::min(nc, tune(TUNE_CG6)));
+    if (tune(TUNE_PRINT) > 0) fprintf(stderr, "[p4v] sweep6 tiles %d x %d ktiles %d cand %d (%d known) -> cgroups %d\n", q.stiles, q.ttiles, q.ktiles, nc, nc_known, cg6);
+    return launch_sweep6(c, q, epi6k, cg6, known ? nc_known : 0);
+}
+
+// k_sweep7 over the candidates [c0, c0 + nc)
+int sweep_chunk_large_k(Ctx& c, const Pass& ps, const SweepPlan& pl, const PassBufs& b, int c0, int nc) {
+    Sweep7Params q{};
+    q.r_cs = ps.col.expanded ? pl.col_plane1 : 0;
+    q.R = b.col - (long)c0 * q.r_cs;
+    q.c_cs = ps.row.expanded ? pl.row_plane1 : 0;
+    q.Cp = b.row - (long)c0 * q.c_cs;
+    q.C2 = pl.kind == SK_SWEEP7_TWIN ? b.row2 : nullptr;
+    q.ldk = pl.Kp; q.ktiles = pl.Kp / SW_BKB;
+    q.S1 = b.S1; q.S2 = b.S2; q.s_cs = ps.s_cs; q.sb_div = ps.s_cs > 1 ? std::max(1, ps.sb_div) : (1 << 30);
+    q.E = b.epi7;
+    q.c0 = c0; q.c1 = c0 + nc; q.crange = ps.crange;
+    q.part = b.part; q.p_cs = pl.p_cs; q.NG = ps.cos7 ? pl.cos6_Sp : pl.NpP;
+    q.rtiles = pl.Np / 256; q.ctiles = pl.Mp / (ps.twin ? 128 : 256);
+    // one workgroup per CU; per k-tile ~0.62 us (16 MFMAs per wave, two waves per SIMD), ~3 k-tiles' worth of
+    // epilogue per candidate, a prologue of a few us (scale tables, first tiles)
+    // (up to one candidate per workgroup: stage A of a pruned pass is 3 tiles x 100 candidates -- with the 25 groups of the
+    // other sweeps 75 workgroups on 256 CUs, 140-160 us per launch)
+    int cg7 = choose_cgroups((long)q.rtiles * q.ctiles, nc, q.ktiles + 3, cu_slots(c, 256, SWEEP_RECORD_KIND[ps.twin ? SK_SWEEP7_TWIN : SK_SWEEP7]), 6.0, 0.62, 100);
+    if (tune(TUNE_CG7) > 0) cg7 = std::max(1, std::min(nc, tune(TUNE_CG7)));
+    q.order = tune(TUNE_ORDER7) > 0 ? tune(TUNE_ORDER7) - 1 : 1;
+    if (tune(TUNE_PRINT) > 0) fprintf(stderr, "[p4v] sweep7 tiles %d x %d ktiles %d cand %d twin %d -> cgroups %d\n", q.rtiles, q.ctiles, q.ktiles, nc, (int)ps.twin, cg7);
+    return launch_sweep7(c, q, pl.kind == SK_SWEEP7_MERGED ? 2 : ps.twin ? 1 : 0, ps.epi, cg7);
+}
+
+// the tiled sweeps (k_bound, k_sweep9 / 8 / 2g / 2, the generic kernels) over the candidates [c0, c0 + nc): `kind` = chunk_kind
+int sweep_chunk_tiled(Ctx& c, const Pass& ps, const SweepPlan& pl, const PassBufs& b, SweepKind kind, int c0, int nc) {
+    const int esz = pl.esz, Mp = pl.Mp, Np = pl.Np, Kp = pl.Kp;
+    SweepParams sp{};
+    // plane pointers are biased so that the kernel can index them with the absolute candidate id
+    sp.a_cs = ps.row.expanded ? pl.row_plane1 : 0;
+    sp.A = b.row - (long)c0 * sp.a_cs;
+    sp.a_zs = ps.row_zs_shared ? 0 : (long)Mp * Kp * esz;
+    if (ps.twin) {
+        sp.a2_cs = ps.row2.expanded ? pl.row_plane1 : 0;
+        sp.A2 = b.row2 - (long)c0 * sp.a2_cs;
+        sp.a2_zs = sp.a_zs;
+    }
+    sp.b_cs = ps.col.expanded ? pl.col_plane1 : 0;
+    sp.B = b.col - (long)c0 * sp.b_cs;
+    sp.b_zs = ps.col_zs_shared ? 0 : (long)pl.NpB * Kp * esz;
+    sp.b_rows = pl.b64 ? 64 : 0;
+    sp.ldk = Kp * esz; sp.ktiles = sp.ldk / SW_BKB;
+    sp.S1 = b.S1; sp.S2 = b.S2; sp.s_cs = ps.s_cs; sp.sb_mode = ps.sb_mode; sp.sb_div = std::max(1, ps.sb_div);
+    sp.bias = ps.bias; sp.bias_axis = ps.bias_axis; sp.bias_zs = ps.bias_zs;
+    sp.O = ps.O; sp.Wt = ps.G ? ps.G : ps.O; sp.wt_mode = ps.wt_mode;
+    sp.o_zs = ps.o_zs; sp.o_bs = ps.o_bs; sp.o_ms = ps.o_ms; sp.o_nbs = ps.o_nbs; sp.o_ns = ps.o_ns;
+    sp.o_inner = ps.o_inner > 0 ? ps.o_inner : INT_MAX;
+    sp.o_ninner = ps.o_ninner > 0 ? ps.o_ninner : INT_MAX;
+    sp.M = ps.Mrows; sp.N = ps.Ncols; sp.Z = ps.Z; sp.c0 = c0; sp.c1 = c0 + nc; sp.crange = ps.crange;
+    sp.crange_blk = pl.rblk_z; sp.cb_div = std::max(1, ps.j_div);
+    sp.part = b.part; sp.p_cs = pl.p_cs; sp.p_zs = pl.p_zs; sp.Np = pl.NpP;
+    sp.mtiles = Mp / SW_BM; sp.ntiles = Np / SW_BN;
+    sp.dbg = g_variant & 3;
+    sp.store = ps.store_out;
+    // candidate groups: the cost model of the family (choose_cgroups), in microseconds
+    const long wgs = (long)sp.mtiles * sp.ntiles * ps.Z;
+    int cgroups;
+    switch (kind) {
+        case SK_GENERIC_I8: case SK_GENERIC_F32:
+            // 2 workgroups per CU; per k-tile step ~2.6 us with fp32 operands (8 x mfma_f32_32x32x2 per 32x32 block), ~1.6 us
+            // on the int8 grid (measured on the patch-embedding search)
+            cgroups = choose_cgroups(wgs, nc, sp.ktiles, cu_slots(c, 512, SWEEP_RECORD_KIND[kind]), 20.0, ps.i8 ? 1.6 : 2.6);
+            break;
+        case SK_SWEEP9:
+            sp.halves = pl.h9;
+            sp.rows_p_stream = sp.a_cs == 0 ? Np : Mp;
+            cgroups = choose_cgroups((long)pl.h9 * ps.Z, nc, 1, cu_slots(c, SW9_NW == 4 ? 512 : 256, SWEEP_RECORD_KIND[SK_SWEEP9]), 12.0, 0.9);
+            break;
+        case SK_BOUND:
+            sp.bound = 1;
+            sp.dbg = tune(TUNE_B1_PATH) >= 16 ? (tune(TUNE_B1_PATH) >> 4) : 0;   // (tuning 12 = 16 / 32: k_bound timing ablations)
+            sp.A = b.row; sp.B = b.col; sp.a_cs = sp.b_cs = 0;   // (the fragment-order image holds the ONE candidate in range)
+            [[fallthrough]];
+        default:    // (the k_sweep2 model, whichever of its kin runs)
+            cgroups = choose_cgroups(wgs, nc, sp.ktiles, cu_slots(c, ps.twin ? 256 : 512, SWEEP_RECORD_KIND[SK_SWEEP2]), ps.twin ? 40.0 : 25.0, ps.twin ? 0.45 : 0.40);
+    }
+    const bool tuned = kind != SK_GENERIC_I8 && kind != SK_GENERIC_F32 && !pl.fast_cos && !ps.store_out;
+    if (tuned) {
+        const char* g = kind == SK_SWEEP2G ? "g" : "";
+        if (const int t_ = tune(kind == SK_SWEEP2G ? TUNE_CG2G : TUNE_CG2); t_ > 0) cgroups = std::max(1, std::min(nc, t_));
+        if (tune(TUNE_PRINT) > 0) fprintf(stderr, "[p4v] sweep2%s tiles %d x %d z %d ktiles %d cand %d twin %d -> cgroups %d\n", g, sp.mtiles, sp.ntiles, ps.Z, sp.ktiles, nc, (int)ps.twin, cgroups);
+    }
+    return launch_sweep(c, sp, kind, ps.twin, ps.epi, cgroups);
+}
+
+// k_finish / k_finish_cos over the table as plan_sweep laid it out
+int finish_pass(Ctx& c, const Pass& ps, const SweepPlan& pl, const PassBufs& b) {
+    if (ps.epi == EPI_COS) {
+        FinishCosParams fp{b.part, pl.p_cs, pl.fin_zs, pl.fin_ld, pl.fin_rows, ps.cos_ZB, ps.cos_ZV, pl.fin_cols, ps.eq_n,
+                           ps.cos_j_mode, pl.fin_jdiv, ps.nj, ps.norm, b.scores};
+        return launch_finish_cos(c, fp);
+    }
+    FinishParams fp{b.part, pl.p_cs, pl.fin_zs, pl.fin_ld, pl.fin_rows, ps.Z, pl.fin_cols, ps.eq_n, ps.j_mode, pl.fin_jdiv, ps.nj, ps.norm,
+                    b.scores, ps.crange};
+    // a pruned pass flags the candidates it packed into the module's plane
+    if (ps.crange && b.pc && b.pc->done) { fp.mark_done = b.pc->done; fp.mark_n = ps.eq_n; }
+    fp.crange_blk = pl.rblk ? pl.rblk : pl.rblk_z;
+    return launch_finish(c, fp);
+}
+
+int run_pass(Ctx& c, Pass& ps) {
+    if (ps.seg) return run_pass_seg(c, ps);
+    g_alg_macs_cand = (double)ps.Mrows * ps.Ncols * ps.K * ps.Z;
+    // SURVEY.md s8-d3: every cached tensor read once per search pass -- both operands in fp32 as captured, raw_out and the metric weight
+    g_alg_bytes = 4.0 * ((double)ps.Mrows * ps.K * (ps.row_zs_shared ? 1 : ps.Z) + (double)ps.Ncols * ps.K * (ps.col_zs_shared ? 1 : ps.Z)) +
+                  (ps.G ? 8.0 : 4.0) * (double)ps.Mrows * ps.Ncols * ps.Z;
+    SweepPlan pl;
+    CHK(plan_sweep(c, ps, pl));
+    const size_t mark = c.ws.off;
+    PassBufs b{};
+    CHK(pass_workspace(c, ps, pl, b));
+    if (ps.pack_only) {
+        // every candidate of the expanded operand into the module's plane cache, in the layout this pass's sweep streams; the
+        // pass itself (and every later one of the module) then finds the plane packed
+        if (b.pc && ps.row.expanded != ps.col.expanded && !ps.crange) CHK(pack_expanded(c, ps, pl, b, 0, ps.eq_n));
+        c.ws.off = mark;
+        return 0;
+    }
+    CHK(prep_epilogue(c, ps, pl, b));
+    if (ps.use_s1 && !ps.s_ready) {
+        ps.s1.S = b.S1; ps.s1.C = ps.eq_n; ps.s1.nblk = ps.s_cs;
+        CHK(launch_scale(c, ps.s1));
+        if (ps.twin) { ps.s2.S = b.S2; ps.s2.C = ps.eq_n; ps.s2.nblk = ps.s_cs; CHK(launch_scale(c, ps.s2)); }
+    }
+    CHK(pack_fixed_planes(c, ps, pl, b));
+    for (int c0 = 0; c0 < ps.eq_n; c0 += pl.chunk) {
+        const int nc = std::min(pl.chunk, ps.eq_n - c0);
+        CHK(pack_expanded(c, ps, pl, b, c0, nc));
+        CHK(chunk_exec_frac(c, ps, pl, c0, nc));
+        const SweepKind kind = chunk_kind(pl, nc);
+        if (sweep_stationary(kind)) CHK(sweep_chunk_stationary(c, ps, pl, b, c0, nc));
+        else if (sweep_large_k(kind)) CHK(sweep_chunk_large_k(c, ps, pl, b, c0, nc));
+        else CHK(sweep_chunk_tiled(c, ps, pl, b, kind, c0, nc));
     }
     g_exec_frac = 1.0;
-    if (ps.store_out) { c.ws.off = mark; return 0; }
-    auto with_marks = [&](FinishParams& fp) {     // a pruned pass flags the candidates it packed into the module's plane
-        if (ps.crange && pc && pc->done) { fp.mark_done = pc->done; fp.mark_n = ps.eq_n; }
-        fp.crange_blk = rblk ? rblk : rblk_z;
-    };
-    if (nine_halves > 0) {      // k_sweep9 wrote [C][Z][halves * 8]
-        const int slots = nine_halves * SW9_NW;
-        FinishParams fp{part, (long)slots * ps.Z, (long)slots, slots, 1, ps.Z, slots, ps.eq_n, ps.j_mode, std::max(1, ps.j_div), ps.nj, ps.norm, scores, ps.crange};
-        with_marks(fp);
-        CHK(launch_finish(c, fp));
-    } else if (!cosm) {
-        const int gdiv = stat_ok ? s3_gw : 32;
-        // k_sweep5 / k_sweep6 activation search (j_mode 0) sums the whole table; its columns are sample groups
-        // (k_sweep6 skips streaming tiles that are pure padding: their table entries are never written)
-        const int fin_cols = stat_ok ? (a_search ? (regs6 ? 2 * cdiv(ps.Mrows, 64) : s3_groups) : cdiv(ps.Ncols, s3_gw))
-                                     : fast ? cdiv(ps.Ncols, 32) : ps.Ncols;
-        FinishParams fp{part, p_cs, p_zs, NpP, stat_ok ? s3_slabs : big7 ? MT7 : MT, ps.Z, fin_cols, ps.eq_n, ps.j_mode,
-                        std::max(1, (fast || stat_ok) && ps.j_mode == 1 ? cdiv(ps.j_div, gdiv) : ps.j_div), ps.nj, ps.norm, scores, ps.crange};
-        with_marks(fp);
-        CHK(launch_finish(c, fp));
-    } else {
-        // part layout [C][ZB][ZV][FS][Sp][3] with z = zb*ZV + zv
-        // (k_sweep6: Z = 1, the V blocks are consecutive runs of 64-feature slabs of the one table; samples = the rows)
-        // (a V block = sb_div features = sb_div / 64 whole slabs, whatever the padding behind the last block)
-        const bool cosp = ps.cos6 || ps.cos7;
-        const int cos6_FS = !cosp ? 0 : ps.cos_ZV == 1 ? cos6_slabs : ps.sb_div / cos_slab;
-        FinishCosParams fp{part, p_cs, cosp ? (long)cos6_FS * cos6_Sp * 3 : p_zs, cosp ? cos6_Sp : Np, cosp ? cos6_FS : MT,
-                           ps.cos_ZB, ps.cos_ZV, cosp ? ps.Mrows : ps.Ncols, ps.eq_n,
-                           ps.cos_j_mode, std::max(1, ps.cos_j_div), ps.nj, ps.norm, scores};
-        CHK(launch_finish_cos(c, fp));
-    }
-    if (!ps.no_select) {
-        SelectParams sl{scores, ps.eq_n, ps.nj, ps.cands, ps.cand_cs, ps.cand_js, ps.cand_off, ps.interval, ps.out_js,
-                        ps.out_off, ps.aux_out, ps.aux_div, ps.scores_out, ps.scores_out_ld, ps.best_out};
-        CHK(launch_select(c, sl));
+    if (!ps.store_out) {
+        CHK(finish_pass(c, ps, pl, b));
+        if (!ps.no_select) CHK(launch_pass_select(c, ps, b.scores));
     }
     c.ws.off = mark;   // scratch of this pass is reusable by the next one (same stream => ordered)
     return 0;
@@ -1684,11 +1800,6 @@ bool prune_ok(const Pass& ps) {
     if (!ps.prunable || !(ps.i8 || ps.prunable_f32) || ps.epi == EPI_COS || ps.store_out || ps.scores_out || ps.best_out || ps.crange || ps.no_select) return false;
     if ((g_variant & 4194304) || ps.eq_n < 32 || ps.nj < 1 || ps.nj > 4096) return false;
     return true;
-}
-int launch_pass_select(Ctx& c, const Pass& ps, const float* scores) {
-    SelectParams sl{scores, ps.eq_n, ps.nj, ps.cands, ps.cand_cs, ps.cand_js, ps.cand_off, ps.interval, ps.out_js,
-                    ps.out_off, ps.aux_out, ps.aux_div, ps.scores_out, ps.scores_out_ld, ps.best_out};
-    return launch_select(c, sl);
 }
 
 #define PRUNE_COUNT(i) do { if (!c.dry) g_prune_cnt[i].fetch_add(1, std::memory_order_relaxed); } while (0)

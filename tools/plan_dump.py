@@ -1,0 +1,161 @@
+"""What the host side plans, as JSON -- to compare two builds of the library (P4V_LIB selects the one to load).
+
+Without a GPU: the four *_workspace_bytes entry points over a grid of descriptors that reaches every sweep kernel family (the
+small shapes of tests/sweep_plan_cases.py, the layers of ViT-B / DeiT-T / Swin-T at the sizes tests/test_hip_production_path.py
+calibrates them; metrics, blocks, pruning on / off, fp32 planes -- the sizes do not depend on the bit width).
+--gpu: also the cases of tests/sweep_plan_cases.py, pruning off and on: launch records (kernel, stage, grid_x, grid_z) in order,
+p4v_launch_counters, p4v_prune_counters, and the raw bytes of the returned intervals, score tables and selections (as hex where
+they are at most 16 bytes, as a sha256 prefix otherwise).  No timings: two runs of the same code give the same file.
+
+    python tools/plan_dump.py [--gpu] [--out FILE]
+"""
+import argparse
+import ctypes as C
+import hashlib
+import itertools
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from ptq4vit_amd import _lib  # noqa: E402
+
+HESSIAN, COSINE, L2 = _lib.METRICS["hessian"], _lib.METRICS["cosine"], _lib.METRICS["L2_norm"]
+
+
+def linear_descs():
+    # (batch, tokens, K, N, n_V): the small cases; ViT-B x 32, DeiT-T x 16, Swin-T x 16 (blocks, patch merging, heads)
+    shapes = [(2, 64, 192, 128, 1), (2, 64, 128, 128, 1), (2, 64, 1024, 64, 1), (2, 64, 1088, 64, 1), (2, 64, 192, 120, 3), (10, 65, 192, 96, 1)]
+    for b, T, D in ((32, 197, 768), (16, 197, 192)):
+        shapes += [(b, T, D, 3 * D, 3), (b, T, D, D, 1), (b, T, D, 4 * D, 1), (b, T, 4 * D, D, 1), (b, 1, D, 1000, 1)]
+    for T, D in ((3136, 96), (784, 192), (196, 384), (49, 768)):
+        shapes += [(16, T, D, 3 * D, 3), (16, T, D, D, 1), (16, T, D, 4 * D, 1), (16, T, 4 * D, D, 1)]
+        if D < 768:
+            shapes.append((16, T // 4, 4 * D, 2 * D, 1))
+    shapes.append((16, 1, 768, 1000, 1))
+    for (b, T, K, N, nV), metric, bits, reserved in itertools.product(shapes, (HESSIAN, COSINE, L2), (8,), (0, 8, 1)):
+        for postgelu in ((0, 1) if K >= N and K >= 768 else (0,)):
+            yield _lib.LinearDesc(b, T, K, N, nV, 1, 1, bits, bits, metric, 100, 3, postgelu, 0, 1, reserved)
+    for (b, T, K, N, nV), metric in itertools.product(shapes[:6] + shapes[6:9], (HESSIAN, COSINE)):      # column / activation blocks
+        if N % 2 == 0 and K % 2 == 0:
+            yield _lib.LinearDesc(b, T, K, N, nV, 2, 2, 8, 8, metric, 100, 3, 0, 0, 1, 0)
+
+
+def _mm(b, H, M, K, N, bits, metric, sos, reserved, out=None):
+    d = out if out is not None else _lib.MatMulDesc()
+    d.batch, d.heads, d.M, d.K, d.N = b, H, M, K, N
+    for i, s in enumerate((H * M * K, M * K, K, 1)):
+        d.a_stride[i] = s
+    # q.k^T reads k transposed ([b][H][N][K] in memory), attn.v reads v as it lies
+    for i, s in enumerate((H * N * K, N * K, 1, K) if not sos else (H * K * N, K * N, N, 1)):
+        d.b_stride[i] = s
+    d.A_bit, d.B_bit, d.metric, d.eq_n, d.search_round, d.sos, d.init_layerwise, d.reserved = bits, bits, metric, 100, 3, sos, 0, reserved
+    return d
+
+
+def matmul_shapes():
+    # (batch, heads, tokens, head_dim): the small cases, ViT-B x 32, DeiT-T x 16, the four stages of Swin-T x 16 (windows of 49)
+    return [(2, 2, 49, 64), (2, 2, 120, 64), (32, 12, 197, 64), (16, 3, 197, 64), (16 * 64, 3, 49, 32), (16 * 16, 6, 49, 32),
+            (16 * 4, 12, 49, 32), (16, 24, 49, 32)]
+
+
+def matmul_descs():
+    for (b, H, T, D), metric, bits, reserved in itertools.product(matmul_shapes(), (HESSIAN, COSINE), (8,), (0, 8)):
+        yield _mm(b, H, T, D, T, bits, metric, 0, reserved)
+        yield _mm(b, H, T, T, D, bits, metric, 1, reserved)
+        yield _mm(b, H, T, T, D, bits, metric, 0, reserved)
+
+
+def matmul_blocks_descs():
+    for (b, H, T, D), blocks in itertools.product(matmul_shapes()[:4], ((2, 2, 2, 3), (1, 2, 3, 1), (1, 1, 2, 2), (1, 1, 1, 1))):
+        for sos in (0, 1):
+            bd = _lib.MatMulBlocksDesc()
+            _mm(b, H, T, T if sos else D, D if sos else T, 8, HESSIAN, sos, 0, out=bd.mm)
+            bd.n_V_A, bd.n_H_A, bd.n_V_B, bd.n_H_B = ((1, 1) + blocks[2:]) if sos else blocks
+            yield bd
+
+
+def conv_descs():
+    # (batch, channels, height, width, out channels, kernel = stride): the small case, the patch embeddings of ViT-B, DeiT-T, Swin-T
+    shapes = [(2, 3, 32, 32, 16, 16), (32, 3, 224, 224, 768, 16), (16, 3, 224, 224, 192, 16), (16, 3, 224, 224, 96, 4)]
+    for (b, ic, h, w, oc, k), metric, a_bit, cw, reserved in itertools.product(shapes, (HESSIAN, COSINE), (32, 8), (1, 0), (0, 8)):
+        yield _lib.ConvDesc(b, ic, h, w, oc, k, k, k, k, 0, 0, 1, 1, 8, a_bit, metric, 100, 3, cw, 0, 1, reserved)
+
+
+def workspace_plan(lib):
+    """per entry point: the number of descriptors, a digest of their bytes (which grid this was) and the sizes in grid order"""
+    plan = {}
+    for fn, descs in (("p4v_linear_workspace_bytes", linear_descs()), ("p4v_matmul_workspace_bytes", matmul_descs()),
+                      ("p4v_matmul_blocks_workspace_bytes", matmul_blocks_descs()), ("p4v_conv_workspace_bytes", conv_descs())):
+        h, sizes = hashlib.sha256(), []
+        for d in descs:
+            h.update(bytes(d))
+            sizes.append(int(getattr(lib, fn)(C.byref(d))))
+        plan[fn] = {"descriptors": len(sizes), "grid_sha256": h.hexdigest()[:16], "bytes": sizes}
+    return plan
+
+
+def _raw(t):
+    """shape and digest of a result tensor's bytes; the bytes themselves (hex) where they are few: the intervals"""
+    b = t.detach().cpu().contiguous().numpy().tobytes()
+    return "x".join(str(n) for n in t.shape) + ":" + (b.hex() if len(b) <= 16 else hashlib.sha256(b).hexdigest()[:16])
+
+
+def _runs(recs):
+    """launch records in order, equal neighbours folded: [kernel, stage, grid_x, grid_z, count]"""
+    out = []
+    for r in recs:
+        if out and out[-1][:4] == list(r):
+            out[-1][4] += 1
+        else:
+            out.append(list(r) + [1])
+    return out
+
+
+def gpu_plan():
+    from ptq4vit_amd import engine
+    from tests.sweep_plan_cases import CASES, run_case
+    rows = []
+    for (name, run, _), prune in itertools.product(CASES, (False, True)):
+        res, recs, launches, pruned = run_case(engine, run, prune)
+        rows.append({"case": name, "prune": int(prune), "records": _runs(recs),
+                     "launch_counters": [launches[k] for k in ("asked", "issued", "rounds", "groups")],
+                     "prune_counters": [pruned[k] for k in ("staged", "staged_no_survivors", "kept_full_sweep", "not_eligible")],
+                     "results": [_raw(t) for t in res]})
+        engine.release_workspace()
+    return rows
+
+
+def _lines(doc):
+    """compact JSON, one entry point / one case per line, the size lists wrapped"""
+    out = ["{"]
+    for fn, e in doc["workspace"].items():
+        sizes = e["bytes"]
+        out.append(' "%s": {"descriptors": %d, "grid_sha256": "%s", "bytes": [' % (fn, e["descriptors"], e["grid_sha256"]))
+        out += ["  " + ", ".join(str(n) for n in sizes[i:i + 16]) + ("," if i + 16 < len(sizes) else "") for i in range(0, len(sizes), 16)]
+        out.append(" ]},")
+    rows = doc.get("gpu", [])
+    out.append(' "gpu": [')
+    out += ["  " + json.dumps(r) + ("," if i + 1 < len(rows) else "") for i, r in enumerate(rows)]
+    out += [" ]", "}"]
+    return "\n".join(out) + "\n"
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--gpu", action="store_true", help="also run the small cases on cuda:0")
+    ap.add_argument("--out", default=None, help="write the JSON here instead of stdout")
+    a = ap.parse_args()
+    doc = {"workspace": workspace_plan(_lib.load())}
+    if a.gpu:
+        doc["gpu"] = gpu_plan()
+    text = _lines(doc)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(text)
+    else:
+        sys.stdout.write(text)
+
+
+if __name__ == "__main__":
+    main()
