@@ -2388,6 +2388,57 @@ int write_dev(Ctx& c, float* d, const std::vector<float>& h) {
     return q_sync(c);                       // h may go out of scope
 }
 
+// Up to two device vectors: the key or the value of one side's memo.  None: a pass that depends on nothing.
+struct DevVecs {
+    int count; float* d[2]; int n[2];
+    DevVecs(float* d0 = nullptr, int n0 = 0, float* d1 = nullptr, int n1 = 0) : count(n1 ? 2 : n0 ? 1 : 0), d{d0, d1}, n{n0, n1} {}
+};
+// read one after the other (each read_dev is a rendezvous), concatenated
+int read_vecs(Ctx& c, const DevVecs& vs, std::vector<float>& h) {
+    std::vector<float> part;
+    h.clear();
+    for (int i = 0; i < vs.count; ++i) { CHK(read_dev(c, vs.d[i], vs.n[i], part)); h.insert(h.end(), part.begin(), part.end()); }
+    return 0;
+}
+// A host copy of an interval vector, valid while no pass has moved the vector since (Linear: what a pass just read back or
+// restored is the next pass's key -- no second read-back)
+struct HostCopy { std::vector<float> v; bool ok = false; };
+
+// The pass memo of ONE side of a module's alternating search: restore() before the side's passes, record() after them when
+// restore() reported no hit.  Switched off (`on` false) both do nothing but invalidate the caller's host copy of the value.
+struct MemoSide {
+    bool on = false;
+    PassMemo table;
+    std::vector<float> key;      // of the lookup in flight: record() files the value under it
+    // key: `key_host` when the caller holds a valid copy, else the key vectors read back; no vectors: the constant key {0}.
+    // On a hit the recorded value goes back into `out` (write_dev: no synchronisation inside a group).
+    int restore(Ctx& c, const DevVecs& key_vecs, const HostCopy* key_host, const DevVecs& out, HostCopy* out_host, bool* hit) {
+        *hit = false;
+        if (!on) return 0;
+        if (key_host && key_host->ok) key = key_host->v;
+        else if (key_vecs.count == 0) key.assign(1, 0.0f);
+        else CHK(read_vecs(c, key_vecs, key));
+        const std::vector<float>* val = table.find(key);
+        if (!val) return 0;
+        size_t off = 0;
+        for (int i = 0; i < out.count; off += out.n[i], ++i)
+            CHK(write_dev(c, out.d[i], std::vector<float>(val->begin() + off, val->begin() + off + out.n[i])));
+        g_memo_hits++;
+        if (out_host) { out_host->v = *val; out_host->ok = true; }
+        *hit = true;
+        return 0;
+    }
+    int record(Ctx& c, const DevVecs& out, HostCopy* out_host) {
+        if (!on) { if (out_host) out_host->ok = false; return 0; }     // the passes moved `out`, nobody read it back
+        std::vector<float> val;
+        CHK(read_vecs(c, out, val));
+        table.entries.push_back({key, val});
+        g_memo_misses++;
+        if (out_host) { out_host->v = val; out_host->ok = true; }
+        return 0;
+    }
+};
+
 // binds the interval vectors of one *_impl call (the ones its pass memo reads back) to the stream's mapped block
 struct MirrorScope {
     MirrorScope(Ctx& c, bool on, const float* a, const float* b = nullptr, const float* d3 = nullptr) {
@@ -2412,6 +2463,27 @@ struct Stage {
     const float* cands2 = nullptr;   // ... of the second operand (a / B)
     bool full() const { return mask == ST_ALL; }
     bool searches() const { return (mask & (ST_S1 | ST_S2)) != 0; }
+};
+
+// What the round loop of a *_impl call derives from its Stage, its descriptor and the caller's tables.
+struct SearchRounds {
+    bool memo_on = false;        // the pass memo: a fused call that really runs, returns no tables and has not switched it off
+    bool keep_planes = false;    // candidate-expanded planes stay packed between the rounds of a fused call
+    int n_rounds = 1;            // a granular call is one pass
+    bool full = true;            // fused call: slot [round][which] of the tables; granular call: the one table of the call
+    int per_round = 2;           // tables per round: the two sides (MatMul with sub-blocks: one per block step)
+    int eq_n = 0, ld = 0;        // a score table is [eq_n][ld], a selection [ld]
+    float* scores = nullptr;
+    int32_t* best = nullptr;
+    SearchRounds() {}
+    SearchRounds(const Stage& sg, int search_round, int reserved, int eq_n_, int ld_, const Ctx& c, float* scores_out, int32_t* best_out,
+                 int per_round_ = 2)
+        : memo_on(sg.full() && !c.dry && !scores_out && !best_out && !(reserved & 2)), keep_planes(sg.full() && search_round > 1),
+          n_rounds(sg.full() ? search_round : 1), full(sg.full()), per_round(per_round_), eq_n(eq_n_), ld(ld_), scores(scores_out),
+          best(best_out) {}
+    long slot(int round, int which) const { return full ? (long)round * per_round + which : 0; }
+    float* scores_of(int round, int which) const { return scores ? scores + slot(round, which) * eq_n * ld : nullptr; }
+    int32_t* best_of(int round, int which) const { return best ? best + slot(round, which) * ld : nullptr; }
 };
 
 PackParams pack2d(const float* src, long rows, long cols, long ld) {
@@ -2449,83 +2521,127 @@ int seg_cut_k(SegPlan& g, const char* who) {
 // ------------------------------------------------------------------------------------------------
 // Linear
 // ------------------------------------------------------------------------------------------------
-int linear_impl(const p4v_linear_desc* d, const float* W, const float* bias, const float* X, const float* O,
-                const float* G, const float* mult, float* w_iv, float* a_iv, float* scores_out, int32_t* best_out,
-                Ctx& c, float* fwd_out = nullptr, const Stage& sg = Stage{}) {
-    // fwd_out != nullptr: quant_forward (linear.py:62-67 / 601-607) -- w_iv / a_iv are INPUTS, nothing is searched
-    const int M = d->batch * d->tokens, K = d->in_features, N = d->out_features;
-    const int nV = d->n_V, nH = d->n_H, nA = d->n_a;
-    if (M <= 0 || K <= 0 || N <= 0 || nV <= 0 || nH <= 0 || nA <= 0 || d->eq_n <= 0)
-        return fail(P4V_ERR_INVALID, "linear: non-positive dimension");
-    if (N % nV || K % nH || K % nA) return fail(P4V_ERR_UNSUPPORTED, "linear: n_V/n_H/n_a must divide the layer (reference ignores remainders, linear.py:118)");
-    if (d->w_bit > 8 || d->a_bit > 8 || d->w_bit < 2 || d->a_bit < 2) return fail(P4V_ERR_UNSUPPORTED, "linear: bit widths 2..8 supported");
-    const int crb_rows = N / nV, crb_cols = K / nH, crb_acts = K / nA;
-    const int wq = 1 << (d->w_bit - 1), aq = 1 << (d->a_bit - 1);
-    const float a_neg = (float)(0.16997124254703522 / aq);   // linear.py:574
-    int epi, wt_mode;
-    metric_epi(d->metric, &epi, &wt_mode);
-    const bool cosm = epi == EPI_COS;
-    if (wt_mode == 1 && !G && !fwd_out && sg.searches()) return fail(P4V_ERR_INVALID, "linear: hessian metric needs raw_grad (linear.py:418)");
-    const bool general = (nH > 1 || nA > 1 || (d->reserved & 1) || (cosm && d->twin_postgelu && !fwd_out));
-    const bool i8 = !general;
-    const bool twin = d->twin_postgelu && i8;
-    // Cosine with column / activation blocks (linear.py:455-533): the K-segmented int8 sweep, transposed -- A := W as n_V heads of
-    // crb_rows x K with intervals w_iv[v][h], B := x as K x samples shared by the heads with intervals a_iv[a]; K cut at the
-    // multiples of crb_cols and crb_acts.  One block step per pass (run_pass_seg), every other block on the interval entering it.
-    const bool segcos = cosm && !fwd_out && (nH > 1 || nA > 1);
-    if (segcos && d->twin_postgelu)
-        return fail(P4V_ERR_UNSUPPORTED, "linear: cosine with n_H>1 / n_a>1 on the post-GELU twin is not implemented on the GPU "
-                                         "(the twin's second plane lies on the column side, k_sweep_seg has no instance for that)");
-    SegPlan sgp{};
-    if (segcos) {
-        if (nH > 8 || nA > 8) return fail(P4V_ERR_UNSUPPORTED, "linear: cosine with up to n_H, n_a = 8 blocks is implemented on the GPU");
-        sgp.batch = 1; sgp.H = nV; sgp.M = crb_rows; sgp.K = K; sgp.N = M;
-        sgp.nVA = 1; sgp.nHA = nH; sgp.nVB = nA; sgp.nHB = 1;
-        sgp.crA = crb_rows; sgp.ccA = crb_cols; sgp.crB = crb_acts; sgp.ccB = M;
-        sgp.A = W; sgp.a_st[0] = 0; sgp.a_st[1] = (long)crb_rows * K; sgp.a_st[2] = K; sgp.a_st[3] = 1;
-        sgp.B = X; sgp.b_st[0] = 0; sgp.b_st[1] = 0; sgp.b_st[2] = 1; sgp.b_st[3] = K; sgp.b_shared = true;
-        sgp.Aq = wq; sgp.Bq = aq; sgp.ivA = w_iv; sgp.ivB = a_iv;
-        CHK(seg_cut_k(sgp, "linear"));
-    }
-    const int ncand = d->eq_n + 1;
+// One linear_impl call: what build() derives from the descriptor, and the builders of its passes.  Sides: 0 = the weight search
+// (reference linear.py:455-495), 1 = the activation search (linear.py:497-533 / 609-642).
+struct LinearCall {
+    Ctx& c;
+    const p4v_linear_desc* d;
+    const Stage& sg;
+    int M = 0, K = 0, N = 0;                          // samples (batch x tokens), in_features, out_features
+    int nV = 1, nH = 1, nA = 1;                       // row / column blocks of the weights, column blocks of the activations
+    int crb_rows = 0, crb_cols = 0, crb_acts = 0;     // ... and their sizes
+    int wq = 0, aq = 0;                               // 2^(bit - 1) of the weights / the activations
+    float a_neg = 0.f;                                // the fixed scale of the post-GELU negative range (linear.py:574)
+    int epi = 0, wt_mode = 0;                         // the metric's epilogue and weighting (metric_epi)
+    int ncand = 0;                                    // rows of a candidate table: eq_n + 1
+    bool cosm = false;                                // cosine metric
+    bool general = false;                             // fp32 candidate planes: column / activation blocks, desc.reserved bit 0, cosine on the twin
+    bool i8 = false;                                  // int8 planes (everything else)
+    bool twin = false;                                // post-GELU on int8 planes: the activations as two planes (positive / negative range)
+    bool segcos = false;                              // cosine with column / activation blocks: the K-segmented int8 sweep, one block step per pass
+    bool cos6 = false, cos7 = false;                  // cosine in the orientation of the difference metrics, on k_sweep6 / k_sweep7
+    int only_blk = -1;                                // granular call, desc.reserved bits 8..11 = 1 + b: the step of block b alone; else -1
+    int tab_blk = 0;                                  // the block whose score table and selections the call returns
+    const float *W = nullptr, *bias = nullptr, *X = nullptr, *O = nullptr, *G = nullptr, *mult = nullptr;
+    float *w_iv = nullptr, *a_iv = nullptr;           // intervals [n_V][n_H] / [n_a]
+    float* fwd_out = nullptr;                         // quant_forward (linear.py:62-67 / 601-607): the intervals are INPUTS, nothing is searched
+    unsigned *enc_w = nullptr, *enc_a = nullptr;      // abs-max per block, order-preserving encoding
+    float *w_cands_ws = nullptr, *a_cands_ws = nullptr;       // candidate tables built by this call ...
+    const float *w_cands = nullptr, *a_cands = nullptr;       // ... or the caller's (granular search)
+    float* Ufold = nullptr;                           // twin activation search: the target with the negative plane folded in
+    float *w_mix = nullptr, *a_mix = nullptr;         // general path: candidates in the searched block's column, the current interval elsewhere
+    float* Ot = nullptr;                              // segcos: raw_out as [feature][sample] (the seg sweep's rows are features)
+    SegPlan sgp{};                                    // segcos: A := W as n_V heads, B := x shared by the heads
+    SearchRounds rounds;
+    PlaneCache plane[2];                              // per side: the candidate-expanded plane, kept across rounds
+    EpiCache ecache[2];                               // per side: k_sweep6's epilogue operands in fragment order
+    SliceCache slice, slice2;                         // the sample slices of the pruned passes (two tiers)
 
-    cvt_bias(c);     // (first call of the process: probe the conversion quant16_sat8 relies on)
-    // ---- interval initialisation (linear.py:380-397 / 576-599) ---------------------------------------
-    unsigned* enc_w = c.ws.get<unsigned>((size_t)nV * nH);
-    unsigned* enc_a = c.ws.get<unsigned>((size_t)nA);
-    float* w_cands_ws = c.ws.get<float>((size_t)ncand * nV * nH);
-    float* a_cands_ws = c.ws.get<float>((size_t)ncand * nA);
-    const float* w_cands = (sg.mask & ST_INIT) ? w_cands_ws : sg.cands1;
-    const float* a_cands = (sg.mask & ST_INIT) ? a_cands_ws : sg.cands2;
-    float* Ufold = twin ? c.ws.get<float>((size_t)M * N) : nullptr;   // twin activation search: folded target
-    float* w_mix = c.ws.get<float>((size_t)ncand * nV * nH);   // general path: candidates of block column h only
-    float* a_mix = c.ws.get<float>((size_t)ncand * nA);
-    float* Ot = segcos ? c.ws.get<float>((size_t)M * N) : nullptr;   // raw_out as [feature][sample]: the seg sweep's rows are features
-    if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small");
-    // (the weight side first: it depends on no captured tensor -- inside a group that was handed a "capture done" event it runs,
-    // with the candidate planes of the weights further down, while the capture passes are still on the GPU)
-    if (!fwd_out && (sg.mask & ST_INIT)) {
-        const long stw[4] = {0, 0, K, 1};
-        CHK(launch_absmax(c, W, stw, 1, 1, N, K, nV, nH, crb_rows, crb_cols, 0, enc_w));
-        CHK(launch_interval(c, enc_w, nV * nH, (float)(wq - 0.5), d->init_layerwise, w_iv));
-        if (sg.searches()) CHK(launch_cands(c, mult, w_iv, ncand, nV * nH, w_cands_ws));
+    LinearCall(Ctx& c_, const p4v_linear_desc* d_, const Stage& sg_) : c(c_), d(d_), sg(sg_) {}
+
+    // argument checks, geometry, the path decisions, the workspace
+    int build(const float* W_, const float* bias_, const float* X_, const float* O_, const float* G_, const float* mult_, float* w_iv_,
+              float* a_iv_, float* scores_out, int32_t* best_out, float* fwd_out_) {
+        W = W_; bias = bias_; X = X_; O = O_; G = G_; mult = mult_; w_iv = w_iv_; a_iv = a_iv_; fwd_out = fwd_out_;
+        M = d->batch * d->tokens; K = d->in_features; N = d->out_features;
+        nV = d->n_V; nH = d->n_H; nA = d->n_a;
+        if (M <= 0 || K <= 0 || N <= 0 || nV <= 0 || nH <= 0 || nA <= 0 || d->eq_n <= 0)
+            return fail(P4V_ERR_INVALID, "linear: non-positive dimension");
+        if (N % nV || K % nH || K % nA) return fail(P4V_ERR_UNSUPPORTED, "linear: n_V/n_H/n_a must divide the layer (reference ignores remainders, linear.py:118)");
+        if (d->w_bit > 8 || d->a_bit > 8 || d->w_bit < 2 || d->a_bit < 2) return fail(P4V_ERR_UNSUPPORTED, "linear: bit widths 2..8 supported");
+        crb_rows = N / nV; crb_cols = K / nH; crb_acts = K / nA;
+        wq = 1 << (d->w_bit - 1); aq = 1 << (d->a_bit - 1);
+        a_neg = (float)(0.16997124254703522 / aq);   // linear.py:574
+        metric_epi(d->metric, &epi, &wt_mode);
+        cosm = epi == EPI_COS;
+        if (wt_mode == 1 && !G && !fwd_out && sg.searches()) return fail(P4V_ERR_INVALID, "linear: hessian metric needs raw_grad (linear.py:418)");
+        general = (nH > 1 || nA > 1 || (d->reserved & 1) || (cosm && d->twin_postgelu && !fwd_out));
+        i8 = !general;
+        twin = d->twin_postgelu && i8;
+        // Cosine with column / activation blocks (linear.py:455-533): the K-segmented int8 sweep, transposed -- A := W as n_V heads of
+        // crb_rows x K with intervals w_iv[v][h], B := x as K x samples shared by the heads with intervals a_iv[a]; K cut at the
+        // multiples of crb_cols and crb_acts.  One block step per pass (run_pass_seg), every other block on the interval entering it.
+        segcos = cosm && !fwd_out && (nH > 1 || nA > 1);
+        if (segcos && d->twin_postgelu)
+            return fail(P4V_ERR_UNSUPPORTED, "linear: cosine with n_H>1 / n_a>1 on the post-GELU twin is not implemented on the GPU "
+                                             "(the twin's second plane lies on the column side, k_sweep_seg has no instance for that)");
+        if (segcos) {
+            if (nH > 8 || nA > 8) return fail(P4V_ERR_UNSUPPORTED, "linear: cosine with up to n_H, n_a = 8 blocks is implemented on the GPU");
+            sgp.batch = 1; sgp.H = nV; sgp.M = crb_rows; sgp.K = K; sgp.N = M;
+            sgp.nVA = 1; sgp.nHA = nH; sgp.nVB = nA; sgp.nHB = 1;
+            sgp.crA = crb_rows; sgp.ccA = crb_cols; sgp.crB = crb_acts; sgp.ccB = M;
+            sgp.A = W; sgp.a_st[0] = 0; sgp.a_st[1] = (long)crb_rows * K; sgp.a_st[2] = K; sgp.a_st[3] = 1;
+            sgp.B = X; sgp.b_st[0] = 0; sgp.b_st[1] = 0; sgp.b_st[2] = 1; sgp.b_st[3] = K; sgp.b_shared = true;
+            sgp.Aq = wq; sgp.Bq = aq; sgp.ivA = w_iv; sgp.ivB = a_iv;
+            CHK(seg_cut_k(sgp, "linear"));
+        }
+        rounds = SearchRounds(sg, d->search_round, d->reserved, d->eq_n, nV, c, scores_out, best_out);
+        only_blk = sg.full() ? -1 : ((d->reserved >> 8) & 15) - 1;
+        if (sg.searches() && only_blk >= ((sg.mask & ST_S1) ? nH : nA)) return fail(P4V_ERR_INVALID, "linear: block %d outside the layer's blocks", only_blk);
+        tab_blk = std::max(0, only_blk);
+        // Cosine on k_sweep6: the layer as ONE GEMM in the orientation of the difference metrics (rows = samples, columns =
+        // features), the register-stationary sweep with the cosine epilogues EPI_COS / EPI_COS_T; the V blocks are runs of 64-feature
+        // slabs of k_finish_cos's table.  Otherwise (K > 768, blocks that are not whole slabs, variant 2048): k_sweep2 on the swapped
+        // operands, one GEMM per V block.
+        cos6 = cosm && i8 && !twin && !general && nH == 1 && nA == 1 && (nV == 1 || crb_rows % 64 == 0) &&
+               sweep6_supported((int)(rup(K, 64) / 64)) && !(g_variant & (4 | 2048)) && !g_force_v1;
+        // ... and on k_sweep7 for K >= 1024 (fc2): 128-feature slabs; the conditions are run_pass's for that kernel
+        cos7 = cosm && i8 && !twin && !general && nH == 1 && nA == 1 && (nV == 1 || crb_rows % 128 == 0) && !cos6 &&
+               rup(K, 64) >= 1024 && rup(K, 64) % 256 == 0 && N % 32 == 0 && (long)M * N * 4 < (1L << 32) &&
+               (c.dry || (((unsigned long long)O) & 15) == 0) && !(g_variant & (2048 | 32768)) && !g_force_v1;
+        ncand = d->eq_n + 1;
+        cvt_bias(c);     // (first call of the process: probe the conversion quant16_sat8 relies on)
+        enc_w = c.ws.get<unsigned>((size_t)nV * nH);
+        enc_a = c.ws.get<unsigned>((size_t)nA);
+        w_cands_ws = c.ws.get<float>((size_t)ncand * nV * nH);
+        a_cands_ws = c.ws.get<float>((size_t)ncand * nA);
+        w_cands = (sg.mask & ST_INIT) ? w_cands_ws : sg.cands1;
+        a_cands = (sg.mask & ST_INIT) ? a_cands_ws : sg.cands2;
+        Ufold = twin ? c.ws.get<float>((size_t)M * N) : nullptr;
+        w_mix = c.ws.get<float>((size_t)ncand * nV * nH);
+        a_mix = c.ws.get<float>((size_t)ncand * nA);
+        Ot = segcos ? c.ws.get<float>((size_t)M * N) : nullptr;
+        if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small");
+        return 0;
     }
-    auto init_activation_side = [&]() -> int {
-        if (!fwd_out && (sg.mask & ST_INIT)) {
-            const long stw[4] = {0, 0, K, 1};
+
+    // interval initialisation of one side (linear.py:380-397 / 576-599): abs-max per block, the interval, its candidate table
+    int init_side(int side) {
+        if (fwd_out || !(sg.mask & ST_INIT)) return 0;
+        const long stw[4] = {0, 0, K, 1};
+        if (side == 0) {
+            CHK(launch_absmax(c, W, stw, 1, 1, N, K, nV, nH, crb_rows, crb_cols, 0, enc_w));
+            CHK(launch_interval(c, enc_w, nV * nH, (float)(wq - 0.5), d->init_layerwise, w_iv));
+            if (sg.searches()) CHK(launch_cands(c, mult, w_iv, ncand, nV * nH, w_cands_ws));
+        } else {
             CHK(launch_absmax(c, X, stw, 1, 1, M, K, 1, nA, M, crb_acts, d->twin_postgelu ? 1 : 0, enc_a));
             CHK(launch_interval(c, enc_a, nA, (float)(aq - 0.5), d->init_layerwise, a_iv));
             if (sg.searches()) CHK(launch_cands(c, mult, a_iv, ncand, nA, a_cands_ws));
         }
         return 0;
-    };
-    if (fwd_out || !sg.full()) {                 // (quant_forward, the granular entry points: no capture to overlap with)
-        CHK(q_wait_inputs(c));
-        CHK(init_activation_side());
     }
-    if (!fwd_out && !sg.searches()) return 0;
 
-    auto x_operand = [&](bool expanded, const float* scales, int sc_cs) {
+    Operand x_operand(bool expanded, const float* scales, int sc_cs) const {
         Operand op{};
         op.present = true; op.expanded = expanded;
         op.pk = pack2d(X, M, K, K);
@@ -2537,15 +2653,15 @@ int linear_impl(const p4v_linear_desc* d, const float* W, const float* bias, con
             else { op.pk.mode = PACK_TWIN_SIM; op.pk.lo = -aq; op.pk.neg_scale = a_neg; }
         }
         return op;
-    };
-    auto xneg_operand = [&]() {
+    }
+    Operand xneg_operand() const {
         Operand op{};
         op.present = true; op.expanded = false;
         op.pk = pack2d(X, M, K, K);
         op.pk.scales = nullptr; op.pk.neg_scale = a_neg; op.pk.lo = -aq; op.pk.hi = 0;
         return op;
-    };
-    auto w_operand = [&](bool expanded, const float* scales, int sc_cs, bool by_vblock) {
+    }
+    Operand w_operand(bool expanded, const float* scales, int sc_cs, bool by_vblock) const {
         Operand op{};
         op.present = true; op.expanded = expanded;
         if (by_vblock) {   // swapped cosine sweep: one GEMM per V block
@@ -2561,11 +2677,11 @@ int linear_impl(const p4v_linear_desc* d, const float* W, const float* bias, con
         op.pk.scales = scales; op.pk.sc_cs = sc_cs;
         op.pk.lo = -wq; op.pk.hi = wq - 1;
         return op;
-    };
+    }
 
-    if (fwd_out) {
-        // out = Q_a(x) . Q_w(W)^T + bias as ONE integer GEMM: grid indices packed to int8 planes (the twin's two ranges
-        // as two planes), scales s_a * s_w[block] applied to the int32 accumulators in the epilogue
+    // out = Q_a(x) . Q_w(W)^T + bias as ONE integer GEMM: grid indices packed to int8 planes (the twin's two ranges
+    // as two planes), scales s_a * s_w[block] applied to the int32 accumulators in the epilogue
+    Pass forward_pass() const {
         Pass fp{};
         fp.i8 = i8; fp.twin = twin; fp.epi = EPI_FWD; fp.wt_mode = 0; fp.eq_n = 1; fp.K = K;
         fp.Z = 1; fp.Mrows = M; fp.Ncols = N;
@@ -2578,226 +2694,178 @@ int linear_impl(const p4v_linear_desc* d, const float* W, const float* bias, con
         fp.bias = bias; fp.bias_axis = 0; fp.bias_zs = 0;
         fp.O = fwd_out; fp.G = nullptr; fp.o_ms = N; fp.o_ns = 1; fp.o_inner = INT_MAX;
         fp.nj = 1; fp.store_out = fwd_out;
-        return run_pass(c, fp);
+        return fp;
     }
-    const bool memo_on = sg.full() && !c.dry && !scores_out && !best_out && !(d->reserved & 2);
-    PassMemo memo_w, memo_a;
-    MirrorScope mirrors(c, memo_on, w_iv, a_iv);
-    PlaneCache plane_w, plane_a;
-    EpiCache epi_w, epi_a;
-    SliceCache slice, slice2;
-    const bool keep_planes = sg.full() && d->search_round > 1;
-    std::vector<float> key, val, host_w, host_a;     // host copies of the current intervals, when a pass just moved them
-    bool host_w_ok = false, host_a_ok = false;
-    const int n_rounds = sg.full() ? d->search_round : 1;
-    auto slot = [&](int round, int which) { return sg.full() ? round * 2 + which : 0; };   // granular call: one table
-    // granular call, desc.reserved bits 8..11 = 1 + b: the step of column / activation block b alone, and ITS tables
-    const int only_blk = sg.full() ? -1 : ((d->reserved >> 8) & 15) - 1;
-    if (only_blk >= ((sg.mask & ST_S1) ? nH : nA)) return fail(P4V_ERR_INVALID, "linear: block %d outside the layer's blocks", only_blk);
-    const int tab_blk = std::max(0, only_blk);       // the block whose score table and selections the call returns
-    // Cosine on k_sweep6 (round 6): the layer as ONE GEMM in the orientation of the difference metrics (rows = samples, columns =
-    // features), the register-stationary sweep with the cosine epilogues EPI_COS / EPI_COS_T; the V blocks are runs of 64-feature
-    // slabs of k_finish_cos's table.  Otherwise (K > 768, blocks that are not whole slabs, variant 2048): k_sweep2 on the swapped
-    // operands, one GEMM per V block.
-    const bool cos6 = cosm && i8 && !twin && !general && nH == 1 && nA == 1 && (nV == 1 || crb_rows % 64 == 0) &&
-                      sweep6_supported((int)(rup(K, 64) / 64)) && !(g_variant & (4 | 2048)) && !g_force_v1;
-    // ... and on k_sweep7 for K >= 1024 (fc2): 128-feature slabs; the conditions are run_pass's for that kernel
-    const bool cos7 = cosm && i8 && !twin && !general && nH == 1 && nA == 1 && (nV == 1 || crb_rows % 128 == 0) && !cos6 &&
-                      rup(K, 64) >= 1024 && rup(K, 64) % 256 == 0 && N % 32 == 0 && (long)M * N * 4 < (1L << 32) &&
-                      (c.dry || (((unsigned long long)O) & 15) == 0) && !(g_variant & (2048 | 32768)) && !g_force_v1;
-    auto cos6_pass = [&](Pass& ps, int j_mode) {
-        ps.cos6 = cos6; ps.cos7 = cos7; ps.G = nullptr; ps.wt_mode = 0; ps.prunable = false; ps.scache = nullptr; ps.scache2 = nullptr;
-        ps.cos_ZB = 1; ps.cos_ZV = nV; ps.cos_j_mode = j_mode;
-        ps.norm = 1.0 / (double)d->tokens;
-    };
-    // the weight search pass of (round, column block h): reference linear.py:455-495
-    auto w_search_pass = [&](int round, int h, const float* wc, int wc_cs, bool memo_w_on) -> Pass {
+
+    // what a pass of (side, round, block) selects from and writes: one score per V block (weights) or one for the layer, the
+    // block's column of the side's candidate table and of its intervals; tables of the first block only (granular: of the one asked for)
+    void selection(Pass& ps, int side, int round, int blk) const {
+        const bool ws = side == 0;
+        ps.nj = ws ? nV : 1; ps.cands = ws ? w_cands : a_cands; ps.cand_cs = ws ? nV * nH : nA; ps.cand_js = ws ? nH : 0; ps.cand_off = blk;
+        ps.interval = ws ? w_iv : a_iv; ps.out_js = ws ? nH : 0; ps.out_off = blk;
+        if (blk == tab_blk) { ps.scores_out = rounds.scores_of(round, side); ps.best_out = rounds.best_of(round, side); }
+        ps.scores_out_ld = nV;
+    }
+    // The search pass of (side, round, block).  The side chooses the expanded operand and its table `cands` ([ncand][cs]: the
+    // side's candidate table, or its mix), what s1 reads, one score per V block or one for the layer; the orientation is the metric's.
+    Pass search_pass(int side, int round, int blk, const float* cands, bool host_sync_ok) {
+        const bool ws = side == 0;
+        const int cs = ws ? nV * nH : nA;
         Pass ps{};
         ps.i8 = i8; ps.twin = twin; ps.epi = epi; ps.wt_mode = wt_mode; ps.eq_n = d->eq_n; ps.K = K;
-        ps.cache = (keep_planes && nH == 1) ? &plane_w : nullptr;   // (n_H > 1: the table mixes in the current interval)
-        ps.ecache = keep_planes ? &epi_w : nullptr;
-        ps.nj = nV; ps.cands = w_cands; ps.cand_cs = nV * nH; ps.cand_js = nH; ps.cand_off = h;
-        ps.interval = w_iv; ps.out_js = nH; ps.out_off = h;
-        ps.scores_out = scores_out ? scores_out + ((long)slot(round, 0) * d->eq_n) * nV : nullptr;
-        ps.scores_out_ld = nV;
-        ps.best_out = best_out ? best_out + (long)slot(round, 0) * nV : nullptr;
-        if (h != tab_blk) { ps.scores_out = nullptr; ps.best_out = nullptr; }  // tables of the first column block only (granular: of the one asked for)
-        if (!cosm || cos6 || cos7) {
+        ps.cache = (rounds.keep_planes && (ws ? nH : nA) == 1) ? &plane[side] : nullptr;   // (blocks: the table mixes in the current interval)
+        ps.ecache = rounds.keep_planes ? &ecache[side] : nullptr;
+        selection(ps, side, round, blk);
+        const bool dense = !cosm || cos6 || cos7;
+        const Operand xo = ws ? x_operand(false, a_iv, 0) : x_operand(true, cands, cs);
+        const Operand wo = ws ? w_operand(true, cands, cs, !dense) : w_operand(false, w_iv, 0, !dense);
+        ps.s1 = ws ? ScaleParams{a_iv, 0, 0, 0.f, w_cands, nV, 1, 0.f, 0, 0, nullptr} : ScaleParams{a_cands, 1, 0, 0.f, w_iv, 0, 1, 0.f, 0, 0, nullptr};
+        ps.use_s1 = i8; ps.s_cs = nV;
+        ps.bias = bias; ps.O = O; ps.o_inner = INT_MAX;
+        if (dense) {
+            // rows = samples, columns = features
             ps.Z = 1; ps.Mrows = M; ps.Ncols = N;
-            ps.row = x_operand(false, a_iv, 0);
-            if (twin) { ps.row2 = xneg_operand(); ps.twin_disjoint = true; }    // linear.py:605-606: clamp(.,0,q-1) / clamp(.,-q,0)
-            ps.col = w_operand(true, wc, wc_cs, false);
-            ps.use_s1 = i8; ps.s_cs = nV; ps.sb_mode = 1; ps.sb_div = crb_rows;
-            ps.s1 = ScaleParams{a_iv, 0, 0, 0.f, w_cands, nV, 1, 0.f, 0, 0, nullptr};
-            ps.s2 = ScaleParams{nullptr, 0, 0, a_neg, w_cands, nV, 1, 0.f, 0, 0, nullptr};
-            ps.bias = bias; ps.bias_axis = 0; ps.bias_zs = 0;
-            ps.O = O; ps.G = G; ps.o_zs = 0; ps.o_bs = 0; ps.o_ms = N; ps.o_ns = 1; ps.o_inner = INT_MAX;
-            ps.j_mode = 1; ps.j_div = crb_rows;
-            ps.norm = 1.0 / ((double)d->tokens * crb_rows);
-            ps.prunable = !(d->reserved & 8); ps.scache = &slice; ps.scache2 = &slice2; ps.host_sync_ok = memo_w_on;
-            if (cos6 || cos7) cos6_pass(ps, 1);
+            ps.row = xo; ps.col = wo;
+            if (twin) { ps.row2 = xneg_operand(); ps.twin_disjoint = ws; }    // linear.py:605-606: clamp(.,0,q-1) / clamp(.,-q,0)
+            ps.sb_mode = 1; ps.sb_div = crb_rows;
+            ps.s2 = ScaleParams{nullptr, 0, 0, a_neg, ws ? w_cands : w_iv, ws ? nV : 0, 1, 0.f, 0, 0, nullptr};
+            ps.bias_axis = 0; ps.bias_zs = 0;
+            ps.G = G; ps.o_zs = 0; ps.o_bs = 0; ps.o_ms = N; ps.o_ns = 1;
+            ps.j_mode = ws ? 1 : 0; ps.j_div = ws ? crb_rows : 0;
+            ps.norm = 1.0 / ((double)d->tokens * (ws ? crb_rows : N));
+            ps.prunable = !(d->reserved & 8); ps.scache = &slice; ps.scache2 = &slice2; ps.host_sync_ok = host_sync_ok;
+            if (cos6 || cos7) {
+                ps.cos6 = cos6; ps.cos7 = cos7; ps.G = nullptr; ps.wt_mode = 0; ps.prunable = false; ps.scache = nullptr; ps.scache2 = nullptr;
+                ps.cos_ZB = 1; ps.cos_ZV = nV; ps.cos_j_mode = ws ? 1 : 0;
+                ps.norm = 1.0 / (double)d->tokens;
+            }
         } else {
-            // swapped: rows = features of V block z, cols = samples
+            // swapped: rows = features of V block z, columns = samples -- one GEMM per V block
             ps.Z = nV; ps.Mrows = crb_rows; ps.Ncols = M;
-            ps.row = w_operand(true, wc, wc_cs, true);
-            ps.col = x_operand(false, a_iv, 0);
+            ps.row = wo; ps.col = xo;
             ps.col_zs_shared = 1;
-            ps.use_s1 = i8; ps.s_cs = nV; ps.sb_mode = 2; ps.sb_div = nV;
-            ps.s1 = ScaleParams{a_iv, 0, 0, 0.f, w_cands, nV, 1, 0.f, 0, 0, nullptr};
-            ps.bias = bias; ps.bias_axis = 1; ps.bias_zs = crb_rows;
-            ps.O = O; ps.G = nullptr; ps.o_zs = crb_rows; ps.o_bs = 0; ps.o_ms = 1; ps.o_ns = N; ps.o_inner = INT_MAX;
-            ps.cos_ZB = 1; ps.cos_ZV = nV; ps.cos_j_mode = 1;
+            ps.sb_mode = 2; ps.sb_div = nV;
+            ps.bias_axis = 1; ps.bias_zs = crb_rows;
+            ps.G = nullptr; ps.o_zs = crb_rows; ps.o_bs = 0; ps.o_ms = 1; ps.o_ns = N;
+            ps.cos_ZB = 1; ps.cos_ZV = nV; ps.cos_j_mode = ws ? 1 : 0;
             ps.norm = 1.0 / (double)d->tokens;
         }
         return ps;
-    };
-    // the block step of the cosine seg sweep: side 1 = column block h of every V block (one score per V block), side 2 =
+    }
+
+    // the block step of the cosine seg sweep: side 0 = column block h of every V block (one score per V block), side 1 =
     // activation block a (ONE score over all features); tables of block 0 only, as for the difference metrics
-    auto seg_cos_pass = [&](int round, int side, int blk) -> Pass {
-        const bool ws_ = side == 1;
-        sgp.side = side; sgp.ov_v = ws_ ? 0 : blk; sgp.ov_h = ws_ ? blk : 0;
-        sgp.cands = (ws_ ? w_cands : a_cands) + blk; sgp.cand_cs = ws_ ? nV * nH : nA; sgp.cand_hs = ws_ ? nH : 0;
+    Pass seg_cos_pass(int side, int round, int blk) {
+        const bool ws = side == 0;
+        sgp.side = side + 1; sgp.ov_v = ws ? 0 : blk; sgp.ov_h = ws ? blk : 0;
+        sgp.cands = (ws ? w_cands : a_cands) + blk; sgp.cand_cs = ws ? nV * nH : nA; sgp.cand_hs = ws ? nH : 0;
         Pass ps{};
         ps.seg = &sgp; ps.i8 = true; ps.epi = EPI_COS; ps.eq_n = d->eq_n; ps.K = K;
         ps.Z = nV; ps.Mrows = crb_rows; ps.Ncols = M;
         ps.bias = bias; ps.bias_axis = 1; ps.bias_zs = crb_rows;
         ps.O = Ot;
-        ps.cos_ZB = 1; ps.cos_ZV = nV; ps.cos_j_mode = ws_ ? 1 : 0;
+        ps.cos_ZB = 1; ps.cos_ZV = nV; ps.cos_j_mode = ws ? 1 : 0;
         ps.norm = 1.0 / (double)d->tokens;
-        ps.nj = ws_ ? nV : 1;
-        ps.cands = ws_ ? w_cands : a_cands; ps.cand_cs = sgp.cand_cs; ps.cand_js = sgp.cand_hs; ps.cand_off = blk;
-        ps.interval = ws_ ? w_iv : a_iv; ps.out_js = ws_ ? nH : 0; ps.out_off = blk;
-        if (blk == tab_blk) {
-            ps.scores_out = scores_out ? scores_out + ((long)slot(round, ws_ ? 0 : 1) * d->eq_n) * nV : nullptr;
-            ps.best_out = best_out ? best_out + (long)slot(round, ws_ ? 0 : 1) * nV : nullptr;
-        }
-        ps.scores_out_ld = nV;
+        selection(ps, side, round, blk);
         return ps;
-    };
+    }
+
+    // General path with blocks: the candidates replace block `blk` only, the others keep the current interval (linear.py:468-469):
+    // mix[c][j] = (j in block blk) ? cands[c][j] : interval[j] -- a broadcast of the interval, then the block's column(s) copied in
+    int mix_candidates(int side, int blk) {
+        if (c.dry) return 0;
+        const bool ws = side == 0;
+        const int n = ws ? nV * nH : nA, rows = ws ? nV : 1;
+        const float* cands = ws ? w_cands : a_cands;
+        float* mix = ws ? w_mix : a_mix;
+        ScaleParams mp{};
+        mp.x = ws ? w_iv : a_iv; mp.x_cs = 0; mp.x_js = 1; mp.y = nullptr; mp.y_const = 1.0f; mp.C = ncand; mp.nblk = n; mp.S = mix;
+        CHK(launch_scale(c, mp));
+        for (int v = 0; v < rows; ++v)
+            CHK(q_copy2d(c, mix + v * nH + blk, sizeof(float) * n, cands + v * nH + blk, sizeof(float) * n, sizeof(float), ncand));
+        return 0;
+    }
+
+    // Twin activation search: the negative-range plane and the weights are candidate-invariant, so their product is folded
+    // into the target once (U = raw_out - bias - s_neg*s_w*(x_neg . W_q)) and the sweep `ps` runs on the positive-range plane
+    // alone: half the MFMA work of this pass.
+    int fold_negative_plane(Pass& ps) {
+        Pass fp = ps;
+        fp.twin = false; fp.epi = EPI_STORE; fp.wt_mode = 0; fp.eq_n = 1;
+        fp.row = xneg_operand(); fp.row2 = Operand{};
+        fp.s1 = ps.s2;
+        fp.store_out = Ufold; fp.cache = nullptr;
+        fp.scores_out = nullptr; fp.best_out = nullptr;
+        CHK(run_pass(c, fp));
+        ps.twin = false; ps.row2 = Operand{};
+        ps.O = Ufold; ps.bias = nullptr;
+        // Ufold depends on the CURRENT w_interval: it is rebuilt for every activation pass that runs, so the
+        // fragment-order image of k_sweep6's epilogue operands (built from ps.O) must be rebuilt with it
+        ps.ecache = nullptr;
+        slice.o_src = nullptr;          // ... and so are the gathered rows of the target in the sample slice
+        slice2.o_src = nullptr;         // (both tiers: the second one compares the same pointer and would otherwise keep
+                                        // the previous pass's target rows when two tier-2 activation passes follow each other)
+        return 0;
+    }
+
+    // One side of one round: the memo, then the side's block steps.
+    // With n_H > 1 the weight search is a coordinate descent over the column blocks: block h is swept with the other
+    // blocks at the interval ENTERING the pass (linear.py:468), so its result also depends on w_iv, not only on a_iv
+    // (same for n_a > 1 and the activation search).  The memo keys on the counterpart interval alone and is therefore
+    // only used where that is the whole input of the pass (`memo.on`: this side has ONE block).
+    int search_side(int side, int round, MemoSide& memo, HostCopy* host) {
+        const bool ws = side == 0;
+        const int nblk = ws ? nH : nA;
+        const DevVecs key = ws ? DevVecs(a_iv, nA) : DevVecs(w_iv, nV * nH), val = ws ? DevVecs(w_iv, nV * nH) : DevVecs(a_iv, nA);
+        bool hit = false;
+        CHK(memo.restore(c, key, &host[1 - side], val, &host[side], &hit));      // (key: just read back / written by the last pass)
+        for (int blk = 0; blk < nblk && !hit && (sg.mask & (ws ? ST_S1 : ST_S2)); ++blk) {
+            if (only_blk >= 0 && blk != only_blk) continue;
+            if (segcos) { Pass ps = seg_cos_pass(side, round, blk); CHK(run_pass(c, ps)); continue; }
+            const float* cands = ws ? w_cands : a_cands;
+            if (general && nblk > 1) { CHK(mix_candidates(side, blk)); cands = ws ? w_mix : a_mix; }
+            Pass ps = search_pass(side, round, blk, cands, memo.on);
+            if (!ws && twin && wt_mode <= 1) CHK(fold_negative_plane(ps));
+            CHK(run_pass_pruned(c, ps));
+        }
+        return hit ? 0 : memo.record(c, val, &host[side]);
+    }
+};
+
+int linear_impl(const p4v_linear_desc* d, const float* W, const float* bias, const float* X, const float* O,
+                const float* G, const float* mult, float* w_iv, float* a_iv, float* scores_out, int32_t* best_out,
+                Ctx& c, float* fwd_out = nullptr, const Stage& sg = Stage{}) {
+    LinearCall L(c, d, sg);
+    CHK(L.build(W, bias, X, O, G, mult, w_iv, a_iv, scores_out, best_out, fwd_out));
+    // (the weight side first: it depends on no captured tensor -- inside a group that was handed a "capture done" event it runs,
+    // with the candidate planes of the weights further down, while the capture passes are still on the GPU)
+    CHK(L.init_side(0));
+    if (fwd_out || !sg.full()) {                 // (quant_forward, the granular entry points: no capture to overlap with)
+        CHK(q_wait_inputs(c));
+        CHK(L.init_side(1));
+    }
+    if (!fwd_out && !sg.searches()) return 0;
+    if (fwd_out) { Pass fp = L.forward_pass(); return run_pass(c, fp); }
+    const SearchRounds& R = L.rounds;
+    MirrorScope mirrors(c, R.memo_on, w_iv, a_iv);
+    MemoSide memo[2];
+    memo[0].on = R.memo_on && L.nH == 1;
+    memo[1].on = R.memo_on && L.nA == 1;
+    HostCopy host[2];                            // host copies of w_iv / a_iv, when a pass just moved them
     if (sg.full()) {
         // The 100 candidate planes of the weights (8.5 GB per ViT-B calibration over its 48 Linear layers) need the weights and
         // their candidate table, nothing captured: packed here, before the call waits for its captured tensors.
-        if (keep_planes && nH == 1 && !cosm && (sg.mask & ST_S1)) {
-            Pass pp = w_search_pass(0, 0, w_cands, nV * nH, memo_on);
+        if (R.keep_planes && L.nH == 1 && !L.cosm && (sg.mask & ST_S1)) {
+            Pass pp = L.search_pass(0, 0, 0, L.w_cands, R.memo_on);
             pp.pack_only = true;
             CHK(run_pass(c, pp));
         }
         CHK(q_wait_inputs(c));
-        CHK(init_activation_side());
+        CHK(L.init_side(1));
     }
-    if (segcos) CHK(enqueue(c, KERN(NchwRowsParams, k_nchw_to_rows), dim3(cdiv(N, 32), cdiv(M, 32), 1), dim3(256), 0, NchwRowsParams{O, M, N, Ot}));
-    for (int round = 0; round < n_rounds; ++round) {
-        // ================= weight search (linear.py:455-495) =================
-        // With n_H > 1 the weight search is a coordinate descent over the column blocks: block h is swept with the other
-        // blocks at the interval ENTERING the pass (linear.py:468), so its result also depends on w_iv, not only on a_iv
-        // (same for n_a > 1 and the activation search).  The memo keys on the counterpart interval alone and is therefore
-        // only used where that is the whole input of the pass.
-        const bool memo_w_on = memo_on && nH == 1, memo_a_on = memo_on && nA == 1;
-        bool skip_w = false;
-        if (memo_w_on) {
-            if (host_a_ok) key = host_a; else CHK(read_dev(c, a_iv, nA, key));     // (just read back / written by the last pass)
-            if (const auto* hit = memo_w.find(key)) { CHK(write_dev(c, w_iv, *hit)); skip_w = true; g_memo_hits++; host_w = *hit; host_w_ok = true; }
-        }
-        for (int h = 0; h < nH && !skip_w && (sg.mask & ST_S1); ++h) {
-            const float* wc = w_cands;
-            int wc_cs = nV * nH;
-            if (only_blk >= 0 && h != only_blk) continue;
-            if (segcos) { Pass ps = seg_cos_pass(round, 1, h); CHK(run_pass(c, ps)); continue; }
-            if (general && nH > 1) {
-                // candidates replace column block h only, the others keep the current interval (linear.py:468-469)
-                if (!c.dry) {
-                    ScaleParams mp{};  // w_mix[c][j] = (j % nH == h) ? w_cands[c][j] : w_iv[j] -- done with two launches
-                    mp.x = w_iv; mp.x_cs = 0; mp.x_js = 1; mp.y = nullptr; mp.y_const = 1.0f; mp.C = ncand; mp.nblk = nV * nH; mp.S = w_mix;
-                    CHK(launch_scale(c, mp));
-                    for (int v = 0; v < nV; ++v)
-                        CHK(q_copy2d(c, w_mix + v * nH + h, sizeof(float) * nV * nH, w_cands + v * nH + h, sizeof(float) * nV * nH, sizeof(float), ncand));
-                }
-                wc = w_mix;
-            }
-            Pass ps = w_search_pass(round, h, wc, wc_cs, memo_w_on);
-            CHK(run_pass_pruned(c, ps));
-        }
-        if (memo_w_on && !skip_w) { CHK(read_dev(c, w_iv, nV * nH, val)); memo_w.entries.push_back({key, val}); g_memo_misses++; host_w = val; host_w_ok = true; }
-        else if (!skip_w) host_w_ok = false;
-        // ================= activation search (linear.py:497-533 / 609-642) =================
-        bool skip_a = false;
-        if (memo_a_on) {
-            if (host_w_ok) key = host_w; else CHK(read_dev(c, w_iv, nV * nH, key));
-            if (const auto* hit = memo_a.find(key)) { CHK(write_dev(c, a_iv, *hit)); skip_a = true; g_memo_hits++; host_a = *hit; host_a_ok = true; }
-        }
-        for (int a = 0; a < nA && !skip_a && (sg.mask & ST_S2); ++a) {
-            if (only_blk >= 0 && a != only_blk) continue;
-            if (segcos) { Pass sp = seg_cos_pass(round, 2, a); CHK(run_pass(c, sp)); continue; }
-            Pass ps{};
-            ps.i8 = i8; ps.twin = twin; ps.epi = epi; ps.wt_mode = wt_mode; ps.eq_n = d->eq_n; ps.K = K;
-            const float* ac = a_cands;
-            if (general && nA > 1) {
-                if (!c.dry) {
-                    ScaleParams mp{};
-                    mp.x = a_iv; mp.x_cs = 0; mp.x_js = 1; mp.y = nullptr; mp.y_const = 1.0f; mp.C = ncand; mp.nblk = nA; mp.S = a_mix;
-                    CHK(launch_scale(c, mp));
-                    CHK(q_copy2d(c, a_mix + a, sizeof(float) * nA, a_cands + a, sizeof(float) * nA, sizeof(float), ncand));
-                }
-                ac = a_mix;
-            }
-            ps.cache = (keep_planes && nA == 1) ? &plane_a : nullptr;
-            ps.ecache = keep_planes ? &epi_a : nullptr;
-            ps.nj = 1; ps.cands = a_cands; ps.cand_cs = nA; ps.cand_js = 0; ps.cand_off = a;
-            ps.interval = a_iv; ps.out_js = 0; ps.out_off = a;
-            ps.scores_out = (scores_out && a == tab_blk) ? scores_out + ((long)slot(round, 1) * d->eq_n) * nV : nullptr;
-            ps.scores_out_ld = nV;
-            ps.best_out = (best_out && a == tab_blk) ? best_out + (long)slot(round, 1) * nV : nullptr;
-            if (!cosm || cos6 || cos7) {
-                ps.Z = 1; ps.Mrows = M; ps.Ncols = N;
-                ps.row = x_operand(true, ac, nA);
-                if (twin) ps.row2 = xneg_operand();
-                ps.col = w_operand(false, w_iv, 0, false);
-                ps.use_s1 = i8; ps.s_cs = nV; ps.sb_mode = 1; ps.sb_div = crb_rows;
-                ps.s1 = ScaleParams{a_cands, 1, 0, 0.f, w_iv, 0, 1, 0.f, 0, 0, nullptr};
-                ps.s2 = ScaleParams{nullptr, 0, 0, a_neg, w_iv, 0, 1, 0.f, 0, 0, nullptr};
-                ps.bias = bias; ps.bias_axis = 0;
-                ps.O = O; ps.G = G; ps.o_ms = N; ps.o_ns = 1; ps.o_inner = INT_MAX;
-                ps.j_mode = 0;
-                ps.norm = 1.0 / ((double)d->tokens * N);
-                ps.prunable = !(d->reserved & 8); ps.scache = &slice; ps.scache2 = &slice2; ps.host_sync_ok = memo_a_on;
-                if (twin && wt_mode <= 1) {
-                    // Twin activation search: the negative-range plane and the weights are candidate-invariant, so
-                    // their product is folded into the target once (U = raw_out - bias - s_neg*s_w*(x_neg . W_q))
-                    // and the sweep runs on the positive-range plane alone: half the MFMA work of this pass.
-                    Pass fp = ps;
-                    fp.twin = false; fp.epi = EPI_STORE; fp.wt_mode = 0; fp.eq_n = 1;
-                    fp.row = xneg_operand(); fp.row2 = Operand{};
-                    fp.s1 = ps.s2;
-                    fp.store_out = Ufold; fp.cache = nullptr;
-                    fp.scores_out = nullptr; fp.best_out = nullptr;
-                    CHK(run_pass(c, fp));
-                    ps.twin = false; ps.row2 = Operand{};
-                    ps.O = Ufold; ps.bias = nullptr;
-                    // Ufold depends on the CURRENT w_interval: it is rebuilt for every activation pass that runs, so the
-                    // fragment-order image of k_sweep6's epilogue operands (built from ps.O) must be rebuilt with it
-                    ps.ecache = nullptr;
-                    slice.o_src = nullptr;          // ... and so are the gathered rows of the target in the sample slice
-                    slice2.o_src = nullptr;         // (both tiers: the second one compares the same pointer and would otherwise keep
-                                                    // the previous pass's target rows when two tier-2 activation passes follow each other)
-                }
-                if (cos6 || cos7) cos6_pass(ps, 0);
-            } else {
-                ps.Z = nV; ps.Mrows = crb_rows; ps.Ncols = M;
-                ps.row = w_operand(false, w_iv, 0, true);
-                ps.col = x_operand(true, ac, nA);
-                ps.col_zs_shared = 1;
-                ps.use_s1 = i8; ps.s_cs = nV; ps.sb_mode = 2; ps.sb_div = nV;
-                ps.s1 = ScaleParams{a_cands, 1, 0, 0.f, w_iv, 0, 1, 0.f, 0, 0, nullptr};
-                ps.bias = bias; ps.bias_axis = 1; ps.bias_zs = crb_rows;
-                ps.O = O; ps.o_zs = crb_rows; ps.o_ms = 1; ps.o_ns = N; ps.o_inner = INT_MAX;
-                ps.cos_ZB = 1; ps.cos_ZV = nV; ps.cos_j_mode = 0;
-                ps.norm = 1.0 / (double)d->tokens;
-            }
-            CHK(run_pass_pruned(c, ps));
-        }
-        if (memo_a_on && !skip_a) { CHK(read_dev(c, a_iv, nA, val)); memo_a.entries.push_back({key, val}); g_memo_misses++; host_a = val; host_a_ok = true; }
-        else if (!skip_a) host_a_ok = false;
-    }
+    if (L.segcos) CHK(enqueue(c, KERN(NchwRowsParams, k_nchw_to_rows), dim3(cdiv(L.N, 32), cdiv(L.M, 32), 1), dim3(256), 0, NchwRowsParams{O, L.M, L.N, L.Ot}));
+    for (int round = 0; round < R.n_rounds; ++round)
+        for (int side = 0; side < 2; ++side) CHK(L.search_side(side, round, memo[side], host));
     return 0;
 }
 
@@ -2813,36 +2881,62 @@ int matmul_blocks_impl(const p4v_matmul_desc* d, const MatMulBlocks& mb, const f
                        const float* mult, float* A_iv, float* B_iv, float* split, float* scores_out, int32_t* best_out, Ctx& c,
                        float* fwd_out, const Stage& sg);
 
-int matmul_impl(const p4v_matmul_desc* d, const float* A, const float* B, const float* O, const float* G,
-                const float* mult, float* A_iv, float* B_iv, float* split, float* scores_out, int32_t* best_out, Ctx& c,
-                float* fwd_out = nullptr, const Stage& sg = Stage{}, const MatMulBlocks* mb = nullptr) {
-    // fwd_out != nullptr: quant_forward (matmul.py:140-145; sos: matmul.py:595-598) -- intervals / split are INPUTS
-    const int H = d->heads, Z = d->batch * d->heads, M = d->M, K = d->K, N = d->N;
-    if (Z <= 0 || M <= 0 || K <= 0 || N <= 0 || d->eq_n <= 0) return fail(P4V_ERR_INVALID, "matmul: non-positive dimension");
-    if (d->A_bit > 8 || d->B_bit > 8 || d->A_bit < 2 || d->B_bit < 2) return fail(P4V_ERR_UNSUPPORTED, "matmul: bit widths 2..8 supported");
-    const int Aq = 1 << (d->A_bit - 1), Bq = 1 << (d->B_bit - 1);
-    int epi, wt_mode;
-    metric_epi(d->metric, &epi, &wt_mode);
-    const bool cosm = epi == EPI_COS;
-    if (wt_mode == 1 && !G && !fwd_out && sg.searches()) return fail(P4V_ERR_INVALID, "matmul: hessian metric needs raw_grad");
-    if (d->sos && !split) return fail(P4V_ERR_INVALID, "matmul: sos needs d_split");
-    cvt_bias(c);     // (first call of the process: probe the conversion quant16_sat8 relies on)
-    CHK(q_wait_inputs(c));     // (inside a group with a "capture done" event: everything below reads captured tensors)
-    // row / column sub-blocks: the K-segmented kernel family; with all four block counts 1 nothing below changes
-    if (mb && mb->any()) return matmul_blocks_impl(d, *mb, A, B, O, G, mult, A_iv, B_iv, split, scores_out, best_out, c, fwd_out, sg);
-    const int ncand = d->eq_n + 1;
-    const int NSPLIT = 20;  // matmul.py:636
+// One head-wise matmul_impl call: geometry, workspace and the builders of its passes.  Sides: 0 = the A search (with sos: the
+// split search), 1 = the B search.
+struct MatMulCall {
+    static constexpr int NSPLIT = 20;                 // matmul.py:636
+    Ctx& c;
+    const p4v_matmul_desc* d;
+    const Stage& sg;
+    int H = 0, Z = 0, M = 0, K = 0, N = 0;            // heads, batch x heads, the GEMM of one head
+    int Aq = 0, Bq = 0;                               // 2^(bit - 1)
+    int epi = 0, wt_mode = 0, ncand = 0;
+    bool cosm = false;
+    const float *A = nullptr, *B = nullptr, *O = nullptr, *G = nullptr, *mult = nullptr;
+    float *A_iv = nullptr, *B_iv = nullptr, *split = nullptr;   // intervals [heads] (sos: the scalar A_interval and the split)
+    float* fwd_out = nullptr;                         // quant_forward (matmul.py:140-145; sos: matmul.py:595-598): intervals / split are INPUTS
+    unsigned *enc_A = nullptr, *enc_B = nullptr;
+    float *A_cands_ws = nullptr, *B_cands_ws = nullptr;
+    const float *A_cands = nullptr, *B_cands = nullptr;         // built by this call, or the caller's (granular search)
+    float* split_cands = nullptr;                     // 2^-i, i < NSPLIT
+    float* A_headwise = nullptr;                      // sos: the inherited head-wise A interval is computed then overwritten (matmul.py:419-440)
+    SearchRounds rounds;
+    PlaneCache plane_A, plane_B;
+    SliceCache slice;
 
-    unsigned* enc_A = c.ws.get<unsigned>(H);
-    unsigned* enc_B = c.ws.get<unsigned>(H);
-    float* A_cands_ws = c.ws.get<float>((size_t)ncand * H);
-    float* B_cands_ws = c.ws.get<float>((size_t)ncand * H);
-    const float* A_cands = (sg.mask & ST_INIT) ? A_cands_ws : sg.cands1;
-    const float* B_cands = (sg.mask & ST_INIT) ? B_cands_ws : sg.cands2;
-    float* split_cands = c.ws.get<float>(NSPLIT);
-    float* A_headwise = c.ws.get<float>(H);   // sos: the inherited head-wise A interval is computed then overwritten (matmul.py:419-440)
-    if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small");
-    if (!fwd_out && (sg.mask & ST_INIT)) {
+    MatMulCall(Ctx& c_, const p4v_matmul_desc* d_, const Stage& sg_) : c(c_), d(d_), sg(sg_) {}
+
+    // argument checks and geometry
+    int build(const float* A_, const float* B_, const float* O_, const float* G_, const float* mult_, float* A_iv_, float* B_iv_,
+              float* split_, float* scores_out, int32_t* best_out, float* fwd_out_) {
+        A = A_; B = B_; O = O_; G = G_; mult = mult_; A_iv = A_iv_; B_iv = B_iv_; split = split_; fwd_out = fwd_out_;
+        H = d->heads; Z = d->batch * d->heads; M = d->M; K = d->K; N = d->N;
+        if (Z <= 0 || M <= 0 || K <= 0 || N <= 0 || d->eq_n <= 0) return fail(P4V_ERR_INVALID, "matmul: non-positive dimension");
+        if (d->A_bit > 8 || d->B_bit > 8 || d->A_bit < 2 || d->B_bit < 2) return fail(P4V_ERR_UNSUPPORTED, "matmul: bit widths 2..8 supported");
+        Aq = 1 << (d->A_bit - 1); Bq = 1 << (d->B_bit - 1);
+        metric_epi(d->metric, &epi, &wt_mode);
+        cosm = epi == EPI_COS;
+        if (wt_mode == 1 && !G && !fwd_out && sg.searches()) return fail(P4V_ERR_INVALID, "matmul: hessian metric needs raw_grad");
+        if (d->sos && !split) return fail(P4V_ERR_INVALID, "matmul: sos needs d_split");
+        ncand = d->eq_n + 1;
+        rounds = SearchRounds(sg, d->search_round, d->reserved, d->eq_n, H, c, scores_out, best_out);
+        return 0;
+    }
+    int workspace() {
+        enc_A = c.ws.get<unsigned>(H);
+        enc_B = c.ws.get<unsigned>(H);
+        A_cands_ws = c.ws.get<float>((size_t)ncand * H);
+        B_cands_ws = c.ws.get<float>((size_t)ncand * H);
+        A_cands = (sg.mask & ST_INIT) ? A_cands_ws : sg.cands1;
+        B_cands = (sg.mask & ST_INIT) ? B_cands_ws : sg.cands2;
+        split_cands = c.ws.get<float>(NSPLIT);
+        A_headwise = c.ws.get<float>(H);
+        if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small");
+        return 0;
+    }
+    // interval initialisation of both operands and their candidate tables
+    int init() {
+        if (fwd_out || !(sg.mask & ST_INIT)) return 0;
         const long sa[4] = {d->a_stride[0], d->a_stride[1], d->a_stride[2], d->a_stride[3]};
         const long sb[4] = {d->b_stride[0], d->b_stride[1], d->b_stride[2], d->b_stride[3]};
         float* a_dst = d->sos ? A_headwise : A_iv;
@@ -2854,51 +2948,61 @@ int matmul_impl(const p4v_matmul_desc* d, const float* A, const float* B, const 
             if (!d->sos) CHK(launch_cands(c, mult, A_iv, ncand, H, A_cands_ws));
             CHK(launch_cands(c, mult, B_iv, ncand, H, B_cands_ws));
         }
+        return 0;
     }
-    if (!fwd_out && !sg.searches()) return 0;
-    if (!fwd_out && (sg.mask & ST_S1)) {
-        if (d->sos && !c.dry) {
-            float sc[NSPLIT];
-            for (int i = 0; i < NSPLIT; ++i) sc[i] = (float)std::ldexp(1.0, -i);  // 2**(-i), exact in fp32
-            CHK(q_h2d(c, split_cands, sc, sizeof sc));
-            if (!c.grp) CHK(q_sync(c));          // sc lives on this stack frame (a group's queue holds a copy)
-        }
+    // the split candidates 2**(-i) of the split-of-softmax search
+    int upload_splits() {
+        if (fwd_out || !(sg.mask & ST_S1) || !d->sos || c.dry) return 0;
+        float sc[NSPLIT];
+        for (int i = 0; i < NSPLIT; ++i) sc[i] = (float)std::ldexp(1.0, -i);  // 2**(-i), exact in fp32
+        CHK(q_h2d(c, split_cands, sc, sizeof sc));
+        if (!c.grp) CHK(q_sync(c));          // sc lives on this stack frame (a group's queue holds a copy)
+        return 0;
     }
+
     // logical [Z][rows][K] views: A rows = m, B rows = n (B given as [K][N])
-    auto A_operand = [&](bool expanded, const float* scales, int sc_cs, int mode) {
+    Operand operand(const float* src, const int64_t* st, int r_ax, int k_ax, int R, int q, bool expanded, const float* scales, int sc_cs, int mode) const {
         Operand op{};
         op.present = true; op.expanded = expanded;
         op.pk = PackParams{};
-        op.pk.src = A; op.pk.s_z = d->a_stride[1]; op.pk.s_r = d->a_stride[2]; op.pk.s_k = d->a_stride[3];
-        op.pk.s_z2 = d->a_stride[0]; op.pk.zdiv = H;
-        op.pk.Z = Z; op.pk.R = M; op.pk.K = K; op.pk.nblk_r = 1; op.pk.nblk_k = 1;
+        op.pk.src = src; op.pk.s_z = st[1]; op.pk.s_r = st[r_ax]; op.pk.s_k = st[k_ax];
+        op.pk.s_z2 = st[0]; op.pk.zdiv = H;
+        op.pk.Z = Z; op.pk.R = R; op.pk.K = K; op.pk.nblk_r = 1; op.pk.nblk_k = 1;
         op.pk.mode = mode; op.pk.scales = scales; op.pk.sc_cs = sc_cs;
         op.pk.blk_mode = (mode == PACK_SYM) ? 2 : 0; op.pk.blk_div = H;
-        op.pk.lo = -Aq; op.pk.hi = Aq - 1; op.pk.qm1 = (float)(Aq - 1);
+        op.pk.lo = -q; op.pk.hi = q - 1;
         return op;
-    };
-    auto B_operand = [&](bool expanded, const float* scales, int sc_cs, int mode) {
-        Operand op{};
-        op.present = true; op.expanded = expanded;
-        op.pk = PackParams{};
-        op.pk.src = B; op.pk.s_z = d->b_stride[1]; op.pk.s_r = d->b_stride[3]; op.pk.s_k = d->b_stride[2];
-        op.pk.s_z2 = d->b_stride[0]; op.pk.zdiv = H;
-        op.pk.Z = Z; op.pk.R = N; op.pk.K = K; op.pk.nblk_r = 1; op.pk.nblk_k = 1;
-        op.pk.mode = mode; op.pk.scales = scales; op.pk.sc_cs = sc_cs;
-        op.pk.blk_mode = (mode == PACK_SYM) ? 2 : 0; op.pk.blk_div = H;
-        op.pk.lo = -Bq; op.pk.hi = Bq - 1;
+    }
+    Operand A_operand(bool expanded, const float* scales, int sc_cs, int mode) const {
+        Operand op = operand(A, d->a_stride, 2, 3, M, Aq, expanded, scales, sc_cs, mode);
+        op.pk.qm1 = (float)(Aq - 1);
         return op;
-    };
-    auto common = [&](Pass& ps) {
+    }
+    Operand B_operand(bool expanded, const float* scales, int sc_cs, int mode) const {
+        return operand(B, d->b_stride, 3, 2, N, Bq, expanded, scales, sc_cs, mode);
+    }
+    // what every search pass shares: the GEMM and its target; cosine runs swapped (rows = n)
+    void common(Pass& ps) const {
         ps.Z = Z; ps.K = K;
         ps.O = O; ps.G = G; ps.wt_mode = wt_mode; ps.epi = epi;
         ps.o_inner = INT_MAX;
         if (!cosm) { ps.Mrows = M; ps.Ncols = N; ps.o_zs = (long)M * N; ps.o_ms = N; ps.o_ns = 1; }
         else { ps.Mrows = N; ps.Ncols = M; ps.o_zs = (long)M * N; ps.o_ms = 1; ps.o_ns = N; ps.G = nullptr;
                ps.cos_ZB = Z; ps.cos_ZV = 1; }
-    };
+    }
+    // A on the rows and B on the columns, or swapped for cosine
+    void place(Pass& ps, const Operand& a, const Operand& b) const {
+        if (!cosm) { ps.row = a; ps.col = b; } else { ps.row = b; ps.col = a; }
+    }
+    // ... and one score, one candidate column, one interval per head
+    void per_head(Pass& ps, const float* cands, float* interval) const {
+        ps.j_mode = 2; ps.j_div = H; ps.nj = H; ps.cos_j_mode = 2; ps.cos_j_div = H;
+        ps.norm = cosm ? 1.0 / (double)M : 1.0 / ((double)M * N);
+        ps.cands = cands; ps.cand_cs = H; ps.cand_js = 1; ps.interval = interval; ps.out_js = 1;
+        ps.scores_out_ld = H;
+    }
 
-    if (fwd_out) {
+    Pass forward_pass() const {
         Pass fp{};
         fp.Z = Z; fp.K = K; fp.Mrows = M; fp.Ncols = N;
         fp.i8 = true; fp.twin = d->sos; fp.epi = EPI_FWD; fp.wt_mode = 0; fp.eq_n = 1;
@@ -2913,121 +3017,124 @@ int matmul_impl(const p4v_matmul_desc* d, const float* A, const float* B, const 
         }
         fp.O = fwd_out; fp.G = nullptr; fp.o_zs = (long)M * N; fp.o_ms = N; fp.o_ns = 1; fp.o_inner = INT_MAX;
         fp.nj = 1; fp.store_out = fwd_out;
-        return run_pass(c, fp);
+        return fp;
     }
-    const bool memo_on = sg.full() && !c.dry && !scores_out && !best_out && !(d->reserved & 2);
-    PassMemo memo_A, memo_B;
-    MirrorScope mirrors(c, memo_on, A_iv, B_iv, d->sos ? split : nullptr);
-    PlaneCache plane_A, plane_B;
-    SliceCache slice;
-    const bool keep_planes = sg.full() && d->search_round > 1;
-    std::vector<float> key, val;
-    const int nAiv = d->sos ? 1 : H;
-    const int n_rounds = sg.full() ? d->search_round : 1;
-    for (int round = 0; round < n_rounds; ++round) {
-        float* so = scores_out ? scores_out + ((long)(round * 2) * d->eq_n) * H : nullptr;
-        int32_t* bo = best_out ? best_out + (long)(round * 2) * H : nullptr;
-        // granular call: the one table of this call starts at offset 0 (the B pass below adds eq_n*H / H otherwise)
-        float* so_B = so ? (sg.full() ? so + (long)d->eq_n * H : so) : nullptr;
-        int32_t* bo_B = bo ? (sg.full() ? bo + H : bo) : nullptr;
-        // the A search (or, with sos, the split search against the RAW B: a function of nothing -> always a hit after round 1)
-        bool skip_A = false;
-        if (memo_on) {
-            if (d->sos) key.assign(1, 0.0f); else CHK(read_dev(c, B_iv, H, key));
-            if (const auto* hit = memo_A.find(key)) {
-                if (d->sos) { std::vector<float> sp(1, (*hit)[0]), ai(1, (*hit)[1]); CHK(write_dev(c, split, sp)); CHK(write_dev(c, A_iv, ai)); }
-                else CHK(write_dev(c, A_iv, *hit));
-                skip_A = true; g_memo_hits++;
-            }
+    // A search, B fixed at its current head-wise interval (matmul.py:483-522)
+    Pass A_pass(int round) {
+        Pass ps{};
+        common(ps);
+        ps.i8 = true; ps.twin = false; ps.eq_n = d->eq_n;
+        place(ps, A_operand(true, A_cands, H, PACK_SYM), B_operand(false, B_iv, 0, PACK_SYM));
+        ps.use_s1 = true; ps.s_cs = H; ps.sb_mode = 2; ps.sb_div = H;
+        ps.s1 = ScaleParams{A_cands, H, 1, 0.f, B_iv, 0, 1, 0.f, 0, 0, nullptr};
+        per_head(ps, A_cands, A_iv);
+        ps.cache = rounds.keep_planes ? &plane_A : nullptr;
+        ps.scores_out = rounds.scores_of(round, 0); ps.best_out = rounds.best_of(round, 0);
+        ps.prunable = !cosm && !(d->reserved & 8); ps.scache = &slice; ps.host_sync_ok = rounds.memo_on;
+        return ps;
+    }
+    // split search against the UNQUANTISED B (matmul.py:600-631): A quantised in registers, one kernel (k_sos_split)
+    SosSplitJob split_job(int round) {
+        SosSplitJob j{};
+        j.kp.A = A; j.kp.a_z2 = d->a_stride[0]; j.kp.a_z = d->a_stride[1]; j.kp.a_r = d->a_stride[2]; j.kp.a_k = d->a_stride[3];
+        j.kp.zdiv = H;
+        j.kp.B = B; j.kp.b_z2 = d->b_stride[0]; j.kp.b_z = d->b_stride[1]; j.kp.b_k = d->b_stride[2]; j.kp.b_n = d->b_stride[3];
+        j.kp.O = O; j.kp.G = G ? G : O;
+        j.kp.Z = Z; j.kp.M = M; j.kp.K = K; j.kp.N = N; j.kp.wt_mode = wt_mode; j.kp.C = NSPLIT;
+        j.kp.splits = split_cands;
+        j.kp.qm1 = (float)(Aq - 1); j.kp.c_inv = 1.0f / (float)(Aq - 1);
+        j.kp.lo_top = std::min(std::nearbyintf(1.0f / j.kp.c_inv), (float)(Aq - 1));
+        j.kp.halves = cdiv(M, 128);
+        j.epi = epi; j.norm = 1.0 / ((double)H * M * N);
+        j.cands = split_cands; j.split = split; j.A_iv = A_iv; j.aux_div = (float)(Aq - 1);   // A_interval = split/(qmax-1) (matmul.py:629)
+        j.scores_out = (d->eq_n >= NSPLIT) ? rounds.scores_of(round, 0) : nullptr; j.scores_out_ld = H; j.best_out = rounds.best_of(round, 0);
+        j.scache = &slice; j.host_sync_ok = rounds.memo_on; j.prunable = !(d->reserved & 8);
+        return j;
+    }
+    // ... the same search on fp32 operands (shapes k_sos_split has no instance for, cosine)
+    Pass split_pass_f32(int round) {
+        Pass ps{};
+        common(ps);
+        ps.i8 = false; ps.twin = false; ps.eq_n = NSPLIT;
+        place(ps, A_operand(true, split_cands, 1, PACK_SOS_SIM), B_operand(false, nullptr, 0, PACK_RAW));
+        ps.use_s1 = false; ps.s_cs = 1; ps.sb_mode = 0;
+        ps.j_mode = 0; ps.nj = 1; ps.cos_j_mode = 0;
+        ps.norm = cosm ? 1.0 / ((double)H * M) : 1.0 / ((double)H * M * N);
+        ps.cands = split_cands; ps.cand_cs = 1; ps.cand_js = 0; ps.interval = split; ps.out_js = 0;
+        ps.aux_out = A_iv; ps.aux_div = (float)(Aq - 1);   // A_interval = split/(qmax-1) (matmul.py:629)
+        ps.scores_out = (d->eq_n >= NSPLIT) ? rounds.scores_of(round, 0) : nullptr; ps.scores_out_ld = H; ps.best_out = rounds.best_of(round, 0);
+        return ps;
+    }
+    // B search, A fixed (matmul.py:524-563); with sos, A is the two-range twin (matmul.py:595-598)
+    Pass B_pass(int round) {
+        Pass ps{};
+        common(ps);
+        ps.eq_n = d->eq_n;
+        const bool twin_rows = d->sos && !cosm;
+        ps.i8 = !(d->sos && cosm);   // cosine + sos: fp32 operands (the twin sits on the column side when swapped)
+        ps.twin = twin_rows;
+        place(ps, d->sos ? A_operand(false, split, 0, ps.i8 ? PACK_SOS_HI : PACK_SOS_SIM) : A_operand(false, A_iv, 0, PACK_SYM),
+              B_operand(true, B_cands, H, PACK_SYM));
+        if (twin_rows) ps.row2 = A_operand(false, split, 0, PACK_SOS_LO);
+        ps.use_s1 = ps.i8; ps.s_cs = H; ps.sb_mode = 2; ps.sb_div = H;
+        if (!d->sos) ps.s1 = ScaleParams{A_iv, 0, 1, 0.f, B_cands, H, 1, 0.f, 0, 0, nullptr};
+        else {
+            // high range: k_hi/(q-1) ; low range: k_lo * (split/(q-1)) = k_lo * A_interval
+            ps.s1 = ScaleParams{nullptr, 0, 0, 1.0f / (float)(Aq - 1), B_cands, H, 1, 0.f, 0, 0, nullptr};
+            ps.s2 = ScaleParams{A_iv, 0, 0, 0.f, B_cands, H, 1, 0.f, 0, 0, nullptr};
         }
-        if (skip_A || !(sg.mask & ST_S1)) {
+        per_head(ps, B_cands, B_iv);
+        ps.cache = rounds.keep_planes ? &plane_B : nullptr;
+        ps.scores_out = rounds.scores_of(round, 1); ps.best_out = rounds.best_of(round, 1);
+        ps.prunable = !cosm && ps.i8 && !(d->reserved & 8); ps.scache = &slice; ps.host_sync_ok = rounds.memo_on;
+        return ps;
+    }
+};
+
+int matmul_impl(const p4v_matmul_desc* d, const float* A, const float* B, const float* O, const float* G,
+                const float* mult, float* A_iv, float* B_iv, float* split, float* scores_out, int32_t* best_out, Ctx& c,
+                float* fwd_out = nullptr, const Stage& sg = Stage{}, const MatMulBlocks* mb = nullptr) {
+    MatMulCall m(c, d, sg);
+    CHK(m.build(A, B, O, G, mult, A_iv, B_iv, split, scores_out, best_out, fwd_out));
+    cvt_bias(c);     // (first call of the process: probe the conversion quant16_sat8 relies on)
+    CHK(q_wait_inputs(c));     // (inside a group with a "capture done" event: everything below reads captured tensors)
+    // row / column sub-blocks: the K-segmented kernel family; with all four block counts 1 nothing below changes
+    if (mb && mb->any()) return matmul_blocks_impl(d, *mb, A, B, O, G, mult, A_iv, B_iv, split, scores_out, best_out, c, fwd_out, sg);
+    CHK(m.workspace());
+    CHK(m.init());
+    if (!fwd_out && !sg.searches()) return 0;
+    CHK(m.upload_splits());
+    if (fwd_out) { Pass fp = m.forward_pass(); return run_pass(c, fp); }
+    const SearchRounds& R = m.rounds;
+    MirrorScope mirrors(c, R.memo_on, A_iv, B_iv, d->sos ? split : nullptr);
+    const int H = m.H, nAiv = d->sos ? 1 : H;
+    // the A search is a function of B's interval; with sos it is the split search against the RAW B: a function of nothing ->
+    // always a hit after round 1, its value the split and the A interval derived from it
+    MemoSide memo_A, memo_B;
+    memo_A.on = memo_B.on = R.memo_on;
+    const DevVecs key_A = d->sos ? DevVecs() : DevVecs(B_iv, H), val_A = d->sos ? DevVecs(split, 1, A_iv, 1) : DevVecs(A_iv, nAiv);
+    const DevVecs key_B(A_iv, nAiv), val_B(B_iv, H);
+    for (int round = 0; round < R.n_rounds; ++round) {
+        bool hit = false;
+        CHK(memo_A.restore(c, key_A, nullptr, val_A, nullptr, &hit));
+        if (hit || !(sg.mask & ST_S1)) {
         } else if (!d->sos) {
-            // ---- A search, B fixed at its current head-wise interval (matmul.py:483-522) ----
-            Pass ps{};
-            common(ps);
-            ps.i8 = true; ps.twin = false; ps.eq_n = d->eq_n;
-            Operand a = A_operand(true, A_cands, H, PACK_SYM), b = B_operand(false, B_iv, 0, PACK_SYM);
-            if (!cosm) { ps.row = a; ps.col = b; } else { ps.row = b; ps.col = a; }
-            ps.use_s1 = true; ps.s_cs = H; ps.sb_mode = 2; ps.sb_div = H;
-            ps.s1 = ScaleParams{A_cands, H, 1, 0.f, B_iv, 0, 1, 0.f, 0, 0, nullptr};
-            ps.j_mode = 2; ps.j_div = H; ps.nj = H; ps.cos_j_mode = 2; ps.cos_j_div = H;
-            ps.norm = cosm ? 1.0 / (double)M : 1.0 / ((double)M * N);
-            ps.cands = A_cands; ps.cand_cs = H; ps.cand_js = 1; ps.interval = A_iv; ps.out_js = 1;
-            ps.cache = keep_planes ? &plane_A : nullptr;
-            ps.scores_out = so; ps.scores_out_ld = H; ps.best_out = bo;
-            ps.prunable = !cosm && !(d->reserved & 8); ps.scache = &slice; ps.host_sync_ok = memo_on;
+            Pass ps = m.A_pass(round);
             CHK(run_pass_pruned(c, ps));
-        } else if (sos_split_ok(M, K, N, cosm)) {
-            // ---- split search against the UNQUANTISED B (matmul.py:600-631): A quantised in registers, one kernel ----
-            SosSplitJob j{};
-            j.kp.A = A; j.kp.a_z2 = d->a_stride[0]; j.kp.a_z = d->a_stride[1]; j.kp.a_r = d->a_stride[2]; j.kp.a_k = d->a_stride[3];
-            j.kp.zdiv = H;
-            j.kp.B = B; j.kp.b_z2 = d->b_stride[0]; j.kp.b_z = d->b_stride[1]; j.kp.b_k = d->b_stride[2]; j.kp.b_n = d->b_stride[3];
-            j.kp.O = O; j.kp.G = G ? G : O;
-            j.kp.Z = Z; j.kp.M = M; j.kp.K = K; j.kp.N = N; j.kp.wt_mode = wt_mode; j.kp.C = NSPLIT;
-            j.kp.splits = split_cands;
-            j.kp.qm1 = (float)(Aq - 1); j.kp.c_inv = 1.0f / (float)(Aq - 1);
-            j.kp.lo_top = std::min(std::nearbyintf(1.0f / j.kp.c_inv), (float)(Aq - 1));
-            j.kp.halves = cdiv(M, 128);
-            j.epi = epi; j.norm = 1.0 / ((double)H * M * N);
-            j.cands = split_cands; j.split = split; j.A_iv = A_iv; j.aux_div = (float)(Aq - 1);   // A_interval = split/(qmax-1) (matmul.py:629)
-            j.scores_out = (d->eq_n >= NSPLIT) ? so : nullptr; j.scores_out_ld = H; j.best_out = bo;
-            j.scache = &slice; j.host_sync_ok = memo_on; j.prunable = !(d->reserved & 8);
+        } else if (sos_split_ok(m.M, m.K, m.N, m.cosm)) {
+            SosSplitJob j = m.split_job(round);
             if (g_sos_debug) return c.grp || c.dry ? fail(P4V_ERR_INVALID, "p4v_debug_sos_sweep: not inside a group") : run_sos_debug_sweep(c, j, *g_sos_debug);
             CHK(run_sos_split_pruned(c, j));
         } else {
-            // ---- split search against the UNQUANTISED B (matmul.py:600-631): fp32 operands ----
-            Pass ps{};
-            common(ps);
-            ps.i8 = false; ps.twin = false; ps.eq_n = NSPLIT;
-            Operand a = A_operand(true, split_cands, 1, PACK_SOS_SIM), b = B_operand(false, nullptr, 0, PACK_RAW);
-            if (!cosm) { ps.row = a; ps.col = b; } else { ps.row = b; ps.col = a; }
-            ps.use_s1 = false; ps.s_cs = 1; ps.sb_mode = 0;
-            ps.j_mode = 0; ps.nj = 1; ps.cos_j_mode = 0;
-            ps.norm = cosm ? 1.0 / ((double)H * M) : 1.0 / ((double)H * M * N);
-            ps.cands = split_cands; ps.cand_cs = 1; ps.cand_js = 0; ps.interval = split; ps.out_js = 0;
-            ps.aux_out = A_iv; ps.aux_div = (float)(Aq - 1);   // A_interval = split/(qmax-1) (matmul.py:629)
-            ps.scores_out = (d->eq_n >= NSPLIT) ? so : nullptr; ps.scores_out_ld = H; ps.best_out = bo;
+            Pass ps = m.split_pass_f32(round);
             CHK(run_pass(c, ps));
         }
-        if (memo_on && !skip_A) {   // (memo_on implies a full run)
-            if (d->sos) { std::vector<float> sp, ai; CHK(read_dev(c, split, 1, sp)); CHK(read_dev(c, A_iv, 1, ai)); val = {sp[0], ai[0]}; }
-            else CHK(read_dev(c, A_iv, nAiv, val));
-            memo_A.entries.push_back({key, val}); g_memo_misses++;
-        }
-        bool skip_B = false;
-        if (memo_on) {
-            CHK(read_dev(c, A_iv, nAiv, key));
-            if (const auto* hit = memo_B.find(key)) { CHK(write_dev(c, B_iv, *hit)); skip_B = true; g_memo_hits++; }
-        }
-        if (!skip_B && (sg.mask & ST_S2)) {
-            // ---- B search, A fixed (matmul.py:524-563); with sos, A is the two-range twin (matmul.py:595-598) ----
-            Pass ps{};
-            common(ps);
-            ps.eq_n = d->eq_n;
-            const bool twin_rows = d->sos && !cosm;
-            ps.i8 = !(d->sos && cosm);   // cosine + sos: fp32 operands (the twin sits on the column side when swapped)
-            ps.twin = twin_rows;
-            Operand b = B_operand(true, B_cands, H, PACK_SYM);
-            Operand a = d->sos ? A_operand(false, split, 0, ps.i8 ? PACK_SOS_HI : PACK_SOS_SIM) : A_operand(false, A_iv, 0, PACK_SYM);
-            if (!cosm) { ps.row = a; ps.col = b; if (twin_rows) ps.row2 = A_operand(false, split, 0, PACK_SOS_LO); }
-            else { ps.row = b; ps.col = a; }
-            ps.use_s1 = ps.i8; ps.s_cs = H; ps.sb_mode = 2; ps.sb_div = H;
-            if (!d->sos) ps.s1 = ScaleParams{A_iv, 0, 1, 0.f, B_cands, H, 1, 0.f, 0, 0, nullptr};
-            else {
-                // high range: k_hi/(q-1) ; low range: k_lo * (split/(q-1)) = k_lo * A_interval
-                ps.s1 = ScaleParams{nullptr, 0, 0, 1.0f / (float)(Aq - 1), B_cands, H, 1, 0.f, 0, 0, nullptr};
-                ps.s2 = ScaleParams{A_iv, 0, 0, 0.f, B_cands, H, 1, 0.f, 0, 0, nullptr};
-            }
-            ps.j_mode = 2; ps.j_div = H; ps.nj = H; ps.cos_j_mode = 2; ps.cos_j_div = H;
-            ps.norm = cosm ? 1.0 / (double)M : 1.0 / ((double)M * N);
-            ps.cands = B_cands; ps.cand_cs = H; ps.cand_js = 1; ps.interval = B_iv; ps.out_js = 1;
-            ps.cache = keep_planes ? &plane_B : nullptr;
-            ps.scores_out = so_B; ps.scores_out_ld = H;
-            ps.best_out = bo_B;
-            ps.prunable = !cosm && ps.i8 && !(d->reserved & 8); ps.scache = &slice; ps.host_sync_ok = memo_on;
+        if (!hit) CHK(memo_A.record(c, val_A, nullptr));   // (a memo that is on implies a full run)
+        CHK(memo_B.restore(c, key_B, nullptr, val_B, nullptr, &hit));
+        if (!hit && (sg.mask & ST_S2)) {
+            Pass ps = m.B_pass(round);
             CHK(run_pass_pruned(c, ps));
-            if (memo_on) { CHK(read_dev(c, B_iv, H, val)); memo_B.entries.push_back({key, val}); g_memo_misses++; }
+            CHK(memo_B.record(c, val_B, nullptr));
         }
     }
     return 0;
@@ -3117,10 +3224,11 @@ int matmul_blocks_impl(const p4v_matmul_desc* d, const MatMulBlocks& mb, const f
         return 0;
     }
     const int stepsA = d->sos ? 1 : nVA * nHA, steps = stepsA + nVB * nHB;
+    const SearchRounds tabs(sg, d->search_round, d->reserved, d->eq_n, H, c, scores_out, best_out, steps);   // tables [round][step]
     for (int round = 0; round < d->search_round; ++round) {
         int st = 0;
-        auto so = [&](int s) { return scores_out ? scores_out + ((long)(round * steps + s) * d->eq_n) * H : nullptr; };
-        auto bo = [&](int s) { return best_out ? best_out + (long)(round * steps + s) * H : nullptr; };
+        auto so = [&](int s) { return tabs.scores_of(round, s); };
+        auto bo = [&](int s) { return tabs.best_of(round, s); };
         if (d->sos) {
             // the split search against the UNQUANTISED B (matmul.py:600-631) knows no blocks: the head-wise engine's pass
             const size_t mark = c.ws.off;
@@ -3252,26 +3360,20 @@ int conv_impl(const p4v_conv_desc* d, const float* W, const float* bias, const f
         }
     };
 
-    const bool memo_on = sg.full() && !c.dry && !scores_out && !best_out && !(d->reserved & 2);
-    PassMemo memo_w, memo_a;
+    const SearchRounds R(sg, d->search_round, d->reserved, d->eq_n, nw, c, scores_out, best_out);
+    const bool memo_on = R.memo_on, keep_planes = R.keep_planes;
     MirrorScope mirrors(c, memo_on, w_iv, a_iv);
     PlaneCache plane_w, plane_a;
     SliceCache slice;
-    const bool keep_planes = sg.full() && d->search_round > 1;
-    std::vector<float> key, val;
-    const int n_rounds = sg.full() ? d->search_round : 1;
-    for (int round = 0; round < n_rounds; ++round) {
-        float* so = scores_out ? scores_out + ((long)(round * 2) * d->eq_n) * nw : nullptr;
-        int32_t* bo = best_out ? best_out + (long)(round * 2) * nw : nullptr;
-        float* so_a = so ? (sg.full() ? so + (long)d->eq_n * nw : so) : nullptr;
-        int32_t* bo_a = bo ? (sg.full() ? bo + nw : bo) : nullptr;
-        bool skip_w = false;
-        if (memo_on) {
-            // with a_bit >= 32 the input is never quantised: the weight search depends on nothing (conv.py:544)
-            if (aquant) CHK(read_dev(c, a_iv, 1, key)); else key.assign(1, 0.0f);
-            if (const auto* hit = memo_w.find(key)) { CHK(write_dev(c, w_iv, *hit)); skip_w = true; g_memo_hits++; }
-        }
-        if (!skip_w && (sg.mask & ST_S1)) {   // ---- weight search (conv.py:526-557 / 365-396) ----
+    MemoSide memo_w, memo_a;
+    memo_w.on = memo_on;
+    memo_a.on = memo_on && aquant;
+    // with a_bit >= 32 the input is never quantised: the weight search depends on nothing (conv.py:544)
+    const DevVecs key_w = aquant ? DevVecs(a_iv, 1) : DevVecs(), val_w(w_iv, nw), key_a(w_iv, nw), val_a(a_iv, 1);
+    for (int round = 0; round < R.n_rounds; ++round) {
+        bool hit = false;
+        CHK(memo_w.restore(c, key_w, nullptr, val_w, nullptr, &hit));
+        if (!hit && (sg.mask & ST_S1)) {   // ---- weight search (conv.py:526-557 / 365-396) ----
             Pass ps{};
             setup(ps, true);
             ps.nj = nw;
@@ -3280,26 +3382,21 @@ int conv_impl(const p4v_conv_desc* d, const float* W, const float* bias, const f
             else { ps.cos_j_mode = 0; ps.norm = 1.0 / (double)L; }
             ps.cands = w_cands; ps.cand_cs = nw; ps.cand_js = 1; ps.interval = w_iv; ps.out_js = 1;
             ps.cache = keep_planes ? &plane_w : nullptr;
-            ps.scores_out = so; ps.scores_out_ld = nw; ps.best_out = bo;
+            ps.scores_out = R.scores_of(round, 0); ps.scores_out_ld = nw; ps.best_out = R.best_of(round, 0);
             ps.prunable = ps.prunable_f32 = prunable; ps.scache = &slice; ps.host_sync_ok = memo_on;
             CHK(run_pass_pruned(c, ps));
-            if (memo_on) { CHK(read_dev(c, w_iv, nw, val)); memo_w.entries.push_back({key, val}); g_memo_misses++; }
+            CHK(memo_w.record(c, val_w, nullptr));
         }
-        bool skip_a = false;
-        if (memo_on && aquant) {
-            CHK(read_dev(c, w_iv, nw, key));
-            if (const auto* hit = memo_a.find(key)) { CHK(write_dev(c, a_iv, *hit)); skip_a = true; g_memo_hits++; }
-        }
-        if (aquant && !skip_a && (sg.mask & ST_S2)) {  // ---- activation search (conv.py:559-589), channel-wise class only ----
+        CHK(memo_a.restore(c, key_a, nullptr, val_a, nullptr, &hit));
+        if (aquant && !hit && (sg.mask & ST_S2)) {  // ---- activation search (conv.py:559-589), channel-wise class only ----
             Pass ps{};
             setup(ps, false);
             ps.nj = 1; ps.j_mode = 0; ps.norm = 1.0 / ((double)L * oc);
             ps.cands = a_cands; ps.cand_cs = 1; ps.cand_js = 0; ps.interval = a_iv; ps.out_js = 0;
             ps.cache = keep_planes ? &plane_a : nullptr;
-            ps.scores_out = so_a; ps.scores_out_ld = nw;
-            ps.best_out = bo_a;
+            ps.scores_out = R.scores_of(round, 1); ps.scores_out_ld = nw; ps.best_out = R.best_of(round, 1);
             CHK(run_pass(c, ps));
-            if (memo_on) { CHK(read_dev(c, a_iv, 1, val)); memo_a.entries.push_back({key, val}); g_memo_misses++; }
+            CHK(memo_a.record(c, val_a, nullptr));
         }
     }
     return 0;

@@ -30,16 +30,21 @@ def _grad(shape, g, token_dim):
     return grad
 
 
+def linear_inputs(K, N, *, seed, images=2, tokens=64, postgelu=False):
+    """(weight, bias, x, out, grad) of a seeded Linear layer, on the host"""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(images, tokens, K, generator=g)
+    if postgelu:
+        x = F.gelu(1.5 * x)
+    w = torch.randn(N, K, generator=g) * 0.05 * torch.linspace(0.6, 1.5, N)[:, None]
+    b = torch.randn(N, generator=g) * 0.1
+    out = F.linear(x, w, b)
+    return w, b, x, out, _grad(out.shape, g, 1)
+
+
 def _linear(K, N, *, seed, images=2, tokens=64, n_V=1, postgelu=False, variant=0):
     def run(eng, prune):
-        g = torch.Generator().manual_seed(seed)
-        x = torch.randn(images, tokens, K, generator=g)
-        if postgelu:
-            x = F.gelu(1.5 * x)
-        w = torch.randn(N, K, generator=g) * 0.05 * torch.linspace(0.6, 1.5, N)[:, None]
-        b = torch.randn(N, generator=g) * 0.1
-        out = F.linear(x, w, b)
-        grad = _grad(out.shape, g, 1)
+        w, b, x, out, grad = linear_inputs(K, N, seed=seed, images=images, tokens=tokens, postgelu=postgelu)
         eng.debug_variant(variant)
         try:
             res = eng.linear_calibrate(weight=_cuda(w), bias=_cuda(b), x=_cuda(x), out=_cuda(out), grad=_cuda(grad), w_bit=8, a_bit=8,
@@ -51,17 +56,22 @@ def _linear(K, N, *, seed, images=2, tokens=64, n_V=1, postgelu=False, variant=0
     return run
 
 
+def matmul_inputs(M, K, N, *, seed, sos=False, batch=2, heads=2):
+    """(A, B, out, grad) of a seeded MatMul, on the host: q.k^T with k transposed in memory, or softmax rows times v"""
+    g = torch.Generator().manual_seed(seed)
+    if sos:
+        A = torch.softmax(torch.randn(batch, heads, M, K, generator=g) * 3.0, dim=-1)
+        B = torch.randn(batch, heads, K, N, generator=g)
+    else:
+        A = torch.randn(batch, heads, M, K, generator=g)
+        B = torch.randn(batch, heads, N, K, generator=g).transpose(-2, -1)
+    out = A @ B
+    return A, B, out, _grad(out.shape, g, 2)
+
+
 def _matmul(M, K, N, *, seed, sos=False, batch=2, heads=2):
     def run(eng, prune):
-        g = torch.Generator().manual_seed(seed)
-        if sos:
-            A = torch.softmax(torch.randn(batch, heads, M, K, generator=g) * 3.0, dim=-1)
-            B = torch.randn(batch, heads, K, N, generator=g)
-        else:
-            A = torch.randn(batch, heads, M, K, generator=g)
-            B = torch.randn(batch, heads, N, K, generator=g).transpose(-2, -1)
-        out = A @ B
-        grad = _grad(out.shape, g, 2)
+        A, B, out, grad = matmul_inputs(M, K, N, seed=seed, sos=sos, batch=batch, heads=heads)
         res = eng.matmul_calibrate(A=_cuda(A), B=_cuda(B), out=_cuda(out), grad=_cuda(grad), A_bit=8, B_bit=8, metric="hessian",
                                    sos=sos, prune=prune, want_scores=not prune, **SEARCH)
         return [t for t in res if t is not None]
@@ -81,14 +91,19 @@ def _matmul_blocks(name):
     return run
 
 
+def conv_inputs(*, seed):
+    """(weight, bias, x, out, grad) of the seeded 2 x 3 x 32 x 32, 16-filter patch embedding, on the host"""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(2, 3, 32, 32, generator=g)
+    w = torch.randn(16, 3, 16, 16, generator=g) * 0.02 * torch.linspace(0.5, 2.0, 16).view(-1, 1, 1, 1)
+    b = torch.randn(16, generator=g) * 0.02
+    out = F.conv2d(x, w, b, stride=16)
+    return w, b, x, out, torch.randn(out.shape, generator=g) * 1e-10
+
+
 def _conv(*, seed):
     def run(eng, prune):
-        g = torch.Generator().manual_seed(seed)
-        x = torch.randn(2, 3, 32, 32, generator=g)
-        w = torch.randn(16, 3, 16, 16, generator=g) * 0.02 * torch.linspace(0.5, 2.0, 16).view(-1, 1, 1, 1)
-        b = torch.randn(16, generator=g) * 0.02
-        out = F.conv2d(x, w, b, stride=16)
-        grad = torch.randn(out.shape, generator=g) * 1e-10
+        w, b, x, out, grad = conv_inputs(seed=seed)
         res = eng.conv_calibrate(weight=_cuda(w), bias=_cuda(b), x=_cuda(x), out=_cuda(out), grad=_cuda(grad), stride=(16, 16),
                                  padding=(0, 0), dilation=(1, 1), w_bit=8, a_bit=32, metric="hessian", prune=prune,
                                  want_scores=not prune, **SEARCH)

@@ -5,7 +5,8 @@ small shapes of tests/sweep_plan_cases.py, the layers of ViT-B / DeiT-T / Swin-T
 calibrates them; metrics, blocks, pruning on / off, fp32 planes -- the sizes do not depend on the bit width).
 --gpu: also the cases of tests/sweep_plan_cases.py, pruning off and on: launch records (kernel, stage, grid_x, grid_z) in order,
 p4v_launch_counters, p4v_prune_counters, and the raw bytes of the returned intervals, score tables and selections (as hex where
-they are at most 16 bytes, as a sha256 prefix otherwise).  No timings: two runs of the same code give the same file.
+they are at most 16 bytes, as a sha256 prefix otherwise); then the three-round cases of tests/search_round_cases.py in each of
+their modes, with the pass memo's (hits, misses) as well.  No timings: two runs of the same code give the same file.
 
     python tools/plan_dump.py [--gpu] [--out FILE]
 """
@@ -122,6 +123,14 @@ def gpu_plan():
                      "launch_counters": [launches[k] for k in ("asked", "issued", "rounds", "groups")],
                      "prune_counters": [pruned[k] for k in ("staged", "staged_no_survivors", "kept_full_sweep", "not_eligible")],
                      "results": [_raw(t) for t in res]})
+        engine.release_workspace()
+    from tests.search_round_cases import CASES as ROUND_CASES, MODES, run_case as run_rounds
+    for (name, run), mode in itertools.product(ROUND_CASES, MODES):
+        r = run_rounds(engine, run, mode)
+        rows.append({"case": name, "mode": mode, "records": _runs(r["records"]),
+                     "launch_counters": [r["launch_counters"][k] for k in ("asked", "issued", "rounds", "groups")],
+                     "prune_counters": [r["prune_counters"][k] for k in ("staged", "staged_no_survivors", "kept_full_sweep", "not_eligible")],
+                     "memo": list(r["memo"]), "results": [_raw(t) for t in r["intervals"] + r["tables"]]})
         engine.release_workspace()
     return rows
 
