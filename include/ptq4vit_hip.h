@@ -19,6 +19,16 @@
  *     already below the complete score of another candidate -- are not swept over the remaining samples; the selected
  *     intervals are bit-identical with and without it.
  *     *_quant_forward, p4v_quantize_i8 and p4v_fake_quant never synchronise;
+ *   - the workspace contract, the same for every entry point that takes `d_workspace` / `workspace_bytes` (and for every
+ *     member of a p4v_calibrate_group call): d_workspace is aligned to at least 16 bytes (the engine carves it at offsets
+ *     that are multiples of 256 from d_workspace and reads the carved planes with 16-byte loads; a pointer below that is
+ *     refused with P4V_ERR_INVALID before anything is launched); its content on entry is arbitrary -- no call reads a byte
+ *     of it that the same call has not written, and no call depends on what an earlier call left there, the granular
+ *     p4v_amax_init_* / p4v_*_search_* calls of one module included; its content on return is unspecified; the value of the
+ *     matching *_workspace_bytes(desc) is sufficient for every call with that descriptor, whatever the alignment of the
+ *     other pointers and whatever the data (the plan of the sizing run bounds every plan a real call can choose); the engine
+ *     neither reads nor writes outside [d_workspace, d_workspace + workspace_bytes).  A smaller workspace_bytes is
+ *     P4V_ERR_WORKSPACE;
  *   - return value 0 = ok, <0 = error; p4v_last_error() returns a per-thread message;
  *   - safe to call concurrently on different devices / streams: the only state outside the call is per calling
  *     thread (error string, the optional launch timing of p4v_stats_*); the process-wide A/B words of

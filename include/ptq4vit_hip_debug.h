@@ -8,6 +8,7 @@
 #ifndef PTQ4VIT_HIP_DEBUG_H
 #define PTQ4VIT_HIP_DEBUG_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -33,6 +34,19 @@ int p4v_debug_set_tuning(int key, int value);
  * [candidate][score block] table in table order.  Nothing but the bound may depend on these numbers (csrc/p4v_api.hip::
  * run_pass_pruned); exposed so that a test can hold two stage-B1 kernels against each other within prune_margin. */
 int p4v_debug_bound_totals(float* out, int64_t capacity, int64_t* count);
+/* The arena that carves the caller's workspace, for the tests of the workspace contract (include/ptq4vit_hip.h, Conventions).
+ * p4v_debug_set_arena_gap: with a non-zero value every allocation of the arena -- from the bottom and from the top, in the sizing
+ * run of *_workspace_bytes() as well, which then includes the gaps -- leaves that many bytes unused behind it; a poisoned workspace
+ * then shows a kernel that stores past ANY carved buffer, not only past the last one.  A multiple of 256 (the arena's alignment;
+ * the gaps move buffers, they never change a buffer's alignment); anything else is P4V_ERR_INVALID.  0 (the default): off.
+ * Process-wide, relaxed atomic: set it while no call is in flight, and size the workspace after setting it. */
+int p4v_debug_set_arena_gap(size_t bytes);
+/* While the arena gap is on (recorded only then: with the gap at 0 the library does nothing for this word and reports no range):
+ * the byte ranges [begin, end), offsets from d_workspace, that any allocation of the LAST call with a workspace made by the calling
+ * thread ever covered, merged and ascending: out receives min(cap, n) pairs {begin, end}, the return value is n.  A pass that
+ * rewinds the arena does not erase its ranges.  Kept on the host per thread, nothing is launched for it.  The members of a
+ * p4v_calibrate_group call run on the library's own threads: their ranges are not reported. */
+int p4v_debug_arena_ranges(uint64_t* out, int cap);
 /* ONE sweep of the split-of-softmax split search (k_sos_split + k_finish) on the operands of `desc`, over the first n_cands of
  * the 20 splits: d_scores [n_cands] receives the score table, entries outside [c_lo, c_hi) as k_finish leaves them (-inf).
  * c_lo < 0: no candidate range.  known_cands: what the caller tells the sweep about the number of candidates in the range

@@ -106,6 +106,7 @@ EXPORTS = [
     "p4v_stats_enable", "p4v_stats_reset", "p4v_stats_get", "p4v_stats_launches", "p4v_prune_counters",
     "p4v_debug_set_variant", "p4v_debug_set_tuning", "p4v_debug_bound_totals", "p4v_debug_topk_rows", "p4v_debug_pack_dual", "p4v_debug_prep_epi6",
     "p4v_debug_pack_cands", "p4v_debug_gather_im2col", "p4v_debug_sos_sweep",
+    "p4v_debug_set_arena_gap", "p4v_debug_arena_ranges",
 ]
 
 _lib = None
@@ -202,6 +203,10 @@ def load():
     lib.p4v_debug_set_variant.argtypes = [C.c_int, C.c_int]
     lib.p4v_debug_set_tuning.restype = C.c_int
     lib.p4v_debug_set_tuning.argtypes = [C.c_int, C.c_int]
+    lib.p4v_debug_set_arena_gap.restype = C.c_int
+    lib.p4v_debug_set_arena_gap.argtypes = [C.c_size_t]
+    lib.p4v_debug_arena_ranges.restype = C.c_int
+    lib.p4v_debug_arena_ranges.argtypes = [C.POINTER(C.c_uint64), C.c_int]
     lib.p4v_debug_bound_totals.restype = C.c_int
     lib.p4v_debug_bound_totals.argtypes = [fp, C.c_int64, C.POINTER(C.c_int64)]
     lib.p4v_stats_enable.restype = C.c_int

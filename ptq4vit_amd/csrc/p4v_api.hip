@@ -59,24 +59,50 @@ inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // Bump allocator over the caller's workspace.  With base == nullptr it only counts (dry run):
 // *_workspace_bytes() runs the same planning code as *_calibrate().
+// Test hooks of the arena (ptq4vit_hip_debug.h).  One switch: with the gap at 0 (production) no allocation moves and nothing is recorded.
+//   g_arena_gap     p4v_debug_set_arena_gap: bytes left unused behind every allocation, in the dry run as well
+//   g_arena_ranges  p4v_debug_arena_ranges: while the gap is on, the merged [begin, end) byte ranges every allocation of the calling
+//                   thread's last non-dry call covered (host side only; a rewind of `off` does not erase a range)
+constexpr size_t WS_ALIGN = 16;            // minimum alignment of d_workspace (dwordx4 / LDS-DMA loads of the planes carved from it)
+std::atomic<size_t> g_arena_gap{0};
+thread_local std::vector<std::pair<size_t, size_t>> g_arena_ranges;
+inline void arena_note(size_t b, size_t e) {
+    if (e <= b) return;
+    auto& v = g_arena_ranges;
+    auto it = v.begin();
+    while (it != v.end() && it->second < b) ++it;            // first range that touches or follows [b, e)
+    if (it == v.end() || it->first > e) { v.insert(it, {b, e}); return; }
+    it->first = std::min(it->first, b);
+    it->second = std::max(it->second, e);
+    auto nx = it + 1;
+    while (nx != v.end() && nx->first <= it->second) { it->second = std::max(it->second, nx->second); nx = v.erase(nx); }
+}
+
 struct Arena {
     char* base;
     size_t cap, off, peak;
     size_t top;   // bytes taken from the END of the buffer: live for the whole call (candidate-plane cache), while the
                   // bump region [0, off) is rewound after every pass
     bool dry;
-    Arena(void* b, size_t c) : base((char*)b), cap(c & ~(size_t)255), off(0), peak(0), top(0), dry(b == nullptr) {}
+    size_t gap;
+    Arena(void* b, size_t c) : base((char*)b), cap(c & ~(size_t)255), off(0), peak(0), top(0), dry(b == nullptr),
+                               gap(g_arena_gap.load(std::memory_order_relaxed)) {
+        if (!dry) g_arena_ranges.clear();
+    }
     template <typename T> T* get(size_t n) {
         off = (size_t)rup((long)off, 256);
         T* p = dry ? nullptr : (T*)(base + off);
-        off += n * sizeof(T);
+        if (gap && !dry) arena_note(off, off + n * sizeof(T));
+        off += n * sizeof(T) + gap;
         if (off + top > peak) peak = off + top;
         return p;
     }
     char* get_top(size_t bytes) {
-        top += (size_t)rup((long)bytes, 256);
+        top += (size_t)rup((long)bytes, 256) + gap;           // (the gap lies behind the buffer, towards the end of the workspace)
         if (off + top > peak) peak = off + top;
-        return (dry || top > cap) ? nullptr : base + cap - top;
+        if (dry || top > cap) return nullptr;
+        if (gap) arena_note(cap - top, cap - top + bytes);
+        return base + cap - top;
     }
     bool ok() const { return dry || off + top <= cap; }
 };
@@ -130,6 +156,11 @@ enum { TUNE_CG6 = 0, TUNE_CG2 = 1, TUNE_CG2G = 2, TUNE_CG7 = 3, TUNE_PRINT = 4, 
 inline bool tune_b1_removed(int v) { return v == 1 || v == 2 || v == 3 || v == 5 || v == 6 || v == 8 || v == 10 || v == 12; }
 inline int tune(int k) { return g_tune[k].load(std::memory_order_relaxed); }
 inline bool b1_previous() { return tune(TUNE_B1_PATH) == 4; }
+
+// Every entry point that takes a workspace refuses a pointer below the documented alignment before anything is launched.
+inline int ws_aligned(const void* p) {
+    return ((uintptr_t)p % WS_ALIGN) == 0 ? 0 : fail(P4V_ERR_INVALID, "d_workspace must be aligned to %zu bytes", WS_ALIGN);
+}
 
 struct Group;
 struct Ctx {
@@ -3503,6 +3534,7 @@ int p4v_linear_calibrate(const p4v_linear_desc* desc, const float* d_weight, con
     if (!desc || !d_weight || !d_x || !d_out || !d_mult || !d_w_interval || !d_a_interval || !d_workspace)
         return fail(P4V_ERR_INVALID, "linear: null pointer");
     if (desc->has_bias && !d_bias) return fail(P4V_ERR_INVALID, "linear: has_bias set but d_bias is NULL");
+    CHK(ws_aligned(d_workspace));
     Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
     return linear_impl(desc, d_weight, desc->has_bias ? d_bias : nullptr, d_x, d_out, d_grad, d_mult, d_w_interval,
                        d_a_interval, d_scores, d_best, c);
@@ -3514,6 +3546,7 @@ int p4v_linear_quant_forward(const p4v_linear_desc* desc, const float* d_weight,
     if (!desc || !d_weight || !d_x || !d_w_interval || !d_a_interval || !d_out || !d_workspace)
         return fail(P4V_ERR_INVALID, "p4v_linear_quant_forward: null pointer");
     if (desc->has_bias && !d_bias) return fail(P4V_ERR_INVALID, "p4v_linear_quant_forward: has_bias set but d_bias is null");
+    CHK(ws_aligned(d_workspace));
     Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
     return linear_impl(desc, d_weight, desc->has_bias ? d_bias : nullptr, d_x, nullptr, nullptr, nullptr,
                        const_cast<float*>(d_w_interval), const_cast<float*>(d_a_interval), nullptr, nullptr, c, d_out);
@@ -3525,6 +3558,7 @@ int p4v_matmul_quant_forward(const p4v_matmul_desc* desc, const float* d_A, cons
     if (!desc || !d_A || !d_B || !d_A_interval || !d_B_interval || !d_out || !d_workspace)
         return fail(P4V_ERR_INVALID, "p4v_matmul_quant_forward: null pointer");
     if (desc->sos && !d_split) return fail(P4V_ERR_INVALID, "p4v_matmul_quant_forward: sos needs d_split");
+    CHK(ws_aligned(d_workspace));
     Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
     return matmul_impl(desc, d_A, d_B, nullptr, nullptr, nullptr, const_cast<float*>(d_A_interval),
                        const_cast<float*>(d_B_interval), const_cast<float*>(d_split), nullptr, nullptr, c, d_out);
@@ -3544,6 +3578,7 @@ int p4v_matmul_calibrate(const p4v_matmul_desc* desc, const float* d_A, const fl
                          float* d_scores, int32_t* d_best, void* d_workspace, size_t workspace_bytes, void* stream) {
     if (!desc || !d_A || !d_B || !d_out || !d_mult || !d_A_interval || !d_B_interval || !d_workspace)
         return fail(P4V_ERR_INVALID, "matmul: null pointer");
+    CHK(ws_aligned(d_workspace));
     Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
     return matmul_impl(desc, d_A, d_B, d_out, d_grad, d_mult, d_A_interval, d_B_interval, d_split, d_scores, d_best, c);
 }
@@ -3577,6 +3612,7 @@ int p4v_matmul_blocks_calibrate(const p4v_matmul_blocks_desc* desc, const float*
     if (!desc || !d_A || !d_B || !d_out || !d_mult || !d_A_interval || !d_B_interval || !d_workspace)
         return fail(P4V_ERR_INVALID, "p4v_matmul_blocks_calibrate: null pointer");
     CHK(blocks_check(desc, "p4v_matmul_blocks_calibrate"));
+    CHK(ws_aligned(d_workspace));
     Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
     const MatMulBlocks mb = blocks_of(desc);
     return matmul_impl(&desc->mm, d_A, d_B, d_out, d_grad, d_mult, d_A_interval, d_B_interval, d_split, d_scores, d_best, c, nullptr,
@@ -3588,6 +3624,7 @@ int p4v_amax_init_matmul_blocks(const p4v_matmul_blocks_desc* desc, const float*
     if (!desc || !d_A || !d_B || !d_A_interval || !d_B_interval || !d_workspace)
         return fail(P4V_ERR_INVALID, "p4v_amax_init_matmul_blocks: null pointer");
     CHK(blocks_check(desc, "p4v_amax_init_matmul_blocks"));
+    CHK(ws_aligned(d_workspace));
     Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
     float dummy_split = 0;   // only checked for presence
     const MatMulBlocks mb = blocks_of(desc);
@@ -3607,6 +3644,7 @@ int p4v_matmul_blocks_search(const p4v_matmul_blocks_desc* desc, int32_t operand
     if (desc->mm.sos && !d_split) return fail(P4V_ERR_INVALID, "p4v_matmul_blocks_search: sos needs d_split");
     const int nV = operand == 0 ? desc->n_V_A : desc->n_V_B, nH = operand == 0 ? desc->n_H_A : desc->n_H_B;
     if (v < 0 || v >= nV || h < 0 || h >= nH) return fail(P4V_ERR_INVALID, "p4v_matmul_blocks_search: block (%d, %d) outside the %d x %d blocks", v, h, nV, nH);
+    CHK(ws_aligned(d_workspace));
     Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
     const MatMulBlocks mb = blocks_of(desc, v, h);
     return matmul_impl(&desc->mm, d_A, d_B, d_out, d_grad, nullptr, d_A_interval, d_B_interval, const_cast<float*>(d_split), d_scores,
@@ -3620,6 +3658,7 @@ int p4v_matmul_blocks_quant_forward(const p4v_matmul_blocks_desc* desc, const fl
         return fail(P4V_ERR_INVALID, "p4v_matmul_blocks_quant_forward: null pointer");
     CHK(blocks_check(desc, "p4v_matmul_blocks_quant_forward"));
     if (desc->mm.sos && !d_split) return fail(P4V_ERR_INVALID, "p4v_matmul_blocks_quant_forward: sos needs d_split");
+    CHK(ws_aligned(d_workspace));
     Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
     const MatMulBlocks mb = blocks_of(desc);
     return matmul_impl(&desc->mm, d_A, d_B, nullptr, nullptr, nullptr, const_cast<float*>(d_A_interval),
@@ -3639,6 +3678,7 @@ int p4v_conv_calibrate(const p4v_conv_desc* desc, const float* d_weight, const f
     if (!desc || !d_weight || !d_x || !d_out || !d_mult || !d_w_interval || !d_a_interval || !d_workspace)
         return fail(P4V_ERR_INVALID, "conv: null pointer");
     if (desc->has_bias && !d_bias) return fail(P4V_ERR_INVALID, "conv: has_bias set but d_bias is NULL");
+    CHK(ws_aligned(d_workspace));
     Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
     return conv_impl(desc, d_weight, desc->has_bias ? d_bias : nullptr, d_x, d_out, d_grad, d_mult, d_w_interval, d_a_interval,
                      d_scores, d_best, c);
@@ -3651,6 +3691,7 @@ int p4v_calibrate_group(p4v_group_job* jobs, int32_t n_jobs, void* stream, void*
     for (int i = 0; i < n_jobs; ++i) {
         jobs[i].status = 0;
         if (!jobs[i].desc || group_desc_bytes(jobs[i].kind) == 0) return fail(P4V_ERR_INVALID, "p4v_calibrate_group: member %d has no descriptor / an unknown kind", i);
+        if ((uintptr_t)jobs[i].workspace % WS_ALIGN) return fail(P4V_ERR_INVALID, "p4v_calibrate_group: member %d: workspace must be aligned to %zu bytes", i, WS_ALIGN);
     }
     int dev = 0;
     HIPCHK(hipGetDevice(&dev));
@@ -3710,6 +3751,7 @@ int p4v_amax_init_linear(const p4v_linear_desc* desc, const float* d_weight, con
                          float* d_a_interval, void* d_workspace, size_t workspace_bytes, void* stream) {
     if (!desc || !d_weight || !d_x || !d_w_interval || !d_a_interval || !d_workspace)
         return fail(P4V_ERR_INVALID, "p4v_amax_init_linear: null pointer");
+    CHK(ws_aligned(d_workspace));
     Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
     return linear_impl(desc, d_weight, nullptr, d_x, nullptr, nullptr, nullptr, d_w_interval, d_a_interval, nullptr, nullptr, c,
                        nullptr, Stage{ST_INIT, nullptr, nullptr});
@@ -3722,6 +3764,7 @@ int p4v_linear_search_w(const p4v_linear_desc* desc, const float* d_weight, cons
     if (!desc || !d_weight || !d_x || !d_out || !d_w_cands || !d_w_interval || !d_a_interval || !d_workspace)
         return fail(P4V_ERR_INVALID, "p4v_linear_search_w: null pointer");
     if (desc->has_bias && !d_bias) return fail(P4V_ERR_INVALID, "p4v_linear_search_w: has_bias set but d_bias is NULL");
+    CHK(ws_aligned(d_workspace));
     Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
     return linear_impl(desc, d_weight, desc->has_bias ? d_bias : nullptr, d_x, d_out, d_grad, nullptr, d_w_interval,
                        const_cast<float*>(d_a_interval), d_scores, d_best, c, nullptr, Stage{ST_S1, d_w_cands, nullptr});
@@ -3734,6 +3777,7 @@ int p4v_linear_search_a(const p4v_linear_desc* desc, const float* d_weight, cons
     if (!desc || !d_weight || !d_x || !d_out || !d_a_cands || !d_w_interval || !d_a_interval || !d_workspace)
         return fail(P4V_ERR_INVALID, "p4v_linear_search_a: null pointer");
     if (desc->has_bias && !d_bias) return fail(P4V_ERR_INVALID, "p4v_linear_search_a: has_bias set but d_bias is NULL");
+    CHK(ws_aligned(d_workspace));
     Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
     return linear_impl(desc, d_weight, desc->has_bias ? d_bias : nullptr, d_x, d_out, d_grad, nullptr,
                        const_cast<float*>(d_w_interval), d_a_interval, d_scores, d_best, c, nullptr,
@@ -3744,6 +3788,7 @@ int p4v_amax_init_matmul(const p4v_matmul_desc* desc, const float* d_A, const fl
                          float* d_B_interval, void* d_workspace, size_t workspace_bytes, void* stream) {
     if (!desc || !d_A || !d_B || !d_A_interval || !d_B_interval || !d_workspace)
         return fail(P4V_ERR_INVALID, "p4v_amax_init_matmul: null pointer");
+    CHK(ws_aligned(d_workspace));
     Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
     float dummy_split = 0;   // only checked for presence
     return matmul_impl(desc, d_A, d_B, nullptr, nullptr, nullptr, d_A_interval, d_B_interval, &dummy_split, nullptr, nullptr, c,
@@ -3756,6 +3801,7 @@ int p4v_matmul_search_A(const p4v_matmul_desc* desc, const float* d_A, const flo
     if (!desc || !d_A || !d_B || !d_out || !d_A_cands || !d_A_interval || !d_B_interval || !d_workspace)
         return fail(P4V_ERR_INVALID, "p4v_matmul_search_A: null pointer");
     if (desc->sos) return fail(P4V_ERR_INVALID, "p4v_matmul_search_A: the split-of-softmax class searches its split (p4v_sos_search_split)");
+    CHK(ws_aligned(d_workspace));
     Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
     return matmul_impl(desc, d_A, d_B, d_out, d_grad, nullptr, d_A_interval, const_cast<float*>(d_B_interval), nullptr,
                        d_scores, d_best, c, nullptr, Stage{ST_S1, d_A_cands, nullptr});
@@ -3767,6 +3813,7 @@ int p4v_sos_search_split(const p4v_matmul_desc* desc, const float* d_A, const fl
     if (!desc || !d_A || !d_B || !d_out || !d_split || !d_A_interval || !d_workspace)
         return fail(P4V_ERR_INVALID, "p4v_sos_search_split: null pointer");
     if (!desc->sos) return fail(P4V_ERR_INVALID, "p4v_sos_search_split: descriptor is not a split-of-softmax matmul");
+    CHK(ws_aligned(d_workspace));
     Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
     return matmul_impl(desc, d_A, d_B, d_out, d_grad, nullptr, d_A_interval, nullptr, d_split, d_scores, d_best, c, nullptr,
                        Stage{ST_S1, nullptr, nullptr});
@@ -3779,6 +3826,7 @@ int p4v_matmul_search_B(const p4v_matmul_desc* desc, const float* d_A, const flo
     if (!desc || !d_A || !d_B || !d_out || !d_B_cands || !d_A_interval || !d_B_interval || !d_workspace)
         return fail(P4V_ERR_INVALID, "p4v_matmul_search_B: null pointer");
     if (desc->sos && !d_split) return fail(P4V_ERR_INVALID, "p4v_matmul_search_B: sos needs d_split");
+    CHK(ws_aligned(d_workspace));
     Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
     return matmul_impl(desc, d_A, d_B, d_out, d_grad, nullptr, const_cast<float*>(d_A_interval), d_B_interval,
                        const_cast<float*>(d_split), d_scores, d_best, c, nullptr, Stage{ST_S2, nullptr, d_B_cands});
@@ -3788,6 +3836,7 @@ int p4v_amax_init_conv(const p4v_conv_desc* desc, const float* d_weight, const f
                        float* d_a_interval, void* d_workspace, size_t workspace_bytes, void* stream) {
     if (!desc || !d_weight || !d_x || !d_w_interval || !d_a_interval || !d_workspace)
         return fail(P4V_ERR_INVALID, "p4v_amax_init_conv: null pointer");
+    CHK(ws_aligned(d_workspace));
     Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
     return conv_impl(desc, d_weight, nullptr, d_x, nullptr, nullptr, nullptr, d_w_interval, d_a_interval, nullptr, nullptr, c,
                      Stage{ST_INIT, nullptr, nullptr});
@@ -3802,6 +3851,7 @@ static int conv_search(const char* who, int want_channelwise, int stage, const p
     if (desc->has_bias && !d_bias) return fail(P4V_ERR_INVALID, "%s: has_bias set but d_bias is NULL", who);
     if (want_channelwise >= 0 && (desc->channelwise != 0) != (want_channelwise != 0))
         return fail(P4V_ERR_INVALID, "%s: descriptor.channelwise does not match the entry point", who);
+    CHK(ws_aligned(d_workspace));
     Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
     return conv_impl(desc, d_weight, desc->has_bias ? d_bias : nullptr, d_x, d_out, d_grad, nullptr, d_w_interval, d_a_interval,
                      d_scores, d_best, c, stage == ST_S1 ? Stage{ST_S1, d_cands, nullptr} : Stage{ST_S2, nullptr, d_cands});
@@ -3969,6 +4019,18 @@ int p4v_debug_set_tuning(int key, int value) {
     return 0;
 }
 
+int p4v_debug_set_arena_gap(size_t bytes) {
+    if (bytes % 256) return fail(P4V_ERR_INVALID, "p4v_debug_set_arena_gap: %zu is not a multiple of the arena's 256-byte alignment", bytes);
+    g_arena_gap.store(bytes, std::memory_order_relaxed);
+    return 0;
+}
+
+int p4v_debug_arena_ranges(uint64_t* out, int cap) {
+    const int n = (int)g_arena_ranges.size();
+    for (int i = 0; out && i < std::min(n, cap); ++i) { out[2 * i] = g_arena_ranges[i].first; out[2 * i + 1] = g_arena_ranges[i].second; }
+    return n;
+}
+
 int p4v_debug_sos_sweep(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_out, const float* d_grad,
                         int n_cands, int c_lo, int c_hi, int known_cands, float* d_scores, void* d_workspace, size_t workspace_bytes,
                         void* stream) {
@@ -3977,6 +4039,7 @@ int p4v_debug_sos_sweep(const p4v_matmul_desc* desc, const float* d_A, const flo
         return fail(P4V_ERR_INVALID, "p4v_debug_sos_sweep: a split-of-softmax matmul of the one-kernel split search, 1..20 candidates");
     const SosDebugSweep dbg{n_cands, c_lo, c_hi, known_cands, d_scores};
     float* d_split = nullptr;                       // (the sweep selects nothing: split and interval go to scratch)
+    CHK(ws_aligned(d_workspace));
     HIPCHK(hipMalloc(&d_split, 2 * sizeof(float)));
     Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
     g_sos_debug = &dbg;

@@ -705,6 +705,22 @@ def debug_tuning(key, value):
     _lib.check(_lib.load().p4v_debug_set_tuning(int(key), int(value)), "p4v_debug_set_tuning")
 
 
+def debug_arena_gap(nbytes=0):
+    """Bytes the arena leaves unused behind every allocation (p4v_debug_set_arena_gap; a multiple of 256, 0 = off).  The sizing
+    queries include the gaps: build the job AFTER setting it.  For the tests of the workspace contract."""
+    _lib.check(_lib.load().p4v_debug_set_arena_gap(int(nbytes)), "p4v_debug_set_arena_gap")
+
+
+def debug_arena_ranges():
+    """[(begin, end)] byte ranges of the workspace that the allocations of the calling thread's last single-module call covered
+    (p4v_debug_arena_ranges), merged and ascending.  Recorded only while the arena gap is on."""
+    lib = _lib.load()
+    n = lib.p4v_debug_arena_ranges(None, 0)
+    buf = (C.c_uint64 * max(2, 2 * n))()
+    n = min(n, lib.p4v_debug_arena_ranges(buf, n))
+    return [(int(buf[2 * i]), int(buf[2 * i + 1])) for i in range(n)]
+
+
 def debug_bound_totals(start=False):
     """start=True: keep the stage-B1 totals (the bound) of this thread's pruned passes from now on.  Otherwise stop and return
     the ones kept, in pass order (p4v_debug_bound_totals) -- for tests that compare two stage-B1 kernels."""

@@ -106,3 +106,127 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "LIB_PATH", str(tmp_path / "nope.so"))
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         _lib.load()
+
+
+# ---- the workspace contract (include/ptq4vit_hip.h, Conventions): what can be checked without a GPU ---------------------------
+def _linear_desc(images, tokens, K, N, *, n_V=1, n_H=1, n_a=1, bits=8, metric="hessian", rounds=1, postgelu=False, reserved=0):
+    from ptq4vit_amd import _lib
+    return _lib.LinearDesc(images, tokens, K, N, n_V, n_H, n_a, bits, bits, _lib.METRICS[metric], 100, rounds, int(postgelu), 0, 1, reserved)
+
+
+def _matmul_desc(M, K, N, *, sos=False, metric="hessian", rounds=1, reserved=0, batch=2, heads=2, blocks=None):
+    import torch
+    from ptq4vit_amd import _lib
+    bd = _lib.MatMulBlocksDesc() if blocks else None
+    d = bd.mm if blocks else _lib.MatMulDesc()
+    A = torch.empty(batch, heads, M, K)
+    B = torch.empty(batch, heads, K, N) if sos else torch.empty(batch, heads, N, K).transpose(-2, -1)    # q.k^T: k transposed in memory
+    d.batch, d.heads, d.M, d.K, d.N = batch, heads, M, K, N
+    for i in range(4):
+        d.a_stride[i], d.b_stride[i] = A.stride(i), B.stride(i)
+    d.A_bit = d.B_bit = 8
+    d.metric, d.eq_n, d.search_round, d.sos, d.init_layerwise, d.reserved = _lib.METRICS[metric], 100, rounds, int(sos), 0, reserved
+    if blocks:
+        bd.n_V_A, bd.n_H_A, bd.n_V_B, bd.n_H_B = blocks
+    return bd if blocks else d
+
+
+def _conv_desc(*, a_bit=32, metric="hessian", rounds=1, channelwise=True, reserved=0):
+    from ptq4vit_amd import _lib
+    return _lib.ConvDesc(2, 3, 32, 32, 16, 16, 16, 16, 16, 0, 0, 1, 1, 8, a_bit, _lib.METRICS[metric], 100, rounds, int(channelwise), 0, 1, reserved)
+
+
+def _contract_descs():
+    """(query, descriptor) of every case of tests/sweep_plan_cases.py::CASES (one round; reserved bit 3 where the case runs unpruned)
+    and of tests/search_round_cases.py::CASES (three rounds; the default call and the one with reserved bit 1)."""
+    L, M, B, Cv = ("p4v_linear_workspace_bytes", "p4v_matmul_workspace_bytes", "p4v_matmul_blocks_workspace_bytes", "p4v_conv_workspace_bytes")
+    out = [(L, _linear_desc(2, 64, 192, 128, reserved=8)), (L, _linear_desc(2, 64, 128, 128, reserved=8)),
+           (L, _linear_desc(2, 64, 1024, 64, reserved=8)), (L, _linear_desc(2, 64, 1024, 64, postgelu=True, reserved=8)),
+           (L, _linear_desc(2, 64, 1088, 64, reserved=8)), (L, _linear_desc(2, 64, 192, 120, n_V=3, reserved=8)),
+           (M, _matmul_desc(49, 64, 49, reserved=8)), (M, _matmul_desc(120, 64, 120, reserved=8)),
+           (M, _matmul_desc(49, 49, 64, sos=True, reserved=8)), (Cv, _conv_desc(reserved=8)), (L, _linear_desc(10, 65, 192, 96)),
+           (B, _matmul_desc(13, 8, 13, batch=4, heads=3, rounds=2, blocks=(2, 2, 2, 3)))]
+    for res in (0, 2):
+        kw = dict(rounds=3, reserved=res)
+        out += [(L, _linear_desc(2, 64, 192, 128, **kw)), (L, _linear_desc(2, 64, 192, 128, postgelu=True, **kw)),
+                (L, _linear_desc(2, 64, 1024, 64, postgelu=True, **kw)), (L, _linear_desc(2, 64, 192, 128, n_H=2, n_a=2, **kw)),
+                (L, _linear_desc(10, 65, 192, 96, **kw)), (L, _linear_desc(2, 64, 192, 128, metric="cosine", **kw)),
+                (L, _linear_desc(2, 64, 1024, 64, metric="cosine", **kw)), (L, _linear_desc(2, 64, 192, 120, n_V=3, metric="cosine", **kw)),
+                (L, _linear_desc(3, 11, 24, 16, n_V=2, n_H=2, n_a=3, bits=4, metric="cosine", **kw)),
+                (M, _matmul_desc(49, 64, 49, **kw)), (M, _matmul_desc(49, 64, 49, metric="cosine", **kw)),
+                (M, _matmul_desc(49, 49, 64, sos=True, **kw)), (M, _matmul_desc(49, 49, 64, sos=True, metric="cosine", **kw)),
+                (Cv, _conv_desc(**kw)), (Cv, _conv_desc(a_bit=8, **kw)), (Cv, _conv_desc(metric="cosine", channelwise=False, **kw))]
+    # (the lists themselves build their tensors on the GPU and expose no parameters: hold the count of this table to theirs, so that a
+    # case added or removed there cannot pass here unnoticed)
+    from tests import search_round_cases, sweep_plan_cases
+    assert len(out) == len(sweep_plan_cases.CASES) + 2 * len(search_round_cases.CASES), "update _contract_descs() with the case lists"
+    loose = {i for i, (q, d) in enumerate(out) if q == L and (d.batch, d.tokens) == (10, 65)}      # the bound cases run under LOOSE
+    assert len(loose) == 3
+    return [(q, d, sweep_plan_cases.LOOSE if i in loose else 0) for i, (q, d) in enumerate(out)]
+
+
+def test_arena_gap_only_grows_the_sizing_and_resets(lib):
+    """p4v_debug_set_arena_gap: the sizing run includes the gaps (>= the value without), both values are repeatable and do not depend
+    on the order of the queries, only multiples of the arena's 256-byte alignment are taken, and 0 restores the plain sizes."""
+    descs = _contract_descs()
+    def size(q, d, variant):
+        assert lib.p4v_debug_set_variant(variant, 0) == 0
+        try:
+            return getattr(lib, q)(C.byref(d))
+        finally:
+            assert lib.p4v_debug_set_variant(0, 0) == 0
+    try:
+        plain = [size(*c) for c in descs]
+        assert all(n > 4096 for n in plain), plain
+        assert lib.p4v_debug_set_arena_gap(100) == -1 and b"256" in lib.p4v_last_error()
+        assert [size(*c) for c in descs] == plain                      # (a refused value changes nothing)
+        assert lib.p4v_debug_set_arena_gap(4096) == 0
+        gapped = [size(*c) for c in descs]
+        assert all(g >= p + 4096 for g, p in zip(gapped, plain)), list(zip(gapped, plain))
+        assert [size(*c) for c in reversed(descs)] == gapped[::-1]     # repeatable, whatever the order of the queries
+        assert lib.p4v_debug_set_arena_gap(8192) == 0
+        assert all(g2 >= g for g2, g in zip([size(*c) for c in descs], gapped))
+    finally:
+        assert lib.p4v_debug_set_arena_gap(0) == 0
+    assert [size(*c) for c in reversed(descs)] == plain[::-1]
+    assert [size(*c) for c in descs] == plain
+    assert lib.p4v_debug_arena_ranges(None, 0) >= 0                          # host-side record: callable without a GPU
+
+
+def test_misaligned_workspace_pointer_is_refused_on_the_host(lib):
+    """Every entry point that takes a workspace refuses a d_workspace below the documented 16-byte alignment with P4V_ERR_INVALID
+    before anything is launched (no GPU here: a call that got past the check would fail differently or crash).  The pointers are
+    fakes that are never dereferenced; 72 is 8-byte aligned only."""
+    from ptq4vit_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "ptq4vit_hip.h")).read()
+    assert "aligned to at least 16 bytes" in hdr
+    one, bad, null = C.c_void_p(64), C.c_void_p(72), C.c_void_p(0)
+    ld, cd = _linear_desc(2, 64, 192, 128), _conv_desc(a_bit=8)
+    cl = _conv_desc(a_bit=8, channelwise=False)
+    md, sd = _matmul_desc(49, 64, 49), _matmul_desc(49, 49, 64, sos=True)
+    bd = _matmul_desc(13, 8, 13, batch=4, heads=3, blocks=(2, 2, 2, 3))
+    r = C.byref
+    calls = [
+        ("p4v_linear_calibrate", (r(ld), *[one] * 10)), ("p4v_matmul_calibrate", (r(md), *[one] * 10)),
+        ("p4v_matmul_blocks_calibrate", (r(bd), *[one] * 10)), ("p4v_conv_calibrate", (r(cd), *[one] * 10)),
+        ("p4v_linear_quant_forward", (r(ld), *[one] * 6)), ("p4v_matmul_quant_forward", (r(md), *[one] * 6)),
+        ("p4v_matmul_blocks_quant_forward", (r(bd), *[one] * 6)),
+        ("p4v_amax_init_linear", (r(ld), *[one] * 4)), ("p4v_linear_search_w", (r(ld), *[one] * 10)),
+        ("p4v_linear_search_a", (r(ld), *[one] * 10)),
+        ("p4v_amax_init_matmul", (r(md), *[one] * 4)), ("p4v_matmul_search_A", (r(md), *[one] * 9)),
+        ("p4v_sos_search_split", (r(sd), *[one] * 8)), ("p4v_matmul_search_B", (r(md), *[one] * 10)),
+        ("p4v_amax_init_matmul_blocks", (r(bd), *[one] * 4)), ("p4v_matmul_blocks_search", (r(bd), 1, 0, 0, *[one] * 10)),
+        ("p4v_amax_init_conv", (r(cd), *[one] * 4)), ("p4v_conv_search_w_channelwise", (r(cd), *[one] * 10)),
+        ("p4v_conv_search_w_layerwise", (r(cl), *[one] * 10)), ("p4v_conv_search_a", (r(cd), *[one] * 10)),
+    ]
+    with_ws = {s for s in _lib.EXPORTS if s not in ("p4v_calibrate_group", "p4v_debug_sos_sweep") and
+               re.search(r"\b%s\s*\([^;]*d_workspace" % s, hdr)}
+    assert with_ws == {name for name, _ in calls}, with_ws ^ {name for name, _ in calls}
+    for name, args in calls:
+        rc = getattr(lib, name)(*args, bad, 1 << 20, null)
+        assert rc == -1 and b"aligned" in lib.p4v_last_error(), (name, rc, lib.p4v_last_error())
+    rc = lib.p4v_debug_sos_sweep(r(sd), one, one, one, one, 20, -1, -1, -1, one, bad, 1 << 20, null)
+    assert rc == -1 and b"aligned" in lib.p4v_last_error(), lib.p4v_last_error()
+    jobs = (_lib.GroupJob * 1)()
+    jobs[0].kind, jobs[0].desc, jobs[0].workspace, jobs[0].workspace_bytes = _lib.JOB_LINEAR, C.cast(C.pointer(ld), C.c_void_p), 72, 1 << 20
+    assert lib.p4v_calibrate_group(jobs, 1, null, null) == -1 and b"aligned" in lib.p4v_last_error()
