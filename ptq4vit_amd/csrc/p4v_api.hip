@@ -120,7 +120,10 @@ thread_local std::vector<StatRec> g_stat_recs;
 thread_local std::vector<StatRec> g_stat_done;   // drained records, kept until p4v_stats_reset (p4v_stats_launches)
 thread_local bool g_b1_keep = false;            // p4v_debug_bound_totals: keep the stage-B1 totals of this thread's pruned passes
 thread_local std::vector<float> g_b1_totals;
-thread_local int g_stage = 0;                   // which stage of a pruned pass is being launched: 0 full sweep, 1 A, 2 B1, 3 B2
+// Which stage of a pruned pass is being launched: a label for the launch records and the prints, nothing decides by it.  Set by
+// run_stage only (and cleared per call at the group entry); _lib.py maps the numbers to the record strings.
+enum PruneStage { STAGE_FULL = 0, STAGE_A = 1, STAGE_B1 = 2, STAGE_B2 = 3, STAGE_A2 = 4 };   // A2: the second tier's slice sweep
+thread_local int g_stage = STAGE_FULL;
 thread_local p4v_kernel_stats g_stats = {};
 thread_local long g_memo_hits = 0, g_memo_misses = 0;
 // Process-wide counters of the exact candidate pruning (p4v_prune_counters): tests and bench.py assert with them that the
@@ -256,7 +259,7 @@ template <typename P, void (*K1)(P)> struct Kern1 {      // kernels off the grou
 constexpr int MIR_SLOT = 2048, MIR_SLOTS = 3;
 // header of a mirror block, in ints: [0,1] / [2,3] survivor ranges of the two tiers, [4] the slice's weight share, [16..79] /
 // [80..143] the per-score-block ranges of the two tiers (<= MIR_BLK blocks: the heads of an attention matmul), then the interval slots
-constexpr int MIR_HDR = 160, MIR_BLK = 32, MIR_RB1 = 16, MIR_RB2 = 80;
+constexpr int MIR_HDR = 160, MIR_BLK = 32, MIR_R1 = 0, MIR_R2 = 2, MIR_RB1 = 16, MIR_RB2 = 80;
 constexpr size_t MIRROR_BYTES = sizeof(int) * MIR_HDR + sizeof(float) * MIR_SLOT * MIR_SLOTS;
 inline int* mirror_alloc() {
     void* p = nullptr;
@@ -957,10 +960,10 @@ struct SliceCache {
     bool assigned = false;
     int k = 0;                        // rows per segment the buffers are sized for
     int k_eff = 0;                    // rows per segment in use (a Linear whose 256 heaviest samples hold the weight uses those)
-    int* idx = nullptr; float* mass = nullptr; float* mass_u = nullptr;
-    float* Os = nullptr; float* Gs = nullptr; float* Rs = nullptr; float* Cs = nullptr;
+    int* idx = nullptr; float* mass = nullptr;
+    float* Os = nullptr; float* Gs = nullptr; float* Rs = nullptr;
     const void* idx_src = nullptr; int idx_wt = -1;      // what the ranking was computed from
-    const void* o_src = nullptr; const void* g_src = nullptr; const void* r_src = nullptr; const void* c_src = nullptr;
+    const void* o_src = nullptr; const void* g_src = nullptr; const void* r_src = nullptr;
     float* frac = nullptr;            // device: share of the metric weight the slice holds
     PlaneCache aplane;                // stage A's candidate-expanded plane of the SLICED operand (the search whose row operand is
                                       // expanded): candidates and slice rows are fixed for the call, the later rounds find it packed
@@ -1495,7 +1498,7 @@ int chunk_exec_frac(Ctx& c, const Pass& ps, const SweepPlan& pl, int c0, int nc)
     if (!(g_stat_on && ps.crange && !c.dry)) return 0;
     int h[2] = {0, 0};
     const bool host_knows = ps.host_hi > ps.host_lo;
-    const bool one_cand = !host_knows && g_stage == 2 && ps.nj == 1;
+    const bool one_cand = !host_knows && ps.host_len == 1;        // (stage_b1_pass: the range holds the slice winner)
     if (host_knows) { h[0] = ps.host_lo; h[1] = ps.host_hi; }
     else if (one_cand) { h[0] = c0; h[1] = c0 + 1; }
     else { CHK(q_d2h(c, h, ps.crange, sizeof h)); CHK(q_sync(c)); }
@@ -1827,10 +1830,77 @@ int slice_fill(Ctx& c, SliceCache* sc, const SliceGeo& g, bool host_sync_ok) {
     return gather_rc;
 }
 
-bool prune_ok(const Pass& ps) {
-    if (!ps.prunable || !(ps.i8 || ps.prunable_f32) || ps.epi == EPI_COS || ps.store_out || ps.scores_out || ps.best_out || ps.crange || ps.no_select) return false;
-    if ((g_variant & 4194304) || ps.eq_n < 32 || ps.nj < 1 || ps.nj > 4096) return false;
-    return true;
+// What became of a pass handed to a pruned driver = its slot of p4v_prune_counters
+enum PruneOutcome { PRUNE_STAGED = 0, PRUNE_NO_SURVIVORS = 1, PRUNE_KEEP_FULL = 2, PRUNE_NOT_ELIGIBLE = 3 };
+inline bool prune_switched_off() { return (g_variant & 4194304) != 0; }
+struct PrunePlan {
+    bool lin;                 // Z = 1 (Linear, Conv): one ranking over all samples; MatMul: one per batch entry, the column operand whole
+    int segs, seg_rows;       // ranking segments, rows ranked per segment
+    int k_cap, k;             // rows per segment the slice buffers hold / stage A starts on (fill_slice: what the module settled on)
+    bool conv_rows;           // the row operand is the im2col view of a conv input (gathered element by element)
+    SliceGeo geo, geo2;       // the slices of the two tiers
+    bool tier2; int k2;       // a second, larger slice is planned (ps.scache2) and its rows
+    bool virt;                // several score blocks whose entries of the candidate table are exactly one row: stage B1 on ONE synthetic candidate
+    bool hull_selects;        // k_prune_hull makes the selection when nothing survives besides stage B1's candidates
+    bool b1_bound;            // stage B1 is ONE candidate per score block over all samples on a layout k_bound takes
+};
+// The only place that decides whether a pass is staged and with what geometry (DESIGN.md s5.1 lists the tests in this order).
+// Allocates nothing; reads the module's slice cache for what earlier passes of the module found out.
+PruneOutcome plan_prune(const Ctx& c, const Pass& ps, PrunePlan& pl) {
+    if (!ps.prunable || !(ps.i8 || ps.prunable_f32) || ps.epi == EPI_COS || ps.store_out || ps.scores_out || ps.best_out || ps.crange || ps.no_select) return PRUNE_NOT_ELIGIBLE;
+    if (prune_switched_off() || ps.eq_n < 32 || ps.nj < 1 || ps.nj > 4096) return PRUNE_NOT_ELIGIBLE;
+    // geometry of the slice.  Linear: the k heaviest of its M samples (rows of x / raw_out / raw_grad).  MatMul: the 16
+    // heaviest rows (queries) of EVERY batch entry (image, head) -- the column operand stays whole.  Measured on ViT-B/224 x 32
+    // (tools/row_mass.py, tools/row_mass_mm.py): 99.9 % of raw_grad^2 sits in 1/8 of a Linear's samples and 99.7-100 % in ONE
+    // row of each (image, head) of the attention matmuls -- the class-token rows, the only ones the classifier reads.
+    const bool lin = pl.lin = ps.Z == 1;
+    pl.segs = lin ? 1 : ps.Z;
+    pl.seg_rows = ps.Mrows;
+    pl.conv_rows = lin && ps.row.pk.conv && ps.row.pk.Z == 1 && !ps.twin;
+    if (lin) {
+        pl.k_cap = (int)std::min<long>(rup(std::max(1, ps.Mrows / (tune(TUNE_SLICE_DIV) > 0 ? tune(TUNE_SLICE_DIV) : 16)), 256), rup(ps.Mrows, 256));
+        if ((long)pl.k_cap * 5 > (long)ps.Mrows * 2) return PRUNE_KEEP_FULL;    // slice > 40 % of the samples: not worth the stages
+        // dense row-major operands only (or the im2col rows of a conv input)
+        if (ps.o_ms != ps.Ncols || ps.o_ns != 1 || ps.o_bs || ps.o_nbs || ps.row.pk.zdiv > 0 ||
+            (!pl.conv_rows && (ps.row.pk.conv || ps.row.pk.s_k != 1 || ps.row.pk.s_r != ps.K))) return PRUNE_KEEP_FULL;
+    } else {
+        pl.k_cap = 16;
+        if (ps.Mrows < 64 || ps.row_zs_shared || ps.o_zs != (long)ps.Mrows * ps.Ncols || ps.o_ms != ps.Ncols || ps.o_ns != 1 ||
+            ps.o_bs || ps.o_nbs || ps.row.pk.zdiv <= 0 || ps.row.pk.conv) return PRUNE_KEEP_FULL;
+    }
+    if (ps.scache && ps.scache->loose) return PRUNE_KEEP_FULL;     // an earlier pass of the module measured the slice (slice_fill)
+    // A Linear first tries a QUARTER of the slice: the M/64 (at least 128) heaviest samples -- in a ViT the class-token rows, one
+    // per image of 197+ tokens, are among them -- hold > 97 % of the weight in every layer but qkv, and stage A costs in proportion
+    // to the slice.  Measured (ViT-B/224 x 32, one box): full slice 155.4 ms per calibration, 256 rows 151.2, 128 rows 148.8,
+    // 64 rows 148.6 (p4v_debug_set_tuning(11, rows) overrides the size)
+    pl.k = pl.k_cap;
+    if (ps.scache && ps.scache->k_eff > 0) pl.k = ps.scache->k_eff;
+    else if (lin && ps.scache && ps.host_sync_ok && !c.dry && pl.k_cap >= 512 && !(g_variant & 8388608))
+        pl.k = tune(TUNE_SLICE_SMALL) > 0 ? std::min(tune(TUNE_SLICE_SMALL), pl.k_cap)
+                                          : (int)std::min<long>(std::max<long>(128, rup(ps.Mrows / 64, 64)), pl.k_cap / 2);
+    pl.geo = SliceGeo{lin, pl.segs, pl.seg_rows, pl.k, ps.Ncols, ps.K, ps.O, ps.G, ps.wt_mode, ps.o_ms, ps.row.pk.src, ps.row.pk.s_r, ps.row.pk.s_k,
+                      ps.row.pk.zdiv, ps.row.pk.s_z2, ps.row.pk.s_z, pl.conv_rows, ps.row.pk, pl.k_cap};
+    // Second tier (Linear layers whose weight is spread over more samples than the first slice holds -- the qkv layers: the keys
+    // and values of EVERY token feed the class token, 0.72 of the weight in their 512 heaviest samples, ~32 of 100 candidates
+    // survive stage B1's bound and stage B2 swept them over all 6304 samples: 37 % of the sweep time of a ViT-B calibration):
+    // the survivors are first swept over the M/4 heaviest samples (a partial sum over ANY subset of the samples is an upper
+    // bound; this one is ~3 x tighter) and only what survives THAT goes to stage B2.  The buffers are planned unconditionally
+    // (the dry run cannot know whether a module will need them).
+    // (M / 4: measured on ViT-B/224 x 32, k_sweep6 time per calibration 30.6 ms without the tier, 29.1 / 28.1 / 28.7 / 29.4 ms with M / 3, 4, 6, 8)
+    pl.k2 = (int)rup(std::max(1, ps.Mrows / (tune(TUNE_TIER2_DIV) > 0 ? tune(TUNE_TIER2_DIV) : 4)), 256);
+    pl.tier2 = lin && ps.scache && ps.scache2 && !ps.row.pk.conv && tune(TUNE_TIER2) != 1 &&
+               pl.k2 >= 2 * pl.k_cap && (long)pl.k2 * 5 <= (long)ps.Mrows * 2;
+    pl.geo2 = pl.geo;
+    pl.geo2.k = pl.geo2.k_cap = pl.k2;
+    pl.virt = ps.nj > 1 && ps.cand_off == 0 && ps.cand_js * ps.nj == ps.cand_cs && ps.cand_cs <= 4096;
+    pl.hull_selects = !ps.scores_out && ps.interval && (pl.virt || ps.nj <= 32);   // (its non-virt selection is serial over the blocks)
+    // ONE candidate per score block over all samples: the kernel built for that (k_bound).
+    // Its totals are summed in another order than the sweeps', so from stage B1 on nothing may depend on its numbers but the
+    // bound: the selections are either "the only survivor of every block" (no totals involved) or come from stage B2, which
+    // always re-evaluates stage B1's candidates together with the other survivors.  The candidate's plane is packed for this
+    // pass (one candidate: ~12 us) instead of being read from the module's plane, whose layout belongs to its sweep kernel.
+    pl.b1_bound = lin && ps.i8 && !ps.twin && (pl.virt || ps.nj == 1);
+    return PRUNE_STAGED;
 }
 
 #define PRUNE_COUNT(i) do { if (!c.dry) g_prune_cnt[i].fetch_add(1, std::memory_order_relaxed); } while (0)
@@ -1845,14 +1915,15 @@ bool prune_ok(const Pass& ps) {
 // PRUNE_FP32_CHAIN).  Variant 134217728 cross-checks every pruned pass against the full sweep (tests).
 constexpr int PRUNE_FP32_CHAIN = 128 + 6;
 inline float prune_margin() { return std::max(1e-4f, 4.0f * 2.0f * (float)PRUNE_FP32_CHAIN * 5.9604645e-8f); }
-int prune_crosscheck_begin(Ctx& c, const float* interval, int n, std::vector<float>& keep) {
-    keep.resize(n);
-    CHK(q_d2h(c, keep.data(), interval, sizeof(float) * n));
-    CHK(q_sync(c));
-    return 0;
-}
-int prune_crosscheck_end(Ctx& c, const float* interval, int n, const std::vector<float>& pruned, const char* what) {
-    std::vector<float> full(n);
+// The debug cross-check: `pruned_fn`, then `full_fn` -- the full sweep of the same pass into the same `interval` --; the n
+// selections must be bit-identical.  A dry run plans both and compares nothing.
+template <class PrunedFn, class FullFn>
+int cross_checked(Ctx& c, const float* interval, int n, const char* what, PrunedFn&& pruned_fn, FullFn&& full_fn) {
+    std::vector<float> pruned(n), full(n);
+    CHK(pruned_fn());
+    if (!c.dry) { CHK(q_d2h(c, pruned.data(), interval, sizeof(float) * n)); CHK(q_sync(c)); }
+    CHK(full_fn());
+    if (c.dry) return 0;
     CHK(q_d2h(c, full.data(), interval, sizeof(float) * n));
     CHK(q_sync(c));
     for (int i = 0; i < n; ++i)
@@ -1982,232 +2053,243 @@ int run_slice_a(Ctx& c, Pass& a, float* SA) {
     return 0;
 }
 
-int run_pass_pruned_impl(Ctx& c, Pass& ps);
-int run_pass_pruned(Ctx& c, Pass& ps) {
-    if (!(g_variant & 134217728) || !prune_ok(ps) || (!c.dry && !ps.interval)) return run_pass_pruned_impl(c, ps);
-    // debug cross-check: the pruned pass, then the full sweep of the same pass; the selections must be bit-identical
-    // (the dry run plans both: the full sweep's planes live in the bump region)
-    const int n = ps.out_off + (std::max(1, ps.nj) - 1) * ps.out_js + 1;
-    std::vector<float> keep;
-    CHK(run_pass_pruned_impl(c, ps));
-    if (!c.dry) CHK(prune_crosscheck_begin(c, ps.interval, n, keep));
-    Pass full = ps;
-    full.prunable = false; full.scache = nullptr; full.scache2 = nullptr; full.cache = nullptr; full.ecache = nullptr;
-    CHK(run_pass(c, full));
-    return c.dry ? 0 : prune_crosscheck_end(c, ps.interval, n, keep, "search pass");
-}
-int run_pass_pruned_impl(Ctx& c, Pass& ps) {
-    if (!prune_ok(ps)) { PRUNE_COUNT(3); return run_pass(c, ps); }
-    const bool lin = ps.Z == 1;
-    // geometry of the slice.  Linear: the k heaviest of its M samples (rows of x / raw_out / raw_grad).  MatMul: the 16
-    // heaviest rows (queries) of EVERY batch entry (image, head) -- the column operand stays whole.  Measured on ViT-B/224 x 32
-    // (tools/row_mass.py, tools/row_mass_mm.py): 99.9 % of raw_grad^2 sits in 1/8 of a Linear's samples and 99.7-100 % in ONE
-    // row of each (image, head) of the attention matmuls -- the class-token rows, the only ones the classifier reads.
-    const int segs = lin ? 1 : ps.Z;                                 // ranking segments
-    const int seg_rows = ps.Mrows;                                   // rows ranked per segment
-    int k;                                                           // rows taken per segment
-    if (lin) {
-        k = (int)std::min<long>(rup(std::max(1, ps.Mrows / (tune(TUNE_SLICE_DIV) > 0 ? tune(TUNE_SLICE_DIV) : 16)), 256), rup(ps.Mrows, 256));
-        if ((long)k * 5 > (long)ps.Mrows * 2) { PRUNE_COUNT(2); return run_pass(c, ps); }   // slice > 40 % of the samples: not worth the stages
-        // dense row-major operands only (or the im2col rows of a conv input, gathered element by element)
-        const bool conv_rows = ps.row.pk.conv && ps.row.pk.Z == 1 && !ps.twin;
-        if (ps.o_ms != ps.Ncols || ps.o_ns != 1 || ps.o_bs || ps.o_nbs || ps.row.pk.zdiv > 0 ||
-            (!conv_rows && (ps.row.pk.conv || ps.row.pk.s_k != 1 || ps.row.pk.s_r != ps.K))) { PRUNE_COUNT(2); return run_pass(c, ps); }
-    } else {
-        k = 16;
-        if (ps.Mrows < 64 || ps.row_zs_shared || ps.o_zs != (long)ps.Mrows * ps.Ncols || ps.o_ms != ps.Ncols || ps.o_ns != 1 ||
-            ps.o_bs || ps.o_nbs || ps.row.pk.zdiv <= 0 || ps.row.pk.conv) { PRUNE_COUNT(2); return run_pass(c, ps); }
-    }
-    SliceCache local;
-    SliceCache* sc = ps.scache ? ps.scache : &local;
-    if (sc->loose) { PRUNE_COUNT(2); return run_pass(c, ps); }
-    // A Linear first tries a QUARTER of the slice: the M/64 (at least 128) heaviest samples -- in a ViT the class-token rows, one
-    // per image of 197+ tokens, are among them -- hold > 97 % of the weight in every layer but qkv, and stage A costs in proportion
-    // to the slice.  Measured (ViT-B/224 x 32, one box): full slice 155.4 ms per calibration, 256 rows 151.2, 128 rows 148.8,
-    // 64 rows 148.6 (p4v_debug_set_tuning(11, rows) overrides the size)
-    const int k_cap = k;
-    if (sc->k_eff > 0) k = sc->k_eff;
-    else if (lin && ps.scache && ps.host_sync_ok && !c.dry && k_cap >= 512 && !(g_variant & 8388608))
-        k = tune(TUNE_SLICE_SMALL) > 0 ? std::min(tune(TUNE_SLICE_SMALL), k_cap)
-                                       : (int)std::min<long>(std::max<long>(128, rup(ps.Mrows / 64, 64)), k_cap / 2);
-    SliceGeo geo{lin, segs, seg_rows, k, ps.Ncols, ps.K, ps.O, ps.G, ps.wt_mode, ps.o_ms, ps.row.pk.src, ps.row.pk.s_r, ps.row.pk.s_k,
-                 ps.row.pk.zdiv, ps.row.pk.s_z2, ps.row.pk.s_z, lin && ps.row.pk.conv != 0, ps.row.pk, k_cap};
-    CHK(slice_alloc(c, sc, geo, ps.scache != nullptr, /*bump=*/false));
-    // Second tier (Linear layers whose weight is spread over more samples than the first slice holds -- the qkv layers: the keys
-    // and values of EVERY token feed the class token, 0.72 of the weight in their 512 heaviest samples, ~32 of 100 candidates
-    // survive stage B1's bound and stage B2 swept them over all 6304 samples: 37 % of the sweep time of a ViT-B calibration):
-    // the survivors are first swept over the M/4 heaviest samples (a partial sum over ANY subset of the samples is an upper
-    // bound; this one is ~3 x tighter) and only what survives THAT goes to stage B2.  The buffers are planned unconditionally
-    // (the dry run cannot know whether a module will need them).
-    SliceCache* sc2 = (lin && ps.scache && ps.scache2 && !ps.row.pk.conv && tune(TUNE_TIER2) != 1) ? ps.scache2 : nullptr;
-    // (M / 4: measured on ViT-B/224 x 32, k_sweep6 time per calibration 30.6 ms without the tier, 29.1 / 28.1 / 28.7 / 29.4 ms with M / 3, 4, 6, 8)
-    const int k2 = (int)rup(std::max(1, ps.Mrows / (tune(TUNE_TIER2_DIV) > 0 ? tune(TUNE_TIER2_DIV) : 4)), 256);
-    if (sc2 && (k2 < 2 * k_cap || (long)k2 * 5 > (long)ps.Mrows * 2)) sc2 = nullptr;
-    SliceGeo geo2 = geo;
-    geo2.k = geo2.k_cap = k2;
-    if (sc2) CHK(slice_alloc(c, sc2, geo2, true, /*bump=*/false));
-    const size_t mark = c.ws.off;
-    const size_t tab = (size_t)ps.eq_n * std::max(1, ps.nj);
-    float* SA = c.ws.get<float>(tab);
-    float* SB = c.ws.get<float>(tab);
-    float* S2 = c.ws.get<float>(tab);
-    float* SA2 = sc2 ? c.ws.get<float>(tab) : nullptr;
-    int* r1 = c.ws.get<int>(6);
-    int* r2 = r1 + 2;
-    int* r3 = r1 + 4;
-    int* best_idx = c.ws.get<int>((size_t)std::max(1, ps.nj));
-    int* rblk2 = c.ws.get<int>((size_t)4 * std::max(1, ps.nj));      // per-score-block survivor ranges of the hull (r2) ...
-    int* rblk3 = rblk2 + 2 * std::max(1, ps.nj);                       // ... and of the second tier's (r3)
-    float* vrow = c.ws.get<float>((size_t)std::max(1, ps.cand_cs));
-    float* S1s = ps.use_s1 ? c.ws.get<float>((size_t)ps.eq_n * ps.s_cs) : nullptr;             // one scale table for all stages
-    float* S2s = (ps.use_s1 && ps.twin) ? c.ws.get<float>((size_t)ps.eq_n * ps.s_cs) : nullptr;
-    if (!ps.scache) CHK(slice_alloc(c, sc, geo, false, /*bump=*/true));
+// ---- the pieces of a pruned pass: buffers, stage passes, stage runner, survivors ------------------------------------------------
+// Carved in this order -- the dry run is the workspace contract.  The module's slices at the top of the workspace (first use),
+// then from `mark` on the scratch of this pass; a pass without a module slice gathers into a pass-local one behind its tables.
+struct PruneBufs {
+    size_t mark, tab;                    // tab: entries of one score table, [eq_n][nj]
+    float *SA, *SB, *S2, *SA2;           // scores of stage A, B1, B2 and (tier 2) A2
+    int *r1, *r2, *r3;                   // candidate ranges: the stage-A winners (k_prune_pick), the survivors of tier 1 and of tier 2 (k_prune_hull)
+    int* best_idx;                       // virt: the stage-A winner of every score block
+    int *rblk2, *rblk3;                  // per-score-block survivor ranges of the two hulls
+    float* vrow;                         // virt: the synthetic candidate's row of the candidate table
+    float *S1s, *S2s;                    // one scale table (twin: two) for all stages
+    SliceCache local; SliceCache *sc, *sc2;
+};
+int prune_workspace(Ctx& c, const Pass& ps, const PrunePlan& pl, PruneBufs& b) {
+    b.sc = ps.scache ? ps.scache : &b.local;
+    CHK(slice_alloc(c, b.sc, pl.geo, ps.scache != nullptr, /*bump=*/false));
+    b.sc2 = pl.tier2 ? ps.scache2 : nullptr;
+    if (b.sc2) CHK(slice_alloc(c, b.sc2, pl.geo2, true, /*bump=*/false));
+    b.mark = c.ws.off;
+    b.tab = (size_t)ps.eq_n * ps.nj;
+    b.SA = c.ws.get<float>(b.tab);
+    b.SB = c.ws.get<float>(b.tab);
+    b.S2 = c.ws.get<float>(b.tab);
+    b.SA2 = b.sc2 ? c.ws.get<float>(b.tab) : nullptr;
+    b.r1 = c.ws.get<int>(6);
+    b.r2 = b.r1 + 2;
+    b.r3 = b.r1 + 4;
+    b.best_idx = c.ws.get<int>((size_t)ps.nj);
+    b.rblk2 = c.ws.get<int>((size_t)4 * ps.nj);
+    b.rblk3 = b.rblk2 + 2 * ps.nj;
+    b.vrow = c.ws.get<float>((size_t)std::max(1, ps.cand_cs));
+    b.S1s = ps.use_s1 ? c.ws.get<float>((size_t)ps.eq_n * ps.s_cs) : nullptr;
+    b.S2s = (ps.use_s1 && ps.twin) ? c.ws.get<float>((size_t)ps.eq_n * ps.s_cs) : nullptr;
+    if (!ps.scache) CHK(slice_alloc(c, b.sc, pl.geo, false, /*bump=*/true));
     if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", c.ws.off);
-    float *Os = sc->Os, *Gs = ps.G ? sc->Gs : nullptr, *Rs = sc->Rs;
+    return 0;
+}
+// The slice's contents (slice_fill: only what changed is redone).  The first pruned pass of a module measures the share of the
+// metric weight its slice holds: a quarter slice that does not hold it gives way to the full one (pl.k follows what the module
+// settled on), and a slice that turns out loose hands the pass back to the full sweep -- PRUNE_KEEP_FULL, the buffers released.
+int fill_slice(Ctx& c, const Pass& ps, PrunePlan& pl, PruneBufs& b, PruneOutcome& outcome) {
+    if (c.dry) return 0;
+    CHK(slice_fill(c, b.sc, pl.geo, ps.host_sync_ok));
+    if (b.sc->loose) { c.ws.off = b.mark; outcome = PRUNE_KEEP_FULL; return 0; }
+    if (b.sc->k_eff > 0) pl.k = b.sc->k_eff;
+    return 0;
+}
+
+// the row operand of a stage that runs on a slice: the gathered rows, dense [segment][k][K]
+inline void slice_rows(PackParams& pk, const float* rows, int k, int K, bool lin) {
+    pk.src = rows; pk.R = k; pk.s_k = 1; pk.s_r = K; pk.conv = 0;
+    if (!lin) { pk.s_z = (long)k * K; pk.s_z2 = (long)pk.zdiv * k * K; }
+}
+// every stage reads the same scale tables; stage A (or B1 on its synthetic candidate) computes them, `ready`: they are there
+inline void shared_scales(Pass& p, const PruneBufs& b, bool ready) { p.S1_pre = b.S1s; p.S2_pre = b.S2s; p.s_ready = ready; }
+// A survivor range as the host read it (read_survivors); all zero: the host does not know it
+struct Survivors { int lo = 0, hi = 0, count = 0; int blk[2 * MIR_BLK] = {}; bool blk_known = false; };
+// a stage on a device-side candidate range, with what the host knows of it (`s` must outlive the pass)
+inline void ranged(Pass& p, const int* crange, const int* crange_blk, const Survivors& s) {
+    p.crange = crange; p.crange_blk = crange_blk;
+    p.host_lo = s.lo; p.host_hi = s.hi; p.host_rblk = s.blk_known ? s.blk : nullptr;
+}
+// Stages A / A2: `ps` on k gathered rows per segment of the row operand, raw_out and raw_grad; scores only.
+// The candidate-expanded plane of the module is shared with the stage when the slice leaves that operand whole (the column
+// operand: weights of a Linear, B of a matmul): stage A packs all candidates into the module's plane cache once, the later
+// stages and rounds find them there -- as the unpruned passes do -- and when it is the sliced operand that is expanded
+// (activation search), its slice plane is kept with the slice.
+Pass slice_stage_pass(const Pass& ps, const PrunePlan& pl, SliceCache* sc, int k, float* scores) {
     Pass a = ps;
-    if (!c.dry) {
-        CHK(slice_fill(c, sc, geo, ps.host_sync_ok));
-        if (sc->loose) { c.ws.off = mark; PRUNE_COUNT(2); return run_pass(c, ps); }
-        if (sc->k_eff > 0) k = sc->k_eff;
-    }
-    PRUNE_COUNT(0);
-    // stage A: all candidates on the slice
-    a.O = Os; a.G = ps.G ? Gs : nullptr;
+    a.O = sc->Os; a.G = ps.G ? sc->Gs : nullptr;
     a.Mrows = k;
-    auto sliced = [&](PackParams& pk) {
-        pk.src = Rs; pk.R = k; pk.s_k = 1; pk.s_r = ps.K; pk.conv = 0;
-        if (!lin) { pk.s_z = (long)k * ps.K; pk.s_z2 = (long)pk.zdiv * k * ps.K; }
-    };
-    sliced(a.row.pk);
-    if (ps.twin) sliced(a.row2.pk);
-    if (!lin) a.o_zs = (long)k * ps.Ncols;
-    // the candidate-expanded plane of the module is shared with stage A when the slice leaves that operand whole (the column
-    // operand: weights of a Linear, B of a matmul): stage A packs all candidates into the module's plane cache once, the later
-    // stages and rounds find them there -- as the unpruned passes do
-    // ... and when it is the sliced operand that is expanded (activation search), its slice plane is kept with the slice
+    slice_rows(a.row.pk, sc->Rs, k, ps.K, pl.lin);
+    if (ps.twin) slice_rows(a.row2.pk, sc->Rs, k, ps.K, pl.lin);
+    if (!pl.lin) a.o_zs = (long)k * ps.Ncols;
     a.cache = ps.col.expanded ? ps.cache : (ps.cache && ps.scache) ? &sc->aplane : nullptr;
-    a.ecache = nullptr; a.scores_keep = SA; a.no_select = true;
-    a.S1_pre = S1s; a.S2_pre = S2s; a.s_ready = false;
-    // several score blocks whose entries of the candidate table are exactly one row: stage B1 on ONE synthetic candidate
-    const bool virt = ps.nj > 1 && ps.cand_off == 0 && ps.cand_js * ps.nj == ps.cand_cs && ps.cand_cs <= 4096;
-    PruneParams pp{SA, SB, ps.eq_n, ps.nj, prune_margin(), r1, r1, virt ? 1 : 0, best_idx, ps.cands, ps.cand_cs, ps.cand_js, ps.cand_off, vrow};
-    g_stage = 1;
-    { const int r_ = slice_b_ok(a) ? run_slice_b(c, a, SA) : slice_a_ok(a) ? run_slice_a(c, a, SA) : run_pass(c, a); g_stage = 0; if (r_) return r_; }
-    CHK(enqueue(c, KERN(PruneParams, k_prune_pick), dim3(1), dim3(256), 0, pp));
-    // stage B1: the stage-A winners on all samples -> the bound
+    a.ecache = nullptr; a.scores_keep = scores; a.no_select = true;
+    return a;
+}
+// stage A: all candidates on the slice
+Pass stage_a_pass(const Pass& ps, const PrunePlan& pl, const PruneBufs& b) {
+    Pass a = slice_stage_pass(ps, pl, b.sc, pl.k, b.SA);
+    shared_scales(a, b, false);
+    return a;
+}
+// stage B1: the stage-A winners on all samples -> the bound
+Pass stage_b1_pass(const Pass& ps, const PrunePlan& pl, const PruneBufs& b) {
     Pass b1 = ps;
-    b1.scores_keep = SB; b1.no_select = true;
-    if (!virt) { b1.S1_pre = S1s; b1.S2_pre = S2s; b1.s_ready = true; }
-    if (virt) {
+    b1.scores_keep = b.SB; b1.no_select = true;
+    if (pl.virt) {              // ONE candidate, its row of the table written by k_prune_pick: whatever read the table reads that row
         b1.eq_n = 1; b1.cache = nullptr;
-        auto swap = [&](const float*& ptr) { if (ptr == ps.cands) ptr = vrow; };
+        auto swap = [&](const float*& ptr) { if (ptr == ps.cands) ptr = b.vrow; };
         swap(b1.row.pk.scales); swap(b1.row2.pk.scales); swap(b1.col.pk.scales);
         swap(b1.s1.x); swap(b1.s1.y); swap(b1.s2.x); swap(b1.s2.y);
-        b1.cands = vrow;
-    } else { b1.crange = r1; if (ps.nj == 1) b1.host_len = 1; }     // (one score block: r1 = [winner, winner + 1), k_prune_pick)
-    // ONE candidate per score block over all samples: the kernel built for that (k_bound).
-    // Its totals are summed in another order than the sweeps', so from here on nothing may depend on stage B1's numbers but the
-    // bound: the selections below are either "the only survivor of every block" (no totals involved) or come from stage B2,
-    // which always re-evaluates stage B1's candidates together with the other survivors.  The candidate's plane is packed for
-    // this pass (one candidate: ~12 us) instead of being read from the module's plane, whose layout belongs to its sweep kernel.
-    if (lin && ps.i8 && !ps.twin && (virt || ps.nj == 1)) { b1.bound_kernel = true; b1.cache = nullptr; b1.ecache = nullptr; }
-    g_stage = 2;
-    { const int r_ = run_pass(c, b1); g_stage = 0; if (r_) return r_; }
-    if (g_b1_keep && !c.dry && !c.grp) {                   // (tests: the bound's totals, the evaluated entries of SB in table order)
-        std::vector<float> h((size_t)b1.eq_n * std::max(1, ps.nj));
-        CHK(q_d2h(c, h.data(), SB, sizeof(float) * h.size()));
-        CHK(q_sync(c));
-        for (float v : h) if (v != -INFINITY) g_b1_totals.push_back(v);
+        b1.cands = b.vrow;
+    } else {
+        shared_scales(b1, b, true);
+        b1.crange = b.r1;
+        if (ps.nj == 1) b1.host_len = 1;     // (one score block: r1 = [winner, winner + 1), k_prune_pick)
     }
+    if (pl.b1_bound) { b1.bound_kernel = true; b1.cache = nullptr; b1.ecache = nullptr; }
+    return b1;
+}
+// stage A2 (second tier): the survivors `s1` of the first hull on the larger slice
+Pass stage_a2_pass(const Pass& ps, const PrunePlan& pl, const PruneBufs& b, const Survivors& s1) {
+    Pass a2 = slice_stage_pass(ps, pl, b.sc2, pl.k2, b.SA2);
+    ranged(a2, b.r2, b.rblk2, s1);
+    shared_scales(a2, b, true);
+    return a2;
+}
+// stage B2: whatever else survives -- the hull `s` of the last tier that ran -- on all samples (an empty range when stage B1
+// already covers the survivors)
+Pass stage_b2_pass(const Pass& ps, const PruneBufs& b, bool second_tier, const Survivors& s) {
+    Pass b2 = ps;
+    ranged(b2, second_tier ? b.r3 : b.r2, second_tier ? b.rblk3 : b.rblk2, s);
+    b2.scores_keep = b.S2; b2.no_select = true;
+    shared_scales(b2, b, true);
+    return b2;
+}
+
+// the launch records of whatever `fn` enqueues carry `stage`
+template <class Fn> int run_stage(PruneStage stage, Fn&& fn) {
+    g_stage = stage;
+    const int rc = fn();
+    g_stage = STAGE_FULL;
+    return rc;
+}
+int launch_pick(Ctx& c, const PruneParams& pp) { return enqueue(c, KERN(PruneParams, k_prune_pick), dim3(1), dim3(256), 0, pp); }
+// the hull of the survivors into pp.r_out / pp.rblk and (hm: the stream's mapped block) the named mirror slots
+int launch_hull(Ctx& c, PruneParams& pp, const SelectParams& hsl, int* hm, int slot_range, int slot_blk) {
+    pp.r_host = hm ? hm + slot_range : nullptr; pp.rblk_host = hm ? hm + slot_blk : nullptr;
+    return enqueue(c, KERN(HullParams, k_prune_hull), dim3(1), dim3(256), 0, HullParams{pp, hsl});
+}
+// The survivor range a hull wrote to `r` (8 bytes), read after a stream synchronisation -- from the mirror slots where there
+// is a mirror -- and, where they are mirrored (nj <= MIR_BLK), the per-block ranges.  For callers that synchronise after the
+// pass anyway (pass memo): in the usual case stage B1's candidates are the only survivors (count 0) and their totals decide.
+int read_survivors(Ctx& c, const int* r, const int* hm, int slot_range, int slot_blk, int nj, Survivors& s) {
+    int h[2] = {0, 1};
+    if (!hm) CHK(q_d2h(c, h, r, sizeof h));
+    CHK(q_sync(c));
+    const volatile int* m = hm;
+    if (m) { h[0] = m[slot_range]; h[1] = m[slot_range + 1]; }
+    s = Survivors{};
+    if (h[0] >= h[1]) return 0;
+    s.lo = h[0]; s.hi = h[1]; s.count = h[1] - h[0];
+    if (m && nj <= MIR_BLK) { for (int i = 0; i < 2 * nj; ++i) s.blk[i] = m[slot_blk + i]; s.blk_known = true; }
+    return 0;
+}
+// p4v_debug_bound_totals (tests): the bound's totals, the evaluated entries of stage B1's table in table order
+int keep_b1_totals(Ctx& c, const float* SB, size_t n) {
+    std::vector<float> h(n);
+    CHK(q_d2h(c, h.data(), SB, sizeof(float) * n));
+    CHK(q_sync(c));
+    for (float v : h) if (v != -INFINITY) g_b1_totals.push_back(v);
+    return 0;
+}
+// nothing survives besides stage B1's candidates: the pass's selection without another sweep
+int select_without_b2(Ctx& c, const Pass& ps, const PrunePlan& pl, const PruneBufs& b) {
+    PRUNE_COUNT(PRUNE_NO_SURVIVORS);
+    if (pl.hull_selects) {}          // k_prune_hull made the selection
+    else if (pl.virt) {              // every block's only survivor is its stage-A winner: the table with those entries filled in
+        CHK(enqueue(c, KERN(FillParams, k_fill_f32), dim3(cdiv((long)b.tab, 256)), dim3(256), 0, FillParams{b.S2, -INFINITY, (int)b.tab}));
+        CHK(enqueue(c, KERN(MergeVirtParams, k_merge_virtual), dim3(cdiv(ps.nj, 64)), dim3(64), 0, MergeVirtParams{b.S2, b.SB, b.best_idx, ps.nj}));
+        CHK(launch_pass_select(c, ps, b.S2));
+    } else CHK(launch_pass_select(c, ps, b.SB));
+    c.ws.off = b.mark;
+    return 0;
+}
+
+// plan -> buffers -> slice -> A -> pick -> B1 -> hull -> survivors -> (tier 2: slice, A2, hull, survivors) -> B2 -> merge -> select
+int run_pass_pruned_impl(Ctx& c, Pass& ps) {
+    PrunePlan pl;
+    PruneBufs b;
+    PruneOutcome outcome = plan_prune(c, ps, pl);
+    if (outcome == PRUNE_STAGED) { CHK(prune_workspace(c, ps, pl, b)); CHK(fill_slice(c, ps, pl, b, outcome)); }
+    if (outcome != PRUNE_STAGED) { PRUNE_COUNT(outcome); return run_pass(c, ps); }      // not eligible / keeps the full sweep
+    PRUNE_COUNT(PRUNE_STAGED);
+    Pass a = stage_a_pass(ps, pl, b);
+    CHK(run_stage(STAGE_A, [&] { return slice_b_ok(a) ? run_slice_b(c, a, b.SA) : slice_a_ok(a) ? run_slice_a(c, a, b.SA) : run_pass(c, a); }));
+    PruneParams pp{b.SA, b.SB, ps.eq_n, ps.nj, prune_margin(), b.r1, b.r1, pl.virt ? 1 : 0, b.best_idx, ps.cands, ps.cand_cs, ps.cand_js, ps.cand_off, b.vrow};
+    CHK(launch_pick(c, pp));
+    Pass b1 = stage_b1_pass(ps, pl, b);
+    CHK(run_stage(STAGE_B1, [&] { return run_pass(c, b1); }));
+    if (g_b1_keep && !c.dry && !c.grp) CHK(keep_b1_totals(c, b.SB, (size_t)b1.eq_n * ps.nj));
     // the survivors, and -- when there are none besides stage B1's candidates -- the pass's selection from its totals
-    pp.r_out = r2; pp.rblk = rblk2;
-    int* hm = (ps.host_sync_ok && !c.dry) ? host_mirror(c) : nullptr;
-    pp.r_host = hm; pp.rblk_host = hm ? hm + MIR_RB1 : nullptr;
-    int hblk[2 * MIR_BLK] = {};                             // host copy of the per-block ranges stage A2 / B2 run on (nj <= MIR_BLK)
-    int hlo = 0, hhi = 0;
-    bool hblk_ok = false;
-    const bool hull_selects = !ps.scores_out && ps.interval && (virt || ps.nj <= 32);   // (its non-virt selection is serial over the blocks)
-    SelectParams hsl{SB, ps.eq_n, ps.nj, ps.cands, ps.cand_cs, ps.cand_js, ps.cand_off, hull_selects ? ps.interval : nullptr,
+    const bool host_reads = ps.host_sync_ok && !c.dry;      // the caller synchronises after this pass anyway
+    int* hm = host_reads ? host_mirror(c) : nullptr;
+    SelectParams hsl{b.SB, ps.eq_n, ps.nj, ps.cands, ps.cand_cs, ps.cand_js, ps.cand_off, pl.hull_selects ? ps.interval : nullptr,
                      ps.out_js, ps.out_off, ps.aux_out, ps.aux_div, nullptr, 0, ps.best_out};
     attach_mirror(hsl);
-    CHK(enqueue(c, KERN(HullParams, k_prune_hull), dim3(1), dim3(256), 0, HullParams{pp, hsl}));
-    // nothing survives besides stage B1's candidates: the pass's selection without another sweep
-    auto select_without_b2 = [&]() -> int {
-        PRUNE_COUNT(1);
-        if (hull_selects) {}          // k_prune_hull made the selection
-        else if (virt) {          // every block's only survivor is its stage-A winner: the table with those entries filled in
-            CHK(enqueue(c, KERN(FillParams, k_fill_f32), dim3(cdiv((long)tab, 256)), dim3(256), 0, FillParams{S2, -INFINITY, (int)tab}));
-            CHK(enqueue(c, KERN(MergeVirtParams, k_merge_virtual), dim3(cdiv(ps.nj, 64)), dim3(64), 0, MergeVirtParams{S2, SB, best_idx, ps.nj}));
-            CHK(launch_pass_select(c, ps, S2));
-        } else CHK(launch_pass_select(c, ps, SB));
-        c.ws.off = mark;
-        return 0;
-    };
-    int nsurv = 0;
-    if (ps.host_sync_ok && !c.dry) {
-        // the caller synchronises after this pass anyway: read the survivor range (8 bytes); in the usual case stage B1's
-        // candidates are the only survivors and its totals decide -- the ~10 launches of an empty stage B2 are not made
-        int h[2] = {0, 1};
-        if (!hm) CHK(q_d2h(c, h, r2, sizeof h));
-        CHK(q_sync(c));
-        if (hm) { h[0] = reinterpret_cast<volatile int*>(hm)[0]; h[1] = reinterpret_cast<volatile int*>(hm)[1]; }
-        if (h[0] >= h[1]) return select_without_b2();
-        nsurv = h[1] - h[0];
-        hlo = h[0]; hhi = h[1];
-        if (hm && ps.nj <= MIR_BLK) { for (int i = 0; i < 2 * ps.nj; ++i) hblk[i] = reinterpret_cast<volatile int*>(hm)[MIR_RB1 + i]; hblk_ok = true; }
+    pp.r_out = b.r2; pp.rblk = b.rblk2;
+    CHK(launch_hull(c, pp, hsl, hm, MIR_R1, MIR_RB1));
+    Survivors s1, s2;
+    if (host_reads) {
+        CHK(read_survivors(c, b.r2, hm, MIR_R1, MIR_RB1, ps.nj, s1));
+        if (!s1.count) return select_without_b2(c, ps, pl, b);     // the ~10 launches of an empty stage B2 are not made
     }
     // second tier: many survivors of a slice that holds well under all of the weight -> sweep THEM over the larger slice first
-    const int* rB = r2;
-    const int* rBblk = rblk2;
+    bool second_tier = false;
     const int t2min = tune(TUNE_TIER2) >= 2 ? tune(TUNE_TIER2) : 8;
-    if (sc2 && (c.dry || (ps.host_sync_ok && nsurv >= t2min && sc->frac_host < 0.9f))) {
-        if (!c.dry) CHK(slice_fill(c, sc2, geo2, /*host_sync_ok=*/false));
-        Pass a2 = ps;
-        a2.O = sc2->Os; a2.G = ps.G ? sc2->Gs : nullptr; a2.Mrows = k2;
-        auto sliced2 = [&](PackParams& pk) { pk.src = sc2->Rs; pk.R = k2; pk.s_k = 1; pk.s_r = ps.K; pk.conv = 0; };
-        sliced2(a2.row.pk);
-        if (ps.twin) sliced2(a2.row2.pk);
-        a2.cache = ps.col.expanded ? ps.cache : ps.cache ? &sc2->aplane : nullptr;
-        a2.ecache = nullptr; a2.scores_keep = SA2; a2.no_select = true; a2.crange = r2; a2.crange_blk = rblk2;
-        int hblk_a2[2 * MIR_BLK];                         // (stage A2 runs on the first tier's ranges; the second hull overwrites hblk)
-        std::copy(hblk, hblk + 2 * MIR_BLK, hblk_a2);
-        a2.host_lo = hlo; a2.host_hi = hhi; a2.host_rblk = hblk_ok ? hblk_a2 : nullptr;
-        a2.S1_pre = S1s; a2.S2_pre = S2s; a2.s_ready = true;
-        g_stage = 4;
-        { const int r_ = run_pass(c, a2); g_stage = 0; if (r_) return r_; }
-        if (!c.dry) {
-            PruneParams pp2 = pp;                 // same bound L* (stage B1's totals), the tighter partial sums, hull into r3
-            pp2.SA = SA2; pp2.r_out = r3; pp2.r_host = hm ? hm + 2 : nullptr; pp2.rblk = rblk3; pp2.rblk_host = hm ? hm + MIR_RB2 : nullptr;
-            CHK(enqueue(c, KERN(HullParams, k_prune_hull), dim3(1), dim3(256), 0, HullParams{pp2, hsl}));
-            int h[2] = {0, 1};
-            if (!hm) CHK(q_d2h(c, h, r3, sizeof h));
-            CHK(q_sync(c));
-            if (hm) { h[0] = reinterpret_cast<volatile int*>(hm)[2]; h[1] = reinterpret_cast<volatile int*>(hm)[3]; }
-            if (tune(TUNE_PRINT) > 0) fprintf(stderr, "[p4v] second tier: %d survivors of the %d-row slice -> %d of the %d-row slice (M %d N %d K %d)\n", nsurv, k, std::max(0, h[1] - h[0]), k2, ps.Mrows, ps.Ncols, ps.K);
-            if (h[0] >= h[1]) return select_without_b2();
-            rB = r3; rBblk = rblk3;
-            hlo = h[0]; hhi = h[1];
-            if (hm && ps.nj <= MIR_BLK) { for (int i = 0; i < 2 * ps.nj; ++i) hblk[i] = reinterpret_cast<volatile int*>(hm)[MIR_RB2 + i]; }
-            else hblk_ok = false;
+    if (b.sc2 && (c.dry || (ps.host_sync_ok && s1.count >= t2min && b.sc->frac_host < 0.9f))) {
+        if (!c.dry) CHK(slice_fill(c, b.sc2, pl.geo2, /*host_sync_ok=*/false));
+        Pass a2 = stage_a2_pass(ps, pl, b, s1);
+        CHK(run_stage(STAGE_A2, [&] { return run_pass(c, a2); }));
+        if (!c.dry) {       // same bound L* (stage B1's totals), the tighter partial sums, hull into r3
+            pp.SA = b.SA2; pp.r_out = b.r3; pp.rblk = b.rblk3;
+            CHK(launch_hull(c, pp, hsl, hm, MIR_R2, MIR_RB2));
+            CHK(read_survivors(c, b.r3, hm, MIR_R2, MIR_RB2, ps.nj, s2));
+            if (tune(TUNE_PRINT) > 0) fprintf(stderr, "[p4v] second tier: %d survivors of the %d-row slice -> %d of the %d-row slice (M %d N %d K %d)\n", s1.count, pl.k, s2.count, pl.k2, ps.Mrows, ps.Ncols, ps.K);
+            if (!s2.count) return select_without_b2(c, ps, pl, b);
+            second_tier = true;
         }
     }
-    // stage B2: whatever else survives, on all samples (an empty range when stage B1 already covers the survivors)
-    Pass b2 = ps;
-    b2.crange = rB; b2.crange_blk = rBblk; b2.scores_keep = S2; b2.no_select = true;
-    b2.host_lo = hlo; b2.host_hi = hhi; b2.host_rblk = hblk_ok ? hblk : nullptr;
-    b2.S1_pre = S1s; b2.S2_pre = S2s; b2.s_ready = true;
-    g_stage = 3;
-    { const int r_ = run_pass(c, b2); g_stage = 0; if (r_) return r_; }
+    Pass b2 = stage_b2_pass(ps, b, second_tier, second_tier ? s2 : s1);
+    CHK(run_stage(STAGE_B2, [&] { return run_pass(c, b2); }));
     // Stage B2's range is the hull of ALL survivors, stage B1's candidates among them: its table decides.  The merge only fills
     // entries stage B2 did NOT evaluate (-inf) with stage B1's -- i.e. it matters when the device-side range was empty and this
     // path ran without the host knowing (no pass memo): then every block's only survivor is stage B1's candidate.
     if (!c.dry) {
-        if (virt) CHK(enqueue(c, KERN(MergeVirtParams, k_merge_virtual), dim3(cdiv(ps.nj, 64)), dim3(64), 0, MergeVirtParams{S2, SB, best_idx, ps.nj}));
-        else CHK(enqueue(c, KERN(MergeParams, k_merge_scores), dim3(cdiv((long)tab, 256)), dim3(256), 0, MergeParams{S2, SB, (int)tab}));
-        CHK(launch_pass_select(c, ps, S2));
+        if (pl.virt) CHK(enqueue(c, KERN(MergeVirtParams, k_merge_virtual), dim3(cdiv(ps.nj, 64)), dim3(64), 0, MergeVirtParams{b.S2, b.SB, b.best_idx, ps.nj}));
+        else CHK(enqueue(c, KERN(MergeParams, k_merge_scores), dim3(cdiv((long)b.tab, 256)), dim3(256), 0, MergeParams{b.S2, b.SB, (int)b.tab}));
+        CHK(launch_pass_select(c, ps, b.S2));
     }
-    c.ws.off = mark;
+    c.ws.off = b.mark;
     return 0;
+}
+// Variant 134217728 (debug): every eligible pruned pass is followed by the full sweep of the same pass; the selections must be
+// bit-identical (the dry run plans both: the full sweep's planes live in the bump region)
+int run_pass_pruned(Ctx& c, Pass& ps) {
+    PrunePlan pl;
+    if (!(g_variant & 134217728) || plan_prune(c, ps, pl) == PRUNE_NOT_ELIGIBLE || (!c.dry && !ps.interval)) return run_pass_pruned_impl(c, ps);
+    auto full_sweep = [&] {
+        Pass full = ps;
+        full.prunable = false; full.scache = nullptr; full.scache2 = nullptr; full.cache = nullptr; full.ecache = nullptr;
+        return run_pass(c, full);
+    };
+    return cross_checked(c, ps.interval, ps.out_off + (std::max(1, ps.nj) - 1) * ps.out_js + 1, "search pass",
+                         [&] { return run_pass_pruned_impl(c, ps); }, full_sweep);
 }
 
 // ---- split search of the split-of-softmax matmul in one kernel (k_sos_split) -------------------------------------------------
@@ -2319,69 +2401,73 @@ int run_sos_split(Ctx& c, SosSplitJob& j) {
 // The split search with the exact pruning of run_pass_pruned: the 20 splits on the 16 heaviest query rows of every (image, head),
 // the winner on everything (the bound), whatever survives on everything.  Runs once per module (its result does not depend on
 // the intervals: the later rounds are memo hits), before any other pass of the module -- it is what builds the module's slice.
-int run_sos_split_pruned_impl(Ctx& c, SosSplitJob& j);
-int run_sos_split_pruned(Ctx& c, SosSplitJob& j) {
-    if (!(g_variant & 134217728) || c.dry || !j.split) return run_sos_split_pruned_impl(c, j);   // (same scratch as the pruned search)
-    std::vector<float> keep;                      // debug cross-check against the full split search (see run_pass_pruned)
-    CHK(run_sos_split_pruned_impl(c, j));
-    CHK(prune_crosscheck_begin(c, j.split, 1, keep));
-    CHK(run_sos_split(c, j));
-    return prune_crosscheck_end(c, j.split, 1, keep, "split search");
-}
-int run_sos_split_pruned_impl(Ctx& c, SosSplitJob& j) {
+struct SosPruneBufs { size_t mark; float *SA, *SB, *S2; int *r1, *r2; };
+// eligibility, the module's slice (allocated and filled here: this is the module's first pruned pass) and the scratch
+int plan_sos_prune(Ctx& c, SosSplitJob& j, SliceGeo& geo, SosPruneBufs& b, PruneOutcome& outcome) {
     const SosSplitParams& kp = j.kp;
+    outcome = (!j.prunable || !j.scache || j.scores_out || j.best_out || prune_switched_off()) ? PRUNE_NOT_ELIGIBLE
+              : (kp.M < 64 || j.scache->loose) ? PRUNE_KEEP_FULL : PRUNE_STAGED;
+    if (outcome != PRUNE_STAGED) return 0;
     const int k = 16;
-    if (!j.prunable || !j.scache || j.scores_out || j.best_out || (g_variant & 4194304) || kp.M < 64 || j.scache->loose) {
-        PRUNE_COUNT((!j.prunable || !j.scache || j.scores_out || j.best_out || (g_variant & 4194304)) ? 3 : 2);
-        return run_sos_split(c, j);
-    }
-    SliceGeo geo{false, kp.Z, kp.M, k, kp.N, kp.K, kp.O, (kp.wt_mode == 1 ? kp.G : nullptr), kp.wt_mode, (long)kp.N, kp.A, kp.a_r, kp.a_k,
-                 kp.zdiv, kp.a_z2, kp.a_z, false, PackParams{}, k};
-    SliceCache* sc = j.scache;
-    CHK(slice_alloc(c, sc, geo, true, false));
-    const size_t mark = c.ws.off;
-    float* SA = c.ws.get<float>((size_t)kp.C);
-    float* SB = c.ws.get<float>((size_t)kp.C);
-    float* S2 = c.ws.get<float>((size_t)kp.C);
-    int* r1 = c.ws.get<int>(4);
-    int* r2 = r1 + 2;
+    geo = SliceGeo{false, kp.Z, kp.M, k, kp.N, kp.K, kp.O, (kp.wt_mode == 1 ? kp.G : nullptr), kp.wt_mode, (long)kp.N, kp.A, kp.a_r, kp.a_k,
+                   kp.zdiv, kp.a_z2, kp.a_z, false, PackParams{}, k};
+    CHK(slice_alloc(c, j.scache, geo, true, false));
+    b.mark = c.ws.off;
+    b.SA = c.ws.get<float>((size_t)kp.C);
+    b.SB = c.ws.get<float>((size_t)kp.C);
+    b.S2 = c.ws.get<float>((size_t)kp.C);
+    b.r1 = c.ws.get<int>(4);
+    b.r2 = b.r1 + 2;
     if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", c.ws.off);
-    if (!c.dry) {
-        CHK(slice_fill(c, sc, geo, j.host_sync_ok));
-        if (sc->loose) { c.ws.off = mark; PRUNE_COUNT(2); return run_sos_split(c, j); }
-    }
-    PRUNE_COUNT(0);
-    SosSplitParams a = kp;                       // stage A: dense slices [Z][16][K] / [Z][16][N]
+    if (c.dry) return 0;
+    CHK(slice_fill(c, j.scache, geo, j.host_sync_ok));
+    if (j.scache->loose) { c.ws.off = b.mark; outcome = PRUNE_KEEP_FULL; }
+    return 0;
+}
+// stage A of the split search: dense slices [Z][k][K] / [Z][k][N]
+SosSplitParams sos_stage_a(const SosSplitParams& kp, const SliceCache* sc, int k) {
+    SosSplitParams a = kp;
     a.A = sc->Rs; a.a_k = 1; a.a_r = kp.K; a.a_z = (long)k * kp.K; a.a_z2 = (long)kp.zdiv * k * kp.K;
     a.O = sc->Os; a.G = (kp.wt_mode == 1) ? sc->Gs : sc->Os; a.M = k; a.halves = 1;
-    PruneParams pp{SA, SB, kp.C, 1, prune_margin(), r1, r1, 0, nullptr, nullptr, 0, 0, 0, nullptr};
-    g_stage = 1;
-    { const int r_ = sos_sweep(c, j, a, nullptr, SA); g_stage = 0; if (r_) return r_; }
-    CHK(enqueue(c, KERN(PruneParams, k_prune_pick), dim3(1), dim3(256), 0, pp));
-    g_stage = 2;
-    { const int r_ = sos_sweep(c, j, kp, r1, SB, 1); g_stage = 0; if (r_) return r_; }   // B1 (the slice winner)
-    pp.r_out = r2;                                // (+ the selection from its totals when nothing else survives)
+    return a;
+}
+// plan -> slice -> A -> pick -> B1 -> hull -> survivors -> B2 -> merge -> select: the sequence of run_pass_pruned_impl on sos_sweep
+int run_sos_split_pruned_impl(Ctx& c, SosSplitJob& j) {
+    const SosSplitParams& kp = j.kp;
+    SliceGeo geo;
+    SosPruneBufs b;
+    PruneOutcome outcome;
+    CHK(plan_sos_prune(c, j, geo, b, outcome));
+    if (outcome != PRUNE_STAGED) { PRUNE_COUNT(outcome); return run_sos_split(c, j); }
+    PRUNE_COUNT(PRUNE_STAGED);
+    const SosSplitParams a = sos_stage_a(kp, j.scache, geo.k);
+    CHK(run_stage(STAGE_A, [&] { return sos_sweep(c, j, a, nullptr, b.SA); }));
+    PruneParams pp{b.SA, b.SB, kp.C, 1, prune_margin(), b.r1, b.r1, 0, nullptr, nullptr, 0, 0, 0, nullptr};
+    CHK(launch_pick(c, pp));
+    CHK(run_stage(STAGE_B1, [&] { return sos_sweep(c, j, kp, b.r1, b.SB, 1); }));      // the slice winner
+    pp.r_out = b.r2;                              // (+ the selection from its totals when nothing else survives)
     if (!c.dry) {
-        SelectParams hsl = sos_select_params(j, SB);
+        SelectParams hsl = sos_select_params(j, b.SB);
         attach_mirror(hsl);
-        CHK(enqueue(c, KERN(HullParams, k_prune_hull), dim3(1), dim3(256), 0, HullParams{pp, hsl}));
+        CHK(launch_hull(c, pp, hsl, nullptr, MIR_R1, MIR_RB1));
     }
     int survivors = -1;
     if (j.host_sync_ok && !c.dry) {
-        int h[2] = {0, 1};
-        CHK(q_d2h(c, h, r2, sizeof h));
-        CHK(q_sync(c));
-        if (h[0] >= h[1]) { PRUNE_COUNT(1); c.ws.off = mark; return 0; }
-        survivors = std::max(0, std::min(h[1], kp.C) - std::max(h[0], 0));
+        Survivors s;
+        CHK(read_survivors(c, b.r2, nullptr, MIR_R1, MIR_RB1, 1, s));
+        if (!s.count) { PRUNE_COUNT(PRUNE_NO_SURVIVORS); c.ws.off = b.mark; return 0; }
+        survivors = std::max(0, std::min(s.hi, kp.C) - std::max(s.lo, 0));
     }
-    g_stage = 3;
-    { const int r_ = sos_sweep(c, j, kp, r2, S2, survivors); g_stage = 0; if (r_) return r_; }   // B2
-    if (!c.dry) {
-        CHK(enqueue(c, KERN(MergeParams, k_merge_scores), dim3(1), dim3(256), 0, MergeParams{S2, SB, kp.C}));
-    }
-    CHK(sos_select(c, j, S2));
-    c.ws.off = mark;
+    CHK(run_stage(STAGE_B2, [&] { return sos_sweep(c, j, kp, b.r2, b.S2, survivors); }));
+    if (!c.dry) CHK(enqueue(c, KERN(MergeParams, k_merge_scores), dim3(1), dim3(256), 0, MergeParams{b.S2, b.SB, kp.C}));
+    CHK(sos_select(c, j, b.S2));
+    c.ws.off = b.mark;
     return 0;
+}
+// (the cross-check of run_pass_pruned; the dry run plans the pruned search only: same scratch)
+int run_sos_split_pruned(Ctx& c, SosSplitJob& j) {
+    if (!(g_variant & 134217728) || c.dry || !j.split) return run_sos_split_pruned_impl(c, j);
+    return cross_checked(c, j.split, 1, "split search", [&] { return run_sos_split_pruned_impl(c, j); }, [&] { return run_sos_split(c, j); });
 }
 
 // ---- exact memoisation of search passes ---------------------------------------------------------------------

@@ -1,0 +1,118 @@
+"""Shared by tests/test_hip_pruned_stages.py and tools/plan_dump.py: the smallest calibration per branch of the pruned drivers
+(csrc/p4v_api.hip: plan_prune, run_pass_pruned, run_sos_split_pruned; DESIGN.md s5.1 "exact candidate pruning"), three search
+rounds each, W8A8, hessian, 100 candidates, seeded inputs (the generators of tests/sweep_plan_cases.py).
+
+The slice rules give the sizes: a Linear is staged from 640 samples (5 k <= 2 M with k >= 256), tries the quarter slice from
+M = 4 112 (k_cap >= 512) and plans a second tier from M = 2 048 (k2 = rup(M / 4, 256) >= 2 k_cap); a MatMul from 64 query rows.
+Which branch a Linear takes depends on the share of the metric weight (raw_grad^2 summed per sample) its slice holds: the cases
+state the share they need as (slice rows, lower bound, upper bound) and `run` asserts it on the host before the call.
+
+`run(eng, mode, prune=True)` makes ONE call and returns (intervals, tables):
+  "default"  the pass memo is on, so the pruned passes may read their survivors back (host_sync_ok)
+  "nomemo"   desc.reserved bit 1: the host does not read the survivors, stage B2 is always launched and the merge decides
+  "xcheck"   the default call with variant bit 134217728: every pruned pass is followed by its full sweep, the engine compares
+prune=False (desc.reserved bit 3) is the same call with full sweeps only: the reference of the intervals."""
+import torch
+
+from tests.search_round_cases import ROUNDS, _call, _cuda, run_case  # noqa: F401  (run_case: re-exported)
+from tests.sweep_plan_cases import LOOSE, conv_inputs, linear_inputs, matmul_inputs
+
+MODES = ("default", "nomemo", "xcheck")
+XCHECK = 134217728
+XCHECKED = ("lin650_cls", "lin650_nV3", "qk65", "sos65")
+
+
+def slice_share(grad, k):
+    """share of the metric weight in the k heaviest samples of a Linear (what k_mass_fraction measures for a k-row slice)"""
+    m = (grad.double() ** 2).sum(-1).flatten()
+    return float(torch.topk(m, k).values.sum() / m.sum())
+
+
+def _linear_grad(grad, shape, kind, spread, seed):
+    """"cls": the class-token-heavy raw_grad of the generator; "flat": every sample alike; "spread": per-sample log-normal"""
+    g = torch.Generator().manual_seed(seed + 1000)
+    if kind == "flat":
+        return torch.randn(shape, generator=g) * 1e-10
+    if kind == "spread":
+        return torch.randn(shape, generator=g) * 1e-10 * torch.exp(spread * torch.randn(shape[0], shape[1], 1, generator=g))
+    return grad
+
+
+def _linear(K, N, *, seed, images, tokens, grad="cls", spread=0.0, shares=(), n_V=1, postgelu=False, variant=0, tuning=(), scores=False):
+    def run(eng, mode, prune=True):
+        w, b, x, out, gr = linear_inputs(K, N, seed=seed, images=images, tokens=tokens, postgelu=postgelu)
+        gr = _linear_grad(gr, out.shape, grad, spread, seed)
+        for k, lo, hi in shares:
+            assert lo <= slice_share(gr, k) < hi, (k, lo, slice_share(gr, k), hi)
+        eng.debug_variant(variant | (XCHECK if mode == "xcheck" else 0))
+        for key, value in tuning:
+            eng.debug_tuning(key, value)
+        try:
+            job = eng.linear_job(weight=_cuda(w), bias=_cuda(b), x=_cuda(x), out=_cuda(out), grad=_cuda(gr), w_bit=8, a_bit=8,
+                                 metric="hessian", n_V=n_V, n_H=1, n_a=1, postgelu=postgelu, want_scores=scores, prune=prune, **ROUNDS)
+            return _call(eng, job, mode)
+        finally:
+            eng.debug_variant(0)
+            for key, _ in tuning:
+                eng.debug_tuning(key, 0)
+    return run
+
+
+def _matmul(M, K, N, *, seed, sos=False):
+    def run(eng, mode, prune=True):
+        A, B, out, grad = matmul_inputs(M, K, N, seed=seed, sos=sos)
+        eng.debug_variant(LOOSE | (XCHECK if mode == "xcheck" else 0))
+        try:
+            job = eng.matmul_job(A=_cuda(A), B=_cuda(B), out=_cuda(out), grad=_cuda(grad), A_bit=8, B_bit=8, metric="hessian", sos=sos,
+                                 prune=prune, **ROUNDS)
+            return _call(eng, job, mode)
+        finally:
+            eng.debug_variant(0)
+    return run
+
+
+def _conv(*, seed, a_bit):
+    def run(eng, mode, prune=True):
+        w, b, x, out, grad = conv_inputs(seed=seed, images=10, size=64, patch=8)
+        eng.debug_variant(LOOSE | (XCHECK if mode == "xcheck" else 0))
+        try:
+            job = eng.conv_job(weight=_cuda(w), bias=_cuda(b), x=_cuda(x), out=_cuda(out), grad=_cuda(grad), stride=(8, 8), padding=(0, 0),
+                               dilation=(1, 1), w_bit=8, a_bit=a_bit, metric="hessian", prune=prune, **ROUNDS)
+            return _call(eng, job, mode)
+        finally:
+            eng.debug_variant(0)
+    return run
+
+
+L650 = dict(images=10, tokens=65)        # 650 samples: one 256-row slice
+L4137 = dict(images=21, tokens=197)      # 4 137 samples: a 512-row slice, tried as 128 rows first
+L2048 = dict(images=16, tokens=128)      # 2 048 samples: a 256-row slice and a 512-row second tier
+
+# (name, run)
+CASES = [
+    # the 650-row Linear: the engine's own decision on a class-token profile and on a flat one (slice loose: full sweeps), the flat
+    # one staged by force (many survivors), three score blocks (stage B1 on the synthetic candidate), the post-GELU twin
+    ("lin650_cls", _linear(192, 96, seed=41, shares=[(256, 0.97, 1.0)], **L650)),
+    ("lin650_flat", _linear(192, 96, seed=41, grad="flat", shares=[(256, 0.0, 0.5)], **L650)),
+    ("lin650_flat_forced", _linear(192, 96, seed=41, grad="flat", shares=[(256, 0.0, 0.5)], variant=LOOSE, **L650)),
+    ("lin650_nV3", _linear(192, 96, seed=42, n_V=3, variant=LOOSE, **L650)),
+    ("postgelu650", _linear(192, 96, seed=45, postgelu=True, variant=LOOSE, **L650)),
+    # the quarter slice kept (it holds >= 0.97 of the weight) and rejected (the full slice is ranked again and holds >= 0.5)
+    ("lin4137_quarter", _linear(64, 64, seed=43, shares=[(128, 0.97, 1.0)], **L4137)),
+    ("lin4137_spread", _linear(64, 64, seed=43, grad="spread", spread=1.1, shares=[(128, 0.0, 0.97), (512, 0.5, 1.0)], **L4137)),
+    # the second tier: a first slice with 0.5 .. 0.9 of the weight and at least two survivors (tuning 13 = 2)
+    ("lin2048_tier2", _linear(64, 96, seed=44, n_V=3, grad="spread", spread=0.8, shares=[(256, 0.5, 0.9)], tuning=[(13, 2)], **L2048)),
+    # MatMul, 2 x 2 heads, 65 query rows: q.k^T with head_dim 64 (stage A in one kernel on both sides) and 128; the split search
+    ("qk65", _matmul(65, 64, 65, seed=46)),
+    ("qk65_d128", _matmul(65, 128, 65, seed=47)),
+    ("sos65", _matmul(65, 65, 64, seed=48, sos=True)),
+    # Conv: 10 x 3 x 64 x 64, 16 filters of 8 x 8, stride 8 -- 640 output pixels; fp32 planes (a_bit 32) and int8
+    ("conv640_a32", _conv(seed=49, a_bit=32)),
+    ("conv640_a8", _conv(seed=50, a_bit=8)),
+    # score tables asked for: no pass is eligible
+    ("lin650_scores", _linear(192, 96, seed=41, scores=True, **L650)),
+]
+
+
+def modes_of(name):
+    return tuple(m for m in MODES if m != "xcheck" or name in XCHECKED)

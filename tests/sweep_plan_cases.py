@@ -91,13 +91,13 @@ def _matmul_blocks(name):
     return run
 
 
-def conv_inputs(*, seed):
-    """(weight, bias, x, out, grad) of the seeded 2 x 3 x 32 x 32, 16-filter patch embedding, on the host"""
+def conv_inputs(*, seed, images=2, size=32, patch=16):
+    """(weight, bias, x, out, grad) of a seeded 16-filter patch embedding (by default 2 x 3 x 32 x 32, 16 x 16 patches), on the host"""
     g = torch.Generator().manual_seed(seed)
-    x = torch.randn(2, 3, 32, 32, generator=g)
-    w = torch.randn(16, 3, 16, 16, generator=g) * 0.02 * torch.linspace(0.5, 2.0, 16).view(-1, 1, 1, 1)
+    x = torch.randn(images, 3, size, size, generator=g)
+    w = torch.randn(16, 3, patch, patch, generator=g) * 0.02 * torch.linspace(0.5, 2.0, 16).view(-1, 1, 1, 1)
     b = torch.randn(16, generator=g) * 0.02
-    out = F.conv2d(x, w, b, stride=16)
+    out = F.conv2d(x, w, b, stride=patch)
     return w, b, x, out, torch.randn(out.shape, generator=g) * 1e-10
 
 

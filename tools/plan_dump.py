@@ -6,7 +6,7 @@ calibrates them; metrics, blocks, pruning on / off, fp32 planes -- the sizes do 
 --gpu: also the cases of tests/sweep_plan_cases.py, pruning off and on: launch records (kernel, stage, grid_x, grid_z) in order,
 p4v_launch_counters, p4v_prune_counters, and the raw bytes of the returned intervals, score tables and selections (as hex where
 they are at most 16 bytes, as a sha256 prefix otherwise); then the three-round cases of tests/search_round_cases.py in each of
-their modes, with the pass memo's (hits, misses) as well.  No timings: two runs of the same code give the same file.
+their modes, with the pass memo's (hits, misses) as well, and the cases of tests/pruned_pass_cases.py in theirs.  No timings: two runs of the same code give the same file.
 
     python tools/plan_dump.py [--gpu] [--out FILE]
 """
@@ -34,6 +34,7 @@ def linear_descs():
         if D < 768:
             shapes.append((16, T // 4, 4 * D, 2 * D, 1))
     shapes.append((16, 1, 768, 1000, 1))
+    shapes += [(16, 128, 64, 96, 3), (21, 197, 64, 64, 1)]      # the smallest that plan a second tier / the quarter slice
     for (b, T, K, N, nV), metric, bits, reserved in itertools.product(shapes, (HESSIAN, COSINE, L2), (8,), (0, 8, 1)):
         for postgelu in ((0, 1) if K >= N and K >= 768 else (0,)):
             yield _lib.LinearDesc(b, T, K, N, nV, 1, 1, bits, bits, metric, 100, 3, postgelu, 0, 1, reserved)
@@ -132,6 +133,15 @@ def gpu_plan():
                      "prune_counters": [r["prune_counters"][k] for k in ("staged", "staged_no_survivors", "kept_full_sweep", "not_eligible")],
                      "memo": list(r["memo"]), "results": [_raw(t) for t in r["intervals"] + r["tables"]]})
         engine.release_workspace()
+    from tests.pruned_pass_cases import CASES as PRUNED_CASES, modes_of
+    for name, run in PRUNED_CASES:
+        for mode in modes_of(name):
+            r = run_rounds(engine, run, mode)
+            rows.append({"case": name, "mode": mode, "records": _runs(r["records"]),
+                         "launch_counters": [r["launch_counters"][k] for k in ("asked", "issued", "rounds", "groups")],
+                         "prune_counters": [r["prune_counters"][k] for k in ("staged", "staged_no_survivors", "kept_full_sweep", "not_eligible")],
+                         "memo": list(r["memo"]), "results": [_raw(t) for t in r["intervals"] + r["tables"]]})
+            engine.release_workspace()
     return rows
 
 
