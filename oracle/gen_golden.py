@@ -8,7 +8,7 @@ intervals, expected score tables).  The reference does not exist on the GPU
 box, so this script is never run there; the committed ``.npz`` files travel.
 
     python oracle/gen_golden.py            # rewrites tests/golden/*.npz
-    python oracle/gen_golden.py convgeo    # only the convgeo_* files (likewise ptqslconv, minivit, mixbit, ...)
+    python oracle/gen_golden.py convgeo    # only the convgeo_* files (likewise ptqslconv, minivit, mixbit, degen, ...)
 """
 import json
 import os
@@ -85,7 +85,10 @@ def _cls_heavy(grad, token_dim, g):
     return grad
 
 
-def gen_linear(name, *, shape_x, oc, postgelu=False, grad_scale=1e-3, seed=0, bias=True, cls_heavy=False, store_qf=True, **kw):
+def gen_linear(name, *, shape_x, oc, postgelu=False, grad_scale=1e-3, seed=0, bias=True, cls_heavy=False, store_qf=True,
+               mutate=None, **kw):
+    """`mutate(w, x)`: changes the two tensors in place BEFORE `out` is computed and the reference runs, and returns what goes
+    into `params` on top of the hyper-parameters (gen_degenerate: `zero_blocks`).  The random stream is not touched."""
     from quant_layers.linear import PTQSLBatchingQuantLinear, PostGeluPTQSLBatchingQuantLinear
 
     g = torch.Generator().manual_seed(seed)
@@ -97,6 +100,7 @@ def gen_linear(name, *, shape_x, oc, postgelu=False, grad_scale=1e-3, seed=0, bi
     x = torch.randn(*shape_x, generator=g)
     if postgelu:
         x = F.gelu(1.5 * x)
+    extra = mutate(w, x) if mutate else {}
     out = F.linear(x, w, b)
     grad = torch.randn(out.shape, generator=g) * grad_scale
     if cls_heavy:
@@ -120,10 +124,11 @@ def gen_linear(name, *, shape_x, oc, postgelu=False, grad_scale=1e-3, seed=0, bi
         arrays["quant_forward"] = qf.numpy()[:1, :8]
     if bias:
         arrays["bias"] = b.numpy()
-    _save(name, dict(kind="linear", postgelu=postgelu, oc=oc, **kw), arrays, rec.tables)
+    _save(name, dict(kind="linear", postgelu=postgelu, oc=oc, **kw, **extra), arrays, rec.tables)
 
 
-def gen_matmul(name, *, b, H, d1, d2, d3, sos=False, grad_scale=1e-3, seed=0, cls_heavy=False, store_qf=True, **kw):
+def gen_matmul(name, *, b, H, d1, d2, d3, sos=False, grad_scale=1e-3, seed=0, cls_heavy=False, store_qf=True, mutate=None, **kw):
+    """`mutate(A, B)`: as in gen_linear, on the two operands (B is the transposed view the reference is handed)."""
     from quant_layers.matmul import PTQSLBatchingQuantMatMul, SoSPTQSLBatchingQuantMatMul
 
     g = torch.Generator().manual_seed(seed)
@@ -133,6 +138,7 @@ def gen_matmul(name, *, b, H, d1, d2, d3, sos=False, grad_scale=1e-3, seed=0, cl
         A = torch.randn(b, H, d1, d2, generator=g) * torch.linspace(0.5, 2.0, H).view(1, H, 1, 1)
     # B is handed over as a transposed view in the q.k^T case (utils/models.py:16)
     Bm = (torch.randn(b, H, d3, d2, generator=g) * torch.linspace(2.0, 0.5, H).view(1, H, 1, 1)).transpose(-2, -1)
+    extra = mutate(A, Bm) if mutate else {}
     out = A @ Bm
     grad = torch.randn(out.shape, generator=g) * grad_scale
     if cls_heavy:
@@ -152,7 +158,7 @@ def gen_matmul(name, *, b, H, d1, d2, d3, sos=False, grad_scale=1e-3, seed=0, cl
         arrays["quant_forward"] = qf.numpy()[:1, :1, :8]
     if sos:
         arrays["split"] = np.asarray(m.split)
-    _save(name, dict(kind="matmul", sos=sos, **kw), arrays, rec.tables)
+    _save(name, dict(kind="matmul", sos=sos, **kw, **extra), arrays, rec.tables)
 
 
 def _pair(v):
@@ -318,9 +324,113 @@ def gen_mixed_bits(cases=None):
         print(f"  {name}: smallest decision gap {gap:.2e}, {os.path.getsize(os.path.join(OUT, name + '.npz'))} bytes")
 
 
+# --------------------------------------------------------------------------- #
+# zero and non-positive initial intervals on Linear and MatMul (prefix `degen_`: no other parametrisation loads them)
+# --------------------------------------------------------------------------- #
+_DG_HS = dict(metric="hessian", eq_alpha=0.01, eq_beta=1.2, eq_n=100, search_round=2)
+_DG_COS = dict(metric="cosine", eq_alpha=0.5, eq_beta=1.2, eq_n=100, search_round=2)
+_DG_L2 = dict(_DG_HS, metric="L2_norm")
+_DG_QKV = dict(shape_x=(4, 13, 48), oc=36, n_V=3)                 # linear_qkv_hessian_w8a8
+_DG_GELU = dict(shape_x=(4, 13, 64), oc=24, postgelu=True, n_V=1, w_bit=8, a_bit=8)          # postgelu_hessian_w8a8
+_DG_QK = dict(b=4, H=3, d1=13, d2=8, d3=13, A_bit=8, B_bit=8)     # matmul_qk_hessian_w8a8
+_DG_SOS = dict(b=4, H=3, d1=13, d2=13, d3=8, sos=True, A_bit=8, B_bit=8)                     # matmul_sos_hessian_w8a8
+
+
+def _zero_w(oc, ic, n_V, n_H, blocks):
+    """Weight blocks (v, h) of the (n_V, n_H) grid set to zero."""
+    def mutate(w, x):
+        for v, h in blocks:
+            w[v * (oc // n_V):(v + 1) * (oc // n_V), h * (ic // n_H):(h + 1) * (ic // n_H)] = 0.0
+        return dict(zero_blocks=[["w", v, h] for v, h in blocks])
+    return mutate
+
+
+def _zero_a(ic, n_a, groups):
+    """Activation column groups set to zero."""
+    def mutate(w, x):
+        for a in groups:
+            x[..., a * (ic // n_a):(a + 1) * (ic // n_a)] = 0.0
+        return dict(zero_blocks=[["a", a] for a in groups])
+    return mutate
+
+
+def _gelu_nonpositive(w, x):
+    """Every positive activation becomes an exact zero -- a NEGATIVE zero, as a product with a negative factor leaves it -- so the
+    twin's SIGNED maximum, the interval and every candidate are -0.0."""
+    x.copy_(torch.where(x > 0, torch.full_like(x, -0.0), x))
+    assert float(x.max()) == 0.0 and float(x.min()) < 0.0 and not bool((torch.signbit(x) == 0).any())
+    return dict(zero_blocks=[["a", 0]])
+
+
+def _gelu_negative(w, x):
+    """Strictly negative input: the signed maximum, and with it the interval and every candidate, is negative."""
+    x.copy_(-x.abs() - 0.0025)
+    assert float(x.max()) < 0.0
+    return dict(zero_blocks=[], negative_interval=True)
+
+
+def _zero_head(which, head, v=None, h=None, n_V=1, n_H=1):
+    """One head of A or B set to zero -- or, with (v, h), one sub-block of that head (blocks of ceil(dim / n))."""
+    def mutate(A, B):
+        X = A if which == "A" else B
+        if v is None:
+            X[:, head] = 0.0
+            return dict(zero_blocks=[[which, head]])
+        cr, cc = -(-X.shape[2] // n_V), -(-X.shape[3] // n_H)
+        X[:, head, v * cr:(v + 1) * cr, h * cc:(h + 1) * cc] = 0.0
+        return dict(zero_blocks=[[which, head, v, h]])
+    return mutate
+
+
+# (generator, name, arguments).  Shapes and hyper-parameters: those of the small layer fixtures named beside them.
+DEGENERATE_CASES = [
+    ("gen_linear", "degen_linear_v3_hessian_zero_rows", dict(_DG_QKV, w_bit=8, a_bit=8, seed=300, mutate=_zero_w(36, 48, 3, 1, [(1, 0)]), **_DG_HS)),
+    ("gen_linear", "degen_linear_v3_cosine_zero_rows", dict(_DG_QKV, w_bit=8, a_bit=8, seed=301, mutate=_zero_w(36, 48, 3, 1, [(1, 0)]), **_DG_COS)),
+    ("gen_linear", "degen_linear_v3_l2_w6a6_zero_rows", dict(_DG_QKV, w_bit=6, a_bit=6, seed=302, mutate=_zero_w(36, 48, 3, 1, [(1, 0)]), **_DG_L2)),
+    ("gen_linear", "degen_linear_v3_hessian_zero_weight",
+     dict(_DG_QKV, w_bit=8, a_bit=8, seed=303, mutate=_zero_w(36, 48, 3, 1, [(0, 0), (1, 0), (2, 0)]), **_DG_HS)),
+    ("gen_linear", "degen_linear_v3_hessian_zero_input", dict(_DG_QKV, w_bit=8, a_bit=8, seed=304, mutate=_zero_a(48, 1, [0]), **_DG_HS)),
+    # linear_blocks_nH2_na2: the fp32 general route
+    ("gen_linear", "degen_linear_v2h2a2_hessian_zero_cols",
+     dict(shape_x=(3, 7, 32), oc=16, n_V=2, n_H=2, n_a=2, w_bit=8, a_bit=8, seed=305, mutate=_zero_w(16, 32, 2, 2, [(0, 1)]),
+          **dict(_DG_HS, eq_alpha=0.2, eq_n=40))),
+    # linblk_cos_v2h2a3_w4a4 with two activation groups: the K-segmented route
+    ("gen_linear", "degen_linear_v2h2a2_cosine_zero_act",
+     dict(shape_x=(3, 11, 24), oc=16, n_V=2, n_H=2, n_a=2, w_bit=4, a_bit=4, seed=306, mutate=_zero_a(24, 2, [1]), **_DG_COS)),
+    ("gen_linear", "degen_postgelu_hessian_nonpositive", dict(_DG_GELU, seed=307, mutate=_gelu_nonpositive, **_DG_HS)),
+    ("gen_linear", "degen_postgelu_hessian_negative", dict(_DG_GELU, seed=308, mutate=_gelu_negative, **_DG_HS)),
+    ("gen_matmul", "degen_matmul_qk_hessian_zero_A_head", dict(_DG_QK, seed=310, mutate=_zero_head("A", 1), **_DG_HS)),
+    ("gen_matmul", "degen_matmul_qk_hessian_zero_B_head", dict(_DG_QK, seed=311, mutate=_zero_head("B", 1), **_DG_HS)),
+    ("gen_matmul", "degen_matmul_sos_hessian_zero_B_head", dict(_DG_SOS, seed=312, mutate=_zero_head("B", 1), **_DG_HS)),
+    # mmblk_qk_hessian_vA2hA2_vB2hB3's shape with 2 x 2 blocks on both operands: a B block of real data that is all zero
+    ("gen_matmul", "degen_mmblk_qk_hessian_zero_B_block",
+     dict(_DG_QK, seed=313, n_V_A=2, n_H_A=2, n_V_B=2, n_H_B=2, mutate=_zero_head("B", 1, 1, 0, 2, 2), **_DG_HS)),
+]
+
+
+def gen_degenerate(cases=None):
+    """Blocks whose initial min-max interval is 0 (fake quantisation 0 / 0, NaN score column, argmax takes
+    candidate 0) or negative (the post-GELU twin's signed maximum) on Linear and MatMul: the existing generators with a hook
+    that changes the tensors before `out` is computed and the reference runs.  A case on which the reference raises is skipped
+    and named (DESIGN.md s1 lists them)."""
+    raised = []
+    for gen, name, kw in (DEGENERATE_CASES if cases is None else cases):
+        try:
+            with np.errstate(invalid="ignore", divide="ignore"):
+                globals()[gen](name, **kw)
+        except Exception as e:      # noqa: BLE001
+            raised.append((name, repr(e)))
+            print(f"  {name}: the reference raised {e!r}")
+            continue
+        print(f"  {name}: {os.path.getsize(os.path.join(OUT, name + '.npz'))} bytes")
+    return raised
+
+
 def main(only=None):
     _install_shims()
     os.chdir(REF)
+    if only == "degen":
+        return gen_degenerate()
     if only == "minivit":
         return gen_mini_vit()
     if only == "ptqslconv":
@@ -368,6 +478,7 @@ def main(only=None):
              metric="hessian", eq_alpha=0.3, eq_beta=1.2, eq_n=30, search_round=2)
     gen_conv_geometries()
     gen_mixed_bits()
+    gen_degenerate()
 
 
 

@@ -1469,6 +1469,7 @@ int pack_fixed_planes(Ctx& c, const Pass& ps, const SweepPlan& pl, const PassBuf
         Operand both = ps.row;              // positive range: scale + upper clamp; negative range: fixed scale + lower clamp
         both.pk.mode = PACK_TWIN_I8;
         both.pk.lo = ps.row2.pk.lo; both.pk.neg_scale = ps.row2.pk.neg_scale;
+        both.pk.dst2 = b.row2;              // ... where the interval is not > 0: the two planes apart (k_pack_twin), for the two-plane sweep
         CHK(pack_operand(c, ps, pl, b, both, b.row, false, 0, 1));
     } else if (ps.twin && ps.i8 && !ps.row.expanded && !ps.row2.expanded && dual_pack_ok(ps.row.pk, ps.row2.pk)) {
         // both planes of the twin row operand from one read of the source (k_pack_dual)
@@ -1603,6 +1604,7 @@ int sweep_chunk_large_k(Ctx& c, const Pass& ps, const SweepPlan& pl, const PassB
     if (tune(TUNE_CG7) > 0) cg7 = std::max(1, std::min(nc, tune(TUNE_CG7)));
     q.order = tune(TUNE_ORDER7) > 0 ? tune(TUNE_ORDER7) - 1 : 1;
     if (tune(TUNE_PRINT) > 0) fprintf(stderr, "[p4v] sweep7 tiles %d x %d ktiles %d cand %d twin %d -> cgroups %d\n", q.rtiles, q.ctiles, q.ktiles, nc, (int)ps.twin, cg7);
+    if (pl.kind == SK_SWEEP7_MERGED) { q.twin_s = ps.row.pk.scales; q.C2 = b.row2; }   // (merged or apart: decided on the device)
     return launch_sweep7(c, q, pl.kind == SK_SWEEP7_MERGED ? 2 : ps.twin ? 1 : 0, ps.epi, cg7);
 }
 
@@ -2897,6 +2899,7 @@ struct LinearCall {
         float* mix = ws ? w_mix : a_mix;
         ScaleParams mp{};
         mp.x = ws ? w_iv : a_iv; mp.x_cs = 0; mp.x_js = 1; mp.y = nullptr; mp.y_const = 1.0f; mp.C = ncand; mp.nblk = n; mp.S = mix;
+        mp.copy = 1;                      // (the fp32 packers divide by these themselves: a zero interval stays 0, its plane is 0 / 0)
         CHK(launch_scale(c, mp));
         for (int v = 0; v < rows; ++v)
             CHK(q_copy2d(c, mix + v * nH + blk, sizeof(float) * n, cands + v * nH + blk, sizeof(float) * n, sizeof(float), ncand));

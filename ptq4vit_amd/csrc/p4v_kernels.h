@@ -161,19 +161,25 @@ __global__ void k_make_cands(CandsParams p) { k_make_cands_body(p, P4V_BIDX, P4V
 __global__ void k_make_cands_g(GroupArgs<CandsParams> a) { P4V_GROUP_ENTER(a); k_make_cands_body(a.p[m_], vb_, vg_); }
 
 // S[c][j] = X(c,j) * Y(c,j); each factor is a device array (with candidate / block strides) or a constant.
+// A factor that is +-0 makes the entry NaN: an interval of 0 is a block that is all zero, whose fake quantisation is 0 / 0 in
+// the reference.  An int8 plane cannot carry that NaN and 0 * dot is finite, so the scale that
+// multiplies the integer dot product carries it into every output the block touches.  `copy`: the table is a broadcast of
+// intervals that the fp32 packers divide by themselves (mix_candidates): zeros stay zeros.
 struct ScaleParams {
     const float* x; int x_cs, x_js; float x_const;
     const float* y; int y_cs, y_js; float y_const;
     int C, nblk;
     float* S;
+    int copy;
 };
+__device__ __forceinline__ float nan_if_zero(float s) { return s == 0.0f ? __builtin_nanf("") : s; }
 __device__ __forceinline__ void k_scale_table_body(const ScaleParams& p, const uint3 blockIdx, const uint3 gridDim) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= p.C * p.nblk) return;
     const int c = i / p.nblk, j = i % p.nblk;
     const float x = p.x ? p.x[c * p.x_cs + j * p.x_js] : p.x_const;
     const float y = p.y ? p.y[c * p.y_cs + j * p.y_js] : p.y_const;
-    p.S[i] = x * y;
+    p.S[i] = (p.copy || (x != 0.0f && y != 0.0f)) ? x * y : __builtin_nanf("");
 }
 __global__ void k_scale_table(ScaleParams p) { k_scale_table_body(p, P4V_BIDX, P4V_GDIM); }
 __global__ void k_scale_table_g(GroupArgs<ScaleParams> a) { P4V_GROUP_ENTER(a); k_scale_table_body(a.p[m_], vb_, vg_); }
@@ -219,6 +225,7 @@ struct PackParams {
     // optional im2col gather (conv): logical r = (b, oy, ox), k = (ci, ki, kj)
     int conv, ic, H, W, kh, kw, sh, sw, ph, pw, dh, dw, fw, L;
     float qbias;          // != 0 (set by launch_pack for PACK_SYM on the full symmetric 8-bit grid): quant16_sat8 with this bias
+    void* dst2;           // PACK_TWIN_I8 (k_pack_twin): where the negative range's plane goes when the two cannot be merged
 };
 
 __device__ __forceinline__ float pack_value(const PackParams& p, float x, float s) {
@@ -242,15 +249,17 @@ __device__ __forceinline__ float pack_value_f32(const PackParams& p, float x, fl
             const float q = rintf(x / s);
             return (q != q ? q : fminf(fmaxf(q, (float)p.lo), (float)p.hi)) * s;
         }
-        case PACK_SOS_SIM: {
+        case PACK_SOS_SIM: {          // (a NaN can only come from the low range's division: split = 0)
             const float a_int = s / p.qm1;
             const float hi = fminf(fmaxf(rintf(fminf(fmaxf(x, s), 1.0f) * p.qm1), 0.0f), p.qm1) / p.qm1;
-            const float lo = fminf(fmaxf(rintf(fminf(fmaxf(x, 0.0f), s) / a_int), 0.0f), p.qm1) * a_int;
+            const float ql = rintf(fminf(fmaxf(x, 0.0f), s) / a_int);
+            const float lo = (ql != ql ? ql : fminf(fmaxf(ql, 0.0f), p.qm1)) * a_int;
             return hi + lo;
         }
-        case PACK_TWIN_SIM: {
-            const float pos = fminf(fmaxf(rintf(x / s), 0.0f), (float)p.hi) * s;
-            const float neg = fminf(fmaxf(rintf(x / p.neg_scale), (float)p.lo), 0.0f) * p.neg_scale;
+        case PACK_TWIN_SIM: {         // s = +-0 (the signed maximum of an input without a positive entry): 0 / 0 where x = 0
+            const float qp = rintf(x / s), qn = rintf(x / p.neg_scale);
+            const float pos = (qp != qp ? qp : fminf(fmaxf(qp, 0.0f), (float)p.hi)) * s;
+            const float neg = (qn != qn ? qn : fminf(fmaxf(qn, (float)p.lo), 0.0f)) * p.neg_scale;
             return pos + neg;
         }
         default: return x;
@@ -542,12 +551,17 @@ __device__ __forceinline__ void pack_load16(const PackParams& p, const float* zb
 // padding included: x = 0 there).  The plane holds the byte of the float sum of the two indices; both are integers in
 // [-128, 127], so that byte is the sum mod 256, added bytewise without carries between the bytes.  (With positive scales
 // the supports are disjoint -- x > 0 clamps the negative range to 0, x < 0 the positive one -- and one of the two is 0.)
+// That holds for a positive interval only.  A negative one (the signed maximum of an input that is negative throughout) puts
+// BOTH indices of a negative x off zero and their sum cannot be split again; 0 and NaN merge nothing either.  With `dst2` set
+// the kernel then writes the two planes apart -- the positive range's to dst, the negative range's to dst2 -- and the sweep,
+// which reads the same interval (Sweep7Params.twin_s), runs its two-plane form on them: no read-back, no second launch.
 __device__ __forceinline__ void k_pack_twin_body(const PackParams& p, const uint3 blockIdx, const uint3 gridDim) {
     const unsigned kchunks = p.Kp / 16;
     const unsigned total = (unsigned)p.Z * p.Rp * kchunks;
     const float s = p.scales[0], sn = p.neg_scale, flo = (float)p.lo, fhi = (float)p.hi;
     const float rs = 1.0f / s, rn = 1.0f / sn;
     const bool wide = !(fmaxf(-flo, fhi) < 129.0f);
+    const bool apart = p.dst2 && !(s > 0.0f);
     for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
         const unsigned row = i / kchunks;
         const int kc = (int)(i - row * kchunks);
@@ -558,13 +572,19 @@ __device__ __forceinline__ void k_pack_twin_body(const PackParams& p, const uint
         v4i a, b;
         quant16_any(x, s, rs, 0.0f, fhi, wide, a);
         quant16_any(x, sn, rn, flo, 0.0f, wide, b);
+        const long o = ((long)z * p.Rp + r) * p.Kp + (long)kc * 16;
+        if (apart) {
+            __builtin_nontemporal_store(a, reinterpret_cast<v4i*>(reinterpret_cast<int8_t*>(p.dst) + o));
+            __builtin_nontemporal_store(b, reinterpret_cast<v4i*>(reinterpret_cast<int8_t*>(p.dst2) + o));
+            continue;
+        }
         v4i w;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const unsigned ua = (unsigned)a[q], ub = (unsigned)b[q];
             w[q] = (int)(((ua & 0x7f7f7f7fu) + (ub & 0x7f7f7f7fu)) ^ ((ua ^ ub) & 0x80808080u));
         }
-        __builtin_nontemporal_store(w, reinterpret_cast<v4i*>(reinterpret_cast<int8_t*>(p.dst) + (((long)z * p.Rp + r) * p.Kp + (long)kc * 16)));
+        __builtin_nontemporal_store(w, reinterpret_cast<v4i*>(reinterpret_cast<int8_t*>(p.dst) + o));
     }
 }
 __global__ __launch_bounds__(256) void k_pack_twin(PackParams p) { k_pack_twin_body(p, P4V_BIDX, P4V_GDIM); }
@@ -3278,6 +3298,10 @@ struct Sweep7Params {
     float* part; long p_cs; int NG;     // part[c * p_cs + (ct * 4 + wc) * NG + rt * 8 + wr * 4 + j]
     int rtiles, ctiles, cgroups;
     int order;                          // workgroup order on the 1-D grid (see the kernel)
+    // TW = 2: the positive range's interval.  The merged plane is the twin only while *twin_s > 0 (k_pack_twin); otherwise that
+    // kernel left the two planes apart in Cp / C2 and the launch runs the two-plane sweep (TW = 1) on them -- same grid, same
+    // LDS, same tables.  The host cannot know the sign without a read-back.  nullptr: merged, unconditionally.
+    const float* twin_s;
 };
 
 // timing-only ablation builds (never in production): -DP4V_SW7_DBG=1 no operand stream, 2 no MFMA, 4 no epilogue (bits add)
@@ -3736,9 +3760,20 @@ __device__ __forceinline__ void k_sweep7_body(const Sweep7Params& p, const uint3
     }
 }
 template <int TW, int EPI>
-__global__ __launch_bounds__(512, 2) void k_sweep7(Sweep7Params p) { k_sweep7_body<TW, EPI>(p, P4V_BIDX, P4V_GDIM); }
+// TW = 2 holds both bodies behind a branch that is uniform over the grid (Sweep7Params.twin_s): twice the code, and the register
+// allocation of the larger of the two.  This is the weight search of every post-GELU fc2 (K = 3072 on ViT-B), a hot kernel of the
+// headline benchmark: tests/test_isa_budget.py holds it to 256 registers / two waves per SIMD, and profiles/r19_bench_ab.json
+// is the A/B of the whole calibration with and without the second body (inside the parent's own spread).
+__global__ __launch_bounds__(512, 2) void k_sweep7(Sweep7Params p) {
+    if constexpr (TW == 2) { if (p.twin_s && !(p.twin_s[0] > 0.0f)) { k_sweep7_body<1, EPI>(p, P4V_BIDX, P4V_GDIM); return; } }
+    k_sweep7_body<TW, EPI>(p, P4V_BIDX, P4V_GDIM);
+}
 template <int TW, int EPI>
-__global__ __launch_bounds__(512, 2) void k_sweep7_g(GroupArgs<Sweep7Params> a) { P4V_GROUP_ENTER(a); k_sweep7_body<TW, EPI>(a.p[m_], vb_, vg_); }
+__global__ __launch_bounds__(512, 2) void k_sweep7_g(GroupArgs<Sweep7Params> a) {
+    P4V_GROUP_ENTER(a);
+    if constexpr (TW == 2) { if (a.p[m_].twin_s && !(a.p[m_].twin_s[0] > 0.0f)) { k_sweep7_body<1, EPI>(a.p[m_], vb_, vg_); return; } }
+    k_sweep7_body<TW, EPI>(a.p[m_], vb_, vg_);
+}
 
 // ------------------------------------------------------------------------------------------
 // k_sos_split: the split search of the split-of-softmax matmul (reference matmul.py:600-631) in one kernel
@@ -4797,7 +4832,7 @@ __device__ __forceinline__ void k_sweep_seg_body(const SweepSegParams& p, const 
             const int s = i >> 7, v = min(min(m0 + (i & 127), p.M - 1) / p.m_div, p.nVA - 1), h = sblk[s];
             float val = TWIN ? p.rs_const : p.ivA[(head * p.nVA + v) * p.nHA + h];
             if (!TWIN && c >= 0 && p.side == 1 && v == p.ov_v && h == p.ov_h) val = p.cands[(long)c * p.cand_cs + head * p.cand_hs];
-            rs[i] = val;
+            rs[i] = nan_if_zero(val);     // (the blocks of real rows only: a block of nothing but padding is never indexed)
         }
     };
     auto fill_cols = [&](int c) {
@@ -4805,12 +4840,12 @@ __device__ __forceinline__ void k_sweep_seg_body(const SweepSegParams& p, const 
             const int s = i >> 7, h = min(min(n0 + (i & 127), p.N - 1) / p.n_div, p.nHB - 1), v = sblk[SEG_MAX + s];
             float val = p.ivB[((p.b_shared ? 0 : head) * p.nVB + v) * p.nHB + h];
             if (c >= 0 && p.side == 2 && v == p.ov_v && h == p.ov_h) val = p.cands[(long)c * p.cand_cs + head * p.cand_hs];
-            cs[i] = val;
+            cs[i] = nan_if_zero(val);
         }
     };
     fill_rows(-1);
     fill_cols(-1);
-    const float rs2 = TWIN ? p.rs2[0] : 0.0f;
+    const float rs2 = TWIN ? nan_if_zero(p.rs2[0]) : 0.0f;
 
     // ---- candidate-invariant epilogue operands (k_sweep's phases 1 and 2) ---------------------------
     float u[2][16], w[2][16];
