@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define P4V_VERSION 141 /* 0.1.4.1: + p4v_matmul_blocks_* (MatMul row / column sub-blocks, n_V / n_H > 1) */
+#define P4V_VERSION 142 /* 0.1.4.2: + p4v_mlp_* (fused int8 MLP forward: fc1, GELU and fc2's quantiser in one pass) */
 
 /* similarity metrics: reference quant_layers/linear.py:399-424 */
 enum p4v_metric {
@@ -428,6 +428,32 @@ int p4v_export_quantize(const p4v_export_desc* desc, const float* d_src, const f
 int p4v_linear_quant_forward(const p4v_linear_desc* desc, const float* d_weight, const float* d_bias, const float* d_x,
                              const float* d_w_interval, const float* d_a_interval, float* d_out, void* d_workspace,
                              size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Fused MLP forward (opt-in, network level): fc2(GELU(fc1(x))) of two calibrated Linear layers with int8 in between.
+ * fc1 is the int8 GEMM above; its epilogue applies the exact (erf) GELU to scale * acc + bias and quantises the result with
+ * fc2's activation quantiser (`fc2.twin_postgelu`: the two ranges of linear.py:605-606 as two planes; else one symmetric
+ * plane) straight into the int8 plane(s) fc2's GEMM reads: the fp32 hidden tensor is neither written nor read.  fc2 is the
+ * GEMM of p4v_linear_quant_forward on those planes.  d_out equals p4v_linear_quant_forward of fc2 on the hidden tensor this
+ * call computes, bit for bit; against the unfused chain the hidden tensor differs where the two builds' erf do (measured:
+ * profiles/r20_fused_mlp_margins.json).
+ * Envelope: w_bit, a_bit 2..8, n_H = n_a = 1 on both layers, any n_V that divides, with or without biases, fc1 not
+ * twin_postgelu, fc1.out_features = fc2.in_features, the same batch * tokens; anything else is P4V_ERR_UNSUPPORTED /
+ * P4V_ERR_INVALID before the first launch.  The descriptors' search fields are ignored.
+ * d_x [M][fc1.in_features]; d_out [M][fc2.out_features]; d_hidden: optional (may be NULL, then nothing is stored for it)
+ * [M][fc1.out_features] fp32, the GELU output the planes were quantised from.  The workspace contract above holds with
+ * p4v_mlp_workspace_bytes (d_ws, ws_bytes: the workspace and its size); a smaller ws_bytes is refused before any launch.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct p4v_mlp_desc {
+    p4v_linear_desc fc1, fc2;
+} p4v_mlp_desc;
+
+size_t p4v_mlp_workspace_bytes(const p4v_mlp_desc* desc);
+
+int p4v_mlp_quant_forward(const p4v_mlp_desc* desc, const float* d_w1, const float* d_b1, const float* d_w2, const float* d_b2,
+                          const float* d_x, const float* d_w1_interval, const float* d_a1_interval,
+                          const float* d_w2_interval, const float* d_a2_interval, float* d_out, float* d_hidden, void* d_ws,
+                          size_t ws_bytes, void* stream);
 
 /* d_A_interval: [heads] (sos: [1]); d_B_interval: [heads]; d_split: [1] (sos only); d_out: [batch*heads][M][N] */
 int p4v_matmul_quant_forward(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_A_interval,

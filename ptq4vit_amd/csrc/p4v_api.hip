@@ -978,6 +978,9 @@ struct Operand {
     PackParams pk;        // src/strides/sizes/scales/mode filled by the caller (dst, C, Rp, Kp set by run_pass)
     bool expanded;        // true: one plane per candidate
     bool present;
+    const void* plane;    // row / row2 of a forward pass only: the operand is PREPACKED -- this is its fixed int8 plane, row-major
+                          // [pl.Mp][pl.Kp] as plan_sweep sizes it, written by an earlier launch on the stream (mlp_impl: fc1's
+                          // epilogue); nothing is allocated or packed for it.  nullptr (everything else): packed from pk.src
 };
 
 // A MatMul pass with row / column sub-blocks (n_V, n_H > 1; matmul_impl): the K axis cut where either operand's scale changes
@@ -1384,8 +1387,9 @@ int pass_workspace(Ctx& c, const Pass& ps, const SweepPlan& pl, PassBufs& b) {
         pc->assigned = true; pc->valid = false;
         if (!c.dry && pc->done) CHK(q_fill(c, pc->done, 0, (size_t)ps.eq_n));
     }
-    b.row = (pc && ps.row.expanded) ? pc->buf : c.ws.get<char>((size_t)pl.row_plane1 * (ps.row.expanded ? pl.chunk_al : 1) + pl.slack);
-    b.row2 = ps.twin ? c.ws.get<char>((size_t)pl.row_plane1 * (ps.row2.expanded ? pl.chunk : 1)) : nullptr;
+    b.row = ps.row.plane ? (char*)ps.row.plane :
+            (pc && ps.row.expanded) ? pc->buf : c.ws.get<char>((size_t)pl.row_plane1 * (ps.row.expanded ? pl.chunk_al : 1) + pl.slack);
+    b.row2 = !ps.twin ? nullptr : ps.row2.plane ? (char*)ps.row2.plane : c.ws.get<char>((size_t)pl.row_plane1 * (ps.row2.expanded ? pl.chunk : 1));
     b.col = (pc && ps.col.expanded) ? pc->buf : c.ws.get<char>((size_t)pl.col_plane1 * (ps.col.expanded ? pl.chunk_al : 1) + pl.slack);
     b.part = c.ws.get<float>((size_t)pl.part_cs * ps.eq_n);
     b.S1 = !ps.use_s1 ? nullptr : ps.S1_pre ? ps.S1_pre : c.ws.get<float>((size_t)ps.eq_n * ps.s_cs);
@@ -1465,7 +1469,11 @@ int prep_epilogue(Ctx& c, const Pass& ps, const SweepPlan& pl, const PassBufs& b
 
 // the planes that do not depend on the candidate, once
 int pack_fixed_planes(Ctx& c, const Pass& ps, const SweepPlan& pl, const PassBufs& b) {
-    if (pl.merged7) {
+    if (ps.row.plane) {
+        // prepacked row operand (the fused MLP forward): its plane(s) are on the stream already
+        if (ps.row.expanded || pl.merged7 || pl.cin_fix != 0 || (ps.twin && (!ps.row2.plane || ps.row2.expanded)))
+            return fail(P4V_ERR_INVALID, "prepacked row operand: fixed row-major plane(s) of a forward pass only");
+    } else if (pl.merged7) {
         Operand both = ps.row;              // positive range: scale + upper clamp; negative range: fixed scale + lower clamp
         both.pk.mode = PACK_TWIN_I8;
         both.pk.lo = ps.row2.pk.lo; both.pk.neg_scale = ps.row2.pk.neg_scale;
@@ -2990,6 +2998,91 @@ int linear_impl(const p4v_linear_desc* d, const float* W, const float* bias, con
 }
 
 // ------------------------------------------------------------------------------------------------
+// Fused MLP forward (p4v_mlp_quant_forward): fc1 -> GELU -> fc2's activation quantiser -> fc2 with int8 in between
+// ------------------------------------------------------------------------------------------------
+// fc1's part: x and W1 packed as LinearCall::forward_pass packs them (pack_operand, k_scale_table), then k_mlp_fc1, whose
+// epilogue writes fc2's row plane(s) -- the fp32 hidden tensor, torch's GELU over it and k_pack_dual / k_pack1 of it are gone.
+// fc2's part: its forward pass as run_pass runs it, the row operand prepacked (Operand.plane): same sweep kernel, same epilogue.
+// Where the planes of the calling thread's last call lie in its workspace (p4v_debug_mlp_planes: the tests read them there)
+struct MlpPlanes { size_t off1 = 0, off2 = 0; long rows = 0, cols = 0; int twin = 0; };
+thread_local MlpPlanes g_mlp_planes;
+constexpr int MLP_RECORD_KIND = 16;
+
+int mlp_impl(const p4v_mlp_desc* d, const float* W1, const float* b1, const float* W2, const float* b2, const float* X,
+             const float* w1_iv, const float* a1_iv, const float* w2_iv, const float* a2_iv, float* out, float* hidden, Ctx& c) {
+    const p4v_linear_desc* d1 = &d->fc1;
+    const p4v_linear_desc* d2 = &d->fc2;
+    // the envelope, before anything is planned or launched
+    if ((long)d1->batch * d1->tokens != (long)d2->batch * d2->tokens || d1->out_features != d2->in_features)
+        return fail(P4V_ERR_INVALID, "mlp: fc1's output [%ld][%d] is not fc2's input [%ld][%d]", (long)d1->batch * d1->tokens, d1->out_features,
+                    (long)d2->batch * d2->tokens, d2->in_features);
+    if (d1->n_H != 1 || d1->n_a != 1 || d2->n_H != 1 || d2->n_a != 1)
+        return fail(P4V_ERR_UNSUPPORTED, "mlp: the fused forward takes n_H = n_a = 1 on both layers");
+    if (d1->twin_postgelu) return fail(P4V_ERR_UNSUPPORTED, "mlp: fc1 reads no GELU output (twin_postgelu belongs on fc2)");
+    if ((d1->reserved | d2->reserved) & 1) return fail(P4V_ERR_UNSUPPORTED, "mlp: int8 planes only (desc.reserved bit 0 is set)");
+    const Stage sg{};
+    float* tag = (float*)16;        // "this is a forward call" for LinearCall::build: fc1 stores no fp32 output, the sizing run has none
+    LinearCall L1(c, d1, sg), L2(c, d2, sg);
+    CHK(L1.build(W1, b1, X, nullptr, nullptr, nullptr, const_cast<float*>(w1_iv), const_cast<float*>(a1_iv), nullptr, nullptr, tag));
+    CHK(L2.build(W2, b2, nullptr, nullptr, nullptr, nullptr, const_cast<float*>(w2_iv), const_cast<float*>(a2_iv), nullptr, nullptr, out ? out : tag));
+    if (!L1.i8 || !L2.i8) return fail(P4V_ERR_UNSUPPORTED, "mlp: int8 planes only");
+    // fc2's pass first: its plan says how large the row plane(s) are
+    Pass fp2 = L2.forward_pass();
+    SweepPlan pl2;
+    CHK(plan_sweep(c, fp2, pl2));
+    if (pl2.cin_fix != 0 || pl2.merged7 || pl2.esz != 1) return fail(P4V_ERR_UNSUPPORTED, "mlp: fc2's sweep does not read row-major int8 planes");
+    const int M = L1.M, K1 = L1.K, Hd = L1.N;
+    const int Mp = pl2.Mp, Kp = pl2.Kp;                       // Kp = roundup64(hidden)
+    const int K1p = (int)rup(K1, 64), Hp = (int)rup(Hd, SW_BN);
+    char* P1 = c.ws.get<char>((size_t)Mp * Kp);
+    char* P2 = L2.twin ? c.ws.get<char>((size_t)Mp * Kp) : nullptr;
+    {
+        const size_t mark = c.ws.off;
+        Pass fp1 = L1.forward_pass();
+        SweepPlan pl1{};                                       // what pack_operand reads of a plan: the plane geometry
+        pl1.esz = 1; pl1.Mp = Mp; pl1.Np = pl1.NpB = Hp; pl1.Kp = K1p; pl1.cin_fix = 0;
+        char* xa = c.ws.get<char>((size_t)Mp * K1p);
+        char* wb = c.ws.get<char>((size_t)Hp * K1p);
+        float* S1 = c.ws.get<float>((size_t)L1.nV);
+        if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", c.ws.off);
+        fp1.s1.S = S1; fp1.s1.C = 1; fp1.s1.nblk = fp1.s_cs;
+        CHK(launch_scale(c, fp1.s1));
+        const PassBufs nb{};
+        CHK(pack_operand(c, fp1, pl1, nb, fp1.row, xa, false, 0, 1));
+        CHK(pack_operand(c, fp1, pl1, nb, fp1.col, wb, true, 0, 1));
+        if (!c.dry) {
+            MlpFc1Params q{};
+            q.A = xa; q.B = wb; q.ldk = K1p; q.ktiles = K1p / SW_BKB;
+            q.S1 = S1; q.s_cs = L1.nV; q.sb_div = L1.crb_rows;
+            q.bias = L1.bias; q.M = M; q.N = Hd; q.mtiles = Mp / SW_BM; q.ntiles = Hp / SW_BN;
+            q.q1 = a2_iv; q.q2 = nullptr; q.q2_const = L2.a_neg;
+            q.lo1 = L2.twin ? 0 : -L2.aq; q.hi1 = L2.aq - 1; q.lo2 = -L2.aq; q.hi2 = 0;
+            q.P1 = (int8_t*)P1; q.P2 = (int8_t*)P2; q.Kp = Kp; q.hidden = hidden;
+            g_alg_macs_cand = (double)M * Hd * K1;
+            g_alg_bytes = 4.0 * ((double)M * K1 + (double)Hd * K1) + (double)M * Hd * (L2.twin ? 2 : 1);
+            g_exec_frac = 1.0;
+            const StatInfo si = stat_info(MLP_RECORD_KIND, (double)Mp * Hp * K1p, g_alg_macs_cand, q.mtiles * q.ntiles, 1, g_alg_bytes);
+            const dim3 grid(q.mtiles * q.ntiles), block(512);
+            const size_t lds = 2 * 2 * SW_TILE_BYTES;
+            if (L2.twin) CHK(enqueue(c, KERN1_T(MlpFc1Params, k_mlp_fc1, true), grid, block, lds, q, &si));
+            else CHK(enqueue(c, KERN1_T(MlpFc1Params, k_mlp_fc1, false), grid, block, lds, q, &si));
+            g_mlp_planes = MlpPlanes{(size_t)(P1 - c.ws.base), P2 ? (size_t)(P2 - c.ws.base) : 0, Mp, Kp, L2.twin ? 1 : 0};
+        }
+        c.ws.off = mark;
+    }
+    fp2.row.plane = P1 ? (const void*)P1 : (const void*)16;   // (the sizing run carves nothing)
+    if (L2.twin) fp2.row2.plane = P2 ? (const void*)P2 : (const void*)16;
+    return run_pass(c, fp2);
+}
+// the dry run of the planner: the envelope's verdict, and the bytes the call needs
+int mlp_sizing_run(const p4v_mlp_desc* d, size_t* need) {
+    Ctx c{nullptr, Arena(nullptr, 0), true};
+    CHK(mlp_impl(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, c));
+    *need = c.ws.peak + 4096;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // MatMul
 // ------------------------------------------------------------------------------------------------
 // Row / column sub-blocks of the (n_G, n_V, n_H) view (reference matmul.py:109-138); (v, h): the block of a granular step
@@ -3641,6 +3734,28 @@ int p4v_linear_quant_forward(const p4v_linear_desc* desc, const float* d_weight,
                        const_cast<float*>(d_w_interval), const_cast<float*>(d_a_interval), nullptr, nullptr, c, d_out);
 }
 
+size_t p4v_mlp_workspace_bytes(const p4v_mlp_desc* desc) {
+    size_t need = 0;
+    return (desc && mlp_sizing_run(desc, &need) == 0) ? need : 0;
+}
+
+int p4v_mlp_quant_forward(const p4v_mlp_desc* desc, const float* d_w1, const float* d_b1, const float* d_w2, const float* d_b2,
+                          const float* d_x, const float* d_w1_interval, const float* d_a1_interval, const float* d_w2_interval,
+                          const float* d_a2_interval, float* d_out, float* d_hidden, void* d_ws, size_t ws_bytes, void* stream) {
+    if (!desc || !d_w1 || !d_w2 || !d_x || !d_w1_interval || !d_a1_interval || !d_w2_interval || !d_a2_interval || !d_out || !d_ws)
+        return fail(P4V_ERR_INVALID, "p4v_mlp_quant_forward: null pointer");
+    if ((desc->fc1.has_bias && !d_b1) || (desc->fc2.has_bias && !d_b2))
+        return fail(P4V_ERR_INVALID, "p4v_mlp_quant_forward: has_bias set but the bias is null");
+    CHK(ws_aligned(d_ws));
+    // fc1's launches precede the planning of fc2's pass: the whole need is checked here, before the first of them
+    size_t need = 0;
+    CHK(mlp_sizing_run(desc, &need));
+    if (ws_bytes < need) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", need);
+    Ctx c{(hipStream_t)stream, Arena(d_ws, ws_bytes), false};
+    return mlp_impl(desc, d_w1, desc->fc1.has_bias ? d_b1 : nullptr, d_w2, desc->fc2.has_bias ? d_b2 : nullptr, d_x, d_w1_interval,
+                    d_a1_interval, d_w2_interval, d_a2_interval, d_out, d_hidden, c);
+}
+
 int p4v_matmul_quant_forward(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_A_interval,
                              const float* d_B_interval, const float* d_split, float* d_out, void* d_workspace,
                              size_t workspace_bytes, void* stream) {
@@ -4045,7 +4160,7 @@ static int stats_drain() {
         float ms = 0;
         HIPCHK(hipEventElapsedTime(&ms, r.a, r.b));
         ms = (float)std::max(0.0, (double)ms - g_evt_overhead_ms);
-        if (r.kind == 0 || (r.kind >= 2 && r.kind <= 9) || (r.kind >= 12 && r.kind <= 15)) { g_stats.sweep_i8_ms += ms; g_stats.sweep_i8_launches++; g_stats.sweep_i8_macs += r.macs; g_stats.sweep_i8_alg_macs += r.alg; }
+        if (r.kind == 0 || (r.kind >= 2 && r.kind <= 9) || (r.kind >= 12 && r.kind <= 16)) { g_stats.sweep_i8_ms += ms; g_stats.sweep_i8_launches++; g_stats.sweep_i8_macs += r.macs; g_stats.sweep_i8_alg_macs += r.alg; }
         if (r.kind == 2) { g_stats.sweep6_ms += ms; g_stats.sweep6_launches++; g_stats.sweep6_macs += r.macs; g_stats.sweep6_alg_macs += r.alg; }
         if (r.kind == 3 || r.kind == 4) { g_stats.sweep7_ms += ms; g_stats.sweep7_launches++; g_stats.sweep7_macs += r.macs; g_stats.sweep7_alg_macs += r.alg; }
         if (r.kind == 4) { g_stats.sweep7_twin_ms += ms; g_stats.sweep7_twin_launches++; }
@@ -4118,6 +4233,13 @@ int p4v_debug_arena_ranges(uint64_t* out, int cap) {
     const int n = (int)g_arena_ranges.size();
     for (int i = 0; out && i < std::min(n, cap); ++i) { out[2 * i] = g_arena_ranges[i].first; out[2 * i + 1] = g_arena_ranges[i].second; }
     return n;
+}
+
+int p4v_debug_mlp_planes(uint64_t* out) {
+    if (!out) return fail(P4V_ERR_INVALID, "p4v_debug_mlp_planes: null pointer");
+    const MlpPlanes& m = g_mlp_planes;
+    out[0] = m.off1; out[1] = m.off2; out[2] = (uint64_t)m.rows; out[3] = (uint64_t)m.cols; out[4] = (uint64_t)m.twin;
+    return m.rows > 0 ? 0 : fail(P4V_ERR_INVALID, "p4v_debug_mlp_planes: no p4v_mlp_quant_forward call on this thread yet");
 }
 
 int p4v_debug_sos_sweep(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_out, const float* d_grad,

@@ -5035,4 +5035,147 @@ __global__ __launch_bounds__(512) void k_sweep_seg(SweepSegParams p) { k_sweep_s
 template <bool TWIN, int EPI>
 __global__ __launch_bounds__(512) void k_sweep_seg_g(GroupArgs<SweepSegParams> a) { P4V_GROUP_ENTER(a); k_sweep_seg_body<TWIN, EPI>(a.p[m_], vb_, vg_); }
 
+// ------------------------------------------------------------------------------------------
+// Fused MLP forward, first half (p4v_mlp_quant_forward): fc1's int8 GEMM whose epilogue ends in fc2's int8 row plane(s)
+// ------------------------------------------------------------------------------------------
+// k_sweep<int8_t>'s LDS-staged 128 x 128 tile (2 x 4 waves of 64 x 32, the same staging, fragment and C/D maps) over ONE pair of
+// planes (no candidates, no batch): A = Q(x) [Mp][ldk], B = Q(W1) [Hp][ldk].  Per output element
+//   v = (float)acc * S1[vblock(n)] + bias[n]            EPI_FWD's expression: what fc1.quant_forward stores
+//   g = v * 0.5 * (1 + erf(v * 0.70710678))             exact GELU, the form torch's nn.GELU() evaluates in fp32
+//   TWIN:  plane 1 = clamp(rint(g / s_pos), 0, hi1), plane 2 = clamp(rint(g / s_neg), lo2, 0)    (post-GELU fc2, linear.py:605-606)
+//   else:  plane 1 = clamp(rint(g / s_a), lo1, hi1)
+// with pack_value -- the quantiser of k_pack<int8_t> / k_pack_dual, IEEE division included.  The planes are fc2's row operand as
+// its forward sweep reads it: row-major [Mp][Kp], Kp = roundup64(hidden); rows >= M and columns >= N are written as zeros (the
+// grid covers every 128-row tile of the plane).  After the k-loop a lane holds one hidden column for 32 rows: the tile's bytes
+// go through the staging LDS (free behind the loop's last barrier; rows 144 bytes apart) and leave as 16-byte pieces, 128
+// contiguous bytes per row.  `hidden` (optional) receives g as fp32 [M][N]; a null pointer costs no store.
+struct MlpFc1Params {
+    const void* A; const void* B;
+    int ldk, ktiles;
+    const float* S1; int s_cs, sb_div;        // combined scale s_a * s_w[block] per V block of fc1 (k_scale_table)
+    const float* bias;                        // fc1's bias [N] or nullptr
+    int M, N;                                 // valid rows; hidden features
+    int mtiles, ntiles;
+    const float* q1; const float* q2; float q2_const;   // fc2's activation interval(s): *q1; TWIN: *q2, or q2_const when q2 is null
+    int lo1, hi1, lo2, hi2;
+    int8_t* P1; int8_t* P2; int Kp;           // the plane(s): [mtiles * 128][Kp]
+    float* hidden;
+};
+static constexpr int MLP_OROW = SW_BN + 16;   // LDS row of the output tile: 128 bytes + 16 bytes pad
+
+template <bool TWIN>
+__device__ __forceinline__ void k_mlp_fc1_body(const MlpFc1Params& p, const uint3 blockIdx, const uint3 gridDim) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int STAGE = 2 * SW_TILE_BYTES;
+    static_assert((TWIN ? 2 : 1) * SW_BM * MLP_OROW <= 2 * STAGE, "the output tile(s) must fit the staging buffers");
+
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int wr = wid >> 2, wc = wid & 3;            // 2 x 4 waves, each 64 rows x 32 cols
+    const int g = lane >> 5, l31 = lane & 31;
+    const int nwg = p.mtiles * p.ntiles;
+    const int t = xcd_remap(blockIdx.x, nwg);
+    const int mt = t % p.mtiles, nt = t / p.mtiles;   // m fastest: tiles sharing a W1 panel are adjacent
+    const int m0 = mt * SW_BM, n0 = nt * SW_BN;
+
+    const int n = n0 + wc * 32 + l31;
+    const bool ncol_ok = n < p.N;
+    const float bias_n = (p.bias && ncol_ok) ? p.bias[n] : 0.0f;
+    const int sb = min(n / p.sb_div, p.s_cs - 1);
+
+    // ---- global -> LDS staging: one 16-byte piece per thread per plane per k-tile ---------------------
+    const int ld_row = tid >> 2, ld_col = (tid & 3) * 16;
+    const char* gA = (const char*)p.A + (long)(m0 + ld_row) * p.ldk + ld_col;
+    const char* gB = (const char*)p.B + (long)(n0 + ld_row) * p.ldk + ld_col;
+    const int lds_st = ld_row * SW_ROW + ld_col;
+    v4i ra, rb;
+    auto gload = [&](int kt) {
+        ra = *reinterpret_cast<const v4i*>(gA + kt * SW_BKB);
+        rb = *reinterpret_cast<const v4i*>(gB + kt * SW_BKB);
+    };
+    auto lstore = [&](int stage) {
+        char* s = smem + stage * STAGE + lds_st;
+        *reinterpret_cast<v4i*>(s) = ra;
+        *reinterpret_cast<v4i*>(s + SW_TILE_BYTES) = rb;
+    };
+
+    v16i acc[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][r] = 0;
+
+    const int fa = (wr * 64 + l31) * SW_ROW;       // + i*32*SW_ROW
+    const int fb = SW_TILE_BYTES + (wc * 32 + l31) * SW_ROW;
+
+    gload(0);
+    lstore(0);
+    __syncthreads();
+
+    for (int kt = 0; kt < p.ktiles; ++kt) {
+        const int stage = kt & 1;
+        if (kt + 1 < p.ktiles) gload(kt + 1);
+        const char* s = smem + stage * STAGE;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {          // two 32-deep K steps per 64-byte row
+            const int off = h * 32 + g * 16;
+            const v4i b = *reinterpret_cast<const v4i*>(s + fb + off);
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const v4i a = *reinterpret_cast<const v4i*>(s + fa + i * 32 * SW_ROW + off);
+                acc[i] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, acc[i], 0, 0, 0);
+            }
+        }
+        if (kt + 1 < p.ktiles) lstore(stage ^ 1);
+        __syncthreads();
+    }
+
+    // ---- epilogue: scale + bias, GELU, fc2's quantiser; the bytes of the tile into LDS ------------------
+    const float s1 = p.S1 ? p.S1[sb] : 1.0f;
+    const float qs1 = p.q1[0];
+    const float qs2 = TWIN ? (p.q2 ? p.q2[0] : p.q2_const) : 0.0f;
+    PackParams pv1{}, pv2{};
+    pv1.mode = PACK_SYM; pv1.lo = p.lo1; pv1.hi = p.hi1;
+    pv2.mode = PACK_SYM; pv2.lo = p.lo2; pv2.hi = p.hi2;
+    char* o1 = smem;
+    char* o2 = smem + SW_BM * MLP_OROW;
+    const int col_l = wc * 32 + l31;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row_l = wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
+            const int m = m0 + row_l;
+            const bool ok = ncol_ok && m < p.M;
+            const float o_sim = (float)acc[i][r] * s1;
+            const float v = o_sim + bias_n;
+            const float ge = v * 0.5f * (1.0f + erff(v * 0.70710678118654752440f));
+            if (p.hidden && ok) p.hidden[(long)m * p.N + n] = ge;
+            const float b1 = ok ? pack_value(pv1, ge, qs1) : 0.0f;
+            o1[row_l * MLP_OROW + col_l] = (char)((int)b1 & 0xff);
+            if (TWIN) {
+                const float b2 = ok ? pack_value(pv2, ge, qs2) : 0.0f;
+                o2[row_l * MLP_OROW + col_l] = (char)((int)b2 & 0xff);
+            }
+        }
+    __syncthreads();
+
+    // ---- LDS -> global: 16-byte pieces, 8 consecutive lanes write the 128 contiguous bytes of a row -----
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int piece = j * 512 + tid;
+        const int row_l = piece >> 3, ch = (piece & 7) * 16;
+        if (n0 + ch < p.Kp) {                  // (Kp is a multiple of 64: whole pieces)
+            const long o = (long)(m0 + row_l) * p.Kp + n0 + ch;
+            const v4i w1 = *reinterpret_cast<const v4i*>(o1 + row_l * MLP_OROW + ch);
+            __builtin_nontemporal_store(w1, reinterpret_cast<v4i*>(p.P1 + o));
+            if (TWIN) {
+                const v4i w2 = *reinterpret_cast<const v4i*>(o2 + row_l * MLP_OROW + ch);
+                __builtin_nontemporal_store(w2, reinterpret_cast<v4i*>(p.P2 + o));
+            }
+        }
+    }
+}
+template <bool TWIN>
+__global__ __launch_bounds__(512) void k_mlp_fc1(MlpFc1Params p) { k_mlp_fc1_body<TWIN>(p, P4V_BIDX, P4V_GDIM); }
+
 }  // namespace p4v

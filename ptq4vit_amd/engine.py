@@ -235,6 +235,51 @@ def linear_quant_forward(*, weight, bias, x, w_interval, a_interval, w_bit, a_bi
     return out
 
 
+def _mlp_layer_desc(batch, tokens, layer):
+    w = layer["weight"]
+    return _lib.LinearDesc(batch, tokens, w.shape[1], w.shape[0], layer["n_V"], layer.get("n_H", 1), layer.get("n_a", 1),
+                           layer["w_bit"], layer["a_bit"], metric_id("L2_norm"), 1, 1, int(bool(layer.get("postgelu", False))), 0,
+                           int(layer.get("bias") is not None), 4)
+
+
+def mlp_quant_forward(*, x, fc1, fc2, want_hidden=False, want_planes=False):
+    """fc2(GELU(fc1(x))) of two calibrated Linear layers in quant_forward, fused (p4v_mlp_quant_forward): fc1's int8 GEMM ends
+    in the exact GELU and fc2's activation quantiser and writes fc2's int8 plane(s); no fp32 hidden tensor in between.
+    `fc1` / `fc2`: dicts with weight, bias (or None), w_interval, a_interval (fc2: the positive range), w_bit, a_bit, n_V and
+    optionally n_H, n_a, postgelu (fc2: the post-GELU twin).  Returns out, or (out, hidden) with `want_hidden` -- the fp32 GELU
+    output the planes were quantised from --, with `want_planes` also the padded int8 plane(s) as the call left them in its
+    workspace (a tuple of one or two [rows_padded][cols_padded] tensors; for the tests)."""
+    lib = _lib.load()
+    dev = device_of(x, fc1["weight"])
+    x = to_dev(x, dev).contiguous()
+    batch, K = x.shape[0], x.shape[-1]
+    tokens = x.numel() // (batch * K)
+    t = {}
+    for name, layer in (("fc1", fc1), ("fc2", fc2)):
+        t[name] = (to_dev(layer["weight"], dev).contiguous(), to_dev(layer.get("bias"), dev),
+                   to_dev(layer["w_interval"], dev).reshape(-1).contiguous(), to_dev(layer["a_interval"], dev).reshape(-1).contiguous())
+    d = _lib.MlpDesc(_mlp_layer_desc(batch, tokens, fc1), _mlp_layer_desc(batch, tokens, fc2))
+    need = _need(lib.p4v_mlp_workspace_bytes, d, "p4v_mlp_workspace_bytes")
+    ws = workspace(dev, need)
+    hidden_n, out_n = fc1["weight"].shape[0], fc2["weight"].shape[0]
+    out = torch.empty(x.shape[:-1] + (out_n,), dtype=torch.float32, device=dev)
+    hidden = torch.empty(x.shape[:-1] + (hidden_n,), dtype=torch.float32, device=dev) if want_hidden else None
+    (w1, b1, w1_iv, a1_iv), (w2, b2, w2_iv, a2_iv) = t["fc1"], t["fc2"]
+    with torch.cuda.device(dev):
+        rc = lib.p4v_mlp_quant_forward(C.byref(d), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(x), ptr(w1_iv), ptr(a1_iv), ptr(w2_iv),
+                                       ptr(a2_iv), ptr(out), ptr(hidden), ptr(ws), ws.numel(), stream_ptr(dev))
+    _lib.check(rc, "p4v_mlp_quant_forward")
+    res = (out, hidden) if want_hidden else out
+    if want_planes:
+        info = (C.c_uint64 * 5)()
+        _lib.check(lib.p4v_debug_mlp_planes(info), "p4v_debug_mlp_planes")
+        off1, off2, rows, cols, twin = (int(v) for v in info)
+        take = lambda off: ws[off:off + rows * cols].view(torch.int8).reshape(rows, cols).clone()
+        planes = (take(off1), take(off2)) if twin else (take(off1),)
+        res = (res if isinstance(res, tuple) else (res,)) + (planes,)
+    return res
+
+
 def matmul_quant_forward(*, A, B, A_interval, B_interval, split, A_bit, B_bit, sos=False):
     """quant_forward of a calibrated MatMul (head-wise intervals; optional split-of-softmax twin on A)."""
     lib = _lib.load()

@@ -1,0 +1,385 @@
+"""GPU: the fused int8 MLP forward (p4v_mlp_quant_forward, engine.mlp_quant_forward, utils/fuse.py).
+
+fc1's int8 GEMM ends in the exact GELU and fc2's activation quantiser and writes fc2's int8 row plane(s); fc2 is the unfused
+forward sweep on those planes.  What is held here, per case, on a poisoned workspace of exactly the size asked for:
+
+1. quantiser and layout: the planes the call left are, byte for byte and padding included, what k_pack_dual (twin) / the
+   single-plane packer (plain fc2) makes of the call's OWN fp32 hidden tensor; padding rows are zero;
+2. fc2 from planes: `out` is fc2.quant_forward(hidden), bit for bit;
+3. GELU: hidden against torch's gelu(fc1.quant_forward(x)) in fp32 ulps -- expected 0 (both sides call ROCm's erff), asserted
+   <= 32 (twice the 16-ulp bound OpenCL C gives erf, which both implementations are built to);
+4. against the unfused chain: a plane byte may differ from the unfused one by one grid step only, and only where the unfused
+   t = g / s lies within (U + 1) * 2^-23 * max(|t|, 1) of a half-integer (U: the ulp distance measured in 3);
+5. the contract: exact workspace, one byte less refused with no launch, n_a = 2 / n_H = 2 refused with no launch, null hidden;
+6. module level on the mini ViT: fuse_mlp's names, logits fused vs unfused, raw / hooked states fall back bit-identically, a
+   second calibration of the fused net gives the unfused net's intervals, unfuse_mlp restores.
+
+Shapes (the smallest that reach every edge): 2 x 197 = 394 rows (three full 128-row tiles and a ragged one), in_features 96
+(one and a half k-tiles), hidden 200 (ragged against the 128 tile and Kp = 256; with fc1 n_V = 2 the block edge at 100 falls
+inside a wave's 32 columns) and 256, out_features 72.
+
+With P4V_FUSED_MLP_OUT set the measured margins are written there (profiles/r20_fused_mlp_margins.json).
+"""
+import copy
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests.workspace_guard import Guard
+
+pytestmark = pytest.mark.gpu
+
+ROWS, K_IN, N_OUT = (2, 197), 96, 72
+ULP_BAR = 32
+_MARGINS = {}
+
+#          id                 twin  bits nV hidden bias
+CASES = [("twin_w8a8",        True,  8, 1, 200, True),
+         ("twin_w6a6",        True,  6, 1, 200, True),
+         ("plain_w8a8",       False, 8, 1, 200, True),
+         ("twin_w8a8_nV2",    True,  8, 2, 200, True),
+         ("plain_w6a6_nV2",   False, 6, 2, 200, True),
+         ("twin_w8a8_nobias", True,  8, 1, 200, False),
+         ("twin_w8a8_h256",   True,  8, 2, 256, True)]
+IDS = [c[0] for c in CASES]
+
+
+@pytest.fixture(scope="module")
+def eng():
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    from ptq4vit_amd import engine
+    yield engine
+    engine.release_workspace()
+    path = os.environ.get("P4V_FUSED_MLP_OUT")
+    if _MARGINS and path:
+        path = os.path.abspath(path)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        old = {}
+        if os.path.exists(path):
+            with open(path) as fh:
+                old = json.load(fh)
+        old.update(_MARGINS)
+        with open(path, "w") as fh:
+            json.dump(old, fh, indent=1, sort_keys=True)
+            fh.write("\n")
+
+
+def _modules(case):
+    """fc1 / fc2 of one case, calibrated by a real calibration_step2 on seeded normal data; and the input."""
+    from ptq4vit_amd.quant_layers.linear import PostGeluPTQSLBatchingQuantLinear, PTQSLBatchingQuantLinear
+    name, twin, bits, nV, hidden, bias = case
+    torch.manual_seed(1000 + IDS.index(name))
+    kw = dict(w_bit=bits, a_bit=bits, metric="L2_norm", search_round=2, eq_alpha=0.01, eq_beta=1.2, eq_n=40, n_V=nV, n_H=1, n_a=1)
+    fc1 = PTQSLBatchingQuantLinear(K_IN, hidden, bias=bias, **kw).cuda()
+    fc2 = (PostGeluPTQSLBatchingQuantLinear if twin else PTQSLBatchingQuantLinear)(hidden, N_OUT, bias=bias, **kw).cuda()
+    x = torch.randn(*ROWS, K_IN, device="cuda")
+    with torch.no_grad():
+        for fc, inp in ((fc1, x), (fc2, F.gelu(F.linear(x, fc1.weight, fc1.bias)))):
+            fc.raw_input, fc.raw_out, fc.raw_grad = inp, F.linear(inp, fc.weight, fc.bias), None
+            fc.calibration_step2()
+            fc.mode = "quant_forward"
+    return fc1, fc2, x
+
+
+def _ordered(t):
+    i = t.contiguous().view(torch.int32).to(torch.int64)
+    return torch.where(i < 0, -(i & 0x7FFFFFFF), i)
+
+
+def ulp_distance(a, b):
+    return (_ordered(a) - _ordered(b)).abs()
+
+
+_RUNS = {}
+
+
+def run_case(eng, monkeypatch, case):
+    """One fused call per case (exact, guarded, poisoned workspace) and the unfused chain next to it; shared by the tests."""
+    name = case[0]
+    if name in _RUNS:
+        return _RUNS[name]
+    from ptq4vit_amd.utils.fuse import _layer
+    fc1, fc2, x = _modules(case)
+    with torch.no_grad():
+        with Guard(eng, monkeypatch, 0xCD) as g:
+            out, hidden, planes = eng.mlp_quant_forward(x=x, fc1=_layer(fc1), fc2=_layer(fc2), want_hidden=True, want_planes=True)
+            reps = g.finish()
+        assert len(reps) == 1 and reps[0]["guard_changed"] == 0 and 0 < reps[0]["touched"] <= reps[0]["need"], reps
+        v_ref = fc1.quant_forward(x)
+        h_ref = F.gelu(v_ref)
+        out_ref = fc2.quant_forward(h_ref)
+    r = dict(fc1=fc1, fc2=fc2, x=x, out=out, hidden=hidden, planes=planes, h_ref=h_ref, out_ref=out_ref, need=reps[0]["need"])
+    _RUNS[name] = r
+    return r
+
+
+def _unfused_planes(eng, case, fc2, h):
+    """fc2's row plane(s) as the unfused forward packs them from the fp32 tensor `h`: (padded planes [M][Kp])."""
+    twin = case[1]
+    h2 = h.reshape(-1, h.shape[-1])
+    q = fc2.a_qmax
+    a_iv = fc2._positive_a_interval().reshape(-1)
+    if twin:
+        _, _, p1, p2 = eng.debug_pack_dual(h2, sos=False, scale=float(a_iv[0]), lo=-q, hi=q - 1, qmax=q, const_scale=fc2.a_neg_interval)
+        return p1, p2
+    _, p1 = eng.pack_plane_i8(h2, mode="sym", scales=a_iv, rows_per_scale=h2.shape[0], lo=-q, hi=q - 1)
+    return (p1,)
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_planes_are_the_packers_bytes_of_the_calls_own_hidden(eng, monkeypatch, case):
+    r = run_case(eng, monkeypatch, case)
+    M, hidden = r["x"].shape[0] * r["x"].shape[1], case[4]
+    want = _unfused_planes(eng, case, r["fc2"], r["hidden"])
+    assert len(want) == len(r["planes"]) == (2 if case[1] else 1)
+    for got, ref in zip(r["planes"], want):
+        assert got.shape[0] % 128 == 0 and got.shape[0] >= M and got.shape[1] == ref.shape[1] == (hidden + 63) // 64 * 64
+        assert torch.equal(got[:M], ref), f"{case[0]}: {(got[:M] != ref).sum().item()} bytes differ from the packer's"
+        assert not got[M:].any(), "padding rows must be zero"
+        assert not got[:, hidden:].any(), "padding columns must be zero"
+    assert r["planes"][0].any()
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_out_is_fc2_quant_forward_of_the_calls_own_hidden(eng, monkeypatch, case):
+    r = run_case(eng, monkeypatch, case)
+    with torch.no_grad():
+        want = r["fc2"].quant_forward(r["hidden"])
+    assert r["out"].shape == want.shape == (*ROWS, N_OUT)
+    assert torch.equal(r["out"], want), f"{case[0]}: max |diff| {(r['out'] - want).abs().max().item():.3e}"
+
+
+def _measured_ulps(r):
+    return int(ulp_distance(r["hidden"], r["h_ref"]).max())
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_gelu_matches_torch_on_fc1_quant_forward(eng, monkeypatch, case):
+    r = run_case(eng, monkeypatch, case)
+    assert torch.isfinite(r["hidden"]).all()
+    U = _measured_ulps(r)
+    print(f"[fused mlp] {case[0]}: hidden vs torch gelu(fc1.quant_forward(x)): max {U} ulp")
+    _MARGINS.setdefault("gelu_max_ulp", {})[case[0]] = U
+    assert U <= ULP_BAR, f"{case[0]}: {U} ulp"
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_planes_against_the_unfused_chain(eng, monkeypatch, case):
+    r = run_case(eng, monkeypatch, case)
+    U = _measured_ulps(r)
+    fc2 = r["fc2"]
+    M = r["x"].shape[0] * r["x"].shape[1]
+    hidden = case[4]
+    scales = [float(fc2._positive_a_interval().reshape(-1)[0])] + ([float(np.float32(fc2.a_neg_interval))] if case[1] else [])
+    h = r["h_ref"].reshape(M, hidden).double()
+    flips = 0
+    for got, ref, s in zip(r["planes"], _unfused_planes(eng, case, fc2, r["h_ref"]), scales):
+        a, b = got[:M, :hidden].to(torch.int32), ref[:, :hidden].to(torch.int32)
+        diff = a != b
+        if diff.any():
+            t = h / s
+            near = ((t - torch.floor(t) - 0.5).abs() <= (U + 1) * 2.0 ** -23 * t.abs().clamp(min=1.0))
+            assert ((a - b).abs()[diff] == 1).all(), f"{case[0]}: a byte differs by more than one grid step"
+            assert near[diff].all(), f"{case[0]}: {(diff & ~near).sum().item()} bytes differ away from a rounding tie"
+        flips += int(diff.sum())
+    print(f"[fused mlp] {case[0]}: {flips} plane bytes differ from the unfused chain's (U = {U})")
+    _MARGINS.setdefault("plane_bytes_differing_from_unfused", {})[case[0]] = flips
+    with torch.no_grad():
+        rel = ((r["out"] - r["out_ref"]).norm() / r["out_ref"].norm()).item()
+    _MARGINS.setdefault("out_rel_diff_vs_unfused", {})[case[0]] = rel
+    if flips == 0:
+        assert torch.equal(r["out"], r["out_ref"])
+
+
+# ---- 5: the contract ------------------------------------------------------------------------------------------------------------
+def test_workspace_contract_and_envelope(eng, monkeypatch):
+    from ptq4vit_amd.utils.fuse import _layer
+    case = CASES[0]
+    r = run_case(eng, monkeypatch, case)          # (the exact, guarded, poisoned call)
+    fc1, fc2, x = r["fc1"], r["fc2"], r["x"]
+    torch.cuda.synchronize()
+    with torch.no_grad():
+        # one byte less: refused, nothing launched
+        before = eng.launch_counters()
+        with Guard(eng, monkeypatch, 0xCD, declare=lambda n: n - 1) as g:
+            with pytest.raises(RuntimeError, match="workspace too small"):
+                eng.mlp_quant_forward(x=x, fc1=_layer(fc1), fc2=_layer(fc2))
+            reps = g.finish()
+        assert eng.launch_counters() == before
+        assert all(rep["touched"] == 0 and rep["guard_changed"] == 0 for rep in reps), reps
+        # outside the envelope: refused before any launch
+        for key in ("n_a", "n_H"):
+            for which in (0, 1):
+                layers = [_layer(fc1), _layer(fc2)]
+                layers[which][key] = 2
+                with pytest.raises(NotImplementedError, match="n_H = n_a = 1"):
+                    eng.mlp_quant_forward(x=x, fc1=layers[0], fc2=layers[1])
+        assert eng.launch_counters() == before
+        # no hidden tensor asked for: the same out
+        out = eng.mlp_quant_forward(x=x, fc1=_layer(fc1), fc2=_layer(fc2))
+        assert torch.equal(out, r["out"])
+        assert eng.launch_counters()["asked"] > before["asked"]
+
+
+# ---- 6: module level, the mini ViT -----------------------------------------------------------------------------------------------
+class _Loader:
+    def __init__(self, images):
+        self.images, self.batch_size = images, images.shape[0]
+
+    def __iter__(self):
+        yield self.images, torch.zeros(self.images.shape[0], dtype=torch.long)
+
+
+def _wrapped_of(net, names):
+    mods = dict(net.named_modules())
+    return {n: mods[n] for n in names}
+
+
+def _intervals(wrapped):
+    out = {}
+    for n, m in wrapped.items():
+        for a in ("w_interval", "a_interval", "A_interval", "B_interval", "split"):
+            v = getattr(m, a, None)
+            if v is not None:
+                out[f"{n}.{a}"] = torch.as_tensor(v).detach().cpu().clone()
+    return out
+
+
+@pytest.fixture(scope="module")
+def mini():
+    from ptq4vit_amd.configs import PTQ4ViT
+    from ptq4vit_amd.utils import models, net_wrap
+    from ptq4vit_amd.utils.quant_calib import HessianQuantCalibrator
+    g = np.load("tests/golden/minivit_ptq4vit.npz", allow_pickle=False)
+    kw = json.loads(str(g["model_kwargs"]))
+    assert kw["img_size"] == 32
+    net = models.get_net("vit_tiny_patch16_224", seed=0, device="cuda", **kw)
+    assert isinstance(net, models.VisionTransformer)
+    wrapped = net_wrap.wrap_modules_in_net(net, PTQ4ViT)
+    images = torch.from_numpy(g["images"][:4]).cuda()
+    HessianQuantCalibrator(net, wrapped, _Loader(images), sequential=False, batch_size=4).batching_quant_calib()
+    return net, wrapped, images
+
+
+def _count_fused_calls(eng, monkeypatch):
+    calls = []
+    orig = eng.mlp_quant_forward
+
+    def counted(**kw):
+        calls.append(1)
+        return orig(**kw)
+    monkeypatch.setattr(eng, "mlp_quant_forward", counted)
+    return calls
+
+
+def test_fused_net_logits_and_fallbacks(eng, mini, monkeypatch):
+    from ptq4vit_amd.utils import fuse, models
+    net, wrapped, images = mini
+    mlps = [n for n, m in net.named_modules() if isinstance(m, models.Mlp)]
+    assert len(mlps) == 2
+    calls = _count_fused_calls(eng, monkeypatch)
+    cls_forward = models.Mlp.forward
+    try:
+        with torch.no_grad():
+            y_u = net(images)
+            assert not calls
+            assert fuse.fuse_mlp(net) == mlps
+            assert fuse.fuse_mlp(net) == mlps                      # idempotent
+            y_f = net(images)
+            assert len(calls) == len(mlps), "the fused path did not run"
+            for m in wrapped.values():
+                m.mode = "raw"
+            y_raw = net(images)
+            assert len(calls) == len(mlps), "raw mode must take the original forward"
+            for m in wrapped.values():
+                m.mode = "quant_forward"
+            assert torch.equal(y_f.argmax(-1), y_u.argmax(-1))
+            ratio = ((y_f - y_u).norm() / (y_u - y_raw).norm()).item()
+            print(f"[fused mlp] mini ViT: |fused - unfused| / |unfused - raw| = {ratio:.3e}")
+            _MARGINS["minivit_fused_over_quant_error"] = ratio
+            assert ratio <= 1e-2
+
+            mods = dict(net.named_modules())
+            probe = torch.randn(4, 17, mods[mlps[0]].fc1.in_features, device="cuda")
+
+            def unfused_twin(fn):
+                """fn() on the fused net, then on the same net unfused, in whatever state it is in"""
+                a = fn()
+                fuse.unfuse_mlp(net)
+                b = fn()
+                fuse.fuse_mlp(net)
+                return a, b
+
+            # one fc2 in raw mode: that MLP takes the original forward -- the net and the MLP itself as on the unfused net
+            mods[mlps[0]].fc2.mode = "raw"
+            del calls[:]
+            y_a, y_b = unfused_twin(lambda: net(images))
+            assert len(calls) == len(mlps) - 1
+            assert torch.equal(y_a, y_b)
+            del calls[:]
+            m_a, m_b = unfused_twin(lambda: mods[mlps[0]](probe))
+            assert not calls and torch.equal(m_a, m_b)
+            mods[mlps[0]].fc2.mode = "quant_forward"
+
+            # a forward hook on fc1: it fires, that MLP takes the original forward, the output is the unfused net's
+            fired = []
+            h = mods[mlps[0]].fc1.register_forward_hook(lambda mod, inp, out: fired.append(tuple(out.shape)))
+            del calls[:]
+            y_a, y_b = unfused_twin(lambda: net(images))
+            assert len(fired) == 2 and len(calls) == len(mlps) - 1
+            assert torch.equal(y_a, y_b)
+            del calls[:]
+            m_a, m_b = unfused_twin(lambda: mods[mlps[0]](probe))
+            assert not calls and torch.equal(m_a, m_b)
+            h.remove()
+            # ... a pre-hook on the activation likewise
+            h = mods[mlps[1]].act.register_forward_pre_hook(lambda mod, inp: fired.append("act"))
+            del calls[:]
+            m_a, m_b = unfused_twin(lambda: mods[mlps[1]](probe))
+            assert not calls and fired[-1] == "act" and torch.equal(m_a, m_b)
+            h.remove()
+            # autograd recording: the original forward
+            del calls[:]
+            with torch.enable_grad():
+                mods[mlps[0]](probe.clone().requires_grad_(True))
+            assert not calls
+            # everything back: fused again, and deterministic
+            del calls[:]
+            assert torch.equal(net(images), y_f) and len(calls) == len(mlps)
+    finally:
+        fuse.unfuse_mlp(net)
+    # unfuse_mlp restores the original forward
+    for n in mlps:
+        m = dict(net.named_modules())[n]
+        assert "forward" not in m.__dict__ and m.forward.__func__ is cls_forward
+    assert fuse.unfuse_mlp(net) == []
+    with torch.no_grad():
+        del calls[:]
+        assert torch.equal(net(images), y_u) and not calls
+
+
+def test_second_calibration_of_a_fused_net_gives_the_unfused_intervals(eng, mini, monkeypatch):
+    from ptq4vit_amd.utils import fuse
+    from ptq4vit_amd.utils.quant_calib import HessianQuantCalibrator
+    net, wrapped, images = mini
+    fuse.unfuse_mlp(net)
+    net_u = copy.deepcopy(net)
+    wrapped_u = _wrapped_of(net_u, wrapped)
+    net_f = copy.deepcopy(net)
+    wrapped_f = _wrapped_of(net_f, wrapped)
+    assert len(fuse.fuse_mlp(net_f)) == 2
+    HessianQuantCalibrator(net_u, wrapped_u, _Loader(images), sequential=False, batch_size=4).batching_quant_calib()
+    HessianQuantCalibrator(net_f, wrapped_f, _Loader(images), sequential=False, batch_size=4).batching_quant_calib()
+    iu, ifu = _intervals(wrapped_u), _intervals(wrapped_f)
+    assert iu.keys() == ifu.keys() and len(iu) >= len(wrapped)
+    for k in iu:
+        assert torch.equal(iu[k], ifu[k]), k
+    # ... and the fused net is still fused, and runs fused
+    calls = _count_fused_calls(eng, monkeypatch)
+    with torch.no_grad():
+        net_f(images)
+    assert len(calls) == 2

@@ -3,17 +3,25 @@
 reference, example/test_vit.py:26-45) next to the raw fp32 forward.
 
     python tools/bench_forward.py --model vit_base_patch16_224 --batch 128
+    python tools/bench_forward.py --model vit_base_patch16_224 --batch 128 --fused --json profiles/forward.json
+
+--fused: the same network with its MLPs fused (utils/fuse.py::fuse_mlp) next to the unfused one, alternating in one process,
+medians over --reps repetitions each, and the per-kernel device time of one forward of each kind: the engine's launch records
+for the GEMMs (k_mlp_fc1, the fc2 sweep), torch's profiler for everything (k_pack*, torch's GELU).
 """
 import argparse
+import json
 import os
+import statistics
 import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
+from ptq4vit_amd import _lib, engine  # noqa: E402
 from ptq4vit_amd.configs import PTQ4ViT  # noqa: E402
-from ptq4vit_amd.utils import models, net_wrap  # noqa: E402
+from ptq4vit_amd.utils import fuse, models, net_wrap  # noqa: E402
 from ptq4vit_amd.utils.quant_calib import HessianQuantCalibrator  # noqa: E402
 
 
@@ -25,11 +33,61 @@ class Loader:
         yield self.x, torch.zeros(self.x.shape[0], dtype=torch.long, device=self.x.device)
 
 
+def engine_records(net, x):
+    """{kernel: [launches, ms]} of the engine's timed launches (the GEMMs) in one forward."""
+    engine.stats_enable(True)
+    engine.stats_reset()
+    with torch.no_grad():
+        net(x)
+    torch.cuda.synchronize()
+    engine.stats_get()                   # (drains the event pairs into the records)
+    out = {}
+    for r in engine.stats_launches():
+        e = out.setdefault(r["kernel"], [0, 0.0])
+        e[0] += 1
+        e[1] += r["ms"]
+    engine.stats_enable(False)
+    engine.stats_reset()
+    return out
+
+
+def profiler_kernels(net, x):
+    """{kernel name: [launches, ms]} of every GPU kernel of one forward (torch.profiler); None where it is not available."""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            with torch.no_grad():
+                net(x)
+            torch.cuda.synchronize()
+        out = {}
+        for ev in prof.events():
+            dt = getattr(ev, "device_time", None)
+            if dt is None:
+                dt = getattr(ev, "cuda_time", 0.0)
+            if str(getattr(ev, "device_type", "")).endswith("CUDA") and dt:
+                e = out.setdefault(ev.name, [0, 0.0])
+                e[0] += 1
+                e[1] += dt / 1e3
+        return out or None
+    except Exception as exc:      # noqa: BLE001 -- a measurement aid: the timing above does not depend on it
+        print(f"[bench_forward] torch.profiler not usable here: {exc}", file=sys.stderr)
+        return None
+
+
+def short(tab, keep=14):
+    if tab is None:
+        return None
+    rows = sorted(tab.items(), key=lambda kv: -kv[1][1])[:keep]
+    return [{"kernel": k[:120], "launches": n, "ms": round(ms, 4)} for k, (n, ms) in rows]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="vit_base_patch16_224")
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--fused", action="store_true", help="also time the network with fused MLPs (utils/fuse.py), alternating")
+    ap.add_argument("--json", default=None, help="write the result to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     net = models.get_net(a.model, seed=0, device=dev)
@@ -40,23 +98,62 @@ def main():
     HessianQuantCalibrator(net, wrapped, Loader(calib), sequential=False, batch_size=4).batching_quant_calib()
     x = torch.randn(a.batch, 3, img, img, generator=g).to(dev)
 
-    def timed(mode):
-        for m in wrapped.values():
-            m.mode = mode
+    def once():
+        torch.cuda.synchronize()
+        t = time.time()
         with torch.no_grad():
             y = net(x)
-            torch.cuda.synchronize()
-            t = time.time()
-            for _ in range(a.reps):
-                y = net(x)
-            torch.cuda.synchronize()
-        return (time.time() - t) / a.reps, y
+        torch.cuda.synchronize()
+        return time.time() - t, y
 
-    t_raw, y_raw = timed("raw")
-    t_q, y_q = timed("quant_forward")
+    def timed(mode, reps):
+        for m in wrapped.values():
+            m.mode = mode
+        once()
+        ts = []
+        for _ in range(reps):
+            t, y = once()
+            ts.append(t)
+        return statistics.median(ts), y
+
+    t_raw, y_raw = timed("raw", a.reps)
+    t_q, y_q = timed("quant_forward", a.reps)
     print(f"{a.model} batch {a.batch}: raw fp32 {a.batch / t_raw:.0f} img/s ({t_raw * 1e3:.1f} ms), "
           f"quant_forward {a.batch / t_q:.0f} img/s ({t_q * 1e3:.1f} ms); "
           f"logit rel diff {((y_q - y_raw).norm() / y_raw.norm()).item():.3e}")
+    res = {"model": a.model, "batch": a.batch, "reps": a.reps, "source_hash": _lib.source_hash(),
+           "raw_fp32_ms": t_raw * 1e3, "quant_forward_ms": t_q * 1e3, "quant_vs_fp32": t_raw / t_q}
+    if a.fused:
+        # fused and unfused alternating, repetition by repetition, after one warm-up of each
+        ts = {False: [], True: []}
+        ys = {}
+        for rep in range(a.reps + 1):
+            for on in (False, True):
+                fuse.fuse_mlp(net) if on else fuse.unfuse_mlp(net)
+                t, ys[on] = once()
+                if rep:
+                    ts[on].append(t)
+        fused_names = fuse.fuse_mlp(net)
+        t_u, t_f = statistics.median(ts[False]), statistics.median(ts[True])
+        rel = ((ys[True] - ys[False]).norm() / ys[False].norm()).item()
+        print(f"  unfused {t_u * 1e3:.2f} ms, fused MLPs ({len(fused_names)}) {t_f * 1e3:.2f} ms: x{t_u / t_f:.3f}; "
+              f"fused vs fp32 x{t_raw / t_f:.2f}; logit rel diff fused vs unfused {rel:.3e}")
+        res.update({"fused_mlps": len(fused_names), "unfused_ms": t_u * 1e3, "fused_ms": t_f * 1e3, "unfused_over_fused": t_u / t_f,
+                    "fused_vs_fp32": t_raw / t_f, "unfused_ms_all": [t * 1e3 for t in ts[False]], "fused_ms_all": [t * 1e3 for t in ts[True]],
+                    "logit_rel_diff_fused_vs_unfused": rel})
+        kern = {}
+        for on in (False, True):
+            fuse.fuse_mlp(net) if on else fuse.unfuse_mlp(net)
+            key = "fused" if on else "unfused"
+            kern[key] = {"engine_records": short(engine_records(net, x)), "profiler": short(profiler_kernels(net, x))}
+            for row in kern[key]["profiler"] or kern[key]["engine_records"]:
+                print(f"  [{key}] {row['ms']:9.3f} ms  {row['launches']:4d} x  {row['kernel'][:90]}")
+        res["kernels_per_forward"] = kern
+        fuse.unfuse_mlp(net)
+    if a.json:
+        with open(a.json, "w") as fh:
+            json.dump(res, fh, indent=1)
+            fh.write("\n")
 
 
 if __name__ == "__main__":
