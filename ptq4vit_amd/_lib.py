@@ -90,6 +90,16 @@ class GroupJob(C.Structure):
 
 
 JOB_LINEAR, JOB_MATMUL, JOB_CONV, JOB_MATMUL_BLOCKS = 0, 1, 2, 3
+# bits of a descriptor's `reserved` word (include/ptq4vit_hip.h documents which descriptor reads which)
+RESERVED_FP32_PLANES, RESERVED_NO_MEMO, RESERVED_FORWARD_ONLY, RESERVED_NO_PRUNE = 1, 2, 4, 8
+RESERVED_BLOCK_SHIFT = 8     # bits 8..11 (p4v_linear_search_w / _a): 1 + b runs the step of block b alone
+
+
+def reserved_block(block):
+    """The block field of `reserved`: 0 (every block in turn) for None, else 1 + block."""
+    return 0 if block is None else (int(block) + 1) << RESERVED_BLOCK_SHIFT
+
+
 PLANE_SYM, PLANE_SOS_HI, PLANE_SOS_LO, PLANE_TWIN = 1, 2, 3, 4
 EXPORT_SYM_I8, EXPORT_SYM_F32, EXPORT_GELU_U8, EXPORT_SOS_U8 = 0, 1, 2, 3
 

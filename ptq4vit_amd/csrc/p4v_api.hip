@@ -173,6 +173,11 @@ struct Ctx {
     Group* grp = nullptr;     // p4v_calibrate_group: this call is member `slot` of a group whose stream operations are deferred and
     int slot = 0;             // issued together (grouped launches); nullptr: every operation goes to `st` at once
     int par = 1;              // members of the group that search in lock step: the launch heuristics plan for 256 / par CUs
+    // a real call on the caller's stream and workspace / the dry run of the planner behind *_workspace_bytes: it carves nothing,
+    // launches nothing and counts; every tensor of its record is null
+    static Ctx on(void* stream, void* workspace, size_t bytes) { return Ctx{(hipStream_t)stream, Arena(workspace, bytes), false}; }
+    static Ctx sizing() { return Ctx{nullptr, Arena(nullptr, 0), true}; }
+    size_t sized_bytes() const { return ws.peak + 4096; }     // what a sizing run reports
 };
 
 // ---- stream operations: issued at once (one module) or deferred and grouped (p4v_calibrate_group) -------------------------------
@@ -978,9 +983,9 @@ struct Operand {
     PackParams pk;        // src/strides/sizes/scales/mode filled by the caller (dst, C, Rp, Kp set by run_pass)
     bool expanded;        // true: one plane per candidate
     bool present;
-    const void* plane;    // row / row2 of a forward pass only: the operand is PREPACKED -- this is its fixed int8 plane, row-major
-                          // [pl.Mp][pl.Kp] as plan_sweep sizes it, written by an earlier launch on the stream (mlp_impl: fc1's
-                          // epilogue); nothing is allocated or packed for it.  nullptr (everything else): packed from pk.src
+    bool prepacked;       // row / row2 of a forward pass only: `plane` is the operand's fixed int8 plane, row-major [pl.Mp][pl.Kp] as
+    const void* plane;    // plan_sweep sizes it, written by an earlier launch on the stream (mlp_impl: fc1's epilogue); nothing is
+                          // allocated or packed for it (a sizing run: no address yet).  false (everything else): packed from pk.src
 };
 
 // A MatMul pass with row / column sub-blocks (n_V, n_H > 1; matmul_impl): the K axis cut where either operand's scale changes
@@ -1025,7 +1030,9 @@ struct Pass {
     float* aux_out; float aux_div;
     float* scores_out; int scores_out_ld;
     int32_t* best_out;
-    float* store_out;         // EPI_STORE pass: one "candidate", writes raw_out - bias - scale*acc, no finish/select
+    float* store_out;         // where a storing pass writes (the address only: null in a sizing run)
+    // EPI_STORE (raw_out - bias - scale*acc) / EPI_FWD (the quantised product): one "candidate", stored, no finish / select
+    bool stores() const { return epi == EPI_STORE || epi == EPI_FWD; }
     bool cos6;                // cosine of a plain Linear layer on k_sweep6 (rows = samples, cols = features, Z = 1): set by linear_impl
     bool cos7;                // ... on k_sweep7 (K >= 1024)
     bool twin_disjoint;       // twin whose two ranges never overlap (post-GELU): k_sweep7 may stream them as one merged plane
@@ -1264,18 +1271,18 @@ int plan_sweep(const Ctx& c, const Pass& ps, SweepPlan& pl) {
     const bool blocks64 = (ps.s_cs == 1 || ps.sb_div % 64 == 0) && (ps.j_mode == 0 || (ps.j_mode == 1 && (ps.nj == 1 || ps.j_div % 64 == 0)));
     // -- the family, in the order of the table in DESIGN.md s5 --
     // k_bound, stage B1 (one candidate over all samples): rows = samples, columns = features of a plain [M][N] layer
-    const bool bound = ps.bound_kernel && i8v2 && !ps.twin && ps.Z == 1 && !ps.store_out && !cosm && plain_out && ps.bias_axis == 0 &&
+    const bool bound = ps.bound_kernel && i8v2 && !ps.twin && ps.Z == 1 && !ps.stores() && !cosm && plain_out && ps.bias_axis == 0 &&
                        (ps.sb_mode == 0 || ps.sb_mode == 1) && score32 && scale32 && (ps.eq_n == 1 || ps.crange);
     // k_sweep6 / k_sweep5, stationary operand: Linear layers whose invariant operand tile (128 x K int8) fits in LDS; in registers
     // (k_sweep6) for the K that sweep6_supported lists
-    const bool stat_ok = !bound && !ps.store_out && i8v2 && !ps.twin && (!cosm || ps.cos6) && !(g_variant & 4) && ps.Z == 1 &&
+    const bool stat_ok = !bound && !ps.stores() && i8v2 && !ps.twin && (!cosm || ps.cos6) && !(g_variant & 4) && ps.Z == 1 &&
                          ps.sb_mode == 1 && blocks64 && one_expanded && K64 <= 768 && plain_out;
     const bool regs6 = stat_ok && sweep6_supported(ktiles);
     if (ps.cos6 && !regs6) return fail(P4V_ERR_UNSUPPORTED, "cosine pass planned for k_sweep6 does not qualify for it");
     // k_sweep7 (large K): rows = samples, columns = output features of a plain [M][N] layer; features contiguous in
     // raw_out / raw_grad and a multiple of 32 (dwordx4 epilogue loads, whole 32-feature blocks), every 32-feature block
     // inside one scale / score block, exactly one operand candidate-expanded, the twin's second plane not expanded
-    const bool big7 = !bound && !stat_ok && !ps.store_out && i8v2 && (!cosm || ps.cos7) && !(g_variant & 32768) && ps.Z == 1 &&
+    const bool big7 = !bound && !stat_ok && !ps.stores() && i8v2 && (!cosm || ps.cos7) && !(g_variant & 32768) && ps.Z == 1 &&
                       K64 >= 1024 && K64 % 256 == 0 && (long)ps.Mrows * ps.o_ms * 4 < (1L << 32) && ps.sb_mode == 1 && scale32 && score32 &&
                       one_expanded && !(ps.twin && (ps.row.expanded || ps.row2.expanded)) &&
                       plain_out && ps.o_ns == 1 && ps.Ncols % 32 == 0 && ps.o_ms % 4 == 0 &&
@@ -1283,7 +1290,7 @@ int plan_sweep(const Ctx& c, const Pass& ps, SweepPlan& pl) {
     if (ps.cos7 && (!big7 || ps.twin)) return fail(P4V_ERR_UNSUPPORTED, "cosine pass planned for k_sweep7 does not qualify for it");
     // the fast tiled sweeps (k_sweep2 and its kin); tuning 12 = 7 keeps the cosine on the generic kernel
     const bool fast = !stat_ok && i8v2 && !cosm && scale32 && (score32 || ps.j_mode == 2);
-    pl.fast_cos = cosm && !stat_ok && !big7 && i8v2 && !ps.store_out && tune(TUNE_B1_PATH) != 7 && scale32;
+    pl.fast_cos = cosm && !stat_ok && !big7 && i8v2 && !ps.stores() && tune(TUNE_B1_PATH) != 7 && scale32;
     pl.pairs = stat_ok && !regs6;
     pl.merged7 = big7 && ps.twin && ps.twin_disjoint && !(g_variant & 2097152);   // (variant 2097152 keeps the two-plane kernel)
     pl.kind = bound ? SK_BOUND : regs6 ? SK_SWEEP6 : stat_ok ? SK_SWEEP5 :
@@ -1295,7 +1302,7 @@ int plan_sweep(const Ctx& c, const Pass& ps, SweepPlan& pl) {
     // tuning 12 = 9 switches them off (A/B)
     const bool blk_ranges = ps.crange && ps.crange_blk && tune(TUNE_B1_PATH) != 9;
     pl.rblk = (blk_ranges && regs6 && !ps.row.expanded && ps.j_mode == 1 && ps.nj == ps.s_cs && ps.j_div == ps.sb_div) ? ps.crange_blk : nullptr;
-    pl.rblk_z = (blk_ranges && !stat_ok && ps.j_mode == 2 && ps.nj == ps.j_div && ps.Z > 1 && !cosm && !ps.store_out && !bound && K64 < 1024)
+    pl.rblk_z = (blk_ranges && !stat_ok && ps.j_mode == 2 && ps.nj == ps.j_div && ps.Z > 1 && !cosm && !ps.stores() && !bound && K64 < 1024)
                     ? ps.crange_blk : nullptr;
     // -- operands and planes --
     // k_sweep6 tiles the stationary operand (the one that is NOT candidate-expanded) in 256-row slabs
@@ -1303,7 +1310,7 @@ int plan_sweep(const Ctx& c, const Pass& ps, SweepPlan& pl) {
     const int Np = pl.Np = (int)rup(ps.Ncols, big7 ? 256 : (regs6 && !ps.col.expanded) ? 256 : SW_BM);
     // rows of the column operand's plane: the tile-padded count, except for the 64-column operands of the batched k_sweep2 passes
     // (attn.v: B = V, N = head_dim = 64): k_sweep2 re-reads rows 0..63 for the tile's upper half
-    pl.b64 = fast && !big7 && !bound && ps.Z > 1 && !ps.col_zs_shared && ps.Ncols <= 64 && ktiles >= 2 && ktiles <= 15 && !ps.store_out;
+    pl.b64 = fast && !big7 && !bound && ps.Z > 1 && !ps.col_zs_shared && ps.Ncols <= 64 && ktiles >= 2 && ktiles <= 15 && !ps.stores();
     pl.NpB = pl.b64 ? 64 : Np;
     pl.row_plane1 = (long)(ps.row_zs_shared ? 1 : ps.Z) * Mp * Kp * esz;
     pl.col_plane1 = (long)(ps.col_zs_shared ? 1 : ps.Z) * pl.NpB * Kp * esz;
@@ -1342,7 +1349,7 @@ int plan_sweep(const Ctx& c, const Pass& ps, SweepPlan& pl) {
     pl.p_cs = pl.part_cs = pl.p_zs * ps.Z;
     // k_sweep9 (before k_sweep8 in the order of the families) writes [C][Z][halves * SW9_NW] into the table allocated for the
     // 128-tile layout, where that holds it
-    if (fast && !bound && !big7 && !ps.store_out && (ps.j_mode == 0 || ps.j_mode == 2)) {
+    if (fast && !bound && !big7 && !ps.stores() && (ps.j_mode == 0 || ps.j_mode == 2)) {
         const int h9 = sweep9_halves(ps, ktiles);
         if (h9 > 0 && (long)h9 * SW9_NW <= pl.p_zs) { pl.kind = SK_SWEEP9; pl.h9 = h9; pl.p_zs = (long)h9 * SW9_NW; pl.p_cs = pl.p_zs * ps.Z; }
     }
@@ -1379,7 +1386,7 @@ struct PassBufs {
 int pass_workspace(Ctx& c, const Pass& ps, const SweepPlan& pl, PassBufs& b) {
     // (planes above PLANE_CACHE_MAX are re-packed every pass: with three search streams and two searched operands per
     // module the cache would otherwise add up to 6 x PLANE_BUDGET of workspace on the 128-image configurations)
-    PlaneCache* pc = b.pc = (ps.cache && pl.chunk >= ps.eq_n && !ps.store_out && ps.row.expanded != ps.col.expanded &&
+    PlaneCache* pc = b.pc = (ps.cache && pl.chunk >= ps.eq_n && !ps.stores() && ps.row.expanded != ps.col.expanded &&
                              !(ps.twin && ps.row2.expanded) && pl.exp_plane * (long)ps.eq_n <= PLANE_CACHE_MAX) ? ps.cache : nullptr;
     if (pc && !pc->assigned) {
         pc->buf = c.ws.get_top((size_t)pl.exp_plane * pl.chunk_al + pl.slack);
@@ -1387,9 +1394,9 @@ int pass_workspace(Ctx& c, const Pass& ps, const SweepPlan& pl, PassBufs& b) {
         pc->assigned = true; pc->valid = false;
         if (!c.dry && pc->done) CHK(q_fill(c, pc->done, 0, (size_t)ps.eq_n));
     }
-    b.row = ps.row.plane ? (char*)ps.row.plane :
+    b.row = ps.row.prepacked ? (char*)ps.row.plane :
             (pc && ps.row.expanded) ? pc->buf : c.ws.get<char>((size_t)pl.row_plane1 * (ps.row.expanded ? pl.chunk_al : 1) + pl.slack);
-    b.row2 = !ps.twin ? nullptr : ps.row2.plane ? (char*)ps.row2.plane : c.ws.get<char>((size_t)pl.row_plane1 * (ps.row2.expanded ? pl.chunk : 1));
+    b.row2 = !ps.twin ? nullptr : ps.row2.prepacked ? (char*)ps.row2.plane : c.ws.get<char>((size_t)pl.row_plane1 * (ps.row2.expanded ? pl.chunk : 1));
     b.col = (pc && ps.col.expanded) ? pc->buf : c.ws.get<char>((size_t)pl.col_plane1 * (ps.col.expanded ? pl.chunk_al : 1) + pl.slack);
     b.part = c.ws.get<float>((size_t)pl.part_cs * ps.eq_n);
     b.S1 = !ps.use_s1 ? nullptr : ps.S1_pre ? ps.S1_pre : c.ws.get<float>((size_t)ps.eq_n * ps.s_cs);
@@ -1469,9 +1476,9 @@ int prep_epilogue(Ctx& c, const Pass& ps, const SweepPlan& pl, const PassBufs& b
 
 // the planes that do not depend on the candidate, once
 int pack_fixed_planes(Ctx& c, const Pass& ps, const SweepPlan& pl, const PassBufs& b) {
-    if (ps.row.plane) {
+    if (ps.row.prepacked) {
         // prepacked row operand (the fused MLP forward): its plane(s) are on the stream already
-        if (ps.row.expanded || pl.merged7 || pl.cin_fix != 0 || (ps.twin && (!ps.row2.plane || ps.row2.expanded)))
+        if (ps.row.expanded || pl.merged7 || pl.cin_fix != 0 || (ps.twin && (!ps.row2.prepacked || ps.row2.expanded)))
             return fail(P4V_ERR_INVALID, "prepacked row operand: fixed row-major plane(s) of a forward pass only");
     } else if (pl.merged7) {
         Operand both = ps.row;              // positive range: scale + upper clamp; negative range: fixed scale + lower clamp
@@ -1668,7 +1675,7 @@ int sweep_chunk_tiled(Ctx& c, const Pass& ps, const SweepPlan& pl, const PassBuf
         default:    // (the k_sweep2 model, whichever of its kin runs)
             cgroups = choose_cgroups(wgs, nc, sp.ktiles, cu_slots(c, ps.twin ? 256 : 512, SWEEP_RECORD_KIND[SK_SWEEP2]), ps.twin ? 40.0 : 25.0, ps.twin ? 0.45 : 0.40);
     }
-    const bool tuned = kind != SK_GENERIC_I8 && kind != SK_GENERIC_F32 && !pl.fast_cos && !ps.store_out;
+    const bool tuned = kind != SK_GENERIC_I8 && kind != SK_GENERIC_F32 && !pl.fast_cos && !ps.stores();
     if (tuned) {
         const char* g = kind == SK_SWEEP2G ? "g" : "";
         if (const int t_ = tune(kind == SK_SWEEP2G ? TUNE_CG2G : TUNE_CG2); t_ > 0) cgroups = std::max(1, std::min(nc, t_));
@@ -1727,7 +1734,7 @@ int run_pass(Ctx& c, Pass& ps) {
         else CHK(sweep_chunk_tiled(c, ps, pl, b, kind, c0, nc));
     }
     g_exec_frac = 1.0;
-    if (!ps.store_out) {
+    if (!ps.stores()) {
         CHK(finish_pass(c, ps, pl, b));
         if (!ps.no_select) CHK(launch_pass_select(c, ps, b.scores));
     }
@@ -1857,7 +1864,7 @@ struct PrunePlan {
 // The only place that decides whether a pass is staged and with what geometry (DESIGN.md s5.1 lists the tests in this order).
 // Allocates nothing; reads the module's slice cache for what earlier passes of the module found out.
 PruneOutcome plan_prune(const Ctx& c, const Pass& ps, PrunePlan& pl) {
-    if (!ps.prunable || !(ps.i8 || ps.prunable_f32) || ps.epi == EPI_COS || ps.store_out || ps.scores_out || ps.best_out || ps.crange || ps.no_select) return PRUNE_NOT_ELIGIBLE;
+    if (!ps.prunable || !(ps.i8 || ps.prunable_f32) || ps.epi == EPI_COS || ps.stores() || ps.scores_out || ps.best_out || ps.crange || ps.no_select) return PRUNE_NOT_ELIGIBLE;
     if (prune_switched_off() || ps.eq_n < 32 || ps.nj < 1 || ps.nj > 4096) return PRUNE_NOT_ELIGIBLE;
     // geometry of the slice.  Linear: the k heaviest of its M samples (rows of x / raw_out / raw_grad).  MatMul: the 16
     // heaviest rows (queries) of EVERY batch entry (image, head) -- the column operand stays whole.  Measured on ViT-B/224 x 32
@@ -1947,7 +1954,7 @@ int cross_checked(Ctx& c, const float* interval, int n, const char* what, Pruned
 // quantiser and the output scales), K <= 256, N <= 208, no bias, a difference metric.
 bool slice_b_ok(const Pass& a) {
     const PackParams& b = a.col.pk;
-    return a.i8 && a.col.expanded && !a.row.expanded && !(a.twin && a.row2.expanded) && a.Z > 1 && a.Mrows <= 16 && !a.store_out &&
+    return a.i8 && a.col.expanded && !a.row.expanded && !(a.twin && a.row2.expanded) && a.Z > 1 && a.Mrows <= 16 && !a.stores() &&
            a.epi != EPI_COS && a.epi != EPI_STORE && a.epi != EPI_FWD && !a.bias && a.use_s1 && a.sb_mode == 2 && a.j_mode == 2 &&
            a.sb_div == a.j_div && a.s_cs == a.sb_div && !a.crange && a.scores_keep && a.no_select &&
            !b.conv && b.mode == PACK_SYM && b.blk_mode == 2 && b.blk_div == a.sb_div && b.scales && !a.col_zs_shared && !a.row_zs_shared &&
@@ -2017,7 +2024,7 @@ int run_slice_b(Ctx& c, Pass& a, float* SA) {
 // ... and of a pruned MatMul A search with K <= 64 (k_slice_a: the slice is quantised per candidate in registers, B fixed)
 bool slice_a_ok(const Pass& a) {
     const PackParams& r = a.row.pk;
-    return a.i8 && a.row.expanded && !a.col.expanded && !a.twin && a.Z > 1 && a.Mrows <= 16 && !a.store_out &&
+    return a.i8 && a.row.expanded && !a.col.expanded && !a.twin && a.Z > 1 && a.Mrows <= 16 && !a.stores() &&
            a.epi != EPI_COS && a.epi != EPI_STORE && a.epi != EPI_FWD && !a.bias && a.use_s1 && a.sb_mode == 2 && a.j_mode == 2 &&
            a.sb_div == a.j_div && a.s_cs == a.sb_div && !a.crange && a.scores_keep && a.no_select &&
            !r.conv && r.mode == PACK_SYM && r.blk_mode == 2 && r.blk_div == a.sb_div && r.scales && r.s_k == 1 && r.s_r == a.K &&
@@ -2579,18 +2586,29 @@ struct MirrorScope {
     MirrorScope& operator=(const MirrorScope&) = delete;
 };
 
-// Which parts of calibration_step2 one call runs.  The fused entry points run everything (ST_ALL: initialisation, then
+// The mode of one *_impl call.  The fused entry points run all of calibration_step2 (ST_ALL: initialisation, then
 // search_round x {first operand, second operand} with memoisation); the granular entry points of the C ABI
 // (p4v_amax_init_*, p4v_*_search_*) run ONE part with the candidate table supplied by the caller, the way the reference's
-// _initialize_intervals / _search_best_*_interval methods are called one by one (linear.py:380-397,455-533).
-enum { ST_INIT = 1, ST_S1 = 2, ST_S2 = 4, ST_ALL = 7 };
+// _initialize_intervals / _search_best_*_interval methods are called one by one (linear.py:380-397,455-533); ST_FWD is
+// quant_forward: the intervals are INPUTS, nothing is initialised or searched.  A sizing run (Ctx::dry) has the mode of the
+// call it sizes; what a mode reads of the call's tensor record is checked for presence in real calls only.
+enum { ST_INIT = 1, ST_S1 = 2, ST_S2 = 4, ST_ALL = 7, ST_FWD = 8 };
 struct Stage {
     int mask = ST_ALL;
     const float* cands1 = nullptr;   // caller's candidate table of the first operand  (w / A), used when ST_INIT is not set
     const float* cands2 = nullptr;   // ... of the second operand (a / B)
     bool full() const { return mask == ST_ALL; }
     bool searches() const { return (mask & (ST_S1 | ST_S2)) != 0; }
+    bool forward() const { return mask == ST_FWD; }
+    bool inits() const { return (mask & ST_INIT) != 0; }
 };
+
+// Bits of a descriptor's `reserved` word (include/ptq4vit_hip.h documents which descriptor reads which): the generic fp32-operand
+// path of a Linear, no pass memo, *_workspace_bytes sizes for *_quant_forward alone (the sizing run's mode is ST_FWD), no exact
+// candidate pruning; bits 8..11 (p4v_linear_search_w / _a): 1 + b runs the step of block b alone; -1: every block in turn
+enum : int { RSV_FP32_PLANES = 1, RSV_NO_MEMO = 2, RSV_FORWARD_ONLY = 4, RSV_NO_PRUNE = 8 };
+inline int reserved_block(int reserved) { return ((reserved >> 8) & 15) - 1; }
+inline Stage sizing_stage(int reserved) { return (reserved & RSV_FORWARD_ONLY) ? Stage{ST_FWD} : Stage{}; }
 
 // What the round loop of a *_impl call derives from its Stage, its descriptor and the caller's tables.
 struct SearchRounds {
@@ -2603,9 +2621,9 @@ struct SearchRounds {
     float* scores = nullptr;
     int32_t* best = nullptr;
     SearchRounds() {}
-    SearchRounds(const Stage& sg, int search_round, int reserved, int eq_n_, int ld_, const Ctx& c, float* scores_out, int32_t* best_out,
+    SearchRounds(const Stage& sg, int search_round, bool memo_allowed, int eq_n_, int ld_, const Ctx& c, float* scores_out, int32_t* best_out,
                  int per_round_ = 2)
-        : memo_on(sg.full() && !c.dry && !scores_out && !best_out && !(reserved & 2)), keep_planes(sg.full() && search_round > 1),
+        : memo_on(sg.full() && !c.dry && !scores_out && !best_out && memo_allowed), keep_planes(sg.full() && search_round > 1),
           n_rounds(sg.full() ? search_round : 1), full(sg.full()), per_round(per_round_), eq_n(eq_n_), ld(ld_), scores(scores_out),
           best(best_out) {}
     long slot(int round, int which) const { return full ? (long)round * per_round + which : 0; }
@@ -2648,11 +2666,22 @@ int seg_cut_k(SegPlan& g, const char* who) {
 // ------------------------------------------------------------------------------------------------
 // Linear
 // ------------------------------------------------------------------------------------------------
+// The device pointers of one linear_impl call, filled by name at the entry points; what the call's mode (Stage) does not read
+// stays null, and a sizing run leaves all of them null.
+struct LinearTensors {
+    const float *W = nullptr, *bias = nullptr, *X = nullptr;    // weight [N][K], bias [N] (null: none), x [M][K]
+    const float *O = nullptr, *G = nullptr;                     // raw_out / raw_grad [M][N] (searches; G: the hessian metric)
+    const float* mult = nullptr;                                // [eq_n + 1] candidate multipliers (ST_INIT with a search)
+    float *w_iv = nullptr, *a_iv = nullptr;                     // intervals [n_V][n_H] / [n_a]: out, in / out, or -- ST_FWD -- in
+    float* scores = nullptr; int32_t* best = nullptr;           // optional score tables / selections
+    float* fwd_out = nullptr;                                   // ST_FWD: the destination [M][N]
+};
 // One linear_impl call: what build() derives from the descriptor, and the builders of its passes.  Sides: 0 = the weight search
 // (reference linear.py:455-495), 1 = the activation search (linear.py:497-533 / 609-642).
 struct LinearCall {
     Ctx& c;
     const p4v_linear_desc* d;
+    const LinearTensors t;
     const Stage& sg;
     int M = 0, K = 0, N = 0;                          // samples (batch x tokens), in_features, out_features
     int nV = 1, nH = 1, nA = 1;                       // row / column blocks of the weights, column blocks of the activations
@@ -2669,9 +2698,6 @@ struct LinearCall {
     bool cos6 = false, cos7 = false;                  // cosine in the orientation of the difference metrics, on k_sweep6 / k_sweep7
     int only_blk = -1;                                // granular call, desc.reserved bits 8..11 = 1 + b: the step of block b alone; else -1
     int tab_blk = 0;                                  // the block whose score table and selections the call returns
-    const float *W = nullptr, *bias = nullptr, *X = nullptr, *O = nullptr, *G = nullptr, *mult = nullptr;
-    float *w_iv = nullptr, *a_iv = nullptr;           // intervals [n_V][n_H] / [n_a]
-    float* fwd_out = nullptr;                         // quant_forward (linear.py:62-67 / 601-607): the intervals are INPUTS, nothing is searched
     unsigned *enc_w = nullptr, *enc_a = nullptr;      // abs-max per block, order-preserving encoding
     float *w_cands_ws = nullptr, *a_cands_ws = nullptr;       // candidate tables built by this call ...
     const float *w_cands = nullptr, *a_cands = nullptr;       // ... or the caller's (granular search)
@@ -2684,12 +2710,10 @@ struct LinearCall {
     EpiCache ecache[2];                               // per side: k_sweep6's epilogue operands in fragment order
     SliceCache slice, slice2;                         // the sample slices of the pruned passes (two tiers)
 
-    LinearCall(Ctx& c_, const p4v_linear_desc* d_, const Stage& sg_) : c(c_), d(d_), sg(sg_) {}
+    LinearCall(Ctx& c_, const p4v_linear_desc* d_, const LinearTensors& t_, const Stage& sg_) : c(c_), d(d_), t(t_), sg(sg_) {}
 
     // argument checks, geometry, the path decisions, the workspace
-    int build(const float* W_, const float* bias_, const float* X_, const float* O_, const float* G_, const float* mult_, float* w_iv_,
-              float* a_iv_, float* scores_out, int32_t* best_out, float* fwd_out_) {
-        W = W_; bias = bias_; X = X_; O = O_; G = G_; mult = mult_; w_iv = w_iv_; a_iv = a_iv_; fwd_out = fwd_out_;
+    int build() {
         M = d->batch * d->tokens; K = d->in_features; N = d->out_features;
         nV = d->n_V; nH = d->n_H; nA = d->n_a;
         if (M <= 0 || K <= 0 || N <= 0 || nV <= 0 || nH <= 0 || nA <= 0 || d->eq_n <= 0)
@@ -2701,14 +2725,14 @@ struct LinearCall {
         a_neg = (float)(0.16997124254703522 / aq);   // linear.py:574
         metric_epi(d->metric, &epi, &wt_mode);
         cosm = epi == EPI_COS;
-        if (wt_mode == 1 && !G && !fwd_out && sg.searches()) return fail(P4V_ERR_INVALID, "linear: hessian metric needs raw_grad (linear.py:418)");
-        general = (nH > 1 || nA > 1 || (d->reserved & 1) || (cosm && d->twin_postgelu && !fwd_out));
+        if (wt_mode == 1 && !t.G && sg.searches() && !c.dry) return fail(P4V_ERR_INVALID, "linear: hessian metric needs raw_grad (linear.py:418)");
+        general = (nH > 1 || nA > 1 || (d->reserved & RSV_FP32_PLANES) || (cosm && d->twin_postgelu && !sg.forward()));
         i8 = !general;
         twin = d->twin_postgelu && i8;
         // Cosine with column / activation blocks (linear.py:455-533): the K-segmented int8 sweep, transposed -- A := W as n_V heads of
         // crb_rows x K with intervals w_iv[v][h], B := x as K x samples shared by the heads with intervals a_iv[a]; K cut at the
         // multiples of crb_cols and crb_acts.  One block step per pass (run_pass_seg), every other block on the interval entering it.
-        segcos = cosm && !fwd_out && (nH > 1 || nA > 1);
+        segcos = cosm && !sg.forward() && (nH > 1 || nA > 1);
         if (segcos && d->twin_postgelu)
             return fail(P4V_ERR_UNSUPPORTED, "linear: cosine with n_H>1 / n_a>1 on the post-GELU twin is not implemented on the GPU "
                                              "(the twin's second plane lies on the column side, k_sweep_seg has no instance for that)");
@@ -2717,13 +2741,13 @@ struct LinearCall {
             sgp.batch = 1; sgp.H = nV; sgp.M = crb_rows; sgp.K = K; sgp.N = M;
             sgp.nVA = 1; sgp.nHA = nH; sgp.nVB = nA; sgp.nHB = 1;
             sgp.crA = crb_rows; sgp.ccA = crb_cols; sgp.crB = crb_acts; sgp.ccB = M;
-            sgp.A = W; sgp.a_st[0] = 0; sgp.a_st[1] = (long)crb_rows * K; sgp.a_st[2] = K; sgp.a_st[3] = 1;
-            sgp.B = X; sgp.b_st[0] = 0; sgp.b_st[1] = 0; sgp.b_st[2] = 1; sgp.b_st[3] = K; sgp.b_shared = true;
-            sgp.Aq = wq; sgp.Bq = aq; sgp.ivA = w_iv; sgp.ivB = a_iv;
+            sgp.A = t.W; sgp.a_st[0] = 0; sgp.a_st[1] = (long)crb_rows * K; sgp.a_st[2] = K; sgp.a_st[3] = 1;
+            sgp.B = t.X; sgp.b_st[0] = 0; sgp.b_st[1] = 0; sgp.b_st[2] = 1; sgp.b_st[3] = K; sgp.b_shared = true;
+            sgp.Aq = wq; sgp.Bq = aq; sgp.ivA = t.w_iv; sgp.ivB = t.a_iv;
             CHK(seg_cut_k(sgp, "linear"));
         }
-        rounds = SearchRounds(sg, d->search_round, d->reserved, d->eq_n, nV, c, scores_out, best_out);
-        only_blk = sg.full() ? -1 : ((d->reserved >> 8) & 15) - 1;
+        rounds = SearchRounds(sg, d->search_round, !(d->reserved & RSV_NO_MEMO), d->eq_n, nV, c, t.scores, t.best);
+        only_blk = sg.full() ? -1 : reserved_block(d->reserved);
         if (sg.searches() && only_blk >= ((sg.mask & ST_S1) ? nH : nA)) return fail(P4V_ERR_INVALID, "linear: block %d outside the layer's blocks", only_blk);
         tab_blk = std::max(0, only_blk);
         // Cosine on k_sweep6: the layer as ONE GEMM in the orientation of the difference metrics (rows = samples, columns =
@@ -2735,15 +2759,15 @@ struct LinearCall {
         // ... and on k_sweep7 for K >= 1024 (fc2): 128-feature slabs; the conditions are run_pass's for that kernel
         cos7 = cosm && i8 && !twin && !general && nH == 1 && nA == 1 && (nV == 1 || crb_rows % 128 == 0) && !cos6 &&
                rup(K, 64) >= 1024 && rup(K, 64) % 256 == 0 && N % 32 == 0 && (long)M * N * 4 < (1L << 32) &&
-               (c.dry || (((unsigned long long)O) & 15) == 0) && !(g_variant & (2048 | 32768)) && !g_force_v1;
+               (c.dry || (((unsigned long long)t.O) & 15) == 0) && !(g_variant & (2048 | 32768)) && !g_force_v1;
         ncand = d->eq_n + 1;
         cvt_bias(c);     // (first call of the process: probe the conversion quant16_sat8 relies on)
         enc_w = c.ws.get<unsigned>((size_t)nV * nH);
         enc_a = c.ws.get<unsigned>((size_t)nA);
         w_cands_ws = c.ws.get<float>((size_t)ncand * nV * nH);
         a_cands_ws = c.ws.get<float>((size_t)ncand * nA);
-        w_cands = (sg.mask & ST_INIT) ? w_cands_ws : sg.cands1;
-        a_cands = (sg.mask & ST_INIT) ? a_cands_ws : sg.cands2;
+        w_cands = sg.inits() ? w_cands_ws : sg.cands1;
+        a_cands = sg.inits() ? a_cands_ws : sg.cands2;
         Ufold = twin ? c.ws.get<float>((size_t)M * N) : nullptr;
         w_mix = c.ws.get<float>((size_t)ncand * nV * nH);
         a_mix = c.ws.get<float>((size_t)ncand * nA);
@@ -2754,16 +2778,16 @@ struct LinearCall {
 
     // interval initialisation of one side (linear.py:380-397 / 576-599): abs-max per block, the interval, its candidate table
     int init_side(int side) {
-        if (fwd_out || !(sg.mask & ST_INIT)) return 0;
+        if (!sg.inits()) return 0;
         const long stw[4] = {0, 0, K, 1};
         if (side == 0) {
-            CHK(launch_absmax(c, W, stw, 1, 1, N, K, nV, nH, crb_rows, crb_cols, 0, enc_w));
-            CHK(launch_interval(c, enc_w, nV * nH, (float)(wq - 0.5), d->init_layerwise, w_iv));
-            if (sg.searches()) CHK(launch_cands(c, mult, w_iv, ncand, nV * nH, w_cands_ws));
+            CHK(launch_absmax(c, t.W, stw, 1, 1, N, K, nV, nH, crb_rows, crb_cols, 0, enc_w));
+            CHK(launch_interval(c, enc_w, nV * nH, (float)(wq - 0.5), d->init_layerwise, t.w_iv));
+            if (sg.searches()) CHK(launch_cands(c, t.mult, t.w_iv, ncand, nV * nH, w_cands_ws));
         } else {
-            CHK(launch_absmax(c, X, stw, 1, 1, M, K, 1, nA, M, crb_acts, d->twin_postgelu ? 1 : 0, enc_a));
-            CHK(launch_interval(c, enc_a, nA, (float)(aq - 0.5), d->init_layerwise, a_iv));
-            if (sg.searches()) CHK(launch_cands(c, mult, a_iv, ncand, nA, a_cands_ws));
+            CHK(launch_absmax(c, t.X, stw, 1, 1, M, K, 1, nA, M, crb_acts, d->twin_postgelu ? 1 : 0, enc_a));
+            CHK(launch_interval(c, enc_a, nA, (float)(aq - 0.5), d->init_layerwise, t.a_iv));
+            if (sg.searches()) CHK(launch_cands(c, t.mult, t.a_iv, ncand, nA, a_cands_ws));
         }
         return 0;
     }
@@ -2771,7 +2795,7 @@ struct LinearCall {
     Operand x_operand(bool expanded, const float* scales, int sc_cs) const {
         Operand op{};
         op.present = true; op.expanded = expanded;
-        op.pk = pack2d(X, M, K, K);
+        op.pk = pack2d(t.X, M, K, K);
         op.pk.scales = scales; op.pk.sc_cs = sc_cs;
         op.pk.lo = -aq; op.pk.hi = aq - 1;
         if (nA > 1) { op.pk.blk_mode = 1; op.pk.blk_div = INT_MAX; op.pk.nblk_r = 1; op.pk.nblk_k = nA; op.pk.blk_div2 = crb_acts; }
@@ -2784,7 +2808,7 @@ struct LinearCall {
     Operand xneg_operand() const {
         Operand op{};
         op.present = true; op.expanded = false;
-        op.pk = pack2d(X, M, K, K);
+        op.pk = pack2d(t.X, M, K, K);
         op.pk.scales = nullptr; op.pk.neg_scale = a_neg; op.pk.lo = -aq; op.pk.hi = 0;
         return op;
     }
@@ -2792,12 +2816,12 @@ struct LinearCall {
         Operand op{};
         op.present = true; op.expanded = expanded;
         if (by_vblock) {   // swapped cosine sweep: one GEMM per V block
-            op.pk = pack2d(W, crb_rows, K, K);
+            op.pk = pack2d(t.W, crb_rows, K, K);
             op.pk.s_z = (long)crb_rows * K;
             op.pk.blk_mode = 2; op.pk.blk_div = nV;
             if (nH > 1) return op;  // unreachable: general path is not swapped per block
         } else {
-            op.pk = pack2d(W, N, K, K);
+            op.pk = pack2d(t.W, N, K, K);
             op.pk.blk_mode = 1; op.pk.blk_div = crb_rows; op.pk.nblk_r = nV; op.pk.nblk_k = nH;
             op.pk.blk_div2 = nH > 1 ? crb_cols : 0;
         }
@@ -2812,15 +2836,15 @@ struct LinearCall {
         Pass fp{};
         fp.i8 = i8; fp.twin = twin; fp.epi = EPI_FWD; fp.wt_mode = 0; fp.eq_n = 1; fp.K = K;
         fp.Z = 1; fp.Mrows = M; fp.Ncols = N;
-        fp.row = x_operand(false, a_iv, 0);
+        fp.row = x_operand(false, t.a_iv, 0);
         if (twin) fp.row2 = xneg_operand();
-        fp.col = w_operand(false, w_iv, 0, false);
+        fp.col = w_operand(false, t.w_iv, 0, false);
         fp.use_s1 = i8; fp.s_cs = nV; fp.sb_mode = 1; fp.sb_div = crb_rows;
-        fp.s1 = ScaleParams{a_iv, 0, 0, 0.f, w_iv, 0, 1, 0.f, 0, 0, nullptr};
-        fp.s2 = ScaleParams{nullptr, 0, 0, a_neg, w_iv, 0, 1, 0.f, 0, 0, nullptr};
-        fp.bias = bias; fp.bias_axis = 0; fp.bias_zs = 0;
-        fp.O = fwd_out; fp.G = nullptr; fp.o_ms = N; fp.o_ns = 1; fp.o_inner = INT_MAX;
-        fp.nj = 1; fp.store_out = fwd_out;
+        fp.s1 = ScaleParams{t.a_iv, 0, 0, 0.f, t.w_iv, 0, 1, 0.f, 0, 0, nullptr};
+        fp.s2 = ScaleParams{nullptr, 0, 0, a_neg, t.w_iv, 0, 1, 0.f, 0, 0, nullptr};
+        fp.bias = t.bias; fp.bias_axis = 0; fp.bias_zs = 0;
+        fp.O = t.fwd_out; fp.G = nullptr; fp.o_ms = N; fp.o_ns = 1; fp.o_inner = INT_MAX;
+        fp.nj = 1; fp.store_out = t.fwd_out;
         return fp;
     }
 
@@ -2829,7 +2853,7 @@ struct LinearCall {
     void selection(Pass& ps, int side, int round, int blk) const {
         const bool ws = side == 0;
         ps.nj = ws ? nV : 1; ps.cands = ws ? w_cands : a_cands; ps.cand_cs = ws ? nV * nH : nA; ps.cand_js = ws ? nH : 0; ps.cand_off = blk;
-        ps.interval = ws ? w_iv : a_iv; ps.out_js = ws ? nH : 0; ps.out_off = blk;
+        ps.interval = ws ? t.w_iv : t.a_iv; ps.out_js = ws ? nH : 0; ps.out_off = blk;
         if (blk == tab_blk) { ps.scores_out = rounds.scores_of(round, side); ps.best_out = rounds.best_of(round, side); }
         ps.scores_out_ld = nV;
     }
@@ -2844,23 +2868,23 @@ struct LinearCall {
         ps.ecache = rounds.keep_planes ? &ecache[side] : nullptr;
         selection(ps, side, round, blk);
         const bool dense = !cosm || cos6 || cos7;
-        const Operand xo = ws ? x_operand(false, a_iv, 0) : x_operand(true, cands, cs);
-        const Operand wo = ws ? w_operand(true, cands, cs, !dense) : w_operand(false, w_iv, 0, !dense);
-        ps.s1 = ws ? ScaleParams{a_iv, 0, 0, 0.f, w_cands, nV, 1, 0.f, 0, 0, nullptr} : ScaleParams{a_cands, 1, 0, 0.f, w_iv, 0, 1, 0.f, 0, 0, nullptr};
+        const Operand xo = ws ? x_operand(false, t.a_iv, 0) : x_operand(true, cands, cs);
+        const Operand wo = ws ? w_operand(true, cands, cs, !dense) : w_operand(false, t.w_iv, 0, !dense);
+        ps.s1 = ws ? ScaleParams{t.a_iv, 0, 0, 0.f, w_cands, nV, 1, 0.f, 0, 0, nullptr} : ScaleParams{a_cands, 1, 0, 0.f, t.w_iv, 0, 1, 0.f, 0, 0, nullptr};
         ps.use_s1 = i8; ps.s_cs = nV;
-        ps.bias = bias; ps.O = O; ps.o_inner = INT_MAX;
+        ps.bias = t.bias; ps.O = t.O; ps.o_inner = INT_MAX;
         if (dense) {
             // rows = samples, columns = features
             ps.Z = 1; ps.Mrows = M; ps.Ncols = N;
             ps.row = xo; ps.col = wo;
             if (twin) { ps.row2 = xneg_operand(); ps.twin_disjoint = ws; }    // linear.py:605-606: clamp(.,0,q-1) / clamp(.,-q,0)
             ps.sb_mode = 1; ps.sb_div = crb_rows;
-            ps.s2 = ScaleParams{nullptr, 0, 0, a_neg, ws ? w_cands : w_iv, ws ? nV : 0, 1, 0.f, 0, 0, nullptr};
+            ps.s2 = ScaleParams{nullptr, 0, 0, a_neg, ws ? w_cands : t.w_iv, ws ? nV : 0, 1, 0.f, 0, 0, nullptr};
             ps.bias_axis = 0; ps.bias_zs = 0;
-            ps.G = G; ps.o_zs = 0; ps.o_bs = 0; ps.o_ms = N; ps.o_ns = 1;
+            ps.G = t.G; ps.o_zs = 0; ps.o_bs = 0; ps.o_ms = N; ps.o_ns = 1;
             ps.j_mode = ws ? 1 : 0; ps.j_div = ws ? crb_rows : 0;
             ps.norm = 1.0 / ((double)d->tokens * (ws ? crb_rows : N));
-            ps.prunable = !(d->reserved & 8); ps.scache = &slice; ps.scache2 = &slice2; ps.host_sync_ok = host_sync_ok;
+            ps.prunable = !(d->reserved & RSV_NO_PRUNE); ps.scache = &slice; ps.scache2 = &slice2; ps.host_sync_ok = host_sync_ok;
             if (cos6 || cos7) {
                 ps.cos6 = cos6; ps.cos7 = cos7; ps.G = nullptr; ps.wt_mode = 0; ps.prunable = false; ps.scache = nullptr; ps.scache2 = nullptr;
                 ps.cos_ZB = 1; ps.cos_ZV = nV; ps.cos_j_mode = ws ? 1 : 0;
@@ -2889,7 +2913,7 @@ struct LinearCall {
         Pass ps{};
         ps.seg = &sgp; ps.i8 = true; ps.epi = EPI_COS; ps.eq_n = d->eq_n; ps.K = K;
         ps.Z = nV; ps.Mrows = crb_rows; ps.Ncols = M;
-        ps.bias = bias; ps.bias_axis = 1; ps.bias_zs = crb_rows;
+        ps.bias = t.bias; ps.bias_axis = 1; ps.bias_zs = crb_rows;
         ps.O = Ot;
         ps.cos_ZB = 1; ps.cos_ZV = nV; ps.cos_j_mode = ws ? 1 : 0;
         ps.norm = 1.0 / (double)d->tokens;
@@ -2906,7 +2930,7 @@ struct LinearCall {
         const float* cands = ws ? w_cands : a_cands;
         float* mix = ws ? w_mix : a_mix;
         ScaleParams mp{};
-        mp.x = ws ? w_iv : a_iv; mp.x_cs = 0; mp.x_js = 1; mp.y = nullptr; mp.y_const = 1.0f; mp.C = ncand; mp.nblk = n; mp.S = mix;
+        mp.x = ws ? t.w_iv : t.a_iv; mp.x_cs = 0; mp.x_js = 1; mp.y = nullptr; mp.y_const = 1.0f; mp.C = ncand; mp.nblk = n; mp.S = mix;
         mp.copy = 1;                      // (the fp32 packers divide by these themselves: a zero interval stays 0, its plane is 0 / 0)
         CHK(launch_scale(c, mp));
         for (int v = 0; v < rows; ++v)
@@ -2922,7 +2946,7 @@ struct LinearCall {
         fp.twin = false; fp.epi = EPI_STORE; fp.wt_mode = 0; fp.eq_n = 1;
         fp.row = xneg_operand(); fp.row2 = Operand{};
         fp.s1 = ps.s2;
-        fp.store_out = Ufold; fp.cache = nullptr;
+        fp.store_out = Ufold; fp.cache = nullptr;      // (EPI_STORE: planned as a storing pass in the sizing run too, where Ufold is null)
         fp.scores_out = nullptr; fp.best_out = nullptr;
         CHK(run_pass(c, fp));
         ps.twin = false; ps.row2 = Operand{};
@@ -2944,7 +2968,7 @@ struct LinearCall {
     int search_side(int side, int round, MemoSide& memo, HostCopy* host) {
         const bool ws = side == 0;
         const int nblk = ws ? nH : nA;
-        const DevVecs key = ws ? DevVecs(a_iv, nA) : DevVecs(w_iv, nV * nH), val = ws ? DevVecs(w_iv, nV * nH) : DevVecs(a_iv, nA);
+        const DevVecs key = ws ? DevVecs(t.a_iv, nA) : DevVecs(t.w_iv, nV * nH), val = ws ? DevVecs(t.w_iv, nV * nH) : DevVecs(t.a_iv, nA);
         bool hit = false;
         CHK(memo.restore(c, key, &host[1 - side], val, &host[side], &hit));      // (key: just read back / written by the last pass)
         for (int blk = 0; blk < nblk && !hit && (sg.mask & (ws ? ST_S1 : ST_S2)); ++blk) {
@@ -2960,22 +2984,20 @@ struct LinearCall {
     }
 };
 
-int linear_impl(const p4v_linear_desc* d, const float* W, const float* bias, const float* X, const float* O,
-                const float* G, const float* mult, float* w_iv, float* a_iv, float* scores_out, int32_t* best_out,
-                Ctx& c, float* fwd_out = nullptr, const Stage& sg = Stage{}) {
-    LinearCall L(c, d, sg);
-    CHK(L.build(W, bias, X, O, G, mult, w_iv, a_iv, scores_out, best_out, fwd_out));
+int linear_impl(const p4v_linear_desc* d, const LinearTensors& t, const Stage& sg, Ctx& c) {
+    LinearCall L(c, d, t, sg);
+    CHK(L.build());
     // (the weight side first: it depends on no captured tensor -- inside a group that was handed a "capture done" event it runs,
     // with the candidate planes of the weights further down, while the capture passes are still on the GPU)
     CHK(L.init_side(0));
-    if (fwd_out || !sg.full()) {                 // (quant_forward, the granular entry points: no capture to overlap with)
+    if (!sg.full()) {                            // (quant_forward, the granular entry points: no capture to overlap with)
         CHK(q_wait_inputs(c));
         CHK(L.init_side(1));
     }
-    if (!fwd_out && !sg.searches()) return 0;
-    if (fwd_out) { Pass fp = L.forward_pass(); return run_pass(c, fp); }
+    if (sg.forward()) { Pass fp = L.forward_pass(); return run_pass(c, fp); }
+    if (!sg.searches()) return 0;
     const SearchRounds& R = L.rounds;
-    MirrorScope mirrors(c, R.memo_on, w_iv, a_iv);
+    MirrorScope mirrors(c, R.memo_on, t.w_iv, t.a_iv);
     MemoSide memo[2];
     memo[0].on = R.memo_on && L.nH == 1;
     memo[1].on = R.memo_on && L.nA == 1;
@@ -2991,7 +3013,7 @@ int linear_impl(const p4v_linear_desc* d, const float* W, const float* bias, con
         CHK(q_wait_inputs(c));
         CHK(L.init_side(1));
     }
-    if (L.segcos) CHK(enqueue(c, KERN(NchwRowsParams, k_nchw_to_rows), dim3(cdiv(L.N, 32), cdiv(L.M, 32), 1), dim3(256), 0, NchwRowsParams{O, L.M, L.N, L.Ot}));
+    if (L.segcos) CHK(enqueue(c, KERN(NchwRowsParams, k_nchw_to_rows), dim3(cdiv(L.N, 32), cdiv(L.M, 32), 1), dim3(256), 0, NchwRowsParams{t.O, L.M, L.N, L.Ot}));
     for (int round = 0; round < R.n_rounds; ++round)
         for (int side = 0; side < 2; ++side) CHK(L.search_side(side, round, memo[side], host));
     return 0;
@@ -3002,14 +3024,15 @@ int linear_impl(const p4v_linear_desc* d, const float* W, const float* bias, con
 // ------------------------------------------------------------------------------------------------
 // fc1's part: x and W1 packed as LinearCall::forward_pass packs them (pack_operand, k_scale_table), then k_mlp_fc1, whose
 // epilogue writes fc2's row plane(s) -- the fp32 hidden tensor, torch's GELU over it and k_pack_dual / k_pack1 of it are gone.
-// fc2's part: its forward pass as run_pass runs it, the row operand prepacked (Operand.plane): same sweep kernel, same epilogue.
+// fc2's part: its forward pass as run_pass runs it, the row operand prepacked (Operand.prepacked): same sweep kernel, same epilogue.
 // Where the planes of the calling thread's last call lie in its workspace (p4v_debug_mlp_planes: the tests read them there)
 struct MlpPlanes { size_t off1 = 0, off2 = 0; long rows = 0, cols = 0; int twin = 0; };
 thread_local MlpPlanes g_mlp_planes;
 constexpr int MLP_RECORD_KIND = 16;
 
-int mlp_impl(const p4v_mlp_desc* d, const float* W1, const float* b1, const float* W2, const float* b2, const float* X,
-             const float* w1_iv, const float* a1_iv, const float* w2_iv, const float* a2_iv, float* out, float* hidden, Ctx& c) {
+// `t1`, `t2`: the two layers' records as p4v_linear_quant_forward fills them -- t1.fwd_out is the optional fp32 copy of the hidden
+// tensor (fc1 stores no other output), t2.X stays null (fc2 reads fc1's planes).
+int mlp_impl(const p4v_mlp_desc* d, const LinearTensors& t1, const LinearTensors& t2, Ctx& c) {
     const p4v_linear_desc* d1 = &d->fc1;
     const p4v_linear_desc* d2 = &d->fc2;
     // the envelope, before anything is planned or launched
@@ -3019,12 +3042,11 @@ int mlp_impl(const p4v_mlp_desc* d, const float* W1, const float* b1, const floa
     if (d1->n_H != 1 || d1->n_a != 1 || d2->n_H != 1 || d2->n_a != 1)
         return fail(P4V_ERR_UNSUPPORTED, "mlp: the fused forward takes n_H = n_a = 1 on both layers");
     if (d1->twin_postgelu) return fail(P4V_ERR_UNSUPPORTED, "mlp: fc1 reads no GELU output (twin_postgelu belongs on fc2)");
-    if ((d1->reserved | d2->reserved) & 1) return fail(P4V_ERR_UNSUPPORTED, "mlp: int8 planes only (desc.reserved bit 0 is set)");
-    const Stage sg{};
-    float* tag = (float*)16;        // "this is a forward call" for LinearCall::build: fc1 stores no fp32 output, the sizing run has none
-    LinearCall L1(c, d1, sg), L2(c, d2, sg);
-    CHK(L1.build(W1, b1, X, nullptr, nullptr, nullptr, const_cast<float*>(w1_iv), const_cast<float*>(a1_iv), nullptr, nullptr, tag));
-    CHK(L2.build(W2, b2, nullptr, nullptr, nullptr, nullptr, const_cast<float*>(w2_iv), const_cast<float*>(a2_iv), nullptr, nullptr, out ? out : tag));
+    if ((d1->reserved | d2->reserved) & RSV_FP32_PLANES) return fail(P4V_ERR_UNSUPPORTED, "mlp: int8 planes only (desc.reserved bit 0 is set)");
+    const Stage sg{ST_FWD};
+    LinearCall L1(c, d1, t1, sg), L2(c, d2, t2, sg);
+    CHK(L1.build());
+    CHK(L2.build());
     if (!L1.i8 || !L2.i8) return fail(P4V_ERR_UNSUPPORTED, "mlp: int8 planes only");
     // fc2's pass first: its plan says how large the row plane(s) are
     Pass fp2 = L2.forward_pass();
@@ -3054,10 +3076,10 @@ int mlp_impl(const p4v_mlp_desc* d, const float* W1, const float* b1, const floa
             MlpFc1Params q{};
             q.A = xa; q.B = wb; q.ldk = K1p; q.ktiles = K1p / SW_BKB;
             q.S1 = S1; q.s_cs = L1.nV; q.sb_div = L1.crb_rows;
-            q.bias = L1.bias; q.M = M; q.N = Hd; q.mtiles = Mp / SW_BM; q.ntiles = Hp / SW_BN;
-            q.q1 = a2_iv; q.q2 = nullptr; q.q2_const = L2.a_neg;
+            q.bias = t1.bias; q.M = M; q.N = Hd; q.mtiles = Mp / SW_BM; q.ntiles = Hp / SW_BN;
+            q.q1 = t2.a_iv; q.q2 = nullptr; q.q2_const = L2.a_neg;
             q.lo1 = L2.twin ? 0 : -L2.aq; q.hi1 = L2.aq - 1; q.lo2 = -L2.aq; q.hi2 = 0;
-            q.P1 = (int8_t*)P1; q.P2 = (int8_t*)P2; q.Kp = Kp; q.hidden = hidden;
+            q.P1 = (int8_t*)P1; q.P2 = (int8_t*)P2; q.Kp = Kp; q.hidden = t1.fwd_out;
             g_alg_macs_cand = (double)M * Hd * K1;
             g_alg_bytes = 4.0 * ((double)M * K1 + (double)Hd * K1) + (double)M * Hd * (L2.twin ? 2 : 1);
             g_exec_frac = 1.0;
@@ -3070,15 +3092,15 @@ int mlp_impl(const p4v_mlp_desc* d, const float* W1, const float* b1, const floa
         }
         c.ws.off = mark;
     }
-    fp2.row.plane = P1 ? (const void*)P1 : (const void*)16;   // (the sizing run carves nothing)
-    if (L2.twin) fp2.row2.plane = P2 ? (const void*)P2 : (const void*)16;
+    fp2.row.prepacked = true; fp2.row.plane = P1;             // (null in the sizing run: it carves nothing)
+    if (L2.twin) { fp2.row2.prepacked = true; fp2.row2.plane = P2; }
     return run_pass(c, fp2);
 }
 // the dry run of the planner: the envelope's verdict, and the bytes the call needs
 int mlp_sizing_run(const p4v_mlp_desc* d, size_t* need) {
-    Ctx c{nullptr, Arena(nullptr, 0), true};
-    CHK(mlp_impl(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, c));
-    *need = c.ws.peak + 4096;
+    Ctx c = Ctx::sizing();
+    CHK(mlp_impl(d, LinearTensors{}, LinearTensors{}, c));
+    *need = c.sized_bytes();
     return 0;
 }
 
@@ -3086,13 +3108,28 @@ int mlp_sizing_run(const p4v_mlp_desc* d, size_t* need) {
 // MatMul
 // ------------------------------------------------------------------------------------------------
 // Row / column sub-blocks of the (n_G, n_V, n_H) view (reference matmul.py:109-138); (v, h): the block of a granular step
+// (all counts 1, the default: no sub-blocks -- the head-wise engine)
 struct MatMulBlocks {
     int nVA = 1, nHA = 1, nVB = 1, nHB = 1, v = 0, h = 0;
     bool any() const { return nVA != 1 || nHA != 1 || nVB != 1 || nHB != 1; }
 };
-int matmul_blocks_impl(const p4v_matmul_desc* d, const MatMulBlocks& mb, const float* A, const float* B, const float* O, const float* G,
-                       const float* mult, float* A_iv, float* B_iv, float* split, float* scores_out, int32_t* best_out, Ctx& c,
-                       float* fwd_out, const Stage& sg);
+MatMulBlocks blocks_of(const p4v_matmul_blocks_desc* d, int v = 0, int h = 0) { return MatMulBlocks{d->n_V_A, d->n_H_A, d->n_V_B, d->n_H_B, v, h}; }
+int blocks_check(const p4v_matmul_blocks_desc* d, const char* who, const char* what = "") {
+    if (d->n_V_A < 1 || d->n_H_A < 1 || d->n_V_B < 1 || d->n_H_B < 1) return fail(P4V_ERR_INVALID, "%s: %snon-positive block count", who, what);
+    return 0;
+}
+// The device pointers of one matmul_impl call, filled by name at the entry points; what the call's mode (Stage) does not read
+// stays null, and a sizing run leaves all of them null.
+struct MatMulTensors {
+    const float *A = nullptr, *B = nullptr;                     // the operands, read through the descriptor's strides
+    const float *O = nullptr, *G = nullptr;                     // raw_out / raw_grad [Z][M][N] (searches; G: the hessian metric)
+    const float* mult = nullptr;                                // [eq_n + 1] candidate multipliers (ST_INIT with a search)
+    float *A_iv = nullptr, *B_iv = nullptr;                     // intervals [heads] (sub-blocks: [heads][n_V][n_H]; sos: the scalar A_interval)
+    float* split = nullptr;                                     // sos: the split -- out of the split search, in for the B search and ST_FWD
+    float* scores = nullptr; int32_t* best = nullptr;           // optional score tables / selections
+    float* fwd_out = nullptr;                                   // ST_FWD: the destination [Z][M][N]
+};
+int matmul_blocks_impl(const p4v_matmul_desc* d, const MatMulBlocks& mb, const MatMulTensors& t, const Stage& sg, Ctx& c);
 
 // One head-wise matmul_impl call: geometry, workspace and the builders of its passes.  Sides: 0 = the A search (with sos: the
 // split search), 1 = the B search.
@@ -3100,14 +3137,12 @@ struct MatMulCall {
     static constexpr int NSPLIT = 20;                 // matmul.py:636
     Ctx& c;
     const p4v_matmul_desc* d;
+    const MatMulTensors t;
     const Stage& sg;
     int H = 0, Z = 0, M = 0, K = 0, N = 0;            // heads, batch x heads, the GEMM of one head
     int Aq = 0, Bq = 0;                               // 2^(bit - 1)
     int epi = 0, wt_mode = 0, ncand = 0;
     bool cosm = false;
-    const float *A = nullptr, *B = nullptr, *O = nullptr, *G = nullptr, *mult = nullptr;
-    float *A_iv = nullptr, *B_iv = nullptr, *split = nullptr;   // intervals [heads] (sos: the scalar A_interval and the split)
-    float* fwd_out = nullptr;                         // quant_forward (matmul.py:140-145; sos: matmul.py:595-598): intervals / split are INPUTS
     unsigned *enc_A = nullptr, *enc_B = nullptr;
     float *A_cands_ws = nullptr, *B_cands_ws = nullptr;
     const float *A_cands = nullptr, *B_cands = nullptr;         // built by this call, or the caller's (granular search)
@@ -3117,22 +3152,21 @@ struct MatMulCall {
     PlaneCache plane_A, plane_B;
     SliceCache slice;
 
-    MatMulCall(Ctx& c_, const p4v_matmul_desc* d_, const Stage& sg_) : c(c_), d(d_), sg(sg_) {}
+    MatMulCall(Ctx& c_, const p4v_matmul_desc* d_, const MatMulTensors& t_, const Stage& sg_) : c(c_), d(d_), t(t_), sg(sg_) {}
 
     // argument checks and geometry
-    int build(const float* A_, const float* B_, const float* O_, const float* G_, const float* mult_, float* A_iv_, float* B_iv_,
-              float* split_, float* scores_out, int32_t* best_out, float* fwd_out_) {
-        A = A_; B = B_; O = O_; G = G_; mult = mult_; A_iv = A_iv_; B_iv = B_iv_; split = split_; fwd_out = fwd_out_;
+    int build() {
         H = d->heads; Z = d->batch * d->heads; M = d->M; K = d->K; N = d->N;
         if (Z <= 0 || M <= 0 || K <= 0 || N <= 0 || d->eq_n <= 0) return fail(P4V_ERR_INVALID, "matmul: non-positive dimension");
         if (d->A_bit > 8 || d->B_bit > 8 || d->A_bit < 2 || d->B_bit < 2) return fail(P4V_ERR_UNSUPPORTED, "matmul: bit widths 2..8 supported");
         Aq = 1 << (d->A_bit - 1); Bq = 1 << (d->B_bit - 1);
         metric_epi(d->metric, &epi, &wt_mode);
         cosm = epi == EPI_COS;
-        if (wt_mode == 1 && !G && !fwd_out && sg.searches()) return fail(P4V_ERR_INVALID, "matmul: hessian metric needs raw_grad");
-        if (d->sos && !split) return fail(P4V_ERR_INVALID, "matmul: sos needs d_split");
+        if (wt_mode == 1 && !t.G && sg.searches() && !c.dry) return fail(P4V_ERR_INVALID, "matmul: hessian metric needs raw_grad");
+        // the split: written by the split search, read by the B search and the forward; the initialisation alone does without
+        if (d->sos && !t.split && (sg.searches() || sg.forward()) && !c.dry) return fail(P4V_ERR_INVALID, "matmul: sos needs d_split");
         ncand = d->eq_n + 1;
-        rounds = SearchRounds(sg, d->search_round, d->reserved, d->eq_n, H, c, scores_out, best_out);
+        rounds = SearchRounds(sg, d->search_round, !(d->reserved & RSV_NO_MEMO), d->eq_n, H, c, t.scores, t.best);
         return 0;
     }
     int workspace() {
@@ -3140,8 +3174,8 @@ struct MatMulCall {
         enc_B = c.ws.get<unsigned>(H);
         A_cands_ws = c.ws.get<float>((size_t)ncand * H);
         B_cands_ws = c.ws.get<float>((size_t)ncand * H);
-        A_cands = (sg.mask & ST_INIT) ? A_cands_ws : sg.cands1;
-        B_cands = (sg.mask & ST_INIT) ? B_cands_ws : sg.cands2;
+        A_cands = sg.inits() ? A_cands_ws : sg.cands1;
+        B_cands = sg.inits() ? B_cands_ws : sg.cands2;
         split_cands = c.ws.get<float>(NSPLIT);
         A_headwise = c.ws.get<float>(H);
         if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small");
@@ -3149,23 +3183,23 @@ struct MatMulCall {
     }
     // interval initialisation of both operands and their candidate tables
     int init() {
-        if (fwd_out || !(sg.mask & ST_INIT)) return 0;
+        if (!sg.inits()) return 0;
         const long sa[4] = {d->a_stride[0], d->a_stride[1], d->a_stride[2], d->a_stride[3]};
         const long sb[4] = {d->b_stride[0], d->b_stride[1], d->b_stride[2], d->b_stride[3]};
-        float* a_dst = d->sos ? A_headwise : A_iv;
-        CHK(launch_absmax(c, A, sa, d->batch, H, M, K, 1, 1, M, K, 0, enc_A));
+        float* a_dst = d->sos ? A_headwise : t.A_iv;
+        CHK(launch_absmax(c, t.A, sa, d->batch, H, M, K, 1, 1, M, K, 0, enc_A));
         CHK(launch_interval(c, enc_A, H, (float)(Aq - 0.5), d->init_layerwise, a_dst));
-        CHK(launch_absmax(c, B, sb, d->batch, H, K, N, 1, 1, K, N, 0, enc_B));
-        CHK(launch_interval(c, enc_B, H, (float)(Bq - 0.5), d->init_layerwise, B_iv));
+        CHK(launch_absmax(c, t.B, sb, d->batch, H, K, N, 1, 1, K, N, 0, enc_B));
+        CHK(launch_interval(c, enc_B, H, (float)(Bq - 0.5), d->init_layerwise, t.B_iv));
         if (sg.searches()) {
-            if (!d->sos) CHK(launch_cands(c, mult, A_iv, ncand, H, A_cands_ws));
-            CHK(launch_cands(c, mult, B_iv, ncand, H, B_cands_ws));
+            if (!d->sos) CHK(launch_cands(c, t.mult, t.A_iv, ncand, H, A_cands_ws));
+            CHK(launch_cands(c, t.mult, t.B_iv, ncand, H, B_cands_ws));
         }
         return 0;
     }
     // the split candidates 2**(-i) of the split-of-softmax search
     int upload_splits() {
-        if (fwd_out || !(sg.mask & ST_S1) || !d->sos || c.dry) return 0;
+        if (!(sg.mask & ST_S1) || !d->sos || c.dry) return 0;
         float sc[NSPLIT];
         for (int i = 0; i < NSPLIT; ++i) sc[i] = (float)std::ldexp(1.0, -i);  // 2**(-i), exact in fp32
         CHK(q_h2d(c, split_cands, sc, sizeof sc));
@@ -3187,17 +3221,17 @@ struct MatMulCall {
         return op;
     }
     Operand A_operand(bool expanded, const float* scales, int sc_cs, int mode) const {
-        Operand op = operand(A, d->a_stride, 2, 3, M, Aq, expanded, scales, sc_cs, mode);
+        Operand op = operand(t.A, d->a_stride, 2, 3, M, Aq, expanded, scales, sc_cs, mode);
         op.pk.qm1 = (float)(Aq - 1);
         return op;
     }
     Operand B_operand(bool expanded, const float* scales, int sc_cs, int mode) const {
-        return operand(B, d->b_stride, 3, 2, N, Bq, expanded, scales, sc_cs, mode);
+        return operand(t.B, d->b_stride, 3, 2, N, Bq, expanded, scales, sc_cs, mode);
     }
     // what every search pass shares: the GEMM and its target; cosine runs swapped (rows = n)
     void common(Pass& ps) const {
         ps.Z = Z; ps.K = K;
-        ps.O = O; ps.G = G; ps.wt_mode = wt_mode; ps.epi = epi;
+        ps.O = t.O; ps.G = t.G; ps.wt_mode = wt_mode; ps.epi = epi;
         ps.o_inner = INT_MAX;
         if (!cosm) { ps.Mrows = M; ps.Ncols = N; ps.o_zs = (long)M * N; ps.o_ms = N; ps.o_ns = 1; }
         else { ps.Mrows = N; ps.Ncols = M; ps.o_zs = (long)M * N; ps.o_ms = 1; ps.o_ns = N; ps.G = nullptr;
@@ -3219,17 +3253,17 @@ struct MatMulCall {
         Pass fp{};
         fp.Z = Z; fp.K = K; fp.Mrows = M; fp.Ncols = N;
         fp.i8 = true; fp.twin = d->sos; fp.epi = EPI_FWD; fp.wt_mode = 0; fp.eq_n = 1;
-        fp.row = d->sos ? A_operand(false, split, 0, PACK_SOS_HI) : A_operand(false, A_iv, 0, PACK_SYM);
-        if (d->sos) fp.row2 = A_operand(false, split, 0, PACK_SOS_LO);
-        fp.col = B_operand(false, B_iv, 0, PACK_SYM);
+        fp.row = d->sos ? A_operand(false, t.split, 0, PACK_SOS_HI) : A_operand(false, t.A_iv, 0, PACK_SYM);
+        if (d->sos) fp.row2 = A_operand(false, t.split, 0, PACK_SOS_LO);
+        fp.col = B_operand(false, t.B_iv, 0, PACK_SYM);
         fp.use_s1 = true; fp.s_cs = H; fp.sb_mode = 2; fp.sb_div = H;
-        if (!d->sos) fp.s1 = ScaleParams{A_iv, 0, 1, 0.f, B_iv, 0, 1, 0.f, 0, 0, nullptr};
+        if (!d->sos) fp.s1 = ScaleParams{t.A_iv, 0, 1, 0.f, t.B_iv, 0, 1, 0.f, 0, 0, nullptr};
         else {
-            fp.s1 = ScaleParams{nullptr, 0, 0, 1.0f / (float)(Aq - 1), B_iv, 0, 1, 0.f, 0, 0, nullptr};
-            fp.s2 = ScaleParams{A_iv, 0, 0, 0.f, B_iv, 0, 1, 0.f, 0, 0, nullptr};
+            fp.s1 = ScaleParams{nullptr, 0, 0, 1.0f / (float)(Aq - 1), t.B_iv, 0, 1, 0.f, 0, 0, nullptr};
+            fp.s2 = ScaleParams{t.A_iv, 0, 0, 0.f, t.B_iv, 0, 1, 0.f, 0, 0, nullptr};
         }
-        fp.O = fwd_out; fp.G = nullptr; fp.o_zs = (long)M * N; fp.o_ms = N; fp.o_ns = 1; fp.o_inner = INT_MAX;
-        fp.nj = 1; fp.store_out = fwd_out;
+        fp.O = t.fwd_out; fp.G = nullptr; fp.o_zs = (long)M * N; fp.o_ms = N; fp.o_ns = 1; fp.o_inner = INT_MAX;
+        fp.nj = 1; fp.store_out = t.fwd_out;
         return fp;
     }
     // A search, B fixed at its current head-wise interval (matmul.py:483-522)
@@ -3237,31 +3271,31 @@ struct MatMulCall {
         Pass ps{};
         common(ps);
         ps.i8 = true; ps.twin = false; ps.eq_n = d->eq_n;
-        place(ps, A_operand(true, A_cands, H, PACK_SYM), B_operand(false, B_iv, 0, PACK_SYM));
+        place(ps, A_operand(true, A_cands, H, PACK_SYM), B_operand(false, t.B_iv, 0, PACK_SYM));
         ps.use_s1 = true; ps.s_cs = H; ps.sb_mode = 2; ps.sb_div = H;
-        ps.s1 = ScaleParams{A_cands, H, 1, 0.f, B_iv, 0, 1, 0.f, 0, 0, nullptr};
-        per_head(ps, A_cands, A_iv);
+        ps.s1 = ScaleParams{A_cands, H, 1, 0.f, t.B_iv, 0, 1, 0.f, 0, 0, nullptr};
+        per_head(ps, A_cands, t.A_iv);
         ps.cache = rounds.keep_planes ? &plane_A : nullptr;
         ps.scores_out = rounds.scores_of(round, 0); ps.best_out = rounds.best_of(round, 0);
-        ps.prunable = !cosm && !(d->reserved & 8); ps.scache = &slice; ps.host_sync_ok = rounds.memo_on;
+        ps.prunable = !cosm && !(d->reserved & RSV_NO_PRUNE); ps.scache = &slice; ps.host_sync_ok = rounds.memo_on;
         return ps;
     }
     // split search against the UNQUANTISED B (matmul.py:600-631): A quantised in registers, one kernel (k_sos_split)
     SosSplitJob split_job(int round) {
         SosSplitJob j{};
-        j.kp.A = A; j.kp.a_z2 = d->a_stride[0]; j.kp.a_z = d->a_stride[1]; j.kp.a_r = d->a_stride[2]; j.kp.a_k = d->a_stride[3];
+        j.kp.A = t.A; j.kp.a_z2 = d->a_stride[0]; j.kp.a_z = d->a_stride[1]; j.kp.a_r = d->a_stride[2]; j.kp.a_k = d->a_stride[3];
         j.kp.zdiv = H;
-        j.kp.B = B; j.kp.b_z2 = d->b_stride[0]; j.kp.b_z = d->b_stride[1]; j.kp.b_k = d->b_stride[2]; j.kp.b_n = d->b_stride[3];
-        j.kp.O = O; j.kp.G = G ? G : O;
+        j.kp.B = t.B; j.kp.b_z2 = d->b_stride[0]; j.kp.b_z = d->b_stride[1]; j.kp.b_k = d->b_stride[2]; j.kp.b_n = d->b_stride[3];
+        j.kp.O = t.O; j.kp.G = t.G ? t.G : t.O;
         j.kp.Z = Z; j.kp.M = M; j.kp.K = K; j.kp.N = N; j.kp.wt_mode = wt_mode; j.kp.C = NSPLIT;
         j.kp.splits = split_cands;
         j.kp.qm1 = (float)(Aq - 1); j.kp.c_inv = 1.0f / (float)(Aq - 1);
         j.kp.lo_top = std::min(std::nearbyintf(1.0f / j.kp.c_inv), (float)(Aq - 1));
         j.kp.halves = cdiv(M, 128);
         j.epi = epi; j.norm = 1.0 / ((double)H * M * N);
-        j.cands = split_cands; j.split = split; j.A_iv = A_iv; j.aux_div = (float)(Aq - 1);   // A_interval = split/(qmax-1) (matmul.py:629)
+        j.cands = split_cands; j.split = t.split; j.A_iv = t.A_iv; j.aux_div = (float)(Aq - 1);   // A_interval = split/(qmax-1) (matmul.py:629)
         j.scores_out = (d->eq_n >= NSPLIT) ? rounds.scores_of(round, 0) : nullptr; j.scores_out_ld = H; j.best_out = rounds.best_of(round, 0);
-        j.scache = &slice; j.host_sync_ok = rounds.memo_on; j.prunable = !(d->reserved & 8);
+        j.scache = &slice; j.host_sync_ok = rounds.memo_on; j.prunable = !(d->reserved & RSV_NO_PRUNE);
         return j;
     }
     // ... the same search on fp32 operands (shapes k_sos_split has no instance for, cosine)
@@ -3273,8 +3307,8 @@ struct MatMulCall {
         ps.use_s1 = false; ps.s_cs = 1; ps.sb_mode = 0;
         ps.j_mode = 0; ps.nj = 1; ps.cos_j_mode = 0;
         ps.norm = cosm ? 1.0 / ((double)H * M) : 1.0 / ((double)H * M * N);
-        ps.cands = split_cands; ps.cand_cs = 1; ps.cand_js = 0; ps.interval = split; ps.out_js = 0;
-        ps.aux_out = A_iv; ps.aux_div = (float)(Aq - 1);   // A_interval = split/(qmax-1) (matmul.py:629)
+        ps.cands = split_cands; ps.cand_cs = 1; ps.cand_js = 0; ps.interval = t.split; ps.out_js = 0;
+        ps.aux_out = t.A_iv; ps.aux_div = (float)(Aq - 1);   // A_interval = split/(qmax-1) (matmul.py:629)
         ps.scores_out = (d->eq_n >= NSPLIT) ? rounds.scores_of(round, 0) : nullptr; ps.scores_out_ld = H; ps.best_out = rounds.best_of(round, 0);
         return ps;
     }
@@ -3286,47 +3320,45 @@ struct MatMulCall {
         const bool twin_rows = d->sos && !cosm;
         ps.i8 = !(d->sos && cosm);   // cosine + sos: fp32 operands (the twin sits on the column side when swapped)
         ps.twin = twin_rows;
-        place(ps, d->sos ? A_operand(false, split, 0, ps.i8 ? PACK_SOS_HI : PACK_SOS_SIM) : A_operand(false, A_iv, 0, PACK_SYM),
+        place(ps, d->sos ? A_operand(false, t.split, 0, ps.i8 ? PACK_SOS_HI : PACK_SOS_SIM) : A_operand(false, t.A_iv, 0, PACK_SYM),
               B_operand(true, B_cands, H, PACK_SYM));
-        if (twin_rows) ps.row2 = A_operand(false, split, 0, PACK_SOS_LO);
+        if (twin_rows) ps.row2 = A_operand(false, t.split, 0, PACK_SOS_LO);
         ps.use_s1 = ps.i8; ps.s_cs = H; ps.sb_mode = 2; ps.sb_div = H;
-        if (!d->sos) ps.s1 = ScaleParams{A_iv, 0, 1, 0.f, B_cands, H, 1, 0.f, 0, 0, nullptr};
+        if (!d->sos) ps.s1 = ScaleParams{t.A_iv, 0, 1, 0.f, B_cands, H, 1, 0.f, 0, 0, nullptr};
         else {
             // high range: k_hi/(q-1) ; low range: k_lo * (split/(q-1)) = k_lo * A_interval
             ps.s1 = ScaleParams{nullptr, 0, 0, 1.0f / (float)(Aq - 1), B_cands, H, 1, 0.f, 0, 0, nullptr};
-            ps.s2 = ScaleParams{A_iv, 0, 0, 0.f, B_cands, H, 1, 0.f, 0, 0, nullptr};
+            ps.s2 = ScaleParams{t.A_iv, 0, 0, 0.f, B_cands, H, 1, 0.f, 0, 0, nullptr};
         }
-        per_head(ps, B_cands, B_iv);
+        per_head(ps, B_cands, t.B_iv);
         ps.cache = rounds.keep_planes ? &plane_B : nullptr;
         ps.scores_out = rounds.scores_of(round, 1); ps.best_out = rounds.best_of(round, 1);
-        ps.prunable = !cosm && ps.i8 && !(d->reserved & 8); ps.scache = &slice; ps.host_sync_ok = rounds.memo_on;
+        ps.prunable = !cosm && ps.i8 && !(d->reserved & RSV_NO_PRUNE); ps.scache = &slice; ps.host_sync_ok = rounds.memo_on;
         return ps;
     }
 };
 
-int matmul_impl(const p4v_matmul_desc* d, const float* A, const float* B, const float* O, const float* G,
-                const float* mult, float* A_iv, float* B_iv, float* split, float* scores_out, int32_t* best_out, Ctx& c,
-                float* fwd_out = nullptr, const Stage& sg = Stage{}, const MatMulBlocks* mb = nullptr) {
-    MatMulCall m(c, d, sg);
-    CHK(m.build(A, B, O, G, mult, A_iv, B_iv, split, scores_out, best_out, fwd_out));
+int matmul_impl(const p4v_matmul_desc* d, const MatMulTensors& t, const Stage& sg, Ctx& c, const MatMulBlocks& mb = MatMulBlocks{}) {
+    MatMulCall m(c, d, t, sg);
+    CHK(m.build());
     cvt_bias(c);     // (first call of the process: probe the conversion quant16_sat8 relies on)
     CHK(q_wait_inputs(c));     // (inside a group with a "capture done" event: everything below reads captured tensors)
     // row / column sub-blocks: the K-segmented kernel family; with all four block counts 1 nothing below changes
-    if (mb && mb->any()) return matmul_blocks_impl(d, *mb, A, B, O, G, mult, A_iv, B_iv, split, scores_out, best_out, c, fwd_out, sg);
+    if (mb.any()) return matmul_blocks_impl(d, mb, t, sg, c);
     CHK(m.workspace());
     CHK(m.init());
-    if (!fwd_out && !sg.searches()) return 0;
+    if (sg.forward()) { Pass fp = m.forward_pass(); return run_pass(c, fp); }
+    if (!sg.searches()) return 0;
     CHK(m.upload_splits());
-    if (fwd_out) { Pass fp = m.forward_pass(); return run_pass(c, fp); }
     const SearchRounds& R = m.rounds;
-    MirrorScope mirrors(c, R.memo_on, A_iv, B_iv, d->sos ? split : nullptr);
+    MirrorScope mirrors(c, R.memo_on, t.A_iv, t.B_iv, d->sos ? t.split : nullptr);
     const int H = m.H, nAiv = d->sos ? 1 : H;
     // the A search is a function of B's interval; with sos it is the split search against the RAW B: a function of nothing ->
     // always a hit after round 1, its value the split and the A interval derived from it
     MemoSide memo_A, memo_B;
     memo_A.on = memo_B.on = R.memo_on;
-    const DevVecs key_A = d->sos ? DevVecs() : DevVecs(B_iv, H), val_A = d->sos ? DevVecs(split, 1, A_iv, 1) : DevVecs(A_iv, nAiv);
-    const DevVecs key_B(A_iv, nAiv), val_B(B_iv, H);
+    const DevVecs key_A = d->sos ? DevVecs() : DevVecs(t.B_iv, H), val_A = d->sos ? DevVecs(t.split, 1, t.A_iv, 1) : DevVecs(t.A_iv, nAiv);
+    const DevVecs key_B(t.A_iv, nAiv), val_B(t.B_iv, H);
     for (int round = 0; round < R.n_rounds; ++round) {
         bool hit = false;
         CHK(memo_A.restore(c, key_A, nullptr, val_A, nullptr, &hit));
@@ -3359,9 +3391,7 @@ int matmul_impl(const p4v_matmul_desc* d, const float* A, const float* B, const 
 // that block's scale only, every other block on the interval entering the step, the score the full-output score per head; each
 // step is one sweep of the whole operand (no pruning, no pass memo: first version).  Score tables [round][step][eq_n][heads],
 // steps = A blocks then B blocks (split-of-softmax: the 20-row split table, then B blocks).
-int matmul_blocks_impl(const p4v_matmul_desc* d, const MatMulBlocks& mb, const float* A, const float* B, const float* O, const float* G,
-                       const float* mult, float* A_iv, float* B_iv, float* split, float* scores_out, int32_t* best_out, Ctx& c,
-                       float* fwd_out, const Stage& sg) {
+int matmul_blocks_impl(const p4v_matmul_desc* d, const MatMulBlocks& mb, const MatMulTensors& t, const Stage& sg, Ctx& c) {
     const int H = d->heads, Z = d->batch * d->heads, M = d->M, K = d->K, N = d->N;
     const int nVA = mb.nVA, nHA = mb.nHA, nVB = mb.nVB, nHB = mb.nHB;
     if (nVA < 1 || nHA < 1 || nVB < 1 || nHB < 1) return fail(P4V_ERR_INVALID, "matmul: non-positive block count");
@@ -3370,13 +3400,13 @@ int matmul_blocks_impl(const p4v_matmul_desc* d, const MatMulBlocks& mb, const f
     if (d->A_bit < 2 || d->B_bit < 2) return fail(P4V_ERR_UNSUPPORTED, "matmul: bit widths 2..8 supported");
     int epi, wt_mode;
     metric_epi(d->metric, &epi, &wt_mode);
-    if (epi == EPI_COS && !fwd_out && sg.searches())
+    if (epi == EPI_COS && sg.searches())
         return fail(P4V_ERR_UNSUPPORTED, "matmul: the cosine metric with row/column sub-blocks (n_V, n_H > 1) is not implemented on the GPU");
     SegPlan g{};
     g.batch = d->batch; g.H = H; g.M = M; g.K = K; g.N = N;
     g.nVA = nVA; g.nHA = nHA; g.nVB = nVB; g.nHB = nHB;
     g.crA = cdiv(M, nVA); g.ccA = cdiv(K, nHA); g.crB = cdiv(K, nVB); g.ccB = cdiv(N, nHB);
-    g.A = A; g.B = B;
+    g.A = t.A; g.B = t.B;
     for (int i = 0; i < 4; ++i) { g.a_st[i] = d->a_stride[i]; g.b_st[i] = d->b_stride[i]; }
     g.Aq = 1 << (d->A_bit - 1); g.Bq = 1 << (d->B_bit - 1); g.sos = d->sos != 0;
     CHK(seg_cut_k(g, "matmul"));
@@ -3386,15 +3416,15 @@ int matmul_blocks_impl(const p4v_matmul_desc* d, const MatMulBlocks& mb, const f
     float* A_cands_ws = c.ws.get<float>((size_t)ncand * H * nVA * nHA);
     float* B_cands_ws = c.ws.get<float>((size_t)ncand * nB);
     if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small");
-    g.ivA = A_iv; g.ivB = B_iv; g.split = split;
+    g.ivA = t.A_iv; g.ivB = t.B_iv; g.split = t.split;
 
-    if (fwd_out) {       // quant_forward (matmul.py:140-145; sos: 595-598): intervals / split are inputs
+    if (sg.forward()) {    // quant_forward (matmul.py:140-145; sos: 595-598): intervals / split are inputs
         Pass fp{};
         fp.seg = &g; fp.Z = Z; fp.K = K; fp.Mrows = M; fp.Ncols = N; fp.i8 = true; fp.twin = g.sos;
-        fp.epi = EPI_FWD; fp.eq_n = 1; fp.store_out = fwd_out;
+        fp.epi = EPI_FWD; fp.eq_n = 1; fp.store_out = t.fwd_out;
         return run_pass(c, fp);
     }
-    if (sg.mask & ST_INIT) {
+    if (sg.inits()) {
         // min-max per block; a block of nothing but padding gets 0 (the reference pads with zeros): the running maxima start at
         // enc(+0.0f) -- the bit pattern of -0.0f --, not at k_absmax's "nothing seen" (which decodes to NaN)
         auto absmax = [&](const float* src, const int64_t* st, int R, int C, int nV, int nH, int crb_r, int crb_c, unsigned* out) -> int {
@@ -3406,14 +3436,14 @@ int matmul_blocks_impl(const p4v_matmul_desc* d, const MatMulBlocks& mb, const f
             return enqueue(c, KERN(AbsMaxParams, k_absmax), dim3(cdiv(crb_r, p.row_tile) * nV * nH, H, d->batch), dim3(256), 0, p);
         };
         if (!d->sos) {
-            CHK(absmax(A, d->a_stride, M, K, nVA, nHA, g.crA, g.ccA, enc_A));
-            CHK(launch_interval(c, enc_A, nA, (float)(g.Aq - 0.5), d->init_layerwise, A_iv));
+            CHK(absmax(t.A, d->a_stride, M, K, nVA, nHA, g.crA, g.ccA, enc_A));
+            CHK(launch_interval(c, enc_A, nA, (float)(g.Aq - 0.5), d->init_layerwise, t.A_iv));
         }
-        CHK(absmax(B, d->b_stride, K, N, nVB, nHB, g.crB, g.ccB, enc_B));
-        CHK(launch_interval(c, enc_B, nB, (float)(g.Bq - 0.5), d->init_layerwise, B_iv));
+        CHK(absmax(t.B, d->b_stride, K, N, nVB, nHB, g.crB, g.ccB, enc_B));
+        CHK(launch_interval(c, enc_B, nB, (float)(g.Bq - 0.5), d->init_layerwise, t.B_iv));
         if (sg.searches()) {
-            if (!d->sos) CHK(launch_cands(c, mult, A_iv, ncand, nA, A_cands_ws));
-            CHK(launch_cands(c, mult, B_iv, ncand, nB, B_cands_ws));
+            if (!d->sos) CHK(launch_cands(c, t.mult, t.A_iv, ncand, nA, A_cands_ws));
+            CHK(launch_cands(c, t.mult, t.B_iv, ncand, nB, B_cands_ws));
         }
     }
     if (!sg.searches()) return 0;
@@ -3424,20 +3454,20 @@ int matmul_blocks_impl(const p4v_matmul_desc* d, const MatMulBlocks& mb, const f
         g.side = side; g.ov_v = v; g.ov_h = h; g.cands = cands; g.cand_cs = cs; g.cand_hs = hs;
         Pass ps{};
         ps.seg = &g; ps.Z = Z; ps.K = K; ps.Mrows = M; ps.Ncols = N; ps.i8 = true; ps.twin = g.sos;
-        ps.epi = epi; ps.wt_mode = wt_mode; ps.O = O; ps.G = G; ps.eq_n = d->eq_n;
+        ps.epi = epi; ps.wt_mode = wt_mode; ps.O = t.O; ps.G = t.G; ps.eq_n = d->eq_n;
         ps.j_mode = 2; ps.j_div = H; ps.nj = H; ps.norm = 1.0 / ((double)M * N);
         ps.cands = cands; ps.cand_cs = cs; ps.cand_js = hs; ps.cand_off = 0;
-        ps.interval = (side == 1 ? A_iv : B_iv) + v * nH + h; ps.out_js = nV * nH; ps.out_off = 0;
+        ps.interval = (side == 1 ? t.A_iv : t.B_iv) + v * nH + h; ps.out_js = nV * nH; ps.out_off = 0;
         ps.scores_out = so; ps.scores_out_ld = H; ps.best_out = bo;
         return run_pass(c, ps);
     };
     if (!sg.full()) {    // granular: ONE block step on the caller's candidate table [eq_n + 1][heads]
-        if (sg.mask & ST_S1) CHK(step(1, mb.v, mb.h, sg.cands1, H, 1, scores_out, best_out));
-        if (sg.mask & ST_S2) CHK(step(2, mb.v, mb.h, sg.cands2, H, 1, scores_out, best_out));
+        if (sg.mask & ST_S1) CHK(step(1, mb.v, mb.h, sg.cands1, H, 1, t.scores, t.best));
+        if (sg.mask & ST_S2) CHK(step(2, mb.v, mb.h, sg.cands2, H, 1, t.scores, t.best));
         return 0;
     }
     const int stepsA = d->sos ? 1 : nVA * nHA, steps = stepsA + nVB * nHB;
-    const SearchRounds tabs(sg, d->search_round, d->reserved, d->eq_n, H, c, scores_out, best_out, steps);   // tables [round][step]
+    const SearchRounds tabs(sg, d->search_round, !(d->reserved & RSV_NO_MEMO), d->eq_n, H, c, t.scores, t.best, steps);   // tables [round][step]
     for (int round = 0; round < d->search_round; ++round) {
         int st = 0;
         auto so = [&](int s) { return tabs.scores_of(round, s); };
@@ -3445,7 +3475,7 @@ int matmul_blocks_impl(const p4v_matmul_desc* d, const MatMulBlocks& mb, const f
         if (d->sos) {
             // the split search against the UNQUANTISED B (matmul.py:600-631) knows no blocks: the head-wise engine's pass
             const size_t mark = c.ws.off;
-            CHK(matmul_impl(d, A, B, O, G, nullptr, A_iv, nullptr, split, so(0), bo(0), c, nullptr, Stage{ST_S1, nullptr, nullptr}));
+            CHK(matmul_impl(d, {.A = t.A, .B = t.B, .O = t.O, .G = t.G, .A_iv = t.A_iv, .split = t.split, .scores = so(0), .best = bo(0)}, Stage{ST_S1}, c));
             c.ws.off = mark;
             st = 1;
         } else {
@@ -3463,9 +3493,10 @@ int matmul_blocks_impl(const p4v_matmul_desc* d, const MatMulBlocks& mb, const f
 // ------------------------------------------------------------------------------------------------
 // Conv2d (patch embedding): fp32 operands (the input stays unquantised with a_bit >= 32, conv.py:544)
 // ------------------------------------------------------------------------------------------------
-int conv_impl(const p4v_conv_desc* d, const float* W, const float* bias, const float* X, const float* O, const float* G,
-              const float* mult, float* w_iv, float* a_iv, float* scores_out, int32_t* best_out, Ctx& c,
-              const Stage& sg = Stage{}) {
+// The device pointers of one conv_impl call are a Linear's: weight [oc][ic][kh][kw], bias [oc], x [b][ic][H][W], raw_out / raw_grad
+// [b][oc][fh][fw], intervals [oc] or [1] / [1].  There is no conv forward: fwd_out stays null.
+typedef LinearTensors ConvTensors;
+int conv_impl(const p4v_conv_desc* d, const ConvTensors& t, const Stage& sg, Ctx& c) {
     const int b = d->batch, ic = d->in_channels, H = d->height, Wd = d->width, oc = d->out_channels;
     const int kh = d->kernel_h, kw = d->kernel_w;
     if (kh <= 0 || kw <= 0 || d->stride_h <= 0 || d->stride_w <= 0 || d->pad_h < 0 || d->pad_w < 0 || d->dil_h <= 0 || d->dil_w <= 0)
@@ -3487,7 +3518,7 @@ int conv_impl(const p4v_conv_desc* d, const float* W, const float* bias, const f
     int epi, wt_mode;
     metric_epi(d->metric, &epi, &wt_mode);
     const bool cosm = epi == EPI_COS;
-    if (wt_mode == 1 && !G && sg.searches()) return fail(P4V_ERR_INVALID, "conv: hessian metric needs raw_grad");
+    if (wt_mode == 1 && !t.G && sg.searches() && !c.dry) return fail(P4V_ERR_INVALID, "conv: hessian metric needs raw_grad");
     if (cosm && aquant) return fail(P4V_ERR_UNSUPPORTED, "conv: cosine does not support the activation search (reference conv.py:505-506)");
     const int nw = d->channelwise ? oc : 1;
     const int ncand = d->eq_n + 1;
@@ -3496,40 +3527,40 @@ int conv_impl(const p4v_conv_desc* d, const float* W, const float* bias, const f
     unsigned* enc_a = c.ws.get<unsigned>(1);
     float* w_cands_ws = c.ws.get<float>((size_t)ncand * nw);
     float* a_cands_ws = c.ws.get<float>(ncand);
-    const float* w_cands = (sg.mask & ST_INIT) ? w_cands_ws : sg.cands1;
-    const float* a_cands = (sg.mask & ST_INIT) ? a_cands_ws : sg.cands2;
+    const float* w_cands = sg.inits() ? w_cands_ws : sg.cands1;
+    const float* a_cands = sg.inits() ? a_cands_ws : sg.cands2;
     if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small");
-    if (sg.mask & ST_INIT) {
+    if (sg.inits()) {
         const long stw[4] = {0, 0, K, 1};
-        CHK(launch_absmax(c, W, stw, 1, 1, oc, K, nw, 1, d->channelwise ? 1 : oc, K, 0, enc_w));
-        CHK(launch_interval(c, enc_w, nw, (float)(wq - 0.5), d->init_layerwise, w_iv));
+        CHK(launch_absmax(c, t.W, stw, 1, 1, oc, K, nw, 1, d->channelwise ? 1 : oc, K, 0, enc_w));
+        CHK(launch_interval(c, enc_w, nw, (float)(wq - 0.5), d->init_layerwise, t.w_iv));
         const long stx[4] = {0, 0, (long)ic * H * Wd, 1};
-        CHK(launch_absmax(c, X, stx, 1, 1, b, ic * H * Wd, 1, 1, b, ic * H * Wd, 0, enc_a));
-        CHK(launch_interval(c, enc_a, 1, aquant ? (float)(aq - 0.5) : (float)(std::ldexp(1.0, d->a_bit - 1) - 0.5), 0, a_iv));
+        CHK(launch_absmax(c, t.X, stx, 1, 1, b, ic * H * Wd, 1, 1, b, ic * H * Wd, 0, enc_a));
+        CHK(launch_interval(c, enc_a, 1, aquant ? (float)(aq - 0.5) : (float)(std::ldexp(1.0, d->a_bit - 1) - 0.5), 0, t.a_iv));
         if (sg.searches()) {
-            CHK(launch_cands(c, mult, w_iv, ncand, nw, w_cands_ws));
-            CHK(launch_cands(c, mult, a_iv, ncand, 1, a_cands_ws));
+            CHK(launch_cands(c, t.mult, t.w_iv, ncand, nw, w_cands_ws));
+            CHK(launch_cands(c, t.mult, t.a_iv, ncand, 1, a_cands_ws));
         }
     }
     if (!sg.searches()) return 0;
     // The difference metrics read raw_out / raw_grad as rows of the im2col GEMM, [b * L][oc]: one transposition of the [b][oc][L]
     // tensors (same elements, same sums) gives the sweeps a dense epilogue operand and lets the weight search be pruned like a
     // Linear's (run_pass_pruned: slices are rows).
-    const bool prunable = !cosm && sg.full() && !scores_out && !best_out && !(d->reserved & 8) && d->eq_n >= 32;
+    const bool prunable = !cosm && sg.full() && !t.scores && !t.best && !(d->reserved & RSV_NO_PRUNE) && d->eq_n >= 32;
     float* Ot = prunable ? c.ws.get<float>((size_t)M * oc) : nullptr;
-    float* Gt = (prunable && G) ? c.ws.get<float>((size_t)M * oc) : nullptr;
+    float* Gt = (prunable && (t.G || c.dry)) ? c.ws.get<float>((size_t)M * oc) : nullptr;   // (the sizing run plans for a call with raw_grad)
     if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small");
     if (prunable && !c.dry) {
         const dim3 grid(cdiv(L, 32), cdiv(oc, 32), b);
-        CHK(enqueue(c, KERN(NchwRowsParams, k_nchw_to_rows), grid, dim3(256), 0, NchwRowsParams{O, oc, L, Ot}));
-        if (G) CHK(enqueue(c, KERN(NchwRowsParams, k_nchw_to_rows), grid, dim3(256), 0, NchwRowsParams{G, oc, L, Gt}));
+        CHK(enqueue(c, KERN(NchwRowsParams, k_nchw_to_rows), grid, dim3(256), 0, NchwRowsParams{t.O, oc, L, Ot}));
+        if (t.G) CHK(enqueue(c, KERN(NchwRowsParams, k_nchw_to_rows), grid, dim3(256), 0, NchwRowsParams{t.G, oc, L, Gt}));
     }
     // x as im2col rows.  per_image: Z = batch, rows = pixels of one image (channel-wise cosine reduces over pixels)
     auto x_operand = [&](bool expanded, const float* scales, int sc_cs, bool per_image) {
         Operand op{};
         op.present = true; op.expanded = expanded;
         op.pk = PackParams{};
-        op.pk.src = X; op.pk.conv = 1; op.pk.ic = ic; op.pk.H = H; op.pk.W = Wd; op.pk.kh = kh; op.pk.kw = kw;
+        op.pk.src = t.X; op.pk.conv = 1; op.pk.ic = ic; op.pk.H = H; op.pk.W = Wd; op.pk.kh = kh; op.pk.kw = kw;
         op.pk.sh = d->stride_h; op.pk.sw = d->stride_w; op.pk.ph = d->pad_h; op.pk.pw = d->pad_w; op.pk.dh = d->dil_h; op.pk.dw = d->dil_w;
         op.pk.fw = fw; op.pk.L = L;
         op.pk.Z = per_image ? b : 1; op.pk.s_z = per_image ? (long)ic * H * Wd : 0;
@@ -3541,7 +3572,7 @@ int conv_impl(const p4v_conv_desc* d, const float* W, const float* bias, const f
     auto w_operand = [&](bool expanded, const float* scales, int sc_cs) {
         Operand op{};
         op.present = true; op.expanded = expanded;
-        op.pk = pack2d(W, oc, K, K);
+        op.pk = pack2d(t.W, oc, K, K);
         op.pk.scales = scales; op.pk.sc_cs = sc_cs;
         op.pk.blk_mode = d->channelwise ? 1 : 0; op.pk.blk_div = 1; op.pk.nblk_r = nw; op.pk.nblk_k = 1;
         op.pk.lo = -wq; op.pk.hi = wq - 1;
@@ -3550,14 +3581,14 @@ int conv_impl(const p4v_conv_desc* d, const float* W, const float* bias, const f
     auto setup = [&](Pass& ps, bool w_search) {
         ps.i8 = false; ps.twin = false; ps.epi = epi; ps.wt_mode = wt_mode; ps.eq_n = d->eq_n; ps.K = K;
         ps.use_s1 = false; ps.s_cs = 1; ps.sb_mode = 0;
-        ps.O = O; ps.G = G; ps.bias = bias;
-        Operand xo = x_operand(!w_search, w_search ? a_iv : a_cands, w_search ? 0 : 1, cosm && d->channelwise);
-        Operand wo = w_operand(w_search, w_search ? w_cands : w_iv, w_search ? nw : 0);
+        ps.O = t.O; ps.G = t.G; ps.bias = t.bias;
+        Operand xo = x_operand(!w_search, w_search ? t.a_iv : a_cands, w_search ? 0 : 1, cosm && d->channelwise);
+        Operand wo = w_operand(w_search, w_search ? w_cands : t.w_iv, w_search ? nw : 0);
         if (!cosm) {
             // rows = (image, pixel), cols = oc;  out[b][oc][l]
             ps.Z = 1; ps.Mrows = M; ps.Ncols = oc; ps.row = xo; ps.col = wo;
             ps.o_inner = L; ps.o_bs = (long)oc * L; ps.o_ms = 1; ps.o_ns = L; ps.bias_axis = 0;
-            if (prunable) { ps.O = Ot; ps.G = G ? Gt : nullptr; ps.o_inner = INT_MAX; ps.o_bs = 0; ps.o_ms = oc; ps.o_ns = 1; }
+            if (prunable) { ps.O = Ot; ps.G = t.G ? Gt : nullptr; ps.o_inner = INT_MAX; ps.o_bs = 0; ps.o_ms = oc; ps.o_ns = 1; }
         } else if (d->channelwise) {
             // cosine over the pixels of one image per (image, oc) (conv.py:504-508): rows = pixels, z = image
             ps.Z = b; ps.Mrows = L; ps.Ncols = oc; ps.row = xo; ps.col = wo; ps.col_zs_shared = 1;
@@ -3573,16 +3604,16 @@ int conv_impl(const p4v_conv_desc* d, const float* W, const float* bias, const f
         }
     };
 
-    const SearchRounds R(sg, d->search_round, d->reserved, d->eq_n, nw, c, scores_out, best_out);
+    const SearchRounds R(sg, d->search_round, !(d->reserved & RSV_NO_MEMO), d->eq_n, nw, c, t.scores, t.best);
     const bool memo_on = R.memo_on, keep_planes = R.keep_planes;
-    MirrorScope mirrors(c, memo_on, w_iv, a_iv);
+    MirrorScope mirrors(c, memo_on, t.w_iv, t.a_iv);
     PlaneCache plane_w, plane_a;
     SliceCache slice;
     MemoSide memo_w, memo_a;
     memo_w.on = memo_on;
     memo_a.on = memo_on && aquant;
     // with a_bit >= 32 the input is never quantised: the weight search depends on nothing (conv.py:544)
-    const DevVecs key_w = aquant ? DevVecs(a_iv, 1) : DevVecs(), val_w(w_iv, nw), key_a(w_iv, nw), val_a(a_iv, 1);
+    const DevVecs key_w = aquant ? DevVecs(t.a_iv, 1) : DevVecs(), val_w(t.w_iv, nw), key_a(t.w_iv, nw), val_a(t.a_iv, 1);
     for (int round = 0; round < R.n_rounds; ++round) {
         bool hit = false;
         CHK(memo_w.restore(c, key_w, nullptr, val_w, nullptr, &hit));
@@ -3593,7 +3624,7 @@ int conv_impl(const p4v_conv_desc* d, const float* W, const float* bias, const f
             if (!cosm) { ps.j_mode = d->channelwise ? 3 : 0; ps.norm = d->channelwise ? 1.0 / (double)L : 1.0 / ((double)L * oc); }
             else if (d->channelwise) { ps.cos_j_mode = 3; ps.norm = 1.0; }
             else { ps.cos_j_mode = 0; ps.norm = 1.0 / (double)L; }
-            ps.cands = w_cands; ps.cand_cs = nw; ps.cand_js = 1; ps.interval = w_iv; ps.out_js = 1;
+            ps.cands = w_cands; ps.cand_cs = nw; ps.cand_js = 1; ps.interval = t.w_iv; ps.out_js = 1;
             ps.cache = keep_planes ? &plane_w : nullptr;
             ps.scores_out = R.scores_of(round, 0); ps.scores_out_ld = nw; ps.best_out = R.best_of(round, 0);
             ps.prunable = ps.prunable_f32 = prunable; ps.scache = &slice; ps.host_sync_ok = memo_on;
@@ -3605,7 +3636,7 @@ int conv_impl(const p4v_conv_desc* d, const float* W, const float* bias, const f
             Pass ps{};
             setup(ps, false);
             ps.nj = 1; ps.j_mode = 0; ps.norm = 1.0 / ((double)L * oc);
-            ps.cands = a_cands; ps.cand_cs = 1; ps.cand_js = 0; ps.interval = a_iv; ps.out_js = 0;
+            ps.cands = a_cands; ps.cand_cs = 1; ps.cand_js = 0; ps.interval = t.a_iv; ps.out_js = 0;
             ps.cache = keep_planes ? &plane_a : nullptr;
             ps.scores_out = R.scores_of(round, 1); ps.scores_out_ld = nw; ps.best_out = R.best_of(round, 1);
             CHK(run_pass(c, ps));
@@ -3658,32 +3689,30 @@ int* group_mirror(hipStream_t st, int dev, int slot) {
     return p;
 }
 
+// one member = one p4v_*_calibrate call without tables: in = {weight, bias, x, raw_out, raw_grad} (MatMul: {A, B, raw_out, raw_grad})
 int run_group_member(const p4v_group_job& j, Ctx& c) {
     switch (j.kind) {
         case P4V_JOB_LINEAR: {
             const p4v_linear_desc* d = (const p4v_linear_desc*)j.desc;
             if (!j.in[0] || !j.in[2] || !j.in[3] || !j.mult || !j.out[0] || !j.out[1] || !j.workspace) return fail(P4V_ERR_INVALID, "group: linear member with a null pointer");
             if (d->has_bias && !j.in[1]) return fail(P4V_ERR_INVALID, "group: linear member has_bias set but bias is NULL");
-            return linear_impl(d, j.in[0], d->has_bias ? j.in[1] : nullptr, j.in[2], j.in[3], j.in[4], j.mult, j.out[0], j.out[1], nullptr, nullptr, c);
+            return linear_impl(d, {.W = j.in[0], .bias = d->has_bias ? j.in[1] : nullptr, .X = j.in[2], .O = j.in[3], .G = j.in[4], .mult = j.mult,
+                                   .w_iv = j.out[0], .a_iv = j.out[1]}, Stage{}, c);
         }
-        case P4V_JOB_MATMUL: {
-            const p4v_matmul_desc* d = (const p4v_matmul_desc*)j.desc;
+        case P4V_JOB_MATMUL: case P4V_JOB_MATMUL_BLOCKS: {
+            const p4v_matmul_blocks_desc* bd = j.kind == P4V_JOB_MATMUL_BLOCKS ? (const p4v_matmul_blocks_desc*)j.desc : nullptr;
+            const p4v_matmul_desc* d = bd ? &bd->mm : (const p4v_matmul_desc*)j.desc;
             if (!j.in[0] || !j.in[1] || !j.in[2] || !j.mult || !j.out[0] || !j.out[1] || !j.workspace) return fail(P4V_ERR_INVALID, "group: matmul member with a null pointer");
-            return matmul_impl(d, j.in[0], j.in[1], j.in[2], j.in[3], j.mult, j.out[0], j.out[1], j.out[2], nullptr, nullptr, c);
-        }
-        case P4V_JOB_MATMUL_BLOCKS: {
-            const p4v_matmul_blocks_desc* d = (const p4v_matmul_blocks_desc*)j.desc;
-            if (!j.in[0] || !j.in[1] || !j.in[2] || !j.mult || !j.out[0] || !j.out[1] || !j.workspace) return fail(P4V_ERR_INVALID, "group: matmul member with a null pointer");
-            if (d->n_V_A < 1 || d->n_H_A < 1 || d->n_V_B < 1 || d->n_H_B < 1) return fail(P4V_ERR_INVALID, "group: matmul member with a non-positive block count");
-            MatMulBlocks mb;
-            mb.nVA = d->n_V_A; mb.nHA = d->n_H_A; mb.nVB = d->n_V_B; mb.nHB = d->n_H_B;
-            return matmul_impl(&d->mm, j.in[0], j.in[1], j.in[2], j.in[3], j.mult, j.out[0], j.out[1], j.out[2], nullptr, nullptr, c, nullptr, Stage{}, &mb);
+            if (bd) CHK(blocks_check(bd, "group", "matmul member with a "));
+            return matmul_impl(d, {.A = j.in[0], .B = j.in[1], .O = j.in[2], .G = j.in[3], .mult = j.mult, .A_iv = j.out[0], .B_iv = j.out[1],
+                                   .split = j.out[2]}, Stage{}, c, bd ? blocks_of(bd) : MatMulBlocks{});
         }
         case P4V_JOB_CONV: {
             const p4v_conv_desc* d = (const p4v_conv_desc*)j.desc;
             if (!j.in[0] || !j.in[2] || !j.in[3] || !j.mult || !j.out[0] || !j.out[1] || !j.workspace) return fail(P4V_ERR_INVALID, "group: conv member with a null pointer");
             if (d->has_bias && !j.in[1]) return fail(P4V_ERR_INVALID, "group: conv member has_bias set but bias is NULL");
-            return conv_impl(d, j.in[0], d->has_bias ? j.in[1] : nullptr, j.in[2], j.in[3], j.in[4], j.mult, j.out[0], j.out[1], nullptr, nullptr, c);
+            return conv_impl(d, {.W = j.in[0], .bias = d->has_bias ? j.in[1] : nullptr, .X = j.in[2], .O = j.in[3], .G = j.in[4], .mult = j.mult,
+                                 .w_iv = j.out[0], .a_iv = j.out[1]}, Stage{}, c);
         }
         default: return fail(P4V_ERR_INVALID, "group: unknown member kind %d", j.kind);
     }
@@ -3701,37 +3730,38 @@ extern "C" {
 int p4v_version(void) { return P4V_VERSION; }
 const char* p4v_last_error(void) { return g_err.c_str(); }
 
+// The prologue of the entry points whose checks are only these, in this order: the required pointers, the bias the descriptor
+// announces, the workspace's alignment.  (The MatMul entry points and conv_search have checks of their own in between.)
+static int entry_checks(const char* who, bool present, bool bias_missing, const void* d_workspace, const char* bias_null = "d_bias is NULL") {
+    if (!present || !d_workspace) return fail(P4V_ERR_INVALID, "%s: null pointer", who);
+    if (bias_missing) return fail(P4V_ERR_INVALID, "%s: has_bias set but %s", who, bias_null);
+    return ws_aligned(d_workspace);
+}
+
 size_t p4v_linear_workspace_bytes(const p4v_linear_desc* desc) {
     if (!desc) return 0;
-    Ctx c{nullptr, Arena(nullptr, 0), true};   // dry run of the planner: counts, launches nothing
-    float* fwd = (desc->reserved & 4) ? (float*)16 : nullptr;   // bit 2: size the workspace for quant_forward only
-    if (linear_impl(desc, nullptr, nullptr, nullptr, nullptr, (const float*)1, nullptr, nullptr, nullptr, nullptr, nullptr, c, fwd) != 0) return 0;
-    return c.ws.peak + 4096;
+    Ctx c = Ctx::sizing();
+    return linear_impl(desc, LinearTensors{}, sizing_stage(desc->reserved), c) == 0 ? c.sized_bytes() : 0;
 }
 
 int p4v_linear_calibrate(const p4v_linear_desc* desc, const float* d_weight, const float* d_bias, const float* d_x,
                          const float* d_out, const float* d_grad, const float* d_mult, float* d_w_interval,
                          float* d_a_interval, float* d_scores, int32_t* d_best, void* d_workspace, size_t workspace_bytes,
                          void* stream) {
-    if (!desc || !d_weight || !d_x || !d_out || !d_mult || !d_w_interval || !d_a_interval || !d_workspace)
-        return fail(P4V_ERR_INVALID, "linear: null pointer");
-    if (desc->has_bias && !d_bias) return fail(P4V_ERR_INVALID, "linear: has_bias set but d_bias is NULL");
-    CHK(ws_aligned(d_workspace));
-    Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
-    return linear_impl(desc, d_weight, desc->has_bias ? d_bias : nullptr, d_x, d_out, d_grad, d_mult, d_w_interval,
-                       d_a_interval, d_scores, d_best, c);
+    CHK(entry_checks("linear", desc && d_weight && d_x && d_out && d_mult && d_w_interval && d_a_interval, desc && desc->has_bias && !d_bias, d_workspace));
+    Ctx c = Ctx::on(stream, d_workspace, workspace_bytes);
+    return linear_impl(desc, {.W = d_weight, .bias = desc->has_bias ? d_bias : nullptr, .X = d_x, .O = d_out, .G = d_grad, .mult = d_mult,
+                              .w_iv = d_w_interval, .a_iv = d_a_interval, .scores = d_scores, .best = d_best}, Stage{}, c);
 }
 
 int p4v_linear_quant_forward(const p4v_linear_desc* desc, const float* d_weight, const float* d_bias, const float* d_x,
                              const float* d_w_interval, const float* d_a_interval, float* d_out, void* d_workspace,
                              size_t workspace_bytes, void* stream) {
-    if (!desc || !d_weight || !d_x || !d_w_interval || !d_a_interval || !d_out || !d_workspace)
-        return fail(P4V_ERR_INVALID, "p4v_linear_quant_forward: null pointer");
-    if (desc->has_bias && !d_bias) return fail(P4V_ERR_INVALID, "p4v_linear_quant_forward: has_bias set but d_bias is null");
-    CHK(ws_aligned(d_workspace));
-    Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
-    return linear_impl(desc, d_weight, desc->has_bias ? d_bias : nullptr, d_x, nullptr, nullptr, nullptr,
-                       const_cast<float*>(d_w_interval), const_cast<float*>(d_a_interval), nullptr, nullptr, c, d_out);
+    CHK(entry_checks("p4v_linear_quant_forward", desc && d_weight && d_x && d_w_interval && d_a_interval && d_out, desc && desc->has_bias && !d_bias,
+                     d_workspace, "d_bias is null"));
+    Ctx c = Ctx::on(stream, d_workspace, workspace_bytes);
+    return linear_impl(desc, {.W = d_weight, .bias = desc->has_bias ? d_bias : nullptr, .X = d_x, .w_iv = const_cast<float*>(d_w_interval),
+                              .a_iv = const_cast<float*>(d_a_interval), .fwd_out = d_out}, Stage{ST_FWD}, c);
 }
 
 size_t p4v_mlp_workspace_bytes(const p4v_mlp_desc* desc) {
@@ -3742,18 +3772,18 @@ size_t p4v_mlp_workspace_bytes(const p4v_mlp_desc* desc) {
 int p4v_mlp_quant_forward(const p4v_mlp_desc* desc, const float* d_w1, const float* d_b1, const float* d_w2, const float* d_b2,
                           const float* d_x, const float* d_w1_interval, const float* d_a1_interval, const float* d_w2_interval,
                           const float* d_a2_interval, float* d_out, float* d_hidden, void* d_ws, size_t ws_bytes, void* stream) {
-    if (!desc || !d_w1 || !d_w2 || !d_x || !d_w1_interval || !d_a1_interval || !d_w2_interval || !d_a2_interval || !d_out || !d_ws)
-        return fail(P4V_ERR_INVALID, "p4v_mlp_quant_forward: null pointer");
-    if ((desc->fc1.has_bias && !d_b1) || (desc->fc2.has_bias && !d_b2))
-        return fail(P4V_ERR_INVALID, "p4v_mlp_quant_forward: has_bias set but the bias is null");
-    CHK(ws_aligned(d_ws));
+    CHK(entry_checks("p4v_mlp_quant_forward", desc && d_w1 && d_w2 && d_x && d_w1_interval && d_a1_interval && d_w2_interval && d_a2_interval && d_out,
+                     desc && ((desc->fc1.has_bias && !d_b1) || (desc->fc2.has_bias && !d_b2)), d_ws, "the bias is null"));
     // fc1's launches precede the planning of fc2's pass: the whole need is checked here, before the first of them
     size_t need = 0;
     CHK(mlp_sizing_run(desc, &need));
     if (ws_bytes < need) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", need);
-    Ctx c{(hipStream_t)stream, Arena(d_ws, ws_bytes), false};
-    return mlp_impl(desc, d_w1, desc->fc1.has_bias ? d_b1 : nullptr, d_w2, desc->fc2.has_bias ? d_b2 : nullptr, d_x, d_w1_interval,
-                    d_a1_interval, d_w2_interval, d_a2_interval, d_out, d_hidden, c);
+    Ctx c = Ctx::on(stream, d_ws, ws_bytes);
+    return mlp_impl(desc,
+                    {.W = d_w1, .bias = desc->fc1.has_bias ? d_b1 : nullptr, .X = d_x, .w_iv = const_cast<float*>(d_w1_interval),
+                     .a_iv = const_cast<float*>(d_a1_interval), .fwd_out = d_hidden},
+                    {.W = d_w2, .bias = desc->fc2.has_bias ? d_b2 : nullptr, .w_iv = const_cast<float*>(d_w2_interval),
+                     .a_iv = const_cast<float*>(d_a2_interval), .fwd_out = d_out}, c);
 }
 
 int p4v_matmul_quant_forward(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_A_interval,
@@ -3763,18 +3793,15 @@ int p4v_matmul_quant_forward(const p4v_matmul_desc* desc, const float* d_A, cons
         return fail(P4V_ERR_INVALID, "p4v_matmul_quant_forward: null pointer");
     if (desc->sos && !d_split) return fail(P4V_ERR_INVALID, "p4v_matmul_quant_forward: sos needs d_split");
     CHK(ws_aligned(d_workspace));
-    Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
-    return matmul_impl(desc, d_A, d_B, nullptr, nullptr, nullptr, const_cast<float*>(d_A_interval),
-                       const_cast<float*>(d_B_interval), const_cast<float*>(d_split), nullptr, nullptr, c, d_out);
+    Ctx c = Ctx::on(stream, d_workspace, workspace_bytes);
+    return matmul_impl(desc, {.A = d_A, .B = d_B, .A_iv = const_cast<float*>(d_A_interval), .B_iv = const_cast<float*>(d_B_interval),
+                              .split = const_cast<float*>(d_split), .fwd_out = d_out}, Stage{ST_FWD}, c);
 }
 
 size_t p4v_matmul_workspace_bytes(const p4v_matmul_desc* desc) {
     if (!desc) return 0;
-    Ctx c{nullptr, Arena(nullptr, 0), true};
-    float dummy = 0;
-    float* fwd = (desc->reserved & 4) ? (float*)16 : nullptr;
-    if (matmul_impl(desc, nullptr, nullptr, nullptr, (const float*)1, nullptr, nullptr, nullptr, &dummy, nullptr, nullptr, c, fwd) != 0) return 0;
-    return c.ws.peak + 4096;
+    Ctx c = Ctx::sizing();
+    return matmul_impl(desc, MatMulTensors{}, sizing_stage(desc->reserved), c) == 0 ? c.sized_bytes() : 0;
 }
 
 int p4v_matmul_calibrate(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_out,
@@ -3783,30 +3810,16 @@ int p4v_matmul_calibrate(const p4v_matmul_desc* desc, const float* d_A, const fl
     if (!desc || !d_A || !d_B || !d_out || !d_mult || !d_A_interval || !d_B_interval || !d_workspace)
         return fail(P4V_ERR_INVALID, "matmul: null pointer");
     CHK(ws_aligned(d_workspace));
-    Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
-    return matmul_impl(desc, d_A, d_B, d_out, d_grad, d_mult, d_A_interval, d_B_interval, d_split, d_scores, d_best, c);
+    Ctx c = Ctx::on(stream, d_workspace, workspace_bytes);
+    return matmul_impl(desc, {.A = d_A, .B = d_B, .O = d_out, .G = d_grad, .mult = d_mult, .A_iv = d_A_interval, .B_iv = d_B_interval,
+                              .split = d_split, .scores = d_scores, .best = d_best}, Stage{}, c);
 }
 
 // ---- MatMul with row / column sub-blocks: matmul_impl with the block counts (all 1: the head-wise path, launch for launch) ----
-static MatMulBlocks blocks_of(const p4v_matmul_blocks_desc* d, int v = 0, int h = 0) {
-    MatMulBlocks mb;
-    mb.nVA = d->n_V_A; mb.nHA = d->n_H_A; mb.nVB = d->n_V_B; mb.nHB = d->n_H_B; mb.v = v; mb.h = h;
-    return mb;
-}
-static int blocks_check(const p4v_matmul_blocks_desc* d, const char* who) {
-    if (d->n_V_A < 1 || d->n_H_A < 1 || d->n_V_B < 1 || d->n_H_B < 1) return fail(P4V_ERR_INVALID, "%s: non-positive block count", who);
-    return 0;
-}
-
 size_t p4v_matmul_blocks_workspace_bytes(const p4v_matmul_blocks_desc* desc) {
     if (!desc || blocks_check(desc, "p4v_matmul_blocks_workspace_bytes")) return 0;
-    Ctx c{nullptr, Arena(nullptr, 0), true};
-    float dummy = 0;
-    float* fwd = (desc->mm.reserved & 4) ? (float*)16 : nullptr;
-    const MatMulBlocks mb = blocks_of(desc);
-    if (matmul_impl(&desc->mm, nullptr, nullptr, nullptr, (const float*)1, nullptr, nullptr, nullptr, &dummy, nullptr, nullptr, c, fwd,
-                    Stage{}, &mb) != 0) return 0;
-    return c.ws.peak + 4096;
+    Ctx c = Ctx::sizing();
+    return matmul_impl(&desc->mm, MatMulTensors{}, sizing_stage(desc->mm.reserved), c, blocks_of(desc)) == 0 ? c.sized_bytes() : 0;
 }
 
 int p4v_matmul_blocks_calibrate(const p4v_matmul_blocks_desc* desc, const float* d_A, const float* d_B, const float* d_out,
@@ -3817,10 +3830,9 @@ int p4v_matmul_blocks_calibrate(const p4v_matmul_blocks_desc* desc, const float*
         return fail(P4V_ERR_INVALID, "p4v_matmul_blocks_calibrate: null pointer");
     CHK(blocks_check(desc, "p4v_matmul_blocks_calibrate"));
     CHK(ws_aligned(d_workspace));
-    Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
-    const MatMulBlocks mb = blocks_of(desc);
-    return matmul_impl(&desc->mm, d_A, d_B, d_out, d_grad, d_mult, d_A_interval, d_B_interval, d_split, d_scores, d_best, c, nullptr,
-                       Stage{}, &mb);
+    Ctx c = Ctx::on(stream, d_workspace, workspace_bytes);
+    return matmul_impl(&desc->mm, {.A = d_A, .B = d_B, .O = d_out, .G = d_grad, .mult = d_mult, .A_iv = d_A_interval, .B_iv = d_B_interval,
+                                   .split = d_split, .scores = d_scores, .best = d_best}, Stage{}, c, blocks_of(desc));
 }
 
 int p4v_amax_init_matmul_blocks(const p4v_matmul_blocks_desc* desc, const float* d_A, const float* d_B, float* d_A_interval,
@@ -3829,11 +3841,8 @@ int p4v_amax_init_matmul_blocks(const p4v_matmul_blocks_desc* desc, const float*
         return fail(P4V_ERR_INVALID, "p4v_amax_init_matmul_blocks: null pointer");
     CHK(blocks_check(desc, "p4v_amax_init_matmul_blocks"));
     CHK(ws_aligned(d_workspace));
-    Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
-    float dummy_split = 0;   // only checked for presence
-    const MatMulBlocks mb = blocks_of(desc);
-    return matmul_impl(&desc->mm, d_A, d_B, nullptr, nullptr, nullptr, d_A_interval, d_B_interval, &dummy_split, nullptr, nullptr, c,
-                       nullptr, Stage{ST_INIT, nullptr, nullptr}, &mb);
+    Ctx c = Ctx::on(stream, d_workspace, workspace_bytes);
+    return matmul_impl(&desc->mm, {.A = d_A, .B = d_B, .A_iv = d_A_interval, .B_iv = d_B_interval}, Stage{ST_INIT}, c, blocks_of(desc));
 }
 
 int p4v_matmul_blocks_search(const p4v_matmul_blocks_desc* desc, int32_t operand, int32_t v, int32_t h, const float* d_A,
@@ -3849,10 +3858,10 @@ int p4v_matmul_blocks_search(const p4v_matmul_blocks_desc* desc, int32_t operand
     const int nV = operand == 0 ? desc->n_V_A : desc->n_V_B, nH = operand == 0 ? desc->n_H_A : desc->n_H_B;
     if (v < 0 || v >= nV || h < 0 || h >= nH) return fail(P4V_ERR_INVALID, "p4v_matmul_blocks_search: block (%d, %d) outside the %d x %d blocks", v, h, nV, nH);
     CHK(ws_aligned(d_workspace));
-    Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
-    const MatMulBlocks mb = blocks_of(desc, v, h);
-    return matmul_impl(&desc->mm, d_A, d_B, d_out, d_grad, nullptr, d_A_interval, d_B_interval, const_cast<float*>(d_split), d_scores,
-                       d_best, c, nullptr, operand == 0 ? Stage{ST_S1, d_cands, nullptr} : Stage{ST_S2, nullptr, d_cands}, &mb);
+    Ctx c = Ctx::on(stream, d_workspace, workspace_bytes);
+    return matmul_impl(&desc->mm, {.A = d_A, .B = d_B, .O = d_out, .G = d_grad, .A_iv = d_A_interval, .B_iv = d_B_interval,
+                                   .split = const_cast<float*>(d_split), .scores = d_scores, .best = d_best},
+                       operand == 0 ? Stage{ST_S1, d_cands, nullptr} : Stage{ST_S2, nullptr, d_cands}, c, blocks_of(desc, v, h));
 }
 
 int p4v_matmul_blocks_quant_forward(const p4v_matmul_blocks_desc* desc, const float* d_A, const float* d_B,
@@ -3863,29 +3872,24 @@ int p4v_matmul_blocks_quant_forward(const p4v_matmul_blocks_desc* desc, const fl
     CHK(blocks_check(desc, "p4v_matmul_blocks_quant_forward"));
     if (desc->mm.sos && !d_split) return fail(P4V_ERR_INVALID, "p4v_matmul_blocks_quant_forward: sos needs d_split");
     CHK(ws_aligned(d_workspace));
-    Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
-    const MatMulBlocks mb = blocks_of(desc);
-    return matmul_impl(&desc->mm, d_A, d_B, nullptr, nullptr, nullptr, const_cast<float*>(d_A_interval),
-                       const_cast<float*>(d_B_interval), const_cast<float*>(d_split), nullptr, nullptr, c, d_out, Stage{}, &mb);
+    Ctx c = Ctx::on(stream, d_workspace, workspace_bytes);
+    return matmul_impl(&desc->mm, {.A = d_A, .B = d_B, .A_iv = const_cast<float*>(d_A_interval), .B_iv = const_cast<float*>(d_B_interval),
+                                   .split = const_cast<float*>(d_split), .fwd_out = d_out}, Stage{ST_FWD}, c, blocks_of(desc));
 }
 
 size_t p4v_conv_workspace_bytes(const p4v_conv_desc* desc) {
     if (!desc) return 0;
-    Ctx c{nullptr, Arena(nullptr, 0), true};
-    if (conv_impl(desc, nullptr, nullptr, nullptr, nullptr, (const float*)1, nullptr, nullptr, nullptr, nullptr, nullptr, c) != 0) return 0;
-    return c.ws.peak + 4096;
+    Ctx c = Ctx::sizing();
+    return conv_impl(desc, ConvTensors{}, Stage{}, c) == 0 ? c.sized_bytes() : 0;
 }
 
 int p4v_conv_calibrate(const p4v_conv_desc* desc, const float* d_weight, const float* d_bias, const float* d_x,
                        const float* d_out, const float* d_grad, const float* d_mult, float* d_w_interval, float* d_a_interval,
                        float* d_scores, int32_t* d_best, void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (!desc || !d_weight || !d_x || !d_out || !d_mult || !d_w_interval || !d_a_interval || !d_workspace)
-        return fail(P4V_ERR_INVALID, "conv: null pointer");
-    if (desc->has_bias && !d_bias) return fail(P4V_ERR_INVALID, "conv: has_bias set but d_bias is NULL");
-    CHK(ws_aligned(d_workspace));
-    Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
-    return conv_impl(desc, d_weight, desc->has_bias ? d_bias : nullptr, d_x, d_out, d_grad, d_mult, d_w_interval, d_a_interval,
-                     d_scores, d_best, c);
+    CHK(entry_checks("conv", desc && d_weight && d_x && d_out && d_mult && d_w_interval && d_a_interval, desc && desc->has_bias && !d_bias, d_workspace));
+    Ctx c = Ctx::on(stream, d_workspace, workspace_bytes);
+    return conv_impl(desc, {.W = d_weight, .bias = desc->has_bias ? d_bias : nullptr, .X = d_x, .O = d_out, .G = d_grad, .mult = d_mult,
+                            .w_iv = d_w_interval, .a_iv = d_a_interval, .scores = d_scores, .best = d_best}, Stage{}, c);
 }
 
 
@@ -3953,39 +3957,37 @@ int p4v_launch_counters(int64_t* out4, int reset) {
 // ---- granular entry points: one part of calibration_step2 per call ----------
 int p4v_amax_init_linear(const p4v_linear_desc* desc, const float* d_weight, const float* d_x, float* d_w_interval,
                          float* d_a_interval, void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (!desc || !d_weight || !d_x || !d_w_interval || !d_a_interval || !d_workspace)
-        return fail(P4V_ERR_INVALID, "p4v_amax_init_linear: null pointer");
-    CHK(ws_aligned(d_workspace));
-    Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
-    return linear_impl(desc, d_weight, nullptr, d_x, nullptr, nullptr, nullptr, d_w_interval, d_a_interval, nullptr, nullptr, c,
-                       nullptr, Stage{ST_INIT, nullptr, nullptr});
+    CHK(entry_checks("p4v_amax_init_linear", desc && d_weight && d_x && d_w_interval && d_a_interval, false, d_workspace));
+    Ctx c = Ctx::on(stream, d_workspace, workspace_bytes);
+    return linear_impl(desc, {.W = d_weight, .X = d_x, .w_iv = d_w_interval, .a_iv = d_a_interval}, Stage{ST_INIT}, c);
+}
+
+// one side's search on the caller's candidate table: `sg` says which
+static int linear_search(const char* who, const Stage& sg, const p4v_linear_desc* desc, const float* d_weight, const float* d_bias,
+                         const float* d_x, const float* d_out, const float* d_grad, const float* d_w_interval, const float* d_a_interval,
+                         float* d_scores, int32_t* d_best, void* d_workspace, size_t workspace_bytes, void* stream) {
+    CHK(entry_checks(who, desc && d_weight && d_x && d_out && (sg.cands1 || sg.cands2) && d_w_interval && d_a_interval,
+                     desc && desc->has_bias && !d_bias, d_workspace));
+    Ctx c = Ctx::on(stream, d_workspace, workspace_bytes);
+    return linear_impl(desc, {.W = d_weight, .bias = desc->has_bias ? d_bias : nullptr, .X = d_x, .O = d_out, .G = d_grad,
+                              .w_iv = const_cast<float*>(d_w_interval), .a_iv = const_cast<float*>(d_a_interval), .scores = d_scores,
+                              .best = d_best}, sg, c);
 }
 
 int p4v_linear_search_w(const p4v_linear_desc* desc, const float* d_weight, const float* d_bias, const float* d_x,
                         const float* d_out, const float* d_grad, const float* d_w_cands, float* d_w_interval,
                         const float* d_a_interval, float* d_scores, int32_t* d_best, void* d_workspace,
                         size_t workspace_bytes, void* stream) {
-    if (!desc || !d_weight || !d_x || !d_out || !d_w_cands || !d_w_interval || !d_a_interval || !d_workspace)
-        return fail(P4V_ERR_INVALID, "p4v_linear_search_w: null pointer");
-    if (desc->has_bias && !d_bias) return fail(P4V_ERR_INVALID, "p4v_linear_search_w: has_bias set but d_bias is NULL");
-    CHK(ws_aligned(d_workspace));
-    Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
-    return linear_impl(desc, d_weight, desc->has_bias ? d_bias : nullptr, d_x, d_out, d_grad, nullptr, d_w_interval,
-                       const_cast<float*>(d_a_interval), d_scores, d_best, c, nullptr, Stage{ST_S1, d_w_cands, nullptr});
+    return linear_search("p4v_linear_search_w", Stage{ST_S1, d_w_cands, nullptr}, desc, d_weight, d_bias, d_x, d_out, d_grad, d_w_interval,
+                         d_a_interval, d_scores, d_best, d_workspace, workspace_bytes, stream);
 }
 
 int p4v_linear_search_a(const p4v_linear_desc* desc, const float* d_weight, const float* d_bias, const float* d_x,
                         const float* d_out, const float* d_grad, const float* d_a_cands, const float* d_w_interval,
                         float* d_a_interval, float* d_scores, int32_t* d_best, void* d_workspace, size_t workspace_bytes,
                         void* stream) {
-    if (!desc || !d_weight || !d_x || !d_out || !d_a_cands || !d_w_interval || !d_a_interval || !d_workspace)
-        return fail(P4V_ERR_INVALID, "p4v_linear_search_a: null pointer");
-    if (desc->has_bias && !d_bias) return fail(P4V_ERR_INVALID, "p4v_linear_search_a: has_bias set but d_bias is NULL");
-    CHK(ws_aligned(d_workspace));
-    Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
-    return linear_impl(desc, d_weight, desc->has_bias ? d_bias : nullptr, d_x, d_out, d_grad, nullptr,
-                       const_cast<float*>(d_w_interval), d_a_interval, d_scores, d_best, c, nullptr,
-                       Stage{ST_S2, nullptr, d_a_cands});
+    return linear_search("p4v_linear_search_a", Stage{ST_S2, nullptr, d_a_cands}, desc, d_weight, d_bias, d_x, d_out, d_grad, d_w_interval,
+                         d_a_interval, d_scores, d_best, d_workspace, workspace_bytes, stream);
 }
 
 int p4v_amax_init_matmul(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, float* d_A_interval,
@@ -3993,10 +3995,8 @@ int p4v_amax_init_matmul(const p4v_matmul_desc* desc, const float* d_A, const fl
     if (!desc || !d_A || !d_B || !d_A_interval || !d_B_interval || !d_workspace)
         return fail(P4V_ERR_INVALID, "p4v_amax_init_matmul: null pointer");
     CHK(ws_aligned(d_workspace));
-    Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
-    float dummy_split = 0;   // only checked for presence
-    return matmul_impl(desc, d_A, d_B, nullptr, nullptr, nullptr, d_A_interval, d_B_interval, &dummy_split, nullptr, nullptr, c,
-                       nullptr, Stage{ST_INIT, nullptr, nullptr});
+    Ctx c = Ctx::on(stream, d_workspace, workspace_bytes);
+    return matmul_impl(desc, {.A = d_A, .B = d_B, .A_iv = d_A_interval, .B_iv = d_B_interval}, Stage{ST_INIT}, c);
 }
 
 int p4v_matmul_search_A(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_out,
@@ -4006,9 +4006,9 @@ int p4v_matmul_search_A(const p4v_matmul_desc* desc, const float* d_A, const flo
         return fail(P4V_ERR_INVALID, "p4v_matmul_search_A: null pointer");
     if (desc->sos) return fail(P4V_ERR_INVALID, "p4v_matmul_search_A: the split-of-softmax class searches its split (p4v_sos_search_split)");
     CHK(ws_aligned(d_workspace));
-    Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
-    return matmul_impl(desc, d_A, d_B, d_out, d_grad, nullptr, d_A_interval, const_cast<float*>(d_B_interval), nullptr,
-                       d_scores, d_best, c, nullptr, Stage{ST_S1, d_A_cands, nullptr});
+    Ctx c = Ctx::on(stream, d_workspace, workspace_bytes);
+    return matmul_impl(desc, {.A = d_A, .B = d_B, .O = d_out, .G = d_grad, .A_iv = d_A_interval, .B_iv = const_cast<float*>(d_B_interval),
+                              .scores = d_scores, .best = d_best}, Stage{ST_S1, d_A_cands, nullptr}, c);
 }
 
 int p4v_sos_search_split(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_out,
@@ -4018,9 +4018,9 @@ int p4v_sos_search_split(const p4v_matmul_desc* desc, const float* d_A, const fl
         return fail(P4V_ERR_INVALID, "p4v_sos_search_split: null pointer");
     if (!desc->sos) return fail(P4V_ERR_INVALID, "p4v_sos_search_split: descriptor is not a split-of-softmax matmul");
     CHK(ws_aligned(d_workspace));
-    Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
-    return matmul_impl(desc, d_A, d_B, d_out, d_grad, nullptr, d_A_interval, nullptr, d_split, d_scores, d_best, c, nullptr,
-                       Stage{ST_S1, nullptr, nullptr});
+    Ctx c = Ctx::on(stream, d_workspace, workspace_bytes);
+    return matmul_impl(desc, {.A = d_A, .B = d_B, .O = d_out, .G = d_grad, .A_iv = d_A_interval, .split = d_split, .scores = d_scores,
+                              .best = d_best}, Stage{ST_S1}, c);
 }
 
 int p4v_matmul_search_B(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_out,
@@ -4031,19 +4031,16 @@ int p4v_matmul_search_B(const p4v_matmul_desc* desc, const float* d_A, const flo
         return fail(P4V_ERR_INVALID, "p4v_matmul_search_B: null pointer");
     if (desc->sos && !d_split) return fail(P4V_ERR_INVALID, "p4v_matmul_search_B: sos needs d_split");
     CHK(ws_aligned(d_workspace));
-    Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
-    return matmul_impl(desc, d_A, d_B, d_out, d_grad, nullptr, const_cast<float*>(d_A_interval), d_B_interval,
-                       const_cast<float*>(d_split), d_scores, d_best, c, nullptr, Stage{ST_S2, nullptr, d_B_cands});
+    Ctx c = Ctx::on(stream, d_workspace, workspace_bytes);
+    return matmul_impl(desc, {.A = d_A, .B = d_B, .O = d_out, .G = d_grad, .A_iv = const_cast<float*>(d_A_interval), .B_iv = d_B_interval,
+                              .split = const_cast<float*>(d_split), .scores = d_scores, .best = d_best}, Stage{ST_S2, nullptr, d_B_cands}, c);
 }
 
 int p4v_amax_init_conv(const p4v_conv_desc* desc, const float* d_weight, const float* d_x, float* d_w_interval,
                        float* d_a_interval, void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (!desc || !d_weight || !d_x || !d_w_interval || !d_a_interval || !d_workspace)
-        return fail(P4V_ERR_INVALID, "p4v_amax_init_conv: null pointer");
-    CHK(ws_aligned(d_workspace));
-    Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
-    return conv_impl(desc, d_weight, nullptr, d_x, nullptr, nullptr, nullptr, d_w_interval, d_a_interval, nullptr, nullptr, c,
-                     Stage{ST_INIT, nullptr, nullptr});
+    CHK(entry_checks("p4v_amax_init_conv", desc && d_weight && d_x && d_w_interval && d_a_interval, false, d_workspace));
+    Ctx c = Ctx::on(stream, d_workspace, workspace_bytes);
+    return conv_impl(desc, {.W = d_weight, .X = d_x, .w_iv = d_w_interval, .a_iv = d_a_interval}, Stage{ST_INIT}, c);
 }
 
 static int conv_search(const char* who, int want_channelwise, int stage, const p4v_conv_desc* desc, const float* d_weight,
@@ -4056,9 +4053,10 @@ static int conv_search(const char* who, int want_channelwise, int stage, const p
     if (want_channelwise >= 0 && (desc->channelwise != 0) != (want_channelwise != 0))
         return fail(P4V_ERR_INVALID, "%s: descriptor.channelwise does not match the entry point", who);
     CHK(ws_aligned(d_workspace));
-    Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
-    return conv_impl(desc, d_weight, desc->has_bias ? d_bias : nullptr, d_x, d_out, d_grad, nullptr, d_w_interval, d_a_interval,
-                     d_scores, d_best, c, stage == ST_S1 ? Stage{ST_S1, d_cands, nullptr} : Stage{ST_S2, nullptr, d_cands});
+    Ctx c = Ctx::on(stream, d_workspace, workspace_bytes);
+    return conv_impl(desc, {.W = d_weight, .bias = desc->has_bias ? d_bias : nullptr, .X = d_x, .O = d_out, .G = d_grad, .w_iv = d_w_interval,
+                            .a_iv = d_a_interval, .scores = d_scores, .best = d_best},
+                     stage == ST_S1 ? Stage{ST_S1, d_cands, nullptr} : Stage{ST_S2, nullptr, d_cands}, c);
 }
 
 int p4v_conv_search_w_channelwise(const p4v_conv_desc* desc, const float* d_weight, const float* d_bias, const float* d_x,
@@ -4090,7 +4088,7 @@ int p4v_score_argmax_gather(const float* d_scores, int32_t eq_n, int32_t n_block
                             int32_t* d_best, void* stream) {
     if (!d_scores || !d_cands || !d_interval || eq_n <= 0 || n_blocks <= 0)
         return fail(P4V_ERR_INVALID, "p4v_score_argmax_gather: bad argument");
-    Ctx c{(hipStream_t)stream, Arena(nullptr, 0), false};
+    Ctx c = Ctx::on(stream, nullptr, 0);
     SelectParams sl{d_scores, eq_n, n_blocks, d_cands, n_blocks, 1, 0, d_interval, 1, 0, nullptr, 0.0f, nullptr, 0, d_best};
     return launch_select(c, sl);
 }
@@ -4099,7 +4097,7 @@ int p4v_quantize_i8(const float* d_x, int64_t rows, int64_t cols, int64_t cols_p
                     int64_t rows_per_scale, int32_t lo, int32_t hi, int8_t* d_q, void* stream) {
     if (!d_x || !d_scales || !d_q || rows <= 0 || cols <= 0 || cols_padded % 64 || cols_padded < cols || rows_per_scale <= 0)
         return fail(P4V_ERR_INVALID, "quantize_i8: bad argument");
-    Ctx c{(hipStream_t)stream, Arena(nullptr, 0), false};
+    Ctx c = Ctx::on(stream, nullptr, 0);
     PackParams p = pack2d(d_x, rows, cols, cols);
     p.Rp = (int)rows; p.Kp = (int)cols_padded; p.dst = d_q; p.C = 1;
     p.scales = d_scales; p.sc_cs = 0; p.blk_mode = 1; p.blk_div = (int)rows_per_scale;
@@ -4252,10 +4250,9 @@ int p4v_debug_sos_sweep(const p4v_matmul_desc* desc, const float* d_A, const flo
     float* d_split = nullptr;                       // (the sweep selects nothing: split and interval go to scratch)
     CHK(ws_aligned(d_workspace));
     HIPCHK(hipMalloc(&d_split, 2 * sizeof(float)));
-    Ctx c{(hipStream_t)stream, Arena(d_workspace, workspace_bytes), false};
+    Ctx c = Ctx::on(stream, d_workspace, workspace_bytes);
     g_sos_debug = &dbg;
-    const int rc = matmul_impl(desc, d_A, d_B, d_out, d_grad, nullptr, d_split + 1, nullptr, d_split, nullptr, nullptr, c, nullptr,
-                               Stage{ST_S1, nullptr, nullptr});
+    const int rc = matmul_impl(desc, {.A = d_A, .B = d_B, .O = d_out, .G = d_grad, .A_iv = d_split + 1, .split = d_split}, Stage{ST_S1}, c);
     g_sos_debug = nullptr;
     (void)hipFree(d_split);
     return rc;
@@ -4291,7 +4288,7 @@ int p4v_debug_pack_dual(const float* d_x, long rows, long cols, long cols_padded
         p1.lo = 0; p1.hi = hi; p2.lo = lo; p2.hi = 0; p2.scales = nullptr; p2.neg_scale = const_scale;
     }
     if (!dual_pack_ok(p1, p2)) return fail(P4V_ERR_INVALID, "p4v_debug_pack_dual: not a dual pair");
-    Ctx c{(hipStream_t)stream, Arena(nullptr, 0), false};
+    Ctx c = Ctx::on(stream, nullptr, 0);
     const long total = rows * (cols_padded / 16);
     if (total >= (1L << 31)) return fail(P4V_ERR_UNSUPPORTED, "p4v_debug_pack_dual: plane too large");
     return enqueue(c, KERN(PackDualParams, k_pack_dual), dim3((unsigned)std::min<long>(cdiv(total, 256), 256L * 64)), dim3(256), 0,
@@ -4305,7 +4302,7 @@ int p4v_debug_pack_cands(const float* d_x, long rows, long cols, long rows_padde
         layout < 0 || layout > 3 || (layout == 3 && rows_padded % 64) || lo > hi || lo < -128 || hi > 127 || n_cands <= 0 ||
         (d_done && !d_crange) || (live_max >= 0 && !d_crange))
         return fail(P4V_ERR_INVALID, "p4v_debug_pack_cands: bad argument");
-    Ctx c{(hipStream_t)stream, Arena(nullptr, 0), false};
+    Ctx c = Ctx::on(stream, nullptr, 0);
     cvt_bias(c);
     PackParams p = pack2d(d_x, rows, cols, cols);
     p.Rp = (int)rows_padded; p.Kp = (int)cols_padded; p.dst = d_q; p.C = n_cands; p.c_inner = layout;
@@ -4332,7 +4329,7 @@ int p4v_debug_gather_im2col(int batch, int in_channels, int height, int width, i
     p.fw = fw; p.L = fh * fw;
     p.Z = 1; p.s_z = 0; p.R = batch * fh * fw; p.K = in_channels * kernel_h * kernel_w; p.nblk_r = 1; p.nblk_k = 1;
     p.mode = PACK_RAW;
-    Ctx c{(hipStream_t)stream, Arena(nullptr, 0), false};
+    Ctx c = Ctx::on(stream, nullptr, 0);
     const long total = (long)k * p.K;
     return enqueue(c, KERN(GatherIm2colParams, k_gather_im2col), dim3((unsigned)std::min<long>(cdiv(total, 256), 256L * 16)), dim3(256), 0,
                    GatherIm2colParams{p, d_idx, k, d_dst});
@@ -4346,7 +4343,7 @@ int p4v_debug_prep_epi6(const float* d_o, const float* d_wt, const float* d_bias
     pe.O = d_o; pe.Wt = d_wt ? d_wt : d_o; pe.bias = d_bias; pe.o_ss = o_ss; pe.o_ts = o_ts; pe.SR = sr; pe.TR = tr;
     pe.bias_on_t = bias_on_t ? 1 : 0; pe.wt_mode = wt_mode; pe.transposed = transposed ? 1 : 0;
     pe.stiles = cdiv(sr, 256); pe.ttiles = cdiv(tr, 64); pe.E = d_e;
-    Ctx c{(hipStream_t)stream, Arena(nullptr, 0), false};
+    Ctx c = Ctx::on(stream, nullptr, 0);
     return enqueue(c, KERN(PrepEpi6Params, k_prep_epi6), dim3((unsigned)std::min<long>((long)pe.stiles * pe.ttiles, 256L * 32)), dim3(256), 0, pe);
 }
 
@@ -4360,7 +4357,7 @@ int p4v_pack_plane_i8(const p4v_plane_desc* d, const float* d_x, const float* d_
     if (d->mode != P4V_PLANE_SYM && !d_scales) return fail(P4V_ERR_INVALID, "p4v_pack_plane_i8: split-of-softmax planes need d_scales = &split");
     if (d->mode == P4V_PLANE_SYM && d_scales && d->rows_per_scale <= 0) return fail(P4V_ERR_INVALID, "p4v_pack_plane_i8: rows_per_scale");
     if (d->lo < -128 || d->hi > 127 || d->qmax < 2 || d->qmax > 128) return fail(P4V_ERR_INVALID, "p4v_pack_plane_i8: grid wider than int8");
-    Ctx c{(hipStream_t)stream, Arena(nullptr, 0), false};
+    Ctx c = Ctx::on(stream, nullptr, 0);
     cvt_bias(c);     // (first use of the process: the conversion quant16_sat8 relies on is probed, into a scratch of the library's own)
     PackParams p = pack2d(d_x, d->rows, d->cols, d->cols);
     p.Rp = (int)d->rows; p.Kp = (int)d->cols_padded; p.dst = d_q; p.C = 1;

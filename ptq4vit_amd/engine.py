@@ -194,7 +194,8 @@ def linear_job(*, weight, bias, x, out, grad, w_bit, a_bit, metric, eq_alpha, eq
     N = weight.shape[0]
     d = _lib.LinearDesc(batch, tokens, K, N, n_V, n_H, n_a, w_bit, a_bit, metric_id(metric), eq_n, search_round,
                         int(postgelu), int(init_layerwise), int(bias is not None),
-                        int(force_f32) | (0 if memoize else 2) | (0 if prune else 8))
+                        (_lib.RESERVED_FP32_PLANES if force_f32 else 0) | (0 if memoize else _lib.RESERVED_NO_MEMO) |
+                        (0 if prune else _lib.RESERVED_NO_PRUNE))
     need = _need(lib.p4v_linear_workspace_bytes, d, "p4v_linear_workspace_bytes")
     mult = candidate_multipliers(eq_alpha, eq_beta, eq_n, dev)
     w_iv = torch.empty(n_V * n_H, dtype=torch.float32, device=dev)
@@ -220,7 +221,7 @@ def linear_quant_forward(*, weight, bias, x, w_interval, a_interval, w_bit, a_bi
     tokens = x.numel() // (batch * K)
     N = weight.shape[0]
     d = _lib.LinearDesc(batch, tokens, K, N, n_V, n_H, n_a, w_bit, a_bit, metric_id("L2_norm"), 1, 1,
-                        int(postgelu), 0, int(bias is not None), 4)
+                        int(postgelu), 0, int(bias is not None), _lib.RESERVED_FORWARD_ONLY)
     need = lib.p4v_linear_workspace_bytes(C.byref(d))
     if need == 0:
         _lib.check(-2, "p4v_linear_workspace_bytes")
@@ -239,7 +240,7 @@ def _mlp_layer_desc(batch, tokens, layer):
     w = layer["weight"]
     return _lib.LinearDesc(batch, tokens, w.shape[1], w.shape[0], layer["n_V"], layer.get("n_H", 1), layer.get("n_a", 1),
                            layer["w_bit"], layer["a_bit"], metric_id("L2_norm"), 1, 1, int(bool(layer.get("postgelu", False))), 0,
-                           int(layer.get("bias") is not None), 4)
+                           int(layer.get("bias") is not None), _lib.RESERVED_FORWARD_ONLY)
 
 
 def mlp_quant_forward(*, x, fc1, fc2, want_hidden=False, want_planes=False):
@@ -293,7 +294,7 @@ def matmul_quant_forward(*, A, B, A_interval, B_interval, split, A_bit, B_bit, s
         d.a_stride[i] = A.stride(i)
         d.b_stride[i] = B.stride(i)
     d.A_bit, d.B_bit, d.metric, d.eq_n, d.search_round = A_bit, B_bit, metric_id("L2_norm"), 1, 1
-    d.sos, d.init_layerwise, d.reserved = int(sos), 0, 4
+    d.sos, d.init_layerwise, d.reserved = int(sos), 0, _lib.RESERVED_FORWARD_ONLY
     need = lib.p4v_matmul_workspace_bytes(C.byref(d))
     if need == 0:
         _lib.check(-2, "p4v_matmul_workspace_bytes")
@@ -338,7 +339,7 @@ def matmul_blocks_quant_forward(*, A, B, A_interval, B_interval, split, A_bit, B
     lib = _lib.load()
     dev = device_of(A, B)
     A, B = to_dev(A, dev), to_dev(B, dev)
-    bd, d = _matmul_desc(A, B, A_bit, B_bit, "L2_norm", 1, 1, sos, 0, 4, blocks, wrap=True)
+    bd, d = _matmul_desc(A, B, A_bit, B_bit, "L2_norm", 1, 1, sos, 0, _lib.RESERVED_FORWARD_ONLY, blocks, wrap=True)
     b, H, M, _ = A.shape
     need = _need(lib.p4v_matmul_blocks_workspace_bytes, bd, "p4v_matmul_blocks_workspace_bytes")
     ws = workspace(dev, need)
@@ -384,7 +385,7 @@ def matmul_job(*, A, B, out, grad, A_bit, B_bit, metric, eq_alpha, eq_beta, eq_n
         d.a_stride[i] = A.stride(i)
         d.b_stride[i] = B.stride(i)
     d.A_bit, d.B_bit, d.metric, d.eq_n, d.search_round = A_bit, B_bit, metric_id(metric), eq_n, search_round
-    d.sos, d.init_layerwise, d.reserved = int(sos), int(init_layerwise), (0 if prune else 8)
+    d.sos, d.init_layerwise, d.reserved = int(sos), int(init_layerwise), (0 if prune else _lib.RESERVED_NO_PRUNE)
     need = _need(lib.p4v_matmul_workspace_bytes, d, "p4v_matmul_workspace_bytes")
     mult = candidate_multipliers(eq_alpha, eq_beta, eq_n, dev)
     A_iv = torch.empty(1 if sos else H, dtype=torch.float32, device=dev)
@@ -412,7 +413,7 @@ def conv_job(*, weight, bias, x, out, grad, stride, padding, dilation, w_bit, a_
     oc, _, kh, kw = weight.shape
     d = _lib.ConvDesc(b, ic, H, W, oc, kh, kw, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1],
                       w_bit, a_bit, metric_id(metric), eq_n, search_round, int(channelwise), int(init_layerwise),
-                      int(bias is not None), 0 if prune else 8)
+                      int(bias is not None), 0 if prune else _lib.RESERVED_NO_PRUNE)
     need = _need(lib.p4v_conv_workspace_bytes, d, "p4v_conv_workspace_bytes")
     mult = candidate_multipliers(eq_alpha, eq_beta, eq_n, dev)
     nw = oc if channelwise else 1
@@ -482,7 +483,7 @@ class LinearStepper(_Stepper):
         """One granular search call; `block`: the step of that column / activation block alone (desc.reserved bits 8..11), whose
         score table the call then returns -- None: every block in turn, the tables of block 0."""
         base = self.d.reserved
-        self.d.reserved = base | (0 if block is None else (int(block) + 1) << 8)
+        self.d.reserved = base | _lib.reserved_block(block)
         try:
             self._call(name, *args)
         finally:

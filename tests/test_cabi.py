@@ -230,3 +230,113 @@ def test_misaligned_workspace_pointer_is_refused_on_the_host(lib):
     jobs = (_lib.GroupJob * 1)()
     jobs[0].kind, jobs[0].desc, jobs[0].workspace, jobs[0].workspace_bytes = _lib.JOB_LINEAR, C.cast(C.pointer(ld), C.c_void_p), 72, 1 << 20
     assert lib.p4v_calibrate_group(jobs, 1, null, null) == -1 and b"aligned" in lib.p4v_last_error()
+
+
+# ---- required pointers (include/ptq4vit_hip.h): every workspace-taking entry point refuses a missing one on the host -----------------
+# (entry point, descriptor, integer arguments behind the descriptor, the pointer arguments in the header's order; "?name": optional)
+def _required_pointer_table():
+    from ptq4vit_amd import _lib
+    ld, cd, cl = _linear_desc(2, 64, 192, 128), _conv_desc(a_bit=8), _conv_desc(channelwise=False)
+    md, sd = _matmul_desc(49, 64, 49), _matmul_desc(49, 49, 64, sos=True)
+    bd = _matmul_desc(13, 8, 13, batch=4, heads=3, blocks=(2, 2, 2, 3))
+    bsd = _matmul_desc(13, 13, 8, batch=4, heads=3, sos=True, blocks=(1, 1, 2, 2))
+    mlp = _lib.MlpDesc()
+    mlp.fc1, mlp.fc2 = _linear_desc(2, 64, 64, 256), _linear_desc(2, 64, 256, 64, postgelu=True)
+    lin_search = "weight bias x out grad cands w_interval a_interval ?scores ?best"
+    mm_cal = "A B out grad mult A_interval B_interval split ?scores ?best"
+    return [
+        ("p4v_linear_calibrate", ld, (), "weight bias x out grad mult w_interval a_interval ?scores ?best"),
+        ("p4v_matmul_calibrate", sd, (), mm_cal), ("p4v_matmul_blocks_calibrate", bsd, (), mm_cal),
+        ("p4v_conv_calibrate", cd, (), "weight bias x out grad mult w_interval a_interval ?scores ?best"),
+        ("p4v_linear_quant_forward", ld, (), "weight bias x w_interval a_interval out"),
+        ("p4v_matmul_quant_forward", sd, (), "A B A_interval B_interval split out"),
+        ("p4v_matmul_blocks_quant_forward", bsd, (), "A B A_interval B_interval split out"),
+        ("p4v_mlp_quant_forward", mlp, (), "w1 bias1 w2 bias2 x w1_interval a1_interval w2_interval a2_interval out ?hidden"),
+        ("p4v_amax_init_linear", ld, (), "weight x w_interval a_interval"),
+        ("p4v_linear_search_w", ld, (), lin_search), ("p4v_linear_search_a", ld, (), lin_search),
+        ("p4v_amax_init_matmul", md, (), "A B A_interval B_interval"),
+        ("p4v_matmul_search_A", md, (), "A B out grad cands A_interval B_interval ?scores ?best"),
+        ("p4v_sos_search_split", sd, (), "A B out grad split A_interval ?scores ?best"),
+        ("p4v_matmul_search_B", sd, (), "A B out grad cands A_interval split B_interval ?scores ?best"),
+        ("p4v_amax_init_matmul_blocks", bd, (), "A B A_interval B_interval"),
+        ("p4v_matmul_blocks_search", bsd, (1, 0, 0), "A B out grad cands A_interval B_interval split ?scores ?best"),
+        ("p4v_amax_init_conv", cd, (), "weight x w_interval a_interval"),
+        ("p4v_conv_search_w_channelwise", cd, (), lin_search), ("p4v_conv_search_w_layerwise", cl, (), lin_search),
+        ("p4v_conv_search_a", cd, (), lin_search),
+    ]
+
+
+def _missing_says(name, missing):
+    """The message of `name` with `missing` NULL, word for word.  Every descriptor of the table has a bias, the hessian metric and --
+    where the header asks for d_split -- the split-of-softmax class.  The three head-wise *_calibrate entry points and the checks
+    inside the engine name the module, every other check the entry point."""
+    module = "conv" if "conv" in name else "matmul" if ("matmul" in name or "sos" in name) else "linear"
+    who = module if name in ("p4v_linear_calibrate", "p4v_matmul_calibrate", "p4v_conv_calibrate") else name
+    if missing in ("bias", "bias1", "bias2"):
+        return who + (": has_bias set but the bias is null" if "mlp" in name else ": has_bias set but d_bias is null" if "forward" in name else
+                      ": has_bias set but d_bias is NULL")
+    if missing == "grad":
+        return module + ": hessian metric needs raw_grad" + (" (linear.py:418)" if module == "linear" else "")
+    if missing == "split" and name != "p4v_sos_search_split":
+        return ("matmul" if name.endswith("_calibrate") else name) + ": sos needs d_split"
+    return who + ": null pointer"
+
+
+def test_every_required_pointer_is_checked_before_any_launch(lib):
+    """One at a time, every pointer include/ptq4vit_hip.h documents as required is NULL: P4V_ERR_INVALID, with the entry point's own
+    message, before anything is launched (no GPU here).  The other pointers are fakes that are never dereferenced."""
+    from ptq4vit_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "ptq4vit_hip.h")).read()
+    one, null = C.c_void_p(64), C.c_void_p(0)
+    table = _required_pointer_table()
+    with_ws = {s for s in _lib.EXPORTS if s != "p4v_calibrate_group" and not s.endswith("_workspace_bytes") and
+               re.search(r"\b%s\s*\([^;]*\bd_(workspace|ws)\b" % s, hdr)}
+    assert with_ws == {name for name, *_ in table}, with_ws ^ {name for name, *_ in table}
+    for name, desc, ints, names in table:
+        fn, names = getattr(lib, name), names.split()
+        # (the header's parameter list has as many pointers as the table's row)
+        proto = re.search(r"\b%s\s*\(([^;]*)\)\s*;" % name, hdr).group(1)
+        assert proto.count("*") == 1 + len(names) + 2, (name, proto)       # desc, the tensors, workspace, stream
+        def call(missing):
+            args = [null if n.lstrip("?") == missing else one for n in names]
+            return fn(None if missing == "desc" else C.byref(desc), *ints, *args, null if missing == "workspace" else one, 1 << 30, null)
+        for missing in ["desc", "workspace"] + [n for n in names if not n.startswith("?")]:
+            rc, msg = call(missing), lib.p4v_last_error().decode()
+            assert rc == -1 and msg == _missing_says(name, missing), (name, missing, rc, msg)
+    # the fused MLP forward takes its workspace as d_ws: below the 16-byte alignment it is refused like every d_workspace
+    name, desc, ints, names = next(r for r in table if r[0] == "p4v_mlp_quant_forward")
+    assert lib.p4v_mlp_quant_forward(C.byref(desc), *[one] * len(names.split()), C.c_void_p(72), 1 << 30, null) == -1
+    assert b"aligned" in lib.p4v_last_error(), lib.p4v_last_error()
+
+
+def test_sizing_refuses_null_and_unsupported_descriptors(lib):
+    """*_workspace_bytes(NULL) and an unsupported descriptor return 0 (the latter with its message), forward-only sizing included."""
+    from ptq4vit_amd import _lib
+    for q in ("p4v_linear_workspace_bytes", "p4v_matmul_workspace_bytes", "p4v_matmul_blocks_workspace_bytes", "p4v_conv_workspace_bytes",
+              "p4v_mlp_workspace_bytes"):
+        assert getattr(lib, q)(None) == 0, q
+    for reserved in (0, 4):
+        bad = _linear_desc(2, 64, 192, 128, n_V=5, reserved=reserved)               # 128 % 5 != 0
+        assert lib.p4v_linear_workspace_bytes(C.byref(bad)) == 0 and b"must divide" in lib.p4v_last_error()
+        bad = _matmul_desc(49, 64, 49, reserved=reserved)
+        bad.A_bit = 9
+        assert lib.p4v_matmul_workspace_bytes(C.byref(bad)) == 0 and b"bit widths" in lib.p4v_last_error()
+        bad = _matmul_desc(13, 8, 13, batch=4, heads=3, reserved=reserved, blocks=(2, 9, 2, 3))
+        assert lib.p4v_matmul_blocks_workspace_bytes(C.byref(bad)) == 0 and b"up to n_V, n_H = 8" in lib.p4v_last_error()
+        bad = _matmul_desc(13, 8, 13, batch=4, heads=3, reserved=reserved, blocks=(2, 0, 2, 3))
+        assert lib.p4v_matmul_blocks_workspace_bytes(C.byref(bad)) == 0 and b"non-positive block count" in lib.p4v_last_error()
+    bad = _conv_desc(a_bit=8, metric="cosine")
+    assert lib.p4v_conv_workspace_bytes(C.byref(bad)) == 0 and b"cosine does not support the activation search" in lib.p4v_last_error()
+    mlp = _lib.MlpDesc()
+    mlp.fc1, mlp.fc2 = _linear_desc(2, 64, 64, 256, postgelu=True), _linear_desc(2, 64, 256, 64)
+    assert lib.p4v_mlp_workspace_bytes(C.byref(mlp)) == 0 and b"twin_postgelu belongs on fc2" in lib.p4v_last_error()
+    mlp.fc1, mlp.fc2 = _linear_desc(2, 64, 64, 256), _linear_desc(2, 64, 128, 64)
+    assert lib.p4v_mlp_workspace_bytes(C.byref(mlp)) == 0 and b"is not fc2's input" in lib.p4v_last_error()
+    # the sizes a supported descriptor gets: the forward alone needs no more than the search, and something
+    ld, md = _linear_desc(2, 64, 192, 128), _matmul_desc(49, 64, 49)
+    full = lib.p4v_linear_workspace_bytes(C.byref(ld))
+    ld.reserved = 4
+    assert 4096 < lib.p4v_linear_workspace_bytes(C.byref(ld)) <= full
+    full = lib.p4v_matmul_workspace_bytes(C.byref(md))
+    md.reserved = 4
+    assert 4096 < lib.p4v_matmul_workspace_bytes(C.byref(md)) <= full

@@ -2,7 +2,9 @@
 
 Without a GPU: the four *_workspace_bytes entry points over a grid of descriptors that reaches every sweep kernel family (the
 small shapes of tests/sweep_plan_cases.py, the layers of ViT-B / DeiT-T / Swin-T at the sizes tests/test_hip_production_path.py
-calibrates them; metrics, blocks, pruning on / off, fp32 planes -- the sizes do not depend on the bit width).
+calibrates them; metrics, blocks, pruning on / off, fp32 planes -- the sizes do not depend on the bit width).  Then the dry runs of
+the forward side: the Linear, MatMul and sub-block grids again with `reserved` bit 2 (the sizes of *_quant_forward alone; the
+small shapes and the ViT-B layers), and p4v_mlp_workspace_bytes over a small grid of fused MLP forwards.
 --gpu: also the cases of tests/sweep_plan_cases.py, pruning off and on: launch records (kernel, stage, grid_x, grid_z) in order,
 p4v_launch_counters, p4v_prune_counters, and the raw bytes of the returned intervals, score tables and selections (as hex where
 they are at most 16 bytes, as a sha256 prefix otherwise); then the three-round cases of tests/search_round_cases.py in each of
@@ -84,15 +86,53 @@ def conv_descs():
         yield _lib.ConvDesc(b, ic, h, w, oc, k, k, k, k, 0, 0, 1, 1, 8, a_bit, metric, 100, 3, cw, 0, 1, reserved)
 
 
+FWD = _lib.RESERVED_FORWARD_ONLY
+
+
+def linear_forward_descs():
+    # the small cases and the ViT-B x 32 layers (post-GELU where fc2 is); int8 planes, fp32 planes (bit 0), column / activation blocks
+    shapes = [(2, 64, 192, 128, 1), (2, 64, 128, 128, 1), (2, 64, 1024, 64, 1), (2, 64, 1088, 64, 1), (2, 64, 192, 120, 3), (10, 65, 192, 96, 1),
+              (32, 197, 768, 2304, 3), (32, 197, 768, 768, 1), (32, 197, 768, 3072, 1), (32, 197, 3072, 768, 1), (32, 1, 768, 1000, 1)]
+    for (b, T, K, N, nV), reserved in itertools.product(shapes, (FWD, FWD | 1)):
+        for postgelu in ((0, 1) if K >= N and K >= 768 else (0,)):
+            yield _lib.LinearDesc(b, T, K, N, nV, 1, 1, 8, 8, HESSIAN, 100, 3, postgelu, 0, 1, reserved)
+    for (b, T, K, N, nV), metric in itertools.product(shapes[:6], (HESSIAN, COSINE)):
+        yield _lib.LinearDesc(b, T, K, N, nV, 2, 2, 8, 8, metric, 100, 3, 0, 0, 1, FWD)
+
+
+def matmul_forward_descs():
+    for (b, H, T, D), metric in itertools.product(matmul_shapes()[:3], (HESSIAN, COSINE)):
+        yield _mm(b, H, T, D, T, 8, metric, 0, FWD)
+        yield _mm(b, H, T, T, D, 8, metric, 1, FWD)
+        yield _mm(b, H, T, T, D, 8, metric, 0, FWD)
+
+
+def matmul_blocks_forward_descs():
+    for bd in matmul_blocks_descs():
+        bd.mm.reserved = FWD
+        yield bd
+
+
+def mlp_descs():
+    # (batch, tokens, in, hidden): rows x in x hidden of 128 x 64 x 256, 130 x 192 x 768, ViT-B x 32; fc2 plain / post-GELU twin; n_V on fc1
+    for (b, T, K, Hd), twin, nV in itertools.product(((2, 64, 64, 256), (10, 13, 192, 768), (32, 197, 768, 3072)), (0, 1), (1, 3)):
+        d = _lib.MlpDesc()
+        d.fc1 = _lib.LinearDesc(b, T, K, Hd, nV, 1, 1, 8, 8, HESSIAN, 100, 3, 0, 0, 1, 0)
+        d.fc2 = _lib.LinearDesc(b, T, Hd, K, 1, 1, 1, 8, 8, HESSIAN, 100, 3, twin, 0, 1, 0)
+        yield d
+
+
 def workspace_plan(lib):
     """per entry point: the number of descriptors, a digest of their bytes (which grid this was) and the sizes in grid order"""
     plan = {}
     for fn, descs in (("p4v_linear_workspace_bytes", linear_descs()), ("p4v_matmul_workspace_bytes", matmul_descs()),
-                      ("p4v_matmul_blocks_workspace_bytes", matmul_blocks_descs()), ("p4v_conv_workspace_bytes", conv_descs())):
+                      ("p4v_matmul_blocks_workspace_bytes", matmul_blocks_descs()), ("p4v_conv_workspace_bytes", conv_descs()),
+                      ("p4v_linear_workspace_bytes:forward", linear_forward_descs()), ("p4v_matmul_workspace_bytes:forward", matmul_forward_descs()),
+                      ("p4v_matmul_blocks_workspace_bytes:forward", matmul_blocks_forward_descs()), ("p4v_mlp_workspace_bytes", mlp_descs())):
         h, sizes = hashlib.sha256(), []
         for d in descs:
             h.update(bytes(d))
-            sizes.append(int(getattr(lib, fn)(C.byref(d))))
+            sizes.append(int(getattr(lib, fn.split(":")[0])(C.byref(d))))
         plan[fn] = {"descriptors": len(sizes), "grid_sha256": h.hexdigest()[:16], "bytes": sizes}
     return plan
 
