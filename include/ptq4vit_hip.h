@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define P4V_VERSION 142 /* 0.1.4.2: + p4v_mlp_* (fused int8 MLP forward: fc1, GELU and fc2's quantiser in one pass) */
+#define P4V_VERSION 143 /* 0.1.4.3: + p4v_attn_* (fused int8 attention forward: q k^T, softmax and matmul2's quantiser in one kernel) */
 
 /* similarity metrics: reference quant_layers/linear.py:399-424 */
 enum p4v_metric {
@@ -455,6 +455,39 @@ int p4v_mlp_quant_forward(const p4v_mlp_desc* desc, const float* d_w1, const flo
                           const float* d_w2_interval, const float* d_a2_interval, float* d_out, float* d_hidden, void* d_ws,
                           size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Fused attention forward (opt-in, network level): matmul2(softmax(matmul1(q, k^T) * scale), v) of the two calibrated MatMuls
+ * of an attention block with int8 in between.  matmul1 (`qk`: head-wise A / B intervals, not sos) is the int8 GEMM of
+ * p4v_matmul_quant_forward; its kernel keeps the scores in registers, multiplies by `scale` (a separate fp32 multiply, as the module
+ * does), takes the softmax over the keys (true row maximum, expf, IEEE division) and quantises the probabilities with matmul2's
+ * A quantiser (`pv.sos`: the two split-of-softmax ranges of matmul.py:595-598 as two planes; else one symmetric plane on the
+ * head-wise A interval) straight into the int8 plane(s) matmul2's GEMM reads: no fp32 score or probability tensor is written or
+ * read.  matmul2 is the GEMM of p4v_matmul_quant_forward on those planes.  d_out equals p4v_matmul_quant_forward of `pv` on
+ * the probabilities this call computes, bit for bit; against the unfused chain the probabilities differ by the order of the
+ * row sum (measured: profiles/r22_fused_attn_margins.json).
+ * Envelope: both MatMuls head-wise (no row / column sub-blocks: this descriptor cannot express them), qk not sos, pv sos or
+ * plain, all widths 2..8, qk.batch / heads / M = pv.batch / heads / M, qk.N = pv.K, int8 planes (reserved bit 0 clear); anything
+ * else is P4V_ERR_UNSUPPORTED / P4V_ERR_INVALID before the first launch.  No limit on the number of keys (the kernel walks
+ * them tile by tile).  The descriptors' search fields are ignored; pv.a_stride is not read.
+ * d_q [b][h][M][D], d_kT [b][h][D][N], d_v [b][h][N][Dv] through qk.a_stride / qk.b_stride / pv.b_stride (views are read in place);
+ * d_qk_A_interval, d_qk_B_interval, d_pv_B_interval [heads]; d_pv_A_interval [heads] (sos: [1]); d_split [1] (sos only);
+ * d_out [batch*heads][M][Dv]; d_probs: optional (may be NULL, then nothing is stored for it) [batch*heads][M][N] fp32, the
+ * probabilities the planes were quantised from.  d_scratch, scratch_bytes: the workspace and its size -- the workspace contract
+ * above holds with p4v_attn_workspace_bytes; a smaller scratch_bytes is refused before any launch.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct p4v_attn_desc {
+    p4v_matmul_desc qk, pv;
+    float scale;
+    int32_t reserved;
+} p4v_attn_desc;
+
+size_t p4v_attn_workspace_bytes(const p4v_attn_desc* desc);
+
+int p4v_attn_quant_forward(const p4v_attn_desc* desc, const float* d_q, const float* d_kT, const float* d_v,
+                           const float* d_qk_A_interval, const float* d_qk_B_interval, const float* d_pv_A_interval,
+                           const float* d_pv_B_interval, const float* d_split, float* d_out, float* d_probs, void* d_scratch,
+                           size_t scratch_bytes, void* stream);
+
 /* d_A_interval: [heads] (sos: [1]); d_B_interval: [heads]; d_split: [1] (sos only); d_out: [batch*heads][M][N] */
 int p4v_matmul_quant_forward(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_A_interval,
                              const float* d_B_interval, const float* d_split, float* d_out, void* d_workspace,
@@ -500,7 +533,8 @@ typedef struct p4v_kernel_stats {
 typedef struct p4v_launch_record {
     int32_t kind;     /* 2 k_sweep6 | 3 k_sweep7 | 4 k_sweep7 twin | 5 k_sweep5 | 6 k_sweep9 | 7 k_sweep8 | 8 k_sweep2g | 9 k_sweep2 |
                          0 generic int8 k_sweep | 1 generic fp32 k_sweep | 11 k_sos_split (fp32) | 12 k_bound (stage B1) |
-                         13 k_slice_b2 / 14 k_slice_a (stage A of a MatMul B / A search) */
+                         13 k_slice_b2 / 14 k_slice_a (stage A of a MatMul B / A search) | 15 k_sweep_seg | 16 k_mlp_fc1 |
+                         17 k_attn_qk */
     int32_t stage;    /* 0 full sweep (pass not pruned) | 1 stage A (all candidates, sample slice) | 2 stage B1 (the bound) |
                          3 stage B2 (survivors, all samples) | 4 stage A2 (survivors of a loose first slice on the larger second one) */
     int32_t grid_x, grid_z;   /* a grouped launch (p4v_calibrate_group): grid_x = its flat grid (all members' blocks, each member padded to a

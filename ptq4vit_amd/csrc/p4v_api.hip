@@ -3385,6 +3385,96 @@ int matmul_impl(const p4v_matmul_desc* d, const MatMulTensors& t, const Stage& s
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Fused attention forward (p4v_attn_quant_forward): matmul1 -> * scale -> softmax -> matmul2's A quantiser -> matmul2, int8 in between
+// ------------------------------------------------------------------------------------------------
+// matmul1's part: q and k^T packed as MatMulCall::forward_pass packs them (pack_operand, k_scale_table), then k_attn_qk, which
+// writes matmul2's row plane(s) -- the fp32 score tensor, torch's `* scale` and softmax over it and k_pack_dual of it are gone.
+// matmul2's part: its forward pass as run_pass runs it, the row operand prepacked ([Z][Mp][Kp]: the tiled sweeps step Mp * Kp
+// per z, the plane's own layout).
+// Where the planes of the calling thread's last call lie in its workspace (p4v_debug_attn_planes: the tests read them there)
+struct AttnPlanes { size_t off1 = 0, off2 = 0; long rows = 0, cols = 0; int twin = 0; };
+thread_local AttnPlanes g_attn_planes;
+constexpr int ATTN_RECORD_KIND = 17;
+
+// `t1`, `t2`: the two MatMuls' records as p4v_matmul_quant_forward fills them -- t1.fwd_out stays null (matmul1 stores nothing),
+// t2.A stays null (matmul2 reads k_attn_qk's planes); `probs`: the optional fp32 copy of the probabilities [Z][M][N].
+int attn_impl(const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulTensors& t2, float* probs, Ctx& c) {
+    const p4v_matmul_desc* d1 = &d->qk;
+    const p4v_matmul_desc* d2 = &d->pv;
+    // the envelope, before anything is planned or launched
+    if (d1->batch != d2->batch || d1->heads != d2->heads || d1->M != d2->M || d1->N != d2->K)
+        return fail(P4V_ERR_INVALID, "attn: q k^T [%d][%d][%d][%d] is not the row operand of p v [%d][%d][%d][%d]", d1->batch, d1->heads, d1->M, d1->N,
+                    d2->batch, d2->heads, d2->M, d2->K);
+    if (d1->sos) return fail(P4V_ERR_UNSUPPORTED, "attn: q k^T is no split-of-softmax operand (sos belongs on p v)");
+    if ((d1->reserved | d2->reserved) & RSV_FP32_PLANES) return fail(P4V_ERR_UNSUPPORTED, "attn: int8 planes only (desc.reserved bit 0 is set)");
+    if (!(d->scale == d->scale)) return fail(P4V_ERR_INVALID, "attn: scale is NaN");
+    const Stage sg{ST_FWD};
+    MatMulCall m1(c, d1, t1, sg), m2(c, d2, t2, sg);
+    CHK(m1.build());
+    CHK(m2.build());
+    cvt_bias(c);     // (first call of the process: probe the conversion quant16_sat8 relies on)
+    CHK(q_wait_inputs(c));
+    // matmul2's pass first: its plan says how large the row plane(s) are
+    Pass fp2 = m2.forward_pass();
+    SweepPlan pl2;
+    CHK(plan_sweep(c, fp2, pl2));
+    if (pl2.cin_fix != 0 || pl2.merged7 || pl2.esz != 1) return fail(P4V_ERR_UNSUPPORTED, "attn: p v's sweep does not read row-major int8 planes");
+    const int Z = m1.Z, H = m1.H, M = m1.M, N = m1.N, K1 = m1.K;
+    const int Mp = pl2.Mp, Kp = pl2.Kp;                        // Kp = roundup64(N)
+    const int K1p = (int)rup(K1, 64), Np1 = (int)rup(N, SW_BN);
+    const bool twin = d2->sos != 0;
+    if (Mp % SW_BM || (long)Z * (Mp / SW_BM) >= (1L << 31)) return fail(P4V_ERR_UNSUPPORTED, "attn: %d x %d row tiles", Z, Mp / SW_BM);
+    char* P1 = c.ws.get<char>((size_t)Z * Mp * Kp);
+    char* P2 = twin ? c.ws.get<char>((size_t)Z * Mp * Kp) : nullptr;
+    {
+        const size_t mark = c.ws.off;
+        Pass fp1 = m1.forward_pass();
+        SweepPlan pl1{};                                       // what pack_operand reads of a plan: the plane geometry
+        pl1.esz = 1; pl1.Mp = Mp; pl1.Np = pl1.NpB = Np1; pl1.Kp = K1p; pl1.cin_fix = 0;
+        char* qa = c.ws.get<char>((size_t)Z * Mp * K1p);
+        char* kb = c.ws.get<char>((size_t)Z * Np1 * K1p);
+        float* S1 = c.ws.get<float>((size_t)H);
+        if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", c.ws.off);
+        fp1.s1.S = S1; fp1.s1.C = 1; fp1.s1.nblk = fp1.s_cs;
+        CHK(launch_scale(c, fp1.s1));
+        const PassBufs nb{};
+        CHK(pack_operand(c, fp1, pl1, nb, fp1.row, qa, false, 0, 1));
+        CHK(pack_operand(c, fp1, pl1, nb, fp1.col, kb, true, 0, 1));
+        if (!c.dry) {
+            AttnQkParams q{};
+            q.Q = qa; q.Kt = kb; q.q_zs = (long)Mp * K1p; q.k_zs = (long)Np1 * K1p; q.ldk = K1p; q.ktiles = K1p / SW_BKB;
+            q.S1 = S1; q.H = H; q.scale = d->scale;
+            q.M = M; q.N = N; q.Mp = Mp; q.Kp = Kp;
+            q.qs = twin ? t2.split : t2.A_iv; q.qs_headwise = twin ? 0 : 1;
+            q.lo = -m2.Aq; q.hi = m2.Aq - 1; q.qm1 = (float)(m2.Aq - 1);
+            q.P1 = (int8_t*)P1; q.P2 = (int8_t*)P2; q.probs = probs;
+            q.mtiles = Mp / SW_BM; q.nwg = Z * q.mtiles;
+            g_alg_macs_cand = (double)Z * M * N * K1;
+            g_alg_bytes = 4.0 * ((double)Z * M * K1 + (double)Z * N * K1) + (double)Z * M * N * (twin ? 2 : 1);
+            g_exec_frac = 1.0;
+            // (three walks over the keys: the maximum, the sum, the write pass)
+            const StatInfo si = stat_info(ATTN_RECORD_KIND, 3.0 * (double)Z * Mp * (double)rup(N, 32) * K1p, g_alg_macs_cand, q.nwg, 1, g_alg_bytes);
+            const dim3 grid(q.nwg), block(256);
+            const size_t lds = (size_t)4 * (twin ? 2 : 1) * 32 * ATTN_OROW;
+            if (twin) CHK(enqueue(c, KERN1_T(AttnQkParams, k_attn_qk, true), grid, block, lds, q, &si));
+            else CHK(enqueue(c, KERN1_T(AttnQkParams, k_attn_qk, false), grid, block, lds, q, &si));
+            g_attn_planes = AttnPlanes{(size_t)(P1 - c.ws.base), P2 ? (size_t)(P2 - c.ws.base) : 0, (long)Z * Mp, Kp, twin ? 1 : 0};
+        }
+        c.ws.off = mark;
+    }
+    fp2.row.prepacked = true; fp2.row.plane = P1;             // (null in the sizing run: it carves nothing)
+    if (twin) { fp2.row2.prepacked = true; fp2.row2.plane = P2; }
+    return run_pass(c, fp2);
+}
+// the dry run of the planner: the envelope's verdict, and the bytes the call needs
+int attn_sizing_run(const p4v_attn_desc* d, size_t* need) {
+    Ctx c = Ctx::sizing();
+    CHK(attn_impl(d, MatMulTensors{}, MatMulTensors{}, nullptr, c));
+    *need = c.sized_bytes();
+    return 0;
+}
+
 // ---- MatMul with row / column sub-blocks (n_V, n_H > 1; reference matmul.py:109-138, 419-440, 483-563) -------------------------
 // Intervals are [heads][n_V][n_H] (the reference's (1, n_G = heads, 1, n_V, 1, n_H, 1)).  The search is the reference's greedy
 // coordinate descent: block (v, h) in product(range(n_V), range(n_H)) order, its candidates mult * INITIAL interval replacing
@@ -3786,6 +3876,30 @@ int p4v_mlp_quant_forward(const p4v_mlp_desc* desc, const float* d_w1, const flo
                      .a_iv = const_cast<float*>(d_a2_interval), .fwd_out = d_out}, c);
 }
 
+size_t p4v_attn_workspace_bytes(const p4v_attn_desc* desc) {
+    size_t need = 0;
+    return (desc && attn_sizing_run(desc, &need) == 0) ? need : 0;
+}
+
+int p4v_attn_quant_forward(const p4v_attn_desc* desc, const float* d_q, const float* d_kT, const float* d_v,
+                           const float* d_qk_A_interval, const float* d_qk_B_interval, const float* d_pv_A_interval,
+                           const float* d_pv_B_interval, const float* d_split, float* d_out, float* d_probs, void* d_ws,
+                           size_t ws_bytes, void* stream) {
+    if (!desc || !d_q || !d_kT || !d_v || !d_qk_A_interval || !d_qk_B_interval || !d_pv_A_interval || !d_pv_B_interval || !d_out || !d_ws)
+        return fail(P4V_ERR_INVALID, "p4v_attn_quant_forward: null pointer");
+    if (desc->pv.sos && !d_split) return fail(P4V_ERR_INVALID, "p4v_attn_quant_forward: sos needs d_split");
+    CHK(ws_aligned(d_ws));
+    // matmul1's launches precede the planning of matmul2's pass: the whole need is checked here, before the first of them
+    size_t need = 0;
+    CHK(attn_sizing_run(desc, &need));
+    if (ws_bytes < need) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", need);
+    Ctx c = Ctx::on(stream, d_ws, ws_bytes);
+    return attn_impl(desc,
+                     {.A = d_q, .B = d_kT, .A_iv = const_cast<float*>(d_qk_A_interval), .B_iv = const_cast<float*>(d_qk_B_interval)},
+                     {.B = d_v, .A_iv = const_cast<float*>(d_pv_A_interval), .B_iv = const_cast<float*>(d_pv_B_interval),
+                      .split = const_cast<float*>(d_split), .fwd_out = d_out}, d_probs, c);
+}
+
 int p4v_matmul_quant_forward(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_A_interval,
                              const float* d_B_interval, const float* d_split, float* d_out, void* d_workspace,
                              size_t workspace_bytes, void* stream) {
@@ -4158,7 +4272,7 @@ static int stats_drain() {
         float ms = 0;
         HIPCHK(hipEventElapsedTime(&ms, r.a, r.b));
         ms = (float)std::max(0.0, (double)ms - g_evt_overhead_ms);
-        if (r.kind == 0 || (r.kind >= 2 && r.kind <= 9) || (r.kind >= 12 && r.kind <= 16)) { g_stats.sweep_i8_ms += ms; g_stats.sweep_i8_launches++; g_stats.sweep_i8_macs += r.macs; g_stats.sweep_i8_alg_macs += r.alg; }
+        if (r.kind == 0 || (r.kind >= 2 && r.kind <= 9) || (r.kind >= 12 && r.kind <= 17)) { g_stats.sweep_i8_ms += ms; g_stats.sweep_i8_launches++; g_stats.sweep_i8_macs += r.macs; g_stats.sweep_i8_alg_macs += r.alg; }
         if (r.kind == 2) { g_stats.sweep6_ms += ms; g_stats.sweep6_launches++; g_stats.sweep6_macs += r.macs; g_stats.sweep6_alg_macs += r.alg; }
         if (r.kind == 3 || r.kind == 4) { g_stats.sweep7_ms += ms; g_stats.sweep7_launches++; g_stats.sweep7_macs += r.macs; g_stats.sweep7_alg_macs += r.alg; }
         if (r.kind == 4) { g_stats.sweep7_twin_ms += ms; g_stats.sweep7_twin_launches++; }
@@ -4238,6 +4352,13 @@ int p4v_debug_mlp_planes(uint64_t* out) {
     const MlpPlanes& m = g_mlp_planes;
     out[0] = m.off1; out[1] = m.off2; out[2] = (uint64_t)m.rows; out[3] = (uint64_t)m.cols; out[4] = (uint64_t)m.twin;
     return m.rows > 0 ? 0 : fail(P4V_ERR_INVALID, "p4v_debug_mlp_planes: no p4v_mlp_quant_forward call on this thread yet");
+}
+
+int p4v_debug_attn_planes(uint64_t* out) {
+    if (!out) return fail(P4V_ERR_INVALID, "p4v_debug_attn_planes: null pointer");
+    const AttnPlanes& m = g_attn_planes;
+    out[0] = m.off1; out[1] = m.off2; out[2] = (uint64_t)m.rows; out[3] = (uint64_t)m.cols; out[4] = (uint64_t)m.twin;
+    return m.rows > 0 ? 0 : fail(P4V_ERR_INVALID, "p4v_debug_attn_planes: no p4v_attn_quant_forward call on this thread yet");
 }
 
 int p4v_debug_sos_sweep(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_out, const float* d_grad,

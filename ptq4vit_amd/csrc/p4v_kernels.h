@@ -5178,4 +5178,169 @@ __device__ __forceinline__ void k_mlp_fc1_body(const MlpFc1Params& p, const uint
 template <bool TWIN>
 __global__ __launch_bounds__(512) void k_mlp_fc1(MlpFc1Params p) { k_mlp_fc1_body<TWIN>(p, P4V_BIDX, P4V_GDIM); }
 
+// ------------------------------------------------------------------------------------------
+// Fused attention forward, first half (p4v_attn_quant_forward): matmul1's int8 GEMM, `* scale`, the softmax over the keys and
+// matmul2's A quantiser, ending in matmul2's int8 row plane(s)
+// ------------------------------------------------------------------------------------------
+// Operands: the planes of matmul1 as its forward pass packs them, Q(q) [Z][Mp][ldk] and Q(k^T) [Z][Np1][ldk], head = z % H.
+// The TRANSPOSED score tile is computed -- Q(k^T) is the MFMA's first operand, Q(q) its second -- so a lane holds ONE query
+// (lane & 31) and 16 of a tile's 32 keys in its accumulator registers (keys 4g + (r & 3) + 8 (r >> 2), g = lane >> 5): the
+// row maximum and the row sum are register reductions plus one exchange between the lane halves.  A wave owns 32 queries and
+// walks all keys three times -- the maximum, the sum, the write pass -- recomputing the 32 x 32 score tile each time (K =
+// head_dim: one or two k-tiles; the GEMM is small next to the expf and the stores), so there is no limit on the number of keys
+// and no score ever leaves the registers.  Per score element, nothing contracted or reassociated:
+//   t = (float)acc * S1[head]                        EPI_FWD's expression without bias: what matmul1.quant_forward stores
+//   u = t * scale                                    Attention.forward's `* self.scale`
+//   p = expf(u - max_n u) / sum_n expf(u - max_n u)  the true row maximum, IEEE division
+// then pack_value: TWIN the split-of-softmax pair (PACK_SOS_HI / PACK_SOS_LO on the split), else PACK_SYM on A_interval[head].
+// The planes are matmul2's row operand as its forward sweep reads it, [Z][Mp][Kp], Kp = roundup64(N): the write pass goes in
+// chunks of 64 keys, a lane's four consecutive keys of a register quad as one dword into the wave's LDS tile (32 rows x 64
+// bytes, rows ATTN_OROW apart), out as 16-byte pieces; rows >= M and columns >= N are written as zeros.  The key fragments come
+// straight from global memory: one head's plane (Np1 x ldk bytes, 16 KB at 197 keys) stays in the L1 / L2 of the workgroups
+// that share it.  `probs` (optional) receives p as fp32 [Z][M][N]; a null pointer costs no store.
+struct AttnQkParams {
+    const void* Q; const void* Kt;            // [Z][Mp][ldk] / [Z][Np1][ldk]
+    long q_zs, k_zs; int ldk, ktiles;
+    const float* S1; int H;                   // A_interval[head] * B_interval[head] of matmul1 (k_scale_table)
+    float scale;
+    int M, N, Mp, Kp;                         // valid queries / keys; the output plane's padded rows / columns
+    const float* qs; int qs_headwise;         // matmul2's A quantiser: the split (TWIN) or A_interval[head]
+    int lo, hi; float qm1;
+    int8_t* P1; int8_t* P2;
+    float* probs;
+    int mtiles, nwg;                          // 128-query tiles per z; workgroups
+};
+static constexpr int ATTN_OROW = 80;          // LDS row of a wave's output tile: 64 bytes + 16 bytes pad
+
+template <bool TWIN>
+__device__ __forceinline__ void k_attn_qk_body(const AttnQkParams& p, const uint3 blockIdx, const uint3 gridDim) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int g = lane >> 5, l31 = lane & 31;
+    const int t = xcd_remap(blockIdx.x, p.nwg);
+    const int z = t / p.mtiles, mt = t % p.mtiles;    // the row tiles of one z are adjacent: they share its key plane
+    const int m0 = mt * SW_BM + wid * 32;             // this wave's 32 queries
+    const int m = m0 + l31;
+    const bool row_ok = m < p.M;
+    const bool wave_live = m0 < p.M;                  // (wave-uniform) a wave of nothing but padding rows writes zeros
+    const int head = z % p.H;
+
+    const char* gQ = (const char*)p.Q + (long)z * p.q_zs + (long)m * p.ldk + g * 16;
+    const char* gK = (const char*)p.Kt + (long)z * p.k_zs + (long)l31 * p.ldk + g * 16;
+    const bool one = p.ktiles == 1;
+    v4i qf0 = {0, 0, 0, 0}, qf1 = {0, 0, 0, 0};       // the query fragments of a single k-tile stay in registers
+    if (one) { qf0 = *reinterpret_cast<const v4i*>(gQ); qf1 = *reinterpret_cast<const v4i*>(gQ + 32); }
+
+    const float s1 = p.S1[head];
+    const float scale = p.scale;
+    // u of the 32 x 32 tile at keys [key0, key0 + 32)
+    auto scores = [&](int key0, float (&u)[16]) {
+        v16i acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0;
+        const char* ka = gK + (long)key0 * p.ldk;
+        if (one) {
+            const v4i a0 = *reinterpret_cast<const v4i*>(ka), a1 = *reinterpret_cast<const v4i*>(ka + 32);
+            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, qf0, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, qf1, acc, 0, 0, 0);
+        } else {
+            for (int kb = 0; kb < p.ktiles * 2; ++kb) {
+                const v4i a = *reinterpret_cast<const v4i*>(ka + kb * 32);
+                const v4i b = *reinterpret_cast<const v4i*>(gQ + kb * 32);
+                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, acc, 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) u[r] = __fmul_rn(__fmul_rn((float)acc[r], s1), scale);
+    };
+
+    const int ntiles = wave_live ? (p.N + 31) / 32 : 0;
+    float u[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) u[r] = 0.0f;
+    // ---- pass 1: the row maximum ------------------------------------------------------------------------
+    float mx = -__builtin_inff();
+    for (int nt = 0; nt < ntiles; ++nt) {
+        scores(nt * 32, u);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int n = nt * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
+            if (n < p.N) mx = fmaxf(mx, u[r]);
+        }
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    // ---- pass 2: the row sum ----------------------------------------------------------------------------
+    // (one partial sum per accumulator register, added up pairwise: a chain of N / 32 additions, not of N / 2)
+    float part[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) part[r] = 0.0f;
+    for (int nt = 0; nt < ntiles; ++nt) {
+        scores(nt * 32, u);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int n = nt * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
+            if (n < p.N) part[r] = __fadd_rn(part[r], expf(__fsub_rn(u[r], mx)));
+        }
+    }
+#pragma unroll
+    for (int w = 8; w >= 1; w >>= 1)
+#pragma unroll
+        for (int r = 0; r < w; ++r) part[r] = __fadd_rn(part[r], part[r + w]);
+    const float sum = __fadd_rn(part[0], __shfl_xor(part[0], 32));
+    // ---- pass 3: the probabilities, matmul2's quantiser, the planes ---------------------------------------
+    const float qs = p.qs[p.qs_headwise ? head : 0];
+    PackParams pv1{}, pv2{};
+    pv1.mode = TWIN ? PACK_SOS_HI : PACK_SYM; pv1.lo = p.lo; pv1.hi = p.hi; pv1.qm1 = p.qm1;
+    pv2.mode = PACK_SOS_LO; pv2.qm1 = p.qm1;
+    char* o1 = smem + wid * (TWIN ? 2 : 1) * 32 * ATTN_OROW;
+    char* o2 = o1 + 32 * ATTN_OROW;
+    const long prow = ((long)z * p.Mp + m0) * p.Kp;
+    for (int ch = 0; ch < p.Kp / 64; ++ch) {
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            const int key0 = ch * 64 + half * 32;
+            if (wave_live && key0 < p.N) scores(key0, u);   // (wave-uniform; a tile of nothing but padding is zeros)
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) {
+                int w1 = 0, w2 = 0;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int r = q4 * 4 + e;
+                    const int n = key0 + e + 8 * q4 + 4 * g;
+                    const bool ok = row_ok && n < p.N;
+                    float b1 = 0.0f, b2 = 0.0f;
+                    if (ok) {
+                        const float pr = __fdiv_rn(expf(__fsub_rn(u[r], mx)), sum);
+                        if (p.probs) p.probs[((long)z * p.M + m) * p.N + n] = pr;
+                        b1 = pack_value(pv1, pr, qs);
+                        if (TWIN) b2 = pack_value(pv2, pr, qs);
+                    }
+                    w1 |= ((int)b1 & 0xff) << (8 * e);
+                    if (TWIN) w2 |= ((int)b2 & 0xff) << (8 * e);
+                }
+                const int off = l31 * ATTN_OROW + half * 32 + 8 * q4 + 4 * g;
+                *reinterpret_cast<int*>(o1 + off) = w1;
+                if (TWIN) *reinterpret_cast<int*>(o2 + off) = w2;
+            }
+        }
+        __syncthreads();
+        // LDS -> global: 16-byte pieces, 4 consecutive lanes write the 64 contiguous bytes of a row
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int piece = j * 64 + lane;
+            const int row_l = piece >> 2, c16 = (piece & 3) * 16;
+            const long o = prow + (long)row_l * p.Kp + ch * 64 + c16;
+            const v4i w1 = *reinterpret_cast<const v4i*>(o1 + row_l * ATTN_OROW + c16);
+            __builtin_nontemporal_store(w1, reinterpret_cast<v4i*>(p.P1 + o));
+            if (TWIN) {
+                const v4i w2 = *reinterpret_cast<const v4i*>(o2 + row_l * ATTN_OROW + c16);
+                __builtin_nontemporal_store(w2, reinterpret_cast<v4i*>(p.P2 + o));
+            }
+        }
+        __syncthreads();
+    }
+}
+template <bool TWIN>
+__global__ __launch_bounds__(256) void k_attn_qk(AttnQkParams p) { k_attn_qk_body<TWIN>(p, P4V_BIDX, P4V_GDIM); }
+
 }  // namespace p4v

@@ -281,6 +281,64 @@ def mlp_quant_forward(*, x, fc1, fc2, want_hidden=False, want_planes=False):
     return res
 
 
+def _attn_matmul_desc(d, A_shape, A_stride, B, side, what):
+    """One p4v_matmul_desc of a p4v_attn_desc; `side`: the dict engine.attn_quant_forward takes per MatMul."""
+    if has_blocks(side.get("blocks")):
+        raise NotImplementedError(f"attn_quant_forward: {what} has row / column sub-blocks (the fused forward is head-wise)")
+    d.batch, d.heads, d.M, d.K, d.N = A_shape[0], A_shape[1], A_shape[2], A_shape[3], B.shape[3]
+    for i in range(4):
+        d.a_stride[i] = A_stride[i]
+        d.b_stride[i] = B.stride(i)
+    d.A_bit, d.B_bit, d.metric, d.eq_n, d.search_round = side["A_bit"], side["B_bit"], metric_id("L2_norm"), 1, 1
+    d.sos, d.init_layerwise, d.reserved = int(bool(side.get("sos", False))), 0, _lib.RESERVED_FORWARD_ONLY
+
+
+def attn_quant_forward(*, q, kT, v, scale, qk, pv, want_probs=False, want_planes=False):
+    """matmul2(softmax(matmul1(q, kT) * scale, -1), v) of the two calibrated MatMuls of an attention block in quant_forward,
+    fused (p4v_attn_quant_forward): matmul1's int8 GEMM keeps the scores in registers, takes the softmax and matmul2's A
+    quantiser and writes matmul2's int8 plane(s); no fp32 score or probability tensor in between.
+    q [B][H][M][D], kT [B][H][D][N], v [B][H][N][Dv]: read through their strides (views are not copied).  `qk` / `pv`: dicts
+    with A_interval, B_interval ([heads] each; the split-of-softmax pv: its scalar A_interval), A_bit, B_bit, optionally
+    blocks (anything but (1, 1, 1, 1) is refused), and for `pv` sos, split.  Returns out [B][H][M][Dv], or (out, probs) with
+    `want_probs` -- the fp32 probabilities the planes were quantised from --, with `want_planes` also the padded int8
+    plane(s) as the call left them in its workspace (a tuple of one or two [B*H][rows_padded][cols_padded] tensors; for the
+    tests)."""
+    lib = _lib.load()
+    dev = device_of(q, kT, v)
+    q, kT, v = to_dev(q, dev), to_dev(kT, dev), to_dev(v, dev)
+    b, H, M, _ = q.shape
+    N, Dv = kT.shape[3], v.shape[3]
+    if qk.get("sos", False):
+        raise NotImplementedError("attn_quant_forward: q k^T is no split-of-softmax operand (sos belongs on p v)")
+    d = _lib.AttnDesc()
+    _attn_matmul_desc(d.qk, q.shape, q.stride(), kT, qk, "q k^T")
+    _attn_matmul_desc(d.pv, (b, H, M, v.shape[2]), (H * M * v.shape[2], M * v.shape[2], v.shape[2], 1), v, pv, "p v")
+    d.scale, d.reserved = float(scale), 0
+    sos = bool(pv.get("sos", False))
+    need = _need(lib.p4v_attn_workspace_bytes, d, "p4v_attn_workspace_bytes")
+    ws = workspace(dev, need)
+    flat = lambda t: to_dev(t, dev).reshape(-1).contiguous()
+    qk_A, qk_B, pv_A, pv_B = flat(qk["A_interval"]), flat(qk["B_interval"]), flat(pv["A_interval"]), flat(pv["B_interval"])
+    if qk_A.numel() != H or qk_B.numel() != H or pv_B.numel() != H or pv_A.numel() != (1 if sos else H):
+        raise ValueError("attn_quant_forward: interval tensors must hold one value per head (the split-of-softmax A: one)")
+    sp = flat(pv["split"]) if sos else None
+    out = torch.empty(b, H, M, Dv, dtype=torch.float32, device=dev)
+    probs = torch.empty(b, H, M, N, dtype=torch.float32, device=dev) if want_probs else None
+    with torch.cuda.device(dev):
+        rc = lib.p4v_attn_quant_forward(C.byref(d), ptr(q), ptr(kT), ptr(v), ptr(qk_A), ptr(qk_B), ptr(pv_A), ptr(pv_B), ptr(sp),
+                                        ptr(out), ptr(probs), ptr(ws), ws.numel(), stream_ptr(dev))
+    _lib.check(rc, "p4v_attn_quant_forward")
+    res = (out, probs) if want_probs else out
+    if want_planes:
+        info = (C.c_uint64 * 5)()
+        _lib.check(lib.p4v_debug_attn_planes(info), "p4v_debug_attn_planes")
+        off1, off2, rows, cols, twin = (int(x) for x in info)
+        take = lambda off: ws[off:off + rows * cols].view(torch.int8).reshape(b * H, rows // (b * H), cols).clone()
+        planes = (take(off1), take(off2)) if twin else (take(off1),)
+        res = (res if isinstance(res, tuple) else (res,)) + (planes,)
+    return res
+
+
 def matmul_quant_forward(*, A, B, A_interval, B_interval, split, A_bit, B_bit, sos=False):
     """quant_forward of a calibrated MatMul (head-wise intervals; optional split-of-softmax twin on A)."""
     lib = _lib.load()

@@ -8,7 +8,13 @@ per call: the fused path only when both layers are calibrated, in quant_forward,
 envelope, the tensor is on the GPU, autograd is not recording and none of the three modules carries a forward (pre-)hook.  In
 every other state (raw, the calibration modes, capture hooks, CPU tensors) it calls the original forward, so calibrators behave
 exactly as on an unfused net.  Nothing calls `fuse_mlp` by default; `unfuse_mlp(net)` restores.
+
+`fuse_attention(net)` / `unfuse_attention(net)` / `takes_fused_attention_path(m, x)` are the same for the attention side: the
+patched forward of a `models.Attention` repeats its forward -- the same qkv call, the same P4V_QKV_CONTIGUOUS branch, the same proj
+-- and replaces matmul1 -> `* scale` -> softmax -> matmul2 by engine.attn_quant_forward (p4v_attn_quant_forward)
+when both MatMuls are calibrated, in quant_forward, head-wise, on the int8 path and unhooked; otherwise the original forward.
 """
+import os
 import types
 
 import torch
@@ -16,6 +22,8 @@ import torch.nn as nn
 
 from .. import engine
 from ..quant_layers.linear import PTQSLQuantLinear
+from ..quant_layers.matmul import PTQSLQuantMatMul
+from . import models
 
 _ORIG = "_p4v_unfused_forward"
 
@@ -84,11 +92,10 @@ def fuse_mlp(net):
     return names
 
 
-def unfuse_mlp(net):
-    """Undo fuse_mlp: every patched container gets its original forward back; returns their names.  Idempotent."""
+def _unfuse(net, attr):
     names = []
     for name, m in net.named_modules():
-        orig = m.__dict__.pop(_ORIG, None)
+        orig = m.__dict__.pop(attr, None)
         if orig is None:
             continue
         m.__dict__.pop("forward", None)
@@ -96,3 +103,90 @@ def unfuse_mlp(net):
             m.forward = orig          # the forward was an instance attribute before: put that one back
         names.append(name)
     return names
+
+
+def unfuse_mlp(net):
+    """Undo fuse_mlp: every patched container gets its original forward back; returns their names.  Idempotent."""
+    return _unfuse(net, _ORIG)
+
+
+# ---- the attention side: matmul1 -> * scale -> softmax -> matmul2 (engine.attn_quant_forward, DESIGN.md s5.9) ----------------------
+# Same shape as the MLP functions, with a saved-forward attribute of its own: an Attention is no MLP container, so fuse_mlp and
+# fuse_attention patch different modules and compose in any order.  WindowAttention (Swin) scales q BEFORE matmul1 and adds a
+# position bias and a mask before the softmax: not this kernel's arithmetic, fuse_attention skips it.
+_ORIG_ATTN = "_p4v_unfused_attn_forward"
+
+
+def _inactive_dropout(drop):
+    return isinstance(drop, nn.Identity) or (isinstance(drop, nn.Dropout) and (not drop.training or drop.p == 0))
+
+
+def attention_fusable(m):
+    """The static half of the decision: an Attention container whose forward `fuse_attention` patches."""
+    return (isinstance(m, models.Attention) and isinstance(m.matmul1, PTQSLQuantMatMul) and isinstance(m.matmul2, PTQSLQuantMatMul)
+            and _inactive_dropout(m.attn_drop))
+
+
+def _matmul_ready(mm):
+    return (getattr(mm, "calibrated", None) and mm.mode == "quant_forward" and mm.int8_forward and not engine.has_blocks(mm._blocks)
+            and 2 <= mm.A_bit <= 8 and 2 <= mm.B_bit <= 8 and mm.A_interval is not None and mm.B_interval is not None
+            and (not mm._sos or mm.split is not None))
+
+
+def takes_fused_attention_path(m, x):
+    """The per-call half: would the patched forward of `m` run the fused kernel chain on `x`?"""
+    if not attention_fusable(m):
+        return False
+    m1, m2 = m.matmul1, m.matmul2
+    if not (_matmul_ready(m1) and _matmul_ready(m2)) or m1._sos:
+        return False
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 3 and x.dtype == torch.float32):
+        return False
+    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in m.qkv.parameters())):
+        return False
+    return not (_hooked(m1) or _hooked(m2) or _hooked(m.attn_drop))
+
+
+def _matmul_side(mm, H):
+    side = dict(A_interval=mm.A_interval if mm._sos else mm._per_head(mm.A_interval, H, mm.crb_groups_A),
+                B_interval=mm._per_head(mm.B_interval, H, mm.crb_groups_B), A_bit=mm.A_bit, B_bit=mm.B_bit, blocks=mm._blocks,
+                sos=mm._sos)
+    if mm._sos:
+        side["split"] = mm.split
+    return side
+
+
+def _fused_attention_forward(self, x):
+    if not takes_fused_attention_path(self, x):
+        return self.__dict__[_ORIG_ATTN](x)
+    # models.Attention.forward, with matmul1 ... matmul2 as one engine call
+    B, N, C = x.shape
+    H = self.num_heads
+    qkv = self.qkv(x).reshape(B, N, 3, H, C // H).permute(2, 0, 3, 1, 4)
+    if os.environ.get("P4V_QKV_CONTIGUOUS", "1") == "1":
+        qkv = qkv.contiguous()
+    q, k, v = qkv.unbind(0)
+    kT = k.transpose(-2, -1)
+    for mm, (a, b) in ((self.matmul1, (q, kT)), (self.matmul2, (torch.empty(B, H, N, N, device="meta"), v))):
+        if mm.crb_rows_A is None or mm.crb_rows_B is None:
+            mm._get_padding_parameters(a, b)          # (intervals loaded from elsewhere: as in quant_forward)
+    out = engine.attn_quant_forward(q=q, kT=kT, v=v, scale=self.scale, qk=_matmul_side(self.matmul1, H), pv=_matmul_side(self.matmul2, H))
+    return self.proj_drop(self.proj(out.transpose(1, 2).reshape(B, N, C)))
+
+
+def fuse_attention(net):
+    """Patch the forward of every fusable Attention container of `net`; returns their names.  Idempotent."""
+    names = []
+    for name, m in net.named_modules():
+        if not attention_fusable(m):
+            continue
+        if _ORIG_ATTN not in m.__dict__:
+            m.__dict__[_ORIG_ATTN] = m.forward
+            m.forward = types.MethodType(_fused_attention_forward, m)
+        names.append(name)
+    return names
+
+
+def unfuse_attention(net):
+    """Undo fuse_attention: every patched container gets its original forward back; returns their names.  Idempotent."""
+    return _unfuse(net, _ORIG_ATTN)

@@ -8,6 +8,8 @@ reference, example/test_vit.py:26-45) next to the raw fp32 forward.
 --fused: the same network with its MLPs fused (utils/fuse.py::fuse_mlp) next to the unfused one, alternating in one process,
 medians over --reps repetitions each, and the per-kernel device time of one forward of each kind: the engine's launch records
 for the GEMMs (k_mlp_fc1, the fc2 sweep), torch's profiler for everything (k_pack*, torch's GELU).
+--fused-attn: a further variant in the same alternation, the attention blocks fused (fuse_attention: k_attn_qk in place of
+matmul1's sweep, torch's `* scale` and softmax and k_pack_dual); with --fused it is MLPs + attention, without it attention alone.
 """
 import argparse
 import json
@@ -87,6 +89,8 @@ def main():
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--fused", action="store_true", help="also time the network with fused MLPs (utils/fuse.py), alternating")
+    ap.add_argument("--fused-attn", action="store_true",
+                    help="also time the network with fused attention (utils/fuse.py::fuse_attention; with --fused: on top of the fused MLPs)")
     ap.add_argument("--json", default=None, help="write the result to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -123,33 +127,56 @@ def main():
           f"logit rel diff {((y_q - y_raw).norm() / y_raw.norm()).item():.3e}")
     res = {"model": a.model, "batch": a.batch, "reps": a.reps, "source_hash": _lib.source_hash(),
            "raw_fp32_ms": t_raw * 1e3, "quant_forward_ms": t_q * 1e3, "quant_vs_fp32": t_raw / t_q}
-    if a.fused:
-        # fused and unfused alternating, repetition by repetition, after one warm-up of each
-        ts = {False: [], True: []}
-        ys = {}
+    if a.fused or a.fused_attn:
+        # the variants alternating, repetition by repetition, after one warm-up of each: (key, fuse the MLPs, fuse the attention)
+        variants = [("unfused", False, False)]
+        if a.fused:
+            variants.append(("fused", True, False))
+        if a.fused_attn:
+            variants.append(("fused_attn", a.fused, True))
+
+        def setup(mlp, attn):
+            fuse.unfuse_mlp(net)
+            fuse.unfuse_attention(net)
+            return (len(fuse.fuse_mlp(net)) if mlp else 0, len(fuse.fuse_attention(net)) if attn else 0)
+
+        ts = {key: [] for key, _, _ in variants}
+        ys, counts = {}, {}
         for rep in range(a.reps + 1):
-            for on in (False, True):
-                fuse.fuse_mlp(net) if on else fuse.unfuse_mlp(net)
-                t, ys[on] = once()
+            for key, mlp, attn in variants:
+                counts[key] = setup(mlp, attn)
+                t, ys[key] = once()
                 if rep:
-                    ts[on].append(t)
-        fused_names = fuse.fuse_mlp(net)
-        t_u, t_f = statistics.median(ts[False]), statistics.median(ts[True])
-        rel = ((ys[True] - ys[False]).norm() / ys[False].norm()).item()
-        print(f"  unfused {t_u * 1e3:.2f} ms, fused MLPs ({len(fused_names)}) {t_f * 1e3:.2f} ms: x{t_u / t_f:.3f}; "
-              f"fused vs fp32 x{t_raw / t_f:.2f}; logit rel diff fused vs unfused {rel:.3e}")
-        res.update({"fused_mlps": len(fused_names), "unfused_ms": t_u * 1e3, "fused_ms": t_f * 1e3, "unfused_over_fused": t_u / t_f,
-                    "fused_vs_fp32": t_raw / t_f, "unfused_ms_all": [t * 1e3 for t in ts[False]], "fused_ms_all": [t * 1e3 for t in ts[True]],
-                    "logit_rel_diff_fused_vs_unfused": rel})
+                    ts[key].append(t)
+        med = {key: statistics.median(v) for key, v in ts.items()}
+        t_u = med["unfused"]
+        res.update({"unfused_ms": t_u * 1e3, "unfused_ms_all": [t * 1e3 for t in ts["unfused"]]})
+        if a.fused:
+            t_f = med["fused"]
+            rel = ((ys["fused"] - ys["unfused"]).norm() / ys["unfused"].norm()).item()
+            print(f"  unfused {t_u * 1e3:.2f} ms, fused MLPs ({counts['fused'][0]}) {t_f * 1e3:.2f} ms: x{t_u / t_f:.3f}; "
+                  f"fused vs fp32 x{t_raw / t_f:.2f}; logit rel diff fused vs unfused {rel:.3e}")
+            res.update({"fused_mlps": counts["fused"][0], "fused_ms": t_f * 1e3, "unfused_over_fused": t_u / t_f,
+                        "fused_vs_fp32": t_raw / t_f, "fused_ms_all": [t * 1e3 for t in ts["fused"]],
+                        "logit_rel_diff_fused_vs_unfused": rel})
+        if a.fused_attn:
+            t_a = med["fused_attn"]
+            base_key = "fused" if a.fused else "unfused"
+            rel = ((ys["fused_attn"] - ys["unfused"]).norm() / ys["unfused"].norm()).item()
+            print(f"  fused attention ({counts['fused_attn'][1]}{' + MLPs' if a.fused else ''}) {t_a * 1e3:.2f} ms: x{med[base_key] / t_a:.3f} "
+                  f"over {base_key}, x{t_u / t_a:.3f} over unfused; vs fp32 x{t_raw / t_a:.2f}; logit rel diff vs unfused {rel:.3e}")
+            res.update({"fused_attentions": counts["fused_attn"][1], "fused_attn_with_mlps": bool(a.fused), "fused_attn_ms": t_a * 1e3,
+                        "unfused_over_fused_attn": t_u / t_a, base_key + "_over_fused_attn": med[base_key] / t_a,
+                        "fused_attn_vs_fp32": t_raw / t_a, "fused_attn_ms_all": [t * 1e3 for t in ts["fused_attn"]],
+                        "logit_rel_diff_fused_attn_vs_unfused": rel})
         kern = {}
-        for on in (False, True):
-            fuse.fuse_mlp(net) if on else fuse.unfuse_mlp(net)
-            key = "fused" if on else "unfused"
+        for key, mlp, attn in variants:
+            setup(mlp, attn)
             kern[key] = {"engine_records": short(engine_records(net, x)), "profiler": short(profiler_kernels(net, x))}
             for row in kern[key]["profiler"] or kern[key]["engine_records"]:
                 print(f"  [{key}] {row['ms']:9.3f} ms  {row['launches']:4d} x  {row['kernel'][:90]}")
         res["kernels_per_forward"] = kern
-        fuse.unfuse_mlp(net)
+        setup(False, False)
     if a.json:
         with open(a.json, "w") as fh:
             json.dump(res, fh, indent=1)

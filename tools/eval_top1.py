@@ -40,7 +40,7 @@ def set_bits(cfg, bits):
 
 
 def evaluate(model, imagenet, weights=None, config="PTQ4ViT", bits=8, calib=32, calib_seed=3, batch=128, max_val=None,
-             workers=0, save_intervals=None, device="cuda", quiet=False, fuse_mlp=False):
+             workers=0, save_intervals=None, device="cuda", quiet=False, fuse_mlp=False, fuse_attn=False):
     """Returns the result dict (see the module docstring).  `weights=None` keeps the seeded random initialisation (tests)."""
     import contextlib
     import importlib
@@ -87,6 +87,10 @@ def evaluate(model, imagenet, weights=None, config="PTQ4ViT", bits=8, calib=32, 
     if fuse_mlp:                               # opt-in: the MLPs' quant_forward as the fused int8 chain (utils/fuse.py)
         from ptq4vit_amd.utils.fuse import fuse_mlp as _fuse
         fused = _fuse(net)
+    fused_attn = []
+    if fuse_attn:                              # opt-in: matmul1 ... matmul2 of every attention block as the fused int8 chain
+        from ptq4vit_amd.utils.fuse import fuse_attention as _fuse_attn
+        fused_attn = _fuse_attn(net)
     t0 = time.time()
     quant = datasets.test_classification(net, test_loader, max_iteration=max_it, description=None if quiet else f"{model} W{bits}A{bits}")
     t_q = time.time() - t0
@@ -95,7 +99,7 @@ def evaluate(model, imagenet, weights=None, config="PTQ4ViT", bits=8, calib=32, 
             "calib_indices_head": [int(i) for i in g.calib_indices(calib, calib_seed)[:8]],
             "fp32_top1": fp32, "quant_top1": quant, "drop": fp32 - quant, "val_images": n_val, "wrapped_modules": len(wrapped),
             "calibration_s": t_cal, "capture_s": cal.timings.get("capture_s"), "search_s": cal.timings.get("search_s"),
-            "fp32_eval_s": t_fp, "quant_eval_s": t_q, "fused_mlps": len(fused), "weights": weights or "random init (seed 0)", **info}
+            "fp32_eval_s": t_fp, "quant_eval_s": t_q, "fused_mlps": len(fused), "fused_attentions": len(fused_attn), "weights": weights or "random init (seed 0)", **info}
 
 
 def main(argv=None):
@@ -113,11 +117,12 @@ def main(argv=None):
     ap.add_argument("--save-intervals", default=None, help="write the calibrated intervals (utils/intervals.py) to this file")
     ap.add_argument("--json", default=None, help="also write the result line to this file")
     ap.add_argument("--fuse-mlp", action="store_true", help="evaluate with the fused int8 MLP forward (utils/fuse.py::fuse_mlp)")
+    ap.add_argument("--fuse-attn", action="store_true", help="evaluate with the fused int8 attention forward (utils/fuse.py::fuse_attention)")
     a = ap.parse_args(argv)
     import ptq4vit_amd
     ptq4vit_amd.configure_runtime()          # GPU_MAX_HW_QUEUES for the search streams, before the first GPU call
     res = evaluate(a.model, a.imagenet, a.weights, a.config, a.bits, a.calib, a.calib_seed, a.batch, a.max_val, a.workers,
-                   a.save_intervals, fuse_mlp=a.fuse_mlp)
+                   a.save_intervals, fuse_mlp=a.fuse_mlp, fuse_attn=a.fuse_attn)
     line = json.dumps(res)
     print(line)
     if a.json:
