@@ -472,8 +472,8 @@ int p4v_mlp_quant_forward(const p4v_mlp_desc* desc, const float* d_w1, const flo
  * d_q [b][h][M][D], d_kT [b][h][D][N], d_v [b][h][N][Dv] through qk.a_stride / qk.b_stride / pv.b_stride (views are read in place);
  * d_qk_A_interval, d_qk_B_interval, d_pv_B_interval [heads]; d_pv_A_interval [heads] (sos: [1]); d_split [1] (sos only);
  * d_out [batch*heads][M][Dv]; d_probs: optional (may be NULL, then nothing is stored for it) [batch*heads][M][N] fp32, the
- * probabilities the planes were quantised from.  d_scratch, scratch_bytes: the workspace and its size -- the workspace contract
- * above holds with p4v_attn_workspace_bytes; a smaller scratch_bytes is refused before any launch.
+ * probabilities the planes were quantised from.  d_ws, ws_bytes: the workspace and its size -- the workspace contract
+ * above holds with p4v_attn_workspace_bytes; a smaller ws_bytes is refused before any launch.
  * ---------------------------------------------------------------------------------------- */
 typedef struct p4v_attn_desc {
     p4v_matmul_desc qk, pv;
@@ -485,8 +485,8 @@ size_t p4v_attn_workspace_bytes(const p4v_attn_desc* desc);
 
 int p4v_attn_quant_forward(const p4v_attn_desc* desc, const float* d_q, const float* d_kT, const float* d_v,
                            const float* d_qk_A_interval, const float* d_qk_B_interval, const float* d_pv_A_interval,
-                           const float* d_pv_B_interval, const float* d_split, float* d_out, float* d_probs, void* d_scratch,
-                           size_t scratch_bytes, void* stream);
+                           const float* d_pv_B_interval, const float* d_split, float* d_out, float* d_probs, void* d_ws,
+                           size_t ws_bytes, void* stream);
 
 /* d_A_interval: [heads] (sos: [1]); d_B_interval: [heads]; d_split: [1] (sos only); d_out: [batch*heads][M][N] */
 int p4v_matmul_quant_forward(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_A_interval,

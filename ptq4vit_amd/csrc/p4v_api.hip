@@ -3020,16 +3020,88 @@ int linear_impl(const p4v_linear_desc* d, const LinearTensors& t, const Stage& s
 }
 
 // ------------------------------------------------------------------------------------------------
-// Fused MLP forward (p4v_mlp_quant_forward): fc1 -> GELU -> fc2's activation quantiser -> fc2 with int8 in between
+// Fused forwards: a producer kernel writes the int8 row plane(s) the consumer's forward pass reads
 // ------------------------------------------------------------------------------------------------
-// fc1's part: x and W1 packed as LinearCall::forward_pass packs them (pack_operand, k_scale_table), then k_mlp_fc1, whose
-// epilogue writes fc2's row plane(s) -- the fp32 hidden tensor, torch's GELU over it and k_pack_dual / k_pack1 of it are gone.
-// fc2's part: its forward pass as run_pass runs it, the row operand prepacked (Operand.prepacked): same sweep kernel, same epilogue.
-// Where the planes of the calling thread's last call lie in its workspace (p4v_debug_mlp_planes: the tests read them there)
-struct MlpPlanes { size_t off1 = 0, off2 = 0; long rows = 0, cols = 0; int twin = 0; };
-thread_local MlpPlanes g_mlp_planes;
-constexpr int MLP_RECORD_KIND = 16;
+// Where the planes of the calling thread's last call lie in its workspace (p4v_debug_mlp_planes / p4v_debug_attn_planes: the
+// tests read them there)
+struct FusedPlanes { size_t off1 = 0, off2 = 0; long rows = 0, cols = 0; int twin = 0; };
+thread_local FusedPlanes g_mlp_planes, g_attn_planes;
+constexpr int MLP_RECORD_KIND = 16, ATTN_RECORD_KIND = 17;
 
+// One producer -> consumer chain, in the order its caller walks it: plan_consumer, produce, consume.
+struct FusedChain {
+    struct Packed { char *rows, *cols; float* S1; int Kp, Np; };    // the producer's operand planes [Z][Mp | Np][Kp] and its scale table
+    Ctx& c;
+    const char *who, *consumer;                                     // for the messages: "mlp" / "attn", "fc2" / "p v"
+    Pass fp2{};                                                     // the consumer's forward pass
+    SweepPlan pl2{};
+    int Z = 1, Mp = 0, Kp = 0;                                      // the consumer's row plane(s): [Z][Mp][Kp] int8
+    bool twin = false;
+    char *P1 = nullptr, *P2 = nullptr;                              // (null in the sizing run: it carves nothing)
+
+    // The consumer's pass first: its plan says how large the row plane(s) are.
+    int plan_consumer(const Pass& fwd, int Z_, bool twin_) {
+        fp2 = fwd; Z = Z_; twin = twin_;
+        CHK(plan_sweep(c, fp2, pl2));
+        if (pl2.cin_fix != 0 || pl2.merged7 || pl2.esz != 1) return fail(P4V_ERR_UNSUPPORTED, "%s: %s's sweep does not read row-major int8 planes", who, consumer);
+        Mp = pl2.Mp; Kp = pl2.Kp;
+        P1 = c.ws.get<char>((size_t)Z * Mp * Kp);
+        P2 = twin ? c.ws.get<char>((size_t)Z * Mp * Kp) : nullptr;
+        return 0;
+    }
+    // The producer: both operands of its forward pass `fp1` (reduction length K1, `ncols` columns, `nscale` scale entries) packed
+    // as run_pass would pack them (pack_operand, k_scale_table) into scratch that is given back at the end, then -- unless the
+    // run is dry -- `launch(Packed)`, which enqueues the kernel that writes P1 / P2.
+    template <class Launch> int produce(Pass fp1, int K1, int ncols, int nscale, FusedPlanes& where, Launch&& launch) {
+        const size_t mark = c.ws.off;
+        Packed pk{};
+        pk.Kp = (int)rup(K1, 64); pk.Np = (int)rup(ncols, SW_BN);
+        SweepPlan pl1{};                                            // what pack_operand reads of a plan: the plane geometry
+        pl1.esz = 1; pl1.Mp = Mp; pl1.Np = pl1.NpB = pk.Np; pl1.Kp = pk.Kp; pl1.cin_fix = 0;
+        pk.rows = c.ws.get<char>((size_t)Z * Mp * pk.Kp);
+        pk.cols = c.ws.get<char>((size_t)Z * pk.Np * pk.Kp);
+        pk.S1 = c.ws.get<float>((size_t)nscale);
+        if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", c.ws.off);
+        fp1.s1.S = pk.S1; fp1.s1.C = 1; fp1.s1.nblk = fp1.s_cs;
+        CHK(launch_scale(c, fp1.s1));
+        const PassBufs nb{};
+        CHK(pack_operand(c, fp1, pl1, nb, fp1.row, pk.rows, false, 0, 1));
+        CHK(pack_operand(c, fp1, pl1, nb, fp1.col, pk.cols, true, 0, 1));
+        if (!c.dry) {
+            CHK(launch(pk));
+            where = FusedPlanes{(size_t)(P1 - c.ws.base), P2 ? (size_t)(P2 - c.ws.base) : 0, (long)Z * Mp, Kp, twin ? 1 : 0};
+        }
+        c.ws.off = mark;
+        return 0;
+    }
+    // The consumer's pass as run_pass runs it, the row operand prepacked (Operand.prepacked): same sweep kernel, same epilogue.
+    int consume() {
+        fp2.row.prepacked = true; fp2.row.plane = P1;
+        if (twin) { fp2.row2.prepacked = true; fp2.row2.plane = P2; }
+        return run_pass(c, fp2);
+    }
+};
+// the dry run of the planner: the envelope's verdict, and the bytes the call needs
+template <class D, class T> int fused_sizing_run(int (*impl)(const D*, const T&, const T&, Ctx&), const D* d, size_t* need) {
+    Ctx c = Ctx::sizing();
+    CHK(impl(d, T{}, T{}, c));
+    *need = c.sized_bytes();
+    return 0;
+}
+// A fused entry point behind its pointer checks.  The producer's launches precede the planning of the consumer's pass: the whole
+// need is checked here, before the first of them.
+template <class D, class T> int fused_call(int (*impl)(const D*, const T&, const T&, Ctx&), const D* d, const T& t1, const T& t2, void* d_ws,
+                                           size_t ws_bytes, void* stream) {
+    size_t need = 0;
+    CHK(fused_sizing_run(impl, d, &need));
+    if (ws_bytes < need) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", need);
+    Ctx c = Ctx::on(stream, d_ws, ws_bytes);
+    return impl(d, t1, t2, c);
+}
+
+// ---- p4v_mlp_quant_forward: fc1 -> GELU -> fc2's activation quantiser -> fc2 with int8 in between ------------------------------
+// The producer is k_mlp_fc1 on x and W1: its epilogue writes fc2's row plane(s) -- the fp32 hidden tensor, torch's GELU over it
+// and k_pack_dual / k_pack1 of it are gone.
 // `t1`, `t2`: the two layers' records as p4v_linear_quant_forward fills them -- t1.fwd_out is the optional fp32 copy of the hidden
 // tensor (fc1 stores no other output), t2.X stays null (fc2 reads fc1's planes).
 int mlp_impl(const p4v_mlp_desc* d, const LinearTensors& t1, const LinearTensors& t2, Ctx& c) {
@@ -3048,60 +3120,27 @@ int mlp_impl(const p4v_mlp_desc* d, const LinearTensors& t1, const LinearTensors
     CHK(L1.build());
     CHK(L2.build());
     if (!L1.i8 || !L2.i8) return fail(P4V_ERR_UNSUPPORTED, "mlp: int8 planes only");
-    // fc2's pass first: its plan says how large the row plane(s) are
-    Pass fp2 = L2.forward_pass();
-    SweepPlan pl2;
-    CHK(plan_sweep(c, fp2, pl2));
-    if (pl2.cin_fix != 0 || pl2.merged7 || pl2.esz != 1) return fail(P4V_ERR_UNSUPPORTED, "mlp: fc2's sweep does not read row-major int8 planes");
+    FusedChain ch{c, "mlp", "fc2"};
+    CHK(ch.plan_consumer(L2.forward_pass(), 1, L2.twin));      // Kp = roundup64(hidden)
     const int M = L1.M, K1 = L1.K, Hd = L1.N;
-    const int Mp = pl2.Mp, Kp = pl2.Kp;                       // Kp = roundup64(hidden)
-    const int K1p = (int)rup(K1, 64), Hp = (int)rup(Hd, SW_BN);
-    char* P1 = c.ws.get<char>((size_t)Mp * Kp);
-    char* P2 = L2.twin ? c.ws.get<char>((size_t)Mp * Kp) : nullptr;
-    {
-        const size_t mark = c.ws.off;
-        Pass fp1 = L1.forward_pass();
-        SweepPlan pl1{};                                       // what pack_operand reads of a plan: the plane geometry
-        pl1.esz = 1; pl1.Mp = Mp; pl1.Np = pl1.NpB = Hp; pl1.Kp = K1p; pl1.cin_fix = 0;
-        char* xa = c.ws.get<char>((size_t)Mp * K1p);
-        char* wb = c.ws.get<char>((size_t)Hp * K1p);
-        float* S1 = c.ws.get<float>((size_t)L1.nV);
-        if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", c.ws.off);
-        fp1.s1.S = S1; fp1.s1.C = 1; fp1.s1.nblk = fp1.s_cs;
-        CHK(launch_scale(c, fp1.s1));
-        const PassBufs nb{};
-        CHK(pack_operand(c, fp1, pl1, nb, fp1.row, xa, false, 0, 1));
-        CHK(pack_operand(c, fp1, pl1, nb, fp1.col, wb, true, 0, 1));
-        if (!c.dry) {
-            MlpFc1Params q{};
-            q.A = xa; q.B = wb; q.ldk = K1p; q.ktiles = K1p / SW_BKB;
-            q.S1 = S1; q.s_cs = L1.nV; q.sb_div = L1.crb_rows;
-            q.bias = t1.bias; q.M = M; q.N = Hd; q.mtiles = Mp / SW_BM; q.ntiles = Hp / SW_BN;
-            q.q1 = t2.a_iv; q.q2 = nullptr; q.q2_const = L2.a_neg;
-            q.lo1 = L2.twin ? 0 : -L2.aq; q.hi1 = L2.aq - 1; q.lo2 = -L2.aq; q.hi2 = 0;
-            q.P1 = (int8_t*)P1; q.P2 = (int8_t*)P2; q.Kp = Kp; q.hidden = t1.fwd_out;
-            g_alg_macs_cand = (double)M * Hd * K1;
-            g_alg_bytes = 4.0 * ((double)M * K1 + (double)Hd * K1) + (double)M * Hd * (L2.twin ? 2 : 1);
-            g_exec_frac = 1.0;
-            const StatInfo si = stat_info(MLP_RECORD_KIND, (double)Mp * Hp * K1p, g_alg_macs_cand, q.mtiles * q.ntiles, 1, g_alg_bytes);
-            const dim3 grid(q.mtiles * q.ntiles), block(512);
-            const size_t lds = 2 * 2 * SW_TILE_BYTES;
-            if (L2.twin) CHK(enqueue(c, KERN1_T(MlpFc1Params, k_mlp_fc1, true), grid, block, lds, q, &si));
-            else CHK(enqueue(c, KERN1_T(MlpFc1Params, k_mlp_fc1, false), grid, block, lds, q, &si));
-            g_mlp_planes = MlpPlanes{(size_t)(P1 - c.ws.base), P2 ? (size_t)(P2 - c.ws.base) : 0, Mp, Kp, L2.twin ? 1 : 0};
-        }
-        c.ws.off = mark;
-    }
-    fp2.row.prepacked = true; fp2.row.plane = P1;             // (null in the sizing run: it carves nothing)
-    if (L2.twin) { fp2.row2.prepacked = true; fp2.row2.plane = P2; }
-    return run_pass(c, fp2);
-}
-// the dry run of the planner: the envelope's verdict, and the bytes the call needs
-int mlp_sizing_run(const p4v_mlp_desc* d, size_t* need) {
-    Ctx c = Ctx::sizing();
-    CHK(mlp_impl(d, LinearTensors{}, LinearTensors{}, c));
-    *need = c.sized_bytes();
-    return 0;
+    CHK(ch.produce(L1.forward_pass(), K1, Hd, L1.nV, g_mlp_planes, [&](const FusedChain::Packed& pk) -> int {
+        MlpFc1Params q{};
+        q.A = pk.rows; q.B = pk.cols; q.ldk = pk.Kp; q.ktiles = pk.Kp / SW_BKB;
+        q.S1 = pk.S1; q.s_cs = L1.nV; q.sb_div = L1.crb_rows;
+        q.bias = t1.bias; q.M = M; q.N = Hd; q.mtiles = ch.Mp / SW_BM; q.ntiles = pk.Np / SW_BN;
+        q.q1 = t2.a_iv; q.q2 = nullptr; q.q2_const = L2.a_neg;
+        q.lo1 = L2.twin ? 0 : -L2.aq; q.hi1 = L2.aq - 1; q.lo2 = -L2.aq; q.hi2 = 0;
+        q.P1 = (int8_t*)ch.P1; q.P2 = (int8_t*)ch.P2; q.Kp = ch.Kp; q.hidden = t1.fwd_out;
+        g_alg_macs_cand = (double)M * Hd * K1;
+        g_alg_bytes = 4.0 * ((double)M * K1 + (double)Hd * K1) + (double)M * Hd * (L2.twin ? 2 : 1);
+        g_exec_frac = 1.0;
+        const StatInfo si = stat_info(MLP_RECORD_KIND, (double)ch.Mp * pk.Np * pk.Kp, g_alg_macs_cand, q.mtiles * q.ntiles, 1, g_alg_bytes);
+        const dim3 grid(q.mtiles * q.ntiles), block(512);
+        const size_t lds = 2 * 2 * SW_TILE_BYTES;
+        return L2.twin ? enqueue(c, KERN1_T(MlpFc1Params, k_mlp_fc1, true), grid, block, lds, q, &si)
+                       : enqueue(c, KERN1_T(MlpFc1Params, k_mlp_fc1, false), grid, block, lds, q, &si);
+    }));
+    return ch.consume();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3385,21 +3424,12 @@ int matmul_impl(const p4v_matmul_desc* d, const MatMulTensors& t, const Stage& s
     return 0;
 }
 
-// ------------------------------------------------------------------------------------------------
-// Fused attention forward (p4v_attn_quant_forward): matmul1 -> * scale -> softmax -> matmul2's A quantiser -> matmul2, int8 in between
-// ------------------------------------------------------------------------------------------------
-// matmul1's part: q and k^T packed as MatMulCall::forward_pass packs them (pack_operand, k_scale_table), then k_attn_qk, which
-// writes matmul2's row plane(s) -- the fp32 score tensor, torch's `* scale` and softmax over it and k_pack_dual of it are gone.
-// matmul2's part: its forward pass as run_pass runs it, the row operand prepacked ([Z][Mp][Kp]: the tiled sweeps step Mp * Kp
-// per z, the plane's own layout).
-// Where the planes of the calling thread's last call lie in its workspace (p4v_debug_attn_planes: the tests read them there)
-struct AttnPlanes { size_t off1 = 0, off2 = 0; long rows = 0, cols = 0; int twin = 0; };
-thread_local AttnPlanes g_attn_planes;
-constexpr int ATTN_RECORD_KIND = 17;
-
-// `t1`, `t2`: the two MatMuls' records as p4v_matmul_quant_forward fills them -- t1.fwd_out stays null (matmul1 stores nothing),
-// t2.A stays null (matmul2 reads k_attn_qk's planes); `probs`: the optional fp32 copy of the probabilities [Z][M][N].
-int attn_impl(const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulTensors& t2, float* probs, Ctx& c) {
+// ---- p4v_attn_quant_forward: matmul1 -> * scale -> softmax -> matmul2's A quantiser -> matmul2, int8 in between (the FusedChain above)
+// The producer is k_attn_qk on q and k^T: it writes matmul2's row plane(s) ([Z][Mp][Kp]: the tiled sweeps step Mp * Kp per z, the
+// plane's own layout) -- the fp32 score tensor, torch's `* scale` and softmax over it and k_pack_dual of it are gone.
+// `t1`, `t2`: the two MatMuls' records as p4v_matmul_quant_forward fills them -- t1.fwd_out is the optional fp32 copy of the
+// probabilities [Z][M][N] (matmul1 stores no other output), t2.A stays null (matmul2 reads k_attn_qk's planes).
+int attn_impl(const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulTensors& t2, Ctx& c) {
     const p4v_matmul_desc* d1 = &d->qk;
     const p4v_matmul_desc* d2 = &d->pv;
     // the envelope, before anything is planned or launched
@@ -3415,64 +3445,31 @@ int attn_impl(const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulTenso
     CHK(m2.build());
     cvt_bias(c);     // (first call of the process: probe the conversion quant16_sat8 relies on)
     CHK(q_wait_inputs(c));
-    // matmul2's pass first: its plan says how large the row plane(s) are
-    Pass fp2 = m2.forward_pass();
-    SweepPlan pl2;
-    CHK(plan_sweep(c, fp2, pl2));
-    if (pl2.cin_fix != 0 || pl2.merged7 || pl2.esz != 1) return fail(P4V_ERR_UNSUPPORTED, "attn: p v's sweep does not read row-major int8 planes");
     const int Z = m1.Z, H = m1.H, M = m1.M, N = m1.N, K1 = m1.K;
-    const int Mp = pl2.Mp, Kp = pl2.Kp;                        // Kp = roundup64(N)
-    const int K1p = (int)rup(K1, 64), Np1 = (int)rup(N, SW_BN);
     const bool twin = d2->sos != 0;
-    if (Mp % SW_BM || (long)Z * (Mp / SW_BM) >= (1L << 31)) return fail(P4V_ERR_UNSUPPORTED, "attn: %d x %d row tiles", Z, Mp / SW_BM);
-    char* P1 = c.ws.get<char>((size_t)Z * Mp * Kp);
-    char* P2 = twin ? c.ws.get<char>((size_t)Z * Mp * Kp) : nullptr;
-    {
-        const size_t mark = c.ws.off;
-        Pass fp1 = m1.forward_pass();
-        SweepPlan pl1{};                                       // what pack_operand reads of a plan: the plane geometry
-        pl1.esz = 1; pl1.Mp = Mp; pl1.Np = pl1.NpB = Np1; pl1.Kp = K1p; pl1.cin_fix = 0;
-        char* qa = c.ws.get<char>((size_t)Z * Mp * K1p);
-        char* kb = c.ws.get<char>((size_t)Z * Np1 * K1p);
-        float* S1 = c.ws.get<float>((size_t)H);
-        if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", c.ws.off);
-        fp1.s1.S = S1; fp1.s1.C = 1; fp1.s1.nblk = fp1.s_cs;
-        CHK(launch_scale(c, fp1.s1));
-        const PassBufs nb{};
-        CHK(pack_operand(c, fp1, pl1, nb, fp1.row, qa, false, 0, 1));
-        CHK(pack_operand(c, fp1, pl1, nb, fp1.col, kb, true, 0, 1));
-        if (!c.dry) {
-            AttnQkParams q{};
-            q.Q = qa; q.Kt = kb; q.q_zs = (long)Mp * K1p; q.k_zs = (long)Np1 * K1p; q.ldk = K1p; q.ktiles = K1p / SW_BKB;
-            q.S1 = S1; q.H = H; q.scale = d->scale;
-            q.M = M; q.N = N; q.Mp = Mp; q.Kp = Kp;
-            q.qs = twin ? t2.split : t2.A_iv; q.qs_headwise = twin ? 0 : 1;
-            q.lo = -m2.Aq; q.hi = m2.Aq - 1; q.qm1 = (float)(m2.Aq - 1);
-            q.P1 = (int8_t*)P1; q.P2 = (int8_t*)P2; q.probs = probs;
-            q.mtiles = Mp / SW_BM; q.nwg = Z * q.mtiles;
-            g_alg_macs_cand = (double)Z * M * N * K1;
-            g_alg_bytes = 4.0 * ((double)Z * M * K1 + (double)Z * N * K1) + (double)Z * M * N * (twin ? 2 : 1);
-            g_exec_frac = 1.0;
-            // (three walks over the keys: the maximum, the sum, the write pass)
-            const StatInfo si = stat_info(ATTN_RECORD_KIND, 3.0 * (double)Z * Mp * (double)rup(N, 32) * K1p, g_alg_macs_cand, q.nwg, 1, g_alg_bytes);
-            const dim3 grid(q.nwg), block(256);
-            const size_t lds = (size_t)4 * (twin ? 2 : 1) * 32 * ATTN_OROW;
-            if (twin) CHK(enqueue(c, KERN1_T(AttnQkParams, k_attn_qk, true), grid, block, lds, q, &si));
-            else CHK(enqueue(c, KERN1_T(AttnQkParams, k_attn_qk, false), grid, block, lds, q, &si));
-            g_attn_planes = AttnPlanes{(size_t)(P1 - c.ws.base), P2 ? (size_t)(P2 - c.ws.base) : 0, (long)Z * Mp, Kp, twin ? 1 : 0};
-        }
-        c.ws.off = mark;
-    }
-    fp2.row.prepacked = true; fp2.row.plane = P1;             // (null in the sizing run: it carves nothing)
-    if (twin) { fp2.row2.prepacked = true; fp2.row2.plane = P2; }
-    return run_pass(c, fp2);
-}
-// the dry run of the planner: the envelope's verdict, and the bytes the call needs
-int attn_sizing_run(const p4v_attn_desc* d, size_t* need) {
-    Ctx c = Ctx::sizing();
-    CHK(attn_impl(d, MatMulTensors{}, MatMulTensors{}, nullptr, c));
-    *need = c.sized_bytes();
-    return 0;
+    FusedChain ch{c, "attn", "p v"};
+    CHK(ch.plan_consumer(m2.forward_pass(), Z, twin));         // Kp = roundup64(N)
+    if (ch.Mp % SW_BM || (long)Z * (ch.Mp / SW_BM) >= (1L << 31)) return fail(P4V_ERR_UNSUPPORTED, "attn: %d x %d row tiles", Z, ch.Mp / SW_BM);
+    CHK(ch.produce(m1.forward_pass(), K1, N, H, g_attn_planes, [&](const FusedChain::Packed& pk) -> int {
+        AttnQkParams q{};
+        q.Q = pk.rows; q.Kt = pk.cols; q.q_zs = (long)ch.Mp * pk.Kp; q.k_zs = (long)pk.Np * pk.Kp; q.ldk = pk.Kp; q.ktiles = pk.Kp / SW_BKB;
+        q.S1 = pk.S1; q.H = H; q.scale = d->scale;
+        q.M = M; q.N = N; q.Mp = ch.Mp; q.Kp = ch.Kp;
+        q.qs = twin ? t2.split : t2.A_iv; q.qs_headwise = twin ? 0 : 1;
+        q.lo = -m2.Aq; q.hi = m2.Aq - 1; q.qm1 = (float)(m2.Aq - 1);
+        q.P1 = (int8_t*)ch.P1; q.P2 = (int8_t*)ch.P2; q.probs = t1.fwd_out;
+        q.mtiles = ch.Mp / SW_BM; q.nwg = Z * q.mtiles;
+        g_alg_macs_cand = (double)Z * M * N * K1;
+        g_alg_bytes = 4.0 * ((double)Z * M * K1 + (double)Z * N * K1) + (double)Z * M * N * (twin ? 2 : 1);
+        g_exec_frac = 1.0;
+        // (three walks over the keys: the maximum, the sum, the write pass)
+        const StatInfo si = stat_info(ATTN_RECORD_KIND, 3.0 * (double)Z * ch.Mp * (double)rup(N, 32) * pk.Kp, g_alg_macs_cand, q.nwg, 1, g_alg_bytes);
+        const dim3 grid(q.nwg), block(256);
+        const size_t lds = (size_t)4 * (twin ? 2 : 1) * 32 * ATTN_OROW;
+        return twin ? enqueue(c, KERN1_T(AttnQkParams, k_attn_qk, true), grid, block, lds, q, &si)
+                    : enqueue(c, KERN1_T(AttnQkParams, k_attn_qk, false), grid, block, lds, q, &si);
+    }));
+    return ch.consume();
 }
 
 // ---- MatMul with row / column sub-blocks (n_V, n_H > 1; reference matmul.py:109-138, 419-440, 483-563) -------------------------
@@ -3856,7 +3853,7 @@ int p4v_linear_quant_forward(const p4v_linear_desc* desc, const float* d_weight,
 
 size_t p4v_mlp_workspace_bytes(const p4v_mlp_desc* desc) {
     size_t need = 0;
-    return (desc && mlp_sizing_run(desc, &need) == 0) ? need : 0;
+    return (desc && fused_sizing_run(mlp_impl, desc, &need) == 0) ? need : 0;
 }
 
 int p4v_mlp_quant_forward(const p4v_mlp_desc* desc, const float* d_w1, const float* d_b1, const float* d_w2, const float* d_b2,
@@ -3864,21 +3861,16 @@ int p4v_mlp_quant_forward(const p4v_mlp_desc* desc, const float* d_w1, const flo
                           const float* d_a2_interval, float* d_out, float* d_hidden, void* d_ws, size_t ws_bytes, void* stream) {
     CHK(entry_checks("p4v_mlp_quant_forward", desc && d_w1 && d_w2 && d_x && d_w1_interval && d_a1_interval && d_w2_interval && d_a2_interval && d_out,
                      desc && ((desc->fc1.has_bias && !d_b1) || (desc->fc2.has_bias && !d_b2)), d_ws, "the bias is null"));
-    // fc1's launches precede the planning of fc2's pass: the whole need is checked here, before the first of them
-    size_t need = 0;
-    CHK(mlp_sizing_run(desc, &need));
-    if (ws_bytes < need) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", need);
-    Ctx c = Ctx::on(stream, d_ws, ws_bytes);
-    return mlp_impl(desc,
-                    {.W = d_w1, .bias = desc->fc1.has_bias ? d_b1 : nullptr, .X = d_x, .w_iv = const_cast<float*>(d_w1_interval),
-                     .a_iv = const_cast<float*>(d_a1_interval), .fwd_out = d_hidden},
-                    {.W = d_w2, .bias = desc->fc2.has_bias ? d_b2 : nullptr, .w_iv = const_cast<float*>(d_w2_interval),
-                     .a_iv = const_cast<float*>(d_a2_interval), .fwd_out = d_out}, c);
+    return fused_call(mlp_impl, desc,
+                      {.W = d_w1, .bias = desc->fc1.has_bias ? d_b1 : nullptr, .X = d_x, .w_iv = const_cast<float*>(d_w1_interval),
+                       .a_iv = const_cast<float*>(d_a1_interval), .fwd_out = d_hidden},
+                      {.W = d_w2, .bias = desc->fc2.has_bias ? d_b2 : nullptr, .w_iv = const_cast<float*>(d_w2_interval),
+                       .a_iv = const_cast<float*>(d_a2_interval), .fwd_out = d_out}, d_ws, ws_bytes, stream);
 }
 
 size_t p4v_attn_workspace_bytes(const p4v_attn_desc* desc) {
     size_t need = 0;
-    return (desc && attn_sizing_run(desc, &need) == 0) ? need : 0;
+    return (desc && fused_sizing_run(attn_impl, desc, &need) == 0) ? need : 0;
 }
 
 int p4v_attn_quant_forward(const p4v_attn_desc* desc, const float* d_q, const float* d_kT, const float* d_v,
@@ -3889,15 +3881,10 @@ int p4v_attn_quant_forward(const p4v_attn_desc* desc, const float* d_q, const fl
         return fail(P4V_ERR_INVALID, "p4v_attn_quant_forward: null pointer");
     if (desc->pv.sos && !d_split) return fail(P4V_ERR_INVALID, "p4v_attn_quant_forward: sos needs d_split");
     CHK(ws_aligned(d_ws));
-    // matmul1's launches precede the planning of matmul2's pass: the whole need is checked here, before the first of them
-    size_t need = 0;
-    CHK(attn_sizing_run(desc, &need));
-    if (ws_bytes < need) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", need);
-    Ctx c = Ctx::on(stream, d_ws, ws_bytes);
-    return attn_impl(desc,
-                     {.A = d_q, .B = d_kT, .A_iv = const_cast<float*>(d_qk_A_interval), .B_iv = const_cast<float*>(d_qk_B_interval)},
-                     {.B = d_v, .A_iv = const_cast<float*>(d_pv_A_interval), .B_iv = const_cast<float*>(d_pv_B_interval),
-                      .split = const_cast<float*>(d_split), .fwd_out = d_out}, d_probs, c);
+    return fused_call(attn_impl, desc,
+                      {.A = d_q, .B = d_kT, .A_iv = const_cast<float*>(d_qk_A_interval), .B_iv = const_cast<float*>(d_qk_B_interval), .fwd_out = d_probs},
+                      {.B = d_v, .A_iv = const_cast<float*>(d_pv_A_interval), .B_iv = const_cast<float*>(d_pv_B_interval),
+                       .split = const_cast<float*>(d_split), .fwd_out = d_out}, d_ws, ws_bytes, stream);
 }
 
 int p4v_matmul_quant_forward(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_A_interval,
@@ -4347,19 +4334,13 @@ int p4v_debug_arena_ranges(uint64_t* out, int cap) {
     return n;
 }
 
-int p4v_debug_mlp_planes(uint64_t* out) {
-    if (!out) return fail(P4V_ERR_INVALID, "p4v_debug_mlp_planes: null pointer");
-    const MlpPlanes& m = g_mlp_planes;
+static int planes_out(const FusedPlanes& m, uint64_t* out, const char* who, const char* call) {
+    if (!out) return fail(P4V_ERR_INVALID, "%s: null pointer", who);
     out[0] = m.off1; out[1] = m.off2; out[2] = (uint64_t)m.rows; out[3] = (uint64_t)m.cols; out[4] = (uint64_t)m.twin;
-    return m.rows > 0 ? 0 : fail(P4V_ERR_INVALID, "p4v_debug_mlp_planes: no p4v_mlp_quant_forward call on this thread yet");
+    return m.rows > 0 ? 0 : fail(P4V_ERR_INVALID, "%s: no %s call on this thread yet", who, call);
 }
-
-int p4v_debug_attn_planes(uint64_t* out) {
-    if (!out) return fail(P4V_ERR_INVALID, "p4v_debug_attn_planes: null pointer");
-    const AttnPlanes& m = g_attn_planes;
-    out[0] = m.off1; out[1] = m.off2; out[2] = (uint64_t)m.rows; out[3] = (uint64_t)m.cols; out[4] = (uint64_t)m.twin;
-    return m.rows > 0 ? 0 : fail(P4V_ERR_INVALID, "p4v_debug_attn_planes: no p4v_attn_quant_forward call on this thread yet");
-}
+int p4v_debug_mlp_planes(uint64_t* out) { return planes_out(g_mlp_planes, out, "p4v_debug_mlp_planes", "p4v_mlp_quant_forward"); }
+int p4v_debug_attn_planes(uint64_t* out) { return planes_out(g_attn_planes, out, "p4v_debug_attn_planes", "p4v_attn_quant_forward"); }
 
 int p4v_debug_sos_sweep(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_out, const float* d_grad,
                         int n_cands, int c_lo, int c_hi, int known_cands, float* d_scores, void* d_workspace, size_t workspace_bytes,

@@ -243,6 +243,26 @@ def _mlp_layer_desc(batch, tokens, layer):
                            int(layer.get("bias") is not None), _lib.RESERVED_FORWARD_ONLY)
 
 
+def _fused_forward(kind, d, tensors, dev, res, want_planes, z=None):
+    """The tail of the fused forwards (`kind`: mlp / attn): p4v_<kind>_workspace_bytes, the workspace, the checked call
+    p4v_<kind>_quant_forward(d, *tensors, workspace, its size, stream).  Returns the tuple `res` -- its one member alone --, with
+    `want_planes` followed by the int8 plane(s) p4v_debug_<kind>_planes locates in the workspace: [rows][cols] each, or `z`
+    of [rows / z][cols]."""
+    lib = _lib.load()
+    ws = workspace(dev, _need(getattr(lib, f"p4v_{kind}_workspace_bytes"), d, f"p4v_{kind}_workspace_bytes"))
+    with torch.cuda.device(dev):
+        rc = getattr(lib, f"p4v_{kind}_quant_forward")(C.byref(d), *[ptr(t) for t in tensors], ptr(ws), ws.numel(), stream_ptr(dev))
+    _lib.check(rc, f"p4v_{kind}_quant_forward")
+    if want_planes:
+        info = (C.c_uint64 * 5)()
+        _lib.check(getattr(lib, f"p4v_debug_{kind}_planes")(info), f"p4v_debug_{kind}_planes")
+        off1, off2, rows, cols, twin = (int(v) for v in info)
+        shape = (rows, cols) if z is None else (z, rows // z, cols)
+        take = lambda off: ws[off:off + rows * cols].view(torch.int8).reshape(shape).clone()
+        res += ((take(off1), take(off2)) if twin else (take(off1),),)
+    return res[0] if len(res) == 1 else res
+
+
 def mlp_quant_forward(*, x, fc1, fc2, want_hidden=False, want_planes=False):
     """fc2(GELU(fc1(x))) of two calibrated Linear layers in quant_forward, fused (p4v_mlp_quant_forward): fc1's int8 GEMM ends
     in the exact GELU and fc2's activation quantiser and writes fc2's int8 plane(s); no fp32 hidden tensor in between.
@@ -250,7 +270,6 @@ def mlp_quant_forward(*, x, fc1, fc2, want_hidden=False, want_planes=False):
     optionally n_H, n_a, postgelu (fc2: the post-GELU twin).  Returns out, or (out, hidden) with `want_hidden` -- the fp32 GELU
     output the planes were quantised from --, with `want_planes` also the padded int8 plane(s) as the call left them in its
     workspace (a tuple of one or two [rows_padded][cols_padded] tensors; for the tests)."""
-    lib = _lib.load()
     dev = device_of(x, fc1["weight"])
     x = to_dev(x, dev).contiguous()
     batch, K = x.shape[0], x.shape[-1]
@@ -260,25 +279,12 @@ def mlp_quant_forward(*, x, fc1, fc2, want_hidden=False, want_planes=False):
         t[name] = (to_dev(layer["weight"], dev).contiguous(), to_dev(layer.get("bias"), dev),
                    to_dev(layer["w_interval"], dev).reshape(-1).contiguous(), to_dev(layer["a_interval"], dev).reshape(-1).contiguous())
     d = _lib.MlpDesc(_mlp_layer_desc(batch, tokens, fc1), _mlp_layer_desc(batch, tokens, fc2))
-    need = _need(lib.p4v_mlp_workspace_bytes, d, "p4v_mlp_workspace_bytes")
-    ws = workspace(dev, need)
     hidden_n, out_n = fc1["weight"].shape[0], fc2["weight"].shape[0]
     out = torch.empty(x.shape[:-1] + (out_n,), dtype=torch.float32, device=dev)
     hidden = torch.empty(x.shape[:-1] + (hidden_n,), dtype=torch.float32, device=dev) if want_hidden else None
     (w1, b1, w1_iv, a1_iv), (w2, b2, w2_iv, a2_iv) = t["fc1"], t["fc2"]
-    with torch.cuda.device(dev):
-        rc = lib.p4v_mlp_quant_forward(C.byref(d), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(x), ptr(w1_iv), ptr(a1_iv), ptr(w2_iv),
-                                       ptr(a2_iv), ptr(out), ptr(hidden), ptr(ws), ws.numel(), stream_ptr(dev))
-    _lib.check(rc, "p4v_mlp_quant_forward")
-    res = (out, hidden) if want_hidden else out
-    if want_planes:
-        info = (C.c_uint64 * 5)()
-        _lib.check(lib.p4v_debug_mlp_planes(info), "p4v_debug_mlp_planes")
-        off1, off2, rows, cols, twin = (int(v) for v in info)
-        take = lambda off: ws[off:off + rows * cols].view(torch.int8).reshape(rows, cols).clone()
-        planes = (take(off1), take(off2)) if twin else (take(off1),)
-        res = (res if isinstance(res, tuple) else (res,)) + (planes,)
-    return res
+    return _fused_forward("mlp", d, (w1, b1, w2, b2, x, w1_iv, a1_iv, w2_iv, a2_iv, out, hidden), dev,
+                          (out, hidden) if want_hidden else (out,), want_planes)
 
 
 def _attn_matmul_desc(d, A_shape, A_stride, B, side, what):
@@ -303,7 +309,6 @@ def attn_quant_forward(*, q, kT, v, scale, qk, pv, want_probs=False, want_planes
     `want_probs` -- the fp32 probabilities the planes were quantised from --, with `want_planes` also the padded int8
     plane(s) as the call left them in its workspace (a tuple of one or two [B*H][rows_padded][cols_padded] tensors; for the
     tests)."""
-    lib = _lib.load()
     dev = device_of(q, kT, v)
     q, kT, v = to_dev(q, dev), to_dev(kT, dev), to_dev(v, dev)
     b, H, M, _ = q.shape
@@ -315,8 +320,6 @@ def attn_quant_forward(*, q, kT, v, scale, qk, pv, want_probs=False, want_planes
     _attn_matmul_desc(d.pv, (b, H, M, v.shape[2]), (H * M * v.shape[2], M * v.shape[2], v.shape[2], 1), v, pv, "p v")
     d.scale, d.reserved = float(scale), 0
     sos = bool(pv.get("sos", False))
-    need = _need(lib.p4v_attn_workspace_bytes, d, "p4v_attn_workspace_bytes")
-    ws = workspace(dev, need)
     flat = lambda t: to_dev(t, dev).reshape(-1).contiguous()
     qk_A, qk_B, pv_A, pv_B = flat(qk["A_interval"]), flat(qk["B_interval"]), flat(pv["A_interval"]), flat(pv["B_interval"])
     if qk_A.numel() != H or qk_B.numel() != H or pv_B.numel() != H or pv_A.numel() != (1 if sos else H):
@@ -324,19 +327,8 @@ def attn_quant_forward(*, q, kT, v, scale, qk, pv, want_probs=False, want_planes
     sp = flat(pv["split"]) if sos else None
     out = torch.empty(b, H, M, Dv, dtype=torch.float32, device=dev)
     probs = torch.empty(b, H, M, N, dtype=torch.float32, device=dev) if want_probs else None
-    with torch.cuda.device(dev):
-        rc = lib.p4v_attn_quant_forward(C.byref(d), ptr(q), ptr(kT), ptr(v), ptr(qk_A), ptr(qk_B), ptr(pv_A), ptr(pv_B), ptr(sp),
-                                        ptr(out), ptr(probs), ptr(ws), ws.numel(), stream_ptr(dev))
-    _lib.check(rc, "p4v_attn_quant_forward")
-    res = (out, probs) if want_probs else out
-    if want_planes:
-        info = (C.c_uint64 * 5)()
-        _lib.check(lib.p4v_debug_attn_planes(info), "p4v_debug_attn_planes")
-        off1, off2, rows, cols, twin = (int(x) for x in info)
-        take = lambda off: ws[off:off + rows * cols].view(torch.int8).reshape(b * H, rows // (b * H), cols).clone()
-        planes = (take(off1), take(off2)) if twin else (take(off1),)
-        res = (res if isinstance(res, tuple) else (res,)) + (planes,)
-    return res
+    return _fused_forward("attn", d, (q, kT, v, qk_A, qk_B, pv_A, pv_B, sp, out, probs), dev, (out, probs) if want_probs else (out,),
+                          want_planes, z=b * H)
 
 
 def matmul_quant_forward(*, A, B, A_interval, B_interval, split, A_bit, B_bit, sos=False):

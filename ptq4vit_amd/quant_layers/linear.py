@@ -108,21 +108,28 @@ class PTQSLQuantLinear(MinMaxQuantLinear):
     def _positive_a_interval(self):
         return self.a_interval[0] if isinstance(self.a_interval, (list, tuple)) else self.a_interval
 
+    def _int8_ready(self, x):
+        """Would quant_forward hand `x` to the engine?  What p4v_linear_quant_forward implements (include/ptq4vit_hip.h):
+        2..8 bit grids, blocks that tile the layer; GPU tensors, autograd not recording.  (utils/fuse.py asks this too.)"""
+        native = (2 <= self.w_bit <= 8 and 2 <= self.a_bit <= 8 and self.out_features % self.n_V == 0
+                  and self.in_features % self.n_H == 0 and self.in_features % self.n_a == 0)
+        return bool(self.int8_forward and native and x.is_cuda
+                    and not (torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad)))
+
+    def _int8_args(self):
+        """The keywords of engine.linear_quant_forward that describe this layer (all but `x`)."""
+        return dict(weight=self.weight.data, bias=None if self.bias is None else self.bias.data, w_interval=self.w_interval,
+                    a_interval=self._positive_a_interval(), w_bit=self.w_bit, a_bit=self.a_bit, n_V=self.n_V, n_H=self.n_H,
+                    n_a=self.n_a, postgelu=self._postgelu)
+
     def quant_forward(self, x):
         """Reference linear.py:62-67.  out = Q_a(x) . Q_w(W)^T + bias; on the GPU the product is taken on the integer
         grid indices (exact int32 accumulation) and rescaled by s_a * s_w[block] -- the arithmetic of the candidate
         sweeps; the fake-quant fp32 formulation below is kept for CPU tensors and whenever autograd is recording."""
         assert self.calibrated is not None, f"You should run calibrate_forward before run quant_forward for {self}"
-        # what p4v_linear_quant_forward implements (include/ptq4vit_hip.h): 2..8 bit grids, blocks that tile the layer.
-        # Inside that envelope the engine's errors propagate -- no silent switch to another arithmetic.
-        native = (2 <= self.w_bit <= 8 and 2 <= self.a_bit <= 8 and self.out_features % self.n_V == 0
-                  and self.in_features % self.n_H == 0 and self.in_features % self.n_a == 0)
-        if (self.int8_forward and native and x.is_cuda
-                and not (torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad))):
-            return engine.linear_quant_forward(
-                weight=self.weight.data, bias=None if self.bias is None else self.bias.data, x=x,
-                w_interval=self.w_interval, a_interval=self._positive_a_interval(), w_bit=self.w_bit,
-                a_bit=self.a_bit, n_V=self.n_V, n_H=self.n_H, n_a=self.n_a, postgelu=self._postgelu)
+        # Inside the envelope the engine's errors propagate -- no silent switch to another arithmetic.
+        if self._int8_ready(x):
+            return engine.linear_quant_forward(x=x, **self._int8_args())
         w_sim, bias_sim = self.quant_weight_bias()
         return F.linear(self.quant_input(x), w_sim, bias_sim)
 

@@ -106,33 +106,38 @@ class PTQSLQuantMatMul(MinMaxQuantMatMul):
         """(n_V_A, n_H_A, n_V_B, n_H_B): the row / column sub-blocks of the two operands."""
         return (self.n_V_A, self.n_H_A, self.n_V_B, self.n_H_B)
 
+    def _int8_ready(self, A, B):
+        """Would quant_forward hand `A`, `B` to the engine?  The envelope of the int8 entry points: 4-D GPU tensors, 2..8 bit
+        grids, autograd not recording.  Only the operands' shapes [1:], device and autograd state are read, so a caller that
+        decides before the operands exist (utils/fuse.py) may pass empty stand-ins of those."""
+        if self.crb_rows_A is None or self.crb_rows_B is None:
+            # intervals loaded from elsewhere (shard.exchange_intervals on a rank that did not search this module, or a
+            # checkpoint): the block geometry is a function of the operand shapes only (matmul.py:109-122)
+            self._get_padding_parameters(A, B)
+        return bool(self.int8_forward and A.is_cuda and A.dim() == 4 and 2 <= self.A_bit <= 8 and 2 <= self.B_bit <= 8
+                    and not (torch.is_grad_enabled() and (A.requires_grad or B.requires_grad)))
+
+    def _int8_args(self, H):
+        """The keywords of engine.matmul_quant_forward -- with row / column sub-blocks (then `blocks` is among them) of
+        engine.matmul_blocks_quant_forward -- that describe this module for `H` heads (all but A and B); group intervals
+        are handed over head by head."""
+        kw = dict(A_interval=self.A_interval if self._sos else self._per_head(self.A_interval, H, self.crb_groups_A, self.n_V_A * self.n_H_A),
+                  B_interval=self._per_head(self.B_interval, H, self.crb_groups_B, self.n_V_B * self.n_H_B),
+                  split=self.split if self._sos else None, A_bit=self.A_bit, B_bit=self.B_bit, sos=self._sos)
+        if engine.has_blocks(self._blocks):
+            kw["blocks"] = self._blocks
+        return kw
+
     def quant_forward(self, A, B):
         """Reference matmul.py:140-145 (SoS operand: matmul.py:595-598).  On the GPU the product is taken on the grid
         indices and rescaled in fp32 -- once for head-wise intervals (the split-of-softmax operand as its two range planes),
         once per K segment with row / column sub-blocks (p4v_matmul_blocks_quant_forward); the fake-quant fp32 formulation is
         kept for CPU tensors and autograd."""
         assert self.calibrated is not None, f"You should run calibrate_forward before run quant_forward for {self}"
-        if self.crb_rows_A is None or self.crb_rows_B is None:
-            # intervals loaded from elsewhere (shard.exchange_intervals on a rank that did not search this module, or a
-            # checkpoint): the block geometry is a function of the operand shapes only (matmul.py:109-122)
-            self._get_padding_parameters(A, B)
-        if (self.int8_forward and A.is_cuda and A.dim() == 4 and 2 <= self.A_bit <= 8 and 2 <= self.B_bit <= 8
-                and not (torch.is_grad_enabled() and (A.requires_grad or B.requires_grad))):
-            # inside the envelope of the int8 entry points the engine's errors propagate (no silent fallback); group
-            # intervals are handed over head by head
-            H = A.shape[1]
-            if engine.has_blocks(self._blocks):
-                A_iv = self.A_interval if self._sos else self._per_head(self.A_interval, H, self.crb_groups_A, self.n_V_A * self.n_H_A)
-                return engine.matmul_blocks_quant_forward(
-                    A=A, B=B, A_interval=A_iv,
-                    B_interval=self._per_head(self.B_interval, H, self.crb_groups_B, self.n_V_B * self.n_H_B),
-                    split=self.split if self._sos else None, A_bit=self.A_bit, B_bit=self.B_bit, sos=self._sos,
-                    blocks=self._blocks)
-            A_iv = self.A_interval if self._sos else self._per_head(self.A_interval, H, self.crb_groups_A)
-            return engine.matmul_quant_forward(A=A, B=B, A_interval=A_iv,
-                                               B_interval=self._per_head(self.B_interval, H, self.crb_groups_B),
-                                               split=self.split if self._sos else None, A_bit=self.A_bit,
-                                               B_bit=self.B_bit, sos=self._sos)
+        if self._int8_ready(A, B):
+            # inside the envelope of the int8 entry points the engine's errors propagate (no silent fallback)
+            kw = self._int8_args(A.shape[1])
+            return (engine.matmul_blocks_quant_forward if "blocks" in kw else engine.matmul_quant_forward)(A=A, B=B, **kw)
         return self.quant_input_A(A) @ self.quant_input_B(B)
 
     # ---- the GPU search --------------------------------------------------------------------------

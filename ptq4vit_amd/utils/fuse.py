@@ -4,7 +4,8 @@ between (engine.mlp_quant_forward / p4v_mlp_quant_forward).
 The drop-in contract keeps every quant module doing what the reference's does; nothing here changes a module.  `fuse_mlp(net)`
 patches the `forward` of the MLP *containers* -- every module with `fc1`, `act`, `fc2` where `act` is the exact (erf) nn.GELU
 and fc1 / fc2 are this package's PTQSL Linear classes: models.Mlp, so ViT, DeiT and Swin alike -- and the patched forward decides
-per call: the fused path only when both layers are calibrated, in quant_forward, on the int8 path and inside the engine's
+per call: the fused path only when both layers are calibrated, in quant_forward, on the int8 path (the layers' own verdict and
+engine keywords: _int8_ready / _int8_args, what their quant_forward uses) and inside the fused entry point's narrower
 envelope, the tensor is on the GPU, autograd is not recording and none of the three modules carries a forward (pre-)hook.  In
 every other state (raw, the calibration modes, capture hooks, CPU tensors) it calls the original forward, so calibrators behave
 exactly as on an unfused net.  Nothing calls `fuse_mlp` by default; `unfuse_mlp(net)` restores.
@@ -42,52 +43,63 @@ def _hooked(m):
     return bool(m._forward_hooks) or bool(m._forward_pre_hooks)
 
 
-def _in_envelope(fc):
-    """What p4v_mlp_quant_forward takes of one layer (include/ptq4vit_hip.h)."""
-    return (2 <= fc.w_bit <= 8 and 2 <= fc.a_bit <= 8 and fc.n_H == 1 and fc.n_a == 1 and fc.out_features % fc.n_V == 0)
+def _live(q):
+    """A quant module whose forward the patched container may bypass: calibrated, in the mode that forward would dispatch to
+    quant_forward, and nobody listening on it."""
+    return bool(getattr(q, "calibrated", None)) and q.mode == "quant_forward" and not _hooked(q)
 
 
-def _ready(fc):
-    return (getattr(fc, "calibrated", None) and fc.mode == "quant_forward" and fc.int8_forward and _in_envelope(fc)
-            and fc.w_interval is not None and fc.a_interval is not None)
+def _recording(x, *modules):
+    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for m in modules for p in m.parameters()))
+
+
+# Whether a module is on its int8 path, and with which engine keywords, the module says itself (_int8_ready / _int8_args of
+# quant_layers/linear.py and matmul.py: what its own quant_forward uses).  Stated here, and only here, is what the fused entry
+# points take LESS than the single ones (include/ptq4vit_hip.h):
+#   p4v_mlp_quant_forward    n_H = n_a = 1 on both layers, fc1 no post-GELU layer
+#   p4v_attn_quant_forward   no row / column sub-blocks, matmul1 no split-of-softmax operand; a float32 [B][N][C] input
+# (_layer / _matmul_side: the names under which the tests fetch those keywords for a direct engine call)
+_layer, _matmul_side = (lambda fc: fc._int8_args()), (lambda mm, H: mm._int8_args(H))
+
+
+def _mlp_args(m, x):
+    """(fc1's, fc2's engine keywords) if the patched forward of `m` runs the fused chain on `x`, else None."""
+    if not (fusable(m) and torch.is_tensor(x) and x.dim() >= 2):
+        return None
+    fc1, fc2 = m.fc1, m.fc2
+    if not (_live(fc1) and _live(fc2)) or _hooked(m.act) or _recording(x, fc1, fc2):
+        return None
+    if x.shape[-1] != fc1.in_features or fc1.out_features != fc2.in_features:
+        return None
+    # (fc2 is asked with x: its input would lie where x lies, and records autograd only when _recording says so)
+    if not (fc1._int8_ready(x) and fc2._int8_ready(x)):
+        return None
+    a1, a2 = fc1._int8_args(), fc2._int8_args()
+    if a1["postgelu"] or any(a["n_H"] != 1 or a["n_a"] != 1 for a in (a1, a2)):
+        return None
+    return a1, a2
 
 
 def takes_fused_path(m, x):
     """The per-call half: would the patched forward of `m` run the fused kernel chain on `x`?"""
-    if not fusable(m):
-        return False
-    fc1, act, fc2 = m.fc1, m.act, m.fc2
-    if not (_ready(fc1) and _ready(fc2)) or fc1._postgelu:
-        return False
-    if not (torch.is_tensor(x) and x.is_cuda and x.dim() >= 2 and x.shape[-1] == fc1.in_features
-            and fc1.out_features == fc2.in_features):
-        return False
-    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for fc in (fc1, fc2) for p in fc.parameters())):
-        return False
-    return not (_hooked(fc1) or _hooked(act) or _hooked(fc2))
-
-
-def _layer(fc):
-    return dict(weight=fc.weight.data, bias=None if fc.bias is None else fc.bias.data, w_interval=fc.w_interval,
-                a_interval=fc._positive_a_interval(), w_bit=fc.w_bit, a_bit=fc.a_bit, n_V=fc.n_V, n_H=fc.n_H, n_a=fc.n_a,
-                postgelu=fc._postgelu)
+    return _mlp_args(m, x) is not None
 
 
 def _fused_forward(self, x):
-    if takes_fused_path(self, x):
-        return engine.mlp_quant_forward(x=x, fc1=_layer(self.fc1), fc2=_layer(self.fc2))
+    args = _mlp_args(self, x)
+    if args is not None:
+        return engine.mlp_quant_forward(x=x, fc1=args[0], fc2=args[1])
     return self.__dict__[_ORIG](x)
 
 
-def fuse_mlp(net):
-    """Patch the forward of every fusable MLP container of `net`; returns their names.  Idempotent."""
+def _patch(net, predicate, attr, forward):
     names = []
     for name, m in net.named_modules():
-        if not fusable(m):
+        if not predicate(m):
             continue
-        if _ORIG not in m.__dict__:
-            m.__dict__[_ORIG] = m.forward
-            m.forward = types.MethodType(_fused_forward, m)
+        if attr not in m.__dict__:
+            m.__dict__[attr] = m.forward
+            m.forward = types.MethodType(forward, m)
         names.append(name)
     return names
 
@@ -103,6 +115,11 @@ def _unfuse(net, attr):
             m.forward = orig          # the forward was an instance attribute before: put that one back
         names.append(name)
     return names
+
+
+def fuse_mlp(net):
+    """Patch the forward of every fusable MLP container of `net`; returns their names.  Idempotent."""
+    return _patch(net, fusable, _ORIG, _fused_forward)
 
 
 def unfuse_mlp(net):
@@ -127,37 +144,32 @@ def attention_fusable(m):
             and _inactive_dropout(m.attn_drop))
 
 
-def _matmul_ready(mm):
-    return (getattr(mm, "calibrated", None) and mm.mode == "quant_forward" and mm.int8_forward and not engine.has_blocks(mm._blocks)
-            and 2 <= mm.A_bit <= 8 and 2 <= mm.B_bit <= 8 and mm.A_interval is not None and mm.B_interval is not None
-            and (not mm._sos or mm.split is not None))
+def _attn_args(m, x):
+    """(matmul1's, matmul2's engine keywords) if the patched forward of `m` runs the fused chain on `x`, else None."""
+    if not (attention_fusable(m) and torch.is_tensor(x) and x.dim() == 3 and x.dtype == torch.float32):
+        return None
+    m1, m2 = m.matmul1, m.matmul2
+    if not (_live(m1) and _live(m2)) or _hooked(m.attn_drop) or _recording(x, m.qkv):
+        return None
+    # the MatMuls are asked before qkv runs: stand-ins without rows for q / v (k^T: transposed) and the probabilities
+    H, N = m.num_heads, x.shape[1]
+    qv, p = x.new_empty((0, H, N, x.shape[2] // H)), x.new_empty((0, H, N, N))
+    if not (m1._int8_ready(qv, qv.transpose(-2, -1)) and m2._int8_ready(p, qv)):
+        return None
+    qk, pv = m1._int8_args(H), m2._int8_args(H)
+    if qk["sos"] or "blocks" in qk or "blocks" in pv:
+        return None
+    return qk, pv
 
 
 def takes_fused_attention_path(m, x):
     """The per-call half: would the patched forward of `m` run the fused kernel chain on `x`?"""
-    if not attention_fusable(m):
-        return False
-    m1, m2 = m.matmul1, m.matmul2
-    if not (_matmul_ready(m1) and _matmul_ready(m2)) or m1._sos:
-        return False
-    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 3 and x.dtype == torch.float32):
-        return False
-    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in m.qkv.parameters())):
-        return False
-    return not (_hooked(m1) or _hooked(m2) or _hooked(m.attn_drop))
-
-
-def _matmul_side(mm, H):
-    side = dict(A_interval=mm.A_interval if mm._sos else mm._per_head(mm.A_interval, H, mm.crb_groups_A),
-                B_interval=mm._per_head(mm.B_interval, H, mm.crb_groups_B), A_bit=mm.A_bit, B_bit=mm.B_bit, blocks=mm._blocks,
-                sos=mm._sos)
-    if mm._sos:
-        side["split"] = mm.split
-    return side
+    return _attn_args(m, x) is not None
 
 
 def _fused_attention_forward(self, x):
-    if not takes_fused_attention_path(self, x):
+    args = _attn_args(self, x)
+    if args is None:
         return self.__dict__[_ORIG_ATTN](x)
     # models.Attention.forward, with matmul1 ... matmul2 as one engine call
     B, N, C = x.shape
@@ -166,25 +178,13 @@ def _fused_attention_forward(self, x):
     if os.environ.get("P4V_QKV_CONTIGUOUS", "1") == "1":
         qkv = qkv.contiguous()
     q, k, v = qkv.unbind(0)
-    kT = k.transpose(-2, -1)
-    for mm, (a, b) in ((self.matmul1, (q, kT)), (self.matmul2, (torch.empty(B, H, N, N, device="meta"), v))):
-        if mm.crb_rows_A is None or mm.crb_rows_B is None:
-            mm._get_padding_parameters(a, b)          # (intervals loaded from elsewhere: as in quant_forward)
-    out = engine.attn_quant_forward(q=q, kT=kT, v=v, scale=self.scale, qk=_matmul_side(self.matmul1, H), pv=_matmul_side(self.matmul2, H))
+    out = engine.attn_quant_forward(q=q, kT=k.transpose(-2, -1), v=v, scale=self.scale, qk=args[0], pv=args[1])
     return self.proj_drop(self.proj(out.transpose(1, 2).reshape(B, N, C)))
 
 
 def fuse_attention(net):
     """Patch the forward of every fusable Attention container of `net`; returns their names.  Idempotent."""
-    names = []
-    for name, m in net.named_modules():
-        if not attention_fusable(m):
-            continue
-        if _ORIG_ATTN not in m.__dict__:
-            m.__dict__[_ORIG_ATTN] = m.forward
-            m.forward = types.MethodType(_fused_attention_forward, m)
-        names.append(name)
-    return names
+    return _patch(net, attention_fusable, _ORIG_ATTN, _fused_attention_forward)
 
 
 def unfuse_attention(net):

@@ -242,6 +242,8 @@ def _required_pointer_table():
     bsd = _matmul_desc(13, 13, 8, batch=4, heads=3, sos=True, blocks=(1, 1, 2, 2))
     mlp = _lib.MlpDesc()
     mlp.fc1, mlp.fc2 = _linear_desc(2, 64, 64, 256), _linear_desc(2, 64, 256, 64, postgelu=True)
+    attn = _lib.AttnDesc()
+    attn.qk, attn.pv, attn.scale = _matmul_desc(49, 64, 49), _matmul_desc(49, 49, 64, sos=True), 0.125
     lin_search = "weight bias x out grad cands w_interval a_interval ?scores ?best"
     mm_cal = "A B out grad mult A_interval B_interval split ?scores ?best"
     return [
@@ -252,6 +254,7 @@ def _required_pointer_table():
         ("p4v_matmul_quant_forward", sd, (), "A B A_interval B_interval split out"),
         ("p4v_matmul_blocks_quant_forward", bsd, (), "A B A_interval B_interval split out"),
         ("p4v_mlp_quant_forward", mlp, (), "w1 bias1 w2 bias2 x w1_interval a1_interval w2_interval a2_interval out ?hidden"),
+        ("p4v_attn_quant_forward", attn, (), "q kT v qk_A_interval qk_B_interval pv_A_interval pv_B_interval split out ?probs"),
         ("p4v_amax_init_linear", ld, (), "weight x w_interval a_interval"),
         ("p4v_linear_search_w", ld, (), lin_search), ("p4v_linear_search_a", ld, (), lin_search),
         ("p4v_amax_init_matmul", md, (), "A B A_interval B_interval"),
@@ -313,7 +316,7 @@ def test_sizing_refuses_null_and_unsupported_descriptors(lib):
     """*_workspace_bytes(NULL) and an unsupported descriptor return 0 (the latter with its message), forward-only sizing included."""
     from ptq4vit_amd import _lib
     for q in ("p4v_linear_workspace_bytes", "p4v_matmul_workspace_bytes", "p4v_matmul_blocks_workspace_bytes", "p4v_conv_workspace_bytes",
-              "p4v_mlp_workspace_bytes"):
+              "p4v_mlp_workspace_bytes", "p4v_attn_workspace_bytes"):
         assert getattr(lib, q)(None) == 0, q
     for reserved in (0, 4):
         bad = _linear_desc(2, 64, 192, 128, n_V=5, reserved=reserved)               # 128 % 5 != 0

@@ -33,6 +33,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.fused_common import _Loader, _count_fused_calls, _intervals, _wrapped_of, ulp_distance
 from tests.workspace_guard import Guard
 
 pytestmark = pytest.mark.gpu
@@ -112,15 +113,6 @@ def _modules(case, q, kT, v):
     m2.B_interval = _headwise(v, (0, 2, 3), m2.B_qmax, HEAD_FACTORS["pB"])
     m2.calibrated = True
     return m1, m2
-
-
-def _ordered(t):
-    i = t.contiguous().view(torch.int32).to(torch.int64)
-    return torch.where(i < 0, -(i & 0x7FFFFFFF), i)
-
-
-def ulp_distance(a, b):
-    return (_ordered(a) - _ordered(b)).abs()
 
 
 _RUNS = {}
@@ -288,29 +280,6 @@ def test_workspace_contract_and_envelope(eng, monkeypatch):
 
 
 # ---- 6: module level, the mini ViT -----------------------------------------------------------------------------------------------
-class _Loader:
-    def __init__(self, images):
-        self.images, self.batch_size = images, images.shape[0]
-
-    def __iter__(self):
-        yield self.images, torch.zeros(self.images.shape[0], dtype=torch.long)
-
-
-def _wrapped_of(net, names):
-    mods = dict(net.named_modules())
-    return {n: mods[n] for n in names}
-
-
-def _intervals(wrapped):
-    out = {}
-    for n, m in wrapped.items():
-        for a in ("w_interval", "a_interval", "A_interval", "B_interval", "split"):
-            v = getattr(m, a, None)
-            if v is not None:
-                out[f"{n}.{a}"] = torch.as_tensor(v).detach().cpu().clone()
-    return out
-
-
 @pytest.fixture(scope="module")
 def mini():
     from ptq4vit_amd.configs import PTQ4ViT
@@ -325,17 +294,6 @@ def mini():
     images = torch.from_numpy(g["images"][:4]).cuda()
     HessianQuantCalibrator(net, wrapped, _Loader(images), sequential=False, batch_size=4).batching_quant_calib()
     return net, wrapped, images
-
-
-def _count_fused_calls(eng, monkeypatch):
-    calls = []
-    orig = eng.attn_quant_forward
-
-    def counted(**kw):
-        calls.append(1)
-        return orig(**kw)
-    monkeypatch.setattr(eng, "attn_quant_forward", counted)
-    return calls
 
 
 def _attention_names(net):
@@ -397,7 +355,7 @@ def test_fused_net_logits_and_fallbacks(eng, mini, monkeypatch):
     attns = _attention_names(net)
     assert len(attns) == 2
     flips, total = _own_tensor_flips(eng, net, images)
-    calls = _count_fused_calls(eng, monkeypatch)
+    calls = _count_fused_calls(eng, monkeypatch, "attn_quant_forward")
     cls_forward = models.Attention.forward
     mods = dict(net.named_modules())
     try:
@@ -508,7 +466,7 @@ def test_both_qkv_layouts_take_the_fused_path(eng, mini, monkeypatch, contiguous
     monkeypatch.setenv("P4V_QKV_CONTIGUOUS", contiguous)
     fuse.unfuse_attention(net)
     flips, total = _own_tensor_flips(eng, net, images)
-    calls = _count_fused_calls(eng, monkeypatch)
+    calls = _count_fused_calls(eng, monkeypatch, "attn_quant_forward")
     try:
         with torch.no_grad():
             y_u = net(images)
@@ -543,7 +501,7 @@ def test_second_calibration_of_a_fused_net_gives_the_unfused_intervals(eng, mini
     for k in iu:
         assert torch.equal(iu[k], ifu[k]), k
     # ... and the fused net is still fused, and runs fused
-    calls = _count_fused_calls(eng, monkeypatch)
+    calls = _count_fused_calls(eng, monkeypatch, "attn_quant_forward")
     with torch.no_grad():
         net_f(images)
     assert len(calls) == 2

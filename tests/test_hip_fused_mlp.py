@@ -29,6 +29,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.fused_common import _Loader, _count_fused_calls, _intervals, _wrapped_of, ulp_distance
 from tests.workspace_guard import Guard
 
 pytestmark = pytest.mark.gpu
@@ -83,15 +84,6 @@ def _modules(case):
             fc.calibration_step2()
             fc.mode = "quant_forward"
     return fc1, fc2, x
-
-
-def _ordered(t):
-    i = t.contiguous().view(torch.int32).to(torch.int64)
-    return torch.where(i < 0, -(i & 0x7FFFFFFF), i)
-
-
-def ulp_distance(a, b):
-    return (_ordered(a) - _ordered(b)).abs()
 
 
 _RUNS = {}
@@ -226,29 +218,6 @@ def test_workspace_contract_and_envelope(eng, monkeypatch):
 
 
 # ---- 6: module level, the mini ViT -----------------------------------------------------------------------------------------------
-class _Loader:
-    def __init__(self, images):
-        self.images, self.batch_size = images, images.shape[0]
-
-    def __iter__(self):
-        yield self.images, torch.zeros(self.images.shape[0], dtype=torch.long)
-
-
-def _wrapped_of(net, names):
-    mods = dict(net.named_modules())
-    return {n: mods[n] for n in names}
-
-
-def _intervals(wrapped):
-    out = {}
-    for n, m in wrapped.items():
-        for a in ("w_interval", "a_interval", "A_interval", "B_interval", "split"):
-            v = getattr(m, a, None)
-            if v is not None:
-                out[f"{n}.{a}"] = torch.as_tensor(v).detach().cpu().clone()
-    return out
-
-
 @pytest.fixture(scope="module")
 def mini():
     from ptq4vit_amd.configs import PTQ4ViT
@@ -265,23 +234,12 @@ def mini():
     return net, wrapped, images
 
 
-def _count_fused_calls(eng, monkeypatch):
-    calls = []
-    orig = eng.mlp_quant_forward
-
-    def counted(**kw):
-        calls.append(1)
-        return orig(**kw)
-    monkeypatch.setattr(eng, "mlp_quant_forward", counted)
-    return calls
-
-
 def test_fused_net_logits_and_fallbacks(eng, mini, monkeypatch):
     from ptq4vit_amd.utils import fuse, models
     net, wrapped, images = mini
     mlps = [n for n, m in net.named_modules() if isinstance(m, models.Mlp)]
     assert len(mlps) == 2
-    calls = _count_fused_calls(eng, monkeypatch)
+    calls = _count_fused_calls(eng, monkeypatch, "mlp_quant_forward")
     cls_forward = models.Mlp.forward
     try:
         with torch.no_grad():
@@ -379,7 +337,7 @@ def test_second_calibration_of_a_fused_net_gives_the_unfused_intervals(eng, mini
     for k in iu:
         assert torch.equal(iu[k], ifu[k]), k
     # ... and the fused net is still fused, and runs fused
-    calls = _count_fused_calls(eng, monkeypatch)
+    calls = _count_fused_calls(eng, monkeypatch, "mlp_quant_forward")
     with torch.no_grad():
         net_f(images)
     assert len(calls) == 2

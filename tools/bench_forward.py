@@ -151,24 +151,20 @@ def main():
         med = {key: statistics.median(v) for key, v in ts.items()}
         t_u = med["unfused"]
         res.update({"unfused_ms": t_u * 1e3, "unfused_ms_all": [t * 1e3 for t in ts["unfused"]]})
-        if a.fused:
-            t_f = med["fused"]
-            rel = ((ys["fused"] - ys["unfused"]).norm() / ys["unfused"].norm()).item()
-            print(f"  unfused {t_u * 1e3:.2f} ms, fused MLPs ({counts['fused'][0]}) {t_f * 1e3:.2f} ms: x{t_u / t_f:.3f}; "
-                  f"fused vs fp32 x{t_raw / t_f:.2f}; logit rel diff fused vs unfused {rel:.3e}")
-            res.update({"fused_mlps": counts["fused"][0], "fused_ms": t_f * 1e3, "unfused_over_fused": t_u / t_f,
-                        "fused_vs_fp32": t_raw / t_f, "fused_ms_all": [t * 1e3 for t in ts["fused"]],
-                        "logit_rel_diff_fused_vs_unfused": rel})
-        if a.fused_attn:
-            t_a = med["fused_attn"]
-            base_key = "fused" if a.fused else "unfused"
-            rel = ((ys["fused_attn"] - ys["unfused"]).norm() / ys["unfused"].norm()).item()
-            print(f"  fused attention ({counts['fused_attn'][1]}{' + MLPs' if a.fused else ''}) {t_a * 1e3:.2f} ms: x{med[base_key] / t_a:.3f} "
-                  f"over {base_key}, x{t_u / t_a:.3f} over unfused; vs fp32 x{t_raw / t_a:.2f}; logit rel diff vs unfused {rel:.3e}")
-            res.update({"fused_attentions": counts["fused_attn"][1], "fused_attn_with_mlps": bool(a.fused), "fused_attn_ms": t_a * 1e3,
-                        "unfused_over_fused_attn": t_u / t_a, base_key + "_over_fused_attn": med[base_key] / t_a,
-                        "fused_attn_vs_fp32": t_raw / t_a, "fused_attn_ms_all": [t * 1e3 for t in ts["fused_attn"]],
-                        "logit_rel_diff_fused_attn_vs_unfused": rel})
+        for key, _, _ in variants[1:]:
+            t_v, (n_mlp, n_attn) = med[key], counts[key]
+            rel = ((ys[key] - ys["unfused"]).norm() / ys["unfused"].norm()).item()
+            if key == "fused":
+                print(f"  unfused {t_u * 1e3:.2f} ms, fused MLPs ({n_mlp}) {t_v * 1e3:.2f} ms: x{t_u / t_v:.3f}; "
+                      f"fused vs fp32 x{t_raw / t_v:.2f}; logit rel diff fused vs unfused {rel:.3e}")
+                res["fused_mlps"] = n_mlp
+            else:
+                base_key = "fused" if a.fused else "unfused"
+                print(f"  fused attention ({n_attn}{' + MLPs' if a.fused else ''}) {t_v * 1e3:.2f} ms: x{med[base_key] / t_v:.3f} "
+                      f"over {base_key}, x{t_u / t_v:.3f} over unfused; vs fp32 x{t_raw / t_v:.2f}; logit rel diff vs unfused {rel:.3e}")
+                res.update({"fused_attentions": n_attn, "fused_attn_with_mlps": bool(a.fused), base_key + "_over_fused_attn": med[base_key] / t_v})
+            res.update({key + "_ms": t_v * 1e3, "unfused_over_" + key: t_u / t_v, key + "_vs_fp32": t_raw / t_v,
+                        key + "_ms_all": [t * 1e3 for t in ts[key]], f"logit_rel_diff_{key}_vs_unfused": rel})
         kern = {}
         for key, mlp, attn in variants:
             setup(mlp, attn)

@@ -4,11 +4,13 @@ Without a GPU: the four *_workspace_bytes entry points over a grid of descriptor
 small shapes of tests/sweep_plan_cases.py, the layers of ViT-B / DeiT-T / Swin-T at the sizes tests/test_hip_production_path.py
 calibrates them; metrics, blocks, pruning on / off, fp32 planes -- the sizes do not depend on the bit width).  Then the dry runs of
 the forward side: the Linear, MatMul and sub-block grids again with `reserved` bit 2 (the sizes of *_quant_forward alone; the
-small shapes and the ViT-B layers), and p4v_mlp_workspace_bytes over a small grid of fused MLP forwards.
+small shapes and the ViT-B layers), p4v_mlp_workspace_bytes over a small grid of fused MLP forwards and p4v_attn_workspace_bytes
+over one of fused attention forwards (3 / 12 heads, 50 / 197 / 577 keys, plain / split-of-softmax p.v, 8 / 4 bit).
 --gpu: also the cases of tests/sweep_plan_cases.py, pruning off and on: launch records (kernel, stage, grid_x, grid_z) in order,
 p4v_launch_counters, p4v_prune_counters, and the raw bytes of the returned intervals, score tables and selections (as hex where
 they are at most 16 bytes, as a sha256 prefix otherwise); then the three-round cases of tests/search_round_cases.py in each of
-their modes, with the pass memo's (hits, misses) as well, and the cases of tests/pruned_pass_cases.py in theirs.  No timings: two runs of the same code give the same file.
+their modes, with the pass memo's (hits, misses) as well, and the cases of tests/pruned_pass_cases.py in theirs; last one
+fused MLP and one fused attention forward (the launch record of the producer kernel, then those of the consumer's sweep).  No timings: two runs of the same code give the same file.
 
     python tools/plan_dump.py [--gpu] [--out FILE]
 """
@@ -122,13 +124,24 @@ def mlp_descs():
         yield d
 
 
+def attn_descs():
+    # batch 2, head_dim 64, tokens = keys
+    for H, T, sos, bits in itertools.product((3, 12), (50, 197, 577), (0, 1), (8, 4)):
+        d = _lib.AttnDesc()
+        _mm(2, H, T, 64, T, bits, L2, 0, FWD, out=d.qk)
+        _mm(2, H, T, T, 64, bits, L2, sos, FWD, out=d.pv)
+        d.scale, d.reserved = 0.125, 0
+        yield d
+
+
 def workspace_plan(lib):
     """per entry point: the number of descriptors, a digest of their bytes (which grid this was) and the sizes in grid order"""
     plan = {}
     for fn, descs in (("p4v_linear_workspace_bytes", linear_descs()), ("p4v_matmul_workspace_bytes", matmul_descs()),
                       ("p4v_matmul_blocks_workspace_bytes", matmul_blocks_descs()), ("p4v_conv_workspace_bytes", conv_descs()),
                       ("p4v_linear_workspace_bytes:forward", linear_forward_descs()), ("p4v_matmul_workspace_bytes:forward", matmul_forward_descs()),
-                      ("p4v_matmul_blocks_workspace_bytes:forward", matmul_blocks_forward_descs()), ("p4v_mlp_workspace_bytes", mlp_descs())):
+                      ("p4v_matmul_blocks_workspace_bytes:forward", matmul_blocks_forward_descs()), ("p4v_mlp_workspace_bytes", mlp_descs()),
+                      ("p4v_attn_workspace_bytes", attn_descs())):
         h, sizes = hashlib.sha256(), []
         for d in descs:
             h.update(bytes(d))
@@ -152,6 +165,26 @@ def _runs(recs):
         else:
             out.append(list(r) + [1])
     return out
+
+
+def _fused_mlp(eng, prune):
+    """130 rows x 192 x 768, n_V = 3 on fc1, fc2 the post-GELU twin"""
+    import torch
+    g = torch.Generator().manual_seed(21)
+    x = torch.randn(10, 13, 192, generator=g).cuda()
+    layer = lambda n, k, n_V, iv, **kw: dict(weight=(torch.randn(n, k, generator=g) * 0.05).cuda(), bias=(torch.randn(n, generator=g) * 0.1).cuda(),
+                                             w_interval=torch.full((n_V,), 0.002), a_interval=torch.tensor([iv]), w_bit=8, a_bit=8, n_V=n_V, **kw)
+    return [eng.mlp_quant_forward(x=x, fc1=layer(768, 192, 3, 0.03), fc2=layer(192, 768, 1, 0.02, postgelu=True))]
+
+
+def _fused_attn(eng, prune):
+    """2 x 3 heads, 50 queries and keys, head_dim 64, p.v split-of-softmax"""
+    import torch
+    g = torch.Generator().manual_seed(22)
+    q, k, v = (torch.randn(2, 3, 50, 64, generator=g).cuda() for _ in range(3))
+    iv = lambda val, n=3: torch.full((n,), val)
+    return [eng.attn_quant_forward(q=q, kT=k.transpose(-2, -1), v=v, scale=0.125, qk=dict(A_interval=iv(0.03), B_interval=iv(0.03), A_bit=8, B_bit=8),
+                                   pv=dict(A_interval=iv(0.01 / 127, 1), B_interval=iv(0.03), A_bit=8, B_bit=8, sos=True, split=iv(0.01, 1)))]
 
 
 def gpu_plan():
@@ -182,6 +215,11 @@ def gpu_plan():
                          "prune_counters": [r["prune_counters"][k] for k in ("staged", "staged_no_survivors", "kept_full_sweep", "not_eligible")],
                          "memo": list(r["memo"]), "results": [_raw(t) for t in r["intervals"] + r["tables"]]})
             engine.release_workspace()
+    for name, run in (("fused_mlp_130x192x768_twin", _fused_mlp), ("fused_attn_2x3x50x64_sos", _fused_attn)):
+        res, recs, launches, _ = run_case(engine, run, False)
+        rows.append({"case": name, "records": _runs(recs), "launch_counters": [launches[k] for k in ("asked", "issued", "rounds", "groups")],
+                     "results": [_raw(t) for t in res]})
+        engine.release_workspace()
     return rows
 
 
