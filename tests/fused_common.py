@@ -1,5 +1,6 @@
 """Shared by tests/test_hip_fused_mlp.py and tests/test_hip_fused_attention.py: fp32 ulp distances, and the module-level helpers of
-the mini-ViT tests (a one-batch loader, the wrapped modules of a copied net, their intervals, a counter on an engine call)."""
+the mini-ViT tests (a one-batch loader, the wrapped modules of a copied net, their intervals, a counter on an engine call), and
+the writer of the margins file."""
 import torch
 
 
@@ -10,6 +11,32 @@ def _ordered(t):
 
 def ulp_distance(a, b):
     return (_ordered(a) - _ordered(b)).abs()
+
+
+def merge_margins(path, section, margins, ids):
+    """Write the measured margins of one test file into the JSON file `path` (nothing when it is empty or unset), under the key
+    `section` and next to what the file already holds: every {case id: value} table turned round into cases[id][table], the
+    other entries as they are."""
+    import json
+    import os
+    if not (margins and path):
+        return
+    path = os.path.abspath(path)
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    old = {}
+    if os.path.exists(path):
+        with open(path) as fh:
+            old = json.load(fh)
+    sec = old.setdefault(section, {})
+    for key, val in margins.items():
+        if isinstance(val, dict) and val and set(val) <= set(ids):
+            for cid, v in val.items():
+                sec.setdefault("cases", {}).setdefault(cid, {})[key] = v
+        else:
+            sec[key] = val
+    with open(path, "w") as fh:
+        json.dump(old, fh, indent=1, sort_keys=True)
+        fh.write("\n")
 
 
 class _Loader:

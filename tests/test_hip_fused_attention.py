@@ -20,20 +20,39 @@ exactly the size asked for:
    raw / hooked / CPU / autograd states fall back bit-identically, a second calibration of the fused net gives the unfused net's
    intervals, unfuse_attention restores, P4V_QKV_CONTIGUOUS 0 and 1.
 
-Shapes (the smallest that reach every edge): 197 queries and keys (a full 128-row tile and a ragged one, six full 32-key tiles
-and a ragged one, Kp = 256), head_dim 64 and 40 (ragged k-tile), 50 keys (less than one 64-byte piece row), 577 keys (ViT-B/384).
+7. the float64 stage references (tests/fused_reference.py; their own test: tests/test_fused_reference_cpu.py), on every case:
+   probs against the float64 softmax of the exact integer product of the oracle's quantisers on the RAW q and k^T
+   (|probs - p64| <= p64 U_row 2^-23, U_row = 10 + N / 64 + 5 max |u|; below 2^-100: 0 <= probs <= 2^-99); the planes against the
+   oracle's sos_planes / quant_int of the call's own probs on the CPU, exactly; `out` against the int64 GEMM of the call's own
+   planes with quant_int(v), scaled in float64, at the int8-forward bar 2e-6 sqrt(K).  1, 2 and 3 compare with this library's
+   other kernels, which are pinned to the oracle at their own tests' shapes only; 7 has no kernel of the library in it;
+8. degenerate intervals (a zero q / k^T / v head under the min-max rule), next to the same call on healthy data: probs (v: out)
+   of that head all NaN, its plane bytes on the grid, every other head's probs, planes and out bit-identical.
 
-With P4V_FUSED_ATTN_OUT set the measured margins are written there (profiles/r22_fused_attn_margins.json).
+Shapes (the smallest that reach every edge): 197 queries and keys (a full 128-row tile and a ragged one, six full 32-key tiles
+and a ragged one, Kp = 256), head_dim 64 and 40 (ragged k-tile), 50 keys (less than one 64-byte piece row), 577 keys (ViT-B/384);
+head_dim 128 and 80 (the ktiles >= 2 score tile, split-of-softmax and plain; 80: a ragged second k-tile), one query for 197 keys,
+130 queries for 64 keys (M > N, keys exactly one 64-byte piece, 2 rows in the second row tile), 256 x 256 (no padding anywhere),
+5 x 5 (fewer keys than one register quad stride), 1025 x 1025 (33 key tiles, matmul2 with ktiles = 17), Dv = 96 != D; matmul2 with
+A_bit != B_bit (2 / 8 -- q - 1 = 1 --, 8 / 4, plain 4 / 8), the split at both ends of its grid (1 and 2^-19); k^T one vector repeated
+(every key ties: probs = float32(1 / N) bit for bit); q x 24 (max - u up to 186: expf underflows through the subnormals to 0, over 10 %
+of the rows nearly one-hot -- the one case exempt from the `max - u < 80` / all-normal guard; its ulp comparison with torch is
+taken where p64 >= 2^-100, the rest is 7's second clause).
+
+With P4V_FUSED_ATTN_OUT set the measured margins are written there, under "attention" (profiles/r24_fused_edges_margins.json; the
+nine older cases alone: profiles/r22_fused_attn_margins.json).
 """
 import copy
 import json
 import os
+from collections import namedtuple
 
 import numpy as np
 import pytest
 import torch
 
-from tests.fused_common import _Loader, _count_fused_calls, _intervals, _wrapped_of, ulp_distance
+from tests import fused_reference as fr
+from tests.fused_common import _Loader, _count_fused_calls, _intervals, _wrapped_of, merge_margins, ulp_distance
 from tests.workspace_guard import Guard
 
 pytestmark = pytest.mark.gpu
@@ -43,16 +62,38 @@ HEAD_FACTORS = {"qA": (1.0, 0.8, 1.25), "qB": (0.9, 1.15, 1.0), "pA": (1.1, 0.9,
 ULP_FLOOR = 8
 _MARGINS = {}
 
-#          id             (batch, H, N, D)    twin   pv bits  qk (A, B) bits  q factor  strided
-CASES = [("sos_w8a8",    (2, 3, 197, 64),    True,  8,       (8, 8),         1.0,      False),
-         ("sos_w6a6",    (2, 3, 197, 64),    True,  6,       (6, 6),         1.0,      False),
-         ("plain_w8a8",  (2, 3, 197, 64),    False, 8,       (8, 8),         1.0,      False),
-         ("sos_qk_a8b4", (2, 3, 197, 64),    True,  8,       (8, 4),         1.0,      False),
-         ("sos_d40",     (2, 3, 197, 40),    True,  8,       (8, 8),         1.0,      False),
-         ("sos_n50",     (2, 3, 50, 64),     True,  8,       (8, 8),         1.0,      False),
-         ("sos_n577",    (1, 2, 577, 64),    True,  8,       (8, 8),         1.0,      False),
-         ("sos_wide",    (2, 3, 197, 64),    True,  8,       (8, 8),         8.0,      False),
-         ("sos_strided", (2, 3, 197, 64),    True,  8,       (8, 8),         1.0,      True)]
+Case = namedtuple("Case", "name shape twin pv_bits qk_bits qf strided split special", defaults=(SPLIT, None))
+S197, S197D = (2, 3, 197, 197, 64, 64), (1, 2, 197, 197, 64, 64)
+#               id                (batch, H, M, N, D, Dv)      twin   pv (A, B) bits  qk (A, B) bits  q factor  strided  split  special
+CASES = [Case("sos_w8a8",         S197,                        True,  (8, 8),         (8, 8),         1.0,      False),
+         Case("sos_w6a6",         S197,                        True,  (6, 6),         (6, 6),         1.0,      False),
+         Case("plain_w8a8",       S197,                        False, (8, 8),         (8, 8),         1.0,      False),
+         Case("sos_qk_a8b4",      S197,                        True,  (8, 8),         (8, 4),         1.0,      False),
+         Case("sos_d40",          (2, 3, 197, 197, 40, 40),    True,  (8, 8),         (8, 8),         1.0,      False),
+         Case("sos_n50",          (2, 3, 50, 50, 64, 64),      True,  (8, 8),         (8, 8),         1.0,      False),
+         Case("sos_n577",         (1, 2, 577, 577, 64, 64),    True,  (8, 8),         (8, 8),         1.0,      False),
+         Case("sos_wide",         S197,                        True,  (8, 8),         (8, 8),         8.0,      False),
+         Case("sos_strided",      S197,                        True,  (8, 8),         (8, 8),         1.0,      True),
+         # head_dim above 64: the ktiles >= 2 score tile of both instances (matmul2's column plane is then not b64 either)
+         Case("sos_d128",         (1, 2, 197, 197, 128, 128),  True,  (8, 8),         (8, 8),         1.0,      False),
+         Case("plain_d128",       (1, 2, 197, 197, 128, 128),  False, (8, 8),         (8, 8),         1.0,      False),
+         Case("sos_d80",          (1, 2, 197, 197, 80, 80),    True,  (8, 8),         (8, 8),         1.0,      False),
+         # M != N, Dv != D, no padding at all, fewer keys than a register quad stride, matmul2 ktiles = 17
+         Case("sos_m1",           (2, 3, 1, 197, 64, 64),      True,  (8, 8),         (8, 8),         1.0,      False),
+         Case("sos_m130_n64",     (1, 2, 130, 64, 64, 64),     True,  (8, 8),         (8, 8),         1.0,      False),
+         Case("sos_n256",         (1, 2, 256, 256, 64, 64),    True,  (8, 8),         (8, 8),         1.0,      False),
+         Case("sos_n5",           (2, 3, 5, 5, 16, 16),        True,  (8, 8),         (8, 8),         1.0,      False),
+         Case("sos_n1025",        (1, 1, 1025, 1025, 64, 64),  True,  (8, 8),         (8, 8),         1.0,      False),
+         Case("sos_dv96",         (1, 2, 197, 197, 64, 96),    True,  (8, 8),         (8, 8),         1.0,      False),
+         # matmul2's quantiser settings: A_bit != B_bit, q - 1 = 1, both ends of the split grid
+         Case("sos_pv_a2b8",      S197D,                       True,  (2, 8),         (8, 8),         4.0,      False),   # (q x 4: 176 p >= 0.5 -- with q - 1 = 1 plane 1 is 0 below that)
+         Case("sos_pv_a8b4",      S197D,                       True,  (8, 4),         (8, 8),         1.0,      False),
+         Case("plain_pv_a4b8",    S197D,                       False, (4, 8),         (8, 8),         1.0,      False),
+         Case("sos_split_1",      S197D,                       True,  (8, 8),         (8, 8),         1.0,      False,   1.0),
+         Case("sos_split_2e-19",  S197D,                       True,  (8, 8),         (8, 8),         1.0,      False,   2.0 ** -19),
+         # every key ties for the maximum; rows that are nearly one-hot, expf underflowing through the subnormals to 0
+         Case("sos_keys_equal",   (1, 2, 70, 70, 64, 64),      True,  (8, 8),         (8, 8),         1.0,      False,   SPLIT, "keys_equal"),
+         Case("sos_peaked",       S197D,                       True,  (8, 8),         (8, 8),         24.0,     False,   SPLIT, "peaked")]
 IDS = [c[0] for c in CASES]
 
 
@@ -62,30 +103,27 @@ def eng():
     from ptq4vit_amd import engine
     yield engine
     engine.release_workspace()
-    path = os.environ.get("P4V_FUSED_ATTN_OUT")
-    if _MARGINS and path:
-        path = os.path.abspath(path)
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        old = {}
-        if os.path.exists(path):
-            with open(path) as fh:
-                old = json.load(fh)
-        old.update(_MARGINS)
-        with open(path, "w") as fh:
-            json.dump(old, fh, indent=1, sort_keys=True)
-            fh.write("\n")
+    merge_margins(os.environ.get("P4V_FUSED_ATTN_OUT"), "attention", _MARGINS, IDS)
 
 
-def _inputs(case):
-    """q, kT, v as Attention.forward hands them over: views of the qkv Linear's output [B][N][3][H][D]."""
-    name, (B, H, N, D), _, _, _, qf, strided = case
+def _inputs(case, device="cuda"):
+    """q, kT, v as Attention.forward hands them over: views of the qkv Linear's output [B][N][3][H][D] -- three tensors of their
+    own where the queries and keys differ in number or v in head dimension."""
+    name, (B, H, M, N, D, Dv), qf, strided = case.name, case.shape, case.qf, case.strided
     g = torch.Generator().manual_seed(2200 + IDS.index(name))
-    qkv = torch.randn(B, N, 3, H, D, generator=g)
-    qkv[:, :, 0] *= qf
-    qkv = qkv.cuda().permute(2, 0, 3, 1, 4)
-    if not strided:
-        qkv = qkv.contiguous()
-    q, k, v = qkv.unbind(0)
+    if M == N and D == Dv:
+        qkv = torch.randn(B, N, 3, H, D, generator=g)
+        qkv[:, :, 0] *= qf
+        if case.special == "keys_equal":
+            qkv[:, :, 1] = qkv[:, :1, 1]
+        qkv = qkv.to(device).permute(2, 0, 3, 1, 4)
+        if not strided:
+            qkv = qkv.contiguous()
+        q, k, v = qkv.unbind(0)
+    else:
+        assert not strided and case.special is None
+        q, k, v = (torch.randn(B, n, H, d, generator=g).to(device).permute(0, 2, 1, 3).contiguous() for n, d in ((M, D), (N, D), (N, Dv)))
+        q = q * qf
     if strided:
         assert not q.is_contiguous() and not v.is_contiguous()
     return q, k.transpose(-2, -1), v
@@ -100,16 +138,16 @@ def _headwise(x, dims, qmax, factors):
 
 def _modules(case, q, kT, v):
     from ptq4vit_amd.quant_layers.matmul import PTQSLBatchingQuantMatMul, SoSPTQSLBatchingQuantMatMul
-    _, _, twin, pv_bits, (qa, qb), _, _ = case
+    twin, (pa, pb), (qa, qb) = case.twin, case.pv_bits, case.qk_bits
     m1 = PTQSLBatchingQuantMatMul(A_bit=qa, B_bit=qb, mode="quant_forward")
     m1.A_interval = _headwise(q, (0, 2, 3), m1.A_qmax, HEAD_FACTORS["qA"])
     m1.B_interval = _headwise(kT, (0, 2, 3), m1.B_qmax, HEAD_FACTORS["qB"])
     m1.calibrated = True
     if twin:
-        m2 = SoSPTQSLBatchingQuantMatMul(A_bit=pv_bits, B_bit=pv_bits, mode="quant_forward", split=torch.tensor(SPLIT, device="cuda"))
-        assert float(m2.A_interval) == float(np.float32(SPLIT) / np.float32(m2.A_qmax - 1))       # A_interval = split / (q - 1)
+        m2 = SoSPTQSLBatchingQuantMatMul(A_bit=pa, B_bit=pb, mode="quant_forward", split=torch.tensor(case.split, device="cuda"))
+        assert float(m2.A_interval) == float(np.float32(case.split) / np.float32(m2.A_qmax - 1))       # A_interval = split / (q - 1)
     else:
-        m2 = PTQSLBatchingQuantMatMul(A_bit=pv_bits, B_bit=pv_bits, mode="quant_forward")
+        m2 = PTQSLBatchingQuantMatMul(A_bit=pa, B_bit=pb, mode="quant_forward")
     m2.B_interval = _headwise(v, (0, 2, 3), m2.B_qmax, HEAD_FACTORS["pB"])
     m2.calibrated = True
     return m1, m2
@@ -120,7 +158,7 @@ _RUNS = {}
 
 def run_case(eng, monkeypatch, case):
     """One fused call per case (exact, guarded, poisoned workspace) and the unfused chain next to it; shared by the tests."""
-    name, (B, H, N, D), twin = case[0], case[1], case[2]
+    name, (B, H, M, N, D, Dv), twin = case[0], case[1], case[2]
     if name in _RUNS:
         return _RUNS[name]
     from ptq4vit_amd.utils.fuse import _matmul_side
@@ -131,13 +169,15 @@ def run_case(eng, monkeypatch, case):
         # the unfused chain
         u_ref = m1.quant_forward(q, kT) * scale
         gap = float((u_ref.amax(-1, keepdim=True) - u_ref).max())
-        assert gap < 80.0, f"{name}: max - u = {gap}: a probability would be subnormal"
+        if case.special != "peaked":                  # (the one case made of underflowing rows: held by the float64 stage reference)
+            assert gap < 80.0, f"{name}: max - u = {gap}: a probability would be subnormal"
         p_ref = u_ref.softmax(dim=-1)
         if not twin:
             m2.A_interval = _headwise(p_ref, (0, 2, 3), m2.A_qmax, HEAD_FACTORS["pA"])
         out_ref = m2.quant_forward(p_ref, v)
         p64 = torch.softmax(u_ref.double().cpu(), dim=-1).float().cuda()
-        assert bool((p64 >= 2.0 ** -126).all()), "every probability is a normal fp32 number"
+        if case.special != "peaked":
+            assert bool((p64 >= 2.0 ** -126).all()), "every probability is a normal fp32 number"
         sides = _matmul_side(m1, H), _matmul_side(m2, H)
         with Guard(eng, monkeypatch, 0xCD) as g:
             out, probs, planes = eng.attn_quant_forward(q=q, kT=kT, v=v, scale=scale, qk=sides[0], pv=sides[1], want_probs=True,
@@ -145,7 +185,9 @@ def run_case(eng, monkeypatch, case):
             reps = g.finish()
         assert len(reps) == 1 and reps[0]["guard_changed"] == 0 and 0 < reps[0]["touched"] <= reps[0]["need"], reps
     r = dict(m1=m1, m2=m2, q=q, kT=kT, v=v, scale=scale, sides=sides, out=out, probs=probs, planes=planes, u_ref=u_ref, p_ref=p_ref,
-             p64=p64, out_ref=out_ref, need=reps[0]["need"], gap=gap)
+             p64=p64, out_ref=out_ref, need=reps[0]["need"], gap=gap, live=None)
+    if case.special == "peaked":                      # the ulp comparison with torch: where the float64 reference is >= 2^-100
+        r["live"] = torch.from_numpy(_stage_reference(r)[1] >= fr.P_FLOOR).cuda()
     _RUNS[name] = r
     return r
 
@@ -167,8 +209,7 @@ def _packed(eng, m2, p):
 @pytest.mark.parametrize("case", CASES, ids=IDS)
 def test_planes_are_the_packers_bytes_of_the_calls_own_probs(eng, monkeypatch, case):
     r = run_case(eng, monkeypatch, case)
-    B, H, N, D = case[1]
-    M = N
+    B, H, M, N, D, Dv = case[1]
     want = _packed(eng, r["m2"], r["probs"])
     assert len(want) == len(r["planes"]) == (2 if case[2] else 1)
     for got, ref in zip(r["planes"], want):
@@ -183,17 +224,18 @@ def test_planes_are_the_packers_bytes_of_the_calls_own_probs(eng, monkeypatch, c
 @pytest.mark.parametrize("case", CASES, ids=IDS)
 def test_out_is_matmul2_quant_forward_of_the_calls_own_probs(eng, monkeypatch, case):
     r = run_case(eng, monkeypatch, case)
-    B, H, N, D = case[1]
+    B, H, M, N, D, Dv = case[1]
     with torch.no_grad():
         want = r["m2"].quant_forward(r["probs"], r["v"])
-    assert r["out"].shape == want.shape == (B, H, N, D)
+    assert r["out"].shape == want.shape == (B, H, M, Dv)
     assert torch.equal(r["out"], want), f"{case[0]}: max |diff| {(r['out'] - want).abs().max().item():.3e}"
 
 
 def _ulps(r):
     """(U_t, U_k, U): torch and the kernel against the rounded float64 softmax, and the kernel against torch"""
-    return (int(ulp_distance(r["p_ref"], r["p64"]).max()), int(ulp_distance(r["probs"], r["p64"]).max()),
-            int(ulp_distance(r["probs"], r["p_ref"]).max()))
+    live = (lambda d: d) if r["live"] is None else (lambda d: d[r["live"]])      # (sos_peaked: entries with p64 >= 2^-100)
+    return (int(live(ulp_distance(r["p_ref"], r["p64"])).max()), int(live(ulp_distance(r["probs"], r["p64"])).max()),
+            int(live(ulp_distance(r["probs"], r["p_ref"])).max()))
 
 
 @pytest.mark.parametrize("case", CASES, ids=IDS)
@@ -244,6 +286,133 @@ def _count_flips(eng, m2, planes, p_ref, U, what):
             assert near[diff].all(), f"{what}: {(diff & ~near).sum().item()} bytes differ away from a rounding tie"
         flips += int(diff.sum())
     return flips
+
+
+# ---- the float64 stage references (tests/fused_reference.py) ----------------------------------------------------------------------
+def _pv_kw(m2):
+    return dict(sos=m2._sos, A_bit=m2.A_bit, split=m2.split if m2._sos else None, A_iv=m2.A_interval)
+
+
+def _stage_reference(r):
+    """(u64, p64) of the case's raw inputs and matmul1's intervals, computed once per case"""
+    if "stage1" not in r:
+        m1 = r["m1"]
+        r["stage1"] = fr.attn_float_stage(r["q"], r["kT"], m1.A_interval, m1.B_interval, m1.A_bit, m1.B_bit, r["scale"])
+    return r["stage1"]
+
+
+def _check_stages(r, what, skip_heads=()):
+    """The three stage checks on one call's probs, planes and out; returns the ratios.  `skip_heads`: heads whose planes hold
+    undefined bytes (NaN probabilities): their `out` is not compared."""
+    m2 = r["m2"]
+    B, H, M, N = r["probs"].shape
+    u64, p64 = _stage_reference(r)
+    s1 = fr.check_probs(r["probs"], u64, p64, what)
+    want, nan, grid = fr.attn_planes_of(r["probs"], H, **_pv_kw(m2))
+    n = fr.check_planes(r["planes"], want, nan, grid, what)
+    ref = fr.attn_consumer_stage(r["planes"], r["v"], H, sos=m2._sos, A_bit=m2.A_bit, B_bit=m2.B_bit, B_iv=m2.B_interval,
+                                 A_iv=m2.A_interval, M=M, N=N)
+    skip = np.zeros((1, H, 1, 1), bool)
+    skip[0, list(skip_heads)] = True
+    s3 = fr.check_out(r["out"], ref, N, what, skip=skip)
+    return dict(probs_over_bound=s1, plane_bytes_compared=n, out_over_bar=s3)
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_stages_against_the_float64_references(eng, monkeypatch, case):
+    r = run_case(eng, monkeypatch, case)
+    got = _check_stages(r, case.name)
+    print(f"[fused attn] {case.name}: |probs - p64| / bound {got['probs_over_bound']:.3f}; {got['plane_bytes_compared']} plane bytes exact; "
+          f"|out - ref| / bar {got['out_over_bar']:.3f}")
+    _MARGINS.setdefault("stage_ratios", {})[case.name] = got
+    assert got["plane_bytes_compared"] == r["probs"].numel() * len(r["planes"])
+
+
+def test_equal_keys_give_one_over_n_bit_for_bit(eng, monkeypatch):
+    """expf(0) = 1, the row sum is the exact integer N, the division is IEEE: float32(1 / N) and nothing else"""
+    case = CASES[IDS.index("sos_keys_equal")]
+    r = run_case(eng, monkeypatch, case)
+    N = case.shape[3]
+    assert bool((r["kT"] == r["kT"][..., :1]).all())
+    want = torch.full_like(r["probs"], float(np.float32(1.0) / np.float32(N)))
+    assert torch.equal(r["probs"], want), f"{int((r['probs'] != want).sum())} probabilities are not float32(1 / {N})"
+
+
+def test_peaked_rows_underflow(eng, monkeypatch):
+    """the premise of sos_peaked on the call itself: probabilities that underflowed to 0 next to rows that are nearly one-hot"""
+    r = run_case(eng, monkeypatch, CASES[IDS.index("sos_peaked")])
+    assert r["gap"] > 150.0
+    assert bool((r["probs"] == 0).any()) and float((r["probs"] < 2.0 ** -100).float().mean()) >= 0.1
+    assert float((r["probs"].amax(-1) > 0.999).float().mean()) >= 0.1
+
+
+# ---- degenerate intervals: a head of zeros under the min-max rule -----------------------------------------------------------------------
+DEGEN_SHAPE = (2, 3, 70, 70, 64, 64)
+
+
+def _degen_inputs(zero, device="cuda"):
+    """q, kT, v of DEGEN_SHAPE, head 1 of `zero` ("q", "kT", "v" or None) zeroed"""
+    g = torch.Generator().manual_seed(2290)
+    B, H, M, N, D, Dv = DEGEN_SHAPE
+    t = {n: torch.randn(B, H, r, c, generator=g).to(device) for n, (r, c) in (("q", (M, D)), ("kT", (D, N)), ("v", (N, Dv)))}
+    if zero is not None:
+        t[zero][:, 1] = 0.0
+    return t["q"], t["kT"], t["v"]
+
+
+def _degen_run(eng, monkeypatch, twin, zero):
+    """The fused call on the data of a case of DEGEN_SHAPE with head 1 of `zero` ("q", "kT", "v" or None) zeroed; min-max intervals"""
+    key = ("degen", twin, zero)
+    if key in _RUNS:
+        return _RUNS[key]
+    from ptq4vit_amd.quant_layers.matmul import PTQSLBatchingQuantMatMul
+    from ptq4vit_amd.utils.fuse import _matmul_side
+    case = Case("degen", DEGEN_SHAPE, twin, (8, 8), (8, 8), 1.0, False)
+    B, H, M, N, D, Dv = DEGEN_SHAPE
+    q, kT, v = _degen_inputs(zero)
+    m1, m2 = _modules(case, q, kT, v)
+    if not twin:                                     # (a fixed head-wise interval: the same in the healthy and the degenerate run)
+        m2.A_interval = (torch.tensor([0.9, 1.1, 1.0], device="cuda") / (m2.A_qmax - 0.5)).view(1, H, 1, 1, 1, 1, 1)
+    assert isinstance(m2, PTQSLBatchingQuantMatMul)
+    scale = D ** -0.5
+    sides = _matmul_side(m1, H), _matmul_side(m2, H)
+    with torch.no_grad(), Guard(eng, monkeypatch, 0xCD) as gd:
+        out, probs, planes = eng.attn_quant_forward(q=q, kT=kT, v=v, scale=scale, qk=sides[0], pv=sides[1], want_probs=True, want_planes=True)
+        reps = gd.finish()
+    assert len(reps) == 1 and reps[0]["guard_changed"] == 0 and 0 < reps[0]["touched"] <= reps[0]["need"], reps
+    r = dict(m1=m1, m2=m2, q=q, kT=kT, v=v, scale=scale, out=out, probs=probs, planes=planes)
+    _RUNS[key] = r
+    return r
+
+
+def _same_bits(a, b):
+    return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
+@pytest.mark.parametrize("twin", [True, False], ids=["sos", "plain"])
+@pytest.mark.parametrize("zero", ["q", "kT", "v"])
+def test_a_zero_head_poisons_that_head_alone(eng, monkeypatch, twin, zero):
+    bad, good = _degen_run(eng, monkeypatch, twin, zero), _degen_run(eng, monkeypatch, twin, None)
+    B, H = DEGEN_SHAPE[:2]
+    others = [h for h in range(H) if h != 1]
+    iv = {"q": bad["m1"].A_interval, "kT": bad["m1"].B_interval, "v": bad["m2"].B_interval}[zero].reshape(-1)
+    assert float(iv[1]) == 0.0 and bool((iv[others] > 0).all()), "the min-max interval of the zero head, and of it alone, is 0"
+    what = f"zero {zero} head, {'sos' if twin else 'plain'}"
+    if zero == "v":
+        assert torch.isnan(bad["out"][:, 1]).all(), "out of the head whose v interval is 0 is the reference's NaN"
+        assert _same_bits(bad["probs"], good["probs"])
+        assert all(torch.equal(a, b) for a, b in zip(bad["planes"], good["planes"]))
+        got = _check_stages(bad, what)
+    else:
+        assert torch.isnan(bad["probs"][:, 1]).all(), "0 / 0 poisons every probability of the head"
+        got = _check_stages(bad, what, skip_heads=(1,))          # (the NaN head's plane bytes: on the grid, checked there)
+    _MARGINS.setdefault("degenerate", {})[what] = got
+    assert torch.isfinite(bad["probs"][:, others]).all() and torch.isfinite(bad["out"][:, others]).all()
+    assert _same_bits(bad["probs"][:, others], good["probs"][:, others])
+    assert _same_bits(bad["out"][:, others], good["out"][:, others])
+    for a, b in zip(bad["planes"], good["planes"]):
+        a, b = a.view(B, H, *a.shape[1:]), b.view(B, H, *b.shape[1:])
+        assert torch.equal(a[:, others], b[:, others])
 
 
 # ---- 5: the contract ------------------------------------------------------------------------------------------------------------
