@@ -818,6 +818,130 @@ __device__ __forceinline__ void clip_crange_blk(const int* rblk, int blk, int& l
     lo = max(lo, a); hi = min(hi, b);
 }
 
+// ---- the epilogue vocabulary: what every sweep / slice / bound family says the same way ----------------------
+// Candidate span of a workgroup: the launch's [c0, c1) dealt over `ngroups` candidate groups (host: choose_cgroups; `even`:
+// kernels that run candidate pairs, groups start on a pair), clipped to the pruned range.  `per` sizes the per-candidate LDS
+// tables.  The caller returns when lo >= hi.  (G: the grid's unsigned or the plan's int -- the division stays the caller's.)
+struct CandSpan { int lo, hi, per; };
+template <typename G>
+__device__ __forceinline__ CandSpan cand_span(int c0, int c1, const int* crange, G group, G ngroups, bool even = false) {
+    const int per = even ? 2 * ((c1 - c0 + 2 * ngroups - 1) / (2 * ngroups)) : (c1 - c0 + ngroups - 1) / ngroups;
+    int lo = c0 + group * per, hi = min(c1, lo + per);
+    clip_crange(crange, lo, hi, even);
+    return {lo, hi, per};
+}
+// ... with the per-score-block ranges of a head-wise search: the workgroup's tile lies inside score block `blk()`
+template <typename G, typename Blk>
+__device__ __forceinline__ CandSpan cand_span(int c0, int c1, const int* crange, G group, G ngroups, const int* rblk, Blk blk) {
+    CandSpan s = cand_span(c0, c1, crange, group, ngroups);
+    if (rblk) clip_crange_blk(rblk, blk(), s.lo, s.hi);
+    return s;
+}
+
+// C/D layout of v_mfma_*_32x32*: lane l holds column l & 31; its 16 accumulator registers are four groups of four consecutive
+// rows, the groups 8 rows apart, and the upper half-wave (g = l >> 5) sits 4 rows below the lower one.
+__device__ __forceinline__ constexpr int acc32_row(int r) { return (r & 3) + 8 * (r >> 2); }
+__device__ __forceinline__ constexpr int acc32_row(int r, int g) { return acc32_row(r) + 4 * g; }
+
+// Metric weight of one output element (SweepParams::wt_mode): 1 the weight tensor (hessian: raw_grad), 2 raw_out
+// (square_weighted_L2_norm), 3 |raw_out| (linear_weighted_L2_norm), else none.  o = raw_out, gw = the weight tensor's element.
+__device__ __forceinline__ float metric_weight(int wm, float o, float gw) {
+    if (wm == 1) return gw; else if (wm == 2) return o; else if (wm == 3) return fabsf(o); else return 1.0f;
+}
+
+// One term of a difference metric added to a running sum; d = raw - simulated, w = the metric weight.  Two arithmetic variants:
+//   metric_add         (w d)^2 | d^2     | |d|   | (w d) d   the weight only where the metric has one; padding elements carry
+//                                                            raw = 0 against an accumulator of 0, so d = 0
+//   metric_add_masked  (w d)^2 | (w d) d | w |d| | (w d) d   w is 0 on padding and doubles as the validity mask (k_sweep9, the
+//                                                            slice kernels, k_sos_split: their d is NOT 0 there)
+// The float forms name their FMAs, the v2f forms are written product + sum and contract (-ffp-contract=fast) into v_pk_fma.
+template <int EPI> __device__ __forceinline__ void metric_add(float& sum, float w, float d) {
+    if (EPI == EPI_SQ_W) { const float t = w * d; sum = fmaf(t, t, sum); }
+    else if (EPI == EPI_SQ) sum = fmaf(d, d, sum);
+    else if (EPI == EPI_ABS) sum += fabsf(d);
+    else sum = fmaf(w * d, d, sum);
+}
+template <int EPI> __device__ __forceinline__ void metric_add(v2f& sum, v2f w, v2f d) {
+    if (EPI == EPI_SQ_W) { const v2f t = w * d; sum = t * t + sum; }
+    else if (EPI == EPI_SQ) sum = d * d + sum;
+    else if (EPI == EPI_ABS) sum += v2f{fabsf(d.x), fabsf(d.y)};
+    else sum = (w * d) * d + sum;
+}
+template <int EPI> __device__ __forceinline__ void metric_add_masked(float& sum, float w, float d) {
+    if (EPI == EPI_SQ_W) { const float t = w * d; sum = fmaf(t, t, sum); }
+    else if (EPI == EPI_ABS) sum = fmaf(w, fabsf(d), sum);
+    else sum = fmaf(w * d, d, sum);
+}
+template <int EPI> __device__ __forceinline__ void metric_add_masked(v2f& sum, v2f w, v2f d) {
+    if (EPI == EPI_SQ_W) { const v2f t = w * d; sum = t * t + sum; }
+    else if (EPI == EPI_ABS) sum += w * v2f{fabsf(d.x), fabsf(d.y)};
+    else sum = (w * d) * d + sum;
+}
+
+// Scale block of column n (or of a wave's first column: the host checks that its 32 columns share one) in batch entry z:
+// sb_mode 1 blocks of sb_div columns (row / column blocks of a Linear), 2 one block per z % sb_div (heads), else one block.
+template <typename P> __device__ __forceinline__ int scale_block(const P& p, int n, int z) {
+    return p.sb_mode == 1 ? min(n / p.sb_div, p.s_cs - 1) : p.sb_mode == 2 ? z % p.sb_div : 0;
+}
+
+// The cosine sweeps leave three floats per (candidate, batch entry, 64-row slab, column) for k_finish_cos: dot(raw, sim),
+// |sim|^2, |raw|^2 over the slab's rows; `part` is [C][Z][slabs][Np][3] with the strides p_cs / p_zs.
+template <typename P> __device__ __forceinline__ float* cos_part(const P& p, int c, int z, int slab, int col) {
+    return p.part + (long)c * p.p_cs + (long)z * p.p_zs + ((long)slab * p.Np + col) * 3;
+}
+
+// The candidate-invariant targets of a 128 x 128 tile on 2 x 4 waves (k_sweep, k_sweep2, k_sweep8, k_sweep_seg), kept in registers
+// for the whole sweep.  Per accumulator element: u = raw_out - bias and w = the metric weight, both 0 on padding rows and
+// columns; cosine (EPI_COS) keeps u = raw_out and carries the bias of the simulated output in w.  EPI_FWD needs neither.
+//   idx(mc)   element index of the (clamped) row mc in this lane's column, into O and Wt alike
+//   row0, g   first row of the wave's 64 x 32 part and the lane's half-wave (acc32_row); ncol_ok: the lane's column is real
+//   bias_n    bias of the lane's column (0: none, or a bias per row); biasz, bias_axis: the bias table of batch entry z and
+//             whether it runs along the rows (the swapped cosine sweeps)
+template <int EPI, typename P, typename Idx>
+__device__ __forceinline__ void tile_targets(const P& p, Idx idx, int row0, int g, bool ncol_ok, float bias_n, const float* biasz,
+                                             int bias_axis, float (&u)[2][16], float (&w)[2][16]) {
+    if constexpr (EPI != EPI_FWD) {
+        // Phase 1: every load of the raw_out / weight tile issued back to back at clamped (always valid) addresses.
+        // (A load inside a per-element branch costs one dependent memory round trip per element.)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const long e = idx(min(row0 + i * 32 + acc32_row(r, g), p.M - 1));
+                u[i][r] = p.O[e];
+                w[i][r] = EPI == EPI_COS ? 0.0f : p.Wt[e];   // host passes Wt = O when the metric has no weight tensor
+            }
+        // Phase 2: pure ALU; the metric switch is hoisted out of the element loops
+        const int wm = EPI == EPI_COS ? 4 : p.wt_mode;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const bool ok = ncol_ok && row0 + i * 32 + acc32_row(r, g) < p.M;
+                const float o = u[i][r], gw = w[i][r];
+                const float ov = o - (EPI == EPI_COS ? 0.0f : bias_n), wv = metric_weight(wm, o, gw);
+                u[i][r] = ok ? ov : 0.0f;
+                w[i][r] = ok ? wv : 0.0f;
+            }
+        if (EPI == EPI_COS) {
+            // cosine keeps the raw output and carries the bias (0 on padding rows) in w
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int m = row0 + i * 32 + acc32_row(r, g);
+                    const bool ok = ncol_ok && m < p.M;
+                    const float braw = (biasz && bias_axis) ? biasz[min(m, p.M - 1)] : bias_n;
+                    w[i][r] = (ok && biasz) ? braw : 0.0f;
+                }
+        }
+    }
+}
+
+// ds_read_b128 at a per-lane base and an immediate offset, outside the compiler's wait insertion: the fragment reads of the
+// LDS-DMA pipelines (k_sweep2, k_sweep8, k_sweep9, k_sweep6, k_sweep7) issue these and count lgkmcnt themselves.
+#define P4V_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
+
 struct SweepParams {
     const int* crange;                 // optional device-side candidate range (see clip_crange)
     const int* crange_blk; int cb_div; // optional per-score-block ranges, block = z % cb_div (head-wise MatMul searches); k_sweep, k_sweep2,
@@ -884,62 +1008,21 @@ __device__ __forceinline__ void k_sweep_body(const SweepParams& p, const uint3 b
     const int z = blockIdx.y;
     const int m0 = mt * SW_BM, n0 = nt * SW_BN;
     // candidate groups over gridDim.z (host: choose_cgroups) -- a sweep with few tiles fills the chip this way
-    const int per = (p.c1 - p.c0 + gridDim.z - 1) / gridDim.z;
-    int c_lo_ = p.c0 + blockIdx.z * per, c_hi_ = min(p.c1, c_lo_ + per);
-    clip_crange(p.crange, c_lo_, c_hi_);
-    if (p.crange_blk) clip_crange_blk(p.crange_blk, z % p.cb_div, c_lo_, c_hi_);
-    const int c_lo = c_lo_, c_hi = c_hi_;
+    const CandSpan cspan = cand_span(p.c0, p.c1, p.crange, blockIdx.z, gridDim.z, p.crange_blk, [&] { return z % p.cb_div; });
+    const int c_lo = cspan.lo, c_hi = cspan.hi, per = cspan.per;
     if (c_lo >= c_hi) return;
 
-    // ---- candidate-invariant epilogue operands, kept in registers for the whole sweep -------------
-    // C/D layout of the 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5).
+    // ---- candidate-invariant epilogue operands, kept in registers for the whole sweep (tile_targets) ----
     float u[2][16], w[2][16];
     const int n = n0 + wc * 32 + l31;
     const bool ncol_ok = n < p.N;
     const float* biasz = p.bias ? p.bias + (long)z * p.bias_zs : nullptr;
     const float bias_n = (biasz && ncol_ok && p.bias_axis == 0) ? biasz[n] : 0.0f;
-    if constexpr (EPI != EPI_FWD) {
-        // Phase 1: every load of the raw_out / weight tile issued back to back at clamped (always valid) addresses.
-        // (A load inside a per-element branch costs one dependent memory round trip per element.)
-        const int nc = min(n, p.N - 1);
-        const long ncol_off = (long)z * p.o_zs + (long)(nc / p.o_ninner) * p.o_nbs + (long)(nc % p.o_ninner) * p.o_ns;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int mc = min(m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g, p.M - 1);
-                const long idx = ncol_off + (long)(mc / p.o_inner) * p.o_bs + (long)(mc % p.o_inner) * p.o_ms;
-                u[i][r] = p.O[idx];
-                w[i][r] = p.Wt[idx];   // host passes Wt = O when the metric has no weight tensor
-            }
-        // Phase 2: pure ALU; the metric switch is hoisted out of the element loops
-        const int wm = EPI == EPI_COS ? 4 : p.wt_mode;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-                const bool ok = ncol_ok && m < p.M;
-                const float o = u[i][r], gw = w[i][r];
-                float ov = o - (EPI == EPI_COS ? 0.0f : bias_n), wv;
-                if (wm == 1) wv = gw; else if (wm == 2) wv = o; else if (wm == 3) wv = fabsf(o); else wv = 1.0f;
-                u[i][r] = ok ? ov : 0.0f;
-                w[i][r] = ok ? wv : 0.0f;
-            }
-        if (EPI == EPI_COS) {
-            // cosine keeps the raw output and carries the bias (0 on padding rows) in w
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int m = m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-                    const bool ok = ncol_ok && m < p.M;
-                    const float braw = (biasz && p.bias_axis) ? biasz[min(m, p.M - 1)] : bias_n;
-                    w[i][r] = (ok && biasz) ? braw : 0.0f;
-                }
-        }
-    }
-    const int sb = p.sb_mode == 1 ? min(n / p.sb_div, p.s_cs - 1) : p.sb_mode == 2 ? z % p.sb_div : 0;
+    const int nc = min(n, p.N - 1);
+    const long ncol_off = (long)z * p.o_zs + (long)(nc / p.o_ninner) * p.o_nbs + (long)(nc % p.o_ninner) * p.o_ns;
+    tile_targets<EPI>(p, [&](int mc) { return ncol_off + (long)(mc / p.o_inner) * p.o_bs + (long)(mc % p.o_inner) * p.o_ms; },
+                      m0 + wr * 64, g, ncol_ok, bias_n, biasz, p.bias_axis, u, w);
+    const int sb = scale_block(p, n, z);
 
     // ---- global -> LDS staging: one 16-byte piece per thread per plane per k-tile ---------------------
     const int ld_row = tid >> 2, ld_col = (tid & 3) * 16;
@@ -1036,7 +1119,7 @@ __device__ __forceinline__ void k_sweep_body(const SweepParams& p, const uint3 b
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int m = m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
+                        const int m = m0 + wr * 64 + i * 32 + acc32_row(r, g);
                         float o_sim = (float)acc[i][r] * s1;
                         if (TWIN) o_sim = fmaf((float)acc2[i][r], s2, o_sim);
                         const float v = (EPI == EPI_FWD) ? o_sim + bias_n : u[i][r] - o_sim;
@@ -1051,10 +1134,7 @@ __device__ __forceinline__ void k_sweep_body(const SweepParams& p, const uint3 b
                         float o_sim = (float)acc[i][r] * s1;
                         if (TWIN) o_sim = fmaf((float)acc2[i][r], s2, o_sim);
                         const float d = u[i][r] - o_sim;
-                        if (EPI == EPI_SQ_W) { const float tt = w[i][r] * d; colsum = fmaf(tt, tt, colsum); }
-                        else if (EPI == EPI_SQ) colsum = fmaf(d, d, colsum);
-                        else if (EPI == EPI_ABS) colsum += fabsf(d);
-                        else colsum = fmaf(w[i][r] * d, d, colsum);
+                        metric_add<EPI>(colsum, w[i][r], d);
                     }
                 colsum += __shfl_xor(colsum, 32);
                 if (g == 0)
@@ -1077,7 +1157,7 @@ __device__ __forceinline__ void k_sweep_body(const SweepParams& p, const uint3 b
                 nn += __shfl_xor(nn, 32);
                 oo += __shfl_xor(oo, 32);
                 if (g == 0) {
-                    float* q = p.part + (long)c * p.p_cs + (long)z * p.p_zs + ((long)(mt * 2 + wr) * p.Np + n0 + wc * 32 + l31) * 3;
+                    float* q = cos_part(p, c, z, mt * 2 + wr, n0 + wc * 32 + l31);
                     q[0] = dot; q[1] = nn; q[2] = oo;
                 }
             }
@@ -1165,11 +1245,8 @@ __device__ __forceinline__ void k_sweep2_body(const SweepParams& p, const uint3 
     const int mt = first_m + (t % per_group) % gsz, nt = (t % per_group) / gsz;
     const int z = blockIdx.y;
     const int m0 = mt * SW_BM, n0 = nt * SW_BN;
-    const int per = (p.c1 - p.c0 + gridDim.z - 1) / gridDim.z;
-    int c_lo_ = p.c0 + blockIdx.z * per, c_hi_ = min(p.c1, c_lo_ + per);
-    clip_crange(p.crange, c_lo_, c_hi_);
-    if (p.crange_blk) clip_crange_blk(p.crange_blk, z % p.cb_div, c_lo_, c_hi_);
-    const int c_lo = c_lo_, c_hi = c_hi_;
+    const CandSpan cspan = cand_span(p.c0, p.c1, p.crange, blockIdx.z, gridDim.z, p.crange_blk, [&] { return z % p.cb_div; });
+    const int c_lo = cspan.lo, c_hi = cspan.hi, per = cspan.per;
     if (c_lo >= c_hi) return;
 
     // Which 64 x 32 part of the tile this wave computes.  Parts that hold only padding (attn.v: N = 64 of a 128-column tile;
@@ -1195,54 +1272,17 @@ __device__ __forceinline__ void k_sweep2_body(const SweepParams& p, const uint3 
     const bool act = !SKIP || ((n0 + wc * 32 < p.N) && (m0 + wr * 64 < p.M));
     const bool act1 = !SKIP || (act && (m0 + wr * 64 + 32 < p.M));   // second 32-row block of the part
 
-    // ---- candidate-invariant epilogue operands (identical to k_sweep) -----------------------------
+    // ---- candidate-invariant epilogue operands (tile_targets) --------------------------------------
     float u[2][16], w[2][16];
     const int n = n0 + wc * 32 + l31;
     const bool ncol_ok = n < p.N;
     const float* biasz = p.bias ? p.bias + (long)z * p.bias_zs : nullptr;
     const float bias_n = (biasz && ncol_ok && p.bias_axis == 0) ? biasz[n] : 0.0f;
     constexpr bool STORES = (EPI == EPI_FWD || EPI == EPI_STORE);   // no metric: the tile itself is written out
-    if constexpr (EPI != EPI_FWD) {
-        // Phase 1: every load of the raw_out / weight tile issued back to back at clamped (always valid) addresses.
-        // (A load inside a per-element branch costs one dependent memory round trip per element.)
-        const int nc = min(n, p.N - 1);
-        const long ncol_off = (long)z * p.o_zs + (long)(nc / p.o_ninner) * p.o_nbs + (long)(nc % p.o_ninner) * p.o_ns;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int mc = min(m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g, p.M - 1);
-                const long idx = ncol_off + (long)(mc / p.o_inner) * p.o_bs + (long)(mc % p.o_inner) * p.o_ms;
-                u[i][r] = p.O[idx];
-                w[i][r] = p.Wt[idx];   // host passes Wt = O when the metric has no weight tensor
-            }
-        // Phase 2: pure ALU; the metric switch is hoisted out of the element loops
-        const int wm = EPI == EPI_COS ? 4 : p.wt_mode;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-                const bool ok = ncol_ok && m < p.M;
-                const float o = u[i][r], gw = w[i][r];
-                float ov = o - (EPI == EPI_COS ? 0.0f : bias_n), wv;
-                if (wm == 1) wv = gw; else if (wm == 2) wv = o; else if (wm == 3) wv = fabsf(o); else wv = 1.0f;
-                u[i][r] = ok ? ov : 0.0f;
-                w[i][r] = ok ? wv : 0.0f;
-            }
-        if (EPI == EPI_COS) {
-            // cosine (as in k_sweep): u keeps the raw output, w carries the bias of the simulated output (0 on padding)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int m = m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-                    const bool ok = ncol_ok && m < p.M;
-                    const float braw = (biasz && p.bias_axis) ? biasz[min(m, p.M - 1)] : bias_n;
-                    w[i][r] = (ok && biasz) ? braw : 0.0f;
-                }
-        }
-    }
+    const int nc = min(n, p.N - 1);
+    const long ncol_off = (long)z * p.o_zs + (long)(nc / p.o_ninner) * p.o_nbs + (long)(nc % p.o_ninner) * p.o_ns;
+    tile_targets<EPI>(p, [&](int mc) { return ncol_off + (long)(mc / p.o_inner) * p.o_bs + (long)(mc % p.o_inner) * p.o_ms; },
+                      m0 + wr * 64, g, ncol_ok, bias_n, biasz, p.bias_axis, u, w);
     // cosine: |o|^2 of this lane's 32 outputs does not depend on the candidate (same order of additions as the per-candidate sum)
     float oo_fix = 0.0f;
     if constexpr (EPI == EPI_COS) {
@@ -1254,7 +1294,7 @@ __device__ __forceinline__ void k_sweep2_body(const SweepParams& p, const uint3 
     }
     // wave-uniform scale block of this wave's 32 columns (host guarantees they share one block)
     const int nw0 = n0 + wc * 32;
-    const int sb = __builtin_amdgcn_readfirstlane(p.sb_mode == 1 ? min(nw0 / p.sb_div, p.s_cs - 1) : p.sb_mode == 2 ? z % p.sb_div : 0);
+    const int sb = __builtin_amdgcn_readfirstlane(scale_block(p, nw0, z));
     // scales of this wave's block for every candidate of this workgroup -> LDS (ordinary loads must not appear
     // inside the LDS-DMA loop: hipcc would wait vmcnt(0) for them and drain the prefetch ring)
     float* s1tab = res + per * 8;
@@ -1314,7 +1354,6 @@ __device__ __forceinline__ void k_sweep2_body(const SweepParams& p, const uint3 
     // Fragment reads are software pipelined one k-tile ahead with inline-asm ds_read_b128 and counted lgkmcnt waits
     // (the compiler's wait insertion degrades to lgkmcnt(0) while an LDS-DMA is pending and, left alone, re-serialises
     // read -> wait -> MFMA: a full LDS round trip exposed per k-tile with both waves of a SIMD in lock step).
-#define P4V_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
     struct Fr { v4i b0, b1, a00, a10, a01, a11, c00, c10, c01, c11; };
     constexpr int NRD = TWIN ? 10 : 6;                       // ds_reads per k-tile
     auto read_fr = [&](Fr& f, auto stage_c) __attribute__((always_inline)) {
@@ -1372,7 +1411,7 @@ __device__ __forceinline__ void k_sweep2_body(const SweepParams& p, const uint3 
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int m = m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
+                        const int m = m0 + wr * 64 + i * 32 + acc32_row(r, g);
                         float o_sim = (float)acc[i][r] * s1;
                         if (TWIN) o_sim = fmaf((float)acc2[i][r], s2, o_sim);
                         const float v = (EPI == EPI_FWD) ? o_sim + bias_n : u[i][r] - o_sim;
@@ -1405,7 +1444,7 @@ __device__ __forceinline__ void k_sweep2_body(const SweepParams& p, const uint3 
                 nn += __shfl_xor(nn, 32);
                 const float oo = oo_fix;
                 if (g == 0) {
-                    float* q = p.part + (long)c * p.p_cs + (long)z * p.p_zs + ((long)(mt * 2 + wr) * p.Np + n0 + wc * 32 + l31) * 3;
+                    float* q = cos_part(p, c, z, mt * 2 + wr, n0 + wc * 32 + l31);
                     q[0] = dot; q[1] = nn; q[2] = oo;
                 }
                 kt = 0;
@@ -1424,10 +1463,7 @@ __device__ __forceinline__ void k_sweep2_body(const SweepParams& p, const uint3 
                     const v2f ww = {w[i][r], w[i][r + 1]};
                     v2f d = uu - a * s1;
                     if (TWIN) { const v2f a2 = {(float)acc2[i][r], (float)acc2[i][r + 1]}; d = d - a2 * s2; }
-                    if (EPI == EPI_SQ_W) { const v2f t2 = ww * d; sum2 = t2 * t2 + sum2; }
-                    else if (EPI == EPI_SQ) sum2 = d * d + sum2;
-                    else if (EPI == EPI_ABS) sum2 += v2f{fabsf(d.x), fabsf(d.y)};
-                    else sum2 = (ww * d) * d + sum2;
+                    metric_add<EPI>(sum2, ww, d);
                     acc[i][r] = 0; acc[i][r + 1] = 0;
                     if (TWIN) { acc2[i][r] = 0; acc2[i][r + 1] = 0; }
                 }
@@ -1448,7 +1484,6 @@ __device__ __forceinline__ void k_sweep2_body(const SweepParams& p, const uint3 
         if (it + 2 < total) tile(it + 2, std::integral_constant<int, 2>{}, fa, fb);
         if (it + 3 < total) tile(it + 3, std::integral_constant<int, 3>{}, fb, fa);
     }
-#undef P4V_DSR
     __syncthreads();
     if constexpr (STORES || EPI == EPI_COS) return;
     // ---- one coalesced write of this workgroup's results: part[c][z][mt*2+wr][nt*4+wc] -----------------
@@ -1599,19 +1634,19 @@ __device__ __forceinline__ void k_bound_body(const SweepParams& p, const uint3 b
             float u[16], w[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {                 // every load at a clamped (valid) address, back to back
-                const int mc = (p.dbg & 2) ? 0 : min(m0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g, p.M - 1);   // (dbg 2: ablation, one row)
+                const int mc = (p.dbg & 2) ? 0 : min(m0 + i * 32 + acc32_row(r, g), p.M - 1);   // (dbg 2: ablation, one row)
                 u[r] = On[(long)mc * p.o_ms];
                 if (EPI == EPI_SQ_W || EPI == EPI_W_SQ) w[r] = Wn[(long)mc * p.o_ms];
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = m0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
+                const int m = m0 + i * 32 + acc32_row(r, g);
                 const bool ok = ncol_ok && m < p.M;
                 const float o = u[r];
                 float wv = 1.0f;
                 if (EPI == EPI_SQ_W) wv = w[r]; else if (EPI == EPI_W_SQ) wv = fabsf(w[r]);
                 const float d = (o - bias_n) - (float)acc[i][j][r] * s1;
-                float term;
+                float term;                    // metric_add's terms as a VALUE: no FMA here, the sum takes them behind a select
                 if (EPI == EPI_SQ_W) { const float t2 = wv * d; term = t2 * t2; }
                 else if (EPI == EPI_SQ) term = d * d;
                 else if (EPI == EPI_ABS) term = fabsf(d);
@@ -1657,11 +1692,8 @@ __device__ __forceinline__ void k_sweep8_body(const SweepParams& p, const uint3 
     const int mt = t % p.mtiles, nt = t / p.mtiles;
     const int z = blockIdx.y;
     const int m0 = mt * SW_BM, n0 = nt * SW_BN;
-    const int per = (p.c1 - p.c0 + gridDim.z - 1) / gridDim.z;
-    int c_lo_ = p.c0 + blockIdx.z * per, c_hi_ = min(p.c1, c_lo_ + per);
-    clip_crange(p.crange, c_lo_, c_hi_);
-    if (p.crange_blk) clip_crange_blk(p.crange_blk, z % p.cb_div, c_lo_, c_hi_);
-    const int c_lo = c_lo_, c_hi = c_hi_;
+    const CandSpan cspan = cand_span(p.c0, p.c1, p.crange, blockIdx.z, gridDim.z, p.crange_blk, [&] { return z % p.cb_div; });
+    const int c_lo = cspan.lo, c_hi = cspan.hi, per = cspan.per;
     if (c_lo >= c_hi) return;
     const int ncand = c_hi - c_lo;
 
@@ -1671,40 +1703,19 @@ __device__ __forceinline__ void k_sweep8_body(const SweepParams& p, const uint3 
     static_assert(!SKIP, "k_sweep8: the padding skip was removed");
     const int wr = wid >> 2, wc = wid & 3;
 
-    // ---- candidate-invariant epilogue operands (as k_sweep2) --------------------------------------------------------------
+    // ---- candidate-invariant epilogue operands (tile_targets; the bias runs along the columns, no cosine instance) -------
+    static_assert(EPI != EPI_COS && EPI != EPI_FWD && EPI != EPI_STORE, "k_sweep8: the four difference metrics only");
     float u[2][16], w[2][16];
     const int n = n0 + wc * 32 + l31;
     const bool ncol_ok = n < p.N;
     const float* biasz = p.bias ? p.bias + (long)z * p.bias_zs : nullptr;
     const float bias_n = (biasz && ncol_ok) ? biasz[n] : 0.0f;
-    {
-        const int nc = min(n, p.N - 1);
-        const long ncol_off = (long)z * p.o_zs + (long)(nc / p.o_ninner) * p.o_nbs + (long)(nc % p.o_ninner) * p.o_ns;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int mc = min(m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g, p.M - 1);
-                const long idx = ncol_off + (long)(mc / p.o_inner) * p.o_bs + (long)(mc % p.o_inner) * p.o_ms;
-                u[i][r] = p.O[idx];
-                w[i][r] = p.Wt[idx];   // host passes Wt = O when the metric has no weight tensor
-            }
-        const int wm = p.wt_mode;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-                const bool ok = ncol_ok && m < p.M;
-                const float o = u[i][r], gw = w[i][r];
-                float wv;
-                if (wm == 1) wv = gw; else if (wm == 2) wv = o; else if (wm == 3) wv = fabsf(o); else wv = 1.0f;
-                u[i][r] = ok ? o - bias_n : 0.0f;
-                w[i][r] = ok ? wv : 0.0f;
-            }
-    }
+    const int nc = min(n, p.N - 1);
+    const long ncol_off = (long)z * p.o_zs + (long)(nc / p.o_ninner) * p.o_nbs + (long)(nc % p.o_ninner) * p.o_ns;
+    tile_targets<EPI>(p, [&](int mc) { return ncol_off + (long)(mc / p.o_inner) * p.o_bs + (long)(mc % p.o_inner) * p.o_ms; },
+                      m0 + wr * 64, g, ncol_ok, bias_n, nullptr, 0, u, w);
     const int nw0 = n0 + wc * 32;
-    const int sb = __builtin_amdgcn_readfirstlane(p.sb_mode == 1 ? min(nw0 / p.sb_div, p.s_cs - 1) : p.sb_mode == 2 ? z % p.sb_div : 0);
+    const int sb = __builtin_amdgcn_readfirstlane(scale_block(p, nw0, z));
     float* s1tab = res + per * 8;
     for (int i = lane; i < ncand; i += 64) s1tab[i * 8 + wid] = p.S1 ? p.S1[(c_lo + i) * p.s_cs + sb] : 1.0f;
 
@@ -1744,7 +1755,6 @@ __device__ __forceinline__ void k_sweep8_body(const SweepParams& p, const uint3 
     const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)smem;
     const unsigned a00 = lds0 + rs0 * 64 + ((g ^ ss0) << 4), a01 = lds0 + rs0 * 64 + (((2 + g) ^ ss0) << 4);
     const unsigned a10 = lds0 + rs1 * 64 + ((g ^ ss1) << 4), a11 = lds0 + rs1 * 64 + (((2 + g) ^ ss1) << 4);
-#define P4V_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
     struct Fr { v4i t00, t01, t10, t11; };               // [block][k-half] of the streamed operand (column side: block 0 only)
     constexpr int NRD = ROWS_FIXED ? 2 : 4;
     auto read_fr = [&](Fr& f, auto stage_c) __attribute__((always_inline)) {
@@ -1803,10 +1813,7 @@ __device__ __forceinline__ void k_sweep8_body(const SweepParams& p, const uint3 
                 const v2f uu = {u[i][r], u[i][r + 1]};
                 const v2f ww = {w[i][r], w[i][r + 1]};
                 const v2f d = uu - a * s1;
-                if (EPI == EPI_SQ_W) { const v2f t2 = ww * d; sum2 = t2 * t2 + sum2; }
-                else if (EPI == EPI_SQ) sum2 = d * d + sum2;
-                else if (EPI == EPI_ABS) sum2 += v2f{fabsf(d.x), fabsf(d.y)};
-                else sum2 = (ww * d) * d + sum2;
+                metric_add<EPI>(sum2, ww, d);
             }
         }
         const float sum = wave_sum_dpp(sum2.x + sum2.y);           // fixed order: deterministic
@@ -1826,7 +1833,6 @@ __device__ __forceinline__ void k_sweep8_body(const SweepParams& p, const uint3 
         if (it + 6 < ncand) step(it + 6, std::integral_constant<int, 6>{}, fa, fb);
         if (it + 7 < ncand) step(it + 7, std::integral_constant<int, 7>{}, fb, fa);
     }
-#undef P4V_DSR
     __syncthreads();
     for (int i = tid; i < ncand * 8; i += 512) {
         const int cc = c_lo + i / 8, wv = i % 8;
@@ -1867,11 +1873,8 @@ __device__ __forceinline__ void k_sweep9_body(const SweepParams& p, const uint3 
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, l4 = lane >> 4;
     const int half = blockIdx.x, z = blockIdx.y;
-    const int per = (p.c1 - p.c0 + gridDim.z - 1) / gridDim.z;
-    int c_lo_ = p.c0 + blockIdx.z * per, c_hi_ = min(p.c1, c_lo_ + per);
-    clip_crange(p.crange, c_lo_, c_hi_);
-    if (p.crange_blk) clip_crange_blk(p.crange_blk, z % p.cb_div, c_lo_, c_hi_);
-    const int c_lo = c_lo_, c_hi = c_hi_;
+    const CandSpan cspan = cand_span(p.c0, p.c1, p.crange, blockIdx.z, gridDim.z, p.crange_blk, [&] { return z % p.cb_div; });
+    const int c_lo = cspan.lo, c_hi = cspan.hi, per = cspan.per;
     if (c_lo >= c_hi) return;
     const int ncand = c_hi - c_lo;
 
@@ -1904,8 +1907,7 @@ __device__ __forceinline__ void k_sweep9_body(const SweepParams& p, const uint3 
             const long idx = ncol_off + (long)(mc / p.o_inner) * p.o_bs + (long)(mc % p.o_inner) * p.o_ms;
             const float o = p.O[idx], gw = p.Wt[idx];
             const bool ok = j < nblk && n < p.N && m < p.M;
-            float wv;
-            if (wm == 1) wv = gw; else if (wm == 2) wv = o; else if (wm == 3) wv = fabsf(o); else wv = 1.0f;
+            const float wv = metric_weight(wm, o, gw);
             u[j][e] = ok ? o - bias_n : 0.0f;
             w[j][e] = ok ? wv : 0.0f;
         }
@@ -1937,7 +1939,6 @@ __device__ __forceinline__ void k_sweep9_body(const SweepParams& p, const uint3 
     const int npre = min(SW9_NS - 1, ncand);
     for (int i = 0; i < npre; ++i) issue(i);
 
-#define P4V_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
     const v4i_ zero4 = {0, 0, 0, 0};
     int c = c_lo;
     // step `it` (compile-time stage): prove candidate `it` landed (own two pieces, then the barrier: candidates it+1 .. it+6 --
@@ -1974,10 +1975,7 @@ __device__ __forceinline__ void k_sweep9_body(const SweepParams& p, const uint3 
                 const v2f uu = {u[j][e], u[j][e + 1]};
                 const v2f ww = {w[j][e], w[j][e + 1]};
                 const v2f d = uu - a * s1;
-                if (EPI == EPI_SQ_W) { const v2f t2 = ww * d; sum2 = t2 * t2 + sum2; }
-                else if (EPI == EPI_SQ) sum2 = (ww * d) * d + sum2;
-                else if (EPI == EPI_ABS) sum2 += ww * v2f{fabsf(d.x), fabsf(d.y)};
-                else sum2 = (ww * d) * d + sum2;
+                metric_add_masked<EPI>(sum2, ww, d);
             }
         };
         // two halves: the fragments of blocks 6 .. 11 are still in flight while blocks 0 .. 5 run their MFMAs and epilogue
@@ -2015,7 +2013,6 @@ __device__ __forceinline__ void k_sweep9_body(const SweepParams& p, const uint3 
             if (it + 7 < ncand) step(it + 7, std::integral_constant<int, 7>{});
         }
     }
-#undef P4V_DSR
     __syncthreads();
     for (int i = tid; i < ncand * SW9_NW; i += SW9_NW * 64)
         p.part[(long)(c_lo + i / SW9_NW) * p.p_cs + (long)z * p.p_zs + half * SW9_NW + (i % SW9_NW)] = res[i];
@@ -2101,8 +2098,7 @@ __device__ __forceinline__ void k_slice_b2_body(const SliceB2Params& pp, const u
             const bool ok = j < nb && n < p.N && m < p.M;
             const long idx = ((long)z * 16 + min(m, 15)) * p.N + min(n, p.N - 1);
             const float o = p.O[idx], gw = p.Wt[idx];
-            float wv;
-            if (wm == 1) wv = gw; else if (wm == 2) wv = o; else if (wm == 3) wv = fabsf(o); else wv = 1.0f;
+            const float wv = metric_weight(wm, o, gw);
             u[i][e] = ok ? o : 0.0f;
             w[i][e] = ok ? wv : 0.0f;
         }
@@ -2134,9 +2130,7 @@ __device__ __forceinline__ void k_slice_b2_body(const SliceB2Params& pp, const u
                     float d = u[i][e] - (float)acc[e] * s1;
                     if (TWIN) d -= (float)acc2[e] * s2;
                     const float ww = w[i][e];
-                    if (EPI == EPI_SQ_W) { const float t2 = ww * d; sum = fmaf(t2, t2, sum); }
-                    else if (EPI == EPI_ABS) sum = fmaf(ww, fabsf(d), sum);
-                    else sum = fmaf(ww * d, d, sum);                        // EPI_SQ (w = validity mask) and EPI_W_SQ
+                    metric_add_masked<EPI>(sum, ww, d);
                 }
             }
         }
@@ -2192,8 +2186,7 @@ __device__ __forceinline__ void k_slice_a_body(const SliceAParams& p, const uint
             const bool ok = j < nb && n < p.N && m < p.M;
             const long idx = ((long)z * 16 + min(m, 15)) * p.N + min(n, p.N - 1);
             const float o = p.O[idx], gw = p.Wt[idx];
-            float wv;
-            if (wm == 1) wv = gw; else if (wm == 2) wv = o; else if (wm == 3) wv = fabsf(o); else wv = 1.0f;
+            const float wv = metric_weight(wm, o, gw);
             u[j][e] = ok ? o : 0.0f;
             w[j][e] = ok ? wv : 0.0f;
         }
@@ -2218,9 +2211,7 @@ __device__ __forceinline__ void k_slice_a_body(const SliceAParams& p, const uint
                 for (int e = 0; e < 4; ++e) {
                     const float d = u[j][e] - (float)acc[e] * s1;
                     const float ww = w[j][e];
-                    if (EPI == EPI_SQ_W) { const float t2 = ww * d; sum = fmaf(t2, t2, sum); }
-                    else if (EPI == EPI_ABS) sum = fmaf(ww, fabsf(d), sum);
-                    else sum = fmaf(ww * d, d, sum);
+                    metric_add_masked<EPI>(sum, ww, d);
                 }
             }
         }
@@ -2266,10 +2257,8 @@ __device__ __forceinline__ void k_sweep2g_body(const SweepParams& p, const uint3
     const int mt = first_m + (t % per_group) % gsz, nt = (t % per_group) / gsz;
     const int z = blockIdx.y;
     const int m0 = mt * SW_BM, n0 = nt * SW_BN;
-    const int per = 2 * ((p.c1 - p.c0 + 2 * gridDim.z - 1) / (2 * gridDim.z));   // even: groups start on a pair
-    int c_lo_ = p.c0 + blockIdx.z * per, c_hi_ = min(p.c1, c_lo_ + per);
-    clip_crange(p.crange, c_lo_, c_hi_, true);
-    const int c_lo = c_lo_, c_hi = c_hi_;
+    const CandSpan cspan = cand_span(p.c0, p.c1, p.crange, blockIdx.z, gridDim.z, true);   // even: groups start on a pair
+    const int c_lo = cspan.lo, c_hi = cspan.hi, per = cspan.per;
     if (c_lo >= c_hi) return;
     const int ncand = c_hi - c_lo, npairs = (ncand + 1) >> 1;
 
@@ -2294,7 +2283,7 @@ __device__ __forceinline__ void k_sweep2g_body(const SweepParams& p, const uint3
     const unsigned m_1 = p.wt_mode == 0 ? 0x3f800000u : 0u;
 
     const int nw0 = n0 + wc * 32;
-    const int sb = __builtin_amdgcn_readfirstlane(p.sb_mode == 1 ? min(nw0 / p.sb_div, p.s_cs - 1) : p.sb_mode == 2 ? z % p.sb_div : 0);
+    const int sb = __builtin_amdgcn_readfirstlane(scale_block(p, nw0, z));
     float* s1tab = res + per * 8;
     float* s2tab = s1tab + per * 8;
     for (int i = lane; i < per; i += 64) {
@@ -2396,7 +2385,7 @@ __device__ __forceinline__ void k_sweep2g_body(const SweepParams& p, const uint3
                         // uniform row of the g = 0 lanes; the g = 1 lanes sit 4 rows below.  Where those 4 rows would leave
                         // the matrix (last rows of a ragged tile) every lane reads the g = 0 row: the g = 1 elements are
                         // masked by `ok`, the g = 0 ones still get their own row
-                        const int br = m0w + i * 32 + (r & 3) + 8 * (r >> 2);
+                        const int br = m0w + i * 32 + acc32_row(r);
                         const bool whole = br + gl_max <= p.M - 1;
                         const long rowb = (long)min(br, p.M - 1) * p.o_ms;
                         const unsigned lo = whole ? lane_off : lane_off0;
@@ -2409,12 +2398,13 @@ __device__ __forceinline__ void k_sweep2g_body(const SweepParams& p, const uint3
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
                         const int r = q * 8 + e;
-                        const bool ok = ncol_ok && (mlane + i * 32 + (r & 3) + 8 * (r >> 2)) < p.M;
+                        const bool ok = ncol_ok && (mlane + i * 32 + acc32_row(r)) < p.M;
                         const unsigned wbits = (__builtin_bit_cast(unsigned, gw[e]) & m_g) | (__builtin_bit_cast(unsigned, uo[e]) & m_o) | m_1;
                         const float uu = ok ? uo[e] - bias_n : 0.0f;
                         const float ww = ok ? __builtin_bit_cast(float, wbits) : 0.0f;
                         float da = uu - (float)acc[0][i][r] * s1a, db = uu - (float)acc[1][i][r] * s1b;
                         if (TWIN) { da -= (float)acc2[0][i][r] * s2a; db -= (float)acc2[1][i][r] * s2b; }
+                        // metric_add, both candidates of the pair term by term (written out: as two calls the hot block is scheduled differently)
                         if (EPI == EPI_SQ_W) { const float ta = ww * da, tb = ww * db; suma = fmaf(ta, ta, suma); sumb = fmaf(tb, tb, sumb); }
                         else if (EPI == EPI_SQ) { suma = fmaf(da, da, suma); sumb = fmaf(db, db, sumb); }
                         else if (EPI == EPI_ABS) { suma += fabsf(da); sumb += fabsf(db); }
@@ -2524,10 +2514,8 @@ __device__ __forceinline__ void k_sweep5_body(const Sweep3Params& p, const uint3
     const int t = xcd_remap(blockIdx.x, nwg);
     const int st = t % p.stiles, tt = t / p.stiles;    // neighbours share the streaming tile
     const int s0 = st * 128, t0 = tt * 128;
-    const int per = 2 * ((p.c1 - p.c0 + 2 * gridDim.z - 1) / (2 * gridDim.z));   // even: groups start on a pair
-    int c_lo_ = p.c0 + blockIdx.z * per, c_hi_ = min(p.c1, c_lo_ + per);
-    clip_crange(p.crange, c_lo_, c_hi_, true);
-    const int c_lo = c_lo_, c_hi = c_hi_;
+    const CandSpan cspan = cand_span(p.c0, p.c1, p.crange, blockIdx.z, gridDim.z, true);   // even: groups start on a pair
+    const int c_lo = cspan.lo, c_hi = cspan.hi, per = cspan.per;
     if (c_lo >= c_hi) return;
 
     const int ld_row = wid * 16 + (lane >> 2);
@@ -2555,7 +2543,7 @@ __device__ __forceinline__ void k_sweep5_body(const Sweep3Params& p, const uint3
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const long idx = toff + (long)min(s0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g, p.SR - 1) * p.o_ss;
+                const long idx = toff + (long)min(s0 + wr * 64 + i * 32 + acc32_row(r, g), p.SR - 1) * p.o_ss;
                 u[i][r] = p.O[idx];
                 w[i][r] = p.Wt[idx];
             }
@@ -2565,14 +2553,14 @@ __device__ __forceinline__ void k_sweep5_body(const Sweep3Params& p, const uint3
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) bias_s[i][r] = p.bias[min(s0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g, p.SR - 1)];
+                for (int r = 0; r < 16; ++r) bias_s[i][r] = p.bias[min(s0 + wr * 64 + i * 32 + acc32_row(r, g), p.SR - 1)];
         }
         const bool t_ok = tr < p.TR;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const bool ok = t_ok && (s0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g) < p.SR;
+                const bool ok = t_ok && (s0 + wr * 64 + i * 32 + acc32_row(r, g)) < p.SR;
                 const float o = u[i][r], gw = w[i][r];
                 const float b = p.bias_on_t ? bias_t : bias_s[i][r];
                 float wv;
@@ -2630,10 +2618,7 @@ __device__ __forceinline__ void k_sweep5_body(const Sweep3Params& p, const uint3
                 const v2f uu = {u[i][r], u[i][r + 1]};
                 const v2f ww = {w[i][r], w[i][r + 1]};
                 const v2f d = uu - a * s1;
-                if (EPI == EPI_SQ_W) { const v2f t2 = ww * d; sum2 = t2 * t2 + sum2; }
-                else if (EPI == EPI_SQ) sum2 = d * d + sum2;
-                else if (EPI == EPI_ABS) sum2 += v2f{fabsf(d.x), fabsf(d.y)};
-                else sum2 = (ww * d) * d + sum2;
+                metric_add<EPI>(sum2, ww, d);
                 a2[i][r] = 0;
                 a2[i][r + 1] = 0;
             }
@@ -2848,11 +2833,9 @@ __device__ __forceinline__ void k_sweep6_body(const Sweep3Params& p, const uint3
     const int t = p.tile0 + xcd_remap(blockIdx.x, nwg);
     const int st = t % p.stiles, tt = t / p.stiles;    // neighbours share the streaming tile
     const int s0 = st * 256 + wid * (32 * RB), t0 = tt * 64;
-    const int per = (p.c1 - p.c0 + gridDim.z - 1) / gridDim.z;
-    int c_lo_ = p.c0 + blockIdx.z * per, c_hi_ = min(p.c1, c_lo_ + per);
-    clip_crange(p.crange, c_lo_, c_hi_);
-    if (p.crange_blk) clip_crange_blk(p.crange_blk, min((p.sb_on_t ? tt * 64 : st * 256) / p.sb_div, p.s_cs - 1), c_lo_, c_hi_);
-    const int c_lo = c_lo_, c_hi = c_hi_;
+    const CandSpan cspan = cand_span(p.c0, p.c1, p.crange, blockIdx.z, gridDim.z, p.crange_blk,
+                                     [&] { return min((p.sb_on_t ? tt * 64 : st * 256) / p.sb_div, p.s_cs - 1); });
+    const int c_lo = cspan.lo, c_hi = cspan.hi, per = cspan.per;
     if (c_lo >= c_hi) return;
     const int ncand = c_hi - c_lo;
 
@@ -2969,7 +2952,7 @@ __device__ __forceinline__ void k_sweep6_body(const Sweep3Params& p, const uint3
             for (int i = 0; i < RB; ++i)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int src = min(s0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g, p.SR - 1);
+                    const int src = min(s0 + i * 32 + acc32_row(r, g), p.SR - 1);
                     const long idx = toff + (long)src * p.o_ss;
                     u[i][cb][r] = p.O[idx];
                     w[i][cb][r] = p.Wt[idx];
@@ -2979,7 +2962,7 @@ __device__ __forceinline__ void k_sweep6_body(const Sweep3Params& p, const uint3
             for (int i = 0; i < RB; ++i)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const bool ok = t_ok && (s0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g) < p.SR;
+                    const bool ok = t_ok && (s0 + i * 32 + acc32_row(r, g)) < p.SR;
                     const float o = u[i][cb][r], gw = w[i][cb][r];
                     const float b = p.bias_on_t ? bias_t : bs[i][r];
                     const unsigned wbits = (__builtin_bit_cast(unsigned, gw) & m_g) | (__builtin_bit_cast(unsigned, o) & m_o) | m_1;
@@ -3051,7 +3034,6 @@ __device__ __forceinline__ void k_sweep6_body(const Sweep3Params& p, const uint3
     const unsigned tbase1 = lds0 + l31 * 64 + (((2 + g) ^ sw0) << 4);    // half 1
     const unsigned s1addr0 = lds0 + 3 * STG + (per + 1) * (8 * NW) + wid * 4;   // &s1tab[0 * NW + wid]
     float* dump = s1tab + per * NW;
-#define P4V_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
     struct TF2 { v4i f[2]; };                 // the two 32-byte halves of one column block of one k-tile
     constexpr int PD = ((2 * KT) % 3 == 0) ? 2 : 3;   // fragment reads run PD steps ahead of their MFMAs (2, 3, 5 measured the same)
     constexpr int NB = PD + 1;                // fragment buffers, ring indexed by (step % NB)
@@ -3129,6 +3111,8 @@ __device__ __forceinline__ void k_sweep6_body(const Sweep3Params& p, const uint3
                 const float d = u[i][cbE][r] - a * es1;
                 const float ww = w[i][cbE][r];
                 float& es = (r & 1) ? esum1 : esum0;
+                // metric_add, written product + sum (the contraction is the compiler's: with the helper's named FMAs the hot block of the
+                // EPI_SQ_W / EPI_SQ instances changes)
                 if (EPI == EPI_SQ_W) { const float t2 = ww * d; es = t2 * t2 + es; }
                 else if (EPI == EPI_SQ) es = d * d + es;
                 else if (EPI == EPI_ABS) es += fabsf(d);
@@ -3248,7 +3232,6 @@ __device__ __forceinline__ void k_sweep6_body(const Sweep3Params& p, const uint3
         const float* r = res + (ci + 1) * (2 * NW);
         p.part[(long)(c_lo + ci) * p.p_cs + (long)(st * 4 + wv) * p.NG + tt * 2 + cb] = r[wv * 2 + cb];
     }
-#undef P4V_DSR
 #ifdef P4V_TRACE
     if (threadIdx.x == 0) { trc[3] = __builtin_amdgcn_s_memrealtime(); trc[7] = (unsigned long long)ncand; trc[9] = __builtin_amdgcn_s_memtime(); }
 #endif
@@ -3396,10 +3379,8 @@ __device__ __forceinline__ void k_sweep7_body(const Sweep7Params& p, const uint3
     } else { rt = t % p.rtiles; ct = (t / p.rtiles) % p.ctiles; cg = t / (p.rtiles * p.ctiles); }
     constexpr int CM = TWIN ? 128 : 256;                 // samples per workgroup tile
     const int r0 = rt * 256, m0 = ct * CM;
-    const int per = (p.c1 - p.c0 + p.cgroups - 1) / p.cgroups;
-    int c_lo_ = p.c0 + cg * per, c_hi_ = min(p.c1, c_lo_ + per);
-    clip_crange(p.crange, c_lo_, c_hi_);
-    const int c_lo = c_lo_, c_hi = c_hi_;
+    const CandSpan cspan = cand_span(p.c0, p.c1, p.crange, cg, p.cgroups);
+    const int c_lo = cspan.lo, c_hi = cspan.hi, per = cspan.per;
     if (c_lo >= c_hi) return;
     const int ncand = c_hi - c_lo;
 
@@ -3465,7 +3446,6 @@ __device__ __forceinline__ void k_sweep7_body(const Sweep7Params& p, const uint3
     const unsigned aR0h = aR0 + 2 * SW7_STAGE, aR1h = aR1 + 2 * SW7_STAGE, aC0h = aC0 + 2 * SW7_STAGE, aC1h = aC1 + 2 * SW7_STAGE;
     constexpr int QOFF = TW == 1 ? 128 * 64 : 32 * 64;   // second sample block: the other plane / the next 32 samples
 
-#define P4V_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
     struct Fr { v4i r[2][4], c[2][2]; };                 // [k-half][block]: the 12 fragments of one k-tile
     Fr f;
     auto read_tile_ = [&](Fr& f, auto stage_c) __attribute__((always_inline)) {
@@ -3618,10 +3598,7 @@ __device__ __forceinline__ void k_sweep7_body(const Sweep7Params& p, const uint3
                     const int r = (2 * h2 + rr) * 4 + e;
                     float d = cur.u[rr][e] - (float)acc[j][TWIN ? 0 : q][r] * s1;
                     if (TWIN) d -= (float)acc[j][1][r] * s2;
-                    if (EPI == EPI_SQ_W) { const float tt = cur.w[rr][e] * d; sum = fmaf(tt, tt, sum); }
-                    else if (EPI == EPI_SQ) sum = fmaf(d, d, sum);
-                    else if (EPI == EPI_ABS) sum += fabsf(d);
-                    else sum = fmaf(cur.w[rr][e] * d, d, sum);
+                    metric_add<EPI>(sum, cur.w[rr][e], d);
                 }
             // pin the arithmetic of this sub-block HERE: nothing orders it against the asm statements, so the instruction
             // selector sinks it towards its only use at the end of the epilogue -- every loaded value of the candidate live
@@ -3749,7 +3726,6 @@ __device__ __forceinline__ void k_sweep7_body(const Sweep7Params& p, const uint3
             __builtin_amdgcn_s_barrier();                                                     // B2 of the candidate's last tile
         }
     }
-#undef P4V_DSR
 #undef P4V_GLD
     __syncthreads();
     if constexpr (COS) return;
@@ -3870,7 +3846,7 @@ __device__ __forceinline__ void k_sos_split_body(const SosSplitParams& p, const 
         for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = row0 + (r & 3) + 8 * (r >> 2) + 4 * g, n = cb * 32 + l31;
+                const int m = row0 + acc32_row(r, g), n = cb * 32 + l31;
                 const bool ok = m < p.M && n < p.N;
                 const long idx = ((long)z * p.M + min(m, p.M - 1)) * p.N + min(n, p.N - 1);
                 const float o = p.O[idx];
@@ -3906,7 +3882,7 @@ __device__ __forceinline__ void k_sos_split_body(const SosSplitParams& p, const 
             for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
                 for (int r = 0; r < NR; ++r) {
-                    const int m = row0 + (r & 3) + 8 * (r >> 2) + 4 * g, n = cb * 32 + l31;
+                    const int m = row0 + acc32_row(r, g), n = cb * 32 + l31;
                     u[cb][r] = *reinterpret_cast<const float*>(ob + (size_t)((unsigned)(min(m, p.M - 1) * p.N + min(n, p.N - 1)) * 4u));
                 }
             if (p.wt_mode == 1) {
@@ -3914,7 +3890,7 @@ __device__ __forceinline__ void k_sos_split_body(const SosSplitParams& p, const 
                 for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
                     for (int r = 0; r < NR; ++r) {
-                        const int m = row0 + (r & 3) + 8 * (r >> 2) + 4 * g, n = cb * 32 + l31;
+                        const int m = row0 + acc32_row(r, g), n = cb * 32 + l31;
                         w[cb][r] = *reinterpret_cast<const float*>(gb + (size_t)((unsigned)(min(m, p.M - 1) * p.N + min(n, p.N - 1)) * 4u));
                     }
             }
@@ -3959,7 +3935,7 @@ __device__ __forceinline__ void k_sos_split_body(const SosSplitParams& p, const 
           for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
             for (int r = 0; r < NR; ++r) {
-                const int m = row0 + (r & 3) + 8 * (r >> 2) + 4 * g, n = cb * 32 + l31;
+                const int m = row0 + acc32_row(r, g), n = cb * 32 + l31;
                 const bool ok = m < p.M && n < p.N;
                 const float o = u[cb][r];
                 const float gw = wsel == 0 ? w[cb][r] : wsel == 1 ? o : wsel == 2 ? fabsf(o) : 1.0f;
@@ -3977,8 +3953,8 @@ __device__ __forceinline__ void k_sos_split_body(const SosSplitParams& p, const 
 
     typedef float v16f __attribute__((ext_vector_type(16)));
     const float* b0 = Bt + g * 64 + l31;      // B fragment of k-step ks, column block cb: b0[ks * 128 + cb * 32]
-    int c_lo_ = 0, c_hi_ = p.C;
-    clip_crange(p.crange, c_lo_, c_hi_);
+    const CandSpan cspan = cand_span(0, p.C, p.crange, 0, 1);      // one group: the whole split table, clipped
+    const int c_lo_ = cspan.lo, c_hi_ = cspan.hi;
     constexpr int CW = PAIR ? 2 : 1;          // candidates of one pass over k
     for (int c = c_lo_ + (share ? wid * CW : 0); c < c_hi_; c += share ? 4 * CW : CW) {
         // PAIR: lanes 16-31 of each half-wave carry candidate c + 1 (the last pair of an odd range: c again, not written)
@@ -4033,10 +4009,7 @@ __device__ __forceinline__ void k_sos_split_body(const SosSplitParams& p, const 
                 for (int r = 0; r < NR; ++r) {
                     const float d = u[cb][r] - (cb ? acc1[h * NR + r] : acc0[h * NR + r]);
                     const float ww = w[cb][r];
-                    if (EPI == EPI_SQ_W) { const float t2 = ww * d; sum = fmaf(t2, t2, sum); }
-                    else if (EPI == EPI_SQ) sum = fmaf(ww * d, d, sum);
-                    else if (EPI == EPI_ABS) sum = fmaf(ww, fabsf(d), sum);
-                    else sum = fmaf(ww * d, d, sum);
+                    metric_add_masked<EPI>(sum, ww, d);
                 }
             sum = wave_sum_dpp(sum);
             const int slot = PAIR ? ((c + h - c_lo_) & 3) : wid;
@@ -4808,10 +4781,8 @@ __device__ __forceinline__ void k_sweep_seg_body(const SweepSegParams& p, const 
     const int mt = t % p.mtiles, nt = t / p.mtiles;
     const int z = blockIdx.y, head = z % p.H;
     const int m0 = mt * SW_BM, n0 = nt * SW_BN;
-    const int per = (p.c1 - p.c0 + gridDim.z - 1) / gridDim.z;
-    int c_lo_ = p.c0 + blockIdx.z * per, c_hi_ = min(p.c1, c_lo_ + per);
-    clip_crange(p.crange, c_lo_, c_hi_);
-    const int c_lo = c_lo_, c_hi = c_hi_;
+    const CandSpan cspan = cand_span(p.c0, p.c1, p.crange, blockIdx.z, gridDim.z);
+    const int c_lo = cspan.lo, c_hi = cspan.hi;
     if (c_lo >= c_hi) return;
     const int S = p.seg.S;
 
@@ -4847,58 +4818,21 @@ __device__ __forceinline__ void k_sweep_seg_body(const SweepSegParams& p, const 
     fill_cols(-1);
     const float rs2 = TWIN ? nan_if_zero(p.rs2[0]) : 0.0f;
 
-    // ---- candidate-invariant epilogue operands (k_sweep's phases 1 and 2) ---------------------------
+    // ---- candidate-invariant epilogue operands (tile_targets: raw_out is [Z][M][N] here and the bias is not part of the
+    // difference; cosine: u = raw_out, w = the bias of the row, both 0 on padding rows and columns) ----
     float u[2][16], w[2][16];
     const int n = n0 + wc * 32 + l31;
     const bool ncol_ok = n < p.N;
+    const long ncol_off = (long)z * p.o_zs + min(n, p.N - 1);
+    const float* biasz = (EPI == EPI_COS && p.bias) ? p.bias + (long)z * p.bias_zs : nullptr;
+    tile_targets<EPI>(p, [&](int mc) { return ncol_off + (long)mc * p.o_ms; }, m0 + wr * 64, g, ncol_ok, 0.0f, biasz, 1, u, w);
     float oo = 0.0f;        // EPI_COS: |raw|^2 over the wave's 64 features of this lane's sample
     if constexpr (EPI == EPI_COS) {
-        // u = raw_out, w = the bias of the row; both 0 on padding rows and columns (k_sweep's cosine prologue)
-        const long ncol_off = (long)z * p.o_zs + min(n, p.N - 1);
-        const float* biasz = p.bias ? p.bias + (long)z * p.bias_zs : nullptr;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int mc = min(m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g, p.M - 1);
-                u[i][r] = p.O[ncol_off + (long)mc * p.o_ms];
-                w[i][r] = biasz ? biasz[mc] : 0.0f;
-            }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-                const bool ok = ncol_ok && m < p.M;
-                u[i][r] = ok ? u[i][r] : 0.0f;
-                w[i][r] = ok ? w[i][r] : 0.0f;
-                oo = fmaf(u[i][r], u[i][r], oo);
-            }
+            for (int r = 0; r < 16; ++r) oo = fmaf(u[i][r], u[i][r], oo);
         oo += __shfl_xor(oo, 32);
-    } else if constexpr (EPI != EPI_FWD) {
-        const long ncol_off = (long)z * p.o_zs + min(n, p.N - 1);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int mc = min(m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g, p.M - 1);
-                const long idx = ncol_off + (long)mc * p.o_ms;
-                u[i][r] = p.O[idx];
-                w[i][r] = p.Wt[idx];   // host passes Wt = O when the metric has no weight tensor
-            }
-        const int wm = p.wt_mode;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-                const bool ok = ncol_ok && m < p.M;
-                const float o = u[i][r], gw = w[i][r];
-                float wv;
-                if (wm == 1) wv = gw; else if (wm == 2) wv = o; else if (wm == 3) wv = fabsf(o); else wv = 1.0f;
-                u[i][r] = ok ? o : 0.0f;
-                w[i][r] = ok ? wv : 0.0f;
-            }
     }
 
     // ---- global -> LDS staging: one 16-byte piece per thread per plane per k-tile ---------------------
@@ -4931,7 +4865,7 @@ __device__ __forceinline__ void k_sweep_seg_body(const SweepSegParams& p, const 
 
     const int fa = (wr * 64 + l31) * SW_ROW;
     const int fb = (NPL - 1) * SW_TILE_BYTES + (wc * 32 + l31) * SW_ROW;
-    const int row_l = wr * 64 + 4 * g, col_l = wc * 32 + l31;     // + i * 32 + (r & 3) + 8 * (r >> 2)
+    const int row_l = wr * 64 + 4 * g, col_l = wc * 32 + l31;     // + i * 32 + acc32_row(r)
 
     gload(0);
     lstore(0);
@@ -4973,7 +4907,7 @@ __device__ __forceinline__ void k_sweep_seg_body(const SweepSegParams& p, const 
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const float rscale = rs[sg * 128 + row_l + i * 32 + (r & 3) + 8 * (r >> 2)];
+                    const float rscale = rs[sg * 128 + row_l + i * 32 + acc32_row(r)];
                     sum[i][r] = fmaf((float)acc[i][r], rscale * cscale, sum[i][r]);
                     acc[i][r] = 0;
                     if (TWIN) { sum[i][r] = fmaf((float)acc2[i][r], rs2 * cscale, sum[i][r]); acc2[i][r] = 0; }
@@ -4986,7 +4920,7 @@ __device__ __forceinline__ void k_sweep_seg_body(const SweepSegParams& p, const 
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int m = m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
+                        const int m = m0 + wr * 64 + i * 32 + acc32_row(r, g);
                         if (ncol_ok && m < p.M) p.store[(long)z * p.M * p.N + (long)m * p.N + n] = sum[i][r];
                     }
             } else if constexpr (EPI == EPI_COS) {
@@ -5003,7 +4937,7 @@ __device__ __forceinline__ void k_sweep_seg_body(const SweepSegParams& p, const 
                 nn += __shfl_xor(nn, 32);
                 const int slab = mt * 2 + wr;          // the table has ceil(M / 64) slabs: a wave of padding rows only has none
                 if (g == 0 && slab * 64 < p.M) {
-                    float* q = p.part + (long)c * p.p_cs + (long)z * p.p_zs + ((long)slab * p.Np + n0 + wc * 32 + l31) * 3;
+                    float* q = cos_part(p, c, z, slab, n0 + wc * 32 + l31);
                     q[0] = dot; q[1] = nn; q[2] = oo;
                 }
             } else {
@@ -5013,10 +4947,7 @@ __device__ __forceinline__ void k_sweep_seg_body(const SweepSegParams& p, const 
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const float d = u[i][r] - sum[i][r];
-                        if (EPI == EPI_SQ_W) { const float tt = w[i][r] * d; colsum = fmaf(tt, tt, colsum); }
-                        else if (EPI == EPI_SQ) colsum = fmaf(d, d, colsum);
-                        else if (EPI == EPI_ABS) colsum += fabsf(d);
-                        else colsum = fmaf(w[i][r] * d, d, colsum);
+                        metric_add<EPI>(colsum, w[i][r], d);
                     }
                 colsum += __shfl_xor(colsum, 32);
                 if (g == 0)
@@ -5143,7 +5074,7 @@ __device__ __forceinline__ void k_mlp_fc1_body(const MlpFc1Params& p, const uint
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row_l = wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
+            const int row_l = wr * 64 + i * 32 + acc32_row(r, g);
             const int m = m0 + row_l;
             const bool ok = ncol_ok && m < p.M;
             const float o_sim = (float)acc[i][r] * s1;
@@ -5264,7 +5195,7 @@ __device__ __forceinline__ void k_attn_qk_body(const AttnQkParams& p, const uint
         scores(nt * 32, u);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int n = nt * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
+            const int n = nt * 32 + acc32_row(r, g);
             if (n < p.N) mx = fmaxf(mx, u[r]);
         }
     }
@@ -5278,7 +5209,7 @@ __device__ __forceinline__ void k_attn_qk_body(const AttnQkParams& p, const uint
         scores(nt * 32, u);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int n = nt * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
+            const int n = nt * 32 + acc32_row(r, g);
             if (n < p.N) part[r] = __fadd_rn(part[r], expf(__fsub_rn(u[r], mx)));
         }
     }

@@ -42,13 +42,13 @@ def linear_inputs(K, N, *, seed, images=2, tokens=64, postgelu=False):
     return w, b, x, out, _grad(out.shape, g, 1)
 
 
-def _linear(K, N, *, seed, images=2, tokens=64, n_V=1, postgelu=False, variant=0):
+def _linear(K, N, *, seed, images=2, tokens=64, n_V=1, postgelu=False, variant=0, metric="hessian"):
     def run(eng, prune):
         w, b, x, out, grad = linear_inputs(K, N, seed=seed, images=images, tokens=tokens, postgelu=postgelu)
         eng.debug_variant(variant)
         try:
             res = eng.linear_calibrate(weight=_cuda(w), bias=_cuda(b), x=_cuda(x), out=_cuda(out), grad=_cuda(grad), w_bit=8, a_bit=8,
-                                       metric="hessian", n_V=n_V, n_H=1, n_a=1, postgelu=postgelu, prune=prune, want_scores=not prune,
+                                       metric=metric, n_V=n_V, n_H=1, n_a=1, postgelu=postgelu, prune=prune, want_scores=not prune,
                                        **SEARCH)
         finally:
             eng.debug_variant(0)
@@ -69,19 +69,21 @@ def matmul_inputs(M, K, N, *, seed, sos=False, batch=2, heads=2):
     return A, B, out, _grad(out.shape, g, 2)
 
 
-def _matmul(M, K, N, *, seed, sos=False, batch=2, heads=2):
+def _matmul(M, K, N, *, seed, sos=False, batch=2, heads=2, metric="hessian"):
     def run(eng, prune):
         A, B, out, grad = matmul_inputs(M, K, N, seed=seed, sos=sos, batch=batch, heads=heads)
-        res = eng.matmul_calibrate(A=_cuda(A), B=_cuda(B), out=_cuda(out), grad=_cuda(grad), A_bit=8, B_bit=8, metric="hessian",
+        res = eng.matmul_calibrate(A=_cuda(A), B=_cuda(B), out=_cuda(out), grad=_cuda(grad), A_bit=8, B_bit=8, metric=metric,
                                    sos=sos, prune=prune, want_scores=not prune, **SEARCH)
         return [t for t in res if t is not None]
     return run
 
 
-def _matmul_blocks(name):
+def _matmul_blocks(name, *, metric=None):
+    """the fixture's inputs and blocks; `metric` replaces the fixture's own (a hessian fixture brings its raw_grad)"""
     def run(eng, prune):
         z = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
         p = json.loads(str(z["params"]))
+        p["metric"] = metric or p["metric"]
         t = lambda k: torch.from_numpy(np.ascontiguousarray(z[k])).cuda()
         blocks = (p.get("n_V_A", 1), p.get("n_H_A", 1), p.get("n_V_B", 1), p.get("n_H_B", 1))
         res = eng.matmul_calibrate(A=t("A"), B=t("B"), out=t("out"), grad=t("grad") if p["metric"] == "hessian" else None,
@@ -101,35 +103,39 @@ def conv_inputs(*, seed, images=2, size=32, patch=16):
     return w, b, x, out, torch.randn(out.shape, generator=g) * 1e-10
 
 
-def _conv(*, seed):
+def _conv(*, seed, metric="hessian"):
     def run(eng, prune):
         w, b, x, out, grad = conv_inputs(seed=seed)
         res = eng.conv_calibrate(weight=_cuda(w), bias=_cuda(b), x=_cuda(x), out=_cuda(out), grad=_cuda(grad), stride=(16, 16),
-                                 padding=(0, 0), dilation=(1, 1), w_bit=8, a_bit=32, metric="hessian", prune=prune,
+                                 padding=(0, 0), dilation=(1, 1), w_bit=8, a_bit=32, metric=metric, prune=prune,
                                  want_scores=not prune, **SEARCH)
         return [t for t in res if t is not None]
     return run
 
 
-# (name, run, pruned): `pruned` cases run with the exact candidate pruning on, the others with desc.reserved bit 3
-CASES = [
-    ("linear_k192_n128", _linear(192, 128, seed=1), False),
-    ("linear_k128_n128", _linear(128, 128, seed=2), False),
-    ("linear_k1024_n64", _linear(1024, 64, seed=3), False),
-    ("postgelu_k1024_n64", _linear(1024, 64, seed=4, postgelu=True), False),
-    ("linear_k1088_n64", _linear(1088, 64, seed=5), False),
-    ("linear_k192_n120_nV3", _linear(192, 120, seed=6, n_V=3), False),
-    ("matmul_qk_49", _matmul(49, 64, 49, seed=7), False),
-    ("matmul_qk_120", _matmul(120, 64, 120, seed=8), False),
-    ("matmul_sos_49", _matmul(49, 49, 64, seed=9, sos=True), False),
-    ("conv_patch16_a32", _conv(seed=10), False),
-    ("bound_650x96_k192", _linear(192, 96, seed=11, images=10, tokens=65, variant=LOOSE), True),
-    ("mmblk_qk_hessian_vA2hA2_vB2hB3", _matmul_blocks("mmblk_qk_hessian_vA2hA2_vB2hB3"), False),
+# (name, maker, its arguments, pruned): the twelve shapes; every maker also takes `metric` (tests/metric_grid_cases.py)
+SHAPES = [
+    ("linear_k192_n128", _linear, ((192, 128), dict(seed=1)), False),
+    ("linear_k128_n128", _linear, ((128, 128), dict(seed=2)), False),
+    ("linear_k1024_n64", _linear, ((1024, 64), dict(seed=3)), False),
+    ("postgelu_k1024_n64", _linear, ((1024, 64), dict(seed=4, postgelu=True)), False),
+    ("linear_k1088_n64", _linear, ((1088, 64), dict(seed=5)), False),
+    ("linear_k192_n120_nV3", _linear, ((192, 120), dict(seed=6, n_V=3)), False),
+    ("matmul_qk_49", _matmul, ((49, 64, 49), dict(seed=7)), False),
+    ("matmul_qk_120", _matmul, ((120, 64, 120), dict(seed=8)), False),
+    ("matmul_sos_49", _matmul, ((49, 49, 64), dict(seed=9, sos=True)), False),
+    ("conv_patch16_a32", _conv, ((), dict(seed=10)), False),
+    ("bound_650x96_k192", _linear, ((192, 96), dict(seed=11, images=10, tokens=65, variant=LOOSE)), True),
+    ("mmblk_qk_hessian_vA2hA2_vB2hB3", _matmul_blocks, (("mmblk_qk_hessian_vA2hA2_vB2hB3",), {}), False),
 ]
+
+# (name, run, pruned): `pruned` cases run with the exact candidate pruning on, the others with desc.reserved bit 3
+CASES = [(name, make(*args, **kw), pruned) for name, make, (args, kw), pruned in SHAPES]
 
 
 def run_case(eng, run, prune):
-    """One case with launch records: (result tensors, [(kernel, stage, grid_x, grid_z)], launch counters, prune counters)."""
+    """One case with launch records: (result tensors, [(kernel, stage, grid_x, grid_z)], launch counters, prune counters); the
+    launch counters also carry the pass memo's (hits, misses) as "memo"."""
     eng.launch_counters(reset=True)
     eng.prune_counters(reset=True)
     eng.stats_reset()
@@ -137,8 +143,8 @@ def run_case(eng, run, prune):
     try:
         res = run(eng, prune)
         torch.cuda.synchronize()
-        eng.stats_get()
+        st = eng.stats_get()
         recs = [(r["kernel"], r["stage"], r["grid_x"], r["grid_z"]) for r in eng.stats_launches()]
     finally:
         eng.stats_enable(False)
-    return res, recs, eng.launch_counters(), eng.prune_counters()
+    return res, recs, dict(eng.launch_counters(), memo=(int(st["memo_hits"]), int(st["memo_misses"]))), eng.prune_counters()

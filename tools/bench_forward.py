@@ -12,6 +12,7 @@ for the GEMMs (k_mlp_fc1, the fc2 sweep), torch's profiler for everything (k_pac
 matmul1's sweep, torch's `* scale` and softmax and k_pack_dual); with --fused it is MLPs + attention, without it attention alone.
 """
 import argparse
+import hashlib
 import json
 import os
 import statistics
@@ -165,6 +166,8 @@ def main():
                 res.update({"fused_attentions": n_attn, "fused_attn_with_mlps": bool(a.fused), base_key + "_over_fused_attn": med[base_key] / t_v})
             res.update({key + "_ms": t_v * 1e3, "unfused_over_" + key: t_u / t_v, key + "_vs_fp32": t_raw / t_v,
                         key + "_ms_all": [t * 1e3 for t in ts[key]], f"logit_rel_diff_{key}_vs_unfused": rel})
+        # a digest of each variant's logit bytes: two libraries that compute the same thing give the same three
+        res["logits_sha256"] = {key: hashlib.sha256(y.float().cpu().numpy().tobytes()).hexdigest()[:16] for key, y in ys.items()}
         kern = {}
         for key, mlp, attn in variants:
             setup(mlp, attn)

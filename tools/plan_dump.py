@@ -10,9 +10,16 @@ over one of fused attention forwards (3 / 12 heads, 50 / 197 / 577 keys, plain /
 p4v_launch_counters, p4v_prune_counters, and the raw bytes of the returned intervals, score tables and selections (as hex where
 they are at most 16 bytes, as a sha256 prefix otherwise); then the three-round cases of tests/search_round_cases.py in each of
 their modes, with the pass memo's (hits, misses) as well, and the cases of tests/pruned_pass_cases.py in theirs; last one
-fused MLP and one fused attention forward (the launch record of the producer kernel, then those of the consumer's sweep).  No timings: two runs of the same code give the same file.
+fused MLP and one fused attention forward (the launch record of the producer kernel, then those of the consumer's sweep); after them
+the metric grid of tests/metric_grid_cases.py: the twelve shapes again, each in its own pruning setting, under the four difference
+metrics the rows above do not run.  No timings: two runs of the
+same code give the same file.
 
-    python tools/plan_dump.py [--gpu] [--out FILE]
+--base FILE: an earlier dump of this tool.  Where this run's workspace section and its first GPU rows equal FILE's, they are not
+written again: the output names FILE, its sha256 and the number of rows found equal, and lists the rows after them.  Anything
+that differs from FILE is written in full.
+
+    python tools/plan_dump.py [--gpu] [--base FILE] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -220,12 +227,33 @@ def gpu_plan():
         rows.append({"case": name, "records": _runs(recs), "launch_counters": [launches[k] for k in ("asked", "issued", "rounds", "groups")],
                      "results": [_raw(t) for t in res]})
         engine.release_workspace()
+    from tests.metric_grid_cases import CASES as METRIC_CASES
+    for name, metric, run, pruned in METRIC_CASES:
+        res, recs, launches, counters = run_case(engine, run, pruned)
+        rows.append({"case": name, "metric": metric, "prune": int(pruned), "records": _runs(recs),
+                     "launch_counters": [launches[k] for k in ("asked", "issued", "rounds", "groups")],
+                     "prune_counters": [counters[k] for k in ("staged", "staged_no_survivors", "kept_full_sweep", "not_eligible")],
+                     "memo": list(launches["memo"]), "results": [_raw(t) for t in res]})
+        engine.release_workspace()
     return rows
+
+
+def _against_base(doc, path):
+    """doc with what equals the earlier dump `path` replaced by a reference to it (see --base)"""
+    base = json.load(open(path))
+    ref = {"file": os.path.basename(path), "sha256": hashlib.sha256(open(path, "rb").read()).hexdigest()[:16], "workspace_equal": doc["workspace"] == {k: v for k, v in base.items() if k not in ("gpu", "base")}}
+    rows, old = doc.get("gpu", []), base.get("gpu", [])
+    if rows[:len(old)] == old:
+        ref["gpu_rows_equal"] = len(old)
+        rows = rows[len(old):]
+    return {"base": ref, "workspace": {} if ref["workspace_equal"] else doc["workspace"], "gpu": rows}
 
 
 def _lines(doc):
     """compact JSON, one entry point / one case per line, the size lists wrapped"""
     out = ["{"]
+    if "base" in doc:
+        out.append(' "base": %s,' % json.dumps(doc["base"]))
     for fn, e in doc["workspace"].items():
         sizes = e["bytes"]
         out.append(' "%s": {"descriptors": %d, "grid_sha256": "%s", "bytes": [' % (fn, e["descriptors"], e["grid_sha256"]))
@@ -241,12 +269,13 @@ def _lines(doc):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--gpu", action="store_true", help="also run the small cases on cuda:0")
+    ap.add_argument("--base", default=None, help="an earlier dump: what equals it is referred to, not written again")
     ap.add_argument("--out", default=None, help="write the JSON here instead of stdout")
     a = ap.parse_args()
     doc = {"workspace": workspace_plan(_lib.load())}
     if a.gpu:
         doc["gpu"] = gpu_plan()
-    text = _lines(doc)
+    text = _lines(_against_base(doc, a.base) if a.base else doc)
     if a.out:
         with open(a.out, "w") as fh:
             fh.write(text)
