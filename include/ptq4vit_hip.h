@@ -101,6 +101,10 @@ typedef struct p4v_linear_desc {
 size_t p4v_linear_workspace_bytes(const p4v_linear_desc* desc);
 
 /*
+ * d_grad          raw_grad, shaped like d_out.  Every entry point below that takes it reads it if and only if desc->metric
+ *                 is P4V_METRIC_HESSIAN (there it is required); under any other metric it may be NULL or any pointer --
+ *                 the call never dereferences it and its results do not depend on it (linear.py:409-421: only the
+ *                 hessian similarity uses raw_grad; the raw_out-weighted metrics weight with raw_out).
  * d_mult          [eq_n+1] candidate multipliers alpha + i(beta-alpha)/eq_n rounded to fp32 (linear.py:544)
  * d_w_interval    [n_V*n_H] out: calibrated weight intervals (reference shape n_V,1,n_H,1)
  * d_a_interval    [n_a]     out: calibrated activation intervals (reference shape n_a,1)

@@ -557,6 +557,18 @@ void metric_epi(int metric, int* epi, int* wt_mode) {
     }
 }
 
+// The weight-source rule (include/ptq4vit_hip.h, d_grad): raw_grad is read if and only if the metric is hessian, as in the
+// reference (linear.py:409-421).  Every *_impl takes its tensor record through this function, so Pass::G and the split job's
+// kp.G are null under every other metric whatever the caller passed, and every `Wt = G ? G : O` below resolves to raw_out
+// there.  That matters to the kernels that take the weight from the POINTER and not from wt_mode -- k_bound's epilogue reads
+// Wt in place -- and to the host code that keys on it (slice_fill's gather of raw_grad rows, the conv's transposed copy).
+template <typename Tensors> Tensors grad_by_metric(Tensors t, int metric) {
+    int epi = 0, wt_mode = 0;
+    metric_epi(metric, &epi, &wt_mode);
+    if (wt_mode != 1) t.G = nullptr;
+    return t;
+}
+
 // ---- launch helpers ---------------------------------------------------------------------------
 int launch_absmax(Ctx& c, const float* src, const long (&st)[4], int D0, int D1, int R, int C, int nV, int nH,
                   int crb_r, int crb_c, int signed_max, unsigned* out) {
@@ -2710,7 +2722,7 @@ struct LinearCall {
     EpiCache ecache[2];                               // per side: k_sweep6's epilogue operands in fragment order
     SliceCache slice, slice2;                         // the sample slices of the pruned passes (two tiers)
 
-    LinearCall(Ctx& c_, const p4v_linear_desc* d_, const LinearTensors& t_, const Stage& sg_) : c(c_), d(d_), t(t_), sg(sg_) {}
+    LinearCall(Ctx& c_, const p4v_linear_desc* d_, const LinearTensors& t_, const Stage& sg_) : c(c_), d(d_), t(grad_by_metric(t_, d_->metric)), sg(sg_) {}
 
     // argument checks, geometry, the path decisions, the workspace
     int build() {
@@ -3191,7 +3203,7 @@ struct MatMulCall {
     PlaneCache plane_A, plane_B;
     SliceCache slice;
 
-    MatMulCall(Ctx& c_, const p4v_matmul_desc* d_, const MatMulTensors& t_, const Stage& sg_) : c(c_), d(d_), t(t_), sg(sg_) {}
+    MatMulCall(Ctx& c_, const p4v_matmul_desc* d_, const MatMulTensors& t_, const Stage& sg_) : c(c_), d(d_), t(grad_by_metric(t_, d_->metric)), sg(sg_) {}
 
     // argument checks and geometry
     int build() {
@@ -3478,7 +3490,8 @@ int attn_impl(const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulTenso
 // that block's scale only, every other block on the interval entering the step, the score the full-output score per head; each
 // step is one sweep of the whole operand (no pruning, no pass memo: first version).  Score tables [round][step][eq_n][heads],
 // steps = A blocks then B blocks (split-of-softmax: the 20-row split table, then B blocks).
-int matmul_blocks_impl(const p4v_matmul_desc* d, const MatMulBlocks& mb, const MatMulTensors& t, const Stage& sg, Ctx& c) {
+int matmul_blocks_impl(const p4v_matmul_desc* d, const MatMulBlocks& mb, const MatMulTensors& t_, const Stage& sg, Ctx& c) {
+    const MatMulTensors t = grad_by_metric(t_, d->metric);
     const int H = d->heads, Z = d->batch * d->heads, M = d->M, K = d->K, N = d->N;
     const int nVA = mb.nVA, nHA = mb.nHA, nVB = mb.nVB, nHB = mb.nHB;
     if (nVA < 1 || nHA < 1 || nVB < 1 || nHB < 1) return fail(P4V_ERR_INVALID, "matmul: non-positive block count");
@@ -3583,7 +3596,8 @@ int matmul_blocks_impl(const p4v_matmul_desc* d, const MatMulBlocks& mb, const M
 // The device pointers of one conv_impl call are a Linear's: weight [oc][ic][kh][kw], bias [oc], x [b][ic][H][W], raw_out / raw_grad
 // [b][oc][fh][fw], intervals [oc] or [1] / [1].  There is no conv forward: fwd_out stays null.
 typedef LinearTensors ConvTensors;
-int conv_impl(const p4v_conv_desc* d, const ConvTensors& t, const Stage& sg, Ctx& c) {
+int conv_impl(const p4v_conv_desc* d, const ConvTensors& t_, const Stage& sg, Ctx& c) {
+    const ConvTensors t = grad_by_metric(t_, d->metric);
     const int b = d->batch, ic = d->in_channels, H = d->height, Wd = d->width, oc = d->out_channels;
     const int kh = d->kernel_h, kw = d->kernel_w;
     if (kh <= 0 || kw <= 0 || d->stride_h <= 0 || d->stride_w <= 0 || d->pad_h < 0 || d->pad_w < 0 || d->dil_h <= 0 || d->dil_w <= 0)

@@ -1612,8 +1612,10 @@ __device__ __forceinline__ void k_bound_body(const SweepParams& p, const uint3 b
     }
 #undef P4V_BLD
     // ---- metric epilogue: raw_out / weight read in place, one sum per (64-row slab, 32-column group) ----
-    // The weight tensor is raw_grad (hessian) or raw_out itself (the host passes Wt = O for the raw_out-weighted metrics:
-    // square-weighted (w d)^2 with w = raw_out, linear-weighted |w| d^2) -- no run-time switch in the element loop.
+    // The weight tensor is raw_grad (hessian) or raw_out itself: square-weighted (w d)^2 with w = raw_out, linear-weighted
+    // |w| d^2 -- no run-time switch in the element loop, so this kernel takes the weight from the POINTER, not from wt_mode.
+    // The host passes Wt = G ? G : O, and its Pass::G is null under every metric but hessian even where the caller passed a
+    // raw_grad (grad_by_metric, p4v_api.hip): Wt = O for the raw_out-weighted metrics.
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
         if (NB > 1 && n0 + j * 32 >= p.N) {                // (a 32-column group of pure padding: its own wave wrote this zero before)
@@ -4423,7 +4425,7 @@ __device__ __forceinline__ void k_row_mass_body(const RowMassParams& a_, const u
     else
         for (long i = lane; i < cols; i += 64) {
             const float v = src[i];
-            s += wt_mode == 2 ? fabsf(v) : v * v;
+            s += wt_mode == 3 ? fabsf(v) : v * v;      // the metric's own weight: |o| d^2 (3), (g d)^2 / (o d)^2 (1 / 2)
         }
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
     if (lane == 0) mass[r] = s;

@@ -11,11 +11,16 @@ state the share they need as (slice rows, lower bound, upper bound) and `run` as
   "default"  the pass memo is on, so the pruned passes may read their survivors back (host_sync_ok)
   "nomemo"   desc.reserved bit 1: the host does not read the survivors, stage B2 is always launched and the merge decides
   "xcheck"   the default call with variant bit 134217728: every pruned pass is followed by its full sweep, the engine compares
-prune=False (desc.reserved bit 3) is the same call with full sweeps only: the reference of the intervals."""
+prune=False (desc.reserved bit 3) is the same call with full sweeps only: the reference of the intervals.
+
+METRIC_CASES: seven of the cases again (the forced ones: their staging does not depend on a share of raw_grad) under the four
+difference metrics that read no raw_grad -- `metric_case(name, metric, grad_given)` makes the run; grad_given False: no tensor,
+True: the case's own raw_grad, "adversarial": 1 / (|raw_out| + 1e-3) (sweep_plan_cases.grad_of).  `metric_oracle(name, metric)`
+is the numpy reference of that call."""
 import torch
 
 from tests.search_round_cases import ROUNDS, _call, _cuda, run_case  # noqa: F401  (run_case: re-exported)
-from tests.sweep_plan_cases import LOOSE, conv_inputs, linear_inputs, matmul_inputs
+from tests.sweep_plan_cases import LOOSE, conv_inputs, grad_of, linear_inputs, matmul_inputs
 
 MODES = ("default", "nomemo", "xcheck")
 XCHECK = 134217728
@@ -38,18 +43,24 @@ def _linear_grad(grad, shape, kind, spread, seed):
     return grad
 
 
-def _linear(K, N, *, seed, images, tokens, grad="cls", spread=0.0, shares=(), n_V=1, postgelu=False, variant=0, tuning=(), scores=False):
+def _given(grad_given, grad, out):
+    return grad_of({False: "none", True: "seeded"}.get(grad_given, grad_given), grad, out)
+
+
+def _linear(K, N, *, seed, images, tokens, grad="cls", spread=0.0, shares=(), n_V=1, postgelu=False, variant=0, tuning=(), scores=False,
+            metric="hessian", grad_given=True):
     def run(eng, mode, prune=True):
         w, b, x, out, gr = linear_inputs(K, N, seed=seed, images=images, tokens=tokens, postgelu=postgelu)
         gr = _linear_grad(gr, out.shape, grad, spread, seed)
-        for k, lo, hi in shares:
+        for k, lo, hi in shares if metric == "hessian" else ():     # (the shares are those of raw_grad^2: the hessian weight)
             assert lo <= slice_share(gr, k) < hi, (k, lo, slice_share(gr, k), hi)
+        gr = _given(grad_given, gr, out)
         eng.debug_variant(variant | (XCHECK if mode == "xcheck" else 0))
         for key, value in tuning:
             eng.debug_tuning(key, value)
         try:
             job = eng.linear_job(weight=_cuda(w), bias=_cuda(b), x=_cuda(x), out=_cuda(out), grad=_cuda(gr), w_bit=8, a_bit=8,
-                                 metric="hessian", n_V=n_V, n_H=1, n_a=1, postgelu=postgelu, want_scores=scores, prune=prune, **ROUNDS)
+                                 metric=metric, n_V=n_V, n_H=1, n_a=1, postgelu=postgelu, want_scores=scores, prune=prune, **ROUNDS)
             return _call(eng, job, mode)
         finally:
             eng.debug_variant(0)
@@ -58,12 +69,13 @@ def _linear(K, N, *, seed, images, tokens, grad="cls", spread=0.0, shares=(), n_
     return run
 
 
-def _matmul(M, K, N, *, seed, sos=False):
+def _matmul(M, K, N, *, seed, sos=False, metric="hessian", grad_given=True):
     def run(eng, mode, prune=True):
         A, B, out, grad = matmul_inputs(M, K, N, seed=seed, sos=sos)
+        grad = _given(grad_given, grad, out)
         eng.debug_variant(LOOSE | (XCHECK if mode == "xcheck" else 0))
         try:
-            job = eng.matmul_job(A=_cuda(A), B=_cuda(B), out=_cuda(out), grad=_cuda(grad), A_bit=8, B_bit=8, metric="hessian", sos=sos,
+            job = eng.matmul_job(A=_cuda(A), B=_cuda(B), out=_cuda(out), grad=_cuda(grad), A_bit=8, B_bit=8, metric=metric, sos=sos,
                                  prune=prune, **ROUNDS)
             return _call(eng, job, mode)
         finally:
@@ -71,13 +83,14 @@ def _matmul(M, K, N, *, seed, sos=False):
     return run
 
 
-def _conv(*, seed, a_bit):
+def _conv(*, seed, a_bit, metric="hessian", grad_given=True):
     def run(eng, mode, prune=True):
         w, b, x, out, grad = conv_inputs(seed=seed, images=10, size=64, patch=8)
+        grad = _given(grad_given, grad, out)
         eng.debug_variant(LOOSE | (XCHECK if mode == "xcheck" else 0))
         try:
             job = eng.conv_job(weight=_cuda(w), bias=_cuda(b), x=_cuda(x), out=_cuda(out), grad=_cuda(grad), stride=(8, 8), padding=(0, 0),
-                               dilation=(1, 1), w_bit=8, a_bit=a_bit, metric="hessian", prune=prune, **ROUNDS)
+                               dilation=(1, 1), w_bit=8, a_bit=a_bit, metric=metric, prune=prune, **ROUNDS)
             return _call(eng, job, mode)
         finally:
             eng.debug_variant(0)
@@ -116,3 +129,48 @@ CASES = [
 
 def modes_of(name):
     return tuple(m for m in MODES if m != "xcheck" or name in XCHECKED)
+
+
+METRICS = ("L2_norm", "L1_norm", "linear_weighted_L2_norm", "square_weighted_L2_norm")
+GRADS_GIVEN = (False, True, "adversarial")
+
+# name -> (maker, arguments, keywords): the rows of CASES that prune by force, without their shares of raw_grad.  Under these
+# metrics they reach what the single pruned Linear of the metric grid does not: the slice kernels (k_slice_a, k_slice_b), the
+# pruned split search, the conv slice (k_gather_im2col), the synthetic candidate of three score blocks, the twin.
+METRIC_SPECS = {
+    "lin650_flat_forced": (_linear, (192, 96), dict(seed=41, grad="flat", variant=LOOSE, **L650)),
+    "lin650_nV3": (_linear, (192, 96), dict(seed=42, n_V=3, variant=LOOSE, **L650)),
+    "postgelu650": (_linear, (192, 96), dict(seed=45, postgelu=True, variant=LOOSE, **L650)),
+    "qk65": (_matmul, (65, 64, 65), dict(seed=46)),
+    "sos65": (_matmul, (65, 65, 64), dict(seed=48, sos=True)),
+    "conv640_a32": (_conv, (), dict(seed=49, a_bit=32)),
+    "conv640_a8": (_conv, (), dict(seed=50, a_bit=8)),
+}
+METRIC_CASES = [(name, metric) for name in METRIC_SPECS for metric in METRICS]
+
+
+def metric_case(name, metric, grad_given):
+    make, args, kw = METRIC_SPECS[name]
+    return make(*args, metric=metric, grad_given=grad_given, **kw)
+
+
+def metric_oracle(name, metric):
+    """the numpy reference of metric_case(name, metric, .): (the intervals in the order the engine returns them; None: not searched, sos)"""
+    from oracle.ptq4vit_oracle import ConvOracle, LinearOracle, MatMulOracle
+    make, args, kw = METRIC_SPECS[name]
+    np_ = lambda *ts: [t.numpy() for t in ts]
+    if make is _linear:
+        w, b, x, out, _ = np_(*linear_inputs(*args, seed=kw["seed"], images=kw["images"], tokens=kw["tokens"], postgelu=kw.get("postgelu", False)))
+        o = LinearOracle(w, b, w_bit=8, a_bit=8, metric=metric, n_V=kw.get("n_V", 1), postgelu=kw.get("postgelu", False), **ROUNDS)
+        o.calibration_step2(x, out, None)
+        return [o.w_interval, o.a_interval], False
+    if make is _conv:
+        w, b, x, out, _ = np_(*conv_inputs(seed=kw["seed"], images=10, size=64, patch=8))
+        o = ConvOracle(w, b, stride=8, w_bit=8, a_bit=kw["a_bit"], metric=metric, **ROUNDS)
+        o.calibration_step2(x, out, None)
+        return [o.w_interval, o.a_interval if kw["a_bit"] < 32 else None], False
+    sos = kw.get("sos", False)
+    A, B, out, _ = np_(*matmul_inputs(*args, seed=kw["seed"], sos=sos))
+    o = MatMulOracle(A_bit=8, B_bit=8, metric=metric, sos=sos, **ROUNDS)
+    res = o.calibration_step2(A, B, out, None)
+    return [res["A_interval"], res["B_interval"]] + ([res["split"]] if sos else []), sos

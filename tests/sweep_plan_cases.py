@@ -30,6 +30,24 @@ def _grad(shape, g, token_dim):
     return grad
 
 
+GRADS = ("seeded", "none", "adversarial", "nan")
+
+
+def grad_of(kind, grad, out):
+    """the raw_grad a case hands to the engine: "seeded" the generator's own, "none" no tensor, "adversarial" 1 / (|raw_out| + 1e-3)
+    -- finite, and it reverses the ranking of the elements by |raw_out|, so a kernel of a raw_out-weighted metric that read it would
+    move its argmax by many entries --, "nan" all NaN.  A metric other than hessian must not read any of them
+    (include/ptq4vit_hip.h, d_grad)."""
+    assert kind in GRADS, kind
+    if kind == "none":
+        return None
+    if kind == "adversarial":
+        return 1.0 / (out.abs() + 1e-3)
+    if kind == "nan":
+        return torch.full_like(out, float("nan"))
+    return grad
+
+
 def linear_inputs(K, N, *, seed, images=2, tokens=64, postgelu=False):
     """(weight, bias, x, out, grad) of a seeded Linear layer, on the host"""
     g = torch.Generator().manual_seed(seed)
@@ -43,11 +61,11 @@ def linear_inputs(K, N, *, seed, images=2, tokens=64, postgelu=False):
 
 
 def _linear(K, N, *, seed, images=2, tokens=64, n_V=1, postgelu=False, variant=0, metric="hessian"):
-    def run(eng, prune):
-        w, b, x, out, grad = linear_inputs(K, N, seed=seed, images=images, tokens=tokens, postgelu=postgelu)
+    def run(eng, prune, grad="seeded"):
+        w, b, x, out, gr = linear_inputs(K, N, seed=seed, images=images, tokens=tokens, postgelu=postgelu)
         eng.debug_variant(variant)
         try:
-            res = eng.linear_calibrate(weight=_cuda(w), bias=_cuda(b), x=_cuda(x), out=_cuda(out), grad=_cuda(grad), w_bit=8, a_bit=8,
+            res = eng.linear_calibrate(weight=_cuda(w), bias=_cuda(b), x=_cuda(x), out=_cuda(out), grad=_cuda(grad_of(grad, gr, out)), w_bit=8, a_bit=8,
                                        metric=metric, n_V=n_V, n_H=1, n_a=1, postgelu=postgelu, prune=prune, want_scores=not prune,
                                        **SEARCH)
         finally:
@@ -70,23 +88,27 @@ def matmul_inputs(M, K, N, *, seed, sos=False, batch=2, heads=2):
 
 
 def _matmul(M, K, N, *, seed, sos=False, batch=2, heads=2, metric="hessian"):
-    def run(eng, prune):
-        A, B, out, grad = matmul_inputs(M, K, N, seed=seed, sos=sos, batch=batch, heads=heads)
-        res = eng.matmul_calibrate(A=_cuda(A), B=_cuda(B), out=_cuda(out), grad=_cuda(grad), A_bit=8, B_bit=8, metric=metric,
+    def run(eng, prune, grad="seeded"):
+        A, B, out, gr = matmul_inputs(M, K, N, seed=seed, sos=sos, batch=batch, heads=heads)
+        res = eng.matmul_calibrate(A=_cuda(A), B=_cuda(B), out=_cuda(out), grad=_cuda(grad_of(grad, gr, out)), A_bit=8, B_bit=8, metric=metric,
                                    sos=sos, prune=prune, want_scores=not prune, **SEARCH)
         return [t for t in res if t is not None]
     return run
 
 
 def _matmul_blocks(name, *, metric=None):
-    """the fixture's inputs and blocks; `metric` replaces the fixture's own (a hessian fixture brings its raw_grad)"""
-    def run(eng, prune):
+    """the fixture's inputs and blocks; `metric` replaces the fixture's own (a hessian fixture brings its raw_grad: by default it is
+    passed under hessian only, a `grad` kind of GRADS passes that one under any metric)"""
+    def run(eng, prune, grad=None):
         z = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
         p = json.loads(str(z["params"]))
         p["metric"] = metric or p["metric"]
         t = lambda k: torch.from_numpy(np.ascontiguousarray(z[k])).cuda()
         blocks = (p.get("n_V_A", 1), p.get("n_H_A", 1), p.get("n_V_B", 1), p.get("n_H_B", 1))
-        res = eng.matmul_calibrate(A=t("A"), B=t("B"), out=t("out"), grad=t("grad") if p["metric"] == "hessian" else None,
+        gr = t("grad") if p["metric"] == "hessian" else None
+        if grad is not None:
+            gr = _cuda(grad_of(grad, torch.from_numpy(np.ascontiguousarray(z["grad"])), torch.from_numpy(np.ascontiguousarray(z["out"]))))
+        res = eng.matmul_calibrate(A=t("A"), B=t("B"), out=t("out"), grad=gr,
                                    A_bit=p["A_bit"], B_bit=p["B_bit"], metric=p["metric"], eq_alpha=p["eq_alpha"], eq_beta=p["eq_beta"],
                                    eq_n=p["eq_n"], search_round=p["search_round"], sos=p["sos"], blocks=blocks, want_scores=True)
         return [t for t in res if t is not None]
@@ -104,9 +126,9 @@ def conv_inputs(*, seed, images=2, size=32, patch=16):
 
 
 def _conv(*, seed, metric="hessian"):
-    def run(eng, prune):
-        w, b, x, out, grad = conv_inputs(seed=seed)
-        res = eng.conv_calibrate(weight=_cuda(w), bias=_cuda(b), x=_cuda(x), out=_cuda(out), grad=_cuda(grad), stride=(16, 16),
+    def run(eng, prune, grad="seeded"):
+        w, b, x, out, gr = conv_inputs(seed=seed)
+        res = eng.conv_calibrate(weight=_cuda(w), bias=_cuda(b), x=_cuda(x), out=_cuda(out), grad=_cuda(grad_of(grad, gr, out)), stride=(16, 16),
                                  padding=(0, 0), dilation=(1, 1), w_bit=8, a_bit=32, metric=metric, prune=prune,
                                  want_scores=not prune, **SEARCH)
         return [t for t in res if t is not None]
@@ -133,15 +155,15 @@ SHAPES = [
 CASES = [(name, make(*args, **kw), pruned) for name, make, (args, kw), pruned in SHAPES]
 
 
-def run_case(eng, run, prune):
+def run_case(eng, run, prune, **kw):
     """One case with launch records: (result tensors, [(kernel, stage, grid_x, grid_z)], launch counters, prune counters); the
-    launch counters also carry the pass memo's (hits, misses) as "memo"."""
+    launch counters also carry the pass memo's (hits, misses) as "memo".  `grad=` one of GRADS: the raw_grad handed to the engine."""
     eng.launch_counters(reset=True)
     eng.prune_counters(reset=True)
     eng.stats_reset()
     eng.stats_enable(True)
     try:
-        res = run(eng, prune)
+        res = run(eng, prune, **kw)
         torch.cuda.synchronize()
         st = eng.stats_get()
         recs = [(r["kernel"], r["stage"], r["grid_x"], r["grid_z"]) for r in eng.stats_launches()]

@@ -15,12 +15,17 @@ rows are pruned under variant 8388608 (prune even where the slice's bounds are l
 Bars.  The B1 totals of the two kernels may differ by prune_margin() * |total| (1e-4: csrc/p4v_api.hip, the deviation the
 exactness argument of the pruning allows the bound); selections and intervals must be bit-identical between pruning on, off and
 the engine's own cross-check (variant 134217728), on the new kernel and on the old one.
+test_every_metric_with_and_without_bias_and_column_blocks also ties the totals to the numpy oracle: see _bound_is_a_score.
 """
+import functools
 import itertools
 
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+from tests.helpers import SCORE_RTOL, record_margin
 
 pytestmark = pytest.mark.gpu
 
@@ -39,9 +44,8 @@ def eng():
     return engine
 
 
-def _layer(T, N, K, bias, seed, metric, images=IMAGES):
-    """tensors of one layer; raw_grad only for the hessian metric, as the quant layers pass it (the engine takes the metric
-    weight of stage B1 from raw_grad whenever it is given)"""
+def _host_layer(T, N, K, bias, seed, images=IMAGES):
+    """host tensors of one layer"""
     g = torch.Generator().manual_seed(seed)
     x = torch.randn(images, T, K, generator=g)
     x[:, 0] *= 4.0                                        # class-token rows: heavy in raw_out too (the raw_out-weighted metrics)
@@ -50,8 +54,17 @@ def _layer(T, N, K, bias, seed, metric, images=IMAGES):
     out = F.linear(x, w, b)
     grad = torch.randn(out.shape, generator=g) * 1e-10
     grad[:, 0] *= 300.0 * torch.exp(torch.randn(images, 1, generator=g))
-    dev = lambda t: None if t is None else t.cuda()
-    return dict(weight=dev(w), bias=dev(b), x=dev(x), out=dev(out), grad=dev(grad) if metric == "hessian" else None)
+    return dict(weight=w, bias=b, x=x, out=out, grad=grad)
+
+
+def _layer(T, N, K, bias, seed, metric, images=IMAGES, grad_given=False):
+    """tensors of one layer on the GPU; raw_grad for the hessian metric, as the quant layers pass it, and for any other metric
+    with `grad_given`: the engine reads raw_grad if and only if the metric is hessian (include/ptq4vit_hip.h, d_grad), so under
+    the other metrics the tensor changes nothing -- stage B1 weights its total with raw_out there."""
+    t = _host_layer(T, N, K, bias, seed, images)
+    if metric != "hessian" and not grad_given:
+        t["grad"] = None
+    return {k: None if v is None else v.cuda() for k, v in t.items()}
 
 
 def _run(eng, args, variant=0, b1_path=0, prune=True, totals=False):
@@ -115,12 +128,53 @@ def test_wide_k_bound_matches_the_previous_kernel_and_the_unpruned_search(eng, i
     _check(eng, args, f"{IMAGES} x {T} rows, N {N}, K {K}, n_V {n_V}, bias {bias}, {metric}")
 
 
+@functools.lru_cache(maxsize=None)
+def _oracle_tables(metric, n_V, bias):
+    """the numpy oracle's score tables of the 650-row layer, one round: [weight search [100][n_V], activation search [100]]"""
+    from oracle.ptq4vit_oracle import LinearOracle
+    t = {k: None if v is None else v.numpy() for k, v in _host_layer(65, 96, 192, bias, 900 + n_V).items()}
+    o = LinearOracle(t["weight"], t["bias"], w_bit=8, a_bit=8, metric=metric, n_V=n_V, search_round=1, **SEARCH)
+    o.calibration_step2(t["x"], t["out"], t["grad"] if metric == "hessian" else None)
+    return [np.asarray(tab, dtype=np.float64) for _, tab in o.trace]
+
+
+def _bound_is_a_score(total, table, what):
+    """The soundness premise of the pruning: the bound of stage B1 is the score that some candidate really has, over ALL samples.
+    So a B1 total of a single-block pass lies within SCORE_RTOL of an entry of the oracle's table of that pass, and does not
+    exceed the table's maximum by more than SCORE_RTOL |max| (scores are negated errors: the maximum is the best).  A total
+    weighted with another tensor than the metric's is off by orders of magnitude."""
+    table = table.reshape(-1)
+    dist = float(np.min(np.abs(table - total) / np.abs(table)))
+    over = (total - table.max()) / abs(table.max())
+    print(f"[bound] {what}: B1 total {total:.6e}, nearest oracle entry {dist:.3e} away, table maximum {table.max():.6e}")
+    record_margin("b1_total_to_nearest_oracle_entry", dist)
+    assert dist <= SCORE_RTOL, (what, total, dist)
+    assert over <= SCORE_RTOL, (what, total, table.max())
+
+
 @pytest.mark.parametrize("metric,n_V,bias", [(m, v, b) for m in METRICS for v, b in ((1, False), (3, True))])
 def test_every_metric_with_and_without_bias_and_column_blocks(eng, metric, n_V, bias):
     """each of the five difference metrics (four epilogues) with n_V in {1, 3} and with / without bias, at one shape with padding
-    in rows (650 = 10 slabs + 10 rows) and columns (96 = one slab and a half)"""
-    args = dict(_layer(65, 96, 192, bias, 900 + n_V, metric), w_bit=8, a_bit=8, n_V=n_V, n_H=1, n_a=1, search_round=1, metric=metric, **SEARCH)
-    _check(eng, args, f"650 rows, N 96, K 192, n_V {n_V}, bias {bias}, {metric}")
+    in rows (650 = 10 slabs + 10 rows) and columns (96 = one slab and a half); the metrics that read no raw_grad without one and
+    with one (grad_given): intervals and B1 totals must be the same, bit for bit.  Stage B1 is also tied to the numpy oracle
+    (_bound_is_a_score): the totals of the single-block passes -- with n_V = 1 both searches, with n_V = 3 the activation search,
+    the last total."""
+    tabs = _oracle_tables(metric, n_V, bias)
+    seen = []
+    for grad_given in ((True,) if metric == "hessian" else (False, True)):
+        what = f"650 rows, N 96, K 192, n_V {n_V}, bias {bias}, {metric}, grad_given {grad_given}"
+        args = dict(_layer(65, 96, 192, bias, 900 + n_V, metric, grad_given=grad_given), w_bit=8, a_bit=8, n_V=n_V, n_H=1, n_a=1, search_round=1,
+                    metric=metric, **SEARCH)
+        _check(eng, args, what)
+        iv, _, totals = _run(eng, args, LOOSE, 0, totals=True)
+        if n_V == 1:
+            assert len(totals) == 2, (what, totals)
+            _bound_is_a_score(totals[0], tabs[0], what + ", weight search")
+        _bound_is_a_score(totals[-1], tabs[1], what + ", activation search")
+        seen.append((iv, totals))
+    for iv, totals in seen[1:]:
+        assert totals == seen[0][1], (metric, n_V, bias, totals, seen[0][1])
+        assert all(torch.equal(a, b) for a, b in zip(iv, seen[0][0])), (metric, n_V, bias)
 
 
 def test_chunked_candidate_plane_runs_the_early_returns(eng):

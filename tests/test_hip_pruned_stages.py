@@ -11,13 +11,19 @@ means a stage was added, dropped or moved, a counter that changes means a pass w
 a refactor.
 Also asserted: the intervals of every mode are bit-equal to those of the same call with prune=False (full sweeps only), and the
 "xcheck" call returns without the engine's own mismatch error.
+
+The cases above are hessian.  test_pruned_passes_under_the_metrics_that_read_no_raw_grad runs the forced ones under the four
+other difference metrics, with and without a raw_grad (tests/pruned_pass_cases.py, METRIC_CASES): those metrics read raw_out alone
+(include/ptq4vit_hip.h, d_grad), so the tensor must change nothing.
 """
 import functools
 
+import numpy as np
 import pytest
 import torch
 
-from tests.pruned_pass_cases import CASES, modes_of, run_case
+from tests.helpers import record_margin
+from tests.pruned_pass_cases import CASES, GRADS_GIVEN, METRIC_CASES, metric_case, metric_oracle, modes_of, run_case
 
 pytestmark = pytest.mark.gpu
 
@@ -178,4 +184,83 @@ def test_pruned_passes_launch_and_count_as_before(eng, name, run):
         assert len(got["intervals"]) == len(full["intervals"]) > 0
         for a, b in zip(got["intervals"], full["intervals"]):
             assert torch.equal(a, b), (name, mode, a, b)
+    eng.release_workspace()
+
+
+@functools.lru_cache(maxsize=None)
+def _metric_oracle(name, metric):
+    return metric_oracle(name, metric)
+
+
+@pytest.mark.parametrize("name,metric", METRIC_CASES, ids=[f"{n}-{m}" for n, m in METRIC_CASES])
+def test_pruned_passes_under_the_metrics_that_read_no_raw_grad(eng, name, metric):
+    """The forced cases under L2_norm, L1_norm and the two raw_out-weighted metrics, in every mode, with no raw_grad, with the
+    case's own and with the adversarial one: each call staged its passes, its intervals are bit-identical to the full sweeps'
+    (prune=False) -- so to each other -- and the full sweeps' intervals are the numpy oracle's at the bar of tests/helpers.py (the
+    oracle's, or the neighbouring entry of the same candidate table)."""
+    from tests.helpers import assert_on_candidate_grid, candidate_grid
+    from tests.pruned_pass_cases import ROUNDS
+    full = run_case(eng, functools.partial(metric_case(name, metric, False), prune=False), "default")
+    assert full["prune_counters"]["staged"] == 0, (name, metric, full["prune_counters"])
+    want, sos = _metric_oracle(name, metric)
+    mult = candidate_grid(ROUNDS["eq_alpha"], ROUNDS["eq_beta"], ROUNDS["eq_n"])
+    assert len(full["intervals"]) == len(want)
+    for k, (got, ref) in enumerate(zip(full["intervals"], want)):
+        if ref is None:
+            continue
+        got, ref = got.cpu().numpy().reshape(-1), np.asarray(ref, dtype=np.float32).reshape(-1)
+        if sos and k != 1:        # the split and A_interval = split / (q - 1): powers of two, not entries of the candidate grid
+            np.testing.assert_array_equal(got, ref, err_msg=f"{name} {metric} interval {k}")
+        else:
+            assert_on_candidate_grid(got, ref, mult, f"{name} {metric} interval {k} (full sweeps against the oracle)")
+    for mode in modes_of(name):
+        for given in GRADS_GIVEN:
+            got = run_case(eng, metric_case(name, metric, given), mode)       # ("xcheck": an engine-side mismatch raises here)
+            what = (name, metric, mode, f"grad_given={given}")
+            print(f"[pruned stages] {what}: prune {got['prune_counters']} {_runs(got['records'])}")
+            assert got["prune_counters"]["staged"] > 0, what
+            assert len(got["intervals"]) == len(full["intervals"]) > 0
+            for a, b in zip(got["intervals"], full["intervals"]):
+                assert torch.equal(a, b), (what, a, b)
+    eng.release_workspace()
+
+
+def _row_share(mass, k):
+    """share of the k heaviest rows in a float64 row mass"""
+    return float(torch.topk(mass, k).values.sum() / mass.sum())
+
+
+@pytest.mark.parametrize("metric,staged", [("square_weighted_L2_norm", True), ("linear_weighted_L2_norm", False)])
+def test_the_slice_is_ranked_and_measured_by_the_metrics_own_weight(eng, metric, staged):
+    """k_row_mass: o^2 per row under square_weighted_L2_norm ((o d)^2), |o| under linear_weighted_L2_norm (|o| d^2).  A 650-row
+    Linear whose ten class-token rows are four times as large: its 256 heaviest rows hold 0.57 of sum o^2 and 0.46 of sum |o|
+    (asserted here in float64, with room on both sides of the engine's threshold 0.5).  So the module is staged under the
+    square-weighted metric and keeps the full sweep under the linear-weighted one -- with the two masses exchanged it is the
+    other way round.  No variant bit: the engine's own decision (k_mass_fraction).  The intervals equal the unpruned search's."""
+    from tests.pruned_pass_cases import ROUNDS, _call, _cuda
+    from tests.sweep_plan_cases import linear_inputs
+    w, b, x, _, _ = linear_inputs(192, 96, seed=41, images=10, tokens=65)
+    x[:, 0] *= 4.0
+    out = torch.nn.functional.linear(x, w, b)
+    o = out.double().reshape(-1, out.shape[-1])
+    share_sq, share_abs = _row_share((o ** 2).sum(-1), 256), _row_share(o.abs().sum(-1), 256)
+    print(f"[pruned stages] the 256 heaviest of 650 rows hold {share_sq:.4f} of sum o^2 and {share_abs:.4f} of sum |o|")
+    record_margin("slice_share_of_o_squared", share_sq)
+    record_margin("slice_share_of_abs_o", share_abs)
+    assert share_sq >= 0.55 and share_abs <= 0.47, (share_sq, share_abs)
+
+    def run(eng, mode, prune=True):
+        job = eng.linear_job(weight=_cuda(w), bias=_cuda(b), x=_cuda(x), out=_cuda(out), grad=None, w_bit=8, a_bit=8, metric=metric,
+                             n_V=1, n_H=1, n_a=1, prune=prune, **ROUNDS)
+        return _call(eng, job, mode)
+    got = run_case(eng, run, "default")
+    full = run_case(eng, functools.partial(run, prune=False), "default")
+    c = got["prune_counters"]
+    print(f"[pruned stages] {metric}: prune {c} {_runs(got['records'])}")
+    if staged:
+        assert c["staged"] > 0 and c["kept_full_sweep"] == 0 and c["not_eligible"] == 0, (metric, c)
+    else:
+        assert c["staged"] == 0 and c["kept_full_sweep"] > 0 and c["not_eligible"] == 0, (metric, c)
+    for a, b_ in zip(got["intervals"], full["intervals"]):
+        assert torch.equal(a, b_), (metric, a, b_)
     eng.release_workspace()

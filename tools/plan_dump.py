@@ -12,8 +12,8 @@ they are at most 16 bytes, as a sha256 prefix otherwise); then the three-round c
 their modes, with the pass memo's (hits, misses) as well, and the cases of tests/pruned_pass_cases.py in theirs; last one
 fused MLP and one fused attention forward (the launch record of the producer kernel, then those of the consumer's sweep); after them
 the metric grid of tests/metric_grid_cases.py: the twelve shapes again, each in its own pruning setting, under the four difference
-metrics the rows above do not run.  No timings: two runs of the
-same code give the same file.
+metrics the rows above do not run, with the generators' raw_grad and then with none (rows marked "grad": "none").  No timings: two
+runs of the same code give the same file.
 
 --base FILE: an earlier dump of this tool.  Where this run's workspace section and its first GPU rows equal FILE's, they are not
 written again: the output names FILE, its sha256 and the number of rows found equal, and lists the rows after them.  Anything
@@ -231,6 +231,14 @@ def gpu_plan():
     for name, metric, run, pruned in METRIC_CASES:
         res, recs, launches, counters = run_case(engine, run, pruned)
         rows.append({"case": name, "metric": metric, "prune": int(pruned), "records": _runs(recs),
+                     "launch_counters": [launches[k] for k in ("asked", "issued", "rounds", "groups")],
+                     "prune_counters": [counters[k] for k in ("staged", "staged_no_survivors", "kept_full_sweep", "not_eligible")],
+                     "memo": list(launches["memo"]), "results": [_raw(t) for t in res]})
+        engine.release_workspace()
+    # ... and once more without a raw_grad: none of these metrics reads it, so every row must repeat the one above
+    for name, metric, run, pruned in METRIC_CASES:
+        res, recs, launches, counters = run_case(engine, run, pruned, grad="none")
+        rows.append({"case": name, "metric": metric, "grad": "none", "prune": int(pruned), "records": _runs(recs),
                      "launch_counters": [launches[k] for k in ("asked", "issued", "rounds", "groups")],
                      "prune_counters": [counters[k] for k in ("staged", "staged_no_survivors", "kept_full_sweep", "not_eligible")],
                      "memo": list(launches["memo"]), "results": [_raw(t) for t in res]})
