@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define P4V_VERSION 143 /* 0.1.4.3: + p4v_attn_* (fused int8 attention forward: q k^T, softmax and matmul2's quantiser in one kernel) */
+#define P4V_VERSION 144 /* 0.1.4.4: + p4v_wattn_* (the fused int8 attention forward for window attention: relative-position bias and shift mask) */
 
 /* similarity metrics: reference quant_layers/linear.py:399-424 */
 enum p4v_metric {
@@ -491,6 +491,46 @@ int p4v_attn_quant_forward(const p4v_attn_desc* desc, const float* d_q, const fl
                            const float* d_qk_A_interval, const float* d_qk_B_interval, const float* d_pv_A_interval,
                            const float* d_pv_B_interval, const float* d_split, float* d_out, float* d_probs, void* d_ws,
                            size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Fused window attention forward (opt-in, network level; Swin's WindowAttention): matmul2(softmax(matmul1(q, k^T) + bias
+ * (+ mask)), v) with int8 in between.  The chain, the planes and the envelope are those of p4v_attn_quant_forward above; what
+ * differs is the arithmetic between matmul1's output and the softmax.  `q` arrives ALREADY SCALED (the module multiplies q
+ * before matmul1, and matmul1 was calibrated on that operand): there is no `* scale`.  Per score element, two separate fp32
+ * additions in the module's order: t + bias[head][m][n], then, with a mask, + mask[window][m][n], window = (z / heads) %
+ * n_windows for z = (image * n_windows + window) * heads + head.  A -inf mask entry gives probability 0; a row whose entries
+ * are all -inf gives NaN, as torch's softmax does.
+ * Envelope: that of p4v_attn_quant_forward on `qk` / `pv`; in addition n_windows >= 1, qk.batch % n_windows == 0, has_mask != 0
+ * exactly when tensors.mask is non-null, bias and mask below 2^30 elements each (the kernel addresses them with 32-bit element
+ * offsets); anything else is P4V_ERR_INVALID / P4V_ERR_UNSUPPORTED before the first launch.
+ * The tensors, the workspace and its size travel in a record: q [b][h][M][D], kT [b][h][D][N], v [b][h][N][Dv] through
+ * qk.a_stride / qk.b_stride / pv.b_stride; bias [heads][M][N] fp32 contiguous; mask (optional) [n_windows][M][N] fp32
+ * contiguous; the four intervals and split as for p4v_attn_quant_forward (split: sos only); out [batch*heads][M][Dv]; probs:
+ * optional (may be NULL) [batch*heads][M][N] fp32; ws, ws_bytes: the workspace and its size -- the workspace contract above
+ * holds with p4v_wattn_workspace_bytes, which equals p4v_attn_workspace_bytes of the same two MatMuls; a smaller ws_bytes is
+ * refused before any launch.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct p4v_wattn_desc {
+    p4v_matmul_desc qk, pv;
+    int32_t n_windows;
+    int32_t has_mask;
+} p4v_wattn_desc;
+
+typedef struct p4v_wattn_tensors {
+    const float *q, *kT, *v;
+    const float* bias;
+    const float* mask;                 /* optional: NULL without a shift mask (has_mask = 0) */
+    const float *qk_A_interval, *qk_B_interval, *pv_A_interval, *pv_B_interval;
+    const float* split;                /* sos only */
+    float* out;
+    float* probs;                      /* optional */
+    void* ws;
+    size_t ws_bytes;
+} p4v_wattn_tensors;
+
+size_t p4v_wattn_workspace_bytes(const p4v_wattn_desc* desc);
+
+int p4v_wattn_quant_forward(const p4v_wattn_desc* desc, const p4v_wattn_tensors* tensors, void* stream);
 
 /* d_A_interval: [heads] (sos: [1]); d_B_interval: [heads]; d_split: [1] (sos only); d_out: [batch*heads][M][N] */
 int p4v_matmul_quant_forward(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_A_interval,

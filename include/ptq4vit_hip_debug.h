@@ -51,8 +51,9 @@ int p4v_debug_arena_ranges(uint64_t* out, int cap);
  * d_ws (plane 2: 0 unless out[4]), out[2] x out[3] = padded rows x columns of a plane (row-major int8), out[4] = 1 for the twin
  * pair.  The planes outlive the call: fc2's scratch lies behind them.  For the tests; nothing is launched. */
 int p4v_debug_mlp_planes(uint64_t* out);
-/* The same for the calling thread's last p4v_attn_quant_forward and matmul2's row plane(s), [batch*heads][Mp][Kp]: out[2] =
- * batch * heads * Mp (all rows of a plane), out[3] = Kp. */
+/* The same for the calling thread's last p4v_attn_quant_forward or p4v_wattn_quant_forward (the window call shares the chain
+ * and its record) and matmul2's row plane(s), [batch*heads][Mp][Kp]: out[2] = batch * heads * Mp (all rows of a plane),
+ * out[3] = Kp. */
 int p4v_debug_attn_planes(uint64_t info[5]);
 /* ONE sweep of the split-of-softmax split search (k_sos_split + k_finish) on the operands of `desc`, over the first n_cands of
  * the 20 splits: d_scores [n_cands] receives the score table, entries outside [c_lo, c_hi) as k_finish leaves them (-inf).

@@ -41,6 +41,17 @@ class AttnDesc(C.Structure):
     _fields_ = [("qk", MatMulDesc), ("pv", MatMulDesc), ("scale", C.c_float), ("reserved", C.c_int32)]
 
 
+class WattnDesc(C.Structure):
+    """p4v_wattn_desc: the two MatMuls of a fused window attention forward, the windows per image, whether a shift mask comes."""
+    _fields_ = [("qk", MatMulDesc), ("pv", MatMulDesc), ("n_windows", C.c_int32), ("has_mask", C.c_int32)]
+
+
+class WattnTensors(C.Structure):
+    """p4v_wattn_tensors: the device pointers of a p4v_wattn_quant_forward call, its workspace and the workspace's size."""
+    POINTERS = ("q", "kT", "v", "bias", "mask", "qk_A_interval", "qk_B_interval", "pv_A_interval", "pv_B_interval", "split", "out", "probs", "ws")
+    _fields_ = [(n, C.c_void_p) for n in POINTERS] + [("ws_bytes", C.c_size_t)]
+
+
 class MatMulBlocksDesc(C.Structure):
     """p4v_matmul_blocks_desc: the MatMul descriptor plus the row / column block counts of both operands."""
     _fields_ = [("mm", MatMulDesc)] + [(n, C.c_int32) for n in ("n_V_A", "n_H_A", "n_V_B", "n_H_B")]
@@ -119,7 +130,7 @@ EXPORTS = [
     "p4v_conv_workspace_bytes", "p4v_conv_calibrate",
     "p4v_calibrate_group", "p4v_launch_counters",
     "p4v_linear_quant_forward", "p4v_matmul_quant_forward", "p4v_mlp_workspace_bytes", "p4v_mlp_quant_forward",
-    "p4v_attn_workspace_bytes", "p4v_attn_quant_forward",
+    "p4v_attn_workspace_bytes", "p4v_attn_quant_forward", "p4v_wattn_workspace_bytes", "p4v_wattn_quant_forward",
     "p4v_amax_init_linear", "p4v_linear_search_w", "p4v_linear_search_a",
     "p4v_amax_init_matmul", "p4v_matmul_search_A", "p4v_sos_search_split", "p4v_matmul_search_B",
     "p4v_amax_init_conv", "p4v_conv_search_w_channelwise", "p4v_conv_search_w_layerwise", "p4v_conv_search_a",
@@ -186,6 +197,10 @@ def load():
     lib.p4v_attn_workspace_bytes.argtypes = [C.POINTER(AttnDesc)]
     lib.p4v_attn_quant_forward.restype = C.c_int
     lib.p4v_attn_quant_forward.argtypes = [C.POINTER(AttnDesc)] + [fp] * 10 + [vp, C.c_size_t, vp]
+    lib.p4v_wattn_workspace_bytes.restype = C.c_size_t
+    lib.p4v_wattn_workspace_bytes.argtypes = [C.POINTER(WattnDesc)]
+    lib.p4v_wattn_quant_forward.restype = C.c_int
+    lib.p4v_wattn_quant_forward.argtypes = [C.POINTER(WattnDesc), C.POINTER(WattnTensors), vp]
     lib.p4v_debug_attn_planes.restype = C.c_int
     lib.p4v_debug_attn_planes.argtypes = [C.POINTER(C.c_uint64)]
     lib.p4v_matmul_quant_forward.restype = C.c_int

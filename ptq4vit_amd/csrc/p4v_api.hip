@@ -3441,10 +3441,21 @@ int matmul_impl(const p4v_matmul_desc* d, const MatMulTensors& t, const Stage& s
 // plane's own layout) -- the fp32 score tensor, torch's `* scale` and softmax over it and k_pack_dual of it are gone.
 // `t1`, `t2`: the two MatMuls' records as p4v_matmul_quant_forward fills them -- t1.fwd_out is the optional fp32 copy of the
 // probabilities [Z][M][N] (matmul1 stores no other output), t2.A stays null (matmul2 reads k_attn_qk's planes).
-int attn_impl(const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulTensors& t2, Ctx& c) {
+// `win` (p4v_wattn_quant_forward; null: the plain call): the window record -- q arrives scaled, the kernel's window instance adds
+// the relative-position bias and the shift mask in place of `* scale`; everything else of the chain is the same.
+struct AttnWindow { const float* bias; const float* mask; int n_windows; };
+int attn_chain(const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulTensors& t2, Ctx& c, const AttnWindow* win) {
     const p4v_matmul_desc* d1 = &d->qk;
     const p4v_matmul_desc* d2 = &d->pv;
     // the envelope, before anything is planned or launched
+    if (win) {
+        if (win->n_windows < 1) return fail(P4V_ERR_INVALID, "wattn: n_windows = %d is not positive", win->n_windows);
+        if (d1->batch % win->n_windows) return fail(P4V_ERR_INVALID, "wattn: qk.batch = %d is no multiple of n_windows = %d", d1->batch, win->n_windows);
+        // (the kernel addresses both tensors with 32-bit element offsets)
+        if ((double)std::max(d1->heads, win->n_windows) * d1->M * d1->N >= (double)(1 << 30))
+            return fail(P4V_ERR_UNSUPPORTED, "wattn: a bias [%d][%d][%d] or mask [%d][%d][%d] of 2^30 elements or more", d1->heads, d1->M, d1->N,
+                        win->n_windows, d1->M, d1->N);
+    }
     if (d1->batch != d2->batch || d1->heads != d2->heads || d1->M != d2->M || d1->N != d2->K)
         return fail(P4V_ERR_INVALID, "attn: q k^T [%d][%d][%d][%d] is not the row operand of p v [%d][%d][%d][%d]", d1->batch, d1->heads, d1->M, d1->N,
                     d2->batch, d2->heads, d2->M, d2->K);
@@ -3473,16 +3484,29 @@ int attn_impl(const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulTenso
         q.mtiles = ch.Mp / SW_BM; q.nwg = Z * q.mtiles;
         g_alg_macs_cand = (double)Z * M * N * K1;
         g_alg_bytes = 4.0 * ((double)Z * M * K1 + (double)Z * N * K1) + (double)Z * M * N * (twin ? 2 : 1);
+        if (win) g_alg_bytes += 4.0 * (double)M * N * (H + (win->mask ? win->n_windows : 0));
         g_exec_frac = 1.0;
         // (three walks over the keys: the maximum, the sum, the write pass)
         const StatInfo si = stat_info(ATTN_RECORD_KIND, 3.0 * (double)Z * ch.Mp * (double)rup(N, 32) * pk.Kp, g_alg_macs_cand, q.nwg, 1, g_alg_bytes);
         const dim3 grid(q.nwg), block(256);
         const size_t lds = (size_t)4 * (twin ? 2 : 1) * 32 * ATTN_OROW;
+        if (win) {
+            AttnWinParams w{};
+            static_cast<AttnQkParams&>(w) = q;
+            w.scale = 1.0f;                                        // (not read by the window instances)
+            w.bias = win->bias; w.mask = win->mask; w.n_windows = win->n_windows;
+            return twin ? enqueue(c, KERN1_T(AttnWinParams, k_attn_qk, true, true), grid, block, lds, w, &si)
+                        : enqueue(c, KERN1_T(AttnWinParams, k_attn_qk, false, true), grid, block, lds, w, &si);
+        }
         return twin ? enqueue(c, KERN1_T(AttnQkParams, k_attn_qk, true), grid, block, lds, q, &si)
                     : enqueue(c, KERN1_T(AttnQkParams, k_attn_qk, false), grid, block, lds, q, &si);
     }));
     return ch.consume();
 }
+int attn_impl(const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulTensors& t2, Ctx& c) { return attn_chain(d, t1, t2, c, nullptr); }
+// the window call as fused_sizing_run / fused_call take it: the p4v_attn_desc of its two MatMuls and the window record
+struct WattnCall { p4v_attn_desc a; AttnWindow w; };
+int wattn_impl(const WattnCall* d, const MatMulTensors& t1, const MatMulTensors& t2, Ctx& c) { return attn_chain(&d->a, t1, t2, c, &d->w); }
 
 // ---- MatMul with row / column sub-blocks (n_V, n_H > 1; reference matmul.py:109-138, 419-440, 483-563) -------------------------
 // Intervals are [heads][n_V][n_H] (the reference's (1, n_G = heads, 1, n_V, 1, n_H, 1)).  The search is the reference's greedy
@@ -3899,6 +3923,34 @@ int p4v_attn_quant_forward(const p4v_attn_desc* desc, const float* d_q, const fl
                       {.A = d_q, .B = d_kT, .A_iv = const_cast<float*>(d_qk_A_interval), .B_iv = const_cast<float*>(d_qk_B_interval), .fwd_out = d_probs},
                       {.B = d_v, .A_iv = const_cast<float*>(d_pv_A_interval), .B_iv = const_cast<float*>(d_pv_B_interval),
                        .split = const_cast<float*>(d_split), .fwd_out = d_out}, d_ws, ws_bytes, stream);
+}
+
+static WattnCall wattn_call(const p4v_wattn_desc* desc, const p4v_wattn_tensors* t) {
+    WattnCall w{};
+    w.a.qk = desc->qk; w.a.pv = desc->pv; w.a.scale = 1.0f;
+    w.w = AttnWindow{t ? t->bias : nullptr, t ? t->mask : nullptr, desc->n_windows};
+    return w;
+}
+size_t p4v_wattn_workspace_bytes(const p4v_wattn_desc* desc) {
+    if (!desc) return 0;
+    const WattnCall w = wattn_call(desc, nullptr);
+    size_t need = 0;
+    return fused_sizing_run(wattn_impl, &w, &need) == 0 ? need : 0;
+}
+
+int p4v_wattn_quant_forward(const p4v_wattn_desc* desc, const p4v_wattn_tensors* t, void* stream) {
+    if (!desc || !t || !t->q || !t->kT || !t->v || !t->bias || !t->qk_A_interval || !t->qk_B_interval || !t->pv_A_interval || !t->pv_B_interval ||
+        !t->out || !t->ws)
+        return fail(P4V_ERR_INVALID, "p4v_wattn_quant_forward: null pointer");
+    if (desc->pv.sos && !t->split) return fail(P4V_ERR_INVALID, "p4v_wattn_quant_forward: sos needs split");
+    if ((desc->has_mask != 0) != (t->mask != nullptr))
+        return fail(P4V_ERR_INVALID, "p4v_wattn_quant_forward: has_mask = %d but the mask pointer is %s", desc->has_mask, t->mask ? "set" : "null");
+    CHK(ws_aligned(t->ws));
+    const WattnCall w = wattn_call(desc, t);
+    return fused_call(wattn_impl, &w,
+                      {.A = t->q, .B = t->kT, .A_iv = const_cast<float*>(t->qk_A_interval), .B_iv = const_cast<float*>(t->qk_B_interval), .fwd_out = t->probs},
+                      {.B = t->v, .A_iv = const_cast<float*>(t->pv_A_interval), .B_iv = const_cast<float*>(t->pv_B_interval),
+                       .split = const_cast<float*>(t->split), .fwd_out = t->out}, t->ws, t->ws_bytes, stream);
 }
 
 int p4v_matmul_quant_forward(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_A_interval,
@@ -4354,7 +4406,7 @@ static int planes_out(const FusedPlanes& m, uint64_t* out, const char* who, cons
     return m.rows > 0 ? 0 : fail(P4V_ERR_INVALID, "%s: no %s call on this thread yet", who, call);
 }
 int p4v_debug_mlp_planes(uint64_t* out) { return planes_out(g_mlp_planes, out, "p4v_debug_mlp_planes", "p4v_mlp_quant_forward"); }
-int p4v_debug_attn_planes(uint64_t* out) { return planes_out(g_attn_planes, out, "p4v_debug_attn_planes", "p4v_attn_quant_forward"); }
+int p4v_debug_attn_planes(uint64_t* out) { return planes_out(g_attn_planes, out, "p4v_debug_attn_planes", "p4v_attn_quant_forward / p4v_wattn_quant_forward"); }
 
 int p4v_debug_sos_sweep(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_out, const float* d_grad,
                         int n_cands, int c_lo, int c_hi, int known_cands, float* d_scores, void* d_workspace, size_t workspace_bytes,

@@ -5144,9 +5144,25 @@ struct AttnQkParams {
     int mtiles, nwg;                          // 128-query tiles per z; workgroups
 };
 static constexpr int ATTN_OROW = 80;          // LDS row of a wave's output tile: 64 bytes + 16 bytes pad
+static constexpr int ATTN_WCH = 4;            // window instances: bias / mask values in flight at once (a register quad: 4 consecutive keys)
+static_assert(ATTN_WCH == 4, "the 16-byte path of the window instances loads one register quad");
+// The window instances (WIN; p4v_wattn_quant_forward, Swin's WindowAttention): q arrives scaled, so there is no `* scale`; the
+// relative-position bias [H][M][N] and the optional shift mask [n_windows][M][N] (window = (z / H) % n_windows: z / H is
+// image * n_windows + window) are two separate fp32 additions, in the module's order:
+//   u = t + bias[head][m][n];   if (mask) u = u + mask[window][m][n]          (each rounded to fp32: no fma, no pre-added table)
+// Both are read by the lane that owns the score, in each of the three walks, for m < M and n < N only: a register quad is four
+// consecutive floats of one row -- one 16-byte load where N is a multiple of 4 and the tensors are 16-byte aligned (144 keys),
+// four dword loads otherwise (rows are N floats apart: no alignment at 49 keys); the lane pair of a query reads 32 contiguous
+// bytes per quad and 128 per tile.  The bias of a head is shared by every image and window, the
+// mask of a window by every image and head: both stay in L2.  A -inf mask entry gives expf(-inf) = 0; a row of nothing but -inf
+// has the maximum -inf and -inf - -inf = NaN everywhere, as in torch.
+struct AttnWinParams : AttnQkParams {
+    const float* bias; const float* mask;     // [H][M][N]; [n_windows][M][N] or null
+    int n_windows;
+};
 
-template <bool TWIN>
-__device__ __forceinline__ void k_attn_qk_body(const AttnQkParams& p, const uint3 blockIdx, const uint3 gridDim) {
+template <bool TWIN, bool WIN, class Params>
+__device__ __forceinline__ void k_attn_qk_body(const Params& p, const uint3 blockIdx, const uint3 gridDim) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int g = lane >> 5, l31 = lane & 31;
@@ -5166,6 +5182,18 @@ __device__ __forceinline__ void k_attn_qk_body(const AttnQkParams& p, const uint
 
     const float s1 = p.S1[head];
     const float scale = p.scale;
+    // WIN: where this query's row of the bias and of the mask begins, in floats (padding rows: the last row's; 32 bits: the host
+    // holds both tensors below 2^30 elements, so a load is the tensor's uniform base + one offset register)
+    [[maybe_unused]] unsigned rowB = 0, rowM = 0;
+    [[maybe_unused]] bool masked = false, vec4 = false;
+    if constexpr (WIN) {
+        const int mc = min(m, p.M - 1);
+        rowB = (unsigned)((head * p.M + mc) * p.N);
+        masked = p.mask != nullptr;
+        // a register quad (4 consecutive keys from a multiple of 4) is one aligned 16-byte load when the rows are (N = 144: window 12)
+        vec4 = (p.N & 3) == 0 && (((unsigned long long)p.bias | (unsigned long long)p.mask) & 15) == 0;
+        rowM = (unsigned)((((z / p.H) % p.n_windows) * p.M + mc) * p.N);
+    }
     // u of the 32 x 32 tile at keys [key0, key0 + 32)
     auto scores = [&](int key0, float (&u)[16]) {
         v16i acc;
@@ -5183,8 +5211,45 @@ __device__ __forceinline__ void k_attn_qk_body(const AttnQkParams& p, const uint
                 acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, acc, 0, 0, 0);
             }
         }
+        if constexpr (WIN) {
+            // torch adds the bias to the STORED fp32 product and the mask to the stored sum: three roundings, no fma.  (Written
+            // with the operators under contract(off): __fmul_rn / __fadd_rn are the header's `x * y` / `x + y` and contract.)
+            // The bias and mask values come ATTN_WCH scores at a time, each quad's loads behind the previous quad's additions
+            // (the empty asm chains them): 80 VGPRs, 6 waves per SIMD; all 16 + 16 in flight at once take 112 VGPRs, 4 waves.
+            // A key or query of the padding reads the last valid one's (clamped, branch-free: its u is never used).
+#pragma clang fp contract(off)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) u[r] = __fmul_rn(__fmul_rn((float)acc[r], s1), scale);
+            for (int r = 0; r < 16; ++r) u[r] = (float)acc[r] * s1;
+            int nb = key0 + 4 * g;                         // the lane's first key of the tile
+#pragma unroll
+            for (int c = 0; c < 16; c += ATTN_WCH) {
+                float bq[ATTN_WCH], mq[ATTN_WCH];
+                if (vec4) {                                // (uniform) the quad is one 16-byte piece, all of it inside the row or none
+                    const unsigned o = (unsigned)min(nb + acc32_row(c), p.N - 4);
+                    const v4f b4 = *reinterpret_cast<const v4f*>(p.bias + rowB + o);
+                    v4f m4 = {0.0f, 0.0f, 0.0f, 0.0f};
+                    if (masked) m4 = *reinterpret_cast<const v4f*>(p.mask + rowM + o);
+#pragma unroll
+                    for (int j = 0; j < ATTN_WCH; ++j) { bq[j] = b4[j]; mq[j] = m4[j]; }
+                } else {
+#pragma unroll
+                    for (int j = 0; j < ATTN_WCH; ++j) {
+                        const unsigned o = (unsigned)min(nb + acc32_row(c + j), p.N - 1);
+                        bq[j] = p.bias[rowB + o];
+                        mq[j] = masked ? p.mask[rowM + o] : 0.0f;
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < ATTN_WCH; ++j) {
+                    u[c + j] = u[c + j] + bq[j];
+                    if (masked) u[c + j] = u[c + j] + mq[j];
+                    asm volatile("" : "+v"(nb), "+v"(u[c + j]));   // (the next chunk's loads stay behind this chunk's additions)
+                }
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) u[r] = __fmul_rn(__fmul_rn((float)acc[r], s1), scale);
+        }
     };
 
     const int ntiles = wave_live ? (p.N + 31) / 32 : 0;
@@ -5273,7 +5338,9 @@ __device__ __forceinline__ void k_attn_qk_body(const AttnQkParams& p, const uint
         __syncthreads();
     }
 }
-template <bool TWIN>
-__global__ __launch_bounds__(256) void k_attn_qk(AttnQkParams p) { k_attn_qk_body<TWIN>(p, P4V_BIDX, P4V_GDIM); }
+template <bool TWIN, bool WIN = false>
+__global__ __launch_bounds__(256) void k_attn_qk(std::conditional_t<WIN, AttnWinParams, AttnQkParams> p) {
+    k_attn_qk_body<TWIN, WIN>(p, P4V_BIDX, P4V_GDIM);
+}
 
 }  // namespace p4v

@@ -244,17 +244,23 @@ def _mlp_layer_desc(batch, tokens, layer):
 
 
 def _fused_forward(kind, d, tensors, dev, res, want_planes, z=None):
-    """The tail of the fused forwards (`kind`: mlp / attn): p4v_<kind>_workspace_bytes, the workspace, the checked call
-    p4v_<kind>_quant_forward(d, *tensors, workspace, its size, stream).  Returns the tuple `res` -- its one member alone --, with
-    `want_planes` followed by the int8 plane(s) p4v_debug_<kind>_planes locates in the workspace: [rows][cols] each, or `z`
-    of [rows / z][cols]."""
+    """The tail of the fused forwards (`kind`: mlp / attn / wattn): p4v_<kind>_workspace_bytes, the workspace, the checked call
+    p4v_<kind>_quant_forward(d, *tensors, workspace, its size, stream) -- wattn: `tensors` maps the members of its
+    p4v_wattn_tensors record, in which the workspace and its size travel too.  Returns the tuple `res` -- its one member alone --,
+    with `want_planes` followed by the int8 plane(s) p4v_debug_<kind>_planes (wattn: attn's) locates in the workspace:
+    [rows][cols] each, or `z` of [rows / z][cols]."""
     lib = _lib.load()
     ws = workspace(dev, _need(getattr(lib, f"p4v_{kind}_workspace_bytes"), d, f"p4v_{kind}_workspace_bytes"))
     with torch.cuda.device(dev):
-        rc = getattr(lib, f"p4v_{kind}_quant_forward")(C.byref(d), *[ptr(t) for t in tensors], ptr(ws), ws.numel(), stream_ptr(dev))
+        if kind == "wattn":
+            rec = _lib.WattnTensors(**{n: ptr(t) for n, t in tensors.items()}, ws=ptr(ws), ws_bytes=ws.numel())
+            rc = lib.p4v_wattn_quant_forward(C.byref(d), C.byref(rec), stream_ptr(dev))
+        else:
+            rc = getattr(lib, f"p4v_{kind}_quant_forward")(C.byref(d), *[ptr(t) for t in tensors], ptr(ws), ws.numel(), stream_ptr(dev))
     _lib.check(rc, f"p4v_{kind}_quant_forward")
     if want_planes:
         info = (C.c_uint64 * 5)()
+        kind = "attn" if kind == "wattn" else kind
         _lib.check(getattr(lib, f"p4v_debug_{kind}_planes")(info), f"p4v_debug_{kind}_planes")
         off1, off2, rows, cols, twin = (int(v) for v in info)
         shape = (rows, cols) if z is None else (z, rows // z, cols)
@@ -287,16 +293,38 @@ def mlp_quant_forward(*, x, fc1, fc2, want_hidden=False, want_planes=False):
                           (out, hidden) if want_hidden else (out,), want_planes)
 
 
-def _attn_matmul_desc(d, A_shape, A_stride, B, side, what):
-    """One p4v_matmul_desc of a p4v_attn_desc; `side`: the dict engine.attn_quant_forward takes per MatMul."""
+def _attn_matmul_desc(d, A_shape, A_stride, B, side, what, who="attn_quant_forward"):
+    """One p4v_matmul_desc of a p4v_attn_desc / p4v_wattn_desc; `side`: the dict engine.attn_quant_forward takes per MatMul."""
     if has_blocks(side.get("blocks")):
-        raise NotImplementedError(f"attn_quant_forward: {what} has row / column sub-blocks (the fused forward is head-wise)")
+        raise NotImplementedError(f"{who}: {what} has row / column sub-blocks (the fused forward is head-wise)")
     d.batch, d.heads, d.M, d.K, d.N = A_shape[0], A_shape[1], A_shape[2], A_shape[3], B.shape[3]
     for i in range(4):
         d.a_stride[i] = A_stride[i]
         d.b_stride[i] = B.stride(i)
     d.A_bit, d.B_bit, d.metric, d.eq_n, d.search_round = side["A_bit"], side["B_bit"], metric_id("L2_norm"), 1, 1
     d.sos, d.init_layerwise, d.reserved = int(bool(side.get("sos", False))), 0, _lib.RESERVED_FORWARD_ONLY
+
+
+def _attn_call(who, q, kT, v, qk, pv, want_probs, desc):
+    """What attn_quant_forward and window_attn_quant_forward share: the operands on the device, the two p4v_matmul_desc of
+    `desc`, the checked interval tensors, the outputs.  Returns (dev, q, kT, v, (qk_A, qk_B, pv_A, pv_B, split), out, probs)."""
+    dev = device_of(q, kT, v)
+    q, kT, v = to_dev(q, dev), to_dev(kT, dev), to_dev(v, dev)
+    b, H, M, _ = q.shape
+    N, Dv = kT.shape[3], v.shape[3]
+    if qk.get("sos", False):
+        raise NotImplementedError(f"{who}: q k^T is no split-of-softmax operand (sos belongs on p v)")
+    _attn_matmul_desc(desc.qk, q.shape, q.stride(), kT, qk, "q k^T", who)
+    _attn_matmul_desc(desc.pv, (b, H, M, v.shape[2]), (H * M * v.shape[2], M * v.shape[2], v.shape[2], 1), v, pv, "p v", who)
+    sos = bool(pv.get("sos", False))
+    flat = lambda t: to_dev(t, dev).reshape(-1).contiguous()
+    qk_A, qk_B, pv_A, pv_B = flat(qk["A_interval"]), flat(qk["B_interval"]), flat(pv["A_interval"]), flat(pv["B_interval"])
+    if qk_A.numel() != H or qk_B.numel() != H or pv_B.numel() != H or pv_A.numel() != (1 if sos else H):
+        raise ValueError(f"{who}: interval tensors must hold one value per head (the split-of-softmax A: one)")
+    sp = flat(pv["split"]) if sos else None
+    out = torch.empty(b, H, M, Dv, dtype=torch.float32, device=dev)
+    probs = torch.empty(b, H, M, N, dtype=torch.float32, device=dev) if want_probs else None
+    return dev, q, kT, v, (qk_A, qk_B, pv_A, pv_B, sp), out, probs
 
 
 def attn_quant_forward(*, q, kT, v, scale, qk, pv, want_probs=False, want_planes=False):
@@ -309,26 +337,35 @@ def attn_quant_forward(*, q, kT, v, scale, qk, pv, want_probs=False, want_planes
     `want_probs` -- the fp32 probabilities the planes were quantised from --, with `want_planes` also the padded int8
     plane(s) as the call left them in its workspace (a tuple of one or two [B*H][rows_padded][cols_padded] tensors; for the
     tests)."""
-    dev = device_of(q, kT, v)
-    q, kT, v = to_dev(q, dev), to_dev(kT, dev), to_dev(v, dev)
-    b, H, M, _ = q.shape
-    N, Dv = kT.shape[3], v.shape[3]
-    if qk.get("sos", False):
-        raise NotImplementedError("attn_quant_forward: q k^T is no split-of-softmax operand (sos belongs on p v)")
     d = _lib.AttnDesc()
-    _attn_matmul_desc(d.qk, q.shape, q.stride(), kT, qk, "q k^T")
-    _attn_matmul_desc(d.pv, (b, H, M, v.shape[2]), (H * M * v.shape[2], M * v.shape[2], v.shape[2], 1), v, pv, "p v")
+    dev, q, kT, v, (qk_A, qk_B, pv_A, pv_B, sp), out, probs = _attn_call("attn_quant_forward", q, kT, v, qk, pv, want_probs, d)
     d.scale, d.reserved = float(scale), 0
-    sos = bool(pv.get("sos", False))
-    flat = lambda t: to_dev(t, dev).reshape(-1).contiguous()
-    qk_A, qk_B, pv_A, pv_B = flat(qk["A_interval"]), flat(qk["B_interval"]), flat(pv["A_interval"]), flat(pv["B_interval"])
-    if qk_A.numel() != H or qk_B.numel() != H or pv_B.numel() != H or pv_A.numel() != (1 if sos else H):
-        raise ValueError("attn_quant_forward: interval tensors must hold one value per head (the split-of-softmax A: one)")
-    sp = flat(pv["split"]) if sos else None
-    out = torch.empty(b, H, M, Dv, dtype=torch.float32, device=dev)
-    probs = torch.empty(b, H, M, N, dtype=torch.float32, device=dev) if want_probs else None
     return _fused_forward("attn", d, (q, kT, v, qk_A, qk_B, pv_A, pv_B, sp, out, probs), dev, (out, probs) if want_probs else (out,),
-                          want_planes, z=b * H)
+                          want_planes, z=q.shape[0] * q.shape[1])
+
+
+def window_attn_quant_forward(*, q, kT, v, bias, mask=None, qk, pv, want_probs=False, want_planes=False):
+    """matmul2(softmax(matmul1(q, kT) + bias (+ mask), -1), v) of the two calibrated MatMuls of a window attention block
+    (models.WindowAttention) in quant_forward, fused (p4v_wattn_quant_forward): attn_quant_forward's chain with the window
+    arithmetic between matmul1 and the softmax.  `q` arrives ALREADY SCALED, as the module hands it to matmul1.
+    q [B_][H][N][D], kT [B_][H][D][N], v [B_][H][N][Dv] (B_ = images * windows, windows innermost; views are not copied); bias
+    [H][N][N]; mask None or [nW][N][N] with B_ % nW == 0, added to window (b_ % nW) of every image and head; -inf entries
+    behave as in torch.  Checks, `qk` / `pv`, want_probs, want_planes and the returned values: as attn_quant_forward."""
+    d = _lib.WattnDesc()
+    dev, q, kT, v, (qk_A, qk_B, pv_A, pv_B, sp), out, probs = _attn_call("window_attn_quant_forward", q, kT, v, qk, pv, want_probs, d)
+    b, H, M, _ = q.shape
+    N = kT.shape[3]
+    bias = to_dev(bias, dev).contiguous()
+    if tuple(bias.shape) != (H, M, N):
+        raise ValueError(f"window_attn_quant_forward: bias {tuple(bias.shape)} is not [heads][M][N] = {(H, M, N)}")
+    if mask is not None:
+        mask = to_dev(mask, dev).contiguous()
+        if mask.dim() != 3 or tuple(mask.shape[1:]) != (M, N):
+            raise ValueError(f"window_attn_quant_forward: mask {tuple(mask.shape)} is not [windows][M][N] = [*]{(M, N)}")
+    d.n_windows, d.has_mask = (1 if mask is None else mask.shape[0]), int(mask is not None)
+    tensors = dict(q=q, kT=kT, v=v, bias=bias, mask=mask, qk_A_interval=qk_A, qk_B_interval=qk_B, pv_A_interval=pv_A, pv_B_interval=pv_B,
+                   split=sp, out=out, probs=probs)
+    return _fused_forward("wattn", d, tensors, dev, (out, probs) if want_probs else (out,), want_planes, z=b * H)
 
 
 def matmul_quant_forward(*, A, B, A_interval, B_interval, split, A_bit, B_bit, sos=False):

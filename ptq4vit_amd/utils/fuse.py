@@ -14,6 +14,13 @@ exactly as on an unfused net.  Nothing calls `fuse_mlp` by default; `unfuse_mlp(
 patched forward of a `models.Attention` repeats its forward -- the same qkv call, the same P4V_QKV_CONTIGUOUS branch, the same proj
 -- and replaces matmul1 -> `* scale` -> softmax -> matmul2 by engine.attn_quant_forward (p4v_attn_quant_forward)
 when both MatMuls are calibrated, in quant_forward, head-wise, on the int8 path and unhooked; otherwise the original forward.
+
+`fuse_window_attention(net)` / `unfuse_window_attention(net)` / `takes_fused_window_attention_path(m, x, mask=None)` are the
+same for Swin's `models.WindowAttention`, which fuse_attention leaves alone: the patched forward(x, mask=None) repeats the
+module's -- qkv, `q * self.scale` in torch (matmul1 was calibrated on the scaled q), the bias gather / permute / contiguous, proj
+-- and replaces matmul1 -> `+ bias` -> `+ mask` -> softmax -> matmul2 by engine.window_attn_quant_forward
+(p4v_wattn_quant_forward) under fuse_attention's per-call conditions and one more: the mask is None or a
+float32 [nW][N][N] tensor with B_ % nW == 0.  Each of the three fuse_* keeps its own saved forward: they compose in any order.
 """
 import os
 import types
@@ -58,6 +65,7 @@ def _recording(x, *modules):
 # points take LESS than the single ones (include/ptq4vit_hip.h):
 #   p4v_mlp_quant_forward    n_H = n_a = 1 on both layers, fc1 no post-GELU layer
 #   p4v_attn_quant_forward   no row / column sub-blocks, matmul1 no split-of-softmax operand; a float32 [B][N][C] input
+#   p4v_wattn_quant_forward  the same; the mask None or float32 [nW][N][N], B_ % nW == 0
 # (_layer / _matmul_side: the names under which the tests fetch those keywords for a direct engine call)
 _layer, _matmul_side = (lambda fc: fc._int8_args()), (lambda mm, H: mm._int8_args(H))
 
@@ -130,7 +138,8 @@ def unfuse_mlp(net):
 # ---- the attention side: matmul1 -> * scale -> softmax -> matmul2 (engine.attn_quant_forward) ----------------------
 # Same shape as the MLP functions, with a saved-forward attribute of its own: an Attention is no MLP container, so fuse_mlp and
 # fuse_attention patch different modules and compose in any order.  WindowAttention (Swin) scales q BEFORE matmul1 and adds a
-# position bias and a mask before the softmax: not this kernel's arithmetic, fuse_attention skips it.
+# position bias and a mask before the softmax: not that kernel instance's arithmetic, fuse_attention skips it (it has
+# fuse_window_attention, below).
 _ORIG_ATTN = "_p4v_unfused_attn_forward"
 
 
@@ -144,9 +153,9 @@ def attention_fusable(m):
             and _inactive_dropout(m.attn_drop))
 
 
-def _attn_args(m, x):
+def _attn_args(m, x, static=attention_fusable):
     """(matmul1's, matmul2's engine keywords) if the patched forward of `m` runs the fused chain on `x`, else None."""
-    if not (attention_fusable(m) and torch.is_tensor(x) and x.dim() == 3 and x.dtype == torch.float32):
+    if not (static(m) and torch.is_tensor(x) and x.dim() == 3 and x.dtype == torch.float32):
         return None
     m1, m2 = m.matmul1, m.matmul2
     if not (_live(m1) and _live(m2)) or _hooked(m.attn_drop) or _recording(x, m.qkv):
@@ -190,3 +199,58 @@ def fuse_attention(net):
 def unfuse_attention(net):
     """Undo fuse_attention: every patched container gets its original forward back; returns their names.  Idempotent."""
     return _unfuse(net, _ORIG_ATTN)
+
+
+# ---- window attention (Swin): matmul1 -> + bias -> + mask -> softmax -> matmul2 (engine.window_attn_quant_forward, DESIGN.md s5.10) ----
+_ORIG_WATTN = "_p4v_unfused_wattn_forward"
+
+
+def window_attention_fusable(m):
+    """The static half of the decision: a WindowAttention container whose forward `fuse_window_attention` patches."""
+    return (isinstance(m, models.WindowAttention) and isinstance(m.matmul1, PTQSLQuantMatMul) and isinstance(m.matmul2, PTQSLQuantMatMul)
+            and _inactive_dropout(m.attn_drop))
+
+
+def _wattn_args(m, x, mask):
+    """_attn_args for a WindowAttention, with the condition on the mask: None, or float32 [nW][N][N] where x lies, B_ % nW == 0."""
+    args = _attn_args(m, x, window_attention_fusable)
+    if args is None or _hooked(m.softmax) or (torch.is_grad_enabled() and m.relative_position_bias_table.requires_grad):
+        return None
+    if mask is not None:
+        N = x.shape[1]
+        if not (torch.is_tensor(mask) and mask.dtype == torch.float32 and mask.device == x.device and not mask.requires_grad
+                and mask.dim() == 3 and tuple(mask.shape[1:]) == (N, N) and mask.shape[0] >= 1 and x.shape[0] % mask.shape[0] == 0):
+            return None
+    return args
+
+
+def takes_fused_window_attention_path(m, x, mask=None):
+    """The per-call half: would the patched forward of `m` run the fused kernel chain on `x` (and `mask`)?"""
+    return _wattn_args(m, x, mask) is not None
+
+
+def _fused_window_attention_forward(self, x, mask=None):
+    args = _wattn_args(self, x, mask)
+    if args is None:
+        return self.__dict__[_ORIG_WATTN](x, mask)
+    # models.WindowAttention.forward, with matmul1 ... matmul2 as one engine call
+    B_, N, C = x.shape
+    H = self.num_heads
+    qkv = self.qkv(x).reshape(B_, N, 3, H, C // H).permute(2, 0, 3, 1, 4)
+    q, k, v = qkv.unbind(0)
+    q = q * self.scale
+    n = self.window_size[0] * self.window_size[1]
+    bias = self.relative_position_bias_table[self.relative_position_index.view(-1)].view(n, n, -1)
+    out = engine.window_attn_quant_forward(q=q, kT=k.transpose(-2, -1), v=v, bias=bias.permute(2, 0, 1).contiguous(), mask=mask,
+                                           qk=args[0], pv=args[1])
+    return self.proj_drop(self.proj(out.transpose(1, 2).reshape(B_, N, C)))
+
+
+def fuse_window_attention(net):
+    """Patch the forward of every fusable WindowAttention container of `net`; returns their names.  Idempotent."""
+    return _patch(net, window_attention_fusable, _ORIG_WATTN, _fused_window_attention_forward)
+
+
+def unfuse_window_attention(net):
+    """Undo fuse_window_attention: every patched container gets its original forward back; returns their names.  Idempotent."""
+    return _unfuse(net, _ORIG_WATTN)

@@ -9,7 +9,9 @@ reference, example/test_vit.py:26-45) next to the raw fp32 forward.
 medians over --reps repetitions each, and the per-kernel device time of one forward of each kind: the engine's launch records
 for the GEMMs (k_mlp_fc1, the fc2 sweep), torch's profiler for everything (k_pack*, torch's GELU).
 --fused-attn: a further variant in the same alternation, the attention blocks fused (fuse_attention: k_attn_qk in place of
-matmul1's sweep, torch's `* scale` and softmax and k_pack_dual); with --fused it is MLPs + attention, without it attention alone.
+matmul1's sweep, torch's `* scale` and softmax and k_pack_dual; on a Swin net fuse_window_attention: the window instances of
+k_attn_qk in place of matmul1's sweep, torch's `+ bias`, `+ mask` and softmax and k_pack_dual); with --fused it is MLPs +
+attention, without it attention alone.
 """
 import argparse
 import hashlib
@@ -91,7 +93,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--fused", action="store_true", help="also time the network with fused MLPs (utils/fuse.py), alternating")
     ap.add_argument("--fused-attn", action="store_true",
-                    help="also time the network with fused attention (utils/fuse.py::fuse_attention; with --fused: on top of the fused MLPs)")
+                    help="also time the network with fused attention (utils/fuse.py::fuse_attention and fuse_window_attention; with --fused: on top of the fused MLPs)")
     ap.add_argument("--json", default=None, help="write the result to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -139,7 +141,8 @@ def main():
         def setup(mlp, attn):
             fuse.unfuse_mlp(net)
             fuse.unfuse_attention(net)
-            return (len(fuse.fuse_mlp(net)) if mlp else 0, len(fuse.fuse_attention(net)) if attn else 0)
+            fuse.unfuse_window_attention(net)
+            return (len(fuse.fuse_mlp(net)) if mlp else 0, len(fuse.fuse_attention(net)) + len(fuse.fuse_window_attention(net)) if attn else 0)
 
         ts = {key: [] for key, _, _ in variants}
         ys, counts = {}, {}

@@ -89,8 +89,8 @@ def evaluate(model, imagenet, weights=None, config="PTQ4ViT", bits=8, calib=32, 
         fused = _fuse(net)
     fused_attn = []
     if fuse_attn:                              # opt-in: matmul1 ... matmul2 of every attention block as the fused int8 chain
-        from ptq4vit_amd.utils.fuse import fuse_attention as _fuse_attn
-        fused_attn = _fuse_attn(net)
+        from ptq4vit_amd.utils.fuse import fuse_attention as _fuse_attn, fuse_window_attention as _fuse_wattn
+        fused_attn = _fuse_attn(net) + _fuse_wattn(net)        # (a net has Attention or WindowAttention blocks)
     t0 = time.time()
     quant = datasets.test_classification(net, test_loader, max_iteration=max_it, description=None if quiet else f"{model} W{bits}A{bits}")
     t_q = time.time() - t0
@@ -117,7 +117,7 @@ def main(argv=None):
     ap.add_argument("--save-intervals", default=None, help="write the calibrated intervals (utils/intervals.py) to this file")
     ap.add_argument("--json", default=None, help="also write the result line to this file")
     ap.add_argument("--fuse-mlp", action="store_true", help="evaluate with the fused int8 MLP forward (utils/fuse.py::fuse_mlp)")
-    ap.add_argument("--fuse-attn", action="store_true", help="evaluate with the fused int8 attention forward (utils/fuse.py::fuse_attention)")
+    ap.add_argument("--fuse-attn", action="store_true", help="evaluate with the fused int8 attention forward (utils/fuse.py::fuse_attention, fuse_window_attention)")
     a = ap.parse_args(argv)
     import ptq4vit_amd
     ptq4vit_amd.configure_runtime()          # GPU_MAX_HW_QUEUES for the search streams, before the first GPU call
