@@ -10,9 +10,15 @@ reference experiment uses.  Differences in HOW (not WHAT):
 * ``module.calibration_step2()`` runs on the GPU through the C ABI;
 * with ``torch.distributed`` initialised the modules are sharded over the ranks (one process per GPU) and the
   calibrated intervals are exchanged with one all-gather at the end (ptq4vit_amd/utils/shard.py).
+
+The knobs of a calibration are decided once, in `calib_options` (attribute on the calibrator, then environment variable, then
+default); the capture passes served from HIP graphs live in utils/capture_graph.py.
 """
 import os
-import sys
+import threading
+import time
+from collections import namedtuple
+from dataclasses import dataclass
 
 import torch
 import torch.nn.functional as F
@@ -20,7 +26,8 @@ import torch.nn.functional as F
 from ..quant_layers.conv import MinMaxQuantConv2d
 from ..quant_layers.linear import MinMaxQuantLinear
 from ..quant_layers.matmul import MinMaxQuantMatMul
-from . import shard
+from . import capture_graph, shard
+from .capture_graph import _cache_like, _same_dense_block, forget_caches  # noqa: F401 - the first two are re-exported
 
 try:
     from tqdm import tqdm
@@ -44,6 +51,56 @@ def _warn_hw_queues(n_streams):
     import warnings
     warnings.warn(f"ptq4vit_amd: {n_streams} search streams but GPU_MAX_HW_QUEUES is unset (runtime default: 4 hardware queues); "
                   "call ptq4vit_amd.configure_runtime() before the first GPU use, or export GPU_MAX_HW_QUEUES=8", stacklevel=3)
+
+
+@dataclass(frozen=True)
+class CalibOptions:
+    """The knobs of one calibration, decided once (`calib_options`).  DESIGN.md §6 has the table of name, attribute, environment
+    variable and default."""
+    use_graph: object        # True / False force the capture graph on / off, None: capture_graph.graph_wanted decides
+    capture_lanes: int       # instances of the capture graph replayed side by side
+    search_streams: int      # modules searched at a time; 1 also selects ONE group call
+    search_grouped: object   # p4v_calibrate_group calls instead of one calibration_step2 per module
+    group_calls: int         # concurrent group calls; <= 0: one for a small calibration, else three (`n_group_calls`)
+    shard_capture: object    # True = sub-batch sharded capture, False = replicated, None = shard.choose_capture_mode
+    arch_graphs: bool        # a fresh network replays the graph of its architecture
+    group_gib: float         # scratch of all concurrent group calls together, GiB at most
+    capture_trace: bool      # phase times of the graph capture and the place of an out-of-memory error on stderr / stdout
+
+    def n_group_calls(self, cache_bytes):
+        """`cache_bytes()` -> bytes of the group's captured tensors, asked only for the automatic choice: three concurrent calls
+        overlap each other's small kernels and round trips (ViT-B/224 x 32: 127 ms with one call, 112 with three; ViT-S x 32:
+        68.7 / 62.7; DeiT-tiny x 32: 44.3 / 41.2); a calibration whose captured tensors are a few hundred MB is issue-bound and
+        pays for every extra round instead (DeiT-tiny BasePTQ x 4, BASELINE config 0: 5 rounds / 27.7 ms with one call,
+        15 rounds / 29.4 ms with three)."""
+        if self.search_streams == 1:     # (the launch order bench.py's roofline records describe)
+            return 1
+        if self.group_calls > 0:
+            return self.group_calls
+        return 1 if cache_bytes() < (512 << 20) else 3
+
+
+def calib_options(cal):
+    """Every knob from (attribute on the calibrator, then environment variable, then default).  The attributes are None after
+    construction and may be set at any time before the calibration; `capture_lanes`, `search_streams` and `group_calls` fall
+    through to the environment when None or 0."""
+    env = os.environ.get
+    shard_env = env("P4V_SHARD_CAPTURE", "auto")      # "1" / "0" force, anything else is auto
+    return CalibOptions(
+        use_graph=cal.use_graph,
+        capture_lanes=int(cal.capture_lanes or env("P4V_CAPTURE_LANES", "3")),
+        search_streams=cal.search_streams or int(env("P4V_SEARCH_STREAMS", "4")),
+        search_grouped=cal.search_grouped if cal.search_grouped is not None else env("P4V_GROUPED", "1") != "0",
+        group_calls=cal.group_calls or int(env("P4V_GROUP_CALLS", "0")),
+        shard_capture=cal.shard_capture if cal.shard_capture is not None else {"1": True, "0": False}.get(shard_env),
+        arch_graphs=env("P4V_ARCH_GRAPHS", "1") != "0",
+        group_gib=float(env("P4V_GROUP_GIB", "150")),
+        capture_trace=env("P4V_CAPTURE_TRACE") == "1")
+
+
+# What is fixed for one `_calibrate` call.  `all_sizes`: {module: cache bytes} of EVERY module when the modules are sharded over
+# ranks, else None; `shard_cap`: sub-batch sharded capture (every rank enters shard.exchange_captures).
+_Calibration = namedtuple("_Calibration", "opts batching with_grad rank world names owner all_sizes n_sub shard_cap raw_pred_softmax")
 
 
 def _dev_of(net):
@@ -117,39 +174,6 @@ def _concat(module, with_grad):
         module.raw_grad = cat(module.raw_grad)
 
 
-def _cache_like(t, n_sub):
-    """Cache for `n_sub` sub-batch pieces shaped like `t`, concatenated on dim 0 -- with t's memory layout when t is a dense
-    permutation whose batch dim is outermost in memory (e.g. the k.transpose(-2, -1) view the attention passes to matmul1):
-    sub-batch i is then ONE contiguous block of the cache, and the consumer reads the view in place as before."""
-    shape = (n_sub * t.shape[0],) + tuple(t.shape[1:])
-    if t.is_contiguous() or t.dim() < 2:
-        return torch.empty(shape, dtype=t.dtype, device=t.device)
-    order = sorted(range(t.dim()), key=lambda k: (-t.stride(k), k))           # outermost -> innermost in memory
-    dense, expect = order[0] == 0, 1
-    for k in reversed(order):
-        dense &= t.stride(k) == expect
-        expect *= t.shape[k]
-    if not dense:
-        return torch.empty(shape, dtype=t.dtype, device=t.device)
-    strides, acc = [0] * t.dim(), 1
-    for k in reversed(order):
-        strides[k] = acc
-        acc *= shape[k]
-    return torch.empty_strided(shape, strides, dtype=t.dtype, device=t.device)
-
-
-def _same_dense_block(cache, t):
-    """True when piece i of `cache` (rows [i*t.shape[0], (i+1)*t.shape[0])) and `t` are the same dense memory block layout,
-    i.e. a flat copy of t's storage block is the copy of the piece."""
-    if t.element_size() != 4 or cache.dtype != t.dtype:
-        return False
-    if tuple(cache.stride()[1:]) != tuple(t.stride()[1:]) or cache.stride(0) != t.stride(0):
-        return False
-    # dense: the block spans exactly numel elements
-    span = 1 + sum((t.shape[k] - 1) * t.stride(k) for k in range(t.dim()))
-    return span == t.numel() and t.stride(0) == max(t.stride())
-
-
 def _groupable(m):
     """May the calibrator replace this module's calibration_step2() by calibration_job() / p4v_calibrate_group / calibration_install()?
     Only while calibration_step2 IS the library's own method: an instance attribute or a subclass override (a user's hook around
@@ -157,6 +181,65 @@ def _groupable(m):
     if "calibration_step2" in m.__dict__ or not hasattr(m, "calibration_job"):
         return False
     return getattr(getattr(type(m), "calibration_step2", None), "_p4v_grouped", False)
+
+
+def _operands(m):
+    """The cached input(s) of a module as a list: two for a MatMul, one otherwise."""
+    ri = m.raw_input
+    return list(ri) if isinstance(ri, (list, tuple)) else [ri]
+
+
+def _calibrated_and_freed(m):
+    """Step 2 has run: the module carries `calibrated` and its caches are deleted (reference linear.py:554)."""
+    return hasattr(m, "calibrated") and not hasattr(m, "raw_out")
+
+
+def _prep_is_copy_free(m):
+    """Does preparing this module's group job launch no torch kernel on captured data (every cached tensor dense fp32 on the
+    device: no `.contiguous()` / `.to()` copy)?"""
+    dense = lambda t: t is None or (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous())
+    ins = _operands(m)
+    if len(ins) == 1 and not dense(ins[0]):          # (matmul operands are read through their strides)
+        return False
+    w = getattr(m, "weight", None)
+    return (all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in ins) and dense(m.raw_out)
+            and dense(getattr(m, "raw_grad", None)) and (w is None or dense(w.data)) and _groupable(m))
+
+
+def _search_work(m):
+    """Size of what a search sweeps (rows x K x N): the LPT order of a network that has no measured times yet."""
+    ins = _operands(m)
+    if len(ins) == 2:                                           # matmul: batch*heads x M x K x N
+        a, b = ins
+        return float(a.numel()) * b.shape[-1] * (0.2 if a.shape[-1] <= 64 else 1.0)
+    ri, w = ins[0], getattr(m, "weight", None)
+    return float(ri.numel()) / max(1, ri.shape[-1] if ri.dim() != 4 else 1) * (w.numel() if w is not None else 1) / (1 if ri.dim() != 4 else ri.shape[1])
+
+
+def plan_groups(todo, sizes, budget, sequential, shard_cap):
+    """Modules captured (and searched) together: greedily as many of `todo`, in order, as `sizes` fit into `budget` bytes -- a
+    module larger than the budget stands alone.  `sizes` is not read when `sequential` or `shard_cap`."""
+    if sequential:
+        return [[n] for n in todo]  # predecessors must already run quantised: one capture per module
+    if shard_cap:
+        return [todo]               # one exchange, then everything this rank owns (possibly nothing)
+    out, cur, acc = [], [], 0
+    for n in todo:
+        if cur and acc + sizes.get(n, 0) > budget:
+            out.append(cur)
+            cur, acc = [], 0
+        cur.append(n)
+        acc += sizes.get(n, 0)
+    if cur:
+        out.append(cur)
+    return out
+
+
+def deal_over_calls(names, kinds, n_calls):
+    """Modules of one kind (`kinds[name]`) are dealt over the group calls, so that every call holds the same mixture (and its
+    launches group); within a kind in the order of `names`."""
+    order = sorted(names, key=lambda n: (str(kinds[n]), names.index(n)))
+    return [order[i::n_calls] for i in range(n_calls)]
 
 
 class QuantCalibrator:
@@ -252,17 +335,15 @@ class HessianQuantCalibrator(QuantCalibrator):
         # workspaces and the capture pass itself (288 GB of HBM3E hold the 207 GB of Swin-B/384 x 128 images in ONE group;
         # every further group repeats the whole capture pass)
         self.cache_budget_bytes = cache_budget_bytes
+        # the knobs (`calib_options`): None = the environment variable, then the default; settable until the calibration starts
+        self.use_graph = self.capture_lanes = self.search_streams = None
+        self.search_grouped = self.group_calls = self.shard_capture = None
         self.timings = {}
 
     SEARCH_HEADROOM_BYTES = 44 << 30
 
-    def _resolve_budget(self, replay_is_cheap=False):
-        """Bytes of captured tensors resident at a time: what the GPU has free minus head room for the search workspaces.
-        `P4V_COLD_GROUP_GIB=<n>` additionally caps a group at n GiB while the memory would have to come fresh from the
-        driver and a capture pass is a cheap graph replay (`replay_is_cheap`).  Measured on MI355X (tools/alloc_probe.py,
-        P4V_CAPTURE_TRACE=1): the FIRST process that maps ~190 GiB on a freshly started box waits 3.5-5.5 s for it (Swin-B/384
-        x 128: 64 GiB groups bring that capture from 4.6-7.7 s to 2.6 s), every later process gets the same memory in
-        milliseconds and is better off with one resident group (1.0 s) -- hence off by default."""
+    def _resolve_budget(self):
+        """Bytes of captured tensors resident at a time: what the GPU has free minus head room for the search workspaces."""
         if self.cache_budget_bytes is not None:
             return int(self.cache_budget_bytes)
         dev = _dev_of(self.net)
@@ -278,11 +359,7 @@ class HessianQuantCalibrator(QuantCalibrator):
             engine.release_workspace()
         free, _total = torch.cuda.mem_get_info(dev)
         pooled = torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)    # cached by torch's allocator: reusable
-        budget = max(8 << 30, int(free + pooled) - self.SEARCH_HEADROOM_BYTES)
-        cold = int(float(os.environ.get("P4V_COLD_GROUP_GIB", "0")) * 2**30)     # 0: no cap
-        if replay_is_cheap and cold > 0:
-            budget = min(budget, max(cold, int(pooled)))
-        return budget
+        return max(8 << 30, int(free + pooled) - self.SEARCH_HEADROOM_BYTES)
 
     # ---- capture ------------------------------------------------------------------------------------
     def _ref_bs(self):
@@ -317,17 +394,16 @@ class HessianQuantCalibrator(QuantCalibrator):
                 raw_pred_softmax = F.softmax(raw_pred, dim=-1).detach()
         return raw_pred_softmax
 
-    def _capture(self, names, raw_pred_softmax, with_grad, stride=None):
+    def _capture(self, names, raw_pred_softmax, with_grad, stride=None, opts=None):
         """Forward (+ backward of the KL loss, reference :333-339) over the calibration set in sub-batches,
         with hooks on `names` only.  `stride = (r, w)`: run only the sub-batches i with i % w == r and leave the
-        per-sub-batch pieces on the modules as lists (sub-batch sharded capture, shard.exchange_captures)."""
+        per-sub-batch pieces on the modules as lists (sub-batch sharded capture, shard.exchange_captures).
+        `opts`: the calibration's options; a direct call (tests, tools) decides its own."""
+        opts = opts or calib_options(self)
         dev = _dev_of(self.net)
         bs = self._capture_bs()
         for n in names:
-            m = self.wrapped_modules[n]
-            m.raw_input = m.raw_out = None
-            if hasattr(m, "metric"):
-                m.raw_grad = None   # step 2 deletes the caches (reference linear.py:554): re-create for re-calibration
+            forget_caches(self.wrapped_modules[n])   # step 2 deletes the caches: re-create for re-calibration
         # Only gradients w.r.t. ACTIVATIONS are captured (grad_hook): no parameter gradient is ever looked at.  For the
         # duration of the capture NO parameter requires grad (no weight-gradient GEMMs -- a third of the backward pass --
         # no bias / LayerNorm reductions, no .grad accumulation); the graph hangs off the input images instead, which
@@ -339,10 +415,11 @@ class HessianQuantCalibrator(QuantCalibrator):
                     prm.requires_grad_(False)
                     frozen.append(prm)
         try:
+            # the passes replayed from HIP graphs kept with the network or its architecture (utils/capture_graph.py) ...
             if stride is None and with_grad and dev.type == "cuda" and not self.sequential:
-                if self._capture_passes_graph(names, dev, bs, raw_pred_softmax):
+                if capture_graph.capture_passes(self, opts, names, dev, bs, raw_pred_softmax):
                     return
-            hooks = []
+            hooks = []                                 # ... or run eagerly under hooks
             for n in names:
                 m = self.wrapped_modules[n]
                 hooks += _register(m, with_grad and hasattr(m, "metric"))
@@ -360,308 +437,7 @@ class HessianQuantCalibrator(QuantCalibrator):
             m = self.wrapped_modules[n]
             _concat(m, with_grad and hasattr(m, "metric"))
 
-    # ---- the capture pass as a HIP graph, kept with the network ---------------------------------------------------------
-    def _graph_key(self, dev, bs, inp):
-        """What a recorded pass depends on: sub-batch geometry and the storage of every parameter (the graph replays
-        kernels on those addresses).  Quantisation settings do not enter: during a non-sequential capture every wrapped
-        module runs its RAW forward, so the same graph serves W8A8, W6A6, ... calibrations of one network -- the grid the
-        reference's experiment driver walks (example/test_all.py:83-103)."""
-        return (str(dev), int(bs), tuple(inp.shape[1:]), str(inp.dtype), tuple(self.wrapped_modules),
-                tuple(getattr(m, "mode", "raw") for m in self.wrapped_modules.values()),     # all "raw", see _capture_passes_graph
-                tuple(p.data_ptr() for p in self.net.parameters()))
-
-    # ---- ... or with the ARCHITECTURE (round 6): a fresh network object replays the graph recorded for its architecture --------
-    # What the reference's driver times is a NEW network object calibrated once (example/test_all.py:24-34), and a process walks
-    # many of them (example/test_all.py:83-103: every bit setting re-creates the network).  A graph recorded on one network's
-    # parameter storage is useless for the next one -- but the kernel sequence of the raw sub-batch pass depends on the
-    # architecture only.  So the graph is recorded on a private copy of the network (the "shadow", own parameter storage, kept
-    # per architecture for the life of the process); a fresh network copies its parameters and buffers into the shadow's storage
-    # (one fused D2D copy, ~0.35 GB for ViT-B: 0.2 ms) and replays: the same kernels on the same values as its own eager pass --
-    # the captured tensors are bit-identical (tests/test_hip_model.py) -- without the ~110 ms of Python / dispatcher time of eight
-    # eager passes.  Built at the SECOND sighting of an architecture (a process that calibrates one network once never pays for
-    # it); P4V_ARCH_GRAPHS=0 switches it off, `use_graph` = True builds at the first.
-    _ARCH = {}            # architecture key -> {"seen": n, "net", "mods", "lanes", "src": [...], "dst": [...]}
-
-    def _arch_key(self, dev, bs, inp):
-        sig = tuple((n, tuple(p.shape), str(p.dtype)) for n, p in self.net.named_parameters()) + \
-            tuple((n, tuple(b.shape), str(b.dtype)) for n, b in self.net.named_buffers())
-        kinds = tuple((n, type(m).__name__) for n, m in self.wrapped_modules.items())
-        return (str(dev), int(bs), tuple(inp.shape[1:]), str(inp.dtype), type(self.net).__name__, sig, kinds)
-
-    def _arch_shadow(self, dev, bs, inp, build):
-        """The shadow of this network's architecture with this network's parameter VALUES in it, or None."""
-        if os.environ.get("P4V_ARCH_GRAPHS", "1") == "0":
-            return None
-        key = self._arch_key(dev, bs, inp)
-        rec = HessianQuantCalibrator._ARCH.setdefault(key, {"seen": 0, "nets": set()})
-        if id(self.net) not in rec["nets"]:
-            rec["nets"].add(id(self.net))
-            rec["seen"] += 1
-        if "net" not in rec:
-            if not (build or rec["seen"] >= 2):
-                return None
-            import copy
-            try:
-                with torch.no_grad():
-                    net2, mods2 = copy.deepcopy((self.net, dict(self.wrapped_modules)))
-            except Exception as e:  # noqa: BLE001 - a network that cannot be copied keeps its own graphs
-                print(f"[ptq4vit_amd] architecture graph unavailable ({type(e).__name__}: {e})")
-                rec["net"] = None
-                return None
-            for m in mods2.values():
-                for a in ("raw_input", "raw_out", "raw_grad"):
-                    m.__dict__.pop(a, None)
-                m.mode = "raw"
-            for p in net2.parameters():
-                p.requires_grad_(False)
-            rec.update(net=net2, mods=mods2, lanes=[])
-        if rec.get("net") is None:
-            return None
-        self._sync_shadow(rec)
-        return rec
-
-    def _sync_shadow(self, rec):
-        """This network's parameter / buffer VALUES into the storage the architecture's graphs replay on."""
-        src = [p.data for p in self.net.parameters()] + [b for b in self.net.buffers()]
-        dst = [p.data for p in rec["net"].parameters()] + [b for b in rec["net"].buffers()]
-        with torch.no_grad():
-            torch._foreach_copy_(dst, src)
-
-    def _build_graph(self, dev, bs, inp, raw_pred_softmax, shadow=None):
-        """Record ONE sub-batch forward + KL backward with hooks on EVERY wrapped module (so that any group of modules, on
-        any later calibration, can be served from it).  Returns the cache entry or None when graph capture is unavailable.
-        `shadow`: record on the architecture's private copy of the network instead of on this one."""
-        mods = self.wrapped_modules if shadow is None else shadow["mods"]
-        net = self.net if shadow is None else shadow["net"]
-        # (a module whose step 2 has run -- here, or on its owner rank before the interval exchange -- has had its cache
-        # attributes DELETED, reference linear.py:554; the hooks below expect them to exist)
-        missing = object()
-        saved = {n: tuple(m.__dict__.get(a, missing) for a in ("raw_input", "raw_out", "raw_grad")) for n, m in mods.items()}
-
-        def reset():
-            for m in mods.values():
-                m.raw_input = m.raw_out = None
-                if hasattr(m, "metric"):
-                    m.raw_grad = None
-
-        inv_n = torch.full((bs,), 1.0 / min(bs, self._ref_bs()), device=dev)      # graph passes are whole sub-batches
-
-        def one_pass(x, tgt):
-            x.grad = None
-            self._kl_loss(net(x), tgt, inv_n).backward()
-
-        hooks = []
-        for m in mods.values():
-            hooks += _register(m, hasattr(m, "metric"))
-        entry = None
-        try:
-            static_in = inp[:bs].to(dev).clone().requires_grad_(True)
-            static_tgt = raw_pred_softmax[:bs].clone()
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            reset()
-            with torch.cuda.stream(side):            # warm-up outside the graph (allocator, autograd, library handles)
-                one_pass(static_in, static_tgt)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            reset()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                one_pass(static_in, static_tgt)
-            # the hooks ran once, during capture: what they appended are the graph's static output tensors
-            statics = {}
-            for n, m in mods.items():
-                with_g = hasattr(m, "metric") and m.raw_grad is not None
-                if isinstance(m, MinMaxQuantMatMul):
-                    stat = [m.raw_input[0][0], m.raw_input[1][0], m.raw_out[0]]
-                else:
-                    stat = [m.raw_input[0], m.raw_out[0]]
-                if with_g:
-                    stat.append(m.raw_grad[0])
-                statics[n] = (stat, with_g)
-            entry = {"graph": graph, "in": static_in, "tgt": static_tgt, "statics": statics,
-                     "inv_n": inv_n}          # read by every replay: must live as long as the graph
-        except Exception as e:  # pragma: no cover - depends on the runtime
-            print(f"[ptq4vit_amd] graph capture unavailable ({type(e).__name__}: {e}); eager capture")
-        finally:
-            for h in hooks:
-                h.remove()
-            for n, m in mods.items():
-                for a, v in zip(("raw_input", "raw_out", "raw_grad"), saved[n]):
-                    if v is missing:
-                        m.__dict__.pop(a, None)
-                    else:
-                        setattr(m, a, v)
-        return entry
-
-    def _capture_passes_graph(self, names, dev, bs, raw_pred_softmax):
-        """The sub-batch forward + KL backward replayed from ONE HIP graph.
-
-        With batch_size=4 (the reference's setting) the eager pass is bound by launch overhead, not by the GPU
-        (~130 ms of Python / dispatcher time for ~70 ms of kernels on ViT-B, tools/prof_capture.py).  All modules run
-        in "raw" mode during a non-sequential capture, so every sub-batch executes the same kernel sequence: it is
-        recorded once (hooks included -- they see the graph's static tensors) and replayed per sub-batch; after each
-        replay the hooked tensors are copied into their slice of the preallocated caches (the copy torch.cat would
-        have done).  The instantiated graph stays with the network (`net._p4v_capture_graphs`): the capture of a second
-        group of modules (cache larger than the budget), and every later calibration of the same network, replays it.
-
-        When it is used (`use_graph` = True / False forces the choice): a graph is already cached; or the calibration
-        has >= 24 sub-batches (recording + instantiating costs about five eager passes); or this network has been
-        calibrated before (from the second calibration on the graph is recorded and kept).  Returns False -- caller
-        falls back to the eager pass -- if the loader is not a single batch divisible into equal sub-batches or if graph
-        capture is not available."""
-        batches = [inp for inp, _ in self.calib_loader]
-        if len(batches) != 1 or batches[0].shape[0] % bs != 0 or batches[0].shape[0] // bs < 2:
-            return False
-        inp = batches[0]
-        total = inp.shape[0]
-        n_sub = total // bs
-        use_graph = getattr(self, "use_graph", None)
-        if use_graph is False:
-            return False
-        # The recorded pass is the RAW forward of every wrapped module (`_graph_key`).  A network that is re-calibrated
-        # while modules are still in "quant_forward" (neither the reference nor `_calibrate` resets the modes) captures
-        # quantised forwards on the eager path; a graph would replay raw ones, or bake in kernels that read interval
-        # tensors which the next step 2 replaces.  Only the all-raw state is served from a graph.
-        if any(getattr(m, "mode", "raw") != "raw" for m in self.wrapped_modules.values()):
-            return False
-        import time
-        trace = os.environ.get("P4V_CAPTURE_TRACE") == "1"
-
-        def tick(label, t_prev):
-            if not trace:
-                return t_prev
-            torch.cuda.synchronize(dev)
-            now = time.time()
-            print(f"[capture] {label}: {now - t_prev:.3f} s", file=sys.stderr, flush=True)
-            return now
-        t_ = time.time()
-        cache = self.net.__dict__.setdefault("_p4v_capture_graphs", {})
-        key = self._graph_key(dev, bs, inp)
-        lanes = cache.get(key)
-        shadow = self.net.__dict__.get("_p4v_capture_shadow") if lanes is not None else None
-        if shadow is not None and lanes is shadow.get("lanes"):
-            self._sync_shadow(shadow)          # (the graphs are the architecture's: this network's values into their storage, every time)
-        else:
-            shadow = None
-        if lanes is None:
-            seen_before = self.net.__dict__.get("_p4v_calibrations", 0) > 0
-            shadow = self._arch_shadow(dev, bs, inp, build=bool(use_graph or n_sub >= 24 or seen_before))
-            if shadow is not None:
-                lanes = shadow["lanes"]
-                if not lanes:
-                    entry = self._build_graph(dev, bs, inp, raw_pred_softmax, shadow)
-                    if entry is None:
-                        shadow["net"] = None
-                        lanes = shadow = None
-                    else:
-                        lanes.append(entry)
-            if shadow is not None:
-                cache.clear()
-                cache[key] = lanes
-                self.net.__dict__["_p4v_capture_shadow"] = shadow
-        if lanes is None:
-            seen_before = self.net.__dict__.get("_p4v_calibrations", 0) > 0
-            if not (use_graph or n_sub >= 24 or seen_before):
-                return False
-            entry = self._build_graph(dev, bs, inp, raw_pred_softmax)
-            if entry is None:
-                return False
-            cache.clear()                      # one geometry per network at a time: a graph pins its activations' memory
-            lanes = cache[key] = [entry]
-        # A pass at 4 images is a chain of ~1500 kernels of a few microseconds each: the GPU is mostly idle while it runs.
-        # `capture_lanes` instances of the graph (own static tensors each) replay different sub-batches on different
-        # streams at the same time; every sub-batch still runs exactly the recorded kernels, so the caches do not change.
-        want = int(getattr(self, "capture_lanes", None) or os.environ.get("P4V_CAPTURE_LANES", "3"))
-        while len(lanes) < max(1, min(want, n_sub)):
-            entry = self._build_graph(dev, bs, inp, raw_pred_softmax, shadow)
-            if entry is None:
-                break
-            lanes.append(entry)
-        n_lanes = max(1, min(want, n_sub, len(lanes)))
-        t_ = tick(f"graphs ready ({len(lanes)} instance(s))", t_)
-        from .. import engine
-        # What does not change between calibrations of one network is kept with the graph instance (`recipe`): the layout of
-        # every cache (shape + strides: _cache_like) and which pieces are one dense block (_same_dense_block) -- ~3 ms of
-        # Python per calibration, during which the GPU had nothing to do.
-        flat_dsts, plans = [], []
-        key_names = tuple(names)
-        recipe0 = lanes[0].setdefault("recipes", {}).get(key_names)
-        if recipe0 is None:
-            statics0 = lanes[0]["statics"]
-            layout, is_block = [], []
-            for n in names:
-                for t in statics0[n][0]:
-                    c = _cache_like(t, n_sub)
-                    layout.append((tuple(c.shape), tuple(c.stride()), t.dtype))
-                    is_block.append(_same_dense_block(c, t))
-                    del c
-            recipe0 = lanes[0]["recipes"][key_names] = {"n_sub": n_sub, "layout": layout, "is_block": is_block}
-        if recipe0["n_sub"] != n_sub:
-            lanes[0]["recipes"].pop(key_names)
-            return self._capture_passes_graph(names, dev, bs, raw_pred_softmax)
-        k_ = 0
-        for n in names:
-            m = self.wrapped_modules[n]
-            stat, with_g = lanes[0]["statics"][n]
-            full = []
-            for _t in stat:
-                shp, strd, dt = recipe0["layout"][k_]
-                full.append(torch.empty_strided(shp, strd, dtype=dt, device=dev))
-                k_ += 1
-            d_ = m.__dict__                        # (plain tensors: what nn.Module.__setattr__ ends up doing, without its checks)
-            if isinstance(m, MinMaxQuantMatMul):
-                d_["raw_input"], d_["raw_out"] = [full[0], full[1]], full[2]
-            else:
-                d_["raw_input"], d_["raw_out"] = full[0], full[1]
-            if hasattr(m, "metric"):
-                d_["raw_grad"] = full[-1] if with_g else None
-            flat_dsts += full
-        for li in range(n_lanes):
-            statics = lanes[li]["statics"]
-            srcs = []
-            for n in names:
-                srcs += statics[n][0]
-            # every (static tensor -> slice i of its cache) whose memory is one dense block goes through ONE launch per
-            # sub-batch (p4v_multi_copy); anything else (overlapping / gapped views) keeps torch's copy
-            # (the recipe's flags were computed from lane 0's recorded tensors; another instance of the graph may have recorded
-            # one of them with other strides -- then the flat copy would scramble the cache: each lane's flags are checked
-            # against ITS statics once and kept with the lane)
-            lane_blocks = lanes[li].setdefault("is_block", {}).get(key_names)
-            if lane_blocks is None:
-                lane_blocks = [bool(b) and _same_dense_block(d, t) for d, t, b in zip(flat_dsts, srcs, recipe0["is_block"])]
-                lanes[li]["is_block"][key_names] = lane_blocks
-            block = [(d, t) for d, t, b in zip(flat_dsts, srcs, lane_blocks) if b]
-            other = [(d, t) for d, t, b in zip(flat_dsts, srcs, lane_blocks) if not b]
-            table, max_bytes = None, 0
-            if block:
-                rows = [[t.data_ptr(), d.data_ptr(), t.numel() * 4] for d, t in block]
-                table = torch.tensor(rows, dtype=torch.int64).to(dev, non_blocking=True)
-                max_bytes = max(r[2] for r in rows)
-            plans.append((lanes[li], table, len(block), max_bytes, other))
-        t_ = tick(f"caches allocated ({sum(d.numel() * 4 for d in flat_dsts) / 2**30:.1f} GiB)", t_)
-        main = torch.cuda.current_stream(dev)
-        streams = [main] if n_lanes == 1 else engine.side_streams(dev, n_lanes)
-        for s_ in streams:
-            if s_ is not main:
-                s_.wait_stream(main)          # the caches / tables / targets were produced on the current stream
-        for i, st in enumerate(range(0, total, bs)):
-            entry, table, n_block, max_bytes, other = plans[i % n_lanes]
-            with torch.cuda.stream(streams[i % n_lanes]):
-                with torch.no_grad():
-                    entry["in"].copy_(inp[st:st + bs])
-                entry["tgt"].copy_(raw_pred_softmax[st:st + bs])
-                entry["graph"].replay()
-                if table is not None:
-                    engine.multi_copy(table, n_block, i, max_bytes, dev)
-                    if i < n_lanes:
-                        table.record_stream(streams[i % n_lanes])     # read on a lane's stream, released without a host sync
-                for d, t in other:
-                    d[i * t.shape[0]:(i + 1) * t.shape[0]].copy_(t)
-        for s_ in streams:
-            if s_ is not main:
-                main.wait_stream(s_)
-        tick(f"{n_sub} replays + appends on {n_lanes} stream(s)", t_)
-        return True
+    _ARCH = capture_graph.ARCH      # architecture key -> capture_graph.ArchRecord: the one table, for the life of the process
 
     def _capture_passes(self, dev, bs, raw_pred_softmax, with_grad, stride=None):
         i = -1
@@ -680,191 +456,43 @@ class HessianQuantCalibrator(QuantCalibrator):
                     with torch.no_grad():
                         self.net(inp_)
 
-    def _search_concurrent(self, names, n_streams):
-        """Independent modules (sequential=False) searched `n_streams` at a time, one host thread + HIP stream each.
-
-        A search is a chain of ~50 kernels with a host round trip after every pass (the pass memo reads the selected
-        interval back); with a single stream the GPU idles during those round trips, during the small
-        finish/select kernels and in the tail of every sweep (1200 workgroups on 256 CUs).  A second stream fills
-        these holes with another module's kernels.  Results do not depend on the interleaving: the kernels are
-        deterministic and every call has its own scratch (engine.workspace is per stream).
-        """
-        import threading
-        import time
+    # ---- search -------------------------------------------------------------------------------------
+    def _on_side_streams(self, names, n_streams, body, inputs_ready=None, on_caller=False):
+        """What both searches of independent modules share: `n_streams` persistent side streams behind the capture, one host
+        thread per stream running `body(i, errors, inputs_ready)` under stream i and no_grad, the first error re-raised on the
+        calling thread after everything has been joined and synchronised.  `on_caller`: a single stream's body runs on the
+        calling thread.  `inputs_ready`: the event recorded behind the capture passes; it is handed on to the bodies -- which then
+        start while the capture is still on the GPU -- only when preparing the calls launches no torch kernel on captured data
+        (`_prep_is_copy_free`); otherwise, and without an event, the streams wait first and the bodies get None."""
+        from .. import engine
         dev = _dev_of(self.net)
         main = torch.cuda.current_stream(dev)
-        from .. import engine
         _warn_hw_queues(n_streams)
         streams = engine.side_streams(dev, n_streams)
         if not hasattr(self, "_module_ms"):
             self._module_ms = {}
-        for s in streams:
-            s.wait_stream(main)                       # the captured tensors were produced on the current stream
-        # the caches are freed by calibration_step2 (reference linear.py:554) while the other stream may still be
-        # running: hold them until everything has been joined so that the allocator cannot hand the memory out again
-        keep = [(m.raw_input, m.raw_out, getattr(m, "raw_grad", None)) for m in (self.wrapped_modules[n] for n in names)]
-        todo = list(names)
-        measured = (self.net.__dict__.get("_p4v_module_ms") or {}).get("ms", {})   # {"world", "ms"}: see _calibrate
-        if os.environ.get("P4V_SEARCH_ORDER", "lpt") == "lpt" and all(n in measured for n in names):
-            todo.sort(key=lambda n: measured[n], reverse=True)        # what each search took last time on this network
-        elif os.environ.get("P4V_SEARCH_ORDER", "lpt") == "lpt":
-            # longest first (by the size of what a search sweeps: rows x K x N), so that the last modules in flight are the
-            # small ones and the streams run dry together; the results do not depend on the order
-            def work(n):
-                m = self.wrapped_modules[n]
-                ri = m.raw_input
-                if isinstance(ri, (list, tuple)):                       # matmul: batch*heads x M x K x N
-                    a, b = ri
-                    return float(a.numel()) * b.shape[-1] * (0.2 if a.shape[-1] <= 64 else 1.0)
-                w = getattr(m, "weight", None)
-                return float(ri.numel()) / max(1, ri.shape[-1] if ri.dim() != 4 else 1) * (w.numel() if w is not None else 1) / (1 if ri.dim() != 4 else ri.shape[1])
-            todo.sort(key=work, reverse=True)
-        lock = threading.Lock()
-        errors = []
-
-        def worker(s):
-            try:
-                torch.cuda.set_device(dev)
-                with torch.cuda.stream(s), torch.no_grad():
-                    while True:
-                        with lock:
-                            if not todo or errors:
-                                return
-                            n = todo.pop(0)
-                        module = self.wrapped_modules[n]
-                        t_mod = time.perf_counter()
-                        module.calibration_step2()
-                        module.mode = "raw"
-                        self._module_ms[n] = (time.perf_counter() - t_mod) * 1e3
-            except BaseException as e:  # noqa: BLE001 - re-raised on the calling thread
-                errors.append(e)
-
-        threads = [threading.Thread(target=worker, args=(s,)) for s in streams]
-        for t in threads:
-            t.start()
-        for t in threads:
-            t.join()
-        for s in streams:
-            main.wait_stream(s)
-        torch.cuda.synchronize(dev)
-        del keep
-        if errors:
-            raise errors[0]
-
-    def _search_grouped(self, names, n_calls, inputs_ready=None):
-        """Independent modules (sequential=False) searched TOGETHER: `n_calls` p4v_calibrate_group calls (one host thread + HIP
-        stream each), every call running the calibration_step2 of its modules in lock step with the kernel launches of the
-        same kind issued once for all of them (csrc/p4v_api.hip, Group).  Replaces the loop of the reference's calibrator
-        (utils/quant_calib.py:371-372).  Results do not depend on the partition: a grouped kernel runs every module's own
-        code on its own parameters and scratch.
-
-        `inputs_ready`: the event recorded behind the capture passes.  The group calls then start while the capture is still on
-        the GPU -- the library issues what needs no captured tensor first (weight abs-max, candidate tables, the 100 candidate
-        planes of every Linear's weights: 8.5 GB of k_pack output per ViT-B calibration) and waits for the event on its own
-        stream where the first captured tensor is read.  Only when preparing the calls launches no torch kernel on captured data
-        (every cached tensor dense fp32 on the device: no `.contiguous()` / `.to()` copy); otherwise the streams wait first."""
-        import threading
-        import time
-        from .. import engine
-        dev = _dev_of(self.net)
-        main = torch.cuda.current_stream(dev)
-        n_calls = max(1, min(n_calls, len(names)))
-        _warn_hw_queues(n_calls)
-        streams = engine.side_streams(dev, n_calls)
-        if not hasattr(self, "_module_ms"):
-            self._module_ms = {}
-        def dense(t):
-            return t is None or (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous())
-
-        def prep_is_copy_free(m):
-            ri = m.raw_input
-            ins = list(ri) if isinstance(ri, (list, tuple)) else [ri]
-            if not isinstance(ri, (list, tuple)) and not dense(ri):          # (matmul operands are read through their strides)
-                return False
-            w = getattr(m, "weight", None)
-            return (all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in ins) and dense(m.raw_out)
-                    and dense(getattr(m, "raw_grad", None)) and (w is None or dense(w.data)) and _groupable(m))
-        early = (inputs_ready is not None and os.environ.get("P4V_EARLY_SEARCH", "1") != "0"
-                 and all(prep_is_copy_free(self.wrapped_modules[n]) for n in names))
-        if not early:
+        mods = [self.wrapped_modules[n] for n in names]
+        if inputs_ready is None or not all(_prep_is_copy_free(m) for m in mods):
             inputs_ready = None
             for s in streams:
                 s.wait_stream(main)                   # the captured tensors were produced on the current stream
-        keep = [(m.raw_input, m.raw_out, getattr(m, "raw_grad", None)) for m in (self.wrapped_modules[n] for n in names)]
-        # modules of one kind are dealt over the calls, so that every call holds the same mixture (and its launches group)
-        def kind(n):
-            m = self.wrapped_modules[n]
-            ri = m.raw_input
-            shp = tuple(tuple(t.shape) for t in ri) if isinstance(ri, (list, tuple)) else tuple(ri.shape)
-            return (type(m).__name__, shp, tuple(m.raw_out.shape))
-        order = sorted(names, key=lambda n: (str(kind(n)), names.index(n)))
-        parts = [order[i::n_calls] for i in range(n_calls)]
-        # Scratch of all concurrent group calls together: P4V_GROUP_GIB at most, and never more than what is free NOW -- the
-        # captured tensors of this group are resident (their allocation is host-side and behind us) -- plus what torch's pool and
-        # the engine's own kept buffers can be re-used for, minus a margin for the allocator's rounding and torch temporaries.
-        # (Round 6 sized it to a constant 150 GiB: next to the 207 GB of captured tensors of Swin-B/384 x 128 the first call ran
-        # out of memory three times, and the buffers it left behind starved the next calibration's caches.)
-        budget_all = int(float(os.environ.get("P4V_GROUP_GIB", "150")) * (1 << 30))
-        if dev.type == "cuda":
-            free, _tot = torch.cuda.mem_get_info(dev)
-            pooled = torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-            avail = int(free + pooled) + engine.workspace_bytes(dev) - (6 << 30)
-            if avail < budget_all:
-                engine.release_workspace()      # (buffers sized for another mixture of members would be stranded next to the new ones)
-                budget_all = max(4 << 30, avail)
-        budget = budget_all // n_calls
+        # the caches are freed by calibration_step2 (reference linear.py:554) while the other stream may still be
+        # running: hold them until everything has been joined so that the allocator cannot hand the memory out again
+        keep = [(m.raw_input, m.raw_out, getattr(m, "raw_grad", None)) for m in mods]
         errors = []
 
-        def cost(n, sizes):
-            return shard.module_cost_ms(self.wrapped_modules[n], sizes[n])
-
-        def worker(s, part):
+        def run(i):
             try:
                 torch.cuda.set_device(dev)
-                with torch.cuda.stream(s), torch.no_grad():
-                    todo = list(part)
-                    while todo and not errors:
-                        t_grp = time.perf_counter()
-                        batch, jobs, sizes, acc = [], [], {}, 0
-                        while todo:
-                            n = todo[0]
-                            m = self.wrapped_modules[n]
-                            if not _groupable(m):        # calibration_step2 overridden / a class without the two-step protocol: alone
-                                if batch:
-                                    break
-                                todo.pop(0)
-                                m.calibration_step2()
-                                m.mode = "raw"
-                                self._module_ms[n] = (time.perf_counter() - t_grp) * 1e3
-                                t_grp = time.perf_counter()
-                                continue
-                            ri = m.raw_input
-                            sizes[n] = 4 * (sum(t.numel() for t in ri) if isinstance(ri, (list, tuple)) else ri.numel()) + 8 * m.raw_out.numel()
-                            job = m.calibration_job()
-                            held = (int(job.need) + 4095) & ~4095          # (its share of the call's arena, engine.calibrate_group)
-                            if batch and acc + held > budget:              # scratch of the members so far fills the budget: next call
-                                break
-                            todo.pop(0)
-                            batch.append(n); jobs.append(job); acc += held
-                        if not batch:
-                            continue
-                        engine.calibrate_group(jobs, inputs_ready=inputs_ready)
-                        for n, j in zip(batch, jobs):
-                            m = self.wrapped_modules[n]
-                            m.calibration_install(j)
-                            m.mode = "raw"
-                        ms = (time.perf_counter() - t_grp) * 1e3
-                        w = {n: cost(n, sizes) for n in batch}
-                        tot = sum(w.values()) or 1.0
-                        for n in batch:                     # (the call's wall time, shared out by the cost model: next LPT plan)
-                            self._module_ms[n] = ms * w[n] / tot
+                with torch.cuda.stream(streams[i]), torch.no_grad():
+                    body(i, errors, inputs_ready)
             except BaseException as e:  # noqa: BLE001 - re-raised on the calling thread
                 errors.append(e)
 
-        if n_calls == 1:
-            worker(streams[0], parts[0])          # on the calling thread (p4v_stats_* are per calling thread: bench.py's roofline step)
+        if on_caller and n_streams == 1:
+            run(0)
         else:
-            threads = [threading.Thread(target=worker, args=(s, p)) for s, p in zip(streams, parts)]
+            threads = [threading.Thread(target=run, args=(i,)) for i in range(n_streams)]
             for t in threads:
                 t.start()
             for t in threads:
@@ -875,6 +503,118 @@ class HessianQuantCalibrator(QuantCalibrator):
         del keep
         if errors:
             raise errors[0]
+
+    def _search_concurrent(self, names, n_streams):
+        """Independent modules (sequential=False) searched `n_streams` at a time, one host thread + HIP stream each.
+
+        A search is a chain of ~50 kernels with a host round trip after every pass (the pass memo reads the selected
+        interval back); with a single stream the GPU idles during those round trips, during the small
+        finish/select kernels and in the tail of every sweep (1200 workgroups on 256 CUs).  A second stream fills
+        these holes with another module's kernels.  Results do not depend on the interleaving: the kernels are
+        deterministic and every call has its own scratch (engine.workspace is per stream).
+        """
+        todo = list(names)
+        measured = (self.net.__dict__.get("_p4v_module_ms") or {}).get("ms", {})   # {"world", "ms"}: see _exchange
+        if all(n in measured for n in names):
+            todo.sort(key=lambda n: measured[n], reverse=True)        # what each search took last time on this network
+        else:
+            # longest first (by the size of what a search sweeps), so that the last modules in flight are the
+            # small ones and the streams run dry together; the results do not depend on the order
+            todo.sort(key=lambda n: _search_work(self.wrapped_modules[n]), reverse=True)
+        lock = threading.Lock()
+
+        def body(_i, errors, _inputs_ready):
+            while True:
+                with lock:
+                    if not todo or errors:
+                        return
+                    n = todo.pop(0)
+                module = self.wrapped_modules[n]
+                t_mod = time.perf_counter()
+                module.calibration_step2()
+                module.mode = "raw"
+                self._module_ms[n] = (time.perf_counter() - t_mod) * 1e3
+
+        self._on_side_streams(names, n_streams, body)
+
+    def _search_grouped(self, names, n_calls, inputs_ready=None, opts=None):
+        """Independent modules (sequential=False) searched TOGETHER: `n_calls` p4v_calibrate_group calls (one host thread + HIP
+        stream each), every call running the calibration_step2 of its modules in lock step with the kernel launches of the
+        same kind issued once for all of them (csrc/p4v_api.hip, Group).  Replaces the loop of the reference's calibrator
+        (utils/quant_calib.py:371-372).  Results do not depend on the partition: a grouped kernel runs every module's own
+        code on its own parameters and scratch.
+
+        `inputs_ready`: the event recorded behind the capture passes.  The group calls then start while the capture is still on
+        the GPU -- the library issues what needs no captured tensor first (weight abs-max, candidate tables, the 100 candidate
+        planes of every Linear's weights: 8.5 GB of k_pack output per ViT-B calibration) and waits for the event on its own
+        stream where the first captured tensor is read (when `_on_side_streams` allows it)."""
+        from .. import engine
+        opts = opts or calib_options(self)
+        dev = _dev_of(self.net)
+        n_calls = max(1, min(n_calls, len(names)))
+        kinds = {}
+        for n in names:
+            m, ins = self.wrapped_modules[n], _operands(self.wrapped_modules[n])
+            shp = tuple(tuple(t.shape) for t in ins) if len(ins) == 2 else tuple(ins[0].shape)
+            kinds[n] = (type(m).__name__, shp, tuple(m.raw_out.shape))
+        parts = deal_over_calls(names, kinds, n_calls)
+        # Scratch of all concurrent group calls together: P4V_GROUP_GIB at most, and never more than what is free NOW -- the
+        # captured tensors of this group are resident (their allocation is host-side and behind us) -- plus what torch's pool and
+        # the engine's own kept buffers can be re-used for, minus a margin for the allocator's rounding and torch temporaries.
+        # (Round 6 sized it to a constant 150 GiB: next to the 207 GB of captured tensors of Swin-B/384 x 128 the first call ran
+        # out of memory three times, and the buffers it left behind starved the next calibration's caches.)
+        budget_all = int(opts.group_gib * (1 << 30))
+        if dev.type == "cuda":
+            free, _tot = torch.cuda.mem_get_info(dev)
+            pooled = torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+            avail = int(free + pooled) + engine.workspace_bytes(dev) - (6 << 30)
+            if avail < budget_all:
+                engine.release_workspace()      # (buffers sized for another mixture of members would be stranded next to the new ones)
+                budget_all = max(4 << 30, avail)
+        budget = budget_all // n_calls
+        # (one call runs on the calling thread: p4v_stats_* are per calling thread -- bench.py's roofline step)
+        self._on_side_streams(names, n_calls, lambda i, errors, ready: self._group_call(parts[i], budget, errors, ready),
+                              inputs_ready=inputs_ready, on_caller=True)
+
+    def _group_call(self, part, budget, errors, inputs_ready):
+        """One stream's share of a grouped search: p4v_calibrate_group over as many modules of `part` at a time as their scratch
+        fits into `budget` bytes."""
+        from .. import engine
+        todo = list(part)
+        while todo and not errors:
+            t_grp = time.perf_counter()
+            batch, jobs, sizes, acc = [], [], {}, 0
+            while todo:
+                n = todo[0]
+                m = self.wrapped_modules[n]
+                if not _groupable(m):        # calibration_step2 overridden / a class without the two-step protocol: alone
+                    if batch:
+                        break
+                    todo.pop(0)
+                    m.calibration_step2()
+                    m.mode = "raw"
+                    self._module_ms[n] = (time.perf_counter() - t_grp) * 1e3
+                    t_grp = time.perf_counter()
+                    continue
+                sizes[n] = 4 * sum(t.numel() for t in _operands(m)) + 8 * m.raw_out.numel()
+                job = m.calibration_job()
+                held = (int(job.need) + 4095) & ~4095          # (its share of the call's arena, engine.calibrate_group)
+                if batch and acc + held > budget:              # scratch of the members so far fills the budget: next call
+                    break
+                todo.pop(0)
+                batch.append(n); jobs.append(job); acc += held
+            if not batch:
+                continue
+            engine.calibrate_group(jobs, inputs_ready=inputs_ready)
+            for n, j in zip(batch, jobs):
+                m = self.wrapped_modules[n]
+                m.calibration_install(j)
+                m.mode = "raw"
+            ms = (time.perf_counter() - t_grp) * 1e3
+            w = {n: shard.module_cost_ms(self.wrapped_modules[n], sizes[n]) for n in batch}
+            tot = sum(w.values()) or 1.0
+            for n in batch:                     # (the call's wall time, shared out by the cost model: next LPT plan)
+                self._module_ms[n] = ms * w[n] / tot
 
     def _estimate_cache_bytes(self, names):
         """One cheap probe forward of a single image to size the caches of `names` (kept with the network: the sizes depend
@@ -939,197 +679,37 @@ class HessianQuantCalibrator(QuantCalibrator):
         self._calibrate(batching=True, with_grad=with_grad)
 
     def _calibrate(self, batching, with_grad):
-        import time
+        opts = calib_options(self)
         names = list(self.wrapped_modules)
         print(f"prepare parallel calibration for {names}")
         print("start hessian calibration")
         rank, world = shard.rank_world()
         t0 = time.time()
-        if world > 1 and not self.sequential:
-            # balance by predicted search time (needs every module's captured size: one single-image probe forward)
-            all_sizes = self._estimate_cache_bytes(names)
-            costs = {n: shard.module_cost_ms(self.wrapped_modules[n], all_sizes.get(n, 0)) for n in names}
-            # from the second calibration of a network on: what every module's search actually took last time (gathered from
-            # all ranks at the end of that calibration, hence the same on every rank) -- the cost model does not know whether
-            # the exact pruning applies to a module (it depends on where raw_grad^2 sits), the clock does
-            # Only a table that was all-gathered by a calibration of THIS world size counts (a single-process warm-up before
-            # init_process_group leaves local wall-clock times behind: tagged world 1, ignored here), and because the owner map
-            # drives the collectives of exchange_captures / exchange_intervals it must be the same on every rank whatever each
-            # rank's history is: rank 0's costs are broadcast (a few hundred floats) before the assignment.
-            measured = self.net.__dict__.get("_p4v_module_ms") or {}
-            if measured.get("world") == world and all(n in measured.get("ms", {}) for n in names):
-                costs = {n: float(measured["ms"][n]) for n in names}
-            box = [[costs[n] for n in names]]
-            shard.dist.broadcast_object_list(box, src=0)
-            costs = dict(zip(names, box[0]))
-            owner = shard.assign_modules(self.wrapped_modules, world, costs)
-        else:
-            all_sizes = None
-            owner = {n: rank for n in names}
+        owner, all_sizes = self._assign_owners(names, rank, world)
         mine = [n for n in names if owner[n] == rank]
         self.owner = owner
         raw_pred_softmax = self._raw_pred_softmax() if with_grad else None
-
-        # Capture plan.  Replicated (the design BASELINE.json's north_star names): every rank runs the same deterministic
-        # capture passes with hooks on its OWN modules only -- no data-path collective -- and the only exchange is the
-        # interval all-gather at the end.  Sharded: every rank runs 1/world of the sub-batch passes hooking ALL modules and
-        # the pieces travel to the module owners in one all_to_all (shard.exchange_captures); chosen by the cost model where
-        # the replicated passes would cap the speed-up.  Whether that collective is entered must be the SAME decision on every rank, so it
-        # is derived from rank-invariant quantities only (all_sizes covers every module on every rank; a rank that owns
-        # nothing, or whose own cache would need several groups, decides exactly like the others).
-        bs_ = self._capture_bs()
-        n_sub = sum(-(-inp.shape[0] // bs_) for inp, _ in self.calib_loader)
-        # `shard_capture` / P4V_SHARD_CAPTURE: True / "1" = sharded, False / "0" = replicated, None / "auto" (default) = the
-        # cost model of shard.choose_capture_mode (rank-invariant inputs only) where all_to_all_single works on every rank
-        want_shard = getattr(self, "shard_capture", None)
-        if want_shard is None:
-            env = os.environ.get("P4V_SHARD_CAPTURE", "auto")
-            want_shard = True if env == "1" else False if env == "0" else None
-        if want_shard is None:
-            # (auto: the cost model with the all_to_all rate MEASURED on this process group -- replicated, north_star's plan,
-            # unless the measurement says the transfer pays; P4V_SHARD_CAPTURE=0 never touches the collective)
-            want_shard = (world > 1 and not self.sequential and with_grad and all_sizes is not None
-                          and shard.choose_capture_mode(self.wrapped_modules, all_sizes, world, n_sub, shard.a2a_rate_gbps()) == "sharded")
-        self.capture_mode = "replicated"
-        shard_cap = False
-        dev_ = _dev_of(self.net)
-        replay_is_cheap = (with_grad and dev_.type == "cuda" and not self.sequential and getattr(self, "use_graph", None) is not False
-                           and len(list(self.calib_loader)) == 1
-                           and (getattr(self, "use_graph", None) is True or n_sub >= 24 or self.net.__dict__.get("_p4v_calibrations", 0) > 0
-                                or bool(self.net.__dict__.get("_p4v_capture_graphs"))))
-        budget = self._resolve_budget(replay_is_cheap)
-
-        def plan(todo, budget_):
-            if self.sequential:
-                return [[n] for n in todo]  # predecessors must already run quantised: one capture per module
-            if shard_cap:
-                return [todo]               # one exchange, then everything this rank owns (possibly nothing)
-            sizes = all_sizes if all_sizes is not None else self._estimate_cache_bytes(todo)
-            out, cur, acc = [], [], 0
-            for n in todo:
-                if cur and acc + sizes.get(n, 0) > budget_:
-                    out.append(cur)
-                    cur, acc = [], 0
-                cur.append(n)
-                acc += sizes.get(n, 0)
-            if cur:
-                out.append(cur)
-            return out
-
-        def run_group(grp):
-            t1 = time.time()
-            n_streams = getattr(self, "search_streams", None) or int(os.environ.get("P4V_SEARCH_STREAMS", "4"))
-            grouped = getattr(self, "search_grouped", None)
-            if grouped is None:
-                grouped = os.environ.get("P4V_GROUPED", "1") != "0"
-            # (the grouped search is one call however many streams the per-module search would use: search_streams = 1 selects ONE
-            # group call, the launch order bench.py's roofline records describe)
-            concurrent = batching and not self.sequential and (n_streams > 1 or grouped) and _dev_of(self.net).type == "cuda" and len(grp) > 1
-            # The search streams wait for the capture ON THE DEVICE (wait_stream): the host does not -- its threads prepare and
-            # enqueue the first searches while the last capture passes still run (a host synchronisation here left the GPU idle
-            # for ~2 ms per calibration: thread start, descriptors, workspace planning).  The capture / search split of the
-            # timings then comes from a device event instead of the host clock.
-            cap_done = None
-            if shard_cap:
-                self._capture(names, raw_pred_softmax, with_grad, stride=(rank, world))
-                grad_names = {n for n in names if with_grad and hasattr(self.wrapped_modules[n], "metric")}
-                shard.exchange_captures(self.wrapped_modules, owner, n_sub, grad_names)
-            else:
-                self._capture(grp, raw_pred_softmax, with_grad)
-            if concurrent and not shard_cap and os.environ.get("P4V_CAPTURE_SYNC", "0") != "1":
-                dev_g = _dev_of(self.net)
-                cap_done = torch.cuda.Event(enable_timing=True)
-                cap_done.record(torch.cuda.current_stream(dev_g))
-            elif torch.cuda.is_available():
-                torch.cuda.synchronize()
-            t2 = time.time()
-            if concurrent:
-                if grouped:
-                    calls = 1 if n_streams == 1 else (getattr(self, "group_calls", None) or int(os.environ.get("P4V_GROUP_CALLS", "0")))
-                    if calls <= 0:
-                        # three concurrent calls overlap each other's small kernels and round trips (ViT-B/224 x 32: 127 ms with one
-                        # call, 112 with three; ViT-S x 32: 68.7 / 62.7; DeiT-tiny x 32: 44.3 / 41.2); a calibration whose captured
-                        # tensors are a few hundred MB is issue-bound and pays for every extra round instead (DeiT-tiny BasePTQ x 4,
-                        # BASELINE config 0: 5 rounds / 27.7 ms with one call, 15 rounds / 29.4 ms with three)
-                        small = sum(self._estimate_cache_bytes(grp).values()) < (512 << 20)
-                        calls = 1 if small else 3
-                    self._search_grouped(grp, calls, inputs_ready=cap_done)
-                else:
-                    self._search_concurrent(grp, n_streams)
-                if cap_done is not None:            # (everything is synchronised now) when the capture really ended
-                    ref = torch.cuda.Event(enable_timing=True)
-                    ref.record(torch.cuda.current_stream(_dev_of(self.net)))
-                    ref.synchronize()
-                    t_end = time.time()
-                    t2 = max(t2, t_end - cap_done.elapsed_time(ref) * 1e-3)
-            else:
-                for n in tqdm(grp, desc="Hessian"):
-                    module = self.wrapped_modules[n]
-                    with torch.no_grad():
-                        if batching:
-                            module.calibration_step2()
-                        elif isinstance(module, MinMaxQuantMatMul):
-                            module.calibration_step2(module.raw_input[0], module.raw_input[1])
-                        else:
-                            module.calibration_step2(module.raw_input)
-                    module.mode = "quant_forward" if self.sequential else "raw"
-            if torch.cuda.is_available():
-                torch.cuda.synchronize()
-            return t2 - t1, time.time() - t2
-
-        if world > 1 and not self.sequential and want_shard:
-            per_rank = [sum(all_sizes.get(n, 0) for n in names if owner[n] == r) for r in range(world)]
-            during = sum(all_sizes.values()) / world          # every rank holds all modules x its share of sub-batches
-            shard_budget = self.cache_budget_bytes if self.cache_budget_bytes is not None else (200 << 30)   # NOT the locally
-            # (pieces of all modules + the send buffer, then the receive buffer + the reassembled tensors of the own modules)
-            shard_cap = (n_sub >= world and 2 * max(per_rank) + 2 * during <= shard_budget                    # measured one
-                         and all(inp.shape[0] % bs_ == 0 for inp, _ in self.calib_loader))
-            self.capture_mode = "sharded" if shard_cap else "replicated"
-        groups = plan(mine, budget)
+        bs = self._capture_bs()
+        n_sub = sum(-(-inp.shape[0] // bs) for inp, _ in self.calib_loader)
+        shard_cap = self._sharded_capture(opts, names, owner, all_sizes, world, n_sub, with_grad)
+        self.capture_mode = "sharded" if shard_cap else "replicated"
+        cal = _Calibration(opts=opts, batching=batching, with_grad=with_grad, rank=rank, world=world, names=names, owner=owner,
+                           all_sizes=all_sizes, n_sub=n_sub, shard_cap=shard_cap, raw_pred_softmax=raw_pred_softmax)
+        budget = self._resolve_budget()
+        groups = self._plan(cal, mine, budget)
         t_cap = t_cal = 0.0
         done = set()
         while groups:
             grp = groups.pop(0)
             try:
-                dc, ds = run_group(grp)
+                dc, ds = self._run_group(cal, grp)
             except torch.cuda.OutOfMemoryError as oom:
-                if os.environ.get("P4V_CAPTURE_TRACE", "0") == "1":
-                    import traceback
-                    tb = traceback.extract_tb(oom.__traceback__)
-                    print("[ptq4vit_amd] OOM at " + " <- ".join(f"{os.path.basename(f.filename)}:{f.lineno}({f.name})" for f in tb[-4:]) + ": " + str(oom).split("\n")[0][:200], flush=True)
-                # the budget was an estimate (allocator fragmentation, another tenant on the GPU): drop this group's caches
-                # and scratch, halve the budget and re-plan what is not calibrated yet.  (Not possible mid-collective.)
-                if shard_cap or len(grp) <= 1:      # a single module that does not fit cannot be split any further
-                    raise
-                from .. import engine
-                for n in grp:
-                    m = self.wrapped_modules[n]
-                    if n not in done and not (hasattr(m, "calibrated") and not hasattr(m, "raw_out")):
-                        m.raw_input = m.raw_out = None
-                        if hasattr(m, "metric"):
-                            m.raw_grad = None
-                engine.release_workspace()
-                torch.cuda.empty_cache()
-                budget //= 2
-                print(f"[ptq4vit_amd] out of memory with {len(grp)} modules resident: retrying with a cache budget of {budget >> 30} GiB")
-                left = [n for n in grp if not (hasattr(self.wrapped_modules[n], "calibrated") and not hasattr(self.wrapped_modules[n], "raw_out"))]
-                left += [n for g in groups for n in g]
-                groups = plan(left, budget)
+                groups, budget = self._replan_after_oom(cal, oom, grp, groups, done, budget)
                 continue
             done.update(grp)
             t_cap += dc
             t_cal += ds
-        t_ex = 0.0
-        mine_ms = dict(getattr(self, "_module_ms", {}))
-        if world > 1 and not self.sequential:
-            t1 = time.time()
-            shard.exchange_intervals(self.wrapped_modules, owner)
-            t_ex = time.time() - t1          # includes waiting for the slowest rank's search (the collective is the barrier)
-            parts = [None] * world
-            shard.dist.all_gather_object(parts, mine_ms)                 # a few hundred floats: next calibration's LPT costs
-            mine_ms = {k: v for part in parts for k, v in (part or {}).items()}
-        if mine_ms:          # replaced, not merged: the table describes ONE calibration (of this world size), gathered from all ranks
-            self.net.__dict__["_p4v_module_ms"] = {"world": world, "ms": dict(mine_ms)}
+        t_ex = self._exchange(cal)
         for module in self.wrapped_modules.values():
             module.mode = "quant_forward"
         self.net.__dict__["_p4v_calibrations"] = self.net.__dict__.get("_p4v_calibrations", 0) + 1
@@ -1137,3 +717,149 @@ class HessianQuantCalibrator(QuantCalibrator):
                         "modules": len(names), "owned": len(mine)}
         self.calibrated = True
         print("hessian calibration finished")
+
+    def _assign_owners(self, names, rank, world):
+        """({module: owning rank}, {module: cache bytes} of every module or None): the modules balanced over the ranks."""
+        if world <= 1 or self.sequential:
+            return {n: rank for n in names}, None
+        # balance by predicted search time (needs every module's captured size: one single-image probe forward)
+        all_sizes = self._estimate_cache_bytes(names)
+        costs = {n: shard.module_cost_ms(self.wrapped_modules[n], all_sizes.get(n, 0)) for n in names}
+        # from the second calibration of a network on: what every module's search actually took last time (gathered from
+        # all ranks at the end of that calibration, hence the same on every rank) -- the cost model does not know whether
+        # the exact pruning applies to a module (it depends on where raw_grad^2 sits), the clock does
+        # Only a table that was all-gathered by a calibration of THIS world size counts (a single-process warm-up before
+        # init_process_group leaves local wall-clock times behind: tagged world 1, ignored here), and because the owner map
+        # drives the collectives of exchange_captures / exchange_intervals it must be the same on every rank whatever each
+        # rank's history is: rank 0's costs are broadcast (a few hundred floats) before the assignment.
+        measured = self.net.__dict__.get("_p4v_module_ms") or {}
+        if measured.get("world") == world and all(n in measured.get("ms", {}) for n in names):
+            costs = {n: float(measured["ms"][n]) for n in names}
+        box = [[costs[n] for n in names]]
+        shard.dist.broadcast_object_list(box, src=0)
+        costs = dict(zip(names, box[0]))
+        return shard.assign_modules(self.wrapped_modules, world, costs), all_sizes
+
+    def _sharded_capture(self, opts, names, owner, all_sizes, world, n_sub, with_grad):
+        """Capture plan.  Replicated (the design BASELINE.json's north_star names; False): every rank runs the same deterministic
+        capture passes with hooks on its OWN modules only -- no data-path collective -- and the only exchange is the
+        interval all-gather at the end.  Sharded (True): every rank runs 1/world of the sub-batch passes hooking ALL modules and
+        the pieces travel to the module owners in one all_to_all (shard.exchange_captures); chosen by the cost model where
+        the replicated passes would cap the speed-up.  Whether that collective is entered must be the SAME decision on every
+        rank, so it is derived from rank-invariant quantities only (all_sizes covers every module on every rank; a rank that
+        owns nothing, or whose own cache would need several groups, decides exactly like the others)."""
+        # `shard_capture` / P4V_SHARD_CAPTURE: True / "1" = sharded, False / "0" = replicated, None / "auto" (default) = the
+        # cost model of shard.choose_capture_mode (rank-invariant inputs only) where all_to_all_single works on every rank
+        want_shard = opts.shard_capture
+        if want_shard is None:
+            # (auto: the cost model with the all_to_all rate MEASURED on this process group -- replicated, north_star's plan,
+            # unless the measurement says the transfer pays; P4V_SHARD_CAPTURE=0 never touches the collective)
+            want_shard = (world > 1 and not self.sequential and with_grad and all_sizes is not None
+                          and shard.choose_capture_mode(self.wrapped_modules, all_sizes, world, n_sub, shard.a2a_rate_gbps()) == "sharded")
+        if not (world > 1 and not self.sequential and want_shard):
+            return False
+        bs = self._capture_bs()
+        per_rank = [sum(all_sizes.get(n, 0) for n in names if owner[n] == r) for r in range(world)]
+        during = sum(all_sizes.values()) / world          # every rank holds all modules x its share of sub-batches
+        shard_budget = self.cache_budget_bytes if self.cache_budget_bytes is not None else (200 << 30)   # NOT the locally
+        # (pieces of all modules + the send buffer, then the receive buffer + the reassembled tensors of the own modules)
+        return (n_sub >= world and 2 * max(per_rank) + 2 * during <= shard_budget                         # measured one
+                and all(inp.shape[0] % bs == 0 for inp, _ in self.calib_loader))
+
+    def _plan(self, cal, todo, budget):
+        sizes = None
+        if not (self.sequential or cal.shard_cap):
+            sizes = cal.all_sizes if cal.all_sizes is not None else self._estimate_cache_bytes(todo)
+        return plan_groups(todo, sizes, budget, self.sequential, cal.shard_cap)
+
+    def _run_group(self, cal, grp):
+        """Capture and search of one group of modules; returns the seconds of either."""
+        opts = cal.opts
+        t1 = time.time()
+        # (the grouped search is one call however many streams the per-module search would use: search_streams = 1 selects ONE
+        # group call)
+        concurrent = (cal.batching and not self.sequential and (opts.search_streams > 1 or opts.search_grouped)
+                      and _dev_of(self.net).type == "cuda" and len(grp) > 1)
+        # The search streams wait for the capture ON THE DEVICE (wait_stream): the host does not -- its threads prepare and
+        # enqueue the first searches while the last capture passes still run (a host synchronisation here left the GPU idle
+        # for ~2 ms per calibration: thread start, descriptors, workspace planning).  The capture / search split of the
+        # timings then comes from a device event instead of the host clock.
+        cap_done = None
+        if cal.shard_cap:
+            self._capture(cal.names, cal.raw_pred_softmax, cal.with_grad, stride=(cal.rank, cal.world), opts=opts)
+            grad_names = {n for n in cal.names if cal.with_grad and hasattr(self.wrapped_modules[n], "metric")}
+            shard.exchange_captures(self.wrapped_modules, cal.owner, cal.n_sub, grad_names)
+        else:
+            self._capture(grp, cal.raw_pred_softmax, cal.with_grad, opts=opts)
+        if concurrent and not cal.shard_cap:
+            cap_done = torch.cuda.Event(enable_timing=True)
+            cap_done.record(torch.cuda.current_stream(_dev_of(self.net)))
+        elif torch.cuda.is_available():
+            torch.cuda.synchronize()
+        t2 = time.time()
+        if not concurrent:
+            self._search_serial(cal, grp)
+        elif opts.search_grouped:
+            calls = opts.n_group_calls(lambda: sum(self._estimate_cache_bytes(grp).values()))
+            self._search_grouped(grp, calls, inputs_ready=cap_done, opts=opts)
+        else:
+            self._search_concurrent(grp, opts.search_streams)
+        if cap_done is not None:            # (everything is synchronised now) when the capture really ended
+            ref = torch.cuda.Event(enable_timing=True)
+            ref.record(torch.cuda.current_stream(_dev_of(self.net)))
+            ref.synchronize()
+            t_end = time.time()
+            t2 = max(t2, t_end - cap_done.elapsed_time(ref) * 1e-3)
+        if torch.cuda.is_available():
+            torch.cuda.synchronize()
+        return t2 - t1, time.time() - t2
+
+    def _search_serial(self, cal, grp):
+        """The reference's loop (quant_calib.py:371-372): one module after the other on the current stream."""
+        for n in tqdm(grp, desc="Hessian"):
+            module = self.wrapped_modules[n]
+            with torch.no_grad():
+                if cal.batching:
+                    module.calibration_step2()
+                elif isinstance(module, MinMaxQuantMatMul):
+                    module.calibration_step2(module.raw_input[0], module.raw_input[1])
+                else:
+                    module.calibration_step2(module.raw_input)
+            module.mode = "quant_forward" if self.sequential else "raw"
+
+    def _replan_after_oom(self, cal, oom, grp, groups, done, budget):
+        """The budget was an estimate (allocator fragmentation, another tenant on the GPU): drop this group's caches and scratch,
+        halve the budget and re-plan what is not calibrated yet; returns (groups, budget).  (Not possible mid-collective.)"""
+        if cal.opts.capture_trace:
+            import traceback
+            tb = traceback.extract_tb(oom.__traceback__)
+            print("[ptq4vit_amd] OOM at " + " <- ".join(f"{os.path.basename(f.filename)}:{f.lineno}({f.name})" for f in tb[-4:]) + ": " + str(oom).split("\n")[0][:200], flush=True)
+        if cal.shard_cap or len(grp) <= 1:      # a single module that does not fit cannot be split any further
+            raise oom
+        from .. import engine
+        for n in grp:
+            if n not in done and not _calibrated_and_freed(self.wrapped_modules[n]):
+                forget_caches(self.wrapped_modules[n])
+        engine.release_workspace()
+        torch.cuda.empty_cache()
+        budget //= 2
+        print(f"[ptq4vit_amd] out of memory with {len(grp)} modules resident: retrying with a cache budget of {budget >> 30} GiB")
+        left = [n for n in grp if not _calibrated_and_freed(self.wrapped_modules[n])]
+        left += [n for g in groups for n in g]
+        return self._plan(cal, left, budget), budget
+
+    def _exchange(self, cal):
+        """Intervals to every rank, and every module's search time of this calibration (of this world size) with the network: the
+        next calibration's LPT order and owner costs.  Returns the seconds of the interval exchange."""
+        t_ex = 0.0
+        mine_ms = dict(getattr(self, "_module_ms", {}))
+        if cal.world > 1 and not self.sequential:
+            t1 = time.time()
+            shard.exchange_intervals(self.wrapped_modules, cal.owner)
+            t_ex = time.time() - t1          # includes waiting for the slowest rank's search (the collective is the barrier)
+            parts = [None] * cal.world
+            shard.dist.all_gather_object(parts, mine_ms)                 # a few hundred floats: next calibration's LPT costs
+            mine_ms = {k: v for part in parts for k, v in (part or {}).items()}
+        if mine_ms:          # replaced, not merged: the table describes ONE calibration (of this world size), gathered from all ranks
+            self.net.__dict__["_p4v_module_ms"] = {"world": cal.world, "ms": dict(mine_ms)}
+        return t_ex

@@ -419,7 +419,7 @@ def test_graph_capture_equals_eager_capture(model, side, kw):
 
 def test_fresh_networks_replay_the_graph_of_their_architecture_with_their_own_weights(monkeypatch):
     """Round 6: the sub-batch passes of a FRESH network object replay the HIP graph recorded for its architecture on a private copy
-    (utils/quant_calib.py, _arch_shadow) after its parameters have been copied into the graph's storage.  Three networks of one
+    (utils/capture_graph.py, arch_shadow) after its parameters have been copied into the graph's storage.  Three networks of one
     architecture with DIFFERENT weights: the third one's captured tensors -- taken through the architecture's graph, which was
     recorded with the second one's weights -- are bit-identical to its own eager capture."""
     import contextlib, io
@@ -455,15 +455,62 @@ def test_fresh_networks_replay_the_graph_of_their_architecture_with_their_own_we
         return cap, bool(net.__dict__.get("_p4v_capture_graphs")) and net.__dict__.get("_p4v_capture_shadow") is None
 
     capture(1, True)                                  # first sighting of the architecture: eager
-    assert not any("net" in r and r["net"] is not None for r in HessianQuantCalibrator._ARCH.values())
+    assert not any(r.net is not None for r in HessianQuantCalibrator._ARCH.values())
     capture(2, True)                                  # second sighting: the shadow and its graph are built (weights of seed 2)
-    assert any(r.get("lanes") for r in HessianQuantCalibrator._ARCH.values())
+    assert any(r.lanes for r in HessianQuantCalibrator._ARCH.values())
     got, own = capture(3, True)                       # a third network, other weights, through the architecture's graph
     assert not own                                    # (no graph of its own was recorded)
     want, _ = capture(3, False)                       # its own eager passes
     for n in want:
         for a, b in zip(got[n], want[n]):
             assert a.shape == b.shape and torch.equal(a, b), n
+    HessianQuantCalibrator._ARCH.clear()
+
+
+def test_one_network_graph_serves_another_image_count_and_one_lane():
+    """One network's capture graph under three replays: 8 images at batch_size=2, then the first 4 of them (the cache layout kept
+    with the graph was made for 4 sub-batches and is rebuilt for 2), then 8 again on one lane.  Each capture is bit-identical to
+    the eager capture of the same images."""
+    import contextlib, io
+    from ptq4vit_amd.configs import PTQ4ViT
+    from ptq4vit_amd.utils import models, net_wrap
+    from ptq4vit_amd.utils.quant_calib import HessianQuantCalibrator
+
+    class L:
+        def __init__(self, x):
+            self.x, self.batch_size = x, x.shape[0]
+
+        def __iter__(self):
+            yield self.x, None
+
+    dev = torch.device("cuda:0")
+    x = torch.randn(8, 3, 64, 64, generator=torch.Generator().manual_seed(5)).to(dev)
+    net = models.get_net("vit_tiny_patch16_224", seed=1, device=dev, img_size=64, patch_size=16, embed_dim=96, depth=2,
+                         num_heads=3, num_classes=10)
+    with contextlib.redirect_stdout(io.StringIO()):
+        wrapped = net_wrap.wrap_modules_in_net(net, PTQ4ViT)
+
+    def capture(images, **attrs):
+        cal = HessianQuantCalibrator(net, wrapped, L(images), sequential=False, batch_size=2)
+        for k, v in attrs.items():
+            setattr(cal, k, v)
+        cal._capture(list(wrapped), cal._raw_pred_softmax(), True)
+        torch.cuda.synchronize()
+        cap = {}
+        for n, m in wrapped.items():
+            ri = m.raw_input if isinstance(m.raw_input, list) else [m.raw_input]
+            cap[n] = [t.clone() for t in ri] + [m.raw_out.clone(), m.raw_grad.clone()]
+        return cap
+
+    HessianQuantCalibrator._ARCH.clear()
+    eager = {8: capture(x, use_graph=False), 4: capture(x[:4], use_graph=False)}
+    assert not net.__dict__.get("_p4v_capture_graphs")
+    for n_img, attrs in ((8, {}), (4, {}), (8, dict(capture_lanes=1))):
+        got = capture(x[:n_img], use_graph=True, **attrs)
+        assert len(net.__dict__["_p4v_capture_graphs"]) == 1
+        for n in eager[n_img]:
+            for a, b in zip(got[n], eager[n_img][n]):
+                assert a.shape == b.shape and torch.equal(a, b), (n_img, attrs, n)
     HessianQuantCalibrator._ARCH.clear()
 
 
