@@ -106,6 +106,13 @@ struct Arena {
     }
     bool ok() const { return dry || off + top <= cap; }
 };
+// gives back, at the end of its scope, what was taken from the bump region since (the peak keeps what it reached)
+struct ArenaMark {
+    Arena& a;
+    const size_t off;
+    explicit ArenaMark(Arena& a_) : a(a_), off(a_.off) {}
+    ~ArenaMark() { a.off = off; }
+};
 
 // ---- optional per-launch timing of the sweep kernels (bench.py roofline) -----------------------
 // Per CALLING THREAD: a thread that enabled timing (p4v_stats_enable) gets an event pair around every sweep launch
@@ -570,10 +577,14 @@ template <typename Tensors> Tensors grad_by_metric(Tensors t, int metric) {
 }
 
 // ---- launch helpers ---------------------------------------------------------------------------
+// `empty_is_zero`: a block of nothing but padding decodes to 0 (the reference pads with zeros) -- the running maxima start at
+// enc(+0.0f), the bit pattern of -0.0f, instead of at "nothing seen" (which decodes to NaN)
 int launch_absmax(Ctx& c, const float* src, const long (&st)[4], int D0, int D1, int R, int C, int nV, int nH,
-                  int crb_r, int crb_c, int signed_max, unsigned* out) {
+                  int crb_r, int crb_c, int signed_max, unsigned* out, bool empty_is_zero = false) {
     if (c.dry) return 0;
-    CHK(q_fill(c, out, 0, sizeof(unsigned) * (size_t)D1 * nV * nH));  // 0 < enc(x) for every float x
+    const int n = D1 * nV * nH;
+    if (empty_is_zero) CHK(enqueue(c, KERN(FillParams, k_fill_f32), dim3(cdiv(n, 256)), dim3(256), 0, FillParams{reinterpret_cast<float*>(out), -0.0f, n}));
+    else CHK(q_fill(c, out, 0, sizeof(unsigned) * (size_t)n));  // 0 < enc(x) for every float x
     AbsMaxParams p{src, st[0], st[1], st[2], st[3], D0, D1, R, C, nV, nH, crb_r, crb_c, 0, signed_max, out};
     p.row_tile = std::max(1, std::min(crb_r, std::max(1, 8192 / std::max(1, std::min(crb_c, C)))));
     const int tiles_per_v = cdiv(crb_r, p.row_tile);
@@ -2643,6 +2654,38 @@ struct SearchRounds {
     int32_t* best_of(int round, int which) const { return best ? best + slot(round, which) * ld : nullptr; }
 };
 
+// One side of a module's alternating search: its Stage bit (0: the call has no such side), its pass memo, the device vectors the
+// memo keys on and the ones it restores / records, and run(round), which builds and runs the side's passes of one round.
+struct SearchSide {
+    int bit;
+    MemoSide memo;
+    DevVecs key, val;
+    std::function<int(int)> run;
+    SearchSide(int bit_, bool memo_on, const DevVecs& key_, const DevVecs& val_, std::function<int(int)> run_)
+        : bit(bit_), key(key_), val(val_), run(std::move(run_)) { memo.on = memo_on; }
+};
+// The alternation of Linear, MatMul and Conv: for round, for side: restore the memo, run the side's passes unless it hit, record.
+// `host` (Linear; null: the key is read back): host copies of the two values, host[1 - s] the key of side s.
+// The form is "record whenever the restore did not hit", whether or not the call's mask has the side's bit.  That is also "record
+// only after the passes ran", the form the MatMul B side and both Conv sides had: a memo that is on implies Stage::full()
+// (SearchRounds::memo_on), so every side that has a memo switched on has its bit in the mask, and the mask test and the record
+// commute; with the memo off record() only invalidates the caller's host copy -- nothing without `host`, and with it what Linear
+// always did for a side that may have moved its value.  For the same reason it does not matter whether the mask is tested
+// before or after restore(): with the memo off restore() does nothing.  A side with bit 0 (Conv's activations with a_bit >= 32)
+// has its memo off and never runs.  A run() that ends a granular call early with 0 (p4v_debug_sos_sweep) is the call's only pass.
+int search_rounds(Ctx& c, const SearchRounds& R, const Stage& sg, SearchSide (&sides)[2], HostCopy* host) {
+    for (int round = 0; round < R.n_rounds; ++round)
+        for (int s = 0; s < 2; ++s) {
+            SearchSide& sd = sides[s];
+            bool hit = false;
+            CHK(sd.memo.restore(c, sd.key, host ? &host[1 - s] : nullptr, sd.val, host ? &host[s] : nullptr, &hit));
+            if (hit) continue;
+            if (sg.mask & sd.bit) CHK(sd.run(round));
+            CHK(sd.memo.record(c, sd.val, host ? &host[s] : nullptr));
+        }
+    return 0;
+}
+
 PackParams pack2d(const float* src, long rows, long cols, long ld) {
     PackParams p{};
     p.src = src; p.s_z = 0; p.s_r = ld; p.s_k = 1; p.Z = 1; p.R = (int)rows; p.K = (int)cols;
@@ -2972,27 +3015,31 @@ struct LinearCall {
         return 0;
     }
 
-    // One side of one round: the memo, then the side's block steps.
-    // With n_H > 1 the weight search is a coordinate descent over the column blocks: block h is swept with the other
-    // blocks at the interval ENTERING the pass (linear.py:468), so its result also depends on w_iv, not only on a_iv
-    // (same for n_a > 1 and the activation search).  The memo keys on the counterpart interval alone and is therefore
-    // only used where that is the whole input of the pass (`memo.on`: this side has ONE block).
-    int search_side(int side, int round, MemoSide& memo, HostCopy* host) {
+    // One side of one round: the side's block steps (`memo_on`: the side's pass memo, see memo_of).
+    int side_passes(int side, int round, bool memo_on) {
         const bool ws = side == 0;
         const int nblk = ws ? nH : nA;
-        const DevVecs key = ws ? DevVecs(t.a_iv, nA) : DevVecs(t.w_iv, nV * nH), val = ws ? DevVecs(t.w_iv, nV * nH) : DevVecs(t.a_iv, nA);
-        bool hit = false;
-        CHK(memo.restore(c, key, &host[1 - side], val, &host[side], &hit));      // (key: just read back / written by the last pass)
-        for (int blk = 0; blk < nblk && !hit && (sg.mask & (ws ? ST_S1 : ST_S2)); ++blk) {
+        for (int blk = 0; blk < nblk; ++blk) {
             if (only_blk >= 0 && blk != only_blk) continue;
             if (segcos) { Pass ps = seg_cos_pass(side, round, blk); CHK(run_pass(c, ps)); continue; }
             const float* cands = ws ? w_cands : a_cands;
             if (general && nblk > 1) { CHK(mix_candidates(side, blk)); cands = ws ? w_mix : a_mix; }
-            Pass ps = search_pass(side, round, blk, cands, memo.on);
+            Pass ps = search_pass(side, round, blk, cands, memo_on);
             if (!ws && twin && wt_mode <= 1) CHK(fold_negative_plane(ps));
             CHK(run_pass_pruned(c, ps));
         }
-        return hit ? 0 : memo.record(c, val, &host[side]);
+        return 0;
+    }
+    // With n_H > 1 the weight search is a coordinate descent over the column blocks: block h is swept with the other
+    // blocks at the interval ENTERING the pass (linear.py:468), so its result also depends on w_iv, not only on a_iv
+    // (same for n_a > 1 and the activation search).  The memo keys on the counterpart interval alone (just read back / written by
+    // the last pass: search_rounds takes the host copies) and is therefore only used where that is the whole input of the pass:
+    // the side has ONE block.
+    bool memo_of(int side) const { return rounds.memo_on && (side == 0 ? nH : nA) == 1; }
+    SearchSide search_side(int side) {
+        const DevVecs w(t.w_iv, nV * nH), a(t.a_iv, nA);
+        const bool on = memo_of(side);
+        return SearchSide(side == 0 ? ST_S1 : ST_S2, on, side == 0 ? a : w, side == 0 ? w : a, [this, side, on](int round) { return side_passes(side, round, on); });
     }
 };
 
@@ -3010,9 +3057,7 @@ int linear_impl(const p4v_linear_desc* d, const LinearTensors& t, const Stage& s
     if (!sg.searches()) return 0;
     const SearchRounds& R = L.rounds;
     MirrorScope mirrors(c, R.memo_on, t.w_iv, t.a_iv);
-    MemoSide memo[2];
-    memo[0].on = R.memo_on && L.nH == 1;
-    memo[1].on = R.memo_on && L.nA == 1;
+    SearchSide sides[2] = {L.search_side(0), L.search_side(1)};
     HostCopy host[2];                            // host copies of w_iv / a_iv, when a pass just moved them
     if (sg.full()) {
         // The 100 candidate planes of the weights (8.5 GB per ViT-B calibration over its 48 Linear layers) need the weights and
@@ -3026,9 +3071,7 @@ int linear_impl(const p4v_linear_desc* d, const LinearTensors& t, const Stage& s
         CHK(L.init_side(1));
     }
     if (L.segcos) CHK(enqueue(c, KERN(NchwRowsParams, k_nchw_to_rows), dim3(cdiv(L.N, 32), cdiv(L.M, 32), 1), dim3(256), 0, NchwRowsParams{t.O, L.M, L.N, L.Ot}));
-    for (int round = 0; round < R.n_rounds; ++round)
-        for (int side = 0; side < 2; ++side) CHK(L.search_side(side, round, memo[side], host));
-    return 0;
+    return search_rounds(c, R, sg, sides, host);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3180,7 +3223,18 @@ struct MatMulTensors {
     float* scores = nullptr; int32_t* best = nullptr;           // optional score tables / selections
     float* fwd_out = nullptr;                                   // ST_FWD: the destination [Z][M][N]
 };
-int matmul_blocks_impl(const p4v_matmul_desc* d, const MatMulBlocks& mb, const MatMulTensors& t, const Stage& sg, Ctx& c);
+// The argument checks of every matmul_impl call, with or without sub-blocks (the block counts are checked after them:
+// MatMulBlocksCall::build)
+int matmul_check(const p4v_matmul_desc* d, const MatMulTensors& t, const Stage& sg, const Ctx& c) {
+    if (d->batch * d->heads <= 0 || d->M <= 0 || d->K <= 0 || d->N <= 0 || d->eq_n <= 0) return fail(P4V_ERR_INVALID, "matmul: non-positive dimension");
+    if (d->A_bit > 8 || d->B_bit > 8 || d->A_bit < 2 || d->B_bit < 2) return fail(P4V_ERR_UNSUPPORTED, "matmul: bit widths 2..8 supported");
+    int epi, wt_mode;
+    metric_epi(d->metric, &epi, &wt_mode);
+    if (wt_mode == 1 && !t.G && sg.searches() && !c.dry) return fail(P4V_ERR_INVALID, "matmul: hessian metric needs raw_grad");
+    // the split: written by the split search, read by the B search and the forward; the initialisation alone does without
+    if (d->sos && !t.split && (sg.searches() || sg.forward()) && !c.dry) return fail(P4V_ERR_INVALID, "matmul: sos needs d_split");
+    return 0;
+}
 
 // One head-wise matmul_impl call: geometry, workspace and the builders of its passes.  Sides: 0 = the A search (with sos: the
 // split search), 1 = the B search.
@@ -3205,20 +3259,14 @@ struct MatMulCall {
 
     MatMulCall(Ctx& c_, const p4v_matmul_desc* d_, const MatMulTensors& t_, const Stage& sg_) : c(c_), d(d_), t(grad_by_metric(t_, d_->metric)), sg(sg_) {}
 
-    // argument checks and geometry
-    int build() {
+    // geometry of a call that passed matmul_check
+    void build() {
         H = d->heads; Z = d->batch * d->heads; M = d->M; K = d->K; N = d->N;
-        if (Z <= 0 || M <= 0 || K <= 0 || N <= 0 || d->eq_n <= 0) return fail(P4V_ERR_INVALID, "matmul: non-positive dimension");
-        if (d->A_bit > 8 || d->B_bit > 8 || d->A_bit < 2 || d->B_bit < 2) return fail(P4V_ERR_UNSUPPORTED, "matmul: bit widths 2..8 supported");
         Aq = 1 << (d->A_bit - 1); Bq = 1 << (d->B_bit - 1);
         metric_epi(d->metric, &epi, &wt_mode);
         cosm = epi == EPI_COS;
-        if (wt_mode == 1 && !t.G && sg.searches() && !c.dry) return fail(P4V_ERR_INVALID, "matmul: hessian metric needs raw_grad");
-        // the split: written by the split search, read by the B search and the forward; the initialisation alone does without
-        if (d->sos && !t.split && (sg.searches() || sg.forward()) && !c.dry) return fail(P4V_ERR_INVALID, "matmul: sos needs d_split");
         ncand = d->eq_n + 1;
         rounds = SearchRounds(sg, d->search_round, !(d->reserved & RSV_NO_MEMO), d->eq_n, H, c, t.scores, t.best);
-        return 0;
     }
     int workspace() {
         enc_A = c.ws.get<unsigned>(H);
@@ -3387,54 +3435,40 @@ struct MatMulCall {
         ps.prunable = !cosm && ps.i8 && !(d->reserved & RSV_NO_PRUNE); ps.scache = &slice; ps.host_sync_ok = rounds.memo_on;
         return ps;
     }
-};
-
-int matmul_impl(const p4v_matmul_desc* d, const MatMulTensors& t, const Stage& sg, Ctx& c, const MatMulBlocks& mb = MatMulBlocks{}) {
-    MatMulCall m(c, d, t, sg);
-    CHK(m.build());
-    cvt_bias(c);     // (first call of the process: probe the conversion quant16_sat8 relies on)
-    CHK(q_wait_inputs(c));     // (inside a group with a "capture done" event: everything below reads captured tensors)
-    // row / column sub-blocks: the K-segmented kernel family; with all four block counts 1 nothing below changes
-    if (mb.any()) return matmul_blocks_impl(d, mb, t, sg, c);
-    CHK(m.workspace());
-    CHK(m.init());
-    if (sg.forward()) { Pass fp = m.forward_pass(); return run_pass(c, fp); }
-    if (!sg.searches()) return 0;
-    CHK(m.upload_splits());
-    const SearchRounds& R = m.rounds;
-    MirrorScope mirrors(c, R.memo_on, t.A_iv, t.B_iv, d->sos ? t.split : nullptr);
-    const int H = m.H, nAiv = d->sos ? 1 : H;
+    // The passes of one side of one round.  The A side has three variants: the head-wise A search; with sos the split search on
+    // k_sos_split, or on fp32 operands where that kernel has no instance.
+    int side_passes(int side, int round) {
+        if (side == 1) { Pass ps = B_pass(round); return run_pass_pruned(c, ps); }
+        if (!d->sos) { Pass ps = A_pass(round); return run_pass_pruned(c, ps); }
+        if (sos_split_ok(M, K, N, cosm)) {
+            SosSplitJob j = split_job(round);
+            if (g_sos_debug) return c.grp || c.dry ? fail(P4V_ERR_INVALID, "p4v_debug_sos_sweep: not inside a group") : run_sos_debug_sweep(c, j, *g_sos_debug);
+            return run_sos_split_pruned(c, j);
+        }
+        Pass ps = split_pass_f32(round);
+        return run_pass(c, ps);
+    }
     // the A search is a function of B's interval; with sos it is the split search against the RAW B: a function of nothing ->
     // always a hit after round 1, its value the split and the A interval derived from it
-    MemoSide memo_A, memo_B;
-    memo_A.on = memo_B.on = R.memo_on;
-    const DevVecs key_A = d->sos ? DevVecs() : DevVecs(t.B_iv, H), val_A = d->sos ? DevVecs(t.split, 1, t.A_iv, 1) : DevVecs(t.A_iv, nAiv);
-    const DevVecs key_B(t.A_iv, nAiv), val_B(t.B_iv, H);
-    for (int round = 0; round < R.n_rounds; ++round) {
-        bool hit = false;
-        CHK(memo_A.restore(c, key_A, nullptr, val_A, nullptr, &hit));
-        if (hit || !(sg.mask & ST_S1)) {
-        } else if (!d->sos) {
-            Pass ps = m.A_pass(round);
-            CHK(run_pass_pruned(c, ps));
-        } else if (sos_split_ok(m.M, m.K, m.N, m.cosm)) {
-            SosSplitJob j = m.split_job(round);
-            if (g_sos_debug) return c.grp || c.dry ? fail(P4V_ERR_INVALID, "p4v_debug_sos_sweep: not inside a group") : run_sos_debug_sweep(c, j, *g_sos_debug);
-            CHK(run_sos_split_pruned(c, j));
-        } else {
-            Pass ps = m.split_pass_f32(round);
-            CHK(run_pass(c, ps));
-        }
-        if (!hit) CHK(memo_A.record(c, val_A, nullptr));   // (a memo that is on implies a full run)
-        CHK(memo_B.restore(c, key_B, nullptr, val_B, nullptr, &hit));
-        if (!hit && (sg.mask & ST_S2)) {
-            Pass ps = m.B_pass(round);
-            CHK(run_pass_pruned(c, ps));
-            CHK(memo_B.record(c, val_B, nullptr));
-        }
+    SearchSide search_side(int side) {
+        const int nAiv = d->sos ? 1 : H;
+        const DevVecs A_key = d->sos ? DevVecs() : DevVecs(t.B_iv, H), A_val = d->sos ? DevVecs(t.split, 1, t.A_iv, 1) : DevVecs(t.A_iv, nAiv);
+        auto run = [this, side](int round) { return side_passes(side, round); };
+        return side == 0 ? SearchSide(ST_S1, rounds.memo_on, A_key, A_val, run) : SearchSide(ST_S2, rounds.memo_on, DevVecs(t.A_iv, nAiv), DevVecs(t.B_iv, H), run);
     }
-    return 0;
-}
+    // the head-wise call, after matmul_impl's checks and its wait for the inputs
+    int run() {
+        build();
+        CHK(workspace());
+        CHK(init());
+        if (sg.forward()) { Pass fp = forward_pass(); return run_pass(c, fp); }
+        if (!sg.searches()) return 0;
+        CHK(upload_splits());
+        MirrorScope mirrors(c, rounds.memo_on, t.A_iv, t.B_iv, d->sos ? t.split : nullptr);
+        SearchSide sides[2] = {search_side(0), search_side(1)};
+        return search_rounds(c, rounds, sg, sides, nullptr);
+    }
+};
 
 // ---- p4v_attn_quant_forward: matmul1 -> * scale -> softmax -> matmul2's A quantiser -> matmul2, int8 in between (the FusedChain above)
 // The producer is k_attn_qk on q and k^T: it writes matmul2's row plane(s) ([Z][Mp][Kp]: the tiled sweeps step Mp * Kp per z, the
@@ -3464,8 +3498,10 @@ int attn_chain(const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulTens
     if (!(d->scale == d->scale)) return fail(P4V_ERR_INVALID, "attn: scale is NaN");
     const Stage sg{ST_FWD};
     MatMulCall m1(c, d1, t1, sg), m2(c, d2, t2, sg);
-    CHK(m1.build());
-    CHK(m2.build());
+    CHK(matmul_check(d1, t1, sg, c));
+    m1.build();
+    CHK(matmul_check(d2, t2, sg, c));
+    m2.build();
     cvt_bias(c);     // (first call of the process: probe the conversion quant16_sat8 relies on)
     CHK(q_wait_inputs(c));
     const int Z = m1.Z, H = m1.H, M = m1.M, N = m1.N, K1 = m1.K;
@@ -3514,104 +3550,158 @@ int wattn_impl(const WattnCall* d, const MatMulTensors& t1, const MatMulTensors&
 // that block's scale only, every other block on the interval entering the step, the score the full-output score per head; each
 // step is one sweep of the whole operand (no pruning, no pass memo: first version).  Score tables [round][step][eq_n][heads],
 // steps = A blocks then B blocks (split-of-softmax: the 20-row split table, then B blocks).
-int matmul_blocks_impl(const p4v_matmul_desc* d, const MatMulBlocks& mb, const MatMulTensors& t_, const Stage& sg, Ctx& c) {
-    const MatMulTensors t = grad_by_metric(t_, d->metric);
-    const int H = d->heads, Z = d->batch * d->heads, M = d->M, K = d->K, N = d->N;
-    const int nVA = mb.nVA, nHA = mb.nHA, nVB = mb.nVB, nHB = mb.nHB;
-    if (nVA < 1 || nHA < 1 || nVB < 1 || nHB < 1) return fail(P4V_ERR_INVALID, "matmul: non-positive block count");
-    if (nVA > 8 || nHA > 8 || nVB > 8 || nHB > 8) return fail(P4V_ERR_UNSUPPORTED, "matmul: sub-blocks up to n_V, n_H = 8 are implemented on the GPU");
-    if (d->sos && (nVA != 1 || nHA != 1)) return fail(P4V_ERR_INVALID, "matmul: the split-of-softmax operand has no sub-blocks (matmul.py:586-588)");
-    if (d->A_bit < 2 || d->B_bit < 2) return fail(P4V_ERR_UNSUPPORTED, "matmul: bit widths 2..8 supported");
-    int epi, wt_mode;
-    metric_epi(d->metric, &epi, &wt_mode);
-    if (epi == EPI_COS && sg.searches())
-        return fail(P4V_ERR_UNSUPPORTED, "matmul: the cosine metric with row/column sub-blocks (n_V, n_H > 1) is not implemented on the GPU");
-    SegPlan g{};
-    g.batch = d->batch; g.H = H; g.M = M; g.K = K; g.N = N;
-    g.nVA = nVA; g.nHA = nHA; g.nVB = nVB; g.nHB = nHB;
-    g.crA = cdiv(M, nVA); g.ccA = cdiv(K, nHA); g.crB = cdiv(K, nVB); g.ccB = cdiv(N, nHB);
-    g.A = t.A; g.B = t.B;
-    for (int i = 0; i < 4; ++i) { g.a_st[i] = d->a_stride[i]; g.b_st[i] = d->b_stride[i]; }
-    g.Aq = 1 << (d->A_bit - 1); g.Bq = 1 << (d->B_bit - 1); g.sos = d->sos != 0;
-    CHK(seg_cut_k(g, "matmul"));
-    const int nA = d->sos ? 1 : H * nVA * nHA, nB = H * nVB * nHB, ncand = d->eq_n + 1;
-    unsigned* enc_A = c.ws.get<unsigned>((size_t)H * nVA * nHA);
-    unsigned* enc_B = c.ws.get<unsigned>((size_t)nB);
-    float* A_cands_ws = c.ws.get<float>((size_t)ncand * H * nVA * nHA);
-    float* B_cands_ws = c.ws.get<float>((size_t)ncand * nB);
-    if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small");
-    g.ivA = t.A_iv; g.ivB = t.B_iv; g.split = t.split;
+struct MatMulBlocksCall {
+    // one step of a round: side 1 / 2 = block (v, h) of A / B; side 0 = the split search of the split-of-softmax class, which
+    // knows no blocks; the step's slot of the [round][step] tables
+    struct Step { int side, v, h; float* scores; int32_t* best; };
+    Ctx& c;
+    const p4v_matmul_desc* d;
+    const MatMulBlocks mb;
+    const MatMulTensors t;
+    const Stage& sg;
+    const Stage split_stage{ST_S1};                   // the mode of the split step's head-wise call
+    int H = 0, Z = 0, M = 0, K = 0, N = 0;            // heads, batch x heads, the GEMM of one head
+    int nVA = 1, nHA = 1, nVB = 1, nHB = 1;           // row / column blocks of A and of B
+    int nA = 0, nB = 0;                               // intervals per operand: heads x n_V x n_H (sos: the scalar A interval)
+    int epi = 0, wt_mode = 0, ncand = 0;
+    SegPlan g{};                                      // the K-segmented view of both operands; step_pass sets its override fields
+    unsigned *enc_A = nullptr, *enc_B = nullptr;      // abs-max per block, order-preserving encoding
+    float *A_cands_ws = nullptr, *B_cands_ws = nullptr;       // candidate tables [eq_n + 1][heads][n_V][n_H], built by this call
+    SearchRounds rounds;                              // tables [round][step]
 
-    if (sg.forward()) {    // quant_forward (matmul.py:140-145; sos: 595-598): intervals / split are inputs
-        Pass fp{};
-        fp.seg = &g; fp.Z = Z; fp.K = K; fp.Mrows = M; fp.Ncols = N; fp.i8 = true; fp.twin = g.sos;
-        fp.epi = EPI_FWD; fp.eq_n = 1; fp.store_out = t.fwd_out;
-        return run_pass(c, fp);
+    MatMulBlocksCall(Ctx& c_, const p4v_matmul_desc* d_, const MatMulBlocks& mb_, const MatMulTensors& t_, const Stage& sg_)
+        : c(c_), d(d_), mb(mb_), t(grad_by_metric(t_, d_->metric)), sg(sg_) {}
+
+    // the checks of the block counts (after matmul_check), the segment plan
+    int build() {
+        H = d->heads; Z = d->batch * d->heads; M = d->M; K = d->K; N = d->N;
+        nVA = mb.nVA; nHA = mb.nHA; nVB = mb.nVB; nHB = mb.nHB;
+        if (nVA < 1 || nHA < 1 || nVB < 1 || nHB < 1) return fail(P4V_ERR_INVALID, "matmul: non-positive block count");
+        if (nVA > 8 || nHA > 8 || nVB > 8 || nHB > 8) return fail(P4V_ERR_UNSUPPORTED, "matmul: sub-blocks up to n_V, n_H = 8 are implemented on the GPU");
+        if (d->sos && (nVA != 1 || nHA != 1)) return fail(P4V_ERR_INVALID, "matmul: the split-of-softmax operand has no sub-blocks (matmul.py:586-588)");
+        if (d->A_bit < 2 || d->B_bit < 2) return fail(P4V_ERR_UNSUPPORTED, "matmul: bit widths 2..8 supported");
+        metric_epi(d->metric, &epi, &wt_mode);
+        if (epi == EPI_COS && sg.searches())
+            return fail(P4V_ERR_UNSUPPORTED, "matmul: the cosine metric with row/column sub-blocks (n_V, n_H > 1) is not implemented on the GPU");
+        g.batch = d->batch; g.H = H; g.M = M; g.K = K; g.N = N;
+        g.nVA = nVA; g.nHA = nHA; g.nVB = nVB; g.nHB = nHB;
+        g.crA = cdiv(M, nVA); g.ccA = cdiv(K, nHA); g.crB = cdiv(K, nVB); g.ccB = cdiv(N, nHB);
+        g.A = t.A; g.B = t.B;
+        for (int i = 0; i < 4; ++i) { g.a_st[i] = d->a_stride[i]; g.b_st[i] = d->b_stride[i]; }
+        g.Aq = 1 << (d->A_bit - 1); g.Bq = 1 << (d->B_bit - 1); g.sos = d->sos != 0;
+        g.ivA = t.A_iv; g.ivB = t.B_iv; g.split = t.split;
+        CHK(seg_cut_k(g, "matmul"));
+        nA = d->sos ? 1 : H * nVA * nHA; nB = H * nVB * nHB; ncand = d->eq_n + 1;
+        const int steps = (d->sos ? 1 : nVA * nHA) + nVB * nHB;
+        rounds = SearchRounds(sg, d->search_round, !(d->reserved & RSV_NO_MEMO), d->eq_n, H, c, t.scores, t.best, steps);
+        return 0;
     }
-    if (sg.inits()) {
-        // min-max per block; a block of nothing but padding gets 0 (the reference pads with zeros): the running maxima start at
-        // enc(+0.0f) -- the bit pattern of -0.0f --, not at k_absmax's "nothing seen" (which decodes to NaN)
-        auto absmax = [&](const float* src, const int64_t* st, int R, int C, int nV, int nH, int crb_r, int crb_c, unsigned* out) -> int {
-            if (c.dry) return 0;
-            const int n = H * nV * nH;
-            CHK(enqueue(c, KERN(FillParams, k_fill_f32), dim3(cdiv(n, 256)), dim3(256), 0, FillParams{reinterpret_cast<float*>(out), -0.0f, n}));
-            AbsMaxParams p{src, (long)st[0], (long)st[1], (long)st[2], (long)st[3], d->batch, H, R, C, nV, nH, crb_r, crb_c, 0, 0, out};
-            p.row_tile = std::max(1, std::min(crb_r, std::max(1, 8192 / std::max(1, std::min(crb_c, C)))));
-            return enqueue(c, KERN(AbsMaxParams, k_absmax), dim3(cdiv(crb_r, p.row_tile) * nV * nH, H, d->batch), dim3(256), 0, p);
-        };
+    int workspace() {
+        enc_A = c.ws.get<unsigned>((size_t)H * nVA * nHA);
+        enc_B = c.ws.get<unsigned>((size_t)nB);
+        A_cands_ws = c.ws.get<float>((size_t)ncand * H * nVA * nHA);
+        B_cands_ws = c.ws.get<float>((size_t)ncand * nB);
+        if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small");
+        return 0;
+    }
+    // min-max per block (a block of nothing but padding gets the interval 0), the intervals, their candidate tables
+    int init() {
+        if (!sg.inits()) return 0;
+        const long sa[4] = {d->a_stride[0], d->a_stride[1], d->a_stride[2], d->a_stride[3]};
+        const long sb[4] = {d->b_stride[0], d->b_stride[1], d->b_stride[2], d->b_stride[3]};
         if (!d->sos) {
-            CHK(absmax(t.A, d->a_stride, M, K, nVA, nHA, g.crA, g.ccA, enc_A));
+            CHK(launch_absmax(c, t.A, sa, d->batch, H, M, K, nVA, nHA, g.crA, g.ccA, 0, enc_A, true));
             CHK(launch_interval(c, enc_A, nA, (float)(g.Aq - 0.5), d->init_layerwise, t.A_iv));
         }
-        CHK(absmax(t.B, d->b_stride, K, N, nVB, nHB, g.crB, g.ccB, enc_B));
+        CHK(launch_absmax(c, t.B, sb, d->batch, H, K, N, nVB, nHB, g.crB, g.ccB, 0, enc_B, true));
         CHK(launch_interval(c, enc_B, nB, (float)(g.Bq - 0.5), d->init_layerwise, t.B_iv));
         if (sg.searches()) {
             if (!d->sos) CHK(launch_cands(c, t.mult, t.A_iv, ncand, nA, A_cands_ws));
             CHK(launch_cands(c, t.mult, t.B_iv, ncand, nB, B_cands_ws));
         }
+        return 0;
     }
-    if (!sg.searches()) return 0;
-    // one block step: `side` 1 / 2 = A / B, candidates cands[c * cs + head * hs] of block (v, h)
-    auto step = [&](int side, int v, int h, const float* cands, int cs, int hs, float* so, int32_t* bo) -> int {
+    // quant_forward (matmul.py:140-145; sos: 595-598): intervals / split are inputs
+    Pass forward_pass() {
+        Pass fp{};
+        fp.seg = &g; fp.Z = Z; fp.K = K; fp.Mrows = M; fp.Ncols = N; fp.i8 = true; fp.twin = g.sos;
+        fp.epi = EPI_FWD; fp.eq_n = 1; fp.store_out = t.fwd_out;
+        return fp;
+    }
+    // The pass of one block step: `side` 1 / 2 = A / B, candidates cands[c * cs + head * hs] replacing the scale of block (v, h),
+    // every other block on the interval entering the step.
+    Pass step_pass(int side, int v, int h, const float* cands, int cs, int hs, float* scores, int32_t* best) {
         const int nV = side == 1 ? nVA : nVB, nH = side == 1 ? nHA : nHB;
-        if (v < 0 || v >= nV || h < 0 || h >= nH) return fail(P4V_ERR_INVALID, "matmul: block (%d, %d) outside the %d x %d blocks", v, h, nV, nH);
-        g.side = side; g.ov_v = v; g.ov_h = h; g.cands = cands; g.cand_cs = cs; g.cand_hs = hs;
+        g.side = side; g.ov_v = v; g.ov_h = h; g.cands = cands; g.cand_cs = cs; g.cand_hs = hs;     // the plan's override: this block
         Pass ps{};
         ps.seg = &g; ps.Z = Z; ps.K = K; ps.Mrows = M; ps.Ncols = N; ps.i8 = true; ps.twin = g.sos;
         ps.epi = epi; ps.wt_mode = wt_mode; ps.O = t.O; ps.G = t.G; ps.eq_n = d->eq_n;
         ps.j_mode = 2; ps.j_div = H; ps.nj = H; ps.norm = 1.0 / ((double)M * N);
         ps.cands = cands; ps.cand_cs = cs; ps.cand_js = hs; ps.cand_off = 0;
         ps.interval = (side == 1 ? t.A_iv : t.B_iv) + v * nH + h; ps.out_js = nV * nH; ps.out_off = 0;
-        ps.scores_out = so; ps.scores_out_ld = H; ps.best_out = bo;
+        ps.scores_out = scores; ps.scores_out_ld = H; ps.best_out = best;
+        return ps;
+    }
+    // granular: ONE block step on the caller's candidate table [eq_n + 1][heads]
+    int granular_step(int side, const float* cands) {
+        const int nV = side == 1 ? nVA : nVB, nH = side == 1 ? nHA : nHB;
+        if (mb.v < 0 || mb.v >= nV || mb.h < 0 || mb.h >= nH) return fail(P4V_ERR_INVALID, "matmul: block (%d, %d) outside the %d x %d blocks", mb.v, mb.h, nV, nH);
+        Pass ps = step_pass(side, mb.v, mb.h, cands, H, 1, t.scores, t.best);
         return run_pass(c, ps);
-    };
-    if (!sg.full()) {    // granular: ONE block step on the caller's candidate table [eq_n + 1][heads]
-        if (sg.mask & ST_S1) CHK(step(1, mb.v, mb.h, sg.cands1, H, 1, t.scores, t.best));
-        if (sg.mask & ST_S2) CHK(step(2, mb.v, mb.h, sg.cands2, H, 1, t.scores, t.best));
+    }
+    // the steps of a round: the A blocks (sos: the split search), then the B blocks, each in product(range(n_V), range(n_H)) order
+    std::vector<Step> steps(int round) const {
+        std::vector<Step> st;
+        auto add = [&](int side, int v, int h) { const int s = (int)st.size(); st.push_back({side, v, h, rounds.scores_of(round, s), rounds.best_of(round, s)}); };
+        if (d->sos) add(0, 0, 0);
+        else for (int v = 0; v < nVA; ++v) for (int h = 0; h < nHA; ++h) add(1, v, h);
+        for (int v = 0; v < nVB; ++v) for (int h = 0; h < nHB; ++h) add(2, v, h);
+        return st;
+    }
+    // The split search against the UNQUANTISED B (matmul.py:600-631) knows no blocks: the head-wise engine's pass, as a head-wise
+    // call in mode ST_S1 would make it.  A call of its own every round, as it always was: its tables, the split candidates and
+    // the slice cache start anew, and its workspace is given back at the end of the step.
+    int split_step(const Step& s) {
+        const ArenaMark mark(c.ws);
+        MatMulCall m(c, d, {.A = t.A, .B = t.B, .O = t.O, .G = t.G, .A_iv = t.A_iv, .split = t.split, .scores = s.scores, .best = s.best}, split_stage);
+        m.build();
+        CHK(q_wait_inputs(c));
+        CHK(m.workspace());
+        CHK(m.upload_splits());
+        return m.side_passes(0, 0);
+    }
+    int run_step(const Step& s) {
+        if (s.side == 0) return split_step(s);
+        const int nV = s.side == 1 ? nVA : nVB, nH = s.side == 1 ? nHA : nHB;
+        Pass ps = step_pass(s.side, s.v, s.h, (s.side == 1 ? A_cands_ws : B_cands_ws) + s.v * nH + s.h, H * nV * nH, nV * nH, s.scores, s.best);
+        return run_pass(c, ps);
+    }
+    // The call with sub-blocks, after matmul_impl's checks and its wait for the inputs.  The rounds are a plain loop over the
+    // steps: no side has a memo, and a round has more than two steps (search_rounds drives two memoised sides).
+    int run() {
+        CHK(build());
+        CHK(workspace());
+        if (sg.forward()) { Pass fp = forward_pass(); return run_pass(c, fp); }
+        CHK(init());
+        if (!sg.searches()) return 0;
+        if (!sg.full()) {
+            if (sg.mask & ST_S1) CHK(granular_step(1, sg.cands1));
+            if (sg.mask & ST_S2) CHK(granular_step(2, sg.cands2));
+            return 0;
+        }
+        for (int round = 0; round < rounds.n_rounds; ++round)
+            for (const Step& s : steps(round)) CHK(run_step(s));
         return 0;
     }
-    const int stepsA = d->sos ? 1 : nVA * nHA, steps = stepsA + nVB * nHB;
-    const SearchRounds tabs(sg, d->search_round, !(d->reserved & RSV_NO_MEMO), d->eq_n, H, c, t.scores, t.best, steps);   // tables [round][step]
-    for (int round = 0; round < d->search_round; ++round) {
-        int st = 0;
-        auto so = [&](int s) { return tabs.scores_of(round, s); };
-        auto bo = [&](int s) { return tabs.best_of(round, s); };
-        if (d->sos) {
-            // the split search against the UNQUANTISED B (matmul.py:600-631) knows no blocks: the head-wise engine's pass
-            const size_t mark = c.ws.off;
-            CHK(matmul_impl(d, {.A = t.A, .B = t.B, .O = t.O, .G = t.G, .A_iv = t.A_iv, .split = t.split, .scores = so(0), .best = bo(0)}, Stage{ST_S1}, c));
-            c.ws.off = mark;
-            st = 1;
-        } else {
-            for (int v = 0; v < nVA; ++v)
-                for (int h = 0; h < nHA; ++h, ++st)
-                    CHK(step(1, v, h, A_cands_ws + v * nHA + h, H * nVA * nHA, nVA * nHA, so(st), bo(st)));
-        }
-        for (int v = 0; v < nVB; ++v)
-            for (int h = 0; h < nHB; ++h, ++st)
-                CHK(step(2, v, h, B_cands_ws + v * nHB + h, nB, nVB * nHB, so(st), bo(st)));
-    }
-    return 0;
+};
+
+int matmul_impl(const p4v_matmul_desc* d, const MatMulTensors& t, const Stage& sg, Ctx& c, const MatMulBlocks& mb = MatMulBlocks{}) {
+    CHK(matmul_check(d, t, sg, c));     // (with sub-blocks too: before the checks of the block counts)
+    cvt_bias(c);     // (first call of the process: probe the conversion quant16_sat8 relies on)
+    CHK(q_wait_inputs(c));     // (inside a group with a "capture done" event: everything below reads captured tensors)
+    // row / column sub-blocks: the K-segmented kernel family; with all four block counts 1 the head-wise engine
+    if (mb.any()) return MatMulBlocksCall(c, d, mb, t, sg).run();
+    return MatMulCall(c, d, t, sg).run();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3620,42 +3710,69 @@ int matmul_blocks_impl(const p4v_matmul_desc* d, const MatMulBlocks& mb, const M
 // The device pointers of one conv_impl call are a Linear's: weight [oc][ic][kh][kw], bias [oc], x [b][ic][H][W], raw_out / raw_grad
 // [b][oc][fh][fw], intervals [oc] or [1] / [1].  There is no conv forward: fwd_out stays null.
 typedef LinearTensors ConvTensors;
-int conv_impl(const p4v_conv_desc* d, const ConvTensors& t_, const Stage& sg, Ctx& c) {
-    const ConvTensors t = grad_by_metric(t_, d->metric);
-    const int b = d->batch, ic = d->in_channels, H = d->height, Wd = d->width, oc = d->out_channels;
-    const int kh = d->kernel_h, kw = d->kernel_w;
-    if (kh <= 0 || kw <= 0 || d->stride_h <= 0 || d->stride_w <= 0 || d->pad_h < 0 || d->pad_w < 0 || d->dil_h <= 0 || d->dil_w <= 0)
-        return fail(P4V_ERR_INVALID, "conv: bad geometry");
-    // output size floor((size + 2 pad - dil (k - 1) - 1) / stride) + 1: the numerators are tested for their sign -- C division
-    // truncates toward zero, so a dilated kernel one larger than the padded image (numerator -1) would give 1 with stride >= 2
-    const int num_h = H + 2 * d->pad_h - d->dil_h * (kh - 1) - 1, num_w = Wd + 2 * d->pad_w - d->dil_w * (kw - 1) - 1;
-    if (b <= 0 || ic <= 0 || oc <= 0 || H <= 0 || Wd <= 0 || num_h < 0 || num_w < 0 || d->eq_n <= 0) return fail(P4V_ERR_INVALID, "conv: bad geometry");
-    const int fh = num_h / d->stride_h + 1, fw = num_w / d->stride_w + 1;
-    if (d->w_bit > 8 || d->w_bit < 2) return fail(P4V_ERR_UNSUPPORTED, "conv: w_bit 2..8 supported");
-    if (d->a_bit < 2) return fail(P4V_ERR_UNSUPPORTED, "conv: a_bit >= 2 supported (>= 32: unquantised input)");
-    const int L = fh * fw, K = ic * kh * kw, M = b * L;
-    const int wq = 1 << (d->w_bit - 1);
-    const bool aquant = d->a_bit < 32;
-    const int aq = aquant ? (1 << (d->a_bit - 1)) : 0;
-    if (aquant && !d->channelwise) return fail(P4V_ERR_UNSUPPORTED, "conv: the layer-wise class cannot search activations (reference conv.py:420 raises IndexError); use a_bit=32");
-    cvt_bias(c);     // (first call of the process: probe the conversion quant16_sat8 relies on)
-    CHK(q_wait_inputs(c));     // (inside a group with a "capture done" event: everything below reads captured tensors)
-    int epi, wt_mode;
-    metric_epi(d->metric, &epi, &wt_mode);
-    const bool cosm = epi == EPI_COS;
-    if (wt_mode == 1 && !t.G && sg.searches() && !c.dry) return fail(P4V_ERR_INVALID, "conv: hessian metric needs raw_grad");
-    if (cosm && aquant) return fail(P4V_ERR_UNSUPPORTED, "conv: cosine does not support the activation search (reference conv.py:505-506)");
-    const int nw = d->channelwise ? oc : 1;
-    const int ncand = d->eq_n + 1;
+// One conv_impl call: what build() derives from the descriptor, and the builders of its passes.  Sides: 0 = the weight search
+// (conv.py:526-557 / 365-396), 1 = the activation search (conv.py:559-589; the channel-wise class only).
+struct ConvCall {
+    Ctx& c;
+    const p4v_conv_desc* d;
+    const ConvTensors t;
+    const Stage& sg;
+    int b = 0, ic = 0, H = 0, Wd = 0, oc = 0, kh = 0, kw = 0;  // batch, input channels, image, output channels, kernel
+    int fh = 0, fw = 0;                               // output pixels per column / per row
+    int L = 0, K = 0, M = 0;                          // pixels of one output image, the im2col row ic x kh x kw, rows: batch x L
+    int nw = 1;                                       // weight intervals: one per output channel, or one
+    int wq = 0, aq = 0;                               // 2^(bit - 1) of the weights / the input (0: unquantised)
+    bool aquant = false;                              // a_bit < 32: the input is quantised and searched
+    int epi = 0, wt_mode = 0, ncand = 0;              // the metric's epilogue and weighting, rows of a candidate table
+    bool cosm = false;                                // cosine metric
+    bool prunable = false;                            // the weight search may be pruned like a Linear's (transpose_targets)
+    unsigned *enc_w = nullptr, *enc_a = nullptr;      // abs-max per interval, order-preserving encoding
+    float *w_cands_ws = nullptr, *a_cands_ws = nullptr;       // candidate tables built by this call ...
+    const float *w_cands = nullptr, *a_cands = nullptr;       // ... or the caller's (granular search)
+    float *Ot = nullptr, *Gt = nullptr;               // prunable: raw_out / raw_grad as rows of the im2col GEMM, [b * L][oc]
+    SearchRounds rounds;
+    PlaneCache plane_w, plane_a;                      // per side: the candidate-expanded plane, kept across rounds
+    SliceCache slice;                                 // the row slices of the pruned weight passes
 
-    unsigned* enc_w = c.ws.get<unsigned>(nw);
-    unsigned* enc_a = c.ws.get<unsigned>(1);
-    float* w_cands_ws = c.ws.get<float>((size_t)ncand * nw);
-    float* a_cands_ws = c.ws.get<float>(ncand);
-    const float* w_cands = sg.inits() ? w_cands_ws : sg.cands1;
-    const float* a_cands = sg.inits() ? a_cands_ws : sg.cands2;
-    if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small");
-    if (sg.inits()) {
+    ConvCall(Ctx& c_, const p4v_conv_desc* d_, const ConvTensors& t_, const Stage& sg_) : c(c_), d(d_), t(grad_by_metric(t_, d_->metric)), sg(sg_) {}
+
+    // argument checks, geometry, the tables' workspace
+    int build() {
+        b = d->batch; ic = d->in_channels; H = d->height; Wd = d->width; oc = d->out_channels; kh = d->kernel_h; kw = d->kernel_w;
+        if (kh <= 0 || kw <= 0 || d->stride_h <= 0 || d->stride_w <= 0 || d->pad_h < 0 || d->pad_w < 0 || d->dil_h <= 0 || d->dil_w <= 0)
+            return fail(P4V_ERR_INVALID, "conv: bad geometry");
+        // output size floor((size + 2 pad - dil (k - 1) - 1) / stride) + 1: the numerators are tested for their sign -- C division
+        // truncates toward zero, so a dilated kernel one larger than the padded image (numerator -1) would give 1 with stride >= 2
+        const int num_h = H + 2 * d->pad_h - d->dil_h * (kh - 1) - 1, num_w = Wd + 2 * d->pad_w - d->dil_w * (kw - 1) - 1;
+        if (b <= 0 || ic <= 0 || oc <= 0 || H <= 0 || Wd <= 0 || num_h < 0 || num_w < 0 || d->eq_n <= 0) return fail(P4V_ERR_INVALID, "conv: bad geometry");
+        fh = num_h / d->stride_h + 1; fw = num_w / d->stride_w + 1;
+        if (d->w_bit > 8 || d->w_bit < 2) return fail(P4V_ERR_UNSUPPORTED, "conv: w_bit 2..8 supported");
+        if (d->a_bit < 2) return fail(P4V_ERR_UNSUPPORTED, "conv: a_bit >= 2 supported (>= 32: unquantised input)");
+        L = fh * fw; K = ic * kh * kw; M = b * L;
+        wq = 1 << (d->w_bit - 1);
+        aquant = d->a_bit < 32;
+        aq = aquant ? (1 << (d->a_bit - 1)) : 0;
+        if (aquant && !d->channelwise) return fail(P4V_ERR_UNSUPPORTED, "conv: the layer-wise class cannot search activations (reference conv.py:420 raises IndexError); use a_bit=32");
+        cvt_bias(c);     // (first call of the process: probe the conversion quant16_sat8 relies on)
+        metric_epi(d->metric, &epi, &wt_mode);
+        cosm = epi == EPI_COS;
+        if (wt_mode == 1 && !t.G && sg.searches() && !c.dry) return fail(P4V_ERR_INVALID, "conv: hessian metric needs raw_grad");
+        if (cosm && aquant) return fail(P4V_ERR_UNSUPPORTED, "conv: cosine does not support the activation search (reference conv.py:505-506)");
+        nw = d->channelwise ? oc : 1;
+        ncand = d->eq_n + 1;
+        rounds = SearchRounds(sg, d->search_round, !(d->reserved & RSV_NO_MEMO), d->eq_n, nw, c, t.scores, t.best);
+        enc_w = c.ws.get<unsigned>(nw);
+        enc_a = c.ws.get<unsigned>(1);
+        w_cands_ws = c.ws.get<float>((size_t)ncand * nw);
+        a_cands_ws = c.ws.get<float>(ncand);
+        w_cands = sg.inits() ? w_cands_ws : sg.cands1;
+        a_cands = sg.inits() ? a_cands_ws : sg.cands2;
+        if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small");
+        return 0;
+    }
+    // interval initialisation of both operands and their candidate tables
+    int init() {
+        if (!sg.inits()) return 0;
         const long stw[4] = {0, 0, K, 1};
         CHK(launch_absmax(c, t.W, stw, 1, 1, oc, K, nw, 1, d->channelwise ? 1 : oc, K, 0, enc_w));
         CHK(launch_interval(c, enc_w, nw, (float)(wq - 0.5), d->init_layerwise, t.w_iv));
@@ -3666,22 +3783,25 @@ int conv_impl(const p4v_conv_desc* d, const ConvTensors& t_, const Stage& sg, Ct
             CHK(launch_cands(c, t.mult, t.w_iv, ncand, nw, w_cands_ws));
             CHK(launch_cands(c, t.mult, t.a_iv, ncand, 1, a_cands_ws));
         }
+        return 0;
     }
-    if (!sg.searches()) return 0;
     // The difference metrics read raw_out / raw_grad as rows of the im2col GEMM, [b * L][oc]: one transposition of the [b][oc][L]
     // tensors (same elements, same sums) gives the sweeps a dense epilogue operand and lets the weight search be pruned like a
     // Linear's (run_pass_pruned: slices are rows).
-    const bool prunable = !cosm && sg.full() && !t.scores && !t.best && !(d->reserved & RSV_NO_PRUNE) && d->eq_n >= 32;
-    float* Ot = prunable ? c.ws.get<float>((size_t)M * oc) : nullptr;
-    float* Gt = (prunable && (t.G || c.dry)) ? c.ws.get<float>((size_t)M * oc) : nullptr;   // (the sizing run plans for a call with raw_grad)
-    if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small");
-    if (prunable && !c.dry) {
+    int transpose_targets() {
+        prunable = !cosm && sg.full() && !t.scores && !t.best && !(d->reserved & RSV_NO_PRUNE) && d->eq_n >= 32;
+        Ot = prunable ? c.ws.get<float>((size_t)M * oc) : nullptr;
+        Gt = (prunable && (t.G || c.dry)) ? c.ws.get<float>((size_t)M * oc) : nullptr;   // (the sizing run plans for a call with raw_grad)
+        if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small");
+        if (!prunable || c.dry) return 0;
         const dim3 grid(cdiv(L, 32), cdiv(oc, 32), b);
         CHK(enqueue(c, KERN(NchwRowsParams, k_nchw_to_rows), grid, dim3(256), 0, NchwRowsParams{t.O, oc, L, Ot}));
         if (t.G) CHK(enqueue(c, KERN(NchwRowsParams, k_nchw_to_rows), grid, dim3(256), 0, NchwRowsParams{t.G, oc, L, Gt}));
+        return 0;
     }
+
     // x as im2col rows.  per_image: Z = batch, rows = pixels of one image (channel-wise cosine reduces over pixels)
-    auto x_operand = [&](bool expanded, const float* scales, int sc_cs, bool per_image) {
+    Operand x_operand(bool expanded, const float* scales, int sc_cs, bool per_image) const {
         Operand op{};
         op.present = true; op.expanded = expanded;
         op.pk = PackParams{};
@@ -3693,8 +3813,8 @@ int conv_impl(const p4v_conv_desc* d, const ConvTensors& t_, const Stage& sg, Ct
         op.pk.mode = aquant ? PACK_SYM : PACK_RAW; op.pk.scales = aquant ? scales : nullptr; op.pk.sc_cs = sc_cs;
         op.pk.lo = -aq; op.pk.hi = aq - 1;
         return op;
-    };
-    auto w_operand = [&](bool expanded, const float* scales, int sc_cs) {
+    }
+    Operand w_operand(bool expanded, const float* scales, int sc_cs) const {
         Operand op{};
         op.present = true; op.expanded = expanded;
         op.pk = pack2d(t.W, oc, K, K);
@@ -3702,13 +3822,17 @@ int conv_impl(const p4v_conv_desc* d, const ConvTensors& t_, const Stage& sg, Ct
         op.pk.blk_mode = d->channelwise ? 1 : 0; op.pk.blk_div = 1; op.pk.nblk_r = nw; op.pk.nblk_k = 1;
         op.pk.lo = -wq; op.pk.hi = wq - 1;
         return op;
-    };
-    auto setup = [&](Pass& ps, bool w_search) {
+    }
+    // The search pass of one side: the searched operand candidate-expanded, the other at its current interval; the GEMM in the
+    // orientation of the metric, then the side's selection.
+    Pass search_pass(int side, int round) {
+        const bool ws = side == 0;
+        Pass ps{};
         ps.i8 = false; ps.twin = false; ps.epi = epi; ps.wt_mode = wt_mode; ps.eq_n = d->eq_n; ps.K = K;
         ps.use_s1 = false; ps.s_cs = 1; ps.sb_mode = 0;
         ps.O = t.O; ps.G = t.G; ps.bias = t.bias;
-        Operand xo = x_operand(!w_search, w_search ? t.a_iv : a_cands, w_search ? 0 : 1, cosm && d->channelwise);
-        Operand wo = w_operand(w_search, w_search ? w_cands : t.w_iv, w_search ? nw : 0);
+        const Operand xo = x_operand(!ws, ws ? t.a_iv : a_cands, ws ? 0 : 1, cosm && d->channelwise);
+        const Operand wo = w_operand(ws, ws ? w_cands : t.w_iv, ws ? nw : 0);
         if (!cosm) {
             // rows = (image, pixel), cols = oc;  out[b][oc][l]
             ps.Z = 1; ps.Mrows = M; ps.Ncols = oc; ps.row = xo; ps.col = wo;
@@ -3727,48 +3851,41 @@ int conv_impl(const p4v_conv_desc* d, const ConvTensors& t_, const Stage& sg, Ct
             ps.bias_axis = 1; ps.G = nullptr;
             ps.cos_ZB = 1; ps.cos_ZV = 1;
         }
-    };
-
-    const SearchRounds R(sg, d->search_round, !(d->reserved & RSV_NO_MEMO), d->eq_n, nw, c, t.scores, t.best);
-    const bool memo_on = R.memo_on, keep_planes = R.keep_planes;
-    MirrorScope mirrors(c, memo_on, t.w_iv, t.a_iv);
-    PlaneCache plane_w, plane_a;
-    SliceCache slice;
-    MemoSide memo_w, memo_a;
-    memo_w.on = memo_on;
-    memo_a.on = memo_on && aquant;
-    // with a_bit >= 32 the input is never quantised: the weight search depends on nothing (conv.py:544)
-    const DevVecs key_w = aquant ? DevVecs(t.a_iv, 1) : DevVecs(), val_w(t.w_iv, nw), key_a(t.w_iv, nw), val_a(t.a_iv, 1);
-    for (int round = 0; round < R.n_rounds; ++round) {
-        bool hit = false;
-        CHK(memo_w.restore(c, key_w, nullptr, val_w, nullptr, &hit));
-        if (!hit && (sg.mask & ST_S1)) {   // ---- weight search (conv.py:526-557 / 365-396) ----
-            Pass ps{};
-            setup(ps, true);
+        if (ws) {   // one score column and one interval per weight interval
             ps.nj = nw;
             if (!cosm) { ps.j_mode = d->channelwise ? 3 : 0; ps.norm = d->channelwise ? 1.0 / (double)L : 1.0 / ((double)L * oc); }
             else if (d->channelwise) { ps.cos_j_mode = 3; ps.norm = 1.0; }
             else { ps.cos_j_mode = 0; ps.norm = 1.0 / (double)L; }
             ps.cands = w_cands; ps.cand_cs = nw; ps.cand_js = 1; ps.interval = t.w_iv; ps.out_js = 1;
-            ps.cache = keep_planes ? &plane_w : nullptr;
-            ps.scores_out = R.scores_of(round, 0); ps.scores_out_ld = nw; ps.best_out = R.best_of(round, 0);
-            ps.prunable = ps.prunable_f32 = prunable; ps.scache = &slice; ps.host_sync_ok = memo_on;
-            CHK(run_pass_pruned(c, ps));
-            CHK(memo_w.record(c, val_w, nullptr));
-        }
-        CHK(memo_a.restore(c, key_a, nullptr, val_a, nullptr, &hit));
-        if (aquant && !hit && (sg.mask & ST_S2)) {  // ---- activation search (conv.py:559-589), channel-wise class only ----
-            Pass ps{};
-            setup(ps, false);
+            ps.prunable = ps.prunable_f32 = prunable; ps.scache = &slice; ps.host_sync_ok = rounds.memo_on;
+        } else {    // the one interval of the input
             ps.nj = 1; ps.j_mode = 0; ps.norm = 1.0 / ((double)L * oc);
             ps.cands = a_cands; ps.cand_cs = 1; ps.cand_js = 0; ps.interval = t.a_iv; ps.out_js = 0;
-            ps.cache = keep_planes ? &plane_a : nullptr;
-            ps.scores_out = R.scores_of(round, 1); ps.scores_out_ld = nw; ps.best_out = R.best_of(round, 1);
-            CHK(run_pass(c, ps));
-            CHK(memo_a.record(c, val_a, nullptr));
         }
+        ps.cache = rounds.keep_planes ? (ws ? &plane_w : &plane_a) : nullptr;
+        ps.scores_out = rounds.scores_of(round, side); ps.scores_out_ld = nw; ps.best_out = rounds.best_of(round, side);
+        return ps;
     }
-    return 0;
+    // The weight side may be pruned; with a_bit >= 32 the input is never quantised: the weight search depends on nothing
+    // (conv.py:544), and there is no activation side -- no Stage bit, no memo.
+    SearchSide search_side(int side) {
+        const DevVecs w(t.w_iv, nw), a(t.a_iv, 1);
+        if (side == 0)
+            return SearchSide(ST_S1, rounds.memo_on, aquant ? a : DevVecs(), w, [this](int round) { Pass ps = search_pass(0, round); return run_pass_pruned(c, ps); });
+        return SearchSide(aquant ? ST_S2 : 0, rounds.memo_on && aquant, w, a, [this](int round) { Pass ps = search_pass(1, round); return run_pass(c, ps); });
+    }
+};
+
+int conv_impl(const p4v_conv_desc* d, const ConvTensors& t, const Stage& sg, Ctx& c) {
+    ConvCall cv(c, d, t, sg);
+    CHK(cv.build());
+    CHK(q_wait_inputs(c));     // (inside a group with a "capture done" event: everything below reads captured tensors)
+    CHK(cv.init());
+    if (!sg.searches()) return 0;
+    CHK(cv.transpose_targets());
+    MirrorScope mirrors(c, cv.rounds.memo_on, t.w_iv, t.a_iv);
+    SearchSide sides[2] = {cv.search_side(0), cv.search_side(1)};
+    return search_rounds(c, cv.rounds, sg, sides, nullptr);
 }
 
 // ---- p4v_calibrate_group: the members' calibration_step2 in lock step, launches grouped ----------------------------------------
@@ -4491,7 +4608,7 @@ int p4v_debug_gather_im2col(int batch, int in_channels, int height, int width, i
     const int num_h = height + 2 * pad_h - dil_h * (kernel_h - 1) - 1, num_w = width + 2 * pad_w - dil_w * (kernel_w - 1) - 1;
     if (num_h < 0 || num_w < 0) return fail(P4V_ERR_INVALID, "p4v_debug_gather_im2col: bad geometry");
     const int fh = num_h / stride_h + 1, fw = num_w / stride_w + 1;
-    PackParams p{};         // the conv view exactly as conv_impl's x_operand builds it for the flat layout (Z = 1, rows = b * L)
+    PackParams p{};         // the conv view exactly as ConvCall::x_operand builds it for the flat layout (Z = 1, rows = b * L)
     p.src = d_x; p.conv = 1; p.ic = in_channels; p.H = height; p.W = width; p.kh = kernel_h; p.kw = kernel_w;
     p.sh = stride_h; p.sw = stride_w; p.ph = pad_h; p.pw = pad_w; p.dh = dil_h; p.dw = dil_w;
     p.fw = fw; p.L = fh * fw;

@@ -1,6 +1,7 @@
-"""Shared by tests/test_hip_search_rounds.py and tools/plan_dump.py: the smallest calibration per path of the round drivers
-(csrc/p4v_api.hip: linear_impl, matmul_impl, conv_impl; DESIGN.md s5.2 "pass memo"), three search rounds each, seeded inputs
-(the generators of tests/sweep_plan_cases.py) or a fixture of tests/golden/.
+"""Shared by tests/test_hip_search_rounds.py and tools/plan_dump.py: the smallest calibration per path of the search rounds
+(csrc/p4v_api.hip: search_rounds under linear_impl, matmul_impl and conv_impl, and the step loop of MatMulBlocksCall; DESIGN.md
+s5.2 "pass memo", s5.6), three search rounds each, seeded inputs (the generators of tests/sweep_plan_cases.py) or a fixture of
+tests/golden/.
 
 `run(eng, mode)` makes ONE call and returns (intervals, tables):
   "default"  no score tables: the pass memo is on, pruning as the engine defaults it
@@ -23,7 +24,7 @@ def _cuda(t):
 
 def _call(eng, job, mode):
     if mode == "nomemo":
-        job.desc.reserved |= 2
+        getattr(job.desc, "mm", job.desc).reserved |= 2      # (a sub-block descriptor wraps the MatMul's)
     eng.run_job(job)
     return [t for t in job.outputs if t is not None], [t for t in (job.scores, job.best) if t is not None]
 
@@ -62,6 +63,33 @@ def _matmul(M, K, N, *, seed, metric="hessian", sos=False):
     return run
 
 
+def _matmul_blocks_fixture(name):
+    def run(eng, mode):
+        g = load_golden(name)
+        p = dict(g["params"])
+        sos = p["sos"]
+        blocks = ((1, 1) if sos else (p.get("n_V_A", 1), p.get("n_H_A", 1))) + (p.get("n_V_B", 1), p.get("n_H_B", 1))
+        t = lambda k: _cuda(torch.from_numpy(g[k]))
+        job = eng.matmul_job(A=t("A"), B=t("B"), out=t("out"), grad=t("grad") if p["metric"] == "hessian" else None, A_bit=p["A_bit"],
+                             B_bit=p["B_bit"], metric=p["metric"], eq_alpha=p["eq_alpha"], eq_beta=p["eq_beta"], eq_n=p["eq_n"],
+                             search_round=3, sos=sos, want_scores=mode == "scores", blocks=blocks)
+        return _call(eng, job, mode)
+    return run
+
+
+def _conv_fixture(name):
+    def run(eng, mode):
+        g = load_golden(name)
+        p = dict(g["params"])
+        p.pop("kind")
+        geo = {k: tuple(p.pop(k)) for k in ("stride", "padding", "dilation")}
+        t = lambda k: _cuda(torch.from_numpy(g[k]))
+        job = eng.conv_job(weight=t("weight"), bias=t("bias"), x=t("x"), out=t("out"), grad=t("grad") if p["metric"] == "hessian" else None,
+                           want_scores=mode == "scores", **geo, **dict(p, search_round=3))
+        return _call(eng, job, mode)
+    return run
+
+
 def _conv(*, seed, metric="hessian", a_bit=32, channelwise=True):
     def run(eng, mode):
         w, b, x, out, grad = conv_inputs(seed=seed)
@@ -96,6 +124,15 @@ CASES = [
     ("conv_cw_hessian_a32", _conv(seed=13)),
     ("conv_cw_hessian_a8", _conv(seed=14, a_bit=8)),
     ("conv_lw_cosine", _conv(seed=15, metric="cosine", channelwise=False)),
+    # MatMul with sub-blocks (fixtures of tests/test_hip_mmblk.py; no memo on this path): 4 x 3 heads, 13 x 8 x 13, ten block steps a
+    # round -- the step enumeration and the [round][step] slots; split-of-softmax 13 x 13 x 8 -- the head-wise split step among the
+    # block steps; 5 x 8 x 5 with n_V_A = 4 -- a block of nothing but padding, the abs-max start value
+    ("mmblk_qk_hessian_vA2hA2_vB2hB3", _matmul_blocks_fixture("mmblk_qk_hessian_vA2hA2_vB2hB3")),
+    ("mmblk_sos_hessian_vB2hB2", _matmul_blocks_fixture("mmblk_sos_hessian_vB2hB2")),
+    ("mmblk_empty_block", _matmul_blocks_fixture("mmblk_empty_block")),
+    # Conv, 3 x 5 x 17 x 23 with a dilated 3 x 5 kernel (a fixture of tests/test_hip_conv_geometry.py), a_bit 8: both sides on a
+    # geometry that is not a patch grid
+    ("convgeo_a_cw_hessian_a8_rect_dil", _conv_fixture("convgeo_a_cw_hessian_a8_rect_dil")),
 ]
 
 

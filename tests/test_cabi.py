@@ -131,9 +131,10 @@ def _matmul_desc(M, K, N, *, sos=False, metric="hessian", rounds=1, reserved=0, 
     return bd if blocks else d
 
 
-def _conv_desc(*, a_bit=32, metric="hessian", rounds=1, channelwise=True, reserved=0):
+def _conv_desc(*, a_bit=32, metric="hessian", rounds=1, channelwise=True, reserved=0, geometry=(2, 3, 32, 32, 16, 16, 16, 16, 16, 0, 0, 1, 1)):
+    """`geometry`: batch, channels, height, width, out channels, kernel h / w, stride h / w, padding h / w, dilation h / w."""
     from ptq4vit_amd import _lib
-    return _lib.ConvDesc(2, 3, 32, 32, 16, 16, 16, 16, 16, 0, 0, 1, 1, 8, a_bit, _lib.METRICS[metric], 100, rounds, int(channelwise), 0, 1, reserved)
+    return _lib.ConvDesc(*geometry, 8, a_bit, _lib.METRICS[metric], 100, rounds, int(channelwise), 0, 1, reserved)
 
 
 def _contract_descs():
@@ -155,7 +156,11 @@ def _contract_descs():
                 (L, _linear_desc(3, 11, 24, 16, n_V=2, n_H=2, n_a=3, bits=4, metric="cosine", **kw)),
                 (M, _matmul_desc(49, 64, 49, **kw)), (M, _matmul_desc(49, 64, 49, metric="cosine", **kw)),
                 (M, _matmul_desc(49, 49, 64, sos=True, **kw)), (M, _matmul_desc(49, 49, 64, sos=True, metric="cosine", **kw)),
-                (Cv, _conv_desc(**kw)), (Cv, _conv_desc(a_bit=8, **kw)), (Cv, _conv_desc(metric="cosine", channelwise=False, **kw))]
+                (Cv, _conv_desc(**kw)), (Cv, _conv_desc(a_bit=8, **kw)), (Cv, _conv_desc(metric="cosine", channelwise=False, **kw)),
+                (B, _matmul_desc(13, 8, 13, batch=4, heads=3, blocks=(2, 2, 2, 3), **kw)),
+                (B, _matmul_desc(13, 13, 8, batch=4, heads=3, sos=True, blocks=(1, 1, 2, 2), **kw)),
+                (B, _matmul_desc(5, 8, 5, blocks=(4, 1, 1, 4), **kw)),
+                (Cv, _conv_desc(a_bit=8, geometry=(3, 5, 17, 23, 10, 3, 5, 2, 1, 1, 2, 2, 1), **kw))]
     # (the lists themselves build their tensors on the GPU and expose no parameters: hold the count of this table to theirs, so that a
     # case added or removed there cannot pass here unnoticed)
     from tests import search_round_cases, sweep_plan_cases

@@ -1,12 +1,15 @@
-"""GPU: the round drivers of csrc/p4v_api.hip (linear_impl, matmul_impl, conv_impl: pass memo, table slots, pass builders) -- the
-smallest shape per path (tests/search_round_cases.py), three search rounds each.
+"""GPU: the search rounds of csrc/p4v_api.hip (search_rounds under linear_impl, matmul_impl and conv_impl: pass memo, table slots,
+pass builders; the step loop of MatMulBlocksCall) -- the smallest shape per path (tests/search_round_cases.py), three search
+rounds each.
 
 Asserted per case: the (kernel, stage) sequence of the launch records and the pass memo's (hits, misses) of the default call
 (no tables: memo on) and of the call with score tables (no memo: every pass runs).  The expected values are what the commit BEFORE
 the drivers were rebuilt around MemoSide / SearchRounds / LinearCall / MatMulCall produced for the same table on an MI355X
-(tools/plan_dump.py --gpu, profiles/r16_calls_parent_gpu.json); they are literals, not derived from the code under test.  A
-sequence that changes here means a pass was added, dropped or moved, a counter that changes means the memo restored or recorded
-something else: a behaviour change, not a refactor.
+(tools/plan_dump.py --gpu, profiles/r16_calls_parent_gpu.json); they are literals, not derived from the code under test.  The
+last four cases (MatMul with sub-blocks, which has no memo: (0, 0) in every mode; the rectangular dilated Conv) were added when
+the Conv and sub-block calls became ConvCall / MatMulBlocksCall on one round driver; their literals are what the commit before
+THAT change produced (profiles/r28_calls_parent_gpu.json).  A sequence that changes here means a pass was added, dropped or
+moved, a counter that changes means the memo restored or recorded something else: a behaviour change, not a refactor.
 Also asserted: the intervals of the default call are bit-equal to those of the call with score tables and of the call with the
 memo switched off (desc.reserved bit 1) -- restoring a recorded selection is exact.
 """
@@ -82,6 +85,22 @@ EXPECTED = {
     "conv_lw_cosine": {
         "default": ([(("k_sweep<float>", "full"), 1)], (2, 1)),
         "scores": ([(("k_sweep<float>", "full"), 3)], (0, 0)),
+    },
+    "mmblk_qk_hessian_vA2hA2_vB2hB3": {
+        "default": ([(("k_sweep_seg", "full"), 30)], (0, 0)),
+        "scores": ([(("k_sweep_seg", "full"), 30)], (0, 0)),
+    },
+    "mmblk_sos_hessian_vB2hB2": {
+        "default": ([(("k_sos_split", "full"), 1), (("k_sweep_seg", "full"), 4)] * 3, (0, 0)),
+        "scores": ([(("k_sos_split", "full"), 1), (("k_sweep_seg", "full"), 4)] * 3, (0, 0)),
+    },
+    "mmblk_empty_block": {
+        "default": ([(("k_sweep_seg", "full"), 24)], (0, 0)),
+        "scores": ([(("k_sweep_seg", "full"), 24)], (0, 0)),
+    },
+    "convgeo_a_cw_hessian_a8_rect_dil": {
+        "default": ([(("k_sweep<float>", "full"), 4)], (2, 4)),
+        "scores": ([(("k_sweep<float>", "full"), 6)], (0, 0)),
     },
 }
 
