@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define P4V_VERSION 144 /* 0.1.4.4: + p4v_wattn_* (the fused int8 attention forward for window attention: relative-position bias and shift mask) */
+#define P4V_VERSION 145 /* 0.1.4.5: + p4v_qkv_attn_* (the fused int8 qkv forward: the qkv GEMM writes the attention operand planes) */
 
 /* similarity metrics: reference quant_layers/linear.py:399-424 */
 enum p4v_metric {
@@ -531,6 +531,48 @@ typedef struct p4v_wattn_tensors {
 size_t p4v_wattn_workspace_bytes(const p4v_wattn_desc* desc);
 
 int p4v_wattn_quant_forward(const p4v_wattn_desc* desc, const p4v_wattn_tensors* tensors, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Fused qkv + attention forward (opt-in, network level; ViT / DeiT Attention): p4v_attn_quant_forward with the qkv Linear layer in
+ * front of it.  The qkv layer is the int8 GEMM of p4v_linear_quant_forward; its kernel (k_qkv_heads) quantises each output
+ * element scale * acc + bias with the quantiser of the MatMul operand it belongs to -- column n = which * C + head * D + d: q on
+ * qk's A interval, k on qk's B interval, v on pv's B interval, each with its own clamp range -- and writes the three int8 operand
+ * planes of the two MatMuls directly: the fp32 qkv tensor, its permute copy and the three packs of q, k^T and v are neither written
+ * nor read.  There is nothing inexact between the GEMM and the quantisers: the planes equal, byte for byte, what the unfused chain
+ * packs from p4v_linear_quant_forward's output, and out / probs equal p4v_attn_quant_forward on the slices of that output bit for bit.
+ * Envelope: that of p4v_attn_quant_forward on `qk` / `pv`; qkv with n_H = n_a = 1, any n_V that divides, not twin_postgelu, int8
+ * planes, w_bit / a_bit 2..8, any in_features, out_features = 3 * heads * D with D = qk.K = pv.N, qkv.batch * qkv.tokens = qk.batch *
+ * qk.M, qk.M = qk.N = pv.K (the tokens of an image); anything else is P4V_ERR_INVALID / P4V_ERR_UNSUPPORTED before the first
+ * launch.  The operand strides of `qk` / `pv` are not read (no fp32 q, k^T or v exists); the search fields are ignored.
+ * x [batch * tokens][in_features]; w [out_features][in_features]; bias [out_features] (has_bias); w_interval [n_V], a_interval [1];
+ * the four MatMul intervals and split as for p4v_attn_quant_forward; out [batch*heads][M][D]; qkv_out: optional (may be NULL)
+ * [batch * tokens][out_features] fp32, the values the planes were quantised from; probs: optional [batch*heads][M][N] fp32; ws,
+ * ws_bytes: the workspace and its size -- the workspace contract above holds with p4v_qkv_attn_workspace_bytes; a smaller
+ * ws_bytes is refused before any launch.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct p4v_qkv_attn_desc {
+    p4v_linear_desc qkv;
+    p4v_matmul_desc qk, pv;
+    float scale;
+    int32_t reserved;
+} p4v_qkv_attn_desc;
+
+typedef struct p4v_qkv_attn_tensors {
+    const float *x, *w;
+    const float* bias;                 /* NULL without a bias (qkv.has_bias = 0) */
+    const float *w_interval, *a_interval;
+    const float *qk_A_interval, *qk_B_interval, *pv_A_interval, *pv_B_interval;
+    const float* split;                /* sos only */
+    float* out;
+    float* qkv_out;                    /* optional */
+    float* probs;                      /* optional */
+    void* ws;
+    size_t ws_bytes;
+} p4v_qkv_attn_tensors;
+
+size_t p4v_qkv_attn_workspace_bytes(const p4v_qkv_attn_desc* desc);
+
+int p4v_qkv_attn_quant_forward(const p4v_qkv_attn_desc* desc, const p4v_qkv_attn_tensors* tensors, void* stream);
 
 /* d_A_interval: [heads] (sos: [1]); d_B_interval: [heads]; d_split: [1] (sos only); d_out: [batch*heads][M][N] */
 int p4v_matmul_quant_forward(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_A_interval,

@@ -55,6 +55,11 @@ int p4v_debug_mlp_planes(uint64_t* out);
  * and its record) and matmul2's row plane(s), [batch*heads][Mp][Kp]: out[2] = batch * heads * Mp (all rows of a plane),
  * out[3] = Kp. */
 int p4v_debug_attn_planes(uint64_t info[5]);
+/* Where the calling thread's last p4v_qkv_attn_quant_forward left the three operand planes k_qkv_heads wrote (matmul2's row
+ * plane(s) of that call: p4v_debug_attn_planes): info[0..2] = byte offsets of Q(q), Q(k^T), Q(v) from ws, info[3] = Z = batch *
+ * heads, info[4], info[5] = padded rows of a z of the q / k^T plane, info[6] = their row length K1p ([Z][rows][K1p] at [tok][d]),
+ * info[7] x info[8] = rows x row length of a z of the v plane ([Z][NpB][Kp] at [d][tok]).  The planes outlive the call. */
+int p4v_debug_qkv_planes(uint64_t info[9]);
 /* ONE sweep of the split-of-softmax split search (k_sos_split + k_finish) on the operands of `desc`, over the first n_cands of
  * the 20 splits: d_scores [n_cands] receives the score table, entries outside [c_lo, c_hi) as k_finish leaves them (-inf).
  * c_lo < 0: no candidate range.  known_cands: what the caller tells the sweep about the number of candidates in the range

@@ -52,6 +52,18 @@ class WattnTensors(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in POINTERS] + [("ws_bytes", C.c_size_t)]
 
 
+class QkvAttnDesc(C.Structure):
+    """p4v_qkv_attn_desc: the qkv Linear layer, the two MatMuls of the attention block behind it and the factor between those."""
+    _fields_ = [("qkv", LinearDesc), ("qk", MatMulDesc), ("pv", MatMulDesc), ("scale", C.c_float), ("reserved", C.c_int32)]
+
+
+class QkvAttnTensors(C.Structure):
+    """p4v_qkv_attn_tensors: the device pointers of a p4v_qkv_attn_quant_forward call, its workspace and the workspace's size."""
+    POINTERS = ("x", "w", "bias", "w_interval", "a_interval", "qk_A_interval", "qk_B_interval", "pv_A_interval", "pv_B_interval", "split",
+                "out", "qkv_out", "probs", "ws")
+    _fields_ = [(n, C.c_void_p) for n in POINTERS] + [("ws_bytes", C.c_size_t)]
+
+
 class MatMulBlocksDesc(C.Structure):
     """p4v_matmul_blocks_desc: the MatMul descriptor plus the row / column block counts of both operands."""
     _fields_ = [("mm", MatMulDesc)] + [(n, C.c_int32) for n in ("n_V_A", "n_H_A", "n_V_B", "n_H_B")]
@@ -81,7 +93,7 @@ class LaunchRecord(C.Structure):
 
 LAUNCH_KINDS = {0: "k_sweep<int8>", 1: "k_sweep<float>", 2: "k_sweep6", 3: "k_sweep7", 4: "k_sweep7 (twin)", 5: "k_sweep4/5", 6: "k_sweep9",
                 7: "k_sweep8", 8: "k_sweep2g", 9: "k_sweep2", 11: "k_sos_split", 12: "k_bound", 13: "k_slice_b", 14: "k_slice_a", 15: "k_sweep_seg", 16: "k_mlp_fc1",
-                17: "k_attn_qk"}
+                17: "k_attn_qk", 18: "k_qkv_heads"}
 LAUNCH_STAGES = {0: "full", 1: "A", 2: "B1", 3: "B2", 4: "A2"}
 
 
@@ -131,6 +143,7 @@ EXPORTS = [
     "p4v_calibrate_group", "p4v_launch_counters",
     "p4v_linear_quant_forward", "p4v_matmul_quant_forward", "p4v_mlp_workspace_bytes", "p4v_mlp_quant_forward",
     "p4v_attn_workspace_bytes", "p4v_attn_quant_forward", "p4v_wattn_workspace_bytes", "p4v_wattn_quant_forward",
+    "p4v_qkv_attn_workspace_bytes", "p4v_qkv_attn_quant_forward",
     "p4v_amax_init_linear", "p4v_linear_search_w", "p4v_linear_search_a",
     "p4v_amax_init_matmul", "p4v_matmul_search_A", "p4v_sos_search_split", "p4v_matmul_search_B",
     "p4v_amax_init_conv", "p4v_conv_search_w_channelwise", "p4v_conv_search_w_layerwise", "p4v_conv_search_a",
@@ -139,7 +152,7 @@ EXPORTS = [
     "p4v_stats_enable", "p4v_stats_reset", "p4v_stats_get", "p4v_stats_launches", "p4v_prune_counters",
     "p4v_debug_set_variant", "p4v_debug_set_tuning", "p4v_debug_bound_totals", "p4v_debug_topk_rows", "p4v_debug_pack_dual", "p4v_debug_prep_epi6",
     "p4v_debug_pack_cands", "p4v_debug_gather_im2col", "p4v_debug_sos_sweep",
-    "p4v_debug_set_arena_gap", "p4v_debug_arena_ranges", "p4v_debug_mlp_planes", "p4v_debug_attn_planes",
+    "p4v_debug_set_arena_gap", "p4v_debug_arena_ranges", "p4v_debug_mlp_planes", "p4v_debug_attn_planes", "p4v_debug_qkv_planes",
 ]
 
 _lib = None
@@ -203,6 +216,12 @@ def load():
     lib.p4v_wattn_quant_forward.argtypes = [C.POINTER(WattnDesc), C.POINTER(WattnTensors), vp]
     lib.p4v_debug_attn_planes.restype = C.c_int
     lib.p4v_debug_attn_planes.argtypes = [C.POINTER(C.c_uint64)]
+    lib.p4v_qkv_attn_workspace_bytes.restype = C.c_size_t
+    lib.p4v_qkv_attn_workspace_bytes.argtypes = [C.POINTER(QkvAttnDesc)]
+    lib.p4v_qkv_attn_quant_forward.restype = C.c_int
+    lib.p4v_qkv_attn_quant_forward.argtypes = [C.POINTER(QkvAttnDesc), C.POINTER(QkvAttnTensors), vp]
+    lib.p4v_debug_qkv_planes.restype = C.c_int
+    lib.p4v_debug_qkv_planes.argtypes = [C.POINTER(C.c_uint64)]
     lib.p4v_matmul_quant_forward.restype = C.c_int
     lib.p4v_matmul_quant_forward.argtypes = [C.POINTER(MatMulDesc), fp, fp, fp, fp, fp, fp, vp, C.c_size_t, vp]
     # granular entry points: (desc, tensors..., workspace, bytes, stream)

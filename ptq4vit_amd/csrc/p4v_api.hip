@@ -1006,9 +1006,10 @@ struct Operand {
     PackParams pk;        // src/strides/sizes/scales/mode filled by the caller (dst, C, Rp, Kp set by run_pass)
     bool expanded;        // true: one plane per candidate
     bool present;
-    bool prepacked;       // row / row2 of a forward pass only: `plane` is the operand's fixed int8 plane, row-major [pl.Mp][pl.Kp] as
-    const void* plane;    // plan_sweep sizes it, written by an earlier launch on the stream (mlp_impl: fc1's epilogue); nothing is
-                          // allocated or packed for it (a sizing run: no address yet).  false (everything else): packed from pk.src
+    bool prepacked;       // a forward pass only: `plane` is the operand's fixed int8 plane, row-major [pl.Mp][pl.Kp] (row / row2) or
+    const void* plane;    // [pl.NpB][pl.Kp] (col) as plan_sweep sizes it, written by an earlier launch on the stream (mlp_impl: fc1's
+                          // epilogue; qkv_attn_impl: k_qkv_heads); nothing is allocated or packed for it (a sizing run: no address
+                          // yet).  false (everything else): packed from pk.src
 };
 
 // A MatMul pass with row / column sub-blocks (n_V, n_H > 1; matmul_impl): the K axis cut where either operand's scale changes
@@ -1420,7 +1421,8 @@ int pass_workspace(Ctx& c, const Pass& ps, const SweepPlan& pl, PassBufs& b) {
     b.row = ps.row.prepacked ? (char*)ps.row.plane :
             (pc && ps.row.expanded) ? pc->buf : c.ws.get<char>((size_t)pl.row_plane1 * (ps.row.expanded ? pl.chunk_al : 1) + pl.slack);
     b.row2 = !ps.twin ? nullptr : ps.row2.prepacked ? (char*)ps.row2.plane : c.ws.get<char>((size_t)pl.row_plane1 * (ps.row2.expanded ? pl.chunk : 1));
-    b.col = (pc && ps.col.expanded) ? pc->buf : c.ws.get<char>((size_t)pl.col_plane1 * (ps.col.expanded ? pl.chunk_al : 1) + pl.slack);
+    b.col = ps.col.prepacked ? (char*)ps.col.plane :
+            (pc && ps.col.expanded) ? pc->buf : c.ws.get<char>((size_t)pl.col_plane1 * (ps.col.expanded ? pl.chunk_al : 1) + pl.slack);
     b.part = c.ws.get<float>((size_t)pl.part_cs * ps.eq_n);
     b.S1 = !ps.use_s1 ? nullptr : ps.S1_pre ? ps.S1_pre : c.ws.get<float>((size_t)ps.eq_n * ps.s_cs);
     b.S2 = !(ps.use_s1 && ps.twin) ? nullptr : ps.S2_pre ? ps.S2_pre : c.ws.get<float>((size_t)ps.eq_n * ps.s_cs);
@@ -1523,7 +1525,11 @@ int pack_fixed_planes(Ctx& c, const Pass& ps, const SweepPlan& pl, const PassBuf
         if (!ps.row.expanded) CHK(pack_operand(c, ps, pl, b, ps.row, b.row, false, 0, 1));
         if (ps.twin && !ps.row2.expanded) CHK(pack_operand(c, ps, pl, b, ps.row2, b.row2, false, 0, 1));
     }
-    if (!ps.col.expanded) CHK(pack_operand(c, ps, pl, b, ps.col, b.col, true, 0, 1));
+    if (ps.col.prepacked) {
+        // prepacked column operand (the fused qkv forward: v), under the row side's refusals
+        if (ps.col.expanded || pl.cin_fix != 0 || !ps.i8 || !ps.stores())
+            return fail(P4V_ERR_INVALID, "prepacked column operand: the fixed row-major int8 plane of a forward pass only");
+    } else if (!ps.col.expanded) CHK(pack_operand(c, ps, pl, b, ps.col, b.col, true, 0, 1));
     return 0;
 }
 
@@ -3081,11 +3087,36 @@ int linear_impl(const p4v_linear_desc* d, const LinearTensors& t, const Stage& s
 // tests read them there)
 struct FusedPlanes { size_t off1 = 0, off2 = 0; long rows = 0, cols = 0; int twin = 0; };
 thread_local FusedPlanes g_mlp_planes, g_attn_planes;
-constexpr int MLP_RECORD_KIND = 16, ATTN_RECORD_KIND = 17;
+// ... and the three operand planes k_qkv_heads wrote (p4v_debug_qkv_planes): offsets, then Z and the planes' rows / row lengths
+struct QkvPlanes { size_t off_q = 0, off_k = 0, off_v = 0; long Z = 0, rows_q = 0, rows_k = 0, ld_qk = 0, rows_v = 0, ld_v = 0; };
+thread_local QkvPlanes g_qkv_planes;
+constexpr int MLP_RECORD_KIND = 16, ATTN_RECORD_KIND = 17, QKV_RECORD_KIND = 18;
 
 // One producer -> consumer chain, in the order its caller walks it: plan_consumer, produce, consume.
 struct FusedChain {
     struct Packed { char *rows, *cols; float* S1; int Kp, Np; };    // the producer's operand planes [Z][Mp | Np][Kp] and its scale table
+    struct PrePlanes { char *rows, *cols, *col2; };                 // planes an earlier launch wrote: the producer's two, the consumer's column plane
+    static int producer_kp(int K1) { return (int)rup(K1, 64); }
+    static int producer_np(int ncols) { return (int)rup(ncols, SW_BN); }
+    // Both operands of a forward pass `fp1` (reduction length K1, `ncols` columns, `nscale` scale entries; rows padded to Mp_) and
+    // its scale table as run_pass would make them (pack_operand, k_scale_table), in scratch of the bump region.  With `pre` the
+    // planes are taken as they are: only the scale table is made.
+    static int pack_pair(Ctx& c, Pass& fp1, int Z_, int Mp_, int K1, int ncols, int nscale, Packed& pk, const PrePlanes* pre = nullptr) {
+        pk.Kp = producer_kp(K1); pk.Np = producer_np(ncols);
+        SweepPlan pl1{};                                            // what pack_operand reads of a plan: the plane geometry
+        pl1.esz = 1; pl1.Mp = Mp_; pl1.Np = pl1.NpB = pk.Np; pl1.Kp = pk.Kp; pl1.cin_fix = 0;
+        pk.rows = pre ? pre->rows : c.ws.get<char>((size_t)Z_ * Mp_ * pk.Kp);
+        pk.cols = pre ? pre->cols : c.ws.get<char>((size_t)Z_ * pk.Np * pk.Kp);
+        pk.S1 = c.ws.get<float>((size_t)nscale);
+        if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", c.ws.off);
+        fp1.s1.S = pk.S1; fp1.s1.C = 1; fp1.s1.nblk = fp1.s_cs;
+        CHK(launch_scale(c, fp1.s1));
+        if (pre) return 0;
+        const PassBufs nb{};
+        CHK(pack_operand(c, fp1, pl1, nb, fp1.row, pk.rows, false, 0, 1));
+        CHK(pack_operand(c, fp1, pl1, nb, fp1.col, pk.cols, true, 0, 1));
+        return 0;
+    }
     Ctx& c;
     const char *who, *consumer;                                     // for the messages: "mlp" / "attn", "fc2" / "p v"
     Pass fp2{};                                                     // the consumer's forward pass
@@ -3107,21 +3138,11 @@ struct FusedChain {
     // The producer: both operands of its forward pass `fp1` (reduction length K1, `ncols` columns, `nscale` scale entries) packed
     // as run_pass would pack them (pack_operand, k_scale_table) into scratch that is given back at the end, then -- unless the
     // run is dry -- `launch(Packed)`, which enqueues the kernel that writes P1 / P2.
-    template <class Launch> int produce(Pass fp1, int K1, int ncols, int nscale, FusedPlanes& where, Launch&& launch) {
+    // `pre` (qkv_attn_impl): the producer's operand planes are on the stream already, in this geometry -- nothing is packed.
+    template <class Launch> int produce(Pass fp1, int K1, int ncols, int nscale, FusedPlanes& where, Launch&& launch, const PrePlanes* pre = nullptr) {
         const size_t mark = c.ws.off;
         Packed pk{};
-        pk.Kp = (int)rup(K1, 64); pk.Np = (int)rup(ncols, SW_BN);
-        SweepPlan pl1{};                                            // what pack_operand reads of a plan: the plane geometry
-        pl1.esz = 1; pl1.Mp = Mp; pl1.Np = pl1.NpB = pk.Np; pl1.Kp = pk.Kp; pl1.cin_fix = 0;
-        pk.rows = c.ws.get<char>((size_t)Z * Mp * pk.Kp);
-        pk.cols = c.ws.get<char>((size_t)Z * pk.Np * pk.Kp);
-        pk.S1 = c.ws.get<float>((size_t)nscale);
-        if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", c.ws.off);
-        fp1.s1.S = pk.S1; fp1.s1.C = 1; fp1.s1.nblk = fp1.s_cs;
-        CHK(launch_scale(c, fp1.s1));
-        const PassBufs nb{};
-        CHK(pack_operand(c, fp1, pl1, nb, fp1.row, pk.rows, false, 0, 1));
-        CHK(pack_operand(c, fp1, pl1, nb, fp1.col, pk.cols, true, 0, 1));
+        CHK(pack_pair(c, fp1, Z, Mp, K1, ncols, nscale, pk, pre));
         if (!c.dry) {
             CHK(launch(pk));
             where = FusedPlanes{(size_t)(P1 - c.ws.base), P2 ? (size_t)(P2 - c.ws.base) : 0, (long)Z * Mp, Kp, twin ? 1 : 0};
@@ -3130,9 +3151,11 @@ struct FusedChain {
         return 0;
     }
     // The consumer's pass as run_pass runs it, the row operand prepacked (Operand.prepacked): same sweep kernel, same epilogue.
-    int consume() {
+    // `pre` (qkv_attn_impl): the column operand's plane [Z][pl2.NpB][pl2.Kp] is on the stream too.
+    int consume(const PrePlanes* pre = nullptr) {
         fp2.row.prepacked = true; fp2.row.plane = P1;
         if (twin) { fp2.row2.prepacked = true; fp2.row2.plane = P2; }
+        if (pre) { fp2.col.prepacked = true; fp2.col.plane = pre->col2; }
         return run_pass(c, fp2);
     }
 };
@@ -3478,7 +3501,54 @@ struct MatMulCall {
 // `win` (p4v_wattn_quant_forward; null: the plain call): the window record -- q arrives scaled, the kernel's window instance adds
 // the relative-position bias and the shift mask in place of `* scale`; everything else of the chain is the same.
 struct AttnWindow { const float* bias; const float* mask; int n_windows; };
-int attn_chain(const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulTensors& t2, Ctx& c, const AttnWindow* win) {
+// `qkv` (p4v_qkv_attn_quant_forward; null: q, k^T and v arrive as fp32 tensors): the qkv layer in front of the chain.  k_qkv_heads
+// -- its int8 GEMM on Q(x) and Q(Wqkv), packed as its forward pass would pack them -- writes matmul1's two operand planes and
+// matmul2's column plane: the fp32 qkv tensor, the permute copy of it and the three k_pack1 of q, k^T and v are gone.  The three
+// planes are carved behind the consumer's row plane(s), outside every region that is handed back, and zeroed first: the kernel
+// writes the bytes of valid elements only.
+struct QkvProducer {
+    const LinearCall& L;
+    const LinearTensors& t;
+    int run(Ctx& c, const FusedChain& ch, int H, int Ntok, int D, const MatMulTensors& t1, const MatMulCall& m1, const MatMulTensors& t2,
+            const MatMulCall& m2, FusedChain::PrePlanes& pre) const {
+        const int Z = ch.Z, K1p = FusedChain::producer_kp(D), Np1 = FusedChain::producer_np(Ntok);
+        const size_t nq = (size_t)Z * ch.Mp * K1p, nk = (size_t)Z * Np1 * K1p, nv = (size_t)Z * ch.pl2.NpB * ch.pl2.Kp;
+        pre.rows = c.ws.get<char>(nq);
+        pre.cols = c.ws.get<char>(nk);
+        pre.col2 = c.ws.get<char>(nv);
+        const size_t mark = c.ws.off;
+        Pass fp = L.forward_pass();
+        FusedChain::Packed pk{};
+        const int Mp = (int)rup(L.M, SW_BM);
+        CHK(FusedChain::pack_pair(c, fp, 1, Mp, L.K, L.N, L.nV, pk));
+        if (!c.dry) {
+            CHK(q_fill(c, pre.rows, 0, nq));
+            CHK(q_fill(c, pre.cols, 0, nk));
+            CHK(q_fill(c, pre.col2, 0, nv));
+            QkvHeadsParams q{};
+            q.A = pk.rows; q.B = pk.cols; q.ldk = pk.Kp; q.ktiles = pk.Kp / SW_BKB;
+            q.S1 = pk.S1; q.s_cs = L.nV; q.sb_div = L.crb_rows;
+            q.bias = t.bias; q.M = L.M; q.N = L.N; q.mtiles = Mp / SW_BM; q.ntiles = pk.Np / SW_BN;
+            q.Ntok = Ntok; q.H = H; q.D = D; q.C = H * D;
+            q.iv_q = t1.A_iv; q.iv_k = t1.B_iv; q.iv_v = t2.B_iv;
+            q.lo_q = -m1.Aq; q.hi_q = m1.Aq - 1; q.lo_k = -m1.Bq; q.hi_k = m1.Bq - 1; q.lo_v = -m2.Bq; q.hi_v = m2.Bq - 1;
+            q.Pq = (int8_t*)pre.rows; q.Pk = (int8_t*)pre.cols; q.Pv = (int8_t*)pre.col2;
+            q.rows_q = ch.Mp; q.rows_k = Np1; q.ld_qk = K1p; q.rows_v = ch.pl2.NpB; q.ld_v = ch.pl2.Kp;
+            q.qkv_out = t.fwd_out;
+            g_alg_macs_cand = (double)L.M * L.N * L.K;
+            // x and Wqkv in fp32, the three planes: the fill and the kernel's bytes
+            g_alg_bytes = 4.0 * ((double)L.M * L.K + (double)L.N * L.K) + (double)(nq + nk + nv) + (double)L.M * L.N;
+            g_exec_frac = 1.0;
+            const StatInfo si = stat_info(QKV_RECORD_KIND, (double)Mp * pk.Np * pk.Kp, g_alg_macs_cand, q.mtiles * q.ntiles, 1, g_alg_bytes);
+            CHK(enqueue(c, Kern1<QkvHeadsParams, k_qkv_heads>::desc(), dim3(q.mtiles * q.ntiles), dim3(512), 2 * 2 * SW_TILE_BYTES, q, &si));
+            g_qkv_planes = QkvPlanes{(size_t)(pre.rows - c.ws.base), (size_t)(pre.cols - c.ws.base), (size_t)(pre.col2 - c.ws.base), Z, ch.Mp, Np1, K1p,
+                                     ch.pl2.NpB, ch.pl2.Kp};
+        }
+        c.ws.off = mark;
+        return 0;
+    }
+};
+int attn_chain(const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulTensors& t2, Ctx& c, const AttnWindow* win, const QkvProducer* qkv = nullptr) {
     const p4v_matmul_desc* d1 = &d->qk;
     const p4v_matmul_desc* d2 = &d->pv;
     // the envelope, before anything is planned or launched
@@ -3509,6 +3579,9 @@ int attn_chain(const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulTens
     FusedChain ch{c, "attn", "p v"};
     CHK(ch.plan_consumer(m2.forward_pass(), Z, twin));         // Kp = roundup64(N)
     if (ch.Mp % SW_BM || (long)Z * (ch.Mp / SW_BM) >= (1L << 31)) return fail(P4V_ERR_UNSUPPORTED, "attn: %d x %d row tiles", Z, ch.Mp / SW_BM);
+    FusedChain::PrePlanes planes{};
+    const FusedChain::PrePlanes* pre = qkv ? &planes : nullptr;
+    if (qkv) CHK(qkv->run(c, ch, H, N, K1, t1, m1, t2, m2, planes));
     CHK(ch.produce(m1.forward_pass(), K1, N, H, g_attn_planes, [&](const FusedChain::Packed& pk) -> int {
         AttnQkParams q{};
         q.Q = pk.rows; q.Kt = pk.cols; q.q_zs = (long)ch.Mp * pk.Kp; q.k_zs = (long)pk.Np * pk.Kp; q.ldk = pk.Kp; q.ktiles = pk.Kp / SW_BKB;
@@ -3536,13 +3609,42 @@ int attn_chain(const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulTens
         }
         return twin ? enqueue(c, KERN1_T(AttnQkParams, k_attn_qk, true), grid, block, lds, q, &si)
                     : enqueue(c, KERN1_T(AttnQkParams, k_attn_qk, false), grid, block, lds, q, &si);
-    }));
-    return ch.consume();
+    }, pre));
+    return ch.consume(pre);
 }
 int attn_impl(const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulTensors& t2, Ctx& c) { return attn_chain(d, t1, t2, c, nullptr); }
 // the window call as fused_sizing_run / fused_call take it: the p4v_attn_desc of its two MatMuls and the window record
 struct WattnCall { p4v_attn_desc a; AttnWindow w; };
 int wattn_impl(const WattnCall* d, const MatMulTensors& t1, const MatMulTensors& t2, Ctx& c) { return attn_chain(&d->a, t1, t2, c, &d->w); }
+
+// ---- p4v_qkv_attn_quant_forward: the qkv layer in front of the attention chain (QkvProducer above) -----------------------------
+// The records of the three modules as their own quant_forward entry points fill them: lin.fwd_out is the optional fp32 copy of
+// the qkv tensor, m1.fwd_out the optional probabilities; m1.A, m1.B and m2.B stay null (no fp32 q, k^T or v exists).
+struct QkvAttnTensors { LinearTensors lin; MatMulTensors m1, m2; };
+int qkv_attn_impl(const p4v_qkv_attn_desc* d, const QkvAttnTensors& t, const QkvAttnTensors&, Ctx& c) {
+    const p4v_linear_desc* dl = &d->qkv;
+    const p4v_matmul_desc* d1 = &d->qk;
+    const p4v_matmul_desc* d2 = &d->pv;
+    // the envelope of the qkv layer and of its seam with the chain, before anything is planned or launched (attn_chain checks the
+    // two MatMuls against each other)
+    if (dl->n_H != 1 || dl->n_a != 1) return fail(P4V_ERR_UNSUPPORTED, "qkv_attn: the fused forward takes n_H = n_a = 1 on qkv");
+    if (dl->twin_postgelu) return fail(P4V_ERR_UNSUPPORTED, "qkv_attn: qkv reads no GELU output (twin_postgelu)");
+    if (dl->reserved & RSV_FP32_PLANES) return fail(P4V_ERR_UNSUPPORTED, "qkv_attn: int8 planes only (qkv.reserved bit 0 is set)");
+    if (d1->heads <= 0 || d1->K <= 0 || d1->M <= 0) return fail(P4V_ERR_INVALID, "qkv_attn: non-positive dimension");
+    if (d2->N != d1->K || (long)dl->out_features != 3L * d1->heads * d1->K)
+        return fail(P4V_ERR_INVALID, "qkv_attn: qkv.out_features = %d, p v's N = %d: not 3 x %d heads x head_dim %d", dl->out_features, d2->N, d1->heads, d1->K);
+    if (d1->M != d1->N || d2->K != d1->M || (long)dl->batch * dl->tokens != (long)d1->batch * d1->M)
+        return fail(P4V_ERR_INVALID, "qkv_attn: qkv's rows %ld are not %d images of %d = %d = %d tokens", (long)dl->batch * dl->tokens, d1->batch, d1->M,
+                    d1->N, d2->K);
+    const Stage sg{ST_FWD};
+    LinearCall L(c, dl, t.lin, sg);
+    CHK(L.build());
+    if (!L.i8) return fail(P4V_ERR_UNSUPPORTED, "qkv_attn: int8 planes only");
+    if (rup(L.M, SW_BM) / SW_BM * (rup(L.N, SW_BN) / SW_BN) >= (1L << 31)) return fail(P4V_ERR_UNSUPPORTED, "qkv_attn: %d x %d output tiles", L.M, L.N);
+    const p4v_attn_desc a{*d1, *d2, d->scale, 0};
+    const QkvProducer qkv{L, t.lin};
+    return attn_chain(&a, t.m1, t.m2, c, nullptr, &qkv);
+}
 
 // ---- MatMul with row / column sub-blocks (n_V, n_H > 1; reference matmul.py:109-138, 419-440, 483-563) -------------------------
 // Intervals are [heads][n_V][n_H] (the reference's (1, n_G = heads, 1, n_V, 1, n_H, 1)).  The search is the reference's greedy
@@ -4070,6 +4172,26 @@ int p4v_wattn_quant_forward(const p4v_wattn_desc* desc, const p4v_wattn_tensors*
                        .split = const_cast<float*>(t->split), .fwd_out = t->out}, t->ws, t->ws_bytes, stream);
 }
 
+size_t p4v_qkv_attn_workspace_bytes(const p4v_qkv_attn_desc* desc) {
+    size_t need = 0;
+    return (desc && fused_sizing_run(qkv_attn_impl, desc, &need) == 0) ? need : 0;
+}
+
+int p4v_qkv_attn_quant_forward(const p4v_qkv_attn_desc* desc, const p4v_qkv_attn_tensors* t, void* stream) {
+    if (!desc || !t || !t->x || !t->w || !t->w_interval || !t->a_interval || !t->qk_A_interval || !t->qk_B_interval || !t->pv_A_interval ||
+        !t->pv_B_interval || !t->out || !t->ws)
+        return fail(P4V_ERR_INVALID, "p4v_qkv_attn_quant_forward: null pointer");
+    if (desc->qkv.has_bias && !t->bias) return fail(P4V_ERR_INVALID, "p4v_qkv_attn_quant_forward: has_bias set but the bias is null");
+    if (desc->pv.sos && !t->split) return fail(P4V_ERR_INVALID, "p4v_qkv_attn_quant_forward: sos needs split");
+    CHK(ws_aligned(t->ws));
+    const QkvAttnTensors rec{
+        {.W = t->w, .bias = desc->qkv.has_bias ? t->bias : nullptr, .X = t->x, .w_iv = const_cast<float*>(t->w_interval),
+         .a_iv = const_cast<float*>(t->a_interval), .fwd_out = t->qkv_out},
+        {.A_iv = const_cast<float*>(t->qk_A_interval), .B_iv = const_cast<float*>(t->qk_B_interval), .fwd_out = t->probs},
+        {.A_iv = const_cast<float*>(t->pv_A_interval), .B_iv = const_cast<float*>(t->pv_B_interval), .split = const_cast<float*>(t->split), .fwd_out = t->out}};
+    return fused_call(qkv_attn_impl, desc, rec, rec, t->ws, t->ws_bytes, stream);
+}
+
 int p4v_matmul_quant_forward(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_A_interval,
                              const float* d_B_interval, const float* d_split, float* d_out, void* d_workspace,
                              size_t workspace_bytes, void* stream) {
@@ -4442,7 +4564,7 @@ static int stats_drain() {
         float ms = 0;
         HIPCHK(hipEventElapsedTime(&ms, r.a, r.b));
         ms = (float)std::max(0.0, (double)ms - g_evt_overhead_ms);
-        if (r.kind == 0 || (r.kind >= 2 && r.kind <= 9) || (r.kind >= 12 && r.kind <= 17)) { g_stats.sweep_i8_ms += ms; g_stats.sweep_i8_launches++; g_stats.sweep_i8_macs += r.macs; g_stats.sweep_i8_alg_macs += r.alg; }
+        if (r.kind == 0 || (r.kind >= 2 && r.kind <= 9) || (r.kind >= 12 && r.kind <= 18)) { g_stats.sweep_i8_ms += ms; g_stats.sweep_i8_launches++; g_stats.sweep_i8_macs += r.macs; g_stats.sweep_i8_alg_macs += r.alg; }
         if (r.kind == 2) { g_stats.sweep6_ms += ms; g_stats.sweep6_launches++; g_stats.sweep6_macs += r.macs; g_stats.sweep6_alg_macs += r.alg; }
         if (r.kind == 3 || r.kind == 4) { g_stats.sweep7_ms += ms; g_stats.sweep7_launches++; g_stats.sweep7_macs += r.macs; g_stats.sweep7_alg_macs += r.alg; }
         if (r.kind == 4) { g_stats.sweep7_twin_ms += ms; g_stats.sweep7_twin_launches++; }
@@ -4524,6 +4646,13 @@ static int planes_out(const FusedPlanes& m, uint64_t* out, const char* who, cons
 }
 int p4v_debug_mlp_planes(uint64_t* out) { return planes_out(g_mlp_planes, out, "p4v_debug_mlp_planes", "p4v_mlp_quant_forward"); }
 int p4v_debug_attn_planes(uint64_t* out) { return planes_out(g_attn_planes, out, "p4v_debug_attn_planes", "p4v_attn_quant_forward / p4v_wattn_quant_forward"); }
+int p4v_debug_qkv_planes(uint64_t* out) {
+    const QkvPlanes& m = g_qkv_planes;
+    if (!out) return fail(P4V_ERR_INVALID, "p4v_debug_qkv_planes: null pointer");
+    const uint64_t v[9] = {m.off_q, m.off_k, m.off_v, (uint64_t)m.Z, (uint64_t)m.rows_q, (uint64_t)m.rows_k, (uint64_t)m.ld_qk, (uint64_t)m.rows_v, (uint64_t)m.ld_v};
+    std::copy(v, v + 9, out);
+    return m.Z > 0 ? 0 : fail(P4V_ERR_INVALID, "p4v_debug_qkv_planes: no p4v_qkv_attn_quant_forward call on this thread yet");
+}
 
 int p4v_debug_sos_sweep(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_out, const float* d_grad,
                         int n_cands, int c_lo, int c_hi, int known_cands, float* d_scores, void* d_workspace, size_t workspace_bytes,

@@ -4968,6 +4968,61 @@ __global__ __launch_bounds__(512) void k_sweep_seg(SweepSegParams p) { k_sweep_s
 template <bool TWIN, int EPI>
 __global__ __launch_bounds__(512) void k_sweep_seg_g(GroupArgs<SweepSegParams> a) { P4V_GROUP_ENTER(a); k_sweep_seg_body<TWIN, EPI>(a.p[m_], vb_, vg_); }
 
+// The GEMM loop of the fused forwards' Linear producers (k_mlp_fc1, k_qkv_heads): one 128 x 128 tile of A [.][ldk] x B [.][ldk]^T
+// at rows m0 / n0, int8, on 2 x 4 waves of 64 x 32 -- k_sweep<int8_t>'s staging, fragment and C/D maps, double-buffered through
+// `smem` (2 stages of two SW_TILE_BYTES tiles).  Returns behind the loop's last barrier: the staging LDS is free.
+__device__ __forceinline__ void i8_tile_gemm(const void* A, const void* B, int ldk, int ktiles, int m0, int n0, char* smem, v16i (&acc)[2]) {
+    constexpr int STAGE = 2 * SW_TILE_BYTES;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int wr = wid >> 2, wc = wid & 3;
+    const int g = lane >> 5, l31 = lane & 31;
+    // ---- global -> LDS staging: one 16-byte piece per thread per plane per k-tile ---------------------
+    const int ld_row = tid >> 2, ld_col = (tid & 3) * 16;
+    const char* gA = (const char*)A + (long)(m0 + ld_row) * ldk + ld_col;
+    const char* gB = (const char*)B + (long)(n0 + ld_row) * ldk + ld_col;
+    const int lds_st = ld_row * SW_ROW + ld_col;
+    v4i ra, rb;
+    auto gload = [&](int kt) {
+        ra = *reinterpret_cast<const v4i*>(gA + kt * SW_BKB);
+        rb = *reinterpret_cast<const v4i*>(gB + kt * SW_BKB);
+    };
+    auto lstore = [&](int stage) {
+        char* s = smem + stage * STAGE + lds_st;
+        *reinterpret_cast<v4i*>(s) = ra;
+        *reinterpret_cast<v4i*>(s + SW_TILE_BYTES) = rb;
+    };
+
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][r] = 0;
+
+    const int fa = (wr * 64 + l31) * SW_ROW;       // + i*32*SW_ROW
+    const int fb = SW_TILE_BYTES + (wc * 32 + l31) * SW_ROW;
+
+    gload(0);
+    lstore(0);
+    __syncthreads();
+
+    for (int kt = 0; kt < ktiles; ++kt) {
+        const int stage = kt & 1;
+        if (kt + 1 < ktiles) gload(kt + 1);
+        const char* s = smem + stage * STAGE;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {          // two 32-deep K steps per 64-byte row
+            const int off = h * 32 + g * 16;
+            const v4i b = *reinterpret_cast<const v4i*>(s + fb + off);
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const v4i a = *reinterpret_cast<const v4i*>(s + fa + i * 32 * SW_ROW + off);
+                acc[i] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, acc[i], 0, 0, 0);
+            }
+        }
+        if (kt + 1 < ktiles) lstore(stage ^ 1);
+        __syncthreads();
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // Fused MLP forward, first half (p4v_mlp_quant_forward): fc1's int8 GEMM whose epilogue ends in fc2's int8 row plane(s)
 // ------------------------------------------------------------------------------------------
@@ -5015,52 +5070,8 @@ __device__ __forceinline__ void k_mlp_fc1_body(const MlpFc1Params& p, const uint
     const float bias_n = (p.bias && ncol_ok) ? p.bias[n] : 0.0f;
     const int sb = min(n / p.sb_div, p.s_cs - 1);
 
-    // ---- global -> LDS staging: one 16-byte piece per thread per plane per k-tile ---------------------
-    const int ld_row = tid >> 2, ld_col = (tid & 3) * 16;
-    const char* gA = (const char*)p.A + (long)(m0 + ld_row) * p.ldk + ld_col;
-    const char* gB = (const char*)p.B + (long)(n0 + ld_row) * p.ldk + ld_col;
-    const int lds_st = ld_row * SW_ROW + ld_col;
-    v4i ra, rb;
-    auto gload = [&](int kt) {
-        ra = *reinterpret_cast<const v4i*>(gA + kt * SW_BKB);
-        rb = *reinterpret_cast<const v4i*>(gB + kt * SW_BKB);
-    };
-    auto lstore = [&](int stage) {
-        char* s = smem + stage * STAGE + lds_st;
-        *reinterpret_cast<v4i*>(s) = ra;
-        *reinterpret_cast<v4i*>(s + SW_TILE_BYTES) = rb;
-    };
-
     v16i acc[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][r] = 0;
-
-    const int fa = (wr * 64 + l31) * SW_ROW;       // + i*32*SW_ROW
-    const int fb = SW_TILE_BYTES + (wc * 32 + l31) * SW_ROW;
-
-    gload(0);
-    lstore(0);
-    __syncthreads();
-
-    for (int kt = 0; kt < p.ktiles; ++kt) {
-        const int stage = kt & 1;
-        if (kt + 1 < p.ktiles) gload(kt + 1);
-        const char* s = smem + stage * STAGE;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {          // two 32-deep K steps per 64-byte row
-            const int off = h * 32 + g * 16;
-            const v4i b = *reinterpret_cast<const v4i*>(s + fb + off);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const v4i a = *reinterpret_cast<const v4i*>(s + fa + i * 32 * SW_ROW + off);
-                acc[i] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, acc[i], 0, 0, 0);
-            }
-        }
-        if (kt + 1 < p.ktiles) lstore(stage ^ 1);
-        __syncthreads();
-    }
+    i8_tile_gemm(p.A, p.B, p.ldk, p.ktiles, m0, n0, smem, acc);
 
     // ---- epilogue: scale + bias, GELU, fc2's quantiser; the bytes of the tile into LDS ------------------
     const float s1 = p.S1 ? p.S1[sb] : 1.0f;
@@ -5110,6 +5121,140 @@ __device__ __forceinline__ void k_mlp_fc1_body(const MlpFc1Params& p, const uint
 }
 template <bool TWIN>
 __global__ __launch_bounds__(512) void k_mlp_fc1(MlpFc1Params p) { k_mlp_fc1_body<TWIN>(p, P4V_BIDX, P4V_GDIM); }
+
+// ------------------------------------------------------------------------------------------
+// Fused qkv forward (p4v_qkv_attn_quant_forward): the qkv layer's int8 GEMM whose epilogue ends in the three int8 operand planes
+// of the attention MatMuls
+// ------------------------------------------------------------------------------------------
+// i8_tile_gemm over A = Q(x) [Mp][ldk], B = Q(Wqkv) [Np][ldk].  Output element (m, n): m = image * Ntok + tok, n = which * C +
+// head * D + d (which: 0 q, 1 k, 2 v; C = H * D).  Per element
+//   val = (float)acc * S1[vblock(n)] + bias[n]          EPI_FWD's expression: what qkv.quant_forward stores
+//   byte = clamp(rint(val / iv[which][head]), lo[which], hi[which])      pack_value, PACK_SYM, IEEE division
+// on matmul1's A / B intervals (q, k) and matmul2's B interval (v), each with its operand's own clamp range.  Destinations, z =
+// image * H + head: q and k go to matmul1's operand planes as k_attn_qk reads them, [Z][rows_q | rows_k][ld_qk] at [tok][d]; v
+// goes to matmul2's column plane as its forward sweep reads it, [Z][rows_v][ld_v] at [d][tok] -- transposed, tokens contiguous.
+// The tile's bytes go through the staging LDS (free behind the loop's last barrier): q / k columns row-major, v columns
+// transposed, each 128 x MLP_OROW.  q / k leave as 16-byte pieces where D is a multiple of 16 (a piece then lies in one head, its
+// destination 16-byte aligned: rows are ld_qk = roundup64(D) apart), byte by byte otherwise; v leaves byte by byte, the lanes of
+// a wave on consecutive tokens of one (head, d) row: 64 contiguous bytes, cut where the row tile crosses an image.  A column
+// tile may hold q / k and v columns both (C is no multiple of 128); a row tile holds several images.  Only bytes of valid (m, n)
+// are written: the padding of the three planes (rows >= Ntok, columns >= D, v rows >= D, v columns >= Ntok) is zeroed by the
+// host before the launch.  `qkv_out` (optional) receives val as fp32 [M][N]; a null pointer costs no store.
+struct QkvHeadsParams {
+    const void* A; const void* B;
+    int ldk, ktiles;
+    const float* S1; int s_cs, sb_div;        // combined scale s_a * s_w[block] per V block of qkv (k_scale_table)
+    const float* bias;                        // qkv's bias [N] or nullptr
+    int M, N;                                 // valid rows (images * Ntok); 3 * C
+    int mtiles, ntiles;
+    int Ntok, H, D, C;
+    const float* iv_q; const float* iv_k; const float* iv_v;      // matmul1.A_interval / matmul1.B_interval / matmul2.B_interval [H]
+    int lo_q, hi_q, lo_k, hi_k, lo_v, hi_v;
+    int8_t* Pq; int8_t* Pk; int8_t* Pv;
+    int rows_q, rows_k, ld_qk;                // [Z][rows_q][ld_qk] / [Z][rows_k][ld_qk]
+    int rows_v, ld_v;                         // [Z][rows_v][ld_v]
+    float* qkv_out;
+};
+
+__device__ __forceinline__ void k_qkv_heads_body(const QkvHeadsParams& p, const uint3 blockIdx, const uint3 gridDim) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    static_assert(2 * SW_BM * MLP_OROW <= 4 * SW_TILE_BYTES, "both output tiles must fit the staging buffers");
+
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int wr = wid >> 2, wc = wid & 3;            // 2 x 4 waves, each 64 rows x 32 cols
+    const int g = lane >> 5, l31 = lane & 31;
+    const int nwg = p.mtiles * p.ntiles;
+    const int t = xcd_remap(blockIdx.x, nwg);
+    const int mt = t % p.mtiles, nt = t / p.mtiles;   // m fastest: tiles sharing a Wqkv panel are adjacent
+    const int m0 = mt * SW_BM, n0 = nt * SW_BN;
+
+    const int n = n0 + wc * 32 + l31;
+    const bool ncol_ok = n < p.N;
+    const float bias_n = (p.bias && ncol_ok) ? p.bias[n] : 0.0f;
+    const int sb = min(n / p.sb_div, p.s_cs - 1);
+    // the lane's column: which operand, which head
+    const int nc = ncol_ok ? n : 0;
+    const int which = nc / p.C, head = (nc - which * p.C) / p.D;
+    const float* ivp = which == 0 ? p.iv_q : which == 1 ? p.iv_k : p.iv_v;
+
+    v16i acc[2];
+    i8_tile_gemm(p.A, p.B, p.ldk, p.ktiles, m0, n0, smem, acc);
+
+    // ---- epilogue: scale + bias, the operand's quantiser; the bytes of the tile into LDS ------------------
+    const float s1 = p.S1 ? p.S1[sb] : 1.0f;
+    const float qs = ivp[head];
+    PackParams pv{};
+    pv.mode = PACK_SYM;
+    pv.lo = which == 0 ? p.lo_q : which == 1 ? p.lo_k : p.lo_v;
+    pv.hi = which == 0 ? p.hi_q : which == 1 ? p.hi_k : p.hi_v;
+    char* o = smem;                            // q / k columns: [row][col]
+    char* ot = smem + SW_BM * MLP_OROW;        // v columns: [col][row]
+    const int col_l = wc * 32 + l31;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row_l = wr * 64 + i * 32 + acc32_row(r, g);
+            const int m = m0 + row_l;
+            const bool ok = ncol_ok && m < p.M;
+            const float o_sim = (float)acc[i][r] * s1;
+            const float v = o_sim + bias_n;
+            if (p.qkv_out && ok) p.qkv_out[(long)m * p.N + n] = v;
+            const float b = ok ? pack_value(pv, v, qs) : 0.0f;
+            if (which == 2) ot[col_l * MLP_OROW + row_l] = (char)((int)b & 0xff);
+            else o[row_l * MLP_OROW + col_l] = (char)((int)b & 0xff);
+        }
+    __syncthreads();
+
+    const int C2 = 2 * p.C;
+    // ---- LDS -> global, q / k: contiguous runs of D bytes per (row, head) ---------------------------------
+    if (n0 < C2) {
+        if (p.D % 16 == 0) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int piece = j * 512 + tid;
+                const int row_l = piece >> 3, ch = (piece & 7) * 16;
+                const int m = m0 + row_l, nn = n0 + ch;
+                if (m < p.M && nn < C2) {
+                    const int w = nn / p.C, rem = nn - w * p.C, h = rem / p.D, d = rem - h * p.D;
+                    const int img = m / p.Ntok, tok = m - img * p.Ntok;
+                    const long z = (long)img * p.H + h;
+                    int8_t* dst = w ? p.Pk + (z * p.rows_k + tok) * p.ld_qk + d : p.Pq + (z * p.rows_q + tok) * p.ld_qk + d;
+                    *reinterpret_cast<v4i*>(dst) = *reinterpret_cast<const v4i*>(o + row_l * MLP_OROW + ch);
+                }
+            }
+        } else {
+            // a thread keeps its column and walks the rows four apart
+            const int cl = tid & 127, nn = n0 + cl;
+            if (nn < C2) {
+                const int w = nn / p.C, rem = nn - w * p.C, h = rem / p.D, d = rem - h * p.D;
+                int8_t* base = w ? p.Pk : p.Pq;
+                const int rows = w ? p.rows_k : p.rows_q;
+                for (int row_l = tid >> 7; row_l < SW_BM; row_l += 4) {
+                    const int m = m0 + row_l;
+                    if (m >= p.M) break;
+                    const int img = m / p.Ntok, tok = m - img * p.Ntok;
+                    base[(((long)img * p.H + h) * rows + tok) * p.ld_qk + d] = o[row_l * MLP_OROW + cl];
+                }
+            }
+        }
+    }
+    // ---- LDS -> global, v: a thread keeps its row (token) and walks the columns four apart ------------------
+    if (n0 + SW_BN > C2) {
+        const int row_l = tid & 127, m = m0 + row_l;
+        if (m < p.M) {
+            const int img = m / p.Ntok, tok = m - img * p.Ntok;
+            for (int cl = tid >> 7; cl < SW_BN; cl += 4) {
+                const int nn = n0 + cl;
+                if (nn >= p.N) break;
+                if (nn < C2) continue;
+                const int rem = nn - C2, h = rem / p.D, d = rem - h * p.D;
+                p.Pv[(((long)img * p.H + h) * p.rows_v + d) * p.ld_v + tok] = ot[cl * MLP_OROW + row_l];
+            }
+        }
+    }
+}
+__global__ __launch_bounds__(512) void k_qkv_heads(QkvHeadsParams p) { k_qkv_heads_body(p, P4V_BIDX, P4V_GDIM); }
 
 // ------------------------------------------------------------------------------------------
 // Fused attention forward, first half (p4v_attn_quant_forward): matmul1's int8 GEMM, `* scale`, the softmax over the keys and

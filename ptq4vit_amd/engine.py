@@ -368,6 +368,70 @@ def window_attn_quant_forward(*, q, kT, v, bias, mask=None, qk, pv, want_probs=F
     return _fused_forward("wattn", d, tensors, dev, (out, probs) if want_probs else (out,), want_planes, z=b * H)
 
 
+def qkv_attn_quant_forward(*, x, qkv, scale, qk, pv, want_qkv=False, want_probs=False, want_planes=False):
+    """matmul2(softmax(matmul1(q, kT) * scale, -1), v) with q, kT, v the head slices of qkv(x), all three modules calibrated and
+    in quant_forward, fused (p4v_qkv_attn_quant_forward): the qkv layer's int8 GEMM quantises its output with the quantisers of
+    the MatMul operands and writes their int8 planes; no fp32 qkv tensor, no permute copy and no pack of q, kT, v in between.
+    x [B][N][in_features]; `qkv`: a Linear dict as in mlp_quant_forward (weight [3 * H * D][in_features]); `qk` / `pv`: as in
+    attn_quant_forward -- the head count is the length of qk's A_interval.  Returns out [B][H][N][D]; then, as asked for, the
+    fp32 qkv tensor [B][N][3 * H * D] the planes were quantised from (`want_qkv`), the probabilities [B][H][N][N]
+    (`want_probs`) and the padded int8 planes as the call left them in its workspace (`want_planes`; for the tests): a tuple
+    (Q [B*H][Mp][K1p], Kt [B*H][Np][K1p], V [B*H][NpB][Kp], P1[, P2] [B*H][Mp][Kp])."""
+    who = "qkv_attn_quant_forward"
+    lib = _lib.load()
+    dev = device_of(x, qkv["weight"])
+    x = to_dev(x, dev).contiguous()
+    if x.dim() != 3:
+        raise ValueError(f"{who}: x {tuple(x.shape)} is not [batch][tokens][in_features]")
+    B, N, _ = x.shape
+    w = to_dev(qkv["weight"], dev).contiguous()
+    bias = to_dev(qkv.get("bias"), dev)
+    flat = lambda t: to_dev(t, dev).reshape(-1).contiguous()
+    qk_A, qk_B, pv_A, pv_B = flat(qk["A_interval"]), flat(qk["B_interval"]), flat(pv["A_interval"]), flat(pv["B_interval"])
+    H = qk_A.numel()
+    sos = bool(pv.get("sos", False))
+    if qk.get("sos", False):
+        raise NotImplementedError(f"{who}: q k^T is no split-of-softmax operand (sos belongs on p v)")
+    if qk_B.numel() != H or pv_B.numel() != H or pv_A.numel() != (1 if sos else H):
+        raise ValueError(f"{who}: interval tensors must hold one value per head (the split-of-softmax A: one)")
+    if w.shape[0] % (3 * H):
+        raise ValueError(f"{who}: qkv's out_features = {w.shape[0]} is not 3 x {H} heads x head_dim")
+    D = w.shape[0] // (3 * H)
+    d = _lib.QkvAttnDesc()
+    d.qkv = _mlp_layer_desc(B, N, qkv)
+    # (the operand strides are not read: no fp32 q, kT, v exists; filled as the contiguous tensors would have them)
+    q_shape, kT_shape, v_shape = (B, H, N, D), (B, H, D, N), (B, H, N, D)
+    cont = lambda s: (s[1] * s[2] * s[3], s[2] * s[3], s[3], 1)
+    like = lambda s: torch.empty(s, device="meta")
+    _attn_matmul_desc(d.qk, q_shape, cont(q_shape), like(kT_shape), qk, "q k^T", who)
+    _attn_matmul_desc(d.pv, (B, H, N, N), cont((B, H, N, N)), like(v_shape), pv, "p v", who)
+    d.scale, d.reserved = float(scale), 0
+    sp = flat(pv["split"]) if sos else None
+    out = torch.empty(B, H, N, D, dtype=torch.float32, device=dev)
+    qkv_out = torch.empty(B, N, w.shape[0], dtype=torch.float32, device=dev) if want_qkv else None
+    probs = torch.empty(B, H, N, N, dtype=torch.float32, device=dev) if want_probs else None
+    ws = workspace(dev, _need(lib.p4v_qkv_attn_workspace_bytes, d, "p4v_qkv_attn_workspace_bytes"))
+    tensors = dict(x=x, w=w, bias=bias, w_interval=flat(qkv["w_interval"]), a_interval=flat(qkv["a_interval"]), qk_A_interval=qk_A,
+                   qk_B_interval=qk_B, pv_A_interval=pv_A, pv_B_interval=pv_B, split=sp, out=out, qkv_out=qkv_out, probs=probs)
+    with torch.cuda.device(dev):
+        rec = _lib.QkvAttnTensors(**{n: ptr(t) for n, t in tensors.items()}, ws=ptr(ws), ws_bytes=ws.numel())
+        rc = lib.p4v_qkv_attn_quant_forward(C.byref(d), C.byref(rec), stream_ptr(dev))
+    _lib.check(rc, "p4v_qkv_attn_quant_forward")
+    res = (out,) + ((qkv_out,) if want_qkv else ()) + ((probs,) if want_probs else ())
+    if want_planes:
+        info = (C.c_uint64 * 9)()
+        _lib.check(lib.p4v_debug_qkv_planes(info), "p4v_debug_qkv_planes")
+        off_q, off_k, off_v, Z, rows_q, rows_k, ld_qk, rows_v, ld_v = (int(v) for v in info)
+        take = lambda off, rows, ld: ws[off:off + Z * rows * ld].view(torch.int8).reshape(Z, rows, ld).clone()
+        planes = (take(off_q, rows_q, ld_qk), take(off_k, rows_k, ld_qk), take(off_v, rows_v, ld_v))
+        info = (C.c_uint64 * 5)()
+        _lib.check(lib.p4v_debug_attn_planes(info), "p4v_debug_attn_planes")
+        off1, off2, rows, cols, twin = (int(v) for v in info)
+        planes += tuple(take(off, rows // Z, cols) for off in ((off1, off2) if twin else (off1,)))
+        res += (planes,)
+    return res[0] if len(res) == 1 else res
+
+
 def matmul_quant_forward(*, A, B, A_interval, B_interval, split, A_bit, B_bit, sos=False):
     """quant_forward of a calibrated MatMul (head-wise intervals; optional split-of-softmax twin on A)."""
     lib = _lib.load()

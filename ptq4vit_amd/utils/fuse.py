@@ -21,6 +21,13 @@ module's -- qkv, `q * self.scale` in torch (matmul1 was calibrated on the scaled
 -- and replaces matmul1 -> `+ bias` -> `+ mask` -> softmax -> matmul2 by engine.window_attn_quant_forward
 (p4v_wattn_quant_forward) under fuse_attention's per-call conditions and one more: the mask is None or a
 float32 [nW][N][N] tensor with B_ % nW == 0.  Each of the three fuse_* keeps its own saved forward: they compose in any order.
+
+`fuse_qkv_attention(net)` / `takes_fused_qkv_attention_path(m, x)` take the qkv layer of a `models.Attention` into the chain
+(engine.qkv_attn_quant_forward / p4v_qkv_attn_quant_forward): qkv's GEMM writes the int8 operand planes of
+the two MatMuls.  It shares fuse_attention's saved forward -- the two do not stack, the later call decides which forward is
+installed, unfuse_attention undoes either -- and its patched forward decides per call: the qkv-fused path when fuse_attention's
+conditions hold and qkv is calibrated, in quant_forward, on the int8 path, unhooked, n_H = n_a = 1, no post-GELU layer, 3 * C
+wide; otherwise fuse_attention's path where its conditions hold; otherwise the original forward.
 """
 import os
 import types
@@ -100,13 +107,17 @@ def _fused_forward(self, x):
     return self.__dict__[_ORIG](x)
 
 
-def _patch(net, predicate, attr, forward):
+def _patch(net, predicate, attr, forward, replace=False):
+    """`replace`: two patched forwards share `attr` -- a container that already carries one gets `forward` installed over it,
+    its saved original stays."""
     names = []
     for name, m in net.named_modules():
         if not predicate(m):
             continue
         if attr not in m.__dict__:
             m.__dict__[attr] = m.forward
+            m.forward = types.MethodType(forward, m)
+        elif replace:
             m.forward = types.MethodType(forward, m)
         names.append(name)
     return names
@@ -192,13 +203,61 @@ def _fused_attention_forward(self, x):
 
 
 def fuse_attention(net):
-    """Patch the forward of every fusable Attention container of `net`; returns their names.  Idempotent."""
-    return _patch(net, attention_fusable, _ORIG_ATTN, _fused_attention_forward)
+    """Patch the forward of every fusable Attention container of `net`; returns their names.  Idempotent.  On a container
+    fuse_qkv_attention patched it replaces that forward (the two share the saved forward: the later call decides)."""
+    return _patch(net, attention_fusable, _ORIG_ATTN, _fused_attention_forward, replace=True)
 
 
 def unfuse_attention(net):
-    """Undo fuse_attention: every patched container gets its original forward back; returns their names.  Idempotent."""
+    """Undo fuse_attention or fuse_qkv_attention: every patched container gets its original forward back; returns their names.
+    Idempotent."""
     return _unfuse(net, _ORIG_ATTN)
+
+
+# ---- qkv in front of the attention chain (engine.qkv_attn_quant_forward, DESIGN.md s5.11) -------------------------------------------
+# The qkv layer's GEMM writes the int8 operand planes of the two MatMuls: p4v_qkv_attn_quant_forward takes, beyond
+# p4v_attn_quant_forward's envelope, a qkv layer with n_H = n_a = 1 that is no post-GELU layer and whose out_features are 3 * C.
+# Same saved-forward attribute as fuse_attention: the two patch the same containers and cannot stack.
+def qkv_attention_fusable(m):
+    """The static half of the decision: an Attention container whose forward `fuse_qkv_attention` patches."""
+    return attention_fusable(m) and isinstance(m.qkv, PTQSLQuantLinear)
+
+
+def _qkv_attn_args(m, x):
+    """(qkv's, matmul1's, matmul2's engine keywords) if the patched forward of `m` runs the qkv-fused chain on `x`, else None."""
+    if not qkv_attention_fusable(m):
+        return None
+    args = _attn_args(m, x)
+    if args is None:
+        return None
+    qkv = m.qkv
+    if not (_live(qkv) and qkv._int8_ready(x)) or x.shape[-1] != qkv.in_features or qkv.out_features != 3 * x.shape[-1]:
+        return None
+    lin = qkv._int8_args()
+    if lin["postgelu"] or lin["n_H"] != 1 or lin["n_a"] != 1:
+        return None
+    return (lin,) + args
+
+
+def takes_fused_qkv_attention_path(m, x):
+    """The per-call half: would the patched forward of `m` run the qkv-fused kernel chain on `x`?"""
+    return _qkv_attn_args(m, x) is not None
+
+
+def _fused_qkv_attention_forward(self, x):
+    args = _qkv_attn_args(self, x)
+    if args is None:
+        return _fused_attention_forward(self, x)      # (fuse_attention's path where its conditions hold, else the original)
+    # models.Attention.forward, with qkv ... matmul2 as one engine call
+    B, N, C = x.shape
+    out = engine.qkv_attn_quant_forward(x=x, qkv=args[0], scale=self.scale, qk=args[1], pv=args[2])
+    return self.proj_drop(self.proj(out.transpose(1, 2).reshape(B, N, C)))
+
+
+def fuse_qkv_attention(net):
+    """Patch the forward of every Attention container of `net` that fuse_attention would patch and whose qkv is a PTQSL Linear
+    layer; returns their names.  Idempotent.  On a container fuse_attention patched it replaces that forward."""
+    return _patch(net, qkv_attention_fusable, _ORIG_ATTN, _fused_qkv_attention_forward, replace=True)
 
 
 # ---- window attention (Swin): matmul1 -> + bias -> + mask -> softmax -> matmul2 (engine.window_attn_quant_forward, DESIGN.md s5.10) ----

@@ -12,6 +12,8 @@ for the GEMMs (k_mlp_fc1, the fc2 sweep), torch's profiler for everything (k_pac
 matmul1's sweep, torch's `* scale` and softmax and k_pack_dual; on a Swin net fuse_window_attention: the window instances of
 k_attn_qk in place of matmul1's sweep, torch's `+ bias`, `+ mask` and softmax and k_pack_dual); with --fused it is MLPs +
 attention, without it attention alone.
+--fused-qkv: a fourth variant in the same alternation: fuse_qkv_attention in place of fuse_attention (k_qkv_heads in place of the
+qkv sweep, the permute copy and the three k_pack1 of q, k^T and v), on top of the fused MLPs with --fused.
 """
 import argparse
 import hashlib
@@ -94,6 +96,8 @@ def main():
     ap.add_argument("--fused", action="store_true", help="also time the network with fused MLPs (utils/fuse.py), alternating")
     ap.add_argument("--fused-attn", action="store_true",
                     help="also time the network with fused attention (utils/fuse.py::fuse_attention and fuse_window_attention; with --fused: on top of the fused MLPs)")
+    ap.add_argument("--fused-qkv", action="store_true",
+                    help="also time the network with the qkv layer fused into the attention chain (utils/fuse.py::fuse_qkv_attention; with --fused: on top of the fused MLPs)")
     ap.add_argument("--json", default=None, help="write the result to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -130,19 +134,23 @@ def main():
           f"logit rel diff {((y_q - y_raw).norm() / y_raw.norm()).item():.3e}")
     res = {"model": a.model, "batch": a.batch, "reps": a.reps, "source_hash": _lib.source_hash(),
            "raw_fp32_ms": t_raw * 1e3, "quant_forward_ms": t_q * 1e3, "quant_vs_fp32": t_raw / t_q}
-    if a.fused or a.fused_attn:
-        # the variants alternating, repetition by repetition, after one warm-up of each: (key, fuse the MLPs, fuse the attention)
+    if a.fused or a.fused_attn or a.fused_qkv:
+        # the variants alternating, repetition by repetition, after one warm-up of each: (key, fuse the MLPs, fuse the attention --
+        # "qkv": with the qkv layer)
         variants = [("unfused", False, False)]
         if a.fused:
             variants.append(("fused", True, False))
         if a.fused_attn:
             variants.append(("fused_attn", a.fused, True))
+        if a.fused_qkv:
+            variants.append(("fused_qkv", a.fused, "qkv"))
 
         def setup(mlp, attn):
             fuse.unfuse_mlp(net)
             fuse.unfuse_attention(net)
             fuse.unfuse_window_attention(net)
-            return (len(fuse.fuse_mlp(net)) if mlp else 0, len(fuse.fuse_attention(net)) + len(fuse.fuse_window_attention(net)) if attn else 0)
+            fuse_attn = fuse.fuse_qkv_attention if attn == "qkv" else fuse.fuse_attention
+            return (len(fuse.fuse_mlp(net)) if mlp else 0, len(fuse_attn(net)) + len(fuse.fuse_window_attention(net)) if attn else 0)
 
         ts = {key: [] for key, _, _ in variants}
         ys, counts = {}, {}
@@ -162,6 +170,12 @@ def main():
                 print(f"  unfused {t_u * 1e3:.2f} ms, fused MLPs ({n_mlp}) {t_v * 1e3:.2f} ms: x{t_u / t_v:.3f}; "
                       f"fused vs fp32 x{t_raw / t_v:.2f}; logit rel diff fused vs unfused {rel:.3e}")
                 res["fused_mlps"] = n_mlp
+            elif key == "fused_qkv":
+                base_key = "fused_attn" if a.fused_attn else "fused" if a.fused else "unfused"
+                print(f"  fused qkv + attention ({n_attn}{' + MLPs' if a.fused else ''}) {t_v * 1e3:.2f} ms: x{med[base_key] / t_v:.3f} "
+                      f"over {base_key} ({(med[base_key] - t_v) * 1e3:+.3f} ms), x{t_u / t_v:.3f} over unfused; logit rel diff vs unfused {rel:.3e}")
+                res.update({"fused_qkv_attentions": n_attn, "fused_qkv_with_mlps": bool(a.fused), base_key + "_over_fused_qkv": med[base_key] / t_v,
+                            base_key + "_minus_fused_qkv_ms": (med[base_key] - t_v) * 1e3})
             else:
                 base_key = "fused" if a.fused else "unfused"
                 print(f"  fused attention ({n_attn}{' + MLPs' if a.fused else ''}) {t_v * 1e3:.2f} ms: x{med[base_key] / t_v:.3f} "

@@ -40,7 +40,7 @@ def set_bits(cfg, bits):
 
 
 def evaluate(model, imagenet, weights=None, config="PTQ4ViT", bits=8, calib=32, calib_seed=3, batch=128, max_val=None,
-             workers=0, save_intervals=None, device="cuda", quiet=False, fuse_mlp=False, fuse_attn=False):
+             workers=0, save_intervals=None, device="cuda", quiet=False, fuse_mlp=False, fuse_attn=False, fuse_qkv=False):
     """Returns the result dict (see the module docstring).  `weights=None` keeps the seeded random initialisation (tests)."""
     import contextlib
     import importlib
@@ -91,6 +91,9 @@ def evaluate(model, imagenet, weights=None, config="PTQ4ViT", bits=8, calib=32, 
     if fuse_attn:                              # opt-in: matmul1 ... matmul2 of every attention block as the fused int8 chain
         from ptq4vit_amd.utils.fuse import fuse_attention as _fuse_attn, fuse_window_attention as _fuse_wattn
         fused_attn = _fuse_attn(net) + _fuse_wattn(net)        # (a net has Attention or WindowAttention blocks)
+    if fuse_qkv:                               # opt-in: qkv ... matmul2 of every ViT / DeiT attention block as one fused int8 chain
+        from ptq4vit_amd.utils.fuse import fuse_qkv_attention as _fuse_qkv
+        fused_attn = _fuse_qkv(net) or fused_attn
     t0 = time.time()
     quant = datasets.test_classification(net, test_loader, max_iteration=max_it, description=None if quiet else f"{model} W{bits}A{bits}")
     t_q = time.time() - t0
@@ -118,11 +121,12 @@ def main(argv=None):
     ap.add_argument("--json", default=None, help="also write the result line to this file")
     ap.add_argument("--fuse-mlp", action="store_true", help="evaluate with the fused int8 MLP forward (utils/fuse.py::fuse_mlp)")
     ap.add_argument("--fuse-attn", action="store_true", help="evaluate with the fused int8 attention forward (utils/fuse.py::fuse_attention, fuse_window_attention)")
+    ap.add_argument("--fuse-qkv", action="store_true", help="evaluate with the qkv layer fused into the attention chain (utils/fuse.py::fuse_qkv_attention)")
     a = ap.parse_args(argv)
     import ptq4vit_amd
     ptq4vit_amd.configure_runtime()          # GPU_MAX_HW_QUEUES for the search streams, before the first GPU call
     res = evaluate(a.model, a.imagenet, a.weights, a.config, a.bits, a.calib, a.calib_seed, a.batch, a.max_val, a.workers,
-                   a.save_intervals, fuse_mlp=a.fuse_mlp, fuse_attn=a.fuse_attn)
+                   a.save_intervals, fuse_mlp=a.fuse_mlp, fuse_attn=a.fuse_attn, fuse_qkv=a.fuse_qkv)
     line = json.dumps(res)
     print(line)
     if a.json:
