@@ -128,6 +128,19 @@ typedef struct p4v_matmul_desc {
     int32_t M, K, N;            /* A: (batch,heads,M,K)  B: (batch,heads,K,N) */
     int64_t a_stride[4];        /* element strides of A for (batch, head, m, k) */
     int64_t b_stride[4];        /* element strides of B for (batch, head, k, n) */
+                                /* Every p4v_matmul_* / p4v_matmul_blocks_* / p4v_sos_* / p4v_amax_init_matmul* entry point, a
+                                   member of p4v_calibrate_group and both fused attention forwards read A and B in place through
+                                   these strides (pinned by tests/test_hip_matmul_layouts.py):
+                                   - any NON-NEGATIVE element strides, in any order and with gaps: a transposed operand, a
+                                     slice of a packed [batch][tokens][3][heads][dim] qkv tensor, padded rows,
+                                     stride[0] < stride[1]; 0 is allowed on every axis and reads the same elements again
+                                     (an expanded batch, stride[0] = 0: supported by every path, none refuses it);
+                                   - the base pointer aligned to 4 bytes, no more (rows and slices need no alignment: a path
+                                     with 16-byte loads tests its condition per call and takes 4-byte loads otherwise);
+                                   - what the strides do not address never enters a result, and A and B are never written;
+                                   - the result does not depend on the layout: bit-identical to the call on a dense copy.
+                                   Not covered: element offsets of 2^31 and above, batch * heads above 65 535.
+                                   raw_out / raw_grad stay dense [batch][heads][M][N]. */
     int32_t A_bit, B_bit;       /* 2..8 each, independently; anything else: P4V_ERR_UNSUPPORTED before any launch */
     int32_t metric;
     int32_t eq_n;

@@ -33,6 +33,12 @@ def record_margin(kind, value, extra=None):
             e[k] = e.get(k, 0) + v
 
 
+def record_note(key, value):
+    """A fact of the running test that is no worst-case figure or count (the kernels it recorded, ...): kept as given."""
+    test = os.environ.get("PYTEST_CURRENT_TEST", "?").split(" ")[0]
+    _MARGINS.setdefault(test, {})[key] = value
+
+
 def _dump_margins():
     if not _MARGINS:
         return
