@@ -34,6 +34,36 @@ int p4v_debug_set_tuning(int key, int value);
  * [candidate][score block] table in table order.  Nothing but the bound may depend on these numbers (csrc/p4v_api.hip::
  * run_pass_pruned); exposed so that a test can hold two stage-B1 kernels against each other within prune_margin. */
 int p4v_debug_bound_totals(float* out, int64_t capacity, int64_t* count);
+/* The stage tables of the pruned search passes of the calling thread (csrc/p4v_api.hip::run_pass_pruned_impl,
+ * run_sos_split_pruned_impl).  out == NULL and count == NULL: start keeping them (costs copies of every table and a stream
+ * synchronise per staged pass; not inside p4v_calibrate_group).  Otherwise: stop, *count = the 32-bit words kept, out receives
+ * min(capacity, *count) of them.  One record per staged pass (p4v_prune_counters[0] counts the same passes), appended at
+ * whichever exit the pass takes, floats by their bits:
+ *   [0] words of the record  [1] 0 search pass, 1 split search  [2] search round, [3] side (0 = w / A / split, 1 = a / B) of the
+ *   fused call, -1 outside one  [4] eq_n  [5] nj  [6] virt  [7] hull_selects  [8] b1_bound  [9] the second tier ran
+ *   [10] the host read the survivors  [11] the margin (float)  [12] rows of stage B1's table (virt: 1, the synthetic candidate)
+ *   [13] SA2 follows  [14] S2 follows (stage B2 ran; after the merge)  [15] per-block ranges kept  [16..21] r1, r2, r3 (lo, hi)
+ *   [22], [23] rows per segment of the two slices;
+ *   then best_idx [nj], rblk2 [2 nj], rblk3 [2 nj], SA [eq_n][nj], SB [rows][nj], SA2 [eq_n][nj], S2 [eq_n][nj].
+ * What the pass did not write is -1 (r3, rblk3, best_idx) or absent (SA2, S2).  For the tests of the two premises of the exact
+ * pruning: the stage-A scores are upper bounds of the totals, and the decision kernels pick what k_select picks from the totals. */
+int p4v_debug_prune_tables(int32_t* out, int64_t capacity, int64_t* count);
+/* The decision chain of a pruned pass on tables of the caller: k_prune_pick -> stage B1 -> k_prune_hull (-> stage A2 ->
+ * k_prune_hull) -> stage B2 -> k_merge_scores / k_merge_virtual -> k_select through the launchers of run_pass_pruned_impl, with
+ * no sweep: the stages are what k_finish would leave of the full totals d_T [C][nj] -- stage B1 holds T on r1 for every block
+ * and -inf elsewhere (virt: T[best[j]][j] in row 0), stage A2 holds d_SA2 (optional: no second tier without it) and stage B2
+ * holds T where the candidate lies in the hull's range and, with honour_blk, in the block's own range; -inf elsewhere.
+ * d_SA [C][nj]: the stage-A scores.  d_cands [C + 1][nj]: the candidate table (row c, column j: the interval candidate c gives
+ * block j).  virt: stage B1 on the synthetic candidate (needs nj > 1).  host_reads: the host reads the survivor ranges and a pass
+ * without survivors ends without stage B2.  hull_selects follows plan_prune's rule.
+ * Out, all on the device: d_ranges [6] = r1, r2, r3; d_rblk [4 nj] = the per-block ranges of the two hulls; d_best [nj] = the
+ * stage-A winners (virt); d_interval [nj], d_best_out [nj] = the selection.  What a branch does not write is -1.  info (host,
+ * [3]): hull_selects, the second tier ran, the exit (0 merge and k_select, 1 / 2 no stage B2 after the first / second hull).
+ * Null pointers, C < 1, nj < 1, nj > 4096 and virt with nj == 1 are P4V_ERR_INVALID before anything is launched.  Synchronises
+ * the stream (several times: it builds the stage tables on the host). */
+int p4v_debug_prune_decide(const float* d_SA, const float* d_SA2, const float* d_T, const float* d_cands, int C, int nj, int virt,
+                           int honour_blk, int host_reads, int32_t* d_ranges, int32_t* d_rblk, int32_t* d_best, float* d_interval,
+                           int32_t* d_best_out, int32_t* info, void* stream);
 /* The arena that carves the caller's workspace, for the tests of the workspace contract (include/ptq4vit_hip.h, Conventions).
  * p4v_debug_set_arena_gap: with a non-zero value every allocation of the arena -- from the bottom and from the top, in the sizing
  * run of *_workspace_bytes() as well, which then includes the gaps -- leaves that many bytes unused behind it; a poisoned workspace

@@ -153,6 +153,7 @@ EXPORTS = [
     "p4v_debug_set_variant", "p4v_debug_set_tuning", "p4v_debug_bound_totals", "p4v_debug_topk_rows", "p4v_debug_pack_dual", "p4v_debug_prep_epi6",
     "p4v_debug_pack_cands", "p4v_debug_gather_im2col", "p4v_debug_sos_sweep",
     "p4v_debug_set_arena_gap", "p4v_debug_arena_ranges", "p4v_debug_mlp_planes", "p4v_debug_attn_planes", "p4v_debug_qkv_planes",
+    "p4v_debug_prune_tables", "p4v_debug_prune_decide",
 ]
 
 _lib = None
@@ -277,6 +278,10 @@ def load():
     lib.p4v_debug_arena_ranges.argtypes = [C.POINTER(C.c_uint64), C.c_int]
     lib.p4v_debug_bound_totals.restype = C.c_int
     lib.p4v_debug_bound_totals.argtypes = [fp, C.c_int64, C.POINTER(C.c_int64)]
+    lib.p4v_debug_prune_tables.restype = C.c_int
+    lib.p4v_debug_prune_tables.argtypes = [C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64)]
+    lib.p4v_debug_prune_decide.restype = C.c_int
+    lib.p4v_debug_prune_decide.argtypes = [fp, fp, fp, fp] + [C.c_int] * 5 + [ip, ip, ip, fp, ip, C.POINTER(C.c_int32), vp]
     lib.p4v_stats_enable.restype = C.c_int
     lib.p4v_stats_enable.argtypes = [C.c_int]
     lib.p4v_stats_reset.restype = C.c_int

@@ -127,6 +127,11 @@ thread_local std::vector<StatRec> g_stat_recs;
 thread_local std::vector<StatRec> g_stat_done;   // drained records, kept until p4v_stats_reset (p4v_stats_launches)
 thread_local bool g_b1_keep = false;            // p4v_debug_bound_totals: keep the stage-B1 totals of this thread's pruned passes
 thread_local std::vector<float> g_b1_totals;
+// p4v_debug_prune_tables: keep the stage tables of this thread's pruned passes (keep_prune_tables: the record's layout).  A record
+// is 32-bit words, the floats by their bits.  g_pass_round / g_pass_side: which pass of the call search_rounds is running (-1: none)
+thread_local bool g_tables_keep = false;
+thread_local std::vector<int32_t> g_tables;
+thread_local int g_pass_round = -1, g_pass_side = -1;
 // Which stage of a pruned pass is being launched: a label for the launch records and the prints, nothing decides by it.  Set by
 // run_stage only (and cleared per call at the group entry); _lib.py maps the numbers to the record strings.
 enum PruneStage { STAGE_FULL = 0, STAGE_A = 1, STAGE_B1 = 2, STAGE_B2 = 3, STAGE_A2 = 4 };   // A2: the second tier's slice sweep
@@ -1890,6 +1895,9 @@ struct PrunePlan {
     bool hull_selects;        // k_prune_hull makes the selection when nothing survives besides stage B1's candidates
     bool b1_bound;            // stage B1 is ONE candidate per score block over all samples on a layout k_bound takes
 };
+// k_prune_hull makes the pass's selection when nothing survives besides stage B1's candidates (its non-virt selection is serial over
+// the blocks: up to 32 of them).  plan_prune and p4v_debug_prune_decide.
+inline bool prune_hull_selects(bool scores_out, bool interval, bool virt, int nj) { return !scores_out && interval && (virt || nj <= 32); }
 // The only place that decides whether a pass is staged and with what geometry (DESIGN.md s5.1 lists the tests in this order).
 // Allocates nothing; reads the module's slice cache for what earlier passes of the module found out.
 PruneOutcome plan_prune(const Ctx& c, const Pass& ps, PrunePlan& pl) {
@@ -1939,7 +1947,7 @@ PruneOutcome plan_prune(const Ctx& c, const Pass& ps, PrunePlan& pl) {
     pl.geo2 = pl.geo;
     pl.geo2.k = pl.geo2.k_cap = pl.k2;
     pl.virt = ps.nj > 1 && ps.cand_off == 0 && ps.cand_js * ps.nj == ps.cand_cs && ps.cand_cs <= 4096;
-    pl.hull_selects = !ps.scores_out && ps.interval && (pl.virt || ps.nj <= 32);   // (its non-virt selection is serial over the blocks)
+    pl.hull_selects = prune_hull_selects(ps.scores_out != nullptr, ps.interval != nullptr, pl.virt, ps.nj);
     // ONE candidate per score block over all samples: the kernel built for that (k_bound).
     // Its totals are summed in another order than the sweeps', so from stage B1 on nothing may depend on its numbers but the
     // bound: the selections are either "the only survivor of every block" (no totals involved) or come from stage B2, which
@@ -1959,6 +1967,10 @@ PruneOutcome plan_prune(const Ctx& c, const Pass& ps, PrunePlan& pl) {
 // u = 2^-24; the slice sum and the bound each carry one such error, so 2 n u = 1.6e-5 bounds their disagreement and the margin
 // is 4 x that, never below the 1e-4 of round 3 (which is therefore what is used; a kernel with a longer fp32 chain must raise
 // PRUNE_FP32_CHAIN).  Variant 134217728 cross-checks every pruned pass against the full sweep (tests).
+// "The same arithmetic" is measured, stage A running on other kernels than the totals (k_slice_a / k_slice_b2 against k_sweep9,
+// slice-shaped launches of the sweeps, k_sos_split on 16 rows): with raw_grad exactly zero outside the slice's rows the slice sum
+// and the total are the same sum, and every pairing agrees to <= 2.4e-7 relative, 0.015 of the 1.6e-5
+// (tests/test_hip_prune_premises.py, p4v_debug_prune_tables; profiles/r31_prune_premises_margins.json).
 constexpr int PRUNE_FP32_CHAIN = 128 + 6;
 inline float prune_margin() { return std::max(1e-4f, 4.0f * 2.0f * (float)PRUNE_FP32_CHAIN * 5.9604645e-8f); }
 // The debug cross-check: `pruned_fn`, then `full_fn` -- the full sweep of the same pass into the same `interval` --; the n
@@ -2254,15 +2266,56 @@ int keep_b1_totals(Ctx& c, const float* SB, size_t n) {
     for (float v : h) if (v != -INFINITY) g_b1_totals.push_back(v);
     return 0;
 }
+// p4v_debug_prune_tables (tests): one record per staged pass, appended at the exit the pass takes.  Words of a record (include/
+// ptq4vit_hip_debug.h has the same list): [0] its length, [1] 0 search pass / 1 split search, [2] round, [3] side, [4] eq_n, [5] nj,
+// [6] virt, [7] hull_selects, [8] b1_bound, [9] tier 2 ran, [10] the host read the survivors, [11] the margin, [12] rows of SB's
+// table (virt: 1), [13] SA2 follows, [14] S2 follows, [15] per-block ranges kept, [16..21] r1, r2, r3, [22] / [23] rows of the two
+// slices; then best_idx [nj], rblk2 [2 nj], rblk3 [2 nj], SA [eq_n][nj], SB [rows][nj], SA2, S2 [eq_n][nj].  What a pass did not
+// write is -1 (ranges) or absent (tables).
+struct PruneKept {
+    int kind, eq_n, nj; bool virt, hull_selects, b1_bound, tier2, host_read; int sb_rows, k, k2;
+    const float *SA, *SB, *SA2, *S2; const int *r, *best_idx, *rblk;
+};
+constexpr int PRUNE_KEPT_HDR = 24;
+int keep_prune_tables(Ctx& c, const PruneKept& k) {
+    if (!g_tables_keep || c.dry || c.grp) return 0;
+    const size_t nj = (size_t)k.nj, tab = (size_t)k.eq_n * nj, sb = (size_t)k.sb_rows * nj;
+    const size_t words = PRUNE_KEPT_HDR + 5 * nj + tab + sb + (k.SA2 ? tab : 0) + (k.S2 ? tab : 0);
+    std::vector<int32_t> rec(words, -1);
+    const float margin = prune_margin();
+    const int32_t hdr[16] = {(int32_t)words, k.kind, g_pass_round, g_pass_side, k.eq_n, k.nj, k.virt, k.hull_selects, k.b1_bound, k.tier2,
+                             k.host_read, 0, k.sb_rows, k.SA2 != nullptr, k.S2 != nullptr, k.rblk != nullptr};
+    std::copy(hdr, hdr + 16, rec.begin());
+    std::memcpy(&rec[11], &margin, sizeof margin);
+    rec[22] = k.k; rec[23] = k.k2;
+    int32_t* w = rec.data() + PRUNE_KEPT_HDR;
+    CHK(q_d2h(c, &rec[16], k.r, sizeof(int) * (k.tier2 ? 6 : 4)));
+    if (k.virt) CHK(q_d2h(c, w, k.best_idx, sizeof(int) * nj));
+    w += nj;
+    if (k.rblk) CHK(q_d2h(c, w, k.rblk, sizeof(int) * (k.tier2 ? 4 : 2) * nj));
+    w += 4 * nj;
+    CHK(q_d2h(c, w, k.SA, sizeof(float) * tab)); w += tab;
+    CHK(q_d2h(c, w, k.SB, sizeof(float) * sb)); w += sb;
+    if (k.SA2) { CHK(q_d2h(c, w, k.SA2, sizeof(float) * tab)); w += tab; }
+    if (k.S2) { CHK(q_d2h(c, w, k.S2, sizeof(float) * tab)); w += tab; }
+    CHK(q_sync(c));
+    g_tables.insert(g_tables.end(), rec.begin(), rec.end());
+    return 0;
+}
 // nothing survives besides stage B1's candidates: the pass's selection without another sweep
-int select_without_b2(Ctx& c, const Pass& ps, const PrunePlan& pl, const PruneBufs& b) {
-    PRUNE_COUNT(PRUNE_NO_SURVIVORS);
+int select_from_b1(Ctx& c, const Pass& ps, const PrunePlan& pl, const PruneBufs& b) {
     if (pl.hull_selects) {}          // k_prune_hull made the selection
     else if (pl.virt) {              // every block's only survivor is its stage-A winner: the table with those entries filled in
         CHK(enqueue(c, KERN(FillParams, k_fill_f32), dim3(cdiv((long)b.tab, 256)), dim3(256), 0, FillParams{b.S2, -INFINITY, (int)b.tab}));
         CHK(enqueue(c, KERN(MergeVirtParams, k_merge_virtual), dim3(cdiv(ps.nj, 64)), dim3(64), 0, MergeVirtParams{b.S2, b.SB, b.best_idx, ps.nj}));
         CHK(launch_pass_select(c, ps, b.S2));
     } else CHK(launch_pass_select(c, ps, b.SB));
+    return 0;
+}
+int select_without_b2(Ctx& c, const Pass& ps, const PrunePlan& pl, const PruneBufs& b, const PruneKept& kept) {
+    PRUNE_COUNT(PRUNE_NO_SURVIVORS);
+    CHK(keep_prune_tables(c, kept));
+    CHK(select_from_b1(c, ps, pl, b));
     c.ws.off = b.mark;
     return 0;
 }
@@ -2290,10 +2343,14 @@ int run_pass_pruned_impl(Ctx& c, Pass& ps) {
     attach_mirror(hsl);
     pp.r_out = b.r2; pp.rblk = b.rblk2;
     CHK(launch_hull(c, pp, hsl, hm, MIR_R1, MIR_RB1));
+    auto kept = [&](bool tier2, const float* S2) {       // p4v_debug_prune_tables: what this pass leaves at the exit it takes
+        return PruneKept{0, ps.eq_n, ps.nj, pl.virt, pl.hull_selects, pl.b1_bound, tier2, host_reads, b1.eq_n, pl.k, tier2 ? pl.k2 : 0,
+                         b.SA, b.SB, tier2 ? b.SA2 : nullptr, S2, b.r1, b.best_idx, b.rblk2};
+    };
     Survivors s1, s2;
     if (host_reads) {
         CHK(read_survivors(c, b.r2, hm, MIR_R1, MIR_RB1, ps.nj, s1));
-        if (!s1.count) return select_without_b2(c, ps, pl, b);     // the ~10 launches of an empty stage B2 are not made
+        if (!s1.count) return select_without_b2(c, ps, pl, b, kept(false, nullptr));     // the ~10 launches of an empty stage B2 are not made
     }
     // second tier: many survivors of a slice that holds well under all of the weight -> sweep THEM over the larger slice first
     bool second_tier = false;
@@ -2307,7 +2364,7 @@ int run_pass_pruned_impl(Ctx& c, Pass& ps) {
             CHK(launch_hull(c, pp, hsl, hm, MIR_R2, MIR_RB2));
             CHK(read_survivors(c, b.r3, hm, MIR_R2, MIR_RB2, ps.nj, s2));
             if (tune(TUNE_PRINT) > 0) fprintf(stderr, "[p4v] second tier: %d survivors of the %d-row slice -> %d of the %d-row slice (M %d N %d K %d)\n", s1.count, pl.k, s2.count, pl.k2, ps.Mrows, ps.Ncols, ps.K);
-            if (!s2.count) return select_without_b2(c, ps, pl, b);
+            if (!s2.count) return select_without_b2(c, ps, pl, b, kept(true, nullptr));
             second_tier = true;
         }
     }
@@ -2321,6 +2378,7 @@ int run_pass_pruned_impl(Ctx& c, Pass& ps) {
         else CHK(enqueue(c, KERN(MergeParams, k_merge_scores), dim3(cdiv((long)b.tab, 256)), dim3(256), 0, MergeParams{b.S2, b.SB, (int)b.tab}));
         CHK(launch_pass_select(c, ps, b.S2));
     }
+    CHK(keep_prune_tables(c, kept(second_tier, b.S2)));
     c.ws.off = b.mark;
     return 0;
 }
@@ -2497,16 +2555,20 @@ int run_sos_split_pruned_impl(Ctx& c, SosSplitJob& j) {
         attach_mirror(hsl);
         CHK(launch_hull(c, pp, hsl, nullptr, MIR_R1, MIR_RB1));
     }
+    auto kept = [&](const float* S2) {               // p4v_debug_prune_tables (one score block, no per-block ranges, the hull selects)
+        return PruneKept{1, kp.C, 1, false, true, false, false, j.host_sync_ok && !c.dry, kp.C, geo.k, 0, b.SA, b.SB, nullptr, S2, b.r1, nullptr, nullptr};
+    };
     int survivors = -1;
     if (j.host_sync_ok && !c.dry) {
         Survivors s;
         CHK(read_survivors(c, b.r2, nullptr, MIR_R1, MIR_RB1, 1, s));
-        if (!s.count) { PRUNE_COUNT(PRUNE_NO_SURVIVORS); c.ws.off = b.mark; return 0; }
+        if (!s.count) { PRUNE_COUNT(PRUNE_NO_SURVIVORS); CHK(keep_prune_tables(c, kept(nullptr))); c.ws.off = b.mark; return 0; }
         survivors = std::max(0, std::min(s.hi, kp.C) - std::max(s.lo, 0));
     }
     CHK(run_stage(STAGE_B2, [&] { return sos_sweep(c, j, kp, b.r2, b.S2, survivors); }));
     if (!c.dry) CHK(enqueue(c, KERN(MergeParams, k_merge_scores), dim3(1), dim3(256), 0, MergeParams{b.S2, b.SB, kp.C}));
     CHK(sos_select(c, j, b.S2));
+    CHK(keep_prune_tables(c, kept(b.S2)));
     c.ws.off = b.mark;
     return 0;
 }
@@ -2686,7 +2748,10 @@ int search_rounds(Ctx& c, const SearchRounds& R, const Stage& sg, SearchSide (&s
             bool hit = false;
             CHK(sd.memo.restore(c, sd.key, host ? &host[1 - s] : nullptr, sd.val, host ? &host[s] : nullptr, &hit));
             if (hit) continue;
-            if (sg.mask & sd.bit) CHK(sd.run(round));
+            g_pass_round = round; g_pass_side = s;
+            const int rc_run = (sg.mask & sd.bit) ? sd.run(round) : 0;
+            g_pass_round = g_pass_side = -1;
+            CHK(rc_run);
             CHK(sd.memo.record(c, sd.val, host ? &host[s] : nullptr));
         }
     return 0;
@@ -4678,6 +4743,103 @@ int p4v_debug_bound_totals(float* out, int64_t capacity, int64_t* count) {
     if (count) *count = (int64_t)g_b1_totals.size();
     if (out) std::copy(g_b1_totals.begin(), g_b1_totals.begin() + std::min<int64_t>(capacity, (int64_t)g_b1_totals.size()), out);
     return 0;
+}
+
+int p4v_debug_prune_tables(int32_t* out, int64_t capacity, int64_t* count) {
+    if (!out && !count) { g_tables_keep = true; g_tables.clear(); return 0; }
+    g_tables_keep = false;
+    if (count) *count = (int64_t)g_tables.size();
+    if (out) std::copy(g_tables.begin(), g_tables.begin() + std::min<int64_t>(capacity, (int64_t)g_tables.size()), out);
+    return 0;
+}
+
+// The decision chain of run_pass_pruned_impl -- same launchers, same order, same branches -- with the three sweeps replaced by the
+// tables k_finish would leave, built on the host from the caller's totals T and the ranges the kernels wrote (the reads this
+// emulation needs are its own: `host_reads` is the pass's "the host reads the survivors", the early exit through select_from_b1).
+int p4v_debug_prune_decide(const float* d_SA, const float* d_SA2, const float* d_T, const float* d_cands, int C, int nj, int virt,
+                           int honour_blk, int host_reads, int32_t* d_ranges, int32_t* d_rblk, int32_t* d_best, float* d_interval,
+                           int32_t* d_best_out, int32_t* info, void* stream) {
+    if (!d_SA || !d_T || !d_cands || !d_ranges || !d_rblk || !d_best || !d_interval || !d_best_out || !info)
+        return fail(P4V_ERR_INVALID, "p4v_debug_prune_decide: null pointer");
+    if (C < 1 || nj < 1 || nj > 4096 || (virt && nj == 1))
+        return fail(P4V_ERR_INVALID, "p4v_debug_prune_decide: 1 <= C, 1 <= nj <= 4096, the synthetic candidate needs nj > 1");
+    Ctx c = Ctx::on(stream, nullptr, 0);
+    const size_t tab = (size_t)C * nj;
+    const float ninf = -INFINITY;
+    struct Scratch { float* p = nullptr; ~Scratch() { if (p) (void)hipFree(p); } } dev;
+    HIPCHK(hipMalloc(&dev.p, sizeof(float) * (3 * tab + nj)));
+    PrunePlan pl{};
+    pl.virt = virt != 0;
+    pl.hull_selects = prune_hull_selects(false, true, pl.virt, nj);
+    PruneBufs b{};
+    b.tab = tab;
+    b.SA = const_cast<float*>(d_SA); b.SB = dev.p; b.S2 = b.SB + tab; b.SA2 = b.S2 + tab; b.vrow = b.SA2 + tab;
+    b.r1 = d_ranges; b.r2 = b.r1 + 2; b.r3 = b.r1 + 4;
+    b.best_idx = d_best; b.rblk2 = d_rblk; b.rblk3 = d_rblk + 2 * nj;
+    Pass ps{};
+    ps.eq_n = C; ps.nj = nj; ps.cands = d_cands; ps.cand_cs = nj; ps.cand_js = 1; ps.cand_off = 0;
+    ps.interval = d_interval; ps.out_js = 1; ps.out_off = 0; ps.aux_div = 1.0f; ps.best_out = d_best_out;
+    std::vector<float> T(tab), SA2(d_SA2 ? tab : 0), h(tab);
+    std::vector<int> best(nj), rblk(2 * (size_t)nj);
+    int r[2] = {0, 0};
+    CHK(q_fill(c, d_ranges, 0xff, sizeof(int) * 6));                 // what a branch does not write stays -1
+    CHK(q_fill(c, d_rblk, 0xff, sizeof(int) * 4 * nj));
+    CHK(q_fill(c, d_best, 0xff, sizeof(int) * nj));
+    CHK(q_d2h(c, T.data(), d_T, sizeof(float) * tab));
+    if (d_SA2) CHK(q_d2h(c, SA2.data(), d_SA2, sizeof(float) * tab));
+    info[0] = pl.hull_selects; info[1] = 0; info[2] = 0;            // hull_selects, tier 2 ran, exit (0 merge, 1 / 2 no stage B2 after tier 1 / 2)
+    // the table a sweep of T over the device-side range `rng` (+ the per-block ranges `blk`) leaves in `dst`
+    auto sweep = [&](const std::vector<float>& src, float* dst, const int* rng, const int* blk) -> int {
+        CHK(q_d2h(c, r, rng, sizeof r));
+        if (blk) CHK(q_d2h(c, rblk.data(), blk, sizeof(int) * 2 * nj));
+        CHK(q_sync(c));
+        std::fill(h.begin(), h.end(), ninf);
+        for (int cc = std::max(r[0], 0); cc < std::min(r[1], C); ++cc)
+            for (int j = 0; j < nj; ++j)
+                if (!blk || (cc >= rblk[2 * j] && cc < rblk[2 * j + 1])) h[(size_t)cc * nj + j] = src[(size_t)cc * nj + j];
+        CHK(q_h2d(c, dst, h.data(), sizeof(float) * tab));
+        return q_sync(c);
+    };
+    PruneParams pp{b.SA, b.SB, C, nj, prune_margin(), b.r1, b.r1, pl.virt ? 1 : 0, b.best_idx, ps.cands, ps.cand_cs, ps.cand_js, ps.cand_off, b.vrow};
+    CHK(launch_pick(c, pp));
+    if (pl.virt) {              // stage B1 on the synthetic candidate: row 0 holds every block's winner's total
+        CHK(q_d2h(c, best.data(), b.best_idx, sizeof(int) * nj));
+        CHK(q_sync(c));
+        std::fill(h.begin(), h.end(), ninf);
+        for (int j = 0; j < nj; ++j) {
+            if (best[j] < 0 || best[j] >= C) return fail(P4V_ERR_INVALID, "p4v_debug_prune_decide: k_prune_pick left winner %d in block %d", best[j], j);
+            h[j] = T[(size_t)best[j] * nj + j];
+        }
+        CHK(q_h2d(c, b.SB, h.data(), sizeof(float) * tab));
+        CHK(q_sync(c));
+    } else CHK(sweep(T, b.SB, b.r1, nullptr));
+    int* hm = host_reads ? host_mirror(c) : nullptr;
+    SelectParams hsl{b.SB, ps.eq_n, ps.nj, ps.cands, ps.cand_cs, ps.cand_js, ps.cand_off, pl.hull_selects ? ps.interval : nullptr,
+                     ps.out_js, ps.out_off, ps.aux_out, ps.aux_div, nullptr, 0, ps.best_out};
+    attach_mirror(hsl);
+    pp.r_out = b.r2; pp.rblk = b.rblk2;
+    CHK(launch_hull(c, pp, hsl, hm, MIR_R1, MIR_RB1));
+    Survivors s1, s2;
+    if (host_reads) {
+        CHK(read_survivors(c, b.r2, hm, MIR_R1, MIR_RB1, nj, s1));
+        if (!s1.count) { info[2] = 1; CHK(select_from_b1(c, ps, pl, b)); return q_sync(c); }
+    }
+    bool second_tier = false;
+    if (d_SA2) {                // stage A2: the caller's partial sums where the first hull's ranges let a sweep evaluate them
+        CHK(sweep(SA2, b.SA2, b.r2, honour_blk ? b.rblk2 : nullptr));
+        pp.SA = b.SA2; pp.r_out = b.r3; pp.rblk = b.rblk3;
+        CHK(launch_hull(c, pp, hsl, hm, MIR_R2, MIR_RB2));
+        second_tier = true; info[1] = 1;
+        if (host_reads) {
+            CHK(read_survivors(c, b.r3, hm, MIR_R2, MIR_RB2, nj, s2));
+            if (!s2.count) { info[2] = 2; CHK(select_from_b1(c, ps, pl, b)); return q_sync(c); }
+        }
+    }
+    CHK(sweep(T, b.S2, second_tier ? b.r3 : b.r2, !honour_blk ? nullptr : second_tier ? b.rblk3 : b.rblk2));      // stage B2
+    if (pl.virt) CHK(enqueue(c, KERN(MergeVirtParams, k_merge_virtual), dim3(cdiv(ps.nj, 64)), dim3(64), 0, MergeVirtParams{b.S2, b.SB, b.best_idx, ps.nj}));
+    else CHK(enqueue(c, KERN(MergeParams, k_merge_scores), dim3(cdiv((long)b.tab, 256)), dim3(256), 0, MergeParams{b.S2, b.SB, (int)b.tab}));
+    CHK(launch_pass_select(c, ps, b.S2));
+    return q_sync(c);
 }
 
 int p4v_debug_topk_rows(const float* d_mass, int segs, int n, int k, int32_t* d_idx, void* stream) {

@@ -932,6 +932,75 @@ def debug_bound_totals(start=False):
     return [float(v) for v in buf[:n.value]]
 
 
+def debug_prune_tables(start=False):
+    """start=True: keep the stage tables of this thread's pruned passes from now on.  Otherwise stop and return one dict per
+    staged pass, in pass order (p4v_debug_prune_tables; include/ptq4vit_hip_debug.h lists the record): the flags, the ranges
+    r1 / r2 / r3 as (lo, hi), best [nj], rblk2 / rblk3 [nj][2] (int32 tensors) and the tables SA, SB, SA2, S2 (fp32 CPU
+    tensors [rows][nj]; None where the pass did not run the stage).  What a pass did not write is -1."""
+    lib = _lib.load()
+    if start:
+        _lib.check(lib.p4v_debug_prune_tables(None, 0, None), "p4v_debug_prune_tables")
+        return None
+    n = C.c_int64(0)
+    _lib.check(lib.p4v_debug_prune_tables(None, 0, C.byref(n)), "p4v_debug_prune_tables")
+    buf = (C.c_int32 * max(1, n.value))()
+    _lib.check(lib.p4v_debug_prune_tables(buf, n.value, C.byref(n)), "p4v_debug_prune_tables")
+    words = torch.frombuffer(buf, dtype=torch.int32)[:n.value].clone()
+    recs, at = [], 0
+    while at < n.value:
+        h = [int(v) for v in words[at:at + 24]]
+        size, eq_n, nj, sb_rows = h[0], h[4], h[5], h[12]
+        assert size >= 24 and at + size <= n.value, "p4v_debug_prune_tables: broken record"
+        body = words[at + 24:at + size]
+        pos = 0
+
+        def take(count, shape, as_float=False):
+            nonlocal pos
+            part = body[pos:pos + count].clone()
+            pos += count
+            return (part.view(torch.float32) if as_float else part).reshape(shape)
+        rec = dict(split_search=bool(h[1]), round=h[2], side=h[3], eq_n=eq_n, nj=nj, virt=bool(h[6]), hull_selects=bool(h[7]),
+                   b1_bound=bool(h[8]), tier2=bool(h[9]), host_read=bool(h[10]),
+                   margin=float(words[at + 11:at + 12].clone().view(torch.float32)), r1=(h[16], h[17]), r2=(h[18], h[19]),
+                   r3=(h[20], h[21]), slice_rows=h[22], slice2_rows=h[23], has_rblk=bool(h[15]))
+        rec["best"] = take(nj, (nj,))
+        rec["rblk2"] = take(2 * nj, (nj, 2))
+        rec["rblk3"] = take(2 * nj, (nj, 2))
+        rec["SA"] = take(eq_n * nj, (eq_n, nj), True)
+        rec["SB"] = take(sb_rows * nj, (sb_rows, nj), True)
+        rec["SA2"] = take(eq_n * nj, (eq_n, nj), True) if h[13] else None
+        rec["S2"] = take(eq_n * nj, (eq_n, nj), True) if h[14] else None
+        assert pos == size - 24, "p4v_debug_prune_tables: broken record"
+        recs.append(rec)
+        at += size
+    return recs
+
+
+def debug_prune_decide(SA, T, cands, *, virt, honour_blk, host_reads, SA2=None):
+    """The decision chain of a pruned pass (k_prune_pick, k_prune_hull, k_merge_*, k_select through the pass's own launchers;
+    p4v_debug_prune_decide) on the stage-A scores `SA` [C][nj], the full totals `T` [C][nj] that stand in for the sweeps of stages
+    B1 / B2, the optional second-tier scores `SA2` and the candidate table `cands` [C + 1][nj], all fp32 on the device.
+    Returns a dict of CPU values: r1, r2, r3 as (lo, hi), rblk2 / rblk3 [nj][2], best [nj], interval [nj], best_out [nj],
+    hull_selects, tier2, exit (0: merge and k_select; 1 / 2: no stage B2 after the first / second hull).  For the tests."""
+    f32 = lambda t: None if t is None else t.contiguous().float()
+    SA, T, cands, SA2 = f32(SA), f32(T), f32(cands), f32(SA2)
+    n_c, nj = (int(v) for v in T.shape) if T is not None and T.dim() == 2 else (0, 0)
+    dev = T.device if T is not None else torch.device("cuda", torch.cuda.current_device())
+    i32 = lambda n: torch.zeros(max(1, n), dtype=torch.int32, device=dev)
+    ranges, rblk, best, best_out = i32(6), i32(4 * nj), i32(nj), i32(nj)
+    interval = torch.full((max(1, nj),), float("nan"), dtype=torch.float32, device=dev)
+    info = (C.c_int32 * 3)()
+    with torch.cuda.device(dev):
+        rc = _lib.load().p4v_debug_prune_decide(ptr(SA), ptr(SA2), ptr(T), ptr(cands), n_c, nj, int(bool(virt)), int(bool(honour_blk)),
+                                                int(bool(host_reads)), ptr(ranges), ptr(rblk), ptr(best), ptr(interval),
+                                                ptr(best_out), info, stream_ptr(dev))
+    _lib.check(rc, "p4v_debug_prune_decide")
+    r = [int(v) for v in ranges.cpu()]
+    rb = rblk.cpu().reshape(2, nj, 2)
+    return dict(r1=(r[0], r[1]), r2=(r[2], r[3]), r3=(r[4], r[5]), rblk2=rb[0], rblk3=rb[1], best=best.cpu(), interval=interval.cpu(),
+                best_out=best_out.cpu(), hull_selects=bool(info[0]), tier2=bool(info[1]), exit=int(info[2]))
+
+
 def debug_topk_rows(mass, k):
     """Row selection of the exact pruning (k_topk_rows) on `mass` [segs, n] fp32: int32 [segs, k], the segment-local indices
     of the k heaviest entries in ascending order (ties: lowest indices).  For the tests."""

@@ -13,6 +13,14 @@ state the share they need as (slice rows, lower bound, upper bound) and `run` as
   "xcheck"   the default call with variant bit 134217728: every pruned pass is followed by its full sweep, the engine compares
 prune=False (desc.reserved bit 3) is the same call with full sweeps only: the reference of the intervals.
 
+`run(..., want_scores=True)` asks for the score tables as well (no pass is eligible then: with prune=False the reference of the
+TOTALS, tests/test_hip_prune_premises.py).
+
+ZERO_REST_CASES (their own list: the EXPECTED literals of tests/test_hip_pruned_stages.py cover CASES): one case per pairing of
+a stage-A kernel with the kernel of the totals, raw_grad EXACTLY zero outside the rows the slice takes (`zero_rest`: that many
+heaviest samples of a Linear / output pixels of a Conv, query rows per (image, head) of a MatMul) -- the slice's sum and the
+total are then the same sum of the same terms, and all that is left between them is the arithmetic of the two kernels.
+
 METRIC_CASES: seven of the cases again (the forced ones: their staging does not depend on a share of raw_grad) under the four
 difference metrics that read no raw_grad -- `metric_case(name, metric, grad_given)` makes the run; grad_given False: no tensor,
 True: the case's own raw_grad, "adversarial": 1 / (|raw_out| + 1e-3) (sweep_plan_cases.grad_of).  `metric_oracle(name, metric)`
@@ -43,15 +51,44 @@ def _linear_grad(grad, shape, kind, spread, seed):
     return grad
 
 
+def zero_rest_rows(grad, k, kind):
+    """raw_grad with everything but the k heaviest rows (by raw_grad^2, the hessian weight) set to exactly 0 -- "linear": rows =
+    samples [images][tokens] of [..., N]; "matmul": k query rows of every (image, head) of [b][H][M][N]; "conv": rows = output
+    pixels (image, y, x) of [b][oc][fh][fw].  The share of the weight in those rows is asserted to be exactly 1."""
+    g = grad.clone()
+    if kind == "matmul":
+        m = (g.double() ** 2).sum(-1)                                        # [b][H][M]
+        keep = torch.zeros_like(m, dtype=torch.bool).scatter_(-1, torch.topk(m, k, dim=-1).indices, True)
+        g[~keep] = 0.0
+        m = (g.double() ** 2).sum(-1)
+        outside = m.masked_fill(keep, 0.0).sum(-1)                            # the weight the slice does not hold: exactly none
+        assert bool((1.0 - outside / m.sum(-1) == 1.0).all()) and bool((outside == 0).all()) and bool(((m > 0).sum(-1) <= k).all())
+        return g
+    m = (g.double() ** 2).sum(1 if kind == "conv" else -1)                   # conv: [b][fh][fw]; linear: [images][tokens]
+    keep = torch.zeros(m.numel(), dtype=torch.bool)
+    keep[torch.topk(m.flatten(), k).indices] = True
+    keep = keep.reshape(m.shape)
+    if kind == "conv":
+        g = g * keep[:, None].to(g.dtype)
+    else:
+        g[~keep] = 0.0
+    m = (g.double() ** 2).sum(1 if kind == "conv" else -1)
+    outside = float(m[~keep].sum())
+    assert 1.0 - outside / float(m.sum()) == 1.0 and outside == 0.0 and int((m > 0).sum()) <= k
+    return g
+
+
 def _given(grad_given, grad, out):
     return grad_of({False: "none", True: "seeded"}.get(grad_given, grad_given), grad, out)
 
 
 def _linear(K, N, *, seed, images, tokens, grad="cls", spread=0.0, shares=(), n_V=1, postgelu=False, variant=0, tuning=(), scores=False,
-            metric="hessian", grad_given=True):
-    def run(eng, mode, prune=True):
+            metric="hessian", grad_given=True, zero_rest=0):
+    def run(eng, mode, prune=True, want_scores=False):
         w, b, x, out, gr = linear_inputs(K, N, seed=seed, images=images, tokens=tokens, postgelu=postgelu)
         gr = _linear_grad(gr, out.shape, grad, spread, seed)
+        if zero_rest:
+            gr = zero_rest_rows(gr, zero_rest, "linear")
         for k, lo, hi in shares if metric == "hessian" else ():     # (the shares are those of raw_grad^2: the hessian weight)
             assert lo <= slice_share(gr, k) < hi, (k, lo, slice_share(gr, k), hi)
         gr = _given(grad_given, gr, out)
@@ -60,7 +97,7 @@ def _linear(K, N, *, seed, images, tokens, grad="cls", spread=0.0, shares=(), n_
             eng.debug_tuning(key, value)
         try:
             job = eng.linear_job(weight=_cuda(w), bias=_cuda(b), x=_cuda(x), out=_cuda(out), grad=_cuda(gr), w_bit=8, a_bit=8,
-                                 metric=metric, n_V=n_V, n_H=1, n_a=1, postgelu=postgelu, want_scores=scores, prune=prune, **ROUNDS)
+                                 metric=metric, n_V=n_V, n_H=1, n_a=1, postgelu=postgelu, want_scores=scores or want_scores, prune=prune, **ROUNDS)
             return _call(eng, job, mode)
         finally:
             eng.debug_variant(0)
@@ -69,28 +106,32 @@ def _linear(K, N, *, seed, images, tokens, grad="cls", spread=0.0, shares=(), n_
     return run
 
 
-def _matmul(M, K, N, *, seed, sos=False, metric="hessian", grad_given=True):
-    def run(eng, mode, prune=True):
+def _matmul(M, K, N, *, seed, sos=False, metric="hessian", grad_given=True, zero_rest=0):
+    def run(eng, mode, prune=True, want_scores=False):
         A, B, out, grad = matmul_inputs(M, K, N, seed=seed, sos=sos)
+        if zero_rest:
+            grad = zero_rest_rows(grad, zero_rest, "matmul")
         grad = _given(grad_given, grad, out)
         eng.debug_variant(LOOSE | (XCHECK if mode == "xcheck" else 0))
         try:
             job = eng.matmul_job(A=_cuda(A), B=_cuda(B), out=_cuda(out), grad=_cuda(grad), A_bit=8, B_bit=8, metric=metric, sos=sos,
-                                 prune=prune, **ROUNDS)
+                                 prune=prune, want_scores=want_scores, **ROUNDS)
             return _call(eng, job, mode)
         finally:
             eng.debug_variant(0)
     return run
 
 
-def _conv(*, seed, a_bit, metric="hessian", grad_given=True):
-    def run(eng, mode, prune=True):
+def _conv(*, seed, a_bit, metric="hessian", grad_given=True, zero_rest=0):
+    def run(eng, mode, prune=True, want_scores=False):
         w, b, x, out, grad = conv_inputs(seed=seed, images=10, size=64, patch=8)
+        if zero_rest:
+            grad = zero_rest_rows(grad, zero_rest, "conv")
         grad = _given(grad_given, grad, out)
         eng.debug_variant(LOOSE | (XCHECK if mode == "xcheck" else 0))
         try:
             job = eng.conv_job(weight=_cuda(w), bias=_cuda(b), x=_cuda(x), out=_cuda(out), grad=_cuda(grad), stride=(8, 8), padding=(0, 0),
-                               dilation=(1, 1), w_bit=8, a_bit=a_bit, metric=metric, prune=prune, **ROUNDS)
+                               dilation=(1, 1), w_bit=8, a_bit=a_bit, metric=metric, prune=prune, want_scores=want_scores, **ROUNDS)
             return _call(eng, job, mode)
         finally:
             eng.debug_variant(0)
@@ -124,6 +165,26 @@ CASES = [
     ("conv640_a8", _conv(seed=50, a_bit=8)),
     # score tables asked for: no pass is eligible
     ("lin650_scores", _linear(192, 96, seed=41, scores=True, **L650)),
+]
+
+
+# (name, run, the pairing the case is there for): raw_grad zero outside the slice's rows.  A Linear of 650 / 2 048 samples slices
+# 256 rows, the 4 137-sample one tries 128 first and -- without the pass memo -- takes 512, which hold the same 128 rows and 384
+# of weight zero; a MatMul slices 16 query rows per (image, head); the Conv's 640 output pixels slice 256.  The second tier runs
+# only on a first slice with less than 0.9 of the weight, so its case keeps 512 rows -- the second slice -- and spreads the weight.
+ZERO_REST_CASES = [
+    ("lin650_zero_rest", _linear(192, 96, seed=41, zero_rest=256, **L650), "k_sweep6"),
+    ("lin650_nV3_zero_rest", _linear(192, 96, seed=42, n_V=3, variant=LOOSE, zero_rest=256, **L650), "k_sweep6, three score blocks"),
+    ("postgelu650_zero_rest", _linear(192, 96, seed=45, postgelu=True, variant=LOOSE, zero_rest=256, **L650), "twin k_sweep2"),
+    ("lin4137_zero_rest", _linear(64, 64, seed=43, zero_rest=128, **L4137), "k_sweep4/5"),
+    ("lin2048_zero_rest", _linear(64, 96, seed=44, n_V=3, zero_rest=256, **L2048), "k_sweep8"),
+    ("lin2048_tier2_zero_rest", _linear(64, 96, seed=44, n_V=3, grad="spread", spread=0.8, shares=[(256, 0.5, 0.9)],
+                                        tuning=[(13, 2)], zero_rest=512, **L2048), "k_sweep8, second tier"),
+    ("qk65_zero_rest", _matmul(65, 64, 65, seed=46, zero_rest=16), "k_slice_a / k_slice_b with k_sweep9"),
+    ("qk65_d128_zero_rest", _matmul(65, 128, 65, seed=47, zero_rest=16), "k_sweep2"),
+    ("sos65_zero_rest", _matmul(65, 65, 64, seed=48, sos=True, zero_rest=16), "k_sos_split"),
+    ("conv640_a32_zero_rest", _conv(seed=49, a_bit=32, zero_rest=256), "conv, fp32 planes"),
+    ("conv640_a8_zero_rest", _conv(seed=50, a_bit=8, zero_rest=256), "conv, int8 planes"),
 ]
 
 

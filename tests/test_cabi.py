@@ -348,3 +348,22 @@ def test_sizing_refuses_null_and_unsupported_descriptors(lib):
     full = lib.p4v_matmul_workspace_bytes(C.byref(md))
     md.reserved = 4
     assert 4096 < lib.p4v_matmul_workspace_bytes(C.byref(md)) <= full
+
+
+def test_prune_decide_refuses_bad_arguments_before_any_launch(lib):
+    """p4v_debug_prune_decide: every null pointer, C < 1, nj < 1, nj > 4096 and the synthetic candidate on one score block are
+    refused on the host (the pointers are never dereferenced: no GPU here); p4v_debug_prune_tables starts and stops without one."""
+    null, one = C.c_void_p(0), C.c_void_p(64)
+    info = (C.c_int32 * 3)()
+
+    def call(C_=32, nj=2, virt=0, **nulls):
+        a = dict(SA=one, SA2=one, T=one, cands=one, ranges=one, rblk=one, best=one, interval=one, best_out=one, info=info)
+        a.update({k: (None if k == "info" else null) for k in nulls})
+        return lib.p4v_debug_prune_decide(a["SA"], a["SA2"], a["T"], a["cands"], C_, nj, virt, 0, 0, a["ranges"], a["rblk"], a["best"],
+                                          a["interval"], a["best_out"], a["info"], null)
+    for name in ("SA", "T", "cands", "ranges", "rblk", "best", "interval", "best_out", "info"):      # (SA2 is optional)
+        assert call(**{name: True}) == -1 and b"p4v_debug_prune_decide: null pointer" in lib.p4v_last_error(), name
+    for kw in (dict(C_=0), dict(C_=-3), dict(nj=0), dict(nj=4097), dict(nj=1, virt=1)):
+        assert call(**kw) == -1 and b"p4v_debug_prune_decide: 1 <= C" in lib.p4v_last_error(), kw
+    n = C.c_int64(-1)
+    assert lib.p4v_debug_prune_tables(None, 0, None) == 0 and lib.p4v_debug_prune_tables(None, 0, C.byref(n)) == 0 and n.value == 0
