@@ -1601,7 +1601,8 @@ int sweep_chunk_stationary(Ctx& c, const Pass& ps, const SweepPlan& pl, const Pa
     if (pl.rblk && known && ps.host_rblk && ps.nj <= 4) {
         // per-score-block ranges known to the host: one launch per run of OPEN blocks (a closed block -- its only survivor
         // is its stage-A winner -- has nothing to sweep: the q block of a ViT qkv layer); score block j = streaming
-        // tiles [j, j + 1) * sb_div / 64
+        // tiles [j, j + 1) * sb_div / 64 -- several blocks are whole tiles each (blocks64); ONE block need not be (96 features:
+        // a tile and a half), its run ends with the last tile
         const int tpb = ps.sb_div / 64;
         for (int j = 0; j < ps.nj;) {
             if (ps.host_rblk[2 * j + 1] <= ps.host_rblk[2 * j]) { ++j; continue; }
@@ -1613,7 +1614,7 @@ int sweep_chunk_stationary(Ctx& c, const Pass& ps, const SweepPlan& pl, const Pa
                 fsum += std::max(0, h - l);
             }
             Sweep3Params qq = q;
-            const int tt0 = j * tpb, tt1 = std::min(q.ttiles, j1 * tpb);
+            const int tt0 = j * tpb, tt1 = j1 == ps.nj ? q.ttiles : std::min(q.ttiles, j1 * tpb);
             qq.tile0 = tt0 * q.stiles; qq.ntile = (tt1 - tt0) * q.stiles;
             const int ncr = std::max(1, hi - lo);
             g_exec_frac = fsum / ((double)(j1 - j) * nc);
