@@ -49,7 +49,8 @@
 extern "C" {
 #endif
 
-#define P4V_VERSION 145 /* 0.1.4.5: + p4v_qkv_attn_* (the fused int8 qkv forward: the qkv GEMM writes the attention operand planes) */
+#define P4V_VERSION 146 /* 0.1.4.6: + P4V_ATTN_ONE_KERNEL (the fused attention core as one kernel: p v from the probabilities in registers) */
+/* 0.1.4.5: + p4v_qkv_attn_* (the fused int8 qkv forward: the qkv GEMM writes the attention operand planes) */
 
 /* similarity metrics: reference quant_layers/linear.py:399-424 */
 enum p4v_metric {
@@ -491,7 +492,15 @@ int p4v_mlp_quant_forward(const p4v_mlp_desc* desc, const float* d_w1, const flo
  * d_out [batch*heads][M][Dv]; d_probs: optional (may be NULL, then nothing is stored for it) [batch*heads][M][N] fp32, the
  * probabilities the planes were quantised from.  d_ws, ws_bytes: the workspace and its size -- the workspace contract
  * above holds with p4v_attn_workspace_bytes; a smaller ws_bytes is refused before any launch.
+ * reserved bit 0 (P4V_ATTN_ONE_KERNEL; also of p4v_qkv_attn_desc.reserved): the two kernels of the chain become one
+ * (k_attn_qkpv).  Its third walk over the keys hands the quantised probabilities, in registers, to matmul2's int8 MFMAs as their
+ * second operand and reads v's bytes from matmul2's column plane as the first: matmul2's row plane(s), their padding and the
+ * sweep that read them do not exist.  Integer accumulation is exact and order-free and the epilogue is the forward sweep's
+ * expression, so d_out and d_probs equal the two-kernel call's bit for bit.  Instances serve Dv = pv.N <= 128; beyond that the
+ * bit is accepted and the two-kernel chain runs.  p4v_attn_workspace_bytes / p4v_qkv_attn_workspace_bytes answer for the
+ * descriptor as given: with the bit the exact, smaller size.  With the bit clear every launch is what it was.
  * ---------------------------------------------------------------------------------------- */
+#define P4V_ATTN_ONE_KERNEL 1
 typedef struct p4v_attn_desc {
     p4v_matmul_desc qk, pv;
     float scale;

@@ -3151,12 +3151,12 @@ int linear_impl(const p4v_linear_desc* d, const LinearTensors& t, const Stage& s
 // ------------------------------------------------------------------------------------------------
 // Where the planes of the calling thread's last call lie in its workspace (p4v_debug_mlp_planes / p4v_debug_attn_planes: the
 // tests read them there)
-struct FusedPlanes { size_t off1 = 0, off2 = 0; long rows = 0, cols = 0; int twin = 0; };
+struct FusedPlanes { size_t off1 = 0, off2 = 0; long rows = 0, cols = 0; int twin = 0; bool none = false; };   // none: a one-kernel call, which has no planes
 thread_local FusedPlanes g_mlp_planes, g_attn_planes;
 // ... and the three operand planes k_qkv_heads wrote (p4v_debug_qkv_planes): offsets, then Z and the planes' rows / row lengths
 struct QkvPlanes { size_t off_q = 0, off_k = 0, off_v = 0; long Z = 0, rows_q = 0, rows_k = 0, ld_qk = 0, rows_v = 0, ld_v = 0; };
 thread_local QkvPlanes g_qkv_planes;
-constexpr int MLP_RECORD_KIND = 16, ATTN_RECORD_KIND = 17, QKV_RECORD_KIND = 18;
+constexpr int MLP_RECORD_KIND = 16, ATTN_RECORD_KIND = 17, QKV_RECORD_KIND = 18, ATTN_PV_RECORD_KIND = 19;
 
 // One producer -> consumer chain, in the order its caller walks it: plan_consumer, produce, consume.
 struct FusedChain {
@@ -3191,15 +3191,19 @@ struct FusedChain {
     bool twin = false;
     char *P1 = nullptr, *P2 = nullptr;                              // (null in the sizing run: it carves nothing)
 
-    // The consumer's pass first: its plan says how large the row plane(s) are.
-    int plan_consumer(const Pass& fwd, int Z_, bool twin_) {
+    // The consumer's pass first: its plan says how large the row plane(s) are.  `carve_planes` false (attn_chain, which may
+    // run the whole chain in one kernel): the caller decides on the plan and calls carve() itself where the planes exist.
+    int plan_consumer(const Pass& fwd, int Z_, bool twin_, bool carve_planes = true) {
         fp2 = fwd; Z = Z_; twin = twin_;
         CHK(plan_sweep(c, fp2, pl2));
         if (pl2.cin_fix != 0 || pl2.merged7 || pl2.esz != 1) return fail(P4V_ERR_UNSUPPORTED, "%s: %s's sweep does not read row-major int8 planes", who, consumer);
         Mp = pl2.Mp; Kp = pl2.Kp;
+        if (carve_planes) carve();
+        return 0;
+    }
+    void carve() {
         P1 = c.ws.get<char>((size_t)Z * Mp * Kp);
         P2 = twin ? c.ws.get<char>((size_t)Z * Mp * Kp) : nullptr;
-        return 0;
     }
     // The producer: both operands of its forward pass `fp1` (reduction length K1, `ncols` columns, `nscale` scale entries) packed
     // as run_pass would pack them (pack_operand, k_scale_table) into scratch that is given back at the end, then -- unless the
@@ -3614,6 +3618,57 @@ struct QkvProducer {
         return 0;
     }
 };
+// The chain as ONE launch (P4V_ATTN_ONE_KERNEL; k_attn_qkpv): matmul1's operand planes and scale table as
+// `produce` makes them, matmul2's column plane and scale table(s) as its forward pass makes them (pack_operand, k_scale_table) --
+// or all three planes as k_qkv_heads wrote them (`pre`) --, then the kernel.  No row plane of matmul2 exists: nothing was carved
+// for it, and p4v_debug_attn_planes reports sizes 0.  Everything is scratch of the bump region and given back.
+int attn_one_kernel(Ctx& c, FusedChain& ch, float scale, int ndt, const MatMulTensors& t1, const MatMulCall& m1, const MatMulTensors& t2,
+                    const MatMulCall& m2, const FusedChain::PrePlanes* pre) {
+    const int Z = ch.Z, H = m1.H, M = m1.M, N = m1.N, K1 = m1.K, Dv = m2.N;
+    const bool twin = ch.twin;
+    const SweepPlan& pl2 = ch.pl2;
+    const size_t mark = c.ws.off;
+    FusedChain::Packed pk{};
+    Pass fp1 = m1.forward_pass();
+    CHK(FusedChain::pack_pair(c, fp1, Z, ch.Mp, K1, N, H, pk, pre));
+    char* vplane = pre ? pre->col2 : c.ws.get<char>((size_t)Z * pl2.NpB * pl2.Kp);
+    float* So1 = c.ws.get<float>((size_t)H);
+    float* So2 = twin ? c.ws.get<float>((size_t)H) : nullptr;
+    if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", c.ws.off);
+    Pass& fp2 = ch.fp2;
+    fp2.s1.S = So1; fp2.s1.C = 1; fp2.s1.nblk = fp2.s_cs;
+    CHK(launch_scale(c, fp2.s1));
+    if (twin) { fp2.s2.S = So2; fp2.s2.C = 1; fp2.s2.nblk = fp2.s_cs; CHK(launch_scale(c, fp2.s2)); }
+    if (!pre) CHK(pack_operand(c, fp2, pl2, PassBufs{}, fp2.col, vplane, true, 0, 1));
+    if (!c.dry) {
+        AttnQkPvParams q{};
+        q.Q = pk.rows; q.Kt = pk.cols; q.q_zs = (long)ch.Mp * pk.Kp; q.k_zs = (long)pk.Np * pk.Kp; q.ldk = pk.Kp; q.ktiles = pk.Kp / SW_BKB;
+        q.S1 = pk.S1; q.H = H; q.scale = scale;
+        q.M = M; q.N = N;
+        q.qs = twin ? t2.split : t2.A_iv; q.qs_headwise = twin ? 0 : 1;
+        q.lo = -m2.Aq; q.hi = m2.Aq - 1; q.qm1 = (float)(m2.Aq - 1);
+        q.V = vplane; q.v_zs = (long)pl2.NpB * pl2.Kp; q.ldv = pl2.Kp;
+        q.So1 = So1; q.So2 = So2;
+        q.out = t2.fwd_out; q.Dv = Dv; q.vec4 = (Dv % 4 == 0 && ((unsigned long long)t2.fwd_out & 15) == 0) ? 1 : 0;
+        q.probs = t1.fwd_out;
+        q.mtiles = ch.Mp / SW_BM; q.nwg = Z * q.mtiles;
+        g_alg_macs_cand = (double)Z * M * N * (K1 + Dv);
+        // the three operand planes, out and probs
+        g_alg_bytes = (double)Z * ((double)M * K1 + (double)N * K1 + (double)N * Dv) + 4.0 * (double)Z * M * Dv + (t1.fwd_out ? 4.0 * (double)Z * M * N : 0.0);
+        g_exec_frac = 1.0;
+        // (three walks over the keys; the third one carries ndt MFMAs per plane and key tile)
+        const double tiles = (double)Z * ch.Mp * (double)rup(N, 32);
+        const StatInfo si = stat_info(ATTN_PV_RECORD_KIND, tiles * (3.0 * pk.Kp + 32.0 * ndt * (twin ? 2 : 1)), g_alg_macs_cand, q.nwg, 1, g_alg_bytes);
+        const dim3 grid(q.nwg), block(256);
+        if (ndt == 2) CHK(twin ? enqueue(c, KERN1_T(AttnQkPvParams, k_attn_qkpv, true, 2), grid, block, 0, q, &si)
+                               : enqueue(c, KERN1_T(AttnQkPvParams, k_attn_qkpv, false, 2), grid, block, 0, q, &si));
+        else CHK(twin ? enqueue(c, KERN1_T(AttnQkPvParams, k_attn_qkpv, true, 4), grid, block, 0, q, &si)
+                      : enqueue(c, KERN1_T(AttnQkPvParams, k_attn_qkpv, false, 4), grid, block, 0, q, &si));
+        g_attn_planes = FusedPlanes{0, 0, 0, 0, twin ? 1 : 0, true};
+    }
+    c.ws.off = mark;
+    return 0;
+}
 int attn_chain(const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulTensors& t2, Ctx& c, const AttnWindow* win, const QkvProducer* qkv = nullptr) {
     const p4v_matmul_desc* d1 = &d->qk;
     const p4v_matmul_desc* d2 = &d->pv;
@@ -3643,11 +3698,18 @@ int attn_chain(const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulTens
     const int Z = m1.Z, H = m1.H, M = m1.M, N = m1.N, K1 = m1.K;
     const bool twin = d2->sos != 0;
     FusedChain ch{c, "attn", "p v"};
-    CHK(ch.plan_consumer(m2.forward_pass(), Z, twin));         // Kp = roundup64(N)
+    CHK(ch.plan_consumer(m2.forward_pass(), Z, twin, false));  // Kp = roundup64(N)
     if (ch.Mp % SW_BM || (long)Z * (ch.Mp / SW_BM) >= (1L << 31)) return fail(P4V_ERR_UNSUPPORTED, "attn: %d x %d row tiles", Z, ch.Mp / SW_BM);
+    // One kernel or two, decided here and nowhere else: the caller asked for it, k_attn_qkpv has an instance for Dv (NDT = 2 / 4
+    // output tiles of 32) and the column plane holds the NDT * 32 rows its lanes address -- b64: 64 rows and Dv <= 64, else
+    // roundup128(Dv).  The window call has no bit to ask with.
+    const int ndt = m2.N <= 64 ? 2 : 4;
+    const bool one_kernel = (d->reserved & P4V_ATTN_ONE_KERNEL) && !win && m2.N <= 128 && ndt * 32 <= ch.pl2.NpB;
+    if (!one_kernel) ch.carve();
     FusedChain::PrePlanes planes{};
     const FusedChain::PrePlanes* pre = qkv ? &planes : nullptr;
     if (qkv) CHK(qkv->run(c, ch, H, N, K1, t1, m1, t2, m2, planes));
+    if (one_kernel) return attn_one_kernel(c, ch, d->scale, ndt, t1, m1, t2, m2, pre);
     CHK(ch.produce(m1.forward_pass(), K1, N, H, g_attn_planes, [&](const FusedChain::Packed& pk) -> int {
         AttnQkParams q{};
         q.Q = pk.rows; q.Kt = pk.cols; q.q_zs = (long)ch.Mp * pk.Kp; q.k_zs = (long)pk.Np * pk.Kp; q.ldk = pk.Kp; q.ktiles = pk.Kp / SW_BKB;
@@ -3707,7 +3769,7 @@ int qkv_attn_impl(const p4v_qkv_attn_desc* d, const QkvAttnTensors& t, const Qkv
     CHK(L.build());
     if (!L.i8) return fail(P4V_ERR_UNSUPPORTED, "qkv_attn: int8 planes only");
     if (rup(L.M, SW_BM) / SW_BM * (rup(L.N, SW_BN) / SW_BN) >= (1L << 31)) return fail(P4V_ERR_UNSUPPORTED, "qkv_attn: %d x %d output tiles", L.M, L.N);
-    const p4v_attn_desc a{*d1, *d2, d->scale, 0};
+    const p4v_attn_desc a{*d1, *d2, d->scale, d->reserved & P4V_ATTN_ONE_KERNEL};
     const QkvProducer qkv{L, t.lin};
     return attn_chain(&a, t.m1, t.m2, c, nullptr, &qkv);
 }
@@ -4630,7 +4692,7 @@ static int stats_drain() {
         float ms = 0;
         HIPCHK(hipEventElapsedTime(&ms, r.a, r.b));
         ms = (float)std::max(0.0, (double)ms - g_evt_overhead_ms);
-        if (r.kind == 0 || (r.kind >= 2 && r.kind <= 9) || (r.kind >= 12 && r.kind <= 18)) { g_stats.sweep_i8_ms += ms; g_stats.sweep_i8_launches++; g_stats.sweep_i8_macs += r.macs; g_stats.sweep_i8_alg_macs += r.alg; }
+        if (r.kind == 0 || (r.kind >= 2 && r.kind <= 9) || (r.kind >= 12 && r.kind <= 19)) { g_stats.sweep_i8_ms += ms; g_stats.sweep_i8_launches++; g_stats.sweep_i8_macs += r.macs; g_stats.sweep_i8_alg_macs += r.alg; }
         if (r.kind == 2) { g_stats.sweep6_ms += ms; g_stats.sweep6_launches++; g_stats.sweep6_macs += r.macs; g_stats.sweep6_alg_macs += r.alg; }
         if (r.kind == 3 || r.kind == 4) { g_stats.sweep7_ms += ms; g_stats.sweep7_launches++; g_stats.sweep7_macs += r.macs; g_stats.sweep7_alg_macs += r.alg; }
         if (r.kind == 4) { g_stats.sweep7_twin_ms += ms; g_stats.sweep7_twin_launches++; }
@@ -4708,7 +4770,7 @@ int p4v_debug_arena_ranges(uint64_t* out, int cap) {
 static int planes_out(const FusedPlanes& m, uint64_t* out, const char* who, const char* call) {
     if (!out) return fail(P4V_ERR_INVALID, "%s: null pointer", who);
     out[0] = m.off1; out[1] = m.off2; out[2] = (uint64_t)m.rows; out[3] = (uint64_t)m.cols; out[4] = (uint64_t)m.twin;
-    return m.rows > 0 ? 0 : fail(P4V_ERR_INVALID, "%s: no %s call on this thread yet", who, call);
+    return (m.rows > 0 || m.none) ? 0 : fail(P4V_ERR_INVALID, "%s: no %s call on this thread yet", who, call);
 }
 int p4v_debug_mlp_planes(uint64_t* out) { return planes_out(g_mlp_planes, out, "p4v_debug_mlp_planes", "p4v_mlp_quant_forward"); }
 int p4v_debug_attn_planes(uint64_t* out) { return planes_out(g_attn_planes, out, "p4v_debug_attn_planes", "p4v_attn_quant_forward / p4v_wattn_quant_forward"); }

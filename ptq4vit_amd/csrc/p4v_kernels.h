@@ -5488,4 +5488,196 @@ __global__ __launch_bounds__(256) void k_attn_qk(std::conditional_t<WIN, AttnWin
     k_attn_qk_body<TWIN, WIN>(p, P4V_BIDX, P4V_GDIM);
 }
 
+// ------------------------------------------------------------------------------------------
+// Fused attention forward, both halves (p4v_attn_quant_forward with P4V_ATTN_ONE_KERNEL): k_attn_qk's three walks, the third one
+// ending in matmul2's int8 GEMM instead of matmul2's row plane(s) -- q k^T -> * scale -> softmax -> split quantiser -> p v
+// ------------------------------------------------------------------------------------------
+// Walks 1 and 2 (row maximum, row sum) are k_attn_qk's, element for element and in its order; the probabilities are its
+// probabilities bit for bit.  That includes where k_attn_qk's build rounds the exponent: its row sum takes expf of
+// fma(t, scale, -max) -- the compiler contracts `t * scale - max` there --, its write pass, whose score tile sits behind a branch,
+// expf of the rounded product u = t * scale minus max.  Both are written out here (fmaf / contract(off)) instead of being left to
+// the compiler; tests/test_hip_fused_attention_pv.py holds the two kernels to the same bits at scales that are no power of two.
+// In walk 3 the four words w[q4] that k_attn_qk sends to LDS ARE the lane's second operand of
+// mfma_i32_32x32x32_i8: lane (l31, g) supplies column l31 -- its query -- and K slots 16 g ... 16 g + 15, and w[q4] holds keys
+// key0 + 8 q4 + 4 g + e in its bytes e = 0 ... 3, so slot 16 g + 4 q4 + e names that key.  The first operand is V^T: lane (l31, g)
+// supplies row d = 32 dt + l31 and, in the same slot order, the bytes V[key][d] of the same 16 keys -- four aligned dword loads
+// from row d of matmul2's column plane Q(v^T) [Z][vrows][ldv] at byte offsets key0 + 8 q4 + 4 g.  (Which key sits in which slot
+// does not matter as long as both operands agree: the sum is an integer.)  NDT = ceil(Dv / 32) output tiles per plane (and
+// range, TWIN) accumulate over ALL key tiles in registers: acc1[NDT] (acc2[NDT]), 16 NDT (32 NDT) VGPRs.  Rows >= Dv of the
+// plane are zeros and NDT * 32 <= vrows (the host checks it), keys >= N and queries >= M give the byte 0.  The V fragments come
+// straight from global memory, as the key fragments do: a head's plane is 16 KB at 197 keys and shared by the row tiles of a z,
+// which xcd_remap keeps adjacent; the loads of a key tile are issued before its score tile, so the expf walk covers them.
+// The accumulator of the transposed product holds, per lane, ONE query (l31) and per register quad four consecutive d
+// (32 dt + 8 (r >> 2) + 4 g + (r & 3)).  Epilogue, the forward sweep's expression per element (EPI_FWD, no bias table):
+//   o = (float)acc1 * So1[head];  TWIN: o = fmaf((float)acc2, So2[head], o);  out = o + 0.0f
+// (the sweep adds its absent bias as 0.0f -- it only turns a -0 into +0, and is kept for that), stored to out [Z][M][Dv] for
+// m < M and d < Dv: a quad as one 16-byte piece where Dv % 4 == 0 and out is 16-byte aligned (`vec4`), else as scalars.
+// No LDS, no barrier, no limit on the number of keys.
+struct AttnQkPvParams {
+    const void* Q; const void* Kt;            // [Z][Mp][ldk] / [Z][Np1][ldk]
+    long q_zs, k_zs; int ldk, ktiles;
+    const float* S1; int H;                   // A_interval[head] * B_interval[head] of matmul1 (k_scale_table)
+    float scale;
+    int M, N;                                 // valid queries / keys
+    const float* qs; int qs_headwise;         // matmul2's A quantiser: the split (TWIN) or A_interval[head]
+    int lo, hi; float qm1;
+    const void* V; long v_zs; int ldv;        // matmul2's column plane [Z][vrows][ldv] at [d][key]; ldv = roundup64(N)
+    const float* So1; const float* So2;       // matmul2's scale tables [H] (So2: TWIN)
+    float* out; int Dv, vec4;                 // [Z][M][Dv]
+    float* probs;
+    int mtiles, nwg;                          // 128-query tiles per z; workgroups
+};
+
+template <bool TWIN, int NDT>
+__global__ __launch_bounds__(256) void k_attn_qkpv(AttnQkPvParams p) {
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int g = lane >> 5, l31 = lane & 31;
+    const int t = xcd_remap(blockIdx.x, p.nwg);
+    const int z = t / p.mtiles, mt = t % p.mtiles;    // the row tiles of one z are adjacent: they share its key and value planes
+    const int m0 = mt * SW_BM + wid * 32;             // this wave's 32 queries
+    if (m0 >= p.M) return;                            // (wave-uniform; no barrier in this kernel) nothing but padding rows
+    const int m = m0 + l31;
+    const bool row_ok = m < p.M;
+    const int head = z % p.H;
+
+    const char* gQ = (const char*)p.Q + (long)z * p.q_zs + (long)m * p.ldk + g * 16;
+    const char* gK = (const char*)p.Kt + (long)z * p.k_zs + (long)l31 * p.ldk + g * 16;
+    const char* gV = (const char*)p.V + (long)z * p.v_zs + (long)l31 * p.ldv + g * 4;
+    const bool one = p.ktiles == 1;
+    v4i qf0 = {0, 0, 0, 0}, qf1 = {0, 0, 0, 0};       // the query fragments of a single k-tile stay in registers
+    if (one) { qf0 = *reinterpret_cast<const v4i*>(gQ); qf1 = *reinterpret_cast<const v4i*>(gQ + 32); }
+    const float s1 = p.S1[head];
+    const float scale = p.scale;
+    // t = (float)acc * S1[head] of the 32 x 32 tile at keys [key0, key0 + 32): k_attn_qk's GEMM, plain instance
+    auto scores = [&](int key0, float (&u)[16]) {
+        v16i acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0;
+        const char* ka = gK + (long)key0 * p.ldk;
+        if (one) {
+            const v4i a0 = *reinterpret_cast<const v4i*>(ka), a1 = *reinterpret_cast<const v4i*>(ka + 32);
+            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, qf0, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, qf1, acc, 0, 0, 0);
+        } else {
+            for (int kb = 0; kb < p.ktiles * 2; ++kb) {
+                const v4i a = *reinterpret_cast<const v4i*>(ka + kb * 32);
+                const v4i b = *reinterpret_cast<const v4i*>(gQ + kb * 32);
+                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, acc, 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) u[r] = __fmul_rn((float)acc[r], s1);
+    };
+
+    const int ntiles = (p.N + 31) / 32;
+    float u[16];
+    // ---- pass 1: the row maximum ------------------------------------------------------------------------
+    float mx = -__builtin_inff();
+    for (int nt = 0; nt < ntiles; ++nt) {
+        scores(nt * 32, u);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int n = nt * 32 + acc32_row(r, g);
+            if (n < p.N) mx = fmaxf(mx, __fmul_rn(u[r], scale));
+        }
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    // ---- pass 2: the row sum (one partial sum per accumulator register, added up pairwise) ---------------
+    float part[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) part[r] = 0.0f;
+    for (int nt = 0; nt < ntiles; ++nt) {
+        scores(nt * 32, u);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int n = nt * 32 + acc32_row(r, g);
+            if (n < p.N) part[r] = __fadd_rn(part[r], expf(fmaf(u[r], scale, -mx)));
+        }
+    }
+#pragma unroll
+    for (int w = 8; w >= 1; w >>= 1)
+#pragma unroll
+        for (int r = 0; r < w; ++r) part[r] = __fadd_rn(part[r], part[r + w]);
+    const float sum = __fadd_rn(part[0], __shfl_xor(part[0], 32));
+    // ---- pass 3: the probabilities, matmul2's quantiser, matmul2's GEMM on the bytes in registers ----------
+    const float qs = p.qs[p.qs_headwise ? head : 0];
+    PackParams pv1{}, pv2{};
+    pv1.mode = TWIN ? PACK_SOS_HI : PACK_SYM; pv1.lo = p.lo; pv1.hi = p.hi; pv1.qm1 = p.qm1;
+    pv2.mode = PACK_SOS_LO; pv2.qm1 = p.qm1;
+    v16i acc1[NDT];
+    [[maybe_unused]] v16i acc2[NDT];
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { acc1[dt][r] = 0; if (TWIN) acc2[dt][r] = 0; }
+    for (int nt = 0; nt < ntiles; ++nt) {
+        const int key0 = nt * 32;
+        // the tile's V fragments first (key0 + 8 q4 + 4 g + 3 < roundup32(N) <= ldv: inside the row)
+        v4i vf[NDT];
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) vf[dt][q4] = *reinterpret_cast<const int*>(gV + (long)dt * 32 * p.ldv + key0 + 8 * q4);
+        scores(key0, u);
+        v4i w1 = {0, 0, 0, 0};
+        [[maybe_unused]] v4i w2 = {0, 0, 0, 0};
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+            int x1 = 0, x2 = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int r = q4 * 4 + e;
+                const int n = key0 + e + 8 * q4 + 4 * g;
+                const bool ok = row_ok && n < p.N;
+                float b1 = 0.0f, b2 = 0.0f;
+                if (ok) {
+                    float pr;
+                    {
+#pragma clang fp contract(off)
+                        pr = u[r] * scale - mx;
+                    }
+                    pr = __fdiv_rn(expf(pr), sum);
+                    if (p.probs) p.probs[((long)z * p.M + m) * p.N + n] = pr;
+                    b1 = pack_value(pv1, pr, qs);
+                    if (TWIN) b2 = pack_value(pv2, pr, qs);
+                }
+                x1 |= ((int)b1 & 0xff) << (8 * e);
+                if (TWIN) x2 |= ((int)b2 & 0xff) << (8 * e);
+            }
+            w1[q4] = x1;
+            if (TWIN) w2[q4] = x2;
+        }
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt) {
+            acc1[dt] = __builtin_amdgcn_mfma_i32_32x32x32_i8(vf[dt], w1, acc1[dt], 0, 0, 0);
+            if (TWIN) acc2[dt] = __builtin_amdgcn_mfma_i32_32x32x32_i8(vf[dt], w2, acc2[dt], 0, 0, 0);
+        }
+    }
+    // ---- epilogue: EPI_FWD's expression, the lane's query row of out -----------------------------------------
+    if (!row_ok) return;
+    const float so1 = p.So1[head];
+    const float so2 = TWIN ? p.So2[head] : 0.0f;
+    float* orow = p.out + ((long)z * p.M + m) * p.Dv;
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+            const int d0 = dt * 32 + 8 * q4 + 4 * g;
+            v4f o4;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float o = (float)acc1[dt][q4 * 4 + e] * so1;
+                if (TWIN) o = fmaf((float)acc2[dt][q4 * 4 + e], so2, o);
+                o4[e] = o + 0.0f;
+            }
+            if (p.vec4) {                              // (uniform) Dv % 4 == 0: the quad is inside the row or outside it
+                if (d0 < p.Dv) *reinterpret_cast<v4f*>(orow + d0) = o4;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (d0 + e < p.Dv) orow[d0 + e] = o4[e];
+            }
+        }
+}
+
 }  // namespace p4v

@@ -327,7 +327,7 @@ def _attn_call(who, q, kT, v, qk, pv, want_probs, desc):
     return dev, q, kT, v, (qk_A, qk_B, pv_A, pv_B, sp), out, probs
 
 
-def attn_quant_forward(*, q, kT, v, scale, qk, pv, want_probs=False, want_planes=False):
+def attn_quant_forward(*, q, kT, v, scale, qk, pv, want_probs=False, want_planes=False, one_kernel=False):
     """matmul2(softmax(matmul1(q, kT) * scale, -1), v) of the two calibrated MatMuls of an attention block in quant_forward,
     fused (p4v_attn_quant_forward): matmul1's int8 GEMM keeps the scores in registers, takes the softmax and matmul2's A
     quantiser and writes matmul2's int8 plane(s); no fp32 score or probability tensor in between.
@@ -336,10 +336,14 @@ def attn_quant_forward(*, q, kT, v, scale, qk, pv, want_probs=False, want_planes
     blocks (anything but (1, 1, 1, 1) is refused), and for `pv` sos, split.  Returns out [B][H][M][Dv], or (out, probs) with
     `want_probs` -- the fp32 probabilities the planes were quantised from --, with `want_planes` also the padded int8
     plane(s) as the call left them in its workspace (a tuple of one or two [B*H][rows_padded][cols_padded] tensors; for the
-    tests)."""
+    tests).  `one_kernel` (P4V_ATTN_ONE_KERNEL): matmul2's GEMM runs inside the same kernel on the quantised probabilities in
+    registers -- no plane exists, so `want_planes` with it is a ValueError; out and probs are the same bits.  Dv > 128 has no
+    instance of that kernel and runs the two-kernel chain."""
+    if one_kernel and want_planes:
+        raise ValueError("attn_quant_forward: one_kernel writes no planes of matmul2 (want_planes)")
     d = _lib.AttnDesc()
     dev, q, kT, v, (qk_A, qk_B, pv_A, pv_B, sp), out, probs = _attn_call("attn_quant_forward", q, kT, v, qk, pv, want_probs, d)
-    d.scale, d.reserved = float(scale), 0
+    d.scale, d.reserved = float(scale), (_lib.ATTN_ONE_KERNEL if one_kernel else 0)
     return _fused_forward("attn", d, (q, kT, v, qk_A, qk_B, pv_A, pv_B, sp, out, probs), dev, (out, probs) if want_probs else (out,),
                           want_planes, z=q.shape[0] * q.shape[1])
 
@@ -368,7 +372,7 @@ def window_attn_quant_forward(*, q, kT, v, bias, mask=None, qk, pv, want_probs=F
     return _fused_forward("wattn", d, tensors, dev, (out, probs) if want_probs else (out,), want_planes, z=b * H)
 
 
-def qkv_attn_quant_forward(*, x, qkv, scale, qk, pv, want_qkv=False, want_probs=False, want_planes=False):
+def qkv_attn_quant_forward(*, x, qkv, scale, qk, pv, want_qkv=False, want_probs=False, want_planes=False, one_kernel=False):
     """matmul2(softmax(matmul1(q, kT) * scale, -1), v) with q, kT, v the head slices of qkv(x), all three modules calibrated and
     in quant_forward, fused (p4v_qkv_attn_quant_forward): the qkv layer's int8 GEMM quantises its output with the quantisers of
     the MatMul operands and writes their int8 planes; no fp32 qkv tensor, no permute copy and no pack of q, kT, v in between.
@@ -376,7 +380,8 @@ def qkv_attn_quant_forward(*, x, qkv, scale, qk, pv, want_qkv=False, want_probs=
     attn_quant_forward -- the head count is the length of qk's A_interval.  Returns out [B][H][N][D]; then, as asked for, the
     fp32 qkv tensor [B][N][3 * H * D] the planes were quantised from (`want_qkv`), the probabilities [B][H][N][N]
     (`want_probs`) and the padded int8 planes as the call left them in its workspace (`want_planes`; for the tests): a tuple
-    (Q [B*H][Mp][K1p], Kt [B*H][Np][K1p], V [B*H][NpB][Kp], P1[, P2] [B*H][Mp][Kp])."""
+    (Q [B*H][Mp][K1p], Kt [B*H][Np][K1p], V [B*H][NpB][Kp], P1[, P2] [B*H][Mp][Kp]).  `one_kernel`: as in attn_quant_forward;
+    with it `want_planes` returns (Q, Kt, V) -- P1 / P2 do not exist."""
     who = "qkv_attn_quant_forward"
     lib = _lib.load()
     dev = device_of(x, qkv["weight"])
@@ -405,7 +410,7 @@ def qkv_attn_quant_forward(*, x, qkv, scale, qk, pv, want_qkv=False, want_probs=
     like = lambda s: torch.empty(s, device="meta")
     _attn_matmul_desc(d.qk, q_shape, cont(q_shape), like(kT_shape), qk, "q k^T", who)
     _attn_matmul_desc(d.pv, (B, H, N, N), cont((B, H, N, N)), like(v_shape), pv, "p v", who)
-    d.scale, d.reserved = float(scale), 0
+    d.scale, d.reserved = float(scale), (_lib.ATTN_ONE_KERNEL if one_kernel else 0)
     sp = flat(pv["split"]) if sos else None
     out = torch.empty(B, H, N, D, dtype=torch.float32, device=dev)
     qkv_out = torch.empty(B, N, w.shape[0], dtype=torch.float32, device=dev) if want_qkv else None
@@ -427,7 +432,8 @@ def qkv_attn_quant_forward(*, x, qkv, scale, qk, pv, want_qkv=False, want_probs=
         info = (C.c_uint64 * 5)()
         _lib.check(lib.p4v_debug_attn_planes(info), "p4v_debug_attn_planes")
         off1, off2, rows, cols, twin = (int(v) for v in info)
-        planes += tuple(take(off, rows // Z, cols) for off in ((off1, off2) if twin else (off1,)))
+        if rows:                                       # (a one-kernel call reports sizes 0: no P1 / P2)
+            planes += tuple(take(off, rows // Z, cols) for off in ((off1, off2) if twin else (off1,)))
         res += (planes,)
     return res[0] if len(res) == 1 else res
 

@@ -152,6 +152,14 @@ def unfuse_mlp(net):
 # position bias and a mask before the softmax: not that kernel instance's arithmetic, fuse_attention skips it (it has
 # fuse_window_attention, below).
 _ORIG_ATTN = "_p4v_unfused_attn_forward"
+_ONE_KERNEL = "_p4v_attn_one_kernel"      # the patched container's choice: the attention core as one kernel
+
+
+def _choose_kernel(net, names, one_kernel):
+    for name, m in net.named_modules():
+        if name in names:
+            m.__dict__[_ONE_KERNEL] = bool(one_kernel)
+    return names
 
 
 def _inactive_dropout(drop):
@@ -198,19 +206,24 @@ def _fused_attention_forward(self, x):
     if os.environ.get("P4V_QKV_CONTIGUOUS", "1") == "1":
         qkv = qkv.contiguous()
     q, k, v = qkv.unbind(0)
-    out = engine.attn_quant_forward(q=q, kT=k.transpose(-2, -1), v=v, scale=self.scale, qk=args[0], pv=args[1])
+    out = engine.attn_quant_forward(q=q, kT=k.transpose(-2, -1), v=v, scale=self.scale, qk=args[0], pv=args[1],
+                                    one_kernel=self.__dict__.get(_ONE_KERNEL, False))
     return self.proj_drop(self.proj(out.transpose(1, 2).reshape(B, N, C)))
 
 
-def fuse_attention(net):
+def fuse_attention(net, one_kernel=False):
     """Patch the forward of every fusable Attention container of `net`; returns their names.  Idempotent.  On a container
-    fuse_qkv_attention patched it replaces that forward (the two share the saved forward: the later call decides)."""
-    return _patch(net, attention_fusable, _ORIG_ATTN, _fused_attention_forward, replace=True)
+    fuse_qkv_attention patched it replaces that forward (the two share the saved forward: the later call decides).
+    `one_kernel`: the patched containers ask the engine for the one-kernel attention core (stored on them; the later call
+    decides here too).  It changes neither when the fused path is taken nor what it returns."""
+    return _choose_kernel(net, _patch(net, attention_fusable, _ORIG_ATTN, _fused_attention_forward, replace=True), one_kernel)
 
 
 def unfuse_attention(net):
     """Undo fuse_attention or fuse_qkv_attention: every patched container gets its original forward back; returns their names.
     Idempotent."""
+    for m in net.modules():
+        m.__dict__.pop(_ONE_KERNEL, None)
     return _unfuse(net, _ORIG_ATTN)
 
 
@@ -250,14 +263,16 @@ def _fused_qkv_attention_forward(self, x):
         return _fused_attention_forward(self, x)      # (fuse_attention's path where its conditions hold, else the original)
     # models.Attention.forward, with qkv ... matmul2 as one engine call
     B, N, C = x.shape
-    out = engine.qkv_attn_quant_forward(x=x, qkv=args[0], scale=self.scale, qk=args[1], pv=args[2])
+    out = engine.qkv_attn_quant_forward(x=x, qkv=args[0], scale=self.scale, qk=args[1], pv=args[2],
+                                        one_kernel=self.__dict__.get(_ONE_KERNEL, False))
     return self.proj_drop(self.proj(out.transpose(1, 2).reshape(B, N, C)))
 
 
-def fuse_qkv_attention(net):
+def fuse_qkv_attention(net, one_kernel=False):
     """Patch the forward of every Attention container of `net` that fuse_attention would patch and whose qkv is a PTQSL Linear
-    layer; returns their names.  Idempotent.  On a container fuse_attention patched it replaces that forward."""
-    return _patch(net, qkv_attention_fusable, _ORIG_ATTN, _fused_qkv_attention_forward, replace=True)
+    layer; returns their names.  Idempotent.  On a container fuse_attention patched it replaces that forward.  `one_kernel`: as
+    in fuse_attention."""
+    return _choose_kernel(net, _patch(net, qkv_attention_fusable, _ORIG_ATTN, _fused_qkv_attention_forward, replace=True), one_kernel)
 
 
 # ---- window attention (Swin): matmul1 -> + bias -> + mask -> softmax -> matmul2 (engine.window_attn_quant_forward, DESIGN.md s5.10) ----

@@ -14,6 +14,8 @@ k_attn_qk in place of matmul1's sweep, torch's `+ bias`, `+ mask` and softmax an
 attention, without it attention alone.
 --fused-qkv: a fourth variant in the same alternation: fuse_qkv_attention in place of fuse_attention (k_qkv_heads in place of the
 qkv sweep, the permute copy and the three k_pack1 of q, k^T and v), on top of the fused MLPs with --fused.
+--one-kernel: a fifth variant in the same alternation: fuse_qkv_attention(one_kernel=True) (k_attn_qkpv in place of k_attn_qk and
+matmul2's sweep), on top of the fused MLPs with --fused; compared with fused_qkv.
 """
 import argparse
 import hashlib
@@ -98,6 +100,8 @@ def main():
                     help="also time the network with fused attention (utils/fuse.py::fuse_attention and fuse_window_attention; with --fused: on top of the fused MLPs)")
     ap.add_argument("--fused-qkv", action="store_true",
                     help="also time the network with the qkv layer fused into the attention chain (utils/fuse.py::fuse_qkv_attention; with --fused: on top of the fused MLPs)")
+    ap.add_argument("--one-kernel", action="store_true",
+                    help="also time fuse_qkv_attention(one_kernel=True): the attention core as one kernel (with --fused: on top of the fused MLPs)")
     ap.add_argument("--json", default=None, help="write the result to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -134,7 +138,7 @@ def main():
           f"logit rel diff {((y_q - y_raw).norm() / y_raw.norm()).item():.3e}")
     res = {"model": a.model, "batch": a.batch, "reps": a.reps, "source_hash": _lib.source_hash(),
            "raw_fp32_ms": t_raw * 1e3, "quant_forward_ms": t_q * 1e3, "quant_vs_fp32": t_raw / t_q}
-    if a.fused or a.fused_attn or a.fused_qkv:
+    if a.fused or a.fused_attn or a.fused_qkv or a.one_kernel:
         # the variants alternating, repetition by repetition, after one warm-up of each: (key, fuse the MLPs, fuse the attention --
         # "qkv": with the qkv layer)
         variants = [("unfused", False, False)]
@@ -144,12 +148,16 @@ def main():
             variants.append(("fused_attn", a.fused, True))
         if a.fused_qkv:
             variants.append(("fused_qkv", a.fused, "qkv"))
+        if a.one_kernel:
+            variants.append(("fused_qkv_one", a.fused, "qkv1"))
 
         def setup(mlp, attn):
             fuse.unfuse_mlp(net)
             fuse.unfuse_attention(net)
             fuse.unfuse_window_attention(net)
-            fuse_attn = fuse.fuse_qkv_attention if attn == "qkv" else fuse.fuse_attention
+            fuse_attn = fuse.fuse_attention
+            if attn in ("qkv", "qkv1"):
+                fuse_attn = lambda n: fuse.fuse_qkv_attention(n, one_kernel=attn == "qkv1")
             return (len(fuse.fuse_mlp(net)) if mlp else 0, len(fuse_attn(net)) + len(fuse.fuse_window_attention(net)) if attn else 0)
 
         ts = {key: [] for key, _, _ in variants}
@@ -170,6 +178,11 @@ def main():
                 print(f"  unfused {t_u * 1e3:.2f} ms, fused MLPs ({n_mlp}) {t_v * 1e3:.2f} ms: x{t_u / t_v:.3f}; "
                       f"fused vs fp32 x{t_raw / t_v:.2f}; logit rel diff fused vs unfused {rel:.3e}")
                 res["fused_mlps"] = n_mlp
+            elif key == "fused_qkv_one":
+                base_key = "fused_qkv" if a.fused_qkv else "fused" if a.fused else "unfused"
+                print(f"  one-kernel attention core ({n_attn}{' + MLPs' if a.fused else ''}) {t_v * 1e3:.2f} ms: x{med[base_key] / t_v:.3f} "
+                      f"over {base_key} ({(med[base_key] - t_v) * 1e3:+.3f} ms), x{t_u / t_v:.3f} over unfused; logit rel diff vs unfused {rel:.3e}")
+                res.update({base_key + "_over_fused_qkv_one": med[base_key] / t_v, base_key + "_minus_fused_qkv_one_ms": (med[base_key] - t_v) * 1e3})
             elif key == "fused_qkv":
                 base_key = "fused_attn" if a.fused_attn else "fused" if a.fused else "unfused"
                 print(f"  fused qkv + attention ({n_attn}{' + MLPs' if a.fused else ''}) {t_v * 1e3:.2f} ms: x{med[base_key] / t_v:.3f} "
