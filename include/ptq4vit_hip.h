@@ -49,7 +49,8 @@
 extern "C" {
 #endif
 
-#define P4V_VERSION 146 /* 0.1.4.6: + P4V_ATTN_ONE_KERNEL (the fused attention core as one kernel: p v from the probabilities in registers) */
+#define P4V_VERSION 147 /* 0.1.4.7: + P4V_WATTN_ONE_KERNEL (the fused window attention core as one kernel: a window's score rows held in registers) */
+/* 0.1.4.6: + P4V_ATTN_ONE_KERNEL (the fused attention core as one kernel: p v from the probabilities in registers) */
 /* 0.1.4.5: + p4v_qkv_attn_* (the fused int8 qkv forward: the qkv GEMM writes the attention operand planes) */
 
 /* similarity metrics: reference quant_layers/linear.py:399-424 */
@@ -531,7 +532,16 @@ int p4v_attn_quant_forward(const p4v_attn_desc* desc, const float* d_q, const fl
  * optional (may be NULL) [batch*heads][M][N] fp32; ws, ws_bytes: the workspace and its size -- the workspace contract above
  * holds with p4v_wattn_workspace_bytes, which equals p4v_attn_workspace_bytes of the same two MatMuls; a smaller ws_bytes is
  * refused before any launch.
+ * pv.reserved bit 4 (P4V_WATTN_ONE_KERNEL; the descriptor has no word of its own to ask with, and `pv` is the MatMul whose launch
+ * disappears): the two kernels of the chain become one (k_wattn_qkpv).  A window has few keys, so a wave keeps the whole score
+ * row of its 32 queries in registers: the scores, the bias and the mask are produced once instead of once per walk over the
+ * keys, matmul2's GEMM runs on the quantised probabilities in registers, and matmul2's row plane(s), their padding and the sweep
+ * that read them do not exist.  d_out and d_probs equal the two-kernel call's bit for bit.  Instances serve N <= 160 keys,
+ * Dv = pv.N <= 32 and qk.K <= 64; beyond that the bit is accepted and the two-kernel chain runs.  p4v_wattn_workspace_bytes
+ * answers for the descriptor as given: with the bit the exact, smaller size.  Every other entry point ignores the bit; with the
+ * bit clear every launch is what it was.
  * ---------------------------------------------------------------------------------------- */
+#define P4V_WATTN_ONE_KERNEL 16
 typedef struct p4v_wattn_desc {
     p4v_matmul_desc qk, pv;
     int32_t n_windows;

@@ -83,8 +83,9 @@ int p4v_debug_arena_ranges(uint64_t* out, int cap);
 int p4v_debug_mlp_planes(uint64_t* out);
 /* The same for the calling thread's last p4v_attn_quant_forward or p4v_wattn_quant_forward (the window call shares the chain
  * and its record) and matmul2's row plane(s), [batch*heads][Mp][Kp]: out[2] = batch * heads * Mp (all rows of a plane),
- * out[3] = Kp.  After a one-kernel call (P4V_ATTN_ONE_KERNEL served by k_attn_qkpv) no such plane exists: the call succeeds with
- * out[0..3] = 0 (out[4] still tells whether the quantiser was the twin pair). */
+ * out[3] = Kp.  After a one-kernel call (P4V_ATTN_ONE_KERNEL served by k_attn_qkpv, P4V_WATTN_ONE_KERNEL served by
+ * k_wattn_qkpv) no such plane exists: the call succeeds with out[0..3] = 0 (out[4] still tells whether the quantiser was the twin
+ * pair). */
 int p4v_debug_attn_planes(uint64_t info[5]);
 /* Where the calling thread's last p4v_qkv_attn_quant_forward left the three operand planes k_qkv_heads wrote (matmul2's row
  * plane(s) of that call: p4v_debug_attn_planes): info[0..2] = byte offsets of Q(q), Q(k^T), Q(v) from ws, info[3] = Z = batch *

@@ -93,7 +93,7 @@ class LaunchRecord(C.Structure):
 
 LAUNCH_KINDS = {0: "k_sweep<int8>", 1: "k_sweep<float>", 2: "k_sweep6", 3: "k_sweep7", 4: "k_sweep7 (twin)", 5: "k_sweep4/5", 6: "k_sweep9",
                 7: "k_sweep8", 8: "k_sweep2g", 9: "k_sweep2", 11: "k_sos_split", 12: "k_bound", 13: "k_slice_b", 14: "k_slice_a", 15: "k_sweep_seg", 16: "k_mlp_fc1",
-                17: "k_attn_qk", 18: "k_qkv_heads", 19: "k_attn_qkpv"}
+                17: "k_attn_qk", 18: "k_qkv_heads", 19: "k_attn_qkpv", 20: "k_wattn_qkpv"}
 LAUNCH_STAGES = {0: "full", 1: "A", 2: "B1", 3: "B2", 4: "A2"}
 
 
@@ -122,6 +122,7 @@ JOB_LINEAR, JOB_MATMUL, JOB_CONV, JOB_MATMUL_BLOCKS = 0, 1, 2, 3
 # bits of a descriptor's `reserved` word (include/ptq4vit_hip.h documents which descriptor reads which)
 RESERVED_FP32_PLANES, RESERVED_NO_MEMO, RESERVED_FORWARD_ONLY, RESERVED_NO_PRUNE = 1, 2, 4, 8
 ATTN_ONE_KERNEL = 1          # p4v_attn_desc / p4v_qkv_attn_desc .reserved bit 0: the attention core as one kernel (version 146)
+WATTN_ONE_KERNEL = 16        # p4v_wattn_desc.pv.reserved bit 4: the window attention core as one kernel (version 147)
 RESERVED_BLOCK_SHIFT = 8     # bits 8..11 (p4v_linear_search_w / _a): 1 + b runs the step of block b alone
 
 

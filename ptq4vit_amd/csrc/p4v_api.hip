@@ -3156,7 +3156,7 @@ thread_local FusedPlanes g_mlp_planes, g_attn_planes;
 // ... and the three operand planes k_qkv_heads wrote (p4v_debug_qkv_planes): offsets, then Z and the planes' rows / row lengths
 struct QkvPlanes { size_t off_q = 0, off_k = 0, off_v = 0; long Z = 0, rows_q = 0, rows_k = 0, ld_qk = 0, rows_v = 0, ld_v = 0; };
 thread_local QkvPlanes g_qkv_planes;
-constexpr int MLP_RECORD_KIND = 16, ATTN_RECORD_KIND = 17, QKV_RECORD_KIND = 18, ATTN_PV_RECORD_KIND = 19;
+constexpr int MLP_RECORD_KIND = 16, ATTN_RECORD_KIND = 17, QKV_RECORD_KIND = 18, ATTN_PV_RECORD_KIND = 19, WATTN_PV_RECORD_KIND = 20;
 
 // One producer -> consumer chain, in the order its caller walks it: plan_consumer, produce, consume.
 struct FusedChain {
@@ -3622,11 +3622,17 @@ struct QkvProducer {
 // `produce` makes them, matmul2's column plane and scale table(s) as its forward pass makes them (pack_operand, k_scale_table) --
 // or all three planes as k_qkv_heads wrote them (`pre`) --, then the kernel.  No row plane of matmul2 exists: nothing was carved
 // for it, and p4v_debug_attn_planes reports sizes 0.  Everything is scratch of the bump region and given back.
+// `win` (P4V_WATTN_ONE_KERNEL; k_wattn_qkpv): the same planes and tables, the window kernel -- its grid is flat
+// over the live 32-row tiles, ceil(M / 32) per z, four to a workgroup; `ndt` then is its NT, the resident 32-key tiles.
 int attn_one_kernel(Ctx& c, FusedChain& ch, float scale, int ndt, const MatMulTensors& t1, const MatMulCall& m1, const MatMulTensors& t2,
-                    const MatMulCall& m2, const FusedChain::PrePlanes* pre) {
+                    const MatMulCall& m2, const FusedChain::PrePlanes* pre, const AttnWindow* win = nullptr) {
     const int Z = ch.Z, H = m1.H, M = m1.M, N = m1.N, K1 = m1.K, Dv = m2.N;
     const bool twin = ch.twin;
-    const SweepPlan& pl2 = ch.pl2;
+    // (the window kernel reads ONE output tile: its column plane is packed with 32 rows per z instead of the sweep's NpB --
+    // k_pack1 takes any row count in the row-major layout, which plan_consumer holds the plan to)
+    SweepPlan plv = ch.pl2;
+    if (win) plv.NpB = 32;
+    const SweepPlan& pl2 = plv;
     const size_t mark = c.ws.off;
     FusedChain::Packed pk{};
     Pass fp1 = m1.forward_pass();
@@ -3640,7 +3646,34 @@ int attn_one_kernel(Ctx& c, FusedChain& ch, float scale, int ndt, const MatMulTe
     CHK(launch_scale(c, fp2.s1));
     if (twin) { fp2.s2.S = So2; fp2.s2.C = 1; fp2.s2.nblk = fp2.s_cs; CHK(launch_scale(c, fp2.s2)); }
     if (!pre) CHK(pack_operand(c, fp2, pl2, PassBufs{}, fp2.col, vplane, true, 0, 1));
-    if (!c.dry) {
+    if (!c.dry && win) {
+        WattnQkPvParams q{};
+        q.Q = pk.rows; q.Kt = pk.cols; q.q_zs = (long)ch.Mp * pk.Kp; q.k_zs = (long)pk.Np * pk.Kp; q.ldk = pk.Kp;
+        q.S1 = pk.S1; q.H = H;
+        q.M = M; q.N = N;
+        q.bias = win->bias; q.mask = win->mask; q.n_windows = win->n_windows;
+        q.qs = twin ? t2.split : t2.A_iv; q.qs_headwise = twin ? 0 : 1;
+        q.lo = -m2.Aq; q.hi = m2.Aq - 1; q.qm1 = (float)(m2.Aq - 1);
+        q.V = vplane; q.v_zs = (long)pl2.NpB * pl2.Kp; q.ldv = pl2.Kp;
+        q.So1 = So1; q.So2 = So2;
+        q.out = t2.fwd_out; q.Dv = Dv; q.vec4 = (Dv % 4 == 0 && ((unsigned long long)t2.fwd_out & 15) == 0) ? 1 : 0;
+        q.probs = t1.fwd_out;
+        q.tpz = (M + 31) / 32; q.nwaves = Z * q.tpz; q.nwg = (q.nwaves + 3) / 4;
+        g_alg_macs_cand = (double)Z * M * N * (K1 + Dv);
+        // the three operand planes, the bias, the mask, out and probs
+        g_alg_bytes = (double)Z * ((double)M * K1 + (double)N * K1 + (double)N * Dv) + 4.0 * (double)M * N * (H + (win->mask ? win->n_windows : 0)) +
+                      4.0 * (double)Z * M * Dv + (t1.fwd_out ? 4.0 * (double)Z * M * N : 0.0);
+        g_exec_frac = 1.0;
+        // (ONE walk over the keys per live row tile: the q k^T MFMAs and one MFMA per plane and key tile)
+        const double tiles = (double)q.nwaves * 32.0 * (double)rup(N, 32);
+        const StatInfo si = stat_info(WATTN_PV_RECORD_KIND, tiles * (pk.Kp + 32.0 * (twin ? 2 : 1)), g_alg_macs_cand, q.nwg, 1, g_alg_bytes);
+        const dim3 grid(q.nwg), block(256);
+        if (ndt == 2) CHK(twin ? enqueue(c, KERN1_T(WattnQkPvParams, k_wattn_qkpv, true, 2), grid, block, 0, q, &si)
+                               : enqueue(c, KERN1_T(WattnQkPvParams, k_wattn_qkpv, false, 2), grid, block, 0, q, &si));
+        else CHK(twin ? enqueue(c, KERN1_T(WattnQkPvParams, k_wattn_qkpv, true, 5), grid, block, 0, q, &si)
+                      : enqueue(c, KERN1_T(WattnQkPvParams, k_wattn_qkpv, false, 5), grid, block, 0, q, &si));
+        g_attn_planes = FusedPlanes{0, 0, 0, 0, twin ? 1 : 0, true};
+    } else if (!c.dry) {
         AttnQkPvParams q{};
         q.Q = pk.rows; q.Kt = pk.cols; q.q_zs = (long)ch.Mp * pk.Kp; q.k_zs = (long)pk.Np * pk.Kp; q.ldk = pk.Kp; q.ktiles = pk.Kp / SW_BKB;
         q.S1 = pk.S1; q.H = H; q.scale = scale;
@@ -3702,14 +3735,19 @@ int attn_chain(const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulTens
     if (ch.Mp % SW_BM || (long)Z * (ch.Mp / SW_BM) >= (1L << 31)) return fail(P4V_ERR_UNSUPPORTED, "attn: %d x %d row tiles", Z, ch.Mp / SW_BM);
     // One kernel or two, decided here and nowhere else: the caller asked for it, k_attn_qkpv has an instance for Dv (NDT = 2 / 4
     // output tiles of 32) and the column plane holds the NDT * 32 rows its lanes address -- b64: 64 rows and Dv <= 64, else
-    // roundup128(Dv).  The window call has no bit to ask with.
-    const int ndt = m2.N <= 64 ? 2 : 4;
-    const bool one_kernel = (d->reserved & P4V_ATTN_ONE_KERNEL) && !win && m2.N <= 128 && ndt * 32 <= ch.pl2.NpB;
+    // roundup128(Dv).  The window call (its entry point translates P4V_WATTN_ONE_KERNEL into the same bit): k_wattn_qkpv has an
+    // instance for N (NT = 2 / 5 resident key tiles of 32), one output tile (Dv <= 32, in a column plane of >= 32 rows) and one
+    // k-tile of q k^T (K <= 64).  Whatever has no instance runs the two-kernel chain: the bit is a request, not a condition.
+    const int ndt = win ? (N <= 64 ? 2 : 5) : (m2.N <= 64 ? 2 : 4);
+    const bool asked = (d->reserved & P4V_ATTN_ONE_KERNEL) != 0;
+    const bool one_kernel = asked && (win ? N <= 160 && m2.N <= 32 && FusedChain::producer_kp(K1) == SW_BKB && 32 <= ch.pl2.NpB &&
+                                                (long)Z * ((M + 31) / 32) < (1L << 31)
+                                          : m2.N <= 128 && ndt * 32 <= ch.pl2.NpB);
     if (!one_kernel) ch.carve();
     FusedChain::PrePlanes planes{};
     const FusedChain::PrePlanes* pre = qkv ? &planes : nullptr;
     if (qkv) CHK(qkv->run(c, ch, H, N, K1, t1, m1, t2, m2, planes));
-    if (one_kernel) return attn_one_kernel(c, ch, d->scale, ndt, t1, m1, t2, m2, pre);
+    if (one_kernel) return attn_one_kernel(c, ch, d->scale, ndt, t1, m1, t2, m2, pre, win);
     CHK(ch.produce(m1.forward_pass(), K1, N, H, g_attn_planes, [&](const FusedChain::Packed& pk) -> int {
         AttnQkParams q{};
         q.Q = pk.rows; q.Kt = pk.cols; q.q_zs = (long)ch.Mp * pk.Kp; q.k_zs = (long)pk.Np * pk.Kp; q.ldk = pk.Kp; q.ktiles = pk.Kp / SW_BKB;
@@ -4275,6 +4313,10 @@ int p4v_attn_quant_forward(const p4v_attn_desc* desc, const float* d_q, const fl
 static WattnCall wattn_call(const p4v_wattn_desc* desc, const p4v_wattn_tensors* t) {
     WattnCall w{};
     w.a.qk = desc->qk; w.a.pv = desc->pv; w.a.scale = 1.0f;
+    // the request for the one-kernel core travels in pv.reserved (the descriptor has no word of its own): hand it to attn_chain as
+    // the chain's bit and take it out of the MatMul descriptor, which does not know it
+    w.a.reserved = (desc->pv.reserved & P4V_WATTN_ONE_KERNEL) ? P4V_ATTN_ONE_KERNEL : 0;
+    w.a.pv.reserved &= ~P4V_WATTN_ONE_KERNEL;
     w.w = AttnWindow{t ? t->bias : nullptr, t ? t->mask : nullptr, desc->n_windows};
     return w;
 }
@@ -4692,7 +4734,7 @@ static int stats_drain() {
         float ms = 0;
         HIPCHK(hipEventElapsedTime(&ms, r.a, r.b));
         ms = (float)std::max(0.0, (double)ms - g_evt_overhead_ms);
-        if (r.kind == 0 || (r.kind >= 2 && r.kind <= 9) || (r.kind >= 12 && r.kind <= 19)) { g_stats.sweep_i8_ms += ms; g_stats.sweep_i8_launches++; g_stats.sweep_i8_macs += r.macs; g_stats.sweep_i8_alg_macs += r.alg; }
+        if (r.kind == 0 || (r.kind >= 2 && r.kind <= 9) || (r.kind >= 12 && r.kind <= 20)) { g_stats.sweep_i8_ms += ms; g_stats.sweep_i8_launches++; g_stats.sweep_i8_macs += r.macs; g_stats.sweep_i8_alg_macs += r.alg; }
         if (r.kind == 2) { g_stats.sweep6_ms += ms; g_stats.sweep6_launches++; g_stats.sweep6_macs += r.macs; g_stats.sweep6_alg_macs += r.alg; }
         if (r.kind == 3 || r.kind == 4) { g_stats.sweep7_ms += ms; g_stats.sweep7_launches++; g_stats.sweep7_macs += r.macs; g_stats.sweep7_alg_macs += r.alg; }
         if (r.kind == 4) { g_stats.sweep7_twin_ms += ms; g_stats.sweep7_twin_launches++; }

@@ -5680,4 +5680,210 @@ __global__ __launch_bounds__(256) void k_attn_qkpv(AttnQkPvParams p) {
         }
 }
 
+// ------------------------------------------------------------------------------------------
+// Fused window attention forward, both halves (p4v_wattn_quant_forward with P4V_WATTN_ONE_KERNEL): q k^T -> + bias -> + mask ->
+// softmax -> split quantiser -> p v in one launch, the whole score row of a window held in registers
+// ------------------------------------------------------------------------------------------
+// A window has few keys (49, 64, 144), so a wave keeps ALL scores of its 32 queries: u[NT][16], NT = the compile-time number of
+// 32-key tiles (2: N <= 64; 5: N <= 160), every loop over the tiles unrolled over NT and guarded by the uniform nt < ceil(N / 32).
+// The scores, the bias and the mask are therefore produced ONCE -- k_attn_qk<., true>, which serves any number of keys, runs
+// the GEMM and the per-lane bias / mask loads in each of its three walks, and those loads are what bound it.
+// Work split: a wave owns 32 queries of one z and never meets another wave -- no LDS, no barrier.  The grid is flat over the
+// LIVE 32-row tiles: tpz = ceil(M / 32) per z, wave w = 4 * workgroup + wid takes z = w / tpz and row tile w % tpz, waves
+// w >= Z * tpz return.  No wave exists for rows that are only plan padding (Mp = roundup128(M): half the waves at 49 tokens).
+// Walk 1 (the only one that reads memory for scores): per resident tile the two MFMAs of the transposed product on the planes
+// `pack_pair` makes (one k-tile: the query fragments stay in two v4i), then k_attn_qk<., true>'s expression, each step rounded:
+//   t = (float)acc * S1[head];  u = t + bias[head][m][n];  if (mask) u = u + mask[window][m][n]
+// with its loads: a register quad is one 16-byte piece where N % 4 == 0 and both tensors are 16-byte aligned, four dwords
+// otherwise, offsets clamped for the padding, each quad's loads chained behind the previous quad's additions.
+// The maximum and the sum come from the registers in k_attn_qk's order (tile by tile, one partial sum per accumulator register,
+// the same pairwise tree, the exchange between the lane halves); e = expf(u - max) overwrites u, so walk 3 calls no expf:
+// k_attn_qk's window build feeds expf the same rounded difference in its sum and write walks (__fsub_rn on a u that is the
+// result of an addition: nothing to contract), which tests/test_hip_fused_window_attention_pv.py holds to the same bits.
+// Walk 3: e / sum, probs, pack_value, the four words w1 / w2 in k_attn_qkpv's slot order (byte e of word q4 is key key0 + 8 q4 +
+// 4 g + e), one MFMA per plane with the tile's V fragment -- four aligned dwords of row l31 (= d) of matmul2's column plane
+// Q(v^T) [Z][vrows][ldv].  Dv <= 32: ONE output tile, acc1 / acc2 of 16 registers.  All NT V fragments are loaded before walk 1,
+// which covers them.  Keys >= N and queries >= M give the byte 0.  Epilogue and stores: k_attn_qkpv's.
+struct WattnQkPvParams {
+    const void* Q; const void* Kt;            // [Z][Mp][ldk] / [Z][Np1][ldk], ldk = 64 (one k-tile)
+    long q_zs, k_zs; int ldk;
+    const float* S1; int H;                   // A_interval[head] * B_interval[head] of matmul1 (k_scale_table)
+    int M, N;                                 // valid queries / keys; ceil(N / 32) <= NT
+    const float* bias; const float* mask;     // [H][M][N]; [n_windows][M][N] or null
+    int n_windows;
+    const float* qs; int qs_headwise;         // matmul2's A quantiser: the split (TWIN) or A_interval[head]
+    int lo, hi; float qm1;
+    const void* V; long v_zs; int ldv;        // matmul2's column plane [Z][vrows >= 32][ldv] at [d][key]; ldv = roundup64(N)
+    const float* So1; const float* So2;       // matmul2's scale tables [H] (So2: TWIN)
+    float* out; int Dv, vec4;                 // [Z][M][Dv], Dv <= 32
+    float* probs;
+    int tpz, nwaves, nwg;                     // 32-query tiles per z; Z * tpz; workgroups = ceil(nwaves / 4)
+};
+
+template <bool TWIN, int NT>
+__global__ __launch_bounds__(256) void k_wattn_qkpv(WattnQkPvParams p) {
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int g = lane >> 5, l31 = lane & 31;
+    const int w = xcd_remap(blockIdx.x, p.nwg) * 4 + wid;
+    if (w >= p.nwaves) return;                        // (wave-uniform; no barrier in this kernel) the flat grid's tail
+    const int z = w / p.tpz, m0 = (w % p.tpz) * 32;   // the row tiles of one z are adjacent: they share its key and value planes
+    const int m = m0 + l31;
+    const bool row_ok = m < p.M;
+    const int head = z % p.H;
+    const int ntiles = (p.N + 31) / 32;               // <= NT (the host chose the instance)
+
+    const char* gQ = (const char*)p.Q + (long)z * p.q_zs + (long)m * p.ldk + g * 16;
+    const char* gK = (const char*)p.Kt + (long)z * p.k_zs + (long)l31 * p.ldk + g * 16;
+    const char* gV = (const char*)p.V + (long)z * p.v_zs + (long)l31 * p.ldv + g * 4;
+    const v4i qf0 = *reinterpret_cast<const v4i*>(gQ), qf1 = *reinterpret_cast<const v4i*>(gQ + 32);
+    // the whole V plane of this z first (nt * 32 + 8 q4 + 4 g + 3 < roundup32(N) <= ldv: inside the row)
+    v4i vf[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) vf[nt][q4] = nt < ntiles ? *reinterpret_cast<const int*>(gV + nt * 32 + 8 * q4) : 0;
+    const float s1 = p.S1[head];
+    // where this query's row of the bias and of the mask begins, in floats (padding rows: the last row's; the host holds both
+    // tensors below 2^30 elements)
+    const int mc = min(m, p.M - 1);
+    const unsigned rowB = (unsigned)((head * p.M + mc) * p.N);
+    const unsigned rowM = (unsigned)((((z / p.H) % p.n_windows) * p.M + mc) * p.N);
+    const bool masked = p.mask != nullptr;
+    const bool vec4 = (p.N & 3) == 0 && (((unsigned long long)p.bias | (unsigned long long)p.mask) & 15) == 0;
+
+    // ---- walk 1: u of every resident tile ------------------------------------------------------------------
+    float u[NT][16];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+#pragma clang fp contract(off)
+        if (nt >= ntiles) break;
+        const int key0 = nt * 32;
+        v16i acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0;
+        const char* ka = gK + (long)key0 * p.ldk;
+        const v4i a0 = *reinterpret_cast<const v4i*>(ka), a1 = *reinterpret_cast<const v4i*>(ka + 32);
+        acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, qf0, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, qf1, acc, 0, 0, 0);
+        // three roundings, no fma, the bias and the mask two separate additions (k_attn_qk<., true>'s block, load for load)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) u[nt][r] = (float)acc[r] * s1;
+        int nb = key0 + 4 * g;                             // the lane's first key of the tile
+#pragma unroll
+        for (int c = 0; c < 16; c += ATTN_WCH) {
+            float bq[ATTN_WCH], mq[ATTN_WCH];
+            if (vec4) {                                    // (uniform) the quad is one 16-byte piece, all of it inside the row or none
+                const unsigned o = (unsigned)min(nb + acc32_row(c), p.N - 4);
+                const v4f b4 = *reinterpret_cast<const v4f*>(p.bias + rowB + o);
+                v4f m4 = {0.0f, 0.0f, 0.0f, 0.0f};
+                if (masked) m4 = *reinterpret_cast<const v4f*>(p.mask + rowM + o);
+#pragma unroll
+                for (int j = 0; j < ATTN_WCH; ++j) { bq[j] = b4[j]; mq[j] = m4[j]; }
+            } else {
+#pragma unroll
+                for (int j = 0; j < ATTN_WCH; ++j) {
+                    const unsigned o = (unsigned)min(nb + acc32_row(c + j), p.N - 1);
+                    bq[j] = p.bias[rowB + o];
+                    mq[j] = masked ? p.mask[rowM + o] : 0.0f;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < ATTN_WCH; ++j) {
+                u[nt][c + j] = u[nt][c + j] + bq[j];
+                if (masked) u[nt][c + j] = u[nt][c + j] + mq[j];
+                asm volatile("" : "+v"(nb), "+v"(u[nt][c + j]));   // (the next quad's loads stay behind this quad's additions)
+            }
+        }
+    }
+    // ---- the row maximum and the row sum, from the registers, in k_attn_qk's order -----------------------------
+    float mx = -__builtin_inff();
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        if (nt >= ntiles) break;
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (nt * 32 + acc32_row(r, g) < p.N) mx = fmaxf(mx, u[nt][r]);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    float part[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) part[r] = 0.0f;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        if (nt >= ntiles) break;
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (nt * 32 + acc32_row(r, g) < p.N) {
+                u[nt][r] = expf(__fsub_rn(u[nt][r], mx));  // (kept for walk 3)
+                part[r] = __fadd_rn(part[r], u[nt][r]);
+            }
+    }
+#pragma unroll
+    for (int w2 = 8; w2 >= 1; w2 >>= 1)
+#pragma unroll
+        for (int r = 0; r < w2; ++r) part[r] = __fadd_rn(part[r], part[r + w2]);
+    const float sum = __fadd_rn(part[0], __shfl_xor(part[0], 32));
+    // ---- walk 3: the probabilities, matmul2's quantiser, matmul2's GEMM on the bytes in registers -------------
+    const float qs = p.qs[p.qs_headwise ? head : 0];
+    PackParams pv1{}, pv2{};
+    pv1.mode = TWIN ? PACK_SOS_HI : PACK_SYM; pv1.lo = p.lo; pv1.hi = p.hi; pv1.qm1 = p.qm1;
+    pv2.mode = PACK_SOS_LO; pv2.qm1 = p.qm1;
+    v16i acc1;
+    [[maybe_unused]] v16i acc2;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc1[r] = 0; if (TWIN) acc2[r] = 0; }
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        if (nt >= ntiles) break;
+        const int key0 = nt * 32;
+        v4i w1 = {0, 0, 0, 0};
+        [[maybe_unused]] v4i w2 = {0, 0, 0, 0};
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+            int x1 = 0, x2 = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int r = q4 * 4 + e;
+                const int n = key0 + e + 8 * q4 + 4 * g;
+                float b1 = 0.0f, b2 = 0.0f;
+                if (row_ok && n < p.N) {
+                    const float pr = __fdiv_rn(u[nt][r], sum);
+                    if (p.probs) p.probs[((long)z * p.M + m) * p.N + n] = pr;
+                    b1 = pack_value(pv1, pr, qs);
+                    if (TWIN) b2 = pack_value(pv2, pr, qs);
+                }
+                x1 |= ((int)b1 & 0xff) << (8 * e);
+                if (TWIN) x2 |= ((int)b2 & 0xff) << (8 * e);
+            }
+            w1[q4] = x1;
+            if (TWIN) w2[q4] = x2;
+        }
+        acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(vf[nt], w1, acc1, 0, 0, 0);
+        if (TWIN) acc2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(vf[nt], w2, acc2, 0, 0, 0);
+    }
+    // ---- epilogue: EPI_FWD's expression, the lane's query row of out (k_attn_qkpv's, one output tile) ---------
+    if (!row_ok) return;
+    const float so1 = p.So1[head];
+    const float so2 = TWIN ? p.So2[head] : 0.0f;
+    float* orow = p.out + ((long)z * p.M + m) * p.Dv;
+#pragma unroll
+    for (int q4 = 0; q4 < 4; ++q4) {
+        const int d0 = 8 * q4 + 4 * g;
+        v4f o4;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float o = (float)acc1[q4 * 4 + e] * so1;
+            if (TWIN) o = fmaf((float)acc2[q4 * 4 + e], so2, o);
+            o4[e] = o + 0.0f;
+        }
+        if (p.vec4) {                                  // (uniform) Dv % 4 == 0: the quad is inside the row or outside it
+            if (d0 < p.Dv) *reinterpret_cast<v4f*>(orow + d0) = o4;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (d0 + e < p.Dv) orow[d0 + e] = o4[e];
+        }
+    }
+}
+
 }  // namespace p4v

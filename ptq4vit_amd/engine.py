@@ -348,13 +348,18 @@ def attn_quant_forward(*, q, kT, v, scale, qk, pv, want_probs=False, want_planes
                           want_planes, z=q.shape[0] * q.shape[1])
 
 
-def window_attn_quant_forward(*, q, kT, v, bias, mask=None, qk, pv, want_probs=False, want_planes=False):
+def window_attn_quant_forward(*, q, kT, v, bias, mask=None, qk, pv, want_probs=False, want_planes=False, one_kernel=False):
     """matmul2(softmax(matmul1(q, kT) + bias (+ mask), -1), v) of the two calibrated MatMuls of a window attention block
     (models.WindowAttention) in quant_forward, fused (p4v_wattn_quant_forward): attn_quant_forward's chain with the window
     arithmetic between matmul1 and the softmax.  `q` arrives ALREADY SCALED, as the module hands it to matmul1.
     q [B_][H][N][D], kT [B_][H][D][N], v [B_][H][N][Dv] (B_ = images * windows, windows innermost; views are not copied); bias
     [H][N][N]; mask None or [nW][N][N] with B_ % nW == 0, added to window (b_ % nW) of every image and head; -inf entries
-    behave as in torch.  Checks, `qk` / `pv`, want_probs, want_planes and the returned values: as attn_quant_forward."""
+    behave as in torch.  Checks, `qk` / `pv`, want_probs, want_planes and the returned values: as attn_quant_forward.
+    `one_kernel` (P4V_WATTN_ONE_KERNEL): the whole chain as k_wattn_qkpv, which keeps a window's score rows in registers -- no
+    plane exists, so `want_planes` with it is a ValueError; out and probs are the same bits.  More than 160 keys, Dv > 32 or a
+    head_dim above 64 have no instance of that kernel and run the two-kernel chain."""
+    if one_kernel and want_planes:
+        raise ValueError("window_attn_quant_forward: one_kernel writes no planes of matmul2 (want_planes)")
     d = _lib.WattnDesc()
     dev, q, kT, v, (qk_A, qk_B, pv_A, pv_B, sp), out, probs = _attn_call("window_attn_quant_forward", q, kT, v, qk, pv, want_probs, d)
     b, H, M, _ = q.shape
@@ -367,6 +372,8 @@ def window_attn_quant_forward(*, q, kT, v, bias, mask=None, qk, pv, want_probs=F
         if mask.dim() != 3 or tuple(mask.shape[1:]) != (M, N):
             raise ValueError(f"window_attn_quant_forward: mask {tuple(mask.shape)} is not [windows][M][N] = [*]{(M, N)}")
     d.n_windows, d.has_mask = (1 if mask is None else mask.shape[0]), int(mask is not None)
+    if one_kernel:
+        d.pv.reserved |= _lib.WATTN_ONE_KERNEL
     tensors = dict(q=q, kT=kT, v=v, bias=bias, mask=mask, qk_A_interval=qk_A, qk_B_interval=qk_B, pv_A_interval=pv_A, pv_B_interval=pv_B,
                    split=sp, out=out, probs=probs)
     return _fused_forward("wattn", d, tensors, dev, (out, probs) if want_probs else (out,), want_planes, z=b * H)

@@ -21,6 +21,7 @@ module's -- qkv, `q * self.scale` in torch (matmul1 was calibrated on the scaled
 -- and replaces matmul1 -> `+ bias` -> `+ mask` -> softmax -> matmul2 by engine.window_attn_quant_forward
 (p4v_wattn_quant_forward) under fuse_attention's per-call conditions and one more: the mask is None or a
 float32 [nW][N][N] tensor with B_ % nW == 0.  Each of the three fuse_* keeps its own saved forward: they compose in any order.
+`fuse_window_attention(net, one_kernel=True)` asks for the one-kernel window core (k_wattn_qkpv): same bits.
 
 `fuse_qkv_attention(net)` / `takes_fused_qkv_attention_path(m, x)` take the qkv layer of a `models.Attention` into the chain
 (engine.qkv_attn_quant_forward / p4v_qkv_attn_quant_forward): qkv's GEMM writes the int8 operand planes of
@@ -277,6 +278,7 @@ def fuse_qkv_attention(net, one_kernel=False):
 
 # ---- window attention (Swin): matmul1 -> + bias -> + mask -> softmax -> matmul2 (engine.window_attn_quant_forward) ----
 _ORIG_WATTN = "_p4v_unfused_wattn_forward"
+_WONE_KERNEL = "_p4v_wattn_one_kernel"    # the patched container's choice: the window core as one kernel
 
 
 def window_attention_fusable(m):
@@ -316,15 +318,23 @@ def _fused_window_attention_forward(self, x, mask=None):
     n = self.window_size[0] * self.window_size[1]
     bias = self.relative_position_bias_table[self.relative_position_index.view(-1)].view(n, n, -1)
     out = engine.window_attn_quant_forward(q=q, kT=k.transpose(-2, -1), v=v, bias=bias.permute(2, 0, 1).contiguous(), mask=mask,
-                                           qk=args[0], pv=args[1])
+                                           qk=args[0], pv=args[1], one_kernel=self.__dict__.get(_WONE_KERNEL, False))
     return self.proj_drop(self.proj(out.transpose(1, 2).reshape(B_, N, C)))
 
 
-def fuse_window_attention(net):
-    """Patch the forward of every fusable WindowAttention container of `net`; returns their names.  Idempotent."""
-    return _patch(net, window_attention_fusable, _ORIG_WATTN, _fused_window_attention_forward)
+def fuse_window_attention(net, one_kernel=False):
+    """Patch the forward of every fusable WindowAttention container of `net`; returns their names.  Idempotent.  `one_kernel`:
+    the patched containers ask the engine for the one-kernel window core (stored on them; the later call decides).  It changes
+    neither when the fused path is taken nor what it returns."""
+    names = _patch(net, window_attention_fusable, _ORIG_WATTN, _fused_window_attention_forward)
+    for name, m in net.named_modules():
+        if name in names:
+            m.__dict__[_WONE_KERNEL] = bool(one_kernel)
+    return names
 
 
 def unfuse_window_attention(net):
     """Undo fuse_window_attention: every patched container gets its original forward back; returns their names.  Idempotent."""
+    for m in net.modules():
+        m.__dict__.pop(_WONE_KERNEL, None)
     return _unfuse(net, _ORIG_WATTN)

@@ -15,7 +15,9 @@ attention, without it attention alone.
 --fused-qkv: a fourth variant in the same alternation: fuse_qkv_attention in place of fuse_attention (k_qkv_heads in place of the
 qkv sweep, the permute copy and the three k_pack1 of q, k^T and v), on top of the fused MLPs with --fused.
 --one-kernel: a fifth variant in the same alternation: fuse_qkv_attention(one_kernel=True) (k_attn_qkpv in place of k_attn_qk and
-matmul2's sweep), on top of the fused MLPs with --fused; compared with fused_qkv.
+matmul2's sweep), on top of the fused MLPs with --fused; compared with fused_qkv.  On a Swin net the same variant is
+fuse_window_attention(one_kernel=True) (k_wattn_qkpv in place of the window instances of k_attn_qk and matmul2's sweep), compared
+with fused_attn: --fused --fused-attn --one-kernel alternates MLPs + windows as two kernels with MLPs + windows as one.
 """
 import argparse
 import hashlib
@@ -101,7 +103,7 @@ def main():
     ap.add_argument("--fused-qkv", action="store_true",
                     help="also time the network with the qkv layer fused into the attention chain (utils/fuse.py::fuse_qkv_attention; with --fused: on top of the fused MLPs)")
     ap.add_argument("--one-kernel", action="store_true",
-                    help="also time fuse_qkv_attention(one_kernel=True): the attention core as one kernel (with --fused: on top of the fused MLPs)")
+                    help="also time fuse_qkv_attention / fuse_window_attention(one_kernel=True): the attention core as one kernel (with --fused: on top of the fused MLPs)")
     ap.add_argument("--json", default=None, help="write the result to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -158,7 +160,8 @@ def main():
             fuse_attn = fuse.fuse_attention
             if attn in ("qkv", "qkv1"):
                 fuse_attn = lambda n: fuse.fuse_qkv_attention(n, one_kernel=attn == "qkv1")
-            return (len(fuse.fuse_mlp(net)) if mlp else 0, len(fuse_attn(net)) + len(fuse.fuse_window_attention(net)) if attn else 0)
+            return (len(fuse.fuse_mlp(net)) if mlp else 0,
+                    len(fuse_attn(net)) + len(fuse.fuse_window_attention(net, one_kernel=attn == "qkv1")) if attn else 0)
 
         ts = {key: [] for key, _, _ in variants}
         ys, counts = {}, {}
@@ -179,7 +182,7 @@ def main():
                       f"fused vs fp32 x{t_raw / t_v:.2f}; logit rel diff fused vs unfused {rel:.3e}")
                 res["fused_mlps"] = n_mlp
             elif key == "fused_qkv_one":
-                base_key = "fused_qkv" if a.fused_qkv else "fused" if a.fused else "unfused"
+                base_key = "fused_qkv" if a.fused_qkv else "fused_attn" if a.fused_attn else "fused" if a.fused else "unfused"
                 print(f"  one-kernel attention core ({n_attn}{' + MLPs' if a.fused else ''}) {t_v * 1e3:.2f} ms: x{med[base_key] / t_v:.3f} "
                       f"over {base_key} ({(med[base_key] - t_v) * 1e3:+.3f} ms), x{t_u / t_v:.3f} over unfused; logit rel diff vs unfused {rel:.3e}")
                 res.update({base_key + "_over_fused_qkv_one": med[base_key] / t_v, base_key + "_minus_fused_qkv_one_ms": (med[base_key] - t_v) * 1e3})

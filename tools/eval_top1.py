@@ -90,7 +90,7 @@ def evaluate(model, imagenet, weights=None, config="PTQ4ViT", bits=8, calib=32, 
     fused_attn = []
     if fuse_attn:                              # opt-in: matmul1 ... matmul2 of every attention block as the fused int8 chain
         from ptq4vit_amd.utils.fuse import fuse_attention as _fuse_attn, fuse_window_attention as _fuse_wattn
-        fused_attn = _fuse_attn(net, one_kernel=one_kernel) + _fuse_wattn(net)        # (a net has Attention or WindowAttention blocks)
+        fused_attn = _fuse_attn(net, one_kernel=one_kernel) + _fuse_wattn(net, one_kernel=one_kernel)        # (a net has Attention or WindowAttention blocks)
     if fuse_qkv:                               # opt-in: qkv ... matmul2 of every ViT / DeiT attention block as one fused int8 chain
         from ptq4vit_amd.utils.fuse import fuse_qkv_attention as _fuse_qkv
         fused_attn = _fuse_qkv(net, one_kernel=one_kernel) or fused_attn
@@ -122,7 +122,7 @@ def main(argv=None):
     ap.add_argument("--fuse-mlp", action="store_true", help="evaluate with the fused int8 MLP forward (utils/fuse.py::fuse_mlp)")
     ap.add_argument("--fuse-attn", action="store_true", help="evaluate with the fused int8 attention forward (utils/fuse.py::fuse_attention, fuse_window_attention)")
     ap.add_argument("--fuse-qkv", action="store_true", help="evaluate with the qkv layer fused into the attention chain (utils/fuse.py::fuse_qkv_attention)")
-    ap.add_argument("--one-kernel", action="store_true", help="with --fuse-attn / --fuse-qkv: the attention core as one kernel (k_attn_qkpv; window attention keeps two)")
+    ap.add_argument("--one-kernel", action="store_true", help="with --fuse-attn / --fuse-qkv: the attention core as one kernel (k_attn_qkpv; window attention: k_wattn_qkpv)")
     a = ap.parse_args(argv)
     import ptq4vit_amd
     ptq4vit_amd.configure_runtime()          # GPU_MAX_HW_QUEUES for the search streams, before the first GPU call
