@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define P4V_VERSION 147 /* 0.1.4.7: + P4V_WATTN_ONE_KERNEL (the fused window attention core as one kernel: a window's score rows held in registers) */
+#define P4V_VERSION 148 /* 0.1.4.8: + the fused LayerNorm producer: p4v_ln_linear_quant_forward, p4v_ln_mlp_quant_forward, LayerNorm writes the Linear's int8 row plane */
 /* 0.1.4.6: + P4V_ATTN_ONE_KERNEL (the fused attention core as one kernel: p v from the probabilities in registers) */
 /* 0.1.4.5: + p4v_qkv_attn_* (the fused int8 qkv forward: the qkv GEMM writes the attention operand planes) */
 
@@ -606,6 +606,66 @@ size_t p4v_qkv_attn_workspace_bytes(const p4v_qkv_attn_desc* desc);
 
 int p4v_qkv_attn_quant_forward(const p4v_qkv_attn_desc* desc, const p4v_qkv_attn_tensors* tensors, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Fused LayerNorm producer (opt-in, network level): Linear(LayerNorm(x)) and fc2(GELU(fc1(LayerNorm(x)))) with the LayerNorm
+ * output never written in fp32.  One kernel (k_ln_pack) reads a row of x once, normalises it in registers -- fp32, two passes:
+ * mean, then the centred squares; rstd = 1 / sqrt(var + eps) in IEEE arithmetic; y = ((x - mean) * rstd) * gamma + beta without
+ * contraction -- quantises y with the Linear's activation quantiser and writes the int8 row plane the Linear's GEMM reads.  The
+ * plane equals, byte for byte, what the unfused chain packs from the y this call computes; `out` equals
+ * p4v_linear_quant_forward / p4v_mlp_quant_forward on that y bit for bit.  Against torch's LayerNorm y differs by the order of the
+ * two row sums (measured: profiles/r35_fused_norm_margins.json).
+ * `map` 1 gathers the rows as SwinBlock.forward does between norm1 and qkv -- roll(-shift) over (H, W), then window_partition:
+ * destination row ((b H/ws + wh) W/ws + ww) ws^2 + i ws + j reads token (b, (wh ws + i + shift) mod H, (ww ws + j + shift) mod W);
+ * `out` (and y_out) are in destination-row order.
+ * Envelope: the Linear (fc1) with int8 planes, n_H = n_a = 1, not twin_postgelu; ln.C = in_features, ln.rows = batch * tokens,
+ * C % 4 == 0, C <= 2048; x, gamma, beta (and y_out) 16-byte aligned, x contiguous; map 1: H % ws == W % ws == 0, 0 <= shift < ws,
+ * rows % (H W) == 0; for the MLP call the envelope of p4v_mlp_quant_forward.  Anything else is P4V_ERR_UNSUPPORTED /
+ * P4V_ERR_INVALID before the first launch.
+ * x [rows][C]; gamma, beta [C]; the Linear's tensors as for p4v_linear_quant_forward (p4v_mlp_quant_forward); y_out: optional (may
+ * be NULL) [rows][C] fp32, the values the plane was quantised from; hidden (MLP): optional, as d_hidden there; ws, ws_bytes: the
+ * workspace and its size -- the workspace contract above holds with p4v_ln_linear_workspace_bytes / p4v_ln_mlp_workspace_bytes; a
+ * smaller ws_bytes is refused before any launch.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct p4v_ln_desc {
+    int64_t rows;
+    int32_t C;
+    float eps;
+    int32_t map;                       /* 0 identity, 1 window */
+    int32_t H, W, ws, shift;           /* map 1 only */
+    int32_t reserved;
+} p4v_ln_desc;
+
+typedef struct p4v_ln_linear_tensors {
+    const float *x, *gamma, *beta;
+    const float* w;
+    const float* bias;                 /* NULL without a bias (has_bias = 0) */
+    const float *w_interval, *a_interval;
+    float* out;
+    float* y_out;                      /* optional */
+    void* ws;
+    size_t ws_bytes;
+} p4v_ln_linear_tensors;
+
+typedef struct p4v_ln_mlp_tensors {
+    const float *x, *gamma, *beta;
+    const float *w1, *w2;
+    const float *bias1, *bias2;        /* NULL without a bias */
+    const float *w1_interval, *a1_interval, *w2_interval, *a2_interval;
+    float* out;
+    float* y_out;                      /* optional */
+    float* hidden;                     /* optional */
+    void* ws;
+    size_t ws_bytes;
+} p4v_ln_mlp_tensors;
+
+size_t p4v_ln_linear_workspace_bytes(const p4v_ln_desc* ln, const p4v_linear_desc* desc);
+
+int p4v_ln_linear_quant_forward(const p4v_ln_desc* ln, const p4v_linear_desc* desc, const p4v_ln_linear_tensors* tensors, void* stream);
+
+size_t p4v_ln_mlp_workspace_bytes(const p4v_ln_desc* ln, const p4v_mlp_desc* desc);
+
+int p4v_ln_mlp_quant_forward(const p4v_ln_desc* ln, const p4v_mlp_desc* desc, const p4v_ln_mlp_tensors* tensors, void* stream);
+
 /* d_A_interval: [heads] (sos: [1]); d_B_interval: [heads]; d_split: [1] (sos only); d_out: [batch*heads][M][N] */
 int p4v_matmul_quant_forward(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_A_interval,
                              const float* d_B_interval, const float* d_split, float* d_out, void* d_workspace,
@@ -652,7 +712,8 @@ typedef struct p4v_launch_record {
     int32_t kind;     /* 2 k_sweep6 | 3 k_sweep7 | 4 k_sweep7 twin | 5 k_sweep5 | 6 k_sweep9 | 7 k_sweep8 | 8 k_sweep2g | 9 k_sweep2 |
                          0 generic int8 k_sweep | 1 generic fp32 k_sweep | 11 k_sos_split (fp32) | 12 k_bound (stage B1) |
                          13 k_slice_b2 / 14 k_slice_a (stage A of a MatMul B / A search) | 15 k_sweep_seg | 16 k_mlp_fc1 |
-                         17 k_attn_qk */
+                         17 k_attn_qk | 18 k_qkv_heads | 19 k_attn_qkpv | 20 k_wattn_qkpv | 21 k_ln_pack (no MACs: alg_bytes = x + gamma +
+                         beta + the int8 plane + y_out where given) */
     int32_t stage;    /* 0 full sweep (pass not pruned) | 1 stage A (all candidates, sample slice) | 2 stage B1 (the bound) |
                          3 stage B2 (survivors, all samples) | 4 stage A2 (survivors of a loose first slice on the larger second one) */
     int32_t grid_x, grid_z;   /* a grouped launch (p4v_calibrate_group): grid_x = its flat grid (all members' blocks, each member padded to a

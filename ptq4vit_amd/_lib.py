@@ -64,6 +64,24 @@ class QkvAttnTensors(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in POINTERS] + [("ws_bytes", C.c_size_t)]
 
 
+class LnDesc(C.Structure):
+    """p4v_ln_desc: the LayerNorm in front of a Linear layer and the row map between them (0 identity, 1 Swin's shifted windows)."""
+    _fields_ = [("rows", C.c_int64), ("C", C.c_int32), ("eps", C.c_float)] + [(n, C.c_int32) for n in ("map", "H", "W", "ws", "shift", "reserved")]
+
+
+class LnLinearTensors(C.Structure):
+    """p4v_ln_linear_tensors: the device pointers of a p4v_ln_linear_quant_forward call, its workspace and the workspace's size."""
+    POINTERS = ("x", "gamma", "beta", "w", "bias", "w_interval", "a_interval", "out", "y_out", "ws")
+    _fields_ = [(n, C.c_void_p) for n in POINTERS] + [("ws_bytes", C.c_size_t)]
+
+
+class LnMlpTensors(C.Structure):
+    """p4v_ln_mlp_tensors: the device pointers of a p4v_ln_mlp_quant_forward call, its workspace and the workspace's size."""
+    POINTERS = ("x", "gamma", "beta", "w1", "w2", "bias1", "bias2", "w1_interval", "a1_interval", "w2_interval", "a2_interval", "out", "y_out",
+                "hidden", "ws")
+    _fields_ = [(n, C.c_void_p) for n in POINTERS] + [("ws_bytes", C.c_size_t)]
+
+
 class MatMulBlocksDesc(C.Structure):
     """p4v_matmul_blocks_desc: the MatMul descriptor plus the row / column block counts of both operands."""
     _fields_ = [("mm", MatMulDesc)] + [(n, C.c_int32) for n in ("n_V_A", "n_H_A", "n_V_B", "n_H_B")]
@@ -93,7 +111,7 @@ class LaunchRecord(C.Structure):
 
 LAUNCH_KINDS = {0: "k_sweep<int8>", 1: "k_sweep<float>", 2: "k_sweep6", 3: "k_sweep7", 4: "k_sweep7 (twin)", 5: "k_sweep4/5", 6: "k_sweep9",
                 7: "k_sweep8", 8: "k_sweep2g", 9: "k_sweep2", 11: "k_sos_split", 12: "k_bound", 13: "k_slice_b", 14: "k_slice_a", 15: "k_sweep_seg", 16: "k_mlp_fc1",
-                17: "k_attn_qk", 18: "k_qkv_heads", 19: "k_attn_qkpv", 20: "k_wattn_qkpv"}
+                17: "k_attn_qk", 18: "k_qkv_heads", 19: "k_attn_qkpv", 20: "k_wattn_qkpv", 21: "k_ln_pack"}
 LAUNCH_STAGES = {0: "full", 1: "A", 2: "B1", 3: "B2", 4: "A2"}
 
 
@@ -146,6 +164,7 @@ EXPORTS = [
     "p4v_linear_quant_forward", "p4v_matmul_quant_forward", "p4v_mlp_workspace_bytes", "p4v_mlp_quant_forward",
     "p4v_attn_workspace_bytes", "p4v_attn_quant_forward", "p4v_wattn_workspace_bytes", "p4v_wattn_quant_forward",
     "p4v_qkv_attn_workspace_bytes", "p4v_qkv_attn_quant_forward",
+    "p4v_ln_linear_workspace_bytes", "p4v_ln_linear_quant_forward", "p4v_ln_mlp_workspace_bytes", "p4v_ln_mlp_quant_forward",
     "p4v_amax_init_linear", "p4v_linear_search_w", "p4v_linear_search_a",
     "p4v_amax_init_matmul", "p4v_matmul_search_A", "p4v_sos_search_split", "p4v_matmul_search_B",
     "p4v_amax_init_conv", "p4v_conv_search_w_channelwise", "p4v_conv_search_w_layerwise", "p4v_conv_search_a",
@@ -155,6 +174,7 @@ EXPORTS = [
     "p4v_debug_set_variant", "p4v_debug_set_tuning", "p4v_debug_bound_totals", "p4v_debug_topk_rows", "p4v_debug_pack_dual", "p4v_debug_prep_epi6",
     "p4v_debug_pack_cands", "p4v_debug_gather_im2col", "p4v_debug_sos_sweep",
     "p4v_debug_set_arena_gap", "p4v_debug_arena_ranges", "p4v_debug_mlp_planes", "p4v_debug_attn_planes", "p4v_debug_qkv_planes",
+    "p4v_debug_ln_planes",
     "p4v_debug_prune_tables", "p4v_debug_prune_decide",
 ]
 
@@ -225,6 +245,16 @@ def load():
     lib.p4v_qkv_attn_quant_forward.argtypes = [C.POINTER(QkvAttnDesc), C.POINTER(QkvAttnTensors), vp]
     lib.p4v_debug_qkv_planes.restype = C.c_int
     lib.p4v_debug_qkv_planes.argtypes = [C.POINTER(C.c_uint64)]
+    lib.p4v_ln_linear_workspace_bytes.restype = C.c_size_t
+    lib.p4v_ln_linear_workspace_bytes.argtypes = [C.POINTER(LnDesc), C.POINTER(LinearDesc)]
+    lib.p4v_ln_linear_quant_forward.restype = C.c_int
+    lib.p4v_ln_linear_quant_forward.argtypes = [C.POINTER(LnDesc), C.POINTER(LinearDesc), C.POINTER(LnLinearTensors), vp]
+    lib.p4v_ln_mlp_workspace_bytes.restype = C.c_size_t
+    lib.p4v_ln_mlp_workspace_bytes.argtypes = [C.POINTER(LnDesc), C.POINTER(MlpDesc)]
+    lib.p4v_ln_mlp_quant_forward.restype = C.c_int
+    lib.p4v_ln_mlp_quant_forward.argtypes = [C.POINTER(LnDesc), C.POINTER(MlpDesc), C.POINTER(LnMlpTensors), vp]
+    lib.p4v_debug_ln_planes.restype = C.c_int
+    lib.p4v_debug_ln_planes.argtypes = [C.POINTER(C.c_uint64)]
     lib.p4v_matmul_quant_forward.restype = C.c_int
     lib.p4v_matmul_quant_forward.argtypes = [C.POINTER(MatMulDesc), fp, fp, fp, fp, fp, fp, vp, C.c_size_t, vp]
     # granular entry points: (desc, tensors..., workspace, bytes, stream)

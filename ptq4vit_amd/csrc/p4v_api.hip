@@ -3157,11 +3157,64 @@ thread_local FusedPlanes g_mlp_planes, g_attn_planes;
 struct QkvPlanes { size_t off_q = 0, off_k = 0, off_v = 0; long Z = 0, rows_q = 0, rows_k = 0, ld_qk = 0, rows_v = 0, ld_v = 0; };
 thread_local QkvPlanes g_qkv_planes;
 constexpr int MLP_RECORD_KIND = 16, ATTN_RECORD_KIND = 17, QKV_RECORD_KIND = 18, ATTN_PV_RECORD_KIND = 19, WATTN_PV_RECORD_KIND = 20;
+constexpr int LN_RECORD_KIND = 21;
+
+// ---- the LayerNorm producer: k_ln_pack writes a Linear layer's int8 row plane from LayerNorm's INPUT -------------
+thread_local FusedPlanes g_ln_planes;                          // where the last call's plane lies (p4v_debug_ln_planes)
+struct LnTensors { const float *x = nullptr, *gamma = nullptr, *beta = nullptr; float* y_out = nullptr; };
+struct LnStep { const p4v_ln_desc* d; LnTensors t; };
+// the envelope of the producer in front of the Linear layer `d`, before anything is planned or launched
+int ln_check(const p4v_ln_desc* n, const p4v_linear_desc* d, const LnTensors& t, const Ctx& c, const char* who) {
+    const long M = (long)d->batch * d->tokens;
+    if (n->rows <= 0 || n->C <= 0 || n->rows != M || n->C != d->in_features)
+        return fail(P4V_ERR_INVALID, "%s: LayerNorm's rows [%ld][%d] are not the Linear's input [%ld][%d]", who, (long)n->rows, n->C, M, d->in_features);
+    if (n->C % 4 || n->C > 2048) return fail(P4V_ERR_UNSUPPORTED, "%s: LayerNorm over %d columns (a multiple of 4 up to 2048 is implemented)", who, n->C);
+    if (n->map != 0 && n->map != 1) return fail(P4V_ERR_INVALID, "%s: unknown row map %d", who, n->map);
+    if (n->map == 1 && (n->H <= 0 || n->W <= 0 || n->ws <= 0 || n->H % n->ws || n->W % n->ws || n->shift < 0 || n->shift >= n->ws ||
+                        n->rows % ((long)n->H * n->W)))
+        return fail(P4V_ERR_INVALID, "%s: window map (H %d, W %d, ws %d, shift %d) over %ld rows: ws must divide H and W, 0 <= shift < ws, H * W the rows",
+                    who, n->H, n->W, n->ws, n->shift, (long)n->rows);
+    if (d->n_H != 1 || d->n_a != 1) return fail(P4V_ERR_UNSUPPORTED, "%s: the fused LayerNorm takes n_H = n_a = 1 on the Linear layer", who);
+    if (d->twin_postgelu) return fail(P4V_ERR_UNSUPPORTED, "%s: the Linear layer reads no GELU output (twin_postgelu)", who);
+    if (d->reserved & RSV_FP32_PLANES) return fail(P4V_ERR_UNSUPPORTED, "%s: int8 planes only (desc.reserved bit 0 is set)", who);
+    if (!c.dry && (((unsigned long long)t.x | (unsigned long long)t.gamma | (unsigned long long)t.beta | (unsigned long long)t.y_out) & 15))
+        return fail(P4V_ERR_INVALID, "%s: x, gamma, beta and y_out must be aligned to 16 bytes", who);
+    return 0;
+}
+// k_ln_pack on a call that passed ln_check: `plane` [Mp][Kp] is the Linear's row plane, `a_iv` / `aq` its activation interval and grid
+int launch_ln_pack(Ctx& c, const LnStep& ln, const float* a_iv, int aq, char* plane, int Mp, int Kp) {
+    if (c.dry) return 0;
+    if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", c.ws.off);
+    const p4v_ln_desc& n = *ln.d;
+    const int lpr = n.C <= 128 ? 32 : 64, nv = n.C <= 256 ? 1 : n.C <= 512 ? 2 : n.C <= 1024 ? 4 : 8;
+    const int rows_wg = 4 * (64 / lpr);
+    if (Mp % rows_wg || Kp < n.C || Kp > 4 * lpr * nv) return fail(P4V_ERR_UNSUPPORTED, "ln: the consumer's row plane [%d][%d] is not k_ln_pack's", Mp, Kp);
+    LnPackParams q{};
+    q.x = ln.t.x; q.gamma = ln.t.gamma; q.beta = ln.t.beta; q.scale = a_iv; q.plane = (int8_t*)plane; q.y_out = ln.t.y_out;
+    q.M = n.rows; q.Mp = Mp; q.C = n.C; q.Kp = Kp; q.eps = n.eps; q.lo = -aq; q.hi = aq - 1;
+    q.qbias = (aq == 128 && tune(TUNE_B1_PATH) != 11) ? cvt_bias(c) : 0.0f;      // (launch_pack's rule)
+    q.map = n.map; q.H = n.H; q.W = n.W; q.ws = n.ws; q.shift = n.shift;
+    q.nwg = Mp / rows_wg;
+    g_alg_macs_cand = 0.0;
+    g_alg_bytes = 4.0 * (double)n.rows * n.C * (ln.t.y_out ? 2 : 1) + 8.0 * n.C + (double)Mp * Kp;
+    g_exec_frac = 1.0;
+    const StatInfo si = stat_info(LN_RECORD_KIND, 0.0, 0.0, q.nwg, 1, g_alg_bytes);
+    const dim3 grid(q.nwg), block(256);
+    g_ln_planes = FusedPlanes{(size_t)(plane - c.ws.base), 0, Mp, Kp, 0};
+    if (lpr == 32) return enqueue(c, KERN1_T(LnPackParams, k_ln_pack, 1, 32), grid, block, 0, q, &si);
+    switch (nv) {
+        case 1: return enqueue(c, KERN1_T(LnPackParams, k_ln_pack, 1, 64), grid, block, 0, q, &si);
+        case 2: return enqueue(c, KERN1_T(LnPackParams, k_ln_pack, 2, 64), grid, block, 0, q, &si);
+        case 4: return enqueue(c, KERN1_T(LnPackParams, k_ln_pack, 4, 64), grid, block, 0, q, &si);
+        default: return enqueue(c, KERN1_T(LnPackParams, k_ln_pack, 8, 64), grid, block, 0, q, &si);
+    }
+}
 
 // One producer -> consumer chain, in the order its caller walks it: plan_consumer, produce, consume.
 struct FusedChain {
     struct Packed { char *rows, *cols; float* S1; int Kp, Np; };    // the producer's operand planes [Z][Mp | Np][Kp] and its scale table
-    struct PrePlanes { char *rows, *cols, *col2; };                 // planes an earlier launch wrote: the producer's two, the consumer's column plane
+    struct PrePlanes { char *rows, *cols, *col2; bool rows_only; }; // planes an earlier launch wrote: the producer's two, the consumer's column plane
+                                                                    // (rows_only, ln_mlp_impl: the producer's row plane alone -- its column plane is packed here)
     static int producer_kp(int K1) { return (int)rup(K1, 64); }
     static int producer_np(int ncols) { return (int)rup(ncols, SW_BN); }
     // Both operands of a forward pass `fp1` (reduction length K1, `ncols` columns, `nscale` scale entries; rows padded to Mp_) and
@@ -3171,16 +3224,16 @@ struct FusedChain {
         pk.Kp = producer_kp(K1); pk.Np = producer_np(ncols);
         SweepPlan pl1{};                                            // what pack_operand reads of a plan: the plane geometry
         pl1.esz = 1; pl1.Mp = Mp_; pl1.Np = pl1.NpB = pk.Np; pl1.Kp = pk.Kp; pl1.cin_fix = 0;
+        const bool pre_cols = pre && !pre->rows_only;
         pk.rows = pre ? pre->rows : c.ws.get<char>((size_t)Z_ * Mp_ * pk.Kp);
-        pk.cols = pre ? pre->cols : c.ws.get<char>((size_t)Z_ * pk.Np * pk.Kp);
+        pk.cols = pre_cols ? pre->cols : c.ws.get<char>((size_t)Z_ * pk.Np * pk.Kp);
         pk.S1 = c.ws.get<float>((size_t)nscale);
         if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", c.ws.off);
         fp1.s1.S = pk.S1; fp1.s1.C = 1; fp1.s1.nblk = fp1.s_cs;
         CHK(launch_scale(c, fp1.s1));
-        if (pre) return 0;
         const PassBufs nb{};
-        CHK(pack_operand(c, fp1, pl1, nb, fp1.row, pk.rows, false, 0, 1));
-        CHK(pack_operand(c, fp1, pl1, nb, fp1.col, pk.cols, true, 0, 1));
+        if (!pre) CHK(pack_operand(c, fp1, pl1, nb, fp1.row, pk.rows, false, 0, 1));
+        if (!pre_cols) CHK(pack_operand(c, fp1, pl1, nb, fp1.col, pk.cols, true, 0, 1));
         return 0;
     }
     Ctx& c;
@@ -3252,7 +3305,8 @@ template <class D, class T> int fused_call(int (*impl)(const D*, const T&, const
 // and k_pack_dual / k_pack1 of it are gone.
 // `t1`, `t2`: the two layers' records as p4v_linear_quant_forward fills them -- t1.fwd_out is the optional fp32 copy of the hidden
 // tensor (fc1 stores no other output), t2.X stays null (fc2 reads fc1's planes).
-int mlp_impl(const p4v_mlp_desc* d, const LinearTensors& t1, const LinearTensors& t2, Ctx& c) {
+// `ln` (ln_mlp_impl): x is LayerNorm's input -- k_ln_pack writes fc1's row plane, which pack_pair then takes as it is.
+int mlp_chain(const p4v_mlp_desc* d, const LinearTensors& t1, const LinearTensors& t2, Ctx& c, const LnStep* ln) {
     const p4v_linear_desc* d1 = &d->fc1;
     const p4v_linear_desc* d2 = &d->fc2;
     // the envelope, before anything is planned or launched
@@ -3271,6 +3325,12 @@ int mlp_impl(const p4v_mlp_desc* d, const LinearTensors& t1, const LinearTensors
     FusedChain ch{c, "mlp", "fc2"};
     CHK(ch.plan_consumer(L2.forward_pass(), 1, L2.twin));      // Kp = roundup64(hidden)
     const int M = L1.M, K1 = L1.K, Hd = L1.N;
+    FusedChain::PrePlanes pre{};
+    if (ln) {                                                   // fc1's row plane, behind fc2's: it outlives the call (p4v_debug_ln_planes)
+        pre.rows_only = true;
+        pre.rows = c.ws.get<char>((size_t)ch.Mp * FusedChain::producer_kp(K1));
+        CHK(launch_ln_pack(c, *ln, t1.a_iv, L1.aq, pre.rows, ch.Mp, FusedChain::producer_kp(K1)));
+    }
     CHK(ch.produce(L1.forward_pass(), K1, Hd, L1.nV, g_mlp_planes, [&](const FusedChain::Packed& pk) -> int {
         MlpFc1Params q{};
         q.A = pk.rows; q.B = pk.cols; q.ldk = pk.Kp; q.ktiles = pk.Kp / SW_BKB;
@@ -3287,8 +3347,35 @@ int mlp_impl(const p4v_mlp_desc* d, const LinearTensors& t1, const LinearTensors
         const size_t lds = 2 * 2 * SW_TILE_BYTES;
         return L2.twin ? enqueue(c, KERN1_T(MlpFc1Params, k_mlp_fc1, true), grid, block, lds, q, &si)
                        : enqueue(c, KERN1_T(MlpFc1Params, k_mlp_fc1, false), grid, block, lds, q, &si);
-    }));
+    }, ln ? &pre : nullptr));
     return ch.consume();
+}
+int mlp_impl(const p4v_mlp_desc* d, const LinearTensors& t1, const LinearTensors& t2, Ctx& c) { return mlp_chain(d, t1, t2, c, nullptr); }
+
+// ---- p4v_ln_linear_quant_forward / p4v_ln_mlp_quant_forward: LayerNorm in front of a Linear layer / of the MLP chain ----------------
+// The records of the two calls as fused_sizing_run / fused_call take them: the descriptors, and the tensors of both halves.
+struct LnLinearCall { p4v_ln_desc ln; p4v_linear_desc lin; };
+struct LnLinearTensors { LnTensors n; LinearTensors l; };
+struct LnMlpCall { p4v_ln_desc ln; p4v_mlp_desc mlp; };
+struct LnMlpTensors { LnTensors n; LinearTensors l1, l2; };
+
+// Linear(LayerNorm(x)): the Linear is the chain's consumer -- its own forward pass with the row operand prepacked.
+int ln_linear_impl(const LnLinearCall* d, const LnLinearTensors& t, const LnLinearTensors&, Ctx& c) {
+    CHK(ln_check(&d->ln, &d->lin, t.n, c, "ln_linear"));
+    const Stage sg{ST_FWD};
+    LinearCall L(c, &d->lin, t.l, sg);
+    CHK(L.build());
+    if (!L.i8 || L.twin) return fail(P4V_ERR_UNSUPPORTED, "ln_linear: int8 planes only");
+    FusedChain ch{c, "ln_linear", "the Linear"};
+    CHK(ch.plan_consumer(L.forward_pass(), 1, false));         // P1: [Mp][roundup64(C)]
+    if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", c.ws.off);
+    CHK(launch_ln_pack(c, LnStep{&d->ln, t.n}, t.l.a_iv, L.aq, ch.P1, ch.Mp, ch.Kp));
+    return ch.consume();
+}
+int ln_mlp_impl(const LnMlpCall* d, const LnMlpTensors& t, const LnMlpTensors&, Ctx& c) {
+    CHK(ln_check(&d->ln, &d->mlp.fc1, t.n, c, "ln_mlp"));
+    const LnStep ln{&d->ln, t.n};
+    return mlp_chain(&d->mlp, t.l1, t.l2, c, &ln);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4362,6 +4449,48 @@ int p4v_qkv_attn_quant_forward(const p4v_qkv_attn_desc* desc, const p4v_qkv_attn
     return fused_call(qkv_attn_impl, desc, rec, rec, t->ws, t->ws_bytes, stream);
 }
 
+size_t p4v_ln_linear_workspace_bytes(const p4v_ln_desc* ln, const p4v_linear_desc* desc) {
+    if (!ln || !desc) return 0;
+    const LnLinearCall d{*ln, *desc};
+    size_t need = 0;
+    return fused_sizing_run(ln_linear_impl, &d, &need) == 0 ? need : 0;
+}
+
+int p4v_ln_linear_quant_forward(const p4v_ln_desc* ln, const p4v_linear_desc* desc, const p4v_ln_linear_tensors* t, void* stream) {
+    if (!ln || !desc || !t || !t->x || !t->gamma || !t->beta || !t->w || !t->w_interval || !t->a_interval || !t->out || !t->ws)
+        return fail(P4V_ERR_INVALID, "p4v_ln_linear_quant_forward: null pointer");
+    if (desc->has_bias && !t->bias) return fail(P4V_ERR_INVALID, "p4v_ln_linear_quant_forward: has_bias set but the bias is null");
+    CHK(ws_aligned(t->ws));
+    const LnLinearCall d{*ln, *desc};
+    const LnLinearTensors rec{{t->x, t->gamma, t->beta, t->y_out},
+                              {.W = t->w, .bias = desc->has_bias ? t->bias : nullptr, .w_iv = const_cast<float*>(t->w_interval),
+                               .a_iv = const_cast<float*>(t->a_interval), .fwd_out = t->out}};
+    return fused_call(ln_linear_impl, &d, rec, rec, t->ws, t->ws_bytes, stream);
+}
+
+size_t p4v_ln_mlp_workspace_bytes(const p4v_ln_desc* ln, const p4v_mlp_desc* desc) {
+    if (!ln || !desc) return 0;
+    const LnMlpCall d{*ln, *desc};
+    size_t need = 0;
+    return fused_sizing_run(ln_mlp_impl, &d, &need) == 0 ? need : 0;
+}
+
+int p4v_ln_mlp_quant_forward(const p4v_ln_desc* ln, const p4v_mlp_desc* desc, const p4v_ln_mlp_tensors* t, void* stream) {
+    if (!ln || !desc || !t || !t->x || !t->gamma || !t->beta || !t->w1 || !t->w2 || !t->w1_interval || !t->a1_interval || !t->w2_interval ||
+        !t->a2_interval || !t->out || !t->ws)
+        return fail(P4V_ERR_INVALID, "p4v_ln_mlp_quant_forward: null pointer");
+    if ((desc->fc1.has_bias && !t->bias1) || (desc->fc2.has_bias && !t->bias2))
+        return fail(P4V_ERR_INVALID, "p4v_ln_mlp_quant_forward: has_bias set but the bias is null");
+    CHK(ws_aligned(t->ws));
+    const LnMlpCall d{*ln, *desc};
+    const LnMlpTensors rec{{t->x, t->gamma, t->beta, t->y_out},
+                           {.W = t->w1, .bias = desc->fc1.has_bias ? t->bias1 : nullptr, .w_iv = const_cast<float*>(t->w1_interval),
+                            .a_iv = const_cast<float*>(t->a1_interval), .fwd_out = t->hidden},
+                           {.W = t->w2, .bias = desc->fc2.has_bias ? t->bias2 : nullptr, .w_iv = const_cast<float*>(t->w2_interval),
+                            .a_iv = const_cast<float*>(t->a2_interval), .fwd_out = t->out}};
+    return fused_call(ln_mlp_impl, &d, rec, rec, t->ws, t->ws_bytes, stream);
+}
+
 int p4v_matmul_quant_forward(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_A_interval,
                              const float* d_B_interval, const float* d_split, float* d_out, void* d_workspace,
                              size_t workspace_bytes, void* stream) {
@@ -4816,6 +4945,7 @@ static int planes_out(const FusedPlanes& m, uint64_t* out, const char* who, cons
 }
 int p4v_debug_mlp_planes(uint64_t* out) { return planes_out(g_mlp_planes, out, "p4v_debug_mlp_planes", "p4v_mlp_quant_forward"); }
 int p4v_debug_attn_planes(uint64_t* out) { return planes_out(g_attn_planes, out, "p4v_debug_attn_planes", "p4v_attn_quant_forward / p4v_wattn_quant_forward"); }
+int p4v_debug_ln_planes(uint64_t* out) { return planes_out(g_ln_planes, out, "p4v_debug_ln_planes", "p4v_ln_linear_quant_forward / p4v_ln_mlp_quant_forward"); }
 int p4v_debug_qkv_planes(uint64_t* out) {
     const QkvPlanes& m = g_qkv_planes;
     if (!out) return fail(P4V_ERR_INVALID, "p4v_debug_qkv_planes: null pointer");

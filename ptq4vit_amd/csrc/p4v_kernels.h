@@ -5886,4 +5886,131 @@ __global__ __launch_bounds__(256) void k_wattn_qkpv(WattnQkPvParams p) {
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// k_ln_pack: LayerNorm fused with a Linear layer's activation quantiser
+// ------------------------------------------------------------------------------------------
+// Writes the int8 row plane [Mp][Kp] (Kp = roundup64(C)) the Linear's forward GEMM reads, straight from the residual stream: the
+// fp32 LayerNorm output, the roll / window_partition copies of it and k_pack1's read of it are gone.  A destination row belongs to
+// a group of LPR lanes (32 for C <= 128: two rows per wave; else 64); lane l of the group loads NV aligned 16-byte pieces of its
+// SOURCE row, piece j = columns 4 (l + LPR j) .. + 3, all before the first arithmetic -- the row is read once and stays in 4 NV
+// registers.  No LDS, no barrier; 4 waves per workgroup.
+// Arithmetic, fp32 under contract(off), in this order: mean = tree(x) * (1 / C), var = tree((x - mean)^2) * (1 / C) on the
+// registers (two passes, not E[x^2] - mean^2), rstd = 1 / sqrt(var + eps) (IEEE), y = ((x - mean) * rstd) * gamma + beta.  tree():
+// the lane's own values in ascending column order, then an xor-butterfly over the group (every lane ends with the same sum).
+// Quantiser: the layer's one activation interval; the bytes are k_pack1's of the same y -- quant16_sat8 / quant16_any on four
+// pieces at a time (NV >= 4), pack_value (PACK_SYM: the IEEE division itself) on one piece at a time below that.
+// Stores: one dword of four bytes per piece (256 contiguous bytes per wave and piece); columns C .. Kp and rows M .. Mp are zeros.
+// Row map: the source row is computed from the destination row -- identity, or SwinBlock's roll(-shift) + window_partition:
+//   dst = ((b H/ws + wh) W/ws + ww) ws^2 + i ws + j   reads token (b, (wh ws + i + shift) mod H, (ww ws + j + shift) mod W).
+// y_out (optional, [M][C] in destination-row order) receives y.
+struct LnPackParams {
+    const float *x, *gamma, *beta;     // [M][C], [C], [C]; 16-byte aligned
+    const float* scale;                // the Linear's a_interval [1]
+    int8_t* plane;                     // [Mp][Kp]
+    float* y_out;                      // optional
+    long M, Mp;
+    int C, Kp;
+    float eps;
+    int lo, hi;                        // the clamp range of the activation grid
+    float qbias;                       // != 0: quant16_sat8 (full symmetric 8-bit grid, conversion probed)
+    int map, H, W, ws, shift;          // map 1: the window map
+    int nwg;
+};
+
+template <int LPR> __device__ __forceinline__ float ln_group_sum(float s) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int o = LPR / 2; o > 0; o >>= 1) s = s + __shfl_xor(s, o);
+    return s;
+}
+
+template <int NV, int LPR> __global__ __launch_bounds__(256) void k_ln_pack(LnPackParams p) {
+    constexpr int RPW = 64 / LPR;                             // rows per wave
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, l = lane & (LPR - 1);
+    const long dst = ((long)xcd_remap(blockIdx.x, p.nwg) * 4 + wid) * RPW + lane / LPR;      // < Mp: the grid is Mp / (4 RPW)
+    const bool live = dst < p.M;
+    long src = dst;
+    if (p.map == 1) {
+        const int per = p.ws * p.ws, nww = p.W / p.ws, nwh = p.H / p.ws;
+        const long win = dst / per;
+        const int r = (int)(dst - win * per), i = r / p.ws, j = r - i * p.ws;
+        const int ww = (int)(win % nww), wh = (int)((win / nww) % nwh);
+        const long b = win / ((long)nww * nwh);
+        int h = wh * p.ws + i + p.shift, w = ww * p.ws + j + p.shift;
+        h -= h >= p.H ? p.H : 0; w -= w >= p.W ? p.W : 0;
+        src = (b * p.H + h) * p.W + w;
+    }
+    const float* xrow = p.x + src * p.C;
+    v4f xv[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int c = 4 * (l + LPR * j);
+        xv[j] = (live && c < p.C) ? *reinterpret_cast<const v4f*>(xrow + c) : v4f{0.f, 0.f, 0.f, 0.f};
+    }
+    unsigned w[NV];
+    {
+#pragma clang fp contract(off)
+        const float inv_c = 1.0f / (float)p.C;
+        float s = 0.0f;
+#pragma unroll
+        for (int j = 0; j < NV; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s = s + xv[j][e];
+        const float mean = ln_group_sum<LPR>(s) * inv_c;
+        float s2 = 0.0f;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const bool in = 4 * (l + LPR * j) < p.C;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float d = xv[j][e] - mean;
+                xv[j][e] = d;
+                s2 = s2 + (in ? d * d : 0.0f);
+            }
+        }
+        const float var = ln_group_sum<LPR>(s2) * inv_c;
+        const float rstd = __fdiv_rn(1.0f, __fsqrt_rn(var + p.eps));
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c = 4 * (l + LPR * j);
+            if (c < p.C) {
+                const v4f g = *reinterpret_cast<const v4f*>(p.gamma + c), b = *reinterpret_cast<const v4f*>(p.beta + c);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) xv[j][e] = (xv[j][e] * rstd) * g[e] + b[e];
+                if (p.y_out && live) *reinterpret_cast<v4f*>(p.y_out + dst * p.C + c) = xv[j];
+            }
+        }
+    }
+    const float s = p.scale[0];
+    if constexpr (NV >= 4) {
+        const float rcp = 1.0f / s, flo = (float)p.lo, fhi = (float)p.hi;
+#pragma unroll
+        for (int q = 0; q < NV / 4; ++q) {
+            float x16[16];
+#pragma unroll
+            for (int e = 0; e < 16; ++e) x16[e] = xv[4 * q + e / 4][e % 4];
+            v4i o;
+            if (p.qbias != 0.0f) quant16_sat8(x16, s, rcp, p.qbias, o);
+            else quant16_any(x16, s, rcp, flo, fhi, false, o);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) w[4 * q + e] = (unsigned)o[e];
+        }
+    } else {
+        PackParams pv{};
+        pv.mode = PACK_SYM; pv.lo = p.lo; pv.hi = p.hi;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            w[j] = 0u;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) w[j] |= ((unsigned)(int)pack_value(pv, xv[j][e], s) & 0xffu) << (8 * e);
+        }
+    }
+    int8_t* prow = p.plane + dst * p.Kp;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int c = 4 * (l + LPR * j);
+        if (c < p.Kp) __builtin_nontemporal_store((live && c < p.C) ? w[j] : 0u, reinterpret_cast<unsigned*>(prow + c));
+    }
+}
+
 }  // namespace p4v

@@ -211,8 +211,20 @@ def linear_calibrate(**kw):
     return job.outputs[0], job.outputs[1], job.scores, job.best
 
 
-def linear_quant_forward(*, weight, bias, x, w_interval, a_interval, w_bit, a_bit, n_V, n_H, n_a, postgelu=False):
-    """quant_forward of a calibrated (post-GELU) Linear as one int8 MFMA GEMM (p4v_linear_quant_forward)."""
+def linear_quant_forward(*, weight, bias, x, w_interval, a_interval, w_bit, a_bit, n_V, n_H, n_a, postgelu=False, ln=None, window=None,
+                         want_norm=False, want_planes=False):
+    """quant_forward of a calibrated (post-GELU) Linear as one int8 MFMA GEMM (p4v_linear_quant_forward).
+    `ln` (a dict of weight, bias, eps): x is the INPUT of a LayerNorm in front of the layer, fused into the layer's activation
+    quantiser (p4v_ln_linear_quant_forward): k_ln_pack reads x once and writes the layer's int8 row plane; the
+    fp32 LayerNorm output is never written.  With it, `window` = (H, W, ws, shift) gathers the rows as SwinBlock.forward's
+    roll(-shift) + window_partition orders them (x [B][H * W][C]; out comes in that order), `want_norm` also returns y (the fp32
+    LayerNorm output the plane was quantised from, in out's row order) and `want_planes` the padded int8 plane (for the tests)."""
+    if ln is None and (window is not None or want_norm or want_planes):
+        raise ValueError("linear_quant_forward: window, want_norm and want_planes belong to the fused LayerNorm (ln=)")
+    if ln is not None:
+        layer = dict(weight=weight, bias=bias, w_interval=w_interval, a_interval=a_interval, w_bit=w_bit, a_bit=a_bit, n_V=n_V, n_H=n_H,
+                     n_a=n_a, postgelu=postgelu)
+        return _ln_linear_forward(x, ln, layer, window, want_norm, want_planes)
     lib = _lib.load()
     dev = device_of(x, weight)
     weight, bias, x = (to_dev(t, dev) for t in (weight, bias, x))
@@ -269,13 +281,20 @@ def _fused_forward(kind, d, tensors, dev, res, want_planes, z=None):
     return res[0] if len(res) == 1 else res
 
 
-def mlp_quant_forward(*, x, fc1, fc2, want_hidden=False, want_planes=False):
+def mlp_quant_forward(*, x, fc1, fc2, want_hidden=False, want_planes=False, ln=None, want_norm=False):
     """fc2(GELU(fc1(x))) of two calibrated Linear layers in quant_forward, fused (p4v_mlp_quant_forward): fc1's int8 GEMM ends
     in the exact GELU and fc2's activation quantiser and writes fc2's int8 plane(s); no fp32 hidden tensor in between.
     `fc1` / `fc2`: dicts with weight, bias (or None), w_interval, a_interval (fc2: the positive range), w_bit, a_bit, n_V and
     optionally n_H, n_a, postgelu (fc2: the post-GELU twin).  Returns out, or (out, hidden) with `want_hidden` -- the fp32 GELU
     output the planes were quantised from --, with `want_planes` also the padded int8 plane(s) as the call left them in its
-    workspace (a tuple of one or two [rows_padded][cols_padded] tensors; for the tests)."""
+    workspace (a tuple of one or two [rows_padded][cols_padded] tensors; for the tests).
+    `ln` (a dict of weight, bias, eps): x is the input of a LayerNorm in front of fc1, and k_ln_pack writes fc1's row plane from
+    it (p4v_ln_mlp_quant_forward).  With it the call returns out, then -- as asked for -- y (`want_norm`),
+    hidden, and for `want_planes` FC1's padded int8 row plane (one tensor)."""
+    if ln is None and want_norm:
+        raise ValueError("mlp_quant_forward: want_norm belongs to the fused LayerNorm (ln=)")
+    if ln is not None:
+        return _ln_mlp_forward(x, ln, fc1, fc2, want_norm, want_hidden, want_planes)
     dev = device_of(x, fc1["weight"])
     x = to_dev(x, dev).contiguous()
     batch, K = x.shape[0], x.shape[-1]
@@ -291,6 +310,67 @@ def mlp_quant_forward(*, x, fc1, fc2, want_hidden=False, want_planes=False):
     (w1, b1, w1_iv, a1_iv), (w2, b2, w2_iv, a2_iv) = t["fc1"], t["fc2"]
     return _fused_forward("mlp", d, (w1, b1, w2, b2, x, w1_iv, a1_iv, w2_iv, a2_iv, out, hidden), dev,
                           (out, hidden) if want_hidden else (out,), want_planes)
+
+
+def _ln_call(kind, x, ln, window, d, layers, outs, want_planes):
+    """The tail of the two LayerNorm-fused forwards (`kind`: ln_linear / ln_mlp): the p4v_ln_desc of `ln` and `window` over x's
+    rows, p4v_<kind>_workspace_bytes, the record of device pointers (`layers`: the Linear members by name; `outs`: out, y_out[,
+    hidden]), the checked call.  Returns the tensors of `outs` that exist, with `want_planes` followed by the int8 row plane
+    k_ln_pack wrote ([rows_padded][cols_padded], p4v_debug_ln_planes) -- one tensor alone, else a tuple."""
+    lib = _lib.load()
+    dev, C_ = x.device, x.shape[-1]
+    row_map = (0, 0, 0, 0, 0) if window is None else (1,) + tuple(int(v) for v in window)
+    n = _lib.LnDesc(x.numel() // C_, C_, float(ln["eps"]), *row_map, 0)
+    need = getattr(lib, f"p4v_{kind}_workspace_bytes")(C.byref(n), C.byref(d))
+    if need == 0:
+        _lib.check(-2, f"p4v_{kind}_workspace_bytes")
+    ws = workspace(dev, need)
+    Rec = _lib.LnLinearTensors if kind == "ln_linear" else _lib.LnMlpTensors
+    gamma, beta = (to_dev(ln[k], dev).contiguous() for k in ("weight", "bias"))
+    tensors = dict(x=x, gamma=gamma, beta=beta, **layers, **outs, ws=ws)
+    rec = Rec(**{k: ptr(t) for k, t in tensors.items()}, ws_bytes=ws.numel())
+    with torch.cuda.device(dev):
+        rc = getattr(lib, f"p4v_{kind}_quant_forward")(C.byref(n), C.byref(d), C.byref(rec), stream_ptr(dev))
+    _lib.check(rc, f"p4v_{kind}_quant_forward")
+    res = tuple(t for t in outs.values() if t is not None)
+    if want_planes:
+        info = (C.c_uint64 * 5)()
+        _lib.check(lib.p4v_debug_ln_planes(info), "p4v_debug_ln_planes")
+        off, _, rows, cols, _ = (int(v) for v in info)
+        res += (ws[off:off + rows * cols].view(torch.int8).reshape(rows, cols).clone(),)
+    return res[0] if len(res) == 1 else res
+
+
+def _ln_layer(layer, dev):
+    return (to_dev(layer["weight"], dev).contiguous(), to_dev(layer.get("bias"), dev),
+            to_dev(layer["w_interval"], dev).reshape(-1).contiguous(), to_dev(layer["a_interval"], dev).reshape(-1).contiguous())
+
+
+def _ln_linear_forward(x, ln, layer, window, want_norm, want_planes):
+    """linear_quant_forward with `ln`"""
+    dev = device_of(x, layer["weight"])
+    x = to_dev(x, dev).contiguous()
+    batch, K = x.shape[0], x.shape[-1]
+    w, b, w_iv, a_iv = _ln_layer(layer, dev)
+    d = _mlp_layer_desc(batch, x.numel() // (batch * K), layer)
+    out = torch.empty(x.shape[:-1] + (w.shape[0],), dtype=torch.float32, device=dev)
+    y = torch.empty_like(x) if want_norm else None
+    return _ln_call("ln_linear", x, ln, window, d, dict(w=w, bias=b, w_interval=w_iv, a_interval=a_iv), dict(out=out, y_out=y), want_planes)
+
+
+def _ln_mlp_forward(x, ln, fc1, fc2, want_norm, want_hidden, want_planes):
+    """mlp_quant_forward with `ln`"""
+    dev = device_of(x, fc1["weight"])
+    x = to_dev(x, dev).contiguous()
+    batch, K = x.shape[0], x.shape[-1]
+    tokens = x.numel() // (batch * K)
+    (w1, b1, w1_iv, a1_iv), (w2, b2, w2_iv, a2_iv) = _ln_layer(fc1, dev), _ln_layer(fc2, dev)
+    d = _lib.MlpDesc(_mlp_layer_desc(batch, tokens, fc1), _mlp_layer_desc(batch, tokens, fc2))
+    out = torch.empty(x.shape[:-1] + (w2.shape[0],), dtype=torch.float32, device=dev)
+    y = torch.empty_like(x) if want_norm else None
+    hidden = torch.empty(x.shape[:-1] + (w1.shape[0],), dtype=torch.float32, device=dev) if want_hidden else None
+    layers = dict(w1=w1, w2=w2, bias1=b1, bias2=b2, w1_interval=w1_iv, a1_interval=a1_iv, w2_interval=w2_iv, a2_interval=a2_iv)
+    return _ln_call("ln_mlp", x, ln, window=None, d=d, layers=layers, outs=dict(out=out, y_out=y, hidden=hidden), want_planes=want_planes)
 
 
 def _attn_matmul_desc(d, A_shape, A_stride, B, side, what, who="attn_quant_forward"):

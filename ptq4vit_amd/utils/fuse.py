@@ -200,10 +200,14 @@ def _fused_attention_forward(self, x):
     args = _attn_args(self, x)
     if args is None:
         return self.__dict__[_ORIG_ATTN](x)
-    # models.Attention.forward, with matmul1 ... matmul2 as one engine call
-    B, N, C = x.shape
+    return _attention_tail(self, self.qkv(x), args)
+
+
+def _attention_tail(self, qkv_out, args):
+    """models.Attention.forward behind `self.qkv(x)`, with matmul1 ... matmul2 as one engine call (`qkv_out` [B][N][3 C])"""
+    B, N, C = qkv_out.shape[0], qkv_out.shape[1], qkv_out.shape[2] // 3
     H = self.num_heads
-    qkv = self.qkv(x).reshape(B, N, 3, H, C // H).permute(2, 0, 3, 1, 4)
+    qkv = qkv_out.reshape(B, N, 3, H, C // H).permute(2, 0, 3, 1, 4)
     if os.environ.get("P4V_QKV_CONTIGUOUS", "1") == "1":
         qkv = qkv.contiguous()
     q, k, v = qkv.unbind(0)
@@ -309,10 +313,14 @@ def _fused_window_attention_forward(self, x, mask=None):
     args = _wattn_args(self, x, mask)
     if args is None:
         return self.__dict__[_ORIG_WATTN](x, mask)
-    # models.WindowAttention.forward, with matmul1 ... matmul2 as one engine call
-    B_, N, C = x.shape
+    return _window_attention_tail(self, self.qkv(x), args, mask)
+
+
+def _window_attention_tail(self, qkv_out, args, mask):
+    """models.WindowAttention.forward behind `self.qkv(x)`, with matmul1 ... matmul2 as one engine call (`qkv_out` [B_][N][3 C])"""
+    B_, N, C = qkv_out.shape[0], qkv_out.shape[1], qkv_out.shape[2] // 3
     H = self.num_heads
-    qkv = self.qkv(x).reshape(B_, N, 3, H, C // H).permute(2, 0, 3, 1, 4)
+    qkv = qkv_out.reshape(B_, N, 3, H, C // H).permute(2, 0, 3, 1, 4)
     q, k, v = qkv.unbind(0)
     q = q * self.scale
     n = self.window_size[0] * self.window_size[1]
@@ -338,3 +346,128 @@ def unfuse_window_attention(net):
     for m in net.modules():
         m.__dict__.pop(_WONE_KERNEL, None)
     return _unfuse(net, _ORIG_WATTN)
+
+
+# ---- LayerNorm in front of qkv and of the MLP (engine.linear_quant_forward / mlp_quant_forward with ln=) -----------
+# fuse_norm patches the BLOCKS (models.Block, models.SwinBlock): the patched forward repeats the block's own and decides per side
+# and per call.  norm2 side: the MLP container carries fuse_mlp's patch and would take its fused path, norm2 is an affine
+# nn.LayerNorm over the last dimension, unhooked, not recording, inside the kernel's envelope -> engine.mlp_quant_forward(ln=) on the
+# residual stream.  norm1 side: the attention container carries fuse_window_attention's (Swin) / fuse_attention's (ViT) patch and
+# would take its fused path, qkv is live on its int8 path with n_H = n_a = 1 and no post-GELU input -> engine.linear_quant_forward(ln=)
+# writes qkv's output (Swin: in window order -- the roll and window_partition are the kernel's row map) and the container's
+# fused forward goes on behind `self.qkv(x)`.  A ViT container patched by fuse_qkv_attention keeps norm1 in torch.  Every other
+# state runs the side as the block's own forward does.  Its own saved-forward attribute: composes with the other fuse_* in any order.
+_ORIG_NORM = "_p4v_unfused_norm_forward"
+
+
+def norm_fusable(m):
+    """The static half of the decision: a block whose forward `fuse_norm` patches."""
+    return isinstance(m, (models.Block, models.SwinBlock))
+
+
+def _norm_ok(norm, x):
+    return (isinstance(norm, nn.LayerNorm) and norm.elementwise_affine and norm.bias is not None and torch.is_tensor(x) and x.is_cuda
+            and x.dtype == torch.float32 and x.dim() == 3 and tuple(norm.normalized_shape) == (x.shape[-1],) and not _hooked(norm)
+            and not _recording(x, norm) and x.shape[-1] % 4 == 0 and x.shape[-1] <= 2048)
+
+
+def _ln_of(norm):
+    return dict(weight=norm.weight, bias=norm.bias, eps=norm.eps)
+
+
+def _installed(m):
+    return getattr(m.__dict__.get("forward"), "__func__", None)
+
+
+def _norm1_args(block, x):
+    """(qkv's engine keywords, the container's (matmul1, matmul2) keywords) if the patched forward of `block` fuses norm1 into
+    qkv's quantiser on `x`, else None."""
+    attn = getattr(block, "attn", None)
+    if attn is None or not _norm_ok(block.norm1, x) or _hooked(attn):
+        return None
+    if isinstance(block, models.SwinBlock):
+        (H, W), ws = block.input_resolution, block.window_size
+        if _installed(attn) is not _fused_window_attention_forward or x.shape[1] != H * W or H % ws or W % ws or not 0 <= block.shift_size < ws:
+            return None
+        xin = x.reshape(-1, ws * ws, x.shape[2])                # (the container's input: its shape is all that is asked about)
+        args = _wattn_args(attn, xin, block.attn_mask)
+    else:
+        if _installed(attn) is not _fused_attention_forward:
+            return None
+        xin, args = x, _attn_args(attn, x)
+    qkv = attn.qkv
+    if args is None or not (isinstance(qkv, PTQSLQuantLinear) and _live(qkv) and qkv._int8_ready(xin)):
+        return None
+    lin = qkv._int8_args()
+    if lin["postgelu"] or lin["n_H"] != 1 or lin["n_a"] != 1 or qkv.in_features != x.shape[-1] or qkv.out_features != 3 * x.shape[-1]:
+        return None
+    return lin, args
+
+
+def _norm2_args(block, x):
+    """(fc1's, fc2's engine keywords) if the patched forward of `block` fuses norm2 into fc1's quantiser on `x`, else None."""
+    mlp = getattr(block, "mlp", None)
+    if mlp is None or _ORIG not in mlp.__dict__ or _hooked(mlp) or not _norm_ok(block.norm2, x):
+        return None
+    return _mlp_args(mlp, x)
+
+
+def takes_fused_norm_path(block, x, side=None):
+    """The per-call half: would the patched forward of `block` fuse the LayerNorm of `side` ("norm1" / "norm2"; None: of both
+    sides) on `x`?"""
+    if not norm_fusable(block):
+        return False
+    sides = {"norm1": _norm1_args, "norm2": _norm2_args}
+    return all(sides[s](block, x) is not None for s in ([side] if side else sides))
+
+
+def _mlp_side(self, x):
+    args = _norm2_args(self, x)
+    if args is None:
+        return self.mlp(self.norm2(x))
+    return engine.mlp_quant_forward(x=x, ln=_ln_of(self.norm2), fc1=args[0], fc2=args[1])
+
+
+def _fused_norm_block_forward(self, x):
+    # models.Block.forward
+    a = _norm1_args(self, x)
+    if a is None:
+        x = x + self.attn(self.norm1(x))
+    else:
+        x = x + _attention_tail(self.attn, engine.linear_quant_forward(x=x, ln=_ln_of(self.norm1), **a[0]), a[1])
+    return x + _mlp_side(self, x)
+
+
+def _fused_norm_swin_block_forward(self, x):
+    # models.SwinBlock.forward
+    H, W = self.input_resolution
+    B, L, C = x.shape
+    shortcut = x
+    ws = self.window_size
+    a = _norm1_args(self, x)
+    if a is None:
+        x = self.norm1(x).view(B, H, W, C)
+        if self.shift_size > 0:
+            x = torch.roll(x, shifts=(-self.shift_size, -self.shift_size), dims=(1, 2))
+        xw = models.window_partition(x, ws).view(-1, ws * ws, C)
+        aw = self.attn(xw, mask=self.attn_mask).view(-1, ws, ws, C)
+    else:
+        qkv = engine.linear_quant_forward(x=x, ln=_ln_of(self.norm1), window=(H, W, ws, self.shift_size), **a[0])
+        aw = _window_attention_tail(self.attn, qkv.view(-1, ws * ws, qkv.shape[-1]), a[1], self.attn_mask).view(-1, ws, ws, C)
+    x = models.window_reverse(aw, ws, H, W)
+    if self.shift_size > 0:
+        x = torch.roll(x, shifts=(self.shift_size, self.shift_size), dims=(1, 2))
+    x = shortcut + x.view(B, H * W, C)
+    return x + _mlp_side(self, x)
+
+
+def fuse_norm(net):
+    """Patch the forward of every Block / SwinBlock of `net`; returns their names.  Idempotent.  What a side fuses is decided per
+    call (see above): without fuse_mlp / fuse_window_attention / fuse_attention on the block's containers nothing changes."""
+    names = _patch(net, lambda m: isinstance(m, models.SwinBlock), _ORIG_NORM, _fused_norm_swin_block_forward)
+    return sorted(names + _patch(net, lambda m: isinstance(m, models.Block), _ORIG_NORM, _fused_norm_block_forward))
+
+
+def unfuse_norm(net):
+    """Undo fuse_norm: every patched block gets its original forward back; returns their names.  Idempotent."""
+    return _unfuse(net, _ORIG_NORM)

@@ -104,6 +104,9 @@ def main():
                     help="also time the network with the qkv layer fused into the attention chain (utils/fuse.py::fuse_qkv_attention; with --fused: on top of the fused MLPs)")
     ap.add_argument("--one-kernel", action="store_true",
                     help="also time fuse_qkv_attention / fuse_window_attention(one_kernel=True): the attention core as one kernel (with --fused: on top of the fused MLPs)")
+    ap.add_argument("--fuse-norm", action="store_true",
+                    help="also time utils/fuse.py::fuse_norm on top of fuse_attention / fuse_window_attention (one_kernel with --one-kernel; with --fused: "
+                         "and the fused MLPs), next to the same net without it (norm_base)")
     ap.add_argument("--json", default=None, help="write the result to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -140,7 +143,7 @@ def main():
           f"logit rel diff {((y_q - y_raw).norm() / y_raw.norm()).item():.3e}")
     res = {"model": a.model, "batch": a.batch, "reps": a.reps, "source_hash": _lib.source_hash(),
            "raw_fp32_ms": t_raw * 1e3, "quant_forward_ms": t_q * 1e3, "quant_vs_fp32": t_raw / t_q}
-    if a.fused or a.fused_attn or a.fused_qkv or a.one_kernel:
+    if a.fused or a.fused_attn or a.fused_qkv or a.one_kernel or a.fuse_norm:
         # the variants alternating, repetition by repetition, after one warm-up of each: (key, fuse the MLPs, fuse the attention --
         # "qkv": with the qkv layer)
         variants = [("unfused", False, False)]
@@ -152,16 +155,25 @@ def main():
             variants.append(("fused_qkv", a.fused, "qkv"))
         if a.one_kernel:
             variants.append(("fused_qkv_one", a.fused, "qkv1"))
+        if a.fuse_norm:                    # ("norm", attn): fuse_norm on top; "attn1": fuse_attention / fuse_window_attention, one kernel
+            base = "attn1" if a.one_kernel else True
+            variants += [("norm_base", a.fused, base), ("fused_norm", a.fused, ("norm", base))]
 
         def setup(mlp, attn):
+            fuse.unfuse_norm(net)
+            norm, attn = (True, attn[1]) if isinstance(attn, tuple) else (False, attn)
             fuse.unfuse_mlp(net)
             fuse.unfuse_attention(net)
             fuse.unfuse_window_attention(net)
             fuse_attn = fuse.fuse_attention
             if attn in ("qkv", "qkv1"):
                 fuse_attn = lambda n: fuse.fuse_qkv_attention(n, one_kernel=attn == "qkv1")
+            if attn == "attn1":
+                fuse_attn = lambda n: fuse.fuse_attention(n, one_kernel=True)
+            if norm:
+                fuse.fuse_norm(net)
             return (len(fuse.fuse_mlp(net)) if mlp else 0,
-                    len(fuse_attn(net)) + len(fuse.fuse_window_attention(net, one_kernel=attn == "qkv1")) if attn else 0)
+                    len(fuse_attn(net)) + len(fuse.fuse_window_attention(net, one_kernel=attn in ("qkv1", "attn1"))) if attn else 0)
 
         ts = {key: [] for key, _, _ in variants}
         ys, counts = {}, {}
@@ -186,6 +198,12 @@ def main():
                 print(f"  one-kernel attention core ({n_attn}{' + MLPs' if a.fused else ''}) {t_v * 1e3:.2f} ms: x{med[base_key] / t_v:.3f} "
                       f"over {base_key} ({(med[base_key] - t_v) * 1e3:+.3f} ms), x{t_u / t_v:.3f} over unfused; logit rel diff vs unfused {rel:.3e}")
                 res.update({base_key + "_over_fused_qkv_one": med[base_key] / t_v, base_key + "_minus_fused_qkv_one_ms": (med[base_key] - t_v) * 1e3})
+            elif key in ("norm_base", "fused_norm"):
+                base_key = "norm_base" if key == "fused_norm" else "unfused"
+                print(f"  {key} ({n_attn} attention containers{' + MLPs' if a.fused else ''}) {t_v * 1e3:.2f} ms: x{med[base_key] / t_v:.3f} over {base_key} "
+                      f"({(med[base_key] - t_v) * 1e3:+.3f} ms); logit rel diff vs unfused {rel:.3e}")
+                if key == "fused_norm":
+                    res.update({"norm_base_over_fused_norm": med[base_key] / t_v, "norm_base_minus_fused_norm_ms": (med[base_key] - t_v) * 1e3})
             elif key == "fused_qkv":
                 base_key = "fused_attn" if a.fused_attn else "fused" if a.fused else "unfused"
                 print(f"  fused qkv + attention ({n_attn}{' + MLPs' if a.fused else ''}) {t_v * 1e3:.2f} ms: x{med[base_key] / t_v:.3f} "
