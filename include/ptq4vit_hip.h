@@ -49,7 +49,8 @@
 extern "C" {
 #endif
 
-#define P4V_VERSION 148 /* 0.1.4.8: + the fused LayerNorm producer: p4v_ln_linear_quant_forward, p4v_ln_mlp_quant_forward, LayerNorm writes the Linear's int8 row plane */
+#define P4V_VERSION 149 /* 0.1.4.9: + the fused block output: p4v_linear_res_quant_forward, p4v_mlp_res_quant_forward, proj / fc2 add the residual in the GEMM epilogue */
+/* 0.1.4.8: + the fused LayerNorm producer: p4v_ln_linear_quant_forward, p4v_ln_mlp_quant_forward, LayerNorm writes the Linear's int8 row plane */
 /* 0.1.4.6: + P4V_ATTN_ONE_KERNEL (the fused attention core as one kernel: p v from the probabilities in registers) */
 /* 0.1.4.5: + p4v_qkv_attn_* (the fused int8 qkv forward: the qkv GEMM writes the attention operand planes) */
 
@@ -666,6 +667,61 @@ size_t p4v_ln_mlp_workspace_bytes(const p4v_ln_desc* ln, const p4v_mlp_desc* des
 
 int p4v_ln_mlp_quant_forward(const p4v_ln_desc* ln, const p4v_mlp_desc* desc, const p4v_ln_mlp_tensors* tensors, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Fused block output (opt-in, network level): residual + Linear(x) and residual + fc2(GELU(fc1([LayerNorm](x)))) with the layer's
+ * fp32 output never written.  One kernel (k_lin_res) runs the Linear's (fc2's) int8 GEMM on the prepacked planes; its epilogue
+ * computes, per element and without contraction, v = (float)acc * s + bias as p4v_linear_quant_forward stores it (the post-GELU
+ * twin: its second plane by fmaf, as there) and writes out[dst(m)][n] = residual[dst(m)][n] + v -- one fp32 add, as torch's
+ * `shortcut + x`: `out` equals the unfused chain's bit for bit.
+ * `map` 1 scatters the rows as SwinBlock.forward does behind proj -- window_reverse, then roll(+shift) over (H, W), the inverse of
+ * p4v_ln_desc's map 1: row ((b H/ws + wh) W/ws + ww) ws^2 + i ws + j goes to token (b, (wh ws + i + shift) mod H,
+ * (ww ws + j + shift) mod W); residual and out are in token order.  The MLP call uses the identity map; with `ln` (may be NULL: no
+ * LayerNorm) x is the input of a LayerNorm in front of fc1 as in p4v_ln_mlp_quant_forward, and the residual is normally x itself.
+ * Envelope: the Linear (fc2) with int8 planes, n_H = n_a = 1, out_features % 4 == 0; the linear call: not twin_postgelu; residual and
+ * out [batch * tokens][out_features] fp32, 16-byte aligned, not overlapping; map 1: H % ws == W % ws == 0, 0 <= shift < ws,
+ * rows % (H W) == 0; for the MLP call the envelope of p4v_mlp_quant_forward (p4v_ln_mlp_quant_forward).  Anything else is
+ * P4V_ERR_UNSUPPORTED / P4V_ERR_INVALID before the first launch.
+ * ws, ws_bytes: the workspace and its size -- the workspace contract above holds with p4v_linear_res_workspace_bytes /
+ * p4v_mlp_res_workspace_bytes; a smaller ws_bytes is refused before any launch.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct p4v_res_desc {
+    int32_t map;                       /* 0 identity, 1 window */
+    int32_t H, W, ws, shift;           /* map 1 only */
+    int32_t reserved;
+} p4v_res_desc;
+
+typedef struct p4v_linear_res_tensors {
+    const float *x, *w;
+    const float* bias;                 /* NULL without a bias (has_bias = 0) */
+    const float *w_interval, *a_interval;
+    const float* residual;
+    float* out;
+    void* ws;
+    size_t ws_bytes;
+} p4v_linear_res_tensors;
+
+typedef struct p4v_mlp_res_tensors {
+    const float* x;
+    const float *gamma, *beta;         /* NULL without a LayerNorm (ln = NULL) */
+    const float *w1, *w2;
+    const float *bias1, *bias2;        /* NULL without a bias */
+    const float *w1_interval, *a1_interval, *w2_interval, *a2_interval;
+    const float* residual;
+    float* out;
+    float* y_out;                      /* optional, with a LayerNorm only */
+    float* hidden;                     /* optional */
+    void* ws;
+    size_t ws_bytes;
+} p4v_mlp_res_tensors;
+
+size_t p4v_linear_res_workspace_bytes(const p4v_linear_desc* desc, const p4v_res_desc* res);
+
+int p4v_linear_res_quant_forward(const p4v_linear_desc* desc, const p4v_res_desc* res, const p4v_linear_res_tensors* tensors, void* stream);
+
+size_t p4v_mlp_res_workspace_bytes(const p4v_ln_desc* ln, const p4v_mlp_desc* desc);
+
+int p4v_mlp_res_quant_forward(const p4v_ln_desc* ln, const p4v_mlp_desc* desc, const p4v_mlp_res_tensors* tensors, void* stream);
+
 /* d_A_interval: [heads] (sos: [1]); d_B_interval: [heads]; d_split: [1] (sos only); d_out: [batch*heads][M][N] */
 int p4v_matmul_quant_forward(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_A_interval,
                              const float* d_B_interval, const float* d_split, float* d_out, void* d_workspace,
@@ -713,7 +769,7 @@ typedef struct p4v_launch_record {
                          0 generic int8 k_sweep | 1 generic fp32 k_sweep | 11 k_sos_split (fp32) | 12 k_bound (stage B1) |
                          13 k_slice_b2 / 14 k_slice_a (stage A of a MatMul B / A search) | 15 k_sweep_seg | 16 k_mlp_fc1 |
                          17 k_attn_qk | 18 k_qkv_heads | 19 k_attn_qkpv | 20 k_wattn_qkpv | 21 k_ln_pack (no MACs: alg_bytes = x + gamma +
-                         beta + the int8 plane + y_out where given) */
+                         beta + the int8 plane + y_out where given) | 22 k_lin_res (alg_bytes = the int8 planes + the residual + out) */
     int32_t stage;    /* 0 full sweep (pass not pruned) | 1 stage A (all candidates, sample slice) | 2 stage B1 (the bound) |
                          3 stage B2 (survivors, all samples) | 4 stage A2 (survivors of a loose first slice on the larger second one) */
     int32_t grid_x, grid_z;   /* a grouped launch (p4v_calibrate_group): grid_x = its flat grid (all members' blocks, each member padded to a

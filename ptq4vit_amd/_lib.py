@@ -82,6 +82,24 @@ class LnMlpTensors(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in POINTERS] + [("ws_bytes", C.c_size_t)]
 
 
+class ResDesc(C.Structure):
+    """p4v_res_desc: the row map of a fused residual add (0 identity, 1 Swin's window_reverse + roll(+shift))."""
+    _fields_ = [(n, C.c_int32) for n in ("map", "H", "W", "ws", "shift", "reserved")]
+
+
+class LinearResTensors(C.Structure):
+    """p4v_linear_res_tensors: the device pointers of a p4v_linear_res_quant_forward call, its workspace and the workspace's size."""
+    POINTERS = ("x", "w", "bias", "w_interval", "a_interval", "residual", "out", "ws")
+    _fields_ = [(n, C.c_void_p) for n in POINTERS] + [("ws_bytes", C.c_size_t)]
+
+
+class MlpResTensors(C.Structure):
+    """p4v_mlp_res_tensors: the device pointers of a p4v_mlp_res_quant_forward call, its workspace and the workspace's size."""
+    POINTERS = ("x", "gamma", "beta", "w1", "w2", "bias1", "bias2", "w1_interval", "a1_interval", "w2_interval", "a2_interval", "residual",
+                "out", "y_out", "hidden", "ws")
+    _fields_ = [(n, C.c_void_p) for n in POINTERS] + [("ws_bytes", C.c_size_t)]
+
+
 class MatMulBlocksDesc(C.Structure):
     """p4v_matmul_blocks_desc: the MatMul descriptor plus the row / column block counts of both operands."""
     _fields_ = [("mm", MatMulDesc)] + [(n, C.c_int32) for n in ("n_V_A", "n_H_A", "n_V_B", "n_H_B")]
@@ -111,7 +129,7 @@ class LaunchRecord(C.Structure):
 
 LAUNCH_KINDS = {0: "k_sweep<int8>", 1: "k_sweep<float>", 2: "k_sweep6", 3: "k_sweep7", 4: "k_sweep7 (twin)", 5: "k_sweep4/5", 6: "k_sweep9",
                 7: "k_sweep8", 8: "k_sweep2g", 9: "k_sweep2", 11: "k_sos_split", 12: "k_bound", 13: "k_slice_b", 14: "k_slice_a", 15: "k_sweep_seg", 16: "k_mlp_fc1",
-                17: "k_attn_qk", 18: "k_qkv_heads", 19: "k_attn_qkpv", 20: "k_wattn_qkpv", 21: "k_ln_pack"}
+                17: "k_attn_qk", 18: "k_qkv_heads", 19: "k_attn_qkpv", 20: "k_wattn_qkpv", 21: "k_ln_pack", 22: "k_lin_res"}
 LAUNCH_STAGES = {0: "full", 1: "A", 2: "B1", 3: "B2", 4: "A2"}
 
 
@@ -165,6 +183,7 @@ EXPORTS = [
     "p4v_attn_workspace_bytes", "p4v_attn_quant_forward", "p4v_wattn_workspace_bytes", "p4v_wattn_quant_forward",
     "p4v_qkv_attn_workspace_bytes", "p4v_qkv_attn_quant_forward",
     "p4v_ln_linear_workspace_bytes", "p4v_ln_linear_quant_forward", "p4v_ln_mlp_workspace_bytes", "p4v_ln_mlp_quant_forward",
+    "p4v_linear_res_workspace_bytes", "p4v_linear_res_quant_forward", "p4v_mlp_res_workspace_bytes", "p4v_mlp_res_quant_forward",
     "p4v_amax_init_linear", "p4v_linear_search_w", "p4v_linear_search_a",
     "p4v_amax_init_matmul", "p4v_matmul_search_A", "p4v_sos_search_split", "p4v_matmul_search_B",
     "p4v_amax_init_conv", "p4v_conv_search_w_channelwise", "p4v_conv_search_w_layerwise", "p4v_conv_search_a",
@@ -253,6 +272,14 @@ def load():
     lib.p4v_ln_mlp_workspace_bytes.argtypes = [C.POINTER(LnDesc), C.POINTER(MlpDesc)]
     lib.p4v_ln_mlp_quant_forward.restype = C.c_int
     lib.p4v_ln_mlp_quant_forward.argtypes = [C.POINTER(LnDesc), C.POINTER(MlpDesc), C.POINTER(LnMlpTensors), vp]
+    lib.p4v_linear_res_workspace_bytes.restype = C.c_size_t
+    lib.p4v_linear_res_workspace_bytes.argtypes = [C.POINTER(LinearDesc), C.POINTER(ResDesc)]
+    lib.p4v_linear_res_quant_forward.restype = C.c_int
+    lib.p4v_linear_res_quant_forward.argtypes = [C.POINTER(LinearDesc), C.POINTER(ResDesc), C.POINTER(LinearResTensors), vp]
+    lib.p4v_mlp_res_workspace_bytes.restype = C.c_size_t
+    lib.p4v_mlp_res_workspace_bytes.argtypes = [C.POINTER(LnDesc), C.POINTER(MlpDesc)]
+    lib.p4v_mlp_res_quant_forward.restype = C.c_int
+    lib.p4v_mlp_res_quant_forward.argtypes = [C.POINTER(LnDesc), C.POINTER(MlpDesc), C.POINTER(MlpResTensors), vp]
     lib.p4v_debug_ln_planes.restype = C.c_int
     lib.p4v_debug_ln_planes.argtypes = [C.POINTER(C.c_uint64)]
     lib.p4v_matmul_quant_forward.restype = C.c_int

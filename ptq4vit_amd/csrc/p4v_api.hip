@@ -3210,6 +3210,51 @@ int launch_ln_pack(Ctx& c, const LnStep& ln, const float* a_iv, int aq, char* pl
     }
 }
 
+// ---- the residual consumer: k_lin_res runs a Linear layer's forward GEMM on prepacked planes and writes residual + output through
+// a row map ---------------------------------------------------------------------------------------------------------
+constexpr int RES_RECORD_KIND = 22;
+struct ResStep { const p4v_res_desc* d; const float* residual; float* out; };
+// the envelope of the consumer behind the Linear layer `d`, before anything is planned or launched
+int res_check(const ResStep& r, const p4v_linear_desc* d, const Ctx& c, const char* who) {
+    const long M = (long)d->batch * d->tokens;
+    const p4v_res_desc& m = *r.d;
+    if (d->n_H != 1 || d->n_a != 1) return fail(P4V_ERR_UNSUPPORTED, "%s: the fused residual takes n_H = n_a = 1 on the Linear layer", who);
+    if (d->reserved & RSV_FP32_PLANES) return fail(P4V_ERR_UNSUPPORTED, "%s: int8 planes only (desc.reserved bit 0 is set)", who);
+    if (d->out_features <= 0 || d->out_features % 4)
+        return fail(P4V_ERR_UNSUPPORTED, "%s: the fused residual over %d output features (a multiple of 4 is implemented)", who, d->out_features);
+    if (m.map != 0 && m.map != 1) return fail(P4V_ERR_INVALID, "%s: unknown row map %d", who, m.map);
+    if (m.map == 1 && (m.H <= 0 || m.W <= 0 || m.ws <= 0 || m.H % m.ws || m.W % m.ws || m.shift < 0 || m.shift >= m.ws || M <= 0 || M % ((long)m.H * m.W)))
+        return fail(P4V_ERR_INVALID, "%s: window map (H %d, W %d, ws %d, shift %d) over %ld rows: ws must divide H and W, 0 <= shift < ws, H * W the rows",
+                    who, m.H, m.W, m.ws, m.shift, M);
+    if (c.dry) return 0;
+    if (((unsigned long long)r.residual | (unsigned long long)r.out) & 15) return fail(P4V_ERR_INVALID, "%s: residual and out must be aligned to 16 bytes", who);
+    const char *a = (const char*)r.residual, *b = (const char*)r.out;
+    const size_t bytes = (size_t)M * d->out_features * sizeof(float);
+    if (a < b + bytes && b < a + bytes) return fail(P4V_ERR_INVALID, "%s: out overlaps the residual", who);
+    return 0;
+}
+// k_lin_res on a call that passed res_check: row plane(s) [Mp][Kp] (`rows2`: the twin's negative range, or null), column plane
+// [Np][Kp], the scale table(s) of the layer's forward pass
+int launch_lin_res(Ctx& c, const ResStep& r, const char* rows, const char* rows2, const char* cols, const float* S1, const float* S2, int s_cs, int sb_div,
+                   const float* bias, int M, int N, int K, int Mp, int Np, int Kp) {
+    if (c.dry) return 0;
+    const bool twin = rows2 != nullptr;
+    LinResParams q{};
+    q.A = rows; q.A2 = rows2; q.B = cols; q.ldk = Kp; q.ktiles = Kp / SW_BKB;
+    q.S1 = S1; q.S2 = S2; q.s_cs = s_cs; q.sb_div = s_cs > 1 ? std::max(1, sb_div) : (1 << 30);
+    q.bias = bias; q.residual = r.residual; q.out = r.out; q.M = M; q.N = N;
+    q.mtiles = Mp / SW_BM; q.ntiles = Np / SW_BN;
+    q.map = r.d->map; q.H = r.d->H; q.W = r.d->W; q.ws = r.d->ws; q.shift = r.d->shift;
+    g_alg_macs_cand = (double)M * N * K;
+    g_alg_bytes = (double)Mp * Kp * (twin ? 2 : 1) + (double)Np * Kp + 8.0 * (double)M * N;        // the planes, the residual, out
+    g_exec_frac = 1.0;
+    const StatInfo si = stat_info(RES_RECORD_KIND, (double)Mp * Np * Kp * (twin ? 2 : 1), g_alg_macs_cand, q.mtiles * q.ntiles, 1, g_alg_bytes);
+    const dim3 grid(q.mtiles * q.ntiles), block(512);
+    const size_t lds = (size_t)2 * (twin ? 3 : 2) * SW_TILE_BYTES + SW_BM * sizeof(int);
+    return twin ? enqueue(c, KERN1_T(LinResParams, k_lin_res, true), grid, block, lds, q, &si)
+                : enqueue(c, KERN1_T(LinResParams, k_lin_res, false), grid, block, lds, q, &si);
+}
+
 // One producer -> consumer chain, in the order its caller walks it: plan_consumer, produce, consume.
 struct FusedChain {
     struct Packed { char *rows, *cols; float* S1; int Kp, Np; };    // the producer's operand planes [Z][Mp | Np][Kp] and its scale table
@@ -3281,6 +3326,32 @@ struct FusedChain {
         if (pre) { fp2.col.prepacked = true; fp2.col.plane = pre->col2; }
         return run_pass(c, fp2);
     }
+    // what pack_operand reads of a plan, for the consumer's planes as k_lin_res reads them: [Mp][Kp] rows, [roundup128(N)][Kp] columns
+    SweepPlan res_planes() const {
+        SweepPlan pl{};
+        pl.esz = 1; pl.Mp = Mp; pl.Np = pl.NpB = producer_np(fp2.Ncols); pl.Kp = Kp; pl.cin_fix = 0;
+        return pl;
+    }
+    // The consumer (a Linear layer: Z = 1) as k_lin_res: its column plane and scale table(s) as pack_pair packs a producer's
+    // (pack_operand, k_scale_table), in scratch that is given back, then the kernel on the carved row plane(s) -- no run_pass, no
+    // fp32 output of the layer: `r.out` receives residual + output through the row map.
+    int consume_res(const ResStep& r) {
+        if (Z != 1 || Mp % SW_BM || Kp % SW_BKB) return fail(P4V_ERR_UNSUPPORTED, "%s: %s's row plane [%d][%d] is not k_lin_res's", who, consumer, Mp, Kp);
+        const size_t mark = c.ws.off;
+        const SweepPlan pl = res_planes();
+        char* cols = c.ws.get<char>((size_t)pl.NpB * Kp);
+        float* S1 = c.ws.get<float>((size_t)fp2.s_cs);
+        float* S2 = twin ? c.ws.get<float>((size_t)fp2.s_cs) : nullptr;
+        if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", c.ws.off);
+        fp2.s1.S = S1; fp2.s1.C = 1; fp2.s1.nblk = fp2.s_cs;
+        CHK(launch_scale(c, fp2.s1));
+        if (twin) { fp2.s2.S = S2; fp2.s2.C = 1; fp2.s2.nblk = fp2.s_cs; CHK(launch_scale(c, fp2.s2)); }
+        const PassBufs nb{};
+        CHK(pack_operand(c, fp2, pl, nb, fp2.col, cols, true, 0, 1));
+        CHK(launch_lin_res(c, r, P1, P2, cols, S1, S2, fp2.s_cs, fp2.sb_div, fp2.bias, fp2.Mrows, fp2.Ncols, fp2.K, Mp, pl.NpB, Kp));
+        c.ws.off = mark;
+        return 0;
+    }
 };
 // the dry run of the planner: the envelope's verdict, and the bytes the call needs
 template <class D, class T> int fused_sizing_run(int (*impl)(const D*, const T&, const T&, Ctx&), const D* d, size_t* need) {
@@ -3306,7 +3377,8 @@ template <class D, class T> int fused_call(int (*impl)(const D*, const T&, const
 // `t1`, `t2`: the two layers' records as p4v_linear_quant_forward fills them -- t1.fwd_out is the optional fp32 copy of the hidden
 // tensor (fc1 stores no other output), t2.X stays null (fc2 reads fc1's planes).
 // `ln` (ln_mlp_impl): x is LayerNorm's input -- k_ln_pack writes fc1's row plane, which pack_pair then takes as it is.
-int mlp_chain(const p4v_mlp_desc* d, const LinearTensors& t1, const LinearTensors& t2, Ctx& c, const LnStep* ln) {
+// `res` (mlp_res_impl, after res_check): fc2 runs as k_lin_res on the planes -- res->out receives residual + fc2's output, t2.fwd_out is not written.
+int mlp_chain(const p4v_mlp_desc* d, const LinearTensors& t1, const LinearTensors& t2, Ctx& c, const LnStep* ln, const ResStep* res = nullptr) {
     const p4v_linear_desc* d1 = &d->fc1;
     const p4v_linear_desc* d2 = &d->fc2;
     // the envelope, before anything is planned or launched
@@ -3348,7 +3420,7 @@ int mlp_chain(const p4v_mlp_desc* d, const LinearTensors& t1, const LinearTensor
         return L2.twin ? enqueue(c, KERN1_T(MlpFc1Params, k_mlp_fc1, true), grid, block, lds, q, &si)
                        : enqueue(c, KERN1_T(MlpFc1Params, k_mlp_fc1, false), grid, block, lds, q, &si);
     }, ln ? &pre : nullptr));
-    return ch.consume();
+    return res ? ch.consume_res(*res) : ch.consume();
 }
 int mlp_impl(const p4v_mlp_desc* d, const LinearTensors& t1, const LinearTensors& t2, Ctx& c) { return mlp_chain(d, t1, t2, c, nullptr); }
 
@@ -3376,6 +3448,40 @@ int ln_mlp_impl(const LnMlpCall* d, const LnMlpTensors& t, const LnMlpTensors&, 
     CHK(ln_check(&d->ln, &d->mlp.fc1, t.n, c, "ln_mlp"));
     const LnStep ln{&d->ln, t.n};
     return mlp_chain(&d->mlp, t.l1, t.l2, c, &ln);
+}
+
+// ---- p4v_linear_res_quant_forward / p4v_mlp_res_quant_forward: the residual add (and Swin's window_reverse + roll) in the epilogue of
+// proj / fc2 -------------------------------------------------------------------------------------------------------
+struct LinResCall { p4v_linear_desc lin; p4v_res_desc res; };
+struct LinResTensors { LinearTensors l; const float* residual = nullptr; };                      // l.fwd_out: out
+struct MlpResCall { bool has_ln; p4v_ln_desc ln; p4v_mlp_desc mlp; };
+struct MlpResTensors { LnTensors n; LinearTensors l1, l2; const float* residual = nullptr; };    // l2.fwd_out: out
+
+// residual + Linear(x) through the row map: the Linear is the chain's consumer, its row plane packed from x as its forward pass
+// packs it (pack_operand: k_pack1), then k_lin_res.
+int linear_res_impl(const LinResCall* d, const LinResTensors& t, const LinResTensors&, Ctx& c) {
+    const ResStep rs{&d->res, t.residual, t.l.fwd_out};
+    CHK(res_check(rs, &d->lin, c, "linear_res"));
+    if (d->lin.twin_postgelu) return fail(P4V_ERR_UNSUPPORTED, "linear_res: the Linear layer reads no GELU output (twin_postgelu: p4v_mlp_res_quant_forward)");
+    const Stage sg{ST_FWD};
+    LinearCall L(c, &d->lin, t.l, sg);
+    CHK(L.build());
+    if (!L.i8 || L.twin) return fail(P4V_ERR_UNSUPPORTED, "linear_res: int8 planes only");
+    FusedChain ch{c, "linear_res", "the Linear"};
+    CHK(ch.plan_consumer(L.forward_pass(), 1, false));         // P1: [Mp][roundup64(K)]
+    if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", c.ws.off);
+    const PassBufs nb{};
+    CHK(pack_operand(c, ch.fp2, ch.res_planes(), nb, ch.fp2.row, ch.P1, false, 0, 1));
+    return ch.consume_res(rs);
+}
+int mlp_res_impl(const MlpResCall* d, const MlpResTensors& t, const MlpResTensors&, Ctx& c) {
+    static const p4v_res_desc identity{};
+    const ResStep rs{&identity, t.residual, t.l2.fwd_out};
+    CHK(res_check(rs, &d->mlp.fc2, c, "mlp_res"));
+    if (!d->has_ln) return mlp_chain(&d->mlp, t.l1, t.l2, c, nullptr, &rs);
+    CHK(ln_check(&d->ln, &d->mlp.fc1, t.n, c, "mlp_res"));
+    const LnStep ln{&d->ln, t.n};
+    return mlp_chain(&d->mlp, t.l1, t.l2, c, &ln, &rs);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4489,6 +4595,47 @@ int p4v_ln_mlp_quant_forward(const p4v_ln_desc* ln, const p4v_mlp_desc* desc, co
                            {.W = t->w2, .bias = desc->fc2.has_bias ? t->bias2 : nullptr, .w_iv = const_cast<float*>(t->w2_interval),
                             .a_iv = const_cast<float*>(t->a2_interval), .fwd_out = t->out}};
     return fused_call(ln_mlp_impl, &d, rec, rec, t->ws, t->ws_bytes, stream);
+}
+
+size_t p4v_linear_res_workspace_bytes(const p4v_linear_desc* desc, const p4v_res_desc* res) {
+    if (!desc || !res) return 0;
+    const LinResCall d{*desc, *res};
+    size_t need = 0;
+    return fused_sizing_run(linear_res_impl, &d, &need) == 0 ? need : 0;
+}
+
+int p4v_linear_res_quant_forward(const p4v_linear_desc* desc, const p4v_res_desc* res, const p4v_linear_res_tensors* t, void* stream) {
+    if (!desc || !res || !t || !t->x || !t->w || !t->w_interval || !t->a_interval || !t->residual || !t->out || !t->ws)
+        return fail(P4V_ERR_INVALID, "p4v_linear_res_quant_forward: null pointer");
+    if (desc->has_bias && !t->bias) return fail(P4V_ERR_INVALID, "p4v_linear_res_quant_forward: has_bias set but the bias is null");
+    CHK(ws_aligned(t->ws));
+    const LinResCall d{*desc, *res};
+    const LinResTensors rec{{.W = t->w, .bias = desc->has_bias ? t->bias : nullptr, .X = t->x, .w_iv = const_cast<float*>(t->w_interval),
+                             .a_iv = const_cast<float*>(t->a_interval), .fwd_out = t->out}, t->residual};
+    return fused_call(linear_res_impl, &d, rec, rec, t->ws, t->ws_bytes, stream);
+}
+
+size_t p4v_mlp_res_workspace_bytes(const p4v_ln_desc* ln, const p4v_mlp_desc* desc) {
+    if (!desc) return 0;
+    const MlpResCall d{ln != nullptr, ln ? *ln : p4v_ln_desc{}, *desc};
+    size_t need = 0;
+    return fused_sizing_run(mlp_res_impl, &d, &need) == 0 ? need : 0;
+}
+
+int p4v_mlp_res_quant_forward(const p4v_ln_desc* ln, const p4v_mlp_desc* desc, const p4v_mlp_res_tensors* t, void* stream) {
+    if (!desc || !t || !t->x || (ln && (!t->gamma || !t->beta)) || !t->w1 || !t->w2 || !t->w1_interval || !t->a1_interval || !t->w2_interval ||
+        !t->a2_interval || !t->residual || !t->out || !t->ws)
+        return fail(P4V_ERR_INVALID, "p4v_mlp_res_quant_forward: null pointer");
+    if ((desc->fc1.has_bias && !t->bias1) || (desc->fc2.has_bias && !t->bias2))
+        return fail(P4V_ERR_INVALID, "p4v_mlp_res_quant_forward: has_bias set but the bias is null");
+    CHK(ws_aligned(t->ws));
+    const MlpResCall d{ln != nullptr, ln ? *ln : p4v_ln_desc{}, *desc};
+    const MlpResTensors rec{{t->x, t->gamma, t->beta, ln ? t->y_out : nullptr},
+                            {.W = t->w1, .bias = desc->fc1.has_bias ? t->bias1 : nullptr, .X = ln ? nullptr : t->x, .w_iv = const_cast<float*>(t->w1_interval),
+                             .a_iv = const_cast<float*>(t->a1_interval), .fwd_out = t->hidden},
+                            {.W = t->w2, .bias = desc->fc2.has_bias ? t->bias2 : nullptr, .w_iv = const_cast<float*>(t->w2_interval),
+                             .a_iv = const_cast<float*>(t->a2_interval), .fwd_out = t->out}, t->residual};
+    return fused_call(mlp_res_impl, &d, rec, rec, t->ws, t->ws_bytes, stream);
 }
 
 int p4v_matmul_quant_forward(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_A_interval,

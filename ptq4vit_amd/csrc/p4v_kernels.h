@@ -4968,11 +4968,14 @@ __global__ __launch_bounds__(512) void k_sweep_seg(SweepSegParams p) { k_sweep_s
 template <bool TWIN, int EPI>
 __global__ __launch_bounds__(512) void k_sweep_seg_g(GroupArgs<SweepSegParams> a) { P4V_GROUP_ENTER(a); k_sweep_seg_body<TWIN, EPI>(a.p[m_], vb_, vg_); }
 
-// The GEMM loop of the fused forwards' Linear producers (k_mlp_fc1, k_qkv_heads): one 128 x 128 tile of A [.][ldk] x B [.][ldk]^T
+// The GEMM loop of the fused forwards' Linear kernels (k_mlp_fc1, k_qkv_heads, k_lin_res): one 128 x 128 tile of A [.][ldk] x B [.][ldk]^T
 // at rows m0 / n0, int8, on 2 x 4 waves of 64 x 32 -- k_sweep<int8_t>'s staging, fragment and C/D maps, double-buffered through
 // `smem` (2 stages of two SW_TILE_BYTES tiles).  Returns behind the loop's last barrier: the staging LDS is free.
-__device__ __forceinline__ void i8_tile_gemm(const void* A, const void* B, int ldk, int ktiles, int m0, int n0, char* smem, v16i (&acc)[2]) {
-    constexpr int STAGE = 2 * SW_TILE_BYTES;
+// TWIN: a second row plane A2 against the same column fragments -- three tiles per stage (A, B, A2), a second accumulator pair.
+template <bool TWIN>
+__device__ __forceinline__ void i8_tile_gemm_t(const void* A, const void* A2, const void* B, int ldk, int ktiles, int m0, int n0, char* smem,
+                                               v16i (&acc)[2], v16i (&acc2)[2]) {
+    constexpr int STAGE = (TWIN ? 3 : 2) * SW_TILE_BYTES;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wr = wid >> 2, wc = wid & 3;
     const int g = lane >> 5, l31 = lane & 31;
@@ -4980,22 +4983,28 @@ __device__ __forceinline__ void i8_tile_gemm(const void* A, const void* B, int l
     const int ld_row = tid >> 2, ld_col = (tid & 3) * 16;
     const char* gA = (const char*)A + (long)(m0 + ld_row) * ldk + ld_col;
     const char* gB = (const char*)B + (long)(n0 + ld_row) * ldk + ld_col;
+    const char* gA2 = TWIN ? (const char*)A2 + (long)(m0 + ld_row) * ldk + ld_col : nullptr;
     const int lds_st = ld_row * SW_ROW + ld_col;
-    v4i ra, rb;
+    v4i ra, rb, rc;
     auto gload = [&](int kt) {
         ra = *reinterpret_cast<const v4i*>(gA + kt * SW_BKB);
         rb = *reinterpret_cast<const v4i*>(gB + kt * SW_BKB);
+        if constexpr (TWIN) rc = *reinterpret_cast<const v4i*>(gA2 + kt * SW_BKB);
     };
     auto lstore = [&](int stage) {
         char* s = smem + stage * STAGE + lds_st;
         *reinterpret_cast<v4i*>(s) = ra;
         *reinterpret_cast<v4i*>(s + SW_TILE_BYTES) = rb;
+        if constexpr (TWIN) *reinterpret_cast<v4i*>(s + 2 * SW_TILE_BYTES) = rc;
     };
 
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][r] = 0;
+        for (int r = 0; r < 16; ++r) {
+            acc[i][r] = 0;
+            if constexpr (TWIN) acc2[i][r] = 0;
+        }
 
     const int fa = (wr * 64 + l31) * SW_ROW;       // + i*32*SW_ROW
     const int fb = SW_TILE_BYTES + (wc * 32 + l31) * SW_ROW;
@@ -5016,11 +5025,18 @@ __device__ __forceinline__ void i8_tile_gemm(const void* A, const void* B, int l
             for (int i = 0; i < 2; ++i) {
                 const v4i a = *reinterpret_cast<const v4i*>(s + fa + i * 32 * SW_ROW + off);
                 acc[i] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, acc[i], 0, 0, 0);
+                if constexpr (TWIN) {
+                    const v4i a2 = *reinterpret_cast<const v4i*>(s + 2 * SW_TILE_BYTES + fa + i * 32 * SW_ROW + off);
+                    acc2[i] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a2, b, acc2[i], 0, 0, 0);
+                }
             }
         }
         if (kt + 1 < ktiles) lstore(stage ^ 1);
         __syncthreads();
     }
+}
+__device__ __forceinline__ void i8_tile_gemm(const void* A, const void* B, int ldk, int ktiles, int m0, int n0, char* smem, v16i (&acc)[2]) {
+    i8_tile_gemm_t<false>(A, nullptr, B, ldk, ktiles, m0, n0, smem, acc, acc);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -5255,6 +5271,116 @@ __device__ __forceinline__ void k_qkv_heads_body(const QkvHeadsParams& p, const 
     }
 }
 __global__ __launch_bounds__(512) void k_qkv_heads(QkvHeadsParams p) { k_qkv_heads_body(p, P4V_BIDX, P4V_GDIM); }
+
+// ------------------------------------------------------------------------------------------
+// k_lin_res: a Linear layer's int8 forward GEMM whose epilogue adds the residual and scatters the rows
+// ------------------------------------------------------------------------------------------
+// i8_tile_gemm_t over prepacked planes: A (TWIN, a post-GELU fc2: A and A2, the positive and the negative range as k_mlp_fc1 writes
+// them) [Mp][ldk], B = Q(W) [Np][ldk].  Per element, under contract(off) with the FMAs named -- EPI_FWD's expression AS THE FORWARD
+// SWEEPS COMPILE IT (k_sweep / k_sweep2 <., EPI_FWD>: without the twin's fmaf in between the compiler contracts `acc * s + bias` into
+// one v_fma_f32; with it the product, the fmaf and the add stay three roundings), then torch's `shortcut + x`:
+//   plain:  v = fmaf((float)acc, S1[vblock(n)], bias[n])
+//   TWIN:   v = fmaf((float)acc2, S2[vblock(n)], (float)acc * S1[vblock(n)]) + bias[n]
+//   out[dst(m)][n] = residual[dst(m)][n] + v
+// so `out` is the unfused chain's bit for bit (tests/test_hip_fused_residual.py holds both forms to it).
+// Row map: dst(m) = m, or (map 1) the token k_ln_pack's window map READS for row m -- window_reverse + roll(+shift) is the inverse
+// of roll(-shift) + window_partition:  m = ((b H/ws + wh) W/ws + ww) ws^2 + i ws + j  goes to token
+// (b, (wh ws + i + shift) mod H, (ww ws + j + shift) mod W).  The 128 destinations of the row tile are computed once, by the first
+// 128 threads before the k-loop, into 512 bytes of LDS behind the staging buffers (-1: a row >= M, which stores nothing).
+// Data path of the epilogue: after the k-loop a lane holds one column for 32 rows.  The fp32 tile goes through the staging LDS
+// (free behind the loop's last barrier) in two row halves -- accumulator i of every wave: 64 rows x 128 columns, rows RES_OROW
+// floats apart (34 816 bytes of the 40 960 / 61 440 staged) -- and leaves as 16-byte pieces: thread t owns floats 4 (t & 31) .. + 3
+// of the half's rows (t >> 5) + 16 j, so 32 lanes write the 512 contiguous bytes of one destination row.  The four residual pieces
+// of a half are loaded (nontemporal) BEFORE its LDS round trip, the sums leave as nontemporal stores.  N % 4 == 0 and 16-byte
+// aligned residual / out (the host refuses anything else): a piece lies inside [0, N) or outside it.
+struct LinResParams {
+    const void* A; const void* A2; const void* B;
+    int ldk, ktiles;
+    const float* S1; const float* S2; int s_cs, sb_div;   // s_a * s_w[block] per V block (k_scale_table); S2: the negative range's
+    const float* bias;                                     // [N] or nullptr
+    const float* residual; float* out;                     // [M][N] in destination-row order
+    int M, N;
+    int mtiles, ntiles;
+    int map, H, W, ws, shift;                              // map 1: the window map
+};
+static constexpr int RES_OROW = SW_BN + 8;    // floats per LDS row of the fp32 half tile: the lane halves' rows (4 apart) lie 32 banks apart
+
+template <bool TWIN>
+__global__ __launch_bounds__(512) void k_lin_res(LinResParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int STAGES = 2 * (TWIN ? 3 : 2) * SW_TILE_BYTES;
+    static_assert(64 * RES_OROW * (int)sizeof(float) <= STAGES, "the fp32 half tile must fit the staging buffers");
+    int* dst_tab = reinterpret_cast<int*>(smem + STAGES);                // [SW_BM]
+
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int wr = wid >> 2, wc = wid & 3;            // 2 x 4 waves, each 64 rows x 32 cols
+    const int g = lane >> 5, l31 = lane & 31;
+    const int nwg = p.mtiles * p.ntiles;
+    const int t = xcd_remap(blockIdx.x, nwg);
+    const int mt = t % p.mtiles, nt = t / p.mtiles;   // m fastest: tiles sharing a weight panel are adjacent
+    const int m0 = mt * SW_BM, n0 = nt * SW_BN;
+
+    if (tid < SW_BM) {                                // (visible behind the k-loop's barriers)
+        const int m = m0 + tid;
+        int d = m < p.M ? m : -1;
+        if (p.map == 1 && d >= 0) {
+            const int per = p.ws * p.ws, nww = p.W / p.ws, nwh = p.H / p.ws;
+            const int win = m / per;
+            const int r = m - win * per, i = r / p.ws, j = r - i * p.ws;
+            const int ww = win % nww, wh = (win / nww) % nwh;
+            const int b = win / (nww * nwh);
+            int h = wh * p.ws + i + p.shift, w = ww * p.ws + j + p.shift;
+            h -= h >= p.H ? p.H : 0; w -= w >= p.W ? p.W : 0;
+            d = (b * p.H + h) * p.W + w;
+        }
+        dst_tab[tid] = d;
+    }
+
+    const int n = n0 + wc * 32 + l31;
+    const bool ncol_ok = n < p.N;
+    const float bias_n = (p.bias && ncol_ok) ? p.bias[n] : 0.0f;
+    const int sb = min(n / p.sb_div, p.s_cs - 1);
+
+    v16i acc[2], acc2[2];
+    i8_tile_gemm_t<TWIN>(p.A, p.A2, p.B, p.ldk, p.ktiles, m0, n0, smem, acc, acc2);
+
+    const float s1 = p.S1 ? p.S1[sb] : 1.0f;
+    const float s2 = (TWIN && p.S2) ? p.S2[sb] : 1.0f;
+    float* o = reinterpret_cast<float*>(smem);
+    const int col_l = wc * 32 + l31;
+    const int prow = tid >> 5, pch = (tid & 31) * 4;  // the thread's pieces: rows prow + 16 j of the half, floats pch .. pch + 3
+    const bool pcol_ok = n0 + pch < p.N;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        v4f res[4];
+        long off[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int rl = prow + 16 * j;                                  // row of the half: wave row rl >> 5, its row rl & 31
+            const int d = dst_tab[(rl >> 5) * 64 + i * 32 + (rl & 31)];
+            off[j] = (d >= 0 && pcol_ok) ? (long)d * p.N + n0 + pch : -1;
+            if (off[j] >= 0) res[j] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p.residual + off[j]));
+        }
+        if (i) __syncthreads();                                            // the first half has been read
+        {
+#pragma clang fp contract(off)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                float v;
+                if constexpr (TWIN) v = fmaf((float)acc2[i][r], s2, (float)acc[i][r] * s1) + bias_n;
+                else v = fmaf((float)acc[i][r], s1, bias_n);
+                o[(wr * 32 + acc32_row(r, g)) * RES_OROW + col_l] = v;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (off[j] >= 0) {
+                const v4f v = *reinterpret_cast<const v4f*>(o + (prow + 16 * j) * RES_OROW + pch);
+                __builtin_nontemporal_store(res[j] + v, reinterpret_cast<v4f*>(p.out + off[j]));
+            }
+    }
+}
 
 // ------------------------------------------------------------------------------------------
 // Fused attention forward, first half (p4v_attn_quant_forward): matmul1's int8 GEMM, `* scale`, the softmax over the keys and

@@ -212,15 +212,29 @@ def linear_calibrate(**kw):
 
 
 def linear_quant_forward(*, weight, bias, x, w_interval, a_interval, w_bit, a_bit, n_V, n_H, n_a, postgelu=False, ln=None, window=None,
-                         want_norm=False, want_planes=False):
+                         want_norm=False, want_planes=False, residual=None, out=None):
     """quant_forward of a calibrated (post-GELU) Linear as one int8 MFMA GEMM (p4v_linear_quant_forward).
     `ln` (a dict of weight, bias, eps): x is the INPUT of a LayerNorm in front of the layer, fused into the layer's activation
     quantiser (p4v_ln_linear_quant_forward): k_ln_pack reads x once and writes the layer's int8 row plane; the
     fp32 LayerNorm output is never written.  With it, `window` = (H, W, ws, shift) gathers the rows as SwinBlock.forward's
     roll(-shift) + window_partition orders them (x [B][H * W][C]; out comes in that order), `want_norm` also returns y (the fp32
-    LayerNorm output the plane was quantised from, in out's row order) and `want_planes` the padded int8 plane (for the tests)."""
+    LayerNorm output the plane was quantised from, in out's row order) and `want_planes` the padded int8 plane (for the tests).
+    `residual` ([B][tokens][out_features] fp32, contiguous): the call returns residual + layer(x), the add made in the GEMM's epilogue
+    (p4v_linear_res_quant_forward, DESIGN.md s5.15: k_lin_res; the layer's own fp32 output is never written).  With it `window` =
+    (H, W, ws, shift) is the OUTPUT map: x's rows are in window order, and row r goes where SwinBlock.forward's window_reverse +
+    roll(+shift) puts it (residual and the result in token order).  `out` (optional): the destination, shaped like `residual`."""
+    if residual is not None:
+        if ln is not None:
+            raise ValueError("linear_quant_forward: ln= and residual= do not go together (the fused MLP takes both: mlp_quant_forward)")
+        if want_norm or want_planes:
+            raise ValueError("linear_quant_forward: want_norm and want_planes belong to the fused LayerNorm (ln=)")
+        layer = dict(weight=weight, bias=bias, w_interval=w_interval, a_interval=a_interval, w_bit=w_bit, a_bit=a_bit, n_V=n_V, n_H=n_H,
+                     n_a=n_a, postgelu=postgelu)
+        return _linear_res_forward(x, layer, residual, window, out)
+    if out is not None:
+        raise ValueError("linear_quant_forward: out belongs to the fused residual (residual=)")
     if ln is None and (window is not None or want_norm or want_planes):
-        raise ValueError("linear_quant_forward: window, want_norm and want_planes belong to the fused LayerNorm (ln=)")
+        raise ValueError("linear_quant_forward: window belongs to ln= or residual=, want_norm and want_planes to the fused LayerNorm (ln=)")
     if ln is not None:
         layer = dict(weight=weight, bias=bias, w_interval=w_interval, a_interval=a_interval, w_bit=w_bit, a_bit=a_bit, n_V=n_V, n_H=n_H,
                      n_a=n_a, postgelu=postgelu)
@@ -281,7 +295,7 @@ def _fused_forward(kind, d, tensors, dev, res, want_planes, z=None):
     return res[0] if len(res) == 1 else res
 
 
-def mlp_quant_forward(*, x, fc1, fc2, want_hidden=False, want_planes=False, ln=None, want_norm=False):
+def mlp_quant_forward(*, x, fc1, fc2, want_hidden=False, want_planes=False, ln=None, want_norm=False, residual=None, out=None):
     """fc2(GELU(fc1(x))) of two calibrated Linear layers in quant_forward, fused (p4v_mlp_quant_forward): fc1's int8 GEMM ends
     in the exact GELU and fc2's activation quantiser and writes fc2's int8 plane(s); no fp32 hidden tensor in between.
     `fc1` / `fc2`: dicts with weight, bias (or None), w_interval, a_interval (fc2: the positive range), w_bit, a_bit, n_V and
@@ -290,9 +304,18 @@ def mlp_quant_forward(*, x, fc1, fc2, want_hidden=False, want_planes=False, ln=N
     workspace (a tuple of one or two [rows_padded][cols_padded] tensors; for the tests).
     `ln` (a dict of weight, bias, eps): x is the input of a LayerNorm in front of fc1, and k_ln_pack writes fc1's row plane from
     it (p4v_ln_mlp_quant_forward).  With it the call returns out, then -- as asked for -- y (`want_norm`),
-    hidden, and for `want_planes` FC1's padded int8 row plane (one tensor)."""
+    hidden, and for `want_planes` FC1's padded int8 row plane (one tensor).
+    `residual` (shaped like the result, fp32, contiguous; with `ln` normally x itself): the call returns residual + fc2(...), the add
+    made in fc2's GEMM epilogue (p4v_mlp_res_quant_forward, DESIGN.md s5.15: k_lin_res on fc1's planes), with or without `ln`;
+    `out` (optional): the destination.  Returns out, then y and hidden as asked for."""
     if ln is None and want_norm:
         raise ValueError("mlp_quant_forward: want_norm belongs to the fused LayerNorm (ln=)")
+    if residual is not None:
+        if want_planes:
+            raise ValueError("mlp_quant_forward: want_planes is not offered with residual=")
+        return _mlp_res_forward(x, ln, fc1, fc2, residual, out, want_norm, want_hidden)
+    if out is not None:
+        raise ValueError("mlp_quant_forward: out belongs to the fused residual (residual=)")
     if ln is not None:
         return _ln_mlp_forward(x, ln, fc1, fc2, want_norm, want_hidden, want_planes)
     dev = device_of(x, fc1["weight"])
@@ -371,6 +394,66 @@ def _ln_mlp_forward(x, ln, fc1, fc2, want_norm, want_hidden, want_planes):
     hidden = torch.empty(x.shape[:-1] + (w1.shape[0],), dtype=torch.float32, device=dev) if want_hidden else None
     layers = dict(w1=w1, w2=w2, bias1=b1, bias2=b2, w1_interval=w1_iv, a1_interval=a1_iv, w2_interval=w2_iv, a2_interval=a2_iv)
     return _ln_call("ln_mlp", x, ln, window=None, d=d, layers=layers, outs=dict(out=out, y_out=y, hidden=hidden), want_planes=want_planes)
+
+
+def _res_pair(residual, out, shape, dev, who):
+    """the residual on the device and its destination: both fp32, contiguous, of the result's `shape`"""
+    residual = to_dev(residual, dev)
+    out = torch.empty(shape, dtype=torch.float32, device=dev) if out is None else out
+    for name, t in (("residual", residual), ("out", out)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape) or t.device != residual.device:
+            raise ValueError(f"{who}: {name} must be a contiguous fp32 tensor of shape {tuple(shape)} on the layer's device")
+    return residual, out
+
+
+def _res_call(kind, descs, Rec, tensors, dev):
+    """The tail of the two residual-fused forwards (`kind`: linear_res / mlp_res): p4v_<kind>_workspace_bytes(*descs), the record of
+    device pointers, the checked call."""
+    lib = _lib.load()
+    refs = [C.byref(d) if d is not None else None for d in descs]
+    need = getattr(lib, f"p4v_{kind}_workspace_bytes")(*refs)
+    if need == 0:
+        _lib.check(-2, f"p4v_{kind}_workspace_bytes")
+    ws = workspace(dev, need)
+    rec = Rec(**{k: ptr(t) for k, t in tensors.items()}, ws=ptr(ws), ws_bytes=ws.numel())
+    with torch.cuda.device(dev):
+        rc = getattr(lib, f"p4v_{kind}_quant_forward")(*refs, C.byref(rec), stream_ptr(dev))
+    _lib.check(rc, f"p4v_{kind}_quant_forward")
+
+
+def _linear_res_forward(x, layer, residual, window, out):
+    """linear_quant_forward with `residual`"""
+    dev = device_of(x, layer["weight"])
+    x = to_dev(x, dev).contiguous()
+    batch, K = x.shape[0], x.shape[-1]
+    w, b, w_iv, a_iv = _ln_layer(layer, dev)
+    d = _mlp_layer_desc(batch, x.numel() // (batch * K), layer)
+    residual, out = _res_pair(residual, out, tuple(residual.shape), dev, "linear_quant_forward")
+    if residual.numel() != x.numel() // K * w.shape[0]:
+        raise ValueError("linear_quant_forward: residual must hold one row of out_features per row of x")
+    r = _lib.ResDesc(*((0, 0, 0, 0, 0) if window is None else (1,) + tuple(int(v) for v in window)), 0)
+    _res_call("linear_res", (d, r), _lib.LinearResTensors, dict(x=x, w=w, bias=b, w_interval=w_iv, a_interval=a_iv, residual=residual, out=out), dev)
+    return out
+
+
+def _mlp_res_forward(x, ln, fc1, fc2, residual, out, want_norm, want_hidden):
+    """mlp_quant_forward with `residual`, with or without `ln`"""
+    dev = device_of(x, fc1["weight"])
+    x = to_dev(x, dev).contiguous()
+    batch, K = x.shape[0], x.shape[-1]
+    tokens = x.numel() // (batch * K)
+    (w1, b1, w1_iv, a1_iv), (w2, b2, w2_iv, a2_iv) = _ln_layer(fc1, dev), _ln_layer(fc2, dev)
+    d = _lib.MlpDesc(_mlp_layer_desc(batch, tokens, fc1), _mlp_layer_desc(batch, tokens, fc2))
+    residual, out = _res_pair(residual, out, x.shape[:-1] + (w2.shape[0],), dev, "mlp_quant_forward")
+    n = None if ln is None else _lib.LnDesc(x.numel() // K, K, float(ln["eps"]), 0, 0, 0, 0, 0, 0)
+    gamma, beta = (None, None) if ln is None else (to_dev(ln[k], dev).contiguous() for k in ("weight", "bias"))
+    y = torch.empty_like(x) if want_norm else None
+    hidden = torch.empty(x.shape[:-1] + (w1.shape[0],), dtype=torch.float32, device=dev) if want_hidden else None
+    _res_call("mlp_res", (n, d), _lib.MlpResTensors,
+              dict(x=x, gamma=gamma, beta=beta, w1=w1, w2=w2, bias1=b1, bias2=b2, w1_interval=w1_iv, a1_interval=a1_iv, w2_interval=w2_iv,
+                   a2_interval=a2_iv, residual=residual, out=out, y_out=y, hidden=hidden), dev)
+    res = tuple(t for t in (out, y, hidden) if t is not None)
+    return res[0] if len(res) == 1 else res
 
 
 def _attn_matmul_desc(d, A_shape, A_stride, B, side, what, who="attn_quant_forward"):

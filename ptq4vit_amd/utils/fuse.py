@@ -205,6 +205,11 @@ def _fused_attention_forward(self, x):
 
 def _attention_tail(self, qkv_out, args):
     """models.Attention.forward behind `self.qkv(x)`, with matmul1 ... matmul2 as one engine call (`qkv_out` [B][N][3 C])"""
+    return self.proj_drop(self.proj(_attention_core(self, qkv_out, args)))
+
+
+def _attention_core(self, qkv_out, args):
+    """... up to proj's input [B][N][C]: proj is the caller's"""
     B, N, C = qkv_out.shape[0], qkv_out.shape[1], qkv_out.shape[2] // 3
     H = self.num_heads
     qkv = qkv_out.reshape(B, N, 3, H, C // H).permute(2, 0, 3, 1, 4)
@@ -213,7 +218,7 @@ def _attention_tail(self, qkv_out, args):
     q, k, v = qkv.unbind(0)
     out = engine.attn_quant_forward(q=q, kT=k.transpose(-2, -1), v=v, scale=self.scale, qk=args[0], pv=args[1],
                                     one_kernel=self.__dict__.get(_ONE_KERNEL, False))
-    return self.proj_drop(self.proj(out.transpose(1, 2).reshape(B, N, C)))
+    return out.transpose(1, 2).reshape(B, N, C)
 
 
 def fuse_attention(net, one_kernel=False):
@@ -318,6 +323,11 @@ def _fused_window_attention_forward(self, x, mask=None):
 
 def _window_attention_tail(self, qkv_out, args, mask):
     """models.WindowAttention.forward behind `self.qkv(x)`, with matmul1 ... matmul2 as one engine call (`qkv_out` [B_][N][3 C])"""
+    return self.proj_drop(self.proj(_window_attention_core(self, qkv_out, args, mask)))
+
+
+def _window_attention_core(self, qkv_out, args, mask):
+    """... up to proj's input [B_][N][C]: proj is the caller's"""
     B_, N, C = qkv_out.shape[0], qkv_out.shape[1], qkv_out.shape[2] // 3
     H = self.num_heads
     qkv = qkv_out.reshape(B_, N, 3, H, C // H).permute(2, 0, 3, 1, 4)
@@ -327,7 +337,7 @@ def _window_attention_tail(self, qkv_out, args, mask):
     bias = self.relative_position_bias_table[self.relative_position_index.view(-1)].view(n, n, -1)
     out = engine.window_attn_quant_forward(q=q, kT=k.transpose(-2, -1), v=v, bias=bias.permute(2, 0, 1).contiguous(), mask=mask,
                                            qk=args[0], pv=args[1], one_kernel=self.__dict__.get(_WONE_KERNEL, False))
-    return self.proj_drop(self.proj(out.transpose(1, 2).reshape(B_, N, C)))
+    return out.transpose(1, 2).reshape(B_, N, C)
 
 
 def fuse_window_attention(net, one_kernel=False):
@@ -358,6 +368,7 @@ def unfuse_window_attention(net):
 # fused forward goes on behind `self.qkv(x)`.  A ViT container patched by fuse_qkv_attention keeps norm1 in torch.  Every other
 # state runs the side as the block's own forward does.  Its own saved-forward attribute: composes with the other fuse_* in any order.
 _ORIG_NORM = "_p4v_unfused_norm_forward"
+_RESIDUAL = "_p4v_fuse_residual"          # the patched block's choice: proj / fc2 add the residual in their GEMM epilogue
 
 
 def norm_fusable(m):
@@ -379,22 +390,52 @@ def _installed(m):
     return getattr(m.__dict__.get("forward"), "__func__", None)
 
 
+def _container_args(block, x):
+    """(the attention container's input -- its shape is all that is asked about --, its (matmul1, matmul2) keywords) if the container
+    carries our fused forward and would take it on the block's input `x`, else (None, None)."""
+    attn = getattr(block, "attn", None)
+    if attn is None or _hooked(attn) or not (torch.is_tensor(x) and x.dim() == 3):
+        return None, None
+    if isinstance(block, models.SwinBlock):
+        (H, W), ws = block.input_resolution, block.window_size
+        if _installed(attn) is not _fused_window_attention_forward or x.shape[1] != H * W or H % ws or W % ws or not 0 <= block.shift_size < ws:
+            return None, None
+        xin = x.reshape(-1, ws * ws, x.shape[2])
+        return xin, _wattn_args(attn, xin, block.attn_mask)
+    if _installed(attn) is not _fused_attention_forward:
+        return None, None
+    return x, _attn_args(attn, x)
+
+
+def _proj_res_args(block, x):
+    """(proj's engine keywords, the container's (matmul1, matmul2) keywords) if the patched forward of `block` lets proj add the
+    residual on `x` (fuse_norm(net, residual=True)), else None: the container carries our fused forward and would
+    take it; proj is live on its int8 path with n_H = n_a = 1, unhooked, no post-GELU layer, C -> C with C % 4 == 0; proj_drop is
+    inactive and unhooked."""
+    if not block.__dict__.get(_RESIDUAL, False) or not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32):
+        return None
+    xin, args = _container_args(block, x)
+    if args is None:
+        return None
+    attn = block.attn
+    proj, C = attn.proj, x.shape[-1]
+    if not (isinstance(proj, PTQSLQuantLinear) and _live(proj) and proj._int8_ready(xin)) or _recording(x, proj):
+        return None
+    if not _inactive_dropout(attn.proj_drop) or _hooked(attn.proj_drop) or C % 4 or proj.in_features != C or proj.out_features != C:
+        return None
+    lin = proj._int8_args()
+    if lin["postgelu"] or lin["n_H"] != 1 or lin["n_a"] != 1:
+        return None
+    return lin, args
+
+
 def _norm1_args(block, x):
     """(qkv's engine keywords, the container's (matmul1, matmul2) keywords) if the patched forward of `block` fuses norm1 into
     qkv's quantiser on `x`, else None."""
     attn = getattr(block, "attn", None)
-    if attn is None or not _norm_ok(block.norm1, x) or _hooked(attn):
+    if attn is None or not _norm_ok(block.norm1, x):
         return None
-    if isinstance(block, models.SwinBlock):
-        (H, W), ws = block.input_resolution, block.window_size
-        if _installed(attn) is not _fused_window_attention_forward or x.shape[1] != H * W or H % ws or W % ws or not 0 <= block.shift_size < ws:
-            return None
-        xin = x.reshape(-1, ws * ws, x.shape[2])                # (the container's input: its shape is all that is asked about)
-        args = _wattn_args(attn, xin, block.attn_mask)
-    else:
-        if _installed(attn) is not _fused_attention_forward:
-            return None
-        xin, args = x, _attn_args(attn, x)
+    xin, args = _container_args(block, x)
     qkv = attn.qkv
     if args is None or not (isinstance(qkv, PTQSLQuantLinear) and _live(qkv) and qkv._int8_ready(xin)):
         return None
@@ -422,20 +463,34 @@ def takes_fused_norm_path(block, x, side=None):
 
 
 def _mlp_side(self, x):
+    """x + mlp(norm2(x)), the block's second half"""
+    res = self.__dict__.get(_RESIDUAL, False) and x.shape[-1] % 4 == 0
     args = _norm2_args(self, x)
-    if args is None:
-        return self.mlp(self.norm2(x))
-    return engine.mlp_quant_forward(x=x, ln=_ln_of(self.norm2), fc1=args[0], fc2=args[1])
+    if args is not None:
+        if res:
+            return engine.mlp_quant_forward(x=x, ln=_ln_of(self.norm2), fc1=args[0], fc2=args[1], residual=x.contiguous())
+        return x + engine.mlp_quant_forward(x=x, ln=_ln_of(self.norm2), fc1=args[0], fc2=args[1])
+    mlp = getattr(self, "mlp", None)
+    if res and mlp is not None and _ORIG in mlp.__dict__ and not _hooked(mlp) and x.is_cuda and x.dtype == torch.float32:
+        y = self.norm2(x)
+        args = _mlp_args(mlp, y)
+        if args is not None:
+            return engine.mlp_quant_forward(x=y, fc1=args[0], fc2=args[1], residual=x.contiguous())
+        return x + mlp(y)
+    return x + self.mlp(self.norm2(x))
 
 
 def _fused_norm_block_forward(self, x):
     # models.Block.forward
-    a = _norm1_args(self, x)
-    if a is None:
+    a, p = _norm1_args(self, x), _proj_res_args(self, x)
+    if p is not None:
+        qkv = engine.linear_quant_forward(x=x, ln=_ln_of(self.norm1), **a[0]) if a is not None else self.attn.qkv(self.norm1(x))
+        x = engine.linear_quant_forward(x=_attention_core(self.attn, qkv, p[1]), residual=x.contiguous(), **p[0])
+    elif a is None:
         x = x + self.attn(self.norm1(x))
     else:
         x = x + _attention_tail(self.attn, engine.linear_quant_forward(x=x, ln=_ln_of(self.norm1), **a[0]), a[1])
-    return x + _mlp_side(self, x)
+    return _mlp_side(self, x)
 
 
 def _fused_norm_swin_block_forward(self, x):
@@ -444,30 +499,51 @@ def _fused_norm_swin_block_forward(self, x):
     B, L, C = x.shape
     shortcut = x
     ws = self.window_size
-    a = _norm1_args(self, x)
+    a, p = _norm1_args(self, x), _proj_res_args(self, x)
     if a is None:
         x = self.norm1(x).view(B, H, W, C)
         if self.shift_size > 0:
             x = torch.roll(x, shifts=(-self.shift_size, -self.shift_size), dims=(1, 2))
         xw = models.window_partition(x, ws).view(-1, ws * ws, C)
-        aw = self.attn(xw, mask=self.attn_mask).view(-1, ws, ws, C)
+        qkv = self.attn.qkv(xw) if p is not None else None
     else:
         qkv = engine.linear_quant_forward(x=x, ln=_ln_of(self.norm1), window=(H, W, ws, self.shift_size), **a[0])
-        aw = _window_attention_tail(self.attn, qkv.view(-1, ws * ws, qkv.shape[-1]), a[1], self.attn_mask).view(-1, ws, ws, C)
+        qkv = qkv.view(-1, ws * ws, qkv.shape[-1])
+    if p is not None:
+        # proj scatters its rows through window_reverse + roll(+shift) and adds the shortcut: k_lin_res's row map
+        core = _window_attention_core(self.attn, qkv, p[1], self.attn_mask)
+        x = engine.linear_quant_forward(x=core, residual=shortcut.contiguous(), window=(H, W, ws, self.shift_size), **p[0])
+        return _mlp_side(self, x)
+    if a is None:
+        aw = self.attn(xw, mask=self.attn_mask).view(-1, ws, ws, C)
+    else:
+        aw = _window_attention_tail(self.attn, qkv, a[1], self.attn_mask).view(-1, ws, ws, C)
     x = models.window_reverse(aw, ws, H, W)
     if self.shift_size > 0:
         x = torch.roll(x, shifts=(self.shift_size, self.shift_size), dims=(1, 2))
     x = shortcut + x.view(B, H * W, C)
-    return x + _mlp_side(self, x)
+    return _mlp_side(self, x)
 
 
-def fuse_norm(net):
+def fuse_norm(net, residual=False):
     """Patch the forward of every Block / SwinBlock of `net`; returns their names.  Idempotent.  What a side fuses is decided per
-    call (see above): without fuse_mlp / fuse_window_attention / fuse_attention on the block's containers nothing changes."""
+    call (see above): without fuse_mlp / fuse_window_attention / fuse_attention on the block's containers nothing changes.
+    `residual`: the patched blocks also let proj and fc2 add the residual -- and, on Swin, proj scatter its rows through
+    window_reverse and the back-roll -- in their GEMM epilogue (engine.linear_quant_forward / mlp_quant_forward with residual=,
+    DESIGN.md s5.15), per side and per call, whether or not that side's LayerNorm fused: the attention side where the container
+    carries our fused forward and would take it, proj is live on its int8 path with n_H = n_a = 1, unhooked, proj_drop inactive and
+    C % 4 == 0; the MLP side where the fused MLP chain would run.  Every other state runs the side as before.  The flag is stored
+    on the blocks (the later call decides) and changes no bit of what the net returns."""
     names = _patch(net, lambda m: isinstance(m, models.SwinBlock), _ORIG_NORM, _fused_norm_swin_block_forward)
-    return sorted(names + _patch(net, lambda m: isinstance(m, models.Block), _ORIG_NORM, _fused_norm_block_forward))
+    names = sorted(names + _patch(net, lambda m: isinstance(m, models.Block), _ORIG_NORM, _fused_norm_block_forward))
+    for name, m in net.named_modules():
+        if name in names:
+            m.__dict__[_RESIDUAL] = bool(residual)
+    return names
 
 
 def unfuse_norm(net):
     """Undo fuse_norm: every patched block gets its original forward back; returns their names.  Idempotent."""
+    for m in net.modules():
+        m.__dict__.pop(_RESIDUAL, None)
     return _unfuse(net, _ORIG_NORM)

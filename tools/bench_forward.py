@@ -107,6 +107,8 @@ def main():
     ap.add_argument("--fuse-norm", action="store_true",
                     help="also time utils/fuse.py::fuse_norm on top of fuse_attention / fuse_window_attention (one_kernel with --one-kernel; with --fused: "
                          "and the fused MLPs), next to the same net without it (norm_base)")
+    ap.add_argument("--fuse-residual", action="store_true",
+                    help="with --fuse-norm: also time fuse_norm(net, residual=True) -- proj / fc2 add the residual in their GEMM epilogue -- next to fused_norm")
     ap.add_argument("--json", default=None, help="write the result to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -158,10 +160,12 @@ def main():
         if a.fuse_norm:                    # ("norm", attn): fuse_norm on top; "attn1": fuse_attention / fuse_window_attention, one kernel
             base = "attn1" if a.one_kernel else True
             variants += [("norm_base", a.fused, base), ("fused_norm", a.fused, ("norm", base))]
+            if a.fuse_residual:
+                variants.append(("fused_residual", a.fused, ("res", base)))
 
         def setup(mlp, attn):
             fuse.unfuse_norm(net)
-            norm, attn = (True, attn[1]) if isinstance(attn, tuple) else (False, attn)
+            norm, attn = (attn[0], attn[1]) if isinstance(attn, tuple) else (False, attn)
             fuse.unfuse_mlp(net)
             fuse.unfuse_attention(net)
             fuse.unfuse_window_attention(net)
@@ -171,7 +175,7 @@ def main():
             if attn == "attn1":
                 fuse_attn = lambda n: fuse.fuse_attention(n, one_kernel=True)
             if norm:
-                fuse.fuse_norm(net)
+                fuse.fuse_norm(net, residual=norm == "res")
             return (len(fuse.fuse_mlp(net)) if mlp else 0,
                     len(fuse_attn(net)) + len(fuse.fuse_window_attention(net, one_kernel=attn in ("qkv1", "attn1"))) if attn else 0)
 
@@ -198,10 +202,12 @@ def main():
                 print(f"  one-kernel attention core ({n_attn}{' + MLPs' if a.fused else ''}) {t_v * 1e3:.2f} ms: x{med[base_key] / t_v:.3f} "
                       f"over {base_key} ({(med[base_key] - t_v) * 1e3:+.3f} ms), x{t_u / t_v:.3f} over unfused; logit rel diff vs unfused {rel:.3e}")
                 res.update({base_key + "_over_fused_qkv_one": med[base_key] / t_v, base_key + "_minus_fused_qkv_one_ms": (med[base_key] - t_v) * 1e3})
-            elif key in ("norm_base", "fused_norm"):
-                base_key = "norm_base" if key == "fused_norm" else "unfused"
+            elif key in ("norm_base", "fused_norm", "fused_residual"):
+                base_key = "fused_norm" if key == "fused_residual" else "norm_base" if key == "fused_norm" else "unfused"
                 print(f"  {key} ({n_attn} attention containers{' + MLPs' if a.fused else ''}) {t_v * 1e3:.2f} ms: x{med[base_key] / t_v:.3f} over {base_key} "
                       f"({(med[base_key] - t_v) * 1e3:+.3f} ms); logit rel diff vs unfused {rel:.3e}")
+                if key == "fused_residual":
+                    res.update({"fused_norm_over_fused_residual": med[base_key] / t_v, "fused_norm_minus_fused_residual_ms": (med[base_key] - t_v) * 1e3})
                 if key == "fused_norm":
                     res.update({"norm_base_over_fused_norm": med[base_key] / t_v, "norm_base_minus_fused_norm_ms": (med[base_key] - t_v) * 1e3})
             elif key == "fused_qkv":

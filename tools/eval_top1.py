@@ -40,7 +40,7 @@ def set_bits(cfg, bits):
 
 
 def evaluate(model, imagenet, weights=None, config="PTQ4ViT", bits=8, calib=32, calib_seed=3, batch=128, max_val=None,
-             workers=0, save_intervals=None, device="cuda", quiet=False, fuse_mlp=False, fuse_attn=False, fuse_qkv=False, one_kernel=False, fuse_norm=False):
+             workers=0, save_intervals=None, device="cuda", quiet=False, fuse_mlp=False, fuse_attn=False, fuse_qkv=False, one_kernel=False, fuse_norm=False, fuse_residual=False):
     """Returns the result dict (see the module docstring).  `weights=None` keeps the seeded random initialisation (tests)."""
     import contextlib
     import importlib
@@ -96,7 +96,7 @@ def evaluate(model, imagenet, weights=None, config="PTQ4ViT", bits=8, calib=32, 
         fused_attn = _fuse_qkv(net, one_kernel=one_kernel) or fused_attn
     if fuse_norm:                              # opt-in: norm1 / norm2 write the int8 planes of qkv / fc1 (on top of --fuse-attn / --fuse-mlp)
         from ptq4vit_amd.utils.fuse import fuse_norm as _fuse_norm
-        _fuse_norm(net)
+        _fuse_norm(net, residual=fuse_residual)
     t0 = time.time()
     quant = datasets.test_classification(net, test_loader, max_iteration=max_it, description=None if quiet else f"{model} W{bits}A{bits}")
     t_q = time.time() - t0
@@ -127,11 +127,12 @@ def main(argv=None):
     ap.add_argument("--fuse-qkv", action="store_true", help="evaluate with the qkv layer fused into the attention chain (utils/fuse.py::fuse_qkv_attention)")
     ap.add_argument("--one-kernel", action="store_true", help="with --fuse-attn / --fuse-qkv: the attention core as one kernel (k_attn_qkpv; window attention: k_wattn_qkpv)")
     ap.add_argument("--fuse-norm", action="store_true", help="with --fuse-mlp / --fuse-attn: LayerNorm fused into fc1's / qkv's quantiser (utils/fuse.py::fuse_norm)")
+    ap.add_argument("--fuse-residual", action="store_true", help="with --fuse-norm: proj / fc2 add the residual in their GEMM epilogue (fuse_norm(net, residual=True))")
     a = ap.parse_args(argv)
     import ptq4vit_amd
     ptq4vit_amd.configure_runtime()          # GPU_MAX_HW_QUEUES for the search streams, before the first GPU call
     res = evaluate(a.model, a.imagenet, a.weights, a.config, a.bits, a.calib, a.calib_seed, a.batch, a.max_val, a.workers,
-                   a.save_intervals, fuse_mlp=a.fuse_mlp, fuse_attn=a.fuse_attn, fuse_qkv=a.fuse_qkv, one_kernel=a.one_kernel, fuse_norm=a.fuse_norm)
+                   a.save_intervals, fuse_mlp=a.fuse_mlp, fuse_attn=a.fuse_attn, fuse_qkv=a.fuse_qkv, one_kernel=a.one_kernel, fuse_norm=a.fuse_norm, fuse_residual=a.fuse_residual)
     line = json.dumps(res)
     print(line)
     if a.json:
