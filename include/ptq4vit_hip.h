@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define P4V_VERSION 149 /* 0.1.4.9: + the fused block output: p4v_linear_res_quant_forward, p4v_mlp_res_quant_forward, proj / fc2 add the residual in the GEMM epilogue */
+#define P4V_VERSION 150 /* 0.1.5.0: + proj behind the one-kernel attention cores: p4v_attn_proj_quant_forward, p4v_wattn_proj_quant_forward write proj's int8 row plane */
 /* 0.1.4.8: + the fused LayerNorm producer: p4v_ln_linear_quant_forward, p4v_ln_mlp_quant_forward, LayerNorm writes the Linear's int8 row plane */
 /* 0.1.4.6: + P4V_ATTN_ONE_KERNEL (the fused attention core as one kernel: p v from the probabilities in registers) */
 /* 0.1.4.5: + p4v_qkv_attn_* (the fused int8 qkv forward: the qkv GEMM writes the attention operand planes) */
@@ -722,6 +722,54 @@ size_t p4v_mlp_res_workspace_bytes(const p4v_ln_desc* ln, const p4v_mlp_desc* de
 
 int p4v_mlp_res_quant_forward(const p4v_ln_desc* ln, const p4v_mlp_desc* desc, const p4v_mlp_res_tensors* tensors, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Attention core + proj (opt-in, network level): proj(merge_heads(attention(q, k^T, v))) [+ residual] with the attention output
+ * never written in fp32.  With the one-kernel core asked for (P4V_ATTN_ONE_KERNEL / P4V_WATTN_ONE_KERNEL), an instance for the shape
+ * and Dv = pv.N % 4 == 0, the core's epilogue (k_attn_qkpv_plane / k_wattn_qkpv_plane) quantises its output o -- computed exactly as
+ * p4v_attn_quant_forward / p4v_wattn_quant_forward store it -- with proj's activation quantiser, clamp(rint(o / a_interval)) in IEEE
+ * arithmetic, and writes proj's int8 row plane [Mp][roundup64(heads Dv)] at row (z / heads) M + m, column (z % heads) Dv + d: the
+ * fp32 output [batch*heads][M][Dv], the transpose copy that merges the heads and the pack of that copy do not exist.  The plane
+ * equals, byte for byte, what p4v_linear_quant_forward packs from the head-merged output of the attention call; `out` equals the
+ * unfused chain's bit for bit.  Everything else (no instance, the bit clear) runs the attention call of today into scratch, a
+ * head-merging copy and proj's own pack: the same bits, the request is not a condition.
+ * `res` (may be NULL): out = residual + proj(...) through p4v_res_desc's row map, made by k_lin_res as in
+ * p4v_linear_res_quant_forward.
+ * Envelope: that of the attention call on `desc`; proj with int8 planes, n_H = n_a = 1, not twin_postgelu, in_features = heads Dv,
+ * batch * tokens = qk.batch * M; with `res` the envelope of p4v_linear_res_quant_forward.  Anything else is P4V_ERR_UNSUPPORTED /
+ * P4V_ERR_INVALID before the first launch.
+ * The tensors of the attention call as there (rel_bias, mask: the window call's bias and mask; ignored by the plain call); w, bias,
+ * w_interval, a_interval: proj's, as for p4v_linear_quant_forward; residual: with `res` only; out [batch * tokens][out_features];
+ * core: optional (may be NULL) [batch*heads][M][Dv] fp32, the values the plane was quantised from; probs: optional; ws, ws_bytes:
+ * the workspace and its size -- the workspace contract above holds with p4v_attn_proj_workspace_bytes /
+ * p4v_wattn_proj_workspace_bytes; a smaller ws_bytes is refused before any launch.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct p4v_attn_proj_tensors {
+    const float *q, *kT, *v;
+    const float* rel_bias;             /* the window call only */
+    const float* mask;                 /* the window call only, optional */
+    const float *qk_A_interval, *qk_B_interval, *pv_A_interval, *pv_B_interval;
+    const float* split;                /* sos only */
+    const float* w;
+    const float* bias;                 /* NULL without a bias (proj.has_bias = 0) */
+    const float *w_interval, *a_interval;
+    const float* residual;             /* with `res` only */
+    float* out;
+    float* core;                       /* optional */
+    float* probs;                      /* optional */
+    void* ws;
+    size_t ws_bytes;
+} p4v_attn_proj_tensors;
+
+size_t p4v_attn_proj_workspace_bytes(const p4v_attn_desc* desc, const p4v_linear_desc* proj, const p4v_res_desc* res);
+
+int p4v_attn_proj_quant_forward(const p4v_attn_desc* desc, const p4v_linear_desc* proj, const p4v_res_desc* res, const p4v_attn_proj_tensors* tensors,
+                                void* stream);
+
+size_t p4v_wattn_proj_workspace_bytes(const p4v_wattn_desc* desc, const p4v_linear_desc* proj, const p4v_res_desc* res);
+
+int p4v_wattn_proj_quant_forward(const p4v_wattn_desc* desc, const p4v_linear_desc* proj, const p4v_res_desc* res, const p4v_attn_proj_tensors* tensors,
+                                 void* stream);
+
 /* d_A_interval: [heads] (sos: [1]); d_B_interval: [heads]; d_split: [1] (sos only); d_out: [batch*heads][M][N] */
 int p4v_matmul_quant_forward(const p4v_matmul_desc* desc, const float* d_A, const float* d_B, const float* d_A_interval,
                              const float* d_B_interval, const float* d_split, float* d_out, void* d_workspace,
@@ -769,7 +817,8 @@ typedef struct p4v_launch_record {
                          0 generic int8 k_sweep | 1 generic fp32 k_sweep | 11 k_sos_split (fp32) | 12 k_bound (stage B1) |
                          13 k_slice_b2 / 14 k_slice_a (stage A of a MatMul B / A search) | 15 k_sweep_seg | 16 k_mlp_fc1 |
                          17 k_attn_qk | 18 k_qkv_heads | 19 k_attn_qkpv | 20 k_wattn_qkpv | 21 k_ln_pack (no MACs: alg_bytes = x + gamma +
-                         beta + the int8 plane + y_out where given) | 22 k_lin_res (alg_bytes = the int8 planes + the residual + out) */
+                         beta + the int8 plane + y_out where given) | 22 k_lin_res (alg_bytes = the int8 planes + the residual + out) |
+                         23 k_attn_qkpv_plane | 24 k_wattn_qkpv_plane (alg_bytes: the live rows of proj's plane in place of the fp32 out) */
     int32_t stage;    /* 0 full sweep (pass not pruned) | 1 stage A (all candidates, sample slice) | 2 stage B1 (the bound) |
                          3 stage B2 (survivors, all samples) | 4 stage A2 (survivors of a loose first slice on the larger second one) */
     int32_t grid_x, grid_z;   /* a grouped launch (p4v_calibrate_group): grid_x = its flat grid (all members' blocks, each member padded to a

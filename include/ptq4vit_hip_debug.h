@@ -96,6 +96,9 @@ int p4v_debug_qkv_planes(uint64_t info[9]);
  * (the Linear's / fc1's): info[0] = its byte offset from ws, info[2] x info[3] = padded rows x row length (row-major int8),
  * info[1] = info[4] = 0.  The plane outlives the call.  (fc2's planes of the MLP call: p4v_debug_mlp_planes.) */
 int p4v_debug_ln_planes(uint64_t info[5]);
+/* Where the calling thread's last p4v_attn_proj_quant_forward / p4v_wattn_proj_quant_forward left proj's row plane (written by the
+ * plane instance of the one-kernel core, or packed from the head-merged copy): the layout of p4v_debug_ln_planes. */
+int p4v_debug_proj_planes(uint64_t info[5]);
 /* ONE sweep of the split-of-softmax split search (k_sos_split + k_finish) on the operands of `desc`, over the first n_cands of
  * the 20 splits: d_scores [n_cands] receives the score table, entries outside [c_lo, c_hi) as k_finish leaves them (-inf).
  * c_lo < 0: no candidate range.  known_cands: what the caller tells the sweep about the number of candidates in the range

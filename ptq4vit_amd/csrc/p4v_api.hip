@@ -3213,6 +3213,7 @@ int launch_ln_pack(Ctx& c, const LnStep& ln, const float* a_iv, int aq, char* pl
 // ---- the residual consumer: k_lin_res runs a Linear layer's forward GEMM on prepacked planes and writes residual + output through
 // a row map ---------------------------------------------------------------------------------------------------------
 constexpr int RES_RECORD_KIND = 22;
+constexpr int ATTN_PLANE_RECORD_KIND = 23, WATTN_PLANE_RECORD_KIND = 24;   // the plane instances of the one-kernel attention cores
 struct ResStep { const p4v_res_desc* d; const float* residual; float* out; };
 // the envelope of the consumer behind the Linear layer `d`, before anything is planned or launched
 int res_check(const ResStep& r, const p4v_linear_desc* d, const Ctx& c, const char* who) {
@@ -3817,8 +3818,10 @@ struct QkvProducer {
 // for it, and p4v_debug_attn_planes reports sizes 0.  Everything is scratch of the bump region and given back.
 // `win` (P4V_WATTN_ONE_KERNEL; k_wattn_qkpv): the same planes and tables, the window kernel -- its grid is flat
 // over the live 32-row tiles, ceil(M / 32) per z, four to a workgroup; `ndt` then is its NT, the resident 32-key tiles.
+// `po` (attn_chain with a proj layer behind the core): the plane instances -- the epilogue quantises into proj's row
+// plane; t2.fwd_out, the fp32 output, is then optional.
 int attn_one_kernel(Ctx& c, FusedChain& ch, float scale, int ndt, const MatMulTensors& t1, const MatMulCall& m1, const MatMulTensors& t2,
-                    const MatMulCall& m2, const FusedChain::PrePlanes* pre, const AttnWindow* win = nullptr) {
+                    const MatMulCall& m2, const FusedChain::PrePlanes* pre, const AttnWindow* win = nullptr, const AttnPlaneOut* po = nullptr) {
     const int Z = ch.Z, H = m1.H, M = m1.M, N = m1.N, K1 = m1.K, Dv = m2.N;
     const bool twin = ch.twin;
     // (the window kernel reads ONE output tile: its column plane is packed with 32 rows per z instead of the sweep's NpB --
@@ -3839,6 +3842,8 @@ int attn_one_kernel(Ctx& c, FusedChain& ch, float scale, int ndt, const MatMulTe
     CHK(launch_scale(c, fp2.s1));
     if (twin) { fp2.s2.S = So2; fp2.s2.C = 1; fp2.s2.nblk = fp2.s_cs; CHK(launch_scale(c, fp2.s2)); }
     if (!pre) CHK(pack_operand(c, fp2, pl2, PassBufs{}, fp2.col, vplane, true, 0, 1));
+    // what the epilogue writes: out [Z][M][Dv] -- or (`po`) the live rows of proj's plane, and out where it was asked for
+    const double out_bytes = po ? (double)(Z / H) * M * po->Kp + (t2.fwd_out ? 4.0 * (double)Z * M * Dv : 0.0) : 4.0 * (double)Z * M * Dv;
     if (!c.dry && win) {
         WattnQkPvParams q{};
         q.Q = pk.rows; q.Kt = pk.cols; q.q_zs = (long)ch.Mp * pk.Kp; q.k_zs = (long)pk.Np * pk.Kp; q.ldk = pk.Kp;
@@ -3855,13 +3860,22 @@ int attn_one_kernel(Ctx& c, FusedChain& ch, float scale, int ndt, const MatMulTe
         g_alg_macs_cand = (double)Z * M * N * (K1 + Dv);
         // the three operand planes, the bias, the mask, out and probs
         g_alg_bytes = (double)Z * ((double)M * K1 + (double)N * K1 + (double)N * Dv) + 4.0 * (double)M * N * (H + (win->mask ? win->n_windows : 0)) +
-                      4.0 * (double)Z * M * Dv + (t1.fwd_out ? 4.0 * (double)Z * M * N : 0.0);
+                      out_bytes + (t1.fwd_out ? 4.0 * (double)Z * M * N : 0.0);
         g_exec_frac = 1.0;
         // (ONE walk over the keys per live row tile: the q k^T MFMAs and one MFMA per plane and key tile)
         const double tiles = (double)q.nwaves * 32.0 * (double)rup(N, 32);
-        const StatInfo si = stat_info(WATTN_PV_RECORD_KIND, tiles * (pk.Kp + 32.0 * (twin ? 2 : 1)), g_alg_macs_cand, q.nwg, 1, g_alg_bytes);
+        const StatInfo si = stat_info(po ? WATTN_PLANE_RECORD_KIND : WATTN_PV_RECORD_KIND, tiles * (pk.Kp + 32.0 * (twin ? 2 : 1)), g_alg_macs_cand, q.nwg, 1,
+                                      g_alg_bytes);
         const dim3 grid(q.nwg), block(256);
-        if (ndt == 2) CHK(twin ? enqueue(c, KERN1_T(WattnQkPvParams, k_wattn_qkpv, true, 2), grid, block, 0, q, &si)
+        if (po) {
+            WattnQkPvPlaneParams qp{};
+            static_cast<WattnQkPvParams&>(qp) = q;
+            qp.po = *po;
+            if (ndt == 2) CHK(twin ? enqueue(c, KERN1_T(WattnQkPvPlaneParams, k_wattn_qkpv_plane, true, 2), grid, block, 0, qp, &si)
+                                   : enqueue(c, KERN1_T(WattnQkPvPlaneParams, k_wattn_qkpv_plane, false, 2), grid, block, 0, qp, &si));
+            else CHK(twin ? enqueue(c, KERN1_T(WattnQkPvPlaneParams, k_wattn_qkpv_plane, true, 5), grid, block, 0, qp, &si)
+                          : enqueue(c, KERN1_T(WattnQkPvPlaneParams, k_wattn_qkpv_plane, false, 5), grid, block, 0, qp, &si));
+        } else if (ndt == 2) CHK(twin ? enqueue(c, KERN1_T(WattnQkPvParams, k_wattn_qkpv, true, 2), grid, block, 0, q, &si)
                                : enqueue(c, KERN1_T(WattnQkPvParams, k_wattn_qkpv, false, 2), grid, block, 0, q, &si));
         else CHK(twin ? enqueue(c, KERN1_T(WattnQkPvParams, k_wattn_qkpv, true, 5), grid, block, 0, q, &si)
                       : enqueue(c, KERN1_T(WattnQkPvParams, k_wattn_qkpv, false, 5), grid, block, 0, q, &si));
@@ -3880,13 +3894,22 @@ int attn_one_kernel(Ctx& c, FusedChain& ch, float scale, int ndt, const MatMulTe
         q.mtiles = ch.Mp / SW_BM; q.nwg = Z * q.mtiles;
         g_alg_macs_cand = (double)Z * M * N * (K1 + Dv);
         // the three operand planes, out and probs
-        g_alg_bytes = (double)Z * ((double)M * K1 + (double)N * K1 + (double)N * Dv) + 4.0 * (double)Z * M * Dv + (t1.fwd_out ? 4.0 * (double)Z * M * N : 0.0);
+        g_alg_bytes = (double)Z * ((double)M * K1 + (double)N * K1 + (double)N * Dv) + out_bytes + (t1.fwd_out ? 4.0 * (double)Z * M * N : 0.0);
         g_exec_frac = 1.0;
         // (three walks over the keys; the third one carries ndt MFMAs per plane and key tile)
         const double tiles = (double)Z * ch.Mp * (double)rup(N, 32);
-        const StatInfo si = stat_info(ATTN_PV_RECORD_KIND, tiles * (3.0 * pk.Kp + 32.0 * ndt * (twin ? 2 : 1)), g_alg_macs_cand, q.nwg, 1, g_alg_bytes);
+        const StatInfo si = stat_info(po ? ATTN_PLANE_RECORD_KIND : ATTN_PV_RECORD_KIND, tiles * (3.0 * pk.Kp + 32.0 * ndt * (twin ? 2 : 1)), g_alg_macs_cand,
+                                      q.nwg, 1, g_alg_bytes);
         const dim3 grid(q.nwg), block(256);
-        if (ndt == 2) CHK(twin ? enqueue(c, KERN1_T(AttnQkPvParams, k_attn_qkpv, true, 2), grid, block, 0, q, &si)
+        if (po) {
+            AttnQkPvPlaneParams qp{};
+            static_cast<AttnQkPvParams&>(qp) = q;
+            qp.po = *po;
+            if (ndt == 2) CHK(twin ? enqueue(c, KERN1_T(AttnQkPvPlaneParams, k_attn_qkpv_plane, true, 2), grid, block, 0, qp, &si)
+                                   : enqueue(c, KERN1_T(AttnQkPvPlaneParams, k_attn_qkpv_plane, false, 2), grid, block, 0, qp, &si));
+            else CHK(twin ? enqueue(c, KERN1_T(AttnQkPvPlaneParams, k_attn_qkpv_plane, true, 4), grid, block, 0, qp, &si)
+                          : enqueue(c, KERN1_T(AttnQkPvPlaneParams, k_attn_qkpv_plane, false, 4), grid, block, 0, qp, &si));
+        } else if (ndt == 2) CHK(twin ? enqueue(c, KERN1_T(AttnQkPvParams, k_attn_qkpv, true, 2), grid, block, 0, q, &si)
                                : enqueue(c, KERN1_T(AttnQkPvParams, k_attn_qkpv, false, 2), grid, block, 0, q, &si));
         else CHK(twin ? enqueue(c, KERN1_T(AttnQkPvParams, k_attn_qkpv, true, 4), grid, block, 0, q, &si)
                       : enqueue(c, KERN1_T(AttnQkPvParams, k_attn_qkpv, false, 4), grid, block, 0, q, &si));
@@ -3895,9 +3918,35 @@ int attn_one_kernel(Ctx& c, FusedChain& ch, float scale, int ndt, const MatMulTe
     c.ws.off = mark;
     return 0;
 }
-int attn_chain(const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulTensors& t2, Ctx& c, const AttnWindow* win, const QkvProducer* qkv = nullptr) {
+// `proj` (p4v_attn_proj_quant_forward / p4v_wattn_proj_quant_forward): the Linear layer behind the attention core
+// is the consumer of a second chain whose producer is the core.  On the one-kernel cores (Dv % 4 == 0) the plane instance writes
+// proj's int8 row plane -- rows B M ... Mp zeroed by one fill before it --, then proj's forward pass runs on the prepacked plane
+// (consume), or k_lin_res with the residual and its row map (consume_res).  Where the core has no plane instance the chain of today
+// runs into a scratch fp32 output, k_head_merge copies it to [B M][H Dv] and proj packs that as its x: the same bits.
+// t.fwd_out: proj's output (with `res`: residual + output through the map); t2.fwd_out becomes the optional fp32 core output.
+struct AttnProj { const p4v_linear_desc* d; LinearTensors t; const p4v_res_desc* res; const float* residual; };
+thread_local FusedPlanes g_proj_planes;                        // where the last call's plane of proj lies (p4v_debug_proj_planes)
+int attn_two_kernels(Ctx& c, FusedChain& ch, const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulCall& m1, const MatMulTensors& t2, const MatMulCall& m2,
+                     const FusedChain::PrePlanes* pre, const AttnWindow* win);
+// the envelope of proj behind the core whose second MatMul is `d2`, before anything is planned or launched
+int proj_check(const AttnProj& pj, const p4v_matmul_desc* d2, const Ctx& c, const char* who) {
+    const p4v_linear_desc* d = pj.d;
+    if (d->n_H != 1 || d->n_a != 1) return fail(P4V_ERR_UNSUPPORTED, "%s: the fused proj takes n_H = n_a = 1 on the Linear layer", who);
+    if (d->twin_postgelu) return fail(P4V_ERR_UNSUPPORTED, "%s: proj reads no GELU output (twin_postgelu)", who);
+    if (d->reserved & RSV_FP32_PLANES) return fail(P4V_ERR_UNSUPPORTED, "%s: int8 planes only (proj.reserved bit 0 is set)", who);
+    if ((long)d->in_features != (long)d2->heads * d2->N || (long)d->batch * d->tokens != (long)d2->batch * d2->M)
+        return fail(P4V_ERR_INVALID, "%s: proj's input [%ld][%d] is not the head-merged attention output [%ld][%d x %d]", who, (long)d->batch * d->tokens,
+                    d->in_features, (long)d2->batch * d2->M, d2->heads, d2->N);
+    if (pj.res) CHK(res_check(ResStep{pj.res, pj.residual, pj.t.fwd_out}, d, c, who));
+    return 0;
+}
+int attn_chain(const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulTensors& t2_, Ctx& c, const AttnWindow* win, const QkvProducer* qkv = nullptr,
+               const AttnProj* proj = nullptr) {
     const p4v_matmul_desc* d1 = &d->qk;
     const p4v_matmul_desc* d2 = &d->pv;
+    const char* who = win ? "p4v_wattn_proj_quant_forward" : "p4v_attn_proj_quant_forward";
+    if (proj) CHK(proj_check(*proj, d2, c, who));
+    MatMulTensors t2 = t2_;                                    // (with proj: fwd_out may become scratch)
     // the envelope, before anything is planned or launched
     if (win) {
         if (win->n_windows < 1) return fail(P4V_ERR_INVALID, "wattn: n_windows = %d is not positive", win->n_windows);
@@ -3936,11 +3985,66 @@ int attn_chain(const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulTens
     const bool one_kernel = asked && (win ? N <= 160 && m2.N <= 32 && FusedChain::producer_kp(K1) == SW_BKB && 32 <= ch.pl2.NpB &&
                                                 (long)Z * ((M + 31) / 32) < (1L << 31)
                                           : m2.N <= 128 && ndt * 32 <= ch.pl2.NpB);
+    if (proj) {
+        // proj's chain first: its row plane (and, without a plane instance, the fp32 tensors in front of it) outlive the core's scratch
+        const int Dv = m2.N;
+        const bool plane_inst = one_kernel && Dv % 4 == 0;
+        const size_t n_core = (size_t)Z * M * Dv;
+        float* merged = nullptr;
+        if (!plane_inst) {
+            if (!t2.fwd_out) t2.fwd_out = c.ws.get<float>(n_core);
+            merged = c.ws.get<float>(n_core);
+            ch.fp2.O = t2.fwd_out; ch.fp2.store_out = t2.fwd_out;       // (the two-kernel chain's consumer stores the core's output there)
+        }
+        LinearTensors lt = proj->t;
+        lt.X = merged;
+        LinearCall L(c, proj->d, lt, sg);
+        CHK(L.build());
+        if (!L.i8 || L.twin) return fail(P4V_ERR_UNSUPPORTED, "%s: int8 planes only", who);
+        FusedChain pc{c, who, "proj"};
+        CHK(pc.plan_consumer(L.forward_pass(), 1, false));     // P1: [Mp][roundup64(H Dv)]
+        if (!c.ws.ok()) return fail(P4V_ERR_WORKSPACE, "workspace too small: need >= %zu bytes", c.ws.off);
+        if (plane_inst) {
+            const long live = (long)(Z / H) * M;
+            if (pc.Kp != (int)rup((long)H * Dv, 64) || pc.Mp < live) return fail(P4V_ERR_UNSUPPORTED, "%s: proj's row plane [%d][%d] is not the core's", who, pc.Mp, pc.Kp);
+            CHK(q_fill(c, pc.P1 + live * pc.Kp, 0, (size_t)(pc.Mp - live) * pc.Kp));
+            AttnPlaneOut po{};
+            po.plane = (int8_t*)pc.P1; po.a_iv = proj->t.a_iv; po.lo = -L.aq; po.hi = L.aq - 1; po.Kp = pc.Kp;
+            po.wide = (Dv % 16 == 0 && ((unsigned long long)pc.P1 & 15) == 0) ? 1 : 0;
+            if (!c.dry && ((unsigned long long)pc.P1 & 3)) return fail(P4V_ERR_INVALID, "%s: proj's row plane is not aligned to 4 bytes", who);
+            CHK(attn_one_kernel(c, ch, d->scale, ndt, t1, m1, t2, m2, nullptr, win, &po));
+            if (!c.dry) g_proj_planes = FusedPlanes{(size_t)(pc.P1 - c.ws.base), 0, pc.Mp, pc.Kp, 0};
+        } else {
+            const size_t mark = c.ws.off;
+            if (one_kernel) CHK(attn_one_kernel(c, ch, d->scale, ndt, t1, m1, t2, m2, nullptr, win));
+            else {
+                ch.carve();
+                CHK(attn_two_kernels(c, ch, d, t1, m1, t2, m2, nullptr, win));
+                CHK(ch.consume());
+            }
+            c.ws.off = mark;
+            if (!c.dry) {
+                const HeadMergeParams hm{t2.fwd_out, merged, (long)n_core, H, M, Dv};
+                CHK(enqueue(c, Kern1<HeadMergeParams, k_head_merge>::desc(), dim3((unsigned)std::min<long>(cdiv((long)n_core, 256), 4096)), dim3(256), 0, hm, nullptr));
+            }
+            CHK(pack_operand(c, pc.fp2, pc.res_planes(), PassBufs{}, pc.fp2.row, pc.P1, false, 0, 1));
+            if (!c.dry) g_proj_planes = FusedPlanes{(size_t)(pc.P1 - c.ws.base), 0, pc.Mp, pc.Kp, 0};
+        }
+        return proj->res ? pc.consume_res(ResStep{proj->res, proj->residual, proj->t.fwd_out}) : pc.consume();
+    }
     if (!one_kernel) ch.carve();
     FusedChain::PrePlanes planes{};
     const FusedChain::PrePlanes* pre = qkv ? &planes : nullptr;
     if (qkv) CHK(qkv->run(c, ch, H, N, K1, t1, m1, t2, m2, planes));
     if (one_kernel) return attn_one_kernel(c, ch, d->scale, ndt, t1, m1, t2, m2, pre, win);
+    CHK(attn_two_kernels(c, ch, d, t1, m1, t2, m2, pre, win));
+    return ch.consume(pre);
+}
+// the two-kernel chain's producer: k_attn_qk on q and k^T writes matmul2's row plane(s)
+int attn_two_kernels(Ctx& c, FusedChain& ch, const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulCall& m1, const MatMulTensors& t2, const MatMulCall& m2,
+                     const FusedChain::PrePlanes* pre, const AttnWindow* win) {
+    const int Z = m1.Z, H = m1.H, M = m1.M, N = m1.N, K1 = m1.K;
+    const bool twin = ch.twin;
     CHK(ch.produce(m1.forward_pass(), K1, N, H, g_attn_planes, [&](const FusedChain::Packed& pk) -> int {
         AttnQkParams q{};
         q.Q = pk.rows; q.Kt = pk.cols; q.q_zs = (long)ch.Mp * pk.Kp; q.k_zs = (long)pk.Np * pk.Kp; q.ldk = pk.Kp; q.ktiles = pk.Kp / SW_BKB;
@@ -3969,12 +4073,21 @@ int attn_chain(const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulTens
         return twin ? enqueue(c, KERN1_T(AttnQkParams, k_attn_qk, true), grid, block, lds, q, &si)
                     : enqueue(c, KERN1_T(AttnQkParams, k_attn_qk, false), grid, block, lds, q, &si);
     }, pre));
-    return ch.consume(pre);
+    return 0;
 }
 int attn_impl(const p4v_attn_desc* d, const MatMulTensors& t1, const MatMulTensors& t2, Ctx& c) { return attn_chain(d, t1, t2, c, nullptr); }
 // the window call as fused_sizing_run / fused_call take it: the p4v_attn_desc of its two MatMuls and the window record
 struct WattnCall { p4v_attn_desc a; AttnWindow w; };
 int wattn_impl(const WattnCall* d, const MatMulTensors& t1, const MatMulTensors& t2, Ctx& c) { return attn_chain(&d->a, t1, t2, c, &d->w); }
+
+// ---- p4v_attn_proj_quant_forward / p4v_wattn_proj_quant_forward: proj behind the attention core (AttnProj above) ----
+struct AttnProjCall { p4v_attn_desc a; AttnWindow w; bool win; p4v_linear_desc lin; bool has_res; p4v_res_desc res; };
+struct AttnProjTensors { MatMulTensors m1, m2; LinearTensors l; const float* residual = nullptr; };      // m2.fwd_out: the optional core; l.fwd_out: out
+int attn_proj_impl(const AttnProjCall* d, const AttnProjTensors& t, const AttnProjTensors&, Ctx& c) {
+    AttnWindow w = d->w;
+    const AttnProj pj{&d->lin, t.l, d->has_res ? &d->res : nullptr, t.residual};
+    return attn_chain(&d->a, t.m1, t.m2, c, d->win ? &w : nullptr, nullptr, &pj);
+}
 
 // ---- p4v_qkv_attn_quant_forward: the qkv layer in front of the attention chain (QkvProducer above) -----------------------------
 // The records of the three modules as their own quant_forward entry points fill them: lin.fwd_out is the optional fp32 copy of
@@ -4535,6 +4648,50 @@ int p4v_wattn_quant_forward(const p4v_wattn_desc* desc, const p4v_wattn_tensors*
                        .split = const_cast<float*>(t->split), .fwd_out = t->out}, t->ws, t->ws_bytes, stream);
 }
 
+static AttnProjCall attn_proj_call(const p4v_attn_desc* a, const p4v_wattn_desc* wd, const p4v_linear_desc* proj, const p4v_res_desc* res, const p4v_attn_proj_tensors* t) {
+    AttnProjCall d{};
+    if (wd) { const WattnCall w = wattn_call(wd, nullptr); d.a = w.a; d.w = AttnWindow{t ? t->rel_bias : nullptr, t ? t->mask : nullptr, wd->n_windows}; }
+    else d.a = *a;
+    d.win = wd != nullptr; d.lin = *proj; d.has_res = res != nullptr;
+    if (res) d.res = *res;
+    return d;
+}
+static int attn_proj_forward(const char* who, const AttnProjCall& d, bool has_mask, const p4v_attn_proj_tensors* t, void* stream) {
+    if (!t->q || !t->kT || !t->v || (d.win && !t->rel_bias) || !t->qk_A_interval || !t->qk_B_interval || !t->pv_A_interval || !t->pv_B_interval || !t->w ||
+        !t->w_interval || !t->a_interval || (d.has_res && !t->residual) || !t->out || !t->ws)
+        return fail(P4V_ERR_INVALID, "%s: null pointer", who);
+    if (d.a.pv.sos && !t->split) return fail(P4V_ERR_INVALID, "%s: sos needs split", who);
+    if (d.lin.has_bias && !t->bias) return fail(P4V_ERR_INVALID, "%s: has_bias set but the bias is null", who);
+    if (d.win && has_mask != (t->mask != nullptr)) return fail(P4V_ERR_INVALID, "%s: has_mask = %d but the mask pointer is %s", who, (int)has_mask, t->mask ? "set" : "null");
+    CHK(ws_aligned(t->ws));
+    const AttnProjTensors rec{
+        {.A = t->q, .B = t->kT, .A_iv = const_cast<float*>(t->qk_A_interval), .B_iv = const_cast<float*>(t->qk_B_interval), .fwd_out = t->probs},
+        {.B = t->v, .A_iv = const_cast<float*>(t->pv_A_interval), .B_iv = const_cast<float*>(t->pv_B_interval), .split = const_cast<float*>(t->split), .fwd_out = t->core},
+        {.W = t->w, .bias = d.lin.has_bias ? t->bias : nullptr, .w_iv = const_cast<float*>(t->w_interval), .a_iv = const_cast<float*>(t->a_interval), .fwd_out = t->out},
+        t->residual};
+    return fused_call(attn_proj_impl, &d, rec, rec, t->ws, t->ws_bytes, stream);
+}
+size_t p4v_attn_proj_workspace_bytes(const p4v_attn_desc* desc, const p4v_linear_desc* proj, const p4v_res_desc* res) {
+    if (!desc || !proj) return 0;
+    const AttnProjCall d = attn_proj_call(desc, nullptr, proj, res, nullptr);
+    size_t need = 0;
+    return fused_sizing_run(attn_proj_impl, &d, &need) == 0 ? need : 0;
+}
+int p4v_attn_proj_quant_forward(const p4v_attn_desc* desc, const p4v_linear_desc* proj, const p4v_res_desc* res, const p4v_attn_proj_tensors* t, void* stream) {
+    if (!desc || !proj || !t) return fail(P4V_ERR_INVALID, "p4v_attn_proj_quant_forward: null pointer");
+    return attn_proj_forward("p4v_attn_proj_quant_forward", attn_proj_call(desc, nullptr, proj, res, t), false, t, stream);
+}
+size_t p4v_wattn_proj_workspace_bytes(const p4v_wattn_desc* desc, const p4v_linear_desc* proj, const p4v_res_desc* res) {
+    if (!desc || !proj) return 0;
+    const AttnProjCall d = attn_proj_call(nullptr, desc, proj, res, nullptr);
+    size_t need = 0;
+    return fused_sizing_run(attn_proj_impl, &d, &need) == 0 ? need : 0;
+}
+int p4v_wattn_proj_quant_forward(const p4v_wattn_desc* desc, const p4v_linear_desc* proj, const p4v_res_desc* res, const p4v_attn_proj_tensors* t, void* stream) {
+    if (!desc || !proj || !t) return fail(P4V_ERR_INVALID, "p4v_wattn_proj_quant_forward: null pointer");
+    return attn_proj_forward("p4v_wattn_proj_quant_forward", attn_proj_call(nullptr, desc, proj, res, t), desc->has_mask != 0, t, stream);
+}
+
 size_t p4v_qkv_attn_workspace_bytes(const p4v_qkv_attn_desc* desc) {
     size_t need = 0;
     return (desc && fused_sizing_run(qkv_attn_impl, desc, &need) == 0) ? need : 0;
@@ -5092,6 +5249,9 @@ static int planes_out(const FusedPlanes& m, uint64_t* out, const char* who, cons
 }
 int p4v_debug_mlp_planes(uint64_t* out) { return planes_out(g_mlp_planes, out, "p4v_debug_mlp_planes", "p4v_mlp_quant_forward"); }
 int p4v_debug_attn_planes(uint64_t* out) { return planes_out(g_attn_planes, out, "p4v_debug_attn_planes", "p4v_attn_quant_forward / p4v_wattn_quant_forward"); }
+int p4v_debug_proj_planes(uint64_t* out) {
+    return planes_out(g_proj_planes, out, "p4v_debug_proj_planes", "p4v_attn_proj_quant_forward / p4v_wattn_proj_quant_forward");
+}
 int p4v_debug_ln_planes(uint64_t* out) { return planes_out(g_ln_planes, out, "p4v_debug_ln_planes", "p4v_ln_linear_quant_forward / p4v_ln_mlp_quant_forward"); }
 int p4v_debug_qkv_planes(uint64_t* out) {
     const QkvPlanes& m = g_qkv_planes;

@@ -5614,6 +5614,73 @@ __global__ __launch_bounds__(256) void k_attn_qk(std::conditional_t<WIN, AttnWin
     k_attn_qk_body<TWIN, WIN>(p, P4V_BIDX, P4V_GDIM);
 }
 
+// The plane-writing epilogue of both one-kernel cores (k_attn_qkpv_plane / k_wattn_qkpv_plane): the chain ends in the
+// int8 row plane [Mp][Kp] of the Linear layer behind the attention core (proj), Kp = roundup64(H Dv) -- no fp32 attention output, no
+// transpose copy of it, no k_pack1 of the copy.  The head merge is an address: row (z / H) M + m, column (z % H) Dv + d.
+// Per output tile the lane computes o exactly as the fp32 epilogue does, quantises it with proj's one activation interval
+// (pack_value, PACK_SYM: the IEEE division -- the bytes are k_pack1's of the same o) and holds four dwords, bytes d = 8 q4 + 4 g + e
+// of the tile: they interleave with the other lane half's four.  Two v_permlane32_swap (gfx950: lanes 32..63 of one register
+// against lanes 0..31 of another) trade the dwords q4 = 2, 3 of the lower half against q4 = 0, 1 of the upper one: lane (l31, g) then
+// owns the 16 contiguous bytes 16 g ... 16 g + 15 of the tile and issues ONE 16-byte store (`wide`: Dv % 16 == 0), or up to four
+// dword stores (Dv % 4 == 0).  No LDS.  Columns >= Dv of a tile are never stored: they belong to the next head.
+struct AttnPlaneOut {
+    int8_t* plane;                            // proj's row plane [Mp][Kp], 16-byte aligned
+    const float* a_iv;                        // proj's a_interval [1]
+    int lo, hi;                               // proj's clamp range
+    int Kp, wide;                             // roundup64(H Dv); Dv % 16 == 0
+};
+// one output tile (columns dbase ... dbase + 31 of the head) of the lane's query row; `prow`: the row's first byte of this head
+template <bool TWIN>
+__device__ __forceinline__ void attn_plane_tile(const AttnPlaneOut& po, const v16i& a1, const v16i& a2, float so1, float so2, float qs,
+                                                float* orow, int vec4, bool row_ok, int8_t* prow, int dbase, int Dv, int g) {
+    PackParams pq{};
+    pq.mode = PACK_SYM; pq.lo = po.lo; pq.hi = po.hi;
+    unsigned w[4];
+#pragma unroll
+    for (int q4 = 0; q4 < 4; ++q4) {
+        const int d0 = dbase + 8 * q4 + 4 * g;
+        v4f o4;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float o = (float)a1[q4 * 4 + e] * so1;
+            if (TWIN) o = fmaf((float)a2[q4 * 4 + e], so2, o);
+            o4[e] = o + 0.0f;
+        }
+        if (orow && row_ok) {                          // the fp32 values the bytes come from, where the caller asked for them
+            if (vec4) {
+                if (d0 < Dv) *reinterpret_cast<v4f*>(orow + d0) = o4;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (d0 + e < Dv) orow[d0 + e] = o4[e];
+            }
+        }
+        unsigned x = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x |= (unsigned)((int)pack_value(pq, o4[e], qs) & 0xff) << (8 * e);
+        w[q4] = x;
+    }
+    // (w0, w2) -> lower half: bytes 0..3 | 4..7, upper half: 16..19 | 20..23; (w1, w3) -> 8..11 | 12..15 and 24..27 | 28..31
+    const auto s02 = __builtin_amdgcn_permlane32_swap(w[0], w[2], false, false);
+    const auto s13 = __builtin_amdgcn_permlane32_swap(w[1], w[3], false, false);
+    if (!row_ok) return;
+    const int c0 = dbase + 16 * g;
+    if (po.wide) {                                     // (uniform) the 16 bytes are inside the head's columns or outside them
+        const v4i st = {(int)s02[0], (int)s02[1], (int)s13[0], (int)s13[1]};
+        if (c0 < Dv) *reinterpret_cast<v4i*>(prow + c0) = st;
+    } else {
+        if (c0 < Dv) *reinterpret_cast<int*>(prow + c0) = (int)s02[0];
+        if (c0 + 4 < Dv) *reinterpret_cast<int*>(prow + c0 + 4) = (int)s02[1];
+        if (c0 + 8 < Dv) *reinterpret_cast<int*>(prow + c0 + 8) = (int)s13[0];
+        if (c0 + 12 < Dv) *reinterpret_cast<int*>(prow + c0 + 12) = (int)s13[1];
+    }
+}
+// the plane's column padding H Dv ... Kp of the lane's row (`rowp`: the row's first byte), written by the wave of the LAST head: zeros,
+// as k_pack1 leaves them -- the kernel relies on nothing the workspace held
+__device__ __forceinline__ void attn_plane_pad(const AttnPlaneOut& po, int8_t* rowp, int HDv, int g) {
+    for (int c = HDv + 4 * g; c < po.Kp; c += 8) *reinterpret_cast<int*>(rowp + c) = 0;
+}
+
 // ------------------------------------------------------------------------------------------
 // Fused attention forward, both halves (p4v_attn_quant_forward with P4V_ATTN_ONE_KERNEL): k_attn_qk's three walks, the third one
 // ending in matmul2's int8 GEMM instead of matmul2's row plane(s) -- q k^T -> * scale -> softmax -> split quantiser -> p v
@@ -5804,6 +5871,147 @@ __global__ __launch_bounds__(256) void k_attn_qkpv(AttnQkPvParams p) {
                     if (d0 + e < p.Dv) orow[d0 + e] = o4[e];
             }
         }
+}
+
+// The plane instance: k_attn_qkpv up to the accumulators, statement for statement -- the existing instances keep their
+// own text, so that their code is what it was --, then attn_plane_tile per output tile; p.out is optional here.
+struct AttnQkPvPlaneParams : AttnQkPvParams { AttnPlaneOut po; };
+
+template <bool TWIN, int NDT>
+__global__ __launch_bounds__(256) void k_attn_qkpv_plane(AttnQkPvPlaneParams p) {
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int g = lane >> 5, l31 = lane & 31;
+    const int t = xcd_remap(blockIdx.x, p.nwg);
+    const int z = t / p.mtiles, mt = t % p.mtiles;    // the row tiles of one z are adjacent: they share its key and value planes
+    const int m0 = mt * SW_BM + wid * 32;             // this wave's 32 queries
+    if (m0 >= p.M) return;                            // (wave-uniform; no barrier in this kernel) nothing but padding rows
+    const int m = m0 + l31;
+    const bool row_ok = m < p.M;
+    const int head = z % p.H;
+
+    const char* gQ = (const char*)p.Q + (long)z * p.q_zs + (long)m * p.ldk + g * 16;
+    const char* gK = (const char*)p.Kt + (long)z * p.k_zs + (long)l31 * p.ldk + g * 16;
+    const char* gV = (const char*)p.V + (long)z * p.v_zs + (long)l31 * p.ldv + g * 4;
+    const bool one = p.ktiles == 1;
+    v4i qf0 = {0, 0, 0, 0}, qf1 = {0, 0, 0, 0};       // the query fragments of a single k-tile stay in registers
+    if (one) { qf0 = *reinterpret_cast<const v4i*>(gQ); qf1 = *reinterpret_cast<const v4i*>(gQ + 32); }
+    const float s1 = p.S1[head];
+    const float scale = p.scale;
+    // t = (float)acc * S1[head] of the 32 x 32 tile at keys [key0, key0 + 32): k_attn_qk's GEMM, plain instance
+    auto scores = [&](int key0, float (&u)[16]) {
+        v16i acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0;
+        const char* ka = gK + (long)key0 * p.ldk;
+        if (one) {
+            const v4i a0 = *reinterpret_cast<const v4i*>(ka), a1 = *reinterpret_cast<const v4i*>(ka + 32);
+            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, qf0, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, qf1, acc, 0, 0, 0);
+        } else {
+            for (int kb = 0; kb < p.ktiles * 2; ++kb) {
+                const v4i a = *reinterpret_cast<const v4i*>(ka + kb * 32);
+                const v4i b = *reinterpret_cast<const v4i*>(gQ + kb * 32);
+                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, acc, 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) u[r] = __fmul_rn((float)acc[r], s1);
+    };
+
+    const int ntiles = (p.N + 31) / 32;
+    float u[16];
+    // ---- pass 1: the row maximum ------------------------------------------------------------------------
+    float mx = -__builtin_inff();
+    for (int nt = 0; nt < ntiles; ++nt) {
+        scores(nt * 32, u);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int n = nt * 32 + acc32_row(r, g);
+            if (n < p.N) mx = fmaxf(mx, __fmul_rn(u[r], scale));
+        }
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    // ---- pass 2: the row sum (one partial sum per accumulator register, added up pairwise) ---------------
+    float part[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) part[r] = 0.0f;
+    for (int nt = 0; nt < ntiles; ++nt) {
+        scores(nt * 32, u);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int n = nt * 32 + acc32_row(r, g);
+            if (n < p.N) part[r] = __fadd_rn(part[r], expf(fmaf(u[r], scale, -mx)));
+        }
+    }
+#pragma unroll
+    for (int w = 8; w >= 1; w >>= 1)
+#pragma unroll
+        for (int r = 0; r < w; ++r) part[r] = __fadd_rn(part[r], part[r + w]);
+    const float sum = __fadd_rn(part[0], __shfl_xor(part[0], 32));
+    // ---- pass 3: the probabilities, matmul2's quantiser, matmul2's GEMM on the bytes in registers ----------
+    const float qs = p.qs[p.qs_headwise ? head : 0];
+    PackParams pv1{}, pv2{};
+    pv1.mode = TWIN ? PACK_SOS_HI : PACK_SYM; pv1.lo = p.lo; pv1.hi = p.hi; pv1.qm1 = p.qm1;
+    pv2.mode = PACK_SOS_LO; pv2.qm1 = p.qm1;
+    v16i acc1[NDT];
+    [[maybe_unused]] v16i acc2[NDT];
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { acc1[dt][r] = 0; if (TWIN) acc2[dt][r] = 0; }
+    for (int nt = 0; nt < ntiles; ++nt) {
+        const int key0 = nt * 32;
+        // the tile's V fragments first (key0 + 8 q4 + 4 g + 3 < roundup32(N) <= ldv: inside the row)
+        v4i vf[NDT];
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) vf[dt][q4] = *reinterpret_cast<const int*>(gV + (long)dt * 32 * p.ldv + key0 + 8 * q4);
+        scores(key0, u);
+        v4i w1 = {0, 0, 0, 0};
+        [[maybe_unused]] v4i w2 = {0, 0, 0, 0};
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+            int x1 = 0, x2 = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int r = q4 * 4 + e;
+                const int n = key0 + e + 8 * q4 + 4 * g;
+                const bool ok = row_ok && n < p.N;
+                float b1 = 0.0f, b2 = 0.0f;
+                if (ok) {
+                    float pr;
+                    {
+#pragma clang fp contract(off)
+                        pr = u[r] * scale - mx;
+                    }
+                    pr = __fdiv_rn(expf(pr), sum);
+                    if (p.probs) p.probs[((long)z * p.M + m) * p.N + n] = pr;
+                    b1 = pack_value(pv1, pr, qs);
+                    if (TWIN) b2 = pack_value(pv2, pr, qs);
+                }
+                x1 |= ((int)b1 & 0xff) << (8 * e);
+                if (TWIN) x2 |= ((int)b2 & 0xff) << (8 * e);
+            }
+            w1[q4] = x1;
+            if (TWIN) w2[q4] = x2;
+        }
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt) {
+            acc1[dt] = __builtin_amdgcn_mfma_i32_32x32x32_i8(vf[dt], w1, acc1[dt], 0, 0, 0);
+            if (TWIN) acc2[dt] = __builtin_amdgcn_mfma_i32_32x32x32_i8(vf[dt], w2, acc2[dt], 0, 0, 0);
+        }
+    }
+    // ---- epilogue: EPI_FWD's expression, quantised into proj's row plane (attn_plane_tile above) ---------------
+    const float so1 = p.So1[head];
+    const float so2 = TWIN ? p.So2[head] : 0.0f;
+    const float pqs = p.po.a_iv[0];                    // proj's activation interval
+    float* orow = p.out ? p.out + ((long)z * p.M + (row_ok ? m : 0)) * p.Dv : nullptr;
+    int8_t* rowp = p.po.plane + ((long)(z / p.H) * p.M + (row_ok ? m : 0)) * p.po.Kp;
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt)
+        attn_plane_tile<TWIN>(p.po, acc1[dt], TWIN ? acc2[dt] : acc1[dt], so1, so2, pqs, orow, p.vec4, row_ok, rowp + head * p.Dv, dt * 32, p.Dv, g);
+    if (row_ok && head == p.H - 1) attn_plane_pad(p.po, rowp, p.H * p.Dv, g);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -6011,6 +6219,174 @@ __global__ __launch_bounds__(256) void k_wattn_qkpv(WattnQkPvParams p) {
         }
     }
 }
+
+// The plane instance: k_wattn_qkpv up to the accumulators, statement for statement, with the core's own work split,
+// then attn_plane_tile on its one output tile; p.out is optional here.
+struct WattnQkPvPlaneParams : WattnQkPvParams { AttnPlaneOut po; };
+
+template <bool TWIN, int NT>
+__global__ __launch_bounds__(256) void k_wattn_qkpv_plane(WattnQkPvPlaneParams p) {
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int g = lane >> 5, l31 = lane & 31;
+    const int w = xcd_remap(blockIdx.x, p.nwg) * 4 + wid;
+    if (w >= p.nwaves) return;                        // (wave-uniform; no barrier in this kernel) the flat grid's tail
+    const int z = w / p.tpz, m0 = (w % p.tpz) * 32;   // the row tiles of one z are adjacent: they share its key and value planes
+    const int m = m0 + l31;
+    const bool row_ok = m < p.M;
+    const int head = z % p.H;
+    const int ntiles = (p.N + 31) / 32;               // <= NT (the host chose the instance)
+
+    const char* gQ = (const char*)p.Q + (long)z * p.q_zs + (long)m * p.ldk + g * 16;
+    const char* gK = (const char*)p.Kt + (long)z * p.k_zs + (long)l31 * p.ldk + g * 16;
+    const char* gV = (const char*)p.V + (long)z * p.v_zs + (long)l31 * p.ldv + g * 4;
+    const v4i qf0 = *reinterpret_cast<const v4i*>(gQ), qf1 = *reinterpret_cast<const v4i*>(gQ + 32);
+    // the whole V plane of this z first (nt * 32 + 8 q4 + 4 g + 3 < roundup32(N) <= ldv: inside the row)
+    v4i vf[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) vf[nt][q4] = nt < ntiles ? *reinterpret_cast<const int*>(gV + nt * 32 + 8 * q4) : 0;
+    const float s1 = p.S1[head];
+    // where this query's row of the bias and of the mask begins, in floats (padding rows: the last row's; the host holds both
+    // tensors below 2^30 elements)
+    const int mc = min(m, p.M - 1);
+    const unsigned rowB = (unsigned)((head * p.M + mc) * p.N);
+    const unsigned rowM = (unsigned)((((z / p.H) % p.n_windows) * p.M + mc) * p.N);
+    const bool masked = p.mask != nullptr;
+    const bool vec4 = (p.N & 3) == 0 && (((unsigned long long)p.bias | (unsigned long long)p.mask) & 15) == 0;
+
+    // ---- walk 1: u of every resident tile ------------------------------------------------------------------
+    float u[NT][16];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+#pragma clang fp contract(off)
+        if (nt >= ntiles) break;
+        const int key0 = nt * 32;
+        v16i acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0;
+        const char* ka = gK + (long)key0 * p.ldk;
+        const v4i a0 = *reinterpret_cast<const v4i*>(ka), a1 = *reinterpret_cast<const v4i*>(ka + 32);
+        acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, qf0, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, qf1, acc, 0, 0, 0);
+        // three roundings, no fma, the bias and the mask two separate additions (k_attn_qk<., true>'s block, load for load)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) u[nt][r] = (float)acc[r] * s1;
+        int nb = key0 + 4 * g;                             // the lane's first key of the tile
+#pragma unroll
+        for (int c = 0; c < 16; c += ATTN_WCH) {
+            float bq[ATTN_WCH], mq[ATTN_WCH];
+            if (vec4) {                                    // (uniform) the quad is one 16-byte piece, all of it inside the row or none
+                const unsigned o = (unsigned)min(nb + acc32_row(c), p.N - 4);
+                const v4f b4 = *reinterpret_cast<const v4f*>(p.bias + rowB + o);
+                v4f m4 = {0.0f, 0.0f, 0.0f, 0.0f};
+                if (masked) m4 = *reinterpret_cast<const v4f*>(p.mask + rowM + o);
+#pragma unroll
+                for (int j = 0; j < ATTN_WCH; ++j) { bq[j] = b4[j]; mq[j] = m4[j]; }
+            } else {
+#pragma unroll
+                for (int j = 0; j < ATTN_WCH; ++j) {
+                    const unsigned o = (unsigned)min(nb + acc32_row(c + j), p.N - 1);
+                    bq[j] = p.bias[rowB + o];
+                    mq[j] = masked ? p.mask[rowM + o] : 0.0f;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < ATTN_WCH; ++j) {
+                u[nt][c + j] = u[nt][c + j] + bq[j];
+                if (masked) u[nt][c + j] = u[nt][c + j] + mq[j];
+                asm volatile("" : "+v"(nb), "+v"(u[nt][c + j]));   // (the next quad's loads stay behind this quad's additions)
+            }
+        }
+    }
+    // ---- the row maximum and the row sum, from the registers, in k_attn_qk's order -----------------------------
+    float mx = -__builtin_inff();
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        if (nt >= ntiles) break;
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (nt * 32 + acc32_row(r, g) < p.N) mx = fmaxf(mx, u[nt][r]);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    float part[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) part[r] = 0.0f;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        if (nt >= ntiles) break;
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (nt * 32 + acc32_row(r, g) < p.N) {
+                u[nt][r] = expf(__fsub_rn(u[nt][r], mx));  // (kept for walk 3)
+                part[r] = __fadd_rn(part[r], u[nt][r]);
+            }
+    }
+#pragma unroll
+    for (int w2 = 8; w2 >= 1; w2 >>= 1)
+#pragma unroll
+        for (int r = 0; r < w2; ++r) part[r] = __fadd_rn(part[r], part[r + w2]);
+    const float sum = __fadd_rn(part[0], __shfl_xor(part[0], 32));
+    // ---- walk 3: the probabilities, matmul2's quantiser, matmul2's GEMM on the bytes in registers -------------
+    const float qs = p.qs[p.qs_headwise ? head : 0];
+    PackParams pv1{}, pv2{};
+    pv1.mode = TWIN ? PACK_SOS_HI : PACK_SYM; pv1.lo = p.lo; pv1.hi = p.hi; pv1.qm1 = p.qm1;
+    pv2.mode = PACK_SOS_LO; pv2.qm1 = p.qm1;
+    v16i acc1;
+    [[maybe_unused]] v16i acc2;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc1[r] = 0; if (TWIN) acc2[r] = 0; }
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        if (nt >= ntiles) break;
+        const int key0 = nt * 32;
+        v4i w1 = {0, 0, 0, 0};
+        [[maybe_unused]] v4i w2 = {0, 0, 0, 0};
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+            int x1 = 0, x2 = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int r = q4 * 4 + e;
+                const int n = key0 + e + 8 * q4 + 4 * g;
+                float b1 = 0.0f, b2 = 0.0f;
+                if (row_ok && n < p.N) {
+                    const float pr = __fdiv_rn(u[nt][r], sum);
+                    if (p.probs) p.probs[((long)z * p.M + m) * p.N + n] = pr;
+                    b1 = pack_value(pv1, pr, qs);
+                    if (TWIN) b2 = pack_value(pv2, pr, qs);
+                }
+                x1 |= ((int)b1 & 0xff) << (8 * e);
+                if (TWIN) x2 |= ((int)b2 & 0xff) << (8 * e);
+            }
+            w1[q4] = x1;
+            if (TWIN) w2[q4] = x2;
+        }
+        acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(vf[nt], w1, acc1, 0, 0, 0);
+        if (TWIN) acc2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(vf[nt], w2, acc2, 0, 0, 0);
+    }
+    // ---- epilogue: EPI_FWD's expression, quantised into proj's row plane (attn_plane_tile) -----------------------
+    const float so1 = p.So1[head];
+    const float so2 = TWIN ? p.So2[head] : 0.0f;
+    float* orow = p.out ? p.out + ((long)z * p.M + mc) * p.Dv : nullptr;
+    int8_t* rowp = p.po.plane + ((long)(z / p.H) * p.M + mc) * p.po.Kp;
+    attn_plane_tile<TWIN>(p.po, acc1, TWIN ? acc2 : acc1, so1, so2, p.po.a_iv[0], orow, p.vec4, row_ok, rowp + head * p.Dv, 0, p.Dv, g);
+    if (row_ok && head == p.H - 1) attn_plane_pad(p.po, rowp, p.H * p.Dv, g);
+}
+
+// Where the attention core in front of proj has no plane instance (the two-kernel chain, Dv % 4 != 0): the head merge of its fp32
+// output as a copy, [B][H][M][Dv] -> [B M][H Dv], which proj's forward pass then packs as it packs any x.
+struct HeadMergeParams { const float* src; float* dst; long n; int H, M, Dv; };
+__global__ __launch_bounds__(256) void k_head_merge(HeadMergeParams p) {
+    const int C = p.H * p.Dv;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < p.n; i += (long)gridDim.x * 256) {
+        const long row = i / C;
+        const int col = (int)(i - row * C), h = col / p.Dv, d = col - h * p.Dv;
+        const long b = row / p.M;
+        p.dst[i] = p.src[((b * p.H + h) * p.M + (row - b * p.M)) * p.Dv + d];
+    }
+}
+
 
 // ------------------------------------------------------------------------------------------
 // k_ln_pack: LayerNorm fused with a Linear layer's activation quantiser

@@ -468,7 +468,7 @@ def _attn_matmul_desc(d, A_shape, A_stride, B, side, what, who="attn_quant_forwa
     d.sos, d.init_layerwise, d.reserved = int(bool(side.get("sos", False))), 0, _lib.RESERVED_FORWARD_ONLY
 
 
-def _attn_call(who, q, kT, v, qk, pv, want_probs, desc):
+def _attn_call(who, q, kT, v, qk, pv, want_probs, desc, want_out=True):
     """What attn_quant_forward and window_attn_quant_forward share: the operands on the device, the two p4v_matmul_desc of
     `desc`, the checked interval tensors, the outputs.  Returns (dev, q, kT, v, (qk_A, qk_B, pv_A, pv_B, split), out, probs)."""
     dev = device_of(q, kT, v)
@@ -485,12 +485,60 @@ def _attn_call(who, q, kT, v, qk, pv, want_probs, desc):
     if qk_A.numel() != H or qk_B.numel() != H or pv_B.numel() != H or pv_A.numel() != (1 if sos else H):
         raise ValueError(f"{who}: interval tensors must hold one value per head (the split-of-softmax A: one)")
     sp = flat(pv["split"]) if sos else None
-    out = torch.empty(b, H, M, Dv, dtype=torch.float32, device=dev)
+    out = torch.empty(b, H, M, Dv, dtype=torch.float32, device=dev) if want_out else None     # (proj= without want_core: no fp32 core)
     probs = torch.empty(b, H, M, N, dtype=torch.float32, device=dev) if want_probs else None
     return dev, q, kT, v, (qk_A, qk_B, pv_A, pv_B, sp), out, probs
 
 
-def attn_quant_forward(*, q, kT, v, scale, qk, pv, want_probs=False, want_planes=False, one_kernel=False):
+def _attn_proj_forward(kind, d, dev, tensors, proj, residual, window, out, want_core, want_probs, want_planes):
+    """attn_quant_forward / window_attn_quant_forward with `proj` (`kind`: attn / wattn; p4v_<kind>_proj_quant_forward, DESIGN.md
+    s5.16): `tensors` maps the attention call's members of p4v_attn_proj_tensors, `out` among them as the fp32 core [B][H][M][Dv] or None.
+    Returns proj's output, then -- as asked for -- the core, the probabilities and proj's padded int8 row plane."""
+    lib = _lib.load()
+    who = "attn_quant_forward" if kind == "attn" else "window_attn_quant_forward"
+    (b, H, M), Dv = tensors["q"].shape[:3], tensors["v"].shape[3]
+    w, bias, w_iv, a_iv = _ln_layer(proj, dev)
+    ld = _mlp_layer_desc(b, M, proj)
+    shape = (b, M, w.shape[0])
+    if residual is not None:
+        residual, out = _res_pair(residual, out, tuple(residual.shape), dev, who)
+        if residual.numel() != b * M * w.shape[0]:
+            raise ValueError(f"{who}: residual must hold one row of proj's out_features per query")
+        r = _lib.ResDesc(*((0, 0, 0, 0, 0) if window is None else (1,) + tuple(int(x) for x in window)), 0)
+    else:
+        if window is not None:
+            raise ValueError(f"{who}: window belongs to the fused residual (residual=)")
+        out = torch.empty(shape, dtype=torch.float32, device=dev) if out is None else out
+        if out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != shape or out.device != w.device:
+            raise ValueError(f"{who}: out must be a contiguous fp32 tensor of shape {shape} on the layer's device")
+        r = None
+    core = tensors.pop("out")
+    tensors = dict(tensors, w=w, bias=bias, w_interval=w_iv, a_interval=a_iv, residual=residual, out=out, core=core)
+    refs = (C.byref(d), C.byref(ld), None if r is None else C.byref(r))
+    need = getattr(lib, f"p4v_{kind}_proj_workspace_bytes")(*refs)
+    if need == 0:
+        _lib.check(-2, f"p4v_{kind}_proj_workspace_bytes")
+    ws = workspace(dev, need)
+    rec = _lib.AttnProjTensors(**{k: ptr(t) for k, t in tensors.items()}, ws=ptr(ws), ws_bytes=ws.numel())
+    with torch.cuda.device(dev):
+        rc = getattr(lib, f"p4v_{kind}_proj_quant_forward")(*refs, C.byref(rec), stream_ptr(dev))
+    _lib.check(rc, f"p4v_{kind}_proj_quant_forward")
+    res = (out,) + ((core,) if want_core else ()) + ((tensors["probs"],) if want_probs else ())
+    if want_planes:
+        info = (C.c_uint64 * 5)()
+        _lib.check(lib.p4v_debug_proj_planes(info), "p4v_debug_proj_planes")
+        off, _, rows, cols, _ = (int(x) for x in info)
+        res += (ws[off:off + rows * cols].view(torch.int8).reshape(rows, cols).clone(),)
+    return res[0] if len(res) == 1 else res
+
+
+def _proj_args(who, proj, residual, window, out, want_core):
+    if proj is None and (residual is not None or window is not None or out is not None or want_core):
+        raise ValueError(f"{who}: residual, window, out and want_core belong to proj=")
+
+
+def attn_quant_forward(*, q, kT, v, scale, qk, pv, want_probs=False, want_planes=False, one_kernel=False, proj=None, residual=None,
+                       window=None, out=None, want_core=False):
     """matmul2(softmax(matmul1(q, kT) * scale, -1), v) of the two calibrated MatMuls of an attention block in quant_forward,
     fused (p4v_attn_quant_forward): matmul1's int8 GEMM keeps the scores in registers, takes the softmax and matmul2's A
     quantiser and writes matmul2's int8 plane(s); no fp32 score or probability tensor in between.
@@ -501,17 +549,32 @@ def attn_quant_forward(*, q, kT, v, scale, qk, pv, want_probs=False, want_planes
     plane(s) as the call left them in its workspace (a tuple of one or two [B*H][rows_padded][cols_padded] tensors; for the
     tests).  `one_kernel` (P4V_ATTN_ONE_KERNEL): matmul2's GEMM runs inside the same kernel on the quantised probabilities in
     registers -- no plane exists, so `want_planes` with it is a ValueError; out and probs are the same bits.  Dv > 128 has no
-    instance of that kernel and runs the two-kernel chain."""
-    if one_kernel and want_planes:
+    instance of that kernel and runs the two-kernel chain.
+    `proj` (a Linear dict as mlp_quant_forward's fc1 / fc2: the layer behind the attention core, in_features = H * Dv): the call
+    returns proj's output [B][M][out_features] (p4v_attn_proj_quant_forward).  With `one_kernel` and Dv % 4 == 0 the
+    core's epilogue writes proj's int8 row plane -- no fp32 core output, no transpose copy, no pack of it; otherwise today's chain
+    runs in front of proj: the same bits.  `residual`, `window` and `out` mean what they mean on linear_quant_forward (the add and
+    Swin's window_reverse + roll in proj's GEMM epilogue; `out` is taken without a residual too).  `want_core` also returns the fp32
+    [B][H][M][Dv] values the plane was quantised from, `want_planes` proj's padded int8 row plane.  Returns out, then core, probs and
+    the plane as asked for."""
+    _proj_args("attn_quant_forward", proj, residual, window, out, want_core)
+    if proj is None and one_kernel and want_planes:
         raise ValueError("attn_quant_forward: one_kernel writes no planes of matmul2 (want_planes)")
     d = _lib.AttnDesc()
-    dev, q, kT, v, (qk_A, qk_B, pv_A, pv_B, sp), out, probs = _attn_call("attn_quant_forward", q, kT, v, qk, pv, want_probs, d)
+    res_out = out
+    dev, q, kT, v, (qk_A, qk_B, pv_A, pv_B, sp), out, probs = _attn_call("attn_quant_forward", q, kT, v, qk, pv, want_probs, d,
+                                                                              want_out=proj is None or want_core)
     d.scale, d.reserved = float(scale), (_lib.ATTN_ONE_KERNEL if one_kernel else 0)
+    if proj is not None:
+        tensors = dict(q=q, kT=kT, v=v, qk_A_interval=qk_A, qk_B_interval=qk_B, pv_A_interval=pv_A, pv_B_interval=pv_B, split=sp, out=out,
+                       probs=probs)
+        return _attn_proj_forward("attn", d, dev, tensors, proj, residual, window, res_out, want_core, want_probs, want_planes)
     return _fused_forward("attn", d, (q, kT, v, qk_A, qk_B, pv_A, pv_B, sp, out, probs), dev, (out, probs) if want_probs else (out,),
                           want_planes, z=q.shape[0] * q.shape[1])
 
 
-def window_attn_quant_forward(*, q, kT, v, bias, mask=None, qk, pv, want_probs=False, want_planes=False, one_kernel=False):
+def window_attn_quant_forward(*, q, kT, v, bias, mask=None, qk, pv, want_probs=False, want_planes=False, one_kernel=False, proj=None,
+                              residual=None, window=None, out=None, want_core=False):
     """matmul2(softmax(matmul1(q, kT) + bias (+ mask), -1), v) of the two calibrated MatMuls of a window attention block
     (models.WindowAttention) in quant_forward, fused (p4v_wattn_quant_forward): attn_quant_forward's chain with the window
     arithmetic between matmul1 and the softmax.  `q` arrives ALREADY SCALED, as the module hands it to matmul1.
@@ -520,11 +583,16 @@ def window_attn_quant_forward(*, q, kT, v, bias, mask=None, qk, pv, want_probs=F
     behave as in torch.  Checks, `qk` / `pv`, want_probs, want_planes and the returned values: as attn_quant_forward.
     `one_kernel` (P4V_WATTN_ONE_KERNEL): the whole chain as k_wattn_qkpv, which keeps a window's score rows in registers -- no
     plane exists, so `want_planes` with it is a ValueError; out and probs are the same bits.  More than 160 keys, Dv > 32 or a
-    head_dim above 64 have no instance of that kernel and run the two-kernel chain."""
-    if one_kernel and want_planes:
+    head_dim above 64 have no instance of that kernel and run the two-kernel chain.
+    `proj`, `residual`, `window`, `out`, `want_core` and, with proj, `want_planes`: as attn_quant_forward (p4v_wattn_proj_quant_forward,
+    DESIGN.md s5.16); the result is [B_][N][out_features], with a residual shaped like it."""
+    _proj_args("window_attn_quant_forward", proj, residual, window, out, want_core)
+    if proj is None and one_kernel and want_planes:
         raise ValueError("window_attn_quant_forward: one_kernel writes no planes of matmul2 (want_planes)")
     d = _lib.WattnDesc()
-    dev, q, kT, v, (qk_A, qk_B, pv_A, pv_B, sp), out, probs = _attn_call("window_attn_quant_forward", q, kT, v, qk, pv, want_probs, d)
+    res_out = out
+    dev, q, kT, v, (qk_A, qk_B, pv_A, pv_B, sp), out, probs = _attn_call("window_attn_quant_forward", q, kT, v, qk, pv, want_probs, d,
+                                                                              want_out=proj is None or want_core)
     b, H, M, _ = q.shape
     N = kT.shape[3]
     bias = to_dev(bias, dev).contiguous()
@@ -537,6 +605,10 @@ def window_attn_quant_forward(*, q, kT, v, bias, mask=None, qk, pv, want_probs=F
     d.n_windows, d.has_mask = (1 if mask is None else mask.shape[0]), int(mask is not None)
     if one_kernel:
         d.pv.reserved |= _lib.WATTN_ONE_KERNEL
+    if proj is not None:
+        tensors = dict(q=q, kT=kT, v=v, rel_bias=bias, mask=mask, qk_A_interval=qk_A, qk_B_interval=qk_B, pv_A_interval=pv_A,
+                       pv_B_interval=pv_B, split=sp, out=out, probs=probs)
+        return _attn_proj_forward("wattn", d, dev, tensors, proj, residual, window, res_out, want_core, want_probs, want_planes)
     tensors = dict(q=q, kT=kT, v=v, bias=bias, mask=mask, qk_A_interval=qk_A, qk_B_interval=qk_B, pv_A_interval=pv_A, pv_B_interval=pv_B,
                    split=sp, out=out, probs=probs)
     return _fused_forward("wattn", d, tensors, dev, (out, probs) if want_probs else (out,), want_planes, z=b * H)

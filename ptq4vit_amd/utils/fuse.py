@@ -29,6 +29,12 @@ the two MatMuls.  It shares fuse_attention's saved forward -- the two do not sta
 installed, unfuse_attention undoes either -- and its patched forward decides per call: the qkv-fused path when fuse_attention's
 conditions hold and qkv is calibrated, in quant_forward, on the int8 path, unhooked, n_H = n_a = 1, no post-GELU layer, 3 * C
 wide; otherwise fuse_attention's path where its conditions hold; otherwise the original forward.
+
+`fuse_norm(net, residual=True, proj_plane=True)`: on blocks whose attention container asked for its one-kernel
+core, proj travels into the container's core call (engine.attn_quant_forward / window_attn_quant_forward with proj=, residual=) and
+the core's epilogue writes proj's int8 row plane -- no fp32 attention output, no head-merging transpose copy, no pack of it in
+front of proj.  Without `residual`, or on a container that did not ask for one kernel, the flag changes nothing; the net returns
+the same bits either way.
 """
 import os
 import types
@@ -208,16 +214,20 @@ def _attention_tail(self, qkv_out, args):
     return self.proj_drop(self.proj(_attention_core(self, qkv_out, args)))
 
 
-def _attention_core(self, qkv_out, args):
-    """... up to proj's input [B][N][C]: proj is the caller's"""
+def _attention_core(self, qkv_out, args, proj=None, residual=None):
+    """... up to proj's input [B][N][C]: proj is the caller's.  `proj` (its engine keywords, with the block's `residual`): the engine
+    call runs proj behind the core and returns residual + proj's output (fuse_norm(proj_plane=True))"""
     B, N, C = qkv_out.shape[0], qkv_out.shape[1], qkv_out.shape[2] // 3
     H = self.num_heads
     qkv = qkv_out.reshape(B, N, 3, H, C // H).permute(2, 0, 3, 1, 4)
     if os.environ.get("P4V_QKV_CONTIGUOUS", "1") == "1":
         qkv = qkv.contiguous()
     q, k, v = qkv.unbind(0)
-    out = engine.attn_quant_forward(q=q, kT=k.transpose(-2, -1), v=v, scale=self.scale, qk=args[0], pv=args[1],
-                                    one_kernel=self.__dict__.get(_ONE_KERNEL, False))
+    one = self.__dict__.get(_ONE_KERNEL, False)
+    if proj is not None:
+        return engine.attn_quant_forward(q=q, kT=k.transpose(-2, -1), v=v, scale=self.scale, qk=args[0], pv=args[1], one_kernel=one, proj=proj,
+                                         residual=residual)
+    out = engine.attn_quant_forward(q=q, kT=k.transpose(-2, -1), v=v, scale=self.scale, qk=args[0], pv=args[1], one_kernel=one)
     return out.transpose(1, 2).reshape(B, N, C)
 
 
@@ -326,8 +336,10 @@ def _window_attention_tail(self, qkv_out, args, mask):
     return self.proj_drop(self.proj(_window_attention_core(self, qkv_out, args, mask)))
 
 
-def _window_attention_core(self, qkv_out, args, mask):
-    """... up to proj's input [B_][N][C]: proj is the caller's"""
+def _window_attention_core(self, qkv_out, args, mask, proj=None, residual=None, window=None):
+    """... up to proj's input [B_][N][C]: proj is the caller's.  `proj` (its engine keywords, with the block's `residual` and the
+    `window` map): the engine call runs proj behind the core and returns residual + proj's output in token order
+    (fuse_norm(proj_plane=True))"""
     B_, N, C = qkv_out.shape[0], qkv_out.shape[1], qkv_out.shape[2] // 3
     H = self.num_heads
     qkv = qkv_out.reshape(B_, N, 3, H, C // H).permute(2, 0, 3, 1, 4)
@@ -335,8 +347,12 @@ def _window_attention_core(self, qkv_out, args, mask):
     q = q * self.scale
     n = self.window_size[0] * self.window_size[1]
     bias = self.relative_position_bias_table[self.relative_position_index.view(-1)].view(n, n, -1)
+    one = self.__dict__.get(_WONE_KERNEL, False)
+    if proj is not None:
+        return engine.window_attn_quant_forward(q=q, kT=k.transpose(-2, -1), v=v, bias=bias.permute(2, 0, 1).contiguous(), mask=mask,
+                                                qk=args[0], pv=args[1], one_kernel=one, proj=proj, residual=residual, window=window)
     out = engine.window_attn_quant_forward(q=q, kT=k.transpose(-2, -1), v=v, bias=bias.permute(2, 0, 1).contiguous(), mask=mask,
-                                           qk=args[0], pv=args[1], one_kernel=self.__dict__.get(_WONE_KERNEL, False))
+                                           qk=args[0], pv=args[1], one_kernel=one)
     return out.transpose(1, 2).reshape(B_, N, C)
 
 
@@ -369,6 +385,13 @@ def unfuse_window_attention(net):
 # state runs the side as the block's own forward does.  Its own saved-forward attribute: composes with the other fuse_* in any order.
 _ORIG_NORM = "_p4v_unfused_norm_forward"
 _RESIDUAL = "_p4v_fuse_residual"          # the patched block's choice: proj / fc2 add the residual in their GEMM epilogue
+_PROJ_PLANE = "_p4v_fuse_proj_plane"      # ... and the one-kernel attention core writes proj's int8 row plane
+
+
+def _proj_plane(block):
+    """the patched block hands proj to its container's core call: the flag is set and the container asked for the one-kernel core"""
+    one = _WONE_KERNEL if isinstance(block, models.SwinBlock) else _ONE_KERNEL
+    return block.__dict__.get(_PROJ_PLANE, False) and block.attn.__dict__.get(one, False)
 
 
 def norm_fusable(m):
@@ -485,7 +508,10 @@ def _fused_norm_block_forward(self, x):
     a, p = _norm1_args(self, x), _proj_res_args(self, x)
     if p is not None:
         qkv = engine.linear_quant_forward(x=x, ln=_ln_of(self.norm1), **a[0]) if a is not None else self.attn.qkv(self.norm1(x))
-        x = engine.linear_quant_forward(x=_attention_core(self.attn, qkv, p[1]), residual=x.contiguous(), **p[0])
+        if _proj_plane(self):
+            x = _attention_core(self.attn, qkv, p[1], proj=p[0], residual=x.contiguous())
+        else:
+            x = engine.linear_quant_forward(x=_attention_core(self.attn, qkv, p[1]), residual=x.contiguous(), **p[0])
     elif a is None:
         x = x + self.attn(self.norm1(x))
     else:
@@ -511,6 +537,10 @@ def _fused_norm_swin_block_forward(self, x):
         qkv = qkv.view(-1, ws * ws, qkv.shape[-1])
     if p is not None:
         # proj scatters its rows through window_reverse + roll(+shift) and adds the shortcut: k_lin_res's row map
+        if _proj_plane(self):
+            x = _window_attention_core(self.attn, qkv, p[1], self.attn_mask, proj=p[0], residual=shortcut.contiguous(),
+                                       window=(H, W, ws, self.shift_size))
+            return _mlp_side(self, x)
         core = _window_attention_core(self.attn, qkv, p[1], self.attn_mask)
         x = engine.linear_quant_forward(x=core, residual=shortcut.contiguous(), window=(H, W, ws, self.shift_size), **p[0])
         return _mlp_side(self, x)
@@ -525,7 +555,7 @@ def _fused_norm_swin_block_forward(self, x):
     return _mlp_side(self, x)
 
 
-def fuse_norm(net, residual=False):
+def fuse_norm(net, residual=False, proj_plane=False):
     """Patch the forward of every Block / SwinBlock of `net`; returns their names.  Idempotent.  What a side fuses is decided per
     call (see above): without fuse_mlp / fuse_window_attention / fuse_attention on the block's containers nothing changes.
     `residual`: the patched blocks also let proj and fc2 add the residual -- and, on Swin, proj scatter its rows through
@@ -533,12 +563,17 @@ def fuse_norm(net, residual=False):
     DESIGN.md s5.15), per side and per call, whether or not that side's LayerNorm fused: the attention side where the container
     carries our fused forward and would take it, proj is live on its int8 path with n_H = n_a = 1, unhooked, proj_drop inactive and
     C % 4 == 0; the MLP side where the fused MLP chain would run.  Every other state runs the side as before.  The flag is stored
-    on the blocks (the later call decides) and changes no bit of what the net returns."""
+    on the blocks (the later call decides) and changes no bit of what the net returns.
+    `proj_plane` (with `residual`): where proj adds the residual AND the block's attention container asked for its one-kernel core
+    (fuse_attention / fuse_window_attention with one_kernel=True), proj travels into the container's core call
+    (engine.attn_quant_forward / window_attn_quant_forward with proj=, residual=): the core's epilogue writes proj's
+    int8 row plane -- no fp32 attention output, no transpose copy, no pack of it.  Stored on the blocks like `residual`; the same bits."""
     names = _patch(net, lambda m: isinstance(m, models.SwinBlock), _ORIG_NORM, _fused_norm_swin_block_forward)
     names = sorted(names + _patch(net, lambda m: isinstance(m, models.Block), _ORIG_NORM, _fused_norm_block_forward))
     for name, m in net.named_modules():
         if name in names:
             m.__dict__[_RESIDUAL] = bool(residual)
+            m.__dict__[_PROJ_PLANE] = bool(residual and proj_plane)
     return names
 
 
@@ -546,4 +581,5 @@ def unfuse_norm(net):
     """Undo fuse_norm: every patched block gets its original forward back; returns their names.  Idempotent."""
     for m in net.modules():
         m.__dict__.pop(_RESIDUAL, None)
+        m.__dict__.pop(_PROJ_PLANE, None)
     return _unfuse(net, _ORIG_NORM)

@@ -18,6 +18,8 @@ qkv sweep, the permute copy and the three k_pack1 of q, k^T and v), on top of th
 matmul2's sweep), on top of the fused MLPs with --fused; compared with fused_qkv.  On a Swin net the same variant is
 fuse_window_attention(one_kernel=True) (k_wattn_qkpv in place of the window instances of k_attn_qk and matmul2's sweep), compared
 with fused_attn: --fused --fused-attn --one-kernel alternates MLPs + windows as two kernels with MLPs + windows as one.
+--proj-plane (with --one-kernel --fuse-norm --fuse-residual): fuse_norm(net, residual=True, proj_plane=True) next to fused_residual in
+the same alternation -- the one-kernel attention cores write proj's int8 row plane; the result also holds the spread of the base.
 """
 import argparse
 import hashlib
@@ -109,6 +111,9 @@ def main():
                          "and the fused MLPs), next to the same net without it (norm_base)")
     ap.add_argument("--fuse-residual", action="store_true",
                     help="with --fuse-norm: also time fuse_norm(net, residual=True) -- proj / fc2 add the residual in their GEMM epilogue -- next to fused_norm")
+    ap.add_argument("--proj-plane", action="store_true",
+                    help="with --fuse-residual and --one-kernel: also time fuse_norm(net, residual=True, proj_plane=True) -- the one-kernel attention cores "
+                         "write proj's int8 row plane -- next to fused_residual")
     ap.add_argument("--json", default=None, help="write the result to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -162,6 +167,8 @@ def main():
             variants += [("norm_base", a.fused, base), ("fused_norm", a.fused, ("norm", base))]
             if a.fuse_residual:
                 variants.append(("fused_residual", a.fused, ("res", base)))
+                if a.proj_plane:
+                    variants.append(("fused_proj_plane", a.fused, ("plane", base)))
 
         def setup(mlp, attn):
             fuse.unfuse_norm(net)
@@ -175,7 +182,7 @@ def main():
             if attn == "attn1":
                 fuse_attn = lambda n: fuse.fuse_attention(n, one_kernel=True)
             if norm:
-                fuse.fuse_norm(net, residual=norm == "res")
+                fuse.fuse_norm(net, residual=norm in ("res", "plane"), proj_plane=norm == "plane")
             return (len(fuse.fuse_mlp(net)) if mlp else 0,
                     len(fuse_attn(net)) + len(fuse.fuse_window_attention(net, one_kernel=attn in ("qkv1", "attn1"))) if attn else 0)
 
@@ -202,10 +209,13 @@ def main():
                 print(f"  one-kernel attention core ({n_attn}{' + MLPs' if a.fused else ''}) {t_v * 1e3:.2f} ms: x{med[base_key] / t_v:.3f} "
                       f"over {base_key} ({(med[base_key] - t_v) * 1e3:+.3f} ms), x{t_u / t_v:.3f} over unfused; logit rel diff vs unfused {rel:.3e}")
                 res.update({base_key + "_over_fused_qkv_one": med[base_key] / t_v, base_key + "_minus_fused_qkv_one_ms": (med[base_key] - t_v) * 1e3})
-            elif key in ("norm_base", "fused_norm", "fused_residual"):
-                base_key = "fused_norm" if key == "fused_residual" else "norm_base" if key == "fused_norm" else "unfused"
+            elif key in ("norm_base", "fused_norm", "fused_residual", "fused_proj_plane"):
+                base_key = {"fused_proj_plane": "fused_residual", "fused_residual": "fused_norm", "fused_norm": "norm_base"}.get(key, "unfused")
                 print(f"  {key} ({n_attn} attention containers{' + MLPs' if a.fused else ''}) {t_v * 1e3:.2f} ms: x{med[base_key] / t_v:.3f} over {base_key} "
                       f"({(med[base_key] - t_v) * 1e3:+.3f} ms); logit rel diff vs unfused {rel:.3e}")
+                if key == "fused_proj_plane":
+                    res.update({"fused_residual_over_fused_proj_plane": med[base_key] / t_v, "fused_residual_minus_fused_proj_plane_ms": (med[base_key] - t_v) * 1e3,
+                                "fused_residual_spread_ms": (max(ts[base_key]) - min(ts[base_key])) * 1e3})
                 if key == "fused_residual":
                     res.update({"fused_norm_over_fused_residual": med[base_key] / t_v, "fused_norm_minus_fused_residual_ms": (med[base_key] - t_v) * 1e3})
                 if key == "fused_norm":
